@@ -8,7 +8,10 @@ One "step" = one pass of the hot path over one batch of synthetic input = ONE IM
 hint block + cross-attention K/V precompute (once per image), 20 DDIM steps of ControlNet + ControlledUnet on the
 fused CFG pair (N=2) with the CFG/DDIM update, VAE decode and the uint8 post-process -- all on the GPU, inputs
 resident in HBM.  Images are sharded over ranks by image index (no data-path collective); the final latents are
-gathered once with RCCL inside the timed region.  Rank 0 prints ONE JSON line.
+gathered once with RCCL inside the timed region.  Rank 0 prints ONE JSON line; `ms_per_step` is the wall time of one timed step.
+
+--dump-outputs DIR writes what the last timed step returned on rank 0 -- the final latents (latent.npy) and the uint8 image
+(image.npy) -- as float32 .npy files; the inputs (weights, x_T, hint, contexts) are seeded, so two builds can be compared file by file.
 
 Extra objects on that line:
   roofline     -- the conv / GEMM kernel family of one profiled image (the group holding most of the device time): algorithmic FLOPs
@@ -63,7 +66,27 @@ def parse():
                     help="draw the synthetic weights with the device generator (seconds faster to start; NOT the parity-tested weights, "
                          "so the reference-golden check of the output is skipped)")
     ap.add_argument("--dump-profile", default="", help="write the full per-(kernel, shape) table of the profiled image to this JSON file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (final latents, uint8 image) as DIR/<name>.npy "
+                         "(float32, rank 0; at most 64 MB in all, a fixed seeded sample of a larger array)")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> host tensor.  Each file gets an equal share of DUMP_BUDGET; an array larger than its share is replaced by a
+    sample of its flattened elements at indices drawn with a fixed seed (sorted), the same for every run with the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_BUDGET - 4096) // max(len(arrays), 1)      # 4 KiB left for the .npy headers
+    for name, t in arrays.items():
+        x = t.detach().cpu().float().numpy()
+        if x.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(x, dtype=np.float32))
 
 
 def cpu_baseline(res, ddim_steps, scale):
@@ -235,6 +258,8 @@ def main():
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:      # outside the timed region: what a caller of the timed path received in its last step
+        dump_outputs(a.dump_outputs, {"latent": z, "image": img})
     per_rank = None
     if dist:
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
