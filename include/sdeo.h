@@ -74,6 +74,17 @@ int sdeo_conv2d_nhwc_f16(void* y, const void* x, const void* w_krsc, const float
                          int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, int act, float scale,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* sdeo_conv2d_nhwc_f16 with explicit zero padding: pad_before rows / columns at the top / left, pad_after at the bottom / right
+ * (each < ksize; pad_before = pad_after = ksize / 2 is exactly sdeo_conv2d_nhwc_f16, same plan, same bits).  ho = (h' + pad_before +
+ * pad_after - ksize) / stride + 1 with h' = h or 2h (upsample2x), likewise wo.  The VAE encoder's Downsample (F.pad(x, (0,1,0,1)) then
+ * conv3x3 stride 2 pad 0, ldm/modules/diffusionmodules/model.py:78-86) is ksize 3, stride 2, pad_before 0, pad_after 1.  1x1 filters take
+ * symmetric padding only.  workspace: >= sdeo_conv2d_pad_workspace_bytes(...) bytes. */
+size_t sdeo_conv2d_pad_workspace_bytes(int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, int pad_before,
+                                       int pad_after);
+int sdeo_conv2d_pad_nhwc_f16(void* y, const void* x, const void* w_krsc, const float* bias, const float* bias2, const void* res,
+                             int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, int pad_before, int pad_after,
+                             int act, float scale, void* workspace, size_t workspace_bytes, void* stream);
+
 /* GEMM  y[m][n] = act(x[m][k] . w[n][k]^T + bias) * scale + res   (both operands K-contiguous; nn.Linear layout).
  * out_f32=1 writes fp32.  bias_per_row=1 indexes bias by m.  ld* in elements. */
 size_t sdeo_gemm_workspace_bytes(int m, int n, int k);
@@ -242,6 +253,27 @@ int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float
  * z [n][4][h][w] fp32 NCHW -> images [n][3][8h][8w] fp32 NCHW in [-1,1]; images_u8 (optional, may be NULL)
  * additionally receives the NHWC uint8 post-process of canny2image_torch.py:68. n must be <= configured n. */
 int sdeo_vae_decode(sdeo_handle h, const float* z, int n, float* images, uint8_t* images_u8, void* stream);
+
+/* VAE encoder (opt-in).  Registers "first_stage_model.encoder.*" (the Encoder of ldm/modules/diffusionmodules/model.py:452-545 built
+ * with the VAE fields of sdeo_config, attn_resolutions = [], double_z = True: conv_out has 2 * vae_z_channels outputs, vae_out_ch is
+ * the image channel count) and "first_stage_model.quant_conv" as expected weights, and makes sdeo_configure build the encode program
+ * for images of 8h x 8w.  Call it once, after sdeo_create and before the first sdeo_load_weight (the weight slab is sized at
+ * registration).  The encoder stays fp16 whatever sdeo_set_weight_precision says.  Without this call nothing about the handle changes:
+ * the expected weights, the device bytes and the programs are those of a handle without an encoder. */
+int sdeo_enable_vae_encoder(sdeo_handle h);
+/* encode_first_stage + get_first_stage_encoding (upstream AutoencoderKL.encode / LatentDiffusion.get_first_stage_encoding; both absent
+ * from the reference tree): moments = quant_conv(Encoder(x)), DiagonalGaussianDistribution (ldm/modules/distributions/distributions.py:
+ * 24-35), z = scale_factor * (mean + exp(0.5 clamp(logvar, -30, 20)) * noise).
+ *   images    fp32 NCHW [n][C][8h][8w] in [-1,1], OR
+ *   images_u8 uint8 NHWC [n][8h][8w][C] (exactly one of the two non-NULL), mapped like upstream load_img: 2 * (u / 255) - 1 in fp32;
+ *             both are rounded once to fp16, so a u8 image and its fp32 mapping give identical results;
+ *   n <= configured n; C = vae_out_ch;
+ *   noise     fp32 [n][zc][h][w] or NULL (= the posterior mode: z = scale_factor * mean); zc = vae_z_channels;
+ *   z         fp32 [n][zc][h][w];
+ *   moments   optional fp32 [n][2zc][h][w]: quant_conv output (mean, then logvar) before the clamp.
+ * Images are encoded one at a time (results do not depend on n).  Fails when the handle has no encoder.  Capturable. */
+int sdeo_vae_encode(sdeo_handle h, const float* images, const uint8_t* images_u8, int n, const float* noise, float* z, float* moments,
+                    void* stream);
 
 /* bytes of device memory the handle owns (weights + arena) */
 size_t sdeo_device_bytes(sdeo_handle h);

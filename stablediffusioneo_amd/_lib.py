@@ -67,7 +67,7 @@ def load(path: str = LIB_PATH):
         raise SdeoError(f"{path} reports ABI version {lib.sdeo_version()}, include/sdeo.h declares {want}: rebuild the library "
                         f"(operand semantics changed between versions)")
     lib.sdeo_last_error.restype = C.c_char_p
-    for name in ("sdeo_groupnorm_workspace_bytes", "sdeo_conv2d_workspace_bytes", "sdeo_gemm_workspace_bytes",
+    for name in ("sdeo_groupnorm_workspace_bytes", "sdeo_conv2d_workspace_bytes", "sdeo_conv2d_pad_workspace_bytes", "sdeo_gemm_workspace_bytes",
                  "sdeo_device_bytes", "sdeo_clip_device_bytes"):
         getattr(lib, name).restype = C.c_size_t
     lib.sdeo_device_bytes.argtypes = [C.c_void_p]

@@ -40,12 +40,12 @@ def _default_canny():
 
 class hackathon():
 
-    def initialize(self, weights="synthetic:0", config="sd15", apply_canny=None, text_encoder=None):
+    def initialize(self, weights="synthetic:0", config="sd15", apply_canny=None, text_encoder=None, vae_encoder=False):
         """text_encoder: None = `synthetic_text_encoder` (seeded stand-in contexts); "clip:<tokenizer dir>" = the
         FrozenCLIPEmbedder mirror on the HIP path (weights from the same source as the UNet's: synthetic seed or the
         checkpoint's `cond_stage_model.transformer.text_model.*`); bare "clip" is accepted only with synthetic weights (the
         tokenizer is then the crc32 stand-in, which is meaningless next to real weights); or any callable(prompts) ->
-        (B, 77, 768) tensor."""
+        (B, 77, 768) tensor.  vae_encoder=True also builds the VAE encoder, which `process(init_image=...)` (img2img) needs."""
         self.apply_canny = apply_canny or _default_canny()
         if isinstance(text_encoder, str) and text_encoder.split(":")[0] == "clip":
             from . import spec as S
@@ -55,7 +55,7 @@ class hackathon():
             text_encoder = FrozenCLIPEmbedder(version=tok_dir, config=S.CLIP_TINY if config == "tiny" else S.CLIP_SD15,
                                               allow_hash_tokenizer=synthetic and tok_dir is None)
         self.text_encoder = text_encoder or synthetic_text_encoder
-        self.model = create_model(config, cond_stage_model=self.text_encoder)
+        self.model = create_model(config, cond_stage_model=self.text_encoder, vae_encoder=vae_encoder)
         if isinstance(weights, str) and weights.startswith("synthetic"):
             seed = int(weights.split(":")[1]) if ":" in weights else 0
             self.model.rt.load_synthetic(seed)
@@ -70,7 +70,10 @@ class hackathon():
         return self
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, ddim_steps, guess_mode,
-                strength, scale, seed, eta, low_threshold, high_threshold, x_T=None):
+                strength, scale, seed, eta, low_threshold, high_threshold, x_T=None, init_image=None, denoise_strength=0.75):
+        """init_image (HxWx3 uint8, optional): img2img with upstream `scripts/img2img.py` semantics -- the image is resized like the
+        input, encoded (posterior sample), noised to t_enc = int(denoise_strength * ddim_steps) by stochastic_encode and denoised from
+        there by DDIMSampler.decode; the Canny hint still comes from `input_image`.  Needs initialize(..., vae_encoder=True)."""
         with torch.no_grad():
             img = resize_image(HWC3(input_image), image_resolution)
             H, W, C = img.shape
@@ -97,9 +100,30 @@ class hackathon():
             # `canny2image_torch.py:54`: guess-mode scales 0.825**(12-i)
             self.model.control_scales = ([strength * (0.825 ** float(12 - i)) for i in range(13)] if guess_mode
                                          else ([strength] * 13))
-            samples, intermediates = self.ddim_sampler.sample(ddim_steps, num_samples, shape, cond, verbose=False, eta=eta,
-                                                              unconditional_guidance_scale=scale,
-                                                              unconditional_conditioning=un_cond, x_T=x_T)
+            if init_image is None:
+                samples, intermediates = self.ddim_sampler.sample(ddim_steps, num_samples, shape, cond, verbose=False, eta=eta,
+                                                                  unconditional_guidance_scale=scale,
+                                                                  unconditional_conditioning=un_cond, x_T=x_T)
+            else:
+                samples = self._img2img(init_image, image_resolution, (H, W), num_samples, cond, un_cond, ddim_steps, eta, scale,
+                                        denoise_strength)
             x_samples = self.model.decode_first_stage_uint8(samples).cpu().numpy()
             results = [x_samples[i] for i in range(num_samples)]
         return results
+
+    def _img2img(self, init_image, image_resolution, hw, num_samples, cond, un_cond, ddim_steps, eta, scale, denoise_strength):
+        """upstream `scripts/img2img.py`: init_latent = get_first_stage_encoding(encode_first_stage(init_image)); t_enc steps of
+        stochastic_encode; DDIMSampler.decode from t_enc (the per-step p_sample_ddim path)."""
+        t_enc = int(denoise_strength * ddim_steps)
+        if not (denoise_strength >= 0.0 and t_enc < ddim_steps):
+            raise ValueError(f"denoise_strength {denoise_strength}: t_enc = int(strength * steps) must lie in [0, {ddim_steps})")
+        init = resize_image(HWC3(init_image), image_resolution)
+        if init.shape[:2] != tuple(hw):
+            raise ValueError(f"init_image resizes to {init.shape[:2]}, the input image to {tuple(hw)}: give them the same aspect ratio")
+        device = self.model.device
+        x = torch.from_numpy(np.ascontiguousarray(init)).to(device).float() / 255.0 * 2.0 - 1.0
+        x = x.permute(2, 0, 1).unsqueeze(0).expand(num_samples, -1, -1, -1).contiguous()
+        z0 = self.model.get_first_stage_encoding(self.model.encode_first_stage(x))
+        self.ddim_sampler.make_schedule(ddim_num_steps=ddim_steps, ddim_eta=eta, verbose=False)
+        z_enc = self.ddim_sampler.stochastic_encode(z0, torch.tensor([t_enc] * num_samples, device=device))
+        return self.ddim_sampler.decode(z_enc, cond, t_enc, unconditional_guidance_scale=scale, unconditional_conditioning=un_cond)

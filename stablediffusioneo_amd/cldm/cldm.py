@@ -53,8 +53,33 @@ class ControlledUnetModel:
     __call__ = forward
 
 
+class DiagonalGaussianDistribution:
+    """`ldm/modules/distributions/distributions.py:24-35,61-62` over the moments the HIP encoder returned: mean / logvar are the two
+    halves of quant_conv's output, logvar clamped to [-30, 20].  `sample(noise)` takes the noise from the caller (None draws it with
+    torch.randn, like the reference).  The library's own z (`SdeoRuntime.vae_encode`) applies the same formula on the device."""
+
+    def __init__(self, parameters, deterministic=False):
+        self.parameters = parameters
+        self.mean, self.logvar = torch.chunk(parameters, 2, dim=1)
+        self.logvar = torch.clamp(self.logvar, -30.0, 20.0)
+        self.deterministic = deterministic
+        self.std = torch.exp(0.5 * self.logvar)
+        self.var = torch.exp(self.logvar)
+        if self.deterministic:
+            self.var = self.std = torch.zeros_like(self.mean)
+
+    def sample(self, noise=None):
+        if noise is None:
+            noise = torch.randn(self.mean.shape).to(device=self.parameters.device)
+        return self.mean + self.std * noise.to(device=self.parameters.device, dtype=self.mean.dtype)
+
+    def mode(self):
+        return self.mean
+
+
 class AutoencoderKLDecoder:
-    """decode side of `ldm.models.autoencoder.AutoencoderKL` (absent from the reference tree)."""
+    """`ldm.models.autoencoder.AutoencoderKL` (absent from the reference tree): decode always, encode when the runtime was built with
+    the VAE encoder (create_model(..., vae_encoder=True))."""
 
     def __init__(self, runtime: SdeoRuntime):
         self.rt = runtime
@@ -62,6 +87,16 @@ class AutoencoderKLDecoder:
     def decode(self, z):
         """z is ALREADY divided by scale_factor (upstream AutoencoderKL.decode contract)."""
         return self.rt.vae_decode(z * self.rt.vcfg.scale_factor)
+
+    def encode(self, x):
+        """upstream AutoencoderKL.encode: x (b,3,8h,8w) in [-1,1] -> DiagonalGaussianDistribution(quant_conv(encoder(x)))."""
+        if not self.rt.vae_encoder:
+            raise RuntimeError("first_stage_model.encode: the runtime was built without the VAE encoder "
+                               "(create_model(..., vae_encoder=True) / SdeoRuntime(..., vae_encoder=True))")
+        x = x.to(device=self.rt.device, dtype=torch.float32)
+        self.rt.configure(max(self.rt.n, x.shape[0]), x.shape[2] // 8, x.shape[3] // 8)
+        _, moments = self.rt.vae_encode(images=x, want_moments=True)
+        return DiagonalGaussianDistribution(moments)
 
 
 class ControlLDM:
@@ -142,6 +177,21 @@ class ControlLDM:
             return self.rt.apply_model(x_noisy, None, t, cond_txt, None, self.only_mid_control, flags & CONTEXT_CACHED, out)
         hint = torch.cat(cond["c_concat"], 1)
         return self.rt.apply_model(x_noisy, hint, t, cond_txt, self.control_scales, self.only_mid_control, flags, out)
+
+    def encode_first_stage(self, x):
+        """upstream LatentDiffusion.encode_first_stage: first_stage_model.encode(x) (a DiagonalGaussianDistribution)."""
+        return self.first_stage_model.encode(x)
+
+    def get_first_stage_encoding(self, encoder_posterior, noise=None):
+        """upstream LatentDiffusion.get_first_stage_encoding: scale_factor * encoder_posterior.sample() (a tensor is taken as is).
+        `noise` fixes the posterior sample (None: torch.randn, as upstream)."""
+        if isinstance(encoder_posterior, DiagonalGaussianDistribution):
+            z = encoder_posterior.sample(noise)
+        elif isinstance(encoder_posterior, torch.Tensor):
+            z = encoder_posterior
+        else:
+            raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
+        return self.scale_factor * z
 
     def decode_first_stage(self, z):
         """`canny2image_torch.py:63-67`: z = 1/scale_factor * z; first_stage_model.decode(z)."""

@@ -66,15 +66,21 @@ static void take_fp8(ConvGemm& p, const Fp8Arm& a) {
   p.w = (const f16*)a.q; p.wscale = a.s; p.ldw = p.K;
 }
 
-static int fill_conv(ConvGemm& p, int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x) {
+// pad_before / pad_after < 0: ksize / 2 (the symmetric "same" padding of every conv of the networks)
+static int fill_conv(ConvGemm& p, int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, int pad_before = -1,
+                     int pad_after = -1) {
   SDEO_CHECK(ksize == 1 || ksize == 3, "conv2d: ksize %d unsupported", ksize);
   SDEO_CHECK(stride == 1 || stride == 2, "conv2d: stride %d unsupported", stride);
-  const int pad = ksize / 2;
+  const int pad = pad_before < 0 ? ksize / 2 : pad_before;
+  const int pa = pad_after < 0 ? ksize / 2 : pad_after;
+  SDEO_CHECK(pad < ksize && pa < ksize, "conv2d: padding (%d, %d) out of range for ksize %d", pad, pa, ksize);
   const int hv = upsample2x ? 2 * h : h, wv = upsample2x ? 2 * w : w;
   p.B = n; p.Hi = h; p.Wi = w; p.Cin = cin;
   p.R = p.S = ksize; p.stride = stride; p.pad = pad; p.ups = upsample2x;
-  p.Ho = (hv + 2 * pad - ksize) / stride + 1;
-  p.Wo = (wv + 2 * pad - ksize) / stride + 1;
+  if (pa != pad) p.pad_after = pa;
+  p.Ho = (hv + pad + pa - ksize) / stride + 1;
+  p.Wo = (wv + pad + pa - ksize) / stride + 1;
+  SDEO_CHECK(p.Ho >= 1 && p.Wo >= 1, "conv2d: empty output (%dx%d, padding %d / %d)", h, w, pad, pa);
   p.M = n * p.Ho * p.Wo; p.N = cout; p.K = ksize * ksize * cin;
   p.ldx = cin; p.ldw = p.K; p.ldy = cout; p.ldres = cout; p.ld_bias2 = cout;
   return 0;
@@ -124,6 +130,27 @@ int sdeo_conv2d_nhwc_f16(void* y, const void* x, const void* w_krsc, const float
   const Fp8Arm arm = disarm_fp8();
   ConvGemm p;
   if (int rc = fill_conv(p, n, h, w, cin, cout, ksize, stride, upsample2x)) return rc;
+  p.x = (const f16*)x; p.w = (const f16*)w_krsc; p.y = (f16*)y; p.bias = bias; p.bias2 = bias2; p.res = (const f16*)res;
+  p.act = act; p.scale = scale; p.workspace = (float*)workspace; p.workspace_bytes = workspace_bytes;
+  take_fp8(p, arm);
+  return conv_gemm(p, S(stream));
+}
+
+// sdeo_conv2d_nhwc_f16 with explicit padding: pad_before rows / columns of zeros at the top / left, pad_after at the bottom / right
+size_t sdeo_conv2d_pad_workspace_bytes(int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, int pad_before,
+                                       int pad_after) {
+  ConvGemm p;
+  if (fill_conv(p, n, h, w, cin, cout, ksize, stride, upsample2x, pad_before, pad_after)) return 0;
+  return conv_gemm_workspace_bytes(p);
+}
+
+int sdeo_conv2d_pad_nhwc_f16(void* y, const void* x, const void* w_krsc, const float* bias, const float* bias2, const void* res,
+                             int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, int pad_before, int pad_after,
+                             int act, float scale, void* workspace, size_t workspace_bytes, void* stream) {
+  const Fp8Arm arm = disarm_fp8();
+  SDEO_CHECK(pad_before >= 0 && pad_after >= 0, "conv2d_pad: negative padding (%d, %d)", pad_before, pad_after);
+  ConvGemm p;
+  if (int rc = fill_conv(p, n, h, w, cin, cout, ksize, stride, upsample2x, pad_before, pad_after)) return rc;
   p.x = (const f16*)x; p.w = (const f16*)w_krsc; p.y = (f16*)y; p.bias = bias; p.bias2 = bias2; p.res = (const f16*)res;
   p.act = act; p.scale = scale; p.workspace = (float*)workspace; p.workspace_bytes = workspace_bytes;
   take_fp8(p, arm);

@@ -817,7 +817,7 @@ static bool is_fast(const ConvGemm& p) { return p.Cin % 64 == 0; }
 static bool halo_ok(const ConvGemm& p, const TileCfg& c) {
   if (c.kind != TK_HALO) return false;
   const HaloCfg& h = kHaloCfgs[c.stages];
-  return p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 && !p.ups && p.Cin % 64 == 0 && p.act != 3 && !p.bias_per_row &&
+  return p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 && conv_pad_after(p) == 1 && !p.ups && p.Cin % 64 == 0 && p.act != 3 && !p.bias_per_row &&
          p.Hi % h.ph == 0 && p.Wi % h.pw == 0 && p.Ho == p.Hi && p.Wo == p.Wi;
 }
 // tiles and K-steps of a plan: a halo tile is a patch of one image and steps through Cin in 64-channel slices (9 taps each)
@@ -1025,9 +1025,15 @@ static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
              "conv_gemm: operands must be 16-byte aligned");
   {
     const int Hv = p.ups ? 2 * p.Hi : p.Hi, Wv = p.ups ? 2 * p.Wi : p.Wi;
-    SDEO_CHECK((Hv + 2 * p.pad - p.R) / p.stride + 1 == p.Ho && (Wv + 2 * p.pad - p.S) / p.stride + 1 == p.Wo,
-               "conv_gemm: geometry mismatch Hi=%d Wi=%d -> Ho=%d Wo=%d (R=%d S=%d stride=%d pad=%d ups=%d)", p.Hi, p.Wi,
-               p.Ho, p.Wo, p.R, p.S, p.stride, p.pad, p.ups);
+    // pad = top / left, pad_after = bottom / right: the kernels place tap (0, 0) of output (ho, wo) at (ho stride - pad, wo stride - pad)
+    // and read every tap outside [0, Hv) x [0, Wv) as zero, so the bottom / right padding only enters through Ho / Wo
+    const int pa = conv_pad_after(p);
+    SDEO_CHECK(p.pad >= 0 && pa >= 0 && p.pad < p.R && pa < p.R && p.pad < p.S && pa < p.S,
+               "conv_gemm: padding (%d, %d) out of range for a %dx%d filter", p.pad, pa, p.R, p.S);
+    SDEO_CHECK(pa == p.pad || p.K != p.Cin, "conv_gemm: asymmetric padding needs a filter larger than 1x1");
+    SDEO_CHECK((Hv + p.pad + pa - p.R) / p.stride + 1 == p.Ho && (Wv + p.pad + pa - p.S) / p.stride + 1 == p.Wo,
+               "conv_gemm: geometry mismatch Hi=%d Wi=%d -> Ho=%d Wo=%d (R=%d S=%d stride=%d pad=%d/%d ups=%d)", p.Hi, p.Wi,
+               p.Ho, p.Wo, p.R, p.S, p.stride, p.pad, pa, p.ups);
   }
   if (p.act == 3)
     SDEO_CHECK(p.N % 32 == 0 && p.y && !p.y32 && !p.res && !p.bias2 && !p.bias_per_row && p.ldy >= p.N / 2 && p.scale == 1.0f,

@@ -25,6 +25,8 @@ struct ConvGemm {
   int M = 0, N = 0, K = 0;
   int B = 1, Hi = 1, Wi = 1, Cin = 0;  // source tensor geometry (Cin = channels consumed per tap)
   int Ho = 1, Wo = 1, R = 1, S = 1, stride = 1, pad = 0;
+  int pad_after = -1;          // zero padding at the bottom / right (`pad` is the top / left one); -1: = pad.  The VAE encoder's
+                               // Downsample is F.pad(x, (0,1,0,1)) + conv3x3 stride 2 pad 0 = pad 0, pad_after 1 (model.py:78-86)
   int ups = 0;                 // 1: the conv sees the source nearest-upsampled x2 (Upsample folded in)
   int ldx = 0, ldw = 0, ldy = 0, ldres = 0, ld_bias2 = 0;
   int act = 0;                 // 0 none, 1 SiLU, 2 quick-GELU  v * sigmoid(1.702 v)  (CLIP MLP),
@@ -64,6 +66,7 @@ struct ConvGemm {
   int mx_ldsx = 0, mx_ldsw = 0;
 };
 int conv_gemm(const ConvGemm& p, hipStream_t stream);
+inline int conv_pad_after(const ConvGemm& p) { return p.pad_after < 0 ? p.pad : p.pad_after; }
 // M tiles per image of the plan chosen for p when its epilogue can emit GroupNorm partials for groups of cpg channels, else 0
 int conv_gemm_gn_slots(const ConvGemm& p, int cpg);
 // whether the plan chosen for p can apply a GroupNorm(32) of its input itself (ConvGemm::gn_in): a halo-reuse 3x3 kernel with LDS left
@@ -154,6 +157,13 @@ int nchw_f32_to_nhwc_f16(f16* y, int ldy, const float* x, int B, int C, int HW, 
 // context [B][T][C] fp32 -> fp16 [B][Tpad][C], rows >= T zero
 int pad_rows_f32_to_f16(f16* y, const float* x, int B, int T, int Tpad, int C, hipStream_t stream);
 int nhwc_f16_to_nchw_f32(float* y, const f16* x, int ldx, int B, int C, int HW, float scale, hipStream_t stream);
+// VAE encoder intake: images fp32 NCHW [B][C][HW] in [-1,1] OR (x == nullptr) uint8 HWC [B][HW][C] mapped as 2 * (u / 255.0f) - 1 in
+// fp32 -> fp16 NHWC [B][HW][8] (C <= 8 channels, the stored ones above C zero)
+int image_to_nhwc8_f16(f16* y, const float* x, const uint8_t* x_u8, int B, int C, int HW, hipStream_t stream);
+// DiagonalGaussianDistribution of the VAE encoder's moments (distributions.py:24-35 + get_first_stage_encoding) on one image:
+// m fp16 NHWC [HW][ldm], channels [0, zc) = mean, [zc, 2zc) = logvar.  moments fp32 NCHW [2zc][HW] (may be null) = m as stored;
+// z fp32 NCHW [zc][HW] = scale * (mean + exp(0.5 clamp(logvar, -30, 20)) * noise), or scale * mean when noise is null
+int vae_posterior(float* z, float* moments, const f16* m, int ldm, const float* noise, int zc, int HW, float scale, hipStream_t stream);
 int nhwc_f16_to_nhwc_u8(uint8_t* y, const f16* x, int ldx, int64_t pixels, int C, hipStream_t stream);
 // weights: fp32 [O][I][R][S] -> fp16 [O][R][S][Ipad]
 int oihw_f32_to_ohwi_f16(f16* y, const float* w, int O, int I, int R, int S, int Ipad, hipStream_t stream);

@@ -265,6 +265,11 @@ struct sdeo_handle_s {
   float* out_eps = nullptr;
   float* out_ctrl[13] = {nullptr};
   float* vae_in = nullptr; float* vae_out = nullptr; uint8_t* vae_u8 = nullptr;
+  // VAE encoder (sdeo_enable_vae_encoder): boundary buffers of one image, and what the next run of p_vae_enc reads (set by
+  // sdeo_vae_encode, read at launch): the uint8 image instead of the fp32 one, the noise instead of the posterior mode
+  bool vae_encoder = false;
+  float* enc_img = nullptr; uint8_t* enc_img_u8 = nullptr; float* enc_noise = nullptr; float* enc_z = nullptr; float* enc_moments = nullptr;
+  int enc_from_u8 = 0, enc_with_noise = 0;
   std::vector<void*> extra_allocs;
   // persistent activations
   T ctrl[13];            // fp16 NHWC controls (ControlNet output / UNet input), unscaled
@@ -286,7 +291,7 @@ struct sdeo_handle_s {
   T x0;                  // fp16 NHWC copy of the latent input, shared by ControlNet and UNet (p_x0 writes it from in_x)
   T eps16;               // the UNet's eps before the NCHW fp32 export (p_eps_export), read directly by sdeo_ddim_step
   // programs
-  Program p_hint, p_ctx_cn, p_ctx_unet, p_cn, p_cn_export, p_ctrl_import, p_unet_enc, p_unet_dec, p_unet_noctrl, p_vae;
+  Program p_hint, p_ctx_cn, p_ctx_unet, p_cn, p_cn_export, p_ctrl_import, p_unet_enc, p_unet_dec, p_unet_noctrl, p_vae, p_vae_enc;
   Program p_temb[2], p_temb_tab, p_x0, p_eps_export, p_unet_dec_fused;
   std::vector<size_t> ctrl_elems;
   size_t device_bytes = 0;
@@ -511,6 +516,35 @@ static void build_registry(Engine* e) {
   e->wslab_bytes = align_up(r.size, 256);
 }
 
+// VAE encoder (`model.py:452-545`, attn_resolutions = [], double_z) + quant_conv, appended behind everything build_registry placed
+// (sdeo_enable_vae_encoder): the offsets of the existing tensors do not move
+static void reg_vae_encoder(Engine* e) {
+  Registry r{e};
+  r.size = e->wslab_bytes;
+  r.quant = false;                   // fp16 like the decoder
+  const sdeo_config& c = e->cfg;
+  const std::string d = std::string(NS_VAE) + "encoder";
+  const int zc2 = 2 * c.vae_z_channels;
+  r.conv(d + ".conv_in", c.vae_out_ch, c.vae_ch, 3);
+  int bi = c.vae_ch;
+  for (int l = 0; l < c.vae_num_levels; ++l) {
+    const int bo = c.vae_ch * c.vae_ch_mult[l];
+    for (int j = 0; j < c.vae_num_res_blocks; ++j) {
+      reg_vae_res(r, d + ".down." + std::to_string(l) + ".block." + std::to_string(j), bi, bo);
+      bi = bo;
+    }
+    if (l != c.vae_num_levels - 1) r.conv(d + ".down." + std::to_string(l) + ".downsample.conv", bi, bi, 3);
+  }
+  reg_vae_res(r, d + ".mid.block_1", bi, bi);
+  r.norm(d + ".mid.attn_1.norm", bi);
+  for (const char* n : {"q", "k", "v", "proj_out"}) r.conv(d + ".mid.attn_1." + n, bi, bi, 1);
+  reg_vae_res(r, d + ".mid.block_2", bi, bi);
+  r.norm(d + ".norm_out", bi);
+  r.conv(d + ".conv_out", bi, zc2, 3, round8(zc2));
+  r.conv(std::string(NS_VAE) + "quant_conv", zc2, zc2, 1, round8(zc2));
+  e->wslab_bytes = align_up(r.size, 256);
+}
+
 // ------------------------------------------------------------------------------------------------
 // program builder
 // ------------------------------------------------------------------------------------------------
@@ -536,6 +570,8 @@ struct ConvOpts {                     // conv / gemm options
   float gn_in_eps = 1e-5f; int gn_in_silu = 0;
   // conv(): stream this [cout][k*k*x.c] matrix / bias instead of the tensors registered under `name` (a composed Linear)
   const f16* w_ovr = nullptr; const float* b_ovr = nullptr;
+  // conv(): zero padding top / left and bottom / right; -1 = k / 2 (the VAE encoder's Downsample: 0 and 1)
+  int pad_before = -1, pad_after = -1;
 };
 
 struct Builder {
@@ -700,9 +736,10 @@ struct Builder {
   T conv(const T& x, const std::string& name, int cout, int k, int stride, int ups, const CO& o = CO()) {
     const WEntry* w = o.w_ovr ? nullptr : W(name + ".weight");
     ConvGemm p;
-    const int pad = k / 2;
+    const int pad = o.pad_before >= 0 ? o.pad_before : k / 2;
+    const int pad_after = o.pad_after >= 0 ? o.pad_after : k / 2;
     const int hv = ups ? 2 * x.h : x.h, wv = ups ? 2 * x.w : x.w;
-    const int ho = (hv + 2 * pad - k) / stride + 1, wo = (wv + 2 * pad - k) / stride + 1;
+    const int ho = (hv + pad + pad_after - k) / stride + 1, wo = (wv + pad + pad_after - k) / stride + 1;
     const int cs = o.cout_store > 0 ? o.cout_store : cout;
     T y = o.out ? *o.out : alloc(x.n, ho, wo, cs);
     if (w && w->ipad != x.c && err.empty()) err = "conv " + name + ": input has " + std::to_string(x.c) + " channels, weight expects " + std::to_string(w->ipad);
@@ -711,6 +748,7 @@ struct Builder {
     p.bias2 = o.bias2; p.ld_bias2 = o.ld_bias2;
     if (o.res) { p.res = o.res->p; p.ldres = o.res->ld; }
     p.B = x.n; p.Hi = x.h; p.Wi = x.w; p.Cin = x.c; p.Ho = ho; p.Wo = wo; p.R = p.S = k; p.stride = stride; p.pad = pad; p.ups = ups;
+    if (pad_after != pad) p.pad_after = pad_after;
     p.M = x.n * ho * wo; p.N = cs; p.K = k * k * x.c;
     p.ldx = x.ld; p.ldw = p.K; p.ldy = y.ld; p.act = o.act;
     if (o.gn_in) {
@@ -1002,6 +1040,64 @@ static int run(Engine* e, const Program& p, hipStream_t s, bool skip_zero_convs 
   return 0;
 }
 
+// ResnetBlock (`model.py:82-128`, no time embedding, dropout 0) of the VAE decoder and encoder: every conv feeds a GroupNorm
+static T build_vae_res(Builder& b, const std::string& p, const T& x, int cin, int cout) {
+  Builder::CO gnx; gnx.gn_next = true;
+  T h1 = b.gn_conv(x, p + ".norm1", 1e-6f, 1, p + ".conv1", cout, gnx);
+  T sk; const T* res = &x;
+  if (cin != cout) { sk = b.conv(x, p + ".nin_shortcut", cout, 1, 1, 0); res = &sk; }
+  Builder::CO o; o.res = res; o.gn_next = true;
+  T y = b.gn_conv(h1, p + ".norm2", 1e-6f, 1, p + ".conv2", cout, o);
+  b.release(h1);
+  if (cin != cout) b.release(sk);
+  return y;
+}
+
+// AttnBlock (`model.py:179-203`) of the VAE decoder and encoder: single head of x.c channels over the x.h * x.w tokens of one image;
+// consumes (releases) hcur, returns x + proj_out(attention)
+static T build_vae_attn(Builder& b, const std::string& p, T hcur) {
+  const int bin = hcur.c, h = hcur.h, w = hcur.w;
+  const int Tn = h * w;
+  T g = b.gn(hcur, p + ".norm", 1e-6f, 0);
+  T q = b.conv(g, p + ".q", bin, 1, 1, 0);
+  T k = b.conv(g, p + ".k", bin, 1, 1, 0);
+  T o;
+  if ((bin % 8 == 0 && bin <= 160) || bin == 256 || bin == 512) {
+    // flash attention (d = 512 on the wide-head kernel: the four waves of a workgroup split the channels)
+    T v = b.conv(g, p + ".v", bin, 1, 1, 0);
+    b.release(g);
+    o = b.alloc(1, h, w, bin);
+    b.attn(o, q.p, q.ld, k.p, k.ld, v.p, v.ld, 1, 1, Tn, Tn, Tn, Tn, bin);
+    b.release(q);
+    b.release(k);
+    b.release(v);
+  } else {
+    // other widths: scores materialised in fp32, row softmax, second GEMM
+    T vt = b.gemm_t(g, b.wptr(p + ".v.weight"), bin, bin, b.vptr(p + ".v.bias"));
+    b.release(g);
+    T s32 = b.alloc2d(Tn, Tn * 2);
+    float* sp = reinterpret_cast<float*>(s32.p);
+    b.gemm(q, k.p, k.ld, Tn, nullptr, Builder::CO(), sp, Tn);
+    b.release(q);
+    b.release(k);
+    T pr = b.alloc2d(Tn, Tn);
+    {
+      f16* pp = pr.p; const float sc = 1.0f / sqrtf((float)bin);
+      b.push([=](hipStream_t s) { return softmax_rows(pp, Tn, sp, Tn, Tn, Tn, sc, s); });
+    }
+    b.release(s32);
+    o = b.gemm(pr, vt.p, vt.ld, bin, nullptr);
+    o.n = 1; o.h = h; o.w = w;
+    b.release(pr);
+    b.release(vt);
+  }
+  Builder::CO ro; ro.res = &hcur; ro.gn_next = true;
+  T yo = b.conv(o, p + ".proj_out", bin, 1, 1, 0, ro);
+  b.release(o);
+  b.release(hcur);
+  return yo;
+}
+
 static void build_all(Engine* e, Arena& arena, Arena& arena2, bool dry, size_t* max_splitk, size_t* max_gn, std::string* err) {
   const sdeo_config& c = e->cfg;
   const int N = e->N, h = e->lh, w = e->lw;
@@ -1258,68 +1354,17 @@ static void build_all(Engine* e, Arena& arena, Arena& arena2, bool dry, size_t* 
     Builder::CO gnx; gnx.gn_next = true;       // every conv of the decoder below feeds a GroupNorm
     T hcur = b.conv(z2, d + ".conv_in", bin, 3, 1, 0, gnx);
     b.release(z2);
-    auto vres = [&](const std::string& p, const T& x, int cin, int cout) {
-      T h1 = b.gn_conv(x, p + ".norm1", 1e-6f, 1, p + ".conv1", cout, gnx);
-      T sk; const T* res = &x;
-      if (cin != cout) { sk = b.conv(x, p + ".nin_shortcut", cout, 1, 1, 0); res = &sk; }
-      Builder::CO o; o.res = res; o.gn_next = true;
-      T y = b.gn_conv(h1, p + ".norm2", 1e-6f, 1, p + ".conv2", cout, o);
-      b.release(h1);
-      if (cin != cout) b.release(sk);
-      return y;
-    };
-    T y = vres(d + ".mid.block_1", hcur, bin, bin);
+    T y = build_vae_res(b, d + ".mid.block_1", hcur, bin, bin);
     b.release(hcur);
     hcur = y;
-    {   // AttnBlock (`model.py:179-203`): single head of `bin` channels over h*w tokens
-      const std::string p = d + ".mid.attn_1";
-      const int Tn = h * w;
-      T g = b.gn(hcur, p + ".norm", 1e-6f, 0);
-      T q = b.conv(g, p + ".q", bin, 1, 1, 0);
-      T k = b.conv(g, p + ".k", bin, 1, 1, 0);
-      T o;
-      if ((bin % 8 == 0 && bin <= 160) || bin == 256 || bin == 512) {
-        // flash attention (d = 512 on the wide-head kernel: the four waves of a workgroup split the channels)
-        T v = b.conv(g, p + ".v", bin, 1, 1, 0);
-        b.release(g);
-        o = b.alloc(1, h, w, bin);
-        b.attn(o, q.p, q.ld, k.p, k.ld, v.p, v.ld, 1, 1, Tn, Tn, Tn, Tn, bin);
-        b.release(q);
-        b.release(k);
-        b.release(v);
-      } else {
-        // other widths: scores materialised in fp32, row softmax, second GEMM
-        T vt = b.gemm_t(g, b.wptr(p + ".v.weight"), bin, bin, b.vptr(p + ".v.bias"));
-        b.release(g);
-        T s32 = b.alloc2d(Tn, Tn * 2);
-        float* sp = reinterpret_cast<float*>(s32.p);
-        b.gemm(q, k.p, k.ld, Tn, nullptr, Builder::CO(), sp, Tn);
-        b.release(q);
-        b.release(k);
-        T pr = b.alloc2d(Tn, Tn);
-        {
-          f16* pp = pr.p; const float sc = 1.0f / sqrtf((float)bin);
-          b.push([=](hipStream_t s) { return softmax_rows(pp, Tn, sp, Tn, Tn, Tn, sc, s); });
-        }
-        b.release(s32);
-        o = b.gemm(pr, vt.p, vt.ld, bin, nullptr);
-        o.n = 1; o.h = h; o.w = w;
-        b.release(pr);
-        b.release(vt);
-      }
-      Builder::CO ro; ro.res = &hcur; ro.gn_next = true;
-      T yo = b.conv(o, p + ".proj_out", bin, 1, 1, 0, ro);
-      b.release(o);
-      b.release(hcur);
-      hcur = yo;
-    }
-    y = vres(d + ".mid.block_2", hcur, bin, bin);
+    hcur = build_vae_attn(b, d + ".mid.attn_1", hcur);
+    y = build_vae_res(b, d + ".mid.block_2", hcur, bin, bin);
     b.release(hcur);
     hcur = y;
     int last = bin;
     for (auto& L : levels) {
       for (size_t j = 0; j < L.blocks.size(); ++j) {
-        y = vres(d + ".up." + std::to_string(L.level) + ".block." + std::to_string(j), hcur, L.blocks[j].first, L.blocks[j].second);
+        y = build_vae_res(b, d + ".up." + std::to_string(L.level) + ".block." + std::to_string(j), hcur, L.blocks[j].first, L.blocks[j].second);
         b.release(hcur);
         hcur = y;
         last = L.blocks[j].second;
@@ -1341,6 +1386,62 @@ static void build_all(Engine* e, Arena& arena, Arena& arena2, bool dry, size_t* 
       });
     }
     b.release(img);
+  }
+
+  // ---- VAE encode program, batch 1 (sdeo_enable_vae_encoder only): image intake -> Encoder (`model.py:452-545`) -> quant_conv ->
+  //      posterior tail (encode_first_stage + get_first_stage_encoding; AutoencoderKL itself is absent from the reference tree)
+  if (e->vae_encoder) {
+    b.prog = &e->p_vae_enc;
+    const std::string d = std::string(NS_VAE) + "encoder";
+    const int H = 8 * h, W = 8 * w, zc = c.vae_z_channels;
+    T img = b.alloc(1, H, W, round8(c.vae_out_ch));
+    {
+      f16* o = img.p; const float* in = e->enc_img; const uint8_t* in8 = e->enc_img_u8; const int Cc = c.vae_out_ch, HW = H * W;
+      const int* from_u8 = &e->enc_from_u8;
+      b.push([=](hipStream_t s) { return image_to_nhwc8_f16(o, *from_u8 ? nullptr : in, in8, 1, Cc, HW, s); }, "image_intake", 0,
+             (4.0 + 16.0) * HW);
+    }
+    Builder::CO gnx; gnx.gn_next = true;       // every conv of the encoder up to norm_out feeds a GroupNorm
+    T hcur = b.conv(img, d + ".conv_in", c.vae_ch, 3, 1, 0, gnx);
+    b.release(img);
+    int bi = c.vae_ch;
+    for (int l = 0; l < c.vae_num_levels; ++l) {
+      const int bo = c.vae_ch * c.vae_ch_mult[l];
+      for (int j = 0; j < c.vae_num_res_blocks; ++j) {
+        T y = build_vae_res(b, d + ".down." + std::to_string(l) + ".block." + std::to_string(j), hcur, bi, bo);
+        b.release(hcur);
+        hcur = y;
+        bi = bo;
+      }
+      if (l != c.vae_num_levels - 1) {        // Downsample: F.pad(x, (0,1,0,1)) + conv3x3 stride 2 pad 0 (`model.py:78-86`)
+        Builder::CO o = gnx; o.pad_before = 0; o.pad_after = 1;
+        T y = b.conv(hcur, d + ".down." + std::to_string(l) + ".downsample.conv", bi, 3, 2, 0, o);
+        b.release(hcur);
+        hcur = y;
+      }
+    }
+    if ((hcur.h != h || hcur.w != w) && b.err.empty())
+      b.err = "VAE encoder: " + std::to_string(H) + "x" + std::to_string(W) + " images encode to " + std::to_string(hcur.h) + "x" +
+              std::to_string(hcur.w) + ", not the configured latent " + std::to_string(h) + "x" + std::to_string(w);
+    T y = build_vae_res(b, d + ".mid.block_1", hcur, bi, bi);
+    b.release(hcur);
+    hcur = build_vae_attn(b, d + ".mid.attn_1", y);
+    y = build_vae_res(b, d + ".mid.block_2", hcur, bi, bi);
+    b.release(hcur);
+    hcur = y;
+    Builder::CO oo; oo.cout_store = round8(2 * zc);
+    T mo = b.gn_conv(hcur, d + ".norm_out", 1e-6f, 1, d + ".conv_out", 2 * zc, oo);
+    b.release(hcur);
+    Builder::CO qo; qo.cout_store = round8(2 * zc);
+    T q = b.conv(mo, std::string(NS_VAE) + "quant_conv", 2 * zc, 1, 1, 0, qo);
+    b.release(mo);
+    {
+      float* zp = e->enc_z; float* mp = e->enc_moments; const float* np_ = e->enc_noise; const int* with_noise = &e->enc_with_noise;
+      const f16* in = q.p; const int ld = q.ld, HW = h * w; const float sf = c.vae_scale_factor;
+      b.push([=](hipStream_t s) { return vae_posterior(zp, mp, in, ld, *with_noise ? np_ : nullptr, zc, HW, sf, s); }, "vae_posterior", 0,
+             (2.0 * 2 * zc + 4.0 * 4 * zc) * HW);
+    }
+    b.release(q);
   }
   *max_splitk = b.max_splitk;
   *max_gn = b.max_gn;
@@ -1365,7 +1466,7 @@ static void free_configured(Engine* e) {
   if (e->arena2) (void)hipFree(e->arena2);
   e->arena2 = nullptr;
   for (Program* p : {&e->p_hint, &e->p_ctx_cn, &e->p_ctx_unet, &e->p_cn, &e->p_cn_export, &e->p_ctrl_import, &e->p_unet_enc,
-                     &e->p_unet_dec, &e->p_unet_noctrl, &e->p_vae, &e->p_temb[0], &e->p_temb[1], &e->p_temb_tab, &e->p_x0, &e->p_eps_export, &e->p_unet_dec_fused})
+                     &e->p_unet_dec, &e->p_unet_noctrl, &e->p_vae, &e->p_vae_enc, &e->p_temb[0], &e->p_temb[1], &e->p_temb_tab, &e->p_x0, &e->p_eps_export, &e->p_unet_dec_fused})
     p->clear();
   e->tab_count = 0;
 }
@@ -1425,6 +1526,38 @@ int sdeo_destroy(sdeo_handle h) {
   if (h->mxslab) (void)hipFree(h->mxslab);
   if (h->stage) (void)hipFree(h->stage);
   delete h;
+  return 0;
+}
+
+int sdeo_enable_vae_encoder(sdeo_handle h) {
+  SDEO_CHECK(h, "sdeo_enable_vae_encoder: null handle");
+  if (h->vae_encoder) return 0;
+  for (const auto& w : h->weights)
+    SDEO_CHECK(!w.loaded, "sdeo_enable_vae_encoder: call it before the first sdeo_load_weight (%s is loaded)", w.name.c_str());
+  SDEO_CHECK(!h->finalized && !h->arena, "sdeo_enable_vae_encoder: call it before sdeo_finalize_weights / sdeo_configure");
+  SDEO_CHECK(h->cfg.vae_num_levels == 4, "sdeo_enable_vae_encoder: %d VAE levels downsample by %d, the 8h x 8w image boundary needs 8",
+             h->cfg.vae_num_levels, 1 << (h->cfg.vae_num_levels - 1));
+  SDEO_CHECK(h->cfg.vae_out_ch <= 8, "sdeo_enable_vae_encoder: %d image channels (at most 8)", h->cfg.vae_out_ch);
+  reg_vae_encoder(h);
+  // nothing is loaded yet: the larger slab starts from zeros like the first one
+  if (h->wslab) (void)hipFree(h->wslab);
+  h->wslab = nullptr;
+  SDEO_HIP(hipMalloc((void**)&h->wslab, h->wslab_bytes));
+  SDEO_HIP(hipMemset(h->wslab, 0, h->wslab_bytes));
+  size_t mx = 0;
+  for (auto& w : h->weights) {
+    size_t n = 1;
+    for (int i = 0; i < w.ndim; ++i) n *= (size_t)w.dims[i];
+    mx = std::max(mx, n);
+  }
+  if (mx * sizeof(float) > h->stage_bytes) {
+    if (h->stage) (void)hipFree(h->stage);
+    h->stage = nullptr;
+    h->stage_bytes = mx * sizeof(float);
+    SDEO_HIP(hipMalloc((void**)&h->stage, h->stage_bytes));
+  }
+  h->device_bytes = h->wslab_bytes;
+  h->vae_encoder = true;
   return 0;
 }
 
@@ -1598,6 +1731,13 @@ int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w) {
   if (int rc = dev_alloc(h, &h->vae_in, (size_t)c.vae_z_channels * px * 4)) return rc;
   if (int rc = dev_alloc(h, &h->vae_out, (size_t)c.vae_out_ch * px * 64 * 4)) return rc;
   if (int rc = dev_alloc(h, &h->vae_u8, (size_t)c.vae_out_ch * px * 64)) return rc;
+  if (h->vae_encoder) {
+    if (int rc = dev_alloc(h, &h->enc_img, (size_t)c.vae_out_ch * px * 64 * 4)) return rc;
+    if (int rc = dev_alloc(h, &h->enc_img_u8, (size_t)c.vae_out_ch * px * 64)) return rc;
+    if (int rc = dev_alloc(h, &h->enc_noise, (size_t)c.vae_z_channels * px * 4)) return rc;
+    if (int rc = dev_alloc(h, &h->enc_z, (size_t)c.vae_z_channels * px * 4)) return rc;
+    if (int rc = dev_alloc(h, &h->enc_moments, (size_t)2 * c.vae_z_channels * px * 4)) return rc;
+  }
   const int nctrl = (int)h->cplan.in.size() + 1;
   for (int i = 0; i < nctrl; ++i) {
     const int idx = i < (int)h->cplan.in.size() ? i : (int)h->cplan.in.size() - 1;
@@ -1836,6 +1976,32 @@ int sdeo_vae_decode(sdeo_handle h, const float* z, int n, float* images, uint8_t
       if (int rc = copy_in(images + (size_t)i * c.vae_out_ch * px * 64, h->vae_out, (size_t)c.vae_out_ch * px * 64 * 4, s)) return rc;
     if (images_u8)
       if (int rc = copy_in(images_u8 + (size_t)i * c.vae_out_ch * px * 64, h->vae_u8, (size_t)c.vae_out_ch * px * 64, s)) return rc;
+  }
+  return 0;
+}
+
+int sdeo_vae_encode(sdeo_handle h, const float* images, const uint8_t* images_u8, int n, const float* noise, float* z, float* moments,
+                    void* stream) {
+  SDEO_CHECK(h, "sdeo_vae_encode: null handle");
+  SDEO_CHECK(h->vae_encoder, "sdeo_vae_encode: this handle has no VAE encoder (call sdeo_enable_vae_encoder before loading weights)");
+  REQUIRE_READY(h);
+  SDEO_CHECK(!images != !images_u8, "sdeo_vae_encode: pass exactly one of images (fp32) and images_u8");
+  SDEO_CHECK(z && n >= 1 && n <= h->N, "sdeo_vae_encode: bad argument (z %s, n = %d, configured %d)", z ? "set" : "NULL", n, h->N);
+  hipStream_t s = S(stream);
+  const sdeo_config& c = h->cfg;
+  const size_t px = (size_t)h->lh * h->lw, ipx = px * 64, zc = (size_t)c.vae_z_channels;
+  h->enc_from_u8 = images ? 0 : 1;
+  h->enc_with_noise = noise ? 1 : 0;
+  for (int i = 0; i < n; ++i) {
+    if (images) {
+      if (int rc = copy_in(h->enc_img, images + (size_t)i * c.vae_out_ch * ipx, (size_t)c.vae_out_ch * ipx * 4, s)) return rc;
+    } else {
+      if (int rc = copy_in(h->enc_img_u8, images_u8 + (size_t)i * c.vae_out_ch * ipx, (size_t)c.vae_out_ch * ipx, s)) return rc;
+    }
+    if (noise) if (int rc = copy_in(h->enc_noise, noise + (size_t)i * zc * px, zc * px * 4, s)) return rc;
+    if (int rc = run(h, h->p_vae_enc, s)) return rc;
+    if (int rc = copy_in(z + (size_t)i * zc * px, h->enc_z, zc * px * 4, s)) return rc;
+    if (moments) if (int rc = copy_in(moments + (size_t)i * 2 * zc * px, h->enc_moments, 2 * zc * px * 4, s)) return rc;
   }
   return 0;
 }

@@ -115,6 +115,25 @@ def conv2d_nhwc(x, w_krsc, bias=None, bias2=None, res=None, stride=1, upsample2x
     return y
 
 
+def conv2d_pad_nhwc(x, w_krsc, pad_before, pad_after, bias=None, bias2=None, res=None, stride=1, upsample2x=False, act=0, scale=1.0):
+    """conv2d_nhwc with explicit zero padding: pad_before rows / columns at the top / left, pad_after at the bottom / right.
+    (0, 1) with k = 3, stride 2 is the VAE encoder's Downsample, F.conv2d(F.pad(x, (0, 1, 0, 1)), w, stride=2)."""
+    lib = _lib.load()
+    _need_cuda(x, w_krsc)
+    n, h, w, cin = x.shape
+    cout, k, _, cin_w = w_krsc.shape
+    assert cin == cin_w and x.is_contiguous() and w_krsc.is_contiguous()
+    hv, wv = (2 * h, 2 * w) if upsample2x else (h, w)
+    ho = (hv + pad_before + pad_after - k) // stride + 1
+    wo = (wv + pad_before + pad_after - k) // stride + 1
+    y = torch.empty((n, ho, wo, cout), dtype=torch.float16, device=x.device)
+    args = (_i(n), _i(h), _i(w), _i(cin), _i(cout), _i(k), _i(stride), _i(int(upsample2x)), _i(pad_before), _i(pad_after))
+    ws = _ws(lib.sdeo_conv2d_pad_workspace_bytes(*args), x.device)
+    check(lib.sdeo_conv2d_pad_nhwc_f16(ptr(y), ptr(x), ptr(w_krsc), ptr(bias), ptr(bias2), ptr(res), *args, _i(act), _f(scale),
+                                       ptr(ws), C.c_size_t(ws.numel()), cur_stream()), "conv2d_pad")
+    return y
+
+
 def conv2d_gn(x, w_krsc, gamma, beta, bias=None, res=None, stride=1, upsample2x=False, groups=32, eps=1e-5, swish=False):
     """[conv2d whose epilogue emits the GroupNorm partials of its output] -> [normalise-only GroupNorm]: returns (y, GroupNorm(y), slots)
     or None when the plan of this shape cannot emit partials (split-K, strips cutting a group, ...)."""

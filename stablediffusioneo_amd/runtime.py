@@ -43,9 +43,10 @@ class SdeoRuntime:
     """create -> load_state_dict -> configure(n, h, w) -> controlnet / unet / apply_model / vae_decode."""
 
     def __init__(self, ucfg: S.UNetConfig = S.UNET_SD15, vcfg: S.VAEConfig = S.VAE_SD15, device: Optional[torch.device] = None,
-                 weight_bits: int = 16, act_bits: int = 16, mx_min_rows: int = 0):
+                 weight_bits: int = 16, act_bits: int = 16, mx_min_rows: int = 0, vae_encoder: bool = False):
         """weight_bits = 8: the UNet / ControlNet matrices are packed to fp8 (OCP e4m3fn, per-output-channel power-of-two scale) when
-        the weights are finalised (BASELINE configs[4]; the reference's precision switch is `onnx2trt_static_plugin.py:40-42`)."""
+        the weights are finalised (BASELINE configs[4]; the reference's precision switch is `onnx2trt_static_plugin.py:40-42`).
+        vae_encoder = True: the handle also expects `first_stage_model.encoder.*` / `quant_conv.*` and runs `vae_encode`."""
         if not torch.cuda.is_available():
             raise _lib.SdeoError("SdeoRuntime needs a HIP device (there is no CPU fallback)")
         self.lib = _lib.load()
@@ -55,6 +56,9 @@ class SdeoRuntime:
         self.handle = C.c_void_p()
         self._cfg = make_config(ucfg, vcfg)
         check(self.lib.sdeo_create(C.byref(self._cfg), C.byref(self.handle)), "sdeo_create")
+        self.vae_encoder = bool(vae_encoder)
+        if self.vae_encoder:        # before any weight: the weight slab is sized when the encoder registers its tensors
+            check(self.lib.sdeo_enable_vae_encoder(self.handle), "enable_vae_encoder")
         self.weight_bits = int(weight_bits)
         if self.weight_bits != 16:
             check(self.lib.sdeo_set_weight_precision(self.handle, C.c_int(self.weight_bits)), "set_weight_precision")
@@ -279,6 +283,35 @@ class SdeoRuntime:
         u8 = torch.empty((b, 8 * self.h, 8 * self.w, v.out_ch), dtype=torch.uint8, device=self.device) if want_u8 else None
         check(self.lib.sdeo_vae_decode(self.handle, ptr(z), C.c_int(b), ptr(img), ptr(u8), cur_stream()), "vae_decode")
         return (img, u8) if want_u8 else img
+
+    def vae_encode(self, images=None, images_u8=None, noise=None, want_moments: bool = False):
+        """encode_first_stage + get_first_stage_encoding: images (b,3,8h,8w) fp32 in [-1,1] OR images_u8 (b,8h,8w,3) uint8 (mapped as
+        2 * (u / 255) - 1) -> z (b,4,h,w) fp32 = scale_factor * (mean + std * noise), or scale_factor * mean when noise is None.
+        want_moments: also return the quant_conv output (b,8,h,w) fp32 (mean, then logvar, before the clamp)."""
+        if not self.vae_encoder:
+            raise _lib.SdeoError("vae_encode: this runtime was created without the VAE encoder (SdeoRuntime(..., vae_encoder=True))")
+        if (images is None) == (images_u8 is None):
+            raise _lib.SdeoError("vae_encode: pass exactly one of images (fp32 NCHW) and images_u8 (uint8 NHWC)")
+        v = self.vcfg
+        if images is not None:
+            images = self._f32(images)
+            b = images.shape[0]
+            if tuple(images.shape[1:]) != (v.out_ch, 8 * self.h, 8 * self.w):
+                raise _lib.SdeoError(f"image shape {tuple(images.shape)} does not match the configured latent {self.h}x{self.w}")
+        else:
+            images_u8 = images_u8.to(device=self.device, dtype=torch.uint8).contiguous()
+            b = images_u8.shape[0]
+            if tuple(images_u8.shape[1:]) != (8 * self.h, 8 * self.w, v.out_ch):
+                raise _lib.SdeoError(f"image shape {tuple(images_u8.shape)} does not match the configured latent {self.h}x{self.w}")
+        if b > self.n:
+            raise _lib.SdeoError(f"vae_encode: {b} images, the runtime is configured for {self.n}")
+        if noise is not None:
+            noise = self._f32(noise, (b, v.z_channels, self.h, self.w))
+        z = torch.empty((b, v.z_channels, self.h, self.w), dtype=torch.float32, device=self.device)
+        mom = torch.empty((b, 2 * v.z_channels, self.h, self.w), dtype=torch.float32, device=self.device) if want_moments else None
+        check(self.lib.sdeo_vae_encode(self.handle, ptr(images), ptr(images_u8), C.c_int(b), ptr(noise), ptr(z), ptr(mom),
+                                       cur_stream()), "vae_encode")
+        return (z, mom) if want_moments else z
 
 
 class ClipRuntime:

@@ -322,6 +322,32 @@ def param_spec_vae(cfg: VAEConfig = VAE_SD15):
     return spec
 
 
+def param_spec_vae_encoder(cfg: VAEConfig = VAE_SD15):
+    """`first_stage_model.*` parameters on the encode path: encoder.* + quant_conv (`model.py:452-545` with attn_resolutions = [],
+    double_z = True, in_channels = out_ch; quant_conv = upstream AutoencoderKL's 2 z_channels -> 2 embed_dim conv1x1).  Not part of
+    param_spec_vae / param_spec_full: a runtime expects these only when built with vae_encoder=True."""
+    spec = OrderedDict()
+    d = "encoder"
+    _conv(spec, f"{d}.conv_in", cfg.out_ch, cfg.ch, 3)
+    bi = cfg.ch
+    for i_level, m in enumerate(cfg.ch_mult):
+        bo = cfg.ch * m
+        for j in range(cfg.num_res_blocks):
+            _vae_res(spec, f"{d}.down.{i_level}.block.{j}", bi, bo)
+            bi = bo
+        if i_level != len(cfg.ch_mult) - 1:
+            _conv(spec, f"{d}.down.{i_level}.downsample.conv", bi, bi, 3)
+    _vae_res(spec, f"{d}.mid.block_1", bi, bi)
+    _norm(spec, f"{d}.mid.attn_1.norm", bi)
+    for n in ("q", "k", "v", "proj_out"):
+        _conv(spec, f"{d}.mid.attn_1.{n}", bi, bi, 1)
+    _vae_res(spec, f"{d}.mid.block_2", bi, bi)
+    _norm(spec, f"{d}.norm_out", bi)
+    _conv(spec, f"{d}.conv_out", bi, 2 * cfg.z_channels, 3)
+    _conv(spec, "quant_conv", 2 * cfg.z_channels, 2 * cfg.embed_dim, 1)
+    return spec
+
+
 # checkpoint namespaces of `control_sd15_canny.pth` (SURVEY.md 3.3)
 NS_UNET = "model.diffusion_model."
 NS_CONTROL = "control_model."
@@ -413,6 +439,12 @@ def synth_tensor(name: str, shape, seed: int = 0) -> torch.Tensor:
 
 def synth_state_dict(spec, seed: int = 0, prefix: str = "") -> Dict[str, torch.Tensor]:
     return OrderedDict((k, synth_tensor(prefix + k, shp, seed)) for k, shp in spec.items())
+
+
+def synth_vae_encoder_state_dict(cfg: VAEConfig = VAE_SD15, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Synthetic `first_stage_model.encoder.*` / `quant_conv.*` tensors, drawn exactly as SdeoRuntime(vae_encoder=True).load_synthetic
+    draws them (full checkpoint names)."""
+    return OrderedDict((NS_VAE + k, v) for k, v in synth_state_dict(param_spec_vae_encoder(cfg), seed, NS_VAE).items())
 
 
 def count_params(spec) -> int:
