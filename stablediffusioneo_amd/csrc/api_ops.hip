@@ -124,6 +124,23 @@ const char* sdeo_debug_conv2d_kernel_name(int n, int h, int w, int cin, int cout
   return conv_gemm_kernel_name(p);
 }
 
+// Plan query (tests): the ConvGemm of an sdeo_conv2d_nhwc_f16 / sdeo_gemm_f16 call, built by the same fill_conv / fill_gemm, with
+// `act` and armed fp8 weights (fp8 != 0) as that call would see them; returns the tuned-table key it looks up (key10) and the
+// (tile, split-K) the launcher picks.  Host only: no device call.
+static const float g_query_scale = 1.f;
+static const Fp8Arm kQueryFp8{&g_query_scale, &g_query_scale};
+
+int sdeo_debug_conv2d_plan(int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, int act, int fp8, int* key10,
+                           int* tile, int* splitk) {
+  SDEO_CHECK(key10 && tile && splitk, "conv2d_plan: null argument");
+  ConvGemm p;
+  if (int rc = fill_conv(p, n, h, w, cin, cout, ksize, stride, upsample2x)) return rc;
+  p.act = act;
+  if (fp8) take_fp8(p, kQueryFp8);
+  conv_gemm_query_plan(p, key10, tile, splitk);
+  return 0;
+}
+
 int sdeo_conv2d_nhwc_f16(void* y, const void* x, const void* w_krsc, const float* bias, const float* bias2, const void* res,
                          int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, int act, float scale,
                          void* workspace, size_t workspace_bytes, void* stream) {
@@ -201,6 +218,19 @@ static void fill_gemm(ConvGemm& p, int m, int n, int k) {
   p.B = m; p.Hi = p.Wi = p.Ho = p.Wo = 1; p.Cin = k; p.R = p.S = 1; p.stride = 1; p.pad = 0;
   p.M = m; p.N = n; p.K = k;
 }
+
+int sdeo_debug_gemm_plan(int m, int n, int k, int act, int fp8, int* key10, int* tile, int* splitk) {
+  SDEO_CHECK(key10 && tile && splitk, "gemm_plan: null argument");
+  ConvGemm p;
+  fill_gemm(p, m, n, k);
+  p.act = act;
+  if (fp8) take_fp8(p, kQueryFp8);
+  conv_gemm_query_plan(p, key10, tile, splitk);
+  return 0;
+}
+
+// (tile, split-K) of the last conv / GEMM launch (host-side record; -1 / 0 before the first)
+void sdeo_debug_last_gemm_plan(int* tile, int* splitk) { conv_gemm_last_plan(tile, splitk); }
 
 size_t sdeo_gemm_workspace_bytes(int m, int n, int k) {
   ConvGemm p;

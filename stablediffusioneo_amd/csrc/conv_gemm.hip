@@ -960,6 +960,19 @@ size_t conv_gemm_workspace_bytes(const ConvGemm& p0) {
 const char* conv_gemm_kernel_name(const ConvGemm& p) { return kTiles[make_plan(mx_view(p)).tile].name; }
 int conv_gemm_plan_splitk(const ConvGemm& p) { return make_plan(mx_view(p)).splitk; }
 
+void conv_gemm_query_plan(const ConvGemm& p0, int key[10], int* tile, int* splitk) {
+  const ConvGemm p = mx_view(p0);
+  const ShapeKey k = key_of(p);
+  for (int i = 0; i < 10; ++i) key[i] = k[i];
+  const Plan pl = make_plan(p);
+  *tile = pl.tile;
+  *splitk = pl.splitk;
+}
+
+// (tile, split-K) of the last problem conv_gemm() launched: host-side only, read by the tests through sdeo_debug_last_gemm_plan
+static int g_last_tile = -1, g_last_splitk = 0;
+void conv_gemm_last_plan(int* tile, int* splitk) { *tile = g_last_tile; *splitk = g_last_splitk; }
+
 template <typename K>
 static int launch_k(K kernel, int smem, DeviceOnce* attr_done, const KP2& kp, int count, int tiles, hipStream_t stream, int threads = 256) {
   if (attr_done->need()) {
@@ -1199,6 +1212,7 @@ int conv_gemm(const ConvGemm& p0, hipStream_t stream) {
   Plan pl;
   KP2 kk{};
   if (int rc = prepare(p, pl, kk.k[0])) return rc;
+  g_last_tile = pl.tile; g_last_splitk = pl.splitk;
   return dispatch(pl, p.ups, p.wscale != nullptr, kk, 1, stream);
 }
 

@@ -81,6 +81,9 @@ int conv_gemm_read_stamps(unsigned long long* out, int n);
 int conv_halo_read_stamps(unsigned long long* out, int n);
 size_t conv_gemm_workspace_bytes(const ConvGemm& p);
 int conv_gemm_plan_splitk(const ConvGemm& p);       // split-K factor of the plan chosen for p
+// tests: the tuned-table key of p and the (tile, split-K) the launcher picks for it (host only); the plan of the last launch
+void conv_gemm_query_plan(const ConvGemm& p, int key[10], int* tile, int* splitk);
+void conv_gemm_last_plan(int* tile, int* splitk);
 // name of the kernel instantiation the launcher will pick (for profiles; matches the rocprof kernel name's template args)
 const char* conv_gemm_kernel_name(const ConvGemm& p);
 void conv_gemm_debug_force(int tile, int splitk);

@@ -94,8 +94,18 @@ def _arm_fp8(lib, w8):
         lib.sdeo_debug_next_weights_fp8(ptr(q), ptr(sc))
 
 
-def conv2d_nhwc(x, w_krsc, bias=None, bias2=None, res=None, stride=1, upsample2x=False, act=0, scale=1.0, w8=None):
-    """x (N,H,W,Cin) fp16; w_krsc (Cout,k,k,Cin) fp16; returns (N,Ho,Wo,Cout) fp16.  w8 = (codes, scales): stream the fp8 copy."""
+def _out(out, shape, dtype, device):
+    """the caller's output tensor (contiguous, of exactly this shape and type) or a new one"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    assert tuple(out.shape) == tuple(shape) and out.dtype == dtype and out.is_contiguous() and out.device == device, \
+        (tuple(out.shape), tuple(shape), out.dtype, dtype)
+    return out
+
+
+def conv2d_nhwc(x, w_krsc, bias=None, bias2=None, res=None, stride=1, upsample2x=False, act=0, scale=1.0, w8=None, out=None):
+    """x (N,H,W,Cin) fp16; w_krsc (Cout,k,k,Cin) fp16; returns (N,Ho,Wo,Cout) fp16.  w8 = (codes, scales): stream the fp8 copy.
+    out: write into this contiguous (N,Ho,Wo,Cout) fp16 tensor instead of a new one."""
     lib = _lib.load()
     _need_cuda(x, w_krsc)
     n, h, w, cin = x.shape
@@ -105,7 +115,7 @@ def conv2d_nhwc(x, w_krsc, bias=None, bias2=None, res=None, stride=1, upsample2x
     pad = k // 2
     ho = (hv + 2 * pad - k) // stride + 1
     wo = (wv + 2 * pad - k) // stride + 1
-    y = torch.empty((n, ho, wo, cout), dtype=torch.float16, device=x.device)
+    y = _out(out, (n, ho, wo, cout), torch.float16, x.device)
     args = (_i(n), _i(h), _i(w), _i(cin), _i(cout), _i(k), _i(stride), _i(int(upsample2x)))
     nb = lib.sdeo_conv2d_workspace_bytes(*args)
     ws = _ws(nb if w8 is None else max(nb, 64 << 20), x.device)
@@ -176,15 +186,15 @@ def conv3x3_gn_in(x, w_krsc, gamma, beta, partials, bias=None, eps=1e-5, swish=T
     return y if ok.value else None
 
 
-def gemm(x, w, bias=None, res=None, act=0, scale=1.0, out_f32=False, bias_per_row=False, w8=None):
+def gemm(x, w, bias=None, res=None, act=0, scale=1.0, out_f32=False, bias_per_row=False, w8=None, out=None):
     """y[m][n] = x[m][k] . w[n][k]^T (+bias)(+res); x, w fp16 row-major (may be strided views with unit inner stride).
-    w8 = (codes, scales): stream the fp8 copy of w instead."""
+    w8 = (codes, scales): stream the fp8 copy of w instead.  out: write into this contiguous (m, n) tensor instead of a new one."""
     lib = _lib.load()
     _need_cuda(x, w)
     m, k = x.shape
     n, k2 = w.shape
     assert k == k2 and x.stride(1) == 1 and w.stride(1) == 1
-    y = torch.empty((m, n), dtype=torch.float32 if out_f32 else torch.float16, device=x.device)
+    y = _out(out, (m, n), torch.float32 if out_f32 else torch.float16, x.device)
     nb = lib.sdeo_gemm_workspace_bytes(_i(m), _i(n), _i(k))
     ws = _ws(nb if w8 is None else max(nb, 64 << 20), x.device)
     _arm_fp8(lib, w8)
@@ -266,15 +276,17 @@ def geglu_interleave(w):
     return torch.cat([v, g], 1).reshape(w.shape).contiguous()
 
 
-def gemm_geglu(x, w_interleaved, bias_interleaved=None):
+def gemm_geglu(x, w_interleaved, bias_interleaved=None, w8=None, out=None):
     """y[m][0:H] = (x w_v^T + b_v) * gelu_erf(x w_g^T + b_g): ff.net.0.proj + GEGLU (`attention.py:49-56`) in one launch.
-    Weights / bias already in `geglu_interleave` order."""
+    Weights / bias already in `geglu_interleave` order.  w8 = (codes, scales) of the interleaved weights: stream the fp8 copy.
+    out: write into this contiguous (m, H) fp16 tensor instead of a new one."""
     lib = _lib.load()
     _need_cuda(x, w_interleaved)
     m, k = x.shape
     n, k2 = w_interleaved.shape
     assert k == k2 and n % 32 == 0 and x.stride(1) == 1 and w_interleaved.stride(1) == 1
-    y = torch.empty((m, n // 2), dtype=torch.float16, device=x.device)
+    y = _out(out, (m, n // 2), torch.float16, x.device)
+    _arm_fp8(lib, w8)
     check(lib.sdeo_gemm_f16(ptr(y), _i(n // 2), ptr(x), _i(x.stride(0)), ptr(w_interleaved), _i(w_interleaved.stride(0)),
                             ptr(bias_interleaved), None, _i(0), _i(m), _i(n), _i(k), _i(3), _f(1.0), _i(0), _i(0), None,
                             C.c_size_t(0), cur_stream()), "gemm_geglu")

@@ -49,9 +49,11 @@ W8_TILES = [1, 2, 6, 9, 19, 20]      # conv_gemm.hip: tile_has_w8
 
 
 @pytest.mark.parametrize("tile", W8_TILES)
-@pytest.mark.parametrize("shape", [(128, 1280, 1280, 1), (512, 640, 1920, 2), (2, 20160, 1280, 1), (100, 324, 640, 4)])
+@pytest.mark.parametrize("shape", [(128, 1280, 1280, 1), (512, 640, 1920, 2), (2, 20160, 1280, 1), (100, 324, 640, 4),
+                                   (128, 1280, 1472, 12)])      # 23 K-steps: 11 slabs of 2 and a last one of 1
 def test_fp8_gemm_bit_identical_to_fp16_on_dequantised_weights(tile, shape):
     from stablediffusioneo_amd import _lib, ops
+    from tests.test_ops_gpu import assert_same_but_order, run_forced
     m, n, k, sk = shape
     lib = _lib.load()
     x = h16(randn((m, k), 40)).to(DEV)
@@ -67,8 +69,12 @@ def test_fp8_gemm_bit_identical_to_fp16_on_dequantised_weights(tile, shape):
         lib.sdeo_debug_force_gemm_plan(C.c_int(-1), C.c_int(0))
     assert torch.isfinite(y8).all()
     assert torch.equal(y8, y16), f"tile {tile} {shape}: {int((y8 != y16).sum())} of {y8.numel()} differ, max {float((y8.float() - y16.float()).abs().max())}"
-    ref = x.float() @ wdeq.float().t() + bias + res.float()
-    assert float((y8.float() - ref).abs().max()) <= 4e-3 * float(ref.abs().max()) + 4e-3
+    ref = x.double() @ wdeq.double().t() + bias.double() + res.double()
+    assert float((y8.double() - ref).abs().max()) <= 4e-3 * float(ref.abs().max()) + 4e-3
+    if sk == 12:
+        y8b, ran = run_forced(tile, sk, lambda: ops.gemm(x, wdeq, bias=bias, res=res, w8=(q, sc)))
+        assert ran == (tile, sk) and torch.equal(y8b, y8), ran
+        assert_same_but_order(y8, run_forced(tile, 1, lambda: ops.gemm(x, wdeq, bias=bias, res=res, w8=(q, sc)))[0], f"fp8 tile {tile} {shape}")
 
 
 @pytest.mark.parametrize("tile,sk", [(9, 4), (2, 2), (6, 1), (20, 8)])

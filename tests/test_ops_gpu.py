@@ -40,6 +40,41 @@ def assert_close(got, ref, rtol=2e-3, atol=2e-3, what=""):
                           f"(ref max {float(ref.abs().max()):.4g})"
 
 
+def ulp16(v):
+    """spacing of fp16 at |v| (2^-24, the subnormal spacing, below the normal range)"""
+    a = v.abs()
+    _, e = torch.frexp(a)
+    return torch.where(a < 2.0 ** -14, torch.full_like(a, 2.0 ** -24), torch.ldexp(torch.ones_like(a), e - 11))
+
+
+SPLITK = [1, 2, 7, 12]    # forced split-K factors of the reduce-epilogue cases (K chosen so each survives make_plan's normalisation)
+
+
+def run_forced(tile, sk, fn):
+    """fn() under the forced plan (tile, sk); returns (its result, the (tile, split-K) the launch ran)"""
+    import ctypes as C
+    from stablediffusioneo_amd import _lib
+    lib = _lib.load()
+    t, k = C.c_int(-1), C.c_int(0)
+    try:
+        lib.sdeo_debug_force_gemm_plan(C.c_int(tile), C.c_int(sk))
+        y = fn()
+        lib.sdeo_debug_last_gemm_plan(C.byref(t), C.byref(k))
+    finally:
+        lib.sdeo_debug_force_gemm_plan(C.c_int(-1), C.c_int(0))
+    return y, (t.value, k.value)
+
+
+def assert_same_but_order(got, unsplit, what):
+    """a split-K result against the same call at split-K 1 on the same tile: they differ only in fp32 summation order, so every
+    element is within 1 fp16 ulp (+ 1e-6: near zero the reordering error of O(1) partial sums, ~1e-7, exceeds the 6e-8
+    subnormal spacing).  A slab or epilogue rounded through fp16 is off by a fraction of an ulp of the slab: far beyond 1e-6."""
+    got, unsplit = got.detach().double(), unsplit.detach().double()
+    err = (got - unsplit).abs()
+    bad = ~(err <= ulp16(unsplit) + 1e-6)
+    assert not bad.any(), f"{what}: {int(bad.sum())}/{bad.numel()} differ from split-K 1 by more than 1 ulp, max {float(err.max()):.3g}"
+
+
 # ------------------------------------------------------------------ GroupNorm
 
 GN_SHAPES = [  # (N, C, H, W): every (C, level) of SURVEY.md App. A that matters + VAE + odd sizes
@@ -167,25 +202,30 @@ def test_gemm_grouped_barrier_tiles_every_k(ops, tile):
 
 
 @pytest.mark.parametrize("tile", DMA_TILES)
-@pytest.mark.parametrize("sk", [1, 3])
+@pytest.mark.parametrize("sk", [1, 2, 3, 7, 12])
 def test_conv2d_every_dma_tile(ops, tile, sk):
-    """every LDS-DMA tile shape (forced), with and without split-K, on ragged M / N and on the folded upsample"""
-    import ctypes as C
-    from stablediffusioneo_amd import _lib
-    lib = _lib.load()
-    try:
-        lib.sdeo_debug_force_gemm_plan(C.c_int(tile), C.c_int(sk))
-        for (n, cin, h, w, cout, ups) in [(2, 128, 13, 11, 328, 0), (1, 64, 9, 10, 160, 1), (2, 192, 8, 8, 72, 0)]:
-            x = h16(randn((n, cin, h, w), 230 + cin))
-            wt = h16(randn((cout, cin, 3, 3), 231) * (1.0 / (cin * 9)) ** 0.5)
-            bias = 0.1 * randn((cout,), 232)
-            xin = F.interpolate(x.float(), scale_factor=2, mode="nearest") if ups else x.float()
-            ref = F.conv2d(xin, wt.float(), bias, padding=1)
-            y = ops.conv2d_nhwc(x.permute(0, 2, 3, 1).contiguous().to(DEV), wt.permute(0, 2, 3, 1).contiguous().to(DEV),
-                                bias.to(DEV), upsample2x=bool(ups))
-            assert_close(y.permute(0, 3, 1, 2), ref, rtol=2e-3, atol=3e-3, what=f"tile {tile} sk {sk} conv {(n, cin, h, w, cout, ups)}")
-    finally:
-        lib.sdeo_debug_force_gemm_plan(C.c_int(-1), C.c_int(0))
+    """every LDS-DMA tile shape (forced), with and without split-K, on ragged M / N and on the folded upsample, with the per-image
+    bias2.  The last case (three 8x8 images, K = 9 x 320 = 45 K-steps) keeps every split-K factor, each with a short last slab,
+    and its 128- and 256-row M-tiles straddle images, so bias2 must be picked per row (m / HoWo), in the unsplit epilogue and
+    in the split-K reduce alike; it is also checked against the same tile at split-K 1."""
+    for (n, cin, h, w, cout, ups) in [(2, 128, 13, 11, 328, 0), (1, 64, 9, 10, 160, 1), (2, 192, 8, 8, 72, 0), (3, 320, 8, 8, 200, 0)]:
+        x = h16(randn((n, cin, h, w), 230 + cin))
+        wt = h16(randn((cout, cin, 3, 3), 231) * (1.0 / (cin * 9)) ** 0.5)
+        bias = 0.1 * randn((cout,), 232)
+        bias2 = 0.3 * randn((n, cout), 233)
+        xin = F.interpolate(x.double(), scale_factor=2, mode="nearest") if ups else x.double()
+        ref = F.conv2d(xin, wt.double(), bias.double(), padding=1) + bias2.double()[:, :, None, None]
+        xd, wd = x.permute(0, 2, 3, 1).contiguous().to(DEV), wt.permute(0, 2, 3, 1).contiguous().to(DEV)
+
+        def run(s):
+            return run_forced(tile, s, lambda: ops.conv2d_nhwc(xd, wd, bias.to(DEV), bias2.to(DEV), upsample2x=bool(ups)))
+        y, ran = run(sk)
+        what = f"tile {tile} sk {sk} conv {(n, cin, h, w, cout, ups)}"
+        assert_close(y.permute(0, 3, 1, 2), ref, rtol=2e-3, atol=3e-3, what=what)
+        if cin == 320:
+            assert ran == (tile, sk), f"{what}: ran {ran}"
+            if sk > 1:
+                assert_same_but_order(y, run(1)[0], what)
 
 
 HALO_TILES = {13: (8, 16, 80, 4), 14: (8, 16, 160, 4), 15: (8, 8, 80, 4), 16: (8, 8, 160, 4), 17: (8, 16, 64, 4), 18: (8, 16, 128, 4),
@@ -285,14 +325,50 @@ def test_gemm(ops, m, n, k):
 
 
 def test_gemm_f32_out_bias_per_row(ops):
-    m, n, k = 64, 200, 128
-    x = h16(randn((m, k), 310))
-    w = h16(randn((n, k), 311) * (1.0 / k) ** 0.5)
-    bias = randn((m,), 312)
-    ref = x.float() @ w.float().t() + bias[:, None]
-    y = ops.gemm(x.to(DEV), w.to(DEV), bias.to(DEV), out_f32=True, bias_per_row=True)
-    assert y.dtype == torch.float32
-    assert_close(y, ref, rtol=1e-4, atol=1e-4, what="gemm f32 out")
+    """fp32 output with a per-row bias; sk > 0: forced split-K on tile 6 (the reduce applies both), K = 1280 / 1472 leaving the
+    last slab short at 7 / 12"""
+    m, n = 64, 200
+    for k, sk in [(128, 0)] + [(1280, s) for s in SPLITK[:3]] + [(1472, SPLITK[3])]:
+        x = h16(randn((m, k), 310))
+        w = h16(randn((n, k), 311) * (1.0 / k) ** 0.5)
+        bias = randn((m,), 312)
+        ref = x.double() @ w.double().t() + bias.double()[:, None]
+
+        def run():
+            return ops.gemm(x.to(DEV), w.to(DEV), bias.to(DEV), out_f32=True, bias_per_row=True)
+        if sk == 0:
+            y = run()
+        else:
+            y, ran = run_forced(6, sk, run)
+            assert ran == (6, sk), ran
+        assert y.dtype == torch.float32
+        assert_close(y, ref, rtol=1e-4, atol=1e-4, what=f"gemm f32 out K {k} sk {sk}")
+        if sk > 1:
+            assert_same_but_order(y, run_forced(6, 1, run)[0], f"gemm f32 out K {k} sk {sk}")
+
+
+@pytest.mark.parametrize("k,sk", [(320, 0)] + [(1280, s) for s in SPLITK[:3]] + [(1536, SPLITK[3])])
+def test_gemm_quick_gelu_scale(ops, k, sk):
+    """act 2 (quick-GELU, CLIP's MLP) and an output scale ahead of the residual; sk > 0: forced split-K on tile 0, the reduce
+    applies them"""
+    m, n = 96, 328
+    x = h16(randn((m, k), 320))
+    w = h16(randn((n, k), 321) * (1.0 / k) ** 0.5)
+    bias = 0.1 * randn((n,), 322)
+    res = h16(randn((m, n), 323))
+    lin = x.double() @ w.double().t() + bias.double()
+    ref = lin * torch.sigmoid(1.702 * lin) * 0.625 + res.double()
+
+    def run():
+        return ops.gemm(x.to(DEV), w.to(DEV), bias.to(DEV), res.to(DEV), act=2, scale=0.625)
+    if sk == 0:
+        y = run()
+    else:
+        y, ran = run_forced(0, sk, run)
+        assert ran == (0, sk), ran
+    assert_close(y, ref, rtol=2e-3, atol=3e-3, what=f"gemm quick-GELU K {k} sk {sk}")
+    if sk > 1:
+        assert_same_but_order(y, run_forced(0, 1, run)[0], f"gemm quick-GELU K {k} sk {sk}")
 
 
 @pytest.mark.parametrize("m,c", [(8192, 320), (2048, 640), (512, 1280), (128, 1280), (130, 64), (77, 32)])
@@ -329,10 +405,12 @@ def test_geglu(ops, rows, c):
     assert_close(ops.geglu(a.to(DEV)), ref, what="geglu")
 
 
-LN_CASES = [  # (rows, C, N of the consuming Linear, act, residual on the producer)
+LN_CASES = [  # (rows, C, N of the consuming Linear, act, residual on the producer[, forced split-K on tile 6])
     (200, 320, 960, 0, True), (8192, 320, 960, 0, True), (512, 1280, 1280, 0, True), (128, 1280, 3840, 0, False),
     (130, 64, 192, 0, True), (256, 96, 128, 0, False), (300, 320, 2560, 3, True), (2048, 640, 5120, 3, True),
-]
+    (32, 1280, 1280, 0, True),      # to_q of the 4x4 level at the 32x32 latent: its tuned plan is split-K 5 (the reduce applies the fold)
+] + [(512, 1280, 1280, 0, True, sk) for sk in SPLITK[:3]] + [(256, 1472, 1280, 0, True, SPLITK[3])]
+# (C = 1280 is 20 K-steps: slabs 10+10 at split-K 2, 6x3+2 at 7; C = 1472 is 23: 11x2+1 at 12)
 
 
 @pytest.mark.parametrize("case", LN_CASES)
@@ -340,7 +418,8 @@ def test_gemm_with_folded_layernorm(ops, case):
     """BasicTransformerBlock's x + f(LN(x)) (`attention.py:381-385`) as the networks run it: the GEMM that writes x also
     writes x's per-row (sum, sumsq); the consuming Linear runs on the raw x with LayerNorm folded in (gamma into the weights,
     mean / rstd in the epilogue).  Reference: fp32 F.layer_norm + F.linear on the fp16 tensor the producer stored."""
-    rows, c, n, act, with_res = case
+    rows, c, n, act, with_res = case[:5]
+    sk = case[5] if len(case) > 5 else 0
     x0 = h16(randn((rows, c), 700)).to(DEV)
     w0 = h16(randn((c, c), 701) * c ** -0.5).to(DEV)
     b0 = (randn((c,), 702) * 0.1).to(DEV)
@@ -359,11 +438,20 @@ def test_gemm_with_folded_layernorm(ops, case):
     else:
         w1d, b1d = w1.to(DEV), b1
     wf, s, bf = ops.fold_layernorm(w1d, gamma, beta, b1d)
-    y = ops.gemm_layernorm(tok, stats, strips, wf, s, bf, act=act)
-    lin = F.linear(F.layer_norm(tf, (c,), gamma, beta, 1e-5), w1.to(DEV).float(), b1)
+
+    def run():
+        return ops.gemm_layernorm(tok, stats, strips, wf, s, bf, act=act)
+    if sk == 0:
+        y = run()
+    else:
+        y, ran = run_forced(6, sk, run)
+        assert ran == (6, sk), ran
+    lin = F.linear(F.layer_norm(tf.double(), (c,), gamma.double(), beta.double(), 1e-5), w1.to(DEV).double(), b1.double())
     ref = lin if act != 3 else lin[:, : n // 2] * F.gelu(lin[:, n // 2:])
     # two fp16 roundings on the folded weights (W, then W * gamma) instead of one on W and one on LN(x)
-    assert_close(y, ref, rtol=4e-3, atol=4e-3, what=f"LayerNorm-folded GEMM {case}")
+    assert_close(y, ref, rtol=4e-3, atol=4e-3, what=f"LayerNorm-folded GEMM {case} sk {sk}")
+    if sk > 1:
+        assert_same_but_order(y, run_forced(6, 1, run)[0], f"LayerNorm-folded GEMM {case} sk {sk}")
 
 
 @pytest.mark.parametrize("case", [(256, 64), (512, 320), (96, 640)], ids=str)
