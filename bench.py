@@ -1,6 +1,6 @@
 """bench.py -- headline benchmark of the MI355X-native canny2image hot path (BASELINE.json configs[1]).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -13,7 +13,10 @@ gathered once with RCCL inside the timed region.  Rank 0 prints ONE JSON line; `
 --dump-outputs DIR writes what the last timed step returned on rank 0 -- the final latents (latent.npy) and the uint8 image
 (image.npy) -- as float32 .npy files; the inputs (weights, x_T, hint, contexts) are seeded, so two builds can be compared file by file.
 
-Extra objects on that line:
+A plain run does only what that line's headline needs: set up, warm up, time the steps, dump the outputs when asked, print.
+--full adds everything else the benchmark measures or checks, after the timed region and without changing it:
+  output_check -- the final latent of image 0 against the reference golden tests/golden/sd15_full.npz (default sd15 workload);
+  fp8_check    -- with --fp8, one N=2 pass against the reference modules on the same fp8-dequantised weights;
   roofline     -- the conv / GEMM kernel family of one profiled image (the group holding most of the device time): algorithmic FLOPs
                   of its launches / their summed HIP-event durations, against the dense fp16 MFMA peak (2.5 PFLOP/s); `traffic` =
                   HBM-side bytes of one DDIM step from the committed rocprofv3 --pmc passes (profiles/r0N_step_counters.json);
@@ -52,8 +55,11 @@ def parse():
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--ddim-steps", type=int, default=20)
     ap.add_argument("--scale", type=float, default=9.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the reference checks (output_check, fp8_check), the profiled image (roofline) "
+                         "and the CPU baseline; the headline figures are the same with or without it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the profiled image (roofline, --dump-profile)")
     ap.add_argument("--config", default="sd15", choices=["sd15", "tiny"])
     ap.add_argument("--fp8", action="store_true",
                     help="BASELINE configs[4]: UNet / ControlNet matrices packed to fp8 e4m3fn (per-output-channel scales), fp16 activations")
@@ -65,11 +71,15 @@ def parse():
     ap.add_argument("--fast-weights", action="store_true",
                     help="draw the synthetic weights with the device generator (seconds faster to start; NOT the parity-tested weights, "
                          "so the reference-golden check of the output is skipped)")
-    ap.add_argument("--dump-profile", default="", help="write the full per-(kernel, shape) table of the profiled image to this JSON file")
+    ap.add_argument("--dump-profile", default="",
+                    help="with --full: write the full per-(kernel, shape) table of the profiled image to this JSON file")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps write what the last timed step returned (final latents, uint8 image) as DIR/<name>.npy "
                          "(float32, rank 0; at most 64 MB in all, a fixed seeded sample of a larger array)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.dump_profile and (not a.full or a.no_roofline):
+        ap.error("--dump-profile needs the profiled image of --full (and no --no-roofline)")
+    return a
 
 
 DUMP_BUDGET = 64 << 20
@@ -274,7 +284,7 @@ def main():
     # own DDIMSampler + ControlLDM.apply_model produced in tests/golden/sd15_full.npz (same weights, x_T, hint, contexts)
     golden_check = None
     gpath = os.path.join(ROOT, "tests", "golden", "sd15_full.npz")
-    if (rank == 0 and not a.fast_weights and not a.fp8 and a.config == "sd15" and (a.res, a.ddim_steps, a.scale) == (512, 20, 9.0)
+    if (a.full and rank == 0 and not a.fast_weights and not a.fp8 and a.config == "sd15" and (a.res, a.ddim_steps, a.scale) == (512, 20, 9.0)
             and os.path.exists(gpath)):
         import numpy as np
         zref = torch.tensor(np.load(gpath)["traj64.z"])
@@ -286,7 +296,7 @@ def main():
 
     fp8_check = None
     fpath = os.path.join(ROOT, "tests", "golden", "sd15_fp8.npz")
-    if rank == 0 and a.fp8 and not a.fast_weights and a.config == "sd15" and a.res == 512 and os.path.exists(fpath):
+    if a.full and rank == 0 and a.fp8 and not a.fast_weights and a.config == "sd15" and a.res == 512 and os.path.exists(fpath):
         # distance of ONE pass (N = 2, t = 951) to the reference modules run in fp32 on the same fp8-dequantised weights
         # (tests/golden/make_golden_full.py --only pass64_fp8): what is left is the activation precision (fp16, or block-scaled fp8 with --mx)
         import numpy as np
@@ -306,7 +316,7 @@ def main():
                      "mean_abs_err_over_ref_max": round(float(err.mean() / ref.abs().max()), 6),
                      "gemm_launches_on_fp8_mfma_in_configured_programs": int(L.load().sdeo_debug_mx_launches(rt.handle))}      # ControlNet + UNet (+ the no-control UNet variant)
     roof = None
-    if not a.no_roofline and rank == 0:
+    if a.full and not a.no_roofline and rank == 0:
         import stablediffusioneo_amd.cldm.ddim_hacked as dh
         dh.USE_GRAPH = False          # events are recorded around eager launches only (a graph replay has no host-side hooks)
         rt.profile_begin()
@@ -399,7 +409,7 @@ def main():
             out["fp8_check"] = fp8_check
         if roof:
             out["roofline"] = roof
-        if world == 1 and not a.no_cpu_baseline and a.config == "sd15":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.config == "sd15":
             out["cpu_baseline"] = cpu_baseline(a.res, a.ddim_steps, a.scale)
         print(json.dumps(out), flush=True)
     if dist:

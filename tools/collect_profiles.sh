@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/kt.err
+rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/kt.err
 echo "kernel-trace rc=$?"
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c -d $OUT/attn_$c -o p -- python3 $R/tools/one_attn.py 4096 40 5 > /dev/null 2> $OUT/attn_$c.err; echo "attn $c rc=$?"

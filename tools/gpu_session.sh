@@ -4,7 +4,7 @@
 #
 # steps:  pytest            all -m gpu tests                              -> pytest.log
 #         pytest:<expr>     -m gpu tests selected with -k <expr>          -> pytest_<n>.log
-#         bench             bench.py --steps 5 --warmup 1 with roofline + cpu baseline + per-shape dump -> bench.json, profile.json
+#         bench             bench.py --steps 5 --warmup 1 --full: roofline + cpu baseline + per-shape dump -> bench.json, profile.json
 #         quick[:flags]     bench.py --steps 3 --warmup 1 --no-cpu-baseline --fast-weights --no-roofline [flags, comma separated]
 #         ab:<ENV=V>        the quick bench twice, without and with the environment setting (same box A/B)
 #         profile[:flags]   per-(kernel, shape) table of one eagerly profiled image (in-library HIP events) -> profile_<n>.json
@@ -23,16 +23,16 @@ cd $R
 N=0
 step() { echo "=== $1"; shift; "$@"; rc=$?; echo "=== rc=$rc"; if [ $rc -ge 124 ]; then echo "killed: stopping"; exit $rc; fi; return 0; }
 s_pytest() { timeout -k 10 1100 python -m pytest tests -m gpu -q -s ${1:+-k "$1"} > $OUT/pytest${2}.log 2>&1; rc=$?; tail -5 $OUT/pytest${2}.log; return $rc; }
-s_bench() { timeout -k 10 700 python bench.py --steps 5 --warmup 1 --dump-profile $OUT/profile.json > $OUT/bench.json 2> $OUT/bench.err; rc=$?; head -c 600 $OUT/bench.json; echo; tail -2 $OUT/bench.err; return $rc; }
+s_bench() { timeout -k 10 700 python bench.py --steps 5 --warmup 1 --full --dump-profile $OUT/profile.json > $OUT/bench.json 2> $OUT/bench.err; rc=$?; head -c 600 $OUT/bench.json; echo; tail -2 $OUT/bench.err; return $rc; }
 s_quick() { name=$1; shift; timeout -k 10 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --fast-weights --no-roofline "$@" > $OUT/quick_$name.json 2> $OUT/quick_$name.err; rc=$?
   python -c "
 import json; b=json.load(open('$OUT/quick_$name.json')); print('quick $name', b['value'], 'img/s', b.get('ms_per_unet_step'), 'ms/step')"; return $rc; }
-s_profile() { timeout -k 10 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --fast-weights --dump-profile $OUT/profile_$1.json "${@:2}" > $OUT/profile_bench_$1.json 2> $OUT/profile_$1.err; rc=$?
+s_profile() { timeout -k 10 400 python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --fast-weights --dump-profile $OUT/profile_$1.json "${@:2}" > $OUT/profile_bench_$1.json 2> $OUT/profile_$1.err; rc=$?
   python -c "
 import json; d=json.load(open('$OUT/profile_$1.json')); tot=sum(x['total_ms'] for x in d); n=sum(x['launches'] for x in d)
 print('profile: %.1f ms eager per image, %d launches' % (tot, n))
 for x in d[:40]: print('%-64s n=%5d ms=%7.2f us=%6.1f' % (x['kernel'][:64], x['launches'], x['total_ms'], 1e3*x['total_ms']/x['launches']))"; return $rc; }
-s_kt() { cd /tmp; export TMPDIR=/tmp; timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline > $OUT/bench_under_rocprof.json 2> $OUT/kt.err; rc=$?; cd $R
+s_kt() { cd /tmp; export TMPDIR=/tmp; timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-roofline > $OUT/bench_under_rocprof.json 2> $OUT/kt.err; rc=$?; cd $R
   tail -2 $OUT/kt.err; db=$(find $OUT/kt -name "*.db" | head -1)
   python tools/rocpd_summary.py stats $db $OUT/kernel_stats.csv > $OUT/kernel_stats.txt 2>&1; python tools/timeline.py $db 9200 > $OUT/timeline.txt 2>&1
   find $OUT/kt -name "*.db" -size +20M -delete; return $rc; }
@@ -81,7 +81,7 @@ for st in "$@"; do
     pmc_graph_only) step pmc_graph_only s_pmc_mode graph_only ;;
     pmc_overlap_only) step pmc_overlap_only s_pmc_mode overlap_only ;;
     pmc_both) step pmc_both s_pmc_mode both ;;
-    benchx:*) a=${st#benchx:}; nm=$(echo $a | tr -d ',-' | cut -c1-30); step "$st" bash -c "timeout -k 10 500 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline $(echo $a | tr ',' ' ') > $OUT/benchx_$nm.json 2> $OUT/benchx_$nm.err; rc=\$?; head -c 900 $OUT/benchx_$nm.json; echo; exit \$rc" ;;
+    benchx:*) a=${st#benchx:}; nm=$(echo $a | tr -d ',-' | cut -c1-30); step "$st" bash -c "timeout -k 10 500 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-roofline $(echo $a | tr ',' ' ') > $OUT/benchx_$nm.json 2> $OUT/benchx_$nm.err; rc=\$?; head -c 900 $OUT/benchx_$nm.json; echo; exit \$rc" ;;
     py:*) a=${st#py:}; step "$st" bash -c "timeout -k 10 600 python $(echo $a | tr ',' ' ') > $OUT/py_$N.log 2>&1; rc=\$?; tail -25 $OUT/py_$N.log; exit \$rc" ;;
     *) echo "unknown step $st" ;;
   esac
