@@ -67,7 +67,8 @@ int sdeo_groupnorm_nhwc_f16(void* y, const void* x, const float* gamma, const fl
 /* conv2d on NHWC fp16 activations with KRSC fp16 weights (implicit GEMM on MFMA).
  *   y[n][ho][wo][cout] = act( conv(x, w) + bias[cout] + bias2[n][cout] ) * scale + res[n][ho][wo][cout]
  * cin/cout are the STORED channel counts (cin % 8 == 0, cout % 4 == 0); upsample2x=1 folds a nearest x2
- * upsample of x in front of the conv.  bias/bias2 fp32 or NULL, res fp16 NHWC or NULL. act: 0 none, 1 SiLU.
+ * upsample of x in front of the conv.  bias/bias2 fp32 or NULL, res fp16 NHWC or NULL. act: 0 none, 1 SiLU,
+ * 4 ReLU (plans exactly like act 0).  sdeo_conv2d_pad_nhwc_f16 and sdeo_gemm_f16 take the same codes (sdeo_gemm_f16 also 2 = quick-GELU).
  * workspace (split-K partials): >= sdeo_conv2d_workspace_bytes(...) bytes, may be NULL when that is 0. */
 size_t sdeo_conv2d_workspace_bytes(int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x);
 int sdeo_conv2d_nhwc_f16(void* y, const void* x, const void* w_krsc, const float* bias, const float* bias2, const void* res,
@@ -301,6 +302,29 @@ int sdeo_clip_configure(sdeo_clip_handle h, int batch);
  * vocabulary are clamped */
 int sdeo_clip_encode(sdeo_clip_handle h, const int32_t* tokens, int batch, float* out, void* stream);
 size_t sdeo_clip_device_bytes(sdeo_clip_handle h);
+
+/* ------------------------------------------------------------------ HED soft-edge annotator
+ * annotator/hed/__init__.py (ControlNetHED_Apache2 + HEDdetector.__call__): x - norm, five VGG blocks of 3x3 convs + ReLU (2, 2, 3, 3,
+ * 3 convs; 64, 128, 256, 512, 512 channels) with a 2x2 / stride-2 max-pool in front of blocks 2..5 and a 1x1 projection to one
+ * channel behind each block; the five projections resized bilinearly to H x W (cv2.resize INTER_LINEAR on float32 =
+ * F.interpolate(mode="bilinear", align_corners=False)), averaged, passed through a sigmoid and stored as uint8 (truncated).
+ * Tensor names are those of the reference state dict (= ControlNetHED.pth): "norm" (1,3,1,1), "block{1..5}.convs.{i}.weight/bias",
+ * "block{1..5}.projection.weight/bias"; 37 tensors.  One image per call, any H, W >= 16 (floor pooling). */
+typedef struct sdeo_hed_handle_s* sdeo_hed_handle;
+int sdeo_hed_create(sdeo_hed_handle* out);
+int sdeo_hed_destroy(sdeo_hed_handle h);
+int sdeo_hed_num_weights(sdeo_hed_handle h);
+int sdeo_hed_weight_info(sdeo_hed_handle h, int i, const char** name, int64_t dims[4], int* ndim);
+/* host_data: fp32 in PyTorch layout, host or device pointer; unknown names are ignored unless strict */
+int sdeo_hed_load_weight(sdeo_hed_handle h, const char* name, const float* host_data, const int64_t* dims, int ndim, int strict);
+int sdeo_hed_finalize_weights(sdeo_hed_handle h);
+/* fix the image size (one image of height x width, both >= 16) and allocate the activation arena and split-K workspace once */
+int sdeo_hed_configure(sdeo_hed_handle h, int height, int width);
+/* img_hwc: device uint8 [H][W][3] RGB.  Outputs (each may be NULL, all device): edges uint8 [H][W]; control_chw fp32 [3][H][W] =
+ * edges / 255 on three identical channels (as sdeo_canny_u8); side[5]: fp32 [h_k][w_k] projection maps of the five blocks (h_1 = H,
+ * h_{k+1} = h_k / 2 rounded down), before the resize.  No allocation, no synchronisation: capturable. */
+int sdeo_hed_detect_u8(sdeo_hed_handle h, const uint8_t* img_hwc, uint8_t* edges, float* control_chw, float* const* side, void* stream);
+size_t sdeo_hed_device_bytes(sdeo_hed_handle h);
 
 /* Per-kernel timing for bench.py's roofline: between begin and end every launch of the net-level calls is
  * bracketed by HIP events on the stream it runs on; end synchronises the device and returns a JSON array

@@ -68,10 +68,11 @@ def load(path: str = LIB_PATH):
                         f"(operand semantics changed between versions)")
     lib.sdeo_last_error.restype = C.c_char_p
     for name in ("sdeo_groupnorm_workspace_bytes", "sdeo_conv2d_workspace_bytes", "sdeo_conv2d_pad_workspace_bytes", "sdeo_gemm_workspace_bytes",
-                 "sdeo_device_bytes", "sdeo_clip_device_bytes"):
+                 "sdeo_device_bytes", "sdeo_clip_device_bytes", "sdeo_hed_device_bytes"):
         getattr(lib, name).restype = C.c_size_t
     lib.sdeo_device_bytes.argtypes = [C.c_void_p]
     lib.sdeo_clip_device_bytes.argtypes = [C.c_void_p]
+    lib.sdeo_hed_device_bytes.argtypes = [C.c_void_p]
     lib.sdeo_tuned_gemm_plans_json.restype = C.c_char_p
     _lib = lib
     load_tuned_plans(lib)

@@ -47,6 +47,10 @@ class hackathon():
         tokenizer is then the crc32 stand-in, which is meaningless next to real weights); or any callable(prompts) ->
         (B, 77, 768) tensor.  vae_encoder=True also builds the VAE encoder, which `process(init_image=...)` (img2img) needs."""
         self.apply_canny = apply_canny or _default_canny()
+        return self._init_model(weights, config, text_encoder, vae_encoder)
+
+    def _init_model(self, weights, config, text_encoder, vae_encoder=False):
+        """text encoder, ControlLDM and DDIM sampler of `initialize` (shared with hed2image)"""
         if isinstance(text_encoder, str) and text_encoder.split(":")[0] == "clip":
             from . import spec as S
             from .ldm.modules.encoders.modules import FrozenCLIPEmbedder
@@ -87,6 +91,14 @@ class hackathon():
                 control = torch.from_numpy(detected_map.copy()).float().to(device) / 255.0
                 control = torch.stack([control for _ in range(num_samples)], dim=0)
                 control = control.permute(0, 3, 1, 2).contiguous()
+            return self._sample(control, prompt, a_prompt, n_prompt, num_samples, H, W, ddim_steps, guess_mode, strength, scale, seed, eta,
+                                x_T=x_T, init_image=init_image, image_resolution=image_resolution, denoise_strength=denoise_strength)
+
+    def _sample(self, control, prompt, a_prompt, n_prompt, num_samples, H, W, ddim_steps, guess_mode, strength, scale, seed, eta, x_T=None,
+                init_image=None, image_resolution=None, denoise_strength=0.75):
+        """everything of `process` after the hint (`canny2image_torch.py:40-71`): seeding, conditioning, the DDIM loop and the decode
+        to uint8 HWC images; control is the (num_samples, 3, H, W) fp32 hint on the device"""
+        with torch.no_grad():
             if seed == -1:
                 seed = random.randint(0, 65535)
             random.seed(seed)

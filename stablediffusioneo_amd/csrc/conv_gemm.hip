@@ -723,6 +723,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const KP2 pp) {
   } else if (p.act == 2) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) v[t] = quick_gelu_f(v[t]);
+  } else if (p.act == 4) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) v[t] = fmaxf(v[t], 0.f);
   }
   v *= p.scale;
 #pragma unroll
@@ -1025,6 +1028,7 @@ static int launch_dma_light(int ups, const KP2& kp, int count, int tiles, hipStr
 static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
   SDEO_CHECK(p.x && p.w && (p.y || p.y32), "conv_gemm: null operand");
   SDEO_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "conv_gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
+  SDEO_CHECK(p.act >= 0 && p.act <= 4, "conv_gemm: act=%d unsupported (0 none, 1 SiLU, 2 quick-GELU, 3 GEGLU pair, 4 ReLU)", p.act);
   SDEO_CHECK(p.N % 4 == 0, "conv_gemm: N=%d must be a multiple of 4", p.N);
   SDEO_CHECK(p.Cin % 8 == 0 && p.ldx % 8 == 0 && p.ldw % 8 == 0, "conv_gemm: Cin=%d ldx=%d ldw=%d must be multiples of 8",
              p.Cin, p.ldx, p.ldw);

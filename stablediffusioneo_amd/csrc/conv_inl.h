@@ -182,6 +182,9 @@ __device__ __forceinline__ void stage_block(const KP& p, const f32x4 (&accj)[NI]
     } else if (ACT == 2) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) v[t] = quick_gelu_f(v[t]);
+    } else if (ACT == 4) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) v[t] = fmaxf(v[t], 0.f);
     }
     v *= p.scale;
     *reinterpret_cast<f32x4*>(scratch + frow * ROWB + (i * 16 + fq * 4) * 4) = v;
@@ -323,7 +326,7 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
       nn[t] = nb + (id - rr[t] * G) * 8;
       live[t] = id < 16 * G && nn[t] < p.N;
     }
-    const int mode = (p.bias2 ? 3 : 0) + p.act;   // act is 0..2 here (3 = GEGLU never takes this path)
+    const int mode = (p.bias2 ? 8 : 0) | p.act;   // act is 0, 1, 2 or 4 here (3 = GEGLU never takes this path)
     // GroupNorm partials (KP::gn_out): lane c (and c + 64 ...) sums column c of every stored block, read back from an fp16 copy of
     // the block in LDS -- two registers per column instead of sixteen per (row, vector) slot
     constexpr int GCH = (TN + 63) / 64;
@@ -366,9 +369,11 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
           case 0: stage_block<NI, TN, false, 0>(p, accj, bias, m, nb, fq, frow, sc); break;
           case 1: stage_block<NI, TN, false, 1>(p, accj, bias, m, nb, fq, frow, sc); break;
           case 2: stage_block<NI, TN, false, 2>(p, accj, bias, m, nb, fq, frow, sc); break;
-          case 3: stage_block<NI, TN, true, 0>(p, accj, bias, m, nb, fq, frow, sc); break;
-          case 4: stage_block<NI, TN, true, 1>(p, accj, bias, m, nb, fq, frow, sc); break;
-          default: stage_block<NI, TN, true, 2>(p, accj, bias, m, nb, fq, frow, sc); break;
+          case 4: stage_block<NI, TN, false, 4>(p, accj, bias, m, nb, fq, frow, sc); break;
+          case 8: stage_block<NI, TN, true, 0>(p, accj, bias, m, nb, fq, frow, sc); break;
+          case 9: stage_block<NI, TN, true, 1>(p, accj, bias, m, nb, fq, frow, sc); break;
+          case 10: stage_block<NI, TN, true, 2>(p, accj, bias, m, nb, fq, frow, sc); break;
+          default: stage_block<NI, TN, true, 4>(p, accj, bias, m, nb, fq, frow, sc); break;
         }
       }
       __builtin_amdgcn_wave_barrier();
@@ -492,6 +497,9 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
       } else if (p.act == 2) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) v[t] = quick_gelu_f(v[t]);
+      } else if (p.act == 4) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = fmaxf(v[t], 0.f);
       }
       v *= p.scale;
       if (p.res) {

@@ -1,0 +1,514 @@
+// HED soft-edge annotator (`annotator/hed/__init__.py`: ControlNetHED_Apache2 + HEDdetector.__call__) on gfx950:
+//   h = x - norm;  block k: [2x2 / stride-2 max-pool for k >= 2] -> n_k x (conv3x3 + ReLU) -> projection conv1x1 C_k -> 1
+//   edge = uint8(clip(255 sigmoid(mean_k resize_bilinear(projection_k, H x W)), 0, 255))      (truncated, like .astype(np.uint8))
+// The thirteen 3x3 convs run on the implicit-GEMM / halo kernels of conv_gemm.hip with the ReLU epilogue (ConvGemm::act = 4).  The
+// kernels of this file are the memory-bound pieces around them, one thread (or eight lanes) per pixel:
+//   hed_intake_kernel    uint8 RGB HWC -> fp16 NHWC, 8 stored channels, v = (float)u - norm[c] rounded once (the first conv's zero
+//                        padding pads x - norm, so the subtraction happens here)
+//   maxpool2x2_kernel    F.max_pool2d(kernel 2, stride 2) on NHWC fp16, floor semantics (an odd last row / column is dropped); exact
+//   side_proj_kernel     the 1x1 projection C -> 1 + bias into an fp32 map (eight lanes per pixel, 16-byte loads, one read of the
+//                        block output)
+//   hed_fuse_kernel      cv2.resize INTER_LINEAR on float32 (= F.interpolate bilinear, align_corners=False) of the five maps at each
+//                        output pixel, fp32 mean in numpy's order, fp64 sigmoid, truncation to uint8 (+ optional control tensor)
+#include <map>
+#include <string>
+#include <vector>
+#include <functional>
+
+#include "../../include/sdeo.h"
+#include "kernels.h"
+
+using namespace sdeo;
+
+namespace sdeo {
+
+static inline dim3 grid_px(int64_t work_items) {
+  int64_t b = cdiv64(work_items, 256);
+  if (b > 8192) b = 8192;
+  if (b < 1) b = 1;
+  return dim3((unsigned)b);
+}
+
+__global__ __launch_bounds__(256) void hed_intake_kernel(f16* __restrict__ y, const uint8_t* __restrict__ img,
+                                                         const float* __restrict__ norm, int64_t HW) {
+  const float n0 = norm[0], n1 = norm[1], n2 = norm[2];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < HW; i += (int64_t)gridDim.x * 256) {
+    const uint8_t* px = img + i * 3;
+    f16x8 o = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    o[0] = (f16)((float)px[0] - n0);
+    o[1] = (f16)((float)px[1] - n1);
+    o[2] = (f16)((float)px[2] - n2);
+    *reinterpret_cast<f16x8*>(y + i * 8) = o;
+  }
+}
+
+int hed_intake(f16* y, const uint8_t* img, const float* norm, int H, int W, hipStream_t stream) {
+  SDEO_CHECK(y && img && norm && H > 0 && W > 0, "hed_intake: bad operand");
+  const int64_t HW = (int64_t)H * W;
+  hipLaunchKernelGGL(hed_intake_kernel, grid_px(HW), dim3(256), 0, stream, y, img, norm, HW);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
+// one thread per (output pixel, 8-channel group); the four source pixels exist for every output pixel (floor semantics)
+__global__ __launch_bounds__(256) void maxpool2x2_kernel(f16* __restrict__ y, const f16* __restrict__ x, int Hi, int Wi, int C) {
+  const int Ho = Hi / 2, Wo = Wi / 2, G = C / 8;
+  const int64_t total = (int64_t)Ho * Wo * G;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int g = (int)(i % G);
+    const int64_t p = i / G;
+    const int wo = (int)(p % Wo), ho = (int)(p / Wo);
+    const f16* s = x + ((int64_t)(2 * ho) * Wi + 2 * wo) * C + g * 8;
+    const f16x8 a = *reinterpret_cast<const f16x8*>(s), b = *reinterpret_cast<const f16x8*>(s + C);
+    const f16x8 c = *reinterpret_cast<const f16x8*>(s + (int64_t)Wi * C), d = *reinterpret_cast<const f16x8*>(s + (int64_t)Wi * C + C);
+    f16x8 o;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) o[t] = (f16)fmaxf(fmaxf((float)a[t], (float)b[t]), fmaxf((float)c[t], (float)d[t]));
+    *reinterpret_cast<f16x8*>(y + p * C + g * 8) = o;
+  }
+}
+
+int maxpool2x2_nhwc(f16* y, const f16* x, int Hi, int Wi, int C, hipStream_t stream) {
+  SDEO_CHECK(y && x && Hi >= 2 && Wi >= 2 && C > 0 && C % 8 == 0, "maxpool2x2: bad operand (%dx%d, C=%d: C %% 8 == 0)", Hi, Wi, C);
+  SDEO_CHECK((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0, "maxpool2x2: operands must be 16-byte aligned");
+  hipLaunchKernelGGL(maxpool2x2_kernel, grid_px((int64_t)(Hi / 2) * (Wi / 2) * (C / 8)), dim3(256), 0, stream, y, x, Hi, Wi, C);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
+// out[p] = bias + sum_c x[p][c] w[c]: eight lanes per pixel, lane j reads channels [8 j + 64 t, 8 j + 64 t + 8) (16 bytes; the eight
+// lanes of a pixel read 128 contiguous bytes per step), fp32 products, then a fixed three-step butterfly over the eight lanes
+__global__ __launch_bounds__(256) void side_proj_kernel(float* __restrict__ out, const f16* __restrict__ x, const float* __restrict__ w,
+                                                        const float* __restrict__ bias, int64_t HW, int C) {
+  const int j = threadIdx.x & 7;
+  const float b = bias[0];
+  const int64_t stride = (int64_t)gridDim.x * 32;
+  for (int64_t p0 = (int64_t)blockIdx.x * 32; p0 < HW; p0 += stride) {
+    const int64_t p = p0 + (threadIdx.x >> 3);
+    float s = 0.f;
+    if (p < HW) {
+      const f16* row = x + p * C;
+      for (int c = j * 8; c < C; c += 64) {
+        const f16x8 v = *reinterpret_cast<const f16x8*>(row + c);
+        const f32x4 w0 = *reinterpret_cast<const f32x4*>(w + c), w1 = *reinterpret_cast<const f32x4*>(w + c + 4);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) s = fmaf((float)v[t], w0[t], s);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) s = fmaf((float)v[4 + t], w1[t], s);
+      }
+    }
+    s += __shfl_xor(s, 4, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 1, 64);
+    if (p < HW && j == 0) out[p] = s + b;
+  }
+}
+
+int side_proj(float* out, const f16* x, const float* w, const float* bias, int H, int W, int C, hipStream_t stream) {
+  SDEO_CHECK(out && x && w && bias && H > 0 && W > 0 && C > 0 && C % 64 == 0, "side_proj: bad operand (C=%d: C %% 64 == 0)", C);
+  const int64_t HW = (int64_t)H * W;
+  int64_t blocks = cdiv64(HW, 32);
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(side_proj_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, out, x, w, bias, HW, C);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
+struct HedMaps {
+  const float* m[5];
+  int h[5], w[5];
+};
+
+// F.interpolate(bilinear, align_corners=False) index and weights along one axis (upsample_bilinear2d's CPU arithmetic in fp32):
+// src = max(scale (d + 0.5) - 0.5, 0), i0 = min(floor(src), n - 1), l1 = clamp(src - i0, 0, 1), i1 = i0 + (i0 < n - 1)
+__device__ __forceinline__ void lin_axis(int d, int n, float scale, int& i0, int& i1, float& l0, float& l1) {
+  float src = __fsub_rn(__fmul_rn(scale, (float)d + 0.5f), 0.5f);
+  src = src < 0.f ? 0.f : src;
+  i0 = (int)floorf(src);
+  i0 = i0 < n - 1 ? i0 : n - 1;
+  l1 = fminf(fmaxf(__fsub_rn(src, (float)i0), 0.f), 1.f);
+  i1 = i0 + (i0 < n - 1 ? 1 : 0);
+  l0 = __fsub_rn(1.f, l1);
+}
+
+__global__ __launch_bounds__(256) void hed_fuse_kernel(uint8_t* __restrict__ edges, float* __restrict__ control, const HedMaps maps, int H,
+                                                       int W) {
+  const int64_t HW = (int64_t)H * W;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < HW; i += (int64_t)gridDim.x * 256) {
+    const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      const int h = maps.h[k], w = maps.w[k];
+      int y0, y1, x0, x1;
+      float ly0, ly1, lx0, lx1;
+      lin_axis(y, h, (float)h / (float)H, y0, y1, ly0, ly1);
+      lin_axis(x, w, (float)w / (float)W, x0, x1, lx0, lx1);
+      const float* m = maps.m[k];
+      const float t0 = __fadd_rn(__fmul_rn(m[y0 * w + x0], lx0), __fmul_rn(m[y0 * w + x1], lx1));
+      const float t1 = __fadd_rn(__fmul_rn(m[y1 * w + x0], lx0), __fmul_rn(m[y1 * w + x1], lx1));
+      const float v = __fadd_rn(__fmul_rn(t0, ly0), __fmul_rn(t1, ly1));
+      s = k ? __fadd_rn(s, v) : v;                 // ((((a + b) + c) + d) + e): numpy's order for five float32 elements
+    }
+    const float mean = s / 5.0f;                   // IEEE division (np.mean divides the float32 sum by the count)
+    const double e = 1.0 / (1.0 + exp(-(double)mean));
+    double v = e * 255.0;
+    v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
+    const uint8_t u = (uint8_t)(int)v;             // truncation, as .astype(np.uint8)
+    if (edges) edges[i] = u;
+    if (control) {
+      const float c = (float)u / 255.0f;           // HWC3(edge) / 255 in fp32
+      control[i] = c;
+      control[HW + i] = c;
+      control[2 * HW + i] = c;
+    }
+  }
+}
+
+int hed_fuse(uint8_t* edges, float* control, const HedMaps& maps, int H, int W, hipStream_t stream) {
+  SDEO_CHECK(H > 0 && W > 0, "hed_fuse: bad size");
+  for (int k = 0; k < 5; ++k) SDEO_CHECK(maps.m[k] && maps.h[k] >= 1 && maps.w[k] >= 1, "hed_fuse: map %d missing", k);
+  if (!edges && !control) return 0;
+  hipLaunchKernelGGL(hed_fuse_kernel, grid_px((int64_t)H * W), dim3(256), 0, stream, edges, control, maps, H, W);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace sdeo
+
+// ------------------------------------------------------------------------------------------------ handle
+namespace {
+
+struct HWeight {
+  std::string name;
+  int64_t dims[4];
+  int ndim;
+  bool conv;         // fp16 KRSC [O][3][3][cin_pad] (else fp32, stored as is)
+  int cin_pad;
+  size_t off;
+  bool loaded;
+};
+
+struct HedOp {
+  std::function<int(hipStream_t)> fn;
+  std::string name;
+  double flops;
+};
+
+const int kBlockConvs[5] = {2, 2, 3, 3, 3};
+const int kBlockCh[5] = {64, 128, 256, 512, 512};
+
+}  // namespace
+
+struct sdeo_hed_handle_s {
+  std::vector<HWeight> weights;
+  std::map<std::string, int> index;
+  char* slab = nullptr;
+  size_t slab_bytes = 0;
+  float* stage = nullptr;
+  size_t stage_bytes = 0;
+  bool finalized = false;
+  // configured state
+  int H = 0, W = 0;
+  char* act = nullptr;
+  size_t act_bytes = 0;
+  float* splitk_ws = nullptr;
+  size_t splitk_bytes = 0;
+  const uint8_t* img = nullptr;      // the image of the current sdeo_hed_detect_u8 call (read by the intake op)
+  uint8_t* edges = nullptr;
+  float* control = nullptr;
+  HedMaps maps{};
+  std::vector<HedOp> prog;
+};
+
+namespace {
+
+typedef sdeo_hed_handle_s Hed;
+
+static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+static void add_w(Hed* e, const std::string& name, int ndim, const int64_t* dims, bool conv, int cin_pad, size_t bytes, size_t& size) {
+  HWeight w{name, {1, 1, 1, 1}, ndim, conv, cin_pad, 0, false};
+  for (int i = 0; i < ndim; ++i) w.dims[i] = dims[i];
+  w.off = align256(size);
+  size = w.off + bytes;
+  e->index[name] = (int)e->weights.size();
+  e->weights.push_back(w);
+}
+
+// reference state-dict order: norm, then per block convs.{i}.weight / bias and projection.weight / bias
+static void build_registry(Hed* e) {
+  size_t size = 0, mx = 3;
+  const int64_t nd[4] = {1, 3, 1, 1};
+  add_w(e, "norm", 4, nd, false, 0, 3 * 4, size);
+  int cin = 3;
+  for (int b = 0; b < 5; ++b) {
+    const std::string p = "block" + std::to_string(b + 1) + ".";
+    const int c = kBlockCh[b];
+    for (int i = 0; i < kBlockConvs[b]; ++i) {
+      const int cp = (cin + 7) / 8 * 8;
+      const int64_t wd[4] = {c, cin, 3, 3}, bd[1] = {c};
+      add_w(e, p + "convs." + std::to_string(i) + ".weight", 4, wd, true, cp, (size_t)c * 9 * cp * 2, size);
+      add_w(e, p + "convs." + std::to_string(i) + ".bias", 1, bd, false, 0, (size_t)c * 4, size);
+      mx = std::max(mx, (size_t)c * cin * 9);
+      cin = c;
+    }
+    const int64_t pw[4] = {1, c, 1, 1}, pb[1] = {1};
+    add_w(e, p + "projection.weight", 4, pw, false, 0, (size_t)c * 4, size);
+    add_w(e, p + "projection.bias", 1, pb, false, 0, 4, size);
+  }
+  e->slab_bytes = align256(size);
+  e->stage_bytes = mx * sizeof(float);
+}
+
+static const char* wp(Hed* e, const std::string& n) { return e->slab + e->weights[e->index.at(n)].off; }
+
+static void free_configured(Hed* e) {
+  if (e->act) (void)hipFree(e->act);
+  if (e->splitk_ws) (void)hipFree(e->splitk_ws);
+  e->act = nullptr; e->splitk_ws = nullptr;
+  e->act_bytes = e->splitk_bytes = 0;
+  e->prog.clear();
+  e->H = e->W = 0;
+}
+
+static int run_prog(Hed* e, hipStream_t s) {
+  for (auto& op : e->prog)
+    if (int rc = op.fn(s)) return rc;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdeo_hed_create(sdeo_hed_handle* out) {
+  SDEO_CHECK(out, "sdeo_hed_create: null argument");
+  Hed* e = new Hed();
+  build_registry(e);
+  if (hipMalloc((void**)&e->slab, e->slab_bytes) != hipSuccess) {
+    const size_t want = e->slab_bytes;
+    delete e;
+    return fail("sdeo_hed_create: cannot allocate %zu bytes of weights", want);
+  }
+  *out = e;
+  return 0;
+}
+
+int sdeo_hed_destroy(sdeo_hed_handle h) {
+  if (!h) return 0;
+  free_configured(h);
+  if (h->slab) (void)hipFree(h->slab);
+  if (h->stage) (void)hipFree(h->stage);
+  delete h;
+  return 0;
+}
+
+int sdeo_hed_num_weights(sdeo_hed_handle h) { return h ? (int)h->weights.size() : 0; }
+
+int sdeo_hed_weight_info(sdeo_hed_handle h, int i, const char** name, int64_t dims[4], int* ndim) {
+  SDEO_CHECK(h && i >= 0 && i < (int)h->weights.size() && name && dims && ndim, "sdeo_hed_weight_info: bad argument");
+  const HWeight& w = h->weights[i];
+  *name = w.name.c_str();
+  for (int k = 0; k < 4; ++k) dims[k] = k < w.ndim ? w.dims[k] : 0;
+  *ndim = w.ndim;
+  return 0;
+}
+
+int sdeo_hed_load_weight(sdeo_hed_handle h, const char* name, const float* host_data, const int64_t* dims, int ndim, int strict) {
+  SDEO_CHECK(h && name && host_data && dims, "sdeo_hed_load_weight: null argument");
+  auto it = h->index.find(name);
+  if (it == h->index.end()) {
+    if (strict) return fail("sdeo_hed_load_weight: unexpected tensor '%s'", name);
+    return 0;
+  }
+  HWeight& w = h->weights[it->second];
+  SDEO_CHECK(ndim == w.ndim, "sdeo_hed_load_weight: %s has %d dims, expected %d", name, ndim, w.ndim);
+  size_t n = 1;
+  for (int i = 0; i < ndim; ++i) {
+    SDEO_CHECK(dims[i] == w.dims[i], "sdeo_hed_load_weight: %s dim %d is %lld, expected %lld", name, i, (long long)dims[i],
+               (long long)w.dims[i]);
+    n *= (size_t)dims[i];
+  }
+  if (!h->stage) SDEO_HIP(hipMalloc((void**)&h->stage, h->stage_bytes));
+  SDEO_HIP(hipMemcpy(h->stage, host_data, n * sizeof(float), hipMemcpyDefault));
+  void* dst = h->slab + w.off;
+  if (w.conv) {
+    if (int rc = oihw_f32_to_ohwi_f16((f16*)dst, h->stage, (int)w.dims[0], (int)w.dims[1], 3, 3, w.cin_pad, 0)) return rc;
+  } else {
+    SDEO_HIP(hipMemcpy(dst, h->stage, n * sizeof(float), hipMemcpyDeviceToDevice));
+  }
+  SDEO_HIP(hipDeviceSynchronize());
+  w.loaded = true;
+  h->finalized = false;
+  return 0;
+}
+
+int sdeo_hed_finalize_weights(sdeo_hed_handle h) {
+  SDEO_CHECK(h, "sdeo_hed_finalize_weights: null handle");
+  std::string missing;
+  int nmiss = 0;
+  for (auto& w : h->weights)
+    if (!w.loaded) {
+      if (nmiss < 5) missing += (nmiss ? ", " : "") + w.name;
+      ++nmiss;
+    }
+  SDEO_CHECK(nmiss == 0, "sdeo_hed_finalize_weights: %d tensors missing (%s%s)", nmiss, missing.c_str(), nmiss > 5 ? ", ..." : "");
+  if (h->stage) { (void)hipFree(h->stage); h->stage = nullptr; }
+  h->finalized = true;
+  return 0;
+}
+
+int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
+  SDEO_CHECK(h, "sdeo_hed_configure: null handle");
+  SDEO_CHECK(h->finalized, "sdeo_hed_configure: weights not finalized");
+  SDEO_CHECK(height >= 16 && width >= 16 && height <= 8192 && width <= 8192, "sdeo_hed_configure: image %dx%d out of range (16..8192)",
+             height, width);
+  free_configured(h);
+  Hed* e = h;
+  const int H = height, W = width;
+  int hk[5], wk[5];
+  hk[0] = H; wk[0] = W;
+  for (int k = 1; k < 5; ++k) { hk[k] = hk[k - 1] / 2; wk[k] = wk[k - 1] / 2; }
+  // arena: intake [H W][8] fp16; two ping-pong activation buffers of max_k h_k w_k C_k fp16 (block 1 is the largest); five side maps
+  size_t act_elems = 0;
+  for (int k = 0; k < 5; ++k) act_elems = std::max(act_elems, (size_t)hk[k] * wk[k] * kBlockCh[k]);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = align256(off); off = o + bytes; return o; };
+  const size_t o_in = take((size_t)H * W * 8 * 2), o_a = take(act_elems * 2), o_b = take(act_elems * 2);
+  size_t o_side[5];
+  for (int k = 0; k < 5; ++k) o_side[k] = take((size_t)hk[k] * wk[k] * 4);
+  e->act_bytes = align256(off);
+  SDEO_HIP(hipMalloc((void**)&e->act, e->act_bytes));
+  SDEO_HIP(hipMemset(e->act, 0, e->act_bytes));
+  f16* xin = reinterpret_cast<f16*>(e->act + o_in);
+  f16* buf[2] = {reinterpret_cast<f16*>(e->act + o_a), reinterpret_cast<f16*>(e->act + o_b)};
+  for (int k = 0; k < 5; ++k) {
+    e->maps.m[k] = reinterpret_cast<float*>(e->act + o_side[k]);
+    e->maps.h[k] = hk[k];
+    e->maps.w[k] = wk[k];
+  }
+
+  const float* norm = reinterpret_cast<const float*>(wp(e, "norm"));
+  e->prog.push_back({[e, xin, norm, H, W](hipStream_t s) { return hed_intake(xin, e->img, norm, H, W, s); }, "hed_intake", 0.0});
+  size_t ws = 0;
+  const f16* cur = xin;
+  int cur_buf = -1, cin = 8;
+  for (int b = 0; b < 5; ++b) {
+    const std::string p = "block" + std::to_string(b + 1) + ".";
+    const int c = kBlockCh[b], h = hk[b], w = wk[b];
+    if (b > 0) {
+      f16* dst = buf[cur_buf ^ 1];
+      const f16* src = cur;
+      const int hi = hk[b - 1], wi = wk[b - 1], cc = cin;
+      e->prog.push_back({[dst, src, hi, wi, cc](hipStream_t s) { return maxpool2x2_nhwc(dst, src, hi, wi, cc, s); }, "maxpool2x2_kernel", 0.0});
+      cur = dst;
+      cur_buf ^= 1;
+    }
+    for (int i = 0; i < kBlockConvs[b]; ++i) {
+      const std::string n = p + "convs." + std::to_string(i) + ".";
+      f16* dst = buf[cur_buf < 0 ? 0 : cur_buf ^ 1];
+      ConvGemm q;
+      q.x = cur; q.w = reinterpret_cast<const f16*>(wp(e, n + "weight")); q.y = dst;
+      q.bias = reinterpret_cast<const float*>(wp(e, n + "bias"));
+      q.B = 1; q.Hi = h; q.Wi = w; q.Cin = cin; q.R = q.S = 3; q.stride = 1; q.pad = 1;
+      q.Ho = h; q.Wo = w; q.M = h * w; q.N = c; q.K = 9 * cin;
+      q.ldx = cin; q.ldw = q.K; q.ldy = c; q.ldres = c; q.ld_bias2 = c;
+      q.act = 4;
+      ws = std::max(ws, conv_gemm_workspace_bytes(q));
+      e->prog.push_back({[q, e](hipStream_t s) mutable {
+                           q.workspace = e->splitk_ws;
+                           q.workspace_bytes = e->splitk_bytes;
+                           return conv_gemm(q, s);
+                         },
+                         conv_gemm_kernel_name(q), 2.0 * q.M * q.N * (double)(9 * (b == 0 && i == 0 ? 3 : cin))});
+      cur = dst;
+      cur_buf = cur_buf < 0 ? 0 : cur_buf ^ 1;
+      cin = c;
+    }
+    {
+      float* out = const_cast<float*>(e->maps.m[b]);
+      const f16* src = cur;
+      const float* pw = reinterpret_cast<const float*>(wp(e, p + "projection.weight"));
+      const float* pb = reinterpret_cast<const float*>(wp(e, p + "projection.bias"));
+      e->prog.push_back({[out, src, pw, pb, h, w, c](hipStream_t s) { return side_proj(out, src, pw, pb, h, w, c, s); }, "side_proj_kernel",
+                         2.0 * h * w * c});
+    }
+  }
+  e->prog.push_back({[e, H, W](hipStream_t s) { return hed_fuse(e->edges, e->control, e->maps, H, W, s); }, "hed_fuse_kernel", 0.0});
+  e->splitk_bytes = ws;
+  if (ws) SDEO_HIP(hipMalloc((void**)&e->splitk_ws, ws));
+  e->H = H;
+  e->W = W;
+  return 0;
+}
+
+int sdeo_hed_detect_u8(sdeo_hed_handle h, const uint8_t* img_hwc, uint8_t* edges, float* control_chw, float* const* side, void* stream) {
+  SDEO_CHECK(h, "sdeo_hed_detect_u8: null handle");
+  SDEO_CHECK(h->finalized, "sdeo_hed_detect_u8: weights not finalized");
+  SDEO_CHECK(h->H > 0, "sdeo_hed_detect_u8: handle not configured (sdeo_hed_configure)");
+  SDEO_CHECK(img_hwc, "sdeo_hed_detect_u8: null image");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  h->img = img_hwc;
+  h->edges = edges;
+  h->control = control_chw;
+  const int rc = run_prog(h, s);
+  h->img = nullptr; h->edges = nullptr; h->control = nullptr;
+  if (rc) return rc;
+  if (side)
+    for (int k = 0; k < 5; ++k)
+      if (side[k])
+        SDEO_HIP(hipMemcpyAsync(side[k], h->maps.m[k], (size_t)h->maps.h[k] * h->maps.w[k] * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+size_t sdeo_hed_device_bytes(sdeo_hed_handle h) { return h ? h->slab_bytes + h->act_bytes + h->splitk_bytes : 0; }
+
+// ---- not in sdeo.h: tests and tools
+
+// F.max_pool2d(x, 2, 2) on NHWC fp16 [h][w][c] (one image), c % 8 == 0 -> y [h/2][w/2][c]
+int sdeo_debug_maxpool2x2_f16(void* y, const void* x, int h, int w, int c, void* stream) {
+  return maxpool2x2_nhwc((f16*)y, (const f16*)x, h, w, c, reinterpret_cast<hipStream_t>(stream));
+}
+
+// one detection with HIP events around every launch; synchronises and returns the JSON array
+// [{"kernel", "launches", "total_ms", "flops"}] aggregated by kernel name (tools/hed_time.py).  Not capturable.
+const char* sdeo_debug_hed_profile(sdeo_hed_handle h, const uint8_t* img_hwc, void* stream) {
+  static thread_local std::string out;
+  out = "[]";
+  if (!h || !h->finalized || h->H <= 0 || !img_hwc) return out.c_str();
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  h->img = img_hwc;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev(h->prog.size());
+  bool ok = true;
+  for (size_t i = 0; i < h->prog.size() && ok; ++i) {
+    ok = hipEventCreate(&ev[i].first) == hipSuccess && hipEventCreate(&ev[i].second) == hipSuccess;
+    if (ok) ok = hipEventRecord(ev[i].first, s) == hipSuccess && h->prog[i].fn(s) == 0 && hipEventRecord(ev[i].second, s) == hipSuccess;
+  }
+  h->img = nullptr;
+  (void)hipStreamSynchronize(s);
+  struct Agg { long n = 0; double ms = 0, flops = 0; };
+  std::vector<std::pair<std::string, Agg>> aggs;
+  for (size_t i = 0; i < h->prog.size(); ++i) {
+    float ms = 0.f;
+    if (ok) (void)hipEventElapsedTime(&ms, ev[i].first, ev[i].second);
+    if (ev[i].first) (void)hipEventDestroy(ev[i].first);
+    if (ev[i].second) (void)hipEventDestroy(ev[i].second);
+    size_t j = 0;
+    while (j < aggs.size() && aggs[j].first != h->prog[i].name) ++j;
+    if (j == aggs.size()) aggs.push_back({h->prog[i].name, Agg{}});
+    aggs[j].second.n += 1; aggs[j].second.ms += ms; aggs[j].second.flops += h->prog[i].flops;
+  }
+  if (!ok) return out.c_str();
+  out = "[";
+  char buf[512];
+  for (size_t i = 0; i < aggs.size(); ++i) {
+    snprintf(buf, sizeof(buf), "%s{\"kernel\": \"%s\", \"launches\": %ld, \"total_ms\": %.6f, \"flops\": %.6e}", i ? ", " : "",
+             aggs[i].first.c_str(), aggs[i].second.n, aggs[i].second.ms, aggs[i].second.flops);
+    out += buf;
+  }
+  out += "]";
+  return out.c_str();
+}
+
+}  // extern "C"

@@ -31,6 +31,7 @@ struct ConvGemm {
   int ldx = 0, ldw = 0, ldy = 0, ldres = 0, ld_bias2 = 0;
   int act = 0;                 // 0 none, 1 SiLU, 2 quick-GELU  v * sigmoid(1.702 v)  (CLIP MLP),
                                // 3 GEGLU pair: W rows interleaved value/gate in blocks of 16, y gets N/2 columns v * gelu(g)
+                               // 4 ReLU (HED's VGG stack); plans like act 0 (not part of the plan key)
   int bias_per_row = 0;
   float scale = 1.0f;
   int force_tile = -1;         // testing hook: tile config index

@@ -370,3 +370,14 @@ def nhwc_to_nchw_f32(x, c=None, scale=1.0):
     check(lib.sdeo_nhwc_f16_to_nchw_f32(ptr(y), ptr(x), _i(ld), _i(n), _i(c), _i(h * w), _f(scale), cur_stream()),
           "nhwc_to_nchw")
     return y
+
+
+def maxpool2x2_nhwc(x):
+    """F.max_pool2d(kernel 2, stride 2) on one NHWC fp16 image (1, H, W, C), C % 8 == 0 (csrc/hed.hip); floor semantics."""
+    lib = _lib.load()
+    _need_cuda(x)
+    n, h, w, c = x.shape
+    assert n == 1 and x.dtype == torch.float16 and x.is_contiguous()
+    y = torch.empty((1, h // 2, w // 2, c), dtype=torch.float16, device=x.device)
+    check(lib.sdeo_debug_maxpool2x2_f16(ptr(y), ptr(x), _i(h), _i(w), _i(c), cur_stream()), "maxpool2x2")
+    return y

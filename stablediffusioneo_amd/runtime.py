@@ -397,3 +397,96 @@ class ClipRuntime:
 
     def device_bytes(self) -> int:
         return int(self.lib.sdeo_clip_device_bytes(self.handle))
+
+
+class HedRuntime:
+    """HED soft-edge annotator on the HIP path (`annotator/hed/__init__.py`: ControlNetHED_Apache2 + HEDdetector.__call__):
+    create -> load_state_dict -> configure(H, W) -> detect(image).  One image per call; csrc/hed.hip."""
+
+    def __init__(self, device: Optional[torch.device] = None):
+        if not torch.cuda.is_available():
+            raise _lib.SdeoError("HedRuntime needs a HIP device (there is no CPU fallback)")
+        self.lib = _lib.load()
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        torch.cuda.set_device(self.device)
+        self.handle = C.c_void_p()
+        check(self.lib.sdeo_hed_create(C.byref(self.handle)), "sdeo_hed_create")
+        self.size = (0, 0)
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None) and self.handle.value:
+                self.lib.sdeo_hed_destroy(self.handle)
+                self.handle = C.c_void_p()
+        except Exception:
+            pass
+
+    def expected_weights(self) -> Dict[str, tuple]:
+        out = {}
+        name = C.c_char_p()
+        dims = (C.c_int64 * 4)()
+        nd = C.c_int()
+        for i in range(self.lib.sdeo_hed_num_weights(self.handle)):
+            check(self.lib.sdeo_hed_weight_info(self.handle, C.c_int(i), C.byref(name), dims, C.byref(nd)), "hed_weight_info")
+            out[name.value.decode()] = tuple(int(dims[k]) for k in range(nd.value))
+        return out
+
+    def load_tensor(self, name: str, t: torch.Tensor, strict: bool = True):
+        t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+        dims = (C.c_int64 * max(t.dim(), 1))(*t.shape)
+        check(self.lib.sdeo_hed_load_weight(self.handle, name.encode(), C.c_void_p(t.data_ptr()), dims, C.c_int(t.dim()),
+                                            C.c_int(int(strict))), f"hed_load_weight({name})")
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False):
+        """The reference state dict / ControlNetHED.pth names (`norm`, `block{1..5}.convs.{i}.*`, `block{1..5}.projection.*`);
+        other floating-point tensors are ignored unless strict."""
+        for k, v in sd.items():
+            if not torch.is_floating_point(v):
+                continue
+            self.load_tensor(k, v, strict)
+        check(self.lib.sdeo_hed_finalize_weights(self.handle), "hed_finalize_weights")
+        self.size = (0, 0)
+        return self
+
+    def load_synthetic(self, seed: int = 0):
+        return self.load_state_dict(S.synth_hed_state_dict(seed), strict=True)
+
+    def configure(self, height: int, width: int):
+        if (height, width) != self.size:
+            self.size = (0, 0)
+            check(self.lib.sdeo_hed_configure(self.handle, C.c_int(height), C.c_int(width)), "sdeo_hed_configure")
+            self.size = (height, width)
+        return self
+
+    def side_shapes(self):
+        h, w = self.size
+        out = []
+        for _ in range(5):
+            out.append((h, w))
+            h, w = h // 2, w // 2
+        return out
+
+    def detect(self, image: torch.Tensor, edges: bool = True, control: bool = False, side: bool = False):
+        """image: uint8 (H, W, 3) RGB (host or device) -> dict with "edges" (H, W) uint8, "control" (3, H, W) fp32 = edges / 255,
+        "side" [five fp32 (h_k, w_k) maps], each on the device and only when asked for."""
+        if image.dim() != 3 or image.shape[2] != 3 or image.dtype != torch.uint8:
+            raise ValueError(f"HED expects a uint8 (H, W, 3) image, got {tuple(image.shape)} {image.dtype}")
+        H, W = int(image.shape[0]), int(image.shape[1])
+        self.configure(H, W)
+        img = image.to(self.device).contiguous()
+        out = {}
+        if edges:
+            out["edges"] = torch.empty((H, W), dtype=torch.uint8, device=self.device)
+        if control:
+            out["control"] = torch.empty((3, H, W), dtype=torch.float32, device=self.device)
+        sp = (C.c_void_p * 5)()
+        if side:
+            out["side"] = [torch.empty(s, dtype=torch.float32, device=self.device) for s in self.side_shapes()]
+            for k, t in enumerate(out["side"]):
+                sp[k] = t.data_ptr()
+        check(self.lib.sdeo_hed_detect_u8(self.handle, ptr(img), ptr(out.get("edges")), ptr(out.get("control")), sp if side else None,
+                                          cur_stream()), "sdeo_hed_detect_u8")
+        return out
+
+    def device_bytes(self) -> int:
+        return int(self.lib.sdeo_hed_device_bytes(self.handle))

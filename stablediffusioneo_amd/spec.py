@@ -455,3 +455,52 @@ def count_params(spec) -> int:
             p *= d
         n += p
     return n
+
+
+# ----------------------------------------------------------------------------------------
+# HED soft-edge annotator (`annotator/hed/__init__.py`: ControlNetHED_Apache2)
+# ----------------------------------------------------------------------------------------
+HED_BLOCKS = [(2, 64), (2, 128), (3, 256), (3, 512), (3, 512)]    # (3x3 convs, channels) of block1..block5
+NS_HED = "hed."                                                  # seed namespace of the synthetic draw (not part of the names)
+# projection gain per block: with He-gain convs every block output sits on the 0-255 input scale, so each side map is scaled down to
+# logits of a few units; the five maps then average to values mostly inside the sigmoid's sensitive range (tests/test_hed_cpu.py)
+HED_PROJ_GAIN = (0.05, 0.02, 0.03, 0.03, 0.02)
+
+
+def param_spec_hed() -> "OrderedDict[str, tuple]":
+    """The reference state dict of ControlNetHED_Apache2 (= the public ControlNetHED.pth): 37 tensors, in module order."""
+    spec = OrderedDict()
+    spec["norm"] = (1, 3, 1, 1)
+    cin = 3
+    for b, (n, c) in enumerate(HED_BLOCKS):
+        for i in range(n):
+            spec[f"block{b + 1}.convs.{i}.weight"] = (c, cin, 3, 3)
+            spec[f"block{b + 1}.convs.{i}.bias"] = (c,)
+            cin = c
+        spec[f"block{b + 1}.projection.weight"] = (1, c, 1, 1)
+        spec[f"block{b + 1}.projection.bias"] = (1,)
+    return spec
+
+
+def synth_hed_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Deterministic HED weights (fp32, CPU), drawn for a ReLU stack rather than with `synth_tensor` (whose N(0, 1/fan_in) shrinks
+    the activations about 90x over 13 layers): 3x3 convs N(0, 2/fan_in) (He gain: activations stay on the 0-255 input scale, so the
+    fp16 range is exercised), conv biases 0.5 N(0,1), norm = 100 + 40 U(0,1) (plausible pixel means), projections
+    N(0,1) HED_PROJ_GAIN[b] / sqrt(C) with bias 0.1 N(0,1)."""
+    out = OrderedDict()
+    for name, shape in param_spec_hed().items():
+        g = torch.Generator(device="cpu")
+        g.manual_seed(_seed_for(seed, NS_HED + name))
+        b = int(name[5]) - 1 if name.startswith("block") else -1
+        if name == "norm":
+            t = 100.0 + 40.0 * torch.rand(shape, generator=g)
+        elif ".projection.weight" in name:
+            t = torch.randn(shape, generator=g) * (HED_PROJ_GAIN[b] / shape[1] ** 0.5)
+        elif ".projection.bias" in name:
+            t = 0.1 * torch.randn(shape, generator=g)
+        elif name.endswith(".weight"):
+            t = torch.randn(shape, generator=g) * (2.0 / (shape[1] * 9)) ** 0.5
+        else:
+            t = 0.5 * torch.randn(shape, generator=g)
+        out[name] = t
+    return out
