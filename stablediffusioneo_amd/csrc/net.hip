@@ -565,9 +565,6 @@ struct ConvOpts {                     // conv / gemm options
   const RowStats* ln = nullptr;  // consumer: LayerNorm folded into this GEMM, statistics of x from *ln, row sums ln_s
   const float* ln_s = nullptr;
   bool gn_next = false;          // the output feeds a GroupNorm(32): let the epilogue emit its partial statistics when the plan can
-  // GroupNorm(32) (+ SiLU) of the conv's INPUT applied inside the conv kernel (Builder::gn_conv decides): the partials of x, gamma / beta
-  const float* gn_in = nullptr; int gn_in_slots = 0; const float* gn_gamma = nullptr; const float* gn_beta = nullptr;
-  float gn_in_eps = 1e-5f; int gn_in_silu = 0;
   // conv(): stream this [cout][k*k*x.c] matrix / bias instead of the tensors registered under `name` (a composed Linear)
   const f16* w_ovr = nullptr; const float* b_ovr = nullptr;
   // conv(): zero padding top / left and bottom / right; -1 = k / 2 (the VAE encoder's Downsample: 0 and 1)
@@ -751,10 +748,6 @@ struct Builder {
     if (pad_after != pad) p.pad_after = pad_after;
     p.M = x.n * ho * wo; p.N = cs; p.K = k * k * x.c;
     p.ldx = x.ld; p.ldw = p.K; p.ldy = y.ld; p.act = o.act;
-    if (o.gn_in) {
-      p.gn_in = o.gn_in; p.gn_in_slots = o.gn_in_slots; p.gn_gamma = o.gn_gamma; p.gn_beta = o.gn_beta; p.gn_in_eps = o.gn_in_eps;
-      p.gn_in_silu = o.gn_in_silu;
-    }
     const bool want_gn = o.gn_next && !o.out && !o.scale_host && cs == y.c;
     if (want_gn) reserve_gn_partials(p, y);
     launch_conv(p, o.scale_host, o.stats, want_gn ? &y : nullptr, &o);
@@ -819,44 +812,13 @@ struct Builder {
     return y;
   }
 
-  // conv3x3(act(GroupNorm(x))) (`openaimodel.py:255-275`, `model.py:129-149`).  When x carries its producer's partials and the conv's
-  // plan is a halo-reuse kernel with LDS left for the (a, b) table, the conv applies the GroupNorm itself (KP::gn_in): no GroupNorm
-  // launch, no normalised copy.  Otherwise GroupNorm launch(es) + conv.
-  // default OFF since the end of round 3: with the launch prologues shortened (kernel-argument fetch) the 21 GroupNorm launches it
-  // removes cost less than the ~6 us it adds to each conv (three same-box alternations: 5.931 vs 5.876 ms per step, 8.13 vs 8.22 images/s)
-  static bool gn_in_enabled() { static const bool on = [] { const char* v = getenv("SDEO_GN_IN_CONV"); return v && atoi(v) != 0; }(); return on; }
+  // conv3x3(act(GroupNorm(x))) (`openaimodel.py:255-275`, `model.py:129-149`): GroupNorm launch(es) + conv
   T gn_conv(const T& x, const std::string& gn_name, float eps, int silu_, const std::string& conv_name, int cout, CO o) {
-    if (gn_in_enabled() && !e->autotune && x.gnp && x.gn_slots > 0 && x.c % 32 == 0) {
-      ConvGemm q;
-      const int cs = o.cout_store > 0 ? o.cout_store : cout;
-      q.B = x.n; q.Hi = x.h; q.Wi = x.w; q.Cin = x.c; q.Ho = x.h; q.Wo = x.w; q.R = q.S = 3; q.stride = 1; q.pad = 1;
-      q.M = x.n * x.h * x.w; q.N = cs; q.K = 9 * x.c; q.ldx = x.ld; q.ldw = q.K; q.ldy = cs; q.act = o.act;
-      if (x.ld == x.c && conv_gemm_gn_in_ok(q)) {
-        const float* part = x.gnp;
-        int slots = x.gn_slots;
-        T folded;
-        if (slots > 128) {               // large images (VAE): fold the entries of a group first, the conv's prologue sums few
-          folded = alloc2d(x.n, 32 * 2 * 2);            // [n][1][32][2] floats
-          float* fp = reinterpret_cast<float*>(folded.p);
-          const int B = x.n, ns = slots;
-          push([=](hipStream_t s) { return groupnorm_fold_partials(fp, part, B, ns, 32, s); }, "groupnorm", 0, 0, "fold " + std::to_string(ns));
-          part = fp;
-          slots = 1;
-        }
-        o.gn_in = part; o.gn_in_slots = slots; o.gn_gamma = vptr(gn_name + ".weight"); o.gn_beta = vptr(gn_name + ".bias");
-        o.gn_in_eps = eps; o.gn_in_silu = silu_;
-        T y = conv(x, conv_name, cout, 3, 1, 0, o);
-        if (slots == 1 && folded.off != (size_t)-1) release(folded);
-        ++gn_in_fused;
-        return y;
-      }
-    }
     T t = gn(x, gn_name, eps, silu_);
     T y = conv(t, conv_name, cout, 3, 1, 0, o);
     release(t);
     return y;
   }
-  int gn_in_fused = 0;
 
   T ln(const T& x, const std::string& name) {
     T y = alloc(x.n, x.h, x.w, x.c);
@@ -938,42 +900,24 @@ static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& 
   b.release(q2);
   // ff.net.2 and proj_out are two Linear maps with only the residual add between them: composed at finalisation into ONE [C][5C]
   // matrix over the row-concatenated operand [GEGLU output (4C) | tok2 (C)] (ComposeJob), so attn2.to_out writes tok2 into the last C
-  // columns of that operand, the GEGLU GEMM writes the first 4C, and one GEMM replaces two launches (SDEO_COMPOSE_FF=0: the two-launch form)
-  static const bool compose = [] { const char* v = getenv("SDEO_COMPOSE_FF"); return !v || atoi(v) != 0; }();
-  T cat, ggv, tok2v;
-  if (compose) {
-    cat = b.alloc(x.n, x.h, x.w, 5 * C);
-    ggv = cat; ggv.c = 4 * C; ggv.off = (size_t)-1;
-    tok2v = cat; tok2v.p = cat.p + 4 * C; tok2v.c = C; tok2v.off = (size_t)-1;
-  }
-  Builder::CO r2; r2.res = &tok1; r2.stats = &st2;
-  if (compose) r2.out = &tok2v;
+  // columns of that operand, the GEGLU GEMM writes the first 4C, and one GEMM replaces two launches
+  T cat = b.alloc(x.n, x.h, x.w, 5 * C);
+  T gg = cat; gg.c = 4 * C; gg.off = (size_t)-1;
+  T tok2v = cat; tok2v.p = cat.p + 4 * C; tok2v.c = C; tok2v.off = (size_t)-1;
+  Builder::CO r2; r2.res = &tok1; r2.stats = &st2; r2.out = &tok2v;
   T tok2 = b.gemm(o2, b.wptr(t + ".attn2.to_out.0.weight"), C, C, b.vptr(t + ".attn2.to_out.0.bias"), r2);
   b.release(o2);
   b.release(tok1);
   // GEGLU feed-forward: LN3 + ff.net.0.proj + GEGLU in one launch (act 3: value * gelu(gate) in the GEMM epilogue, 4C columns out)
-  T gg = compose ? ggv : b.alloc(x.n, x.h, x.w, 4 * C);
   {
     Builder::CO og; og.act = 3; og.out = &gg; og.ln = &st2; og.ln_s = b.named_v(t + ".ff1_ln.s");
     b.gemm(tok2, b.named_w(t + ".ff1_ln.w"), C, 8 * C, b.named_v(t + ".ff1_ln.b"), og);
   }
-  T y;
-  if (compose) {
-    b.release_stats();
-    Builder::CO ro; ro.res = &x; ro.out = out; ro.gn_next = true;
-    ro.w_ovr = b.named_w(t + ".ffproj.w"); ro.b_ovr = b.named_v(t + ".ffproj.b");
-    y = b.conv(cat, p + ".proj_out", C, 1, 1, 0, ro);
-    b.release(cat);
-  } else {
-    Builder::CO r3; r3.res = &tok2;
-    T tok3 = b.gemm(gg, b.wptr(t + ".ff.net.2.weight"), 4 * C, C, b.vptr(t + ".ff.net.2.bias"), r3);
-    b.release(gg);
-    b.release(tok2);
-    b.release_stats();
-    Builder::CO ro; ro.res = &x; ro.out = out; ro.gn_next = true;
-    y = b.conv(tok3, p + ".proj_out", C, 1, 1, 0, ro);
-    b.release(tok3);
-  }
+  b.release_stats();
+  Builder::CO ro; ro.res = &x; ro.out = out; ro.gn_next = true;
+  ro.w_ovr = b.named_w(t + ".ffproj.w"); ro.b_ovr = b.named_v(t + ".ffproj.b");
+  T y = b.conv(cat, p + ".proj_out", C, 1, 1, 0, ro);
+  b.release(cat);
   return y;
 }
 
