@@ -215,6 +215,10 @@ int sdeo_debug_gemm_plan(int m, int n, int k, int act, int fp8, int* key10, int*
 // (tile, split-K) of the last conv / GEMM launch (host-side record; -1 / 0 before the first)
 void sdeo_debug_last_gemm_plan(int* tile, int* splitk) { conv_gemm_last_plan(tile, splitk); }
 
+int sdeo_debug_tile_info(int tile, int* kind, int* bm, int* bn, int* stages, int* caps, const char** name) {
+  return conv_gemm_tile_info(tile, kind, bm, bn, stages, caps, name);
+}
+
 size_t sdeo_gemm_workspace_bytes(int m, int n, int k) {
   ConvGemm p;
   fill_gemm(p, m, n, k);

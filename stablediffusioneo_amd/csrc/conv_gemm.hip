@@ -57,12 +57,12 @@ namespace sdeo {
 // 16-byte chunks and issue v_mfma_scale_f32_16x16x128_f8f6f4 with the two e8m0 block scales of the lane's row and 32-code block:
 // 4x the K per MFMA at twice its cycles, half the operand bytes per FLOP.  GEMM (1x1) only, wave-specialised only.
 template <int BM, int BN, int STAGES, bool UPS, bool WS, bool W8 = false, int KPB = 1, bool MX = false>
-__global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const KP2 pp) {
-  kernarg_warm<sizeof(KP2)>();
+__global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const KP pp) {
+  kernarg_warm<sizeof(KP)>();
   // The scalars both roles need before their first DMA / fragment read, fetched in ONE batch and pinned in SGPRs: left to the
   // compiler each is an s_load + s_waitcnt lgkmcnt(0) next to its first use, ten dependent scalar round trips in front of the
-  // first DMA of a launch whose whole K loop lasts a few microseconds.  (blockIdx.y is always 0: one problem per launch.)
-  KP pl = pp.k[0];
+  // first DMA of a launch whose whole K loop lasts a few microseconds.
+  KP pl = pp;
   // (integers only: a pointer that has been through the asm loses its address space and every access through it becomes a flat_ one)
   asm volatile("" : "+s"(pl.M), "+s"(pl.N), "+s"(pl.K), "+s"(pl.Hi), "+s"(pl.Wi), "+s"(pl.Cin), "+s"(pl.Wo),
                "+s"(pl.S), "+s"(pl.stride), "+s"(pl.pad), "+s"(pl.HoWo), "+s"(pl.ldx), "+s"(pl.ldw), "+s"(pl.nk),
@@ -520,9 +520,9 @@ __global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const KP2
 // fallback kernel: register-staged double buffer (any Cin % 8 == 0)
 // ------------------------------------------------------------------------------------------------
 template <int BM, int BN, int BK, bool GENERIC>
-__global__ __launch_bounds__(256) void conv_gemm_kernel(const KP2 pp) {
-  kernarg_warm<sizeof(KP2)>();
-  const KP& p = pp.k[blockIdx.y];
+__global__ __launch_bounds__(256) void conv_gemm_kernel(const KP pp) {
+  kernarg_warm<sizeof(KP)>();
+  const KP& p = pp;
   constexpr int CPR = BK / 8;         // 16-byte chunks per tile row
   constexpr int RPP = 256 / CPR;      // tile rows covered per pass of the 256 threads
   constexpr int XP = BM / RPP;        // passes for the activation tile
@@ -677,10 +677,10 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const KP2 pp) {
 }
 
 // split-K: sum the fp32 partial slabs and apply the epilogue. One thread per 4 output channels.
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const KP2 pp) {
-  kernarg_warm<sizeof(KP2)>();
-  // every scalar the loads below depend on, in one batch (see conv_gemm_dma_kernel); blockIdx.y is always 0
-  KP pl = pp.k[0];
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(const KP pp) {
+  kernarg_warm<sizeof(KP)>();
+  // every scalar the loads below depend on, in one batch (see conv_gemm_dma_kernel)
+  KP pl = pp;
   asm volatile("" : "+s"(pl.M), "+s"(pl.N), "+s"(pl.HoWo), "+s"(pl.ldy), "+s"(pl.ldres), "+s"(pl.ld_bias2), "+s"(pl.act),
                "+s"(pl.bias_per_row), "+s"(pl.splitk));     // integers only: pinned pointers would turn their accesses into flat_ ones
   const KP& p = pl;
@@ -743,75 +743,101 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const KP2 pp) {
 // ------------------------------------------------------------------------------------------------
 // host side: tile / split-K selection and launch
 // ------------------------------------------------------------------------------------------------
-enum TileKind { TK_DMA, TK_GENERIC, TK_HALO };
-// TK_HALO (conv_halo.hip): bm = patch pixels, `stages` = index into kHaloCfgs, bk = 64
-struct TileCfg { int bm, bn, bk, stages; TileKind kind; float weight; int wg_per_cu; const char* name; };
+// launch of one instantiation; the attribute call raises the dynamic-LDS limit once per device
+template <typename K>
+static int launch_k(K kernel, int smem, DeviceOnce* attr_done, const KP& kp, int tiles, hipStream_t stream, int threads = 256) {
+  if (attr_done->need()) {
+    SDEO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    attr_done->mark();
+  }
+  hipLaunchKernelGGL(kernel, dim3(tiles, 1, kp.splitk), dim3(threads), smem, stream, kp);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
+template <int BM, int BN, int ST, bool UPS, bool WS, bool W8 = false, int KPB = 1, bool MX = false>
+static int launch_dma(const KP& kp, int tiles, hipStream_t stream) {
+  static DeviceOnce done;
+  // ring + the LayerNorm row scalars (conv_gemm_dma_kernel: lnsm); an fp8 weight row is 64 bytes, one DMA pass covers 64 rows
+  constexpr int smem = ST * (W8 ? BM * 128 + (BN + 63) / 64 * 4096 : (BM + BN) * 128) + BM * 8;
+  static_assert(smem <= 160 * 1024, "LDS");
+  return launch_k(&conv_gemm_dma_kernel<BM, BN, ST, UPS, WS, W8, KPB, MX>, smem, &done, kp, tiles, stream, WS ? 512 : 256);
+}
+
+template <int BM, int BN>
+static int launch_generic(const KP& kp, int tiles, hipStream_t stream) {
+  static DeviceOnce done;
+  return launch_k(&conv_gemm_kernel<BM, BN, 32, true>, 2 * (BM + BN) * 64, &done, kp, tiles, stream);
+}
+
+// The tile table (TileCfg: conv_inl.h).  Adding a tile = one row here (appended: indices are public) + its index in the tests' tile
+// lists, which tests/test_tile_table_cpu.py holds against this table.  CAPS: CAP_LIGHT makes the row the four-wave instantiation;
+// CAP_W8 / CAP_MX add the fp8-weight / block-scaled-fp8 instantiation of the same shape (wave-specialised, no folded Upsample, KPB 1).
+template <int BM, int BN, int ST, int CAPS = 0, int KPB = 1>
+static constexpr TileCfg dma_tile(const char* name) {
+  constexpr bool WS = !(CAPS & CAP_LIGHT);
+  TileCfg c{BM, BN, 64, ST, TK_DMA, CAPS | (KPB > 1 ? CAP_GROUPED : 0), KPB, 0, 0, name,
+            &launch_dma<BM, BN, ST, false, WS, false, KPB>, &launch_dma<BM, BN, ST, true, WS, false, KPB>, nullptr, nullptr};
+  if constexpr ((CAPS & CAP_W8) != 0) c.w8 = &launch_dma<BM, BN, ST, false, true, true>;
+  if constexpr ((CAPS & CAP_MX) != 0) c.mx = &launch_dma<BM, BN, ST, false, true, false, 1, true>;
+  return c;
+}
+template <int BM, int BN>
+static constexpr TileCfg generic_tile(const char* name) {      // the kernel folds the Upsample at run time
+  return {BM, BN, 32, 2, TK_GENERIC, 0, 1, 0, 0, name, &launch_generic<BM, BN>, &launch_generic<BM, BN>, nullptr, nullptr};
+}
 static const TileCfg kTiles[] = {
-    {128, 128, 64, 3, TK_DMA, 1.00f, 1, "conv_gemm_dma_kernel<128,128,3>"},
-    {128, 64, 64, 3, TK_DMA, 0.85f, 2, "conv_gemm_dma_kernel<128,64,3>"},
-    {64, 64, 64, 4, TK_DMA, 0.65f, 2, "conv_gemm_dma_kernel<64,64,4>"},
-    {128, 64, 32, 2, TK_GENERIC, 0.85f, 3, "conv_gemm_kernel<128,64,32,true>"},
-    {64, 64, 32, 2, TK_GENERIC, 0.65f, 4, "conv_gemm_kernel<64,64,32,true>"},
-    {256, 128, 64, 3, TK_DMA, 1.25f, 1, "conv_gemm_dma_kernel<256,128,3>"},
+    dma_tile<128, 128, 3, CAP_MX>("conv_gemm_dma_kernel<128,128,3>"),
+    dma_tile<128, 64, 3, CAP_W8 | CAP_MX>("conv_gemm_dma_kernel<128,64,3>"),
+    dma_tile<64, 64, 4, CAP_W8>("conv_gemm_dma_kernel<64,64,4>"),
+    generic_tile<128, 64>("conv_gemm_kernel<128,64,32,true>"),
+    generic_tile<64, 64>("conv_gemm_kernel<64,64,32,true>"),
+    dma_tile<256, 128, 3>("conv_gemm_dma_kernel<256,128,3>"),
     // 160-wide weight panels: the channel counts of this model are multiples of 320, and what bounds these kernels is the
     // bytes a CU has to take in per K-step, so the tile menu is built to hit 256 equal workgroups
-    {64, 160, 64, 3, TK_DMA, 0.90f, 1, "conv_gemm_dma_kernel<64,160,3>"},
-    {128, 160, 64, 3, TK_DMA, 1.10f, 1, "conv_gemm_dma_kernel<128,160,3>"},
-    {256, 160, 64, 3, TK_DMA, 1.30f, 1, "conv_gemm_dma_kernel<256,160,3>"},
-    {32, 160, 64, 4, TK_DMA, 0.60f, 2, "conv_gemm_dma_kernel<32,160,4>"},
-    {64, 160, 64, 5, TK_DMA, 0.90f, 1, "conv_gemm_dma_kernel<64,160,5>"},
-    {128, 160, 64, 4, TK_DMA, 1.10f, 1, "conv_gemm_dma_kernel<128,160,4>"},
-    {128, 64, 64, 5, TK_DMA, 0.85f, 1, "conv_gemm_dma_kernel<128,64,5>"},
+    dma_tile<64, 160, 3, CAP_W8 | CAP_MX>("conv_gemm_dma_kernel<64,160,3>"),
+    dma_tile<128, 160, 3>("conv_gemm_dma_kernel<128,160,3>"),      // (its block-scaled fp8 form spills at the 256-register cap)
+    dma_tile<256, 160, 3>("conv_gemm_dma_kernel<256,160,3>"),
+    dma_tile<32, 160, 4, CAP_W8>("conv_gemm_dma_kernel<32,160,4>"),
+    dma_tile<64, 160, 5>("conv_gemm_dma_kernel<64,160,5>"),
+    dma_tile<128, 160, 4>("conv_gemm_dma_kernel<128,160,4>"),
+    dma_tile<128, 64, 5>("conv_gemm_dma_kernel<128,64,5>"),
     // halo-reuse 3x3 kernels (stride 1, pad 1, Cin % 64 == 0, image a multiple of the patch)
-    {128, 80, 64, 0, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,80,4>"},
-    {128, 160, 64, 1, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,160,4>"},
-    {64, 80, 64, 2, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,8,80,4>"},
-    {64, 160, 64, 3, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,8,160,4>"},
-    {128, 64, 64, 4, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,64,4>"},
-    {128, 128, 64, 5, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,128,4>"},
+    halo_row(0), halo_row(1), halo_row(2), halo_row(3), halo_row(4), halo_row(5),
     // deep rings: a K-step is bound by bytes in flight per CU (a DMA lands ~1 us after issue under load), so small tiles get
     // as many stages as LDS holds
-    {64, 64, 64, 8, TK_DMA, 0.65f, 1, "conv_gemm_dma_kernel<64,64,8>"},
-    {32, 160, 64, 6, TK_DMA, 0.60f, 1, "conv_gemm_dma_kernel<32,160,6>"},
-    {128, 128, 64, 4, TK_DMA, 1.00f, 1, "conv_gemm_dma_kernel<128,128,4>"},
+    dma_tile<64, 64, 8, CAP_W8>("conv_gemm_dma_kernel<64,64,8>"),
+    dma_tile<32, 160, 6, CAP_W8>("conv_gemm_dma_kernel<32,160,6>"),
+    dma_tile<128, 128, 4, CAP_MX>("conv_gemm_dma_kernel<128,128,4>"),
     // halo kernels with two MFMA waves per SIMD
-    {128, 80, 64, 6, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,80,8>"},
-    {128, 160, 64, 7, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,160,8>"},
-    {128, 64, 64, 8, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,64,8>"},
-    {128, 128, 64, 9, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,128,8>"},
+    halo_row(6), halo_row(7), halo_row(8), halo_row(9),
     // many-tile, short-K problems (ff.net.0.proj, q|k|v: thousands of tiles of 5 - 10 K-steps): a tile's prologue, K loop and
     // epilogue are each ~2 us and serial inside a workgroup (tools/stamps.py), so what overlaps them is OTHER workgroups on the
     // same CU.  Four-wave workgroups (no loader waves: half the register footprint per workgroup) on a two-slot ring fit three
     // or four to a CU.
-    {128, 64, 64, 2, TK_DMA, 0.85f, 3, "conv_gemm_dma_kernel<128,64,2>"},
-    {64, 64, 64, 2, TK_DMA, 0.65f, 4, "conv_gemm_dma_kernel<64,64,2>"},
-    {128, 128, 64, 2, TK_DMA, 1.00f, 2, "conv_gemm_dma_kernel<128,128,2>"},
-    {128, 160, 64, 2, TK_DMA, 1.10f, 2, "conv_gemm_dma_kernel<128,160,2>"},
-    {64, 160, 64, 2, TK_DMA, 0.90f, 2, "conv_gemm_dma_kernel<64,160,2>"},
-    {32, 160, 64, 2, TK_DMA, 0.60f, 3, "conv_gemm_dma_kernel<32,160,2>"},
-    {64, 64, 64, 3, TK_DMA, 0.65f, 3, "conv_gemm_dma_kernel<64,64,3>"},
-    {128, 64, 64, 3, TK_DMA, 0.85f, 2, "conv_gemm_dma_kernel<128,64,3>/4w"},
-    // halo kernels with one barrier per filter row (three taps): indices 34..40 = kHaloCfgs 10..16
-    {128, 80, 64, 10, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,80,4,3>"},
-    {128, 80, 64, 11, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,80,8,3>"},
-    {128, 64, 64, 12, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,64,4,3>"},
-    {64, 80, 64, 13, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,8,80,4,3>"},
-    {64, 160, 64, 14, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,8,160,4,3>"},
-    {128, 128, 64, 15, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,128,8,3>"},
-    {128, 64, 64, 16, TK_HALO, 1.0f, 1, "conv3x3_halo_kernel<8,16,64,8,3>"},
+    dma_tile<128, 64, 2, CAP_LIGHT>("conv_gemm_dma_kernel<128,64,2>"),
+    dma_tile<64, 64, 2, CAP_LIGHT>("conv_gemm_dma_kernel<64,64,2>"),
+    dma_tile<128, 128, 2, CAP_LIGHT>("conv_gemm_dma_kernel<128,128,2>"),
+    dma_tile<128, 160, 2, CAP_LIGHT>("conv_gemm_dma_kernel<128,160,2>"),
+    dma_tile<64, 160, 2, CAP_LIGHT>("conv_gemm_dma_kernel<64,160,2>"),
+    dma_tile<32, 160, 2, CAP_LIGHT>("conv_gemm_dma_kernel<32,160,2>"),
+    dma_tile<64, 64, 3, CAP_LIGHT>("conv_gemm_dma_kernel<64,64,3>"),
+    dma_tile<128, 64, 3, CAP_LIGHT>("conv_gemm_dma_kernel<128,64,3>/4w"),
+    // halo kernels with one barrier per filter row (three taps)
+    halo_row(10), halo_row(11), halo_row(12), halo_row(13), halo_row(14), halo_row(15), halo_row(16),
     // implicit-GEMM tiles with one barrier per GROUP of K-steps (conv_gemm_dma_kernel KPB): name<BM,BN,STAGES,KPB>
-    {32, 160, 64, 6, TK_DMA, 0.60f, 1, "conv_gemm_dma_kernel<32,160,6,k2>"},
-    {64, 64, 64, 8, TK_DMA, 0.65f, 1, "conv_gemm_dma_kernel<64,64,8,k2>"},
-    {64, 64, 64, 9, TK_DMA, 0.65f, 1, "conv_gemm_dma_kernel<64,64,9,k3>"},
-    {64, 160, 64, 5, TK_DMA, 0.90f, 1, "conv_gemm_dma_kernel<64,160,5,k2>"},
-    {128, 64, 64, 6, TK_DMA, 0.85f, 1, "conv_gemm_dma_kernel<128,64,6,k2>"},
-    {64, 64, 64, 6, TK_DMA, 0.65f, 1, "conv_gemm_dma_kernel<64,64,6,k2>"},
-    {128, 128, 64, 4, TK_DMA, 1.00f, 1, "conv_gemm_dma_kernel<128,128,4,k2>"},
-    {32, 160, 64, 5, TK_DMA, 0.60f, 1, "conv_gemm_dma_kernel<32,160,5,k2>"},
+    dma_tile<32, 160, 6, 0, 2>("conv_gemm_dma_kernel<32,160,6,k2>"),
+    dma_tile<64, 64, 8, 0, 2>("conv_gemm_dma_kernel<64,64,8,k2>"),
+    dma_tile<64, 64, 9, 0, 3>("conv_gemm_dma_kernel<64,64,9,k3>"),
+    dma_tile<64, 160, 5, 0, 2>("conv_gemm_dma_kernel<64,160,5,k2>"),
+    dma_tile<128, 64, 6, 0, 2>("conv_gemm_dma_kernel<128,64,6,k2>"),
+    dma_tile<64, 64, 6, 0, 2>("conv_gemm_dma_kernel<64,64,6,k2>"),
+    dma_tile<128, 128, 4, 0, 2>("conv_gemm_dma_kernel<128,128,4,k2>"),
+    dma_tile<32, 160, 5, 0, 2>("conv_gemm_dma_kernel<32,160,5,k2>"),
 };
-static const int kNumTiles = 49;
-static bool tile_is_grouped(int t) { return t >= 41 && t <= 48; }
-static bool tile_is_light(int t) { return t >= 26 && t <= 33; }     // four-wave (non-specialised) instantiations
+static const int kTileCount = (int)std::size(kTiles);
+// halo, four-wave and grouped-barrier tiles enter through the measured plan table or a forced plan only
+static bool by_plan_only(const TileCfg& c) { return (c.caps & (CAP_HALO | CAP_LIGHT | CAP_GROUPED)) != 0; }
 static const int kNumCU = 256;
 
 struct Plan { int tile; int splitk; int nk; int tiles_m, tiles_n; };
@@ -819,14 +845,12 @@ struct Plan { int tile; int splitk; int nk; int tiles_m, tiles_n; };
 static bool is_fast(const ConvGemm& p) { return p.Cin % 64 == 0; }
 static bool halo_ok(const ConvGemm& p, const TileCfg& c) {
   if (c.kind != TK_HALO) return false;
-  const HaloCfg& h = kHaloCfgs[c.stages];
   return p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 && conv_pad_after(p) == 1 && !p.ups && p.Cin % 64 == 0 && p.act != 3 && !p.bias_per_row &&
-         p.Hi % h.ph == 0 && p.Wi % h.pw == 0 && p.Ho == p.Hi && p.Wo == p.Wi;
+         p.Hi % c.ph == 0 && p.Wi % c.pw == 0 && p.Ho == p.Hi && p.Wo == p.Wi;
 }
 // tiles and K-steps of a plan: a halo tile is a patch of one image and steps through Cin in 64-channel slices (9 taps each)
 static int plan_tiles_m(const ConvGemm& p, const TileCfg& c) {
-  if (c.kind == TK_HALO) { const HaloCfg& h = kHaloCfgs[c.stages]; return p.B * (p.Hi / h.ph) * (p.Wi / h.pw); }
-  return cdiv(p.M, c.bm);
+  return c.kind == TK_HALO ? p.B * (p.Hi / c.ph) * (p.Wi / c.pw) : cdiv(p.M, c.bm);
 }
 static int plan_nk(const ConvGemm& p, const TileCfg& c) { return c.kind == TK_HALO ? p.Cin / 64 : cdiv(p.K, c.bk); }
 
@@ -843,10 +867,9 @@ static std::map<ShapeKey, std::pair<int, int>> g_tuned;
 static ShapeKey key_of(const ConvGemm& p) {
   return {p.M, p.N, p.K, p.Cin, p.R, p.stride, (p.act == 3 ? 2 : p.ups) + (p.wscale ? 4 : 0) + (p.mx_sx ? 8 : 0), p.Hi, p.Wi, p.B};
 }
-// tiles instantiated for block-scaled fp8 operands (the MFMA-bound GEMMs: many rows)
-static bool tile_has_mx(int t) { return t == 0 || t == 1 || t == 6 || t == 21; }      // (<128,160,3> spills at the 256-register cap)
-// tiles instantiated with fp8 weights (the weight-bound shapes: few rows, long K)
-static bool tile_has_w8(int t) { return t == 1 || t == 2 || t == 6 || t == 9 || t == 19 || t == 20; }
+// the instantiations p's operands need exist for tile c: fp8 weights (the weight-bound shapes: few rows, long K) / block-scaled fp8
+// operands (the MFMA-bound GEMMs: many rows)
+static bool has_operand_form(const ConvGemm& p, const TileCfg& c) { return (!p.wscale || (c.caps & CAP_W8)) && (!p.mx_sx || (c.caps & CAP_MX)); }
 
 static Plan make_plan(const ConvGemm& p) {
   Plan best{};
@@ -858,24 +881,21 @@ static Plan make_plan(const ConvGemm& p) {
     auto it = g_tuned.find(key_of(p));
     if (it != g_tuned.end() && !(pair && ((kTiles[it->second.first].bn / 2) % 32 != 0 || it->second.second != 1))) {
       const TileCfg& c = kTiles[it->second.first];
-      if ((c.kind != TK_HALO || halo_ok(p, c)) && (!p.wscale || tile_has_w8(it->second.first)) && (!p.mx_sx || tile_has_mx(it->second.first)))
+      if ((c.kind != TK_HALO || halo_ok(p, c)) && has_operand_form(p, c))
         return Plan{it->second.first, it->second.second, plan_nk(p, c), plan_tiles_m(p, c), cdiv(p.N, c.bn)};
     }
   }
   float best_t = 1e30f;
-  for (int t = 0; t < kNumTiles; ++t) {
+  for (int t = 0; t < kTileCount; ++t) {
     const TileCfg& c = kTiles[t];
     auto usable = [&](int ti) {
       const TileCfg& cc = kTiles[ti];
-      if (p.wscale && !tile_has_w8(ti)) return false;
-      if (p.mx_sx && !tile_has_mx(ti)) return false;
+      if (!has_operand_form(p, cc)) return false;
       if (cc.kind == TK_HALO) return halo_ok(p, cc);
       return (cc.kind == TK_DMA) == fast && !(pair && (cc.bn / 2) % 32 != 0);
     };
     if (!usable(t)) continue;
-    if (c.kind == TK_HALO && force_tile != t) continue;      // halo tiles enter through the measured plan table or a forced plan only
-    if (tile_is_light(t) && force_tile != t) continue;       // so do the four-wave tiles
-    if (tile_is_grouped(t) && force_tile != t) continue;     // and the grouped-barrier tiles
+    if (by_plan_only(c) && force_tile != t) continue;
     if (force_tile >= 0 && usable(force_tile) && force_tile != t) continue;
     const int tmn = plan_tiles_m(p, c), tnn = cdiv(p.N, c.bn);
     const int tiles = tmn * tnn;
@@ -940,7 +960,7 @@ static int gn_slots_of(const ConvGemm& p, int cpg) {       // p: the view the ke
   const TileCfg& c = kTiles[pl.tile];
   if (pl.splitk != 1 || c.kind == TK_GENERIC || plan_tn(pl) % cpg) return 0;
   if (p.N % 8 || p.ldy % 8 || (reinterpret_cast<uintptr_t>(p.y) & 15) || (p.res && (p.ldres % 8 || (reinterpret_cast<uintptr_t>(p.res) & 15)))) return 0;
-  if (c.kind == TK_HALO) { const HaloCfg& h = kHaloCfgs[c.stages]; return (p.Hi / h.ph) * (p.Wi / h.pw); }
+  if (c.kind == TK_HALO) return (p.Hi / c.ph) * (p.Wi / c.pw);
   const int hw = p.Ho * p.Wo;
   return hw % c.bm == 0 ? hw / c.bm : 0;
 }
@@ -966,44 +986,6 @@ void conv_gemm_query_plan(const ConvGemm& p0, int key[10], int* tile, int* split
 // (tile, split-K) of the last problem conv_gemm() launched: host-side only, read by the tests through sdeo_debug_last_gemm_plan
 static int g_last_tile = -1, g_last_splitk = 0;
 void conv_gemm_last_plan(int* tile, int* splitk) { *tile = g_last_tile; *splitk = g_last_splitk; }
-
-template <typename K>
-static int launch_k(K kernel, int smem, DeviceOnce* attr_done, const KP2& kp, int count, int tiles, hipStream_t stream, int threads = 256) {
-  if (attr_done->need()) {
-    SDEO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    attr_done->mark();
-  }
-  dim3 grid(tiles, count, kp.k[0].splitk);
-  hipLaunchKernelGGL(kernel, grid, dim3(threads), smem, stream, kp);
-  SDEO_HIP(hipGetLastError());
-  return 0;
-}
-
-// fp8-weight instantiations: wave-specialised only, no folded Upsample (the weight-bound convs have neither)
-template <int BM, int BN, int ST>
-static int launch_dma_w8(const KP2& kp, int count, int tiles, hipStream_t stream) {
-  static DeviceOnce done;
-  constexpr int smem = ST * (BM * 128 + (BN + 63) / 64 * 4096) + BM * 8;
-  return launch_k(&conv_gemm_dma_kernel<BM, BN, ST, false, true, true>, smem, &done, kp, count, tiles, stream, 512);
-}
-
-template <int BM, int BN, int ST, int KPB = 1>
-static int launch_dma(int ups, const KP2& kp, int count, int tiles, hipStream_t stream) {
-  static DeviceOnce done[2];
-  constexpr int smem = ST * (BM + BN) * 128 + BM * 8;      // ring + the LayerNorm row scalars (conv_gemm_dma_kernel: lnsm)
-  static_assert(smem <= 160 * 1024, "LDS");
-  return ups ? launch_k(&conv_gemm_dma_kernel<BM, BN, ST, true, true, false, KPB>, smem, &done[1], kp, count, tiles, stream, 512)
-             : launch_k(&conv_gemm_dma_kernel<BM, BN, ST, false, true, false, KPB>, smem, &done[0], kp, count, tiles, stream, 512);
-}
-
-// four-wave workgroups on a two-slot ring (tiles 26..28)
-template <int BM, int BN, int ST>
-static int launch_dma_light(int ups, const KP2& kp, int count, int tiles, hipStream_t stream) {
-  static DeviceOnce done[2];
-  constexpr int smem = ST * (BM + BN) * 128 + BM * 8;
-  return ups ? launch_k(&conv_gemm_dma_kernel<BM, BN, ST, true, false>, smem, &done[1], kp, count, tiles, stream)
-             : launch_k(&conv_gemm_dma_kernel<BM, BN, ST, false, false>, smem, &done[0], kp, count, tiles, stream);
-}
 
 // argument checks + plan + kernel parameters of one problem
 static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
@@ -1040,8 +1022,8 @@ static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
     SDEO_CHECK(p.Cin % 64 == 0 && !p.ups && p.ldw % 16 == 0 && !p.bias_per_row,
                "conv_gemm: fp8 weights need Cin %% 64 == 0 (Cin=%d), no folded upsample and 16-byte aligned rows (ldw=%d bytes)", p.Cin, p.ldw);
   pl = make_plan(p);
-  SDEO_CHECK(!p.wscale || (tile_has_w8(pl.tile) && kTiles[pl.tile].kind == TK_DMA), "conv_gemm: no fp8-weight plan for this shape");
-  SDEO_CHECK(!p.mx_sx || (tile_has_mx(pl.tile) && kTiles[pl.tile].kind == TK_DMA), "conv_gemm: no block-scaled fp8 plan for this shape");
+  SDEO_CHECK(!p.wscale || (kTiles[pl.tile].caps & CAP_W8), "conv_gemm: no fp8-weight plan for this shape");
+  SDEO_CHECK(!p.mx_sx || (kTiles[pl.tile].caps & CAP_MX), "conv_gemm: no block-scaled fp8 plan for this shape");
   SDEO_CHECK(p.act != 3 || (pl.splitk == 1 && (kTiles[pl.tile].bn / 2) % 32 == 0), "conv_gemm: no GEGLU-capable plan");
   kp = KP{};
   kp.x = p.x; kp.w = p.w; kp.y = p.y; kp.y32 = p.y32; kp.bias = p.bias; kp.bias2 = p.bias2; kp.res = p.res;
@@ -1104,80 +1086,16 @@ static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
   return 0;
 }
 
-// launch the problem(s) in kp at plan `pl` (count is always 1)
-// block-scaled fp8 instantiations
-template <int BM, int BN, int ST>
-static int launch_dma_mx(const KP2& kp, int count, int tiles, hipStream_t stream) {
-  static DeviceOnce done;
-  constexpr int smem = ST * (BM + BN) * 128 + BM * 8;
-  return launch_k(&conv_gemm_dma_kernel<BM, BN, ST, false, true, false, 1, true>, smem, &done, kp, count, tiles, stream, 512);
-}
-
-static int dispatch(const Plan& pl, int ups, bool w8, const KP2& kp, int count, hipStream_t stream) {
-  const int tiles = pl.tiles_m * pl.tiles_n;
-  int rc = 0;
-  if (kp.k[0].mx_sx) {
-    switch (pl.tile) {
-      case 0: rc = launch_dma_mx<128, 128, 3>(kp, count, tiles, stream); break;
-      case 1: rc = launch_dma_mx<128, 64, 3>(kp, count, tiles, stream); break;
-      case 6: rc = launch_dma_mx<64, 160, 3>(kp, count, tiles, stream); break;
-      case 21: rc = launch_dma_mx<128, 128, 4>(kp, count, tiles, stream); break;
-      default: return fail("conv_gemm: tile %d has no block-scaled fp8 instantiation", pl.tile);
-    }
-  } else if (w8) {
-    switch (pl.tile) {
-      case 1: rc = launch_dma_w8<128, 64, 3>(kp, count, tiles, stream); break;
-      case 2: rc = launch_dma_w8<64, 64, 4>(kp, count, tiles, stream); break;
-      case 6: rc = launch_dma_w8<64, 160, 3>(kp, count, tiles, stream); break;
-      case 9: rc = launch_dma_w8<32, 160, 4>(kp, count, tiles, stream); break;
-      case 19: rc = launch_dma_w8<64, 64, 8>(kp, count, tiles, stream); break;
-      case 20: rc = launch_dma_w8<32, 160, 6>(kp, count, tiles, stream); break;
-      default: return fail("conv_gemm: tile %d has no fp8-weight instantiation", pl.tile);
-    }
-  } else
-  switch (pl.tile) {
-    case 0: rc = launch_dma<128, 128, 3>(ups, kp, count, tiles, stream); break;
-    case 1: rc = launch_dma<128, 64, 3>(ups, kp, count, tiles, stream); break;
-    case 2: rc = launch_dma<64, 64, 4>(ups, kp, count, tiles, stream); break;
-    case 3: { static DeviceOnce d; rc = launch_k(&conv_gemm_kernel<128, 64, 32, true>, 2 * (128 + 64) * 64, &d, kp, count, tiles, stream); break; }
-    case 4: { static DeviceOnce d; rc = launch_k(&conv_gemm_kernel<64, 64, 32, true>, 2 * (64 + 64) * 64, &d, kp, count, tiles, stream); break; }
-    case 5: rc = launch_dma<256, 128, 3>(ups, kp, count, tiles, stream); break;
-    case 6: rc = launch_dma<64, 160, 3>(ups, kp, count, tiles, stream); break;
-    case 7: rc = launch_dma<128, 160, 3>(ups, kp, count, tiles, stream); break;
-    case 8: rc = launch_dma<256, 160, 3>(ups, kp, count, tiles, stream); break;
-    case 9: rc = launch_dma<32, 160, 4>(ups, kp, count, tiles, stream); break;
-    case 10: rc = launch_dma<64, 160, 5>(ups, kp, count, tiles, stream); break;
-    case 11: rc = launch_dma<128, 160, 4>(ups, kp, count, tiles, stream); break;
-    case 12: rc = launch_dma<128, 64, 5>(ups, kp, count, tiles, stream); break;
-    case 19: rc = launch_dma<64, 64, 8>(ups, kp, count, tiles, stream); break;
-    case 20: rc = launch_dma<32, 160, 6>(ups, kp, count, tiles, stream); break;
-    case 21: rc = launch_dma<128, 128, 4>(ups, kp, count, tiles, stream); break;
-    case 26: rc = launch_dma_light<128, 64, 2>(ups, kp, count, tiles, stream); break;
-    case 27: rc = launch_dma_light<64, 64, 2>(ups, kp, count, tiles, stream); break;
-    case 28: rc = launch_dma_light<128, 128, 2>(ups, kp, count, tiles, stream); break;
-    case 29: rc = launch_dma_light<128, 160, 2>(ups, kp, count, tiles, stream); break;
-    case 30: rc = launch_dma_light<64, 160, 2>(ups, kp, count, tiles, stream); break;
-    case 31: rc = launch_dma_light<32, 160, 2>(ups, kp, count, tiles, stream); break;
-    case 32: rc = launch_dma_light<64, 64, 3>(ups, kp, count, tiles, stream); break;
-    case 33: rc = launch_dma_light<128, 64, 3>(ups, kp, count, tiles, stream); break;
-    case 41: rc = launch_dma<32, 160, 6, 2>(ups, kp, count, tiles, stream); break;
-    case 42: rc = launch_dma<64, 64, 8, 2>(ups, kp, count, tiles, stream); break;
-    case 43: rc = launch_dma<64, 64, 9, 3>(ups, kp, count, tiles, stream); break;
-    case 44: rc = launch_dma<64, 160, 5, 2>(ups, kp, count, tiles, stream); break;
-    case 45: rc = launch_dma<128, 64, 6, 2>(ups, kp, count, tiles, stream); break;
-    case 46: rc = launch_dma<64, 64, 6, 2>(ups, kp, count, tiles, stream); break;
-    case 47: rc = launch_dma<128, 128, 4, 2>(ups, kp, count, tiles, stream); break;
-    case 48: rc = launch_dma<32, 160, 5, 2>(ups, kp, count, tiles, stream); break;
-    case 13: case 14: case 15: case 16: case 17: case 18: case 22: case 23: case 24: case 25:
-    case 34: case 35: case 36: case 37: case 38: case 39: case 40:
-      rc = launch_halo(kTiles[pl.tile].stages, kp, count, pl.tiles_m, pl.tiles_n, stream);
-      break;
-    default: return fail("conv_gemm: bad tile %d", pl.tile);
-  }
-  if (rc) return rc;
+// launch the problem in kp at plan `pl`: the row's instantiation for these operands, then the split-K reduce
+static int dispatch(const Plan& pl, int ups, bool w8, const KP& kp, hipStream_t stream) {
+  if (pl.tile < 0 || pl.tile >= kTileCount) return fail("conv_gemm: bad tile %d", pl.tile);
+  const TileCfg& c = kTiles[pl.tile];
+  const TileLaunch launch = kp.mx_sx ? c.mx : w8 ? c.w8 : ups ? c.ups : c.plain;
+  if (!launch) return fail("conv_gemm: tile %d has no %s instantiation", pl.tile, kp.mx_sx ? "block-scaled fp8" : w8 ? "fp8-weight" : "folded-upsample");
+  if (int rc = launch(kp, pl.tiles_m * pl.tiles_n, stream)) return rc;
   if (pl.splitk > 1) {
-    const int64_t n = (int64_t)kp.k[0].M * (kp.k[0].N / 4);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)cdiv64(n, 256), count), dim3(256), 0, stream, kp);
+    const int64_t n = (int64_t)kp.M * (kp.N / 4);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, stream, kp);
     SDEO_HIP(hipGetLastError());
   }
   return 0;
@@ -1188,10 +1106,17 @@ int conv_gemm(const ConvGemm& p0, hipStream_t stream) {
     SDEO_CHECK(p0.K % 128 == 0 && p0.ldx % 16 == 0 && p0.ldw % 16 == 0 && p0.K == p0.Cin, "conv_gemm: block-scaled fp8 GEMM needs K %% 128 == 0 (K=%d, ldx=%d, ldw=%d)", p0.K, p0.ldx, p0.ldw);
   const ConvGemm p = mx_view(p0);
   Plan pl;
-  KP2 kk{};
-  if (int rc = prepare(p, pl, kk.k[0])) return rc;
+  KP kp{};
+  if (int rc = prepare(p, pl, kp)) return rc;
   g_last_tile = pl.tile; g_last_splitk = pl.splitk;
-  return dispatch(pl, p.ups, p.wscale != nullptr, kk, 1, stream);
+  return dispatch(pl, p.ups, p.wscale != nullptr, kp, stream);
+}
+
+int conv_gemm_tile_info(int tile, int* kind, int* bm, int* bn, int* stages, int* caps, const char** name) {
+  if (tile < 0 || tile >= kTileCount) return 1;
+  const TileCfg& c = kTiles[tile];
+  *kind = c.kind; *bm = c.bm; *bn = c.bn; *stages = c.stages; *caps = c.caps; *name = c.name;
+  return 0;
 }
 
 int conv_gemm_read_stamps(unsigned long long* out, int n) {
@@ -1205,7 +1130,7 @@ int conv_gemm_read_stamps(unsigned long long* out, int n) {
 void conv_gemm_set_tuned(const int key[10], int tile, int splitk) {
   ShapeKey k;
   for (int i = 0; i < 10; ++i) k[i] = key[i];
-  if (tile >= 0 && tile < kNumTiles && kTiles[tile].kind != TK_GENERIC && splitk >= 1) g_tuned[k] = {tile, splitk};
+  if (tile >= 0 && tile < kTileCount && kTiles[tile].kind != TK_GENERIC && splitk >= 1) g_tuned[k] = {tile, splitk};
 }
 
 std::string conv_gemm_tuned_json() {
@@ -1242,17 +1167,17 @@ int conv_gemm_autotune(const ConvGemm& p, hipStream_t stream) {
   if (!is_fast(p) || g_force_tile >= 0 || g_force_splitk > 0) return 0;
   const ShapeKey key = key_of(p);
   if (g_tuned.count(key)) return 0;
-  static const int tiles[] = {0, 1, 2, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48};
   static const int sks[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20};
   hipEvent_t a, b;
   SDEO_HIP(hipEventCreate(&a));
   SDEO_HIP(hipEventCreate(&b));
   float best = 1e30f;
   std::pair<int, int> pick(-1, 1);
-  for (int t : tiles) {
+  for (int t = 0; t < kTileCount; ++t) {
+    if (kTiles[t].kind == TK_GENERIC) continue;
     const bool halo = kTiles[t].kind == TK_HALO;
     if (halo && !halo_ok(p, kTiles[t])) continue;
-    if (p.wscale && !tile_has_w8(t)) continue;
+    if (p.wscale && !(kTiles[t].caps & CAP_W8)) continue;
     const int nk = plan_nk(p, kTiles[t]);
     const int wgs1 = plan_tiles_m(p, kTiles[t]) * cdiv(p.N, kTiles[t].bn);
     if (p.act == 3 && (kTiles[t].bn / 2) % 32 != 0) continue;

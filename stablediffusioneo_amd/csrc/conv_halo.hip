@@ -34,10 +34,10 @@ constexpr int halo_stages(int ph, int pw, int bn, int tpb = 1) {
 // per-step skeleton (counted wait + barrier + loop bookkeeping, ~120 ns per tap by the ablations of DESIGN.md section 11) is paid a
 // third as often and the MFMA waves run three taps of fragment reads and MFMAs without meeting the loaders.
 template <int PH, int PW, int BN, int NMW, int TPB = 1>
-__global__ __launch_bounds__(NMW * 64 + 256) void conv3x3_halo_kernel(const KP2 pp) {
-  kernarg_warm<sizeof(KP2)>();
-  // prologue scalars in one batch, pinned in SGPRs (see conv_gemm_dma_kernel); blockIdx.y is always 0
-  KP pl = pp.k[0];
+__global__ __launch_bounds__(NMW * 64 + 256) void conv3x3_halo_kernel(const KP pp) {
+  kernarg_warm<sizeof(KP)>();
+  // prologue scalars in one batch, pinned in SGPRs (see conv_gemm_dma_kernel)
+  KP pl = pp;
   // (integers only: a pointer that has been through the asm loses its address space and every access through it becomes a flat_ one)
   asm volatile("" : "+s"(pl.M), "+s"(pl.N), "+s"(pl.Hi), "+s"(pl.Wi), "+s"(pl.Cin), "+s"(pl.ldx), "+s"(pl.ldw),
                "+s"(pl.nk_per_split), "+s"(pl.tiles_m), "+s"(pl.tiles_n));
@@ -299,32 +299,10 @@ int conv_halo_read_stamps(unsigned long long* out, int n) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// variants + launcher
+// launcher + the variants' rows of the tile table
 // ------------------------------------------------------------------------------------------------
-const HaloCfg kHaloCfgs[] = {
-    {8, 16, 80, "conv3x3_halo_kernel<8,16,80,4>"},
-    {8, 16, 160, "conv3x3_halo_kernel<8,16,160,4>"},
-    {8, 8, 80, "conv3x3_halo_kernel<8,8,80,4>"},
-    {8, 8, 160, "conv3x3_halo_kernel<8,8,160,4>"},
-    {8, 16, 64, "conv3x3_halo_kernel<8,16,64,4>"},
-    {8, 16, 128, "conv3x3_halo_kernel<8,16,128,4>"},
-    {8, 16, 80, "conv3x3_halo_kernel<8,16,80,8>"},
-    {8, 16, 160, "conv3x3_halo_kernel<8,16,160,8>"},
-    {8, 16, 64, "conv3x3_halo_kernel<8,16,64,8>"},
-    {8, 16, 128, "conv3x3_halo_kernel<8,16,128,8>"},
-    // one barrier per filter row (TPB = 3)
-    {8, 16, 80, "conv3x3_halo_kernel<8,16,80,4,3>"},
-    {8, 16, 80, "conv3x3_halo_kernel<8,16,80,8,3>"},
-    {8, 16, 64, "conv3x3_halo_kernel<8,16,64,4,3>"},
-    {8, 8, 80, "conv3x3_halo_kernel<8,8,80,4,3>"},
-    {8, 8, 160, "conv3x3_halo_kernel<8,8,160,4,3>"},
-    {8, 16, 128, "conv3x3_halo_kernel<8,16,128,8,3>"},
-    {8, 16, 64, "conv3x3_halo_kernel<8,16,64,8,3>"},
-};
-const int kNumHaloCfgs = 17;
-
 template <int PH, int PW, int BN, int NMW, int TPB = 1>
-static int launch_halo_t(const KP2& kp, int count, int tiles_m, int tiles_n, hipStream_t stream) {
+static int launch_halo_t(const KP& kp, int tiles, hipStream_t stream) {
   constexpr int smem = 2 * halo_xbytes(PH, PW) + halo_stages(PH, PW, BN, TPB) * TPB * halo_wbytes(BN);
   static_assert(smem <= 160 * 1024, "LDS");
   static DeviceOnce done;
@@ -333,32 +311,27 @@ static int launch_halo_t(const KP2& kp, int count, int tiles_m, int tiles_n, hip
                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     done.mark();
   }
-  hipLaunchKernelGGL((conv3x3_halo_kernel<PH, PW, BN, NMW, TPB>), dim3(tiles_m * tiles_n, count, kp.k[0].splitk), dim3(NMW * 64 + 256), smem, stream, kp);
+  hipLaunchKernelGGL((conv3x3_halo_kernel<PH, PW, BN, NMW, TPB>), dim3(tiles, 1, kp.splitk), dim3(NMW * 64 + 256), smem, stream, kp);
   SDEO_HIP(hipGetLastError());
   return 0;
 }
 
-int launch_halo(int variant, const KP2& kp, int count, int tiles_m, int tiles_n, hipStream_t stream) {
-  switch (variant) {
-    case 0: return launch_halo_t<8, 16, 80, 4>(kp, count, tiles_m, tiles_n, stream);
-    case 1: return launch_halo_t<8, 16, 160, 4>(kp, count, tiles_m, tiles_n, stream);
-    case 2: return launch_halo_t<8, 8, 80, 4>(kp, count, tiles_m, tiles_n, stream);
-    case 3: return launch_halo_t<8, 8, 160, 4>(kp, count, tiles_m, tiles_n, stream);
-    case 4: return launch_halo_t<8, 16, 64, 4>(kp, count, tiles_m, tiles_n, stream);
-    case 5: return launch_halo_t<8, 16, 128, 4>(kp, count, tiles_m, tiles_n, stream);
-    case 6: return launch_halo_t<8, 16, 80, 8>(kp, count, tiles_m, tiles_n, stream);
-    case 7: return launch_halo_t<8, 16, 160, 8>(kp, count, tiles_m, tiles_n, stream);
-    case 8: return launch_halo_t<8, 16, 64, 8>(kp, count, tiles_m, tiles_n, stream);
-    case 9: return launch_halo_t<8, 16, 128, 8>(kp, count, tiles_m, tiles_n, stream);
-    case 10: return launch_halo_t<8, 16, 80, 4, 3>(kp, count, tiles_m, tiles_n, stream);
-    case 11: return launch_halo_t<8, 16, 80, 8, 3>(kp, count, tiles_m, tiles_n, stream);
-    case 12: return launch_halo_t<8, 16, 64, 4, 3>(kp, count, tiles_m, tiles_n, stream);
-    case 13: return launch_halo_t<8, 8, 80, 4, 3>(kp, count, tiles_m, tiles_n, stream);
-    case 14: return launch_halo_t<8, 8, 160, 4, 3>(kp, count, tiles_m, tiles_n, stream);
-    case 15: return launch_halo_t<8, 16, 128, 8, 3>(kp, count, tiles_m, tiles_n, stream);
-    case 16: return launch_halo_t<8, 16, 64, 8, 3>(kp, count, tiles_m, tiles_n, stream);
-    default: return fail("launch_halo: bad variant %d", variant);
-  }
+template <int PH, int PW, int BN, int NMW, int TPB = 1>
+static constexpr TileCfg halo_tile(const char* name) {
+  return {PH * PW, BN, 64, halo_stages(PH, PW, BN, TPB), TK_HALO, CAP_HALO, 1, PH, PW, name, &launch_halo_t<PH, PW, BN, NMW, TPB>, nullptr, nullptr, nullptr};
 }
+// a variant is written down once: its template arguments, spelled without blanks, are also its name
+#define HALO(...) halo_tile<__VA_ARGS__>("conv3x3_halo_kernel<" #__VA_ARGS__ ">")
+const TileCfg& halo_row(int variant) {
+  static const TileCfg rows[] = {
+      HALO(8,16,80,4), HALO(8,16,160,4), HALO(8,8,80,4), HALO(8,8,160,4), HALO(8,16,64,4), HALO(8,16,128,4),
+      // two MFMA waves per SIMD
+      HALO(8,16,80,8), HALO(8,16,160,8), HALO(8,16,64,8), HALO(8,16,128,8),
+      // one barrier per filter row (TPB = 3)
+      HALO(8,16,80,4,3), HALO(8,16,80,8,3), HALO(8,16,64,4,3), HALO(8,8,80,4,3), HALO(8,8,160,4,3), HALO(8,16,128,8,3), HALO(8,16,64,8,3),
+  };
+  return rows[variant];
+}
+#undef HALO
 
 }  // namespace sdeo

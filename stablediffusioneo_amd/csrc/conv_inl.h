@@ -58,9 +58,6 @@ struct KP {
   int mx_ldsx, mx_ldsw;
 };
 
-// what a kernel receives (blockIdx.y indexes the problem; always one)
-struct KP2 { KP k[1]; };
-
 // Ablation / stamp switches exist only in the measurement build: in the production library dbg_on() is the constant false and
 // every branch on it (and the stamp code) is compiled out of the K loops.
 #ifdef SDEO_DEBUG_KERNELS
@@ -595,10 +592,22 @@ __device__ __forceinline__ void wait_vmcnt() {
 }
 
 
-// halo-reuse 3x3 kernel family (conv_halo.hip): variant table + launcher used by conv_gemm's planner
-struct HaloCfg { int ph, pw, bn; const char* name; };
-extern const HaloCfg kHaloCfgs[];
-extern const int kNumHaloCfgs;
-int launch_halo(int variant, const KP2& kp, int count, int tiles_m, int tiles_n, hipStream_t stream);
+// One row of the conv / GEMM tile table (conv_gemm.hip: kTiles), the only description of a tile: the planner, the launcher, the
+// autotuner and sdeo_debug_tile_info all read it.  A tile's index in that table is public (tuned_plans_gfx950.json, the force hook).
+enum TileKind { TK_DMA, TK_GENERIC, TK_HALO };
+// CAP_LIGHT: four-wave workgroups (no loader waves); CAP_GROUPED: one barrier per group of `kpb` K-steps; CAP_W8 / CAP_MX: an
+// fp8-weight / block-scaled-fp8 instantiation exists; CAP_HALO: kind == TK_HALO.  (the bit values are those of sdeo_debug_tile_info)
+enum TileCap { CAP_LIGHT = 1, CAP_GROUPED = 2, CAP_W8 = 4, CAP_MX = 8, CAP_HALO = 16 };
+typedef int (*TileLaunch)(const KP& kp, int tiles, hipStream_t stream);      // one launch of tiles x 1 x kp.splitk workgroups
+struct TileCfg {
+  int bm, bn, bk, stages;      // TK_HALO: bm = ph * pw pixels of one image, stages = weight ring slots
+  TileKind kind;
+  int caps, kpb;
+  int ph, pw;                  // TK_HALO: the patch of output pixels a workgroup owns
+  const char* name;            // the instantiation, as profiles and bench.py --full key on it
+  TileLaunch plain, ups, w8, mx;    // fp16 / folded nearest-x2 upsample / fp8 weights / block-scaled fp8; null where none exists
+};
+// the halo-reuse 3x3 kernel's rows (conv_halo.hip: 17 variants), which kTiles takes in by position
+const TileCfg& halo_row(int variant);
 
 }  // namespace sdeo

@@ -14,6 +14,17 @@ void sdeo_debug_force_gemm_plan(int tile, int splitk);
 void sdeo_debug_force_gemm_order(int order); /* -1 heuristic, 0 M-fastest, 1 N-fastest tile order within an XCD */
 /* name of the kernel instantiation sdeo_conv2d_nhwc_f16 would launch for this problem (plan table / forced plan / heuristic) */
 const char* sdeo_debug_conv2d_kernel_name(int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x);
+/* plan queries (tests; host only, no device call): the problem of an sdeo_conv2d_nhwc_f16 / sdeo_gemm_f16 call of this shape with
+ * `act` and, for fp8 != 0, fp8 weights -> the tuned-table key it looks up (key10) and the (tile, split-K) it would launch */
+int sdeo_debug_conv2d_plan(int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, int act, int fp8, int* key10,
+                           int* tile, int* splitk);
+int sdeo_debug_gemm_plan(int m, int n, int k, int act, int fp8, int* key10, int* tile, int* splitk);
+/* (tile, split-K) of the last conv / GEMM launch (host-side record; -1 / 0 before the first) */
+void sdeo_debug_last_gemm_plan(int* tile, int* splitk);
+/* row `tile` of the conv / GEMM tile table (csrc/conv_gemm.hip: kTiles); returns non-zero past the end.  kind: 0 LDS-DMA implicit GEMM,
+ * 1 register-staged fallback, 2 halo-reuse 3x3.  caps: 1 four-wave, 2 grouped barrier, 4 has an fp8-weight instantiation,
+ * 8 has a block-scaled-fp8 instantiation, 16 halo.  Host only. */
+int sdeo_debug_tile_info(int tile, int* kind, int* bm, int* bn, int* stages, int* caps, const char** name);
 /* measurement builds only (python -m stablediffusioneo_amd.build --debug, SDEO_DBG_GEMM bit 6): per-workgroup phase stamps of
  * the last GEMM (which = 0) / halo conv (1) launch, 8 x uint64 per workgroup in 10 ns units */
 int sdeo_debug_read_stamps(int which, unsigned long long* out, int n);

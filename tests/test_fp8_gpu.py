@@ -45,7 +45,7 @@ def test_fp8_pack_matches_oracle_and_torch():
         assert torch.equal(q.cpu().view(torch.float8_e4m3fn).float() * sc0[:, None], deq0)
 
 
-W8_TILES = [1, 2, 6, 9, 19, 20]      # conv_gemm.hip: tile_has_w8
+W8_TILES = [1, 2, 6, 9, 19, 20]      # conv_gemm.hip: the kTiles rows with CAP_W8 (held against the table by tests/test_tile_table_cpu.py)
 
 
 @pytest.mark.parametrize("tile", W8_TILES)
