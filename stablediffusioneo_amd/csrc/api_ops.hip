@@ -124,6 +124,10 @@ const char* sdeo_debug_conv2d_kernel_name(int n, int h, int w, int cin, int cout
   return conv_gemm_kernel_name(p);
 }
 
+const char* sdeo_debug_attention_kernel_name(int B, int H, int Tq, int Tk, int d, int causal) {
+  return attention_kernel_name(B, H, Tq, Tk, d, causal);
+}
+
 // Plan query (tests): the ConvGemm of an sdeo_conv2d_nhwc_f16 / sdeo_gemm_f16 call, built by the same fill_conv / fill_gemm, with
 // `act` and armed fp8 weights (fp8 != 0) as that call would see them; returns the tuned-table key it looks up (key10) and the
 // (tile, split-K) the launcher picks.  Host only: no device call.

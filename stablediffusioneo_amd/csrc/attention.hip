@@ -677,33 +677,66 @@ static int launch_attn_ks(const AP2& ap2, int count, int B, hipStream_t stream) 
   return 0;
 }
 
-// key split pays when there are enough keys for the serial chain to dominate and the head dim keeps the merge small
-static int attn_key_split(const AP& ap, int d16) {
-  static const int forced = [] { const char* e = getenv("SDEO_ATTN_KS"); return e ? atoi(e) : 0; }();
-  if (d16 > 5) return 1;
-  if (forced) return forced;
-  return ap.Tk >= 128 ? 2 : 1;
+// Which kernel a problem runs.  attn_select is the ONLY place that decides it: the launcher switches on the value it returns and
+// attention_kernel_name (sdeo_debug_attention_kernel_name) formats it, so the name a test is told is the kernel a launch runs.
+struct AttnForm {
+  int wide;                  // DS of attention_wide_kernel<DS> (d = 4 DS), or 0: attention_kernel<d16, ks, mpad, qb>
+  int d16, ks, mpad, qb;
+};
+
+// Host only (no device call).  Depends on nothing but the shape: operands and strides are attn_prepare's.
+static int attn_select(AttnForm& f, int B, int H, int Tq, int Tk, int d, int causal) {
+  SDEO_CHECK(B > 0 && H > 0 && Tq > 0 && Tk > 0, "attention: bad sizes B=%d H=%d Tq=%d Tk=%d", B, H, Tq, Tk);
+  f = AttnForm{0, 0, 1, 0, 4};
+  if (d == 256 || d == 512) {
+    SDEO_CHECK(!causal, "attention: causal masking is not built for head dim %d", d);
+    f.wide = d / 4;
+    return 0;
+  }
+  const int d16 = cdiv(d, 16);
+  // instantiated k-step counts: 1..6, 8, 10 (7 and 9, d = 104 / 112 / 136 / 144, are not)
+  SDEO_CHECK(d % 8 == 0 && d >= 8 && d <= 160 && d16 != 7 && d16 != 9,
+             "attention: head dim %d unsupported (8..96 in steps of 8, 120, 128, 152, 160, 256, 512)", d);
+  SDEO_CHECK(!causal || Tq == Tk, "attention: causal needs Tq == Tk (got %d, %d)", Tq, Tk);
+  f.d16 = d16;
+  if (d16 > 5) return 0;
+  // a free K-dim slot right after the head's channels (d = 8, 24, 40, 56, 72): the reference-in-the-pad form
+  static const bool mpad_on = [] { const char* e = getenv("SDEO_ATTN_MPAD"); return !e || atoi(e) != 0; }();
+  f.mpad = mpad_on && d % 16 == 8;
+  // key split pays when there are enough keys for the serial chain to dominate and the head dim keeps the merge small
+  static const int ks_forced = [] { const char* e = getenv("SDEO_ATTN_KS"); return e ? atoi(e) : 0; }();
+  f.ks = (ks_forced ? ks_forced == 2 : Tk >= 128) ? 2 : 1;
+  if (f.ks == 2 && (d16 == 3 || d16 == 5)) {
+    // 64-query workgroups where 128-query ones leave CUs empty (T = 1024 on 16 (batch, head) pairs: 128 workgroups on 256 CUs;
+    // measured 19.3 -> 17.2 us at d = 80); with the chip already full they lose (T = 4096: 71 -> 95 us: twice the staging per
+    // query, one prefetch set).  SDEO_ATTN_QB = 2 / 4 forces one form (measurement).  Instantiated for d = 40 / 80.
+    static const int qb_forced = [] { const char* e = getenv("SDEO_ATTN_QB"); return e ? atoi(e) : 0; }();
+    const bool small_grid = cdiv(Tq, 128) * B * H < 256;
+    if (qb_forced ? qb_forced == 2 : small_grid) f.qb = 2;
+  }
+  return 0;
+}
+
+const char* attention_kernel_name(int B, int H, int Tq, int Tk, int d, int causal) {
+  static thread_local char name[48];
+  AttnForm f;
+  if (attn_select(f, B, H, Tq, Tk, d, causal)) return nullptr;
+  if (f.wide) snprintf(name, sizeof(name), "attention_wide_kernel<%d>", f.wide);
+  else snprintf(name, sizeof(name), "attention_kernel<%d,%d,%s,%d>", f.d16, f.ks, f.mpad ? "true" : "false", f.qb);
+  return name;
 }
 
 template <int D16>
-static int launch_attn(const AP2& ap, int count, int B, hipStream_t stream) {
+static int launch_attn(const AttnForm& f, const AP2& ap, int count, int B, hipStream_t stream) {
   if constexpr (D16 <= 5) {
-    // a free K-dim slot right after the head's channels (d = 8, 24, 40, 56, 72): the reference-in-the-pad form
-    static const bool mpad_on = [] { const char* e = getenv("SDEO_ATTN_MPAD"); return !e || atoi(e) != 0; }();
-    const bool mpad = mpad_on && ap.k[0].d % 16 == 8;
-    if (attn_key_split(ap.k[0], D16) == 2) {
+    if (f.ks == 2) {
       if constexpr (D16 == 3 || D16 == 5) {
-        // 64-query workgroups where 128-query ones leave CUs empty (T = 1024 on 16 (batch, head) pairs: 128 workgroups on 256 CUs;
-        // measured 19.3 -> 17.2 us at d = 80); with the chip already full they lose (T = 4096: 71 -> 95 us: twice the staging per
-        // query, one prefetch set).  SDEO_ATTN_QB = 2 / 4 forces one form (measurement).  Instantiated for d = 40 / 80.
-        static const int qb_forced = [] { const char* e = getenv("SDEO_ATTN_QB"); return e ? atoi(e) : 0; }();
-        const bool small_grid = cdiv(ap.k[0].Tq, 128) * B * ap.k[0].H < 256;
-        if (qb_forced ? qb_forced == 2 : small_grid)
-          return mpad ? launch_attn_ks<D16, 2, true, 2>(ap, count, B, stream) : launch_attn_ks<D16, 2, false, 2>(ap, count, B, stream);
+        if (f.qb == 2)
+          return f.mpad ? launch_attn_ks<D16, 2, true, 2>(ap, count, B, stream) : launch_attn_ks<D16, 2, false, 2>(ap, count, B, stream);
       }
-      return mpad ? launch_attn_ks<D16, 2, true>(ap, count, B, stream) : launch_attn_ks<D16, 2, false>(ap, count, B, stream);
+      return f.mpad ? launch_attn_ks<D16, 2, true>(ap, count, B, stream) : launch_attn_ks<D16, 2, false>(ap, count, B, stream);
     }
-    return mpad ? launch_attn_ks<D16, 1, true>(ap, count, B, stream) : launch_attn_ks<D16, 1, false>(ap, count, B, stream);
+    return f.mpad ? launch_attn_ks<D16, 1, true>(ap, count, B, stream) : launch_attn_ks<D16, 1, false>(ap, count, B, stream);
   } else {
     return launch_attn_ks<D16, 1, false>(ap, count, B, stream);
   }
@@ -711,42 +744,38 @@ static int launch_attn(const AP2& ap, int count, int B, hipStream_t stream) {
 
 static int attn_prepare(AP& ap, const AttnArgs& a) {
   SDEO_CHECK(a.o && a.q && a.k && a.v, "attention: null operand");
-  SDEO_CHECK(a.B > 0 && a.H > 0 && a.Tq > 0 && a.Tk > 0 && a.TkS >= a.Tk && a.TkSv >= a.Tk,
-             "attention: bad sizes B=%d H=%d Tq=%d Tk=%d TkS=%d TkSv=%d", a.B, a.H, a.Tq, a.Tk, a.TkS, a.TkSv);
-  SDEO_CHECK((a.d % 8 == 0 && a.d >= 8 && a.d <= 160) || a.d == 256 || a.d == 512,
-             "attention: head dim %d unsupported (multiple of 8 up to 160, or 256 / 512)", a.d);
-  SDEO_CHECK(a.d <= 160 || !a.causal, "attention: causal masking is not built for head dim %d", a.d);
+  SDEO_CHECK(a.TkS >= a.Tk && a.TkSv >= a.Tk, "attention: bad sizes Tk=%d TkS=%d TkSv=%d", a.Tk, a.TkS, a.TkSv);
   SDEO_CHECK(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 4 == 0,
              "attention: strides must keep 16-byte alignment (ldq=%d ldk=%d ldv=%d ldo=%d)", a.ldq, a.ldk, a.ldv, a.ldo);
   SDEO_CHECK((reinterpret_cast<uintptr_t>(a.q) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.k) & 15) == 0 &&
                  (reinterpret_cast<uintptr_t>(a.v) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.o) & 7) == 0,
              "attention: operands must be 16-byte aligned");
-  SDEO_CHECK(!a.causal || a.Tq == a.Tk, "attention: causal needs Tq == Tk (got %d, %d)", a.Tq, a.Tk);
   ap = AP{a.o, a.q, a.k, a.v, a.ldo, a.ldq, a.ldk, a.ldv, a.H, a.Tq, a.Tk, a.TkS, a.TkSv, a.d, a.scale * 1.4426950408889634f, a.causal ? 1 : 0};
   return 0;
 }
 
-static int attn_dispatch(const AP2& ap, int count, int B, hipStream_t stream) {
-  const int d = ap.k[0].d;
-  switch (cdiv(d, 16)) {
-    case 1: return launch_attn<1>(ap, count, B, stream);
-    case 2: return launch_attn<2>(ap, count, B, stream);
-    case 3: return launch_attn<3>(ap, count, B, stream);
-    case 4: return launch_attn<4>(ap, count, B, stream);
-    case 5: return launch_attn<5>(ap, count, B, stream);
-    case 6: return launch_attn<6>(ap, count, B, stream);
-    case 8: return launch_attn<8>(ap, count, B, stream);
-    case 10: return launch_attn<10>(ap, count, B, stream);
-    default: return fail("attention: head dim %d not instantiated", d);
+static int attn_dispatch(const AttnForm& f, const AP2& ap, int count, int B, hipStream_t stream) {
+  if (f.wide == 128) return launch_attn_wide<128>(ap.k[0], B, stream);
+  if (f.wide == 64) return launch_attn_wide<64>(ap.k[0], B, stream);
+  switch (f.d16) {
+    case 1: return launch_attn<1>(f, ap, count, B, stream);
+    case 2: return launch_attn<2>(f, ap, count, B, stream);
+    case 3: return launch_attn<3>(f, ap, count, B, stream);
+    case 4: return launch_attn<4>(f, ap, count, B, stream);
+    case 5: return launch_attn<5>(f, ap, count, B, stream);
+    case 6: return launch_attn<6>(f, ap, count, B, stream);
+    case 8: return launch_attn<8>(f, ap, count, B, stream);
+    case 10: return launch_attn<10>(f, ap, count, B, stream);
+    default: return fail("attention: no kernel for the selected form (d16 = %d)", f.d16);   // attn_select never returns one
   }
 }
 
 int attention(const AttnArgs& a, hipStream_t stream) {
   AP2 ap{};
+  AttnForm f;
   if (int rc = attn_prepare(ap.k[0], a)) return rc;
-  if (a.d == 512) return launch_attn_wide<128>(ap.k[0], a.B, stream);
-  if (a.d == 256) return launch_attn_wide<64>(ap.k[0], a.B, stream);
-  return attn_dispatch(ap, 1, a.B, stream);
+  if (int rc = attn_select(f, a.B, a.H, a.Tq, a.Tk, a.d, a.causal)) return rc;
+  return attn_dispatch(f, ap, 1, a.B, stream);
 }
 
 int attention(f16* o, int ldo, const f16* q, int ldq, const f16* k, int ldk, const f16* v, int ldv, int B, int H,

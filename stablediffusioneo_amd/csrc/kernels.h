@@ -129,6 +129,9 @@ struct AttnArgs {
   int causal;
 };
 int attention(const AttnArgs& a, hipStream_t stream);
+// the instantiation attention() launches for this shape ("attention_kernel<3,2,true,4>", "attention_wide_kernel<128>"), from the
+// launcher's own selection; nullptr with the error set for a shape attention() rejects.  Host only.
+const char* attention_kernel_name(int B, int H, int Tq, int Tk, int d, int causal);
 // vt[c][b*TkSv + t] = v[(b*T + t)*ldv + c]   (VAE AttnBlock's materialised-score path)
 int transpose_pad(f16* vt, int ldvt, const f16* v, int ldv, int B, int T, int TkSv, int C, hipStream_t stream);
 

@@ -14,6 +14,11 @@ void sdeo_debug_force_gemm_plan(int tile, int splitk);
 void sdeo_debug_force_gemm_order(int order); /* -1 heuristic, 0 M-fastest, 1 N-fastest tile order within an XCD */
 /* name of the kernel instantiation sdeo_conv2d_nhwc_f16 would launch for this problem (plan table / forced plan / heuristic) */
 const char* sdeo_debug_conv2d_kernel_name(int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x);
+/* name of the kernel instantiation sdeo_attention_f16 / sdeo_attention_causal_f16 would launch for this shape, template arguments as
+ * the device symbol carries them ("attention_kernel<3,2,true,4>": D16, KS, MPAD, QB; "attention_wide_kernel<128>"), formatted from
+ * the launcher's own selection.  NULL, with sdeo_last_error set, for a shape the launch rejects (head dim).  Host only, no device call;
+ * the string is valid until the calling thread's next query. */
+const char* sdeo_debug_attention_kernel_name(int B, int H, int Tq, int Tk, int d, int causal);
 /* plan queries (tests; host only, no device call): the problem of an sdeo_conv2d_nhwc_f16 / sdeo_gemm_f16 call of this shape with
  * `act` and, for fp8 != 0, fp8 weights -> the tuned-table key it looks up (key10) and the (tile, split-K) it would launch */
 int sdeo_debug_conv2d_plan(int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, int act, int fp8, int* key10,

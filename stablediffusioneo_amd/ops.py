@@ -286,20 +286,34 @@ def layernorm(x, gamma, beta, eps=1e-5):
     return y
 
 
-def attention(q, k, v, heads, tk=None, scale=None, causal=False):
-    """q (B,Tq,H*d), k (B,TkS,H*d), v (B,TkS,H*d) fp16 -> (B,Tq,H*d); causal masks key j > query t (Tq == tk)."""
+def _rows_view(t, what):
+    """(row stride, in elements) of a (B, rows, C) operand the attention kernels can address: unit inner stride, batches stacked
+    at rows x row stride (a contiguous tensor, or a column block / row prefix of a wider buffer)"""
+    b, rows, _ = t.shape
+    ld = t.stride(1)
+    assert t.dtype == torch.float16 and t.stride(2) == 1 and (b == 1 or t.stride(0) == rows * ld), \
+        f"attention: {what} must be fp16 with unit inner stride and batch stride = rows x row stride (shape {tuple(t.shape)}, strides {t.stride()})"
+    return ld
+
+
+def attention(q, k, v, heads, tk=None, scale=None, causal=False, out=None):
+    """q (B,Tq,H*d), k (B,TkS,H*d), v (B,TkSv,H*d) fp16 -> (B,Tq,H*d); causal masks key j > query t (Tq == tk).
+    Operands may be column blocks of wider buffers (the fused q|k|v projection, the k|v context buffer): the row stride is taken
+    from .stride(1).  k and v may pad their rows differently (keys >= tk are masked).  out: optional destination view of the same kind."""
     lib = _lib.load()
-    _need_cuda(q, k, v)
+    _need_cuda(q, k, v, out)
     b, tq, c = q.shape
-    tks = k.shape[1]
-    tk = tks if tk is None else tk
+    tks, tksv = k.shape[1], v.shape[1]
+    tk = min(tks, tksv) if tk is None else tk
     d = c // heads
     scale = d ** -0.5 if scale is None else scale
-    assert q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and v.shape == k.shape
-    o = torch.empty_like(q)
+    assert k.shape[0] == b and v.shape[0] == b and k.shape[2] == c and v.shape[2] == c
+    o = torch.empty_like(q, memory_format=torch.contiguous_format) if out is None else out
+    assert o.shape == q.shape
+    ldq, ldk, ldv, ldo = _rows_view(q, "q"), _rows_view(k, "k"), _rows_view(v, "v"), _rows_view(o, "out")
     fn = lib.sdeo_attention_causal_f16 if causal else lib.sdeo_attention_f16
-    check(fn(ptr(o), _i(c), ptr(q), _i(c), ptr(k), _i(k.shape[2]), ptr(v), _i(v.shape[2]), _i(b), _i(heads),
-             _i(tq), _i(tk), _i(tks), _i(tks), _i(d), _f(scale), cur_stream()), "attention")
+    check(fn(ptr(o), _i(ldo), ptr(q), _i(ldq), ptr(k), _i(ldk), ptr(v), _i(ldv), _i(b), _i(heads),
+             _i(tq), _i(tk), _i(tks), _i(tksv), _i(d), _f(scale), cur_stream()), "attention")
     return o
 
 
