@@ -7,37 +7,14 @@
 //   out = final_layer_norm(x)                              (LayerNorm eps 1e-5 throughout)
 // Built from the same hand-written kernels as the UNet (layernorm, LDS-DMA GEMM with fused bias / activation /
 // residual epilogues, flash attention with a causal mask).  q_proj and k_proj are stacked into one GEMM.
-#include <map>
-#include <string>
-#include <vector>
-#include <functional>
-
 #include "../../include/sdeo.h"
-#include "kernels.h"
+#include "handle_common.h"
 
 using namespace sdeo;
 
-namespace {
-
-struct CWeight {
-  std::string name;
-  int64_t dims[2];
-  int ndim;
-  bool matrix;       // fp16 [rows][cols] (else fp32 vector)
-  size_t off;
-  bool loaded;
-};
-
-}  // namespace
-
 struct sdeo_clip_handle_s {
   sdeo_clip_config cfg{};
-  std::vector<CWeight> weights;
-  std::map<std::string, int> index;
-  char* slab = nullptr;
-  size_t slab_bytes = 0;
-  float* stage = nullptr;
-  size_t stage_bytes = 0;
+  WeightStore ws;
   bool finalized = false;
   // configured state
   int batch = 0;
@@ -46,7 +23,7 @@ struct sdeo_clip_handle_s {
   float* splitk_ws = nullptr;
   size_t splitk_bytes = 0;
   int32_t* tokens = nullptr;
-  std::vector<std::function<int(hipStream_t)>> prog;
+  Program prog;
   f16* out16 = nullptr;
 };
 
@@ -54,57 +31,40 @@ namespace {
 
 typedef sdeo_clip_handle_s Clip;
 
-static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-static void add_w(Clip* e, const std::string& name, bool matrix, int64_t d0, int64_t d1, size_t off) {
-  CWeight w{name, {d0, d1}, matrix ? 2 : 1, matrix, off, false};
-  e->index[name] = (int)e->weights.size();
-  e->weights.push_back(w);
-}
-
 // names follow the HuggingFace state dict below "text_model." (the SD checkpoint stores them as
 // "cond_stage_model.transformer.text_model.*"; sdeo_clip_load_weight strips everything up to "text_model.")
 static void build_registry(Clip* e) {
   const sdeo_clip_config& c = e->cfg;
-  size_t size = 0;
-  auto take = [&](size_t bytes) { const size_t off = align256(size); size = off + bytes; return off; };
+  WeightStore& r = e->ws;
   const int W = c.width, F = c.ffn;
-  add_w(e, "embeddings.token_embedding.weight", true, c.vocab, W, take((size_t)c.vocab * W * 2));
-  add_w(e, "embeddings.position_embedding.weight", true, c.positions, W, take((size_t)c.positions * W * 2));
+  auto mat = [&](const std::string& n, int rows, int cols, size_t off) { r.add(n, W_LINEAR, {rows, cols}, off); };
+  auto vec = [&](const std::string& n, int len, size_t off) { r.add(n, W_VEC, {len}, off); };
+  mat("embeddings.token_embedding.weight", c.vocab, W, r.take((size_t)c.vocab * W * 2));
+  mat("embeddings.position_embedding.weight", c.positions, W, r.take((size_t)c.positions * W * 2));
   for (int l = 0; l < c.layers; ++l) {
     const std::string p = "encoder.layers." + std::to_string(l) + ".";
     // q_proj, k_proj and v_proj stacked: one [3W][W] matrix and one [3W] bias (one GEMM; the attention kernel reads V row-major)
-    const size_t qkv = take((size_t)3 * W * W * 2), qkvb = take((size_t)3 * W * 4);
-    add_w(e, p + "self_attn.q_proj.weight", true, W, W, qkv);
-    add_w(e, p + "self_attn.k_proj.weight", true, W, W, qkv + (size_t)W * W * 2);
-    add_w(e, p + "self_attn.v_proj.weight", true, W, W, qkv + (size_t)2 * W * W * 2);
-    add_w(e, p + "self_attn.q_proj.bias", false, W, 0, qkvb);
-    add_w(e, p + "self_attn.k_proj.bias", false, W, 0, qkvb + (size_t)W * 4);
-    add_w(e, p + "self_attn.v_proj.bias", false, W, 0, qkvb + (size_t)2 * W * 4);
-    add_w(e, p + "self_attn.out_proj.weight", true, W, W, take((size_t)W * W * 2));
-    add_w(e, p + "self_attn.out_proj.bias", false, W, 0, take((size_t)W * 4));
-    add_w(e, p + "layer_norm1.weight", false, W, 0, take((size_t)W * 4));
-    add_w(e, p + "layer_norm1.bias", false, W, 0, take((size_t)W * 4));
-    add_w(e, p + "mlp.fc1.weight", true, F, W, take((size_t)F * W * 2));
-    add_w(e, p + "mlp.fc1.bias", false, F, 0, take((size_t)F * 4));
-    add_w(e, p + "mlp.fc2.weight", true, W, F, take((size_t)W * F * 2));
-    add_w(e, p + "mlp.fc2.bias", false, W, 0, take((size_t)W * 4));
-    add_w(e, p + "layer_norm2.weight", false, W, 0, take((size_t)W * 4));
-    add_w(e, p + "layer_norm2.bias", false, W, 0, take((size_t)W * 4));
+    const size_t qkv = r.take((size_t)3 * W * W * 2), qkvb = r.take((size_t)3 * W * 4);
+    mat(p + "self_attn.q_proj.weight", W, W, qkv);
+    mat(p + "self_attn.k_proj.weight", W, W, qkv + (size_t)W * W * 2);
+    mat(p + "self_attn.v_proj.weight", W, W, qkv + (size_t)2 * W * W * 2);
+    vec(p + "self_attn.q_proj.bias", W, qkvb);
+    vec(p + "self_attn.k_proj.bias", W, qkvb + (size_t)W * 4);
+    vec(p + "self_attn.v_proj.bias", W, qkvb + (size_t)2 * W * 4);
+    mat(p + "self_attn.out_proj.weight", W, W, r.take((size_t)W * W * 2));
+    vec(p + "self_attn.out_proj.bias", W, r.take((size_t)W * 4));
+    vec(p + "layer_norm1.weight", W, r.take((size_t)W * 4));
+    vec(p + "layer_norm1.bias", W, r.take((size_t)W * 4));
+    mat(p + "mlp.fc1.weight", F, W, r.take((size_t)F * W * 2));
+    vec(p + "mlp.fc1.bias", F, r.take((size_t)F * 4));
+    mat(p + "mlp.fc2.weight", W, F, r.take((size_t)W * F * 2));
+    vec(p + "mlp.fc2.bias", W, r.take((size_t)W * 4));
+    vec(p + "layer_norm2.weight", W, r.take((size_t)W * 4));
+    vec(p + "layer_norm2.bias", W, r.take((size_t)W * 4));
   }
-  add_w(e, "final_layer_norm.weight", false, W, 0, take((size_t)W * 4));
-  add_w(e, "final_layer_norm.bias", false, W, 0, take((size_t)W * 4));
-  e->slab_bytes = align256(size);
-  size_t mx = 0;
-  for (auto& w : e->weights) {
-    const size_t n = (size_t)w.dims[0] * (w.ndim == 2 ? (size_t)w.dims[1] : 1);
-    mx = n > mx ? n : mx;
-  }
-  e->stage_bytes = mx * sizeof(float);
+  vec("final_layer_norm.weight", W, r.take((size_t)W * 4));
+  vec("final_layer_norm.bias", W, r.take((size_t)W * 4));
 }
-
-static const f16* wp(Clip* e, const std::string& n) { return reinterpret_cast<const f16*>(e->slab + e->weights[e->index.at(n)].off); }
-static const float* vp(Clip* e, const std::string& n) { return reinterpret_cast<const float*>(e->slab + e->weights[e->index.at(n)].off); }
 
 static void free_configured(Clip* e) {
   if (e->act) (void)hipFree(e->act);
@@ -129,10 +89,9 @@ int sdeo_clip_create(const sdeo_clip_config* cfg, sdeo_clip_handle* out) {
   Clip* e = new Clip();
   e->cfg = *cfg;
   build_registry(e);
-  if (hipMalloc((void**)&e->slab, e->slab_bytes) != hipSuccess) {
-    const size_t want = e->slab_bytes;
+  if (int rc = e->ws.alloc("sdeo_clip_create", /*zero_fill=*/false)) {
     delete e;
-    return fail("sdeo_clip_create: cannot allocate %zu bytes of weights", want);
+    return rc;
   }
   *out = e;
   return 0;
@@ -141,20 +100,16 @@ int sdeo_clip_create(const sdeo_clip_config* cfg, sdeo_clip_handle* out) {
 int sdeo_clip_destroy(sdeo_clip_handle h) {
   if (!h) return 0;
   free_configured(h);
-  if (h->slab) (void)hipFree(h->slab);
-  if (h->stage) (void)hipFree(h->stage);
+  h->ws.destroy();
   delete h;
   return 0;
 }
 
-int sdeo_clip_num_weights(sdeo_clip_handle h) { return h ? (int)h->weights.size() : 0; }
+int sdeo_clip_num_weights(sdeo_clip_handle h) { return h ? (int)h->ws.entries.size() : 0; }
 
 int sdeo_clip_weight_info(sdeo_clip_handle h, int i, const char** name, int64_t dims[2], int* ndim) {
-  SDEO_CHECK(h && i >= 0 && i < (int)h->weights.size() && name && dims && ndim, "sdeo_clip_weight_info: bad argument");
-  const CWeight& w = h->weights[i];
-  *name = w.name.c_str();
-  dims[0] = w.dims[0]; dims[1] = w.ndim == 2 ? w.dims[1] : 0;
-  *ndim = w.ndim;
+  SDEO_CHECK(h && i >= 0 && i < (int)h->ws.entries.size() && name && dims && ndim, "sdeo_clip_weight_info: bad argument");
+  h->ws.info(i, name, dims, 2, 0, ndim);
   return 0;
 }
 
@@ -163,43 +118,12 @@ int sdeo_clip_load_weight(sdeo_clip_handle h, const char* name, const float* hos
   std::string key(name);
   const size_t pos = key.find("text_model.");
   if (pos != std::string::npos) key = key.substr(pos + 11);
-  auto it = h->index.find(key);
-  if (it == h->index.end()) {
-    if (strict) return fail("sdeo_clip_load_weight: unexpected tensor '%s'", name);
-    return 0;
-  }
-  CWeight& w = h->weights[it->second];
-  SDEO_CHECK(ndim == w.ndim, "sdeo_clip_load_weight: %s has %d dims, expected %d", name, ndim, w.ndim);
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) {
-    SDEO_CHECK(dims[i] == w.dims[i], "sdeo_clip_load_weight: %s dim %d is %lld, expected %lld", name, i, (long long)dims[i],
-               (long long)w.dims[i]);
-    n *= (size_t)dims[i];
-  }
-  if (!h->stage) SDEO_HIP(hipMalloc((void**)&h->stage, h->stage_bytes));
-  SDEO_HIP(hipMemcpy(h->stage, host_data, n * sizeof(float), hipMemcpyDefault));
-  void* dst = h->slab + w.off;
-  if (w.matrix) {
-    if (int rc = f32_to_f16((f16*)dst, h->stage, (int64_t)n, 0)) return rc;
-  } else {
-    SDEO_HIP(hipMemcpy(dst, h->stage, n * sizeof(float), hipMemcpyDeviceToDevice));
-  }
-  SDEO_HIP(hipDeviceSynchronize());
-  w.loaded = true;
-  return 0;
+  return h->ws.load("sdeo_clip_load_weight", name, key, host_data, dims, ndim, strict);
 }
 
 int sdeo_clip_finalize_weights(sdeo_clip_handle h) {
   SDEO_CHECK(h, "sdeo_clip_finalize_weights: null handle");
-  std::string missing;
-  int nmiss = 0;
-  for (auto& w : h->weights)
-    if (!w.loaded) {
-      if (nmiss < 5) missing += (nmiss ? ", " : "") + w.name;
-      ++nmiss;
-    }
-  SDEO_CHECK(nmiss == 0, "sdeo_clip_finalize_weights: %d tensors missing (%s%s)", nmiss, missing.c_str(), nmiss > 5 ? ", ..." : "");
-  if (h->stage) { (void)hipFree(h->stage); h->stage = nullptr; }
+  if (int rc = h->ws.require_all("sdeo_clip_finalize_weights")) return rc;
   h->finalized = true;
   return 0;
 }
@@ -214,10 +138,10 @@ int sdeo_clip_configure(sdeo_clip_handle h, int batch) {
   const int rows = B * T;
   // activation buffers (fp16): xa, xb, a [rows][W]; qkv [rows][3W]; o [rows][W]; hid [rows][F]
   size_t off = 0;
-  auto take = [&](size_t elems) { const size_t o = align256(off); off = o + elems * 2; return o; };
+  auto take = [&](size_t elems) { const size_t o = align_up(off, 256); off = o + elems * 2; return o; };
   const size_t o_xa = take((size_t)rows * W), o_xb = take((size_t)rows * W), o_a = take((size_t)rows * W),
                o_qkv = take((size_t)rows * 3 * W), o_o = take((size_t)rows * W), o_h = take((size_t)rows * F);
-  e->act_bytes = align256(off);
+  e->act_bytes = align_up(off, 256);
   SDEO_HIP(hipMalloc((void**)&e->act, e->act_bytes));
   SDEO_HIP(hipMemset(e->act, 0, e->act_bytes));
   SDEO_HIP(hipMalloc((void**)&e->tokens, (size_t)rows * sizeof(int32_t)));
@@ -231,42 +155,41 @@ int sdeo_clip_configure(sdeo_clip_handle h, int batch) {
     p.B = rows; p.Cin = K; p.M = rows; p.N = N; p.K = K; p.ldx = K; p.ldw = K; p.ldy = N; p.act = act;
     const size_t need = conv_gemm_workspace_bytes(p);
     ws = need > ws ? need : ws;
-    e->prog.push_back([p, e](hipStream_t s) mutable {
+    e->prog.push_back(Op([p, e](hipStream_t s) mutable {
       p.workspace = e->splitk_ws;
       p.workspace_bytes = e->splitk_bytes;
       return conv_gemm(p, s);
-    });
+    }, conv_gemm_kernel_name(p), 2.0 * p.M * p.N * p.K, 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N)));
   };
-  const f16* tok = wp(e, "embeddings.token_embedding.weight");
-  const f16* pos = wp(e, "embeddings.position_embedding.weight");
+  auto ln = [&](const f16* xi, const float* g, const float* b) {
+    e->prog.push_back(Op([=](hipStream_t s) { return layernorm(a, W, xi, W, g, b, rows, W, 1e-5f, s); }, "layernorm", 0, 4.0 * rows * W));
+  };
+  auto wp = [&](const std::string& n) { return e->ws.ptr<f16>(n); };
+  auto vp = [&](const std::string& n) { return e->ws.ptr<float>(n); };
+  const f16* tok = wp("embeddings.token_embedding.weight");
+  const f16* pos = wp("embeddings.position_embedding.weight");
   const int32_t* ids = e->tokens;
   const int vocab = c.vocab;
-  e->prog.push_back([=](hipStream_t s) { return embed_tokens(xa, ids, tok, pos, B, T, W, vocab, s); });
+  e->prog.push_back(Op([=](hipStream_t s) { return embed_tokens(xa, ids, tok, pos, B, T, W, vocab, s); }, "embed_tokens"));
   f16* x = xa;
   f16* xn = xb;
   const float scale = 1.0f / sqrtf((float)d);
   for (int l = 0; l < c.layers; ++l) {
     const std::string p = "encoder.layers." + std::to_string(l) + ".";
-    const float *g1 = vp(e, p + "layer_norm1.weight"), *b1 = vp(e, p + "layer_norm1.bias");
-    const float *g2 = vp(e, p + "layer_norm2.weight"), *b2 = vp(e, p + "layer_norm2.bias");
-    { const f16* xi = x; e->prog.push_back([=](hipStream_t s) { return layernorm(a, W, xi, W, g1, b1, rows, W, 1e-5f, s); }); }
-    gemm(a, W, wp(e, p + "self_attn.q_proj.weight"), 3 * W, vp(e, p + "self_attn.q_proj.bias"), 0, nullptr, qkv);
-    e->prog.push_back([=](hipStream_t s) {
+    ln(x, vp(p + "layer_norm1.weight"), vp(p + "layer_norm1.bias"));
+    gemm(a, W, wp(p + "self_attn.q_proj.weight"), 3 * W, vp(p + "self_attn.q_proj.bias"), 0, nullptr, qkv);
+    e->prog.push_back(Op([=](hipStream_t s) {
       return attention(o, W, qkv, 3 * W, qkv + W, 3 * W, qkv + 2 * W, 3 * W, B, H, T, T, T, T, d, scale, s, /*causal=*/1);
-    });
-    gemm(o, W, wp(e, p + "self_attn.out_proj.weight"), W, vp(e, p + "self_attn.out_proj.bias"), 0, x, xn);
+    }, "attention", 4.0 * B * H * (double)T * T * d, 2.0 * B * H * d * (2.0 * T + 2.0 * T)));
+    gemm(o, W, wp(p + "self_attn.out_proj.weight"), W, vp(p + "self_attn.out_proj.bias"), 0, x, xn);
     std::swap(x, xn);
-    { const f16* xi = x; e->prog.push_back([=](hipStream_t s) { return layernorm(a, W, xi, W, g2, b2, rows, W, 1e-5f, s); }); }
-    gemm(a, W, wp(e, p + "mlp.fc1.weight"), F, vp(e, p + "mlp.fc1.bias"), 2, nullptr, hid);
-    gemm(hid, F, wp(e, p + "mlp.fc2.weight"), W, vp(e, p + "mlp.fc2.bias"), 0, x, xn);
+    ln(x, vp(p + "layer_norm2.weight"), vp(p + "layer_norm2.bias"));
+    gemm(a, W, wp(p + "mlp.fc1.weight"), F, vp(p + "mlp.fc1.bias"), 2, nullptr, hid);
+    gemm(hid, F, wp(p + "mlp.fc2.weight"), W, vp(p + "mlp.fc2.bias"), 0, x, xn);
     std::swap(x, xn);
   }
-  {
-    const float *g = vp(e, "final_layer_norm.weight"), *b = vp(e, "final_layer_norm.bias");
-    const f16* xi = x;
-    e->prog.push_back([=](hipStream_t s) { return layernorm(a, W, xi, W, g, b, rows, W, 1e-5f, s); });
-    e->out16 = a;
-  }
+  ln(x, vp("final_layer_norm.weight"), vp("final_layer_norm.bias"));
+  e->out16 = a;
   e->splitk_bytes = ws;
   if (ws) SDEO_HIP(hipMalloc((void**)&e->splitk_ws, ws));
   e->batch = B;
@@ -279,11 +202,10 @@ int sdeo_clip_encode(sdeo_clip_handle h, const int32_t* tokens, int batch, float
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const size_t rows = (size_t)batch * h->cfg.positions;
   SDEO_HIP(hipMemcpyAsync(h->tokens, tokens, rows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  for (auto& op : h->prog)
-    if (int rc = op(s)) return rc;
+  if (int rc = run_program(h->prog, s)) return rc;
   return f16_to_f32(out, h->out16, (int64_t)rows * h->cfg.width, s);
 }
 
-size_t sdeo_clip_device_bytes(sdeo_clip_handle h) { return h ? h->slab_bytes + h->act_bytes + h->splitk_bytes : 0; }
+size_t sdeo_clip_device_bytes(sdeo_clip_handle h) { return h ? h->ws.slab_bytes + h->act_bytes + h->splitk_bytes : 0; }
 
 }  // extern "C"

@@ -1,0 +1,211 @@
+// Host-side machinery shared by the network handles (net.hip, clip.hip, hed.hip): the weight registry / slab / loader and the
+// program runner with its per-launch profiler.  A handle registers its tensors (take / add), allocates the slab once, forwards its
+// *_weight_info / *_load_weight / *_finalize_weights entry points here, and unrolls its network into a Program at configure time.
+#pragma once
+#include <stdlib.h>
+
+#include <algorithm>
+#include <functional>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "kernels.h"
+
+namespace sdeo {
+
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// how sdeo_*_load_weight stores a tensor: fp16 KRSC [O][R][S][ipad] conv weight, fp16 [rows][cols] matrix, fp32 as is, and
+// ff.net.0.proj with its value / gate rows interleaved
+enum WKind { W_CONV, W_LINEAR, W_VEC, W_GEGLU_W, W_GEGLU_B };
+struct WEntry {
+  std::string name;
+  int64_t dims[4];
+  int ndim;
+  WKind kind;
+  size_t off;      // byte offset into the weight slab
+  int ipad;        // conv: stored (padded) input channels
+  bool loaded;
+};
+
+struct WeightStore {
+  std::vector<WEntry> entries;
+  std::unordered_map<std::string, int> index;
+  size_t size = 0;           // bytes handed out by take()
+  char* slab = nullptr;
+  size_t slab_bytes = 0;
+  float* stage = nullptr;    // fp32 upload buffer of the largest tensor: allocated by the first load, freed by require_all
+  size_t stage_bytes = 0;
+
+  size_t take(size_t bytes) {
+    const size_t off = align_up(size, 256);
+    size = off + bytes;
+    return off;
+  }
+  // `off` is the caller's: tensors stacked into one matrix (q | k | v) share one take()
+  void add(const std::string& name, WKind kind, std::initializer_list<int64_t> dims, size_t off, int ipad = 0) {
+    WEntry w{name, {1, 1, 1, 1}, (int)dims.size(), kind, off, ipad, false};
+    int i = 0;
+    for (auto d : dims) w.dims[i++] = d;
+    index[name] = (int)entries.size();
+    entries.push_back(w);
+  }
+  const WEntry* find(const std::string& name) const {
+    auto it = index.find(name);
+    return it == index.end() ? nullptr : &entries[it->second];
+  }
+  template <class T>
+  const T* ptr(const std::string& name) const { return reinterpret_cast<const T*>(slab + entries[index.at(name)].off); }
+
+  // (re)allocate the slab for everything registered so far; nothing loaded survives
+  int alloc(const char* who, bool zero_fill) {
+    destroy();
+    slab_bytes = align_up(size, 256);
+    if (hipMalloc((void**)&slab, slab_bytes) != hipSuccess) {
+      slab = nullptr;
+      return fail("%s: cannot allocate %zu bytes of weights", who, slab_bytes);
+    }
+    if (zero_fill) SDEO_HIP(hipMemset(slab, 0, slab_bytes));
+    size_t mx = 0;
+    for (auto& w : entries) mx = std::max(mx, (size_t)(w.dims[0] * w.dims[1] * w.dims[2] * w.dims[3]));
+    stage_bytes = mx * sizeof(float);
+    return 0;
+  }
+  void destroy() {
+    if (slab) (void)hipFree(slab);
+    if (stage) (void)hipFree(stage);
+    slab = nullptr; stage = nullptr;
+  }
+
+  // dims[k] = pad for k in [ndim, ndims); null outputs are skipped (each entry point checks the ones it requires)
+  void info(int i, const char** name, int64_t* dims, int ndims, int64_t pad, int* ndim) const {
+    const WEntry& w = entries[i];
+    if (name) *name = w.name.c_str();
+    if (ndim) *ndim = w.ndim;
+    if (dims) for (int k = 0; k < ndims; ++k) dims[k] = k < w.ndim ? w.dims[k] : pad;
+  }
+
+  // `who` is the public entry point and `name` what its caller passed (both only for messages); `key` is the registry name
+  int load(const char* who, const char* name, const std::string& key, const float* host_data, const int64_t* dims, int ndim, int strict) {
+    auto it = index.find(key);
+    if (it == index.end()) {
+      if (strict) return fail("%s: unexpected tensor '%s'", who, name);
+      return 0;
+    }
+    WEntry& w = entries[it->second];
+    SDEO_CHECK(ndim == w.ndim, "%s: %s has %d dims, expected %d", who, name, ndim, w.ndim);
+    size_t n = 1;
+    for (int i = 0; i < ndim; ++i) {
+      SDEO_CHECK(dims[i] == w.dims[i], "%s: %s dim %d is %lld, expected %lld", who, name, i, (long long)dims[i], (long long)w.dims[i]);
+      n *= (size_t)dims[i];
+    }
+    if (!stage) SDEO_HIP(hipMalloc((void**)&stage, stage_bytes));
+    SDEO_HIP(hipMemcpy(stage, host_data, n * sizeof(float), hipMemcpyDefault));
+    void* dst = slab + w.off;
+    int rc = 0;
+    switch (w.kind) {
+      case W_CONV: rc = oihw_f32_to_ohwi_f16((f16*)dst, stage, (int)w.dims[0], (int)w.dims[1], (int)w.dims[2], (int)w.dims[3], w.ipad, 0); break;
+      case W_LINEAR: rc = f32_to_f16((f16*)dst, stage, (int64_t)n, 0); break;
+      case W_VEC: SDEO_HIP(hipMemcpy(dst, stage, n * sizeof(float), hipMemcpyDeviceToDevice)); break;
+      case W_GEGLU_W: rc = geglu_interleave_f32_to_f16((f16*)dst, stage, (int)(w.dims[0] / 2), (int)w.dims[1], 0); break;
+      case W_GEGLU_B: rc = geglu_interleave_f32((float*)dst, stage, (int)(w.dims[0] / 2), 0); break;
+    }
+    if (rc) return rc;
+    SDEO_HIP(hipDeviceSynchronize());
+    w.loaded = true;
+    return 0;
+  }
+
+  int require_all(const char* who) {
+    std::string missing;
+    int nmiss = 0;
+    for (auto& w : entries)
+      if (!w.loaded) {
+        if (nmiss < 5) missing += (nmiss ? ", " : "") + w.name;
+        ++nmiss;
+      }
+    SDEO_CHECK(nmiss == 0, "%s: %d tensors missing (%s%s)", who, nmiss, missing.c_str(), nmiss > 5 ? ", ..." : "");
+    if (stage) { (void)hipFree(stage); stage = nullptr; }
+    return 0;
+  }
+};
+
+struct Op {          // one launch of a program + what it is for the profiler
+  std::function<int(hipStream_t)> fn;
+  const char* key = "other";
+  std::string tag;           // problem shape, shown by the profiler when SDEO_PROFILE_DETAIL=1
+  double flops = 0, bytes = 0;
+  bool zero_conv = false;    // net.hip's ControlNet program: a zero conv (skipped when the UNet decoder applies the zero convs itself)
+  template <class F>
+  Op(F f, const char* key_ = "other", double flops_ = 0, double bytes_ = 0, std::string tag_ = std::string())
+      : fn(std::move(f)), key(key_), tag(std::move(tag_)), flops(flops_), bytes(bytes_) {}
+  int operator()(hipStream_t s) const { return fn(s); }
+};
+typedef std::vector<Op> Program;
+
+// HIP events around every launch between begin() and end(); end() synchronises and reports per key
+struct Profiler {
+  struct Rec { std::string key; double flops, bytes; hipEvent_t a, b; };
+  bool on = false;
+  std::vector<Rec> recs;
+  std::string report;
+
+  void begin() {
+    for (auto& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+    recs.clear();
+    on = true;
+  }
+  int record(const Op& op, hipStream_t s) {
+    static const bool detail = [] { const char* v = getenv("SDEO_PROFILE_DETAIL"); return v && atoi(v) != 0; }();
+    Rec r{detail && !op.tag.empty() ? std::string(op.key) + " | " + op.tag : std::string(op.key), op.flops, op.bytes, nullptr, nullptr};
+    SDEO_HIP(hipEventCreate(&r.a));
+    SDEO_HIP(hipEventCreate(&r.b));
+    SDEO_HIP(hipEventRecord(r.a, s));
+    if (int rc = op(s)) return rc;
+    SDEO_HIP(hipEventRecord(r.b, s));
+    recs.push_back(r);
+    return 0;
+  }
+  // JSON array [{"kernel", "launches", "total_ms", "flops", "bytes"}] in order of first appearance
+  const char* end() {
+    on = false;
+    (void)hipDeviceSynchronize();
+    struct Agg { long n = 0; double ms = 0, flops = 0, bytes = 0; };
+    std::vector<std::pair<std::string, Agg>> aggs;
+    for (auto& r : recs) {
+      float ms = 0.f;
+      (void)hipEventElapsedTime(&ms, r.a, r.b);
+      (void)hipEventDestroy(r.a);
+      (void)hipEventDestroy(r.b);
+      size_t i = 0;
+      for (; i < aggs.size(); ++i) if (aggs[i].first == r.key) break;
+      if (i == aggs.size()) aggs.push_back({r.key, Agg()});
+      aggs[i].second.n += 1; aggs[i].second.ms += ms; aggs[i].second.flops += r.flops; aggs[i].second.bytes += r.bytes;
+    }
+    recs.clear();
+    report = "[";
+    char buf[768];
+    for (size_t i = 0; i < aggs.size(); ++i) {
+      snprintf(buf, sizeof(buf), "%s{\"kernel\": \"%s\", \"launches\": %ld, \"total_ms\": %.6f, \"flops\": %.6e, \"bytes\": %.6e}",
+               i ? ", " : "", aggs[i].first.c_str(), aggs[i].second.n, aggs[i].second.ms, aggs[i].second.flops, aggs[i].second.bytes);
+      report += buf;
+    }
+    report += "]";
+    return report.c_str();
+  }
+};
+
+// profiling off (or no profiler): one std::function call per op and nothing else
+static inline int run_program(const Program& p, hipStream_t s, Profiler* prof = nullptr) {
+  if (!prof || !prof->on) {
+    for (auto& op : p)
+      if (int rc = op(s)) return rc;
+    return 0;
+  }
+  for (auto& op : p)
+    if (int rc = prof->record(op, s)) return rc;
+  return 0;
+}
+
+}  // namespace sdeo

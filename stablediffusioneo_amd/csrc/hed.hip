@@ -10,13 +10,8 @@
 //                        block output)
 //   hed_fuse_kernel      cv2.resize INTER_LINEAR on float32 (= F.interpolate bilinear, align_corners=False) of the five maps at each
 //                        output pixel, fp32 mean in numpy's order, fp64 sigmoid, truncation to uint8 (+ optional control tensor)
-#include <map>
-#include <string>
-#include <vector>
-#include <functional>
-
 #include "../../include/sdeo.h"
-#include "kernels.h"
+#include "handle_common.h"
 
 using namespace sdeo;
 
@@ -179,34 +174,13 @@ int hed_fuse(uint8_t* edges, float* control, const HedMaps& maps, int H, int W, 
 // ------------------------------------------------------------------------------------------------ handle
 namespace {
 
-struct HWeight {
-  std::string name;
-  int64_t dims[4];
-  int ndim;
-  bool conv;         // fp16 KRSC [O][3][3][cin_pad] (else fp32, stored as is)
-  int cin_pad;
-  size_t off;
-  bool loaded;
-};
-
-struct HedOp {
-  std::function<int(hipStream_t)> fn;
-  std::string name;
-  double flops;
-};
-
 const int kBlockConvs[5] = {2, 2, 3, 3, 3};
 const int kBlockCh[5] = {64, 128, 256, 512, 512};
 
 }  // namespace
 
 struct sdeo_hed_handle_s {
-  std::vector<HWeight> weights;
-  std::map<std::string, int> index;
-  char* slab = nullptr;
-  size_t slab_bytes = 0;
-  float* stage = nullptr;
-  size_t stage_bytes = 0;
+  WeightStore ws;
   bool finalized = false;
   // configured state
   int H = 0, W = 0;
@@ -218,50 +192,32 @@ struct sdeo_hed_handle_s {
   uint8_t* edges = nullptr;
   float* control = nullptr;
   HedMaps maps{};
-  std::vector<HedOp> prog;
+  Program prog;
+  Profiler prof;                     // sdeo_debug_hed_profile
 };
 
 namespace {
 
 typedef sdeo_hed_handle_s Hed;
 
-static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-static void add_w(Hed* e, const std::string& name, int ndim, const int64_t* dims, bool conv, int cin_pad, size_t bytes, size_t& size) {
-  HWeight w{name, {1, 1, 1, 1}, ndim, conv, cin_pad, 0, false};
-  for (int i = 0; i < ndim; ++i) w.dims[i] = dims[i];
-  w.off = align256(size);
-  size = w.off + bytes;
-  e->index[name] = (int)e->weights.size();
-  e->weights.push_back(w);
-}
-
 // reference state-dict order: norm, then per block convs.{i}.weight / bias and projection.weight / bias
 static void build_registry(Hed* e) {
-  size_t size = 0, mx = 3;
-  const int64_t nd[4] = {1, 3, 1, 1};
-  add_w(e, "norm", 4, nd, false, 0, 3 * 4, size);
+  WeightStore& r = e->ws;
+  r.add("norm", W_VEC, {1, 3, 1, 1}, r.take(3 * 4));
   int cin = 3;
   for (int b = 0; b < 5; ++b) {
     const std::string p = "block" + std::to_string(b + 1) + ".";
     const int c = kBlockCh[b];
     for (int i = 0; i < kBlockConvs[b]; ++i) {
       const int cp = (cin + 7) / 8 * 8;
-      const int64_t wd[4] = {c, cin, 3, 3}, bd[1] = {c};
-      add_w(e, p + "convs." + std::to_string(i) + ".weight", 4, wd, true, cp, (size_t)c * 9 * cp * 2, size);
-      add_w(e, p + "convs." + std::to_string(i) + ".bias", 1, bd, false, 0, (size_t)c * 4, size);
-      mx = std::max(mx, (size_t)c * cin * 9);
+      r.add(p + "convs." + std::to_string(i) + ".weight", W_CONV, {c, cin, 3, 3}, r.take((size_t)c * 9 * cp * 2), cp);
+      r.add(p + "convs." + std::to_string(i) + ".bias", W_VEC, {c}, r.take((size_t)c * 4));
       cin = c;
     }
-    const int64_t pw[4] = {1, c, 1, 1}, pb[1] = {1};
-    add_w(e, p + "projection.weight", 4, pw, false, 0, (size_t)c * 4, size);
-    add_w(e, p + "projection.bias", 1, pb, false, 0, 4, size);
+    r.add(p + "projection.weight", W_VEC, {1, c, 1, 1}, r.take((size_t)c * 4));
+    r.add(p + "projection.bias", W_VEC, {1}, r.take(4));
   }
-  e->slab_bytes = align256(size);
-  e->stage_bytes = mx * sizeof(float);
 }
-
-static const char* wp(Hed* e, const std::string& n) { return e->slab + e->weights[e->index.at(n)].off; }
 
 static void free_configured(Hed* e) {
   if (e->act) (void)hipFree(e->act);
@@ -272,12 +228,6 @@ static void free_configured(Hed* e) {
   e->H = e->W = 0;
 }
 
-static int run_prog(Hed* e, hipStream_t s) {
-  for (auto& op : e->prog)
-    if (int rc = op.fn(s)) return rc;
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -286,10 +236,9 @@ int sdeo_hed_create(sdeo_hed_handle* out) {
   SDEO_CHECK(out, "sdeo_hed_create: null argument");
   Hed* e = new Hed();
   build_registry(e);
-  if (hipMalloc((void**)&e->slab, e->slab_bytes) != hipSuccess) {
-    const size_t want = e->slab_bytes;
+  if (int rc = e->ws.alloc("sdeo_hed_create", /*zero_fill=*/false)) {
     delete e;
-    return fail("sdeo_hed_create: cannot allocate %zu bytes of weights", want);
+    return rc;
   }
   *out = e;
   return 0;
@@ -298,63 +247,29 @@ int sdeo_hed_create(sdeo_hed_handle* out) {
 int sdeo_hed_destroy(sdeo_hed_handle h) {
   if (!h) return 0;
   free_configured(h);
-  if (h->slab) (void)hipFree(h->slab);
-  if (h->stage) (void)hipFree(h->stage);
+  h->ws.destroy();
   delete h;
   return 0;
 }
 
-int sdeo_hed_num_weights(sdeo_hed_handle h) { return h ? (int)h->weights.size() : 0; }
+int sdeo_hed_num_weights(sdeo_hed_handle h) { return h ? (int)h->ws.entries.size() : 0; }
 
 int sdeo_hed_weight_info(sdeo_hed_handle h, int i, const char** name, int64_t dims[4], int* ndim) {
-  SDEO_CHECK(h && i >= 0 && i < (int)h->weights.size() && name && dims && ndim, "sdeo_hed_weight_info: bad argument");
-  const HWeight& w = h->weights[i];
-  *name = w.name.c_str();
-  for (int k = 0; k < 4; ++k) dims[k] = k < w.ndim ? w.dims[k] : 0;
-  *ndim = w.ndim;
+  SDEO_CHECK(h && i >= 0 && i < (int)h->ws.entries.size() && name && dims && ndim, "sdeo_hed_weight_info: bad argument");
+  h->ws.info(i, name, dims, 4, 0, ndim);
   return 0;
 }
 
 int sdeo_hed_load_weight(sdeo_hed_handle h, const char* name, const float* host_data, const int64_t* dims, int ndim, int strict) {
   SDEO_CHECK(h && name && host_data && dims, "sdeo_hed_load_weight: null argument");
-  auto it = h->index.find(name);
-  if (it == h->index.end()) {
-    if (strict) return fail("sdeo_hed_load_weight: unexpected tensor '%s'", name);
-    return 0;
-  }
-  HWeight& w = h->weights[it->second];
-  SDEO_CHECK(ndim == w.ndim, "sdeo_hed_load_weight: %s has %d dims, expected %d", name, ndim, w.ndim);
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) {
-    SDEO_CHECK(dims[i] == w.dims[i], "sdeo_hed_load_weight: %s dim %d is %lld, expected %lld", name, i, (long long)dims[i],
-               (long long)w.dims[i]);
-    n *= (size_t)dims[i];
-  }
-  if (!h->stage) SDEO_HIP(hipMalloc((void**)&h->stage, h->stage_bytes));
-  SDEO_HIP(hipMemcpy(h->stage, host_data, n * sizeof(float), hipMemcpyDefault));
-  void* dst = h->slab + w.off;
-  if (w.conv) {
-    if (int rc = oihw_f32_to_ohwi_f16((f16*)dst, h->stage, (int)w.dims[0], (int)w.dims[1], 3, 3, w.cin_pad, 0)) return rc;
-  } else {
-    SDEO_HIP(hipMemcpy(dst, h->stage, n * sizeof(float), hipMemcpyDeviceToDevice));
-  }
-  SDEO_HIP(hipDeviceSynchronize());
-  w.loaded = true;
-  h->finalized = false;
+  if (int rc = h->ws.load("sdeo_hed_load_weight", name, name, host_data, dims, ndim, strict)) return rc;
+  if (h->ws.find(name)) h->finalized = false;      // a tensor changed: finalize again before the next configure / detect
   return 0;
 }
 
 int sdeo_hed_finalize_weights(sdeo_hed_handle h) {
   SDEO_CHECK(h, "sdeo_hed_finalize_weights: null handle");
-  std::string missing;
-  int nmiss = 0;
-  for (auto& w : h->weights)
-    if (!w.loaded) {
-      if (nmiss < 5) missing += (nmiss ? ", " : "") + w.name;
-      ++nmiss;
-    }
-  SDEO_CHECK(nmiss == 0, "sdeo_hed_finalize_weights: %d tensors missing (%s%s)", nmiss, missing.c_str(), nmiss > 5 ? ", ..." : "");
-  if (h->stage) { (void)hipFree(h->stage); h->stage = nullptr; }
+  if (int rc = h->ws.require_all("sdeo_hed_finalize_weights")) return rc;
   h->finalized = true;
   return 0;
 }
@@ -374,11 +289,11 @@ int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
   size_t act_elems = 0;
   for (int k = 0; k < 5; ++k) act_elems = std::max(act_elems, (size_t)hk[k] * wk[k] * kBlockCh[k]);
   size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = align256(off); off = o + bytes; return o; };
+  auto take = [&](size_t bytes) { const size_t o = align_up(off, 256); off = o + bytes; return o; };
   const size_t o_in = take((size_t)H * W * 8 * 2), o_a = take(act_elems * 2), o_b = take(act_elems * 2);
   size_t o_side[5];
   for (int k = 0; k < 5; ++k) o_side[k] = take((size_t)hk[k] * wk[k] * 4);
-  e->act_bytes = align256(off);
+  e->act_bytes = align_up(off, 256);
   SDEO_HIP(hipMalloc((void**)&e->act, e->act_bytes));
   SDEO_HIP(hipMemset(e->act, 0, e->act_bytes));
   f16* xin = reinterpret_cast<f16*>(e->act + o_in);
@@ -389,8 +304,8 @@ int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
     e->maps.w[k] = wk[k];
   }
 
-  const float* norm = reinterpret_cast<const float*>(wp(e, "norm"));
-  e->prog.push_back({[e, xin, norm, H, W](hipStream_t s) { return hed_intake(xin, e->img, norm, H, W, s); }, "hed_intake", 0.0});
+  const float* norm = e->ws.ptr<float>("norm");
+  e->prog.push_back(Op([e, xin, norm, H, W](hipStream_t s) { return hed_intake(xin, e->img, norm, H, W, s); }, "hed_intake"));
   size_t ws = 0;
   const f16* cur = xin;
   int cur_buf = -1, cin = 8;
@@ -401,7 +316,7 @@ int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
       f16* dst = buf[cur_buf ^ 1];
       const f16* src = cur;
       const int hi = hk[b - 1], wi = wk[b - 1], cc = cin;
-      e->prog.push_back({[dst, src, hi, wi, cc](hipStream_t s) { return maxpool2x2_nhwc(dst, src, hi, wi, cc, s); }, "maxpool2x2_kernel", 0.0});
+      e->prog.push_back(Op([dst, src, hi, wi, cc](hipStream_t s) { return maxpool2x2_nhwc(dst, src, hi, wi, cc, s); }, "maxpool2x2_kernel"));
       cur = dst;
       cur_buf ^= 1;
     }
@@ -409,19 +324,20 @@ int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
       const std::string n = p + "convs." + std::to_string(i) + ".";
       f16* dst = buf[cur_buf < 0 ? 0 : cur_buf ^ 1];
       ConvGemm q;
-      q.x = cur; q.w = reinterpret_cast<const f16*>(wp(e, n + "weight")); q.y = dst;
-      q.bias = reinterpret_cast<const float*>(wp(e, n + "bias"));
+      q.x = cur; q.w = e->ws.ptr<f16>(n + "weight"); q.y = dst;
+      q.bias = e->ws.ptr<float>(n + "bias");
       q.B = 1; q.Hi = h; q.Wi = w; q.Cin = cin; q.R = q.S = 3; q.stride = 1; q.pad = 1;
       q.Ho = h; q.Wo = w; q.M = h * w; q.N = c; q.K = 9 * cin;
       q.ldx = cin; q.ldw = q.K; q.ldy = c; q.ldres = c; q.ld_bias2 = c;
       q.act = 4;
       ws = std::max(ws, conv_gemm_workspace_bytes(q));
-      e->prog.push_back({[q, e](hipStream_t s) mutable {
-                           q.workspace = e->splitk_ws;
-                           q.workspace_bytes = e->splitk_bytes;
-                           return conv_gemm(q, s);
-                         },
-                         conv_gemm_kernel_name(q), 2.0 * q.M * q.N * (double)(9 * (b == 0 && i == 0 ? 3 : cin))});
+      e->prog.push_back(Op([q, e](hipStream_t s) mutable {
+                             q.workspace = e->splitk_ws;
+                             q.workspace_bytes = e->splitk_bytes;
+                             return conv_gemm(q, s);
+                           },
+                           conv_gemm_kernel_name(q), 2.0 * q.M * q.N * (double)(9 * (b == 0 && i == 0 ? 3 : cin)),
+                           2.0 * ((double)q.M * q.Cin + (double)q.N * q.K + (double)q.M * q.N)));
       cur = dst;
       cur_buf = cur_buf < 0 ? 0 : cur_buf ^ 1;
       cin = c;
@@ -429,13 +345,13 @@ int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
     {
       float* out = const_cast<float*>(e->maps.m[b]);
       const f16* src = cur;
-      const float* pw = reinterpret_cast<const float*>(wp(e, p + "projection.weight"));
-      const float* pb = reinterpret_cast<const float*>(wp(e, p + "projection.bias"));
-      e->prog.push_back({[out, src, pw, pb, h, w, c](hipStream_t s) { return side_proj(out, src, pw, pb, h, w, c, s); }, "side_proj_kernel",
-                         2.0 * h * w * c});
+      const float* pw = e->ws.ptr<float>(p + "projection.weight");
+      const float* pb = e->ws.ptr<float>(p + "projection.bias");
+      e->prog.push_back(Op([out, src, pw, pb, h, w, c](hipStream_t s) { return side_proj(out, src, pw, pb, h, w, c, s); }, "side_proj_kernel",
+                           2.0 * h * w * c));
     }
   }
-  e->prog.push_back({[e, H, W](hipStream_t s) { return hed_fuse(e->edges, e->control, e->maps, H, W, s); }, "hed_fuse_kernel", 0.0});
+  e->prog.push_back(Op([e, H, W](hipStream_t s) { return hed_fuse(e->edges, e->control, e->maps, H, W, s); }, "hed_fuse_kernel"));
   e->splitk_bytes = ws;
   if (ws) SDEO_HIP(hipMalloc((void**)&e->splitk_ws, ws));
   e->H = H;
@@ -452,7 +368,7 @@ int sdeo_hed_detect_u8(sdeo_hed_handle h, const uint8_t* img_hwc, uint8_t* edges
   h->img = img_hwc;
   h->edges = edges;
   h->control = control_chw;
-  const int rc = run_prog(h, s);
+  const int rc = run_program(h->prog, s);
   h->img = nullptr; h->edges = nullptr; h->control = nullptr;
   if (rc) return rc;
   if (side)
@@ -462,7 +378,7 @@ int sdeo_hed_detect_u8(sdeo_hed_handle h, const uint8_t* img_hwc, uint8_t* edges
   return 0;
 }
 
-size_t sdeo_hed_device_bytes(sdeo_hed_handle h) { return h ? h->slab_bytes + h->act_bytes + h->splitk_bytes : 0; }
+size_t sdeo_hed_device_bytes(sdeo_hed_handle h) { return h ? h->ws.slab_bytes + h->act_bytes + h->splitk_bytes : 0; }
 
 // ---- not in sdeo.h: tests and tools
 
@@ -472,43 +388,15 @@ int sdeo_debug_maxpool2x2_f16(void* y, const void* x, int h, int w, int c, void*
 }
 
 // one detection with HIP events around every launch; synchronises and returns the JSON array
-// [{"kernel", "launches", "total_ms", "flops"}] aggregated by kernel name (tools/hed_time.py).  Not capturable.
+// [{"kernel", "launches", "total_ms", "flops", "bytes"}] aggregated by kernel name (tools/hed_time.py).  Not capturable.
 const char* sdeo_debug_hed_profile(sdeo_hed_handle h, const uint8_t* img_hwc, void* stream) {
-  static thread_local std::string out;
-  out = "[]";
-  if (!h || !h->finalized || h->H <= 0 || !img_hwc) return out.c_str();
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (!h || !h->finalized || h->H <= 0 || !img_hwc) return "[]";
   h->img = img_hwc;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev(h->prog.size());
-  bool ok = true;
-  for (size_t i = 0; i < h->prog.size() && ok; ++i) {
-    ok = hipEventCreate(&ev[i].first) == hipSuccess && hipEventCreate(&ev[i].second) == hipSuccess;
-    if (ok) ok = hipEventRecord(ev[i].first, s) == hipSuccess && h->prog[i].fn(s) == 0 && hipEventRecord(ev[i].second, s) == hipSuccess;
-  }
+  h->prof.begin();
+  const int rc = run_program(h->prog, reinterpret_cast<hipStream_t>(stream), &h->prof);
   h->img = nullptr;
-  (void)hipStreamSynchronize(s);
-  struct Agg { long n = 0; double ms = 0, flops = 0; };
-  std::vector<std::pair<std::string, Agg>> aggs;
-  for (size_t i = 0; i < h->prog.size(); ++i) {
-    float ms = 0.f;
-    if (ok) (void)hipEventElapsedTime(&ms, ev[i].first, ev[i].second);
-    if (ev[i].first) (void)hipEventDestroy(ev[i].first);
-    if (ev[i].second) (void)hipEventDestroy(ev[i].second);
-    size_t j = 0;
-    while (j < aggs.size() && aggs[j].first != h->prog[i].name) ++j;
-    if (j == aggs.size()) aggs.push_back({h->prog[i].name, Agg{}});
-    aggs[j].second.n += 1; aggs[j].second.ms += ms; aggs[j].second.flops += h->prog[i].flops;
-  }
-  if (!ok) return out.c_str();
-  out = "[";
-  char buf[512];
-  for (size_t i = 0; i < aggs.size(); ++i) {
-    snprintf(buf, sizeof(buf), "%s{\"kernel\": \"%s\", \"launches\": %ld, \"total_ms\": %.6f, \"flops\": %.6e}", i ? ", " : "",
-             aggs[i].first.c_str(), aggs[i].second.n, aggs[i].second.ms, aggs[i].second.flops);
-    out += buf;
-  }
-  out += "]";
-  return out.c_str();
+  const char* out = h->prof.end();
+  return rc ? "[]" : out;
 }
 
 }  // extern "C"

@@ -27,13 +27,12 @@
 #include <vector>
 
 #include "../../include/sdeo.h"
-#include "kernels.h"
+#include "handle_common.h"
 
 using namespace sdeo;
 
 namespace {
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int round8(int c) { return (c + 7) / 8 * 8; }
 
 const char* NS_UNET = "model.diffusion_model.";
@@ -123,20 +122,6 @@ static std::vector<HintConv> hint_convs(const sdeo_config& c) {
   return v;
 }
 
-// ------------------------------------------------------------------------------------------------
-// weights
-// ------------------------------------------------------------------------------------------------
-enum WKind { W_CONV, W_LINEAR, W_VEC, W_GEGLU_W, W_GEGLU_B };   // W_GEGLU_*: ff.net.0.proj, value / gate rows interleaved
-struct WEntry {
-  std::string name;
-  int64_t dims[4];
-  int ndim;
-  WKind kind;
-  size_t off;      // byte offset into the weight slab
-  int ipad;        // conv: stored (padded) input channels
-  bool loaded;
-};
-
 struct Arena {   // first-fit planner over one device allocation; offsets only
   struct Blk_ { size_t off, size; bool free; };
   std::vector<Blk_> blocks;
@@ -189,20 +174,6 @@ struct T {           // fp16 activation view: rows x c, row stride ld; (n,h,w) w
   int rows() const { return n * h * w; }
 };
 
-struct Op {          // one launch of a program + what it is for the profiler
-  std::function<int(hipStream_t)> fn;
-  const char* key = "other";
-  std::string tag;           // problem shape, shown by the profiler when SDEO_PROFILE_DETAIL=1
-  double flops = 0, bytes = 0;
-  bool zero_conv = false;    // ControlNet program: a zero conv (skipped when the UNet decoder applies the zero convs itself)
-  template <class F>
-  Op(F f) : fn(std::move(f)) {}
-  int operator()(hipStream_t s) const { return fn(s); }
-};
-typedef std::vector<Op> Program;
-
-struct ProfRec { std::string key; double flops, bytes; hipEvent_t a, b; };
-
 // LayerNorm folded into a Linear at weight-finalisation time (fold_layernorm): offsets into the weight slab
 struct FoldJob { size_t w_out, s_out, b_out, w_in; std::string gamma, beta, bias; int rows, C; };
 // ff.net.2 and proj_out of one SpatialTransformer composed into one [C][5C] Linear at weight-finalisation time (compose_proj)
@@ -217,9 +188,7 @@ struct sdeo_handle_s {
   sdeo_config cfg;
   UPlan uplan, cplan;
   std::vector<HintConv> hconvs;
-  // weights
-  std::vector<WEntry> weights;
-  std::unordered_map<std::string, int> windex;
+  WeightStore ws;                                      // registry, slab and loader of the checkpoint tensors
   std::unordered_map<std::string, size_t> named_off;   // extra named regions (stacked parents, LayerNorm-folded copies)
   std::vector<FoldJob> folds;
   std::vector<ComposeJob> composes;
@@ -234,10 +203,6 @@ struct sdeo_handle_s {
   int mx_launches = 0;                                 // GEMMs of the current programs that run on the block-scaled fp8 MFMA
   char* q8slab = nullptr;                              // fp8 codes + scales (allocated at the first fp8 finalize)
   size_t q8_bytes = 0;
-  char* wslab = nullptr;
-  size_t wslab_bytes = 0;
-  float* stage = nullptr;
-  size_t stage_bytes = 0;
   bool finalized = false;
   // per-net stacked time-embedding projection
   int emb_total[2] = {0, 0};
@@ -297,9 +262,7 @@ struct sdeo_handle_s {
   size_t device_bytes = 0;
   // profiling (sdeo_profile_*): HIP events around every launch of the next programs
   bool autotune = false;    // SDEO_AUTOTUNE=1: measure GEMM plans of untabled shapes at configure time (tuning aid; tools/tune_plans.py)
-  bool profiling = false;
-  std::vector<ProfRec> prof;
-  std::string prof_report;
+  Profiler prof;
 };
 
 namespace {
@@ -311,25 +274,15 @@ typedef sdeo_handle_s Engine;
 // ------------------------------------------------------------------------------------------------
 struct Registry {
   Engine* e;
-  size_t size = 0;
   bool quant = true;          // matrices registered now belong to the UNet / ControlNet (fp8-eligible), not the VAE
   void region(size_t off, int rows, int cols) {
     if (!quant) return;
     e->qindex[off] = (int)e->qregions.size();
     e->qregions.push_back(QRegion{off, rows, cols, 0, 0});
   }
-  size_t take(size_t bytes) {
-    const size_t off = align_up(size, 256);
-    size = off + bytes;
-    return off;
-  }
+  size_t take(size_t bytes) { return e->ws.take(bytes); }
   void add(const std::string& name, WKind kind, std::initializer_list<int64_t> dims, size_t off, int ipad = 0) {
-    WEntry w{};
-    w.name = name; w.kind = kind; w.ndim = (int)dims.size(); w.off = off; w.ipad = ipad; w.loaded = false;
-    int i = 0;
-    for (auto d : dims) w.dims[i++] = d;
-    e->windex[name] = (int)e->weights.size();
-    e->weights.push_back(w);
+    e->ws.add(name, kind, dims, off, ipad);
   }
   // conv: weight [cout][cin][k][k] -> fp16 [opad][k][k][ipad]; bias -> fp32 [opad]
   void conv(const std::string& name, int cin, int cout, int k, int opad = -1) {
@@ -402,7 +355,7 @@ static void reg_attn(Registry& r, const std::string& ns, const Blk& b, int ctx) 
     r.region(f.w_out, rows, c);        // the folded copy is what the network streams (the raw one is only the fold's input)
   };
   fold(t + ".attn1.qkv_ln", qkv, 3 * c, t + ".norm1", "");
-  fold(t + ".attn2.q_ln", r.e->weights[r.e->windex.at(t + ".attn2.to_q.weight")].off, c, t + ".norm2", "");
+  fold(t + ".attn2.q_ln", r.e->ws.find(t + ".attn2.to_q.weight")->off, c, t + ".norm2", "");
   fold(t + ".ff1_ln", ff1, 8 * c, t + ".norm3", t + ".ff.net.0.proj.bias");
   r.norm(t + ".norm1", c);
   r.norm(t + ".norm2", c);
@@ -513,14 +466,12 @@ static void build_registry(Engine* e) {
   }
   r.norm(d + ".norm_out", last);
   r.conv(d + ".conv_out", last, c.vae_out_ch, 3, (c.vae_out_ch + 3) / 4 * 4);
-  e->wslab_bytes = align_up(r.size, 256);
 }
 
 // VAE encoder (`model.py:452-545`, attn_resolutions = [], double_z) + quant_conv, appended behind everything build_registry placed
 // (sdeo_enable_vae_encoder): the offsets of the existing tensors do not move
 static void reg_vae_encoder(Engine* e) {
   Registry r{e};
-  r.size = e->wslab_bytes;
   r.quant = false;                   // fp16 like the decoder
   const sdeo_config& c = e->cfg;
   const std::string d = std::string(NS_VAE) + "encoder";
@@ -542,7 +493,6 @@ static void reg_vae_encoder(Engine* e) {
   r.norm(d + ".norm_out", bi);
   r.conv(d + ".conv_out", bi, zc2, 3, round8(zc2));
   r.conv(std::string(NS_VAE) + "quant_conv", zc2, zc2, 1, round8(zc2));
-  e->wslab_bytes = align_up(r.size, 256);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -615,21 +565,21 @@ struct Builder {
   }
 
   const WEntry* W(const std::string& name) {
-    auto it = e->windex.find(name);
-    if (it == e->windex.end()) { if (err.empty()) err = "unknown weight " + name; return nullptr; }
-    return &e->weights[it->second];
+    const WEntry* w = e->ws.find(name);
+    if (!w && err.empty()) err = "unknown weight " + name;
+    return w;
   }
-  const f16* wptr(const std::string& name) { auto w = W(name); return w ? reinterpret_cast<const f16*>(e->wslab + w->off) : nullptr; }
-  const float* vptr(const std::string& name) { auto w = W(name); return w ? reinterpret_cast<const float*>(e->wslab + w->off) : nullptr; }
-  const f16* named_w(const std::string& name) { return reinterpret_cast<const f16*>(e->wslab + e->named_off.at(name)); }
-  const float* named_v(const std::string& name) { return reinterpret_cast<const float*>(e->wslab + e->named_off.at(name)); }
+  const f16* wptr(const std::string& name) { return W(name) ? e->ws.ptr<f16>(name) : nullptr; }
+  const float* vptr(const std::string& name) { return W(name) ? e->ws.ptr<float>(name) : nullptr; }
+  const f16* named_w(const std::string& name) { return reinterpret_cast<const f16*>(e->ws.slab + e->named_off.at(name)); }
+  const float* named_v(const std::string& name) { return reinterpret_cast<const float*>(e->ws.slab + e->named_off.at(name)); }
 
 
   void launch_conv(ConvGemm p, const float* scale_host, RowStats* stats = nullptr, T* gn_y = nullptr, const ConvOpts* lo = nullptr) {
     if (e->act_bits == 8 && e->mxslab && p.M >= e->mx_min_rows && p.R == 1 && p.S == 1 && p.stride == 1 && !p.ups && p.K % 128 == 0 &&
         p.K == p.Cin && p.ldx % 16 == 0 && !p.bias_per_row && p.y && !p.y32) {
       // block-scaled fp8 on both sides: pack the activations (one launch), run the GEMM on the fp8 MFMA
-      auto it = e->mxindex.find((size_t)(reinterpret_cast<const char*>(p.w) - e->wslab));
+      auto it = e->mxindex.find((size_t)(reinterpret_cast<const char*>(p.w) - e->ws.slab));
       if (it != e->mxindex.end() && it->second.cols == p.ldw && p.N <= it->second.rows) {
         T xq = alloc2d(p.M, p.K / 2), xs = alloc2d(p.M, (p.K / 32 + 15) / 16 * 8);      // bytes: M x K codes, M x roundup(K/32, 16) scales
         uint8_t* q = reinterpret_cast<uint8_t*>(xq.p);
@@ -649,7 +599,7 @@ struct Builder {
     if (!p.mx_sx && e->weight_bits == 8 && p.M <= 512 && p.Cin % 64 == 0 && !p.ups && !p.bias_per_row && !conv_gemm_plan_is_halo(p)) {
       // weight-bound shapes stream the fp8 copy of their matrix (same numbers: the fp16 copy holds the dequantised values); where
       // the measured fp16 plan is a halo-reuse 3x3 kernel (activation-bound: M = 512 at long K) that kernel keeps the job
-      auto it = e->qindex.find((size_t)(reinterpret_cast<const char*>(p.w) - e->wslab));
+      auto it = e->qindex.find((size_t)(reinterpret_cast<const char*>(p.w) - e->ws.slab));
       if (it != e->qindex.end()) {
         const QRegion& q = e->qregions[it->second];
         if (q.cols == p.ldw && p.N <= q.rows) {
@@ -963,23 +913,10 @@ struct Built {
 };
 
 static int run(Engine* e, const Program& p, hipStream_t s, bool skip_zero_convs = false) {
-  if (!e->profiling) {
-    for (auto& op : p) {
-      if (skip_zero_convs && op.zero_conv) continue;
-      if (int rc = op(s)) return rc;
-    }
-    return 0;
-  }
-  static const bool detail = [] { const char* v = getenv("SDEO_PROFILE_DETAIL"); return v && atoi(v) != 0; }();
-  for (auto& op : p) {
-    if (skip_zero_convs && op.zero_conv) continue;
-    ProfRec r{detail && !op.tag.empty() ? std::string(op.key) + " | " + op.tag : std::string(op.key), op.flops, op.bytes, nullptr, nullptr};
-    SDEO_HIP(hipEventCreate(&r.a));
-    SDEO_HIP(hipEventCreate(&r.b));
-    SDEO_HIP(hipEventRecord(r.a, s));
-    if (int rc = op(s)) return rc;
-    SDEO_HIP(hipEventRecord(r.b, s));
-    e->prof.push_back(r);
+  if (!skip_zero_convs) return run_program(p, s, &e->prof);
+  for (auto& op : p) {       // the ControlNet program without its zero convs
+    if (op.zero_conv) continue;
+    if (int rc = e->prof.on ? e->prof.record(op, s) : op(s)) return rc;
   }
   return 0;
 }
@@ -1444,17 +1381,8 @@ int sdeo_create(const sdeo_config* cfg, sdeo_handle* out) {
   SDEO_HIP(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
   for (int i = 0; i < 13; ++i) e->scales[i] = 1.0f;
   build_registry(e.get());
-  SDEO_HIP(hipMalloc((void**)&e->wslab, e->wslab_bytes));
-  SDEO_HIP(hipMemset(e->wslab, 0, e->wslab_bytes));
-  size_t mx = 0;
-  for (auto& w : e->weights) {
-    size_t n = 1;
-    for (int i = 0; i < w.ndim; ++i) n *= (size_t)w.dims[i];
-    mx = std::max(mx, n);
-  }
-  e->stage_bytes = mx * sizeof(float);
-  SDEO_HIP(hipMalloc((void**)&e->stage, e->stage_bytes));
-  e->device_bytes = e->wslab_bytes;
+  if (int rc = e->ws.alloc("sdeo_create", /*zero_fill=*/true)) return rc;
+  e->device_bytes = e->ws.slab_bytes;
   *out = e.release();
   return 0;
 }
@@ -1465,10 +1393,9 @@ int sdeo_destroy(sdeo_handle h) {
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-  if (h->wslab) (void)hipFree(h->wslab);
+  h->ws.destroy();
   if (h->q8slab) (void)hipFree(h->q8slab);
   if (h->mxslab) (void)hipFree(h->mxslab);
-  if (h->stage) (void)hipFree(h->stage);
   delete h;
   return 0;
 }
@@ -1476,7 +1403,7 @@ int sdeo_destroy(sdeo_handle h) {
 int sdeo_enable_vae_encoder(sdeo_handle h) {
   SDEO_CHECK(h, "sdeo_enable_vae_encoder: null handle");
   if (h->vae_encoder) return 0;
-  for (const auto& w : h->weights)
+  for (const auto& w : h->ws.entries)
     SDEO_CHECK(!w.loaded, "sdeo_enable_vae_encoder: call it before the first sdeo_load_weight (%s is loaded)", w.name.c_str());
   SDEO_CHECK(!h->finalized && !h->arena, "sdeo_enable_vae_encoder: call it before sdeo_finalize_weights / sdeo_configure");
   SDEO_CHECK(h->cfg.vae_num_levels == 4, "sdeo_enable_vae_encoder: %d VAE levels downsample by %d, the 8h x 8w image boundary needs 8",
@@ -1484,92 +1411,33 @@ int sdeo_enable_vae_encoder(sdeo_handle h) {
   SDEO_CHECK(h->cfg.vae_out_ch <= 8, "sdeo_enable_vae_encoder: %d image channels (at most 8)", h->cfg.vae_out_ch);
   reg_vae_encoder(h);
   // nothing is loaded yet: the larger slab starts from zeros like the first one
-  if (h->wslab) (void)hipFree(h->wslab);
-  h->wslab = nullptr;
-  SDEO_HIP(hipMalloc((void**)&h->wslab, h->wslab_bytes));
-  SDEO_HIP(hipMemset(h->wslab, 0, h->wslab_bytes));
-  size_t mx = 0;
-  for (auto& w : h->weights) {
-    size_t n = 1;
-    for (int i = 0; i < w.ndim; ++i) n *= (size_t)w.dims[i];
-    mx = std::max(mx, n);
-  }
-  if (mx * sizeof(float) > h->stage_bytes) {
-    if (h->stage) (void)hipFree(h->stage);
-    h->stage = nullptr;
-    h->stage_bytes = mx * sizeof(float);
-    SDEO_HIP(hipMalloc((void**)&h->stage, h->stage_bytes));
-  }
-  h->device_bytes = h->wslab_bytes;
+  if (int rc = h->ws.alloc("sdeo_enable_vae_encoder", /*zero_fill=*/true)) return rc;
+  h->device_bytes = h->ws.slab_bytes;
   h->vae_encoder = true;
   return 0;
 }
 
-int sdeo_num_weights(sdeo_handle h) { return h ? (int)h->weights.size() : 0; }
+int sdeo_num_weights(sdeo_handle h) { return h ? (int)h->ws.entries.size() : 0; }
 
 int sdeo_weight_info(sdeo_handle h, int i, const char** name, int64_t dims[4], int* ndim) {
-  SDEO_CHECK(h && i >= 0 && i < (int)h->weights.size(), "sdeo_weight_info: bad index");
-  const WEntry& w = h->weights[i];
-  if (name) *name = w.name.c_str();
-  if (ndim) *ndim = w.ndim;
-  if (dims) for (int k = 0; k < 4; ++k) dims[k] = k < w.ndim ? w.dims[k] : 1;
+  SDEO_CHECK(h && i >= 0 && i < (int)h->ws.entries.size(), "sdeo_weight_info: bad index");
+  h->ws.info(i, name, dims, 4, 1, ndim);
   return 0;
 }
 
 int sdeo_load_weight(sdeo_handle h, const char* name, const float* host_data, const int64_t* dims, int ndim, int strict) {
   SDEO_CHECK(h && name && host_data && dims, "sdeo_load_weight: null argument");
-  auto it = h->windex.find(name);
-  if (it == h->windex.end()) {
-    if (strict) return fail("sdeo_load_weight: unexpected tensor '%s'", name);
-    return 0;
-  }
-  WEntry& w = h->weights[it->second];
-  SDEO_CHECK(ndim == w.ndim, "sdeo_load_weight: %s has %d dims, expected %d", name, ndim, w.ndim);
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) {
-    SDEO_CHECK(dims[i] == w.dims[i], "sdeo_load_weight: %s dim %d is %lld, expected %lld", name, i, (long long)dims[i],
-               (long long)w.dims[i]);
-    n *= (size_t)dims[i];
-  }
-  if (h->stage == nullptr) {
-    SDEO_HIP(hipMalloc((void**)&h->stage, h->stage_bytes));
-  }
-  SDEO_HIP(hipMemcpy(h->stage, host_data, n * sizeof(float), hipMemcpyDefault));
-  void* dst = h->wslab + w.off;
-  int rc = 0;
-  switch (w.kind) {
-    case W_CONV:
-      rc = oihw_f32_to_ohwi_f16((f16*)dst, h->stage, (int)w.dims[0], (int)w.dims[1], (int)w.dims[2], (int)w.dims[3], w.ipad, 0);
-      break;
-    case W_LINEAR: rc = f32_to_f16((f16*)dst, h->stage, (int64_t)n, 0); break;
-    case W_VEC: SDEO_HIP(hipMemcpy(dst, h->stage, n * sizeof(float), hipMemcpyDeviceToDevice)); break;
-    case W_GEGLU_W: rc = geglu_interleave_f32_to_f16((f16*)dst, h->stage, (int)(w.dims[0] / 2), (int)w.dims[1], 0); break;
-    case W_GEGLU_B: rc = geglu_interleave_f32((float*)dst, h->stage, (int)(w.dims[0] / 2), 0); break;
-  }
-  if (rc) return rc;
-  SDEO_HIP(hipDeviceSynchronize());
-  w.loaded = true;
-  return 0;
+  return h->ws.load("sdeo_load_weight", name, name, host_data, dims, ndim, strict);
 }
 
 int sdeo_finalize_weights(sdeo_handle h) {
   SDEO_CHECK(h, "sdeo_finalize_weights: null handle");
-  std::string missing;
-  int nmiss = 0;
-  for (auto& w : h->weights)
-    if (!w.loaded) {
-      if (nmiss < 5) missing += (nmiss ? ", " : "") + w.name;
-      ++nmiss;
-    }
-  SDEO_CHECK(nmiss == 0, "sdeo_finalize_weights: %d tensors missing (%s%s)", nmiss, missing.c_str(), nmiss > 5 ? ", ..." : "");
-  if (h->stage) { (void)hipFree(h->stage); h->stage = nullptr; }
+  if (int rc = h->ws.require_all("sdeo_finalize_weights")) return rc;
   // LayerNorm-folded copies of the Linear layers that consume a LayerNorm (rebuilt on every finalize, from the raw tensors)
   for (const FoldJob& f : h->folds) {
-    auto vec = [&](const std::string& n) -> const float* {
-      return n.empty() ? nullptr : reinterpret_cast<const float*>(h->wslab + h->weights[h->windex.at(n)].off);
-    };
-    if (int rc = fold_layernorm(reinterpret_cast<f16*>(h->wslab + f.w_out), reinterpret_cast<float*>(h->wslab + f.s_out),
-                                reinterpret_cast<float*>(h->wslab + f.b_out), reinterpret_cast<const f16*>(h->wslab + f.w_in),
+    auto vec = [&](const std::string& n) { return n.empty() ? nullptr : h->ws.ptr<float>(n); };
+    if (int rc = fold_layernorm(reinterpret_cast<f16*>(h->ws.slab + f.w_out), reinterpret_cast<float*>(h->ws.slab + f.s_out),
+                                reinterpret_cast<float*>(h->ws.slab + f.b_out), reinterpret_cast<const f16*>(h->ws.slab + f.w_in),
                                 vec(f.gamma), vec(f.beta), vec(f.bias), f.rows, f.C, 0))
       return rc;
   }
@@ -1587,18 +1455,16 @@ int sdeo_finalize_weights(sdeo_handle h) {
     }
     for (const QRegion& q : h->qregions)
       if (int rc = quantize_fp8_rows(reinterpret_cast<uint8_t*>(h->q8slab + q.q_off), reinterpret_cast<float*>(h->q8slab + q.s_off),
-                                     reinterpret_cast<f16*>(h->wslab + q.off), q.rows, q.cols, q.cols, q.cols, 0))
+                                     reinterpret_cast<f16*>(h->ws.slab + q.off), q.rows, q.cols, q.cols, q.cols, 0))
         return rc;
     for (const FoldJob& f : h->folds)          // the row sums of the LayerNorm fold must be those of the re-quantised matrix
-      if (int rc = row_sums_f16(reinterpret_cast<float*>(h->wslab + f.s_out), reinterpret_cast<const f16*>(h->wslab + f.w_out), f.rows, f.C, 0))
+      if (int rc = row_sums_f16(reinterpret_cast<float*>(h->ws.slab + f.s_out), reinterpret_cast<const f16*>(h->ws.slab + f.w_out), f.rows, f.C, 0))
         return rc;
   }
   // ff.net.2 x proj_out products, from the values the fp16 copies hold NOW (the dequantised ones when weight_bits == 8)
   for (const ComposeJob& cj : h->composes) {
-    auto off = [&](const std::string& n) { return h->wslab + h->weights[h->windex.at(n)].off; };
-    if (int rc = compose_proj(reinterpret_cast<f16*>(h->wslab + cj.w_out), reinterpret_cast<float*>(h->wslab + cj.b_out),
-                              reinterpret_cast<const f16*>(off(cj.wp)), reinterpret_cast<const float*>(off(cj.bp)),
-                              reinterpret_cast<const f16*>(off(cj.w2)), reinterpret_cast<const float*>(off(cj.b2)), cj.C, 4 * cj.C, 0))
+    if (int rc = compose_proj(reinterpret_cast<f16*>(h->ws.slab + cj.w_out), reinterpret_cast<float*>(h->ws.slab + cj.b_out),
+                              h->ws.ptr<f16>(cj.wp), h->ws.ptr<float>(cj.bp), h->ws.ptr<f16>(cj.w2), h->ws.ptr<float>(cj.b2), cj.C, 4 * cj.C, 0))
       return rc;
   }
   if (h->act_bits == 8) {
@@ -1620,7 +1486,7 @@ int sdeo_finalize_weights(sdeo_handle h) {
     }
     for (auto& kv : h->mxindex)
       if (int rc = quantize_mx(reinterpret_cast<uint8_t*>(h->mxslab + kv.second.q_off), reinterpret_cast<uint8_t*>(h->mxslab + kv.second.s_off),
-                               reinterpret_cast<const f16*>(h->wslab + kv.first), kv.second.rows, kv.second.cols, kv.second.cols, kv.second.cols,
+                               reinterpret_cast<const f16*>(h->ws.slab + kv.first), kv.second.rows, kv.second.cols, kv.second.cols, kv.second.cols,
                                kv.second.cols / 32, 0))
         return rc;
   }
@@ -1655,7 +1521,7 @@ int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w) {
              "sdeo_configure: latent %dx%d must be a positive multiple of %d", latent_h, latent_w, maxds);
   SDEO_CHECK(h->weight_bits != 8 || h->q8slab, "sdeo_configure: fp8 weights are packed by sdeo_finalize_weights: call it first");
   free_configured(h);
-  h->device_bytes = h->wslab_bytes + h->q8_bytes + h->mx_bytes;
+  h->device_bytes = h->ws.slab_bytes + h->q8_bytes + h->mx_bytes;
   h->mx_launches = 0;
   h->N = n; h->lh = latent_h; h->lw = latent_w;
   const sdeo_config& c = h->cfg;
@@ -1776,7 +1642,7 @@ static int run_step_programs(sdeo_handle h, bool no_control, bool time_from_tabl
     if (!time_from_table) if (int rc = run(h, h->p_temb[0], s)) return rc;
     return run(h, h->p_unet_noctrl, s);
   }
-  if (h->overlap && !h->profiling) {
+  if (h->overlap && !h->prof.on) {
     // fork: ControlNet on the side stream, UNet encoder + middle block on the caller's stream (capturable)
     SDEO_HIP(hipEventRecord(h->ev_fork, s));
     SDEO_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
@@ -1954,39 +1820,10 @@ size_t sdeo_device_bytes(sdeo_handle h) { return h ? h->device_bytes : 0; }
 
 int sdeo_profile_begin(sdeo_handle h) {
   SDEO_CHECK(h, "sdeo_profile_begin: null handle");
-  for (auto& r : h->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  h->prof.clear();
-  h->profiling = true;
+  h->prof.begin();
   return 0;
 }
 
-const char* sdeo_profile_end(sdeo_handle h) {
-  if (!h) return "";
-  h->profiling = false;
-  (void)hipDeviceSynchronize();
-  struct Agg { long n = 0; double ms = 0, flops = 0, bytes = 0; };
-  std::vector<std::pair<std::string, Agg>> aggs;
-  for (auto& r : h->prof) {
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, r.a, r.b);
-    (void)hipEventDestroy(r.a);
-    (void)hipEventDestroy(r.b);
-    size_t i = 0;
-    for (; i < aggs.size(); ++i) if (aggs[i].first == r.key) break;
-    if (i == aggs.size()) aggs.push_back({r.key, Agg()});
-    aggs[i].second.n += 1; aggs[i].second.ms += ms; aggs[i].second.flops += r.flops; aggs[i].second.bytes += r.bytes;
-  }
-  h->prof.clear();
-  std::string out = "[";
-  char buf[768];
-  for (size_t i = 0; i < aggs.size(); ++i) {
-    snprintf(buf, sizeof(buf), "%s{\"kernel\": \"%s\", \"launches\": %ld, \"total_ms\": %.6f, \"flops\": %.6e, \"bytes\": %.6e}",
-             i ? ", " : "", aggs[i].first.c_str(), aggs[i].second.n, aggs[i].second.ms, aggs[i].second.flops, aggs[i].second.bytes);
-    out += buf;
-  }
-  out += "]";
-  h->prof_report = out;
-  return h->prof_report.c_str();
-}
+const char* sdeo_profile_end(sdeo_handle h) { return h ? h->prof.end() : ""; }
 
 }  // extern "C"

@@ -39,7 +39,63 @@ def make_config(ucfg: S.UNetConfig = S.UNET_SD15, vcfg: S.VAEConfig = S.VAE_SD15
     return c
 
 
-class SdeoRuntime:
+class _HandleRuntime:
+    """What the owners of a libsdeo handle share: the device, the handle's lifetime and the weight calls.  A subclass names its
+    symbol prefix and the length of the dims array its `<prefix>weight_info` fills, and creates the handle in its __init__."""
+    _prefix = "sdeo_"
+    _ndims = 4
+
+    def __init__(self, device: Optional[torch.device] = None):
+        if not torch.cuda.is_available():
+            raise _lib.SdeoError(f"{type(self).__name__} needs a HIP device (there is no CPU fallback)")
+        self.lib = _lib.load()
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        torch.cuda.set_device(self.device)
+        self.handle = C.c_void_p()
+
+    def _sym(self, fn: str):
+        return getattr(self.lib, self._prefix + fn)
+
+    def _call(self, fn: str, *args, detail: str = ""):
+        """check(<prefix><fn>(handle, *args)); a failure is reported as "load_weight", "clip_load_weight", ... + detail"""
+        check(self._sym(fn)(self.handle, *args), self._prefix[len("sdeo_"):] + fn + detail)
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None) and self.handle.value:
+                self._sym("destroy")(self.handle)
+                self.handle = C.c_void_p()
+        except Exception:
+            pass
+
+    def expected_weights(self) -> Dict[str, tuple]:
+        out = {}
+        name = C.c_char_p()
+        dims = (C.c_int64 * self._ndims)()
+        nd = C.c_int()
+        for i in range(self._sym("num_weights")(self.handle)):
+            self._call("weight_info", C.c_int(i), C.byref(name), dims, C.byref(nd))
+            out[name.value.decode()] = tuple(int(dims[k]) for k in range(nd.value))
+        return out
+
+    def _load_ptr(self, name: str, data_ptr: int, shape, strict: bool = True):
+        """fp32 contiguous data of `shape` at `data_ptr`, on the host or on this device"""
+        dims = (C.c_int64 * max(len(shape), 1))(*shape)
+        self._call("load_weight", name.encode(), C.c_void_p(data_ptr), dims, C.c_int(len(shape)), C.c_int(int(strict)),
+                   detail=f"({name})")
+
+    def load_tensor(self, name: str, t: torch.Tensor, strict: bool = True):
+        t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+        self._load_ptr(name, t.data_ptr(), tuple(t.shape), strict)
+
+    def _finalize(self):
+        self._call("finalize_weights")
+
+    def device_bytes(self) -> int:
+        return int(self._sym("device_bytes")(self.handle))
+
+
+class SdeoRuntime(_HandleRuntime):
     """create -> load_state_dict -> configure(n, h, w) -> controlnet / unet / apply_model / vae_decode."""
 
     def __init__(self, ucfg: S.UNetConfig = S.UNET_SD15, vcfg: S.VAEConfig = S.VAE_SD15, device: Optional[torch.device] = None,
@@ -47,13 +103,8 @@ class SdeoRuntime:
         """weight_bits = 8: the UNet / ControlNet matrices are packed to fp8 (OCP e4m3fn, per-output-channel power-of-two scale) when
         the weights are finalised (BASELINE configs[4]; the reference's precision switch is `onnx2trt_static_plugin.py:40-42`).
         vae_encoder = True: the handle also expects `first_stage_model.encoder.*` / `quant_conv.*` and runs `vae_encode`."""
-        if not torch.cuda.is_available():
-            raise _lib.SdeoError("SdeoRuntime needs a HIP device (there is no CPU fallback)")
-        self.lib = _lib.load()
+        super().__init__(device)
         self.ucfg, self.vcfg = ucfg, vcfg
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        torch.cuda.set_device(self.device)
-        self.handle = C.c_void_p()
         self._cfg = make_config(ucfg, vcfg)
         check(self.lib.sdeo_create(C.byref(self._cfg), C.byref(self.handle)), "sdeo_create")
         self.vae_encoder = bool(vae_encoder)
@@ -72,43 +123,19 @@ class SdeoRuntime:
         # captured under an older generation points into freed memory and must be re-captured, never replayed
         self.generation = 0
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None) and self.handle.value:
-                self.lib.sdeo_destroy(self.handle)
-                self.handle = C.c_void_p()
-        except Exception:
-            pass
-
     # ---------------------------------------------------------------- weights
-    def expected_weights(self) -> Dict[str, tuple]:
-        out = {}
-        name = C.c_char_p()
-        dims = (C.c_int64 * 4)()
-        nd = C.c_int()
-        for i in range(self.lib.sdeo_num_weights(self.handle)):
-            check(self.lib.sdeo_weight_info(self.handle, C.c_int(i), C.byref(name), dims, C.byref(nd)), "weight_info")
-            out[name.value.decode()] = tuple(int(dims[k]) for k in range(nd.value))
-        return out
-
-    def load_tensor(self, name: str, t: torch.Tensor, strict: bool = True):
-        t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-        dims = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-        check(self.lib.sdeo_load_weight(self.handle, name.encode(), C.c_void_p(t.data_ptr()), dims, C.c_int(t.dim()),
-                                        C.c_int(int(strict))), f"load_weight({name})")
-
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False):
         """`sd` uses the reference checkpoint names (model.diffusion_model.*, control_model.*, first_stage_model.*).
         Tensors the hot path does not use (CLIP, VAE encoder, EMA ...) are ignored unless strict."""
         for k, v in sd.items():
             self.load_tensor(k, v, strict)
-        check(self.lib.sdeo_finalize_weights(self.handle), "finalize_weights")
+        self._finalize()
 
     def load_synthetic(self, seed: int = 0):
         """Seeded synthetic weights, generated tensor by tensor (never holds the full fp32 model on the host)."""
         for name, shape in self.expected_weights().items():
             self.load_tensor(name, S.synth_tensor(name, shape, seed))
-        check(self.lib.sdeo_finalize_weights(self.handle), "finalize_weights")
+        self._finalize()
 
     def load_synthetic_device(self, seed: int = 0):
         """Synthetic weights drawn on the GPU (device generator) -- fast path for bench.py; NOT reproducible on the
@@ -126,11 +153,8 @@ class SdeoRuntime:
                 for d in shape[1:]:
                     fan_in *= d
                 t = torch.randn(shape, generator=g, device=self.device) * (1.0 / fan_in) ** 0.5
-            t = t.contiguous()
-            dims = (C.c_int64 * len(shape))(*shape)
-            check(self.lib.sdeo_load_weight(self.handle, name.encode(), C.c_void_p(t.data_ptr()), dims, C.c_int(len(shape)),
-                                            C.c_int(1)), f"load_weight({name})")
-        check(self.lib.sdeo_finalize_weights(self.handle), "finalize_weights")
+            self._load_ptr(name, t.contiguous().data_ptr(), shape)
+        self._finalize()
 
     # ---------------------------------------------------------------- profiling
     def profile_begin(self):
@@ -158,9 +182,6 @@ class SdeoRuntime:
         shp = [(self.n, c, self.h // ds, self.w // ds) for c, ds in zip(plan.input_block_chans, plan.input_block_ds)]
         shp.append(shp[-1])
         return shp
-
-    def device_bytes(self) -> int:
-        return int(self.lib.sdeo_device_bytes(self.handle))
 
     # ---------------------------------------------------------------- forward calls
     def _f32(self, t, shape=None):
@@ -314,47 +335,21 @@ class SdeoRuntime:
         return (z, mom) if want_moments else z
 
 
-class ClipRuntime:
+class ClipRuntime(_HandleRuntime):
     """CLIP text transformer on the HIP path: create -> load_state_dict -> configure(batch) ->
     encode(tokens).  Mirrors what `FrozenCLIPEmbedder.forward` does after tokenisation
     (`ldm/modules/encoders/modules.py:126-131`: `self.transformer(input_ids=tokens).last_hidden_state`)."""
 
+    _prefix = "sdeo_clip_"
+    _ndims = 2
+
     def __init__(self, cfg: S.ClipConfig = S.CLIP_SD15, device: Optional[torch.device] = None):
-        if not torch.cuda.is_available():
-            raise _lib.SdeoError("ClipRuntime needs a HIP device (there is no CPU fallback)")
-        self.lib = _lib.load()
+        super().__init__(device)
         self.cfg = cfg
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        torch.cuda.set_device(self.device)
-        self.handle = C.c_void_p()
         self._cfg = _lib.SdeoClipConfig(cfg.vocab, cfg.positions, cfg.width, cfg.layers, cfg.heads, cfg.ffn)
         check(self.lib.sdeo_clip_create(C.byref(self._cfg), C.byref(self.handle)), "sdeo_clip_create")
         self.batch = 0
         self.generation = 0          # bumped by every re-plan of the activation buffers (see SdeoRuntime.generation)
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None) and self.handle.value:
-                self.lib.sdeo_clip_destroy(self.handle)
-                self.handle = C.c_void_p()
-        except Exception:
-            pass
-
-    def expected_weights(self) -> Dict[str, tuple]:
-        out = {}
-        name = C.c_char_p()
-        dims = (C.c_int64 * 2)()
-        nd = C.c_int()
-        for i in range(self.lib.sdeo_clip_num_weights(self.handle)):
-            check(self.lib.sdeo_clip_weight_info(self.handle, C.c_int(i), C.byref(name), dims, C.byref(nd)), "clip_weight_info")
-            out[name.value.decode()] = tuple(int(dims[k]) for k in range(nd.value))
-        return out
-
-    def load_tensor(self, name: str, t: torch.Tensor, strict: bool = True):
-        t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-        dims = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-        check(self.lib.sdeo_clip_load_weight(self.handle, name.encode(), C.c_void_p(t.data_ptr()), dims, C.c_int(t.dim()),
-                                             C.c_int(int(strict))), f"clip_load_weight({name})")
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False):
         """Accepts HuggingFace names (`text_model.*`, or bare), or the SD checkpoint's `cond_stage_model.transformer.text_model.*`;
@@ -363,13 +358,13 @@ class ClipRuntime:
             if not torch.is_floating_point(v):
                 continue
             self.load_tensor(k, v, strict)
-        check(self.lib.sdeo_clip_finalize_weights(self.handle), "clip_finalize_weights")
+        self._finalize()
         return self
 
     def load_synthetic(self, seed: int = 0):
         for name, shape in self.expected_weights().items():
             self.load_tensor(name, S.synth_tensor(S.NS_CLIP + name, shape, seed))
-        check(self.lib.sdeo_clip_finalize_weights(self.handle), "clip_finalize_weights")
+        self._finalize()
         return self
 
     def configure(self, batch: int):
@@ -395,47 +390,17 @@ class ClipRuntime:
         check(self.lib.sdeo_clip_encode(self.handle, ptr(tok), C.c_int(self.batch), ptr(out), cur_stream()), "sdeo_clip_encode")
         return out
 
-    def device_bytes(self) -> int:
-        return int(self.lib.sdeo_clip_device_bytes(self.handle))
 
-
-class HedRuntime:
+class HedRuntime(_HandleRuntime):
     """HED soft-edge annotator on the HIP path (`annotator/hed/__init__.py`: ControlNetHED_Apache2 + HEDdetector.__call__):
     create -> load_state_dict -> configure(H, W) -> detect(image).  One image per call; csrc/hed.hip."""
 
+    _prefix = "sdeo_hed_"
+
     def __init__(self, device: Optional[torch.device] = None):
-        if not torch.cuda.is_available():
-            raise _lib.SdeoError("HedRuntime needs a HIP device (there is no CPU fallback)")
-        self.lib = _lib.load()
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        torch.cuda.set_device(self.device)
-        self.handle = C.c_void_p()
+        super().__init__(device)
         check(self.lib.sdeo_hed_create(C.byref(self.handle)), "sdeo_hed_create")
         self.size = (0, 0)
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None) and self.handle.value:
-                self.lib.sdeo_hed_destroy(self.handle)
-                self.handle = C.c_void_p()
-        except Exception:
-            pass
-
-    def expected_weights(self) -> Dict[str, tuple]:
-        out = {}
-        name = C.c_char_p()
-        dims = (C.c_int64 * 4)()
-        nd = C.c_int()
-        for i in range(self.lib.sdeo_hed_num_weights(self.handle)):
-            check(self.lib.sdeo_hed_weight_info(self.handle, C.c_int(i), C.byref(name), dims, C.byref(nd)), "hed_weight_info")
-            out[name.value.decode()] = tuple(int(dims[k]) for k in range(nd.value))
-        return out
-
-    def load_tensor(self, name: str, t: torch.Tensor, strict: bool = True):
-        t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-        dims = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-        check(self.lib.sdeo_hed_load_weight(self.handle, name.encode(), C.c_void_p(t.data_ptr()), dims, C.c_int(t.dim()),
-                                            C.c_int(int(strict))), f"hed_load_weight({name})")
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False):
         """The reference state dict / ControlNetHED.pth names (`norm`, `block{1..5}.convs.{i}.*`, `block{1..5}.projection.*`);
@@ -444,7 +409,7 @@ class HedRuntime:
             if not torch.is_floating_point(v):
                 continue
             self.load_tensor(k, v, strict)
-        check(self.lib.sdeo_hed_finalize_weights(self.handle), "hed_finalize_weights")
+        self._finalize()
         self.size = (0, 0)
         return self
 
@@ -487,6 +452,3 @@ class HedRuntime:
         check(self.lib.sdeo_hed_detect_u8(self.handle, ptr(img), ptr(out.get("edges")), ptr(out.get("control")), sp if side else None,
                                           cur_stream()), "sdeo_hed_detect_u8")
         return out
-
-    def device_bytes(self) -> int:
-        return int(self.lib.sdeo_hed_device_bytes(self.handle))
