@@ -245,8 +245,13 @@ int sdeo_set_timestep_table(sdeo_handle h, const int64_t* host_timesteps, int co
  * x <- sqrt(a_prev) pred_x0 + sqrt(1 - a_prev) e.  x [n/2][4][h][w] fp32 is updated IN PLACE, pred_x0 (may be NULL) receives the
  * prediction.  Arithmetic and rounding are those of sdeo_apply_model + sdeo_cfg_ddim_step (bit-identical results); what is saved
  * is the NCHW fp32 round trip of eps and the latent between the two.  flags: SDEO_STEP_LATENT_STAGED = x is exactly what the
- * previous sdeo_ddim_step on this handle left (its fp16 copy is already staged; skips one conversion launch).  Capturable. */
+ * previous sdeo_ddim_step on this handle left (its fp16 copy is already staged; skips one conversion launch).
+ * The two halves of [x; x] differ only in their text context, so the UNet computes input_blocks.1 up to its cross-attention once, on
+ * the first half (same kernels, same plans: the results do not change).  SDEO_STEP_HINT_SHARED = the cached hint of image i + n/2 is
+ * that of image i (the sampler passed the same control image for the conditional and the unconditional half): the ControlNet does
+ * the same.  Without the flag the ControlNet runs both halves in full.  Capturable. */
 #define SDEO_STEP_LATENT_STAGED 16
+#define SDEO_STEP_HINT_SHARED 32
 int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
                    float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream);
 

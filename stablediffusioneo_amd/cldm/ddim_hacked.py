@@ -216,8 +216,12 @@ class DDIMSampler(object):
                                           unconditional_conditioning=uc)
         intermediates["x_inter"].append(img)             # index == total_steps - 1
         intermediates["pred_x0"].append(pred_x0)
+        # cond and uncond were given the SAME control tensors (canny2image / hed2image outside guess mode): the hint features of the
+        # two halves of the batch are equal, which lets the ControlNet share what precedes its first cross-attention (baked in at capture)
+        hint_shared = self._ident(c["c_concat"]) == self._ident(uc["c_concat"])
         key = (rt.generation, tuple(img.shape), tuple(int(t) for t in time_range), float(scale), int(log_every_t),
-               tuple(float(v) for v in m.control_scales), bool(m.only_mid_control), getattr(self, "_schedule_key", None), LOOP_GRAPH_STEPS)
+               tuple(float(v) for v in m.control_scales), bool(m.only_mid_control), getattr(self, "_schedule_key", None), LOOP_GRAPH_STEPS,
+               hint_shared)
         if getattr(rt, "_table_key", None) != (rt.generation, tuple(int(t) for t in time_range)):
             rt.set_timestep_table(time_range)            # another schedule used the runtime since (the graphs read the table by address)
         if getattr(self, "_loop_key", None) != key:
@@ -237,7 +241,7 @@ class DDIMSampler(object):
                     for i in range(first, min(first + per_graph, total_steps)):
                         index = total_steps - i - 1
                         rt.ddim_step(self._loop_x, self._loop_pred, i, scale, float(a_t[index]), float(a_p[index]), float(s1m[index]),
-                                     m.control_scales, m.only_mid_control, staged=i > first)
+                                     m.control_scales, m.only_mid_control, staged=i > first, hint_shared=hint_shared)
                         if index % log_every_t == 0:
                             kept_x.append(self._loop_x.clone())
                             kept_p.append(self._loop_pred.clone())
@@ -254,6 +258,12 @@ class DDIMSampler(object):
         return self._loop_x.clone(), intermediates
 
     # ------------------------------------------------------------------------------------------ one step
+    @staticmethod
+    def _ident(ts):
+        """identity of the CALLER's conditioning tensors (storage, in-place version, shape): a key built from the result of
+        torch.cat would compare addresses of temporaries, which match from step to step only by allocator luck"""
+        return tuple((v.data_ptr(), v._version, tuple(v.shape)) for v in ts)
+
     def _eps_pair(self, x, c, t, uc, scale):
         """eps for (cond, uncond); returns (eps_c, eps_u) with eps_u None when guidance is off."""
         m = self.model
@@ -266,11 +276,7 @@ class DDIMSampler(object):
             return m.apply_model(x, t, c), m.apply_model(x, t, uc)
         b = x.shape[0]
 
-        # identity of the CALLER's conditioning tensors (storage, in-place version, shape): a key built from the result of
-        # torch.cat would compare addresses of temporaries, which match from step to step only by allocator luck
-        def ident(ts):
-            return tuple((v.data_ptr(), v._version, tuple(v.shape)) for v in ts)
-
+        ident = self._ident
         key = (ident(c["c_concat"]), ident(uc["c_concat"]), ident(c["c_crossattn"]), ident(uc["c_crossattn"]), tuple(x.shape))
         if key == self._cache_key:
             rt = m.rt.configure(2 * b, x.shape[2], x.shape[3])

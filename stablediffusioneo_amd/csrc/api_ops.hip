@@ -289,6 +289,23 @@ int sdeo_debug_gemm_stats_f16(void* y, int ldy, const void* x, int ldx, const vo
   return conv_gemm(p, S(stream));
 }
 
+int sdeo_debug_gemm_res_rows_f16(void* y, int ldy, const void* x, int ldx, const void* w, int ldw, const float* bias, const void* res,
+                                 int ldres, int res_rows, int m, int n, int k, float* stats, int stats_ld, int* strips_out, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  ConvGemm p;
+  fill_gemm(p, m, n, k);
+  p.x = (const f16*)x; p.w = (const f16*)w; p.bias = bias; p.res = (const f16*)res; p.y = (f16*)y;
+  p.ldx = ldx; p.ldw = ldw; p.ldy = ldy; p.ldres = ldres; p.res_rows = res_rows;
+  p.workspace = (float*)workspace; p.workspace_bytes = workspace_bytes;
+  if (stats) {
+    SDEO_CHECK(strips_out, "gemm_res_rows: null argument");
+    *strips_out = conv_gemm_stats_strips(p);
+    SDEO_CHECK(*strips_out <= stats_ld, "gemm_res_rows: %d strips do not fit stats_ld %d", *strips_out, stats_ld);
+    if (*strips_out > 0) { p.stats_out = stats; p.stats_ld = stats_ld; }
+  }
+  return conv_gemm(p, S(stream));
+}
+
 int sdeo_debug_gemm_ln_f16(void* y, int ldy, const void* x, int ldx, const void* w_folded, int ldw, const float* ln_s,
                            const float* bias_folded, const float* stats, int stats_ld, int strips, int ln_c, int m, int n, int k, int act, float eps, void* workspace, size_t workspace_bytes, void* stream) {
   ConvGemm p;
@@ -313,6 +330,13 @@ int sdeo_attention_f16(void* o, int ldo, const void* q, int ldq, const void* k, 
                        int heads, int tq, int tk, int tk_stride, int vt_batch_stride, int d, float scale, void* stream) {
   return attention((f16*)o, ldo, (const f16*)q, ldq, (const f16*)k, ldk, (const f16*)v, ldv, b, heads, tq, tk, tk_stride,
                    vt_batch_stride, d, scale, S(stream));
+}
+
+int sdeo_debug_attention_qb_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int b,
+                                int q_batches, int heads, int tq, int tk, int tk_stride, int v_batch_stride, int d, float scale, void* stream) {
+  AttnArgs a{(f16*)o, (const f16*)q, (const f16*)k, (const f16*)v, ldo, ldq, ldk, ldv, b, heads, tq, tk, tk_stride, v_batch_stride, d, scale, 0};
+  a.qB = q_batches;
+  return attention(a, S(stream));
 }
 
 int sdeo_attention_causal_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int b,

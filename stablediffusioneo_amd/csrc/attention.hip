@@ -41,6 +41,7 @@ struct AP {
   int H, Tq, Tk, TkS, TkSv, d;
   float scale_log2;
   int causal;        // 1: key j is visible to query t only when j <= t (CLIP text transformer)
+  int qB;            // batches of Q: batch b reads the queries of batch b - qB when b >= qB (AttnArgs::qB)
 };
 
 struct AP2 { AP k[1]; };
@@ -91,7 +92,7 @@ void attention_kernel(const AP2 pp) {
   AP pl = pp.k[0];
   // (integers / floats only: a pointer that has been through the asm loses its address space and its accesses become flat_ ones)
   asm volatile("" : "+s"(pl.ldo), "+s"(pl.ldq), "+s"(pl.ldk), "+s"(pl.ldv), "+s"(pl.H),
-               "+s"(pl.Tq), "+s"(pl.Tk), "+s"(pl.TkS), "+s"(pl.TkSv), "+s"(pl.d), "+s"(pl.scale_log2), "+s"(pl.causal));
+               "+s"(pl.Tq), "+s"(pl.Tk), "+s"(pl.TkS), "+s"(pl.TkSv), "+s"(pl.d), "+s"(pl.scale_log2), "+s"(pl.causal), "+s"(pl.qB));
   const AP& p = pl;
   constexpr int NT = 64 * QB * KS;                           // threads per workgroup
   constexpr int NKB = 2 / KS;                                // 32-key blocks of a tile each wave handles
@@ -139,7 +140,7 @@ void attention_kernel(const AP2 pp) {
   // ---- Q fragments (B operand of S^T = K Q^T): lane holds Q[qrow][ks*16 + 8*lh + 0..7]
   f16x8 qf[D16];
   {
-    const f16* qp = p.q + ((size_t)b * p.Tq + (qvalid ? qrow : 0)) * p.ldq + h * d;
+    const f16* qp = p.q + ((size_t)(b >= p.qB ? b - p.qB : b) * p.Tq + (qvalid ? qrow : 0)) * p.ldq + h * d;
     // unconditional loads (rows past Tq read row 0, chunks past d read chunk 0; zeroed at their first use below): a load under an
     // exec mask cannot be counted by the compiler's wait pass, and every later wait of the prologue would become vmcnt(0)
 #pragma unroll
@@ -471,7 +472,7 @@ __global__ __launch_bounds__(256, 1) void attention_wide_kernel(const AP p) {
 
   f16x8 qf[KS16];
   {
-    const f16* qp = p.q + ((size_t)b * p.Tq + (qvalid ? qrow : 0)) * p.ldq + h * D + c0;
+    const f16* qp = p.q + ((size_t)(b >= p.qB ? b - p.qB : b) * p.Tq + (qvalid ? qrow : 0)) * p.ldq + h * D + c0;
 #pragma unroll
     for (int ks = 0; ks < KS16; ++ks)
       qf[ks] = *reinterpret_cast<const f16x8*>(qp + (ks * 2 + lh) * 8);       // row 0 for queries past Tq: never stored
@@ -750,7 +751,10 @@ static int attn_prepare(AP& ap, const AttnArgs& a) {
   SDEO_CHECK((reinterpret_cast<uintptr_t>(a.q) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.k) & 15) == 0 &&
                  (reinterpret_cast<uintptr_t>(a.v) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.o) & 7) == 0,
              "attention: operands must be 16-byte aligned");
-  ap = AP{a.o, a.q, a.k, a.v, a.ldo, a.ldq, a.ldk, a.ldv, a.H, a.Tq, a.Tk, a.TkS, a.TkSv, a.d, a.scale * 1.4426950408889634f, a.causal ? 1 : 0};
+  SDEO_CHECK(a.qB == 0 || (a.qB <= a.B && 2 * a.qB >= a.B), "attention: qB=%d must lie in [B/2, B] (B=%d)", a.qB, a.B);
+  SDEO_CHECK(a.plan_B == 0 || a.plan_B >= a.B, "attention: plan_B=%d is smaller than B=%d", a.plan_B, a.B);
+  ap = AP{a.o, a.q, a.k, a.v, a.ldo, a.ldq, a.ldk, a.ldv, a.H, a.Tq, a.Tk, a.TkS, a.TkSv, a.d, a.scale * 1.4426950408889634f, a.causal ? 1 : 0,
+          a.qB > 0 ? a.qB : a.B};
   return 0;
 }
 
@@ -774,7 +778,7 @@ int attention(const AttnArgs& a, hipStream_t stream) {
   AP2 ap{};
   AttnForm f;
   if (int rc = attn_prepare(ap.k[0], a)) return rc;
-  if (int rc = attn_select(f, a.B, a.H, a.Tq, a.Tk, a.d, a.causal)) return rc;
+  if (int rc = attn_select(f, a.plan_B > 0 ? a.plan_B : a.B, a.H, a.Tq, a.Tk, a.d, a.causal)) return rc;
   return attn_dispatch(f, ap, 1, a.B, stream);
 }
 

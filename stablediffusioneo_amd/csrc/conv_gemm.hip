@@ -682,7 +682,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const KP pp) {
   // every scalar the loads below depend on, in one batch (see conv_gemm_dma_kernel)
   KP pl = pp;
   asm volatile("" : "+s"(pl.M), "+s"(pl.N), "+s"(pl.HoWo), "+s"(pl.ldy), "+s"(pl.ldres), "+s"(pl.ld_bias2), "+s"(pl.act),
-               "+s"(pl.bias_per_row), "+s"(pl.splitk));     // integers only: pinned pointers would turn their accesses into flat_ ones
+               "+s"(pl.bias_per_row), "+s"(pl.splitk), "+s"(pl.res_rows));     // integers only: pinned pointers would turn their accesses into flat_ ones
   const KP& p = pl;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int n4 = p.N / 4;
@@ -700,7 +700,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const KP pp) {
     else bv = *reinterpret_cast<const f32x4*>(p.bias + n);
   }
   if (p.bias2) b2 = *reinterpret_cast<const f32x4*>(p.bias2 + (size_t)(m / p.HoWo) * p.ld_bias2 + n);
-  if (p.res) rv = *reinterpret_cast<const f16x4*>(p.res + (size_t)m * p.ldres + n);
+  if (p.res) rv = *reinterpret_cast<const f16x4*>(p.res + (size_t)res_row(p, m) * p.ldres + n);
   for (int z0 = 0; z0 < p.splitk; z0 += 8) {
     f32x4 t[8];
 #pragma unroll
@@ -872,6 +872,15 @@ static ShapeKey key_of(const ConvGemm& p) {
 static bool has_operand_form(const ConvGemm& p, const TileCfg& c) { return (!p.wscale || (c.caps & CAP_W8)) && (!p.mx_sx || (c.caps & CAP_MX)); }
 
 static Plan make_plan(const ConvGemm& p) {
+  if (p.plan_B > 0 && p.plan_B != p.B) {
+    // a batch prefix of a larger problem (ConvGemm::plan_B) runs that problem's plan on fewer M tiles: tile, split-K factor and
+    // K-steps decide the instruction sequence of every output row, the number of M tiles does not
+    ConvGemm q = p;
+    q.M = p.M / p.B * p.plan_B; q.B = p.plan_B; q.plan_B = 0;
+    Plan pl = make_plan(q);
+    pl.tiles_m = plan_tiles_m(p, kTiles[pl.tile]);
+    return pl;
+  }
   Plan best{};
   const bool fast = is_fast(p);
   const int force_tile = p.force_tile >= 0 ? p.force_tile : g_force_tile;
@@ -1001,6 +1010,9 @@ static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
   SDEO_CHECK(p.M == p.B * p.Ho * p.Wo, "conv_gemm: M=%d != B*Ho*Wo=%d", p.M, p.B * p.Ho * p.Wo);
   SDEO_CHECK(p.ldy % 4 == 0 && p.ldy >= (p.act == 3 ? p.N / 2 : p.N), "conv_gemm: ldy=%d", p.ldy);
   SDEO_CHECK(!p.res || p.ldres % 4 == 0, "conv_gemm: ldres=%d", p.ldres);
+  SDEO_CHECK(p.res_rows == 0 || (p.res && p.res_rows <= p.M && 2 * p.res_rows >= p.M),
+             "conv_gemm: res_rows=%d must lie in [M/2, M] (M=%d) and needs a residual", p.res_rows, p.M);
+  SDEO_CHECK(p.plan_B == 0 || (p.plan_B >= p.B && p.M % p.B == 0), "conv_gemm: plan_B=%d is smaller than B=%d", p.plan_B, p.B);
   SDEO_CHECK((reinterpret_cast<uintptr_t>(p.x) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.w) & 15) == 0,
              "conv_gemm: operands must be 16-byte aligned");
   {
@@ -1032,6 +1044,7 @@ static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
   kp.Hi = p.Hi; kp.Wi = p.Wi; kp.Cin = p.Cin; kp.Ho = p.Ho; kp.Wo = p.Wo; kp.S = p.S; kp.stride = p.stride; kp.pad = p.pad;
   kp.ups = p.ups; kp.HoWo = p.Ho * p.Wo;
   kp.ldx = p.ldx; kp.ldw = p.ldw; kp.ldy = p.ldy; kp.ldres = p.ldres; kp.ld_bias2 = p.ld_bias2;
+  kp.res_rows = p.res_rows > 0 ? p.res_rows : p.M;
   kp.act = p.act; kp.bias_per_row = p.bias_per_row; kp.scale = p.scale;
   kp.wscale = p.wscale;
   if (p.mx_sx) {       // (p arrives with K, Cin, ldx, ldw already halved: conv_gemm())

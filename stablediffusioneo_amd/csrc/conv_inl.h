@@ -20,6 +20,8 @@ struct KP {
   int Hi, Wi, Cin, Ho, Wo, S, stride, pad, ups;
   int HoWo;
   int ldx, ldw, ldy, ldres, ld_bias2;
+  int res_rows;      // rows of `res`: output row m adds residual row m - res_rows when m >= res_rows (= M: one residual row per output
+                     // row; M / 2: the second half of the batch re-reads the first half's residual, see ConvGemm::res_rows)
   int act, bias_per_row;
   float scale;
   int nk, nk_per_split, splitk;
@@ -129,11 +131,15 @@ __device__ __forceinline__ void pin_epilogue_scalars(KP& q) {
   SDEO_PIN_PTR(wscale) SDEO_PIN_PTR(stats_out) SDEO_PIN_PTR(ln_stats) SDEO_PIN_PTR(ln_s) SDEO_PIN_PTR(gn_out)
 #undef SDEO_PIN_PTR
   q.M = pin_i32(q.M); q.N = pin_i32(q.N); q.HoWo = pin_i32(q.HoWo); q.ldy = pin_i32(q.ldy); q.ldres = pin_i32(q.ldres);
+  q.res_rows = pin_i32(q.res_rows);
   q.ld_bias2 = pin_i32(q.ld_bias2); q.act = pin_i32(q.act); q.bias_per_row = pin_i32(q.bias_per_row); q.scale = pin_f32(q.scale);
   q.splitk = pin_i32(q.splitk); q.coalesce = pin_i32(q.coalesce); q.stats_ld = pin_i32(q.stats_ld); q.ln_strips = pin_i32(q.ln_strips);
   q.ln_ld = pin_i32(q.ln_ld); q.ln_invc = pin_f32(q.ln_invc); q.ln_eps = pin_f32(q.ln_eps);
   q.gn_cpg = pin_i32(q.gn_cpg); q.gn_slots = pin_i32(q.gn_slots); q.gn_groups = pin_i32(q.gn_groups);
 }
+
+// row of `res` that output row m adds (KP::res_rows)
+__device__ __forceinline__ int res_row(const KP& p, int m) { return m >= p.res_rows ? m - p.res_rows : m; }
 
 // blocks staged per round: the largest divisor of MI whose scratch fits `budget` bytes per wave and whose residual registers
 // (PASSES 16-byte vectors per block) stay within 8 vectors
@@ -341,7 +347,7 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
         for (int jb = 0; jb < NB; ++jb)
 #pragma unroll
           for (int t = 0; t < PASSES; ++t)
-            if (mm[jb][t] >= 0) resv[jb][t] = *reinterpret_cast<const f16x8*>(p.res + (size_t)mm[jb][t] * p.ldres + nn[t]);
+            if (mm[jb][t] >= 0) resv[jb][t] = *reinterpret_cast<const f16x8*>(p.res + (size_t)res_row(p, mm[jb][t]) * p.ldres + nn[t]);
       }
       if (j0 == 0) stamp(p, 9);
 #pragma unroll
@@ -490,7 +496,7 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
       }
       v *= p.scale;
       if (p.res) {
-        const f16x4 r = *reinterpret_cast<const f16x4*>(p.res + (size_t)m * p.ldres + n);
+        const f16x4 r = *reinterpret_cast<const f16x4*>(p.res + (size_t)res_row(p, m) * p.ldres + n);
 #pragma unroll
         for (int t = 0; t < 4; ++t) v[t] += (float)r[t];
       }

@@ -58,6 +58,13 @@ struct ConvGemm {
   const uint8_t* mx_sx = nullptr;  // [M][mx_ldsx]
   const uint8_t* mx_sw = nullptr;  // [N][mx_ldsw]
   int mx_ldsx = 0, mx_ldsw = 0;
+  // shared prefix of a batch whose halves are identical up to here (the CFG pair, csrc/net.hip build_attn):
+  // res_rows: `res` holds this many rows and output row m adds row m - res_rows when m >= res_rows (0: M rows, one per output row;
+  //   M / 2: both halves of the batch add the residual the first half computed).  M / 2 <= res_rows <= M.
+  // plan_B: this launch is the first B images (rows, for a GEMM) of a problem of plan_B; it runs that problem's plan (tile, split-K,
+  //   K-steps), so every output row is computed by the instruction sequence it has in the full-batch launch.  0: its own plan.
+  int res_rows = 0;
+  int plan_B = 0;
 };
 int conv_gemm(const ConvGemm& p, hipStream_t stream);
 inline int conv_pad_after(const ConvGemm& p) { return p.pad_after < 0 ? p.pad : p.pad_after; }
@@ -127,6 +134,11 @@ struct AttnArgs {
   int ldo, ldq, ldk, ldv, B, H, Tq, Tk, TkS, TkSv, d;
   float scale;
   int causal;
+  // shared prefix of a batch whose halves are identical up to here (the CFG pair, csrc/net.hip build_attn):
+  // qB: batches of Q; batch b reads the queries of batch b - qB when b >= qB (0: B, one per batch; B / 2 <= qB <= B)
+  // plan_B: select the kernel as for a problem of plan_B batches (this launch is a batch prefix of it); 0: B
+  int qB = 0;
+  int plan_B = 0;
 };
 int attention(const AttnArgs& a, hipStream_t stream);
 // the instantiation attention() launches for this shape ("attention_kernel<3,2,true,4>", "attention_wide_kernel<128>"), from the

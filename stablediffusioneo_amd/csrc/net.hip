@@ -20,7 +20,10 @@
 //     time, mean / rstd as two per-row scalars in the epilogue); the per-row statistics are written by the epilogue of the
 //     GEMM that produced the residual stream, so no LayerNorm kernel and no normalised copy of the tokens exists;
 //   * cross-attention K / V^T depend only on the text context and the hint block only on the hint: both are
-//     computed once per image and cached across the DDIM steps.
+//     computed once per image and cached across the DDIM steps;
+//   * the two halves of sdeo_ddim_step's CFG batch [x; x] differ only in their text context, so what a network computes before its
+//     first cross-attention (input_blocks.1: ResBlock, proj_in, self-attention, attn2.to_q) runs on the first half only and the
+//     full-batch launches behind it read the half-batch tensors twice (p_unet_enc_sh / p_cn_sh, build_shared_prefix).
 #include <functional>
 #include <memory>
 #include <unordered_map>
@@ -258,6 +261,9 @@ struct sdeo_handle_s {
   // programs
   Program p_hint, p_ctx_cn, p_ctx_unet, p_cn, p_cn_export, p_ctrl_import, p_unet_enc, p_unet_dec, p_unet_noctrl, p_vae, p_vae_enc;
   Program p_temb[2], p_temb_tab, p_x0, p_eps_export, p_unet_dec_fused;
+  // p_unet_enc / p_cn with input_blocks.1 up to its cross-attention run on the first N / 2 images only (build_shared_prefix); empty
+  // when N is odd or the block has no transformer
+  Program p_unet_enc_sh, p_cn_sh;
   std::vector<size_t> ctrl_elems;
   size_t device_bytes = 0;
   // profiling (sdeo_profile_*): HIP events around every launch of the next programs
@@ -507,6 +513,7 @@ struct ConvOpts {                     // conv / gemm options
   const float* bias2 = nullptr; int ld_bias2 = 0;
   const float* const* bias2_cur = nullptr; const int* ld_bias2_cur = nullptr; int bias2_off = 0;    // read at launch time (time embedding)
   const T* res = nullptr;
+  bool res_half = false;         // a full-batch launch whose residual was computed for the first half of the batch only (Builder::share)
   int act = 0;
   const float* scale_host = nullptr;   // read at launch time (control scales)
   const T* out = nullptr;        // write into this view instead of allocating
@@ -528,6 +535,11 @@ struct Builder {
   bool dry;
   char* base = nullptr;      // device base of `arena`
   int ws_sel = 0;            // 0: main-stream workspaces, 1: side-stream (ControlNet) workspaces
+  // Shared prefix of the CFG pair (build_shared_prefix).  `share`: the block built now is the variant whose ops in front of the first
+  // cross-attention run on the first N / 2 images; build_res / build_attn raise `half` around those ops.  A half-batch launch keeps the
+  // full-batch tensors (same arena plan, it writes a prefix of them) and the full-batch problem's kernel plan (ConvGemm::plan_B,
+  // AttnArgs::plan_B), so every row it writes is bit-identical to the full-batch launch's.
+  bool share = false, half = false;
   Program* prog = nullptr;
   size_t max_splitk = 0, max_gn = 0;
   std::string err;
@@ -555,7 +567,7 @@ struct Builder {
   void reserve_gn_partials(const ConvGemm& p, T& y) {
     if (!gn_from_producer() || p.N % 32) return;
     const int hw = p.Ho * p.Wo;
-    y.gnp_off = arena->alloc((size_t)p.B * ((hw + 31) / 32) * 32 * 2 * sizeof(float));
+    y.gnp_off = arena->alloc((size_t)(p.plan_B ? p.plan_B : p.B) * ((hw + 31) / 32) * 32 * 2 * sizeof(float));
     y.gnp = nullptr;                       // set by launch_conv when the plan emits
     y.gn_slots = 0;
   }
@@ -576,12 +588,14 @@ struct Builder {
 
 
   void launch_conv(ConvGemm p, const float* scale_host, RowStats* stats = nullptr, T* gn_y = nullptr, const ConvOpts* lo = nullptr) {
-    if (e->act_bits == 8 && e->mxslab && p.M >= e->mx_min_rows && p.R == 1 && p.S == 1 && p.stride == 1 && !p.ups && p.K % 128 == 0 &&
+    // precision and scratch sizes follow the problem whose plan the launch takes (a half-batch launch: the full-batch one)
+    const int Mplan = p.plan_B ? p.M / p.B * p.plan_B : p.M;
+    if (e->act_bits == 8 && e->mxslab && Mplan >= e->mx_min_rows && p.R == 1 && p.S == 1 && p.stride == 1 && !p.ups && p.K % 128 == 0 &&
         p.K == p.Cin && p.ldx % 16 == 0 && !p.bias_per_row && p.y && !p.y32) {
       // block-scaled fp8 on both sides: pack the activations (one launch), run the GEMM on the fp8 MFMA
       auto it = e->mxindex.find((size_t)(reinterpret_cast<const char*>(p.w) - e->ws.slab));
       if (it != e->mxindex.end() && it->second.cols == p.ldw && p.N <= it->second.rows) {
-        T xq = alloc2d(p.M, p.K / 2), xs = alloc2d(p.M, (p.K / 32 + 15) / 16 * 8);      // bytes: M x K codes, M x roundup(K/32, 16) scales
+        T xq = alloc2d(Mplan, p.K / 2), xs = alloc2d(Mplan, (p.K / 32 + 15) / 16 * 8);      // bytes: M x K codes, M x roundup(K/32, 16) scales
         uint8_t* q = reinterpret_cast<uint8_t*>(xq.p);
         uint8_t* sc = reinterpret_cast<uint8_t*>(xs.p);
         const int lds = (p.K / 32 + 15) / 16 * 16;
@@ -592,11 +606,11 @@ struct Builder {
         p.w = reinterpret_cast<const f16*>(e->mxslab + it->second.q_off); p.ldw = it->second.cols;
         p.mx_sx = sc; p.mx_ldsx = lds;
         p.mx_sw = reinterpret_cast<const uint8_t*>(e->mxslab + it->second.s_off); p.mx_ldsw = it->second.cols / 32;
-        if (!dry) ++e->mx_launches;
+        if (!dry && !share) ++e->mx_launches;
         mx_tmp.push_back(xq); mx_tmp.push_back(xs);
       }
     }
-    if (!p.mx_sx && e->weight_bits == 8 && p.M <= 512 && p.Cin % 64 == 0 && !p.ups && !p.bias_per_row && !conv_gemm_plan_is_halo(p)) {
+    if (!p.mx_sx && e->weight_bits == 8 && Mplan <= 512 && p.Cin % 64 == 0 && !p.ups && !p.bias_per_row && !conv_gemm_plan_is_halo(p)) {
       // weight-bound shapes stream the fp8 copy of their matrix (same numbers: the fp16 copy holds the dequantised values); where
       // the measured fp16 plan is a halo-reuse 3x3 kernel (activation-bound: M = 512 at long K) that kernel keeps the job
       auto it = e->qindex.find((size_t)(reinterpret_cast<const char*>(p.w) - e->ws.slab));
@@ -609,7 +623,7 @@ struct Builder {
       }
     }
     max_splitk = std::max(max_splitk, e->autotune ? conv_gemm_autotune_workspace_bytes(p) : conv_gemm_workspace_bytes(p));
-    if (!dry && e->autotune) {
+    if (!dry && e->autotune && !share) {       // (the shared variant of a block runs the plans its full-batch build measured)
       ConvGemm q = p;
       q.workspace = ws_sel ? e->splitk_ws2 : e->splitk_ws;
       q.workspace_bytes = e->splitk_ws_bytes;
@@ -623,7 +637,7 @@ struct Builder {
         p.gn_out = gn_y->gnp; p.gn_cpg = cpg; p.gn_slots = slots; p.gn_groups = 32;
       }
     }
-    if (!dry && getenv("SDEO_DUMP_GEMM"))   // shape census for tools/tune_gemm.py
+    if (!dry && !share && getenv("SDEO_DUMP_GEMM"))   // shape census for tools/tune_gemm.py
       fprintf(stderr, "SDEO_GEMM %d %d %d %d %d %d %d %d %d %d %s\n", p.M, p.N, p.K, p.Cin, p.R, p.stride, p.ups, p.B, p.Hi, p.Wi,
               conv_gemm_kernel_name(p));
     bool stats_by_kernel = false;
@@ -689,14 +703,17 @@ struct Builder {
     const int ho = (hv + pad + pad_after - k) / stride + 1, wo = (wv + pad + pad_after - k) / stride + 1;
     const int cs = o.cout_store > 0 ? o.cout_store : cout;
     T y = o.out ? *o.out : alloc(x.n, ho, wo, cs);
+    const int n = half ? x.n / 2 : x.n;
     if (w && w->ipad != x.c && err.empty()) err = "conv " + name + ": input has " + std::to_string(x.c) + " channels, weight expects " + std::to_string(w->ipad);
     p.x = x.p; p.y = y.p;
     if (o.w_ovr) { p.w = o.w_ovr; p.bias = o.b_ovr; } else { p.w = wptr(name + ".weight"); p.bias = vptr(name + ".bias"); }
     p.bias2 = o.bias2; p.ld_bias2 = o.ld_bias2;
     if (o.res) { p.res = o.res->p; p.ldres = o.res->ld; }
-    p.B = x.n; p.Hi = x.h; p.Wi = x.w; p.Cin = x.c; p.Ho = ho; p.Wo = wo; p.R = p.S = k; p.stride = stride; p.pad = pad; p.ups = ups;
+    p.B = n; p.Hi = x.h; p.Wi = x.w; p.Cin = x.c; p.Ho = ho; p.Wo = wo; p.R = p.S = k; p.stride = stride; p.pad = pad; p.ups = ups;
     if (pad_after != pad) p.pad_after = pad_after;
-    p.M = x.n * ho * wo; p.N = cs; p.K = k * k * x.c;
+    p.M = n * ho * wo; p.N = cs; p.K = k * k * x.c;
+    if (half) p.plan_B = x.n;
+    if (o.res_half) p.res_rows = p.M / 2;
     p.ldx = x.ld; p.ldw = p.K; p.ldy = y.ld; p.act = o.act;
     const bool want_gn = o.gn_next && !o.out && !o.scale_host && cs == y.c;
     if (want_gn) reserve_gn_partials(p, y);
@@ -709,7 +726,7 @@ struct Builder {
   // y[rows][n] = x[rows][k] . w[n][k]^T (+bias)(+res)
   T gemm(const T& x, const f16* w, int ldw, int n, const float* bias, const CO& o = CO(), float* out32 = nullptr, int ld32 = 0) {
     ConvGemm p;
-    const int rows = x.rows();
+    const int rows = half ? x.rows() / 2 : x.rows();
     T y;
     if (!out32) y = o.out ? *o.out : alloc(x.n, x.h, x.w, n);
     p.x = x.p; p.w = w; p.bias = bias;
@@ -717,6 +734,8 @@ struct Builder {
     if (o.res) { p.res = o.res->p; p.ldres = o.res->ld; }
     p.B = rows; p.Cin = x.c; p.M = rows; p.N = n; p.K = x.c;
     p.ldx = x.ld; p.ldw = ldw; p.act = o.act;
+    if (half) p.plan_B = x.rows();
+    if (o.res_half) p.res_rows = rows / 2;
     set_ln(p, o);
     if (o.ln && o.ln->c != x.c && err.empty()) err = "LayerNorm statistics of a " + std::to_string(o.ln->c) + "-channel tensor fed to K = " + std::to_string(x.c);
     launch_conv(p, o.scale_host, o.stats);
@@ -740,7 +759,7 @@ struct Builder {
     T y = out ? *out : alloc(x.n, x.h, x.w, x.c);
     const float* g = vptr(name + ".weight");
     const float* b = vptr(name + ".bias");
-    const int B = x.n, HW = x.h * x.w, C = x.c;
+    const int B = half ? x.n / 2 : x.n, HW = x.h * x.w, C = x.c;      // (no plan to inherit: the GroupNorm kernels work image by image)
     max_gn = std::max(max_gn, (size_t)B * gn_chunks(HW) * 32 * 2 * sizeof(float));
     Engine* eng = e;
     const int sel = ws_sel;
@@ -780,10 +799,14 @@ struct Builder {
     return y;
   }
 
-  void attn(const T& o, const f16* q, int ldq, const f16* k, int ldk, const f16* v, int ldv, int B, int H, int Tq, int Tk, int TkS, int TkSv, int d) {
-    f16* op = o.p; const int ldo = o.ld;
-    const float scale = 1.0f / sqrtf((float)d);
-    push([=](hipStream_t s) { return attention(op, ldo, q, ldq, k, ldk, v, ldv, B, H, Tq, Tk, TkS, TkSv, d, scale, s); }, "attention",
+  // qB: batches of q when the full-batch launch reads the queries of the first half twice (0: B).  Under `half` the first B / 2 batches run.
+  void attn(const T& o, const f16* q, int ldq, const f16* k, int ldk, const f16* v, int ldv, int B, int H, int Tq, int Tk, int TkS, int TkSv, int d,
+            int qB = 0) {
+    AttnArgs a{o.p, q, k, v, o.ld, ldq, ldk, ldv, B, H, Tq, Tk, TkS, TkSv, d, 1.0f / sqrtf((float)d), 0};
+    a.qB = qB;
+    if (half) { a.plan_B = B; a.B = B / 2; }
+    B = a.B;
+    push([=](hipStream_t s) { return attention(a, s); }, "attention",
          4.0 * B * H * (double)Tq * Tk * d, 2.0 * B * H * d * (2.0 * Tq + 2.0 * Tk),
          "Tq" + std::to_string(Tq) + " Tk" + std::to_string(Tk) + " d" + std::to_string(d));
   }
@@ -792,6 +815,7 @@ struct Builder {
 // ResBlock._forward (`openaimodel.py:255-275`)
 static T build_res(Builder& b, const std::string& ns, const Blk& blk, const T& x, int net, const T* out = nullptr) {
   const std::string p = ns + blk.name;
+  b.half = b.share;              // the ResBlock in front of the first transformer: both halves of the CFG pair are the same images
   Builder::CO o1;
   o1.bias2_off = b.e->emb_row.at(p);
   o1.bias2 = b.e->emb_all[net] + o1.bias2_off;     // what planning / autotune see; the launch reads emb_cur / emb_ld_cur
@@ -813,6 +837,7 @@ static T build_res(Builder& b, const std::string& ns, const Blk& blk, const T& x
   T y = b.gn_conv(h1, p + ".out_layers.0", 1e-5f, 1, p + ".out_layers.3", blk.cout, o2);
   b.release(h1);
   if (blk.cin != blk.cout) b.release(skip);
+  b.half = false;
   return y;
 }
 
@@ -827,6 +852,9 @@ static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& 
   const std::string t = p + ".transformer_blocks.0";
   const int C = blk.cin, H = c.num_heads, d = C / H, N = x.n, Tq = x.h * x.w;
   const int TkS = round8(c.context_len);
+  // b.share: x holds the first N / 2 images only and everything up to attn2.to_q runs on them; the cross-attention (per-image K / V),
+  // attn2.to_out and the last GEMM run at full batch and read q2 / tok1 / x of image i - N / 2 for the second half
+  b.half = b.share;
   T g = b.gn(x, p + ".norm", 1e-6f, 0);
   RowStats st0 = b.alloc_stats(x.rows(), C), st1 = b.alloc_stats(x.rows(), C), st2 = b.alloc_stats(x.rows(), C);
   Builder::CO pi; pi.stats = &st0;
@@ -845,8 +873,9 @@ static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& 
   // attn2 (cross, K | V precomputed from the context)
   Builder::CO l2; l2.ln = &st1; l2.ln_s = b.named_v(t + ".attn2.q_ln.s");
   T q2 = b.gemm(tok1, b.named_w(t + ".attn2.q_ln.w"), C, C, b.named_v(t + ".attn2.q_ln.b"), l2);
+  b.half = false;
   T o2 = b.alloc(x.n, x.h, x.w, C);
-  b.attn(o2, q2.p, C, kv.kv.p, 2 * C, kv.kv.p + C, 2 * C, N, H, Tq, c.context_len, TkS, TkS, d);
+  b.attn(o2, q2.p, C, kv.kv.p, 2 * C, kv.kv.p + C, 2 * C, N, H, Tq, c.context_len, TkS, TkS, d, b.share ? N / 2 : 0);
   b.release(q2);
   // ff.net.2 and proj_out are two Linear maps with only the residual add between them: composed at finalisation into ONE [C][5C]
   // matrix over the row-concatenated operand [GEGLU output (4C) | tok2 (C)] (ComposeJob), so attn2.to_out writes tok2 into the last C
@@ -854,7 +883,7 @@ static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& 
   T cat = b.alloc(x.n, x.h, x.w, 5 * C);
   T gg = cat; gg.c = 4 * C; gg.off = (size_t)-1;
   T tok2v = cat; tok2v.p = cat.p + 4 * C; tok2v.c = C; tok2v.off = (size_t)-1;
-  Builder::CO r2; r2.res = &tok1; r2.stats = &st2; r2.out = &tok2v;
+  Builder::CO r2; r2.res = &tok1; r2.res_half = b.share; r2.stats = &st2; r2.out = &tok2v;
   T tok2 = b.gemm(o2, b.wptr(t + ".attn2.to_out.0.weight"), C, C, b.vptr(t + ".attn2.to_out.0.bias"), r2);
   b.release(o2);
   b.release(tok1);
@@ -864,7 +893,7 @@ static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& 
     b.gemm(tok2, b.named_w(t + ".ff1_ln.w"), C, 8 * C, b.named_v(t + ".ff1_ln.b"), og);
   }
   b.release_stats();
-  Builder::CO ro; ro.res = &x; ro.out = out; ro.gn_next = true;
+  Builder::CO ro; ro.res = &x; ro.res_half = b.share; ro.out = out; ro.gn_next = true;
   ro.w_ovr = b.named_w(t + ".ffproj.w"); ro.b_ovr = b.named_v(t + ".ffproj.b");
   T y = b.conv(cat, p + ".proj_out", C, 1, 1, 0, ro);
   b.release(cat);
@@ -1084,8 +1113,39 @@ static void build_all(Engine* e, Arena& arena, Arena& arena2, bool dry, size_t* 
     return x;
   };
 
+  // input_blocks.1 built twice from the same arena state: as it is, into the current program, and as the variant whose ops in front of
+  // the first cross-attention run on the first N / 2 images (Builder::share), into sp.var.  Both place every tensor at the same address,
+  // so the rest of the program, the zero convs and the decoder serve either; splice() puts the variant program together.
+  struct Splice { size_t first = 0, last = 0; Program var; bool on = false; };
+  auto build_shared_prefix = [&](const std::string& ns, const std::vector<Blk>& blocks, const T& x, int net, Splice& sp) -> T {
+    const Arena before = *b.arena;
+    sp.first = b.prog->size();
+    T y = run_blocks(ns, blocks, x, false, net, nullptr);
+    sp.last = b.prog->size();
+    if (N % 2 || blocks.size() != 2 || blocks[0].kind != B_RES || blocks[1].kind != B_ATTN) return y;
+    Arena after = *b.arena;
+    *b.arena = before;
+    Program* prog = b.prog;
+    b.prog = &sp.var; b.share = true;
+    T ys = run_blocks(ns, blocks, x, false, net, nullptr);
+    b.prog = prog; b.share = false;
+    if ((ys.p != y.p || ys.gnp != y.gnp || ys.gn_slots != y.gn_slots || b.arena->end != after.end) && b.err.empty())
+      b.err = "the shared-prefix variant of " + ns + blocks[0].name + " plans another arena";
+    after.peak = std::max(after.peak, b.arena->peak);
+    *b.arena = after;
+    sp.on = true;
+    return y;
+  };
+  auto splice = [&](Program& out, const Program& full, const Splice& sp) {
+    if (dry || !sp.on) return;
+    out.assign(full.begin(), full.begin() + sp.first);
+    out.insert(out.end(), sp.var.begin(), sp.var.end());
+    out.insert(out.end(), full.begin() + sp.last, full.end());
+  };
+
   // ---- ControlNet program (`cldm/cldm.py:284-305`)
   {
+    Splice sp;
     b.prog = &e->p_cn;
     b.arena = &arena2; b.base = e->arena2; b.ws_sel = 1;
     const std::string ns = NS_CN;
@@ -1104,6 +1164,8 @@ static void build_all(Engine* e, Arena& arena, Arena& arena2, bool dry, size_t* 
         // input_blocks.0 conv, then h += guided_hint (residual epilogue)
         Builder::CO o; o.res = &bt.hint_feat; o.gn_next = true;
         y = b.conv(hcur, ns + e->cplan.in[0][0].name, c.model_channels, 3, 1, 0, o);
+      } else if (i == 1) {
+        y = build_shared_prefix(ns, e->cplan.in[i], hcur, 1, sp);
       } else {
         y = run_blocks(ns, e->cplan.in[i], hcur, false, 1, nullptr);
       }
@@ -1114,6 +1176,7 @@ static void build_all(Engine* e, Arena& arena, Arena& arena2, bool dry, size_t* 
     T m = run_blocks(ns, e->cplan.mid, hcur, false, 1, nullptr);
     e->cn_h[e->cplan.in.size()] = m;
     zero_conv(m, ns + "middle_block_out.0", e->cplan.in_ch.back(), &e->ctrl[e->cplan.in.size()]);
+    splice(e->p_cn_sh, e->p_cn, sp);
     b.arena = &arena; b.base = e->arena; b.ws_sel = 0;
   }
   const int nctrl = (int)e->cplan.in.size() + 1;
@@ -1140,8 +1203,9 @@ static void build_all(Engine* e, Arena& arena, Arena& arena2, bool dry, size_t* 
     const std::string ns = NS_UNET;
     std::vector<T> hs;
     T hcur = e->x0;
+    Splice sp;
     for (size_t i = 0; i < e->uplan.in.size(); ++i) {
-      T y = run_blocks(ns, e->uplan.in[i], hcur, false, 0, nullptr);
+      T y = (i == 1 && with_ctrl) ? build_shared_prefix(ns, e->uplan.in[i], hcur, 0, sp) : run_blocks(ns, e->uplan.in[i], hcur, false, 0, nullptr);
       hs.push_back(y);
       hcur = y;
     }
@@ -1150,6 +1214,7 @@ static void build_all(Engine* e, Arena& arena, Arena& arena2, bool dry, size_t* 
     T cat0 = cat_for(e->uplan.mid.back().cout, hs.back());
     T view0 = cat0; view0.c = e->uplan.mid.back().cout; view0.off = (size_t)-1;
     run_blocks(ns, e->uplan.mid, hcur, false, 0, &view0);
+    if (with_ctrl) splice(e->p_unet_enc_sh, e->p_unet_enc, sp);
     // The decoder (`openaimodel.py:797-801` with `cldm/cldm.py:33-41`): h = cat([h, hs.pop() + control.pop()]).  Three forms of the same
     // program: no control; controls given as tensors (the 13-tensor boundary: one add per control); controls applied as the ControlNet's
     // zero convs themselves, out = scale * zero_conv(cn_h) + skip written straight into the concat buffer (no add launches, no fp16
@@ -1347,7 +1412,8 @@ static void free_configured(Engine* e) {
   if (e->arena2) (void)hipFree(e->arena2);
   e->arena2 = nullptr;
   for (Program* p : {&e->p_hint, &e->p_ctx_cn, &e->p_ctx_unet, &e->p_cn, &e->p_cn_export, &e->p_ctrl_import, &e->p_unet_enc,
-                     &e->p_unet_dec, &e->p_unet_noctrl, &e->p_vae, &e->p_vae_enc, &e->p_temb[0], &e->p_temb[1], &e->p_temb_tab, &e->p_x0, &e->p_eps_export, &e->p_unet_dec_fused})
+                     &e->p_unet_dec, &e->p_unet_noctrl, &e->p_vae, &e->p_vae_enc, &e->p_temb[0], &e->p_temb[1], &e->p_temb_tab, &e->p_x0, &e->p_eps_export, &e->p_unet_dec_fused,
+                     &e->p_unet_enc_sh, &e->p_cn_sh})
     p->clear();
   e->tab_count = 0;
 }
@@ -1637,7 +1703,12 @@ static void set_effective_scales(sdeo_handle h) {
 }
 
 // ControlNet || UNet encoder, join, UNet decoder: eps16 holds the result.  The latent is already in x0.
-static int run_step_programs(sdeo_handle h, bool no_control, bool time_from_table, hipStream_t s) {
+// shared_unet / shared_cn: the two halves of the batch are the same images at the same timestep (and, for the ControlNet, under the same
+// hint): run the programs whose shared prefix is computed once, where configure built them
+static int run_step_programs(sdeo_handle h, bool no_control, bool time_from_table, hipStream_t s, bool shared_unet = false,
+                             bool shared_cn = false) {
+  const Program& p_unet_enc = shared_unet && !h->p_unet_enc_sh.empty() ? h->p_unet_enc_sh : h->p_unet_enc;
+  const Program& p_cn = shared_cn && !h->p_cn_sh.empty() ? h->p_cn_sh : h->p_cn;
   if (no_control) {
     if (!time_from_table) if (int rc = run(h, h->p_temb[0], s)) return rc;
     return run(h, h->p_unet_noctrl, s);
@@ -1647,18 +1718,18 @@ static int run_step_programs(sdeo_handle h, bool no_control, bool time_from_tabl
     SDEO_HIP(hipEventRecord(h->ev_fork, s));
     SDEO_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
     if (!time_from_table) if (int rc = run(h, h->p_temb[1], h->side)) return rc;
-    if (int rc = run(h, h->p_cn, h->side, true)) return rc;
+    if (int rc = run(h, p_cn, h->side, true)) return rc;
     SDEO_HIP(hipEventRecord(h->ev_join, h->side));
     if (!time_from_table) if (int rc = run(h, h->p_temb[0], s)) return rc;
-    if (int rc = run(h, h->p_unet_enc, s)) return rc;
+    if (int rc = run(h, p_unet_enc, s)) return rc;
     SDEO_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
   } else {
     if (!time_from_table) {
       if (int rc = run(h, h->p_temb[1], s)) return rc;
       if (int rc = run(h, h->p_temb[0], s)) return rc;
     }
-    if (int rc = run(h, h->p_cn, s, true)) return rc;
-    if (int rc = run(h, h->p_unet_enc, s)) return rc;
+    if (int rc = run(h, p_cn, s, true)) return rc;
+    if (int rc = run(h, p_unet_enc, s)) return rc;
   }
   return run(h, h->p_unet_dec_fused, s);      // applies the zero convs itself (skipped above)
 }
@@ -1768,7 +1839,8 @@ int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float
   set_effective_scales(h);
   if (!(flags & 16))
     if (int rc = latent_pair_to_nhwc(h->x0.p, h->x0.ld, x, b, c.in_channels, HW, s)) return rc;
-  if (int rc = run_step_programs(h, false, true, s)) return rc;
+  // x0 = [x; x] at one timestep: the UNet's shared prefix always holds, the ControlNet's when the caller vouches for the hints
+  if (int rc = run_step_programs(h, false, true, s, true, (flags & SDEO_STEP_HINT_SHARED) != 0)) return rc;
   return cfg_ddim_pair(x, pred_x0, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, b, c.out_channels, HW, cfg_scale, a_t, a_prev,
                        sqrt_one_minus_at, s);
 }

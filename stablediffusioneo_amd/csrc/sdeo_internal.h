@@ -59,6 +59,19 @@ int sdeo_debug_conv2d_gn_f16(void* ynorm, void* y, const void* x, const void* w_
                              int w, int cin, int cout, int ksize, int stride, int upsample2x, const float* gamma, const float* beta,
                              int groups, float eps, int with_silu, float* partials, size_t partial_floats, int* slots, void* stream);
 
+/* op-level hooks of the shared prefix of the CFG pair (tests; csrc/net.hip build_attn): operands that a full-batch launch reads from a
+ * half-batch tensor.
+ * gemm_res_rows: sdeo_gemm_f16 (fp16 out) whose residual holds res_rows rows (m / 2 <= res_rows <= m): output row r adds residual
+ *   row r - res_rows when r >= res_rows.  stats != NULL: also the per-row partials as sdeo_debug_gemm_stats_f16, except that with a
+ *   split-K plan (*strips_out = 0) the GEMM still runs and the caller takes the statistics from sdeo_debug_row_stats_f16
+ * attention_qb: sdeo_attention_f16 whose q holds q_batches batches (b / 2 <= q_batches <= b): batch i reads the queries of batch
+ *   i - q_batches when i >= q_batches; k, v and o hold b batches */
+int sdeo_debug_gemm_res_rows_f16(void* y, int ldy, const void* x, int ldx, const void* w, int ldw, const float* bias, const void* res,
+                                 int ldres, int res_rows, int m, int n, int k, float* stats, int stats_ld, int* strips_out, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+int sdeo_debug_attention_qb_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int b,
+                                int q_batches, int heads, int tq, int tk, int tk_stride, int v_batch_stride, int d, float scale, void* stream);
+
 /* fp8 weight pack at op level (tests): quantise [rows][cols] fp16 in place to its dequantised values, codes -> q, scales -> scale;
  * sdeo_debug_next_weights_fp8 makes the NEXT sdeo_gemm_f16 / sdeo_conv2d_nhwc_f16 call of this thread stream these codes
  * (K-contiguous bytes, same [N][K] / KRSC layout) instead of its fp16 weight argument */

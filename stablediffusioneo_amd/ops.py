@@ -234,6 +234,31 @@ def gemm_with_row_stats(x, w, bias=None, res=None):
     return y, stats, strips.value
 
 
+def gemm_res_rows(x, w, res, res_rows, bias=None, want_stats=False):
+    """y = x w^T (+bias) + res[r mod res_rows] in fp16: the residual holds res_rows = m / 2 rows that both halves of the batch add
+    (the shared prefix of the CFG pair, csrc/net.hip build_attn).  res may be a column block of a wider tensor.
+    want_stats: returns (y, stats, strips) as gemm_with_row_stats."""
+    lib = _lib.load()
+    _need_cuda(x, w, res)
+    m, k = x.shape
+    n = w.shape[0]
+    assert res.shape == (res_rows, n) and res.stride(1) == 1
+    y = torch.empty((m, n), dtype=torch.float16, device=x.device)
+    ld = max(1, (n + 31) // 32)
+    stats = torch.zeros((m, ld, 2), dtype=torch.float32, device=x.device) if want_stats else None
+    strips = C.c_int(0)
+    ws = _ws(lib.sdeo_gemm_workspace_bytes(_i(m), _i(n), _i(k)), x.device)
+    check(lib.sdeo_debug_gemm_res_rows_f16(ptr(y), _i(n), ptr(x), _i(x.stride(0)), ptr(w), _i(w.stride(0)), ptr(bias), ptr(res),
+                                           _i(res.stride(0)), _i(res_rows), _i(m), _i(n), _i(k), ptr(stats), _i(ld), C.byref(strips),
+                                           ptr(ws), C.c_size_t(ws.numel()), cur_stream()), "gemm_res_rows")
+    if not want_stats:
+        return y
+    if strips.value == 0:
+        check(lib.sdeo_debug_row_stats_f16(ptr(stats), _i(ld), ptr(y), _i(n), _i(m), _i(n), cur_stream()), "row_stats")
+        return y, stats, 1
+    return y, stats, strips.value
+
+
 def gemm_layernorm(x, stats, strips, w_folded, ln_s, bias_folded, act=0, eps=1e-5):
     """y[m][n] = act(LN(x)[m] . w[n] + b[n]) with x [m][k] raw and the fold of (w, gamma, beta, bias)."""
     lib = _lib.load()
@@ -314,6 +339,24 @@ def attention(q, k, v, heads, tk=None, scale=None, causal=False, out=None):
     fn = lib.sdeo_attention_causal_f16 if causal else lib.sdeo_attention_f16
     check(fn(ptr(o), _i(ldo), ptr(q), _i(ldq), ptr(k), _i(ldk), ptr(v), _i(ldv), _i(b), _i(heads),
              _i(tq), _i(tk), _i(tks), _i(tksv), _i(d), _f(scale), cur_stream()), "attention")
+    return o
+
+
+def attention_q_shared(q, k, v, heads, tk=None, scale=None):
+    """attention() whose q (B/2,Tq,H*d) is shared by the two halves of the batch of k / v (B,...): batch i attends with the queries of
+    batch i mod B/2 (the cross-attention of the CFG pair's shared prefix, csrc/net.hip build_attn).  Returns (B,Tq,H*d)."""
+    lib = _lib.load()
+    _need_cuda(q, k, v)
+    qb, tq, c = q.shape
+    b, tks, tksv = k.shape[0], k.shape[1], v.shape[1]
+    tk = min(tks, tksv) if tk is None else tk
+    d = c // heads
+    scale = d ** -0.5 if scale is None else scale
+    assert b == 2 * qb and v.shape[0] == b and k.shape[2] == c and v.shape[2] == c
+    o = torch.empty((b, tq, c), dtype=torch.float16, device=q.device)
+    ldq, ldk, ldv, ldo = _rows_view(q, "q"), _rows_view(k, "k"), _rows_view(v, "v"), _rows_view(o, "out")
+    check(lib.sdeo_debug_attention_qb_f16(ptr(o), _i(ldo), ptr(q), _i(ldq), ptr(k), _i(ldk), ptr(v), _i(ldv), _i(b), _i(qb), _i(heads),
+                                          _i(tq), _i(tk), _i(tks), _i(tksv), _i(d), _f(scale), cur_stream()), "attention_q_shared")
     return o
 
 

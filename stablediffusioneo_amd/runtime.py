@@ -12,6 +12,7 @@ from ._lib import SdeoConfig, check, cur_stream, ptr
 
 HINT_CACHED, CONTEXT_CACHED, NO_CONTROL = 1, 2, 4
 STEP_LATENT_STAGED = 16
+STEP_HINT_SHARED = 32
 
 
 def TIMESTEP_ROW(i: int) -> int:
@@ -283,13 +284,16 @@ class SdeoRuntime(_HandleRuntime):
         return len(ts)
 
     def ddim_step(self, x, pred_x0, row: int, cfg_scale: float, a_t: float, a_prev: float, sqrt_one_minus_at: float, scales=None,
-                  only_mid_control: bool = False, staged: bool = False):
-        """`sdeo_ddim_step`: one eta = 0 DDIM step of the CFG pair; x (b,4,h,w) fp32 contiguous is updated in place."""
+                  only_mid_control: bool = False, staged: bool = False, hint_shared: bool = False):
+        """`sdeo_ddim_step`: one eta = 0 DDIM step of the CFG pair; x (b,4,h,w) fp32 contiguous is updated in place.
+        hint_shared: the cached hints of the unconditional half are those of the conditional half (SDEO_STEP_HINT_SHARED), so the
+        ControlNet too computes what precedes its first cross-attention once."""
         assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
         assert pred_x0 is None or (pred_x0.is_contiguous() and pred_x0.dtype == torch.float32 and pred_x0.shape == x.shape)
         check(self.lib.sdeo_ddim_step(self.handle, ptr(x), ptr(pred_x0), C.c_int(int(row)), C.c_float(cfg_scale), C.c_float(a_t),
                                       C.c_float(a_prev), C.c_float(sqrt_one_minus_at), self._scales(scales),
-                                      C.c_int(int(only_mid_control)), C.c_int(STEP_LATENT_STAGED if staged else 0), cur_stream()),
+                                      C.c_int(int(only_mid_control)), C.c_int((STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)),
+                                      cur_stream()),
               "ddim_step")
         return x
 
