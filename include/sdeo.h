@@ -331,6 +331,28 @@ int sdeo_hed_configure(sdeo_hed_handle h, int height, int width);
 int sdeo_hed_detect_u8(sdeo_hed_handle h, const uint8_t* img_hwc, uint8_t* edges, float* control_chw, float* const* side, void* stream);
 size_t sdeo_hed_device_bytes(sdeo_hed_handle h);
 
+/* The scribble family (csrc/scribble.hip): `nms(x, t, s)` of annotator/hed/__init__.py and the hint preparation of upstream
+ * gradio_fake_scribble2image / gradio_scribble2image.  All images are on the device; single planes are uint8 [h][w], any h, w >= 1.
+ * Each call only launches: no allocation, no synchronisation, no copy, hipGraph-capturable.  Arguments are checked before the first
+ * HIP call (null image, h or w < 1, sigma <= 0 or a Gaussian wider than 65 taps, workspace too small).
+ *
+ * sdeo_nms_u8: b = cv2.GaussianBlur(float32(x), (0, 0), sigma) (round(8 sigma + 1) | 1 taps, BORDER_REFLECT_101); y = b where b is
+ * the maximum of one of the four 3-tap lines through the pixel (cv2.dilate(b, line) == b, neighbours outside the image ignored), else
+ * 0; z = y > t ? 255 : 0.  z (optional) uint8 [h][w]; blurred (optional) fp32 [h][w] receives b.
+ * workspace: >= sdeo_nms_workspace_bytes(h, w) bytes, 4-byte aligned. */
+size_t sdeo_nms_workspace_bytes(int h, int w);
+int sdeo_nms_u8(const uint8_t* x, int h, int w, float t, float sigma, uint8_t* z, float* blurred, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* edges -> nms(edges, 127, 3.0) -> cv2.GaussianBlur(uint8, (0, 0), 3.0) (OpenCV's 8-bit fixed-point path) -> > 4 ? 255 : 0.
+ * scribble (optional): uint8 [h][w]; control_chw (optional): fp32 [3][h][w] = scribble / 255 on three identical channels (as
+ * sdeo_canny_u8).  workspace: >= sdeo_fake_scribble_workspace_bytes(h, w) bytes, 4-byte aligned. */
+size_t sdeo_fake_scribble_workspace_bytes(int h, int w);
+int sdeo_fake_scribble_u8(const uint8_t* edges, int h, int w, uint8_t* scribble, float* control_chw, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* img_hwc: uint8 [h][w][c], c in 1..4.  map (optional): uint8 [h][w], 255 where the smallest channel is below 127, else 0;
+ * control_chw (optional): fp32 [3][h][w] = map / 255. */
+int sdeo_scribble_u8(const uint8_t* img_hwc, int h, int w, int c, uint8_t* map, float* control_chw, void* stream);
+
 /* Per-kernel timing for bench.py's roofline: between begin and end every launch of the net-level calls is
  * bracketed by HIP events on the stream it runs on; end synchronises the device and returns a JSON array
  * [{"kernel", "launches", "total_ms", "flops", "bytes"}] (algorithmic flops / bytes summed over the launches).

@@ -87,6 +87,11 @@ void sdeo_debug_next_weights_fp8(const void* q, const float* scale);
  * (sdeo_set_activation_precision(h, 8, ...)) */
 int sdeo_debug_mx_launches(sdeo_handle h);
 
+/* one sdeo_fake_scribble_u8 call (same arguments) with HIP events between its three launches; synchronises and returns the JSON array
+ * [{"kernel", "launches", "total_ms"}] (tools/scribble_time.py), "[]" when the call fails.  Not capturable. */
+const char* sdeo_debug_fake_scribble_profile(const uint8_t* edges, int h, int w, uint8_t* scribble, float* control_chw, void* workspace,
+                                             size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -421,3 +421,55 @@ def maxpool2x2_nhwc(x):
     y = torch.empty((1, h // 2, w // 2, c), dtype=torch.float16, device=x.device)
     check(lib.sdeo_debug_maxpool2x2_f16(ptr(y), ptr(x), _i(h), _i(w), _i(c), cur_stream()), "maxpool2x2")
     return y
+
+
+def _u8_plane(x, what):
+    _need_cuda(x)
+    if x.dtype != torch.uint8 or x.dim() != 2:
+        raise _lib.SdeoError(f"{what}: a uint8 (H, W) plane expected, got {tuple(x.shape)} {x.dtype}")
+    return x.contiguous()
+
+
+def hed_nms(x, t, s, z=True, blurred=False):
+    """`nms(x, t, s)` of annotator/hed/__init__.py on one uint8 (H, W) device plane (csrc/scribble.hip): the uint8 0 / 255 map, and /
+    or the fp32 Gaussian blur it is taken from; (z, blurred), each None unless asked for."""
+    lib = _lib.load()
+    x = _u8_plane(x, "hed_nms")
+    h, w = x.shape
+    lib.sdeo_nms_workspace_bytes.restype = C.c_size_t
+    nb = int(lib.sdeo_nms_workspace_bytes(_i(h), _i(w)))
+    ws = _ws(nb, x.device)
+    zt = torch.empty((h, w), dtype=torch.uint8, device=x.device) if z else None
+    bt = torch.empty((h, w), dtype=torch.float32, device=x.device) if blurred else None
+    check(lib.sdeo_nms_u8(ptr(x), _i(h), _i(w), _f(t), _f(s), ptr(zt), ptr(bt), ptr(ws), C.c_size_t(nb), cur_stream()), "hed_nms")
+    return zt, bt
+
+
+def fake_scribble(edges, scribble=True, control=False):
+    """upstream gradio_fake_scribble2image's hint from a uint8 (H, W) device edge map: nms(127, 3.0), 8-bit Gaussian sigma 3, > 4.
+    (scribble uint8 (H, W), control fp32 (3, H, W) = scribble / 255), each None unless asked for."""
+    lib = _lib.load()
+    edges = _u8_plane(edges, "fake_scribble")
+    h, w = edges.shape
+    lib.sdeo_fake_scribble_workspace_bytes.restype = C.c_size_t
+    nb = int(lib.sdeo_fake_scribble_workspace_bytes(_i(h), _i(w)))
+    ws = _ws(nb, edges.device)
+    st = torch.empty((h, w), dtype=torch.uint8, device=edges.device) if scribble else None
+    ct = torch.empty((3, h, w), dtype=torch.float32, device=edges.device) if control else None
+    check(lib.sdeo_fake_scribble_u8(ptr(edges), _i(h), _i(w), ptr(st), ptr(ct), ptr(ws), C.c_size_t(nb), cur_stream()), "fake_scribble")
+    return st, ct
+
+
+def scribble_map(img, map=True, control=False):
+    """upstream gradio_scribble2image's hint from a uint8 (H, W, C) device image, C in 1..4: 255 where the darkest channel is below
+    127.  (map uint8 (H, W), control fp32 (3, H, W) = map / 255), each None unless asked for."""
+    lib = _lib.load()
+    _need_cuda(img)
+    if img.dtype != torch.uint8 or img.dim() != 3:
+        raise _lib.SdeoError(f"scribble_map: a uint8 (H, W, C) image expected, got {tuple(img.shape)} {img.dtype}")
+    img = img.contiguous()
+    h, w, c = img.shape
+    mt = torch.empty((h, w), dtype=torch.uint8, device=img.device) if map else None
+    ct = torch.empty((3, h, w), dtype=torch.float32, device=img.device) if control else None
+    check(lib.sdeo_scribble_u8(ptr(img), _i(h), _i(w), _i(c), ptr(mt), ptr(ct), cur_stream()), "scribble_map")
+    return mt, ct

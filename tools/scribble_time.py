@@ -1,0 +1,79 @@
+"""Device time of one fake-scribble hint (csrc/scribble.hip, sdeo_fake_scribble_u8: fp32 Gaussian, nms, 8-bit Gaussian + threshold +
+control) on a seeded soft-edge-like map:
+
+    python tools/scribble_time.py [--res 512] [--iters 50] [--warmup 5] [--json out.json]
+
+The call is captured once in a hipGraph; the figure is the median over `iters` replays, each bracketed by HIP events.  Then one eager
+call with events between its launches (sdeo_debug_fake_scribble_profile) is printed as the per-kernel table."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", type=int, default=512)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--json", default="")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a HIP device"
+    from stablediffusioneo_amd import _lib
+    from tests.scribble_cases import band_image
+    lib = _lib.load()
+    H = W = a.res
+    x = torch.from_numpy(band_image(H, W)).cuda()
+    sc = torch.empty((H, W), dtype=torch.uint8, device="cuda")
+    ct = torch.empty((3, H, W), dtype=torch.float32, device="cuda")
+    lib.sdeo_fake_scribble_workspace_bytes.restype = C.c_size_t
+    nb = int(lib.sdeo_fake_scribble_workspace_bytes(H, W))
+    ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
+    args = (_lib.ptr(x), H, W, _lib.ptr(sc), _lib.ptr(ct), _lib.ptr(ws), C.c_size_t(nb))
+
+    def run():
+        _lib.check(lib.sdeo_fake_scribble_u8(*args, _lib.cur_stream()), "fake_scribble")
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(a.warmup):
+            run()
+    s.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        run()
+    for _ in range(a.warmup):
+        g.replay()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(a.iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    med = statistics.median(times)
+    fn = lib.sdeo_debug_fake_scribble_profile
+    fn.restype = C.c_char_p
+    prof = json.loads(fn(*args, _lib.cur_stream()).decode())
+    kern_ms = sum(r["total_ms"] for r in prof) or 1.0
+    print(f"{'kernel':<32} {'launches':>8} {'ms':>9} {'share':>6}")
+    for r in prof:
+        print(f"{r['kernel']:<32} {r['launches']:>8} {r['total_ms']:>9.4f} {100 * r['total_ms'] / kern_ms:>5.1f}%")
+    res = {"res": a.res, "iters": a.iters, "median_ms": round(med, 4), "min_ms": round(min(times), 4), "max_ms": round(max(times), 4),
+           "profiled_kernel_ms": round(kern_ms, 4), "kept_share": round(float((sc == 255).float().mean()), 4)}
+    print(json.dumps(res))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump({"summary": res, "profile": prof}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
