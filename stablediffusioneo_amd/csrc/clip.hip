@@ -72,7 +72,7 @@ static void free_configured(Clip* e) {
   if (e->tokens) (void)hipFree(e->tokens);
   e->act = nullptr; e->splitk_ws = nullptr; e->tokens = nullptr;
   e->prog.clear();
-  e->batch = 0;
+  e->batch = 0; e->splitk_bytes = 0;
 }
 
 }  // namespace
@@ -148,18 +148,11 @@ int sdeo_clip_configure(sdeo_clip_handle h, int batch) {
   auto P = [&](size_t o) { return reinterpret_cast<f16*>(e->act + o); };
   f16 *xa = P(o_xa), *xb = P(o_xb), *a = P(o_a), *qkv = P(o_qkv), *o = P(o_o), *hid = P(o_h);
 
-  size_t ws = 0;
   auto gemm = [&](const f16* x, int K, const f16* w, int N, const float* bias, int act, const f16* res, f16* y) {
     ConvGemm p;
     p.x = x; p.w = w; p.y = y; p.bias = bias; p.res = res; p.ldres = N;
     p.B = rows; p.Cin = K; p.M = rows; p.N = N; p.K = K; p.ldx = K; p.ldw = K; p.ldy = N; p.act = act;
-    const size_t need = conv_gemm_workspace_bytes(p);
-    ws = need > ws ? need : ws;
-    e->prog.push_back(Op([p, e](hipStream_t s) mutable {
-      p.workspace = e->splitk_ws;
-      p.workspace_bytes = e->splitk_bytes;
-      return conv_gemm(p, s);
-    }, conv_gemm_kernel_name(p), 2.0 * p.M * p.N * p.K, 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N)));
+    e->prog.push_back(conv_gemm_op(p, WorkspaceRef{&e->splitk_ws, &e->splitk_bytes}, &e->splitk_bytes));
   };
   auto ln = [&](const f16* xi, const float* g, const float* b) {
     e->prog.push_back(Op([=](hipStream_t s) { return layernorm(a, W, xi, W, g, b, rows, W, 1e-5f, s); }, "layernorm", 0, 4.0 * rows * W));
@@ -190,8 +183,7 @@ int sdeo_clip_configure(sdeo_clip_handle h, int batch) {
   }
   ln(x, vp("final_layer_norm.weight"), vp("final_layer_norm.bias"));
   e->out16 = a;
-  e->splitk_bytes = ws;
-  if (ws) SDEO_HIP(hipMalloc((void**)&e->splitk_ws, ws));
+  if (e->splitk_bytes) SDEO_HIP(hipMalloc((void**)&e->splitk_ws, e->splitk_bytes));
   e->batch = B;
   return 0;
 }

@@ -10,11 +10,10 @@
 #include <unordered_map>
 #include <vector>
 
+#include "arena.h"
 #include "kernels.h"
 
 namespace sdeo {
-
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // how sdeo_*_load_weight stores a tensor: fp16 KRSC [O][R][S][ipad] conv weight, fp16 [rows][cols] matrix, fp32 as is, and
 // ff.net.0.proj with its value / gate rows interleaved
@@ -195,6 +194,27 @@ struct Profiler {
     return report.c_str();
   }
 };
+
+// The split-K workspace of a handle is sized by the largest conv_gemm_workspace_bytes of its programs, so it is allocated after they
+// are built: a launch reads where it is through this.
+struct WorkspaceRef { float* const* p; const size_t* bytes; };
+
+// THE constructor of a conv / GEMM launch: binds the workspace (and whatever else `late` sets) at launch time, names the kernel of
+// p's plan for the profiler with 2 M N K flops and the algorithmic bytes of x, w and y, and raises *max_ws to what p's plan needs.
+// tagged: shape in the profiler key; flop_k: the K that counts when the stored one is padded (HED's first conv: 3 image channels in 8)
+static inline Op conv_gemm_op(const ConvGemm& p0, WorkspaceRef ws, size_t* max_ws, bool tagged = false, int flop_k = 0,
+                              std::function<void(ConvGemm&)> late = nullptr) {
+  *max_ws = std::max(*max_ws, conv_gemm_workspace_bytes(p0));
+  return Op([p = p0, ws, late](hipStream_t s) mutable {
+    p.workspace = *ws.p;
+    p.workspace_bytes = *ws.bytes;
+    if (late) late(p);
+    return conv_gemm(p, s);
+  }, conv_gemm_kernel_name(p0), 2.0 * p0.M * p0.N * (double)(flop_k ? flop_k : p0.K),
+     2.0 * ((double)p0.M * p0.Cin + (double)p0.N * p0.K + (double)p0.M * p0.N),
+     !tagged ? std::string() : "M" + std::to_string(p0.M) + " N" + std::to_string(p0.N) + " K" + std::to_string(p0.K) + " R" +
+         std::to_string(p0.R) + " s" + std::to_string(p0.stride) + " u" + std::to_string(p0.ups));
+}
 
 // profiling off (or no profiler): one std::function call per op and nothing else
 static inline int run_program(const Program& p, hipStream_t s, Profiler* prof = nullptr) {

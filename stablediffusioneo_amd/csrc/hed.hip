@@ -306,7 +306,6 @@ int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
 
   const float* norm = e->ws.ptr<float>("norm");
   e->prog.push_back(Op([e, xin, norm, H, W](hipStream_t s) { return hed_intake(xin, e->img, norm, H, W, s); }, "hed_intake"));
-  size_t ws = 0;
   const f16* cur = xin;
   int cur_buf = -1, cin = 8;
   for (int b = 0; b < 5; ++b) {
@@ -330,14 +329,7 @@ int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
       q.Ho = h; q.Wo = w; q.M = h * w; q.N = c; q.K = 9 * cin;
       q.ldx = cin; q.ldw = q.K; q.ldy = c; q.ldres = c; q.ld_bias2 = c;
       q.act = 4;
-      ws = std::max(ws, conv_gemm_workspace_bytes(q));
-      e->prog.push_back(Op([q, e](hipStream_t s) mutable {
-                             q.workspace = e->splitk_ws;
-                             q.workspace_bytes = e->splitk_bytes;
-                             return conv_gemm(q, s);
-                           },
-                           conv_gemm_kernel_name(q), 2.0 * q.M * q.N * (double)(9 * (b == 0 && i == 0 ? 3 : cin)),
-                           2.0 * ((double)q.M * q.Cin + (double)q.N * q.K + (double)q.M * q.N)));
+      e->prog.push_back(conv_gemm_op(q, WorkspaceRef{&e->splitk_ws, &e->splitk_bytes}, &e->splitk_bytes, false, 9 * (b == 0 && i == 0 ? 3 : cin)));
       cur = dst;
       cur_buf = cur_buf < 0 ? 0 : cur_buf ^ 1;
       cin = c;
@@ -352,8 +344,7 @@ int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
     }
   }
   e->prog.push_back(Op([e, H, W](hipStream_t s) { return hed_fuse(e->edges, e->control, e->maps, H, W, s); }, "hed_fuse_kernel"));
-  e->splitk_bytes = ws;
-  if (ws) SDEO_HIP(hipMalloc((void**)&e->splitk_ws, ws));
+  if (e->splitk_bytes) SDEO_HIP(hipMalloc((void**)&e->splitk_ws, e->splitk_bytes));
   e->H = H;
   e->W = W;
   return 0;

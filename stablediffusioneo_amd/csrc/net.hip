@@ -23,7 +23,7 @@
 //     computed once per image and cached across the DDIM steps;
 //   * the two halves of sdeo_ddim_step's CFG batch [x; x] differ only in their text context, so what a network computes before its
 //     first cross-attention (input_blocks.1: ResBlock, proj_in, self-attention, attn2.to_q) runs on the first half only and the
-//     full-batch launches behind it read the half-batch tensors twice (p_unet_enc_sh / p_cn_sh, build_shared_prefix).
+//     full-batch launches behind it read the half-batch tensors twice (P_UNET_ENC_SH / P_CN_SH, build_shared_prefix).
 #include <functional>
 #include <memory>
 #include <unordered_map>
@@ -31,151 +31,13 @@
 
 #include "../../include/sdeo.h"
 #include "handle_common.h"
+#include "net_plan.h"
 
 using namespace sdeo;
 
 namespace {
 
 static inline int round8(int c) { return (c + 7) / 8 * 8; }
-
-const char* NS_UNET = "model.diffusion_model.";
-const char* NS_CN = "control_model.";
-const char* NS_VAE = "first_stage_model.";
-
-// ------------------------------------------------------------------------------------------------
-// architecture plans (mirror of stablediffusioneo_amd/spec.py, itself pinned to the reference
-// constructors by tests/golden/manifest_sd15.json)
-// ------------------------------------------------------------------------------------------------
-enum BlkKind { B_CONV_IN, B_RES, B_ATTN, B_DOWN, B_UP };
-struct Blk { BlkKind kind; std::string name; int cin, cout; };
-struct UPlan {
-  std::vector<std::vector<Blk>> in, out;
-  std::vector<Blk> mid;
-  std::vector<int> in_ch, in_ds;
-};
-
-static bool in_list(const int* v, int n, int x) {
-  for (int i = 0; i < n; ++i) if (v[i] == x) return true;
-  return false;
-}
-
-static UPlan make_uplan(const sdeo_config& c, bool with_decoder) {
-  UPlan p;
-  const int mc = c.model_channels;
-  auto nm = [](const char* pre, int i, int j) { return std::string(pre) + "." + std::to_string(i) + "." + std::to_string(j); };
-  p.in.push_back({{B_CONV_IN, "input_blocks.0.0", c.in_channels, mc}});
-  p.in_ch.push_back(mc);
-  p.in_ds.push_back(1);
-  int ch = mc, ds = 1, idx = 1;
-  for (int level = 0; level < c.num_levels; ++level) {
-    const int mult = c.channel_mult[level];
-    for (int r = 0; r < c.num_res_blocks; ++r) {
-      std::vector<Blk> layers;
-      layers.push_back({B_RES, nm("input_blocks", idx, 0), ch, mult * mc});
-      ch = mult * mc;
-      if (in_list(c.attention_resolutions, c.num_attention_resolutions, ds))
-        layers.push_back({B_ATTN, nm("input_blocks", idx, 1), ch, ch});
-      p.in.push_back(layers);
-      p.in_ch.push_back(ch);
-      p.in_ds.push_back(ds);
-      ++idx;
-    }
-    if (level != c.num_levels - 1) {
-      p.in.push_back({{B_DOWN, nm("input_blocks", idx, 0), ch, ch}});
-      p.in_ch.push_back(ch);
-      ds *= 2;
-      p.in_ds.push_back(ds);
-      ++idx;
-    }
-  }
-  p.mid = {{B_RES, "middle_block.0", ch, ch}, {B_ATTN, "middle_block.1", ch, ch}, {B_RES, "middle_block.2", ch, ch}};
-  if (!with_decoder) return p;
-  std::vector<int> stack = p.in_ch;
-  int oidx = 0;
-  for (int level = c.num_levels - 1; level >= 0; --level) {
-    const int mult = c.channel_mult[level];
-    for (int i = 0; i <= c.num_res_blocks; ++i) {
-      const int ich = stack.back();
-      stack.pop_back();
-      std::vector<Blk> layers;
-      layers.push_back({B_RES, nm("output_blocks", oidx, 0), ch + ich, mc * mult});
-      ch = mc * mult;
-      if (in_list(c.attention_resolutions, c.num_attention_resolutions, ds))
-        layers.push_back({B_ATTN, nm("output_blocks", oidx, 1), ch, ch});
-      if (level && i == c.num_res_blocks) {
-        layers.push_back({B_UP, nm("output_blocks", oidx, (int)layers.size()), ch, ch});
-        ds /= 2;
-      }
-      p.out.push_back(layers);
-      ++oidx;
-    }
-  }
-  return p;
-}
-
-struct HintConv { std::string name; int cin, cout, stride; };
-static std::vector<HintConv> hint_convs(const sdeo_config& c) {
-  const int chans[8][3] = {{-1, 16, 1}, {16, 16, 1}, {16, 32, 2}, {32, 32, 1}, {32, 96, 2}, {96, 96, 1}, {96, 256, 2}, {256, -2, 1}};
-  std::vector<HintConv> v;
-  for (int i = 0; i < 8; ++i) {
-    const int ci = chans[i][0] == -1 ? c.hint_channels : chans[i][0];
-    const int co = chans[i][1] == -2 ? c.model_channels : chans[i][1];
-    v.push_back({"input_hint_block." + std::to_string(2 * i), ci, co, chans[i][2]});
-  }
-  return v;
-}
-
-struct Arena {   // first-fit planner over one device allocation; offsets only
-  struct Blk_ { size_t off, size; bool free; };
-  std::vector<Blk_> blocks;
-  size_t end = 0, peak = 0;
-  size_t alloc(size_t bytes) {
-    bytes = align_up(bytes, 256);
-    for (size_t i = 0; i < blocks.size(); ++i) {
-      if (blocks[i].free && blocks[i].size >= bytes) {
-        if (blocks[i].size > bytes) {
-          Blk_ rest{blocks[i].off + bytes, blocks[i].size - bytes, true};
-          blocks[i].size = bytes;
-          blocks.insert(blocks.begin() + i + 1, rest);
-        }
-        blocks[i].free = false;
-        return blocks[i].off;
-      }
-    }
-    if (!blocks.empty() && blocks.back().free) {   // grow the trailing free block
-      blocks.back().size = bytes;
-      blocks.back().free = false;
-      end = blocks.back().off + bytes;
-      peak = std::max(peak, end);
-      return blocks.back().off;
-    }
-    blocks.push_back({end, bytes, false});
-    end += bytes;
-    peak = std::max(peak, end);
-    return blocks.back().off;
-  }
-  void release(size_t off) {
-    for (size_t i = 0; i < blocks.size(); ++i) {
-      if (blocks[i].off == off && !blocks[i].free) {
-        blocks[i].free = true;
-        if (i + 1 < blocks.size() && blocks[i + 1].free) { blocks[i].size += blocks[i + 1].size; blocks.erase(blocks.begin() + i + 1); }
-        if (i > 0 && blocks[i - 1].free) { blocks[i - 1].size += blocks[i].size; blocks.erase(blocks.begin() + i); }
-        return;
-      }
-    }
-  }
-};
-
-struct T {           // fp16 activation view: rows x c, row stride ld; (n,h,w) when it is an image
-  f16* p = nullptr;
-  size_t off = (size_t)-1;   // arena offset when owned
-  int n = 0, h = 0, w = 0, c = 0, ld = 0;
-  // GroupNorm partials of this tensor written by the epilogue of the conv / GEMM that produced it (ConvGemm::gn_out), 32 groups
-  float* gnp = nullptr;
-  size_t gnp_off = (size_t)-1;
-  int gn_slots = 0;
-  int rows() const { return n * h * w; }
-};
 
 // LayerNorm folded into a Linear at weight-finalisation time (fold_layernorm): offsets into the weight slab
 struct FoldJob { size_t w_out, s_out, b_out, w_in; std::string gamma, beta, bias; int rows, C; };
@@ -184,6 +46,50 @@ struct ComposeJob { size_t w_out, b_out; std::string wp, bp, w2, b2; int C; };
 // a [rows][cols] fp16 matrix of the UNet / ControlNet that a conv / GEMM streams as its weight operand: with fp8 weights
 // (sdeo_set_weight_precision) it gets an e4m3fn copy + per-row scales and its fp16 copy is replaced by the dequantised values
 struct QRegion { size_t off; int rows, cols; size_t q_off, s_off; };
+
+struct Builder;
+
+// fp8 state of a handle: the per-row-scaled fp8 weight copies (sdeo_set_weight_precision) and the block-scaled packs
+// (sdeo_set_activation_precision), with the two operand substitutions Builder::launch_conv applies, in this order
+struct Fp8State {
+  std::vector<QRegion> qregions;
+  std::unordered_map<size_t, int> qindex;              // fp16 slab offset -> qregions index
+  int weight_bits = 16;                                // 8: fp8 e4m3fn weights for the UNet / ControlNet matrices
+  char* q8slab = nullptr;                              // fp8 codes + scales (allocated at the first fp8 finalize)
+  size_t q8_bytes = 0;
+  int act_bits = 16, mx_min_rows = 2048;               // 8: block-scaled fp8 activations x weights for GEMMs of >= mx_min_rows rows
+  char* mxslab = nullptr;                              // block-scaled packs of the matrices (codes + e8m0 scales)
+  size_t mx_bytes = 0;
+  struct MxRegion { size_t q_off, s_off; int rows, cols; };
+  std::unordered_map<size_t, MxRegion> mxindex;        // fp16 slab offset of a matrix -> its block-scaled pack
+  int mx_launches = 0;                                 // GEMMs of the current programs that run on the block-scaled fp8 MFMA
+  void use_mx(ConvGemm& p, int Mplan, Builder& b);
+  void use_fp8_weights(ConvGemm& p, int Mplan, const char* slab) const;
+};
+
+// What the launches of one stream work in: an arena and the two workspaces.  The workspaces are sized by the programs, so they are
+// allocated between the planning pass and the build pass: a launch reads them through the Lane* it captured.
+struct Lane {
+  Arena* arena = nullptr;        // planner of the build pass under way
+  char* base = nullptr;          // device allocation the offsets of `arena` index, and its size
+  size_t bytes = 0;
+  float* splitk_ws = nullptr; size_t splitk_ws_bytes = 0;
+  float* gn_ws = nullptr;
+  WorkspaceRef splitk() const { return WorkspaceRef{&splitk_ws, &splitk_ws_bytes}; }
+};
+// L_SIDE: ControlNet runs concurrently with the UNet encoder on a stream of its own (both depend only on x, t, context), joined
+// before the decoder consumes the controls
+enum { L_MAIN, L_SIDE, L_COUNT };
+
+constexpr int kMaxControls = 13;
+
+// Programs of a configured handle.  P_TEMB + net: the time embedding of one network.  P_UNET_ENC_SH / P_CN_SH: P_UNET_ENC / P_CN with
+// input_blocks.1 up to its cross-attention run on the first N / 2 images only (build_shared_prefix); empty when N is odd or the block
+// has no transformer
+enum ProgId {
+  P_HINT, P_CTX_CN, P_CTX_UNET, P_CN, P_CN_SH, P_CN_EXPORT, P_CTRL_IMPORT, P_UNET_ENC, P_UNET_ENC_SH, P_UNET_DEC, P_UNET_DEC_FUSED,
+  P_UNET_NOCTRL, P_VAE, P_VAE_ENC, P_TEMB, P_TEMB_CN, P_TEMB_TAB, P_X0, P_EPS_EXPORT, P_COUNT
+};
 
 }  // namespace
 
@@ -195,58 +101,36 @@ struct sdeo_handle_s {
   std::unordered_map<std::string, size_t> named_off;   // extra named regions (stacked parents, LayerNorm-folded copies)
   std::vector<FoldJob> folds;
   std::vector<ComposeJob> composes;
-  std::vector<QRegion> qregions;
-  std::unordered_map<size_t, int> qindex;              // fp16 slab offset -> qregions index
-  int weight_bits = 16;                                // 8: fp8 e4m3fn weights for the UNet / ControlNet matrices
-  int act_bits = 16, mx_min_rows = 2048;               // 8: block-scaled fp8 activations x weights for GEMMs of >= mx_min_rows rows
-  char* mxslab = nullptr;                              // block-scaled packs of the matrices (codes + e8m0 scales)
-  size_t mx_bytes = 0;
-  struct MxRegion { size_t q_off, s_off; int rows, cols; };
-  std::unordered_map<size_t, MxRegion> mxindex;        // fp16 slab offset of a matrix -> its block-scaled pack
-  int mx_launches = 0;                                 // GEMMs of the current programs that run on the block-scaled fp8 MFMA
-  char* q8slab = nullptr;                              // fp8 codes + scales (allocated at the first fp8 finalize)
-  size_t q8_bytes = 0;
+  Fp8State fp8;
   bool finalized = false;
   // per-net stacked time-embedding projection
   int emb_total[2] = {0, 0};
   std::unordered_map<std::string, int> emb_row;        // "<ns><resblock>" -> row offset
-  // problem size + arena
+  // problem size, arenas + workspaces (lanes[L_MAIN].base != nullptr: configured), side stream
   int N = 0, lh = 0, lw = 0;
-  char* arena = nullptr;
-  size_t arena_bytes = 0;
-  float* splitk_ws = nullptr;
-  size_t splitk_ws_bytes = 0;
-  float* gn_ws = nullptr;
-  size_t gn_ws_bytes = 0;
-  // second arena + workspaces + stream: ControlNet runs concurrently with the UNet encoder (both depend only on
-  // x, t, context), joined before the decoder consumes the controls
-  char* arena2 = nullptr;
-  size_t arena2_bytes = 0;
-  float* splitk_ws2 = nullptr;
-  float* gn_ws2 = nullptr;
+  Lane lanes[L_COUNT];
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool overlap = true;       // SDEO_OVERLAP=0 runs ControlNet and UNet back to back on one stream
   // boundary buffers (device, owned)
   float* in_x = nullptr; float* in_hint = nullptr; float* in_ctx = nullptr; int64_t* in_t = nullptr;
-  float* in_ctrl[13] = {nullptr};
+  float* in_ctrl[kMaxControls] = {nullptr};
   float* out_eps = nullptr;
-  float* out_ctrl[13] = {nullptr};
+  float* out_ctrl[kMaxControls] = {nullptr};
   float* vae_in = nullptr; float* vae_out = nullptr; uint8_t* vae_u8 = nullptr;
-  // VAE encoder (sdeo_enable_vae_encoder): boundary buffers of one image, and what the next run of p_vae_enc reads (set by
+  // VAE encoder (sdeo_enable_vae_encoder): boundary buffers of one image, and what the next run of P_VAE_ENC reads (set by
   // sdeo_vae_encode, read at launch): the uint8 image instead of the fp32 one, the noise instead of the posterior mode
   bool vae_encoder = false;
   float* enc_img = nullptr; uint8_t* enc_img_u8 = nullptr; float* enc_noise = nullptr; float* enc_z = nullptr; float* enc_moments = nullptr;
   int enc_from_u8 = 0, enc_with_noise = 0;
   std::vector<void*> extra_allocs;
   // persistent activations
-  T ctrl[13];            // fp16 NHWC controls (ControlNet output / UNet input), unscaled
-  T cn_h[13];            // the ControlNet block outputs the zero convs read (kept until the UNet decoder has run)
-  float scales[13];
-  float eff_scales[13];  // scales with only_mid_control folded in (0 for the twelve skip controls), read at launch by p_unet_dec_fused
+  T ctrl[kMaxControls];  // fp16 NHWC controls (ControlNet output / UNet input), unscaled
+  T cn_h[kMaxControls];  // the ControlNet block outputs the zero convs read (kept until the UNet decoder has run)
+  float scales[kMaxControls];
+  float eff_scales[kMaxControls];  // scales with only_mid_control folded in (0 for the twelve skip controls), read at launch by P_UNET_DEC_FUSED
   int only_mid = 0;
-  bool use_control = true;
-  // time embedding (`openaimodel.py:777-781` + every ResBlock's emb_layers): fp32 [N][emb_total] per net, written by p_temb[net] from
+  // time embedding (`openaimodel.py:777-781` + every ResBlock's emb_layers): fp32 [N][emb_total] per net, written by P_TEMB + net from
   // in_t -- or, for a sampler that announced its schedule (sdeo_set_timestep_table), one row of a table computed once per schedule.
   // The ResBlock convs read their pointer / row stride at LAUNCH time (emb_cur / emb_ld_cur), like the control scales.
   static constexpr int kTabRows = 128;
@@ -256,14 +140,9 @@ struct sdeo_handle_s {
   int tab_count = 0;
   const float* emb_cur[2] = {nullptr, nullptr};
   int emb_ld_cur[2] = {0, 0};
-  T x0;                  // fp16 NHWC copy of the latent input, shared by ControlNet and UNet (p_x0 writes it from in_x)
-  T eps16;               // the UNet's eps before the NCHW fp32 export (p_eps_export), read directly by sdeo_ddim_step
-  // programs
-  Program p_hint, p_ctx_cn, p_ctx_unet, p_cn, p_cn_export, p_ctrl_import, p_unet_enc, p_unet_dec, p_unet_noctrl, p_vae, p_vae_enc;
-  Program p_temb[2], p_temb_tab, p_x0, p_eps_export, p_unet_dec_fused;
-  // p_unet_enc / p_cn with input_blocks.1 up to its cross-attention run on the first N / 2 images only (build_shared_prefix); empty
-  // when N is odd or the block has no transformer
-  Program p_unet_enc_sh, p_cn_sh;
+  T x0;                  // fp16 NHWC copy of the latent input, shared by ControlNet and UNet (P_X0 writes it from in_x)
+  T eps16;               // the UNet's eps before the NCHW fp32 export (P_EPS_EXPORT), read directly by sdeo_ddim_step
+  Program prog[P_COUNT]; // free_configured clears them all
   std::vector<size_t> ctrl_elems;
   size_t device_bytes = 0;
   // profiling (sdeo_profile_*): HIP events around every launch of the next programs
@@ -274,7 +153,6 @@ struct sdeo_handle_s {
 namespace {
 
 typedef sdeo_handle_s Engine;
-
 // ------------------------------------------------------------------------------------------------
 // registry construction
 // ------------------------------------------------------------------------------------------------
@@ -283,8 +161,8 @@ struct Registry {
   bool quant = true;          // matrices registered now belong to the UNet / ControlNet (fp8-eligible), not the VAE
   void region(size_t off, int rows, int cols) {
     if (!quant) return;
-    e->qindex[off] = (int)e->qregions.size();
-    e->qregions.push_back(QRegion{off, rows, cols, 0, 0});
+    e->fp8.qindex[off] = (int)e->fp8.qregions.size();
+    e->fp8.qregions.push_back(QRegion{off, rows, cols, 0, 0});
   }
   size_t take(size_t bytes) { return e->ws.take(bytes); }
   void add(const std::string& name, WKind kind, std::initializer_list<int64_t> dims, size_t off, int ipad = 0) {
@@ -378,12 +256,12 @@ static void reg_attn(Registry& r, const std::string& ns, const Blk& b, int ctx) 
   r.e->composes.push_back(cj);
 }
 
+// where the one conv3x3 of a conv-only block (B_CONV_IN / B_DOWN / B_UP) keeps its parameters below the block's name
+static const char* conv_suffix(BlkKind k) { return k == B_DOWN ? ".op" : k == B_UP ? ".conv" : ""; }
+
 static int plan_emb_total(const UPlan& p) {
   int t = 0;
-  auto acc = [&](const std::vector<Blk>& v) { for (auto& b : v) if (b.kind == B_RES) t += b.cout; };
-  for (auto& v : p.in) acc(v);
-  acc(p.mid);
-  for (auto& v : p.out) acc(v);
+  for_each_block(p, [&](const Blk& b) { if (b.kind == B_RES) t += b.cout; });
   return t;
 }
 
@@ -399,20 +277,13 @@ static void reg_unet_like(Registry& r, const std::string& ns, const UPlan& p, co
   r.region(ew, total, emb);
   r.e->named_off[ns + "emb_all.bias"] = eb;
   int row = 0;
-  auto blocks = [&](const std::vector<Blk>& v) {
-    for (auto& b : v) {
-      switch (b.kind) {
-        case B_CONV_IN: r.conv(ns + b.name, b.cin, b.cout, 3); break;
-        case B_RES: reg_res(r, ns, b, emb, ew, eb, row); break;
-        case B_ATTN: reg_attn(r, ns, b, c.context_dim); break;
-        case B_DOWN: r.conv(ns + b.name + ".op", b.cin, b.cout, 3); break;
-        case B_UP: r.conv(ns + b.name + ".conv", b.cin, b.cout, 3); break;
-      }
+  for_each_block(p, [&](const Blk& b) {
+    switch (b.kind) {
+      case B_RES: reg_res(r, ns, b, emb, ew, eb, row); break;
+      case B_ATTN: reg_attn(r, ns, b, c.context_dim); break;
+      default: r.conv(ns + b.name + conv_suffix(b.kind), b.cin, b.cout, 3);
     }
-  };
-  for (auto& v : p.in) blocks(v);
-  blocks(p.mid);
-  for (auto& v : p.out) blocks(v);
+  });
 }
 
 static void reg_vae_res(Registry& r, const std::string& p, int cin, int cout) {
@@ -421,21 +292,6 @@ static void reg_vae_res(Registry& r, const std::string& p, int cin, int cout) {
   r.norm(p + ".norm2", cout);
   r.conv(p + ".conv2", cout, cout, 3);
   if (cin != cout) r.conv(p + ".nin_shortcut", cin, cout, 1);
-}
-
-struct VLevel { int level; std::vector<std::pair<int, int>> blocks; bool up; };
-static std::vector<VLevel> vae_levels(const sdeo_config& c, int* block_in_out) {
-  const int nl = c.vae_num_levels;
-  int bi = c.vae_ch * c.vae_ch_mult[nl - 1];
-  *block_in_out = bi;
-  std::vector<VLevel> v;
-  for (int l = nl - 1; l >= 0; --l) {
-    const int bo = c.vae_ch * c.vae_ch_mult[l];
-    VLevel L{l, {}, l != 0};
-    for (int j = 0; j <= c.vae_num_res_blocks; ++j) { L.blocks.push_back({bi, bo}); bi = bo; }
-    v.push_back(L);
-  }
-  return v;
 }
 
 static void build_registry(Engine* e) {
@@ -531,10 +387,8 @@ struct ConvOpts {                     // conv / gemm options
 struct Builder {
   typedef ConvOpts CO;
   Engine* e;
-  Arena* arena;
+  const Lane* lane;          // arena and workspaces of the stream the program built now runs on
   bool dry;
-  char* base = nullptr;      // device base of `arena`
-  int ws_sel = 0;            // 0: main-stream workspaces, 1: side-stream (ControlNet) workspaces
   // Shared prefix of the CFG pair (build_shared_prefix).  `share`: the block built now is the variant whose ops in front of the first
   // cross-attention run on the first N / 2 images; build_res / build_attn raise `half` around those ops.  A half-batch launch keeps the
   // full-batch tensors (same arena plan, it writes a prefix of them) and the full-batch problem's kernel plan (ConvGemm::plan_B,
@@ -547,18 +401,15 @@ struct Builder {
   T alloc(int n, int h, int w, int c) {
     T t;
     t.n = n; t.h = h; t.w = w; t.c = c; t.ld = c;
-    t.off = arena->alloc((size_t)n * h * w * c * 2);
-    t.p = reinterpret_cast<f16*>(base + t.off);
+    t.off = lane->arena->alloc((size_t)n * h * w * c * 2);
+    t.p = reinterpret_cast<f16*>(lane->base + t.off);
     return t;
   }
   T alloc2d(int rows, int c) { return alloc(1, 1, rows, c); }
-  void release(T& t) {
-    if (t.off != (size_t)-1) arena->release(t.off);
-    t.off = (size_t)-1;
-    if (t.gnp_off != (size_t)-1) arena->release(t.gnp_off);
-    t.gnp_off = (size_t)-1;
-    t.gnp = nullptr;
-  }
+  void release(T& t) { t.release(*lane->arena); }
+  void advance(T& cur, T next) { release(cur); cur = next; }      // cur = f(cur): the input is released once its successor exists
+  template <class F>
+  void on_lane(const Lane* l, F build) { const Lane* saved = lane; lane = l; build(); lane = saved; }      // what `build` builds runs on l
   // producer side of the GroupNorm fusion: when the plan of p can, give it a partials buffer and record it on the output tensor
   static bool gn_from_producer() { static const bool on = [] { const char* v = getenv("SDEO_GN_PRODUCER_STATS"); return !v || atoi(v) != 0; }(); return on; }
   // The buffer is reserved whatever the plan (sized for the smallest tile: 32 rows per entry), so that the arena plan does not depend
@@ -567,7 +418,7 @@ struct Builder {
   void reserve_gn_partials(const ConvGemm& p, T& y) {
     if (!gn_from_producer() || p.N % 32) return;
     const int hw = p.Ho * p.Wo;
-    y.gnp_off = arena->alloc((size_t)(p.plan_B ? p.plan_B : p.B) * ((hw + 31) / 32) * 32 * 2 * sizeof(float));
+    y.gnp_off = lane->arena->alloc((size_t)(p.plan_B ? p.plan_B : p.B) * ((hw + 31) / 32) * 32 * 2 * sizeof(float));
     y.gnp = nullptr;                       // set by launch_conv when the plan emits
     y.gn_slots = 0;
   }
@@ -586,53 +437,22 @@ struct Builder {
   const f16* named_w(const std::string& name) { return reinterpret_cast<const f16*>(e->ws.slab + e->named_off.at(name)); }
   const float* named_v(const std::string& name) { return reinterpret_cast<const float*>(e->ws.slab + e->named_off.at(name)); }
 
-
   void launch_conv(ConvGemm p, const float* scale_host, RowStats* stats = nullptr, T* gn_y = nullptr, const ConvOpts* lo = nullptr) {
     // precision and scratch sizes follow the problem whose plan the launch takes (a half-batch launch: the full-batch one)
     const int Mplan = p.plan_B ? p.M / p.B * p.plan_B : p.M;
-    if (e->act_bits == 8 && e->mxslab && Mplan >= e->mx_min_rows && p.R == 1 && p.S == 1 && p.stride == 1 && !p.ups && p.K % 128 == 0 &&
-        p.K == p.Cin && p.ldx % 16 == 0 && !p.bias_per_row && p.y && !p.y32) {
-      // block-scaled fp8 on both sides: pack the activations (one launch), run the GEMM on the fp8 MFMA
-      auto it = e->mxindex.find((size_t)(reinterpret_cast<const char*>(p.w) - e->ws.slab));
-      if (it != e->mxindex.end() && it->second.cols == p.ldw && p.N <= it->second.rows) {
-        T xq = alloc2d(Mplan, p.K / 2), xs = alloc2d(Mplan, (p.K / 32 + 15) / 16 * 8);      // bytes: M x K codes, M x roundup(K/32, 16) scales
-        uint8_t* q = reinterpret_cast<uint8_t*>(xq.p);
-        uint8_t* sc = reinterpret_cast<uint8_t*>(xs.p);
-        const int lds = (p.K / 32 + 15) / 16 * 16;
-        const f16* xp = p.x; const int M_ = p.M, K_ = p.K, ldx_ = p.ldx;
-        push([=](hipStream_t s) { return quantize_mx(q, sc, xp, M_, K_, ldx_, K_, lds, s); }, "quantize_mx", 0, 3.0 * M_ * K_,
-             "rows" + std::to_string(M_) + " C" + std::to_string(K_));
-        p.x = reinterpret_cast<const f16*>(q); p.ldx = p.K;
-        p.w = reinterpret_cast<const f16*>(e->mxslab + it->second.q_off); p.ldw = it->second.cols;
-        p.mx_sx = sc; p.mx_ldsx = lds;
-        p.mx_sw = reinterpret_cast<const uint8_t*>(e->mxslab + it->second.s_off); p.mx_ldsw = it->second.cols / 32;
-        if (!dry && !share) ++e->mx_launches;
-        mx_tmp.push_back(xq); mx_tmp.push_back(xs);
-      }
-    }
-    if (!p.mx_sx && e->weight_bits == 8 && Mplan <= 512 && p.Cin % 64 == 0 && !p.ups && !p.bias_per_row && !conv_gemm_plan_is_halo(p)) {
-      // weight-bound shapes stream the fp8 copy of their matrix (same numbers: the fp16 copy holds the dequantised values); where
-      // the measured fp16 plan is a halo-reuse 3x3 kernel (activation-bound: M = 512 at long K) that kernel keeps the job
-      auto it = e->qindex.find((size_t)(reinterpret_cast<const char*>(p.w) - e->ws.slab));
-      if (it != e->qindex.end()) {
-        const QRegion& q = e->qregions[it->second];
-        if (q.cols == p.ldw && p.N <= q.rows) {
-          p.w = reinterpret_cast<const f16*>(e->q8slab + q.q_off);
-          p.wscale = reinterpret_cast<const float*>(e->q8slab + q.s_off);
-        }
-      }
-    }
-    max_splitk = std::max(max_splitk, e->autotune ? conv_gemm_autotune_workspace_bytes(p) : conv_gemm_workspace_bytes(p));
+    e->fp8.use_mx(p, Mplan, *this);
+    e->fp8.use_fp8_weights(p, Mplan, e->ws.slab);
+    const size_t tune_ws = e->autotune ? conv_gemm_autotune_workspace_bytes(p) : 0;
     if (!dry && e->autotune && !share) {       // (the shared variant of a block runs the plans its full-batch build measured)
       ConvGemm q = p;
-      q.workspace = ws_sel ? e->splitk_ws2 : e->splitk_ws;
-      q.workspace_bytes = e->splitk_ws_bytes;
+      q.workspace = lane->splitk_ws;
+      q.workspace_bytes = lane->splitk_ws_bytes;
       if (conv_gemm_autotune(q, 0) && err.empty()) err = std::string("autotune failed: ") + sdeo_last_error();
     }
-    if (gn_y && gn_y->gnp_off != (size_t)-1) {      // the plan of this shape is final now: emit the GroupNorm partials if it can
+    if (gn_y && gn_y->gn_reserved()) {      // the plan of this shape is final now: emit the GroupNorm partials if it can
       const int cpg = p.N / 32, slots = conv_gemm_gn_slots(p, cpg);
       if (slots > 0) {
-        gn_y->gnp = reinterpret_cast<float*>(base + gn_y->gnp_off);
+        gn_y->gnp = reinterpret_cast<float*>(lane->base + gn_y->gnp_off);
         gn_y->gn_slots = slots;
         p.gn_out = gn_y->gnp; p.gn_cpg = cpg; p.gn_slots = slots; p.gn_groups = 32;
       }
@@ -648,21 +468,14 @@ struct Builder {
       if (stats->strips > 0 && stats->strips <= stats->ld) { p.stats_out = stats->p; p.stats_ld = stats->ld; }
       else { stats->strips = 1; stats_by_kernel = true; }
     }
-    Engine* eng = e;
-    const int sel = ws_sel;
-    const float* const* b2cur = lo ? lo->bias2_cur : nullptr;
-    const int* b2ld = lo ? lo->ld_bias2_cur : nullptr;
-    const int b2off = lo ? lo->bias2_off : 0;
-    push([p, scale_host, eng, sel, b2cur, b2ld, b2off](hipStream_t s) mutable {
-      p.workspace = sel ? eng->splitk_ws2 : eng->splitk_ws;
-      p.workspace_bytes = eng->splitk_ws_bytes;
-      if (scale_host) p.scale = *scale_host;
-      if (b2cur) { p.bias2 = *b2cur + b2off; p.ld_bias2 = *b2ld; }
-      return conv_gemm(p, s);
-    }, conv_gemm_kernel_name(p), 2.0 * p.M * p.N * p.K,
-       2.0 * ((double)p.M * p.Cin * (p.R * p.S > 1 ? 1 : 1) + (double)p.N * p.K + (double)p.M * p.N),
-       "M" + std::to_string(p.M) + " N" + std::to_string(p.N) + " K" + std::to_string(p.K) + " R" + std::to_string(p.R) + " s" +
-           std::to_string(p.stride) + " u" + std::to_string(p.ups));
+    const float* const* b2cur = lo ? lo->bias2_cur : nullptr; const int* b2ld = lo ? lo->ld_bias2_cur : nullptr; const int b2off = lo ? lo->bias2_off : 0;
+    size_t need = 0;
+    Op op = conv_gemm_op(p, lane->splitk(), &need, true, 0, [scale_host, b2cur, b2ld, b2off](ConvGemm& q) {      // read when the launch runs
+      if (scale_host) q.scale = *scale_host;
+      if (b2cur) { q.bias2 = *b2cur + b2off; q.ld_bias2 = *b2ld; }
+    });
+    if (!dry) prog->push_back(std::move(op));
+    max_splitk = std::max(max_splitk, e->autotune ? tune_ws : need);      // (autotune: sized before it could change the plan)
     for (auto& t : mx_tmp) release(t);       // the packed activations live for this one launch
     mx_tmp.clear();
     if (stats_by_kernel) {
@@ -702,7 +515,7 @@ struct Builder {
     const int hv = ups ? 2 * x.h : x.h, wv = ups ? 2 * x.w : x.w;
     const int ho = (hv + pad + pad_after - k) / stride + 1, wo = (wv + pad + pad_after - k) / stride + 1;
     const int cs = o.cout_store > 0 ? o.cout_store : cout;
-    T y = o.out ? *o.out : alloc(x.n, ho, wo, cs);
+    T y = o.out ? o.out->view() : alloc(x.n, ho, wo, cs);
     const int n = half ? x.n / 2 : x.n;
     if (w && w->ipad != x.c && err.empty()) err = "conv " + name + ": input has " + std::to_string(x.c) + " channels, weight expects " + std::to_string(w->ipad);
     p.x = x.p; p.y = y.p;
@@ -718,9 +531,7 @@ struct Builder {
     const bool want_gn = o.gn_next && !o.out && !o.scale_host && cs == y.c;
     if (want_gn) reserve_gn_partials(p, y);
     launch_conv(p, o.scale_host, o.stats, want_gn ? &y : nullptr, &o);
-    T r = y;
-    if (o.out) r.off = (size_t)-1;
-    return r;
+    return y;
   }
 
   // y[rows][n] = x[rows][k] . w[n][k]^T (+bias)(+res)
@@ -728,7 +539,7 @@ struct Builder {
     ConvGemm p;
     const int rows = half ? x.rows() / 2 : x.rows();
     T y;
-    if (!out32) y = o.out ? *o.out : alloc(x.n, x.h, x.w, n);
+    if (!out32) y = o.out ? o.out->view() : alloc(x.n, x.h, x.w, n);
     p.x = x.p; p.w = w; p.bias = bias;
     if (out32) { p.y32 = out32; p.ldy = ld32; } else { p.y = y.p; p.ldy = y.ld; }
     if (o.res) { p.res = o.res->p; p.ldres = o.res->ld; }
@@ -739,7 +550,6 @@ struct Builder {
     set_ln(p, o);
     if (o.ln && o.ln->c != x.c && err.empty()) err = "LayerNorm statistics of a " + std::to_string(o.ln->c) + "-channel tensor fed to K = " + std::to_string(x.c);
     launch_conv(p, o.scale_host, o.stats);
-    if (o.out) y.off = (size_t)-1;
     return y;
   }
 
@@ -756,28 +566,22 @@ struct Builder {
   }
 
   T gn(const T& x, const std::string& name, float eps, int silu_, const T* out = nullptr) {
-    T y = out ? *out : alloc(x.n, x.h, x.w, x.c);
+    T y = out ? out->view() : alloc(x.n, x.h, x.w, x.c);
     const float* g = vptr(name + ".weight");
     const float* b = vptr(name + ".bias");
     const int B = half ? x.n / 2 : x.n, HW = x.h * x.w, C = x.c;      // (no plan to inherit: the GroupNorm kernels work image by image)
     max_gn = std::max(max_gn, (size_t)B * gn_chunks(HW) * 32 * 2 * sizeof(float));
-    Engine* eng = e;
-    const int sel = ws_sel;
+    const Lane* ws = lane;                 // its GroupNorm workspace exists when the launch runs
     const f16* xp = x.p; f16* yp = y.p; const int ldx = x.ld, ldy = y.ld;
-    const GnArgs gargs{yp, xp, g, b, nullptr, ldy, ldx, B, HW, C, 32, eps, silu_};
-    if (x.gnp && !groupnorm_is_single_launch(gargs)) {
-      // the statistics came out of the producer's epilogue: one launch (normalise) instead of two
-      GnArgs ga = gargs;
+    GnArgs ga{yp, xp, g, b, nullptr, ldy, ldx, B, HW, C, 32, eps, silu_};
+    // statistics that came out of the producer's epilogue: one launch (normalise) instead of two
+    const bool apply_only = x.gnp && !groupnorm_is_single_launch(ga);
+    if (apply_only) {
       ga.ext_partials = x.gnp; ga.ext_nsc = x.gn_slots;
       max_gn = std::max(max_gn, (size_t)B * 32 * 2 * sizeof(float));
-      push([=](hipStream_t s) mutable { ga.partials = sel ? eng->gn_ws2 : eng->gn_ws; return groupnorm_nhwc(ga, s); }, "groupnorm", 0,
-           2.0 * 2.0 * B * HW * C, "C" + std::to_string(C) + " HW" + std::to_string(HW) + " apply");
-      if (out) y.off = (size_t)-1;
-      return y;
     }
-    push([=](hipStream_t s) { return groupnorm_nhwc(yp, ldy, xp, ldx, g, b, B, HW, C, 32, eps, silu_, sel ? eng->gn_ws2 : eng->gn_ws, s); }, "groupnorm", 0,
-         3.0 * 2.0 * B * HW * C, "C" + std::to_string(C) + " HW" + std::to_string(HW));
-    if (out) y.off = (size_t)-1;
+    push([=](hipStream_t s) mutable { ga.partials = ws->gn_ws; return groupnorm_nhwc(ga, s); }, "groupnorm", 0,
+         (apply_only ? 2.0 : 3.0) * 2.0 * B * HW * C, "C" + std::to_string(C) + " HW" + std::to_string(HW) + (apply_only ? " apply" : ""));
     return y;
   }
 
@@ -786,16 +590,6 @@ struct Builder {
     T t = gn(x, gn_name, eps, silu_);
     T y = conv(t, conv_name, cout, 3, 1, 0, o);
     release(t);
-    return y;
-  }
-
-  T ln(const T& x, const std::string& name) {
-    T y = alloc(x.n, x.h, x.w, x.c);
-    const float* g = vptr(name + ".weight");
-    const float* b = vptr(name + ".bias");
-    const f16* xp = x.p; f16* yp = y.p; const int ldx = x.ld, ldy = y.ld, rows = x.rows(), C = x.c;
-    push([=](hipStream_t s) { return layernorm(yp, ldy, xp, ldx, g, b, rows, C, 1e-5f, s); }, "layernorm", 0, 4.0 * rows * C,
-         "rows" + std::to_string(rows) + " C" + std::to_string(C));
     return y;
   }
 
@@ -812,7 +606,62 @@ struct Builder {
   }
 };
 
-// ResBlock._forward (`openaimodel.py:255-275`)
+// block-scaled fp8 on both sides: pack the activations (one launch), run the GEMM on the fp8 MFMA
+void Fp8State::use_mx(ConvGemm& p, int Mplan, Builder& b) {
+  if (!(act_bits == 8 && mxslab && Mplan >= mx_min_rows && p.R == 1 && p.S == 1 && p.stride == 1 && !p.ups && p.K % 128 == 0 &&
+        p.K == p.Cin && p.ldx % 16 == 0 && !p.bias_per_row && p.y && !p.y32))
+    return;
+  auto it = mxindex.find((size_t)(reinterpret_cast<const char*>(p.w) - b.e->ws.slab));
+  if (it == mxindex.end() || it->second.cols != p.ldw || p.N > it->second.rows) return;
+  T xq = b.alloc2d(Mplan, p.K / 2), xs = b.alloc2d(Mplan, (p.K / 32 + 15) / 16 * 8);      // bytes: M x K codes, M x roundup(K/32, 16) scales
+  uint8_t* q = reinterpret_cast<uint8_t*>(xq.p);
+  uint8_t* sc = reinterpret_cast<uint8_t*>(xs.p);
+  const int lds = (p.K / 32 + 15) / 16 * 16;
+  const f16* xp = p.x; const int M_ = p.M, K_ = p.K, ldx_ = p.ldx;
+  b.push([=](hipStream_t s) { return quantize_mx(q, sc, xp, M_, K_, ldx_, K_, lds, s); }, "quantize_mx", 0, 3.0 * M_ * K_,
+         "rows" + std::to_string(M_) + " C" + std::to_string(K_));
+  p.x = reinterpret_cast<const f16*>(q); p.ldx = p.K;
+  p.w = reinterpret_cast<const f16*>(mxslab + it->second.q_off); p.ldw = it->second.cols;
+  p.mx_sx = sc; p.mx_ldsx = lds;
+  p.mx_sw = reinterpret_cast<const uint8_t*>(mxslab + it->second.s_off); p.mx_ldsw = it->second.cols / 32;
+  if (!b.dry && !b.share) ++mx_launches;
+  b.mx_tmp.push_back(xq); b.mx_tmp.push_back(xs);
+}
+
+// weight-bound shapes stream the fp8 copy of their matrix (same numbers: the fp16 copy holds the dequantised values); where
+// the measured fp16 plan is a halo-reuse 3x3 kernel (activation-bound: M = 512 at long K) that kernel keeps the job
+void Fp8State::use_fp8_weights(ConvGemm& p, int Mplan, const char* slab) const {
+  if (p.mx_sx || weight_bits != 8 || Mplan > 512 || p.Cin % 64 != 0 || p.ups || p.bias_per_row || conv_gemm_plan_is_halo(p)) return;
+  auto it = qindex.find((size_t)(reinterpret_cast<const char*>(p.w) - slab));
+  if (it == qindex.end()) return;
+  const QRegion& q = qregions[it->second];
+  if (q.cols != p.ldw || p.N > q.rows) return;
+  p.w = reinterpret_cast<const f16*>(q8slab + q.q_off);
+  p.wscale = reinterpret_cast<const float*>(q8slab + q.s_off);
+}
+
+// GroupNorm + SiLU -> conv3x3 -> GroupNorm + SiLU -> conv3x3, plus x (through a conv1x1 when the channel count changes); every conv
+// feeds a GroupNorm.  The UNet's ResBlock (`openaimodel.py:255-275`; o1 adds the time embedding) and, under the VAE's names and eps,
+// its ResnetBlock (`model.py:82-128`, no time embedding, dropout 0)
+static T build_resblock(Builder& b, const std::string& p, bool vae, const T& x, int cin, int cout, Builder::CO o1, const T* out = nullptr) {
+  static const char* const nm[2][5] = {{".in_layers.0", ".in_layers.2", ".out_layers.0", ".out_layers.3", ".skip_connection"},
+                                       {".norm1", ".conv1", ".norm2", ".conv2", ".nin_shortcut"}};
+  const float eps = vae ? 1e-6f : 1e-5f;
+  o1.gn_next = true;
+  T h1 = b.gn_conv(x, p + nm[vae][0], eps, 1, p + nm[vae][1], cout, o1);
+  T skip;
+  if (cin != cout) skip = b.conv(x, p + nm[vae][4], cout, 1, 1, 0);
+  Builder::CO o2;
+  o2.res = cin != cout ? &skip : &x;
+  o2.out = out;
+  o2.gn_next = true;
+  T y = b.gn_conv(h1, p + nm[vae][2], eps, 1, p + nm[vae][3], cout, o2);
+  b.release(h1);
+  if (cin != cout) b.release(skip);
+  return y;
+}
+static T build_vae_res(Builder& b, const std::string& p, const T& x, int cin, int cout) { return build_resblock(b, p, true, x, cin, cout, Builder::CO()); }
+
 static T build_res(Builder& b, const std::string& ns, const Blk& blk, const T& x, int net, const T* out = nullptr) {
   const std::string p = ns + blk.name;
   b.half = b.share;              // the ResBlock in front of the first transformer: both halves of the CFG pair are the same images
@@ -822,31 +671,16 @@ static T build_res(Builder& b, const std::string& ns, const Blk& blk, const T& x
   o1.ld_bias2 = b.e->emb_total[net];
   o1.bias2_cur = &b.e->emb_cur[net];
   o1.ld_bias2_cur = &b.e->emb_ld_cur[net];
-  o1.gn_next = true;
-  T h1 = b.gn_conv(x, p + ".in_layers.0", 1e-5f, 1, p + ".in_layers.2", blk.cout, o1);
-  T skip;
-  const T* res = &x;
-  if (blk.cin != blk.cout) {
-    skip = b.conv(x, p + ".skip_connection", blk.cout, 1, 1, 0);
-    res = &skip;
-  }
-  Builder::CO o2;
-  o2.res = res;
-  o2.out = out;
-  o2.gn_next = true;
-  T y = b.gn_conv(h1, p + ".out_layers.0", 1e-5f, 1, p + ".out_layers.3", blk.cout, o2);
-  b.release(h1);
-  if (blk.cin != blk.cout) b.release(skip);
+  T y = build_resblock(b, p, false, x, blk.cin, blk.cout, o1, out);
   b.half = false;
   return y;
 }
 
-struct CtxKV { T kv; };   // cross-attention K | V of one attention block: [N*TkS][2C] (K in columns 0..C-1, V in C..2C-1)
-
 // SpatialTransformer.forward + BasicTransformerBlock._forward (`attention.py:381-385,431-450`).  Each pre-LN sub-block
 // x + f(LN(x)) runs as: [GEMM that writes x also writes x's per-row statistics] -> [GEMM of f's first Linear on the RAW x with
 // LN folded in] -> ... ; see the file comment.
-static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& x, const CtxKV& kv, const T* out = nullptr) {
+// kv: cross-attention K | V of this block, computed from the context: [N*TkS][2C] (K in columns 0..C-1, V in C..2C-1)
+static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& x, const T& kv, const T* out = nullptr) {
   const sdeo_config& c = b.e->cfg;
   const std::string p = ns + blk.name;
   const std::string t = p + ".transformer_blocks.0";
@@ -875,14 +709,13 @@ static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& 
   T q2 = b.gemm(tok1, b.named_w(t + ".attn2.q_ln.w"), C, C, b.named_v(t + ".attn2.q_ln.b"), l2);
   b.half = false;
   T o2 = b.alloc(x.n, x.h, x.w, C);
-  b.attn(o2, q2.p, C, kv.kv.p, 2 * C, kv.kv.p + C, 2 * C, N, H, Tq, c.context_len, TkS, TkS, d, b.share ? N / 2 : 0);
+  b.attn(o2, q2.p, C, kv.p, 2 * C, kv.p + C, 2 * C, N, H, Tq, c.context_len, TkS, TkS, d, b.share ? N / 2 : 0);
   b.release(q2);
   // ff.net.2 and proj_out are two Linear maps with only the residual add between them: composed at finalisation into ONE [C][5C]
   // matrix over the row-concatenated operand [GEGLU output (4C) | tok2 (C)] (ComposeJob), so attn2.to_out writes tok2 into the last C
   // columns of that operand, the GEGLU GEMM writes the first 4C, and one GEMM replaces two launches
   T cat = b.alloc(x.n, x.h, x.w, 5 * C);
-  T gg = cat; gg.c = 4 * C; gg.off = (size_t)-1;
-  T tok2v = cat; tok2v.p = cat.p + 4 * C; tok2v.c = C; tok2v.off = (size_t)-1;
+  const T gg = cat.view(0, 4 * C), tok2v = cat.view(4 * C, C);
   Builder::CO r2; r2.res = &tok1; r2.res_half = b.share; r2.stats = &st2; r2.out = &tok2v;
   T tok2 = b.gemm(o2, b.wptr(t + ".attn2.to_out.0.weight"), C, C, b.vptr(t + ".attn2.to_out.0.bias"), r2);
   b.release(o2);
@@ -910,21 +743,16 @@ static void build_time_embed(Builder& b, const std::string& ns, int net, int row
     b.push([=](hipStream_t s) { return timestep_embedding(o, tp, rows, mc, s); });
   }
   Builder::CO a; a.act = 1;
-  T e1 = b.gemm(te, b.wptr(ns + "time_embed.0.weight"), mc, emb, b.vptr(ns + "time_embed.0.bias"), a);
-  b.release(te);
+  b.advance(te, b.gemm(te, b.wptr(ns + "time_embed.0.weight"), mc, emb, b.vptr(ns + "time_embed.0.bias"), a));
   // every consumer of emb applies SiLU first (emb_layers = SiLU -> Linear), so store SiLU(emb)
-  T e2 = b.gemm(e1, b.wptr(ns + "time_embed.2.weight"), emb, emb, b.vptr(ns + "time_embed.2.bias"), a);
-  b.release(e1);
-  b.gemm(e2, b.named_w(ns + "emb_all.weight"), emb, total, b.named_v(ns + "emb_all.bias"), Builder::CO(), out, total);
-  b.release(e2);
+  b.advance(te, b.gemm(te, b.wptr(ns + "time_embed.2.weight"), emb, emb, b.vptr(ns + "time_embed.2.bias"), a));
+  b.gemm(te, b.named_w(ns + "emb_all.weight"), emb, total, b.named_v(ns + "emb_all.bias"), Builder::CO(), out, total);
+  b.release(te);
 }
 
 static std::vector<const Blk*> attn_blocks(const UPlan& p) {
   std::vector<const Blk*> v;
-  auto acc = [&](const std::vector<Blk>& l) { for (auto& b : l) if (b.kind == B_ATTN) v.push_back(&b); };
-  for (auto& l : p.in) acc(l);
-  acc(p.mid);
-  for (auto& l : p.out) acc(l);
+  for_each_block(p, [&](const Blk& b) { if (b.kind == B_ATTN) v.push_back(&b); });
   return v;
 }
 
@@ -935,12 +763,6 @@ static std::vector<const Blk*> attn_blocks(const UPlan& p) {
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-struct Built {
-  std::unordered_map<std::string, CtxKV> kv[2];   // per net: attn block name -> cached K / V^T
-  T ctx16;
-  T hint_feat;
-};
-
 static int run(Engine* e, const Program& p, hipStream_t s, bool skip_zero_convs = false) {
   if (!skip_zero_convs) return run_program(p, s, &e->prof);
   for (auto& op : p) {       // the ControlNet program without its zero convs
@@ -948,19 +770,6 @@ static int run(Engine* e, const Program& p, hipStream_t s, bool skip_zero_convs 
     if (int rc = e->prof.on ? e->prof.record(op, s) : op(s)) return rc;
   }
   return 0;
-}
-
-// ResnetBlock (`model.py:82-128`, no time embedding, dropout 0) of the VAE decoder and encoder: every conv feeds a GroupNorm
-static T build_vae_res(Builder& b, const std::string& p, const T& x, int cin, int cout) {
-  Builder::CO gnx; gnx.gn_next = true;
-  T h1 = b.gn_conv(x, p + ".norm1", 1e-6f, 1, p + ".conv1", cout, gnx);
-  T sk; const T* res = &x;
-  if (cin != cout) { sk = b.conv(x, p + ".nin_shortcut", cout, 1, 1, 0); res = &sk; }
-  Builder::CO o; o.res = res; o.gn_next = true;
-  T y = b.gn_conv(h1, p + ".norm2", 1e-6f, 1, p + ".conv2", cout, o);
-  b.release(h1);
-  if (cin != cout) b.release(sk);
-  return y;
 }
 
 // AttnBlock (`model.py:179-203`) of the VAE decoder and encoder: single head of x.c channels over the x.h * x.w tokens of one image;
@@ -1008,390 +817,379 @@ static T build_vae_attn(Builder& b, const std::string& p, T hcur) {
   return yo;
 }
 
-static void build_all(Engine* e, Arena& arena, Arena& arena2, bool dry, size_t* max_splitk, size_t* max_gn, std::string* err) {
-  const sdeo_config& c = e->cfg;
-  const int N = e->N, h = e->lh, w = e->lw;
-  Builder b{e, &arena, dry};
-  b.base = e->arena;
-  Built bt;
-  const int TkS = round8(c.context_len);
+struct BuildCtx {      // state of one build_all pass
+  Builder b;
+  int N, h, w, TkS, nctrl;
+  std::unordered_map<std::string, T> kv[2];   // per net: attn block name -> cached K | V
+  T ctx16, hint_feat;
+};
+static const char* const kNetNs[2] = {NS_UNET, NS_CN};
 
-  // ---- persistent tensors first (never released): controls, context, cached K/V^T, hint features
-  for (size_t i = 0; i < e->cplan.in_ch.size(); ++i) {
-    const int ds = e->cplan.in_ds[i];
-    e->ctrl[i] = b.alloc(N, h / ds, w / ds, e->cplan.in_ch[i]);
+// persistent tensors first (never released): controls, context, cached K/V^T, hint features
+static void build_persistent(BuildCtx& c) {
+  Builder& b = c.b; Engine* e = b.e;
+  const UPlan& cp = e->cplan;
+  for (int i = 0; i < c.nctrl; ++i) {
+    const size_t j = std::min((size_t)i, cp.in_ch.size() - 1);       // the middle block's control is shaped like the last input block's
+    e->ctrl[i] = b.alloc(c.N, c.h / cp.in_ds[j], c.w / cp.in_ds[j], cp.in_ch[j]);
   }
-  {
-    const int ds = e->cplan.in_ds.back();
-    e->ctrl[e->cplan.in_ch.size()] = b.alloc(N, h / ds, w / ds, e->cplan.in_ch.back());
-  }
-  bt.ctx16 = b.alloc2d(N * TkS, c.context_dim);
-  bt.hint_feat = b.alloc(N, h, w, c.model_channels);
-  e->x0 = b.alloc(N, h, w, round8(c.in_channels));
-  e->eps16 = b.alloc(N, h, w, 4 * ((c.out_channels + 3) / 4));
-  const char* nss[2] = {NS_UNET, NS_CN};
-  const UPlan* plans[2] = {&e->uplan, &e->cplan};
+  c.ctx16 = b.alloc2d(c.N * c.TkS, e->cfg.context_dim);
+  c.hint_feat = b.alloc(c.N, c.h, c.w, e->cfg.model_channels);
+  e->x0 = b.alloc(c.N, c.h, c.w, round8(e->cfg.in_channels));
+  e->eps16 = b.alloc(c.N, c.h, c.w, 4 * ((e->cfg.out_channels + 3) / 4));
   for (int net = 0; net < 2; ++net)
-    for (const Blk* ab : attn_blocks(*plans[net])) {
-      CtxKV kv;
-      kv.kv = b.alloc2d(N * TkS, 2 * ab->cin);
-      bt.kv[net][std::string(nss[net]) + ab->name] = kv;
-    }
+    for (const Blk* ab : attn_blocks(net ? e->cplan : e->uplan)) c.kv[net][std::string(kNetNs[net]) + ab->name] = b.alloc2d(c.N * c.TkS, 2 * ab->cin);
+}
 
-  // ---- small programs (their temporaries come and go: only after every persistent tensor has its place)
-  {   // latent in: NCHW fp32 -> NHWC fp16, once for both networks
-    b.prog = &e->p_x0;
-    f16* o = e->x0.p; const float* in = e->in_x; const int Cc = c.in_channels, ld = e->x0.ld, HW = h * w;
-    b.push([=](hipStream_t s) { return nchw_f32_to_nhwc_f16(o, ld, in, N, Cc, HW, 1.0f, s); });
-    b.prog = &e->p_eps_export;
-    float* eo = e->out_eps; const f16* ein = e->eps16.p; const int eld = e->eps16.ld, Ce = c.out_channels;
-    b.push([=](hipStream_t s) { return nhwc_f16_to_nchw_f32(eo, ein, eld, N, Ce, HW, 1.0f, s); });
-  }
-  {   // time embedding: per forward (rows = N, t from in_t) and per schedule (rows = kTabRows, t from tab_t), both networks
-    // (the ControlNet's runs on the side stream beside the UNet encoder: its temporaries and split-K workspace are the side stream's)
-    const char* tns[2] = {NS_UNET, NS_CN};
-    for (int net = 0; net < 2; ++net) {
-      b.prog = &e->p_temb[net];
-      if (net == 1) { b.arena = &arena2; b.base = e->arena2; b.ws_sel = 1; }
-      build_time_embed(b, tns[net], net, N, e->in_t, e->emb_all[net]);
-      if (net == 1) { b.arena = &arena; b.base = e->arena; b.ws_sel = 0; }
-    }
-    b.prog = &e->p_temb_tab;
-    for (int net = 0; net < 2; ++net) build_time_embed(b, tns[net], net, Engine::kTabRows, e->tab_t, e->temb_tab[net]);
-  }
+// latent in: NCHW fp32 -> NHWC fp16, once for both networks; eps out: the reverse
+static void build_latent_io(BuildCtx& c) {
+  Builder& b = c.b; Engine* e = b.e;
+  const int N = c.N, HW = c.h * c.w;
+  b.prog = &e->prog[P_X0];
+  f16* o = e->x0.p; const float* in = e->in_x; const int Cc = e->cfg.in_channels, ld = e->x0.ld;
+  b.push([=](hipStream_t s) { return nchw_f32_to_nhwc_f16(o, ld, in, N, Cc, HW, 1.0f, s); });
+  b.prog = &e->prog[P_EPS_EXPORT];
+  float* eo = e->out_eps; const f16* ein = e->eps16.p; const int eld = e->eps16.ld, Ce = e->cfg.out_channels;
+  b.push([=](hipStream_t s) { return nhwc_f16_to_nchw_f32(eo, ein, eld, N, Ce, HW, 1.0f, s); });
+}
 
-  // ---- context programs: fp32 [N][77][768] -> fp16 padded; K | V = ctx [Wk; Wv]^T per attn block, one GEMM each
+// time embedding: per forward (rows = N, t from in_t) and per schedule (rows = kTabRows, t from tab_t), both networks
+// (the ControlNet's runs on the side stream beside the UNet encoder: its temporaries and split-K workspace are the side stream's)
+static void build_time_embeds(BuildCtx& c) {
+  Builder& b = c.b; Engine* e = b.e;
   for (int net = 0; net < 2; ++net) {
-    b.prog = net == 0 ? &e->p_ctx_unet : &e->p_ctx_cn;
-    {
-      f16* o = bt.ctx16.p; const float* in = e->in_ctx; const int T_ = c.context_len, Cd = c.context_dim;
-      b.push([=](hipStream_t s) { return pad_rows_f32_to_f16(o, in, N, T_, TkS, Cd, s); });
-    }
-    for (const Blk* ab : attn_blocks(*plans[net])) {
-      const std::string t = std::string(nss[net]) + ab->name + ".transformer_blocks.0";
-      const CtxKV& kv = bt.kv[net][std::string(nss[net]) + ab->name];
-      Builder::CO o; o.out = &kv.kv;
-      b.gemm(bt.ctx16, b.named_w(t + ".attn2.to_kv"), c.context_dim, 2 * ab->cin, nullptr, o);
-    }
+    b.prog = &e->prog[P_TEMB + net];
+    b.on_lane(&e->lanes[net == 1 ? L_SIDE : L_MAIN], [&] { build_time_embed(b, kNetNs[net], net, c.N, e->in_t, e->emb_all[net]); });
   }
+  b.prog = &e->prog[P_TEMB_TAB];
+  for (int net = 0; net < 2; ++net) build_time_embed(b, kNetNs[net], net, Engine::kTabRows, e->tab_t, e->temb_tab[net]);
+}
 
-  // ---- hint program (`cldm/cldm.py:147-163,288`): 8 conv3x3, SiLU between, cached across steps
-  {
-    b.prog = &e->p_hint;
-    T x = b.alloc(N, 8 * h, 8 * w, round8(c.hint_channels));
-    {
-      f16* o = x.p; const float* in = e->in_hint; const int Cc = c.hint_channels, ld = x.ld, HW = 64 * h * w;
-      b.push([=](hipStream_t s) { return nchw_f32_to_nhwc_f16(o, ld, in, N, Cc, HW, 1.0f, s); });
-    }
-    for (size_t i = 0; i < e->hconvs.size(); ++i) {
-      const HintConv& hc = e->hconvs[i];
-      Builder::CO o;
-      o.act = i + 1 < e->hconvs.size() ? 1 : 0;
-      o.cout_store = round8(hc.cout);
-      if (i + 1 == e->hconvs.size()) o.out = &bt.hint_feat;
-      T y = b.conv(x, std::string(NS_CN) + hc.name, hc.cout, 3, hc.stride, 0, o);
-      b.release(x);
-      x = y;
-    }
+// context programs: fp32 [N][77][768] -> fp16 padded; K | V = ctx [Wk; Wv]^T per attn block, one GEMM each
+static void build_context(BuildCtx& c, int net) {
+  Builder& b = c.b; Engine* e = b.e;
+  b.prog = &e->prog[net == 0 ? P_CTX_UNET : P_CTX_CN];
+  f16* o = c.ctx16.p; const float* in = e->in_ctx; const int N = c.N, T_ = e->cfg.context_len, TkS = c.TkS, Cd = e->cfg.context_dim;
+  b.push([=](hipStream_t s) { return pad_rows_f32_to_f16(o, in, N, T_, TkS, Cd, s); });
+  for (const Blk* ab : attn_blocks(net ? e->cplan : e->uplan)) {
+    const std::string name = std::string(kNetNs[net]) + ab->name;
+    Builder::CO kvo; kvo.out = &c.kv[net][name];
+    b.gemm(c.ctx16, b.named_w(name + ".transformer_blocks.0.attn2.to_kv"), e->cfg.context_dim, 2 * ab->cin, nullptr, kvo);
   }
+}
 
-  auto run_blocks = [&](const std::string& ns, const std::vector<Blk>& blocks, T x, bool release_in, int net, const T* final_out) -> T {
-    for (size_t i = 0; i < blocks.size(); ++i) {
-      const Blk& blk = blocks[i];
-      const T* out = (i + 1 == blocks.size()) ? final_out : nullptr;
-      T y;
-      switch (blk.kind) {
-        case B_CONV_IN: { Builder::CO o; o.out = out; o.gn_next = true; y = b.conv(x, ns + blk.name, blk.cout, 3, 1, 0, o); break; }
-        case B_RES: y = build_res(b, ns, blk, x, net, out); break;
-        case B_ATTN: y = build_attn(b, ns, blk, x, bt.kv[net].at(ns + blk.name), out); break;
-        case B_DOWN: { Builder::CO o; o.out = out; o.gn_next = true; y = b.conv(x, ns + blk.name + ".op", blk.cout, 3, 2, 0, o); break; }
-        case B_UP: { Builder::CO o; o.out = out; o.gn_next = true; y = b.conv(x, ns + blk.name + ".conv", blk.cout, 3, 1, 1, o); break; }
+// hint program (`cldm/cldm.py:147-163,288`): 8 conv3x3, SiLU between, cached across steps
+static void build_hint(BuildCtx& c) {
+  Builder& b = c.b; Engine* e = b.e;
+  b.prog = &e->prog[P_HINT];
+  T x = b.alloc(c.N, 8 * c.h, 8 * c.w, round8(e->cfg.hint_channels));
+  f16* xp = x.p; const float* in = e->in_hint; const int N = c.N, Cc = e->cfg.hint_channels, ld = x.ld, HW = 64 * c.h * c.w;
+  b.push([=](hipStream_t s) { return nchw_f32_to_nhwc_f16(xp, ld, in, N, Cc, HW, 1.0f, s); });
+  for (size_t i = 0; i < e->hconvs.size(); ++i) {
+    const HintConv& hc = e->hconvs[i];
+    Builder::CO o;
+    o.act = i + 1 < e->hconvs.size() ? 1 : 0;
+    o.cout_store = round8(hc.cout);
+    if (i + 1 == e->hconvs.size()) o.out = &c.hint_feat;
+    b.advance(x, b.conv(x, std::string(NS_CN) + hc.name, hc.cout, 3, hc.stride, 0, o));
+  }
+}
+
+static T run_blocks(BuildCtx& c, const std::string& ns, const std::vector<Blk>& blocks, T x, bool release_in, int net, const T* final_out) {
+  Builder& b = c.b;
+  for (size_t i = 0; i < blocks.size(); ++i) {
+    const Blk& blk = blocks[i];
+    const T* out = (i + 1 == blocks.size()) ? final_out : nullptr;
+    T y;
+    switch (blk.kind) {
+      case B_RES: y = build_res(b, ns, blk, x, net, out); break;
+      case B_ATTN: y = build_attn(b, ns, blk, x, c.kv[net].at(ns + blk.name), out); break;
+      default: {   // B_CONV_IN / B_DOWN / B_UP: one conv3x3, stride 2 (Downsample) or over the nearest-x2 source (Upsample)
+        Builder::CO o; o.out = out; o.gn_next = true;
+        y = b.conv(x, ns + blk.name + conv_suffix(blk.kind), blk.cout, 3, blk.kind == B_DOWN ? 2 : 1, blk.kind == B_UP ? 1 : 0, o);
       }
-      if (release_in || i > 0) b.release(x);
-      x = y;
     }
-    return x;
+    if (release_in || i > 0) b.release(x);
+    x = y;
+  }
+  return x;
+}
+
+// input_blocks.1 built twice from the same arena state: as it is, into the current program, and as the variant whose ops in front of
+// the first cross-attention run on the first N / 2 images (Builder::share), into sp.var.  Both place every tensor at the same address,
+// so the rest of the program, the zero convs and the decoder serve either; splice() puts the variant program together.
+struct Splice { size_t first = 0, last = 0; Program var; bool on = false; };
+static T build_shared_prefix(BuildCtx& c, const std::string& ns, const std::vector<Blk>& blocks, const T& x, int net, Splice& sp) {
+  Builder& b = c.b;
+  Arena& arena = *b.lane->arena;
+  const Arena before = arena;
+  sp.first = b.prog->size();
+  T y = run_blocks(c, ns, blocks, x, false, net, nullptr);
+  sp.last = b.prog->size();
+  if (c.N % 2 || blocks.size() != 2 || blocks[0].kind != B_RES || blocks[1].kind != B_ATTN) return y;
+  Arena after = arena;
+  arena = before;
+  Program* prog = b.prog;
+  b.prog = &sp.var; b.share = true;
+  T ys = run_blocks(c, ns, blocks, x, false, net, nullptr);
+  b.prog = prog; b.share = false;
+  if ((ys.p != y.p || ys.gnp != y.gnp || ys.gn_slots != y.gn_slots || arena.end != after.end) && b.err.empty())
+    b.err = "the shared-prefix variant of " + ns + blocks[0].name + " plans another arena";
+  after.peak = std::max(after.peak, arena.peak);
+  arena = after;
+  sp.on = true;
+  return y;
+}
+static void splice(const BuildCtx& c, Program& out, const Program& full, const Splice& sp) {
+  if (c.b.dry || !sp.on) return;
+  out.assign(full.begin(), full.begin() + sp.first);
+  out.insert(out.end(), sp.var.begin(), sp.var.end());
+  out.insert(out.end(), full.begin() + sp.last, full.end());
+}
+
+// ControlNet program (`cldm/cldm.py:284-305`)
+static void build_controlnet(BuildCtx& c) {
+  Builder& b = c.b; Engine* e = b.e;
+  Splice sp;
+  Program& p_cn = e->prog[P_CN];
+  b.prog = &p_cn;
+  const std::string ns = NS_CN;
+  // The block outputs stay allocated (cn_h): sdeo_apply_model / sdeo_ddim_step skip the zero convs here and let the UNet decoder apply
+  // them with the skip connection as the residual operand (P_UNET_DEC_FUSED); sdeo_controlnet_forward runs them here (13 controls out).
+  auto zero_conv = [&](const T& x, const std::string& name, int cout, const T* out) {
+    const size_t first = p_cn.size();
+    Builder::CO zo; zo.out = out;
+    b.conv(x, name, cout, 1, 1, 0, zo);
+    for (size_t k = first; k < p_cn.size(); ++k) p_cn[k].zero_conv = true;
   };
-
-  // input_blocks.1 built twice from the same arena state: as it is, into the current program, and as the variant whose ops in front of
-  // the first cross-attention run on the first N / 2 images (Builder::share), into sp.var.  Both place every tensor at the same address,
-  // so the rest of the program, the zero convs and the decoder serve either; splice() puts the variant program together.
-  struct Splice { size_t first = 0, last = 0; Program var; bool on = false; };
-  auto build_shared_prefix = [&](const std::string& ns, const std::vector<Blk>& blocks, const T& x, int net, Splice& sp) -> T {
-    const Arena before = *b.arena;
-    sp.first = b.prog->size();
-    T y = run_blocks(ns, blocks, x, false, net, nullptr);
-    sp.last = b.prog->size();
-    if (N % 2 || blocks.size() != 2 || blocks[0].kind != B_RES || blocks[1].kind != B_ATTN) return y;
-    Arena after = *b.arena;
-    *b.arena = before;
-    Program* prog = b.prog;
-    b.prog = &sp.var; b.share = true;
-    T ys = run_blocks(ns, blocks, x, false, net, nullptr);
-    b.prog = prog; b.share = false;
-    if ((ys.p != y.p || ys.gnp != y.gnp || ys.gn_slots != y.gn_slots || b.arena->end != after.end) && b.err.empty())
-      b.err = "the shared-prefix variant of " + ns + blocks[0].name + " plans another arena";
-    after.peak = std::max(after.peak, b.arena->peak);
-    *b.arena = after;
-    sp.on = true;
-    return y;
-  };
-  auto splice = [&](Program& out, const Program& full, const Splice& sp) {
-    if (dry || !sp.on) return;
-    out.assign(full.begin(), full.begin() + sp.first);
-    out.insert(out.end(), sp.var.begin(), sp.var.end());
-    out.insert(out.end(), full.begin() + sp.last, full.end());
-  };
-
-  // ---- ControlNet program (`cldm/cldm.py:284-305`)
-  {
-    Splice sp;
-    b.prog = &e->p_cn;
-    b.arena = &arena2; b.base = e->arena2; b.ws_sel = 1;
-    const std::string ns = NS_CN;
-    // The block outputs stay allocated (cn_h): sdeo_apply_model / sdeo_ddim_step skip the zero convs here and let the UNet decoder apply
-    // them with the skip connection as the residual operand (p_unet_dec_fused); sdeo_controlnet_forward runs them here (13 controls out).
-    auto zero_conv = [&](const T& x, const std::string& name, int cout, const T* out) {
-      const size_t first = e->p_cn.size();
-      Builder::CO zo; zo.out = out;
-      b.conv(x, name, cout, 1, 1, 0, zo);
-      for (size_t k = first; k < e->p_cn.size(); ++k) e->p_cn[k].zero_conv = true;
-    };
-    T hcur = e->x0;
-    for (size_t i = 0; i < e->cplan.in.size(); ++i) {
-      T y;
-      if (i == 0) {
-        // input_blocks.0 conv, then h += guided_hint (residual epilogue)
-        Builder::CO o; o.res = &bt.hint_feat; o.gn_next = true;
-        y = b.conv(hcur, ns + e->cplan.in[0][0].name, c.model_channels, 3, 1, 0, o);
-      } else if (i == 1) {
-        y = build_shared_prefix(ns, e->cplan.in[i], hcur, 1, sp);
-      } else {
-        y = run_blocks(ns, e->cplan.in[i], hcur, false, 1, nullptr);
-      }
-      hcur = y;
-      e->cn_h[i] = y;
-      zero_conv(hcur, ns + "zero_convs." + std::to_string(i) + ".0", e->cplan.in_ch[i], &e->ctrl[i]);
-    }
-    T m = run_blocks(ns, e->cplan.mid, hcur, false, 1, nullptr);
-    e->cn_h[e->cplan.in.size()] = m;
-    zero_conv(m, ns + "middle_block_out.0", e->cplan.in_ch.back(), &e->ctrl[e->cplan.in.size()]);
-    splice(e->p_cn_sh, e->p_cn, sp);
-    b.arena = &arena; b.base = e->arena; b.ws_sel = 0;
-  }
-  const int nctrl = (int)e->cplan.in.size() + 1;
-
-  // ---- control export (fp16 NHWC -> fp32 NCHW boundary buffers) and import
-  {
-    e->ctrl_elems.clear();
-    for (int i = 0; i < nctrl; ++i) {
-      const T& t = e->ctrl[i];
-      e->ctrl_elems.push_back((size_t)t.n * t.c * t.h * t.w);
-      if (!dry) {
-        float* o = e->out_ctrl[i]; const f16* in = t.p; const int ld = t.ld, Cc = t.c, HW = t.h * t.w;
-        e->p_cn_export.push_back([=](hipStream_t s) { return nhwc_f16_to_nchw_f32(o, in, ld, N, Cc, HW, 1.0f, s); });
-        const float* ci = e->in_ctrl[i]; f16* co = t.p;
-        e->p_ctrl_import.push_back([=](hipStream_t s) { return nchw_f32_to_nhwc_f16(co, ld, ci, N, Cc, HW, 1.0f, s); });
-      }
-    }
-  }
-
-  // ---- UNet programs (`cldm/cldm.py:22-45`), with and without control
-  for (int variant = 0; variant < 2; ++variant) {
-    const bool with_ctrl = variant == 0;
-    b.prog = with_ctrl ? &e->p_unet_enc : &e->p_unet_noctrl;
-    const std::string ns = NS_UNET;
-    std::vector<T> hs;
-    T hcur = e->x0;
-    Splice sp;
-    for (size_t i = 0; i < e->uplan.in.size(); ++i) {
-      T y = (i == 1 && with_ctrl) ? build_shared_prefix(ns, e->uplan.in[i], hcur, 0, sp) : run_blocks(ns, e->uplan.in[i], hcur, false, 0, nullptr);
-      hs.push_back(y);
-      hcur = y;
-    }
-    // middle block; its output goes straight into the first concat buffer
-    auto cat_for = [&](int c_h, const T& skip) { return b.alloc(skip.n, skip.h, skip.w, c_h + skip.c); };
-    T cat0 = cat_for(e->uplan.mid.back().cout, hs.back());
-    T view0 = cat0; view0.c = e->uplan.mid.back().cout; view0.off = (size_t)-1;
-    run_blocks(ns, e->uplan.mid, hcur, false, 0, &view0);
-    if (with_ctrl) splice(e->p_unet_enc_sh, e->p_unet_enc, sp);
-    // The decoder (`openaimodel.py:797-801` with `cldm/cldm.py:33-41`): h = cat([h, hs.pop() + control.pop()]).  Three forms of the same
-    // program: no control; controls given as tensors (the 13-tensor boundary: one add per control); controls applied as the ControlNet's
-    // zero convs themselves, out = scale * zero_conv(cn_h) + skip written straight into the concat buffer (no add launches, no fp16
-    // round trip of the control).  The latter two start from the same encoder state, so the arena is rewound between them.
-    enum { D_NOCTRL, D_ADD, D_FUSED };
-    auto build_decoder = [&](int mode, std::vector<T> hs, T cat, T view) {
-      int ci = nctrl - 1;
-      if (mode == D_ADD) {   // h += control.pop()
-        f16* yp = view.p; const int ld = view.ld, rows = view.rows(), Cc = view.c;
-        const f16* cp = e->ctrl[ci].p; const int ldc = e->ctrl[ci].ld; const float* sc = &e->scales[ci];
-        b.push([=](hipStream_t s) { return add_scaled(yp, ld, yp, ld, cp, ldc, *sc, rows, Cc, s); });
-      } else if (mode == D_FUSED) {
-        Builder::CO zo; zo.out = &view; zo.res = &view; zo.scale_host = &e->eff_scales[ci];
-        b.conv(e->cn_h[ci], std::string(NS_CN) + "middle_block_out.0", view.c, 1, 1, 0, zo);
-      }
-      --ci;
-      for (size_t oi = 0; oi < e->uplan.out.size(); ++oi) {
-        // second half of the concat buffer: hs.pop() (+ control.pop() unless only_mid_control)
-        T skip = hs.back();
-        hs.pop_back();
-        const int c_h = cat.c - skip.c;
-        if (mode == D_FUSED) {
-          T half = cat; half.p = cat.p + c_h; half.c = skip.c; half.off = (size_t)-1;
-          Builder::CO zo; zo.out = &half; zo.res = &skip; zo.scale_host = &e->eff_scales[ci];
-          b.conv(e->cn_h[ci], std::string(NS_CN) + "zero_convs." + std::to_string(ci) + ".0", skip.c, 1, 1, 0, zo);
-        } else {
-          f16* yp = cat.p + c_h; const int ld = cat.ld, rows = cat.rows(), Cc = skip.c;
-          const f16* ap = skip.p; const int lda = skip.ld;
-          const f16* cp = mode == D_ADD ? e->ctrl[ci].p : nullptr; const int ldc = mode == D_ADD ? e->ctrl[ci].ld : 0;
-          const float* sc = &e->scales[ci]; const int* om = &e->only_mid;
-          b.push([=](hipStream_t s) { return add_scaled(yp, ld, ap, lda, (*om) ? nullptr : cp, ldc, *sc, rows, Cc, s); });
-        }
-        --ci;
-        b.release(skip);
-        const std::vector<Blk>& blocks = e->uplan.out[oi];
-        if (oi + 1 < e->uplan.out.size()) {
-          const T& nskip = hs.back();
-          const int c_hn = blocks.back().cout;
-          const int up = blocks.back().kind == B_UP ? 2 : 1;
-          T ncat = b.alloc(cat.n, cat.h * up, cat.w * up, c_hn + nskip.c);
-          T nview = ncat; nview.c = c_hn; nview.off = (size_t)-1;
-          run_blocks(ns, blocks, cat, true, 0, &nview);
-          cat = ncat;
-        } else {
-          T y = run_blocks(ns, blocks, cat, true, 0, nullptr);
-          Builder::CO oo; oo.cout_store = 4 * ((c.out_channels + 3) / 4);
-          oo.out = &e->eps16;
-          b.gn_conv(y, ns + "out.0", 1e-5f, 1, ns + "out.2", c.out_channels, oo);
-          b.release(y);
-        }
-      }
-    };
-    if (!with_ctrl) {
-      build_decoder(D_NOCTRL, hs, cat0, view0);
+  T hcur = e->x0;
+  for (size_t i = 0; i < e->cplan.in.size(); ++i) {
+    if (i == 0) {
+      // input_blocks.0 conv, then h += guided_hint (residual epilogue)
+      Builder::CO o; o.res = &c.hint_feat; o.gn_next = true;
+      hcur = b.conv(hcur, ns + e->cplan.in[0][0].name, e->cfg.model_channels, 3, 1, 0, o);
+    } else if (i == 1) {
+      hcur = build_shared_prefix(c, ns, e->cplan.in[i], hcur, 1, sp);
     } else {
-      const Arena after_encoder = arena;          // everything below needs the controls: runs after the join
-      b.prog = &e->p_unet_dec;
-      build_decoder(D_ADD, hs, cat0, view0);
-      const size_t peak_add = arena.peak;
-      arena = after_encoder;
-      arena.peak = std::max(arena.peak, peak_add);
-      b.prog = &e->p_unet_dec_fused;
-      build_decoder(D_FUSED, hs, cat0, view0);
+      hcur = run_blocks(c, ns, e->cplan.in[i], hcur, false, 1, nullptr);
     }
+    e->cn_h[i] = hcur;
+    zero_conv(hcur, ns + "zero_convs." + std::to_string(i) + ".0", e->cplan.in_ch[i], &e->ctrl[i]);
   }
+  T m = run_blocks(c, ns, e->cplan.mid, hcur, false, 1, nullptr);
+  e->cn_h[c.nctrl - 1] = m;
+  zero_conv(m, ns + "middle_block_out.0", e->cplan.in_ch.back(), &e->ctrl[c.nctrl - 1]);
+  splice(c, e->prog[P_CN_SH], p_cn, sp);
+}
 
-  // ---- VAE decode program, batch 1 (`model.py:619-652`; decode_first_stage wrapper: z/scale_factor ->
-  //      post_quant_conv -> Decoder; the wrapper itself is absent from the reference tree)
-  {
-    b.prog = &e->p_vae;
-    const std::string d = std::string(NS_VAE) + "decoder";
-    T z = b.alloc(1, h, w, round8(c.vae_z_channels));
-    {
-      f16* o = z.p; const float* in = e->vae_in; const int Cc = c.vae_z_channels, ld = z.ld, HW = h * w;
-      const float sc = 1.0f / c.vae_scale_factor;
-      b.push([=](hipStream_t s) { return nchw_f32_to_nhwc_f16(o, ld, in, 1, Cc, HW, sc, s); });
-    }
-    Builder::CO pq; pq.cout_store = round8(c.vae_z_channels);
-    T z2 = b.conv(z, std::string(NS_VAE) + "post_quant_conv", c.vae_z_channels, 1, 1, 0, pq);
-    b.release(z);
-    int bin = 0;
-    auto levels = vae_levels(c, &bin);
-    Builder::CO gnx; gnx.gn_next = true;       // every conv of the decoder below feeds a GroupNorm
-    T hcur = b.conv(z2, d + ".conv_in", bin, 3, 1, 0, gnx);
-    b.release(z2);
-    T y = build_vae_res(b, d + ".mid.block_1", hcur, bin, bin);
-    b.release(hcur);
-    hcur = y;
-    hcur = build_vae_attn(b, d + ".mid.attn_1", hcur);
-    y = build_vae_res(b, d + ".mid.block_2", hcur, bin, bin);
-    b.release(hcur);
-    hcur = y;
-    int last = bin;
-    for (auto& L : levels) {
-      for (size_t j = 0; j < L.blocks.size(); ++j) {
-        y = build_vae_res(b, d + ".up." + std::to_string(L.level) + ".block." + std::to_string(j), hcur, L.blocks[j].first, L.blocks[j].second);
-        b.release(hcur);
-        hcur = y;
-        last = L.blocks[j].second;
-      }
-      if (L.up) {
-        y = b.conv(hcur, d + ".up." + std::to_string(L.level) + ".upsample.conv", last, 3, 1, 1, gnx);
-        b.release(hcur);
-        hcur = y;
-      }
-    }
-    Builder::CO oo; oo.cout_store = 4 * ((c.vae_out_ch + 3) / 4);
-    T img = b.gn_conv(hcur, d + ".norm_out", 1e-6f, 1, d + ".conv_out", c.vae_out_ch, oo);
-    b.release(hcur);
-    {
-      float* o = e->vae_out; uint8_t* u8 = e->vae_u8; const f16* in = img.p; const int ld = img.ld, Cc = c.vae_out_ch, HW = 64 * h * w;
-      b.push([=](hipStream_t s) {
-        if (int rc = nhwc_f16_to_nchw_f32(o, in, ld, 1, Cc, HW, 1.0f, s)) return rc;
-        return nhwc_f16_to_nhwc_u8(u8, in, ld, HW, Cc, s);
-      });
-    }
-    b.release(img);
+// control export (fp16 NHWC -> fp32 NCHW boundary buffers) and import
+static void build_control_io(BuildCtx& c) {
+  Engine* e = c.b.e;
+  e->ctrl_elems.clear();
+  for (int i = 0; i < c.nctrl; ++i) {
+    const T& t = e->ctrl[i];
+    e->ctrl_elems.push_back((size_t)t.n * t.c * t.h * t.w);
+    if (c.b.dry) continue;
+    float* o = e->out_ctrl[i]; const f16* in = t.p; const int N = c.N, ld = t.ld, Cc = t.c, HW = t.h * t.w;
+    e->prog[P_CN_EXPORT].push_back([=](hipStream_t s) { return nhwc_f16_to_nchw_f32(o, in, ld, N, Cc, HW, 1.0f, s); });
+    const float* ci = e->in_ctrl[i]; f16* co = t.p;
+    e->prog[P_CTRL_IMPORT].push_back([=](hipStream_t s) { return nchw_f32_to_nhwc_f16(co, ld, ci, N, Cc, HW, 1.0f, s); });
   }
+}
 
-  // ---- VAE encode program, batch 1 (sdeo_enable_vae_encoder only): image intake -> Encoder (`model.py:452-545`) -> quant_conv ->
-  //      posterior tail (encode_first_stage + get_first_stage_encoding; AutoencoderKL itself is absent from the reference tree)
-  if (e->vae_encoder) {
-    b.prog = &e->p_vae_enc;
-    const std::string d = std::string(NS_VAE) + "encoder";
-    const int H = 8 * h, W = 8 * w, zc = c.vae_z_channels;
-    T img = b.alloc(1, H, W, round8(c.vae_out_ch));
-    {
-      f16* o = img.p; const float* in = e->enc_img; const uint8_t* in8 = e->enc_img_u8; const int Cc = c.vae_out_ch, HW = H * W;
-      const int* from_u8 = &e->enc_from_u8;
-      b.push([=](hipStream_t s) { return image_to_nhwc8_f16(o, *from_u8 ? nullptr : in, in8, 1, Cc, HW, s); }, "image_intake", 0,
-             (4.0 + 16.0) * HW);
-    }
-    Builder::CO gnx; gnx.gn_next = true;       // every conv of the encoder up to norm_out feeds a GroupNorm
-    T hcur = b.conv(img, d + ".conv_in", c.vae_ch, 3, 1, 0, gnx);
-    b.release(img);
-    int bi = c.vae_ch;
-    for (int l = 0; l < c.vae_num_levels; ++l) {
-      const int bo = c.vae_ch * c.vae_ch_mult[l];
-      for (int j = 0; j < c.vae_num_res_blocks; ++j) {
-        T y = build_vae_res(b, d + ".down." + std::to_string(l) + ".block." + std::to_string(j), hcur, bi, bo);
-        b.release(hcur);
-        hcur = y;
-        bi = bo;
-      }
-      if (l != c.vae_num_levels - 1) {        // Downsample: F.pad(x, (0,1,0,1)) + conv3x3 stride 2 pad 0 (`model.py:78-86`)
-        Builder::CO o = gnx; o.pad_before = 0; o.pad_after = 1;
-        T y = b.conv(hcur, d + ".down." + std::to_string(l) + ".downsample.conv", bi, 3, 2, 0, o);
-        b.release(hcur);
-        hcur = y;
-      }
-    }
-    if ((hcur.h != h || hcur.w != w) && b.err.empty())
-      b.err = "VAE encoder: " + std::to_string(H) + "x" + std::to_string(W) + " images encode to " + std::to_string(hcur.h) + "x" +
-              std::to_string(hcur.w) + ", not the configured latent " + std::to_string(h) + "x" + std::to_string(w);
-    T y = build_vae_res(b, d + ".mid.block_1", hcur, bi, bi);
-    b.release(hcur);
-    hcur = build_vae_attn(b, d + ".mid.attn_1", y);
-    y = build_vae_res(b, d + ".mid.block_2", hcur, bi, bi);
-    b.release(hcur);
-    hcur = y;
-    Builder::CO oo; oo.cout_store = round8(2 * zc);
-    T mo = b.gn_conv(hcur, d + ".norm_out", 1e-6f, 1, d + ".conv_out", 2 * zc, oo);
-    b.release(hcur);
-    Builder::CO qo; qo.cout_store = round8(2 * zc);
-    T q = b.conv(mo, std::string(NS_VAE) + "quant_conv", 2 * zc, 1, 1, 0, qo);
-    b.release(mo);
-    {
-      float* zp = e->enc_z; float* mp = e->enc_moments; const float* np_ = e->enc_noise; const int* with_noise = &e->enc_with_noise;
-      const f16* in = q.p; const int ld = q.ld, HW = h * w; const float sf = c.vae_scale_factor;
-      b.push([=](hipStream_t s) { return vae_posterior(zp, mp, in, ld, *with_noise ? np_ : nullptr, zc, HW, sf, s); }, "vae_posterior", 0,
-             (2.0 * 2 * zc + 4.0 * 4 * zc) * HW);
-    }
-    b.release(q);
+// The decoder (`openaimodel.py:797-801` with `cldm/cldm.py:33-41`): h = cat([h, hs.pop() + control.pop()]).  Three forms of the same
+// program: no control; controls given as tensors (the 13-tensor boundary: one add per control); controls applied as the ControlNet's
+// zero convs themselves, out = scale * zero_conv(cn_h) + skip written straight into the concat buffer (no add launches, no fp16
+// round trip of the control).
+enum DecoderMode { D_NOCTRL, D_ADD, D_FUSED };
+static void build_unet_decoder(BuildCtx& c, DecoderMode mode, std::vector<T> hs, T cat, T view) {
+  Builder& b = c.b; Engine* e = b.e;
+  const std::string ns = NS_UNET;
+  int ci = c.nctrl - 1;
+  if (mode == D_ADD) {   // h += control.pop()
+    f16* yp = view.p; const int ld = view.ld, rows = view.rows(), Cc = view.c;
+    const f16* cp = e->ctrl[ci].p; const int ldc = e->ctrl[ci].ld; const float* sc = &e->scales[ci];
+    b.push([=](hipStream_t s) { return add_scaled(yp, ld, yp, ld, cp, ldc, *sc, rows, Cc, s); });
+  } else if (mode == D_FUSED) {
+    Builder::CO zo; zo.out = &view; zo.res = &view; zo.scale_host = &e->eff_scales[ci];
+    b.conv(e->cn_h[ci], std::string(NS_CN) + "middle_block_out.0", view.c, 1, 1, 0, zo);
   }
-  *max_splitk = b.max_splitk;
-  *max_gn = b.max_gn;
-  *err = b.err;
+  --ci;
+  for (size_t oi = 0; oi < e->uplan.out.size(); ++oi) {
+    // second half of the concat buffer: hs.pop() (+ control.pop() unless only_mid_control)
+    T skip = hs.back();
+    hs.pop_back();
+    const int c_h = cat.c - skip.c;
+    if (mode == D_FUSED) {
+      const T half = cat.view(c_h, skip.c);
+      Builder::CO zo; zo.out = &half; zo.res = &skip; zo.scale_host = &e->eff_scales[ci];
+      b.conv(e->cn_h[ci], std::string(NS_CN) + "zero_convs." + std::to_string(ci) + ".0", skip.c, 1, 1, 0, zo);
+    } else {
+      f16* yp = cat.p + c_h; const int ld = cat.ld, rows = cat.rows(), Cc = skip.c;
+      const f16* ap = skip.p; const int lda = skip.ld;
+      const f16* cp = mode == D_ADD ? e->ctrl[ci].p : nullptr; const int ldc = mode == D_ADD ? e->ctrl[ci].ld : 0;
+      const float* sc = &e->scales[ci]; const int* om = &e->only_mid;
+      b.push([=](hipStream_t s) { return add_scaled(yp, ld, ap, lda, (*om) ? nullptr : cp, ldc, *sc, rows, Cc, s); });
+    }
+    --ci;
+    b.release(skip);
+    const std::vector<Blk>& blocks = e->uplan.out[oi];
+    if (oi + 1 < e->uplan.out.size()) {
+      const T& nskip = hs.back();
+      const int c_hn = blocks.back().cout;
+      const int up = blocks.back().kind == B_UP ? 2 : 1;
+      T ncat = b.alloc(cat.n, cat.h * up, cat.w * up, c_hn + nskip.c);
+      const T nview = ncat.view(0, c_hn);
+      run_blocks(c, ns, blocks, cat, true, 0, &nview);
+      cat = ncat;
+    } else {
+      T y = run_blocks(c, ns, blocks, cat, true, 0, nullptr);
+      Builder::CO oo; oo.cout_store = 4 * ((e->cfg.out_channels + 3) / 4);
+      oo.out = &e->eps16;
+      b.gn_conv(y, ns + "out.0", 1e-5f, 1, ns + "out.2", e->cfg.out_channels, oo);
+      b.release(y);
+    }
+  }
+}
+
+// UNet programs (`cldm/cldm.py:22-45`): encoder + middle block into P_UNET_ENC (and its shared-prefix variant) with the two decoders that
+// take controls, or everything into P_UNET_NOCTRL.  The middle block's output goes straight into the first concat buffer of the decoder
+// (cat0, of which view0 is the middle block's part).  The two decoders start from the same encoder state: the arena is rewound between them
+static void build_unet(BuildCtx& c, bool with_ctrl) {
+  Builder& b = c.b; Engine* e = b.e;
+  b.prog = &e->prog[with_ctrl ? P_UNET_ENC : P_UNET_NOCTRL];
+  const std::string ns = NS_UNET;
+  std::vector<T> hs;
+  T hcur = e->x0;
+  Splice sp;
+  for (size_t i = 0; i < e->uplan.in.size(); ++i) {
+    hcur = (i == 1 && with_ctrl) ? build_shared_prefix(c, ns, e->uplan.in[i], hcur, 0, sp) : run_blocks(c, ns, e->uplan.in[i], hcur, false, 0, nullptr);
+    hs.push_back(hcur);
+  }
+  const int c_mid = e->uplan.mid.back().cout;
+  const T cat0 = b.alloc(hcur.n, hcur.h, hcur.w, c_mid + hcur.c), view0 = cat0.view(0, c_mid);
+  run_blocks(c, ns, e->uplan.mid, hcur, false, 0, &view0);
+  if (!with_ctrl) return build_unet_decoder(c, D_NOCTRL, hs, cat0, view0);
+  splice(c, e->prog[P_UNET_ENC_SH], e->prog[P_UNET_ENC], sp);
+  Arena& arena = *b.lane->arena;
+  const Arena after_encoder = arena;          // everything below needs the controls: runs after the join
+  b.prog = &e->prog[P_UNET_DEC];
+  build_unet_decoder(c, D_ADD, hs, cat0, view0);
+  const size_t peak_add = arena.peak;
+  arena = after_encoder;
+  arena.peak = std::max(arena.peak, peak_add);
+  b.prog = &e->prog[P_UNET_DEC_FUSED];
+  build_unet_decoder(c, D_FUSED, hs, cat0, view0);
+}
+
+// VAE decode program, batch 1 (`model.py:619-652`; decode_first_stage wrapper: z/scale_factor -> post_quant_conv -> Decoder; the
+// wrapper itself is absent from the reference tree)
+static void build_vae_decoder(BuildCtx& c) {
+  Builder& b = c.b; Engine* e = b.e;
+  const sdeo_config& cfg = e->cfg;
+  b.prog = &e->prog[P_VAE];
+  const std::string d = std::string(NS_VAE) + "decoder";
+  T z = b.alloc(1, c.h, c.w, round8(cfg.vae_z_channels));
+  f16* zp = z.p; const float* zin = e->vae_in; const int zc = cfg.vae_z_channels, zld = z.ld, zHW = c.h * c.w;
+  const float sc = 1.0f / cfg.vae_scale_factor;
+  b.push([=](hipStream_t s) { return nchw_f32_to_nhwc_f16(zp, zld, zin, 1, zc, zHW, sc, s); });
+  Builder::CO pq; pq.cout_store = round8(cfg.vae_z_channels);
+  T hcur = z;
+  b.advance(hcur, b.conv(hcur, std::string(NS_VAE) + "post_quant_conv", cfg.vae_z_channels, 1, 1, 0, pq));
+  int bin = 0;
+  auto levels = vae_levels(cfg, &bin);
+  Builder::CO gnx; gnx.gn_next = true;       // every conv of the decoder below feeds a GroupNorm
+  b.advance(hcur, b.conv(hcur, d + ".conv_in", bin, 3, 1, 0, gnx));
+  b.advance(hcur, build_vae_res(b, d + ".mid.block_1", hcur, bin, bin));
+  hcur = build_vae_attn(b, d + ".mid.attn_1", hcur);
+  b.advance(hcur, build_vae_res(b, d + ".mid.block_2", hcur, bin, bin));
+  int last = bin;
+  for (auto& L : levels) {
+    const std::string up = d + ".up." + std::to_string(L.level);
+    for (size_t j = 0; j < L.blocks.size(); ++j) {
+      b.advance(hcur, build_vae_res(b, up + ".block." + std::to_string(j), hcur, L.blocks[j].first, L.blocks[j].second));
+      last = L.blocks[j].second;
+    }
+    if (L.up) b.advance(hcur, b.conv(hcur, up + ".upsample.conv", last, 3, 1, 1, gnx));
+  }
+  Builder::CO oo; oo.cout_store = 4 * ((cfg.vae_out_ch + 3) / 4);
+  b.advance(hcur, b.gn_conv(hcur, d + ".norm_out", 1e-6f, 1, d + ".conv_out", cfg.vae_out_ch, oo));
+  float* o = e->vae_out; uint8_t* u8 = e->vae_u8; const f16* in = hcur.p; const int ld = hcur.ld, Cc = cfg.vae_out_ch, HW = 64 * c.h * c.w;
+  b.push([=](hipStream_t s) {
+    if (int rc = nhwc_f16_to_nchw_f32(o, in, ld, 1, Cc, HW, 1.0f, s)) return rc;
+    return nhwc_f16_to_nhwc_u8(u8, in, ld, HW, Cc, s);
+  });
+  b.release(hcur);
+}
+
+// VAE encode program, batch 1 (sdeo_enable_vae_encoder only): image intake -> Encoder (`model.py:452-545`) -> quant_conv -> posterior
+// tail (encode_first_stage + get_first_stage_encoding; AutoencoderKL itself is absent from the reference tree)
+static void build_vae_encoder(BuildCtx& c) {
+  Builder& b = c.b; Engine* e = b.e;
+  const sdeo_config& cfg = e->cfg;
+  b.prog = &e->prog[P_VAE_ENC];
+  const std::string d = std::string(NS_VAE) + "encoder";
+  const int h = c.h, w = c.w, H = 8 * h, W = 8 * w, zc = cfg.vae_z_channels;
+  T hcur = b.alloc(1, H, W, round8(cfg.vae_out_ch));
+  f16* ip = hcur.p; const float* in = e->enc_img; const uint8_t* in8 = e->enc_img_u8; const int Cc = cfg.vae_out_ch, iHW = H * W;
+  const int* from_u8 = &e->enc_from_u8;
+  b.push([=](hipStream_t s) { return image_to_nhwc8_f16(ip, *from_u8 ? nullptr : in, in8, 1, Cc, iHW, s); }, "image_intake", 0,
+         (4.0 + 16.0) * iHW);
+  Builder::CO gnx; gnx.gn_next = true;       // every conv of the encoder up to norm_out feeds a GroupNorm
+  b.advance(hcur, b.conv(hcur, d + ".conv_in", cfg.vae_ch, 3, 1, 0, gnx));
+  int bi = cfg.vae_ch;
+  for (int l = 0; l < cfg.vae_num_levels; ++l) {
+    const std::string down = d + ".down." + std::to_string(l);
+    const int bo = cfg.vae_ch * cfg.vae_ch_mult[l];
+    for (int j = 0; j < cfg.vae_num_res_blocks; ++j) {
+      b.advance(hcur, build_vae_res(b, down + ".block." + std::to_string(j), hcur, bi, bo));
+      bi = bo;
+    }
+    if (l != cfg.vae_num_levels - 1) {        // Downsample: F.pad(x, (0,1,0,1)) + conv3x3 stride 2 pad 0 (`model.py:78-86`)
+      Builder::CO o = gnx; o.pad_before = 0; o.pad_after = 1;
+      b.advance(hcur, b.conv(hcur, down + ".downsample.conv", bi, 3, 2, 0, o));
+    }
+  }
+  if ((hcur.h != h || hcur.w != w) && b.err.empty())
+    b.err = "VAE encoder: " + std::to_string(H) + "x" + std::to_string(W) + " images encode to " + std::to_string(hcur.h) + "x" +
+            std::to_string(hcur.w) + ", not the configured latent " + std::to_string(h) + "x" + std::to_string(w);
+  b.advance(hcur, build_vae_res(b, d + ".mid.block_1", hcur, bi, bi));
+  hcur = build_vae_attn(b, d + ".mid.attn_1", hcur);
+  b.advance(hcur, build_vae_res(b, d + ".mid.block_2", hcur, bi, bi));
+  Builder::CO oo; oo.cout_store = round8(2 * zc);
+  b.advance(hcur, b.gn_conv(hcur, d + ".norm_out", 1e-6f, 1, d + ".conv_out", 2 * zc, oo));
+  b.advance(hcur, b.conv(hcur, std::string(NS_VAE) + "quant_conv", 2 * zc, 1, 1, 0, oo));
+  float* zp = e->enc_z; float* mp = e->enc_moments; const float* np_ = e->enc_noise; const int* with_noise = &e->enc_with_noise;
+  const f16* qp = hcur.p; const int ld = hcur.ld, HW = h * w; const float sf = cfg.vae_scale_factor;
+  b.push([=](hipStream_t s) { return vae_posterior(zp, mp, qp, ld, *with_noise ? np_ : nullptr, zc, HW, sf, s); }, "vae_posterior", 0,
+         (2.0 * 2 * zc + 4.0 * 4 * zc) * HW);
+  b.release(hcur);
+}
+
+// One pass over every program of the handle, on fresh arenas and in a fixed order: the arena plan is a function of the order of alloc /
+// release.  Out: the workspaces the launches need and what each lane's arena has to hold
+static int build_all(Engine* e, bool dry, size_t* max_splitk, size_t* max_gn, size_t peaks[L_COUNT]) {
+  Arena arenas[L_COUNT];
+  for (int i = 0; i < L_COUNT; ++i) e->lanes[i].arena = &arenas[i];
+  BuildCtx c{Builder{e, &e->lanes[L_MAIN], dry}, e->N, e->lh, e->lw, round8(e->cfg.context_len), (int)e->cplan.in.size() + 1};
+  build_persistent(c);
+  // small programs (their temporaries come and go: only after every persistent tensor has its place)
+  build_latent_io(c);
+  build_time_embeds(c);
+  for (int net = 0; net < 2; ++net) build_context(c, net);
+  build_hint(c);
+  c.b.on_lane(&e->lanes[L_SIDE], [&] { build_controlnet(c); });
+  build_control_io(c);
+  for (int variant = 0; variant < 2; ++variant) build_unet(c, variant == 0);
+  build_vae_decoder(c);
+  if (e->vae_encoder) build_vae_encoder(c);
+  for (int i = 0; i < L_COUNT; ++i) {
+    e->lanes[i].arena = nullptr;
+    peaks[i] = align_up(arenas[i].peak, 256);
+  }
+  *max_splitk = c.b.max_splitk; *max_gn = c.b.max_gn;
+  SDEO_CHECK(c.b.err.empty(), "sdeo_configure: %s", c.b.err.c_str());
+  return 0;
 }
 
 template <typename Tp>
@@ -1404,18 +1202,29 @@ static int dev_alloc(Engine* e, Tp** p, size_t bytes) {
   return 0;
 }
 
+static bool configured(const Engine* e) { return e->lanes[L_MAIN].base != nullptr; }
+
 static void free_configured(Engine* e) {
-  for (void* v : e->extra_allocs) (void)hipFree(v);
+  for (void* v : e->extra_allocs) (void)hipFree(v);      // (the lanes' workspaces among them)
   e->extra_allocs.clear();
-  if (e->arena) (void)hipFree(e->arena);
-  e->arena = nullptr;
-  if (e->arena2) (void)hipFree(e->arena2);
-  e->arena2 = nullptr;
-  for (Program* p : {&e->p_hint, &e->p_ctx_cn, &e->p_ctx_unet, &e->p_cn, &e->p_cn_export, &e->p_ctrl_import, &e->p_unet_enc,
-                     &e->p_unet_dec, &e->p_unet_noctrl, &e->p_vae, &e->p_vae_enc, &e->p_temb[0], &e->p_temb[1], &e->p_temb_tab, &e->p_x0, &e->p_eps_export, &e->p_unet_dec_fused,
-                     &e->p_unet_enc_sh, &e->p_cn_sh})
-    p->clear();
-  e->tab_count = 0;
+  for (Lane& l : e->lanes) {
+    if (l.base) (void)hipFree(l.base);
+    l = Lane();
+  }
+  for (Program& p : e->prog) p.clear();
+  e->tab_count = e->fp8.mx_launches = 0;
+  e->device_bytes = e->ws.slab_bytes + e->fp8.q8_bytes + e->fp8.mx_bytes;      // what stays: the weights and their fp8 packs
+}
+
+// control scales of the next forward (null: all 1) and what P_UNET_DEC_FUSED applies of them: with only_mid_control
+// (`cldm/cldm.py:35-41`) the twelve skip controls are dropped, the middle one stays
+static void set_scales(Engine* h, const float* host_scales, int only_mid) {
+  const int mid = (int)h->cplan.in.size();
+  h->only_mid = only_mid;
+  for (int i = 0; i < kMaxControls; ++i) {
+    h->scales[i] = host_scales ? host_scales[i] : 1.0f;
+    h->eff_scales[i] = (only_mid && i != mid) ? 0.0f : h->scales[i];
+  }
 }
 
 }  // namespace
@@ -1438,14 +1247,14 @@ int sdeo_create(const sdeo_config* cfg, sdeo_handle* out) {
   e->cfg = *cfg;
   e->uplan = make_uplan(*cfg, true);
   e->cplan = make_uplan(*cfg, false);
-  SDEO_CHECK(e->cplan.in.size() + 1 <= 13, "sdeo_create: more than 13 control tensors");
+  SDEO_CHECK(e->cplan.in.size() + 1 <= kMaxControls, "sdeo_create: more than %d control tensors", kMaxControls);
   e->hconvs = hint_convs(*cfg);
   if (const char* at = getenv("SDEO_AUTOTUNE")) e->autotune = atoi(at) != 0;
   if (const char* ov = getenv("SDEO_OVERLAP")) e->overlap = atoi(ov) != 0;
   SDEO_HIP(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
   SDEO_HIP(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
   SDEO_HIP(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-  for (int i = 0; i < 13; ++i) e->scales[i] = 1.0f;
+  set_scales(e.get(), nullptr, 0);
   build_registry(e.get());
   if (int rc = e->ws.alloc("sdeo_create", /*zero_fill=*/true)) return rc;
   e->device_bytes = e->ws.slab_bytes;
@@ -1460,8 +1269,8 @@ int sdeo_destroy(sdeo_handle h) {
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
   h->ws.destroy();
-  if (h->q8slab) (void)hipFree(h->q8slab);
-  if (h->mxslab) (void)hipFree(h->mxslab);
+  if (h->fp8.q8slab) (void)hipFree(h->fp8.q8slab);
+  if (h->fp8.mxslab) (void)hipFree(h->fp8.mxslab);
   delete h;
   return 0;
 }
@@ -1471,7 +1280,7 @@ int sdeo_enable_vae_encoder(sdeo_handle h) {
   if (h->vae_encoder) return 0;
   for (const auto& w : h->ws.entries)
     SDEO_CHECK(!w.loaded, "sdeo_enable_vae_encoder: call it before the first sdeo_load_weight (%s is loaded)", w.name.c_str());
-  SDEO_CHECK(!h->finalized && !h->arena, "sdeo_enable_vae_encoder: call it before sdeo_finalize_weights / sdeo_configure");
+  SDEO_CHECK(!h->finalized && !configured(h), "sdeo_enable_vae_encoder: call it before sdeo_finalize_weights / sdeo_configure");
   SDEO_CHECK(h->cfg.vae_num_levels == 4, "sdeo_enable_vae_encoder: %d VAE levels downsample by %d, the 8h x 8w image boundary needs 8",
              h->cfg.vae_num_levels, 1 << (h->cfg.vae_num_levels - 1));
   SDEO_CHECK(h->cfg.vae_out_ch <= 8, "sdeo_enable_vae_encoder: %d image channels (at most 8)", h->cfg.vae_out_ch);
@@ -1507,20 +1316,20 @@ int sdeo_finalize_weights(sdeo_handle h) {
                                 vec(f.gamma), vec(f.beta), vec(f.bias), f.rows, f.C, 0))
       return rc;
   }
-  if (h->weight_bits == 8) {
+  if (h->fp8.weight_bits == 8) {
     // fp8 pack: codes + per-row scales in a slab of their own; the fp16 copies become the dequantised values
-    if (!h->q8slab) {
+    if (!h->fp8.q8slab) {
       size_t sz = 0;
-      for (QRegion& q : h->qregions) {
+      for (QRegion& q : h->fp8.qregions) {
         q.q_off = align_up(sz, 256); sz = q.q_off + (size_t)q.rows * q.cols;
         q.s_off = align_up(sz, 256); sz = q.s_off + (size_t)q.rows * 4;
       }
-      h->q8_bytes = align_up(sz, 256);
-      SDEO_HIP(hipMalloc((void**)&h->q8slab, h->q8_bytes));
-      h->device_bytes += h->q8_bytes;
+      h->fp8.q8_bytes = align_up(sz, 256);
+      SDEO_HIP(hipMalloc((void**)&h->fp8.q8slab, h->fp8.q8_bytes));
+      h->device_bytes += h->fp8.q8_bytes;
     }
-    for (const QRegion& q : h->qregions)
-      if (int rc = quantize_fp8_rows(reinterpret_cast<uint8_t*>(h->q8slab + q.q_off), reinterpret_cast<float*>(h->q8slab + q.s_off),
+    for (const QRegion& q : h->fp8.qregions)
+      if (int rc = quantize_fp8_rows(reinterpret_cast<uint8_t*>(h->fp8.q8slab + q.q_off), reinterpret_cast<float*>(h->fp8.q8slab + q.s_off),
                                      reinterpret_cast<f16*>(h->ws.slab + q.off), q.rows, q.cols, q.cols, q.cols, 0))
         return rc;
     for (const FoldJob& f : h->folds)          // the row sums of the LayerNorm fold must be those of the re-quantised matrix
@@ -1533,25 +1342,25 @@ int sdeo_finalize_weights(sdeo_handle h) {
                               h->ws.ptr<f16>(cj.wp), h->ws.ptr<float>(cj.bp), h->ws.ptr<f16>(cj.w2), h->ws.ptr<float>(cj.b2), cj.C, 4 * cj.C, 0))
       return rc;
   }
-  if (h->act_bits == 8) {
+  if (h->fp8.act_bits == 8) {
     // block-scaled packs of every Linear / conv1x1 matrix whose K is a multiple of 128 (from the values the fp16 copies hold now,
     // i.e. after the per-row fp8 rounding when weight_bits == 8)
-    if (!h->mxslab) {
+    if (!h->fp8.mxslab) {
       size_t sz = 0;
-      for (const QRegion& q : h->qregions) {
+      for (const QRegion& q : h->fp8.qregions) {
         if (q.cols % 128) continue;
-        sdeo_handle_s::MxRegion m{};
+        Fp8State::MxRegion m{};
         m.rows = q.rows; m.cols = q.cols;
         m.q_off = align_up(sz, 256); sz = m.q_off + (size_t)q.rows * q.cols;
         m.s_off = align_up(sz, 256); sz = m.s_off + (size_t)q.rows * (q.cols / 32);
-        h->mxindex[q.off] = m;
+        h->fp8.mxindex[q.off] = m;
       }
-      h->mx_bytes = align_up(sz, 256);
-      SDEO_HIP(hipMalloc((void**)&h->mxslab, h->mx_bytes < 256 ? 256 : h->mx_bytes));
-      h->device_bytes += h->mx_bytes;
+      h->fp8.mx_bytes = align_up(sz, 256);
+      SDEO_HIP(hipMalloc((void**)&h->fp8.mxslab, h->fp8.mx_bytes < 256 ? 256 : h->fp8.mx_bytes));
+      h->device_bytes += h->fp8.mx_bytes;
     }
-    for (auto& kv : h->mxindex)
-      if (int rc = quantize_mx(reinterpret_cast<uint8_t*>(h->mxslab + kv.second.q_off), reinterpret_cast<uint8_t*>(h->mxslab + kv.second.s_off),
+    for (auto& kv : h->fp8.mxindex)
+      if (int rc = quantize_mx(reinterpret_cast<uint8_t*>(h->fp8.mxslab + kv.second.q_off), reinterpret_cast<uint8_t*>(h->fp8.mxslab + kv.second.s_off),
                                reinterpret_cast<const f16*>(h->ws.slab + kv.first), kv.second.rows, kv.second.cols, kv.second.cols, kv.second.cols,
                                kv.second.cols / 32, 0))
         return rc;
@@ -1564,31 +1373,23 @@ int sdeo_finalize_weights(sdeo_handle h) {
 int sdeo_set_activation_precision(sdeo_handle h, int bits, int min_rows) {
   SDEO_CHECK(h, "sdeo_set_activation_precision: null handle");
   SDEO_CHECK(bits == 16 || bits == 8, "sdeo_set_activation_precision: %d bits unsupported (16 or 8)", bits);
-  SDEO_CHECK(!h->finalized && !h->arena, "sdeo_set_activation_precision: call it before sdeo_finalize_weights / sdeo_configure");
-  h->act_bits = bits;
-  h->mx_min_rows = min_rows > 0 ? min_rows : 2048;
+  SDEO_CHECK(!h->finalized && !configured(h), "sdeo_set_activation_precision: call it before sdeo_finalize_weights / sdeo_configure");
+  h->fp8.act_bits = bits;
+  h->fp8.mx_min_rows = min_rows > 0 ? min_rows : 2048;
   return 0;
 }
-int sdeo_debug_mx_launches(sdeo_handle h) { return h ? h->mx_launches : -1; }
+int sdeo_debug_mx_launches(sdeo_handle h) { return h ? h->fp8.mx_launches : -1; }
 
 int sdeo_set_weight_precision(sdeo_handle h, int bits) {
   SDEO_CHECK(h, "sdeo_set_weight_precision: null handle");
   SDEO_CHECK(bits == 16 || bits == 8, "sdeo_set_weight_precision: %d bits unsupported (16 or 8)", bits);
-  SDEO_CHECK(!h->finalized && !h->arena, "sdeo_set_weight_precision: call it before sdeo_finalize_weights / sdeo_configure");
-  h->weight_bits = bits;
+  SDEO_CHECK(!h->finalized && !configured(h), "sdeo_set_weight_precision: call it before sdeo_finalize_weights / sdeo_configure");
+  h->fp8.weight_bits = bits;
   return 0;
 }
 
-int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w) {
-  SDEO_CHECK(h, "sdeo_configure: null handle");
-  SDEO_CHECK(n >= 1 && n <= 64, "sdeo_configure: n=%d out of range", n);
-  const int maxds = 1 << (h->cfg.num_levels - 1);
-  SDEO_CHECK(latent_h >= maxds && latent_w >= maxds && latent_h % maxds == 0 && latent_w % maxds == 0,
-             "sdeo_configure: latent %dx%d must be a positive multiple of %d", latent_h, latent_w, maxds);
-  SDEO_CHECK(h->weight_bits != 8 || h->q8slab, "sdeo_configure: fp8 weights are packed by sdeo_finalize_weights: call it first");
+static int configure_impl(sdeo_handle h, int n, int latent_h, int latent_w) {
   free_configured(h);
-  h->device_bytes = h->ws.slab_bytes + h->q8_bytes + h->mx_bytes;
-  h->mx_launches = 0;
   h->N = n; h->lh = latent_h; h->lw = latent_w;
   const sdeo_config& c = h->cfg;
   const size_t px = (size_t)latent_h * latent_w;
@@ -1622,36 +1423,36 @@ int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w) {
     if (int rc = dev_alloc(h, &h->in_ctrl[i], elems * 4)) return rc;
     if (int rc = dev_alloc(h, &h->out_ctrl[i], elems * 4)) return rc;
   }
-  // pass 1: plan the arena (no launches recorded), pass 2: build for real
-  size_t ms = 0, mg = 0;
-  std::string err;
-  {
-    Arena a, a2;
-    build_all(h, a, a2, true, &ms, &mg, &err);
-    SDEO_CHECK(err.empty(), "sdeo_configure: %s", err.c_str());
-    h->arena_bytes = align_up(a.peak, 256);
-    h->arena2_bytes = align_up(a2.peak, 256);
+  // pass 1: plan the arenas (no launches recorded), pass 2: build for real
+  size_t ms = 0, mg = 0, peaks[L_COUNT];
+  if (int rc = build_all(h, true, &ms, &mg, peaks)) return rc;
+  for (int i = 0; i < L_COUNT; ++i) {
+    Lane& l = h->lanes[i];
+    l.bytes = peaks[i];
+    SDEO_HIP(hipMalloc((void**)&l.base, l.bytes));
+    SDEO_HIP(hipMemset(l.base, 0, l.bytes));
+    h->device_bytes += l.bytes;
+    if (int rc = dev_alloc(h, &l.splitk_ws, l.splitk_ws_bytes = ms)) return rc;
+    if (int rc = dev_alloc(h, &l.gn_ws, mg)) return rc;
   }
-  SDEO_HIP(hipMalloc((void**)&h->arena, h->arena_bytes));
-  SDEO_HIP(hipMemset(h->arena, 0, h->arena_bytes));
-  SDEO_HIP(hipMalloc((void**)&h->arena2, h->arena2_bytes));
-  SDEO_HIP(hipMemset(h->arena2, 0, h->arena2_bytes));
-  h->device_bytes += h->arena_bytes + h->arena2_bytes;
-  if (int rc = dev_alloc(h, &h->splitk_ws, ms)) return rc;
-  if (int rc = dev_alloc(h, &h->splitk_ws2, ms)) return rc;
-  h->splitk_ws_bytes = ms;
-  if (int rc = dev_alloc(h, &h->gn_ws, mg)) return rc;
-  if (int rc = dev_alloc(h, &h->gn_ws2, mg)) return rc;
-  h->gn_ws_bytes = mg;
-  {
-    Arena a, a2;
-    build_all(h, a, a2, false, &ms, &mg, &err);
-    SDEO_CHECK(err.empty(), "sdeo_configure: %s", err.c_str());
-    SDEO_CHECK(align_up(a.peak, 256) == h->arena_bytes && align_up(a2.peak, 256) == h->arena2_bytes,
-               "sdeo_configure: arena plan not reproducible");
-  }
+  if (int rc = build_all(h, false, &ms, &mg, peaks)) return rc;
+  SDEO_CHECK(peaks[L_MAIN] == h->lanes[L_MAIN].bytes && peaks[L_SIDE] == h->lanes[L_SIDE].bytes, "sdeo_configure: arena plan not reproducible");
   SDEO_HIP(hipDeviceSynchronize());      // autotune launches are done before the first real forward
   return 0;
+}
+
+// A configure that fails part-way leaves the handle unconfigured (never half-built programs); one whose arguments are rejected leaves
+// the previous configuration in place
+int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w) {
+  SDEO_CHECK(h, "sdeo_configure: null handle");
+  SDEO_CHECK(n >= 1 && n <= 64, "sdeo_configure: n=%d out of range", n);
+  const int maxds = 1 << (h->cfg.num_levels - 1);
+  SDEO_CHECK(latent_h >= maxds && latent_w >= maxds && latent_h % maxds == 0 && latent_w % maxds == 0,
+             "sdeo_configure: latent %dx%d must be a positive multiple of %d", latent_h, latent_w, maxds);
+  SDEO_CHECK(h->fp8.weight_bits != 8 || h->fp8.q8slab, "sdeo_configure: fp8 weights are packed by sdeo_finalize_weights: call it first");
+  const int rc = configure_impl(h, n, latent_h, latent_w);
+  if (rc) free_configured(h);
+  return rc;
 }
 
 static int copy_in(void* dst, const void* src, size_t bytes, hipStream_t s) {
@@ -1668,12 +1469,12 @@ static int stage_inputs(sdeo_handle h, const float* x, const float* hint, const 
   if (t) if (int rc = copy_in(h->in_t, t, (size_t)h->N * 8, s)) return rc;
   if (hint && hint_is_new) {
     if (int rc = copy_in(h->in_hint, hint, (size_t)h->N * c.hint_channels * px * 64 * 4, s)) return rc;
-    if (int rc = run(h, h->p_hint, s)) return rc;
+    if (int rc = run(h, h->prog[P_HINT], s)) return rc;
   }
   if (ctx) {
     if (int rc = copy_in(h->in_ctx, ctx, (size_t)h->N * c.context_len * c.context_dim * 4, s)) return rc;
-    if (ctx_for_net & 1) if (int rc = run(h, h->p_ctx_unet, s)) return rc;
-    if (ctx_for_net & 2) if (int rc = run(h, h->p_ctx_cn, s)) return rc;
+    if (ctx_for_net & 1) if (int rc = run(h, h->prog[P_CTX_UNET], s)) return rc;
+    if (ctx_for_net & 2) if (int rc = run(h, h->prog[P_CTX_CN], s)) return rc;
   }
   return 0;
 }
@@ -1681,9 +1482,9 @@ static int stage_inputs(sdeo_handle h, const float* x, const float* hint, const 
 #define REQUIRE_READY(h)                                                                     \
   SDEO_CHECK(h, "null handle");                                                              \
   SDEO_CHECK(h->finalized, "weights not finalized (call sdeo_finalize_weights)");            \
-  SDEO_CHECK(h->arena, "not configured (call sdeo_configure)")
+  SDEO_CHECK(configured(h), "not configured (call sdeo_configure)")
 
-// time embedding of this forward: row `row` of the schedule table (>= 0; every image of the batch at that timestep), or in_t via p_temb
+// time embedding of this forward: row `row` of the schedule table (>= 0; every image of the batch at that timestep), or in_t via P_TEMB + net
 static int select_time(sdeo_handle h, int flags, const int64_t* timesteps, const char* who, int* row_out) {
   const int row = (flags & 8) ? (flags >> 8) : -1;
   SDEO_CHECK(row >= 0 || timesteps, "%s: timesteps required", who);
@@ -1696,42 +1497,36 @@ static int select_time(sdeo_handle h, int flags, const int64_t* timesteps, const
   return 0;
 }
 
-// only_mid_control (`cldm/cldm.py:35-41`): the twelve skip controls are dropped, the middle one stays
-static void set_effective_scales(sdeo_handle h) {
-  const int mid = (int)h->cplan.in.size();
-  for (int i = 0; i < 13; ++i) h->eff_scales[i] = (h->only_mid && i != mid) ? 0.0f : h->scales[i];
-}
-
 // ControlNet || UNet encoder, join, UNet decoder: eps16 holds the result.  The latent is already in x0.
 // shared_unet / shared_cn: the two halves of the batch are the same images at the same timestep (and, for the ControlNet, under the same
 // hint): run the programs whose shared prefix is computed once, where configure built them
 static int run_step_programs(sdeo_handle h, bool no_control, bool time_from_table, hipStream_t s, bool shared_unet = false,
                              bool shared_cn = false) {
-  const Program& p_unet_enc = shared_unet && !h->p_unet_enc_sh.empty() ? h->p_unet_enc_sh : h->p_unet_enc;
-  const Program& p_cn = shared_cn && !h->p_cn_sh.empty() ? h->p_cn_sh : h->p_cn;
+  const Program& p_unet_enc = shared_unet && !h->prog[P_UNET_ENC_SH].empty() ? h->prog[P_UNET_ENC_SH] : h->prog[P_UNET_ENC];
+  const Program& p_cn = shared_cn && !h->prog[P_CN_SH].empty() ? h->prog[P_CN_SH] : h->prog[P_CN];
   if (no_control) {
-    if (!time_from_table) if (int rc = run(h, h->p_temb[0], s)) return rc;
-    return run(h, h->p_unet_noctrl, s);
+    if (!time_from_table) if (int rc = run(h, h->prog[P_TEMB + 0], s)) return rc;
+    return run(h, h->prog[P_UNET_NOCTRL], s);
   }
   if (h->overlap && !h->prof.on) {
     // fork: ControlNet on the side stream, UNet encoder + middle block on the caller's stream (capturable)
     SDEO_HIP(hipEventRecord(h->ev_fork, s));
     SDEO_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-    if (!time_from_table) if (int rc = run(h, h->p_temb[1], h->side)) return rc;
+    if (!time_from_table) if (int rc = run(h, h->prog[P_TEMB + 1], h->side)) return rc;
     if (int rc = run(h, p_cn, h->side, true)) return rc;
     SDEO_HIP(hipEventRecord(h->ev_join, h->side));
-    if (!time_from_table) if (int rc = run(h, h->p_temb[0], s)) return rc;
+    if (!time_from_table) if (int rc = run(h, h->prog[P_TEMB + 0], s)) return rc;
     if (int rc = run(h, p_unet_enc, s)) return rc;
     SDEO_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
   } else {
     if (!time_from_table) {
-      if (int rc = run(h, h->p_temb[1], s)) return rc;
-      if (int rc = run(h, h->p_temb[0], s)) return rc;
+      if (int rc = run(h, h->prog[P_TEMB + 1], s)) return rc;
+      if (int rc = run(h, h->prog[P_TEMB + 0], s)) return rc;
     }
     if (int rc = run(h, p_cn, s, true)) return rc;
     if (int rc = run(h, p_unet_enc, s)) return rc;
   }
-  return run(h, h->p_unet_dec_fused, s);      // applies the zero convs itself (skipped above)
+  return run(h, h->prog[P_UNET_DEC_FUSED], s);      // applies the zero convs itself (skipped above)
 }
 
 int sdeo_controlnet_forward(sdeo_handle h, const float* x_noisy, const float* hint, const int64_t* timesteps,
@@ -1745,10 +1540,10 @@ int sdeo_controlnet_forward(sdeo_handle h, const float* x_noisy, const float* hi
   int trow = -1;
   if (int rc = select_time(h, flags, timesteps, "sdeo_controlnet_forward", &trow)) return rc;
   if (int rc = stage_inputs(h, x_noisy, hint, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, hint_new, 2, s)) return rc;
-  if (int rc = run(h, h->p_x0, s)) return rc;
-  if (trow < 0) if (int rc = run(h, h->p_temb[1], s)) return rc;
-  if (int rc = run(h, h->p_cn, s)) return rc;
-  if (int rc = run(h, h->p_cn_export, s)) return rc;
+  if (int rc = run(h, h->prog[P_X0], s)) return rc;
+  if (trow < 0) if (int rc = run(h, h->prog[P_TEMB + 1], s)) return rc;
+  if (int rc = run(h, h->prog[P_CN], s)) return rc;
+  if (int rc = run(h, h->prog[P_CN_EXPORT], s)) return rc;
   for (size_t i = 0; i < h->ctrl_elems.size(); ++i)
     if (controls[i]) if (int rc = copy_in(controls[i], h->out_ctrl[i], h->ctrl_elems[i] * 4, s)) return rc;
   return 0;
@@ -1765,22 +1560,21 @@ int sdeo_unet_forward(sdeo_handle h, const float* x_noisy, const int64_t* timest
   int trow = -1;
   if (int rc = select_time(h, flags, timesteps, "sdeo_unet_forward", &trow)) return rc;
   if (int rc = stage_inputs(h, x_noisy, nullptr, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, 0, 1, s)) return rc;
-  h->only_mid = only_mid_control;
-  for (int i = 0; i < 13; ++i) h->scales[i] = host_control_scales ? host_control_scales[i] : 1.0f;
-  if (int rc = run(h, h->p_x0, s)) return rc;
-  if (trow < 0) if (int rc = run(h, h->p_temb[0], s)) return rc;
+  set_scales(h, host_control_scales, only_mid_control);
+  if (int rc = run(h, h->prog[P_X0], s)) return rc;
+  if (trow < 0) if (int rc = run(h, h->prog[P_TEMB + 0], s)) return rc;
   if (controls) {
     for (size_t i = 0; i < h->ctrl_elems.size(); ++i) {
       SDEO_CHECK(controls[i], "sdeo_unet_forward: control %zu is null", i);
       if (int rc = copy_in(h->in_ctrl[i], controls[i], h->ctrl_elems[i] * 4, s)) return rc;
     }
-    if (int rc = run(h, h->p_ctrl_import, s)) return rc;
-    if (int rc = run(h, h->p_unet_enc, s)) return rc;
-    if (int rc = run(h, h->p_unet_dec, s)) return rc;
+    if (int rc = run(h, h->prog[P_CTRL_IMPORT], s)) return rc;
+    if (int rc = run(h, h->prog[P_UNET_ENC], s)) return rc;
+    if (int rc = run(h, h->prog[P_UNET_DEC], s)) return rc;
   } else {
-    if (int rc = run(h, h->p_unet_noctrl, s)) return rc;
+    if (int rc = run(h, h->prog[P_UNET_NOCTRL], s)) return rc;
   }
-  if (int rc = run(h, h->p_eps_export, s)) return rc;
+  if (int rc = run(h, h->prog[P_EPS_EXPORT], s)) return rc;
   return copy_in(eps, h->out_eps, (size_t)h->N * h->cfg.out_channels * h->lh * h->lw * 4, s);
 }
 
@@ -1797,12 +1591,10 @@ int sdeo_apply_model(sdeo_handle h, const float* x_noisy, const float* hint, con
   if (int rc = stage_inputs(h, x_noisy, no_control ? nullptr : hint, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, hint_new,
                             no_control ? 1 : 3, s))
     return rc;
-  h->only_mid = only_mid_control;
-  for (int i = 0; i < 13; ++i) h->scales[i] = host_control_scales ? host_control_scales[i] : 1.0f;
-  set_effective_scales(h);
-  if (int rc = run(h, h->p_x0, s)) return rc;
+  set_scales(h, host_control_scales, only_mid_control);
+  if (int rc = run(h, h->prog[P_X0], s)) return rc;
   if (int rc = run_step_programs(h, no_control, trow >= 0, s)) return rc;
-  if (int rc = run(h, h->p_eps_export, s)) return rc;
+  if (int rc = run(h, h->prog[P_EPS_EXPORT], s)) return rc;
   return copy_in(eps, h->out_eps, (size_t)h->N * h->cfg.out_channels * h->lh * h->lw * 4, s);
 }
 
@@ -1816,7 +1608,7 @@ int sdeo_set_timestep_table(sdeo_handle h, const int64_t* host_timesteps, int co
   h->tab_count = 0;
   SDEO_HIP(hipMemcpyAsync(h->tab_t, padded, sizeof(padded), hipMemcpyHostToDevice, s));
   SDEO_HIP(hipStreamSynchronize(s));          // `padded` is a stack array; this call is made once per schedule, outside any capture
-  if (int rc = run(h, h->p_temb_tab, s)) return rc;
+  if (int rc = run(h, h->prog[P_TEMB_TAB], s)) return rc;
   h->tab_count = count;
   return 0;
 }
@@ -1834,9 +1626,7 @@ int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float
   const int b = h->N / 2, HW = h->lh * h->lw;
   int trow = -1;
   if (int rc = select_time(h, 8 | (table_row << 8), nullptr, "sdeo_ddim_step", &trow)) return rc;
-  h->only_mid = only_mid_control;
-  for (int i = 0; i < 13; ++i) h->scales[i] = host_control_scales ? host_control_scales[i] : 1.0f;
-  set_effective_scales(h);
+  set_scales(h, host_control_scales, only_mid_control);
   if (!(flags & 16))
     if (int rc = latent_pair_to_nhwc(h->x0.p, h->x0.ld, x, b, c.in_channels, HW, s)) return rc;
   // x0 = [x; x] at one timestep: the UNet's shared prefix always holds, the ControlNet's when the caller vouches for the hints
@@ -1853,7 +1643,7 @@ int sdeo_vae_decode(sdeo_handle h, const float* z, int n, float* images, uint8_t
   const size_t px = (size_t)h->lh * h->lw;
   for (int i = 0; i < n; ++i) {
     if (int rc = copy_in(h->vae_in, z + (size_t)i * c.vae_z_channels * px, (size_t)c.vae_z_channels * px * 4, s)) return rc;
-    if (int rc = run(h, h->p_vae, s)) return rc;
+    if (int rc = run(h, h->prog[P_VAE], s)) return rc;
     if (images)
       if (int rc = copy_in(images + (size_t)i * c.vae_out_ch * px * 64, h->vae_out, (size_t)c.vae_out_ch * px * 64 * 4, s)) return rc;
     if (images_u8)
@@ -1881,7 +1671,7 @@ int sdeo_vae_encode(sdeo_handle h, const float* images, const uint8_t* images_u8
       if (int rc = copy_in(h->enc_img_u8, images_u8 + (size_t)i * c.vae_out_ch * ipx, (size_t)c.vae_out_ch * ipx, s)) return rc;
     }
     if (noise) if (int rc = copy_in(h->enc_noise, noise + (size_t)i * zc * px, zc * px * 4, s)) return rc;
-    if (int rc = run(h, h->p_vae_enc, s)) return rc;
+    if (int rc = run(h, h->prog[P_VAE_ENC], s)) return rc;
     if (int rc = copy_in(z + (size_t)i * zc * px, h->enc_z, zc * px * 4, s)) return rc;
     if (moments) if (int rc = copy_in(moments + (size_t)i * 2 * zc * px, h->enc_moments, 2 * zc * px * 4, s)) return rc;
   }
