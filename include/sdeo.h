@@ -68,7 +68,8 @@ int sdeo_groupnorm_nhwc_f16(void* y, const void* x, const float* gamma, const fl
  *   y[n][ho][wo][cout] = act( conv(x, w) + bias[cout] + bias2[n][cout] ) * scale + res[n][ho][wo][cout]
  * cin/cout are the STORED channel counts (cin % 8 == 0, cout % 4 == 0); upsample2x=1 folds a nearest x2
  * upsample of x in front of the conv.  bias/bias2 fp32 or NULL, res fp16 NHWC or NULL. act: 0 none, 1 SiLU,
- * 4 ReLU (plans exactly like act 0).  sdeo_conv2d_pad_nhwc_f16 and sdeo_gemm_f16 take the same codes (sdeo_gemm_f16 also 2 = quick-GELU).
+ * 4 ReLU (plans exactly like act 0).  sdeo_conv2d_pad_nhwc_f16 and sdeo_gemm_f16 take the same codes (sdeo_gemm_f16 also 2 = quick-GELU
+ * and 5 = erf GELU, F.gelu's default, planned like act 0).
  * workspace (split-K partials): >= sdeo_conv2d_workspace_bytes(...) bytes, may be NULL when that is 0. */
 size_t sdeo_conv2d_workspace_bytes(int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x);
 int sdeo_conv2d_nhwc_f16(void* y, const void* x, const void* w_krsc, const float* bias, const float* bias2, const void* res,
@@ -122,6 +123,13 @@ int sdeo_timestep_embedding_f16(void* out, const int64_t* t, int b, int dim, voi
 int sdeo_cfg_ddim_step(float* x_prev, float* pred_x0, const float* x, const float* eps_c, const float* eps_u,
                        const float* noise, float cfg_scale, float a_t, float a_prev, float sigma_t,
                        float sqrt_one_minus_at, int64_t n, void* stream);
+/* The same step for a v-prediction model (SD-2.x 768-v; ddim_hacked.py:194-197,214-217 with upstream LatentDiffusion's
+ * predict_eps_from_z_and_v / predict_start_from_z_and_v): the operands in the places of eps_c / eps_u are the model's v outputs.
+ *   v = v_u + cfg_scale (v_c - v_u);  e = sqrt(a_t) v + sqrt(1 - a_t) x;  pred_x0 = sqrt(a_t) x - sqrt(1 - a_t) v;
+ *   x_prev = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev - sigma_t^2) e + sigma_t noise */
+int sdeo_cfg_ddim_step_v(float* x_prev, float* pred_x0, const float* x, const float* v_c, const float* v_u,
+                         const float* noise, float cfg_scale, float a_t, float a_prev, float sigma_t,
+                         float sqrt_one_minus_at, int64_t n, void* stream);
 
 /* Canny edge map: replaces `cv2.Canny(img, low_threshold, high_threshold)` of annotator/canny/__init__.py:4-6
  * (aperture 3, L1 gradient magnitude; called at canny2image_torch.py:33 on the HWC3 uint8 image) and the control preparation of
@@ -170,6 +178,16 @@ typedef struct sdeo_config {
 
 /* Create / destroy an engine instance on the current HIP device. */
 int sdeo_create(const sdeo_config* cfg, sdeo_handle* out);
+/* The layout switches of the SD-2.x family (cldm_v21.yaml; cldm/cldm.py:64,77,184-207, ldm/modules/attention.py:409-449), kept out of
+ * sdeo_config so that its layout does not change.  sdeo_create(cfg, out) is sdeo_create_ex(cfg, NULL, out).  Checked before any
+ * device call, each with its own message: num_head_channels divides the channel count of every attention block, and is a head dim
+ * sdeo_attention_f16 accepts. */
+typedef struct sdeo_config_ext {
+  int size;                        /* = sizeof(sdeo_config_ext), checked */
+  int num_head_channels;           /* 0 / -1 = use cfg->num_heads; else heads = C / num_head_channels per block */
+  int use_linear_in_transformer;   /* 0 = conv1x1 proj_in / proj_out, weights (C,C,1,1); 1 = nn.Linear, weights (C,C) */
+} sdeo_config_ext;
+int sdeo_create_ex(const sdeo_config* cfg, const sdeo_config_ext* ext, sdeo_handle* out);
 int sdeo_destroy(sdeo_handle h);
 
 /* Weights: one call per checkpoint tensor, names exactly as in the reference state dict
@@ -252,6 +270,8 @@ int sdeo_set_timestep_table(sdeo_handle h, const int64_t* host_timesteps, int co
  * the same.  Without the flag the ControlNet runs both halves in full.  Capturable. */
 #define SDEO_STEP_LATENT_STAGED 16
 #define SDEO_STEP_HINT_SHARED 32
+/* the model predicts v: the update is that of sdeo_cfg_ddim_step_v.  Without the flag nothing about the step changes. */
+#define SDEO_STEP_V_PREDICTION 64
 int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
                    float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream);
 
@@ -302,6 +322,11 @@ int sdeo_clip_finalize_weights(sdeo_clip_handle h);
 int sdeo_clip_num_weights(sdeo_clip_handle h);
 int sdeo_clip_weight_info(sdeo_clip_handle h, int i, const char** name, int64_t dims[2], int* ndim);
 /* fix the number of prompts per call and allocate the activation buffers */
+/* The OpenCLIP text tower behind FrozenOpenCLIPEmbedder (ldm/modules/encoders/modules.py:147-206): the same transformer with two
+ * differences.  Call before sdeo_clip_configure; hidden_act 0 = quick-GELU (default), 1 = erf GELU; skip_last_layers 0 (default) or
+ * k < layers: the last k blocks are expected as weights (checkpoints hold them) but not run, final_layer_norm follows block
+ * layers - k (layer = "penultimate" is k = 1).  (0, 0) leaves the handle exactly as it was created. */
+int sdeo_clip_set_variant(sdeo_clip_handle h, int hidden_act, int skip_last_layers);
 int sdeo_clip_configure(sdeo_clip_handle h, int batch);
 /* tokens int32 [batch][positions] (device) -> out fp32 [batch][positions][width] (device); ids outside the
  * vocabulary are clamped */

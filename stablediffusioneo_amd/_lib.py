@@ -31,6 +31,11 @@ class SdeoConfig(C.Structure):
     ]
 
 
+class SdeoConfigExt(C.Structure):
+    """sdeo_config_ext of include/sdeo.h (the SD-2.x layout switches of sdeo_create_ex)"""
+    _fields_ = [("size", C.c_int), ("num_head_channels", C.c_int), ("use_linear_in_transformer", C.c_int)]
+
+
 class SdeoClipConfig(C.Structure):
     _fields_ = [("vocab", C.c_int), ("positions", C.c_int), ("width", C.c_int), ("layers", C.c_int), ("heads", C.c_int),
                 ("ffn", C.c_int)]
@@ -74,6 +79,8 @@ def load(path: str = LIB_PATH):
     lib.sdeo_clip_device_bytes.argtypes = [C.c_void_p]
     lib.sdeo_hed_device_bytes.argtypes = [C.c_void_p]
     lib.sdeo_tuned_gemm_plans_json.restype = C.c_char_p
+    lib.sdeo_create_ex.argtypes = [C.POINTER(SdeoConfig), C.POINTER(SdeoConfigExt), C.POINTER(C.c_void_p)]
+    lib.sdeo_create_ex.restype = C.c_int
     _lib = lib
     load_tuned_plans(lib)
     return lib

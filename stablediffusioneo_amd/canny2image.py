@@ -10,6 +10,8 @@ The two stages around the loop are injectable:
 """
 from __future__ import annotations
 
+import dataclasses
+import functools
 import hashlib
 import random
 
@@ -45,21 +47,33 @@ class hackathon():
         FrozenCLIPEmbedder mirror on the HIP path (weights from the same source as the UNet's: synthetic seed or the
         checkpoint's `cond_stage_model.transformer.text_model.*`); bare "clip" is accepted only with synthetic weights (the
         tokenizer is then the crc32 stand-in, which is meaningless next to real weights); or any callable(prompts) ->
-        (B, 77, 768) tensor.  vae_encoder=True also builds the VAE encoder, which `process(init_image=...)` (img2img) needs."""
+        (B, 77, context_dim) tensor.  config "sd21" / "sd21v" (and "tiny21" / "tiny21v") select the SD-2.x layout (eps / v-prediction);
+        their text encoder is "openclip[:<tokenizer dir>]", the FrozenOpenCLIPEmbedder mirror (penultimate layer, as cldm_v21.yaml), under
+        the same rules as "clip".  vae_encoder=True also builds the VAE encoder, which `process(init_image=...)` (img2img) needs."""
         self.apply_canny = apply_canny or _default_canny()
         return self._init_model(weights, config, text_encoder, vae_encoder)
 
     def _init_model(self, weights, config, text_encoder, vae_encoder=False):
         """text encoder, ControlLDM and DDIM sampler of `initialize` (shared with hed2image)"""
-        if isinstance(text_encoder, str) and text_encoder.split(":")[0] == "clip":
-            from . import spec as S
-            from .ldm.modules.encoders.modules import FrozenCLIPEmbedder
+        if isinstance(text_encoder, str) and text_encoder.split(":")[0] in ("clip", "openclip"):
+            from .ldm.modules.encoders.modules import FrozenCLIPEmbedder, FrozenOpenCLIPEmbedder
+            kind = text_encoder.split(":")[0]
             tok_dir = text_encoder.split(":", 1)[1] if ":" in text_encoder else None
             synthetic = isinstance(weights, str) and weights.startswith("synthetic")
-            text_encoder = FrozenCLIPEmbedder(version=tok_dir, config=S.CLIP_TINY if config == "tiny" else S.CLIP_SD15,
-                                              allow_hash_tokenizer=synthetic and tok_dir is None)
-        self.text_encoder = text_encoder or synthetic_text_encoder
-        self.model = create_model(config, cond_stage_model=self.text_encoder, vae_encoder=vae_encoder)
+            tiny = isinstance(config, str) and config.startswith("tiny")
+            if kind == "clip":
+                text_encoder = FrozenCLIPEmbedder(version=tok_dir, config=S.CLIP_TINY if tiny else S.CLIP_SD15,
+                                                  allow_hash_tokenizer=synthetic and tok_dir is None)
+            else:
+                # (the reduced tower is built as wide as the reduced UNet's context: CLIP_TINY21 is 128 wide, UNET_TINY21 reads 96)
+                ccfg = dataclasses.replace(S.CLIP_TINY21, width=S.UNET_TINY21.context_dim) if tiny else S.CLIP_SD21
+                text_encoder = FrozenOpenCLIPEmbedder(version=tok_dir, layer="penultimate", config=ccfg,
+                                                      allow_hash_tokenizer=synthetic and tok_dir is None)
+        self.model = create_model(config, cond_stage_model=text_encoder, vae_encoder=vae_encoder)
+        if text_encoder is None:      # the seeded stand-in, as wide as the chosen config's context
+            text_encoder = functools.partial(synthetic_text_encoder, length=self.model.rt.ucfg.context_len, dim=self.model.rt.ucfg.context_dim)
+            self.model.cond_stage_model = text_encoder
+        self.text_encoder = text_encoder
         if isinstance(weights, str) and weights.startswith("synthetic"):
             seed = int(weights.split(":")[1]) if ":" in weights else 0
             self.model.rt.load_synthetic(seed)

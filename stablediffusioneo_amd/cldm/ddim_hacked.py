@@ -196,10 +196,10 @@ class DDIMSampler(object):
 
     def _loop_graph_ok(self, img, c, uc, scale, total_steps):
         """Steps 2..S as one graph: only the plain canny2image loop qualifies -- fused CFG pair, eta = 0 (no noise drawn inside
-        the loop), eps-parameterisation, no mask / callbacks / correctors (the callers check those)."""
+        the loop), eps- or v-parameterisation, no mask / callbacks / correctors (the callers check those)."""
         if not (USE_GRAPH and USE_LOOP_GRAPH and img.is_cuda and total_steps >= 2 and self._fusable(c, uc, scale)):
             return False
-        if self.model.parameterization != "eps":
+        if self.model.parameterization not in ("eps", "v"):
             return False
         return bool(getattr(self, "_sigmas_all_zero", False))      # computed with the schedule: no device -> host copy per image
 
@@ -221,7 +221,7 @@ class DDIMSampler(object):
         hint_shared = self._ident(c["c_concat"]) == self._ident(uc["c_concat"])
         key = (rt.generation, tuple(img.shape), tuple(int(t) for t in time_range), float(scale), int(log_every_t),
                tuple(float(v) for v in m.control_scales), bool(m.only_mid_control), getattr(self, "_schedule_key", None), LOOP_GRAPH_STEPS,
-               hint_shared)
+               hint_shared, m.parameterization)
         if getattr(rt, "_table_key", None) != (rt.generation, tuple(int(t) for t in time_range)):
             rt.set_timestep_table(time_range)            # another schedule used the runtime since (the graphs read the table by address)
         if getattr(self, "_loop_key", None) != key:
@@ -241,7 +241,8 @@ class DDIMSampler(object):
                     for i in range(first, min(first + per_graph, total_steps)):
                         index = total_steps - i - 1
                         rt.ddim_step(self._loop_x, self._loop_pred, i, scale, float(a_t[index]), float(a_p[index]), float(s1m[index]),
-                                     m.control_scales, m.only_mid_control, staged=i > first, hint_shared=hint_shared)
+                                     m.control_scales, m.only_mid_control, staged=i > first, hint_shared=hint_shared,
+                                     v_prediction=m.parameterization == "v")
                         if index % log_every_t == 0:
                             kept_x.append(self._loop_x.clone())
                             kept_p.append(self._loop_pred.clone())
@@ -297,10 +298,11 @@ class DDIMSampler(object):
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, dynamic_threshold=None):
-        """`cldm/ddim_hacked.py:180-231` (eps-parameterisation; v-prediction, score correctors, x0 quantisation and
-        dynamic thresholding are not on the canny2image path and raise)."""
-        if self.model.parameterization != "eps":
-            raise NotImplementedError("only eps-parameterisation is on the canny2image path")
+        """`cldm/ddim_hacked.py:180-231` (eps- and v-parameterisation, `:194-197,214-217`: the guided model output is combined first
+        and converted inside the update kernel; score correctors, x0 quantisation and dynamic thresholding are not on the
+        canny2image path and raise)."""
+        if self.model.parameterization not in ("eps", "v"):
+            raise NotImplementedError(f"parameterization {self.model.parameterization!r}: only eps and v are built")
         if score_corrector is not None or quantize_denoised or dynamic_threshold is not None:
             raise NotImplementedError("score_corrector / quantize_denoised / dynamic_threshold are off the hot path")
         eps_c, eps_u = self._eps_pair(x, c, t, unconditional_conditioning, unconditional_guidance_scale)
@@ -317,7 +319,8 @@ class DDIMSampler(object):
             if noise_dropout > 0.:
                 noise = torch.nn.functional.dropout(noise, p=noise_dropout)
         x_prev, pred_x0 = ops.cfg_ddim_step(x.contiguous(), eps_c.contiguous(), None if eps_u is None else eps_u.contiguous(),
-                                            unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m, noise=noise)
+                                            unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m, noise=noise,
+                                            v_prediction=self.model.parameterization == "v")
         return x_prev, pred_x0
 
     # ------------------------------------------------------------------------------------------ TRT-variant entry
@@ -327,7 +330,7 @@ class DDIMSampler(object):
                       score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, dynamic_threshold=None,
                       ucg_schedule=None, **kwargs):
-        """`cldm_trt/ddim_hacked.py:88-197`: sample + ddim_sampling + p_sample_ddim flattened, eps-parameterisation,
+        """`cldm_trt/ddim_hacked.py:88-197`: sample + ddim_sampling + p_sample_ddim flattened, eps- or v-parameterisation,
         no mask / corrector paths.  (`canny2image_TRT.py:80` calls this.)"""
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
@@ -370,7 +373,10 @@ class DDIMSampler(object):
                unconditional_conditioning=None, callback=None):
         """DDIM inversion, `cldm/ddim_hacked.py:233-279`: t_enc deterministic steps from x0 towards noise.  (With guidance the
         reference concatenates the two conditionings as tensors, `:257-259`, which only works for tensor conditionings; here the
-        pair goes through the same fused cond / uncond pass as sampling.)"""
+        pair goes through the same fused cond / uncond pass as sampling.)  The reference has no v handling here (`:233-279` use the
+        model output as eps), so a v-prediction model is refused rather than inverted with v taken for eps."""
+        if self.model.parameterization != "eps":
+            raise NotImplementedError("encode (DDIM inversion) is built for eps-parameterisation only")
         timesteps = np.arange(self.ddpm_num_timesteps) if use_original_steps else self.ddim_timesteps
         assert t_enc <= timesteps.shape[0]
         num_steps = t_enc

@@ -357,7 +357,14 @@ int sdeo_cfg_ddim_step(float* x_prev, float* pred_x0, const float* x, const floa
                        const float* noise, float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at,
                        int64_t n, void* stream) {
   return cfg_ddim_step(x_prev, pred_x0, x, eps_c, eps_u, noise, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, n,
-                       S(stream));
+                       false, S(stream));
+}
+
+int sdeo_cfg_ddim_step_v(float* x_prev, float* pred_x0, const float* x, const float* v_c, const float* v_u,
+                         const float* noise, float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at,
+                         int64_t n, void* stream) {
+  return cfg_ddim_step(x_prev, pred_x0, x, v_c, v_u, noise, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, n,
+                       true, S(stream));
 }
 
 int sdeo_nchw_f32_to_nhwc_f16(void* y, int ldy, const float* x, int n, int c, int hw, void* stream) {

@@ -5,6 +5,8 @@
 //   per layer:  x += out_proj(softmax_causal((q_proj(LN1 x) * d^-1/2) k_proj(LN1 x)^T) v_proj(LN1 x))
 //               x += fc2(quick_gelu(fc1(LN2 x)))          quick_gelu(v) = v * sigmoid(1.702 v)
 //   out = final_layer_norm(x)                              (LayerNorm eps 1e-5 throughout)
+// `FrozenOpenCLIPEmbedder.encode_with_transformer` (`modules.py:186-203`, the SD-2.x text tower) is the same program with erf GELU in
+// the MLP and, for layer = "penultimate", without the last block (sdeo_clip_set_variant).
 // Built from the same hand-written kernels as the UNet (layernorm, LDS-DMA GEMM with fused bias / activation /
 // residual epilogues, flash attention with a causal mask).  q_proj and k_proj are stacked into one GEMM.
 #include "../../include/sdeo.h"
@@ -14,6 +16,7 @@ using namespace sdeo;
 
 struct sdeo_clip_handle_s {
   sdeo_clip_config cfg{};
+  int hidden_act = 0, skip_last = 0;       // sdeo_clip_set_variant: erf GELU in the MLP; blocks at the end that are loaded but not run
   WeightStore ws;
   bool finalized = false;
   // configured state
@@ -128,6 +131,17 @@ int sdeo_clip_finalize_weights(sdeo_clip_handle h) {
   return 0;
 }
 
+int sdeo_clip_set_variant(sdeo_clip_handle h, int hidden_act, int skip_last_layers) {
+  SDEO_CHECK(h, "sdeo_clip_set_variant: null handle");
+  SDEO_CHECK(hidden_act == 0 || hidden_act == 1, "sdeo_clip_set_variant: hidden_act %d (0 quick-GELU, 1 erf GELU)", hidden_act);
+  SDEO_CHECK(skip_last_layers >= 0 && skip_last_layers < h->cfg.layers, "sdeo_clip_set_variant: cannot skip %d of %d layers", skip_last_layers,
+             h->cfg.layers);
+  SDEO_CHECK(h->batch == 0, "sdeo_clip_set_variant: call it before sdeo_clip_configure");
+  h->hidden_act = hidden_act;
+  h->skip_last = skip_last_layers;
+  return 0;
+}
+
 int sdeo_clip_configure(sdeo_clip_handle h, int batch) {
   SDEO_CHECK(h && h->finalized, "sdeo_clip_configure: weights not finalized");
   SDEO_CHECK(batch >= 1 && batch <= 64, "sdeo_clip_configure: batch=%d out of range", batch);
@@ -167,7 +181,8 @@ int sdeo_clip_configure(sdeo_clip_handle h, int batch) {
   f16* x = xa;
   f16* xn = xb;
   const float scale = 1.0f / sqrtf((float)d);
-  for (int l = 0; l < c.layers; ++l) {
+  const int mlp_act = e->hidden_act ? 5 : 2;
+  for (int l = 0; l < c.layers - e->skip_last; ++l) {
     const std::string p = "encoder.layers." + std::to_string(l) + ".";
     ln(x, vp(p + "layer_norm1.weight"), vp(p + "layer_norm1.bias"));
     gemm(a, W, wp(p + "self_attn.q_proj.weight"), 3 * W, vp(p + "self_attn.q_proj.bias"), 0, nullptr, qkv);
@@ -177,7 +192,7 @@ int sdeo_clip_configure(sdeo_clip_handle h, int batch) {
     gemm(o, W, wp(p + "self_attn.out_proj.weight"), W, vp(p + "self_attn.out_proj.bias"), 0, x, xn);
     std::swap(x, xn);
     ln(x, vp(p + "layer_norm2.weight"), vp(p + "layer_norm2.bias"));
-    gemm(a, W, wp(p + "mlp.fc1.weight"), F, vp(p + "mlp.fc1.bias"), 2, nullptr, hid);
+    gemm(a, W, wp(p + "mlp.fc1.weight"), F, vp(p + "mlp.fc1.bias"), mlp_act, nullptr, hid);
     gemm(hid, F, wp(p + "mlp.fc2.weight"), W, vp(p + "mlp.fc2.bias"), 0, x, xn);
     std::swap(x, xn);
   }

@@ -726,6 +726,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const KP pp) {
   } else if (p.act == 4) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) v[t] = fmaxf(v[t], 0.f);
+  } else if (p.act == 5) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) v[t] = gelu_erf_f(v[t]);
   }
   v *= p.scale;
 #pragma unroll
@@ -1000,7 +1003,8 @@ void conv_gemm_last_plan(int* tile, int* splitk) { *tile = g_last_tile; *splitk 
 static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
   SDEO_CHECK(p.x && p.w && (p.y || p.y32), "conv_gemm: null operand");
   SDEO_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "conv_gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
-  SDEO_CHECK(p.act >= 0 && p.act <= 4, "conv_gemm: act=%d unsupported (0 none, 1 SiLU, 2 quick-GELU, 3 GEGLU pair, 4 ReLU)", p.act);
+  SDEO_CHECK(p.act >= 0 && p.act <= 5, "conv_gemm: act=%d unsupported (0 none, 1 SiLU, 2 quick-GELU, 3 GEGLU pair, 4 ReLU, 5 erf GELU)", p.act);
+  SDEO_CHECK(p.act != 5 || !p.bias2, "conv_gemm: act 5 (erf GELU) is not built with a per-image bias2");
   SDEO_CHECK(p.N % 4 == 0, "conv_gemm: N=%d must be a multiple of 4", p.N);
   SDEO_CHECK(p.Cin % 8 == 0 && p.ldx % 8 == 0 && p.ldw % 8 == 0, "conv_gemm: Cin=%d ldx=%d ldw=%d must be multiples of 8",
              p.Cin, p.ldx, p.ldw);

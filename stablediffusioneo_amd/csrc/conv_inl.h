@@ -178,6 +178,9 @@ __device__ __forceinline__ void stage_block(const KP& p, const f32x4 (&accj)[NI]
     } else if (ACT == 4) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) v[t] = fmaxf(v[t], 0.f);
+    } else if (ACT == 5) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) v[t] = gelu_erf_f(v[t]);
     }
     v *= p.scale;
     *reinterpret_cast<f32x4*>(scratch + frow * ROWB + (i * 16 + fq * 4) * 4) = v;
@@ -319,7 +322,7 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
       nn[t] = nb + (id - rr[t] * G) * 8;
       live[t] = id < 16 * G && nn[t] < p.N;
     }
-    const int mode = (p.bias2 ? 8 : 0) | p.act;   // act is 0, 1, 2 or 4 here (3 = GEGLU never takes this path)
+    const int mode = (p.bias2 ? 8 : 0) | p.act;   // act is 0, 1, 2, 4 or 5 here (3 = GEGLU never takes this path; 5 never comes with bias2)
     // GroupNorm partials (KP::gn_out): lane c (and c + 64 ...) sums column c of every stored block, read back from an fp16 copy of
     // the block in LDS -- two registers per column instead of sixteen per (row, vector) slot
     constexpr int GCH = (TN + 63) / 64;
@@ -363,6 +366,7 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
           case 1: stage_block<NI, TN, false, 1>(p, accj, bias, m, nb, fq, frow, sc); break;
           case 2: stage_block<NI, TN, false, 2>(p, accj, bias, m, nb, fq, frow, sc); break;
           case 4: stage_block<NI, TN, false, 4>(p, accj, bias, m, nb, fq, frow, sc); break;
+          case 5: stage_block<NI, TN, false, 5>(p, accj, bias, m, nb, fq, frow, sc); break;
           case 8: stage_block<NI, TN, true, 0>(p, accj, bias, m, nb, fq, frow, sc); break;
           case 9: stage_block<NI, TN, true, 1>(p, accj, bias, m, nb, fq, frow, sc); break;
           case 10: stage_block<NI, TN, true, 2>(p, accj, bias, m, nb, fq, frow, sc); break;
@@ -493,6 +497,9 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
       } else if (p.act == 4) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) v[t] = fmaxf(v[t], 0.f);
+      } else if (p.act == 5) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = gelu_erf_f(v[t]);
       }
       v *= p.scale;
       if (p.res) {

@@ -281,14 +281,34 @@ __device__ __forceinline__ void cfg_ddim_elem(float x, float c, float u, bool gu
   xp = fmaf(sqrt_aprev, p0, dir_coef * e);
 }
 
+// The v-parameterisation of the same step (SD-2.x 768-v; upstream LatentDiffusion.predict_eps_from_z_and_v / predict_start_from_z_and_v,
+// called at `cldm/ddim_hacked.py:194-197,214-217`): the model outputs are combined first, v = v_u + s (v_c - v_u), then with
+// a = sqrt(a_t), s1 = sqrt(1 - a_t):   e = a v + s1 x;   pred_x0 = a x - s1 v;   x_prev as above.  No division.
+__device__ __forceinline__ void cfg_ddim_elem_v(float x, float c, float u, bool guided, float s, float sqrt_at, float sqrt_aprev, float dir_coef,
+                                                float sqrt_1m_at, float& p0, float& xp) {
+  const float v = guided ? fmaf(s, c - u, u) : c;
+  const float e = fmaf(sqrt_at, v, sqrt_1m_at * x);
+  p0 = fmaf(sqrt_at, x, -(sqrt_1m_at * v));
+  xp = fmaf(sqrt_aprev, p0, dir_coef * e);
+}
+
+// VPRED: `at_coef` is sqrt(a_t) and the model output is v; else 1 / sqrt(a_t) and eps (both kernels below)
+template <bool VPRED>
+__device__ __forceinline__ void cfg_ddim_elem_sel(float x, float c, float u, bool guided, float s, float at_coef, float sqrt_aprev, float dir_coef,
+                                                  float sqrt_1m_at, float& p0, float& xp) {
+  if constexpr (VPRED) cfg_ddim_elem_v(x, c, u, guided, s, at_coef, sqrt_aprev, dir_coef, sqrt_1m_at, p0, xp);
+  else cfg_ddim_elem(x, c, u, guided, s, at_coef, sqrt_aprev, dir_coef, sqrt_1m_at, p0, xp);
+}
+
+template <bool VPRED>
 __global__ __launch_bounds__(256) void cfg_ddim_kernel(float* __restrict__ x_prev, float* __restrict__ pred_x0,
                                                        const float* __restrict__ x, const float* __restrict__ ec,
                                                        const float* __restrict__ eu, const float* __restrict__ noise,
-                                                       float s, float rsqrt_at, float sqrt_aprev, float dir_coef, float sigma,
+                                                       float s, float at_coef, float sqrt_aprev, float dir_coef, float sigma,
                                                        float sqrt_1m_at, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     float p0, xp;
-    cfg_ddim_elem(x[i], ec[i], eu ? eu[i] : 0.f, eu != nullptr, s, rsqrt_at, sqrt_aprev, dir_coef, sqrt_1m_at, p0, xp);
+    cfg_ddim_elem_sel<VPRED>(x[i], ec[i], eu ? eu[i] : 0.f, eu != nullptr, s, at_coef, sqrt_aprev, dir_coef, sqrt_1m_at, p0, xp);
     if (noise) xp += sigma * noise[i];
     x_prev[i] = xp;
     if (pred_x0) pred_x0[i] = p0;
@@ -298,9 +318,10 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(float* __restrict__ x_pre
 // The same update for the fused CFG pair inside the library (sdeo_ddim_step): eps comes straight from the UNet's fp16 NHWC output
 // (images 0..b-1 conditional, b..2b-1 unconditional), x [b][C][HW] fp32 is updated in place, and the fp16 NHWC latent of the NEXT
 // forward (both halves of the pair, padding channels zero) is written on the way out.  One thread per (image, pixel).
+template <bool VPRED>
 __global__ __launch_bounds__(256) void cfg_ddim_pair_kernel(float* __restrict__ x, float* __restrict__ pred_x0, const f16* __restrict__ eps,
                                                             int lde, f16* __restrict__ x0, int ld0, int b, int C, int HW, float s,
-                                                            float rsqrt_at, float sqrt_aprev, float dir_coef, float sqrt_1m_at) {
+                                                            float at_coef, float sqrt_aprev, float dir_coef, float sqrt_1m_at) {
   const int64_t total = (int64_t)b * HW;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int64_t n = i / HW, pix = i - n * HW;
@@ -311,7 +332,7 @@ __global__ __launch_bounds__(256) void cfg_ddim_pair_kernel(float* __restrict__ 
       if (c < C) {
         const int64_t j = (n * C + c) * HW + pix;
         float p0, xp;
-        cfg_ddim_elem(x[j], (float)ec[c], (float)eu[c], true, s, rsqrt_at, sqrt_aprev, dir_coef, sqrt_1m_at, p0, xp);
+        cfg_ddim_elem_sel<VPRED>(x[j], (float)ec[c], (float)eu[c], true, s, at_coef, sqrt_aprev, dir_coef, sqrt_1m_at, p0, xp);
         x[j] = xp;
         if (pred_x0) pred_x0[j] = p0;
         v = (f16)xp;
@@ -323,11 +344,15 @@ __global__ __launch_bounds__(256) void cfg_ddim_pair_kernel(float* __restrict__ 
 }
 
 int cfg_ddim_pair(float* x, float* pred_x0, const f16* eps, int lde, f16* x0, int ld0, int b, int C, int HW, float cfg_scale, float a_t,
-                  float a_prev, float sqrt_one_minus_at, hipStream_t stream) {
+                  float a_prev, float sqrt_one_minus_at, bool v_prediction, hipStream_t stream) {
   SDEO_CHECK(x && eps && x0 && b > 0 && C > 0 && HW > 0 && lde >= C && ld0 >= C, "cfg_ddim_pair: bad operand");
   SDEO_CHECK(a_t > 0.f && (1.f - a_prev) >= 0.f, "cfg_ddim_pair: invalid schedule a_t=%g a_prev=%g", a_t, a_prev);
-  hipLaunchKernelGGL(cfg_ddim_pair_kernel, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, pred_x0, eps, lde, x0, ld0, b, C, HW,
-                     cfg_scale, 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev), sqrt_one_minus_at);
+  if (v_prediction)
+    hipLaunchKernelGGL(cfg_ddim_pair_kernel<true>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, pred_x0, eps, lde, x0, ld0, b, C, HW,
+                       cfg_scale, sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev), sqrt_one_minus_at);
+  else
+    hipLaunchKernelGGL(cfg_ddim_pair_kernel<false>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, pred_x0, eps, lde, x0, ld0, b, C, HW,
+                       cfg_scale, 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev), sqrt_one_minus_at);
   SDEO_HIP(hipGetLastError());
   return 0;
 }
@@ -353,13 +378,17 @@ int latent_pair_to_nhwc(f16* x0, int ld0, const float* x, int b, int C, int HW, 
 }
 
 int cfg_ddim_step(float* x_prev, float* pred_x0, const float* x, const float* eps_c, const float* eps_u, const float* noise,
-                  float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, int64_t n,
+                  float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, int64_t n, bool v_prediction,
                   hipStream_t stream) {
   SDEO_CHECK(x_prev && x && eps_c && n > 0, "cfg_ddim_step: bad operand");
   SDEO_CHECK(a_t > 0.f && (1.f - a_prev - sigma_t * sigma_t) >= 0.f, "cfg_ddim_step: invalid schedule a_t=%g a_prev=%g sigma=%g",
              a_t, a_prev, sigma_t);
-  hipLaunchKernelGGL(cfg_ddim_kernel, grid_for(n), dim3(256), 0, stream, x_prev, pred_x0, x, eps_c, eps_u, noise, cfg_scale,
-                     1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sigma_t * sigma_t), sigma_t, sqrt_one_minus_at, n);
+  if (v_prediction)
+    hipLaunchKernelGGL(cfg_ddim_kernel<true>, grid_for(n), dim3(256), 0, stream, x_prev, pred_x0, x, eps_c, eps_u, noise, cfg_scale,
+                       sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sigma_t * sigma_t), sigma_t, sqrt_one_minus_at, n);
+  else
+    hipLaunchKernelGGL(cfg_ddim_kernel<false>, grid_for(n), dim3(256), 0, stream, x_prev, pred_x0, x, eps_c, eps_u, noise, cfg_scale,
+                       1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sigma_t * sigma_t), sigma_t, sqrt_one_minus_at, n);
   SDEO_HIP(hipGetLastError());
   return 0;
 }

@@ -32,6 +32,7 @@ struct ConvGemm {
   int act = 0;                 // 0 none, 1 SiLU, 2 quick-GELU  v * sigmoid(1.702 v)  (CLIP MLP),
                                // 3 GEGLU pair: W rows interleaved value/gate in blocks of 16, y gets N/2 columns v * gelu(g)
                                // 4 ReLU (HED's VGG stack); plans like act 0 (not part of the plan key)
+                               // 5 erf GELU (the OpenCLIP text tower's MLP); plans like act 0, never with bias2
   int bias_per_row = 0;
   float scale = 1.0f;
   int force_tile = -1;         // testing hook: tile config index
@@ -212,10 +213,10 @@ int resize_area_u8(uint8_t* dst, const uint8_t* src, int h, int w, int c, int dh
 int resize_area_fast_u8(uint8_t* dst, const uint8_t* src, int h, int w, int c, int dh, int dw, hipStream_t stream);
 // classifier-free guidance + DDIM update on NCHW fp32 latents (ddim_hacked.py:192,208-231)
 int cfg_ddim_pair(float* x, float* pred_x0, const f16* eps, int lde, f16* x0, int ld0, int b, int C, int HW, float cfg_scale, float a_t,
-                  float a_prev, float sqrt_one_minus_at, hipStream_t stream);
+                  float a_prev, float sqrt_one_minus_at, bool v_prediction, hipStream_t stream);
 int latent_pair_to_nhwc(f16* x0, int ld0, const float* x, int b, int C, int HW, hipStream_t stream);
 int cfg_ddim_step(float* x_prev, float* pred_x0, const float* x, const float* eps_c, const float* eps_u, const float* noise,
                   float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, int64_t n,
-                  hipStream_t stream);
+                  bool v_prediction, hipStream_t stream);
 
 }  // namespace sdeo

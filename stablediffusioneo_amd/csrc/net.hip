@@ -95,6 +95,8 @@ enum ProgId {
 
 struct sdeo_handle_s {
   sdeo_config cfg;
+  int num_head_channels = 0;  // sdeo_config_ext: > 0 = heads of a block = C / num_head_channels (Blk::heads holds the result)
+  bool use_linear = false;    // sdeo_config_ext: proj_in / proj_out of every SpatialTransformer are nn.Linear, weights (C, C)
   UPlan uplan, cplan;
   std::vector<HintConv> hconvs;
   WeightStore ws;                                      // registry, slab and loader of the checkpoint tensors
@@ -183,6 +185,15 @@ struct Registry {
     region(off, cout, cin);
     if (bias) add(name + ".bias", W_VEC, {cout}, take((size_t)cout * 4));
   }
+  // proj_in / proj_out of a SpatialTransformer: conv1x1 weights (c, c, 1, 1), or nn.Linear weights (c, c) when the handle was created with
+  // use_linear_in_transformer.  c % 8 == 0, so both are stored as the same fp16 [c][c] matrix and run as the same row GEMM on NHWC
+  void proj(const std::string& name, int c) {
+    if (!e->use_linear) return conv(name, c, c, 1);
+    const size_t off = take((size_t)c * c * 2);
+    add(name + ".weight", W_LINEAR, {c, c}, off, c);
+    region(off, c, c);
+    add(name + ".bias", W_VEC, {c}, take((size_t)c * 4));
+  }
   void vec(const std::string& name, int c) { add(name, W_VEC, {c}, take((size_t)c * 4)); }
   void norm(const std::string& name, int c) { vec(name + ".weight", c); vec(name + ".bias", c); }
 };
@@ -205,7 +216,7 @@ static void reg_attn(Registry& r, const std::string& ns, const Blk& b, int ctx) 
   const std::string p = ns + b.name;
   const int c = b.cin;
   r.norm(p + ".norm", c);
-  r.conv(p + ".proj_in", c, c, 1);
+  r.proj(p + ".proj_in", c);
   const std::string t = p + ".transformer_blocks.0";
   // attn1: to_q, to_k, to_v stacked as one [3c][c] matrix (raw); the copy the network runs on has norm1 folded in
   const size_t qkv = r.take((size_t)3 * c * c * 2);
@@ -244,7 +255,7 @@ static void reg_attn(Registry& r, const std::string& ns, const Blk& b, int ctx) 
   r.norm(t + ".norm1", c);
   r.norm(t + ".norm2", c);
   r.norm(t + ".norm3", c);
-  r.conv(p + ".proj_out", c, c, 1);
+  r.proj(p + ".proj_out", c);
   // ff.net.2 + proj_out as one Linear over [GEGLU output | tok2] (build_attn); no fp8 / block-scaled copy: the reference modules the
   // fp8 goldens come from round ff.net.2 and proj_out separately, and this product is formed from exactly those rounded values
   ComposeJob cj;
@@ -684,7 +695,7 @@ static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& 
   const sdeo_config& c = b.e->cfg;
   const std::string p = ns + blk.name;
   const std::string t = p + ".transformer_blocks.0";
-  const int C = blk.cin, H = c.num_heads, d = C / H, N = x.n, Tq = x.h * x.w;
+  const int C = blk.cin, H = blk.heads, d = C / H, N = x.n, Tq = x.h * x.w;
   const int TkS = round8(c.context_len);
   // b.share: x holds the first N / 2 images only and everything up to attn2.to_q runs on them; the cross-attention (per-image K / V),
   // attn2.to_out and the last GEMM run at full batch and read q2 / tok1 / x of image i - N / 2 for the second half
@@ -1236,17 +1247,35 @@ static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); 
 
 extern "C" {
 
-int sdeo_create(const sdeo_config* cfg, sdeo_handle* out) {
+int sdeo_create(const sdeo_config* cfg, sdeo_handle* out) { return sdeo_create_ex(cfg, nullptr, out); }
+
+int sdeo_create_ex(const sdeo_config* cfg, const sdeo_config_ext* ext, sdeo_handle* out) {
   SDEO_CHECK(cfg && out, "sdeo_create: null argument");
+  SDEO_CHECK(!ext || ext->size == (int)sizeof(sdeo_config_ext), "sdeo_create_ex: sdeo_config_ext.size is %d, this library's struct has %d bytes",
+             ext ? ext->size : 0, (int)sizeof(sdeo_config_ext));
   SDEO_CHECK(cfg->num_levels >= 1 && cfg->num_levels <= 8 && cfg->vae_num_levels >= 1 && cfg->vae_num_levels <= 8,
              "sdeo_create: bad level count");
   SDEO_CHECK(cfg->model_channels % 32 == 0 && cfg->vae_ch % 32 == 0, "sdeo_create: channels must be multiples of 32 (GroupNorm)");
   SDEO_CHECK(cfg->context_dim % 8 == 0, "sdeo_create: context_dim must be a multiple of 8");
-  SDEO_CHECK((cfg->model_channels / cfg->num_heads) % 8 == 0, "sdeo_create: head dim must be a multiple of 8");
+  const int nhc = ext && ext->num_head_channels > 0 ? ext->num_head_channels : 0;
+  if (!nhc) SDEO_CHECK((cfg->model_channels / cfg->num_heads) % 8 == 0, "sdeo_create: head dim must be a multiple of 8");
   std::unique_ptr<Engine> e(new Engine());
   e->cfg = *cfg;
-  e->uplan = make_uplan(*cfg, true);
-  e->cplan = make_uplan(*cfg, false);
+  e->num_head_channels = nhc;
+  e->use_linear = ext && ext->use_linear_in_transformer != 0;
+  if (nhc) {
+    // host-only checks, before any device call: Blk::heads = C / nhc must be exact, and the head dim one the attention launcher has
+    const UPlan probe = make_uplan(*cfg, true, 0);
+    int bad_c = 0;
+    for_each_block(probe, [&](const Blk& b) { if (b.kind == B_ATTN && b.cin % nhc != 0 && !bad_c) bad_c = b.cin; });
+    SDEO_CHECK(!bad_c, "sdeo_create_ex: num_head_channels %d does not divide the %d channels of an attention block", nhc, bad_c);
+    if (!attention_kernel_name(1, 1, 1, 1, nhc, 0)) {
+      const std::string why = sdeo_last_error();
+      return fail("sdeo_create_ex: num_head_channels %d is not a head dim the attention kernels are built for (%s)", nhc, why.c_str());
+    }
+  }
+  e->uplan = make_uplan(*cfg, true, nhc);
+  e->cplan = make_uplan(*cfg, false, nhc);
   SDEO_CHECK(e->cplan.in.size() + 1 <= kMaxControls, "sdeo_create: more than %d control tensors", kMaxControls);
   e->hconvs = hint_convs(*cfg);
   if (const char* at = getenv("SDEO_AUTOTUNE")) e->autotune = atoi(at) != 0;
@@ -1632,7 +1661,7 @@ int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float
   // x0 = [x; x] at one timestep: the UNet's shared prefix always holds, the ControlNet's when the caller vouches for the hints
   if (int rc = run_step_programs(h, false, true, s, true, (flags & SDEO_STEP_HINT_SHARED) != 0)) return rc;
   return cfg_ddim_pair(x, pred_x0, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, b, c.out_channels, HW, cfg_scale, a_t, a_prev,
-                       sqrt_one_minus_at, s);
+                       sqrt_one_minus_at, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
 }
 
 int sdeo_vae_decode(sdeo_handle h, const float* z, int n, float* images, uint8_t* images_u8, void* stream) {

@@ -15,7 +15,7 @@ static const char* const NS_CN = "control_model.";
 static const char* const NS_VAE = "first_stage_model.";
 
 enum BlkKind { B_CONV_IN, B_RES, B_ATTN, B_DOWN, B_UP };
-struct Blk { BlkKind kind; std::string name; int cin, cout; };
+struct Blk { BlkKind kind; std::string name; int cin, cout; int heads = 0; };      // heads: B_ATTN only (spec.Block.heads)
 struct UPlan {
   std::vector<std::vector<Blk>> in, out;
   std::vector<Blk> mid;
@@ -27,9 +27,11 @@ static inline bool in_list(const int* v, int n, int x) {
   return false;
 }
 
-static inline UPlan make_uplan(const sdeo_config& c, bool with_decoder) {
+// num_head_channels > 0: every attention block has ch / num_head_channels heads (`cldm/cldm.py:184-191`); else c.num_heads
+static inline UPlan make_uplan(const sdeo_config& c, bool with_decoder, int num_head_channels = 0) {
   UPlan p;
   const int mc = c.model_channels;
+  auto heads = [&](int ch) { return num_head_channels > 0 ? ch / num_head_channels : c.num_heads; };
   auto nm = [](const char* pre, int i, int j) { return std::string(pre) + "." + std::to_string(i) + "." + std::to_string(j); };
   p.in.push_back({{B_CONV_IN, "input_blocks.0.0", c.in_channels, mc}});
   p.in_ch.push_back(mc);
@@ -42,7 +44,7 @@ static inline UPlan make_uplan(const sdeo_config& c, bool with_decoder) {
       layers.push_back({B_RES, nm("input_blocks", idx, 0), ch, mult * mc});
       ch = mult * mc;
       if (in_list(c.attention_resolutions, c.num_attention_resolutions, ds))
-        layers.push_back({B_ATTN, nm("input_blocks", idx, 1), ch, ch});
+        layers.push_back({B_ATTN, nm("input_blocks", idx, 1), ch, ch, heads(ch)});
       p.in.push_back(layers);
       p.in_ch.push_back(ch);
       p.in_ds.push_back(ds);
@@ -56,7 +58,7 @@ static inline UPlan make_uplan(const sdeo_config& c, bool with_decoder) {
       ++idx;
     }
   }
-  p.mid = {{B_RES, "middle_block.0", ch, ch}, {B_ATTN, "middle_block.1", ch, ch}, {B_RES, "middle_block.2", ch, ch}};
+  p.mid = {{B_RES, "middle_block.0", ch, ch}, {B_ATTN, "middle_block.1", ch, ch, heads(ch)}, {B_RES, "middle_block.2", ch, ch}};
   if (!with_decoder) return p;
   std::vector<int> stack = p.in_ch;
   int oidx = 0;
@@ -69,7 +71,7 @@ static inline UPlan make_uplan(const sdeo_config& c, bool with_decoder) {
       layers.push_back({B_RES, nm("output_blocks", oidx, 0), ch + ich, mc * mult});
       ch = mc * mult;
       if (in_list(c.attention_resolutions, c.num_attention_resolutions, ds))
-        layers.push_back({B_ATTN, nm("output_blocks", oidx, 1), ch, ch});
+        layers.push_back({B_ATTN, nm("output_blocks", oidx, 1), ch, ch, heads(ch)});
       if (level && i == c.num_res_blocks) {
         layers.push_back({B_UP, nm("output_blocks", oidx, (int)layers.size()), ch, ch});
         ds /= 2;

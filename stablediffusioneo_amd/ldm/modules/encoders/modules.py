@@ -1,4 +1,4 @@
-"""`ldm/modules/encoders/modules.py` mirror: FrozenCLIPEmbedder on the HIP path.
+"""`ldm/modules/encoders/modules.py` mirror: FrozenCLIPEmbedder and FrozenOpenCLIPEmbedder on the HIP path.
 
 The reference class (`ldm/modules/encoders/modules.py:90-141`) owns a HuggingFace tokenizer and `CLIPTextModel`, both
 fetched by name from the hub.  Here the transformer runs through libsdeo.so (`sdeo_clip_*`); the tokenizer stays on the
@@ -31,12 +31,14 @@ class HashTokenizer:
     the shape and padding convention of `CLIPTokenizer(..., padding="max_length", truncation=True)`
     (`ldm/modules/encoders/modules.py:124-125`), not its byte-pair vocabulary."""
 
-    def __init__(self, vocab: int = 49408, max_length: int = 77):
+    def __init__(self, vocab: int = 49408, max_length: int = 77, pad: Optional[int] = None):
+        """pad: id of the padding tail (None = EOS, CLIPTokenizer's; 0 = `open_clip.tokenize`'s)"""
         self.vocab, self.max_length = vocab, max_length
         self.bos, self.eos = vocab - 2, vocab - 1
+        self.pad = self.eos if pad is None else int(pad)
 
     def __call__(self, texts: Sequence[str]) -> np.ndarray:
-        out = np.full((len(texts), self.max_length), self.eos, dtype=np.int32)
+        out = np.full((len(texts), self.max_length), self.pad, dtype=np.int32)
         for i, t in enumerate(texts):
             words = re.findall(r"[a-z0-9]+|[^\sa-z0-9]", t.lower())
             ids = [self.bos] + [zlib.crc32(w.encode()) % (self.vocab - 2) for w in words][: self.max_length - 2] + [self.eos]
@@ -95,6 +97,77 @@ class FrozenCLIPEmbedder(AbstractEncoder):
         return self.transformer.encode(self.tokenize(list(text)))
 
     __call__ = forward
+
+    def encode(self, text):
+        return self(text)
+
+
+class FrozenOpenCLIPEmbedder(AbstractEncoder):
+    """Uses the OpenCLIP transformer encoder for text (`ldm/modules/encoders/modules.py:147-206`, the SD-2.x cond_stage_model):
+    `forward(text)` returns ln_final of the last (layer="last") or last-but-one (layer="penultimate", what cldm_v21.yaml asks for)
+    residual block, [B, 77, width] fp32 on the device.  The tower runs through libsdeo.so as `ClipRuntime` with erf GELU and
+    `layer_idx` skipped blocks.  `arch` / `version` name a hub model in the reference; here `version` is a LOCAL directory with CLIP's
+    vocab.json / merges.txt (OpenCLIP tokenises with the same byte-pair vocabulary, then pads with 0 instead of EOS), and the width /
+    depth come from `config`.  The `open_clip` package is not used: its own text clean-up (ftfy, html unescape) is not restated, so
+    prompts with markup or mis-encoded characters may tokenise differently."""
+    LAYERS = ["last", "penultimate"]
+
+    def __init__(self, arch="ViT-H-14", version: Optional[str] = None, device="cuda", max_length=77, freeze=True, layer="last",
+                 config: S.ClipConfig = S.CLIP_SD21, runtime: Optional[ClipRuntime] = None, allow_hash_tokenizer: bool = False):
+        assert layer in self.LAYERS
+        self.arch = arch
+        self.device = device
+        self.max_length = max_length
+        self.layer = layer
+        self.layer_idx = {"last": 0, "penultimate": 1}[layer]
+        self.config = config
+        self.tokenizer = None
+        if version is not None and os.path.isdir(version):
+            from transformers import CLIPTokenizer
+            self.tokenizer = CLIPTokenizer.from_pretrained(version, local_files_only=True)
+        if self.tokenizer is None:
+            if not allow_hash_tokenizer:
+                raise RuntimeError(
+                    f"FrozenOpenCLIPEmbedder: no local CLIP tokenizer at version={version!r} (a directory with vocab.json + merges.txt is "
+                    f"needed; the reference's default {arch!r} / 'laion2b_s32b_b79k' are hub names and there is no network).  Pass "
+                    f"allow_hash_tokenizer=True to use the crc32 stand-in -- token ids are then NOT byte-pair ids, which is only "
+                    f"meaningful with synthetic weights.")
+            self.tokenizer = HashTokenizer(config.vocab, max_length, pad=0)
+        if runtime is not None and runtime.variant != (1, self.layer_idx):
+            raise ValueError(f"FrozenOpenCLIPEmbedder(layer={layer!r}) needs a ClipRuntime of variant {(1, self.layer_idx)}, got {runtime.variant}")
+        self.transformer = runtime if runtime is not None else ClipRuntime(config, variant=(1, self.layer_idx))
+        self.model = self.transformer          # the reference keeps its tower in `.model`
+
+    def freeze(self):
+        return self
+
+    def load_state_dict(self, sd, strict=False):
+        if isinstance(self.tokenizer, HashTokenizer) and len(sd):
+            warnings.warn("FrozenOpenCLIPEmbedder: checkpoint weights loaded next to the HashTokenizer stand-in: prompts are hashed, not "
+                          "BPE-tokenised, so the conditioning is meaningless for real weights (supply version=<tokenizer dir>)",
+                          RuntimeWarning, stacklevel=2)
+        self.transformer.load_state_dict(sd, strict=strict)
+        return self
+
+    def tokenize(self, text: List[str]) -> torch.Tensor:
+        """`open_clip.tokenize`: SOT + byte-pair ids + EOT, cut to max_length with EOT last, the tail padded with 0"""
+        if isinstance(self.tokenizer, HashTokenizer):
+            return torch.from_numpy(np.asarray(self.tokenizer(text), dtype=np.int64))
+        rows = self.tokenizer(text, truncation=True, max_length=self.max_length, padding=False)["input_ids"]
+        ids = np.zeros((len(rows), self.max_length), dtype=np.int64)
+        for i, r in enumerate(rows):
+            ids[i, : len(r)] = r
+        return torch.from_numpy(ids)
+
+    def forward(self, text):
+        if isinstance(text, str):
+            text = [text]
+        return self.encode_with_transformer(self.tokenize(list(text)))
+
+    __call__ = forward
+
+    def encode_with_transformer(self, tokens):
+        return self.transformer.encode(tokens)
 
     def encode(self, text):
         return self(text)

@@ -378,15 +378,18 @@ def timestep_embedding(t, dim):
     return out
 
 
-def cfg_ddim_step(x, eps_c, eps_u, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise=None, want_pred_x0=True):
+def cfg_ddim_step(x, eps_c, eps_u, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise=None, want_pred_x0=True,
+                  v_prediction=False):
+    """v_prediction: eps_c / eps_u hold the v outputs of a v-prediction model (`sdeo_cfg_ddim_step_v`)."""
     lib = _lib.load()
     _need_cuda(x, eps_c)
     assert x.dtype == torch.float32 and x.is_contiguous() and eps_c.is_contiguous()
     x_prev = torch.empty_like(x)
     p0 = torch.empty_like(x) if want_pred_x0 else None
-    check(lib.sdeo_cfg_ddim_step(ptr(x_prev), ptr(p0), ptr(x), ptr(eps_c), ptr(eps_u), ptr(noise), _f(cfg_scale), _f(a_t),
-                                 _f(a_prev), _f(sigma_t), _f(sqrt_one_minus_at), C.c_int64(x.numel()), cur_stream()),
-          "cfg_ddim_step")
+    fn = lib.sdeo_cfg_ddim_step_v if v_prediction else lib.sdeo_cfg_ddim_step
+    check(fn(ptr(x_prev), ptr(p0), ptr(x), ptr(eps_c), ptr(eps_u), ptr(noise), _f(cfg_scale), _f(a_t),
+             _f(a_prev), _f(sigma_t), _f(sqrt_one_minus_at), C.c_int64(x.numel()), cur_stream()),
+          "cfg_ddim_step_v" if v_prediction else "cfg_ddim_step")
     return x_prev, p0
 
 

@@ -13,6 +13,7 @@ from ._lib import SdeoConfig, check, cur_stream, ptr
 HINT_CACHED, CONTEXT_CACHED, NO_CONTROL = 1, 2, 4
 STEP_LATENT_STAGED = 16
 STEP_HINT_SHARED = 32
+STEP_V_PREDICTION = 64
 
 
 def TIMESTEP_ROW(i: int) -> int:
@@ -38,6 +39,13 @@ def make_config(ucfg: S.UNetConfig = S.UNET_SD15, vcfg: S.VAEConfig = S.VAE_SD15
     c.vae_num_levels, c.vae_num_res_blocks, c.vae_z_channels = len(vcfg.ch_mult), vcfg.num_res_blocks, vcfg.z_channels
     c.vae_scale_factor = vcfg.scale_factor
     return c
+
+
+def make_config_ext(ucfg: S.UNetConfig) -> Optional[_lib.SdeoConfigExt]:
+    """sdeo_config_ext for a config of the 2.x layout; None when plain sdeo_create describes it (every 1.5 config)"""
+    if ucfg.num_head_channels in (-1, 0) and not ucfg.use_linear_in_transformer:
+        return None
+    return _lib.SdeoConfigExt(C.sizeof(_lib.SdeoConfigExt), max(0, ucfg.num_head_channels), int(ucfg.use_linear_in_transformer))
 
 
 class _HandleRuntime:
@@ -107,7 +115,11 @@ class SdeoRuntime(_HandleRuntime):
         super().__init__(device)
         self.ucfg, self.vcfg = ucfg, vcfg
         self._cfg = make_config(ucfg, vcfg)
-        check(self.lib.sdeo_create(C.byref(self._cfg), C.byref(self.handle)), "sdeo_create")
+        self._ext = make_config_ext(ucfg)
+        if self._ext is None:
+            check(self.lib.sdeo_create(C.byref(self._cfg), C.byref(self.handle)), "sdeo_create")
+        else:
+            check(self.lib.sdeo_create_ex(C.byref(self._cfg), C.byref(self._ext), C.byref(self.handle)), "sdeo_create_ex")
         self.vae_encoder = bool(vae_encoder)
         if self.vae_encoder:        # before any weight: the weight slab is sized when the encoder registers its tensors
             check(self.lib.sdeo_enable_vae_encoder(self.handle), "enable_vae_encoder")
@@ -284,15 +296,17 @@ class SdeoRuntime(_HandleRuntime):
         return len(ts)
 
     def ddim_step(self, x, pred_x0, row: int, cfg_scale: float, a_t: float, a_prev: float, sqrt_one_minus_at: float, scales=None,
-                  only_mid_control: bool = False, staged: bool = False, hint_shared: bool = False):
+                  only_mid_control: bool = False, staged: bool = False, hint_shared: bool = False, v_prediction: bool = False):
         """`sdeo_ddim_step`: one eta = 0 DDIM step of the CFG pair; x (b,4,h,w) fp32 contiguous is updated in place.
         hint_shared: the cached hints of the unconditional half are those of the conditional half (SDEO_STEP_HINT_SHARED), so the
-        ControlNet too computes what precedes its first cross-attention once."""
+        ControlNet too computes what precedes its first cross-attention once.  v_prediction: the model predicts v
+        (SDEO_STEP_V_PREDICTION)."""
         assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
         assert pred_x0 is None or (pred_x0.is_contiguous() and pred_x0.dtype == torch.float32 and pred_x0.shape == x.shape)
         check(self.lib.sdeo_ddim_step(self.handle, ptr(x), ptr(pred_x0), C.c_int(int(row)), C.c_float(cfg_scale), C.c_float(a_t),
                                       C.c_float(a_prev), C.c_float(sqrt_one_minus_at), self._scales(scales),
-                                      C.c_int(int(only_mid_control)), C.c_int((STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)),
+                                      C.c_int(int(only_mid_control)), C.c_int((STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)
+                                              | (STEP_V_PREDICTION if v_prediction else 0)),
                                       cur_stream()),
               "ddim_step")
         return x
@@ -339,6 +353,39 @@ class SdeoRuntime(_HandleRuntime):
         return (z, mom) if want_moments else z
 
 
+def openclip_to_hf(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Rename the text-tower tensors of an OpenCLIP state dict (`open_clip.model.CLIP`: what `FrozenOpenCLIPEmbedder.model` holds,
+    `ldm/modules/encoders/modules.py:160-162`) to the HuggingFace names the library registers.  `attn.in_proj_weight` / `_bias` are the
+    fused [3W][W] / [3W] tensors: their thirds are q, k, v.  `text_projection`, `logit_scale`, `attn_mask` and the visual tower have no
+    counterpart and are dropped; a dict without OpenCLIP names is returned as it is."""
+    if not any("transformer.resblocks." in k and "visual." not in k for k in sd):
+        return sd
+    out = {}
+    blk = {"ln_1.": "layer_norm1.", "ln_2.": "layer_norm2.", "attn.out_proj.": "self_attn.out_proj.", "mlp.c_fc.": "mlp.fc1.",
+           "mlp.c_proj.": "mlp.fc2."}
+    for k, v in sd.items():
+        n = k[len("cond_stage_model."):] if k.startswith("cond_stage_model.") else k
+        n = n[len("model."):] if n.startswith("model.") else n
+        if n == "token_embedding.weight":
+            out["embeddings.token_embedding.weight"] = v
+        elif n == "positional_embedding":
+            out["embeddings.position_embedding.weight"] = v
+        elif n.startswith("ln_final."):
+            out["final_layer_norm." + n[len("ln_final."):]] = v
+        elif n.startswith("transformer.resblocks."):
+            i, rest = n[len("transformer.resblocks."):].split(".", 1)
+            p = f"encoder.layers.{i}."
+            if rest in ("attn.in_proj_weight", "attn.in_proj_bias"):
+                leaf = rest.rsplit("_", 1)[1]
+                for name, part in zip(("q_proj", "k_proj", "v_proj"), torch.chunk(v, 3, dim=0)):
+                    out[f"{p}self_attn.{name}.{leaf}"] = part
+            else:
+                for a, b in blk.items():
+                    if rest.startswith(a):
+                        out[p + b + rest[len(a):]] = v
+    return out
+
+
 class ClipRuntime(_HandleRuntime):
     """CLIP text transformer on the HIP path: create -> load_state_dict -> configure(batch) ->
     encode(tokens).  Mirrors what `FrozenCLIPEmbedder.forward` does after tokenisation
@@ -347,17 +394,24 @@ class ClipRuntime(_HandleRuntime):
     _prefix = "sdeo_clip_"
     _ndims = 2
 
-    def __init__(self, cfg: S.ClipConfig = S.CLIP_SD15, device: Optional[torch.device] = None):
+    def __init__(self, cfg: S.ClipConfig = S.CLIP_SD15, device: Optional[torch.device] = None, variant: Optional[tuple] = None):
+        """variant = (hidden_act, skip_last_layers) of `sdeo_clip_set_variant`: (1, k) is the OpenCLIP text tower of
+        `FrozenOpenCLIPEmbedder` (erf GELU; layer "last" k = 0, "penultimate" k = 1).  None: the call is not made."""
         super().__init__(device)
         self.cfg = cfg
         self._cfg = _lib.SdeoClipConfig(cfg.vocab, cfg.positions, cfg.width, cfg.layers, cfg.heads, cfg.ffn)
         check(self.lib.sdeo_clip_create(C.byref(self._cfg), C.byref(self.handle)), "sdeo_clip_create")
+        self.variant = None if variant is None else (int(variant[0]), int(variant[1]))
+        if self.variant is not None:
+            self._call("set_variant", C.c_int(self.variant[0]), C.c_int(self.variant[1]))
         self.batch = 0
         self.generation = 0          # bumped by every re-plan of the activation buffers (see SdeoRuntime.generation)
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False):
-        """Accepts HuggingFace names (`text_model.*`, or bare), or the SD checkpoint's `cond_stage_model.transformer.text_model.*`;
-        anything else (e.g. `position_ids`, the UNet tensors of a full checkpoint) is ignored unless strict."""
+        """Accepts HuggingFace names (`text_model.*`, or bare), or the SD checkpoint's `cond_stage_model.transformer.text_model.*`,
+        or OpenCLIP's names (bare, or below `model.` / `cond_stage_model.model.` as an SD-2.x checkpoint stores them; see
+        `openclip_to_hf`); anything else (e.g. `position_ids`, the UNet tensors of a full checkpoint) is ignored unless strict."""
+        sd = openclip_to_hf(sd)
         for k, v in sd.items():
             if not torch.is_floating_point(v):
                 continue

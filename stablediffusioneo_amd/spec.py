@@ -42,10 +42,18 @@ class UNetConfig:
     num_heads: int = 8
     context_dim: int = 768
     context_len: int = 77
+    # the cldm_v21.yaml layout (`cldm/cldm.py:64,77,184-207`): a fixed head width instead of a fixed head count (-1: num_heads
+    # holds), and nn.Linear instead of conv1x1 as the SpatialTransformer's proj_in / proj_out (`ldm/modules/attention.py:409-429`)
+    num_head_channels: int = -1
+    use_linear_in_transformer: bool = False
 
     @property
     def time_embed_dim(self) -> int:
         return self.model_channels * 4
+
+    def heads_for(self, ch: int) -> int:
+        """Heads of an attention block of `ch` channels (`cldm/cldm.py:184-191`)."""
+        return self.num_heads if self.num_head_channels in (-1, 0) else ch // self.num_head_channels
 
 
 @dataclass(frozen=True)
@@ -71,10 +79,16 @@ class ScheduleConfig:
 UNET_SD15 = UNetConfig()
 VAE_SD15 = VAEConfig()
 SCHEDULE_SD15 = ScheduleConfig()
+# SD-2.x + its ControlNet (the cldm_v21.yaml layout): head width 64 (5 / 10 / 20 / 20 heads), Linear projections, OpenCLIP-H context;
+# the 768-v checkpoints predict v instead of eps
+UNET_SD21 = UNetConfig(num_head_channels=64, use_linear_in_transformer=True, context_dim=1024)
+SCHEDULE_SD21V = ScheduleConfig(parameterization="v")
 
 # reduced configuration with the same topology, for fast numeric tests
 UNET_TINY = UNetConfig(model_channels=64, context_dim=96, num_heads=4)  # context_dim must differ from every query dim (attention.py:168-173 quirk)
 VAE_TINY = VAEConfig(ch=32)
+# the 2.x layout reduced: heads 2 / 4 / 8 / 8 at width 32
+UNET_TINY21 = UNetConfig(model_channels=64, num_head_channels=32, use_linear_in_transformer=True, context_dim=96)
 
 
 # ----------------------------------------------------------------------------------------
@@ -118,7 +132,7 @@ def unet_plan(cfg: UNetConfig, with_decoder: bool = True) -> UNetPlan:
             layers = [Block("res", f"input_blocks.{idx}.0", ch, mult * mc)]
             ch = mult * mc
             if ds in cfg.attention_resolutions:
-                layers.append(Block("attn", f"input_blocks.{idx}.1", ch, ch, cfg.num_heads))
+                layers.append(Block("attn", f"input_blocks.{idx}.1", ch, ch, cfg.heads_for(ch)))
             plan.input_blocks.append(layers)
             chans.append(ch)
             dss.append(ds)
@@ -133,7 +147,7 @@ def unet_plan(cfg: UNetConfig, with_decoder: bool = True) -> UNetPlan:
     plan.input_block_ds = list(dss)
     plan.middle_block = [
         Block("res", "middle_block.0", ch, ch),
-        Block("attn", "middle_block.1", ch, ch, cfg.num_heads),
+        Block("attn", "middle_block.1", ch, ch, cfg.heads_for(ch)),
         Block("res", "middle_block.2", ch, ch),
     ]
     if not with_decoder:
@@ -146,7 +160,7 @@ def unet_plan(cfg: UNetConfig, with_decoder: bool = True) -> UNetPlan:
             layers = [Block("res", f"output_blocks.{oidx}.0", ch + ich, mc * mult)]
             ch = mc * mult
             if ds in cfg.attention_resolutions:
-                layers.append(Block("attn", f"output_blocks.{oidx}.1", ch, ch, cfg.num_heads))
+                layers.append(Block("attn", f"output_blocks.{oidx}.1", ch, ch, cfg.heads_for(ch)))
             if level and i == cfg.num_res_blocks:
                 layers.append(Block("up", f"output_blocks.{oidx}.{len(layers)}", ch, ch))
                 ds //= 2
@@ -202,12 +216,14 @@ def _res(spec, b: Block, emb: int):
         _conv(spec, f"{b.name}.skip_connection", b.cin, b.cout, 1)
 
 
-def _attn(spec, b: Block, ctx: int):
+def _attn(spec, b: Block, ctx: int, linear: bool = False):
     """SpatialTransformer parameters (`ldm/modules/attention.py:397-429`, depth 1,
-    BasicTransformerBlock `:360-375`, CrossAttention `:154-179`, GEGLU FeedForward `:49-76`)."""
+    BasicTransformerBlock `:360-375`, CrossAttention `:154-179`, GEGLU FeedForward `:49-76`).
+    linear: proj_in / proj_out are nn.Linear, weights (C, C) (`use_linear`, `:409-429`)."""
     c = b.cin
+    proj = (lambda n: _lin(spec, n, c, c)) if linear else (lambda n: _conv(spec, n, c, c, 1))
     _norm(spec, f"{b.name}.norm", c)
-    _conv(spec, f"{b.name}.proj_in", c, c, 1)
+    proj(f"{b.name}.proj_in")
     t = f"{b.name}.transformer_blocks.0"
     for a, kd in (("attn1", c), ("attn2", ctx)):
         _lin(spec, f"{t}.{a}.to_q", c, c, bias=False)
@@ -218,7 +234,7 @@ def _attn(spec, b: Block, ctx: int):
     _lin(spec, f"{t}.ff.net.2", 4 * c, c)
     for n in ("norm1", "norm2", "norm3"):
         _norm(spec, f"{t}.{n}", c)
-    _conv(spec, f"{b.name}.proj_out", c, c, 1)
+    proj(f"{b.name}.proj_out")
 
 
 def _blocks(spec, blocks: List[Block], cfg: UNetConfig):
@@ -228,7 +244,7 @@ def _blocks(spec, blocks: List[Block], cfg: UNetConfig):
         elif b.kind == "res":
             _res(spec, b, cfg.time_embed_dim)
         elif b.kind == "attn":
-            _attn(spec, b, cfg.context_dim)
+            _attn(spec, b, cfg.context_dim, cfg.use_linear_in_transformer)
         elif b.kind == "down":
             _conv(spec, f"{b.name}.op", b.cin, b.cout, 3)
         elif b.kind == "up":
@@ -387,6 +403,10 @@ class ClipConfig:
 
 CLIP_SD15 = ClipConfig()
 CLIP_TINY = ClipConfig(vocab=1000, positions=77, width=64, layers=2, heads=4, ffn=128)
+# the OpenCLIP ViT-H/14 text tower behind `FrozenOpenCLIPEmbedder` (`ldm/modules/encoders/modules.py:147-206`): erf-GELU, and the
+# SD-2.x configs read the penultimate block's output through ln_final; same tensor inventory as the CLIP-L tower
+CLIP_SD21 = ClipConfig(vocab=49408, positions=77, width=1024, layers=24, heads=16, ffn=4096)
+CLIP_TINY21 = ClipConfig(vocab=1000, positions=77, width=128, layers=3, heads=4, ffn=256)
 NS_CLIP = "cond_stage_model.transformer.text_model."
 
 

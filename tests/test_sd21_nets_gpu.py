@@ -1,0 +1,130 @@
+"""Net-level GPU parity of the SD-2.x layout (heads = C / num_head_channels per block, nn.Linear proj_in / proj_out, its own context
+width) through sdeo_create_ex, against the golden outputs of the REFERENCE modules built with the cldm_v21.yaml switches
+(tests/golden/tiny21_nets.npz, sd21_lat8.npz: fp32, tests/golden/make_golden_sd21.py).
+
+Bounds (relative to max|ref|, as tests/test_nets_gpu.py states them: cap 2e-2 max / 4e-3 mean).  Measured on MI355X against these
+goldens, worst of all outputs: max 2.6e-3 / mean 5.7e-4 (tiny21: eps without control at 8x24), max 1.9e-3 / mean 4.6e-4 (sd21 at latent
+8x8: control11 / eps); both under a third of the cap, next to 1.7e-3 / 3.3e-4 for the SD-1.5 tiny eps in the same run.  The test bounds
+are about three times the measured values: 8e-3 max / 1.7e-3 mean (tiny21) and 6e-3 max / 1.4e-3 mean (sd21)."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests.common import GOLDEN, make_inputs
+from tests.test_nets_gpu import REL_MAX, REL_MEAN, check
+
+pytestmark = pytest.mark.gpu
+
+TINY21_MAX, TINY21_MEAN = 8e-3, 1.7e-3
+SD21_MAX, SD21_MEAN = 6e-3, 1.4e-3
+assert TINY21_MAX <= REL_MAX and SD21_MAX <= REL_MAX and TINY21_MEAN <= REL_MEAN and SD21_MEAN <= REL_MEAN
+
+
+@pytest.fixture(scope="module")
+def tiny21_rt():
+    from stablediffusioneo_amd import spec as S
+    from stablediffusioneo_amd.runtime import SdeoRuntime
+    rt = SdeoRuntime(S.UNET_TINY21, S.VAE_TINY)
+    rt.load_synthetic(0)
+    return rt
+
+
+def test_expected_weights_match_spec(tiny21_rt):
+    from stablediffusioneo_amd import spec as S
+    exp = tiny21_rt.expected_weights()
+    assert exp == {k: tuple(v) for k, v in S.param_spec_full(S.UNET_TINY21, S.VAE_TINY).items()}
+    assert exp["model.diffusion_model.input_blocks.1.1.proj_in.weight"] == (64, 64)           # 2-D: nn.Linear
+    assert exp["control_model.middle_block.1.proj_out.weight"] == (256, 256)
+
+
+@pytest.mark.parametrize("n,h,w,t", [(2, 16, 16, [801, 1]), (1, 8, 24, [401])])
+def test_tiny21_nets_vs_reference_golden(tiny21_rt, n, h, w, t):
+    from stablediffusioneo_amd import spec as S
+    from stablediffusioneo_amd.runtime import CONTEXT_CACHED, HINT_CACHED
+    g = np.load(os.path.join(GOLDEN, "tiny21_nets.npz"))
+    tag = f"n{n}_{h}x{w}"
+    rt = tiny21_rt.configure(n, h, w)
+    x, ctx, hint = make_inputs(n, h, w, ctx_dim=S.UNET_TINY21.context_dim)
+    tt = torch.tensor(t, dtype=torch.long)
+    kw = dict(rel_max=TINY21_MAX, rel_mean=TINY21_MEAN)
+    ctrl = rt.controlnet(x, hint, tt, ctx)
+    assert len(ctrl) == 13
+    for i, c in enumerate(ctrl):
+        check(c, g[f"{tag}.control{i}"], f"tiny21 {tag} control{i}", **kw)
+    eps = rt.unet(x, tt, ctx, control=[torch.tensor(g[f"{tag}.control{i}"]) for i in range(13)])
+    check(eps, g[f"{tag}.eps"], f"tiny21 {tag} eps (unet, golden controls)", **kw)
+    check(rt.unet(x, tt, ctx, control=None), g[f"{tag}.eps_nocontrol"], f"tiny21 {tag} eps (no control)", **kw)
+    eps2 = rt.apply_model(x, hint, tt, ctx, scales=[1.0] * 13)
+    check(eps2, g[f"{tag}.eps"], f"tiny21 {tag} eps (apply_model)", **kw)
+    eps3 = rt.apply_model(x, None, tt, None, scales=[1.0] * 13, flags=HINT_CACHED | CONTEXT_CACHED)
+    assert torch.equal(eps2, eps3)               # cached hint / context: the same bits
+
+
+def test_full_sd21_latent8_vs_reference_golden():
+    """Full SD-2.1 layout (865.9 M + its ControlNet; heads 5 / 10 / 20 / 20 at d = 64, context 1024) at latent 8x8, N = 2."""
+    from stablediffusioneo_amd import spec as S
+    from stablediffusioneo_amd.runtime import SdeoRuntime
+    g = np.load(os.path.join(GOLDEN, "sd21_lat8.npz"))
+    rt = SdeoRuntime(S.UNET_SD21, S.VAE_TINY)
+    rt.load_synthetic(0)
+    exp = rt.expected_weights()
+    assert exp["model.diffusion_model.middle_block.1.proj_in.weight"] == (1280, 1280)
+    assert exp["model.diffusion_model.middle_block.1.transformer_blocks.0.attn2.to_v.weight"] == (1280, 1024)
+    rt.configure(2, 8, 8)
+    x, ctx, hint = make_inputs(2, 8, 8, ctx_dim=S.UNET_SD21.context_dim)
+    t = torch.tensor([801, 1], dtype=torch.long)
+    ctrl = rt.controlnet(x, hint, t, ctx)
+    for i, c in enumerate(ctrl):
+        check(c, g[f"control{i}"], f"sd21 control{i}", rel_max=SD21_MAX, rel_mean=SD21_MEAN)
+    check(rt.apply_model(x, hint, t, ctx), g["eps"], "sd21 eps (apply_model)", rel_max=SD21_MAX, rel_mean=SD21_MEAN)
+
+
+def _create_ex(cfg, nhc, linear, size=None):
+    from stablediffusioneo_amd import _lib, runtime
+    lib = _lib.load()
+    c = runtime.make_config(cfg)
+    ext = _lib.SdeoConfigExt(C.sizeof(_lib.SdeoConfigExt) if size is None else size, nhc, linear)
+    h = C.c_void_p()
+    rc = lib.sdeo_create_ex(C.byref(c), C.byref(ext), C.byref(h))
+    return lib, rc, h
+
+
+def test_create_ex_refuses_bad_head_channels():
+    from stablediffusioneo_amd import spec as S
+    lib, rc, h = _create_ex(S.UNET_TINY, 48, 1)             # 64 % 48 != 0
+    assert rc != 0 and not h.value and b"does not divide" in lib.sdeo_last_error()
+    cfg104 = S.UNetConfig(model_channels=416, context_dim=96)             # 416 = 4 x 104 = 13 x 32: divides, but d = 104 has no kernel
+    lib, rc, h = _create_ex(cfg104, 104, 1)
+    assert rc != 0 and not h.value and b"head dim" in lib.sdeo_last_error() and b"104" in lib.sdeo_last_error()
+    lib, rc, h = _create_ex(S.UNET_TINY, 32, 1, size=4)               # a struct of another size
+    assert rc != 0 and not h.value and b"size" in lib.sdeo_last_error()
+
+
+def test_create_ex_null_is_create():
+    """sdeo_create(cfg) and sdeo_create_ex(cfg, NULL) on UNET_TINY: the same expected weights and the same bits, which still meet
+    tiny_nets.npz"""
+    from stablediffusioneo_amd import _lib, spec as S
+    from stablediffusioneo_amd.runtime import SdeoRuntime
+    g = np.load(os.path.join(GOLDEN, "tiny_nets.npz"))
+    a = SdeoRuntime(S.UNET_TINY, S.VAE_TINY)
+    b = SdeoRuntime(S.UNET_TINY, S.VAE_TINY)
+    lib = a.lib
+    assert lib.sdeo_destroy(b.handle) == 0                 # swap b's handle for one made by sdeo_create_ex(cfg, NULL)
+    b.handle = C.c_void_p()
+    _lib.check(lib.sdeo_create_ex(C.byref(b._cfg), None, C.byref(b.handle)), "sdeo_create_ex")
+    assert a.expected_weights() == b.expected_weights()
+    n, h, w = 2, 16, 16
+    x, ctx, hint = make_inputs(n, h, w, ctx_dim=S.UNET_TINY.context_dim)
+    tt = torch.tensor([801, 1], dtype=torch.long)
+    outs = []
+    for rt in (a, b):
+        rt.load_synthetic(0)
+        rt.configure(n, h, w)
+        outs.append((rt.apply_model(x, hint, tt, ctx, scales=[1.0] * 13).clone(), [c.clone() for c in rt.controlnet(x, hint, tt, ctx)]))
+    assert torch.equal(outs[0][0], outs[1][0])
+    for u, v in zip(outs[0][1], outs[1][1]):
+        assert torch.equal(u, v)
+    check(outs[0][0], g["n2_16x16.eps"], "tiny eps via sdeo_create")
