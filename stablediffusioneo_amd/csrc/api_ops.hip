@@ -51,6 +51,22 @@ int sdeo_groupnorm_nhwc_f16(void* y, const void* x, const float* gamma, const fl
                         S(stream));
 }
 
+int sdeo_debug_groupnorm_path(int n, int hw, int c, int groups) {
+  if (!(n > 0 && hw > 0 && c > 0 && c % 8 == 0 && groups > 0 && groups <= 64 && c % groups == 0)) {
+    fail("groupnorm_path: n=%d hw=%d c=%d groups=%d", n, hw, c, groups);
+    return -1;
+  }
+  GnArgs a{};
+  a.B = n; a.HW = hw; a.C = c; a.groups = groups; a.ldx = a.ldy = c;
+  return gn_fused_threads(a);
+}
+
+int sdeo_debug_groupnorm_ld_f16(void* y, int ldy, const void* x, int ldx, const float* gamma, const float* beta, int n, int hw, int c,
+                                int groups, float eps, int with_silu, void* workspace, void* stream) {
+  SDEO_CHECK(ldx >= c && ldy >= c, "groupnorm_ld: ldx=%d ldy=%d below c=%d", ldx, ldy, c);
+  return groupnorm_nhwc((f16*)y, ldy, (const f16*)x, ldx, gamma, beta, n, hw, c, groups, eps, with_silu, (float*)workspace, S(stream));
+}
+
 static thread_local const void* g_next_q8 = nullptr;
 static thread_local const float* g_next_q8_scale = nullptr;
 // sdeo_debug_next_weights_fp8 is one-shot: every conv / GEMM entry point disarms it FIRST (before any validation can fail), so a
@@ -324,6 +340,17 @@ int sdeo_debug_row_stats_f16(float* stats, int stats_ld, const void* x, int ldx,
 int sdeo_layernorm_f16(void* y, const void* x, const float* gamma, const float* beta, int rows, int c, float eps,
                        void* stream) {
   return layernorm((f16*)y, c, (const f16*)x, c, gamma, beta, rows, c, eps, S(stream));
+}
+
+int sdeo_debug_layernorm_ld_f16(void* y, int ldy, const void* x, int ldx, const float* gamma, const float* beta, int rows, int c,
+                                float eps, void* stream) {
+  SDEO_CHECK(ldx >= c && ldy >= c, "layernorm_ld: ldx=%d ldy=%d below c=%d", ldx, ldy, c);
+  return layernorm((f16*)y, ldy, (const f16*)x, ldx, gamma, beta, rows, c, eps, S(stream));
+}
+
+int sdeo_debug_softmax_rows(void* p, int ldp, const float* s, int lds, int rows, int cols, float scale, void* stream) {
+  SDEO_CHECK(ldp >= cols && lds >= cols, "softmax_rows: ldp=%d lds=%d below cols=%d", ldp, lds, cols);
+  return softmax_rows((f16*)p, ldp, s, lds, rows, cols, scale, S(stream));
 }
 
 int sdeo_attention_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int b,

@@ -116,6 +116,9 @@ struct GnArgs {
 };
 // whether groupnorm_nhwc(a) runs as ONE launch with its slice in LDS
 bool groupnorm_is_single_launch(const GnArgs& a);
+// the launcher's own selection for a (only HW, C and groups are read; C % groups == 0): 0 = two launches (statistics, apply),
+// 256 / 1024 = threads of the single-launch kernel.  Host only.
+int gn_fused_threads(const GnArgs& a);
 int groupnorm_nhwc(const GnArgs& a, hipStream_t stream);
 
 // LayerNorm over the last dim of [rows][C] fp16 (two-pass in registers, fp32 math).

@@ -436,7 +436,7 @@ static int gn_check(const GnArgs& a) {
 }
 
 // 0: two-launch path; 256 / 1024: threads of the single-launch kernel
-static int gn_fused_threads(const GnArgs& a) {
+int gn_fused_threads(const GnArgs& a) {
   const int HW = a.HW, C = a.C, cpg = C / a.groups;
   static const int two_pass = [] { const char* e = getenv("SDEO_GN_TWO_PASS"); return e ? atoi(e) : 0; }();
   const int nvw = two_pass ? 0 : gn_fused_vecs(C, cpg);

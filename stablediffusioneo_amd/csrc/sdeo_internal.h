@@ -36,6 +36,21 @@ int sdeo_debug_read_stamps(int which, unsigned long long* out, int n);
 /* y = silu(x) on n fp16 elements: launch-floor probe for tools/launch_floor.py */
 int sdeo_debug_silu(void* y, const void* x, int64_t n, void* stream);
 
+/* op-level hooks of csrc/norm.hip (tests).
+ * groupnorm_path: what sdeo_groupnorm_nhwc_f16 launches for this shape, from the launcher's own selection: 0 = two launches
+ *   (statistics, apply), 256 / 1024 = the single-launch kernel with that many threads; -1, with sdeo_last_error set, for a shape the
+ *   launch rejects.  Host only, no device call.
+ * groupnorm_ld / layernorm_ld: sdeo_groupnorm_nhwc_f16 / sdeo_layernorm_f16 on channel blocks of wider buffers: row strides ldx / ldy
+ *   in elements (multiples of 8, >= c), as the networks' views pass them
+ * softmax_rows: p[r][0:cols] (fp16, row stride ldp) = softmax(s[r][0:cols] * scale) of fp32 scores (row stride lds): the VAE
+ *   AttnBlock's materialised-score path */
+int sdeo_debug_groupnorm_path(int n, int hw, int c, int groups);
+int sdeo_debug_groupnorm_ld_f16(void* y, int ldy, const void* x, int ldx, const float* gamma, const float* beta, int n, int hw, int c,
+                                int groups, float eps, int with_silu, void* workspace, void* stream);
+int sdeo_debug_layernorm_ld_f16(void* y, int ldy, const void* x, int ldx, const float* gamma, const float* beta, int rows, int c,
+                                float eps, void* stream);
+int sdeo_debug_softmax_rows(void* p, int ldp, const float* s, int lds, int rows, int cols, float scale, void* stream);
+
 /* op-level hooks for the LayerNorm fold (tests): the networks use these paths internally (csrc/net.hip build_attn).
  * fold: w_out = fp16(w * gamma) [rows][c], s_out[rows] = row sums of w_out, b_out[rows] = bias + w beta (bias may be NULL)
  * gemm_stats: sdeo_gemm_f16 (fp16 out) that also writes per-row (sum, sumsq) partials of y: stats fp32 [m][stats_ld][2];

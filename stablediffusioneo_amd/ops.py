@@ -23,16 +23,43 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
-def groupnorm_nhwc(x, gamma, beta, groups=32, eps=1e-5, swish=False):
-    """x: (N,H,W,C) fp16 contiguous; gamma/beta fp32 (C,)."""
+def _nhwc_ld(t, what):
+    """row (pixel) stride, in elements, of an (N,H,W,C) fp16 operand the GroupNorm kernels can address: a contiguous tensor or a
+    channel block of a wider contiguous NHWC buffer"""
+    n, h, w, _ = t.shape
+    ld = t.stride(2)
+    assert t.dtype == torch.float16 and t.stride(3) == 1 and (h == 1 or t.stride(1) == w * ld) and (n == 1 or t.stride(0) == h * w * ld), \
+        f"groupnorm: {what} must be fp16 NHWC with unit channel stride and densely stacked pixels (shape {tuple(t.shape)}, strides {t.stride()})"
+    return ld
+
+
+def groupnorm_path(n, hw, c, groups=32):
+    """What groupnorm_nhwc launches for an (n, hw, c) tensor, from the launcher's own selection: 0 = two launches (statistics, then
+    apply), 256 / 1024 = the single-launch kernel with that many threads.  Host only."""
     lib = _lib.load()
-    _need_cuda(x, gamma, beta)
+    r = lib.sdeo_debug_groupnorm_path(_i(n), _i(hw), _i(c), _i(groups))
+    if r < 0:
+        check(r, "groupnorm_path")
+    return r
+
+
+def groupnorm_nhwc(x, gamma, beta, groups=32, eps=1e-5, swish=False, out=None):
+    """x: (N,H,W,C) fp16; gamma/beta fp32 (C,).  x and out (optional destination) may be channel blocks of wider NHWC buffers:
+    the pixel stride is taken from .stride(2)."""
+    lib = _lib.load()
+    _need_cuda(x, gamma, beta, out)
     n, h, w, c = x.shape
-    assert x.dtype == torch.float16 and x.is_contiguous()
-    y = torch.empty_like(x)
     ws = _ws(lib.sdeo_groupnorm_workspace_bytes(_i(n), _i(h * w), _i(groups)), x.device)
-    check(lib.sdeo_groupnorm_nhwc_f16(ptr(y), ptr(x), ptr(gamma), ptr(beta), _i(n), _i(h), _i(w), _i(c), _i(groups),
-                                      _f(eps), _i(int(swish)), ptr(ws), cur_stream()), "groupnorm")
+    if out is None and x.is_contiguous():
+        assert x.dtype == torch.float16
+        y = torch.empty_like(x)
+        check(lib.sdeo_groupnorm_nhwc_f16(ptr(y), ptr(x), ptr(gamma), ptr(beta), _i(n), _i(h), _i(w), _i(c), _i(groups),
+                                          _f(eps), _i(int(swish)), ptr(ws), cur_stream()), "groupnorm")
+        return y
+    y = torch.empty((n, h, w, c), dtype=torch.float16, device=x.device) if out is None else out
+    assert y.shape == x.shape
+    check(lib.sdeo_debug_groupnorm_ld_f16(ptr(y), _i(_nhwc_ld(y, "out")), ptr(x), _i(_nhwc_ld(x, "x")), ptr(gamma), ptr(beta), _i(n),
+                                          _i(h * w), _i(c), _i(groups), _f(eps), _i(int(swish)), ptr(ws), cur_stream()), "groupnorm")
     return y
 
 
@@ -301,14 +328,33 @@ def gemm_geglu(x, w_interleaved, bias_interleaved=None, w8=None, out=None):
     return y
 
 
-def layernorm(x, gamma, beta, eps=1e-5):
+def layernorm(x, gamma, beta, eps=1e-5, out=None):
+    """x (rows, C) fp16.  x and out (optional destination) may be column blocks of wider buffers: the row stride is .stride(0)."""
     lib = _lib.load()
-    _need_cuda(x, gamma, beta)
+    _need_cuda(x, gamma, beta, out)
     rows, c = x.shape
-    assert x.is_contiguous()
-    y = torch.empty_like(x)
-    check(lib.sdeo_layernorm_f16(ptr(y), ptr(x), ptr(gamma), ptr(beta), _i(rows), _i(c), _f(eps), cur_stream()), "layernorm")
+    if out is None and x.is_contiguous():
+        y = torch.empty_like(x)
+        check(lib.sdeo_layernorm_f16(ptr(y), ptr(x), ptr(gamma), ptr(beta), _i(rows), _i(c), _f(eps), cur_stream()), "layernorm")
+        return y
+    y = torch.empty((rows, c), dtype=torch.float16, device=x.device) if out is None else out
+    assert y.shape == x.shape and x.dtype == torch.float16 and y.dtype == torch.float16 and x.stride(1) == 1 and y.stride(1) == 1
+    check(lib.sdeo_debug_layernorm_ld_f16(ptr(y), _i(y.stride(0)), ptr(x), _i(x.stride(0)), ptr(gamma), ptr(beta), _i(rows), _i(c),
+                                          _f(eps), cur_stream()), "layernorm")
     return y
+
+
+def softmax_rows(s, scale=1.0, out=None):
+    """fp16 softmax(s * scale) over the last dim of fp32 scores s (rows, cols): the VAE AttnBlock's materialised-score path.
+    s and out (optional destination) may be column blocks of wider buffers: the row stride is .stride(0)."""
+    lib = _lib.load()
+    _need_cuda(s, out)
+    rows, cols = s.shape
+    p = torch.empty((rows, cols), dtype=torch.float16, device=s.device) if out is None else out
+    assert s.dtype == torch.float32 and p.dtype == torch.float16 and p.shape == s.shape and s.stride(1) == 1 and p.stride(1) == 1
+    check(lib.sdeo_debug_softmax_rows(ptr(p), _i(p.stride(0)), ptr(s), _i(s.stride(0)), _i(rows), _i(cols), _f(scale), cur_stream()),
+          "softmax_rows")
+    return p
 
 
 def _rows_view(t, what):

@@ -41,34 +41,70 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", CASES)
-def test_conv_emits_groupnorm_partials(ops, case):
+def check_pair(ops, case, bias, eps=1e-5, x_scale=1.0, ref_dtype=torch.float32):
+    """[conv + partials] -> [normalise only] of one case under its forced tile: conv bits unchanged, deterministic, within the bound of
+    a torch GroupNorm (ref_dtype) of the conv's own fp16 output and next to the two-pass kernel.  Returns (y, yn, ref, slots)."""
     from stablediffusioneo_amd import _lib
     lib = _lib.load()
     tile, n, cin, h, w, cout, k, with_res = case
-    x = h16(randn((n, h, w, cin), 500 + tile)).to(DEV)
+    x = h16(randn((n, h, w, cin), 500 + tile) * x_scale).to(DEV)
     wt = h16(randn((cout, k, k, cin), 501) * (1.0 / (cin * k * k)) ** 0.5).to(DEV)
-    bias = (0.5 * randn((cout,), 502) + 0.3).to(DEV)           # a non-zero mean exercises the E[x^2] - E[x]^2 form
+    bias = bias.to(DEV)
     res = h16(randn((n, h, w, cout), 503)).to(DEV) if with_res else None
     gamma = (1.0 + 0.2 * randn((cout,), 504)).to(DEV)
     beta = (0.1 * randn((cout,), 505)).to(DEV)
     try:
         lib.sdeo_debug_force_gemm_plan(C.c_int(tile), C.c_int(1))
-        got = ops.conv2d_gn(x, wt, gamma, beta, bias=bias, res=res, eps=1e-5, swish=True)
+        got = ops.conv2d_gn(x, wt, gamma, beta, bias=bias, res=res, eps=eps, swish=True)
         assert got is not None, f"tile {tile}: the plan refused to emit partials for {case}"
         y, yn, slots = got
         y_plain = ops.conv2d_nhwc(x, wt, bias=bias, res=res)
-        got2 = ops.conv2d_gn(x, wt, gamma, beta, bias=bias, res=res, eps=1e-5, swish=True)
+        got2 = ops.conv2d_gn(x, wt, gamma, beta, bias=bias, res=res, eps=eps, swish=True)
     finally:
         lib.sdeo_debug_force_gemm_plan(C.c_int(-1), C.c_int(0))
     assert torch.equal(y, y_plain), "emitting the partials changed the conv's output"
     assert torch.equal(yn, got2[1]), "not deterministic"
-    ref = F.silu(F.group_norm(y.float().permute(0, 3, 1, 2), 32, gamma, beta, 1e-5)).permute(0, 2, 3, 1)
-    err = (yn.float() - ref).abs()
+    ref = F.silu(F.group_norm(y.to(ref_dtype).permute(0, 3, 1, 2), 32, gamma.to(ref_dtype), beta.to(ref_dtype), eps)).permute(0, 2, 3, 1)
+    err = (yn.to(ref_dtype) - ref).abs()
     tol = 2e-3 * ref.abs() + 3e-3
     assert bool((err <= tol).all()), f"{case}: slots {slots}, max err {float(err.max()):.3e}"
-    two_pass = ops.groupnorm_nhwc(y, gamma, beta, 32, 1e-5, True)
+    two_pass = ops.groupnorm_nhwc(y, gamma, beta, 32, eps, True)
     assert float((yn.float() - two_pass.float()).abs().max()) <= 4e-3
+    return y, yn, ref, slots
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_conv_emits_groupnorm_partials(ops, case):
+    cout = case[5]
+    check_pair(ops, case, 0.5 * randn((cout,), 502) + 0.3)     # a non-zero mean exercises the E[x^2] - E[x]^2 form
+
+
+@pytest.mark.parametrize("case", [CASES[0], CASES[2]], ids=["tile13-cpg10", "tile14-cpg40"])
+def test_partials_of_offset_groups(ops, case):
+    """a conv bias of 16 standard deviations of the conv's output (x ~ N(0, 1), unit-gain weights, plus an N(0, 1) residual: std
+    sqrt(2)), its sign alternating from group to group: |mean| / std = 16 in every group, inside the r <= 64 contract of the
+    (sum, sumsq) statistics.  fp64 reference, the bounds of this file."""
+    tile, cout, with_res = case[0], case[5], case[7]
+    assert tile in (13, 14) and with_res
+    sign = torch.tensor([1.0, -1.0]).repeat(16).repeat_interleave(cout // 32)
+    y, _, _, _ = check_pair(ops, case, 16.0 * 2.0 ** 0.5 * sign + 0.1 * randn((cout,), 502), ref_dtype=torch.float64)
+    yg = y.double().reshape(y.shape[0], -1, 32, cout // 32)
+    r = (yg.mean(dim=(1, 3)).abs() / yg.std(dim=(1, 3))).cpu()
+    assert float(r.min()) > 12 and float(r.max()) < 20, (float(r.min()), float(r.max()))     # the input is what the test claims
+
+
+def test_partials_of_small_variance(ops):
+    """the conv's output has std ~ 2e-3 (x scaled, no residual), variance ~ 4e-6: eps 1e-6 and eps 1e-5 give different outputs, each
+    checked against its own fp64 reference.  256 slots: the partials go through gn_fold_partials_kernel first."""
+    case = (25, 1, 64, 256, 128, 128, 3, False)
+    refs = {}
+    for eps in (1e-6, 1e-5):
+        y, _, refs[eps], slots = check_pair(ops, case, 2e-4 * randn((128,), 502), eps=eps, x_scale=2e-3, ref_dtype=torch.float64)
+        assert slots > 128
+        assert 1e-3 < float(y.float().std()) < 4e-3
+    gap = (refs[1e-5] - refs[1e-6]).abs()
+    bound = 2e-3 * torch.minimum(refs[1e-5].abs(), refs[1e-6].abs()) + 3e-3
+    assert float((gap > 10 * bound).double().mean()) > 0.5, "the two references must differ far beyond the bound"
 
 
 def test_plans_that_cannot_emit_are_refused(ops):
