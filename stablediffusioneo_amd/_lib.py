@@ -12,6 +12,7 @@ import re
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SDEO_LIB") or os.path.join(HERE, "libsdeo.so")     # SDEO_LIB: A/B of two builds on one device
 HEADER = os.path.join(os.path.dirname(HERE), "include", "sdeo.h")
+INTERNAL_HEADER = os.path.join(HERE, "csrc", "sdeo_internal.h")      # the private hooks of tools/ and tests
 
 _lib = None
 
@@ -41,15 +42,63 @@ class SdeoClipConfig(C.Structure):
                 ("ffn", C.c_int)]
 
 
-def declared_symbols(header: str = HEADER):
-    """Names of every function include/sdeo.h declares (used by the CPU export test)."""
-    txt = open(header).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(sdeo_[a-z0-9_]+)\s*\(", txt)))
-
-
 class SdeoError(RuntimeError):
     pass
+
+
+# The binding's description of the C boundary is the two headers themselves: parse_header reads every prototype and struct layout
+# out of them and load() types the library with the result.  A parser for these two files, not for C: the vocabulary is closed.
+_SCALARS = {"void": None, "int": C.c_int, "float": C.c_float, "size_t": C.c_size_t, "int32_t": C.c_int32, "int64_t": C.c_int64,
+            "unsigned long long": C.c_ulonglong}
+_DECL = re.compile(r"\s*(.*?)\s*\b(\w+)\s*(?:\[(\w*)\])?\s*")        # type, name, array length (None: not an array)
+
+
+def _ctype(decl, where):
+    """ctypes type of the C type `decl`.  Every pointer but a plain char* is c_void_p, and so is every handle: callers pass ptr(t),
+    byref(struct), ctypes arrays and None, and c_void_p takes all of them."""
+    base = " ".join(w for w in re.findall(r"\w+", decl) if w != "const")
+    if "*" in decl:
+        return C.c_char_p if base == "char" and decl.count("*") == 1 else C.c_void_p
+    if re.fullmatch(r"sdeo_\w*handle", base):
+        return C.c_void_p
+    if base not in _SCALARS:
+        raise SdeoError(f"{where}: the binding has no mapping for the type '{decl.strip()}'")
+    return _SCALARS[base]
+
+
+def parse_header(text: str):
+    """({function: (restype, [argtypes])}, {struct: [(field, scalar ctype, array length or None)]}) of a header's text"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    defines = dict(re.findall(r"^\s*#\s*define\s+(\w+)\s+(\d+)\s*$", text, re.M))
+    text = re.sub(r"^\s*#.*$|extern\s+\"C\"\s*\{", "", text, flags=re.M)
+    struct = r"typedef\s+struct\s+\w+\s*\{(.*?)\}\s*(\w+)\s*;"
+    structs = {}
+    for body, name in re.findall(struct, text, re.S):
+        fields = structs[name] = []
+        for stmt in filter(str.strip, body.split(";")):                  # `int a, b[8], c`: one type, several declarators
+            first = _DECL.fullmatch(stmt.split(",")[0])
+            ctype = _ctype(first.group(1), f"struct {name}")
+            for m in map(_DECL.fullmatch, stmt[first.end(1):].split(",")):
+                fields.append((m.group(2), ctype, None if m.group(3) is None else int(defines.get(m.group(3), m.group(3)))))
+    text = re.sub(struct + r"|typedef[^;{]*;|\}", "", text, flags=re.S)   # what is left: prototypes (and extern "C"'s brace)
+    protos = {}
+    for stmt in filter(str.strip, text.split(";")):
+        m = re.fullmatch(r"\s*(.*?)\b(sdeo_\w+)\s*\((.*)\)\s*", stmt, re.S)
+        if not m:
+            raise SdeoError(f"cannot read the declaration '{' '.join(stmt.split())}'")
+        name, params = m.group(2), [] if m.group(3).strip() == "void" else map(_DECL.fullmatch, m.group(3).split(","))
+        protos[name] = (_ctype(m.group(1), name), [C.c_void_p if p.group(3) is not None else _ctype(p.group(1), name) for p in params])
+    return protos, structs
+
+
+def prototypes(header: str):
+    """{name: (restype, [argtypes])} of every function the header at this path declares"""
+    return parse_header(open(header).read())[0]
+
+
+def declared_symbols(header: str = HEADER):
+    """Names of every function include/sdeo.h declares (used by the CPU export test)."""
+    return sorted(prototypes(header))
 
 
 def load(path: str = LIB_PATH):
@@ -64,23 +113,20 @@ def load(path: str = LIB_PATH):
     # HIP call fails with "no ROCm-capable device".  This host uses torch for device memory and streams, so torch goes first.
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    missing = [s for s in declared_symbols() if not hasattr(lib, s)]
+    missing = []
+    for header in (HEADER, INTERNAL_HEADER):
+        for name, (restype, argtypes) in prototypes(header).items():
+            if hasattr(lib, name):
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = restype, argtypes
+            else:
+                missing.append(name)
     if missing:
-        raise SdeoError(f"libsdeo.so does not export {missing}")
+        raise SdeoError(f"{path} does not export {missing}")
     want = int(re.search(r"#define\s+SDEO_ABI_VERSION\s+(\d+)", open(HEADER).read()).group(1))
     if lib.sdeo_version() != want:
         raise SdeoError(f"{path} reports ABI version {lib.sdeo_version()}, include/sdeo.h declares {want}: rebuild the library "
                         f"(operand semantics changed between versions)")
-    lib.sdeo_last_error.restype = C.c_char_p
-    for name in ("sdeo_groupnorm_workspace_bytes", "sdeo_conv2d_workspace_bytes", "sdeo_conv2d_pad_workspace_bytes", "sdeo_gemm_workspace_bytes",
-                 "sdeo_device_bytes", "sdeo_clip_device_bytes", "sdeo_hed_device_bytes"):
-        getattr(lib, name).restype = C.c_size_t
-    lib.sdeo_device_bytes.argtypes = [C.c_void_p]
-    lib.sdeo_clip_device_bytes.argtypes = [C.c_void_p]
-    lib.sdeo_hed_device_bytes.argtypes = [C.c_void_p]
-    lib.sdeo_tuned_gemm_plans_json.restype = C.c_char_p
-    lib.sdeo_create_ex.argtypes = [C.POINTER(SdeoConfig), C.POINTER(SdeoConfigExt), C.POINTER(C.c_void_p)]
-    lib.sdeo_create_ex.restype = C.c_int
     _lib = lib
     load_tuned_plans(lib)
     return lib
@@ -99,7 +145,7 @@ def load_tuned_plans(lib, path: str = TUNED_PLANS) -> int:
         return 0
     rows = json.load(open(path))
     for r in rows:
-        lib.sdeo_set_tuned_gemm_plan((C.c_int * 10)(*r[:10]), C.c_int(r[10]), C.c_int(r[11]))
+        lib.sdeo_set_tuned_gemm_plan((C.c_int * 10)(*r[:10]), r[10], r[11])
     return len(rows)
 
 

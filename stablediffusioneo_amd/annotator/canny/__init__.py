@@ -3,8 +3,6 @@
 `sdeo_canny_u8`.  There is no CPU path: without the library or a HIP device the call raises."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -15,7 +13,6 @@ from ..._lib import check, cur_stream, ptr
 class CannyDetector:
     def _run(self, img, low_threshold, high_threshold, want_edges: bool, want_control: bool):
         lib = _lib.load()
-        lib.sdeo_canny_workspace_bytes.restype = C.c_size_t
         if not torch.cuda.is_available():
             raise _lib.SdeoError("CannyDetector needs a HIP device (there is no CPU fallback)")
         t = torch.from_numpy(np.ascontiguousarray(img)) if isinstance(img, np.ndarray) else img
@@ -27,10 +24,10 @@ class CannyDetector:
         t = t.to("cuda").contiguous()
         edges = torch.empty((h, w), dtype=torch.uint8, device=t.device) if want_edges else None
         control = torch.empty((3, h, w), dtype=torch.float32, device=t.device) if want_control else None
-        nb = int(lib.sdeo_canny_workspace_bytes(C.c_int(h), C.c_int(w)))
+        nb = lib.sdeo_canny_workspace_bytes(h, w)
         ws = torch.empty(nb, dtype=torch.uint8, device=t.device)
-        check(lib.sdeo_canny_u8(ptr(t), C.c_int(h), C.c_int(w), C.c_int(c), C.c_float(low_threshold), C.c_float(high_threshold),
-                                ptr(edges), ptr(control), ptr(ws), C.c_size_t(nb), cur_stream()), "canny")
+        check(lib.sdeo_canny_u8(ptr(t), h, w, c, low_threshold, high_threshold, ptr(edges), ptr(control), ptr(ws), nb,
+                                cur_stream()), "canny")
         return edges, control
 
     def __call__(self, img, low_threshold, high_threshold):

@@ -8,8 +8,6 @@ through -- O(W + H) numbers that depend only on the sizes (OpenCV 4.3 `resize.cp
 keeps the image on the device from here through Canny to the control tensor.  There is no host resampling path."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -125,7 +123,7 @@ def resize_u8(img, dst_h: int, dst_w: int, interpolation: str):
     t = t.to("cuda").contiguous()
     out = torch.empty((dst_h, dst_w, c), dtype=torch.uint8, device=t.device)
     dev = lambda a: torch.from_numpy(a).to(t.device)
-    geo = (C.c_int(h), C.c_int(w), C.c_int(c), C.c_int(dst_h), C.c_int(dst_w))
+    geo = (h, w, c, dst_h, dst_w)
     if interpolation == "lanczos4":
         x0, ax = _lanczos4_axis(w, dst_w)
         y0, by = _lanczos4_axis(h, dst_h)

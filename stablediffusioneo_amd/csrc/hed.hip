@@ -12,6 +12,7 @@
 //                        output pixel, fp32 mean in numpy's order, fp64 sigmoid, truncation to uint8 (+ optional control tensor)
 #include "../../include/sdeo.h"
 #include "handle_common.h"
+#include "sdeo_internal.h"
 
 using namespace sdeo;
 

@@ -107,6 +107,11 @@ int sdeo_debug_mx_launches(sdeo_handle h);
 const char* sdeo_debug_fake_scribble_profile(const uint8_t* edges, int h, int w, uint8_t* scribble, float* control_chw, void* workspace,
                                              size_t workspace_bytes, void* stream);
 
+/* F.max_pool2d(x, 2, 2) on one NHWC fp16 image [h][w][c], c % 8 == 0 -> y [h / 2][w / 2][c] (csrc/hed.hip; tests) */
+int sdeo_debug_maxpool2x2_f16(void* y, const void* x, int h, int w, int c, void* stream);
+/* one HED detection with HIP events around every launch: the JSON array of sdeo_profile_end, "[]" on failure (tools/hed_time.py) */
+const char* sdeo_debug_hed_profile(sdeo_hed_handle h, const uint8_t* img_hwc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

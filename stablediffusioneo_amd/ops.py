@@ -9,9 +9,6 @@ import torch
 from . import _lib
 from ._lib import check, cur_stream, ptr
 
-_f = C.c_float
-_i = C.c_int
-
 
 def _need_cuda(*ts):
     for t in ts:
@@ -37,7 +34,7 @@ def groupnorm_path(n, hw, c, groups=32):
     """What groupnorm_nhwc launches for an (n, hw, c) tensor, from the launcher's own selection: 0 = two launches (statistics, then
     apply), 256 / 1024 = the single-launch kernel with that many threads.  Host only."""
     lib = _lib.load()
-    r = lib.sdeo_debug_groupnorm_path(_i(n), _i(hw), _i(c), _i(groups))
+    r = lib.sdeo_debug_groupnorm_path(n, hw, c, groups)
     if r < 0:
         check(r, "groupnorm_path")
     return r
@@ -49,17 +46,17 @@ def groupnorm_nhwc(x, gamma, beta, groups=32, eps=1e-5, swish=False, out=None):
     lib = _lib.load()
     _need_cuda(x, gamma, beta, out)
     n, h, w, c = x.shape
-    ws = _ws(lib.sdeo_groupnorm_workspace_bytes(_i(n), _i(h * w), _i(groups)), x.device)
+    ws = _ws(lib.sdeo_groupnorm_workspace_bytes(n, h * w, groups), x.device)
     if out is None and x.is_contiguous():
         assert x.dtype == torch.float16
         y = torch.empty_like(x)
-        check(lib.sdeo_groupnorm_nhwc_f16(ptr(y), ptr(x), ptr(gamma), ptr(beta), _i(n), _i(h), _i(w), _i(c), _i(groups),
-                                          _f(eps), _i(int(swish)), ptr(ws), cur_stream()), "groupnorm")
+        check(lib.sdeo_groupnorm_nhwc_f16(ptr(y), ptr(x), ptr(gamma), ptr(beta), n, h, w, c, groups, eps, int(swish), ptr(ws),
+                                          cur_stream()), "groupnorm")
         return y
     y = torch.empty((n, h, w, c), dtype=torch.float16, device=x.device) if out is None else out
     assert y.shape == x.shape
-    check(lib.sdeo_debug_groupnorm_ld_f16(ptr(y), _i(_nhwc_ld(y, "out")), ptr(x), _i(_nhwc_ld(x, "x")), ptr(gamma), ptr(beta), _i(n),
-                                          _i(h * w), _i(c), _i(groups), _f(eps), _i(int(swish)), ptr(ws), cur_stream()), "groupnorm")
+    check(lib.sdeo_debug_groupnorm_ld_f16(ptr(y), _nhwc_ld(y, "out"), ptr(x), _nhwc_ld(x, "x"), ptr(gamma), ptr(beta), n, h * w, c,
+                                          groups, eps, int(swish), ptr(ws), cur_stream()), "groupnorm")
     return y
 
 
@@ -70,8 +67,7 @@ def krsc_from_oihw(w_oihw_f32, cin_pad=None):
     o, i, r, s = w_oihw_f32.shape
     ip = cin_pad or ((i + 7) // 8) * 8
     y = torch.empty((o, r, s, ip), dtype=torch.float16, device=w_oihw_f32.device)
-    check(lib.sdeo_oihw_f32_to_krsc_f16(ptr(y), ptr(w_oihw_f32.contiguous()), _i(o), _i(i), _i(r), _i(s), _i(ip),
-                                        cur_stream()), "krsc")
+    check(lib.sdeo_oihw_f32_to_krsc_f16(ptr(y), ptr(w_oihw_f32.contiguous()), o, i, r, s, ip, cur_stream()), "krsc")
     return y
 
 
@@ -83,7 +79,7 @@ def quantize_fp8_rows(w):
     wd = w.reshape(rows, -1).clone().contiguous()
     q = torch.empty(wd.shape, dtype=torch.uint8, device=w.device)
     sc = torch.empty((rows,), dtype=torch.float32, device=w.device)
-    check(lib.sdeo_debug_quantize_fp8_rows(ptr(wd), ptr(q), ptr(sc), _i(rows), _i(wd.shape[1]), cur_stream()), "quantize_fp8_rows")
+    check(lib.sdeo_debug_quantize_fp8_rows(ptr(wd), ptr(q), ptr(sc), rows, wd.shape[1], cur_stream()), "quantize_fp8_rows")
     return q.reshape(w.shape), sc, wd.reshape(w.shape)
 
 
@@ -95,7 +91,7 @@ def quantize_mx(x):
     assert x.dtype == torch.float16 and x.is_contiguous() and cols % 32 == 0
     q = torch.empty((rows, cols), dtype=torch.uint8, device=x.device)
     sc = torch.empty((rows, cols // 32), dtype=torch.uint8, device=x.device)
-    check(lib.sdeo_debug_quantize_mx(ptr(q), ptr(sc), ptr(x), _i(rows), _i(cols), cur_stream()), "quantize_mx")
+    check(lib.sdeo_debug_quantize_mx(ptr(q), ptr(sc), ptr(x), rows, cols, cur_stream()), "quantize_mx")
     return q, sc
 
 
@@ -108,9 +104,8 @@ def gemm_mx(xq, xs, wq, ws, bias=None, res=None, act=0):
     assert k % 128 == 0 and wq.shape[1] == k and xs.shape == (m, k // 32) and ws.shape == (n, k // 32)
     y = torch.empty((m, n // 2 if act == 3 else n), dtype=torch.float16, device=xq.device)
     wsb = _ws(64 << 20, xq.device)
-    check(lib.sdeo_debug_gemm_mx_f16(ptr(y), _i(y.shape[1]), ptr(xq), ptr(xs), ptr(wq), ptr(ws), ptr(bias), ptr(res),
-                                     _i(res.stride(0) if res is not None else 0), _i(m), _i(n), _i(k), _i(act), ptr(wsb),
-                                     C.c_size_t(wsb.numel()), cur_stream()), "gemm_mx")
+    check(lib.sdeo_debug_gemm_mx_f16(ptr(y), y.shape[1], ptr(xq), ptr(xs), ptr(wq), ptr(ws), ptr(bias), ptr(res),
+                                     res.stride(0) if res is not None else 0, m, n, k, act, ptr(wsb), wsb.numel(), cur_stream()), "gemm_mx")
     return y
 
 
@@ -143,12 +138,12 @@ def conv2d_nhwc(x, w_krsc, bias=None, bias2=None, res=None, stride=1, upsample2x
     ho = (hv + 2 * pad - k) // stride + 1
     wo = (wv + 2 * pad - k) // stride + 1
     y = _out(out, (n, ho, wo, cout), torch.float16, x.device)
-    args = (_i(n), _i(h), _i(w), _i(cin), _i(cout), _i(k), _i(stride), _i(int(upsample2x)))
+    args = (n, h, w, cin, cout, k, stride, int(upsample2x))
     nb = lib.sdeo_conv2d_workspace_bytes(*args)
     ws = _ws(nb if w8 is None else max(nb, 64 << 20), x.device)
     _arm_fp8(lib, w8)
-    check(lib.sdeo_conv2d_nhwc_f16(ptr(y), ptr(x), ptr(w_krsc), ptr(bias), ptr(bias2), ptr(res), *args, _i(act), _f(scale),
-                                   ptr(ws), C.c_size_t(ws.numel()), cur_stream()), "conv2d")
+    check(lib.sdeo_conv2d_nhwc_f16(ptr(y), ptr(x), ptr(w_krsc), ptr(bias), ptr(bias2), ptr(res), *args, act, scale,
+                                   ptr(ws), ws.numel(), cur_stream()), "conv2d")
     return y
 
 
@@ -164,10 +159,10 @@ def conv2d_pad_nhwc(x, w_krsc, pad_before, pad_after, bias=None, bias2=None, res
     ho = (hv + pad_before + pad_after - k) // stride + 1
     wo = (wv + pad_before + pad_after - k) // stride + 1
     y = torch.empty((n, ho, wo, cout), dtype=torch.float16, device=x.device)
-    args = (_i(n), _i(h), _i(w), _i(cin), _i(cout), _i(k), _i(stride), _i(int(upsample2x)), _i(pad_before), _i(pad_after))
+    args = (n, h, w, cin, cout, k, stride, int(upsample2x), pad_before, pad_after)
     ws = _ws(lib.sdeo_conv2d_pad_workspace_bytes(*args), x.device)
-    check(lib.sdeo_conv2d_pad_nhwc_f16(ptr(y), ptr(x), ptr(w_krsc), ptr(bias), ptr(bias2), ptr(res), *args, _i(act), _f(scale),
-                                       ptr(ws), C.c_size_t(ws.numel()), cur_stream()), "conv2d_pad")
+    check(lib.sdeo_conv2d_pad_nhwc_f16(ptr(y), ptr(x), ptr(w_krsc), ptr(bias), ptr(bias2), ptr(res), *args, act, scale,
+                                       ptr(ws), ws.numel(), cur_stream()), "conv2d_pad")
     return y
 
 
@@ -188,9 +183,9 @@ def conv2d_gn(x, w_krsc, gamma, beta, bias=None, res=None, stride=1, upsample2x=
     pf = n * (ho * wo) * groups * 2 // 16 + n * groups * 2 + 1024           # tiles hold >= 32 rows: more than any plan needs
     part = torch.empty(pf, dtype=torch.float32, device=x.device)
     slots = C.c_int(0)
-    check(lib.sdeo_debug_conv2d_gn_f16(ptr(yn), ptr(y), ptr(x), ptr(w_krsc), ptr(bias), ptr(res), _i(n), _i(h), _i(w), _i(cin), _i(cout),
-                                       _i(k), _i(stride), _i(int(upsample2x)), ptr(gamma), ptr(beta), _i(groups), _f(eps), _i(int(swish)),
-                                       ptr(part), C.c_size_t(pf), C.byref(slots), cur_stream()), "conv2d_gn")
+    check(lib.sdeo_debug_conv2d_gn_f16(ptr(yn), ptr(y), ptr(x), ptr(w_krsc), ptr(bias), ptr(res), n, h, w, cin, cout, k, stride,
+                                       int(upsample2x), ptr(gamma), ptr(beta), groups, eps, int(swish), ptr(part), pf, C.byref(slots),
+                                       cur_stream()), "conv2d_gn")
     if slots.value == 0:
         return None
     return y, yn, slots.value
@@ -205,12 +200,12 @@ def gemm(x, w, bias=None, res=None, act=0, scale=1.0, out_f32=False, bias_per_ro
     n, k2 = w.shape
     assert k == k2 and x.stride(1) == 1 and w.stride(1) == 1
     y = _out(out, (m, n), torch.float32 if out_f32 else torch.float16, x.device)
-    nb = lib.sdeo_gemm_workspace_bytes(_i(m), _i(n), _i(k))
+    nb = lib.sdeo_gemm_workspace_bytes(m, n, k)
     ws = _ws(nb if w8 is None else max(nb, 64 << 20), x.device)
     _arm_fp8(lib, w8)
-    check(lib.sdeo_gemm_f16(ptr(y), _i(n), ptr(x), _i(x.stride(0)), ptr(w), _i(w.stride(0)), ptr(bias), ptr(res),
-                            _i(res.stride(0) if res is not None else 0), _i(m), _i(n), _i(k), _i(act), _f(scale),
-                            _i(int(out_f32)), _i(int(bias_per_row)), ptr(ws), C.c_size_t(ws.numel()), cur_stream()), "gemm")
+    check(lib.sdeo_gemm_f16(ptr(y), n, ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(res),
+                            res.stride(0) if res is not None else 0, m, n, k, act, scale, int(out_f32), int(bias_per_row), ptr(ws),
+                            ws.numel(), cur_stream()), "gemm")
     return y
 
 
@@ -223,8 +218,8 @@ def fold_layernorm(w, gamma, beta, bias=None):
     wo = torch.empty_like(w)
     s = torch.empty((rows,), dtype=torch.float32, device=w.device)
     b = torch.empty((rows,), dtype=torch.float32, device=w.device)
-    check(lib.sdeo_debug_fold_layernorm(ptr(wo), ptr(s), ptr(b), ptr(w), ptr(gamma), ptr(beta), ptr(bias), _i(rows), _i(c),
-                                        cur_stream()), "fold_layernorm")
+    check(lib.sdeo_debug_fold_layernorm(ptr(wo), ptr(s), ptr(b), ptr(w), ptr(gamma), ptr(beta), ptr(bias), rows, c, cur_stream()),
+          "fold_layernorm")
     return wo, s, b
 
 
@@ -236,7 +231,7 @@ def compose_proj(wp, bp, w2, b2):
     assert wp.shape == (c, c) and wp.dtype == torch.float16 and w2.dtype == torch.float16 and wp.is_contiguous() and w2.is_contiguous()
     wo = torch.empty((c, k2 + c), dtype=torch.float16, device=wp.device)
     bo = torch.empty((c,), dtype=torch.float32, device=wp.device)
-    check(lib.sdeo_debug_compose_proj(ptr(wo), ptr(bo), ptr(wp), ptr(bp), ptr(w2), ptr(b2), _i(c), _i(k2), cur_stream()), "compose_proj")
+    check(lib.sdeo_debug_compose_proj(ptr(wo), ptr(bo), ptr(wp), ptr(bp), ptr(w2), ptr(b2), c, k2, cur_stream()), "compose_proj")
     return wo, bo
 
 
@@ -251,12 +246,12 @@ def gemm_with_row_stats(x, w, bias=None, res=None):
     ld = max(1, (n + 31) // 32)
     stats = torch.zeros((m, ld, 2), dtype=torch.float32, device=x.device)
     strips = C.c_int(0)
-    check(lib.sdeo_debug_gemm_stats_f16(ptr(y), _i(n), ptr(x), _i(x.stride(0)), ptr(w), _i(w.stride(0)), ptr(bias), ptr(res),
-                                        _i(res.stride(0) if res is not None else 0), _i(m), _i(n), _i(k), ptr(stats), _i(ld),
-                                        C.byref(strips), cur_stream()), "gemm_stats")
+    check(lib.sdeo_debug_gemm_stats_f16(ptr(y), n, ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(res),
+                                        res.stride(0) if res is not None else 0, m, n, k, ptr(stats), ld, C.byref(strips),
+                                        cur_stream()), "gemm_stats")
     if strips.value == 0:
         y = gemm(x, w, bias=bias, res=res)
-        check(lib.sdeo_debug_row_stats_f16(ptr(stats), _i(ld), ptr(y), _i(n), _i(m), _i(n), cur_stream()), "row_stats")
+        check(lib.sdeo_debug_row_stats_f16(ptr(stats), ld, ptr(y), n, m, n, cur_stream()), "row_stats")
         return y, stats, 1
     return y, stats, strips.value
 
@@ -274,14 +269,14 @@ def gemm_res_rows(x, w, res, res_rows, bias=None, want_stats=False):
     ld = max(1, (n + 31) // 32)
     stats = torch.zeros((m, ld, 2), dtype=torch.float32, device=x.device) if want_stats else None
     strips = C.c_int(0)
-    ws = _ws(lib.sdeo_gemm_workspace_bytes(_i(m), _i(n), _i(k)), x.device)
-    check(lib.sdeo_debug_gemm_res_rows_f16(ptr(y), _i(n), ptr(x), _i(x.stride(0)), ptr(w), _i(w.stride(0)), ptr(bias), ptr(res),
-                                           _i(res.stride(0)), _i(res_rows), _i(m), _i(n), _i(k), ptr(stats), _i(ld), C.byref(strips),
-                                           ptr(ws), C.c_size_t(ws.numel()), cur_stream()), "gemm_res_rows")
+    ws = _ws(lib.sdeo_gemm_workspace_bytes(m, n, k), x.device)
+    check(lib.sdeo_debug_gemm_res_rows_f16(ptr(y), n, ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(res),
+                                           res.stride(0), res_rows, m, n, k, ptr(stats), ld, C.byref(strips), ptr(ws), ws.numel(),
+                                           cur_stream()), "gemm_res_rows")
     if not want_stats:
         return y
     if strips.value == 0:
-        check(lib.sdeo_debug_row_stats_f16(ptr(stats), _i(ld), ptr(y), _i(n), _i(m), _i(n), cur_stream()), "row_stats")
+        check(lib.sdeo_debug_row_stats_f16(ptr(stats), ld, ptr(y), n, m, n, cur_stream()), "row_stats")
         return y, stats, 1
     return y, stats, strips.value
 
@@ -293,11 +288,9 @@ def gemm_layernorm(x, stats, strips, w_folded, ln_s, bias_folded, act=0, eps=1e-
     m, k = x.shape
     n = w_folded.shape[0]
     y = torch.empty((m, n // 2 if act == 3 else n), dtype=torch.float16, device=x.device)
-    ws = _ws(lib.sdeo_gemm_workspace_bytes(_i(m), _i(n), _i(k)), x.device)
-    check(lib.sdeo_debug_gemm_ln_f16(ptr(y), _i(y.shape[1]), ptr(x), _i(x.stride(0)), ptr(w_folded), _i(w_folded.stride(0)),
-                                     ptr(ln_s), ptr(bias_folded), ptr(stats), _i(stats.shape[1]), _i(strips), _i(k),
-                                     _i(m), _i(n), _i(k), _i(act), _f(eps), ptr(ws), C.c_size_t(ws.numel()), cur_stream()),
-          "gemm_ln")
+    ws = _ws(lib.sdeo_gemm_workspace_bytes(m, n, k), x.device)
+    check(lib.sdeo_debug_gemm_ln_f16(ptr(y), y.shape[1], ptr(x), x.stride(0), ptr(w_folded), w_folded.stride(0), ptr(ln_s), ptr(bias_folded),
+                                     ptr(stats), stats.shape[1], strips, k, m, n, k, act, eps, ptr(ws), ws.numel(), cur_stream()), "gemm_ln")
     return y
 
 
@@ -322,9 +315,8 @@ def gemm_geglu(x, w_interleaved, bias_interleaved=None, w8=None, out=None):
     assert k == k2 and n % 32 == 0 and x.stride(1) == 1 and w_interleaved.stride(1) == 1
     y = _out(out, (m, n // 2), torch.float16, x.device)
     _arm_fp8(lib, w8)
-    check(lib.sdeo_gemm_f16(ptr(y), _i(n // 2), ptr(x), _i(x.stride(0)), ptr(w_interleaved), _i(w_interleaved.stride(0)),
-                            ptr(bias_interleaved), None, _i(0), _i(m), _i(n), _i(k), _i(3), _f(1.0), _i(0), _i(0), None,
-                            C.c_size_t(0), cur_stream()), "gemm_geglu")
+    check(lib.sdeo_gemm_f16(ptr(y), n // 2, ptr(x), x.stride(0), ptr(w_interleaved), w_interleaved.stride(0),
+                            ptr(bias_interleaved), None, 0, m, n, k, 3, 1.0, 0, 0, None, 0, cur_stream()), "gemm_geglu")
     return y
 
 
@@ -335,12 +327,12 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
     rows, c = x.shape
     if out is None and x.is_contiguous():
         y = torch.empty_like(x)
-        check(lib.sdeo_layernorm_f16(ptr(y), ptr(x), ptr(gamma), ptr(beta), _i(rows), _i(c), _f(eps), cur_stream()), "layernorm")
+        check(lib.sdeo_layernorm_f16(ptr(y), ptr(x), ptr(gamma), ptr(beta), rows, c, eps, cur_stream()), "layernorm")
         return y
     y = torch.empty((rows, c), dtype=torch.float16, device=x.device) if out is None else out
     assert y.shape == x.shape and x.dtype == torch.float16 and y.dtype == torch.float16 and x.stride(1) == 1 and y.stride(1) == 1
-    check(lib.sdeo_debug_layernorm_ld_f16(ptr(y), _i(y.stride(0)), ptr(x), _i(x.stride(0)), ptr(gamma), ptr(beta), _i(rows), _i(c),
-                                          _f(eps), cur_stream()), "layernorm")
+    check(lib.sdeo_debug_layernorm_ld_f16(ptr(y), y.stride(0), ptr(x), x.stride(0), ptr(gamma), ptr(beta), rows, c, eps,
+                                          cur_stream()), "layernorm")
     return y
 
 
@@ -352,7 +344,7 @@ def softmax_rows(s, scale=1.0, out=None):
     rows, cols = s.shape
     p = torch.empty((rows, cols), dtype=torch.float16, device=s.device) if out is None else out
     assert s.dtype == torch.float32 and p.dtype == torch.float16 and p.shape == s.shape and s.stride(1) == 1 and p.stride(1) == 1
-    check(lib.sdeo_debug_softmax_rows(ptr(p), _i(p.stride(0)), ptr(s), _i(s.stride(0)), _i(rows), _i(cols), _f(scale), cur_stream()),
+    check(lib.sdeo_debug_softmax_rows(ptr(p), p.stride(0), ptr(s), s.stride(0), rows, cols, scale, cur_stream()),
           "softmax_rows")
     return p
 
@@ -383,8 +375,7 @@ def attention(q, k, v, heads, tk=None, scale=None, causal=False, out=None):
     assert o.shape == q.shape
     ldq, ldk, ldv, ldo = _rows_view(q, "q"), _rows_view(k, "k"), _rows_view(v, "v"), _rows_view(o, "out")
     fn = lib.sdeo_attention_causal_f16 if causal else lib.sdeo_attention_f16
-    check(fn(ptr(o), _i(ldo), ptr(q), _i(ldq), ptr(k), _i(ldk), ptr(v), _i(ldv), _i(b), _i(heads),
-             _i(tq), _i(tk), _i(tks), _i(tksv), _i(d), _f(scale), cur_stream()), "attention")
+    check(fn(ptr(o), ldo, ptr(q), ldq, ptr(k), ldk, ptr(v), ldv, b, heads, tq, tk, tks, tksv, d, scale, cur_stream()), "attention")
     return o
 
 
@@ -401,8 +392,8 @@ def attention_q_shared(q, k, v, heads, tk=None, scale=None):
     assert b == 2 * qb and v.shape[0] == b and k.shape[2] == c and v.shape[2] == c
     o = torch.empty((b, tq, c), dtype=torch.float16, device=q.device)
     ldq, ldk, ldv, ldo = _rows_view(q, "q"), _rows_view(k, "k"), _rows_view(v, "v"), _rows_view(o, "out")
-    check(lib.sdeo_debug_attention_qb_f16(ptr(o), _i(ldo), ptr(q), _i(ldq), ptr(k), _i(ldk), ptr(v), _i(ldv), _i(b), _i(qb), _i(heads),
-                                          _i(tq), _i(tk), _i(tks), _i(tksv), _i(d), _f(scale), cur_stream()), "attention_q_shared")
+    check(lib.sdeo_debug_attention_qb_f16(ptr(o), ldo, ptr(q), ldq, ptr(k), ldk, ptr(v), ldv, b, qb, heads, tq, tk, tks, tksv,
+                                          d, scale, cur_stream()), "attention_q_shared")
     return o
 
 
@@ -411,7 +402,7 @@ def geglu(a):
     _need_cuda(a)
     rows, c2 = a.shape
     y = torch.empty((rows, c2 // 2), dtype=torch.float16, device=a.device)
-    check(lib.sdeo_geglu_f16(ptr(y), ptr(a), _i(rows), _i(c2 // 2), cur_stream()), "geglu")
+    check(lib.sdeo_geglu_f16(ptr(y), ptr(a), rows, c2 // 2, cur_stream()), "geglu")
     return y
 
 
@@ -420,7 +411,7 @@ def timestep_embedding(t, dim):
     _need_cuda(t)
     assert t.dtype == torch.int64
     out = torch.empty((t.shape[0], dim), dtype=torch.float16, device=t.device)
-    check(lib.sdeo_timestep_embedding_f16(ptr(out), ptr(t), _i(t.shape[0]), _i(dim), cur_stream()), "timestep_embedding")
+    check(lib.sdeo_timestep_embedding_f16(ptr(out), ptr(t), t.shape[0], dim, cur_stream()), "timestep_embedding")
     return out
 
 
@@ -433,8 +424,8 @@ def cfg_ddim_step(x, eps_c, eps_u, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_min
     x_prev = torch.empty_like(x)
     p0 = torch.empty_like(x) if want_pred_x0 else None
     fn = lib.sdeo_cfg_ddim_step_v if v_prediction else lib.sdeo_cfg_ddim_step
-    check(fn(ptr(x_prev), ptr(p0), ptr(x), ptr(eps_c), ptr(eps_u), ptr(noise), _f(cfg_scale), _f(a_t),
-             _f(a_prev), _f(sigma_t), _f(sqrt_one_minus_at), C.c_int64(x.numel()), cur_stream()),
+    check(fn(ptr(x_prev), ptr(p0), ptr(x), ptr(eps_c), ptr(eps_u), ptr(noise), cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at,
+             x.numel(), cur_stream()),
           "cfg_ddim_step_v" if v_prediction else "cfg_ddim_step")
     return x_prev, p0
 
@@ -445,7 +436,7 @@ def nchw_to_nhwc_f16(x, c_pad=None):
     n, c, h, w = x.shape
     cp = c_pad or c
     y = torch.empty((n, h, w, cp), dtype=torch.float16, device=x.device)
-    check(lib.sdeo_nchw_f32_to_nhwc_f16(ptr(y), _i(cp), ptr(x.contiguous().float()), _i(n), _i(c), _i(h * w), cur_stream()),
+    check(lib.sdeo_nchw_f32_to_nhwc_f16(ptr(y), cp, ptr(x.contiguous().float()), n, c, h * w, cur_stream()),
           "nchw_to_nhwc")
     return y
 
@@ -456,7 +447,7 @@ def nhwc_to_nchw_f32(x, c=None, scale=1.0):
     n, h, w, ld = x.shape
     c = c or ld
     y = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
-    check(lib.sdeo_nhwc_f16_to_nchw_f32(ptr(y), ptr(x), _i(ld), _i(n), _i(c), _i(h * w), _f(scale), cur_stream()),
+    check(lib.sdeo_nhwc_f16_to_nchw_f32(ptr(y), ptr(x), ld, n, c, h * w, scale, cur_stream()),
           "nhwc_to_nchw")
     return y
 
@@ -468,7 +459,7 @@ def maxpool2x2_nhwc(x):
     n, h, w, c = x.shape
     assert n == 1 and x.dtype == torch.float16 and x.is_contiguous()
     y = torch.empty((1, h // 2, w // 2, c), dtype=torch.float16, device=x.device)
-    check(lib.sdeo_debug_maxpool2x2_f16(ptr(y), ptr(x), _i(h), _i(w), _i(c), cur_stream()), "maxpool2x2")
+    check(lib.sdeo_debug_maxpool2x2_f16(ptr(y), ptr(x), h, w, c, cur_stream()), "maxpool2x2")
     return y
 
 
@@ -485,12 +476,11 @@ def hed_nms(x, t, s, z=True, blurred=False):
     lib = _lib.load()
     x = _u8_plane(x, "hed_nms")
     h, w = x.shape
-    lib.sdeo_nms_workspace_bytes.restype = C.c_size_t
-    nb = int(lib.sdeo_nms_workspace_bytes(_i(h), _i(w)))
+    nb = lib.sdeo_nms_workspace_bytes(h, w)
     ws = _ws(nb, x.device)
     zt = torch.empty((h, w), dtype=torch.uint8, device=x.device) if z else None
     bt = torch.empty((h, w), dtype=torch.float32, device=x.device) if blurred else None
-    check(lib.sdeo_nms_u8(ptr(x), _i(h), _i(w), _f(t), _f(s), ptr(zt), ptr(bt), ptr(ws), C.c_size_t(nb), cur_stream()), "hed_nms")
+    check(lib.sdeo_nms_u8(ptr(x), h, w, t, s, ptr(zt), ptr(bt), ptr(ws), nb, cur_stream()), "hed_nms")
     return zt, bt
 
 
@@ -500,12 +490,11 @@ def fake_scribble(edges, scribble=True, control=False):
     lib = _lib.load()
     edges = _u8_plane(edges, "fake_scribble")
     h, w = edges.shape
-    lib.sdeo_fake_scribble_workspace_bytes.restype = C.c_size_t
-    nb = int(lib.sdeo_fake_scribble_workspace_bytes(_i(h), _i(w)))
+    nb = lib.sdeo_fake_scribble_workspace_bytes(h, w)
     ws = _ws(nb, edges.device)
     st = torch.empty((h, w), dtype=torch.uint8, device=edges.device) if scribble else None
     ct = torch.empty((3, h, w), dtype=torch.float32, device=edges.device) if control else None
-    check(lib.sdeo_fake_scribble_u8(ptr(edges), _i(h), _i(w), ptr(st), ptr(ct), ptr(ws), C.c_size_t(nb), cur_stream()), "fake_scribble")
+    check(lib.sdeo_fake_scribble_u8(ptr(edges), h, w, ptr(st), ptr(ct), ptr(ws), nb, cur_stream()), "fake_scribble")
     return st, ct
 
 
@@ -520,5 +509,5 @@ def scribble_map(img, map=True, control=False):
     h, w, c = img.shape
     mt = torch.empty((h, w), dtype=torch.uint8, device=img.device) if map else None
     ct = torch.empty((3, h, w), dtype=torch.float32, device=img.device) if control else None
-    check(lib.sdeo_scribble_u8(ptr(img), _i(h), _i(w), _i(c), ptr(mt), ptr(ct), cur_stream()), "scribble_map")
+    check(lib.sdeo_scribble_u8(ptr(img), h, w, c, ptr(mt), ptr(ct), cur_stream()), "scribble_map")
     return mt, ct

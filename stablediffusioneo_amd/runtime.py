@@ -83,15 +83,14 @@ class _HandleRuntime:
         dims = (C.c_int64 * self._ndims)()
         nd = C.c_int()
         for i in range(self._sym("num_weights")(self.handle)):
-            self._call("weight_info", C.c_int(i), C.byref(name), dims, C.byref(nd))
+            self._call("weight_info", i, C.byref(name), dims, C.byref(nd))
             out[name.value.decode()] = tuple(int(dims[k]) for k in range(nd.value))
         return out
 
     def _load_ptr(self, name: str, data_ptr: int, shape, strict: bool = True):
         """fp32 contiguous data of `shape` at `data_ptr`, on the host or on this device"""
         dims = (C.c_int64 * max(len(shape), 1))(*shape)
-        self._call("load_weight", name.encode(), C.c_void_p(data_ptr), dims, C.c_int(len(shape)), C.c_int(int(strict)),
-                   detail=f"({name})")
+        self._call("load_weight", name.encode(), C.c_void_p(data_ptr), dims, len(shape), int(strict), detail=f"({name})")
 
     def load_tensor(self, name: str, t: torch.Tensor, strict: bool = True):
         t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
@@ -125,11 +124,11 @@ class SdeoRuntime(_HandleRuntime):
             check(self.lib.sdeo_enable_vae_encoder(self.handle), "enable_vae_encoder")
         self.weight_bits = int(weight_bits)
         if self.weight_bits != 16:
-            check(self.lib.sdeo_set_weight_precision(self.handle, C.c_int(self.weight_bits)), "set_weight_precision")
+            check(self.lib.sdeo_set_weight_precision(self.handle, self.weight_bits), "set_weight_precision")
         # act_bits = 8: the GEMMs of >= mx_min_rows rows (default 2048) run block-scaled fp8 x fp8 on the fp8 MFMA (sdeo.h)
         self.act_bits = int(act_bits)
         if self.act_bits != 16:
-            check(self.lib.sdeo_set_activation_precision(self.handle, C.c_int(self.act_bits), C.c_int(int(mx_min_rows))), "set_activation_precision")
+            check(self.lib.sdeo_set_activation_precision(self.handle, self.act_bits, int(mx_min_rows)), "set_activation_precision")
         self.n = self.h = self.w = 0
         self.n_controls = 13
         # bumped by every sdeo_configure: the library frees and re-plans its arenas / boundary buffers there, so a hipGraph
@@ -175,8 +174,6 @@ class SdeoRuntime(_HandleRuntime):
 
     def profile_end(self):
         import json
-        self.lib.sdeo_profile_end.restype = C.c_char_p
-        self.lib.sdeo_profile_end.argtypes = [C.c_void_p]
         return json.loads(self.lib.sdeo_profile_end(self.handle).decode())
 
     # ---------------------------------------------------------------- shapes
@@ -186,7 +183,7 @@ class SdeoRuntime(_HandleRuntime):
             self._graphs = None
             self.generation += 1
             self.n = self.h = self.w = 0            # a failed configure leaves the handle unconfigured
-            check(self.lib.sdeo_configure(self.handle, C.c_int(n), C.c_int(h), C.c_int(w)), "configure")
+            check(self.lib.sdeo_configure(self.handle, n, h, w), "configure")
             self.n, self.h, self.w = n, h, w
         return self
 
@@ -225,8 +222,8 @@ class SdeoRuntime(_HandleRuntime):
         if outs is None:
             outs = [torch.empty(s, dtype=torch.float32, device=self.device) for s in self.control_shapes()]
         arr = (C.c_void_p * 13)(*[o.data_ptr() for o in outs])
-        check(self.lib.sdeo_controlnet_forward(self.handle, ptr(x), ptr(hint), ptr(t), ptr(ctx), arr, C.c_int(flags),
-                                               cur_stream()), "controlnet_forward")
+        check(self.lib.sdeo_controlnet_forward(self.handle, ptr(x), ptr(hint), ptr(t), ptr(ctx), arr, flags, cur_stream()),
+              "controlnet_forward")
         return list(outs)
 
     def unet(self, x, t, ctx, control=None, scales=None, only_mid_control=False, flags: int = 0, out=None):
@@ -242,7 +239,7 @@ class SdeoRuntime(_HandleRuntime):
         eps = out if out is not None else torch.empty((self.n, u.out_channels, self.h, self.w), dtype=torch.float32,
                                                       device=self.device)
         check(self.lib.sdeo_unet_forward(self.handle, ptr(x), ptr(t), ptr(ctx), arr, self._scales(scales),
-                                         C.c_int(int(only_mid_control)), ptr(eps), C.c_int(flags), cur_stream()), "unet_forward")
+                                         int(only_mid_control), ptr(eps), flags, cur_stream()), "unet_forward")
         return eps
 
     def apply_model(self, x, hint, t, ctx, scales=None, only_mid_control=False, flags: int = 0, out=None):
@@ -256,7 +253,7 @@ class SdeoRuntime(_HandleRuntime):
         eps = out if out is not None else torch.empty((self.n, u.out_channels, self.h, self.w), dtype=torch.float32,
                                                       device=self.device)
         check(self.lib.sdeo_apply_model(self.handle, ptr(x), ptr(hint), ptr(t), ptr(ctx), self._scales(scales),
-                                        C.c_int(int(only_mid_control)), C.c_int(flags), ptr(eps), cur_stream()), "apply_model")
+                                        int(only_mid_control), flags, ptr(eps), cur_stream()), "apply_model")
         return eps
 
     def apply_model_graphed(self, x, t, scales=None, only_mid_control=False):
@@ -291,7 +288,7 @@ class SdeoRuntime(_HandleRuntime):
         embeddings of both networks for every step are computed once (`sdeo_set_timestep_table`).  Returns the number of rows."""
         ts = [int(t) for t in timesteps]
         arr = (C.c_int64 * len(ts))(*ts)
-        check(self.lib.sdeo_set_timestep_table(self.handle, arr, C.c_int(len(ts)), cur_stream()), "set_timestep_table")
+        check(self.lib.sdeo_set_timestep_table(self.handle, arr, len(ts), cur_stream()), "set_timestep_table")
         self._table_key = (self.generation, tuple(ts))      # whose schedule the table holds (captured graphs read it by address)
         return len(ts)
 
@@ -303,12 +300,10 @@ class SdeoRuntime(_HandleRuntime):
         (SDEO_STEP_V_PREDICTION)."""
         assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
         assert pred_x0 is None or (pred_x0.is_contiguous() and pred_x0.dtype == torch.float32 and pred_x0.shape == x.shape)
-        check(self.lib.sdeo_ddim_step(self.handle, ptr(x), ptr(pred_x0), C.c_int(int(row)), C.c_float(cfg_scale), C.c_float(a_t),
-                                      C.c_float(a_prev), C.c_float(sqrt_one_minus_at), self._scales(scales),
-                                      C.c_int(int(only_mid_control)), C.c_int((STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)
-                                              | (STEP_V_PREDICTION if v_prediction else 0)),
-                                      cur_stream()),
-              "ddim_step")
+        check(self.lib.sdeo_ddim_step(self.handle, ptr(x), ptr(pred_x0), int(row), cfg_scale, a_t, a_prev, sqrt_one_minus_at,
+                                      self._scales(scales), int(only_mid_control),
+                                      (STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)
+                                      | (STEP_V_PREDICTION if v_prediction else 0), cur_stream()), "ddim_step")
         return x
 
     def vae_decode(self, z, want_u8: bool = False):
@@ -320,7 +315,7 @@ class SdeoRuntime(_HandleRuntime):
             raise _lib.SdeoError(f"latent shape {tuple(z.shape)} does not match the configured {self.h}x{self.w}")
         img = torch.empty((b, v.out_ch, 8 * self.h, 8 * self.w), dtype=torch.float32, device=self.device)
         u8 = torch.empty((b, 8 * self.h, 8 * self.w, v.out_ch), dtype=torch.uint8, device=self.device) if want_u8 else None
-        check(self.lib.sdeo_vae_decode(self.handle, ptr(z), C.c_int(b), ptr(img), ptr(u8), cur_stream()), "vae_decode")
+        check(self.lib.sdeo_vae_decode(self.handle, ptr(z), b, ptr(img), ptr(u8), cur_stream()), "vae_decode")
         return (img, u8) if want_u8 else img
 
     def vae_encode(self, images=None, images_u8=None, noise=None, want_moments: bool = False):
@@ -348,7 +343,7 @@ class SdeoRuntime(_HandleRuntime):
             noise = self._f32(noise, (b, v.z_channels, self.h, self.w))
         z = torch.empty((b, v.z_channels, self.h, self.w), dtype=torch.float32, device=self.device)
         mom = torch.empty((b, 2 * v.z_channels, self.h, self.w), dtype=torch.float32, device=self.device) if want_moments else None
-        check(self.lib.sdeo_vae_encode(self.handle, ptr(images), ptr(images_u8), C.c_int(b), ptr(noise), ptr(z), ptr(mom),
+        check(self.lib.sdeo_vae_encode(self.handle, ptr(images), ptr(images_u8), b, ptr(noise), ptr(z), ptr(mom),
                                        cur_stream()), "vae_encode")
         return (z, mom) if want_moments else z
 
@@ -403,7 +398,7 @@ class ClipRuntime(_HandleRuntime):
         check(self.lib.sdeo_clip_create(C.byref(self._cfg), C.byref(self.handle)), "sdeo_clip_create")
         self.variant = None if variant is None else (int(variant[0]), int(variant[1]))
         if self.variant is not None:
-            self._call("set_variant", C.c_int(self.variant[0]), C.c_int(self.variant[1]))
+            self._call("set_variant", self.variant[0], self.variant[1])
         self.batch = 0
         self.generation = 0          # bumped by every re-plan of the activation buffers (see SdeoRuntime.generation)
 
@@ -429,7 +424,7 @@ class ClipRuntime(_HandleRuntime):
         if batch != self.batch:
             self.generation += 1
             self.batch = 0
-            check(self.lib.sdeo_clip_configure(self.handle, C.c_int(batch)), "sdeo_clip_configure")
+            check(self.lib.sdeo_clip_configure(self.handle, batch), "sdeo_clip_configure")
             self.batch = batch
         return self
 
@@ -445,7 +440,7 @@ class ClipRuntime(_HandleRuntime):
             out = torch.empty(shape, dtype=torch.float32, device=self.device)
         elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
             raise _lib.SdeoError(f"encode: out must be a contiguous fp32 tensor of shape {shape}")
-        check(self.lib.sdeo_clip_encode(self.handle, ptr(tok), C.c_int(self.batch), ptr(out), cur_stream()), "sdeo_clip_encode")
+        check(self.lib.sdeo_clip_encode(self.handle, ptr(tok), self.batch, ptr(out), cur_stream()), "sdeo_clip_encode")
         return out
 
 
@@ -477,7 +472,7 @@ class HedRuntime(_HandleRuntime):
     def configure(self, height: int, width: int):
         if (height, width) != self.size:
             self.size = (0, 0)
-            check(self.lib.sdeo_hed_configure(self.handle, C.c_int(height), C.c_int(width)), "sdeo_hed_configure")
+            check(self.lib.sdeo_hed_configure(self.handle, height, width), "sdeo_hed_configure")
             self.size = (height, width)
         return self
 

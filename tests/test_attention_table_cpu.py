@@ -24,7 +24,6 @@ REJECTED = (104, 112, 136, 144)
 def lib():
     build.build(verbose=False)
     lib = _lib.load()
-    lib.sdeo_debug_attention_kernel_name.restype = C.c_char_p
     return lib
 
 

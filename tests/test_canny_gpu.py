@@ -103,7 +103,6 @@ def test_canny_is_graph_capturable():
     from oracle import canny_oracle as O
     from stablediffusioneo_amd import _lib
     lib = _lib.load()
-    lib.sdeo_canny_workspace_bytes.restype = C.c_size_t
     H, W = 160, 224
     rng = np.random.default_rng(5)
     from scipy import ndimage

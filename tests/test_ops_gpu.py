@@ -244,7 +244,6 @@ def test_conv2d_every_halo_tile(ops, tile, sk):
     import ctypes as C
     from stablediffusioneo_amd import _lib
     lib = _lib.load()
-    lib.sdeo_debug_conv2d_kernel_name.restype = C.c_char_p
     ph, pw, bn, nmw = HALO_TILES[tile][:4]
     kname = "conv3x3_halo_kernel<" + ",".join(str(v) for v in HALO_TILES[tile]) + ">"
     try:
@@ -272,7 +271,6 @@ def test_halo_plan_falls_back_when_ineligible(ops):
     import ctypes as C
     from stablediffusioneo_amd import _lib
     lib = _lib.load()
-    lib.sdeo_debug_conv2d_kernel_name.restype = C.c_char_p
     try:
         lib.sdeo_debug_force_gemm_plan(C.c_int(13), C.c_int(1))
         for (n, cin, h, w, cout, k, stride, ups) in [(2, 320, 32, 32, 320, 3, 2, 0), (1, 128, 12, 20, 64, 3, 1, 0), (2, 960, 16, 16, 320, 1, 1, 0),

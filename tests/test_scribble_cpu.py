@@ -24,8 +24,6 @@ def test_library_exports_scribble_symbols(lib):
 
 
 def test_workspace_sizes(lib):
-    lib.sdeo_nms_workspace_bytes.restype = ctypes.c_size_t
-    lib.sdeo_fake_scribble_workspace_bytes.restype = ctypes.c_size_t
     assert lib.sdeo_nms_workspace_bytes(5, 40) >= 5 * 40 * 4             # the fp32 blurred plane
     assert lib.sdeo_fake_scribble_workspace_bytes(5, 40) >= 5 * 40 * 5       # + the uint8 nms map
 

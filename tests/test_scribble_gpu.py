@@ -115,7 +115,6 @@ def test_fake_scribble_is_capturable(ops, lib):
     x = dev(xa)
     sc = torch.zeros((H, W), dtype=torch.uint8, device="cuda")
     ct = torch.zeros((3, H, W), dtype=torch.float32, device="cuda")
-    lib.sdeo_fake_scribble_workspace_bytes.restype = C.c_size_t
     nb = int(lib.sdeo_fake_scribble_workspace_bytes(H, W))
     ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
     s = torch.cuda.Stream()

@@ -3,7 +3,6 @@
 blocks of one [B][T][3C] buffer, "cross" = k | v halves of a row-padded [B][TkS][2C] context buffer.  No kernel here is new: each row
 names the instantiation it selects, which tests/test_attention_gpu.py already runs at other shapes, and is held to the same fp64
 reference and the same per-kernel bound (|err| <= 3e-3 + 3e-3 |ref|)."""
-import ctypes
 
 import pytest
 import torch
@@ -30,7 +29,6 @@ def test_sd21_attention_shape(case):
     from stablediffusioneo_amd import _lib, ops
     b, h, tq, tk, d, causal, form, name = case
     fn = _lib.load().sdeo_debug_attention_kernel_name
-    fn.restype = ctypes.c_char_p
     assert fn(b, h, tq, tk, d, causal).decode() == name and name in {c[7] for c in A.CASES}
     c = h * d
     q, k, v = A.operands(case)

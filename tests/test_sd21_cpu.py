@@ -1,7 +1,6 @@
 """CPU-side checks of the SD-2.x support: the new entry points, the cldm_v21 parameter inventory against the reference constructors
 (tests/golden/manifest_sd21.json), the v-prediction update against the reference sampler's own trajectory (tests/golden/sampler_v.npz)
 and the attention kernels the 2.x shapes select (none that the attention tests do not already run)."""
-import ctypes
 import json
 import os
 
@@ -111,7 +110,6 @@ def test_sd21_attention_shapes_select_tested_kernels(lib):
     from tests.attention_cases import CASES
     tested = {c[7] for c in CASES}
     fn = lib.sdeo_debug_attention_kernel_name
-    fn.restype = ctypes.c_char_p
     assert len(SD21_ATTENTION) == 17
     for b, h, tq, tk, d, causal in SD21_ATTENTION:
         name = fn(b, h, tq, tk, d, causal)

@@ -31,7 +31,6 @@ def plan_sweep(lib, problem, num_tiles):
     """[[tile, split-K] or [tile, split-K, kernel name] ...] of one problem for force_tile in -1 .. num_tiles - 1 (outer) x
     force_splitk in FORCE_SPLITK (inner).  problem = ["conv", n, h, w, cin, cout, ksize, stride, ups, act, fp8] or
     ["gemm", m, n, k, act, fp8]; the name (convs only) is that of the fp16, act 0 launch of the shape, as the query takes it."""
-    lib.sdeo_debug_conv2d_kernel_name.restype = C.c_char_p
     kind, args = problem[0], [C.c_int(v) for v in problem[1:]]
     out = []
     try:

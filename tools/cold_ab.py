@@ -51,7 +51,6 @@ CONVS = [(2, 8, 8, 1280, 1280), (2, 16, 16, 1280, 1280), (2, 64, 64, 320, 320), 
 DMA = [0, 1, 2, 5, 6, 7, 9, 10, 11, 12, 19, 20, 21, 26, 27, 28, 29, 30, 31, 32, 33, 41, 42, 43, 44, 45, 46, 47, 48]
 HALO = [13, 14, 15, 16, 22, 23, 34, 35, 37, 38]
 name = lib.sdeo_debug_conv2d_kernel_name
-name.restype = C.c_char_p
 
 
 def run(label, fn, tiles, sks):

@@ -6,7 +6,6 @@ The detection is captured once in a hipGraph; the figure is the median over `ite
 eager detection with events around every launch (sdeo_debug_hed_profile) is printed as the per-kernel table.  FLOPs are algorithmic:
 2 M N K per conv (K counting the three real input channels of the first conv) and 2 H W C per side projection."""
 import argparse
-import ctypes as C
 import json
 import os
 import statistics
@@ -58,7 +57,6 @@ def main():
         times.append(e0.elapsed_time(e1))
     med = statistics.median(times)
     fn = rt.lib.sdeo_debug_hed_profile
-    fn.restype = C.c_char_p
     prof = json.loads(fn(rt.handle, _lib.ptr(img), _lib.cur_stream()).decode())
     flops = sum(r["flops"] for r in prof)
     kern_ms = sum(r["total_ms"] for r in prof)

@@ -54,7 +54,6 @@ for (n, h, w, cin, cout) in SHAPES:
         lib.sdeo_debug_force_gemm_plan(C.c_int(tile), C.c_int(sk))
         try:
             name = lib.sdeo_debug_conv2d_kernel_name
-            name.restype = C.c_char_p
             kn = name(C.c_int(n), C.c_int(h), C.c_int(w), C.c_int(cin), C.c_int(cout), C.c_int(3), C.c_int(1), C.c_int(0)).decode()
             try:
                 conv_us = graph_us(lambda: ops.conv2d_nhwc(x, wt, bias=bias))

@@ -32,7 +32,6 @@ def main():
     x = torch.from_numpy(band_image(H, W)).cuda()
     sc = torch.empty((H, W), dtype=torch.uint8, device="cuda")
     ct = torch.empty((3, H, W), dtype=torch.float32, device="cuda")
-    lib.sdeo_fake_scribble_workspace_bytes.restype = C.c_size_t
     nb = int(lib.sdeo_fake_scribble_workspace_bytes(H, W))
     ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
     args = (_lib.ptr(x), H, W, _lib.ptr(sc), _lib.ptr(ct), _lib.ptr(ws), C.c_size_t(nb))
@@ -61,7 +60,6 @@ def main():
         times.append(e0.elapsed_time(e1))
     med = statistics.median(times)
     fn = lib.sdeo_debug_fake_scribble_profile
-    fn.restype = C.c_char_p
     prof = json.loads(fn(*args, _lib.cur_stream()).decode())
     kern_ms = sum(r["total_ms"] for r in prof) or 1.0
     print(f"{'kernel':<32} {'launches':>8} {'ms':>9} {'share':>6}")
