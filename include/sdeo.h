@@ -131,6 +131,14 @@ int sdeo_cfg_ddim_step_v(float* x_prev, float* pred_x0, const float* x, const fl
                          const float* noise, float cfg_scale, float a_t, float a_prev, float sigma_t,
                          float sqrt_one_minus_at, int64_t n, void* stream);
 
+/* CFG + one linear-multistep update on fp32 latents: D as pred_x0 of sdeo_cfg_ddim_step(_v) (flags & SDEO_STEP_V_PREDICTION),
+ * x_next = k_x x + k_d D + k_p d(on entry); d receives D.  m_u may be NULL; d may be NULL only when k_p == 0.
+ * DPM-Solver++(2M) (Lu et al. 2022) with alpha = sqrt(a), sigma = sqrt(1 - a), lambda = ln(alpha / sigma), h = lambda_next - lambda_t,
+ * phi = -expm1(-h), r = h_prev / h:  k_x = sigma_next / sigma_t, k_d = alpha_next phi (1 + 1 / (2r)), k_p = -alpha_next phi / (2r);
+ * first order: k_d = alpha_next phi, k_p = 0 (the eta = 0 DDIM step).  The host computes the coefficients; the kernel never sees lambda. */
+int sdeo_cfg_dpmpp_2m_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, float cfg_scale, float a_t,
+                           float sqrt_one_minus_at, float k_x, float k_d, float k_p, int flags, int64_t n, void* stream);
+
 /* Canny edge map: replaces `cv2.Canny(img, low_threshold, high_threshold)` of annotator/canny/__init__.py:4-6
  * (aperture 3, L1 gradient magnitude; called at canny2image_torch.py:33 on the HWC3 uint8 image) and the control preparation of
  * canny2image_torch.py:34-38.  img_hwc: device uint8 [h][w][c], c in 1..4.  edges (optional): device uint8 [h][w], 0 / 255.
@@ -274,6 +282,12 @@ int sdeo_set_timestep_table(sdeo_handle h, const int64_t* host_timesteps, int co
 #define SDEO_STEP_V_PREDICTION 64
 int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
                    float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream);
+
+/* the fused CFG-pair step, as sdeo_ddim_step with that update: same flags, same caches, same table rows; capturable.
+ * x <- k_x x + k_d D + k_p d(on entry), d <- D (see sdeo_cfg_dpmpp_2m_step); the caller owns d [n/2][4][h][w] fp32 (NULL only when
+ * k_p == 0).  Bit-identical to sdeo_apply_model on [x; x] followed by sdeo_cfg_dpmpp_2m_step. */
+int sdeo_dpmpp_2m_step(sdeo_handle h, float* x, float* d, int table_row, float cfg_scale, float a_t, float sqrt_one_minus_at,
+                       float k_x, float k_d, float k_p, const float* host_control_scales, int only_mid_control, int flags, void* stream);
 
 /* decode_first_stage: z/scale_factor -> post_quant_conv -> Decoder (model.py:619-652).
  * z [n][4][h][w] fp32 NCHW -> images [n][3][8h][8w] fp32 NCHW in [-1,1]; images_u8 (optional, may be NULL)

@@ -42,19 +42,23 @@ def _default_canny():
 
 class hackathon():
 
-    def initialize(self, weights="synthetic:0", config="sd15", apply_canny=None, text_encoder=None, vae_encoder=False):
+    def initialize(self, weights="synthetic:0", config="sd15", apply_canny=None, text_encoder=None, vae_encoder=False, sampler="ddim"):
         """text_encoder: None = `synthetic_text_encoder` (seeded stand-in contexts); "clip:<tokenizer dir>" = the
         FrozenCLIPEmbedder mirror on the HIP path (weights from the same source as the UNet's: synthetic seed or the
         checkpoint's `cond_stage_model.transformer.text_model.*`); bare "clip" is accepted only with synthetic weights (the
         tokenizer is then the crc32 stand-in, which is meaningless next to real weights); or any callable(prompts) ->
         (B, 77, context_dim) tensor.  config "sd21" / "sd21v" (and "tiny21" / "tiny21v") select the SD-2.x layout (eps / v-prediction);
         their text encoder is "openclip[:<tokenizer dir>]", the FrozenOpenCLIPEmbedder mirror (penultimate layer, as cldm_v21.yaml), under
-        the same rules as "clip".  vae_encoder=True also builds the VAE encoder, which `process(init_image=...)` (img2img) needs."""
+        the same rules as "clip".  vae_encoder=True also builds the VAE encoder, which `process(init_image=...)` (img2img) needs.
+        sampler: "ddim" (the reference's DDIMSampler) or "dpmpp_2m" (DPM-Solver++(2M) on a log-SNR grid, `cldm/dpm_solver.py`: a
+        deterministic second-order solver meant for about half of DDIM's step count; `process(..., eta != 0)` raises with it)."""
         self.apply_canny = apply_canny or _default_canny()
-        return self._init_model(weights, config, text_encoder, vae_encoder)
+        return self._init_model(weights, config, text_encoder, vae_encoder, sampler=sampler)
 
-    def _init_model(self, weights, config, text_encoder, vae_encoder=False):
-        """text encoder, ControlLDM and DDIM sampler of `initialize` (shared with hed2image)"""
+    def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim"):
+        """text encoder, ControlLDM and sampler of `initialize` (shared with hed2image)"""
+        if sampler not in ("ddim", "dpmpp_2m"):
+            raise ValueError(f'sampler {sampler!r}: "ddim" or "dpmpp_2m"')
         if isinstance(text_encoder, str) and text_encoder.split(":")[0] in ("clip", "openclip"):
             from .ldm.modules.encoders.modules import FrozenCLIPEmbedder, FrozenOpenCLIPEmbedder
             kind = text_encoder.split(":")[0]
@@ -84,7 +88,11 @@ class hackathon():
         else:
             from .cldm.model import load_state_dict
             self.model.load_state_dict(load_state_dict(weights, location="cuda"))
-        self.ddim_sampler = DDIMSampler(self.model)
+        if sampler == "dpmpp_2m":
+            from .cldm.dpm_solver import DPMSolverSampler
+            self.ddim_sampler = DPMSolverSampler(self.model)     # (the attribute keeps the reference's name whichever sampler it holds)
+        else:
+            self.ddim_sampler = DDIMSampler(self.model)
         return self
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, ddim_steps, guess_mode,
@@ -139,7 +147,7 @@ class hackathon():
 
     def _img2img(self, init_image, image_resolution, hw, num_samples, cond, un_cond, ddim_steps, eta, scale, denoise_strength):
         """upstream `scripts/img2img.py`: init_latent = get_first_stage_encoding(encode_first_stage(init_image)); t_enc steps of
-        stochastic_encode; DDIMSampler.decode from t_enc (the per-step p_sample_ddim path)."""
+        stochastic_encode; the sampler's decode from t_enc (the per-step path of whichever sampler `initialize` selected)."""
         t_enc = int(denoise_strength * ddim_steps)
         if not (denoise_strength >= 0.0 and t_enc < ddim_steps):
             raise ValueError(f"denoise_strength {denoise_strength}: t_enc = int(strength * steps) must lie in [0, {ddim_steps})")

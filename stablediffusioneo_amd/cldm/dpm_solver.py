@@ -1,0 +1,260 @@
+"""DPM-Solver++(2M) (Lu et al. 2022) with the surface of `DDIMSampler`: a deterministic second-order multistep solver of the
+probability-flow ODE in the data-prediction form, on a grid uniform in log-SNR (or on DDIM's uniform-t grid).
+
+With alpha = sqrt(a), sigma = sqrt(1 - a), lambda = ln(alpha / sigma), a step from a_t to a_next has h = lambda_next - lambda_t > 0,
+phi = -expm1(-h), and D the CFG-combined data prediction (the pred_x0 of the DDIM kernels):
+
+    first order   x_next = (sigma_next / sigma_t) x + alpha_next phi D                       (the eta = 0 DDIM step)
+    second order  x_next = (sigma_next / sigma_t) x + alpha_next phi [(1 + 1/(2r)) D - (1/(2r)) D_prev],   r = h_prev / h
+
+The host folds all of it into three fp64 coefficients per step, x_next = k_x x + k_d D + k_p D_prev; the device side
+(`sdeo_cfg_dpmpp_2m_step`, `sdeo_dpmpp_2m_step`) never sees lambda.  The only state next to the latent is one fp32 tensor, D_prev.
+
+The loop has the shape of `DDIMSampler._loop_graphed`: step 1 runs eagerly (it fills the runtime's hint / context caches), steps 2..S are
+replayed from a captured graph with the per-step coefficients baked in; what does not qualify (mask, callbacks, no ControlNet hint on
+one half, scale == 1, a model without a runtime) runs one step at a time.  The switches are ddim_hacked's (SDEO_GRAPH,
+SDEO_LOOP_GRAPH, SDEO_LOOP_GRAPH_STEPS)."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import ops
+from . import ddim_hacked as dh
+from .ddim_hacked import DDIMSampler, make_ddim_timesteps
+
+_DETERMINISTIC = "DPM-Solver++(2M) is a deterministic ODE solver: {} is not available (use DDIMSampler)"
+
+
+def log_snr(alphas_cumprod):
+    """lambda = ln(alpha / sigma) = (ln a - ln(1 - a)) / 2, fp64"""
+    a = np.asarray(alphas_cumprod, dtype=np.float64)
+    return 0.5 * (np.log(a) - np.log1p(-a))
+
+
+def make_logsnr_timesteps(alphas_cumprod, S):
+    """The S timesteps (decreasing, from T - 1) at which an S-step solver on a grid uniform in log-SNR evaluates the model: S + 1 points
+    uniform in lambda from lambda(a[T-1]) to lambda(a[0]), each rounded to the integer timestep with the nearest lambda; where rounding
+    collides (towards t = 0, where lambda moves fastest) the earlier point is pushed one timestep up.  The point after the last entry is
+    t = 0: the last step lands on a[0], as DDIM's alphas_prev[0] does."""
+    lam = log_snr(alphas_cumprod)
+    T = lam.shape[0]
+    if not 1 <= S < T:
+        raise ValueError(f"{S} steps on a schedule of {T} timesteps")
+    tau = [int(np.argmin(np.abs(lam - target))) for target in np.linspace(lam[T - 1], lam[0], S + 1)]
+    for k in range(S, 0, -1):
+        tau[k - 1] = max(tau[k - 1], tau[k] + 1)
+    if tau[0] != T - 1:
+        raise ValueError(f"{S} steps do not fit this schedule without leaving it (first timestep {tau[0]})")
+    return np.asarray(tau[:S], dtype=np.int64)
+
+
+def multistep_coefficients(alphas, alphas_next, lower_order_final=True):
+    """(k_x, k_d, k_p) fp64 arrays of a run of steps a_t -> a_next that starts without history: the first step is first order, the last
+    one too when lower_order_final (and there is more than one step)."""
+    a_t, a_n = np.asarray(alphas, dtype=np.float64), np.asarray(alphas_next, dtype=np.float64)
+    h = log_snr(a_n) - log_snr(a_t)
+    assert (h > 0).all(), "every step must lower the noise level"
+    phi = -np.expm1(-h)
+    k_x = np.sqrt((1.0 - a_n) / (1.0 - a_t))
+    k_d = np.sqrt(a_n) * phi
+    k_p = np.zeros_like(k_d)
+    n = h.shape[0]
+    for k in range(1, n):
+        if lower_order_final and k == n - 1:
+            continue
+        inv_2r = h[k] / (2.0 * h[k - 1])          # 1 / (2r), r = h_prev / h
+        k_p[k] = -k_d[k] * inv_2r
+        k_d[k] = k_d[k] * (1.0 + inv_2r)
+    return k_x, k_d, k_p
+
+
+class DPMSolverSampler(object):
+    def __init__(self, model, discretize="logsnr", lower_order_final=True, **kwargs):
+        super().__init__()
+        if discretize not in ("logsnr", "uniform"):
+            raise NotImplementedError(f'There is no discretization method called "{discretize}" (logsnr, uniform)')
+        self.model = model
+        self.ddpm_num_timesteps = model.num_timesteps
+        self.discretize = discretize
+        self.lower_order_final = bool(lower_order_final)
+        self._pair = DDIMSampler(model)        # the fused cond / uncond forward and its conditioning cache are DDIM's (_eps_pair)
+        self._schedule_key = None
+        self._loop_key = None
+
+    # ------------------------------------------------------------------------------------------ schedule
+    def make_schedule(self, ddim_num_steps, ddim_eta=0., verbose=True):
+        """Host fp64 arrays, one entry per step in the order the loop takes them: timesteps (decreasing), alphas (a_t), alphas_next,
+        k_x / k_d / k_p.  Cached like `DDIMSampler.make_schedule`, by the arguments and the identity of the model's schedule."""
+        if ddim_eta != 0.:
+            raise NotImplementedError(_DETERMINISTIC.format(f"eta = {ddim_eta}"))
+        ac = self.model.alphas_cumprod
+        fp = (id(ac), int(getattr(ac, "_version", 0)), int(ac.data_ptr()) if isinstance(ac, torch.Tensor) else 0, tuple(ac.shape))
+        key = (int(ddim_num_steps), self.discretize, self.lower_order_final, id(self.model), self.ddpm_num_timesteps, fp)
+        if self._schedule_key == key:
+            return
+        self._schedule_key = None
+        acn = ac.detach().double().cpu().numpy() if isinstance(ac, torch.Tensor) else np.asarray(ac, dtype=np.float64)
+        assert acn.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
+        if self.discretize == "logsnr":
+            ts = make_logsnr_timesteps(acn, int(ddim_num_steps))
+        else:
+            ts = np.flip(make_ddim_timesteps("uniform", int(ddim_num_steps), self.ddpm_num_timesteps, verbose=False)).astype(np.int64)
+        if verbose:
+            print(f"Selected timesteps for the DPM-Solver++(2M) sampler ({self.discretize}): {ts}")
+        self.timesteps = ts
+        self.alphas = acn[ts]
+        self.alphas_next = np.append(acn[ts[1:]], acn[0])
+        self.k_x, self.k_d, self.k_p = multistep_coefficients(self.alphas, self.alphas_next, self.lower_order_final)
+        self._schedule_key = key
+
+    # ------------------------------------------------------------------------------------------ sample
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
+               quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
+               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
+               unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, **kwargs):
+        """Signature and return value (samples, intermediates) of `DDIMSampler.sample`; intermediates["pred_x0"] holds D."""
+        if eta != 0.:
+            raise NotImplementedError(_DETERMINISTIC.format(f"eta = {eta}"))
+        for name, off in (("score_corrector", score_corrector is None), ("quantize_x0", not quantize_x0),
+                          ("dynamic_threshold", dynamic_threshold is None)):
+            if not off:
+                raise NotImplementedError(_DETERMINISTIC.format(name))
+        if self.model.parameterization not in ("eps", "v"):
+            raise NotImplementedError(f"parameterization {self.model.parameterization!r}: only eps and v are built")
+        self.make_schedule(S, verbose=verbose)
+        C, H, W = shape
+        device = self.model.device
+        size = (batch_size, C, H, W)
+        img = torch.randn(size, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
+        intermediates = {"x_inter": [img], "pred_x0": [img]}
+        c, uc, scale = conditioning, unconditional_conditioning, unconditional_guidance_scale
+        self._pair._cache_key = None
+        total_steps = int(self.timesteps.shape[0])
+        if (mask is None and callback is None and img_callback is None and ucg_schedule is None
+                and self._loop_graph_ok(img, c, uc, scale, total_steps)):
+            return self._loop_graphed(img, c, uc, scale, total_steps, log_every_t, intermediates)
+        if mask is not None:
+            assert x0 is not None
+        x = self._run(img, c, uc, scale, self.timesteps, self.alphas, self.k_x, self.k_d, self.k_p, mask=mask, x0=x0, callback=callback,
+                      img_callback=img_callback, ucg_schedule=ucg_schedule, log_every_t=log_every_t, intermediates=intermediates)
+        return x, intermediates
+
+    def _step(self, x, d, c, uc, scale, k, timesteps, alphas, k_x, k_d, k_p):
+        """one eager step: the model on the pair, then the update kernel; d (fixed buffer) holds D_prev on entry and D on return"""
+        ts = torch.full((x.shape[0],), int(timesteps[k]), device=x.device, dtype=torch.long)
+        m_c, m_u = self._pair._eps_pair(x, c, ts, uc, scale)
+        a_t = float(alphas[k])
+        return ops.cfg_dpmpp_2m_step(x.contiguous(), m_c.contiguous(), None if m_u is None else m_u.contiguous(), scale, a_t,
+                                     float(np.sqrt(1.0 - a_t)), float(k_x[k]), float(k_d[k]), float(k_p[k]), d=d,
+                                     v_prediction=self.model.parameterization == "v")
+
+    def _run(self, x, c, uc, scale, timesteps, alphas, k_x, k_d, k_p, mask=None, x0=None, callback=None, img_callback=None,
+             ucg_schedule=None, log_every_t=100, intermediates=None):
+        """the per-step path over a run of steps that starts without history (k_p[0] == 0)"""
+        total = len(timesteps)
+        d = torch.empty_like(x, memory_format=torch.contiguous_format)
+        for k in range(total):
+            index = total - k - 1
+            if mask is not None:
+                ts = torch.full((x.shape[0],), int(timesteps[k]), device=x.device, dtype=torch.long)
+                x = self.model.q_sample(x0, ts) * mask + (1. - mask) * x
+            if ucg_schedule is not None:
+                assert len(ucg_schedule) == total
+                scale = ucg_schedule[k]
+            x = self._step(x, d, c, uc, scale, k, timesteps, alphas, k_x, k_d, k_p)
+            if callback:
+                callback(k)
+            if img_callback:
+                img_callback(d.clone(), k)
+            if intermediates is not None and (index % log_every_t == 0 or index == total - 1):
+                intermediates["x_inter"].append(x)
+                intermediates["pred_x0"].append(d.clone())
+        return x
+
+    # ------------------------------------------------------------------------------------------ whole-loop graph
+    def _loop_graph_ok(self, img, c, uc, scale, total_steps):
+        """the gating of `DDIMSampler._loop_graph_ok` (the solver has no noise term to rule out)"""
+        return bool(dh.USE_GRAPH and dh.USE_LOOP_GRAPH and img.is_cuda and total_steps >= 2 and self._pair._fusable(c, uc, scale)
+                    and self.model.parameterization in ("eps", "v"))
+
+    def _loop_graphed(self, img, c, uc, scale, total_steps, log_every_t, intermediates):
+        m, rt = self.model, self.model.rt
+        ts, a_t, k_x, k_d, k_p = self.timesteps, self.alphas, self.k_x, self.k_d, self.k_p
+        time_range = tuple(int(t) for t in ts)
+        ident = DDIMSampler._ident
+        hint_shared = ident(c["c_concat"]) == ident(uc["c_concat"])
+        per_graph = dh.LOOP_GRAPH_STEPS if dh.LOOP_GRAPH_STEPS > 0 else total_steps
+        # (rt.generation is read after step 1: the first forward at a new shape re-plans the runtime)
+        shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), tuple(float(v) for v in m.control_scales),
+                     bool(m.only_mid_control), self._schedule_key, per_graph, hint_shared, m.parameterization)
+        if self._loop_key is None or self._loop_key[1:] != shape_key:
+            self._loop_key = None
+            self._loop_x = torch.empty_like(img, memory_format=torch.contiguous_format)
+            self._loop_d = torch.empty_like(self._loop_x)             # D of the last step taken: the solver's only state next to x
+        x1 = self._step(img, self._loop_d, c, uc, scale, 0, ts, a_t, k_x, k_d, k_p)
+        intermediates["x_inter"].append(x1)                           # index == total_steps - 1
+        intermediates["pred_x0"].append(self._loop_d.clone())
+        self._loop_x.copy_(x1)
+        if getattr(rt, "_table_key", None) != (rt.generation, time_range):
+            rt.set_timestep_table(time_range)                         # another schedule used the runtime since (the graphs read the table by address)
+        key = (rt.generation,) + shape_key
+        if self._loop_key != key:
+            self._loop_key = None
+            torch.cuda.synchronize(img.device)
+            graphs, kept_x, kept_d = [], [], []
+            v_pred = m.parameterization == "v"
+            for first in range(1, total_steps, per_graph):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    for i in range(first, min(first + per_graph, total_steps)):
+                        a = float(a_t[i])
+                        rt.dpmpp_2m_step(self._loop_x, self._loop_d, i, scale, a, float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]),
+                                         float(k_p[i]), m.control_scales, m.only_mid_control, staged=i > first, hint_shared=hint_shared,
+                                         v_prediction=v_pred)
+                        if (total_steps - i - 1) % log_every_t == 0:
+                            kept_x.append(self._loop_x.clone())
+                            kept_d.append(self._loop_d.clone())
+                graphs.append(g)
+            self._loop_graphs, self._loop_kept = graphs, (kept_x, kept_d)
+            self._loop_key = key
+        for g in self._loop_graphs:
+            g.replay()
+        # the graphs' tensors are overwritten by the next replay: hand out copies
+        intermediates["x_inter"].extend(t.clone() for t in self._loop_kept[0])
+        intermediates["pred_x0"].extend(t.clone() for t in self._loop_kept[1])
+        return self._loop_x.clone(), intermediates
+
+    # ------------------------------------------------------------------------------------------ img2img
+    @torch.no_grad()
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
+        """`DDIMSampler.stochastic_encode` on this sampler's grid: index t counts grid points from the low-noise end (index 0 is the
+        last timestep the loop visits), as ddim_alphas[t] does."""
+        if use_original_steps:
+            raise NotImplementedError("stochastic_encode works on the solver's own grid (use_original_steps is DDIM's)")
+        asc = np.ascontiguousarray(self.alphas[::-1])
+        sqrt_ac = torch.as_tensor(np.sqrt(asc), dtype=torch.float32, device=x0.device)
+        sqrt_1m = torch.as_tensor(np.sqrt(1.0 - asc), dtype=torch.float32, device=x0.device)
+        if noise is None:
+            noise = torch.randn_like(x0)
+        ext = lambda a: a[t.to(x0.device)].reshape(-1, *([1] * (x0.dim() - 1)))
+        return ext(sqrt_ac) * x0 + ext(sqrt_1m) * noise
+
+    @torch.no_grad()
+    def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None, use_original_steps=False,
+               callback=None):
+        """`DDIMSampler.decode`: the last t_start steps of the grid.  The run has no history, so it restarts at first order."""
+        if use_original_steps:
+            raise NotImplementedError("decode works on the solver's own grid (use_original_steps is DDIM's)")
+        total = self.timesteps.shape[0]
+        assert 0 <= t_start <= total
+        if t_start == 0:
+            return x_latent
+        first = total - t_start
+        alphas, alphas_next = self.alphas[first:], self.alphas_next[first:]
+        k_x, k_d, k_p = multistep_coefficients(alphas, alphas_next, self.lower_order_final)
+        self._pair._cache_key = None
+        x = x_latent.to(device=self.model.device, dtype=torch.float32)
+        return self._run(x, cond, unconditional_conditioning, unconditional_guidance_scale, self.timesteps[first:], alphas, k_x, k_d, k_p,
+                         callback=callback)

@@ -394,6 +394,12 @@ int sdeo_cfg_ddim_step_v(float* x_prev, float* pred_x0, const float* x, const fl
                        true, S(stream));
 }
 
+int sdeo_cfg_dpmpp_2m_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, float cfg_scale, float a_t,
+                           float sqrt_one_minus_at, float k_x, float k_d, float k_p, int flags, int64_t n, void* stream) {
+  return cfg_lms_step(x_next, d, x, m_c, m_u, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, n, (flags & SDEO_STEP_V_PREDICTION) != 0,
+                      S(stream));
+}
+
 int sdeo_nchw_f32_to_nhwc_f16(void* y, int ldy, const float* x, int n, int c, int hw, void* stream) {
   return nchw_f32_to_nhwc_f16((f16*)y, ldy, x, n, c, hw, 1.0f, S(stream));
 }

@@ -2,6 +2,8 @@
 // grid-stride loops, fp32 math.
 #include "kernels.h"
 
+#include <cmath>
+
 namespace sdeo {
 
 static inline dim3 grid_for(int64_t work_items) {
@@ -389,6 +391,97 @@ int cfg_ddim_step(float* x_prev, float* pred_x0, const float* x, const float* ep
   else
     hipLaunchKernelGGL(cfg_ddim_kernel<false>, grid_for(n), dim3(256), 0, stream, x_prev, pred_x0, x, eps_c, eps_u, noise, cfg_scale,
                        1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sigma_t * sigma_t), sigma_t, sqrt_one_minus_at, n);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
+// CFG combine + one linear-multistep update (DPM-Solver++(2M), Lu et al. 2022): D is the data prediction cfg_ddim_elem_sel forms as
+// pred_x0 (so it is bit-equal to the DDIM kernels'), x_next = k_x x + k_d D + k_p D_prev.  The host folds the log-SNR arithmetic into the
+// three coefficients; k_p == 0 is the first-order step (algebraically the eta = 0 DDIM step) and never reads D_prev.
+// one element of the update; shared by both kernels below so that they round alike
+template <bool VPRED>
+__device__ __forceinline__ void cfg_lms_elem(float x, float c, float u, bool guided, float s, float at_coef, float sqrt_1m_at, float k_x, float k_d,
+                                             float k_p, float d_prev, float& p0, float& xn) {
+  float xp;                                   // the DDIM x_prev: not wanted here (its coefficients are passed as zero)
+  cfg_ddim_elem_sel<VPRED>(x, c, u, guided, s, at_coef, 0.f, 0.f, sqrt_1m_at, p0, xp);
+  xn = fmaf(k_d, p0, k_x * x);
+  if (k_p != 0.f) xn = fmaf(k_p, d_prev, xn);
+}
+
+// fp32 NCHW operands.  d is read (when k_p != 0) and then written by the same thread at the same index, so it carries no __restrict__.
+template <bool VPRED>
+__global__ __launch_bounds__(256) void cfg_lms_kernel(float* __restrict__ x_next, float* d, const float* __restrict__ x,
+                                                      const float* __restrict__ mc, const float* __restrict__ mu, float s, float at_coef,
+                                                      float sqrt_1m_at, float k_x, float k_d, float k_p, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float p0, xn;
+    const float dp = k_p != 0.f ? d[i] : 0.f;
+    cfg_lms_elem<VPRED>(x[i], mc[i], mu ? mu[i] : 0.f, mu != nullptr, s, at_coef, sqrt_1m_at, k_x, k_d, k_p, dp, p0, xn);
+    x_next[i] = xn;
+    if (d) d[i] = p0;
+  }
+}
+
+// The same update for the fused CFG pair (sdeo_dpmpp_2m_step), laid out as cfg_ddim_pair_kernel: fp16 NHWC model output (conditional
+// images first), x [b][C][HW] fp32 updated in place, the fp16 NHWC latent of both halves staged for the next forward.
+template <bool VPRED>
+__global__ __launch_bounds__(256) void cfg_lms_pair_kernel(float* __restrict__ x, float* d, const f16* __restrict__ eps, int lde,
+                                                           f16* __restrict__ x0, int ld0, int b, int C, int HW, float s, float at_coef,
+                                                           float sqrt_1m_at, float k_x, float k_d, float k_p) {
+  const int64_t total = (int64_t)b * HW;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t n = i / HW, pix = i - n * HW;
+    const f16* ec = eps + i * lde;
+    const f16* eu = eps + (i + total) * lde;
+    for (int c = 0; c < ld0; ++c) {
+      f16 v = (f16)0.f;
+      if (c < C) {
+        const int64_t j = (n * C + c) * HW + pix;
+        float p0, xn;
+        const float dp = k_p != 0.f ? d[j] : 0.f;
+        cfg_lms_elem<VPRED>(x[j], (float)ec[c], (float)eu[c], true, s, at_coef, sqrt_1m_at, k_x, k_d, k_p, dp, p0, xn);
+        x[j] = xn;
+        if (d) d[j] = p0;
+        v = (f16)xn;
+      }
+      x0[i * ld0 + c] = v;
+      x0[(i + total) * ld0 + c] = v;
+    }
+  }
+}
+
+static int lms_coefs_ok(const char* who, const float* d, float a_t, float k_x, float k_d, float k_p) {
+  SDEO_CHECK(a_t > 0.f, "%s: invalid schedule a_t=%g", who, a_t);
+  SDEO_CHECK(std::isfinite(k_x) && std::isfinite(k_d) && std::isfinite(k_p), "%s: non-finite coefficient k_x=%g k_d=%g k_p=%g", who, k_x, k_d,
+             k_p);
+  SDEO_CHECK(d || k_p == 0.f, "%s: k_p=%g needs the previous data prediction, but d is null", who, k_p);
+  return 0;
+}
+
+int cfg_lms_pair(float* x, float* d, const f16* eps, int lde, f16* x0, int ld0, int b, int C, int HW, float cfg_scale, float a_t,
+                 float sqrt_one_minus_at, float k_x, float k_d, float k_p, bool v_prediction, hipStream_t stream) {
+  SDEO_CHECK(x && eps && x0 && b > 0 && C > 0 && HW > 0 && lde >= C && ld0 >= C, "cfg_lms_pair: bad operand");
+  if (int rc = lms_coefs_ok("cfg_lms_pair", d, a_t, k_x, k_d, k_p)) return rc;
+  if (v_prediction)
+    hipLaunchKernelGGL(cfg_lms_pair_kernel<true>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, d, eps, lde, x0, ld0, b, C, HW,
+                       cfg_scale, sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p);
+  else
+    hipLaunchKernelGGL(cfg_lms_pair_kernel<false>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, d, eps, lde, x0, ld0, b, C, HW,
+                       cfg_scale, 1.0f / sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
+int cfg_lms_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, float cfg_scale, float a_t,
+                 float sqrt_one_minus_at, float k_x, float k_d, float k_p, int64_t n, bool v_prediction, hipStream_t stream) {
+  SDEO_CHECK(x_next && x && m_c && n > 0, "cfg_lms_step: bad operand");
+  if (int rc = lms_coefs_ok("cfg_lms_step", d, a_t, k_x, k_d, k_p)) return rc;
+  if (v_prediction)
+    hipLaunchKernelGGL(cfg_lms_kernel<true>, grid_for(n), dim3(256), 0, stream, x_next, d, x, m_c, m_u, cfg_scale, sqrtf(a_t),
+                       sqrt_one_minus_at, k_x, k_d, k_p, n);
+  else
+    hipLaunchKernelGGL(cfg_lms_kernel<false>, grid_for(n), dim3(256), 0, stream, x_next, d, x, m_c, m_u, cfg_scale, 1.0f / sqrtf(a_t),
+                       sqrt_one_minus_at, k_x, k_d, k_p, n);
   SDEO_HIP(hipGetLastError());
   return 0;
 }

@@ -221,5 +221,11 @@ int latent_pair_to_nhwc(f16* x0, int ld0, const float* x, int b, int C, int HW, 
 int cfg_ddim_step(float* x_prev, float* pred_x0, const float* x, const float* eps_c, const float* eps_u, const float* noise,
                   float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, int64_t n,
                   bool v_prediction, hipStream_t stream);
+// classifier-free guidance + one linear-multistep update x_next = k_x x + k_d D + k_p D_prev (DPM-Solver++(2M)); D is cfg_ddim_step's
+// pred_x0 and replaces D_prev in d.  The pair form is laid out as cfg_ddim_pair.
+int cfg_lms_pair(float* x, float* d, const f16* eps, int lde, f16* x0, int ld0, int b, int C, int HW, float cfg_scale, float a_t,
+                 float sqrt_one_minus_at, float k_x, float k_d, float k_p, bool v_prediction, hipStream_t stream);
+int cfg_lms_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, float cfg_scale, float a_t,
+                 float sqrt_one_minus_at, float k_x, float k_d, float k_p, int64_t n, bool v_prediction, hipStream_t stream);
 
 }  // namespace sdeo

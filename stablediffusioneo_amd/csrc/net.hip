@@ -1642,26 +1642,40 @@ int sdeo_set_timestep_table(sdeo_handle h, const int64_t* host_timesteps, int co
   return 0;
 }
 
-int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
-                   float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
+// What every fused CFG-pair step does before its update kernel: the checks, the time-embedding row, the control scales, the fp16 copy of
+// [x; x] unless the previous step staged it, and the networks.  Leaves the model output in h->eps16.
+static int cfg_pair_forward(sdeo_handle h, const float* x, int table_row, const float* host_control_scales, int only_mid_control, int flags,
+                            const char* who, hipStream_t s) {
   REQUIRE_READY(h);
-  SDEO_CHECK(x, "sdeo_ddim_step: null latent");
-  SDEO_CHECK(h->cfg.in_channels == h->cfg.out_channels, "sdeo_ddim_step: eps and latent must have the same channel count");
-  SDEO_CHECK(h->N % 2 == 0, "sdeo_ddim_step: configured for %d images; the CFG pair needs an even count (n = 2 x latents)", h->N);
-  SDEO_CHECK(table_row >= 0 && table_row < h->tab_count, "sdeo_ddim_step: timestep row %d, but the table holds %d (sdeo_set_timestep_table)",
+  SDEO_CHECK(x, "%s: null latent", who);
+  SDEO_CHECK(h->cfg.in_channels == h->cfg.out_channels, "%s: eps and latent must have the same channel count", who);
+  SDEO_CHECK(h->N % 2 == 0, "%s: configured for %d images; the CFG pair needs an even count (n = 2 x latents)", who, h->N);
+  SDEO_CHECK(table_row >= 0 && table_row < h->tab_count, "%s: timestep row %d, but the table holds %d (sdeo_set_timestep_table)", who,
              table_row, h->tab_count);
-  hipStream_t s = S(stream);
-  const sdeo_config& c = h->cfg;
-  const int b = h->N / 2, HW = h->lh * h->lw;
   int trow = -1;
-  if (int rc = select_time(h, 8 | (table_row << 8), nullptr, "sdeo_ddim_step", &trow)) return rc;
+  if (int rc = select_time(h, 8 | (table_row << 8), nullptr, who, &trow)) return rc;
   set_scales(h, host_control_scales, only_mid_control);
   if (!(flags & 16))
-    if (int rc = latent_pair_to_nhwc(h->x0.p, h->x0.ld, x, b, c.in_channels, HW, s)) return rc;
+    if (int rc = latent_pair_to_nhwc(h->x0.p, h->x0.ld, x, h->N / 2, h->cfg.in_channels, h->lh * h->lw, s)) return rc;
   // x0 = [x; x] at one timestep: the UNet's shared prefix always holds, the ControlNet's when the caller vouches for the hints
-  if (int rc = run_step_programs(h, false, true, s, true, (flags & SDEO_STEP_HINT_SHARED) != 0)) return rc;
-  return cfg_ddim_pair(x, pred_x0, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, b, c.out_channels, HW, cfg_scale, a_t, a_prev,
-                       sqrt_one_minus_at, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
+  return run_step_programs(h, false, true, s, true, (flags & SDEO_STEP_HINT_SHARED) != 0);
+}
+
+int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
+                   float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
+  hipStream_t s = S(stream);
+  if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, "sdeo_ddim_step", s)) return rc;
+  return cfg_ddim_pair(x, pred_x0, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw, cfg_scale, a_t,
+                       a_prev, sqrt_one_minus_at, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
+}
+
+int sdeo_dpmpp_2m_step(sdeo_handle h, float* x, float* d, int table_row, float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x,
+                       float k_d, float k_p, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
+  hipStream_t s = S(stream);
+  SDEO_CHECK(d || k_p == 0.f, "sdeo_dpmpp_2m_step: k_p=%g needs the previous data prediction, but d is null", k_p);
+  if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, "sdeo_dpmpp_2m_step", s)) return rc;
+  return cfg_lms_pair(x, d, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw, cfg_scale, a_t,
+                      sqrt_one_minus_at, k_x, k_d, k_p, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
 }
 
 int sdeo_vae_decode(sdeo_handle h, const float* z, int n, float* images, uint8_t* images_u8, void* stream) {

@@ -430,6 +430,22 @@ def cfg_ddim_step(x, eps_c, eps_u, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_min
     return x_prev, p0
 
 
+STEP_V_PREDICTION = 64      # SDEO_STEP_V_PREDICTION of include/sdeo.h
+
+
+def cfg_dpmpp_2m_step(x, m_c, m_u, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, d=None, v_prediction=False):
+    """`sdeo_cfg_dpmpp_2m_step`: CFG + one linear-multistep update, x_next = k_x x + k_d D + k_p d (d as it is on entry), then d <- D
+    in place (D is the pred_x0 of cfg_ddim_step on the same operands).  d may be None only when k_p == 0.  Returns x_next."""
+    lib = _lib.load()
+    _need_cuda(x, m_c, m_u, d)
+    assert x.dtype == torch.float32 and x.is_contiguous() and m_c.is_contiguous() and (m_u is None or m_u.is_contiguous())
+    assert d is None or (d.dtype == torch.float32 and d.is_contiguous() and d.shape == x.shape)
+    x_next = torch.empty_like(x)
+    check(lib.sdeo_cfg_dpmpp_2m_step(ptr(x_next), ptr(d), ptr(x), ptr(m_c), ptr(m_u), cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p,
+                                     STEP_V_PREDICTION if v_prediction else 0, x.numel(), cur_stream()), "cfg_dpmpp_2m_step")
+    return x_next
+
+
 def nchw_to_nhwc_f16(x, c_pad=None):
     lib = _lib.load()
     _need_cuda(x)

@@ -306,6 +306,19 @@ class SdeoRuntime(_HandleRuntime):
                                       | (STEP_V_PREDICTION if v_prediction else 0), cur_stream()), "ddim_step")
         return x
 
+    def dpmpp_2m_step(self, x, d, row: int, cfg_scale: float, a_t: float, sqrt_one_minus_at: float, k_x: float, k_d: float, k_p: float,
+                      scales=None, only_mid_control: bool = False, staged: bool = False, hint_shared: bool = False,
+                      v_prediction: bool = False):
+        """`sdeo_dpmpp_2m_step`: one DPM-Solver++(2M) step of the CFG pair, as `ddim_step` with the linear-multistep update
+        x <- k_x x + k_d D + k_p d, d <- D; x and d (b,4,h,w) fp32 contiguous are updated in place (d may be None when k_p == 0)."""
+        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
+        assert d is None or (d.is_contiguous() and d.dtype == torch.float32 and d.shape == x.shape)
+        check(self.lib.sdeo_dpmpp_2m_step(self.handle, ptr(x), ptr(d), int(row), cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p,
+                                          self._scales(scales), int(only_mid_control),
+                                          (STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)
+                                          | (STEP_V_PREDICTION if v_prediction else 0), cur_stream()), "dpmpp_2m_step")
+        return x
+
     def vae_decode(self, z, want_u8: bool = False):
         """z (b,4,h,w) latents (sampler output) -> images (b,3,8h,8w) fp32 in [-1,1] (+ optional NHWC uint8)."""
         v = self.vcfg
