@@ -322,6 +322,33 @@ int sdeo_debug_gemm_res_rows_f16(void* y, int ldy, const void* x, int ldx, const
   return conv_gemm(p, S(stream));
 }
 
+int sdeo_debug_gemm_multi_f16(int count, const int* tile, const int* splitk, const int* m, const int* n, const int* k, void* const* y,
+                              const int* ldy, const void* const* x, const int* ldx, const void* const* w, const int* ldw,
+                              const void* const* bias, const void* const* res, const int* ldres, const float* scale, void* stream) {
+  SDEO_CHECK(count >= 1 && tile && splitk && m && n && k && y && ldy && x && ldx && w && ldw && scale, "gemm_multi: null argument");
+  std::vector<ConvGemm> ps((size_t)count);
+  for (int i = 0; i < count; ++i) {
+    ConvGemm& p = ps[i];
+    fill_gemm(p, m[i], n[i], k[i]);
+    p.x = (const f16*)x[i]; p.w = (const f16*)w[i]; p.y = (f16*)y[i];
+    p.bias = bias ? (const float*)bias[i] : nullptr;
+    p.res = res ? (const f16*)res[i] : nullptr;
+    p.ldx = ldx[i]; p.ldw = ldw[i]; p.ldy = ldy[i]; p.ldres = (res && res[i] && ldres) ? ldres[i] : 0;
+    p.scale = scale[i];
+    p.force_tile = tile[i]; p.force_splitk = splitk[i];
+  }
+  ConvGemmMultiPlan pl;
+  if (int rc = conv_gemm_multi_plan(ps, tile[0], &pl)) return rc;      // every refusal happens here, before any device call
+  void* tab = nullptr;
+  SDEO_HIP(hipMalloc(&tab, pl.table.size()));
+  int rc = 0;
+  if (hipMemcpy(tab, pl.table.data(), pl.table.size(), hipMemcpyHostToDevice) != hipSuccess) rc = fail("gemm_multi: cannot write the problem table");
+  if (!rc) rc = conv_gemm_multi_launch(pl, tab, nullptr, S(stream));
+  if (!rc && hipStreamSynchronize(S(stream)) != hipSuccess) rc = fail("gemm_multi: the launch failed");      // the table must outlive it
+  (void)hipFree(tab);
+  return rc;
+}
+
 int sdeo_debug_gemm_ln_f16(void* y, int ldy, const void* x, int ldx, const void* w_folded, int ldw, const float* ln_s,
                            const float* bias_folded, const float* stats, int stats_ld, int strips, int ln_c, int m, int n, int k, int act, float eps, void* workspace, size_t workspace_bytes, void* stream) {
   ConvGemm p;

@@ -56,13 +56,41 @@ namespace sdeo {
 // address arithmetic is that of an fp16 problem of half the length), the MFMA waves read each lane's 32 consecutive codes as two
 // 16-byte chunks and issue v_mfma_scale_f32_16x16x128_f8f6f4 with the two e8m0 block scales of the lane's row and 32-code block:
 // 4x the K per MFMA at twice its cycles, half the operand bytes per FLOP.  GEMM (1x1) only, wave-specialised only.
-template <int BM, int BN, int STAGES, bool UPS, bool WS, bool W8 = false, int KPB = 1, bool MX = false>
-__global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const KP pp) {
-  kernarg_warm<sizeof(KP)>();
+// MULTI (multi-problem launch): the grid is the concatenation of the tiles of up to kMultiMax problems that share this tile.  The
+// argument is an MPArgs: the problems' parameter blocks and the inclusive prefix sums of their tile counts sit in device memory
+// (MPTable, written when the launch is configured), the per-problem `scale` comes by kernel argument (it is read when the launch runs).
+// A workgroup finds (problem, tile in problem) by a branch-free scan of the prefix sums in SGPRs, copies that problem's block in one
+// batch and from there on IS a workgroup of that problem's own launch: same K order, same epilogue, bit-identical output.  Unsplit
+// fp16 plans only (host-checked).  With MULTI = false nothing of this is compiled and the kernel is the one it was.
+template <int BM, int BN, int STAGES, bool UPS, bool WS, bool W8 = false, int KPB = 1, bool MX = false, bool MULTI = false>
+__global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const std::conditional_t<MULTI, MPArgs, KP> pp) {
+  kernarg_warm<sizeof(pp)>();
+  static_assert(!MULTI || (!W8 && !MX), "multi-problem launches stream fp16 weights");
   // The scalars both roles need before their first DMA / fragment read, fetched in ONE batch and pinned in SGPRs: left to the
   // compiler each is an s_load + s_waitcnt lgkmcnt(0) next to its first use, ten dependent scalar round trips in front of the
   // first DMA of a launch whose whole K loop lasts a few microseconds.
-  KP pl = pp;
+  KP pl;
+  int wg = blockIdx.x;                     // position of this workgroup among the tiles of its problem
+  [[maybe_unused]] int mp_prob = 0;
+  if constexpr (MULTI) {
+    int pre[kMultiMax];
+#pragma unroll
+    for (int i = 0; i < kMultiMax; ++i) pre[i] = mp_prefix(pp.tab, i);     // (entries past the count hold INT_MAX)
+    int prob = 0, first = 0;
+#pragma unroll
+    for (int i = 0; i < kMultiMax - 1; ++i) {
+      const bool past = (int)blockIdx.x >= pre[i];
+      prob += past ? 1 : 0;
+      first = past ? pre[i] : first;
+    }
+    mp_prob = __builtin_amdgcn_readfirstlane(min(prob, pp.count - 1));
+    wg = __builtin_amdgcn_readfirstlane((int)blockIdx.x - first);
+    pl = mp_block(pp.tab, mp_prob);
+    pl.scale = pp.scale[mp_prob];
+    mp_globalize(pl);
+  } else {
+    pl = pp;
+  }
   // (integers only: a pointer that has been through the asm loses its address space and every access through it becomes a flat_ one)
   asm volatile("" : "+s"(pl.M), "+s"(pl.N), "+s"(pl.K), "+s"(pl.Hi), "+s"(pl.Wi), "+s"(pl.Cin), "+s"(pl.Wo),
                "+s"(pl.S), "+s"(pl.stride), "+s"(pl.pad), "+s"(pl.HoWo), "+s"(pl.ldx), "+s"(pl.ldw), "+s"(pl.nk),
@@ -92,7 +120,7 @@ __global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const KP 
     const int tn = p.n_fastest ? tile % p.tiles_n : tile / p.tiles_m;
     m0 = tm * BM; n0 = tn * BN;
   };
-  set_tile(blockIdx.x);
+  set_tile(wg);
   const int z = blockIdx.z;
   const int kbeg = z * p.nk_per_split;
   const int kend = min(p.nk, kbeg + p.nk_per_split);
@@ -492,6 +520,7 @@ __global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const KP 
   // every wave is done reading fragments and no DMA is pending (the last K-step was retired with vmcnt(0)): the ring becomes
   // the waves' private epilogue scratch
   KP pe = p;                               // the epilogue's scalars in one batch of loads, in flight across the barrier
+  if constexpr (MULTI) { pe = mp_block(pp.tab, mp_prob); pe.scale = pp.scale[mp_prob]; }      // (the problem's block again, rather than ~60 SGPRs live across the K loop)
   pin_epilogue_scalars(pe);
   __builtin_amdgcn_s_barrier();
   stamp(p, 3);
@@ -765,6 +794,23 @@ static int launch_dma(const KP& kp, int tiles, hipStream_t stream) {
   constexpr int smem = ST * (W8 ? BM * 128 + (BN + 63) / 64 * 4096 : (BM + BN) * 128) + BM * 8;
   static_assert(smem <= 160 * 1024, "LDS");
   return launch_k(&conv_gemm_dma_kernel<BM, BN, ST, UPS, WS, W8, KPB, MX>, smem, &done, kp, tiles, stream, WS ? 512 : 256);
+}
+
+// multi-problem launch of one instantiation (conv_gemm_dma_kernel MULTI): `tiles` = the sum over the problems
+typedef int (*MultiLaunch)(const MPArgs& a, int tiles, hipStream_t stream);
+template <int BM, int BN, int ST, bool WS>
+static int launch_dma_multi(const MPArgs& a, int tiles, hipStream_t stream) {
+  static DeviceOnce done;
+  constexpr int smem = ST * (BM + BN) * 128 + BM * 8;
+  static_assert(smem <= 160 * 1024, "LDS");
+  auto kernel = &conv_gemm_dma_kernel<BM, BN, ST, false, WS, false, 1, false, true>;
+  if (done.need()) {
+    SDEO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    done.mark();
+  }
+  hipLaunchKernelGGL(kernel, dim3(tiles, 1, 1), dim3(WS ? 512 : 256), smem, stream, a);
+  SDEO_HIP(hipGetLastError());
+  return 0;
 }
 
 template <int BM, int BN>
@@ -1127,6 +1173,71 @@ int conv_gemm(const ConvGemm& p0, hipStream_t stream) {
   if (int rc = prepare(p, pl, kp)) return rc;
   g_last_tile = pl.tile; g_last_splitk = pl.splitk;
   return dispatch(pl, p.ups, p.wscale != nullptr, kp, stream);
+}
+
+// The rows of kTiles that have a multi-problem instantiation (the table itself is untouched: a multi-problem launch is asked for by
+// name, never planned).  Each costs one more kernel, so there are as many as there are users.
+struct MultiTile { int tile, bm, bn, stages; bool light; MultiLaunch launch; const char* name; };
+static const MultiTile kMultiTiles[] = {
+    {2, 64, 64, 4, false, &launch_dma_multi<64, 64, 4, true>, "conv_gemm_dma_kernel<64,64,4> multi"},
+    {6, 64, 160, 3, false, &launch_dma_multi<64, 160, 3, true>, "conv_gemm_dma_kernel<64,160,3> multi"},
+    {26, 128, 64, 2, true, &launch_dma_multi<128, 64, 2, false>, "conv_gemm_dma_kernel<128,64,2> multi"},
+};
+static const MultiTile* multi_tile(int tile) {
+  for (const MultiTile& m : kMultiTiles) {
+    const TileCfg& c = kTiles[m.tile];
+    if (m.tile == tile && c.kind == TK_DMA && c.bm == m.bm && c.bn == m.bn && c.stages == m.stages && c.kpb == 1 &&
+        ((c.caps & CAP_LIGHT) != 0) == m.light)
+      return &m;
+  }
+  return nullptr;
+}
+
+int conv_gemm_multi_plan(const std::vector<ConvGemm>& ps, int tile, ConvGemmMultiPlan* out) {
+  *out = ConvGemmMultiPlan{};
+  // refusals that need no look at the operands come first
+  SDEO_CHECK(!ps.empty() && (int)ps.size() <= kMultiMax, "conv_gemm_multi: %d problems in one launch (1..%d)", (int)ps.size(), kMultiMax);
+  for (const ConvGemm& p : ps) {
+    if (tile < 0) tile = p.force_tile;
+    SDEO_CHECK(p.force_tile < 0 || p.force_tile == tile, "conv_gemm_multi: mixed tiles (%d and %d): one tile serves all problems of a launch", tile, p.force_tile);
+    SDEO_CHECK(p.force_splitk <= 1, "conv_gemm_multi: a split-K plan (factor %d) cannot be part of a multi-problem launch", p.force_splitk);
+  }
+  const MultiTile* mt = multi_tile(tile);
+  SDEO_CHECK(mt, "conv_gemm_multi: tile %d has no multi-problem instantiation", tile);
+  MPTable tab{};
+  int total = 0;
+  for (size_t i = 0; i < ps.size(); ++i) {
+    ConvGemm p = ps[i];
+    SDEO_CHECK(!p.mx_sx && !p.wscale, "conv_gemm_multi: problem %d: fp16 weights only", (int)i);
+    SDEO_CHECK(!p.gn_out && !p.stats_out && !p.ln_stats, "conv_gemm_multi: problem %d: no GroupNorm-partial, row-statistics or LayerNorm-fold epilogue", (int)i);
+    SDEO_CHECK(p.act != 3 && !p.ups && p.plan_B == 0, "conv_gemm_multi: problem %d: no GEGLU pair, folded upsample or batch-prefix plan", (int)i);
+    SDEO_CHECK(is_fast(p), "conv_gemm_multi: problem %d: Cin=%d must be a multiple of 64", (int)i, p.Cin);
+    p.force_tile = tile; p.force_splitk = 1;
+    Plan pl;
+    if (int rc = prepare(p, pl, tab.kp[i])) return rc;
+    SDEO_CHECK(pl.tile == tile && pl.splitk == 1, "conv_gemm_multi: problem %d cannot run unsplit on tile %d", (int)i, tile);
+    total += pl.tiles_m * pl.tiles_n;
+    tab.prefix[i] = total;
+    out->scale[i] = p.scale;
+    out->flops += 2.0 * p.M * p.N * (double)p.K;
+    out->bytes += 2.0 * ((double)p.M * p.Cin + (double)p.N * p.K + (double)p.M * p.N);
+  }
+  for (int i = (int)ps.size(); i < kMultiMax; ++i) tab.prefix[i] = 0x7fffffff;
+  out->tile = tile; out->count = (int)ps.size(); out->tiles = total; out->name = mt->name;
+  out->table.assign(reinterpret_cast<const char*>(&tab), reinterpret_cast<const char*>(&tab) + sizeof(tab));
+  return 0;
+}
+
+int conv_gemm_multi_launch(const ConvGemmMultiPlan& pl, const void* table_dev, const float* scales, hipStream_t stream) {
+  const MultiTile* mt = multi_tile(pl.tile);
+  SDEO_CHECK(mt && pl.count >= 1 && pl.count <= kMultiMax && pl.tiles > 0 && pl.table.size() == sizeof(MPTable), "conv_gemm_multi: launch of an unplanned table");
+  SDEO_CHECK(table_dev && (reinterpret_cast<uintptr_t>(table_dev) & 15) == 0, "conv_gemm_multi: the device table must be 16-byte aligned");
+  MPArgs a{};
+  a.tab = static_cast<const MPTable*>(table_dev);
+  a.count = pl.count;
+  for (int i = 0; i < pl.count; ++i) a.scale[i] = scales ? scales[i] : pl.scale[i];
+  g_last_tile = pl.tile; g_last_splitk = 1;
+  return mt->launch(a, pl.tiles, stream);
 }
 
 int conv_gemm_tile_info(int tile, int* kind, int* bm, int* bn, int* stages, int* caps, const char** name) {

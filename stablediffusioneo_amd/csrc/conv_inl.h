@@ -1,6 +1,7 @@
 // Device-side pieces shared by the implicit-GEMM kernels (conv_gemm.hip) and the halo-reuse 3x3 kernel (conv_halo.hip):
 // kernel parameter block, epilogue, XCD-aware tile order, LDS-DMA / fragment-read helpers.
 #pragma once
+#include <type_traits>
 #include <utility>
 
 #include "kernels.h"
@@ -59,6 +60,45 @@ struct KP {
   const unsigned char* mx_sw;   // [N][mx_ldsw]
   int mx_ldsx, mx_ldsw;
 };
+
+// Multi-problem launch (conv_gemm_dma_kernel<..., MULTI>): several problems that run on the same tile, unsplit, as ONE grid.
+// MPTable lives in device memory and is written when the launch is configured: the problems' parameter blocks and the inclusive
+// prefix sums of their tile counts (entries past the last problem hold INT_MAX, so a scan needs no count).  MPArgs is the kernel
+// argument: sixteen blocks would not fit the 4 KB argument segment, and `scale` must be the value of the moment of the launch.
+struct MPTable {
+  int prefix[kMultiMax];
+  KP kp[kMultiMax];
+};
+struct MPArgs {
+  const MPTable* tab;
+  int count;
+  float scale[kMultiMax];
+};
+// reads of the table go through the constant address space: it does not change under the launch, and loads from there at a uniform
+// address are scalar ones (one s_load_dwordx16 for the prefix sums, a batch of them for a block)
+__device__ __forceinline__ int mp_prefix(const MPTable* tab, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return ((const __attribute__((address_space(4))) MPTable*)tab)->prefix[i];
+#else
+  return tab->prefix[i];
+#endif
+}
+__device__ __forceinline__ KP mp_block(const MPTable* tab, int prob) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return ((const __attribute__((address_space(4))) MPTable*)tab)->kp[prob];
+#else
+  return tab->kp[prob];
+#endif
+}
+// a block read from device memory: its pointers are global ones (the compiler knows that of kernel arguments only, and every access
+// through a generic pointer is a flat_ one, which also counts on lgkmcnt)
+__device__ __forceinline__ void mp_globalize(KP& q) {
+#define SDEO_GLOBAL_PTR(f) q.f = (decltype(q.f))(__attribute__((address_space(1))) std::remove_pointer_t<decltype(q.f)>*)q.f;
+  SDEO_GLOBAL_PTR(x) SDEO_GLOBAL_PTR(w) SDEO_GLOBAL_PTR(y) SDEO_GLOBAL_PTR(y32) SDEO_GLOBAL_PTR(bias) SDEO_GLOBAL_PTR(bias2)
+  SDEO_GLOBAL_PTR(res) SDEO_GLOBAL_PTR(ws) SDEO_GLOBAL_PTR(ln_stats) SDEO_GLOBAL_PTR(ln_s) SDEO_GLOBAL_PTR(wscale)
+  SDEO_GLOBAL_PTR(stats_out) SDEO_GLOBAL_PTR(gn_out) SDEO_GLOBAL_PTR(mx_sx) SDEO_GLOBAL_PTR(mx_sw)
+#undef SDEO_GLOBAL_PTR
+}
 
 // Ablation / stamp switches exist only in the measurement build: in the production library dbg_on() is the constant false and
 // every branch on it (and the stamp code) is compiled out of the K loops.

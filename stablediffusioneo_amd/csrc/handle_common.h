@@ -6,12 +6,16 @@
 
 #include <algorithm>
 #include <functional>
+#include <memory>
+#include <set>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "arena.h"
 #include "kernels.h"
+
+extern "C" const char* sdeo_last_error(void);
 
 namespace sdeo {
 
@@ -214,6 +218,34 @@ static inline Op conv_gemm_op(const ConvGemm& p0, WorkspaceRef ws, size_t* max_w
      2.0 * ((double)p0.M * p0.Cin + (double)p0.N * p0.K + (double)p0.M * p0.N),
      !tagged ? std::string() : "M" + std::to_string(p0.M) + " N" + std::to_string(p0.N) + " K" + std::to_string(p0.K) + " R" +
          std::to_string(p0.R) + " s" + std::to_string(p0.stride) + " u" + std::to_string(p0.ups));
+}
+
+// Several unsplit conv / GEMM problems on one tile as ONE launch (kernels.h: conv_gemm_multi_plan).  The device table is written here,
+// once, and lives as long as the op; scale_host[i] (optional, may hold nulls) is problem i's `scale`, read when the launch runs.  A
+// set of problems the launcher refuses gives an op that fails with that message.  Profile key: the tile's kernel + "multi xN".
+static inline Op conv_gemm_multi_op(const std::vector<ConvGemm>& ps, int tile, std::vector<const float*> scale_host = {}) {
+  static std::set<std::string> keys;       // Op::key is a C string that outlives the op
+  auto pl = std::make_shared<ConvGemmMultiPlan>();
+  std::shared_ptr<void> dev;
+  std::string err;
+  if (conv_gemm_multi_plan(ps, tile, pl.get())) {
+    err = sdeo_last_error();
+  } else {
+    void* d = nullptr;
+    if (hipMalloc(&d, pl->table.size()) != hipSuccess || hipMemcpy(d, pl->table.data(), pl->table.size(), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      err = "conv_gemm_multi: cannot place the problem table in device memory";
+    }
+    dev.reset(d, [](void* q) { if (q) (void)hipFree(q); });
+  }
+  scale_host.resize(ps.size(), nullptr);
+  const char* key = keys.insert(std::string(err.empty() ? pl->name : "conv_gemm multi") + " x" + std::to_string(ps.size())).first->c_str();
+  return Op([pl, dev, err, scale_host](hipStream_t s) {
+    if (!err.empty()) return fail("%s", err.c_str());
+    float sc[kMultiMax];
+    for (int i = 0; i < pl->count; ++i) sc[i] = scale_host[i] ? *scale_host[i] : pl->scale[i];
+    return conv_gemm_multi_launch(*pl, dev.get(), sc, s);
+  }, key, pl->flops, pl->bytes, "tiles" + std::to_string(pl->tiles));
 }
 
 // profiling off (or no profiler): one std::function call per op and nothing else

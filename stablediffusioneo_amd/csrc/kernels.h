@@ -1,6 +1,8 @@
 // Host-side launchers of the hand-written gfx950 kernels.  All are asynchronous on `stream`,
 // never allocate and never synchronise (hipGraph-capturable).
 #pragma once
+#include <vector>
+
 #include "common.h"
 
 namespace sdeo {
@@ -69,6 +71,25 @@ struct ConvGemm {
 };
 int conv_gemm(const ConvGemm& p, hipStream_t stream);
 inline int conv_pad_after(const ConvGemm& p) { return p.pad_after < 0 ? p.pad : p.pad_after; }
+// Multi-problem launch: up to kMultiMax conv / GEMM problems that run on ONE tile of the table, unsplit, as one grid of the
+// LDS-DMA kernel (the sum of their tiles): thirteen 10 us launches become one many-tile launch.  fp16 weights, Cin % 64 == 0, no
+// folded Upsample, no statistics / GroupNorm-partial / LayerNorm-fold epilogue; bias, bias2, residual, act (not the GEGLU pair), scale and
+// output views behave as in conv_gemm(), and every problem's output is bit-identical to its own launch with that tile forced.
+//   conv_gemm_multi_plan: host only, no device call.  tile: a row of the table that has a multi-problem instantiation (< 0: the
+//     problems' own force_tile, which must then agree); a problem whose force_tile names another row is refused ("mixed tiles"), as is
+//     a force_splitk above 1 (the process-wide conv_gemm_debug_force does not reach these launches).  Fills `out`: table = the image of the device table the launch reads.
+//   conv_gemm_multi_launch: table_dev = out.table copied to device memory (16-byte aligned), by the caller, once; scales[count] = the
+//     problems' `scale` at the moment of the launch (null: those of the plan).
+constexpr int kMultiMax = 16;
+struct ConvGemmMultiPlan {
+  int tile = -1, count = 0, tiles = 0;
+  std::vector<char> table;
+  float scale[kMultiMax] = {};
+  double flops = 0, bytes = 0;     // sums over the problems (2 M N K; algorithmic bytes of x, w, y)
+  const char* name = "";           // the tile's instantiation
+};
+int conv_gemm_multi_plan(const std::vector<ConvGemm>& ps, int tile, ConvGemmMultiPlan* out);
+int conv_gemm_multi_launch(const ConvGemmMultiPlan& pl, const void* table_dev, const float* scales, hipStream_t stream);
 // M tiles per image of the plan chosen for p when its epilogue can emit GroupNorm partials for groups of cpg channels, else 0
 int conv_gemm_gn_slots(const ConvGemm& p, int cpg);
 // whether the plan chosen for p is a halo-reuse 3x3 kernel (which has no fp8-weight variant)

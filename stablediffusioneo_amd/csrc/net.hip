@@ -1013,9 +1013,24 @@ static void build_control_io(BuildCtx& c) {
 // zero convs themselves, out = scale * zero_conv(cn_h) + skip written straight into the concat buffer (no add launches, no fp16
 // round trip of the control).
 enum DecoderMode { D_NOCTRL, D_ADD, D_FUSED };
+// D_FUSED: every operand of the zero convs exists at the join (the ControlNet block outputs, the skips, the middle block's output), so
+// all of them run as ONE multi-problem launch (kernels.h: conv_gemm_multi_plan) in front of the decoder, each writing its half of its
+// stage's concat buffer -- which therefore all exist from the start.  A function of the configuration only: the fp16 LDS-DMA kernel
+// takes every problem (channels in multiples of 64, at most kMultiMax of them) and no GEMM of the handle runs block-scaled fp8 (those
+// zero convs keep their own packed launches).
+static const int kZeroConvTile = 26;     // conv_gemm_dma_kernel<128,64,2>, four waves: measured against <64,64,4> and <64,160,3>
+static bool zero_convs_as_one(const BuildCtx& c) {
+  const Engine* e = c.b.e;
+  if (c.nctrl > kMultiMax || e->fp8.act_bits == 8 || e->uplan.out.size() + 1 != (size_t)c.nctrl) return false;
+  for (int i = 0; i < c.nctrl; ++i)
+    if (e->cn_h[i].c % 64) return false;
+  return true;
+}
+static void build_unet_decoder_multi(BuildCtx& c, std::vector<T> hs, T cat0, T view0);
 static void build_unet_decoder(BuildCtx& c, DecoderMode mode, std::vector<T> hs, T cat, T view) {
   Builder& b = c.b; Engine* e = b.e;
   const std::string ns = NS_UNET;
+  if (mode == D_FUSED && zero_convs_as_one(c)) return build_unet_decoder_multi(c, hs, cat, view);
   int ci = c.nctrl - 1;
   if (mode == D_ADD) {   // h += control.pop()
     f16* yp = view.p; const int ld = view.ld, rows = view.rows(), Cc = view.c;
@@ -1055,6 +1070,56 @@ static void build_unet_decoder(BuildCtx& c, DecoderMode mode, std::vector<T> hs,
       cat = ncat;
     } else {
       T y = run_blocks(c, ns, blocks, cat, true, 0, nullptr);
+      Builder::CO oo; oo.cout_store = 4 * ((e->cfg.out_channels + 3) / 4);
+      oo.out = &e->eps16;
+      b.gn_conv(y, ns + "out.0", 1e-5f, 1, ns + "out.2", e->cfg.out_channels, oo);
+      b.release(y);
+    }
+  }
+}
+
+static void build_unet_decoder_multi(BuildCtx& c, std::vector<T> hs, T cat0, T view0) {
+  Builder& b = c.b; Engine* e = b.e;
+  const std::string ns = NS_UNET;
+  const size_t stages = e->uplan.out.size(), nh = hs.size();      // one skip per stage
+  // the concat buffer of every stage; [0, c_h) of stage oi + 1 is written by stage oi's last block
+  std::vector<T> cats{cat0};
+  for (size_t oi = 0; oi + 1 < stages; ++oi) {
+    const std::vector<Blk>& blocks = e->uplan.out[oi];
+    const T& prev = cats.back();
+    const int up = blocks.back().kind == B_UP ? 2 : 1;
+    cats.push_back(b.alloc(prev.n, prev.h * up, prev.w * up, blocks.back().cout + hs[nh - 2 - oi].c));
+  }
+  // out = scale * zero_conv(cn_h[ci]) + skip into the second half of its stage's buffer (the middle block's: in place over view0)
+  std::vector<ConvGemm> zc;
+  std::vector<const float*> zs;
+  auto zero_conv = [&](int ci, const std::string& name, const T& out, const T& res) {
+    const T& x = e->cn_h[ci];
+    const WEntry* w = b.W(name + ".weight");
+    if (w && w->ipad != x.c && b.err.empty()) b.err = "conv " + name + ": input has " + std::to_string(x.c) + " channels, weight expects " + std::to_string(w->ipad);
+    ConvGemm p;
+    p.x = x.p; p.w = b.wptr(name + ".weight"); p.bias = b.vptr(name + ".bias"); p.y = out.p; p.res = res.p;
+    p.B = x.n; p.Hi = p.Ho = x.h; p.Wi = p.Wo = x.w; p.Cin = x.c;
+    p.M = x.rows(); p.N = out.c; p.K = x.c;
+    p.ldx = x.ld; p.ldw = p.K; p.ldy = out.ld; p.ldres = res.ld;
+    zc.push_back(p);
+    zs.push_back(&e->eff_scales[ci]);
+  };
+  int ci = c.nctrl - 1;
+  zero_conv(ci--, std::string(NS_CN) + "middle_block_out.0", view0, view0);
+  for (size_t oi = 0; oi < stages; ++oi, --ci) {
+    const T& skip = hs[nh - 1 - oi];
+    zero_conv(ci, std::string(NS_CN) + "zero_convs." + std::to_string(ci) + ".0", cats[oi].view(cats[oi].c - skip.c, skip.c), skip);
+  }
+  if (!b.dry) b.prog->push_back(conv_gemm_multi_op(zc, kZeroConvTile, zs));
+  for (T& skip : hs) b.release(skip);
+  for (size_t oi = 0; oi < stages; ++oi) {
+    const std::vector<Blk>& blocks = e->uplan.out[oi];
+    if (oi + 1 < stages) {
+      const T nview = cats[oi + 1].view(0, blocks.back().cout);
+      run_blocks(c, ns, blocks, cats[oi], true, 0, &nview);
+    } else {
+      T y = run_blocks(c, ns, blocks, cats[oi], true, 0, nullptr);
       Builder::CO oo; oo.cout_store = 4 * ((e->cfg.out_channels + 3) / 4);
       oo.out = &e->eps16;
       b.gn_conv(y, ns + "out.0", 1e-5f, 1, ns + "out.2", e->cfg.out_channels, oo);

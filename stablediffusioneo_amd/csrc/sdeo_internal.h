@@ -24,6 +24,14 @@ const char* sdeo_debug_attention_kernel_name(int B, int H, int Tq, int Tk, int d
 int sdeo_debug_conv2d_plan(int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, int act, int fp8, int* key10,
                            int* tile, int* splitk);
 int sdeo_debug_gemm_plan(int m, int n, int k, int act, int fp8, int* key10, int* tile, int* splitk);
+/* multi-problem launch (csrc/conv_gemm.hip, conv_gemm_dma_kernel MULTI): `count` GEMMs y_i = scale_i * (x_i w_i^T + bias_i) + res_i
+ * (fp16, row strides in elements, bias_i / res_i may be NULL) as ONE unsplit launch.  Arrays of `count` entries; the pointer arrays
+ * hold device pointers.  tile_i / splitk_i: the plan forced on problem i (as sdeo_debug_force_gemm_plan forces one launch; splitk 0 or
+ * 1 = unsplit); the launch runs on tile_0.  Refused on the host, before any device call: count > 16, a split-K plan, tiles that differ
+ * ("mixed tiles"), a tile without a multi-problem instantiation. */
+int sdeo_debug_gemm_multi_f16(int count, const int* tile, const int* splitk, const int* m, const int* n, const int* k, void* const* y,
+                              const int* ldy, const void* const* x, const int* ldx, const void* const* w, const int* ldw,
+                              const void* const* bias, const void* const* res, const int* ldres, const float* scale, void* stream);
 /* (tile, split-K) of the last conv / GEMM launch (host-side record; -1 / 0 before the first) */
 void sdeo_debug_last_gemm_plan(int* tile, int* splitk);
 /* row `tile` of the conv / GEMM tile table (csrc/conv_gemm.hip: kTiles); returns non-zero past the end.  kind: 0 LDS-DMA implicit GEMM,

@@ -209,6 +209,36 @@ def gemm(x, w, bias=None, res=None, act=0, scale=1.0, out_f32=False, bias_per_ro
     return y
 
 
+def gemm_multi(problems, tile, tiles=None, splitk=None):
+    """Several GEMMs as ONE multi-problem launch on tile `tile` (csrc/conv_gemm.hip, conv_gemm_dma_kernel MULTI).  problems: dicts with
+    x [m][k], w [n][k] (fp16, unit inner stride) and optionally bias (fp32 [n]), res ([m][n] view), scale, out ([m][n] view, e.g. a column
+    block of a wider buffer; default: a new tensor).  tiles / splitk: the plan forced per problem (default: `tile`, unsplit).
+    Returns the outputs."""
+    lib = _lib.load()
+    cnt = len(problems)
+    outs, keep = [], []
+    arr_i = lambda vals: (C.c_int * cnt)(*[int(v) for v in vals])
+    arr_p = lambda ts: (C.c_void_p * cnt)(*[t.data_ptr() if t is not None else None for t in ts])
+    for p in problems:
+        x, w = p["x"], p["w"]
+        _need_cuda(x, w)
+        assert x.shape[1] == w.shape[1] and x.stride(1) == 1 and w.stride(1) == 1
+        y = p.get("out")
+        if y is None:
+            y = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float16, device=x.device)
+        assert y.shape == (x.shape[0], w.shape[0]) and y.stride(1) == 1 and y.dtype == torch.float16
+        outs.append(y)
+    res = [p.get("res") for p in problems]
+    check(lib.sdeo_debug_gemm_multi_f16(
+        cnt, arr_i(tiles if tiles is not None else [tile] * cnt), arr_i(splitk if splitk is not None else [1] * cnt),
+        arr_i(p["x"].shape[0] for p in problems), arr_i(p["w"].shape[0] for p in problems), arr_i(p["x"].shape[1] for p in problems),
+        arr_p(outs), arr_i(y.stride(0) for y in outs), arr_p([p["x"] for p in problems]), arr_i(p["x"].stride(0) for p in problems),
+        arr_p([p["w"] for p in problems]), arr_i(p["w"].stride(0) for p in problems), arr_p([p.get("bias") for p in problems]),
+        arr_p(res), arr_i(r.stride(0) if r is not None else 0 for r in res),
+        (C.c_float * cnt)(*[float(p.get("scale", 1.0)) for p in problems]), cur_stream()), "gemm_multi")
+    return outs
+
+
 def fold_layernorm(w, gamma, beta, bias=None):
     """(w * gamma as fp16 [rows][c], row sums s fp32 [rows], bias + w beta fp32 [rows]): the load-time LayerNorm fold."""
     lib = _lib.load()
