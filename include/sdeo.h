@@ -139,6 +139,21 @@ int sdeo_cfg_ddim_step_v(float* x_prev, float* pred_x0, const float* x, const fl
 int sdeo_cfg_dpmpp_2m_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, float cfg_scale, float a_t,
                            float sqrt_one_minus_at, float k_x, float k_d, float k_p, int flags, int64_t n, void* stream);
 
+/* The sampler's mask / x0 blend (cldm/ddim_hacked.py:154-157: img = q_sample(x0, t) * mask + (1 - mask) * img) on fp32 NCHW latents,
+ * IN PLACE on x:   x <- mask * (sqrt_a * orig + sqrt_one_minus_a * noise) + (1 - mask) * x
+ *   x, orig, noise [n][c][hw];  mask [mask_n][mask_c][hw] with mask_n in {1, n} and mask_c in {1, c} (the broadcasts torch allows a
+ *   (b|1, 1|C, h, w) mask);  sqrt_a / sqrt_one_minus_a: the fp32 entries of sqrt_alphas_cumprod[t] / sqrt_one_minus_alphas_cumprod[t],
+ *   the tables q_sample reads (nothing is recomputed from alpha on the device).
+ * Every operation rounds once, in the order of the torch expression (two products and a sum for q_sample, then q * mask, 1 - mask,
+ * (1 - mask) * x and a sum; no fused multiply-add), so the result is bit-equal to it.  Null pointers and a mask_n / mask_c outside the
+ * allowed values are refused before any device call, each with its own message. */
+int sdeo_mask_blend(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a,
+                    float sqrt_one_minus_a, int n, int c, int hw, void* stream);
+
+/* Inpainting composite on uint8 NHWC images [h][w][c] (c in 1..4, any h, w >= 1) with a uint8 mask [h][w], integer arithmetic:
+ *   dst = (gen * m + orig * (255 - m) + 127) / 255        (m = 255: gen, m = 0: orig, exactly).  dst may be gen or orig. */
+int sdeo_composite_u8(uint8_t* dst, const uint8_t* gen, const uint8_t* orig, const uint8_t* mask, int h, int w, int c, void* stream);
+
 /* Canny edge map: replaces `cv2.Canny(img, low_threshold, high_threshold)` of annotator/canny/__init__.py:4-6
  * (aperture 3, L1 gradient magnitude; called at canny2image_torch.py:33 on the HWC3 uint8 image) and the control preparation of
  * canny2image_torch.py:34-38.  img_hwc: device uint8 [h][w][c], c in 1..4.  edges (optional): device uint8 [h][w], 0 / 255.
@@ -288,6 +303,27 @@ int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float
  * k_p == 0).  Bit-identical to sdeo_apply_model on [x; x] followed by sdeo_cfg_dpmpp_2m_step. */
 int sdeo_dpmpp_2m_step(sdeo_handle h, float* x, float* d, int table_row, float cfg_scale, float a_t, float sqrt_one_minus_at,
                        float k_x, float k_d, float k_p, const float* host_control_scales, int only_mid_control, int flags, void* stream);
+
+/* The fused steps with the mask / x0 blend of sdeo_mask_blend in front: x <- blend(x) IN PLACE, then exactly what sdeo_ddim_step /
+ * sdeo_dpmpp_2m_step do on the blended latent (the same forward, the same update kernel).  orig, noise [n/2][4][h][w] fp32, mask
+ * [mask_n][mask_c][h*w] fp32 with mask_n in {1, n/2}, mask_c in {1, 4}; sqrt_a / sqrt_one_minus_a as in sdeo_mask_blend; every other
+ * argument as in the unmasked step.  The blend runs in the launch that stages the fp16 copy of [x; x] (it takes the place of that
+ * launch), so a masked step has the dispatch count of an unstaged unmasked step.
+ * Contract:
+ *   - x, pred_x0 / d are bit-identical to sdeo_mask_blend followed by the unmasked step without SDEO_STEP_LATENT_STAGED;
+ *   - SDEO_STEP_LATENT_STAGED is refused (the blend changes the latent, so it is always restaged); SDEO_STEP_HINT_SHARED and
+ *     SDEO_STEP_V_PREDICTION keep their meaning;
+ *   - every argument check happens before the first device call, each with its own message: a null x / orig / noise / mask, mask_n or
+ *     mask_c outside the allowed values, an unconfigured handle, an odd configured n, a table row outside the table, an invalid
+ *     schedule (what the update kernel would refuse), d null with k_p != 0.  A refused call leaves x, pred_x0 and d untouched;
+ *   - capturable; sdeo_ddim_step and sdeo_dpmpp_2m_step are unchanged: same signatures, same launches, same bits. */
+int sdeo_ddim_step_masked(sdeo_handle h, float* x, float* pred_x0, const float* orig, const float* noise, const float* mask, int mask_n,
+                          int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row, float cfg_scale, float a_t, float a_prev,
+                          float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream);
+int sdeo_dpmpp_2m_step_masked(sdeo_handle h, float* x, float* d, const float* orig, const float* noise, const float* mask, int mask_n,
+                              int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row, float cfg_scale, float a_t,
+                              float sqrt_one_minus_at, float k_x, float k_d, float k_p, const float* host_control_scales,
+                              int only_mid_control, int flags, void* stream);
 
 /* decode_first_stage: z/scale_factor -> post_quant_conv -> Decoder (model.py:619-652).
  * z [n][4][h][w] fp32 NCHW -> images [n][3][8h][8w] fp32 NCHW in [-1,1]; images_u8 (optional, may be NULL)

@@ -96,10 +96,19 @@ class hackathon():
         return self
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, ddim_steps, guess_mode,
-                strength, scale, seed, eta, low_threshold, high_threshold, x_T=None, init_image=None, denoise_strength=0.75):
+                strength, scale, seed, eta, low_threshold, high_threshold, x_T=None, init_image=None, denoise_strength=0.75, mask_image=None):
         """init_image (HxWx3 uint8, optional): img2img with upstream `scripts/img2img.py` semantics -- the image is resized like the
         input, encoded (posterior sample), noised to t_enc = int(denoise_strength * ddim_steps) by stochastic_encode and denoised from
-        there by DDIMSampler.decode; the Canny hint still comes from `input_image`.  Needs initialize(..., vae_encoder=True)."""
+        there by DDIMSampler.decode; the Canny hint still comes from `input_image`.  Needs initialize(..., vae_encoder=True).
+        mask_image (HxW or HxWx{1,3} uint8, optional; needs init_image and the encoder): inpainting -- white repaints, black keeps the
+        init image.  The mask is resized like the input; the latent keep-mask is 1 - area8x8(mask) / 255, and the sampler's mask / x0
+        branch (`cldm/ddim_hacked.py:154-157`) runs over the FULL schedule from x_T (denoise_strength does not apply with a mask); the
+        decoded image is composited with the resized init image through the pixel mask, so kept pixels come back exactly."""
+        if mask_image is not None:
+            if init_image is None:
+                raise ValueError("mask_image needs init_image: the image whose unmasked pixels are kept")
+            if not getattr(self.model.rt, "vae_encoder", False):
+                raise ValueError("mask_image needs the VAE encoder: initialize(..., vae_encoder=True)")
         with torch.no_grad():
             img = resize_image(HWC3(input_image), image_resolution)
             H, W, C = img.shape
@@ -114,10 +123,11 @@ class hackathon():
                 control = torch.stack([control for _ in range(num_samples)], dim=0)
                 control = control.permute(0, 3, 1, 2).contiguous()
             return self._sample(control, prompt, a_prompt, n_prompt, num_samples, H, W, ddim_steps, guess_mode, strength, scale, seed, eta,
-                                x_T=x_T, init_image=init_image, image_resolution=image_resolution, denoise_strength=denoise_strength)
+                                x_T=x_T, init_image=init_image, image_resolution=image_resolution, denoise_strength=denoise_strength,
+                                mask_image=mask_image)
 
     def _sample(self, control, prompt, a_prompt, n_prompt, num_samples, H, W, ddim_steps, guess_mode, strength, scale, seed, eta, x_T=None,
-                init_image=None, image_resolution=None, denoise_strength=0.75):
+                init_image=None, image_resolution=None, denoise_strength=0.75, mask_image=None):
         """everything of `process` after the hint (`canny2image_torch.py:40-71`): seeding, conditioning, the DDIM loop and the decode
         to uint8 HWC images; control is the (num_samples, 3, H, W) fp32 hint on the device"""
         with torch.no_grad():
@@ -138,12 +148,48 @@ class hackathon():
                 samples, intermediates = self.ddim_sampler.sample(ddim_steps, num_samples, shape, cond, verbose=False, eta=eta,
                                                                   unconditional_guidance_scale=scale,
                                                                   unconditional_conditioning=un_cond, x_T=x_T)
-            else:
+            elif mask_image is None:
                 samples = self._img2img(init_image, image_resolution, (H, W), num_samples, cond, un_cond, ddim_steps, eta, scale,
                                         denoise_strength)
+            else:
+                return self._inpaint(init_image, mask_image, image_resolution, (H, W), num_samples, shape, cond, un_cond, ddim_steps, eta,
+                                     scale, x_T)
             x_samples = self.model.decode_first_stage_uint8(samples).cpu().numpy()
             results = [x_samples[i] for i in range(num_samples)]
         return results
+
+    def _init_latent(self, init_image, image_resolution, hw, num_samples):
+        """(resized init image HxWx3 uint8 on the host, z0 = get_first_stage_encoding(encode_first_stage(it)) for num_samples copies)"""
+        init = resize_image(HWC3(init_image), image_resolution)
+        if init.shape[:2] != tuple(hw):
+            raise ValueError(f"init_image resizes to {init.shape[:2]}, the input image to {tuple(hw)}: give them the same aspect ratio")
+        x = torch.from_numpy(np.ascontiguousarray(init)).to(self.model.device).float() / 255.0 * 2.0 - 1.0
+        x = x.permute(2, 0, 1).unsqueeze(0).expand(num_samples, -1, -1, -1).contiguous()
+        return init, self.model.get_first_stage_encoding(self.model.encode_first_stage(x))
+
+    def _inpaint(self, init_image, mask_image, image_resolution, hw, num_samples, shape, cond, un_cond, ddim_steps, eta, scale, x_T):
+        """The sampler's mask / x0 branch as a pipeline: z0 from the encoder as in `_img2img`; the pixel mask (white = repaint) resized
+        like the input; keep = 1 - area8x8(mask) / 255 as the (1, 1, H/8, W/8) latent mask (1 keeps the known latent); the full schedule
+        from x_T; decode; composite with the resized init image through the pixel mask (`sdeo_composite_u8`)."""
+        from . import ops
+        from .annotator.util import resize_u8
+        if mask_image.dtype != np.uint8 or not (mask_image.ndim == 2 or (mask_image.ndim == 3 and mask_image.shape[2] in (1, 3))):
+            raise ValueError(f"mask_image: HxW or HxWx{{1,3}} uint8 expected, got {mask_image.shape} {mask_image.dtype}")
+        device = self.model.device
+        init, z0 = self._init_latent(init_image, image_resolution, hw, num_samples)
+        m = resize_image(mask_image[:, :, None] if mask_image.ndim == 2 else mask_image, image_resolution)
+        if m.shape[:2] != tuple(hw):
+            raise ValueError(f"mask_image resizes to {m.shape[:2]}, the input image to {tuple(hw)}: give them the same aspect ratio")
+        m = torch.from_numpy(np.ascontiguousarray(m[:, :, :1])).to(device)              # (H, W, 1): the first channel
+        small = resize_u8(m, hw[0] // 8, hw[1] // 8, "area")                            # the integer-factor area resize, on the device
+        keep = (1.0 - small[:, :, 0].float() / 255.0).reshape(1, 1, hw[0] // 8, hw[1] // 8).contiguous()
+        samples, _ = self.ddim_sampler.sample(ddim_steps, num_samples, shape, cond, verbose=False, eta=eta,
+                                              unconditional_guidance_scale=scale, unconditional_conditioning=un_cond, x_T=x_T,
+                                              mask=keep, x0=z0)
+        gen = self.model.decode_first_stage_uint8(samples)
+        orig = torch.from_numpy(np.ascontiguousarray(init)).to(device)
+        plane = m[:, :, 0].contiguous()
+        return [ops.composite_u8(gen[i], orig, plane).cpu().numpy() for i in range(num_samples)]
 
     def _img2img(self, init_image, image_resolution, hw, num_samples, cond, un_cond, ddim_steps, eta, scale, denoise_strength):
         """upstream `scripts/img2img.py`: init_latent = get_first_stage_encoding(encode_first_stage(init_image)); t_enc steps of
@@ -151,13 +197,8 @@ class hackathon():
         t_enc = int(denoise_strength * ddim_steps)
         if not (denoise_strength >= 0.0 and t_enc < ddim_steps):
             raise ValueError(f"denoise_strength {denoise_strength}: t_enc = int(strength * steps) must lie in [0, {ddim_steps})")
-        init = resize_image(HWC3(init_image), image_resolution)
-        if init.shape[:2] != tuple(hw):
-            raise ValueError(f"init_image resizes to {init.shape[:2]}, the input image to {tuple(hw)}: give them the same aspect ratio")
+        _, z0 = self._init_latent(init_image, image_resolution, hw, num_samples)
         device = self.model.device
-        x = torch.from_numpy(np.ascontiguousarray(init)).to(device).float() / 255.0 * 2.0 - 1.0
-        x = x.permute(2, 0, 1).unsqueeze(0).expand(num_samples, -1, -1, -1).contiguous()
-        z0 = self.model.get_first_stage_encoding(self.model.encode_first_stage(x))
         self.ddim_sampler.make_schedule(ddim_num_steps=ddim_steps, ddim_eta=eta, verbose=False)
         z_enc = self.ddim_sampler.stochastic_encode(z0, torch.tensor([t_enc] * num_samples, device=device))
         return self.ddim_sampler.decode(z_enc, cond, t_enc, unconditional_guidance_scale=scale, unconditional_conditioning=un_cond)

@@ -59,6 +59,51 @@ def make_ddim_sampling_parameters(alphacums, ddim_timesteps, eta, verbose=True):
     return sigmas, alphas, alphas_prev
 
 
+def mask_graph_ok(model, img, mask, x0):
+    """Whether a masked call can take the whole-loop graph: the blend then runs in libsdeo with the coefficients of the model's own
+    q_sample tables, so q_sample must be the class's (an instance that replaced it keeps the per-step loop, which calls it), and the
+    operands must be what the kernels read: fp32 device tensors, x0 shaped like the latent, mask (b|1, C|1, h, w)."""
+    if x0 is None or "q_sample" in vars(model) or not hasattr(model, "sqrt_one_minus_alphas_cumprod"):
+        return False
+    ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4
+    if not (ok(mask) and ok(x0) and x0.shape == img.shape):
+        return False
+    return mask.shape[0] in (1, img.shape[0]) and mask.shape[1] in (1, img.shape[1]) and mask.shape[2:] == img.shape[2:]
+
+
+def blend_coefficients(owner, model, timesteps):
+    """[(sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t])] as host floats, one pair per step: the fp32 table entries q_sample
+    multiplies with.  One device -> host copy per schedule (cached on `owner` by the identity of the tables and the timesteps)."""
+    sa, s1 = model.sqrt_alphas_cumprod, model.sqrt_one_minus_alphas_cumprod
+    ts = tuple(int(t) for t in timesteps)
+    key = tuple((id(a), int(a._version), int(a.data_ptr())) for a in (sa, s1)) + (ts,)
+    if getattr(owner, "_blend_key", None) != key:
+        sa_h, s1_h = sa.detach().to(torch.float32).cpu(), s1.detach().to(torch.float32).cpu()
+        owner._blend_coefs = [(float(sa_h[t]), float(s1_h[t])) for t in ts]
+        owner._blend_key = key
+    return owner._blend_coefs
+
+
+def mask_operands(owner, img, mask, x0, steps):
+    """The fixed buffers the masked steps of a captured loop read, owned by the sampler `owner`: orig (the known latent), mask, and one
+    noise row per step.  Every call copies the caller's mask and x0 in and fills the rows with one torch.randn_like(x0) per step, in
+    step order: the draws q_sample makes in the per-step loop (nothing else draws when eta = 0), so a seed gives the same image on
+    both paths.  New shapes get new buffers, and the graphs captured over the old ones are dropped."""
+    key = (tuple(img.shape), tuple(mask.shape), int(steps), img.device)
+    if getattr(owner, "_mask_key", None) != key:
+        owner._mask_key = None
+        owner._loop_key = None
+        owner._loop_orig = torch.empty(img.shape, dtype=torch.float32, device=img.device)
+        owner._loop_mask = torch.empty(mask.shape, dtype=torch.float32, device=img.device)
+        owner._loop_noise = torch.empty((int(steps), *img.shape), dtype=torch.float32, device=img.device)
+        owner._mask_key = key
+    owner._loop_mask.copy_(mask)
+    owner._loop_orig.copy_(x0)
+    for row in owner._loop_noise:
+        row.copy_(torch.randn_like(x0))
+    return owner._loop_orig, owner._loop_mask, owner._loop_noise
+
+
 class DDIMSampler(object):
     def __init__(self, model, schedule="linear", **kwargs):
         super().__init__()
@@ -157,11 +202,12 @@ class DDIMSampler(object):
         time_range = list(reversed(range(0, timesteps))) if ddim_use_original_steps else np.flip(timesteps)
         total_steps = timesteps if ddim_use_original_steps else timesteps.shape[0]
         self._cache_key = None
-        if (mask is None and callback is None and img_callback is None and ucg_schedule is None and not ddim_use_original_steps
+        if (callback is None and img_callback is None and ucg_schedule is None and not ddim_use_original_steps
                 and score_corrector is None and not quantize_denoised and dynamic_threshold is None
+                and (mask is None or mask_graph_ok(self.model, img, mask, x0))
                 and self._loop_graph_ok(img, cond, unconditional_conditioning, unconditional_guidance_scale, total_steps)):
             return self._loop_graphed(img, cond, unconditional_conditioning, unconditional_guidance_scale, time_range,
-                                      total_steps, log_every_t, intermediates)
+                                      total_steps, log_every_t, intermediates, mask=mask, x0=x0)
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
@@ -196,21 +242,28 @@ class DDIMSampler(object):
 
     def _loop_graph_ok(self, img, c, uc, scale, total_steps):
         """Steps 2..S as one graph: only the plain canny2image loop qualifies -- fused CFG pair, eta = 0 (no noise drawn inside
-        the loop), eps- or v-parameterisation, no mask / callbacks / correctors (the callers check those)."""
+        the loop), eps- or v-parameterisation, no callbacks / correctors, a mask only when `mask_graph_ok` (the callers check those)."""
         if not (USE_GRAPH and USE_LOOP_GRAPH and img.is_cuda and total_steps >= 2 and self._fusable(c, uc, scale)):
             return False
         if self.model.parameterization not in ("eps", "v"):
             return False
         return bool(getattr(self, "_sigmas_all_zero", False))      # computed with the schedule: no device -> host copy per image
 
-    def _loop_graphed(self, img, c, uc, scale, time_range, total_steps, log_every_t, intermediates):
+    def _loop_graphed(self, img, c, uc, scale, time_range, total_steps, log_every_t, intermediates, mask=None, x0=None):
         """The loop of `cldm/ddim_hacked.py:137-160` with step 1 run eagerly (it computes the hint block and the context K / V of
         THIS image into the runtime's caches) and steps 2..S replayed from one captured graph.  The graph reads the latent from a
         fixed buffer and the conditioning from those caches, so it is reused for every image of the same shape, step count,
-        guidance scale and control scales; per-step constants (alpha_t, ...) are baked in at capture."""
+        guidance scale and control scales; per-step constants (alpha_t, ...) are baked in at capture.
+        With a mask (`:154-157`) every step starts with the blend img = q_sample(x0, t) * mask + (1 - mask) * img: step 1 calls
+        ops.mask_blend, the captured steps are sdeo_ddim_step_masked calls that read x0, the mask and their noise row from the
+        sampler's fixed buffers (`mask_operands`); the blend coefficients are baked in like the other per-step constants."""
         m, rt = self.model, self.model.rt
         b = img.shape[0]
         dev = img.device
+        if mask is not None:
+            coefs = blend_coefficients(self, m, time_range)
+            orig, mask_buf, noise = mask_operands(self, img, mask, x0, total_steps)
+            img = ops.mask_blend(img.clone(memory_format=torch.contiguous_format), orig, noise[0], mask_buf, *coefs[0])
         ts = torch.full((b,), int(time_range[0]), device=dev, dtype=torch.long)
         img, pred_x0 = self.p_sample_ddim(img, c, ts, index=total_steps - 1, unconditional_guidance_scale=scale,
                                           unconditional_conditioning=uc)
@@ -221,7 +274,7 @@ class DDIMSampler(object):
         hint_shared = self._ident(c["c_concat"]) == self._ident(uc["c_concat"])
         key = (rt.generation, tuple(img.shape), tuple(int(t) for t in time_range), float(scale), int(log_every_t),
                tuple(float(v) for v in m.control_scales), bool(m.only_mid_control), getattr(self, "_schedule_key", None), LOOP_GRAPH_STEPS,
-               hint_shared, m.parameterization)
+               hint_shared, m.parameterization, None if mask is None else tuple(mask.shape))
         if getattr(rt, "_table_key", None) != (rt.generation, tuple(int(t) for t in time_range)):
             rt.set_timestep_table(time_range)            # another schedule used the runtime since (the graphs read the table by address)
         if getattr(self, "_loop_key", None) != key:
@@ -240,9 +293,14 @@ class DDIMSampler(object):
                 with torch.cuda.graph(g):
                     for i in range(first, min(first + per_graph, total_steps)):
                         index = total_steps - i - 1
-                        rt.ddim_step(self._loop_x, self._loop_pred, i, scale, float(a_t[index]), float(a_p[index]), float(s1m[index]),
-                                     m.control_scales, m.only_mid_control, staged=i > first, hint_shared=hint_shared,
-                                     v_prediction=m.parameterization == "v")
+                        if mask is None:
+                            rt.ddim_step(self._loop_x, self._loop_pred, i, scale, float(a_t[index]), float(a_p[index]), float(s1m[index]),
+                                         m.control_scales, m.only_mid_control, staged=i > first, hint_shared=hint_shared,
+                                         v_prediction=m.parameterization == "v")
+                        else:
+                            rt.ddim_step_masked(self._loop_x, self._loop_pred, orig, noise[i], mask_buf, *coefs[i], i, scale,
+                                                float(a_t[index]), float(a_p[index]), float(s1m[index]), m.control_scales,
+                                                m.only_mid_control, hint_shared=hint_shared, v_prediction=m.parameterization == "v")
                         if index % log_every_t == 0:
                             kept_x.append(self._loop_x.clone())
                             kept_p.append(self._loop_pred.clone())

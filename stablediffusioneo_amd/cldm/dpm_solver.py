@@ -11,8 +11,8 @@ The host folds all of it into three fp64 coefficients per step, x_next = k_x x +
 (`sdeo_cfg_dpmpp_2m_step`, `sdeo_dpmpp_2m_step`) never sees lambda.  The only state next to the latent is one fp32 tensor, D_prev.
 
 The loop has the shape of `DDIMSampler._loop_graphed`: step 1 runs eagerly (it fills the runtime's hint / context caches), steps 2..S are
-replayed from a captured graph with the per-step coefficients baked in; what does not qualify (mask, callbacks, no ControlNet hint on
-one half, scale == 1, a model without a runtime) runs one step at a time.  The switches are ddim_hacked's (SDEO_GRAPH,
+replayed from a captured graph with the per-step coefficients baked in (with a mask: the masked steps, `ddim_hacked.mask_operands`); what
+does not qualify (callbacks, a replaced q_sample, no ControlNet hint on one half, scale == 1, a model without a runtime) runs one step at a time.  The switches are ddim_hacked's (SDEO_GRAPH,
 SDEO_LOOP_GRAPH, SDEO_LOOP_GRAPH_STEPS)."""
 from __future__ import annotations
 
@@ -132,9 +132,9 @@ class DPMSolverSampler(object):
         c, uc, scale = conditioning, unconditional_conditioning, unconditional_guidance_scale
         self._pair._cache_key = None
         total_steps = int(self.timesteps.shape[0])
-        if (mask is None and callback is None and img_callback is None and ucg_schedule is None
+        if (callback is None and img_callback is None and ucg_schedule is None and (mask is None or dh.mask_graph_ok(self.model, img, mask, x0))
                 and self._loop_graph_ok(img, c, uc, scale, total_steps)):
-            return self._loop_graphed(img, c, uc, scale, total_steps, log_every_t, intermediates)
+            return self._loop_graphed(img, c, uc, scale, total_steps, log_every_t, intermediates, mask=mask, x0=x0)
         if mask is not None:
             assert x0 is not None
         x = self._run(img, c, uc, scale, self.timesteps, self.alphas, self.k_x, self.k_d, self.k_p, mask=mask, x0=x0, callback=callback,
@@ -179,7 +179,9 @@ class DPMSolverSampler(object):
         return bool(dh.USE_GRAPH and dh.USE_LOOP_GRAPH and img.is_cuda and total_steps >= 2 and self._pair._fusable(c, uc, scale)
                     and self.model.parameterization in ("eps", "v"))
 
-    def _loop_graphed(self, img, c, uc, scale, total_steps, log_every_t, intermediates):
+    def _loop_graphed(self, img, c, uc, scale, total_steps, log_every_t, intermediates, mask=None, x0=None):
+        """With a mask every step starts with x = q_sample(x0, t) * mask + (1 - mask) * x, as in `_run`: ops.mask_blend in front of the eager
+        step 1, sdeo_dpmpp_2m_step_masked for the captured steps (operands: `ddim_hacked.mask_operands`)."""
         m, rt = self.model, self.model.rt
         ts, a_t, k_x, k_d, k_p = self.timesteps, self.alphas, self.k_x, self.k_d, self.k_p
         time_range = tuple(int(t) for t in ts)
@@ -188,7 +190,12 @@ class DPMSolverSampler(object):
         per_graph = dh.LOOP_GRAPH_STEPS if dh.LOOP_GRAPH_STEPS > 0 else total_steps
         # (rt.generation is read after step 1: the first forward at a new shape re-plans the runtime)
         shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), tuple(float(v) for v in m.control_scales),
-                     bool(m.only_mid_control), self._schedule_key, per_graph, hint_shared, m.parameterization)
+                     bool(m.only_mid_control), self._schedule_key, per_graph, hint_shared, m.parameterization,
+                     None if mask is None else tuple(mask.shape))
+        if mask is not None:
+            coefs = dh.blend_coefficients(self, m, ts)
+            orig, mask_buf, noise = dh.mask_operands(self, img, mask, x0, total_steps)
+            img = ops.mask_blend(img.clone(memory_format=torch.contiguous_format), orig, noise[0], mask_buf, *coefs[0])
         if self._loop_key is None or self._loop_key[1:] != shape_key:
             self._loop_key = None
             self._loop_x = torch.empty_like(img, memory_format=torch.contiguous_format)
@@ -210,9 +217,14 @@ class DPMSolverSampler(object):
                 with torch.cuda.graph(g):
                     for i in range(first, min(first + per_graph, total_steps)):
                         a = float(a_t[i])
-                        rt.dpmpp_2m_step(self._loop_x, self._loop_d, i, scale, a, float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]),
-                                         float(k_p[i]), m.control_scales, m.only_mid_control, staged=i > first, hint_shared=hint_shared,
-                                         v_prediction=v_pred)
+                        if mask is None:
+                            rt.dpmpp_2m_step(self._loop_x, self._loop_d, i, scale, a, float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]),
+                                             float(k_p[i]), m.control_scales, m.only_mid_control, staged=i > first, hint_shared=hint_shared,
+                                             v_prediction=v_pred)
+                        else:
+                            rt.dpmpp_2m_step_masked(self._loop_x, self._loop_d, orig, noise[i], mask_buf, *coefs[i], i, scale, a,
+                                                    float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]), float(k_p[i]), m.control_scales,
+                                                    m.only_mid_control, hint_shared=hint_shared, v_prediction=v_pred)
                         if (total_steps - i - 1) % log_every_t == 0:
                             kept_x.append(self._loop_x.clone())
                             kept_d.append(self._loop_d.clone())

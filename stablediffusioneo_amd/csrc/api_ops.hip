@@ -427,6 +427,15 @@ int sdeo_cfg_dpmpp_2m_step(float* x_next, float* d, const float* x, const float*
                       S(stream));
 }
 
+int sdeo_mask_blend(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a,
+                    float sqrt_one_minus_a, int n, int c, int hw, void* stream) {
+  return mask_blend(x, orig, noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a, n, c, hw, S(stream));
+}
+
+int sdeo_composite_u8(uint8_t* dst, const uint8_t* gen, const uint8_t* orig, const uint8_t* mask, int h, int w, int c, void* stream) {
+  return composite_u8(dst, gen, orig, mask, h, w, c, S(stream));
+}
+
 int sdeo_nchw_f32_to_nhwc_f16(void* y, int ldy, const float* x, int n, int c, int hw, void* stream) {
   return nchw_f32_to_nhwc_f16((f16*)y, ldy, x, n, c, hw, 1.0f, S(stream));
 }

@@ -379,6 +379,119 @@ int latent_pair_to_nhwc(f16* x0, int ld0, const float* x, int b, int C, int HW, 
   return 0;
 }
 
+// The sampler's mask / x0 blend (cldm/ddim_hacked.py:154-157): x <- mask * q_sample(orig) + (1 - mask) * x with
+// q_sample(orig) = sqrt_a * orig + sqrt_1ma * noise.  The eager loop evaluates this as seven separate torch kernels, each rounding once;
+// hipcc's default (-ffp-contract=fast) fuses a product into the sum that follows it.  HIP's __fmul_rn / __fadd_rn state the intent but are
+// plain operators to the compiler, and `#pragma clang fp contract(off)` does not reach the backend's combiner either: with both, q still
+// came out as ONE v_pk_fma_f32 (product unrounded).  So every product passes through an empty asm statement: the compiler must hold the
+// rounded fp32 value in a register there and cannot see through it to fuse.  It costs no instruction.  Checked in the ISA of both
+// kernels: four multiplies, a subtract and two adds, no fma.
+__device__ __forceinline__ float rounded(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+__device__ __forceinline__ float mask_blend_elem(float x, float orig, float noise, float m, float sqrt_a, float sqrt_1ma) {
+  const float q = __fadd_rn(rounded(__fmul_rn(sqrt_a, orig)), rounded(__fmul_rn(sqrt_1ma, noise)));
+  return __fadd_rn(rounded(__fmul_rn(q, m)), rounded(__fmul_rn(__fsub_rn(1.0f, m), x)));
+}
+
+// mask [mask_n][mask_c][HW], mask_n in {1, n}, mask_c in {1, C}: the element of image n, channel c, pixel pix
+__device__ __forceinline__ int64_t mask_index(int64_t n, int64_t c, int64_t pix, int mask_n, int mask_c, int HW) {
+  return ((mask_n == 1 ? 0 : n) * mask_c + (mask_c == 1 ? 0 : c)) * HW + pix;
+}
+
+// fp32 NCHW operands [n][C][HW], one thread per element; x is read and written by the same thread at the same index
+__global__ __launch_bounds__(256) void mask_blend_kernel(float* x, const float* __restrict__ orig, const float* __restrict__ noise,
+                                                         const float* __restrict__ mask, int mask_n, int mask_c, float sqrt_a,
+                                                         float sqrt_1ma, int64_t total, int C, int HW) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t plane = i / HW, pix = i - plane * HW;
+    const int64_t n = plane / C, c = plane - n * C;
+    x[i] = mask_blend_elem(x[i], orig[i], noise[i], mask[mask_index(n, c, pix, mask_n, mask_c, HW)], sqrt_a, sqrt_1ma);
+  }
+}
+
+// The blend as the front of a fused CFG-pair step, laid out as latent_pair_kernel (one thread per (image, pixel)): x [b][C][HW] is
+// blended in place and its fp16 NHWC copy goes to both halves of the pair, padding channels zero.
+__global__ __launch_bounds__(256) void mask_blend_pair_kernel(float* x, const float* __restrict__ orig, const float* __restrict__ noise,
+                                                              const float* __restrict__ mask, int mask_n, int mask_c, float sqrt_a,
+                                                              float sqrt_1ma, f16* __restrict__ x0, int ld0, int b, int C, int HW) {
+  const int64_t total = (int64_t)b * HW;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t n = i / HW, pix = i - n * HW;
+    for (int c = 0; c < ld0; ++c) {
+      f16 v = (f16)0.f;
+      if (c < C) {
+        const int64_t j = (n * C + c) * HW + pix;
+        const float xb = mask_blend_elem(x[j], orig[j], noise[j], mask[mask_index(n, c, pix, mask_n, mask_c, HW)], sqrt_a, sqrt_1ma);
+        x[j] = xb;
+        v = (f16)xb;
+      }
+      x0[i * ld0 + c] = v;
+      x0[(i + total) * ld0 + c] = v;
+    }
+  }
+}
+
+int mask_blend_check(const char* who, const float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c,
+                     int n, int C, int HW) {
+  SDEO_CHECK(x, "%s: null latent", who);
+  SDEO_CHECK(orig, "%s: null orig (the known latent)", who);
+  SDEO_CHECK(noise, "%s: null noise", who);
+  SDEO_CHECK(mask, "%s: null mask", who);
+  SDEO_CHECK(n > 0 && C > 0 && HW > 0, "%s: empty latent (n=%d c=%d hw=%d)", who, n, C, HW);
+  SDEO_CHECK(mask_n == 1 || mask_n == n, "%s: mask_n=%d, but the mask holds 1 or n=%d images", who, mask_n, n);
+  SDEO_CHECK(mask_c == 1 || mask_c == C, "%s: mask_c=%d, but the mask holds 1 or c=%d channels", who, mask_c, C);
+  return 0;
+}
+
+int mask_blend(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a, float sqrt_1ma,
+               int n, int C, int HW, hipStream_t stream) {
+  if (int rc = mask_blend_check("mask_blend", x, orig, noise, mask, mask_n, mask_c, n, C, HW)) return rc;
+  const int64_t total = (int64_t)n * C * HW;
+  hipLaunchKernelGGL(mask_blend_kernel, grid_for(total), dim3(256), 0, stream, x, orig, noise, mask, mask_n, mask_c, sqrt_a, sqrt_1ma, total,
+                     C, HW);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
+int mask_blend_pair(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a,
+                    float sqrt_1ma, f16* x0, int ld0, int b, int C, int HW, hipStream_t stream) {
+  if (int rc = mask_blend_check("mask_blend_pair", x, orig, noise, mask, mask_n, mask_c, b, C, HW)) return rc;
+  SDEO_CHECK(x0 && ld0 >= C, "mask_blend_pair: bad staging operand");
+  hipLaunchKernelGGL(mask_blend_pair_kernel, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, orig, noise, mask, mask_n, mask_c, sqrt_a,
+                     sqrt_1ma, x0, ld0, b, C, HW);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
+// dst = (gen * m + orig * (255 - m) + 127) / 255 in integers: uint8 HWC images of C channels, uint8 [H][W] mask; one thread per pixel
+__global__ __launch_bounds__(256) void composite_u8_kernel(uint8_t* __restrict__ dst, const uint8_t* __restrict__ gen,
+                                                           const uint8_t* __restrict__ orig, const uint8_t* __restrict__ mask,
+                                                           int64_t pixels, int C) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pixels; i += (int64_t)gridDim.x * 256) {
+    const int m = mask[i];
+    for (int c = 0; c < C; ++c) {
+      const int64_t j = i * C + c;
+      dst[j] = (uint8_t)(((int)gen[j] * m + (int)orig[j] * (255 - m) + 127) / 255);
+    }
+  }
+}
+
+int composite_u8(uint8_t* dst, const uint8_t* gen, const uint8_t* orig, const uint8_t* mask, int H, int W, int C, hipStream_t stream) {
+  SDEO_CHECK(dst && gen && orig && mask, "composite_u8: null argument");
+  SDEO_CHECK(H >= 1 && W >= 1 && C >= 1 && C <= 4, "composite_u8: h=%d w=%d c=%d (h, w >= 1, c in 1..4)", H, W, C);
+  const int64_t pixels = (int64_t)H * W;
+  hipLaunchKernelGGL(composite_u8_kernel, grid_for(pixels), dim3(256), 0, stream, dst, gen, orig, mask, pixels, C);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
+int cfg_ddim_pair_check(const char* who, float a_t, float a_prev) {
+  SDEO_CHECK(a_t > 0.f && (1.f - a_prev) >= 0.f, "%s: invalid schedule a_t=%g a_prev=%g", who, a_t, a_prev);
+  return 0;
+}
+
 int cfg_ddim_step(float* x_prev, float* pred_x0, const float* x, const float* eps_c, const float* eps_u, const float* noise,
                   float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, int64_t n, bool v_prediction,
                   hipStream_t stream) {
@@ -450,7 +563,7 @@ __global__ __launch_bounds__(256) void cfg_lms_pair_kernel(float* __restrict__ x
   }
 }
 
-static int lms_coefs_ok(const char* who, const float* d, float a_t, float k_x, float k_d, float k_p) {
+int lms_coefs_ok(const char* who, const float* d, float a_t, float k_x, float k_d, float k_p) {
   SDEO_CHECK(a_t > 0.f, "%s: invalid schedule a_t=%g", who, a_t);
   SDEO_CHECK(std::isfinite(k_x) && std::isfinite(k_d) && std::isfinite(k_p), "%s: non-finite coefficient k_x=%g k_d=%g k_p=%g", who, k_x, k_d,
              k_p);

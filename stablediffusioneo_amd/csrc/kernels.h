@@ -248,5 +248,21 @@ int cfg_lms_pair(float* x, float* d, const f16* eps, int lde, f16* x0, int ld0, 
                  float sqrt_one_minus_at, float k_x, float k_d, float k_p, bool v_prediction, hipStream_t stream);
 int cfg_lms_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, float cfg_scale, float a_t,
                  float sqrt_one_minus_at, float k_x, float k_d, float k_p, int64_t n, bool v_prediction, hipStream_t stream);
+// host-side checks of the two pair updates (no device call), for callers that must refuse before they launch anything
+int cfg_ddim_pair_check(const char* who, float a_t, float a_prev);
+int lms_coefs_ok(const char* who, const float* d, float a_t, float k_x, float k_d, float k_p);
+// The sampler's mask / x0 blend (cldm/ddim_hacked.py:154-157) on fp32 NCHW latents [n][C][HW], in place:
+//   x <- mask * (sqrt_a * orig + sqrt_1ma * noise) + (1 - mask) * x,   mask [mask_n][mask_c][HW], mask_n in {1, n}, mask_c in {1, C}
+// rounded operation by operation like the torch expression (no fma contraction).  mask_blend_pair: the same blend as the front of a fused
+// CFG-pair step, in the layout of latent_pair_to_nhwc, whose place it takes: the fp16 NHWC copy of the blended latent goes to both halves
+// of x0 (padding channels zero).  mask_blend_check: their operand checks alone (host only).
+int mask_blend_check(const char* who, const float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c,
+                     int n, int C, int HW);
+int mask_blend(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a, float sqrt_1ma,
+               int n, int C, int HW, hipStream_t stream);
+int mask_blend_pair(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a,
+                    float sqrt_1ma, f16* x0, int ld0, int b, int C, int HW, hipStream_t stream);
+// dst = (gen * m + orig * (255 - m) + 127) / 255 in integers: uint8 HWC images [H][W][C], C in 1..4, uint8 mask [H][W]
+int composite_u8(uint8_t* dst, const uint8_t* gen, const uint8_t* orig, const uint8_t* mask, int H, int W, int C, hipStream_t stream);
 
 }  // namespace sdeo

@@ -1707,40 +1707,93 @@ int sdeo_set_timestep_table(sdeo_handle h, const int64_t* host_timesteps, int co
   return 0;
 }
 
+// The mask / x0 blend a masked step puts in front of its forward (mask_blend_pair); null for an unmasked step.
+struct StepBlend {
+  const float* orig; const float* noise; const float* mask;
+  int mask_n, mask_c;
+  float sqrt_a, sqrt_1ma;
+};
+
 // What every fused CFG-pair step does before its update kernel: the checks, the time-embedding row, the control scales, the fp16 copy of
-// [x; x] unless the previous step staged it, and the networks.  Leaves the model output in h->eps16.
-static int cfg_pair_forward(sdeo_handle h, const float* x, int table_row, const float* host_control_scales, int only_mid_control, int flags,
-                            const char* who, hipStream_t s) {
+// [x; x] unless the previous step staged it, and the networks.  Leaves the model output in h->eps16.  With a blend, x is first replaced
+// by the blended latent, in the launch that stages its fp16 copy.  Every check precedes the first device call.
+static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float* host_control_scales, int only_mid_control, int flags,
+                            const StepBlend* blend, const char* who, hipStream_t s) {
   REQUIRE_READY(h);
   SDEO_CHECK(x, "%s: null latent", who);
   SDEO_CHECK(h->cfg.in_channels == h->cfg.out_channels, "%s: eps and latent must have the same channel count", who);
   SDEO_CHECK(h->N % 2 == 0, "%s: configured for %d images; the CFG pair needs an even count (n = 2 x latents)", who, h->N);
   SDEO_CHECK(table_row >= 0 && table_row < h->tab_count, "%s: timestep row %d, but the table holds %d (sdeo_set_timestep_table)", who,
              table_row, h->tab_count);
+  if (blend) {
+    SDEO_CHECK(!(flags & SDEO_STEP_LATENT_STAGED), "%s: SDEO_STEP_LATENT_STAGED has no meaning here (the blend changes the latent and always restages it)", who);
+    if (int rc = mask_blend_check(who, x, blend->orig, blend->noise, blend->mask, blend->mask_n, blend->mask_c, h->N / 2, h->cfg.in_channels,
+                                  h->lh * h->lw))
+      return rc;
+  }
   int trow = -1;
   if (int rc = select_time(h, 8 | (table_row << 8), nullptr, who, &trow)) return rc;
   set_scales(h, host_control_scales, only_mid_control);
-  if (!(flags & 16))
+  if (blend) {
+    if (int rc = mask_blend_pair(x, blend->orig, blend->noise, blend->mask, blend->mask_n, blend->mask_c, blend->sqrt_a, blend->sqrt_1ma,
+                                 h->x0.p, h->x0.ld, h->N / 2, h->cfg.in_channels, h->lh * h->lw, s))
+      return rc;
+  } else if (!(flags & SDEO_STEP_LATENT_STAGED)) {
     if (int rc = latent_pair_to_nhwc(h->x0.p, h->x0.ld, x, h->N / 2, h->cfg.in_channels, h->lh * h->lw, s)) return rc;
+  }
   // x0 = [x; x] at one timestep: the UNet's shared prefix always holds, the ControlNet's when the caller vouches for the hints
   return run_step_programs(h, false, true, s, true, (flags & SDEO_STEP_HINT_SHARED) != 0);
 }
 
-int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
-                   float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
-  hipStream_t s = S(stream);
-  if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, "sdeo_ddim_step", s)) return rc;
+static int ddim_step_impl(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
+                          float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, const StepBlend* blend,
+                          const char* who, hipStream_t s) {
+  if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, blend, who, s)) return rc;
   return cfg_ddim_pair(x, pred_x0, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw, cfg_scale, a_t,
                        a_prev, sqrt_one_minus_at, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
 }
 
-int sdeo_dpmpp_2m_step(sdeo_handle h, float* x, float* d, int table_row, float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x,
-                       float k_d, float k_p, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
-  hipStream_t s = S(stream);
-  SDEO_CHECK(d || k_p == 0.f, "sdeo_dpmpp_2m_step: k_p=%g needs the previous data prediction, but d is null", k_p);
-  if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, "sdeo_dpmpp_2m_step", s)) return rc;
+static int dpmpp_2m_step_impl(sdeo_handle h, float* x, float* d, int table_row, float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x,
+                              float k_d, float k_p, const float* host_control_scales, int only_mid_control, int flags, const StepBlend* blend,
+                              const char* who, hipStream_t s) {
+  SDEO_CHECK(d || k_p == 0.f, "%s: k_p=%g needs the previous data prediction, but d is null", who, k_p);
+  if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, blend, who, s)) return rc;
   return cfg_lms_pair(x, d, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw, cfg_scale, a_t,
                       sqrt_one_minus_at, k_x, k_d, k_p, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
+}
+
+int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
+                   float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
+  return ddim_step_impl(h, x, pred_x0, table_row, cfg_scale, a_t, a_prev, sqrt_one_minus_at, host_control_scales, only_mid_control, flags,
+                        nullptr, "sdeo_ddim_step", S(stream));
+}
+
+int sdeo_dpmpp_2m_step(sdeo_handle h, float* x, float* d, int table_row, float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x,
+                       float k_d, float k_p, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
+  return dpmpp_2m_step_impl(h, x, d, table_row, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, host_control_scales, only_mid_control,
+                            flags, nullptr, "sdeo_dpmpp_2m_step", S(stream));
+}
+
+// The masked steps change x before the networks run, so what the update kernel would refuse after them is refused here, up front.
+int sdeo_ddim_step_masked(sdeo_handle h, float* x, float* pred_x0, const float* orig, const float* noise, const float* mask, int mask_n,
+                          int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row, float cfg_scale, float a_t, float a_prev,
+                          float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
+  const char* who = "sdeo_ddim_step_masked";
+  if (int rc = cfg_ddim_pair_check(who, a_t, a_prev)) return rc;
+  const StepBlend blend{orig, noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
+  return ddim_step_impl(h, x, pred_x0, table_row, cfg_scale, a_t, a_prev, sqrt_one_minus_at, host_control_scales, only_mid_control, flags,
+                        &blend, who, S(stream));
+}
+
+int sdeo_dpmpp_2m_step_masked(sdeo_handle h, float* x, float* d, const float* orig, const float* noise, const float* mask, int mask_n,
+                              int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row, float cfg_scale, float a_t,
+                              float sqrt_one_minus_at, float k_x, float k_d, float k_p, const float* host_control_scales,
+                              int only_mid_control, int flags, void* stream) {
+  const char* who = "sdeo_dpmpp_2m_step_masked";
+  if (int rc = lms_coefs_ok(who, d, a_t, k_x, k_d, k_p)) return rc;
+  const StepBlend blend{orig, noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
+  return dpmpp_2m_step_impl(h, x, d, table_row, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, host_control_scales, only_mid_control,
+                            flags, &blend, who, S(stream));
 }
 
 int sdeo_vae_decode(sdeo_handle h, const float* z, int n, float* images, uint8_t* images_u8, void* stream) {

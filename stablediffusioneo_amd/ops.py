@@ -476,6 +476,44 @@ def cfg_dpmpp_2m_step(x, m_c, m_u, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, 
     return x_next
 
 
+def mask_dims(mask, x):
+    """(mask_n, mask_c) of a mask torch would broadcast against the (n, C, h, w) latent x: shape (n|1, C|1, h, w)"""
+    n, c, h, w = x.shape
+    if mask.dim() != 4 or mask.shape[0] not in (1, n) or mask.shape[1] not in (1, c) or tuple(mask.shape[2:]) != (h, w):
+        raise _lib.SdeoError(f"mask of shape {tuple(mask.shape)} against a latent of shape {tuple(x.shape)}: ({n}|1, {c}|1, {h}, {w}) expected")
+    return int(mask.shape[0]), int(mask.shape[1])
+
+
+def mask_blend(x, orig, noise, mask, sqrt_a, sqrt_one_minus_a):
+    """`sdeo_mask_blend`: x <- mask * (sqrt_a * orig + sqrt_one_minus_a * noise) + (1 - mask) * x IN PLACE on the fp32 (n, C, h, w) latent
+    x, bit-equal to the sampler's torch expression `q_sample(x0, t) * mask + (1 - mask) * img`; mask is (n|1, C|1, h, w) fp32.  Returns x."""
+    lib = _lib.load()
+    _need_cuda(x, orig, noise, mask)
+    for t in (x, orig, noise, mask):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert orig.shape == x.shape and noise.shape == x.shape
+    mn, mc = mask_dims(mask, x)
+    n, c, h, w = x.shape
+    check(lib.sdeo_mask_blend(ptr(x), ptr(orig), ptr(noise), ptr(mask), mn, mc, sqrt_a, sqrt_one_minus_a, n, c, h * w, cur_stream()),
+          "mask_blend")
+    return x
+
+
+def composite_u8(gen, orig, mask):
+    """`sdeo_composite_u8`: (gen * m + orig * (255 - m) + 127) // 255 on uint8 (H, W, C) device images, C in 1..4, with a uint8 (H, W) mask"""
+    lib = _lib.load()
+    _need_cuda(gen, orig, mask)
+    if gen.dtype != torch.uint8 or gen.dim() != 3 or orig.dtype != torch.uint8 or orig.shape != gen.shape:
+        raise _lib.SdeoError(f"composite_u8: two uint8 (H, W, C) images expected, got {tuple(gen.shape)} {gen.dtype} and {tuple(orig.shape)} {orig.dtype}")
+    h, w, c = gen.shape
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (h, w):
+        raise _lib.SdeoError(f"composite_u8: a uint8 ({h}, {w}) mask expected, got {tuple(mask.shape)} {mask.dtype}")
+    gen, orig, mask = gen.contiguous(), orig.contiguous(), mask.contiguous()
+    dst = torch.empty_like(gen)
+    check(lib.sdeo_composite_u8(ptr(dst), ptr(gen), ptr(orig), ptr(mask), h, w, c, cur_stream()), "composite_u8")
+    return dst
+
+
 def nchw_to_nhwc_f16(x, c_pad=None):
     lib = _lib.load()
     _need_cuda(x)

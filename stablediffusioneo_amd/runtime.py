@@ -319,6 +319,43 @@ class SdeoRuntime(_HandleRuntime):
                                           | (STEP_V_PREDICTION if v_prediction else 0), cur_stream()), "dpmpp_2m_step")
         return x
 
+    def _blend_args(self, x, orig, noise, mask):
+        """the operand block the two masked steps share: pointers and the mask's broadcast dims, after the checks ctypes cannot make"""
+        from .ops import mask_dims
+        for t in (orig, noise):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.shape == x.shape
+        assert mask.is_contiguous() and mask.dtype == torch.float32
+        mn, mc = mask_dims(mask, x)
+        return ptr(orig), ptr(noise), ptr(mask), mn, mc
+
+    def ddim_step_masked(self, x, pred_x0, orig, noise, mask, sqrt_a: float, sqrt_one_minus_a: float, row: int, cfg_scale: float, a_t: float,
+                         a_prev: float, sqrt_one_minus_at: float, scales=None, only_mid_control: bool = False, hint_shared: bool = False,
+                         v_prediction: bool = False, flags: int = 0):
+        """`sdeo_ddim_step_masked`: x <- mask * (sqrt_a orig + sqrt_one_minus_a noise) + (1 - mask) x, then `ddim_step` on it, both in
+        place; bit-identical to `ops.mask_blend` followed by the unstaged `ddim_step`.  There is no `staged`: the blend always restages
+        (flags: extra SDEO_STEP_* bits as they are, for the tests of what the library refuses)."""
+        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
+        assert pred_x0 is None or (pred_x0.is_contiguous() and pred_x0.dtype == torch.float32 and pred_x0.shape == x.shape)
+        check(self.lib.sdeo_ddim_step_masked(self.handle, ptr(x), ptr(pred_x0), *self._blend_args(x, orig, noise, mask), sqrt_a,
+                                             sqrt_one_minus_a, int(row), cfg_scale, a_t, a_prev, sqrt_one_minus_at, self._scales(scales),
+                                             int(only_mid_control),
+                                             flags | (STEP_HINT_SHARED if hint_shared else 0) | (STEP_V_PREDICTION if v_prediction else 0),
+                                             cur_stream()), "ddim_step_masked")
+        return x
+
+    def dpmpp_2m_step_masked(self, x, d, orig, noise, mask, sqrt_a: float, sqrt_one_minus_a: float, row: int, cfg_scale: float, a_t: float,
+                             sqrt_one_minus_at: float, k_x: float, k_d: float, k_p: float, scales=None, only_mid_control: bool = False,
+                             hint_shared: bool = False, v_prediction: bool = False, flags: int = 0):
+        """`sdeo_dpmpp_2m_step_masked`: the blend of `ddim_step_masked`, then `dpmpp_2m_step` on the blended latent"""
+        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
+        assert d is None or (d.is_contiguous() and d.dtype == torch.float32 and d.shape == x.shape)
+        check(self.lib.sdeo_dpmpp_2m_step_masked(self.handle, ptr(x), ptr(d), *self._blend_args(x, orig, noise, mask), sqrt_a,
+                                                 sqrt_one_minus_a, int(row), cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p,
+                                                 self._scales(scales), int(only_mid_control),
+                                                 flags | (STEP_HINT_SHARED if hint_shared else 0) | (STEP_V_PREDICTION if v_prediction else 0),
+                                                 cur_stream()), "dpmpp_2m_step_masked")
+        return x
+
     def vae_decode(self, z, want_u8: bool = False):
         """z (b,4,h,w) latents (sampler output) -> images (b,3,8h,8w) fp32 in [-1,1] (+ optional NHWC uint8)."""
         v = self.vcfg
