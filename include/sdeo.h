@@ -139,6 +139,15 @@ int sdeo_cfg_ddim_step_v(float* x_prev, float* pred_x0, const float* x, const fl
 int sdeo_cfg_dpmpp_2m_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, float cfg_scale, float a_t,
                            float sqrt_one_minus_at, float k_x, float k_d, float k_p, int flags, int64_t n, void* stream);
 
+/* The stochastic member of the same family, DPM-Solver++(2M) SDE: sdeo_cfg_dpmpp_2m_step with a fourth term,
+ *   x_next = k_x x + k_d D + k_p D_prev + k_n noise,   d <- D,
+ * noise fp32, n elements like x; the host folds exp(-eta h) and the noise level into the four coefficients (cldm/dpm_solver.py,
+ * sde_coefficients).  noise may be NULL only when k_n == 0: then this IS sdeo_cfg_dpmpp_2m_step (the same launch, the same bits).  A
+ * null noise with k_n != 0 and a non-finite k_n are refused before any device call, next to what sdeo_cfg_dpmpp_2m_step refuses. */
+int sdeo_cfg_dpmpp_2m_sde_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, const float* noise,
+                               float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n,
+                               int flags, int64_t n, void* stream);
+
 /* The sampler's mask / x0 blend (cldm/ddim_hacked.py:154-157: img = q_sample(x0, t) * mask + (1 - mask) * img) on fp32 NCHW latents,
  * IN PLACE on x:   x <- mask * (sqrt_a * orig + sqrt_one_minus_a * noise) + (1 - mask) * x
  *   x, orig, noise [n][c][hw];  mask [mask_n][mask_c][hw] with mask_n in {1, n} and mask_c in {1, c} (the broadcasts torch allows a
@@ -324,6 +333,34 @@ int sdeo_dpmpp_2m_step_masked(sdeo_handle h, float* x, float* d, const float* or
                               int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row, float cfg_scale, float a_t,
                               float sqrt_one_minus_at, float k_x, float k_d, float k_p, const float* host_control_scales,
                               int only_mid_control, int flags, void* stream);
+
+/* The fused CFG-pair steps with the sampler's noise term (cldm/ddim_hacked.py:227-230, eta > 0; DPM-Solver++(2M) SDE), IN PLACE on x:
+ *   sdeo_ddim_step_eta:      x <- x_prev + sigma_t * noise, with dir_coef = sqrt(1 - a_prev - sigma_t^2) inside x_prev
+ *   sdeo_dpmpp_2m_sde_step:  x <- k_x x + k_d D + k_p d + k_n * noise,  d <- D
+ * noise [n/2][4][h][w] fp32, read by address (a captured call reads whatever the row holds at replay); the fp16 staging of the next
+ * forward is written from the noisy latent.  orig == NULL: the unmasked step (mask_noise and mask must then be NULL too); else the blend
+ * of sdeo_ddim_step_masked runs in front, with mask_noise as its noise operand, and orig / mask_noise / mask / mask_n / mask_c / sqrt_a /
+ * sqrt_one_minus_a mean what they mean there.  Every other argument as in sdeo_ddim_step / sdeo_dpmpp_2m_step.
+ * Contract:
+ *   - sdeo_ddim_step_eta is bit-identical to sdeo_apply_model on [x; x] followed by sdeo_cfg_ddim_step(_v) with the same noise and
+ *     sigma_t (the noise product is one fused multiply-add in both); sdeo_dpmpp_2m_sde_step likewise to sdeo_cfg_dpmpp_2m_sde_step;
+ *     with blend operands both are bit-identical to sdeo_mask_blend followed by the unmasked call;
+ *   - noise == NULL is allowed only with sigma_t == 0 / k_n == 0 and then runs the launches of the plain (or masked) step; k_n == 0
+ *     runs them whatever noise is;
+ *   - unmasked, SDEO_STEP_LATENT_STAGED keeps its meaning (the previous fused step, stochastic or not, staged the latent);
+ *     SDEO_STEP_HINT_SHARED and SDEO_STEP_V_PREDICTION keep theirs;
+ *   - refused before the first device call, each with its own message, x / pred_x0 / d untouched: a null noise with sigma_t != 0 or
+ *     k_n != 0; 1 - a_prev - sigma_t^2 < 0; a non-finite coefficient; a partial set of blend operands; SDEO_STEP_LATENT_STAGED together
+ *     with a mask; and everything the unmasked and the masked steps refuse;
+ *   - capturable; every earlier entry point is unchanged: same signatures, same launches, same bits. */
+int sdeo_ddim_step_eta(sdeo_handle h, float* x, float* pred_x0, const float* noise, float sigma_t,
+                       const float* orig, const float* mask_noise, const float* mask, int mask_n, int mask_c, float sqrt_a,
+                       float sqrt_one_minus_a, int table_row, float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at,
+                       const float* host_control_scales, int only_mid_control, int flags, void* stream);
+int sdeo_dpmpp_2m_sde_step(sdeo_handle h, float* x, float* d, const float* noise, const float* orig, const float* mask_noise,
+                           const float* mask, int mask_n, int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row,
+                           float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n,
+                           const float* host_control_scales, int only_mid_control, int flags, void* stream);
 
 /* decode_first_stage: z/scale_factor -> post_quant_conv -> Decoder (model.py:619-652).
  * z [n][4][h][w] fp32 NCHW -> images [n][3][8h][8w] fp32 NCHW in [-1,1]; images_u8 (optional, may be NULL)

@@ -50,15 +50,16 @@ class hackathon():
         (B, 77, context_dim) tensor.  config "sd21" / "sd21v" (and "tiny21" / "tiny21v") select the SD-2.x layout (eps / v-prediction);
         their text encoder is "openclip[:<tokenizer dir>]", the FrozenOpenCLIPEmbedder mirror (penultimate layer, as cldm_v21.yaml), under
         the same rules as "clip".  vae_encoder=True also builds the VAE encoder, which `process(init_image=...)` (img2img) needs.
-        sampler: "ddim" (the reference's DDIMSampler) or "dpmpp_2m" (DPM-Solver++(2M) on a log-SNR grid, `cldm/dpm_solver.py`: a
-        deterministic second-order solver meant for about half of DDIM's step count; `process(..., eta != 0)` raises with it)."""
+        sampler: "ddim" (the reference's DDIMSampler), "dpmpp_2m" (DPM-Solver++(2M) on a log-SNR grid, `cldm/dpm_solver.py`: a
+        deterministic second-order solver meant for about half of DDIM's step count; `process(..., eta != 0)` raises with it) or
+        "dpmpp_2m_sde" (its stochastic form, DPMSolverSDESampler: `process(..., eta)` with eta in [0, 1] scales the noise each step adds)."""
         self.apply_canny = apply_canny or _default_canny()
         return self._init_model(weights, config, text_encoder, vae_encoder, sampler=sampler)
 
     def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim"):
         """text encoder, ControlLDM and sampler of `initialize` (shared with hed2image)"""
-        if sampler not in ("ddim", "dpmpp_2m"):
-            raise ValueError(f'sampler {sampler!r}: "ddim" or "dpmpp_2m"')
+        if sampler not in ("ddim", "dpmpp_2m", "dpmpp_2m_sde"):
+            raise ValueError(f'sampler {sampler!r}: "ddim", "dpmpp_2m" or "dpmpp_2m_sde"')
         if isinstance(text_encoder, str) and text_encoder.split(":")[0] in ("clip", "openclip"):
             from .ldm.modules.encoders.modules import FrozenCLIPEmbedder, FrozenOpenCLIPEmbedder
             kind = text_encoder.split(":")[0]
@@ -91,6 +92,9 @@ class hackathon():
         if sampler == "dpmpp_2m":
             from .cldm.dpm_solver import DPMSolverSampler
             self.ddim_sampler = DPMSolverSampler(self.model)     # (the attribute keeps the reference's name whichever sampler it holds)
+        elif sampler == "dpmpp_2m_sde":
+            from .cldm.dpm_solver import DPMSolverSDESampler
+            self.ddim_sampler = DPMSolverSDESampler(self.model)
         else:
             self.ddim_sampler = DDIMSampler(self.model)
         return self

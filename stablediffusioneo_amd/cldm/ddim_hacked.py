@@ -84,11 +84,12 @@ def blend_coefficients(owner, model, timesteps):
     return owner._blend_coefs
 
 
-def mask_operands(owner, img, mask, x0, steps):
+def mask_operands(owner, img, mask, x0, steps, fill=True):
     """The fixed buffers the masked steps of a captured loop read, owned by the sampler `owner`: orig (the known latent), mask, and one
     noise row per step.  Every call copies the caller's mask and x0 in and fills the rows with one torch.randn_like(x0) per step, in
     step order: the draws q_sample makes in the per-step loop (nothing else draws when eta = 0), so a seed gives the same image on
-    both paths.  New shapes get new buffers, and the graphs captured over the old ones are dropped."""
+    both paths.  New shapes get new buffers, and the graphs captured over the old ones are dropped.
+    fill=False leaves the rows to the caller (`draw_rows`): a stochastic loop draws its step noise between them."""
     key = (tuple(img.shape), tuple(mask.shape), int(steps), img.device)
     if getattr(owner, "_mask_key", None) != key:
         owner._mask_key = None
@@ -99,9 +100,35 @@ def mask_operands(owner, img, mask, x0, steps):
         owner._mask_key = key
     owner._loop_mask.copy_(mask)
     owner._loop_orig.copy_(x0)
-    for row in owner._loop_noise:
-        row.copy_(torch.randn_like(x0))
+    if fill:
+        for row in owner._loop_noise:
+            row.copy_(torch.randn_like(x0))
     return owner._loop_orig, owner._loop_mask, owner._loop_noise
+
+
+def step_noise_rows(owner, img, steps):
+    """The fixed rows [S][*shape] the stochastic steps of a captured loop read their noise from (`sigma_t * noise`, `k_n * noise`), owned
+    by the sampler `owner` like `mask_operands`' rows; `draw_rows` fills them per image.  New shapes get new rows, and the graphs
+    captured over the old ones are dropped."""
+    key = (tuple(img.shape), int(steps), img.device)
+    if getattr(owner, "_step_noise_key", None) != key:
+        owner._step_noise_key = None
+        owner._loop_key = None
+        owner._loop_step_noise = torch.empty((int(steps), *img.shape), dtype=torch.float32, device=img.device)
+        owner._step_noise_key = key
+    return owner._loop_step_noise
+
+
+def draw_rows(img, x0, mask_rows, step_rows, live, first, last):
+    """Fill the rows of steps first..last-1 with the per-step loop's draws in the per-step loop's order: per step, first q_sample's
+    torch.randn_like(x0) when there is a mask (mask_rows), then the update's torch.randn(x.shape, device=x.device) when the step has a
+    noise term (live[i]) -- the same functions called the same way, so a seed or a replaced torch.randn gives the same numbers.
+    Nothing else is drawn."""
+    for i in range(first, last):
+        if mask_rows is not None:
+            mask_rows[i].copy_(torch.randn_like(x0))
+        if live[i]:
+            step_rows[i].copy_(torch.randn(img.shape, device=img.device))
 
 
 class DDIMSampler(object):
@@ -150,6 +177,7 @@ class DDIMSampler(object):
         sigmas, alphas, alphas_prev = make_ddim_sampling_parameters(alphacums=ac.numpy(), ddim_timesteps=self.ddim_timesteps,
                                                                     eta=ddim_eta, verbose=verbose)
         self._sigmas_all_zero = bool(float(np.abs(np.asarray(sigmas)).max()) == 0.0)      # host-side, once per schedule (loop-graph gate)
+        self._sigmas_host = np.asarray(sigmas, dtype=np.float64)                          # what the captured eta > 0 steps bake in
         self.register_buffer("ddim_sigmas", sigmas)
         self.register_buffer("ddim_alphas", alphas)
         self.register_buffer("ddim_alphas_prev", alphas_prev)
@@ -205,7 +233,8 @@ class DDIMSampler(object):
         if (callback is None and img_callback is None and ucg_schedule is None and not ddim_use_original_steps
                 and score_corrector is None and not quantize_denoised and dynamic_threshold is None
                 and (mask is None or mask_graph_ok(self.model, img, mask, x0))
-                and self._loop_graph_ok(img, cond, unconditional_conditioning, unconditional_guidance_scale, total_steps)):
+                and self._loop_graph_ok(img, cond, unconditional_conditioning, unconditional_guidance_scale, total_steps,
+                                        temperature, noise_dropout)):
             return self._loop_graphed(img, cond, unconditional_conditioning, unconditional_guidance_scale, time_range,
                                       total_steps, log_every_t, intermediates, mask=mask, x0=x0)
         for i, step in enumerate(time_range):
@@ -240,14 +269,18 @@ class DDIMSampler(object):
         return (uc is not None and scale != 1. and hasattr(m, "rt") and isinstance(c, dict) and isinstance(uc, dict)
                 and c.get("c_concat") is not None and uc.get("c_concat") is not None)
 
-    def _loop_graph_ok(self, img, c, uc, scale, total_steps):
-        """Steps 2..S as one graph: only the plain canny2image loop qualifies -- fused CFG pair, eta = 0 (no noise drawn inside
-        the loop), eps- or v-parameterisation, no callbacks / correctors, a mask only when `mask_graph_ok` (the callers check those)."""
+    def _loop_graph_ok(self, img, c, uc, scale, total_steps, temperature=1., noise_dropout=0.):
+        """Steps 2..S as one graph: only the plain canny2image loop qualifies -- fused CFG pair, eps- or v-parameterisation, no
+        callbacks / correctors, a mask only when `mask_graph_ok` (the callers check those).  With eta > 0 the steps read their noise
+        from the sampler's rows (`step_noise_rows`), which hold plain torch.randn draws: a temperature other than 1 or a noise dropout
+        keep the per-step loop."""
         if not (USE_GRAPH and USE_LOOP_GRAPH and img.is_cuda and total_steps >= 2 and self._fusable(c, uc, scale)):
             return False
         if self.model.parameterization not in ("eps", "v"):
             return False
-        return bool(getattr(self, "_sigmas_all_zero", False))      # computed with the schedule: no device -> host copy per image
+        if getattr(self, "_sigmas_all_zero", False):               # computed with the schedule: no device -> host copy per image
+            return True
+        return hasattr(self, "_sigmas_all_zero") and temperature == 1. and noise_dropout == 0.
 
     def _loop_graphed(self, img, c, uc, scale, time_range, total_steps, log_every_t, intermediates, mask=None, x0=None):
         """The loop of `cldm/ddim_hacked.py:137-160` with step 1 run eagerly (it computes the hint block and the context K / V of
@@ -256,17 +289,30 @@ class DDIMSampler(object):
         guidance scale and control scales; per-step constants (alpha_t, ...) are baked in at capture.
         With a mask (`:154-157`) every step starts with the blend img = q_sample(x0, t) * mask + (1 - mask) * img: step 1 calls
         ops.mask_blend, the captured steps are sdeo_ddim_step_masked calls that read x0, the mask and their noise row from the
-        sampler's fixed buffers (`mask_operands`); the blend coefficients are baked in like the other per-step constants."""
+        sampler's fixed buffers (`mask_operands`); the blend coefficients are baked in like the other per-step constants.
+        With eta > 0 (`:227-230`) the captured steps with sigma_t != 0 are sdeo_ddim_step_eta calls that read their noise row by address;
+        a step with sigma_t == 0 captures the plain step, and the eta = 0 loop captures exactly what it always did."""
         m, rt = self.model, self.model.rt
         b = img.shape[0]
         dev = img.device
+        # eta > 0: loop step i adds sigma[S - 1 - i] * noise; its row is drawn per image in the per-step loop's order (`draw_rows`).  Step 1
+        # runs eagerly and draws inside p_sample_ddim, so with a mask row 0 is drawn before it and everything else after it.
+        stochastic = not self._sigmas_all_zero
+        sig = self._sigmas_host
+        live = [stochastic and float(sig[total_steps - 1 - i]) != 0. for i in range(total_steps)]
+        step_noise = step_noise_rows(self, img, total_steps) if stochastic else None
+        noise = None
         if mask is not None:
             coefs = blend_coefficients(self, m, time_range)
-            orig, mask_buf, noise = mask_operands(self, img, mask, x0, total_steps)
+            orig, mask_buf, noise = mask_operands(self, img, mask, x0, total_steps, fill=not stochastic)
+            if stochastic:
+                draw_rows(img, x0, noise, None, [False], 0, 1)
             img = ops.mask_blend(img.clone(memory_format=torch.contiguous_format), orig, noise[0], mask_buf, *coefs[0])
         ts = torch.full((b,), int(time_range[0]), device=dev, dtype=torch.long)
         img, pred_x0 = self.p_sample_ddim(img, c, ts, index=total_steps - 1, unconditional_guidance_scale=scale,
                                           unconditional_conditioning=uc)
+        if stochastic:
+            draw_rows(img, x0, noise, step_noise, live, 1, total_steps)
         intermediates["x_inter"].append(img)             # index == total_steps - 1
         intermediates["pred_x0"].append(pred_x0)
         # cond and uncond were given the SAME control tensors (canny2image / hed2image outside guess mode): the hint features of the
@@ -293,7 +339,14 @@ class DDIMSampler(object):
                 with torch.cuda.graph(g):
                     for i in range(first, min(first + per_graph, total_steps)):
                         index = total_steps - i - 1
-                        if mask is None:
+                        if live[i]:
+                            blend = {} if mask is None else dict(orig=orig, mask_noise=noise[i], mask=mask_buf, sqrt_a=coefs[i][0],
+                                                                 sqrt_one_minus_a=coefs[i][1])
+                            rt.ddim_step_eta(self._loop_x, self._loop_pred, step_noise[i], float(sig[index]), i, scale, float(a_t[index]),
+                                             float(a_p[index]), float(s1m[index]), m.control_scales, m.only_mid_control,
+                                             staged=i > first and mask is None, hint_shared=hint_shared,
+                                             v_prediction=m.parameterization == "v", **blend)
+                        elif mask is None:
                             rt.ddim_step(self._loop_x, self._loop_pred, i, scale, float(a_t[index]), float(a_p[index]), float(s1m[index]),
                                          m.control_scales, m.only_mid_control, staged=i > first, hint_shared=hint_shared,
                                          v_prediction=m.parameterization == "v")
@@ -398,7 +451,8 @@ class DDIMSampler(object):
         time_range = np.flip(self.ddim_timesteps)
         total_steps = self.ddim_timesteps.shape[0]
         self._cache_key = None
-        if self._loop_graph_ok(img, conditioning, unconditional_conditioning, unconditional_guidance_scale, total_steps):
+        if self._loop_graph_ok(img, conditioning, unconditional_conditioning, unconditional_guidance_scale, total_steps, temperature,
+                               noise_dropout):
             return self._loop_graphed(img, conditioning, unconditional_conditioning, unconditional_guidance_scale, time_range,
                                       total_steps, log_every_t, intermediates)
         for i, step in enumerate(time_range):

@@ -13,7 +13,21 @@ The host folds all of it into three fp64 coefficients per step, x_next = k_x x +
 The loop has the shape of `DDIMSampler._loop_graphed`: step 1 runs eagerly (it fills the runtime's hint / context caches), steps 2..S are
 replayed from a captured graph with the per-step coefficients baked in (with a mask: the masked steps, `ddim_hacked.mask_operands`); what
 does not qualify (callbacks, a replaced q_sample, no ControlNet hint on one half, scale == 1, a model without a runtime) runs one step at a time.  The switches are ddim_hacked's (SDEO_GRAPH,
-SDEO_LOOP_GRAPH, SDEO_LOOP_GRAPH_STEPS)."""
+SDEO_LOOP_GRAPH, SDEO_LOOP_GRAPH_STEPS).
+
+`DPMSolverSDESampler` is the stochastic member of the family, DPM-Solver++(2M) SDE (the same paper's SDE form; eta scales the injected
+noise, eta = 1 is its 2M midpoint solver, eta = 0 the solver above).  It is the same linear update with one more term,
+
+    x_next = (sigma_next / sigma_t) exp(-eta h) x + alpha_next (-expm1(-(1 + eta) h)) [(1 + 1/(2r)) D - (1/(2r)) D_prev]
+             + sigma_next sqrt(-expm1(-2 eta h)) noise,          noise ~ N(0, I) drawn per step
+
+which the host folds into four coefficients, x_next = k_x x + k_d D + k_p D_prev + k_n noise (`sde_coefficients`; the device side is
+`sdeo_cfg_dpmpp_2m_sde_step` / `sdeo_dpmpp_2m_sde_step`).  Its first-order step at eta = 1 is the eta = 1 DDIM step.  The captured loop reads
+each step's noise from a fixed row filled per image with the per-step loop's draws in its order (`ddim_hacked.draw_rows`), so a seed gives
+the same latent on both paths.  Its grid defaults to log-SNR, and for a reason: on DDIM's uniform-t grid the last steps span most of the
+log-SNR range (r = h_prev / h far below 1), the second-order weights 1 + 1/(2r) and -1/(2r) grow large, and the injected noise is
+amplified through them -- on the Gaussian test problem (data variance 0.25, 10 steps, eta = 1) the final variance comes out 109 % too
+large on the uniform grid against 2 to 8 % on the log-SNR grid (tests/test_stochastic_cpu.py).  At low step counts use it on `logsnr` only."""
 from __future__ import annotations
 
 import numpy as np
@@ -69,6 +83,29 @@ def multistep_coefficients(alphas, alphas_next, lower_order_final=True):
     return k_x, k_d, k_p
 
 
+def sde_coefficients(alphas, alphas_next, eta, lower_order_final=True):
+    """(k_x, k_d, k_p, k_n) fp64 arrays of the DPM-Solver++(2M) SDE run of steps a_t -> a_next (symbols as in the module's docstring):
+        k_x = (sigma_next / sigma_t) exp(-eta h),   w = alpha_next * -expm1(-(1 + eta) h),
+        k_d = w (1 + 1/(2r)),  k_p = -w / (2r)  (first order: k_d = w, k_p = 0),   k_n = sigma_next sqrt(-expm1(-2 eta h))
+    with the order rule of `multistep_coefficients`.  eta = 0 returns its three arrays bit for bit, and k_n = 0."""
+    a_t, a_n = np.asarray(alphas, dtype=np.float64), np.asarray(alphas_next, dtype=np.float64)
+    eta = float(eta)
+    h = log_snr(a_n) - log_snr(a_t)
+    assert (h > 0).all(), "every step must lower the noise level"
+    k_x = np.sqrt((1.0 - a_n) / (1.0 - a_t)) * np.exp(-eta * h)
+    k_d = np.sqrt(a_n) * -np.expm1(-((1.0 + eta) * h))
+    k_p = np.zeros_like(k_d)
+    k_n = np.sqrt(1.0 - a_n) * np.sqrt(-np.expm1(-2.0 * eta * h))
+    n = h.shape[0]
+    for k in range(1, n):
+        if lower_order_final and k == n - 1:
+            continue
+        inv_2r = h[k] / (2.0 * h[k - 1])          # 1 / (2r), r = h_prev / h
+        k_p[k] = -k_d[k] * inv_2r
+        k_d[k] = k_d[k] * (1.0 + inv_2r)
+    return k_x, k_d, k_p, k_n
+
+
 class DPMSolverSampler(object):
     def __init__(self, model, discretize="logsnr", lower_order_final=True, **kwargs):
         super().__init__()
@@ -81,6 +118,7 @@ class DPMSolverSampler(object):
         self._pair = DDIMSampler(model)        # the fused cond / uncond forward and its conditioning cache are DDIM's (_eps_pair)
         self._schedule_key = None
         self._loop_key = None
+        self.k_n = None                        # the noise coefficients of the stochastic subclass; None here: no step draws or adds noise
 
     # ------------------------------------------------------------------------------------------ schedule
     def make_schedule(self, ddim_num_steps, ddim_eta=0., verbose=True):
@@ -105,8 +143,12 @@ class DPMSolverSampler(object):
         self.timesteps = ts
         self.alphas = acn[ts]
         self.alphas_next = np.append(acn[ts[1:]], acn[0])
-        self.k_x, self.k_d, self.k_p = multistep_coefficients(self.alphas, self.alphas_next, self.lower_order_final)
+        self.k_x, self.k_d, self.k_p, self.k_n = self._coefficients(self.alphas, self.alphas_next)
         self._schedule_key = key
+
+    def _coefficients(self, alphas, alphas_next):
+        """(k_x, k_d, k_p, k_n) of a run without history; k_n is None: the solver is deterministic"""
+        return (*multistep_coefficients(alphas, alphas_next, self.lower_order_final), None)
 
     # ------------------------------------------------------------------------------------------ sample
     @torch.no_grad()
@@ -133,25 +175,36 @@ class DPMSolverSampler(object):
         self._pair._cache_key = None
         total_steps = int(self.timesteps.shape[0])
         if (callback is None and img_callback is None and ucg_schedule is None and (mask is None or dh.mask_graph_ok(self.model, img, mask, x0))
+                and (self.k_n is None or (temperature == 1. and noise_dropout == 0.))
                 and self._loop_graph_ok(img, c, uc, scale, total_steps)):
             return self._loop_graphed(img, c, uc, scale, total_steps, log_every_t, intermediates, mask=mask, x0=x0)
         if mask is not None:
             assert x0 is not None
         x = self._run(img, c, uc, scale, self.timesteps, self.alphas, self.k_x, self.k_d, self.k_p, mask=mask, x0=x0, callback=callback,
-                      img_callback=img_callback, ucg_schedule=ucg_schedule, log_every_t=log_every_t, intermediates=intermediates)
+                      img_callback=img_callback, ucg_schedule=ucg_schedule, log_every_t=log_every_t, intermediates=intermediates,
+                      k_n=self.k_n, temperature=temperature, noise_dropout=noise_dropout)
         return x, intermediates
 
-    def _step(self, x, d, c, uc, scale, k, timesteps, alphas, k_x, k_d, k_p):
-        """one eager step: the model on the pair, then the update kernel; d (fixed buffer) holds D_prev on entry and D on return"""
+    def _step(self, x, d, c, uc, scale, k, timesteps, alphas, k_x, k_d, k_p, k_n=None, temperature=1., noise_dropout=0.):
+        """one eager step: the model on the pair, then the update kernel; d (fixed buffer) holds D_prev on entry and D on return.
+        With a noise coefficient (k_n[k] != 0, the stochastic subclass) the step draws torch.randn(x.shape, device=x.device) once, as
+        `DDIMSampler.p_sample_ddim` does, temperature and noise_dropout meaning what they mean there."""
         ts = torch.full((x.shape[0],), int(timesteps[k]), device=x.device, dtype=torch.long)
         m_c, m_u = self._pair._eps_pair(x, c, ts, uc, scale)
         a_t = float(alphas[k])
+        if k_n is not None and float(k_n[k]) != 0.:
+            noise = torch.randn(x.shape, device=x.device).expand(x.shape).contiguous() * temperature
+            if noise_dropout > 0.:
+                noise = torch.nn.functional.dropout(noise, p=noise_dropout)
+            return ops.cfg_dpmpp_2m_sde_step(x.contiguous(), m_c.contiguous(), None if m_u is None else m_u.contiguous(), noise, scale, a_t,
+                                             float(np.sqrt(1.0 - a_t)), float(k_x[k]), float(k_d[k]), float(k_p[k]), float(k_n[k]), d=d,
+                                             v_prediction=self.model.parameterization == "v")
         return ops.cfg_dpmpp_2m_step(x.contiguous(), m_c.contiguous(), None if m_u is None else m_u.contiguous(), scale, a_t,
                                      float(np.sqrt(1.0 - a_t)), float(k_x[k]), float(k_d[k]), float(k_p[k]), d=d,
                                      v_prediction=self.model.parameterization == "v")
 
     def _run(self, x, c, uc, scale, timesteps, alphas, k_x, k_d, k_p, mask=None, x0=None, callback=None, img_callback=None,
-             ucg_schedule=None, log_every_t=100, intermediates=None):
+             ucg_schedule=None, log_every_t=100, intermediates=None, k_n=None, temperature=1., noise_dropout=0.):
         """the per-step path over a run of steps that starts without history (k_p[0] == 0)"""
         total = len(timesteps)
         d = torch.empty_like(x, memory_format=torch.contiguous_format)
@@ -163,7 +216,7 @@ class DPMSolverSampler(object):
             if ucg_schedule is not None:
                 assert len(ucg_schedule) == total
                 scale = ucg_schedule[k]
-            x = self._step(x, d, c, uc, scale, k, timesteps, alphas, k_x, k_d, k_p)
+            x = self._step(x, d, c, uc, scale, k, timesteps, alphas, k_x, k_d, k_p, k_n, temperature, noise_dropout)
             if callback:
                 callback(k)
             if img_callback:
@@ -175,7 +228,7 @@ class DPMSolverSampler(object):
 
     # ------------------------------------------------------------------------------------------ whole-loop graph
     def _loop_graph_ok(self, img, c, uc, scale, total_steps):
-        """the gating of `DDIMSampler._loop_graph_ok` (the solver has no noise term to rule out)"""
+        """the gating of `DDIMSampler._loop_graph_ok` (the stochastic subclass's temperature / noise_dropout are ruled out by `sample`)"""
         return bool(dh.USE_GRAPH and dh.USE_LOOP_GRAPH and img.is_cuda and total_steps >= 2 and self._pair._fusable(c, uc, scale)
                     and self.model.parameterization in ("eps", "v"))
 
@@ -192,15 +245,26 @@ class DPMSolverSampler(object):
         shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), tuple(float(v) for v in m.control_scales),
                      bool(m.only_mid_control), self._schedule_key, per_graph, hint_shared, m.parameterization,
                      None if mask is None else tuple(mask.shape))
+        # the stochastic subclass: step i adds k_n[i] * noise, read from a row drawn per image in the per-step loop's order
+        # (`ddim_hacked.draw_rows`).  Step 1 runs eagerly and draws inside `_step`: with a mask, row 0 is drawn before it, the rest after.
+        k_n = self.k_n
+        live = [k_n is not None and float(k_n[i]) != 0. for i in range(total_steps)]
+        stochastic = any(live)
+        step_noise = dh.step_noise_rows(self, img, total_steps) if stochastic else None
+        noise = None
         if mask is not None:
             coefs = dh.blend_coefficients(self, m, ts)
-            orig, mask_buf, noise = dh.mask_operands(self, img, mask, x0, total_steps)
+            orig, mask_buf, noise = dh.mask_operands(self, img, mask, x0, total_steps, fill=not stochastic)
+            if stochastic:
+                dh.draw_rows(img, x0, noise, None, [False], 0, 1)
             img = ops.mask_blend(img.clone(memory_format=torch.contiguous_format), orig, noise[0], mask_buf, *coefs[0])
         if self._loop_key is None or self._loop_key[1:] != shape_key:
             self._loop_key = None
             self._loop_x = torch.empty_like(img, memory_format=torch.contiguous_format)
             self._loop_d = torch.empty_like(self._loop_x)             # D of the last step taken: the solver's only state next to x
-        x1 = self._step(img, self._loop_d, c, uc, scale, 0, ts, a_t, k_x, k_d, k_p)
+        x1 = self._step(img, self._loop_d, c, uc, scale, 0, ts, a_t, k_x, k_d, k_p, k_n)
+        if stochastic:
+            dh.draw_rows(img, x0, noise, step_noise, live, 1, total_steps)
         intermediates["x_inter"].append(x1)                           # index == total_steps - 1
         intermediates["pred_x0"].append(self._loop_d.clone())
         self._loop_x.copy_(x1)
@@ -217,7 +281,13 @@ class DPMSolverSampler(object):
                 with torch.cuda.graph(g):
                     for i in range(first, min(first + per_graph, total_steps)):
                         a = float(a_t[i])
-                        if mask is None:
+                        if live[i]:
+                            blend = {} if mask is None else dict(orig=orig, mask_noise=noise[i], mask=mask_buf, sqrt_a=coefs[i][0],
+                                                                 sqrt_one_minus_a=coefs[i][1])
+                            rt.dpmpp_2m_sde_step(self._loop_x, self._loop_d, step_noise[i], i, scale, a, float(np.sqrt(1.0 - a)), float(k_x[i]),
+                                                 float(k_d[i]), float(k_p[i]), float(k_n[i]), m.control_scales, m.only_mid_control,
+                                                 staged=i > first and mask is None, hint_shared=hint_shared, v_prediction=v_pred, **blend)
+                        elif mask is None:
                             rt.dpmpp_2m_step(self._loop_x, self._loop_d, i, scale, a, float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]),
                                              float(k_p[i]), m.control_scales, m.only_mid_control, staged=i > first, hint_shared=hint_shared,
                                              v_prediction=v_pred)
@@ -265,8 +335,47 @@ class DPMSolverSampler(object):
             return x_latent
         first = total - t_start
         alphas, alphas_next = self.alphas[first:], self.alphas_next[first:]
-        k_x, k_d, k_p = multistep_coefficients(alphas, alphas_next, self.lower_order_final)
+        k_x, k_d, k_p, k_n = self._coefficients(alphas, alphas_next)
         self._pair._cache_key = None
         x = x_latent.to(device=self.model.device, dtype=torch.float32)
         return self._run(x, cond, unconditional_conditioning, unconditional_guidance_scale, self.timesteps[first:], alphas, k_x, k_d, k_p,
-                         callback=callback)
+                         callback=callback, k_n=k_n)
+
+
+class DPMSolverSDESampler(DPMSolverSampler):
+    """DPM-Solver++(2M) SDE with the surface of `DPMSolverSampler` (sample / stochastic_encode / decode): eta in [0, 1] scales the noise
+    each step injects (the module's docstring has the update).  eta = 0 takes the parent's code path: the same calls, the same bits.
+    The grid defaults to log-SNR; the uniform-t grid is accepted but not usable at low step counts (see the module's docstring).
+    temperature != 1 or noise_dropout != 0 run one step at a time, with `DDIMSampler`'s meaning."""
+
+    def __init__(self, model, discretize="logsnr", lower_order_final=True, **kwargs):
+        super().__init__(model, discretize=discretize, lower_order_final=lower_order_final, **kwargs)
+        self.eta = 0.0
+
+    @staticmethod
+    def _check_eta(eta):
+        eta = float(eta)
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError(f"eta = {eta}: DPM-Solver++(2M) SDE takes eta in [0, 1] (0: the ODE solver, 1: the full SDE noise)")
+        return eta
+
+    def make_schedule(self, ddim_num_steps, ddim_eta=None, verbose=True):
+        """the parent's grid; the coefficients are `sde_coefficients` at ddim_eta (the parent's own at 0).  ddim_eta stays in force, for
+        `decode` and for a call without it, until another one is given."""
+        eta = self.eta if ddim_eta is None else self._check_eta(ddim_eta)
+        if eta != self.eta:
+            self._schedule_key = None          # the parent's keys do not know eta: new coefficients, and new graphs that bake them in
+            self._loop_key = None
+            self.eta = eta
+        super().make_schedule(ddim_num_steps, verbose=verbose)
+
+    def _coefficients(self, alphas, alphas_next):
+        if self.eta == 0.0:
+            return super()._coefficients(alphas, alphas_next)
+        return sde_coefficients(alphas, alphas_next, self.eta, self.lower_order_final)
+
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, eta=0., verbose=True, **kwargs):
+        """`DPMSolverSampler.sample` with eta in [0, 1]"""
+        self.make_schedule(S, ddim_eta=self._check_eta(eta), verbose=verbose)
+        return super().sample(S, batch_size, shape, conditioning, eta=0., verbose=verbose, **kwargs)

@@ -427,6 +427,13 @@ int sdeo_cfg_dpmpp_2m_step(float* x_next, float* d, const float* x, const float*
                       S(stream));
 }
 
+int sdeo_cfg_dpmpp_2m_sde_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, const float* noise,
+                               float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, int flags,
+                               int64_t n, void* stream) {
+  return cfg_lms_noise_step(x_next, d, x, m_c, m_u, noise, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, k_n, n,
+                            (flags & SDEO_STEP_V_PREDICTION) != 0, S(stream));
+}
+
 int sdeo_mask_blend(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a,
                     float sqrt_one_minus_a, int n, int c, int hw, void* stream) {
   return mask_blend(x, orig, noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a, n, c, hw, S(stream));

@@ -492,6 +492,64 @@ int cfg_ddim_pair_check(const char* who, float a_t, float a_prev) {
   return 0;
 }
 
+// cfg_ddim_pair_kernel with the sampler's noise term (`cldm/ddim_hacked.py:227-230`, eta > 0): x = x_prev + sigma * noise[j], noise fp32
+// [b][C][HW] like x; the fp16 staging of the next forward is written from the noisy value.  A sibling, so that the eta = 0 kernel keeps
+// its code.  In cfg_ddim_kernel `xp += sigma * noise[i]` is left to the compiler, which contracts it into one v_fmac_f32 (read in the ISA
+// of both of its instantiations): the same single rounding is stated here as fmaf, so the two round alike whatever the compiler does.
+template <bool VPRED>
+__global__ __launch_bounds__(256) void cfg_ddim_pair_noise_kernel(float* __restrict__ x, float* __restrict__ pred_x0,
+                                                                  const f16* __restrict__ eps, int lde, const float* __restrict__ noise,
+                                                                  f16* __restrict__ x0, int ld0, int b, int C, int HW, float s, float at_coef,
+                                                                  float sqrt_aprev, float dir_coef, float sigma, float sqrt_1m_at) {
+  const int64_t total = (int64_t)b * HW;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t n = i / HW, pix = i - n * HW;
+    const f16* ec = eps + i * lde;
+    const f16* eu = eps + (i + total) * lde;
+    for (int c = 0; c < ld0; ++c) {
+      f16 v = (f16)0.f;
+      if (c < C) {
+        const int64_t j = (n * C + c) * HW + pix;
+        float p0, xp;
+        cfg_ddim_elem_sel<VPRED>(x[j], (float)ec[c], (float)eu[c], true, s, at_coef, sqrt_aprev, dir_coef, sqrt_1m_at, p0, xp);
+        xp = fmaf(sigma, noise[j], xp);
+        x[j] = xp;
+        if (pred_x0) pred_x0[j] = p0;
+        v = (f16)xp;
+      }
+      x0[i * ld0 + c] = v;
+      x0[(i + total) * ld0 + c] = v;
+    }
+  }
+}
+
+// what the noisy pair update refuses, host only: callers that change x before it (the blend) or must leave x untouched refuse up front
+int cfg_ddim_pair_noise_check(const char* who, const float* noise, float a_t, float a_prev, float sigma_t) {
+  SDEO_CHECK(std::isfinite(a_t) && std::isfinite(a_prev) && std::isfinite(sigma_t), "%s: non-finite coefficient a_t=%g a_prev=%g sigma_t=%g",
+             who, a_t, a_prev, sigma_t);
+  SDEO_CHECK(noise || sigma_t == 0.f, "%s: sigma_t=%g needs the step noise, but noise is null", who, sigma_t);
+  SDEO_CHECK(a_t > 0.f, "%s: invalid schedule a_t=%g", who, a_t);
+  SDEO_CHECK((1.f - a_prev - sigma_t * sigma_t) >= 0.f, "%s: 1 - a_prev - sigma_t^2 < 0 (a_prev=%g sigma_t=%g)", who, a_prev, sigma_t);
+  return 0;
+}
+
+int cfg_ddim_pair_noise(float* x, float* pred_x0, const f16* eps, int lde, const float* noise, f16* x0, int ld0, int b, int C, int HW,
+                        float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, bool v_prediction,
+                        hipStream_t stream) {
+  SDEO_CHECK(x && eps && noise && x0 && b > 0 && C > 0 && HW > 0 && lde >= C && ld0 >= C, "cfg_ddim_pair_noise: bad operand");
+  if (int rc = cfg_ddim_pair_noise_check("cfg_ddim_pair_noise", noise, a_t, a_prev, sigma_t)) return rc;
+  // the coefficients as cfg_ddim_step forms them, expression for expression
+  if (v_prediction)
+    hipLaunchKernelGGL(cfg_ddim_pair_noise_kernel<true>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, pred_x0, eps, lde, noise, x0, ld0,
+                       b, C, HW, cfg_scale, sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sigma_t * sigma_t), sigma_t, sqrt_one_minus_at);
+  else
+    hipLaunchKernelGGL(cfg_ddim_pair_noise_kernel<false>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, pred_x0, eps, lde, noise, x0, ld0,
+                       b, C, HW, cfg_scale, 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sigma_t * sigma_t), sigma_t,
+                       sqrt_one_minus_at);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
 int cfg_ddim_step(float* x_prev, float* pred_x0, const float* x, const float* eps_c, const float* eps_u, const float* noise,
                   float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, int64_t n, bool v_prediction,
                   hipStream_t stream) {
@@ -581,6 +639,91 @@ int cfg_lms_pair(float* x, float* d, const f16* eps, int lde, f16* x0, int ld0, 
   else
     hipLaunchKernelGGL(cfg_lms_pair_kernel<false>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, d, eps, lde, x0, ld0, b, C, HW,
                        cfg_scale, 1.0f / sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
+// The stochastic member of the family (DPM-Solver++(2M) SDE): the same update with a fourth term, x_next = k_x x + k_d D + k_p D_prev +
+// k_n noise, one more fused multiply-add on what cfg_lms_elem returns (stated as fmaf in both kernels so that they round alike).  They are
+// siblings of cfg_lms_kernel / cfg_lms_pair_kernel, which keep their code; the host launches those when k_n == 0.  noise is fp32, laid
+// out like x.
+template <bool VPRED>
+__global__ __launch_bounds__(256) void cfg_lms_noise_kernel(float* __restrict__ x_next, float* d, const float* __restrict__ x,
+                                                            const float* __restrict__ mc, const float* __restrict__ mu,
+                                                            const float* __restrict__ noise, float s, float at_coef, float sqrt_1m_at,
+                                                            float k_x, float k_d, float k_p, float k_n, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float p0, xn;
+    const float dp = k_p != 0.f ? d[i] : 0.f;
+    cfg_lms_elem<VPRED>(x[i], mc[i], mu ? mu[i] : 0.f, mu != nullptr, s, at_coef, sqrt_1m_at, k_x, k_d, k_p, dp, p0, xn);
+    x_next[i] = fmaf(k_n, noise[i], xn);
+    if (d) d[i] = p0;
+  }
+}
+
+template <bool VPRED>
+__global__ __launch_bounds__(256) void cfg_lms_pair_noise_kernel(float* __restrict__ x, float* d, const f16* __restrict__ eps, int lde,
+                                                                 const float* __restrict__ noise, f16* __restrict__ x0, int ld0, int b, int C,
+                                                                 int HW, float s, float at_coef, float sqrt_1m_at, float k_x, float k_d,
+                                                                 float k_p, float k_n) {
+  const int64_t total = (int64_t)b * HW;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t n = i / HW, pix = i - n * HW;
+    const f16* ec = eps + i * lde;
+    const f16* eu = eps + (i + total) * lde;
+    for (int c = 0; c < ld0; ++c) {
+      f16 v = (f16)0.f;
+      if (c < C) {
+        const int64_t j = (n * C + c) * HW + pix;
+        float p0, xn;
+        const float dp = k_p != 0.f ? d[j] : 0.f;
+        cfg_lms_elem<VPRED>(x[j], (float)ec[c], (float)eu[c], true, s, at_coef, sqrt_1m_at, k_x, k_d, k_p, dp, p0, xn);
+        xn = fmaf(k_n, noise[j], xn);
+        x[j] = xn;
+        if (d) d[j] = p0;
+        v = (f16)xn;
+      }
+      x0[i * ld0 + c] = v;
+      x0[(i + total) * ld0 + c] = v;
+    }
+  }
+}
+
+// lms_coefs_ok plus the noise term's own conditions (host only)
+int lms_noise_coefs_ok(const char* who, const float* d, const float* noise, float a_t, float k_x, float k_d, float k_p, float k_n) {
+  SDEO_CHECK(std::isfinite(k_n), "%s: non-finite coefficient k_n=%g", who, k_n);
+  SDEO_CHECK(noise || k_n == 0.f, "%s: k_n=%g needs the step noise, but noise is null", who, k_n);
+  return lms_coefs_ok(who, d, a_t, k_x, k_d, k_p);
+}
+
+int cfg_lms_pair_noise(float* x, float* d, const f16* eps, int lde, const float* noise, f16* x0, int ld0, int b, int C, int HW,
+                       float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, bool v_prediction,
+                       hipStream_t stream) {
+  SDEO_CHECK(x && eps && noise && x0 && b > 0 && C > 0 && HW > 0 && lde >= C && ld0 >= C, "cfg_lms_pair_noise: bad operand");
+  if (int rc = lms_noise_coefs_ok("cfg_lms_pair_noise", d, noise, a_t, k_x, k_d, k_p, k_n)) return rc;
+  if (v_prediction)
+    hipLaunchKernelGGL(cfg_lms_pair_noise_kernel<true>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, d, eps, lde, noise, x0, ld0, b, C,
+                       HW, cfg_scale, sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p, k_n);
+  else
+    hipLaunchKernelGGL(cfg_lms_pair_noise_kernel<false>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, d, eps, lde, noise, x0, ld0, b, C,
+                       HW, cfg_scale, 1.0f / sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p, k_n);
+  SDEO_HIP(hipGetLastError());
+  return 0;
+}
+
+int cfg_lms_noise_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, const float* noise, float cfg_scale,
+                       float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, int64_t n, bool v_prediction,
+                       hipStream_t stream) {
+  SDEO_CHECK(x_next && x && m_c && n > 0, "cfg_lms_noise_step: bad operand");
+  if (int rc = lms_noise_coefs_ok("cfg_lms_noise_step", d, noise, a_t, k_x, k_d, k_p, k_n)) return rc;
+  if (k_n == 0.f)                                // no noise term: the existing kernel, the same launch, the same bits
+    return cfg_lms_step(x_next, d, x, m_c, m_u, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, n, v_prediction, stream);
+  if (v_prediction)
+    hipLaunchKernelGGL(cfg_lms_noise_kernel<true>, grid_for(n), dim3(256), 0, stream, x_next, d, x, m_c, m_u, noise, cfg_scale, sqrtf(a_t),
+                       sqrt_one_minus_at, k_x, k_d, k_p, k_n, n);
+  else
+    hipLaunchKernelGGL(cfg_lms_noise_kernel<false>, grid_for(n), dim3(256), 0, stream, x_next, d, x, m_c, m_u, noise, cfg_scale,
+                       1.0f / sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p, k_n, n);
   SDEO_HIP(hipGetLastError());
   return 0;
 }

@@ -262,6 +262,23 @@ int mask_blend(float* x, const float* orig, const float* noise, const float* mas
                int n, int C, int HW, hipStream_t stream);
 int mask_blend_pair(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a,
                     float sqrt_1ma, f16* x0, int ld0, int b, int C, int HW, hipStream_t stream);
+// The stochastic forms of the two updates: one more operand, noise (fp32, laid out like x), and one more fused multiply-add.
+//   cfg_ddim_pair_noise: cfg_ddim_pair + sigma_t * noise with dir_coef = sqrt(1 - a_prev - sigma_t^2) (`cldm/ddim_hacked.py:227-230`),
+//     bit-equal to cfg_ddim_step with the same noise / sigma_t; the staged fp16 latent is the noisy one.
+//   cfg_lms_noise_step / cfg_lms_pair_noise: x_next = k_x x + k_d D + k_p D_prev + k_n noise (DPM-Solver++(2M) SDE); with k_n == 0
+//     cfg_lms_noise_step is cfg_lms_step (noise may then be null).
+//   *_check / *_ok: their coefficient checks alone (host only).
+int cfg_ddim_pair_noise_check(const char* who, const float* noise, float a_t, float a_prev, float sigma_t);
+int cfg_ddim_pair_noise(float* x, float* pred_x0, const f16* eps, int lde, const float* noise, f16* x0, int ld0, int b, int C, int HW,
+                        float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, bool v_prediction,
+                        hipStream_t stream);
+int lms_noise_coefs_ok(const char* who, const float* d, const float* noise, float a_t, float k_x, float k_d, float k_p, float k_n);
+int cfg_lms_pair_noise(float* x, float* d, const f16* eps, int lde, const float* noise, f16* x0, int ld0, int b, int C, int HW,
+                       float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, bool v_prediction,
+                       hipStream_t stream);
+int cfg_lms_noise_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, const float* noise, float cfg_scale,
+                       float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, int64_t n, bool v_prediction,
+                       hipStream_t stream);
 // dst = (gen * m + orig * (255 - m) + 127) / 255 in integers: uint8 HWC images [H][W][C], C in 1..4, uint8 mask [H][W]
 int composite_u8(uint8_t* dst, const uint8_t* gen, const uint8_t* orig, const uint8_t* mask, int H, int W, int C, hipStream_t stream);
 

@@ -24,6 +24,7 @@
 //   * the two halves of sdeo_ddim_step's CFG batch [x; x] differ only in their text context, so what a network computes before its
 //     first cross-attention (input_blocks.1: ResBlock, proj_in, self-attention, attn2.to_q) runs on the first half only and the
 //     full-batch launches behind it read the half-batch tensors twice (P_UNET_ENC_SH / P_CN_SH, build_shared_prefix).
+#include <cmath>
 #include <functional>
 #include <memory>
 #include <unordered_map>
@@ -1745,19 +1746,31 @@ static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float*
   return run_step_programs(h, false, true, s, true, (flags & SDEO_STEP_HINT_SHARED) != 0);
 }
 
+// The noise term of a stochastic step (coef: sigma_t of the DDIM step, k_n of the SDE solver's); null, or a null row, for the plain update.
+struct StepNoise {
+  const float* noise;
+  float coef;
+};
+
 static int ddim_step_impl(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
                           float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, const StepBlend* blend,
-                          const char* who, hipStream_t s) {
+                          const StepNoise* sn, const char* who, hipStream_t s) {
   if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, blend, who, s)) return rc;
+  if (sn && sn->noise)
+    return cfg_ddim_pair_noise(x, pred_x0, h->eps16.p, h->eps16.ld, sn->noise, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels,
+                               h->lh * h->lw, cfg_scale, a_t, a_prev, sn->coef, sqrt_one_minus_at, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
   return cfg_ddim_pair(x, pred_x0, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw, cfg_scale, a_t,
                        a_prev, sqrt_one_minus_at, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
 }
 
 static int dpmpp_2m_step_impl(sdeo_handle h, float* x, float* d, int table_row, float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x,
                               float k_d, float k_p, const float* host_control_scales, int only_mid_control, int flags, const StepBlend* blend,
-                              const char* who, hipStream_t s) {
+                              const StepNoise* sn, const char* who, hipStream_t s) {
   SDEO_CHECK(d || k_p == 0.f, "%s: k_p=%g needs the previous data prediction, but d is null", who, k_p);
   if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, blend, who, s)) return rc;
+  if (sn && sn->coef != 0.f)                     // k_n == 0: the existing kernel, whatever the noise pointer
+    return cfg_lms_pair_noise(x, d, h->eps16.p, h->eps16.ld, sn->noise, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw,
+                              cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, sn->coef, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
   return cfg_lms_pair(x, d, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw, cfg_scale, a_t,
                       sqrt_one_minus_at, k_x, k_d, k_p, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
 }
@@ -1765,13 +1778,13 @@ static int dpmpp_2m_step_impl(sdeo_handle h, float* x, float* d, int table_row, 
 int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
                    float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
   return ddim_step_impl(h, x, pred_x0, table_row, cfg_scale, a_t, a_prev, sqrt_one_minus_at, host_control_scales, only_mid_control, flags,
-                        nullptr, "sdeo_ddim_step", S(stream));
+                        nullptr, nullptr, "sdeo_ddim_step", S(stream));
 }
 
 int sdeo_dpmpp_2m_step(sdeo_handle h, float* x, float* d, int table_row, float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x,
                        float k_d, float k_p, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
   return dpmpp_2m_step_impl(h, x, d, table_row, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, host_control_scales, only_mid_control,
-                            flags, nullptr, "sdeo_dpmpp_2m_step", S(stream));
+                            flags, nullptr, nullptr, "sdeo_dpmpp_2m_step", S(stream));
 }
 
 // The masked steps change x before the networks run, so what the update kernel would refuse after them is refused here, up front.
@@ -1782,7 +1795,7 @@ int sdeo_ddim_step_masked(sdeo_handle h, float* x, float* pred_x0, const float* 
   if (int rc = cfg_ddim_pair_check(who, a_t, a_prev)) return rc;
   const StepBlend blend{orig, noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
   return ddim_step_impl(h, x, pred_x0, table_row, cfg_scale, a_t, a_prev, sqrt_one_minus_at, host_control_scales, only_mid_control, flags,
-                        &blend, who, S(stream));
+                        &blend, nullptr, who, S(stream));
 }
 
 int sdeo_dpmpp_2m_step_masked(sdeo_handle h, float* x, float* d, const float* orig, const float* noise, const float* mask, int mask_n,
@@ -1793,7 +1806,49 @@ int sdeo_dpmpp_2m_step_masked(sdeo_handle h, float* x, float* d, const float* or
   if (int rc = lms_coefs_ok(who, d, a_t, k_x, k_d, k_p)) return rc;
   const StepBlend blend{orig, noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
   return dpmpp_2m_step_impl(h, x, d, table_row, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, host_control_scales, only_mid_control,
-                            flags, &blend, who, S(stream));
+                            flags, &blend, nullptr, who, S(stream));
+}
+
+// The stochastic steps.  Like the masked steps they refuse up front what their update kernel would refuse after the networks ran, and
+// what is theirs alone: a coefficient without its noise row, a partial set of blend operands, the staged flag together with a blend.
+static int step_blend_operands(const char* who, const float* orig, const float* mask_noise, const float* mask, int flags) {
+  if (!orig) {
+    SDEO_CHECK(!mask_noise && !mask, "%s: partial blend operands: orig is null, so mask_noise and mask must be null too (the unmasked step)", who);
+    return 0;
+  }
+  SDEO_CHECK(mask_noise && mask, "%s: partial blend operands: orig is given, so mask_noise and mask are needed too", who);
+  SDEO_CHECK(!(flags & SDEO_STEP_LATENT_STAGED), "%s: SDEO_STEP_LATENT_STAGED together with a mask (the blend changes the latent and always restages it)", who);
+  return 0;
+}
+
+int sdeo_ddim_step_eta(sdeo_handle h, float* x, float* pred_x0, const float* noise, float sigma_t, const float* orig,
+                       const float* mask_noise, const float* mask, int mask_n, int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row,
+                       float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, const float* host_control_scales,
+                       int only_mid_control, int flags, void* stream) {
+  const char* who = "sdeo_ddim_step_eta";
+  SDEO_CHECK(std::isfinite(cfg_scale) && std::isfinite(sqrt_one_minus_at), "%s: non-finite coefficient cfg_scale=%g sqrt_one_minus_at=%g", who,
+             cfg_scale, sqrt_one_minus_at);
+  if (int rc = cfg_ddim_pair_noise_check(who, noise, a_t, a_prev, sigma_t)) return rc;
+  if (int rc = step_blend_operands(who, orig, mask_noise, mask, flags)) return rc;
+  const StepBlend blend{orig, mask_noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
+  const StepNoise sn{noise, sigma_t};
+  return ddim_step_impl(h, x, pred_x0, table_row, cfg_scale, a_t, a_prev, sqrt_one_minus_at, host_control_scales, only_mid_control, flags,
+                        orig ? &blend : nullptr, &sn, who, S(stream));
+}
+
+int sdeo_dpmpp_2m_sde_step(sdeo_handle h, float* x, float* d, const float* noise, const float* orig, const float* mask_noise,
+                           const float* mask, int mask_n, int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row, float cfg_scale,
+                           float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, const float* host_control_scales,
+                           int only_mid_control, int flags, void* stream) {
+  const char* who = "sdeo_dpmpp_2m_sde_step";
+  SDEO_CHECK(std::isfinite(cfg_scale) && std::isfinite(a_t) && std::isfinite(sqrt_one_minus_at),
+             "%s: non-finite coefficient cfg_scale=%g a_t=%g sqrt_one_minus_at=%g", who, cfg_scale, a_t, sqrt_one_minus_at);
+  if (int rc = lms_noise_coefs_ok(who, d, noise, a_t, k_x, k_d, k_p, k_n)) return rc;
+  if (int rc = step_blend_operands(who, orig, mask_noise, mask, flags)) return rc;
+  const StepBlend blend{orig, mask_noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
+  const StepNoise sn{noise, k_n};
+  return dpmpp_2m_step_impl(h, x, d, table_row, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, host_control_scales, only_mid_control,
+                            flags, orig ? &blend : nullptr, &sn, who, S(stream));
 }
 
 int sdeo_vae_decode(sdeo_handle h, const float* z, int n, float* images, uint8_t* images_u8, void* stream) {

@@ -476,6 +476,22 @@ def cfg_dpmpp_2m_step(x, m_c, m_u, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, 
     return x_next
 
 
+def cfg_dpmpp_2m_sde_step(x, m_c, m_u, noise, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, k_n, d=None, v_prediction=False):
+    """`sdeo_cfg_dpmpp_2m_sde_step`: `cfg_dpmpp_2m_step` with the SDE solver's fourth term, x_next = k_x x + k_d D + k_p d + k_n noise, then
+    d <- D in place.  noise (fp32, shaped like x) may be None only when k_n == 0: the library then launches `cfg_dpmpp_2m_step`'s kernel
+    (the same bits); None with k_n != 0 is the library's to refuse.  Returns x_next."""
+    lib = _lib.load()
+    _need_cuda(x, m_c, m_u, d, noise)
+    assert x.dtype == torch.float32 and x.is_contiguous() and m_c.is_contiguous() and (m_u is None or m_u.is_contiguous())
+    assert d is None or (d.dtype == torch.float32 and d.is_contiguous() and d.shape == x.shape)
+    assert noise is None or (noise.dtype == torch.float32 and noise.is_contiguous() and noise.shape == x.shape)
+    x_next = torch.empty_like(x)
+    check(lib.sdeo_cfg_dpmpp_2m_sde_step(ptr(x_next), ptr(d), ptr(x), ptr(m_c), ptr(m_u), ptr(noise), cfg_scale, a_t, sqrt_one_minus_at, k_x,
+                                         k_d, k_p, k_n, STEP_V_PREDICTION if v_prediction else 0, x.numel(), cur_stream()),
+          "cfg_dpmpp_2m_sde_step")
+    return x_next
+
+
 def mask_dims(mask, x):
     """(mask_n, mask_c) of a mask torch would broadcast against the (n, C, h, w) latent x: shape (n|1, C|1, h, w)"""
     n, c, h, w = x.shape

@@ -356,6 +356,51 @@ class SdeoRuntime(_HandleRuntime):
                                                  cur_stream()), "dpmpp_2m_step_masked")
         return x
 
+    def _eta_args(self, x, noise, orig, mask_noise, mask):
+        """the operand block the two stochastic steps share: the step noise row, then the blend operands (all null without a mask).  What
+        the library refuses (a missing row, a partial set) is passed through as it is."""
+        from .ops import mask_dims
+        for t in (noise, orig, mask_noise):
+            assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.shape == x.shape)
+        mn = mc = 0
+        if mask is not None:
+            assert mask.is_contiguous() and mask.dtype == torch.float32
+            mn, mc = mask_dims(mask, x)
+        return ptr(noise), ptr(orig), ptr(mask_noise), ptr(mask), mn, mc
+
+    def ddim_step_eta(self, x, pred_x0, noise, sigma_t: float, row: int, cfg_scale: float, a_t: float, a_prev: float,
+                      sqrt_one_minus_at: float, scales=None, only_mid_control: bool = False, staged: bool = False, hint_shared: bool = False,
+                      v_prediction: bool = False, orig=None, mask_noise=None, mask=None, sqrt_a: float = 0.0, sqrt_one_minus_a: float = 0.0,
+                      flags: int = 0):
+        """`sdeo_ddim_step_eta`: `ddim_step` with the sampler's noise term, x <- x_prev + sigma_t * noise (dir_coef = sqrt(1 - a_prev -
+        sigma_t^2)), in place; noise (b,4,h,w) fp32 is read by address, so a captured call sees what the row holds at replay.  With orig /
+        mask_noise / mask / sqrt_a / sqrt_one_minus_a the blend of `ddim_step_masked` runs in front (no `staged` then).  Bit-identical to
+        `apply_model` on [x; x] + `ops.cfg_ddim_step` with the same noise and sigma_t."""
+        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
+        assert pred_x0 is None or (pred_x0.is_contiguous() and pred_x0.dtype == torch.float32 and pred_x0.shape == x.shape)
+        pn, po, pm, pk, mn, mc = self._eta_args(x, noise, orig, mask_noise, mask)
+        check(self.lib.sdeo_ddim_step_eta(self.handle, ptr(x), ptr(pred_x0), pn, sigma_t, po, pm, pk, mn, mc, sqrt_a, sqrt_one_minus_a,
+                                          int(row), cfg_scale, a_t, a_prev, sqrt_one_minus_at, self._scales(scales), int(only_mid_control),
+                                          flags | (STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)
+                                          | (STEP_V_PREDICTION if v_prediction else 0), cur_stream()), "ddim_step_eta")
+        return x
+
+    def dpmpp_2m_sde_step(self, x, d, noise, row: int, cfg_scale: float, a_t: float, sqrt_one_minus_at: float, k_x: float, k_d: float,
+                          k_p: float, k_n: float, scales=None, only_mid_control: bool = False, staged: bool = False,
+                          hint_shared: bool = False, v_prediction: bool = False, orig=None, mask_noise=None, mask=None, sqrt_a: float = 0.0,
+                          sqrt_one_minus_a: float = 0.0, flags: int = 0):
+        """`sdeo_dpmpp_2m_sde_step`: `dpmpp_2m_step` with the SDE solver's fourth term, x <- k_x x + k_d D + k_p d + k_n noise, d <- D;
+        the blend operands as in `ddim_step_eta`"""
+        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
+        assert d is None or (d.is_contiguous() and d.dtype == torch.float32 and d.shape == x.shape)
+        pn, po, pm, pk, mn, mc = self._eta_args(x, noise, orig, mask_noise, mask)
+        check(self.lib.sdeo_dpmpp_2m_sde_step(self.handle, ptr(x), ptr(d), pn, po, pm, pk, mn, mc, sqrt_a, sqrt_one_minus_a, int(row),
+                                              cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, k_n, self._scales(scales),
+                                              int(only_mid_control),
+                                              flags | (STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)
+                                              | (STEP_V_PREDICTION if v_prediction else 0), cur_stream()), "dpmpp_2m_sde_step")
+        return x
+
     def vae_decode(self, z, want_u8: bool = False):
         """z (b,4,h,w) latents (sampler output) -> images (b,3,8h,8w) fp32 in [-1,1] (+ optional NHWC uint8)."""
         v = self.vcfg
