@@ -388,6 +388,28 @@ int sdeo_enable_vae_encoder(sdeo_handle h);
 int sdeo_vae_encode(sdeo_handle h, const float* images, const uint8_t* images_u8, int n, const float* noise, float* z, float* moments,
                     void* stream);
 
+/* Multi-ControlNet (opt-in): K = 1 + count control networks on one UNet, their residuals summed,
+ *   control[i] = sum_j scales_j[i] * ControlNet_j(x, hint_j, t, context)[i],  eps = ControlledUnetModel(x, t, context, control).
+ * Net 0 is "control_model."; net j = 1..count registers the same tensor set under "control_model_<j>." behind everything registered
+ * before (existing offsets do not move), fp8-eligible like net 0's.  count in 1..3.  Call it once, after sdeo_create[_ex] and before
+ * the first sdeo_load_weight.  Without this call nothing about the handle changes.  With it, sdeo_apply_model and every sdeo_*_step
+ * run all the nets (the extra ones on the side stream behind net 0; the fused decoder applies each extra net's 13 zero convs as one
+ * more multi-problem launch, in place over the running sum), sdeo_set_timestep_table fills a table per net, the context K / V of every
+ * net is recomputed whenever net 0's is, SDEO_STEP_HINT_SHARED vouches for the hints of every net, and only_mid_control /
+ * SDEO_NO_CONTROL apply to all of them.  sdeo_unet_forward is untouched.  sdeo_finalize_weights refuses block-scaled fp8 activations
+ * (sdeo_set_activation_precision 8) on such a handle. */
+int sdeo_enable_extra_controlnets(sdeo_handle h, int count);
+/* Net `net`'s (1..count) hint [n][hint_channels][8h][8w] fp32: copied in and run through that net's hint block into its own cached
+ * features (what a new `hint` argument does for net 0; `hint` and SDEO_HINT_CACHED of the other entry points refer to net 0 only).
+ * Capturable.  sdeo_configure invalidates the cache: a forward on a handle with an extra net whose hint was not set since is refused. */
+int sdeo_set_control_hint(sdeo_handle h, int net, const float* hint, void* stream);
+/* Net `net`'s (1..count) 13 control scales (NULL: all 1).  They persist until changed (sdeo_configure resets them to 1) and are read
+ * at launch with only_mid_control folded in, like net 0's: a captured step bakes them in.  Net 0's scales stay an argument of each call. */
+int sdeo_set_control_scales(sdeo_handle h, int net, const float* host_scales13);
+/* sdeo_controlnet_forward for net `net` (0..count; net 0 is that function): the 13 unscaled controls of one net. */
+int sdeo_controlnet_forward_net(sdeo_handle h, int net, const float* x_noisy, const float* hint, const int64_t* timesteps,
+                                const float* context, float* const* controls, int flags, void* stream);
+
 /* bytes of device memory the handle owns (weights + arena) */
 size_t sdeo_device_bytes(sdeo_handle h);
 

@@ -56,8 +56,9 @@ class hackathon():
         self.apply_canny = apply_canny or _default_canny()
         return self._init_model(weights, config, text_encoder, vae_encoder, sampler=sampler)
 
-    def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim"):
-        """text encoder, ControlLDM and sampler of `initialize` (shared with hed2image)"""
+    def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim", extra_control=()):
+        """text encoder, ControlLDM and sampler of `initialize` (shared with hed2image).  extra_control: the weights of each extra
+        control network (multi2image): a checkpoint path, a state dict with `control_model.*` names or "synthetic:<seed>"."""
         if sampler not in ("ddim", "dpmpp_2m", "dpmpp_2m_sde"):
             raise ValueError(f'sampler {sampler!r}: "ddim", "dpmpp_2m" or "dpmpp_2m_sde"')
         if isinstance(text_encoder, str) and text_encoder.split(":")[0] in ("clip", "openclip"):
@@ -74,12 +75,14 @@ class hackathon():
                 ccfg = dataclasses.replace(S.CLIP_TINY21, width=S.UNET_TINY21.context_dim) if tiny else S.CLIP_SD21
                 text_encoder = FrozenOpenCLIPEmbedder(version=tok_dir, layer="penultimate", config=ccfg,
                                                       allow_hash_tokenizer=synthetic and tok_dir is None)
-        self.model = create_model(config, cond_stage_model=text_encoder, vae_encoder=vae_encoder)
+        self.model = create_model(config, cond_stage_model=text_encoder, vae_encoder=vae_encoder, extra_controlnets=len(extra_control))
         if text_encoder is None:      # the seeded stand-in, as wide as the chosen config's context
             text_encoder = functools.partial(synthetic_text_encoder, length=self.model.rt.ucfg.context_len, dim=self.model.rt.ucfg.context_dim)
             self.model.cond_stage_model = text_encoder
         self.text_encoder = text_encoder
-        if isinstance(weights, str) and weights.startswith("synthetic"):
+        if extra_control:
+            self._load_with_extra(weights, extra_control)
+        elif isinstance(weights, str) and weights.startswith("synthetic"):
             seed = int(weights.split(":")[1]) if ":" in weights else 0
             self.model.rt.load_synthetic(seed)
             if hasattr(self.text_encoder, "transformer"):
@@ -98,6 +101,36 @@ class hackathon():
         else:
             self.ddim_sampler = DDIMSampler(self.model)
         return self
+
+    def _load_with_extra(self, weights, extra_control):
+        """`weights` for the UNet, net 0, the VAE and the text encoder as in `_init_model`, extra_control[j - 1] for control net j;
+        tensor by tensor (never a whole fp32 net on the host for the synthetic ones), finalised once"""
+        from .cldm.model import load_state_dict
+        rt = self.model.rt
+        synthetic = lambda w: isinstance(w, str) and w.startswith("synthetic")
+        seed_of = lambda w: int(w.split(":")[1]) if ":" in w else 0
+        expected = rt.expected_weights()
+        prefixes = tuple(f"control_model_{j}." for j in range(1, len(extra_control) + 1))
+        for prefix, cw in zip(prefixes, extra_control):
+            if synthetic(cw):
+                for name, shape in expected.items():
+                    if name.startswith(prefix):
+                        rt.load_tensor(name, S.synth_tensor(name, shape, seed_of(cw)))
+            else:
+                sd = cw if isinstance(cw, dict) else load_state_dict(cw, location="cuda")
+                for k, v in sd.items():
+                    if k.startswith(S.NS_CONTROL):
+                        rt.load_tensor(prefix + k[len(S.NS_CONTROL):], v, False)
+        if synthetic(weights):
+            for name, shape in expected.items():
+                if not name.startswith(prefixes):
+                    rt.load_tensor(name, S.synth_tensor(name, shape, seed_of(weights)))
+            rt._finalize()
+            if hasattr(self.text_encoder, "transformer"):
+                self.text_encoder.transformer.load_synthetic(seed_of(weights))
+        else:
+            sd = weights if isinstance(weights, dict) else load_state_dict(weights, location="cuda")
+            self.model.load_state_dict(sd)       # (the extra nets are loaded: this finalises everything)
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, ddim_steps, guess_mode,
                 strength, scale, seed, eta, low_threshold, high_threshold, x_T=None, init_image=None, denoise_strength=0.75, mask_image=None):
@@ -133,21 +166,23 @@ class hackathon():
     def _sample(self, control, prompt, a_prompt, n_prompt, num_samples, H, W, ddim_steps, guess_mode, strength, scale, seed, eta, x_T=None,
                 init_image=None, image_resolution=None, denoise_strength=0.75, mask_image=None):
         """everything of `process` after the hint (`canny2image_torch.py:40-71`): seeding, conditioning, the DDIM loop and the decode
-        to uint8 HWC images; control is the (num_samples, 3, H, W) fp32 hint on the device"""
+        to uint8 HWC images; control is the (num_samples, 3, H, W) fp32 hint on the device -- or, with several control networks, the list
+        of their hints, and strength one float per net"""
         with torch.no_grad():
             if seed == -1:
                 seed = random.randint(0, 65535)
             random.seed(seed)
             np.random.seed(seed)
             torch.manual_seed(seed)       # pytorch_lightning.seed_everything (`canny2image_torch.py:42`)
-            cond = {"c_concat": [control],
+            control = list(control) if isinstance(control, (list, tuple)) else [control]
+            cond = {"c_concat": control,
                     "c_crossattn": [self.model.get_learned_conditioning([prompt + ", " + a_prompt] * num_samples)]}
-            un_cond = {"c_concat": None if guess_mode else [control],
+            un_cond = {"c_concat": None if guess_mode else control,
                        "c_crossattn": [self.model.get_learned_conditioning([n_prompt] * num_samples)]}
             shape = (4, H // 8, W // 8)
             # `canny2image_torch.py:54`: guess-mode scales 0.825**(12-i)
-            self.model.control_scales = ([strength * (0.825 ** float(12 - i)) for i in range(13)] if guess_mode
-                                         else ([strength] * 13))
+            per_net = lambda st: [st * (0.825 ** float(12 - i)) for i in range(13)] if guess_mode else [st] * 13
+            self.model.control_scales = [per_net(st) for st in strength] if isinstance(strength, (list, tuple)) else per_net(strength)
             if init_image is None:
                 samples, intermediates = self.ddim_sampler.sample(ddim_steps, num_samples, shape, cond, verbose=False, eta=eta,
                                                                   unconditional_guidance_scale=scale,

@@ -137,8 +137,9 @@ class ControlLDM:
     def eval(self):
         return self
 
-    def load_state_dict(self, sd, strict=False):
-        self.rt.load_state_dict(sd, strict=strict)
+    def load_state_dict(self, sd, strict=False, extra_control=None):
+        """extra_control: one state dict per extra control network (`SdeoRuntime.load_state_dict`)"""
+        self.rt.load_state_dict(sd, strict=strict, extra_control=extra_control)
         if hasattr(self.cond_stage_model, "load_state_dict"):      # FrozenCLIPEmbedder mirror: cond_stage_model.transformer.*;
             # FrozenOpenCLIPEmbedder mirror: cond_stage_model.model.*
             self.cond_stage_model.load_state_dict({k: v for k, v in sd.items() if "text_model." in k or k.startswith("cond_stage_model.model.")},
@@ -181,15 +182,48 @@ class ControlLDM:
         ext = lambda a: a.to(x_t.device)[t].reshape(-1, *([1] * (x_t.dim() - 1)))
         return ext(self.sqrt_alphas_cumprod) * v + ext(self.sqrt_one_minus_alphas_cumprod) * x_t
 
+    # -- several control networks: `control_scales` is the reference's one attribute, a flat list of 13 applied to every net, or a list
+    # of one list of 13 per net
+    def per_net_scales(self):
+        k = 1 + self.rt.extra_controlnets
+        cs = list(self.control_scales)
+        if cs and isinstance(cs[0], (list, tuple)):
+            if len(cs) != k:
+                raise ValueError(f"control_scales holds {len(cs)} lists, the model has {k} control networks")
+            return [[float(v) for v in row] for row in cs]
+        return [[float(v) for v in cs] for _ in range(k)]
+
+    def net0_scales(self):
+        """net 0's scales, the argument of every runtime call; the extra nets' are handed to the runtime here when they changed"""
+        per = self.per_net_scales()
+        for j in range(1, len(per)):
+            if self.rt._extra_scales[j - 1] != tuple(per[j]):
+                self.rt.set_control_scales(j, per[j])
+        return per[0]
+
+    def scales_key(self):
+        """every net's scales: part of the key of every captured graph"""
+        return tuple(v for row in self.per_net_scales() for v in row)
+
     def apply_model(self, x_noisy, t, cond, *args, flags: int = 0, out=None, **kwargs):
-        """`cldm/cldm.py:328-341`."""
+        """`cldm/cldm.py:328-341`.  With K control networks the channel concatenation of c_concat holds K hints: chunk j is net j's."""
         assert isinstance(cond, dict)
         cond_txt = torch.cat(cond["c_crossattn"], 1) if cond["c_crossattn"] is not None else None
         self.rt.configure(x_noisy.shape[0], x_noisy.shape[2], x_noisy.shape[3])
         if cond["c_concat"] is None:
             return self.rt.apply_model(x_noisy, None, t, cond_txt, None, self.only_mid_control, flags & CONTEXT_CACHED, out)
         hint = torch.cat(cond["c_concat"], 1)
-        return self.rt.apply_model(x_noisy, hint, t, cond_txt, self.control_scales, self.only_mid_control, flags, out)
+        k, hc = 1 + self.rt.extra_controlnets, self.rt.ucfg.hint_channels
+        if hint.shape[1] != k * hc:
+            raise ValueError(f"c_concat has {hint.shape[1]} channels: {k} control networks of {hc} hint channels each need {k * hc}")
+        scales0 = self.net0_scales()
+        if k > 1:
+            chunks = torch.split(hint, hc, dim=1)
+            hint = chunks[0]
+            for j in range(1, k):
+                if not (flags & HINT_CACHED) or not self.rt.extra_hint_is_set(j):
+                    self.rt.set_control_hint(j, chunks[j])
+        return self.rt.apply_model(x_noisy, hint, t, cond_txt, scales0, self.only_mid_control, flags, out)
 
     def encode_first_stage(self, x):
         """upstream LatentDiffusion.encode_first_stage: first_stage_model.encode(x) (a DiagonalGaussianDistribution)."""

@@ -319,7 +319,7 @@ class DDIMSampler(object):
         # two halves of the batch are equal, which lets the ControlNet share what precedes its first cross-attention (baked in at capture)
         hint_shared = self._ident(c["c_concat"]) == self._ident(uc["c_concat"])
         key = (rt.generation, tuple(img.shape), tuple(int(t) for t in time_range), float(scale), int(log_every_t),
-               tuple(float(v) for v in m.control_scales), bool(m.only_mid_control), getattr(self, "_schedule_key", None), LOOP_GRAPH_STEPS,
+               m.scales_key(), bool(m.only_mid_control), getattr(self, "_schedule_key", None), LOOP_GRAPH_STEPS,
                hint_shared, m.parameterization, None if mask is None else tuple(mask.shape))
         if getattr(rt, "_table_key", None) != (rt.generation, tuple(int(t) for t in time_range)):
             rt.set_timestep_table(time_range)            # another schedule used the runtime since (the graphs read the table by address)
@@ -343,16 +343,16 @@ class DDIMSampler(object):
                             blend = {} if mask is None else dict(orig=orig, mask_noise=noise[i], mask=mask_buf, sqrt_a=coefs[i][0],
                                                                  sqrt_one_minus_a=coefs[i][1])
                             rt.ddim_step_eta(self._loop_x, self._loop_pred, step_noise[i], float(sig[index]), i, scale, float(a_t[index]),
-                                             float(a_p[index]), float(s1m[index]), m.control_scales, m.only_mid_control,
+                                             float(a_p[index]), float(s1m[index]), m.net0_scales(), m.only_mid_control,
                                              staged=i > first and mask is None, hint_shared=hint_shared,
                                              v_prediction=m.parameterization == "v", **blend)
                         elif mask is None:
                             rt.ddim_step(self._loop_x, self._loop_pred, i, scale, float(a_t[index]), float(a_p[index]), float(s1m[index]),
-                                         m.control_scales, m.only_mid_control, staged=i > first, hint_shared=hint_shared,
+                                         m.net0_scales(), m.only_mid_control, staged=i > first, hint_shared=hint_shared,
                                          v_prediction=m.parameterization == "v")
                         else:
                             rt.ddim_step_masked(self._loop_x, self._loop_pred, orig, noise[i], mask_buf, *coefs[i], i, scale,
-                                                float(a_t[index]), float(a_p[index]), float(s1m[index]), m.control_scales,
+                                                float(a_t[index]), float(a_p[index]), float(s1m[index]), m.net0_scales(),
                                                 m.only_mid_control, hint_shared=hint_shared, v_prediction=m.parameterization == "v")
                         if index % log_every_t == 0:
                             kept_x.append(self._loop_x.clone())
@@ -393,9 +393,9 @@ class DDIMSampler(object):
         if key == self._cache_key:
             rt = m.rt.configure(2 * b, x.shape[2], x.shape[3])
             if USE_GRAPH:
-                eps2 = rt.apply_model_graphed(torch.cat([x, x]), torch.cat([t, t]), m.control_scales, m.only_mid_control)
+                eps2 = rt.apply_model_graphed(torch.cat([x, x]), torch.cat([t, t]), m.net0_scales(), m.only_mid_control)
             else:
-                eps2 = rt.apply_model(torch.cat([x, x]), None, torch.cat([t, t]), None, m.control_scales,
+                eps2 = rt.apply_model(torch.cat([x, x]), None, torch.cat([t, t]), None, m.net0_scales(),
                                       m.only_mid_control, HINT_CACHED | CONTEXT_CACHED)
         else:
             hint_c, hint_u = torch.cat(c["c_concat"], 1), torch.cat(uc["c_concat"], 1)

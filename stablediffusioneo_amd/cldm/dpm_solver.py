@@ -242,7 +242,7 @@ class DPMSolverSampler(object):
         hint_shared = ident(c["c_concat"]) == ident(uc["c_concat"])
         per_graph = dh.LOOP_GRAPH_STEPS if dh.LOOP_GRAPH_STEPS > 0 else total_steps
         # (rt.generation is read after step 1: the first forward at a new shape re-plans the runtime)
-        shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), tuple(float(v) for v in m.control_scales),
+        shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), m.scales_key(),
                      bool(m.only_mid_control), self._schedule_key, per_graph, hint_shared, m.parameterization,
                      None if mask is None else tuple(mask.shape))
         # the stochastic subclass: step i adds k_n[i] * noise, read from a row drawn per image in the per-step loop's order
@@ -285,15 +285,15 @@ class DPMSolverSampler(object):
                             blend = {} if mask is None else dict(orig=orig, mask_noise=noise[i], mask=mask_buf, sqrt_a=coefs[i][0],
                                                                  sqrt_one_minus_a=coefs[i][1])
                             rt.dpmpp_2m_sde_step(self._loop_x, self._loop_d, step_noise[i], i, scale, a, float(np.sqrt(1.0 - a)), float(k_x[i]),
-                                                 float(k_d[i]), float(k_p[i]), float(k_n[i]), m.control_scales, m.only_mid_control,
+                                                 float(k_d[i]), float(k_p[i]), float(k_n[i]), m.net0_scales(), m.only_mid_control,
                                                  staged=i > first and mask is None, hint_shared=hint_shared, v_prediction=v_pred, **blend)
                         elif mask is None:
                             rt.dpmpp_2m_step(self._loop_x, self._loop_d, i, scale, a, float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]),
-                                             float(k_p[i]), m.control_scales, m.only_mid_control, staged=i > first, hint_shared=hint_shared,
+                                             float(k_p[i]), m.net0_scales(), m.only_mid_control, staged=i > first, hint_shared=hint_shared,
                                              v_prediction=v_pred)
                         else:
                             rt.dpmpp_2m_step_masked(self._loop_x, self._loop_d, orig, noise[i], mask_buf, *coefs[i], i, scale, a,
-                                                    float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]), float(k_p[i]), m.control_scales,
+                                                    float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]), float(k_p[i]), m.net0_scales(),
                                                     m.only_mid_control, hint_shared=hint_shared, v_prediction=v_pred)
                         if (total_steps - i - 1) % log_every_t == 0:
                             kept_x.append(self._loop_x.clone())

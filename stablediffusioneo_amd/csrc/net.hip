@@ -24,6 +24,8 @@
 //   * the two halves of sdeo_ddim_step's CFG batch [x; x] differ only in their text context, so what a network computes before its
 //     first cross-attention (input_blocks.1: ResBlock, proj_in, self-attention, attn2.to_q) runs on the first half only and the
 //     full-batch launches behind it read the half-batch tensors twice (P_UNET_ENC_SH / P_CN_SH, build_shared_prefix).
+//   * several control networks (sdeo_enable_extra_controlnets) share the UNet: the extra ones run behind net 0 on its stream and the fused
+//     decoder adds scale_j * zero_conv_j(cn_h[j][i]) to the running sum of control i in place, one multi-problem launch per extra net.
 #include <cmath>
 #include <functional>
 #include <memory>
@@ -83,8 +85,14 @@ struct Lane {
 enum { L_MAIN, L_SIDE, L_COUNT };
 
 constexpr int kMaxControls = 13;
+// Control networks of one handle: net 0 is `control_model.`, nets 1.. the ones sdeo_enable_extra_controlnets registered under
+// `control_model_<j>.`.  Per-network state is indexed by `net`: 0 = the UNet, 1 + j = control network j.
+constexpr int kMaxControlNets = 4;
+constexpr int kNets = 1 + kMaxControlNets;
+// programs every control network has: net 0's are P_HINT / P_CTX_CN / P_CN / P_CN_SH / P_TEMB_CN, an extra net's live in Engine::xprog
+enum CnProg { CP_HINT, CP_CTX, CP_CN, CP_CN_SH, CP_TEMB, CP_COUNT };
 
-// Programs of a configured handle.  P_TEMB + net: the time embedding of one network.  P_UNET_ENC_SH / P_CN_SH: P_UNET_ENC / P_CN with
+// Programs of a configured handle.  P_TEMB + net: the time embedding of the UNet (0) and of control net 0 (1).  P_UNET_ENC_SH / P_CN_SH: P_UNET_ENC / P_CN with
 // input_blocks.1 up to its cross-attention run on the first N / 2 images only (build_shared_prefix); empty when N is odd or the block
 // has no transformer
 enum ProgId {
@@ -107,7 +115,7 @@ struct sdeo_handle_s {
   Fp8State fp8;
   bool finalized = false;
   // per-net stacked time-embedding projection
-  int emb_total[2] = {0, 0};
+  int emb_total[kNets] = {0};
   std::unordered_map<std::string, int> emb_row;        // "<ns><resblock>" -> row offset
   // problem size, arenas + workspaces (lanes[L_MAIN].base != nullptr: configured), side stream
   int N = 0, lh = 0, lw = 0;
@@ -116,7 +124,7 @@ struct sdeo_handle_s {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool overlap = true;       // SDEO_OVERLAP=0 runs ControlNet and UNet back to back on one stream
   // boundary buffers (device, owned)
-  float* in_x = nullptr; float* in_hint = nullptr; float* in_ctx = nullptr; int64_t* in_t = nullptr;
+  float* in_x = nullptr; float* in_hint[kMaxControlNets] = {nullptr}; float* in_ctx = nullptr; int64_t* in_t = nullptr;
   float* in_ctrl[kMaxControls] = {nullptr};
   float* out_eps = nullptr;
   float* out_ctrl[kMaxControls] = {nullptr};
@@ -129,20 +137,27 @@ struct sdeo_handle_s {
   std::vector<void*> extra_allocs;
   // persistent activations
   T ctrl[kMaxControls];  // fp16 NHWC controls (ControlNet output / UNet input), unscaled
-  T cn_h[kMaxControls];  // the ControlNet block outputs the zero convs read (kept until the UNet decoder has run)
+  T cn_h[kMaxControlNets][kMaxControls];  // per control net: the block outputs the zero convs read (kept until the UNet decoder has run)
   float scales[kMaxControls];
-  float eff_scales[kMaxControls];  // scales with only_mid_control folded in (0 for the twelve skip controls), read at launch by P_UNET_DEC_FUSED
+  // per control net: scales with only_mid_control folded in (0 for the twelve skip controls), read at launch by P_UNET_DEC_FUSED
+  float eff_scales[kMaxControlNets][kMaxControls];
   int only_mid = 0;
+  // extra control networks (sdeo_enable_extra_controlnets): how many, their programs, the scales sdeo_set_control_scales left
+  // (extra_scales[j - 1], kept until changed) and whether sdeo_set_control_hint filled net j's hint cache since the last configure
+  int extra = 0;
+  Program xprog[kMaxControlNets - 1][CP_COUNT];
+  float extra_scales[kMaxControlNets - 1][kMaxControls];
+  bool extra_hint_set[kMaxControlNets - 1] = {false};
   // time embedding (`openaimodel.py:777-781` + every ResBlock's emb_layers): fp32 [N][emb_total] per net, written by P_TEMB + net from
   // in_t -- or, for a sampler that announced its schedule (sdeo_set_timestep_table), one row of a table computed once per schedule.
   // The ResBlock convs read their pointer / row stride at LAUNCH time (emb_cur / emb_ld_cur), like the control scales.
   static constexpr int kTabRows = 128;
-  float* emb_all[2] = {nullptr, nullptr};
-  float* temb_tab[2] = {nullptr, nullptr};     // [kTabRows][emb_total[net]]
+  float* emb_all[kNets] = {nullptr};
+  float* temb_tab[kNets] = {nullptr};          // [kTabRows][emb_total[net]]
   int64_t* tab_t = nullptr;                    // device int64 [kTabRows]
   int tab_count = 0;
-  const float* emb_cur[2] = {nullptr, nullptr};
-  int emb_ld_cur[2] = {0, 0};
+  const float* emb_cur[kNets] = {nullptr};
+  int emb_ld_cur[kNets] = {0};
   T x0;                  // fp16 NHWC copy of the latent input, shared by ControlNet and UNet (P_X0 writes it from in_x)
   T eps16;               // the UNet's eps before the NCHW fp32 export (P_EPS_EXPORT), read directly by sdeo_ddim_step
   Program prog[P_COUNT]; // free_configured clears them all
@@ -306,6 +321,20 @@ static void reg_vae_res(Registry& r, const std::string& p, int cin, int cout) {
   if (cin != cout) r.conv(p + ".nin_shortcut", cin, cout, 1);
 }
 
+// namespace of network `net`'s tensors: the UNet, `control_model.`, `control_model_<j>.` for the extra control net j = net - 1
+static std::string net_ns(int net) { return net == 0 ? NS_UNET : net == 1 ? NS_CN : "control_model_" + std::to_string(net - 1) + "."; }
+
+// the full tensor set of one control network under its namespace
+static void reg_controlnet(Registry& r, int net) {
+  Engine* e = r.e;
+  const std::string ns = net_ns(net);
+  reg_unet_like(r, ns, e->cplan, e->cfg, net);
+  for (size_t i = 0; i < e->cplan.in_ch.size(); ++i)
+    r.conv(ns + "zero_convs." + std::to_string(i) + ".0", e->cplan.in_ch[i], e->cplan.in_ch[i], 1);
+  for (auto& hc : e->hconvs) r.conv(ns + hc.name, hc.cin, hc.cout, 3, round8(hc.cout));
+  r.conv(ns + "middle_block_out.0", e->cplan.in_ch.back(), e->cplan.in_ch.back(), 1);
+}
+
 static void build_registry(Engine* e) {
   Registry r{e};
   const sdeo_config& c = e->cfg;
@@ -313,12 +342,7 @@ static void build_registry(Engine* e) {
   reg_unet_like(r, NS_UNET, e->uplan, c, 0);
   r.norm(std::string(NS_UNET) + "out.0", c.model_channels);
   r.conv(std::string(NS_UNET) + "out.2", c.model_channels, c.out_channels, 3, (c.out_channels + 3) / 4 * 4);
-  // ControlNet
-  reg_unet_like(r, NS_CN, e->cplan, c, 1);
-  for (size_t i = 0; i < e->cplan.in_ch.size(); ++i)
-    r.conv(std::string(NS_CN) + "zero_convs." + std::to_string(i) + ".0", e->cplan.in_ch[i], e->cplan.in_ch[i], 1);
-  for (auto& hc : e->hconvs) r.conv(std::string(NS_CN) + hc.name, hc.cin, hc.cout, 3, round8(hc.cout));
-  r.conv(std::string(NS_CN) + "middle_block_out.0", e->cplan.in_ch.back(), e->cplan.in_ch.back(), 1);
+  reg_controlnet(r, 1);
   // VAE decode path
   r.quant = false;                   // the VAE stays fp16 (BASELINE configs[4])
   const std::string d = std::string(NS_VAE) + "decoder";
@@ -832,10 +856,11 @@ static T build_vae_attn(Builder& b, const std::string& p, T hcur) {
 struct BuildCtx {      // state of one build_all pass
   Builder b;
   int N, h, w, TkS, nctrl;
-  std::unordered_map<std::string, T> kv[2];   // per net: attn block name -> cached K | V
-  T ctx16, hint_feat;
+  std::unordered_map<std::string, T> kv[kNets];   // per net: attn block name -> cached K | V
+  T ctx16, hint_feat[kMaxControlNets];            // per control net: the cached output of its hint block
 };
-static const char* const kNetNs[2] = {NS_UNET, NS_CN};
+static const ProgId kCnProg0[CP_COUNT] = {P_HINT, P_CTX_CN, P_CN, P_CN_SH, P_TEMB_CN};
+static Program& cn_prog(Engine* e, int j, CnProg k) { return j == 0 ? e->prog[kCnProg0[k]] : e->xprog[j - 1][k]; }
 
 // persistent tensors first (never released): controls, context, cached K/V^T, hint features
 static void build_persistent(BuildCtx& c) {
@@ -846,11 +871,13 @@ static void build_persistent(BuildCtx& c) {
     e->ctrl[i] = b.alloc(c.N, c.h / cp.in_ds[j], c.w / cp.in_ds[j], cp.in_ch[j]);
   }
   c.ctx16 = b.alloc2d(c.N * c.TkS, e->cfg.context_dim);
-  c.hint_feat = b.alloc(c.N, c.h, c.w, e->cfg.model_channels);
+  c.hint_feat[0] = b.alloc(c.N, c.h, c.w, e->cfg.model_channels);
   e->x0 = b.alloc(c.N, c.h, c.w, round8(e->cfg.in_channels));
   e->eps16 = b.alloc(c.N, c.h, c.w, 4 * ((e->cfg.out_channels + 3) / 4));
-  for (int net = 0; net < 2; ++net)
-    for (const Blk* ab : attn_blocks(net ? e->cplan : e->uplan)) c.kv[net][std::string(kNetNs[net]) + ab->name] = b.alloc2d(c.N * c.TkS, 2 * ab->cin);
+  for (int net = 0; net < 2 + e->extra; ++net) {        // (the extra nets' tensors behind everything a plain handle places)
+    if (net >= 2) c.hint_feat[net - 1] = b.alloc(c.N, c.h, c.w, e->cfg.model_channels);
+    for (const Blk* ab : attn_blocks(net ? e->cplan : e->uplan)) c.kv[net][net_ns(net) + ab->name] = b.alloc2d(c.N * c.TkS, 2 * ab->cin);
+  }
 }
 
 // latent in: NCHW fp32 -> NHWC fp16, once for both networks; eps out: the reverse
@@ -865,45 +892,46 @@ static void build_latent_io(BuildCtx& c) {
   b.push([=](hipStream_t s) { return nhwc_f16_to_nchw_f32(eo, ein, eld, N, Ce, HW, 1.0f, s); });
 }
 
-// time embedding: per forward (rows = N, t from in_t) and per schedule (rows = kTabRows, t from tab_t), both networks
-// (the ControlNet's runs on the side stream beside the UNet encoder: its temporaries and split-K workspace are the side stream's)
+// time embedding: per forward (rows = N, t from in_t) and per schedule (rows = kTabRows, t from tab_t), every network
+// (a ControlNet's runs on the side stream beside the UNet encoder: its temporaries and split-K workspace are the side stream's)
 static void build_time_embeds(BuildCtx& c) {
   Builder& b = c.b; Engine* e = b.e;
-  for (int net = 0; net < 2; ++net) {
-    b.prog = &e->prog[P_TEMB + net];
-    b.on_lane(&e->lanes[net == 1 ? L_SIDE : L_MAIN], [&] { build_time_embed(b, kNetNs[net], net, c.N, e->in_t, e->emb_all[net]); });
+  for (int net = 0; net < 2 + e->extra; ++net) {
+    b.prog = net == 0 ? &e->prog[P_TEMB] : &cn_prog(e, net - 1, CP_TEMB);
+    b.on_lane(&e->lanes[net >= 1 ? L_SIDE : L_MAIN], [&] { build_time_embed(b, net_ns(net), net, c.N, e->in_t, e->emb_all[net]); });
   }
   b.prog = &e->prog[P_TEMB_TAB];
-  for (int net = 0; net < 2; ++net) build_time_embed(b, kNetNs[net], net, Engine::kTabRows, e->tab_t, e->temb_tab[net]);
+  for (int net = 0; net < 2 + e->extra; ++net) build_time_embed(b, net_ns(net), net, Engine::kTabRows, e->tab_t, e->temb_tab[net]);
 }
 
 // context programs: fp32 [N][77][768] -> fp16 padded; K | V = ctx [Wk; Wv]^T per attn block, one GEMM each
 static void build_context(BuildCtx& c, int net) {
   Builder& b = c.b; Engine* e = b.e;
-  b.prog = &e->prog[net == 0 ? P_CTX_UNET : P_CTX_CN];
+  b.prog = net == 0 ? &e->prog[P_CTX_UNET] : &cn_prog(e, net - 1, CP_CTX);
   f16* o = c.ctx16.p; const float* in = e->in_ctx; const int N = c.N, T_ = e->cfg.context_len, TkS = c.TkS, Cd = e->cfg.context_dim;
   b.push([=](hipStream_t s) { return pad_rows_f32_to_f16(o, in, N, T_, TkS, Cd, s); });
   for (const Blk* ab : attn_blocks(net ? e->cplan : e->uplan)) {
-    const std::string name = std::string(kNetNs[net]) + ab->name;
+    const std::string name = net_ns(net) + ab->name;
     Builder::CO kvo; kvo.out = &c.kv[net][name];
     b.gemm(c.ctx16, b.named_w(name + ".transformer_blocks.0.attn2.to_kv"), e->cfg.context_dim, 2 * ab->cin, nullptr, kvo);
   }
 }
 
-// hint program (`cldm/cldm.py:147-163,288`): 8 conv3x3, SiLU between, cached across steps
-static void build_hint(BuildCtx& c) {
+// hint program of control net j (`cldm/cldm.py:147-163,288`): 8 conv3x3, SiLU between, cached across steps
+static void build_hint(BuildCtx& c, int j) {
   Builder& b = c.b; Engine* e = b.e;
-  b.prog = &e->prog[P_HINT];
+  b.prog = &cn_prog(e, j, CP_HINT);
+  const std::string ns = net_ns(1 + j);
   T x = b.alloc(c.N, 8 * c.h, 8 * c.w, round8(e->cfg.hint_channels));
-  f16* xp = x.p; const float* in = e->in_hint; const int N = c.N, Cc = e->cfg.hint_channels, ld = x.ld, HW = 64 * c.h * c.w;
+  f16* xp = x.p; const float* in = e->in_hint[j]; const int N = c.N, Cc = e->cfg.hint_channels, ld = x.ld, HW = 64 * c.h * c.w;
   b.push([=](hipStream_t s) { return nchw_f32_to_nhwc_f16(xp, ld, in, N, Cc, HW, 1.0f, s); });
   for (size_t i = 0; i < e->hconvs.size(); ++i) {
     const HintConv& hc = e->hconvs[i];
     Builder::CO o;
     o.act = i + 1 < e->hconvs.size() ? 1 : 0;
     o.cout_store = round8(hc.cout);
-    if (i + 1 == e->hconvs.size()) o.out = &c.hint_feat;
-    b.advance(x, b.conv(x, std::string(NS_CN) + hc.name, hc.cout, 3, hc.stride, 0, o));
+    if (i + 1 == e->hconvs.size()) o.out = &c.hint_feat[j];
+    b.advance(x, b.conv(x, ns + hc.name, hc.cout, 3, hc.stride, 0, o));
   }
 }
 
@@ -959,13 +987,15 @@ static void splice(const BuildCtx& c, Program& out, const Program& full, const S
   out.insert(out.end(), full.begin() + sp.last, full.end());
 }
 
-// ControlNet program (`cldm/cldm.py:284-305`)
-static void build_controlnet(BuildCtx& c) {
+// ControlNet program of control net j (`cldm/cldm.py:284-305`).  Every net writes its 13 controls into the same e->ctrl: only
+// sdeo_controlnet_forward[_net] runs the zero convs here, one net per call.
+static void build_controlnet(BuildCtx& c, int j) {
   Builder& b = c.b; Engine* e = b.e;
   Splice sp;
-  Program& p_cn = e->prog[P_CN];
+  Program& p_cn = cn_prog(e, j, CP_CN);
   b.prog = &p_cn;
-  const std::string ns = NS_CN;
+  const int net = 1 + j;
+  const std::string ns = net_ns(net);
   // The block outputs stay allocated (cn_h): sdeo_apply_model / sdeo_ddim_step skip the zero convs here and let the UNet decoder apply
   // them with the skip connection as the residual operand (P_UNET_DEC_FUSED); sdeo_controlnet_forward runs them here (13 controls out).
   auto zero_conv = [&](const T& x, const std::string& name, int cout, const T* out) {
@@ -978,20 +1008,20 @@ static void build_controlnet(BuildCtx& c) {
   for (size_t i = 0; i < e->cplan.in.size(); ++i) {
     if (i == 0) {
       // input_blocks.0 conv, then h += guided_hint (residual epilogue)
-      Builder::CO o; o.res = &c.hint_feat; o.gn_next = true;
+      Builder::CO o; o.res = &c.hint_feat[j]; o.gn_next = true;
       hcur = b.conv(hcur, ns + e->cplan.in[0][0].name, e->cfg.model_channels, 3, 1, 0, o);
     } else if (i == 1) {
-      hcur = build_shared_prefix(c, ns, e->cplan.in[i], hcur, 1, sp);
+      hcur = build_shared_prefix(c, ns, e->cplan.in[i], hcur, net, sp);
     } else {
-      hcur = run_blocks(c, ns, e->cplan.in[i], hcur, false, 1, nullptr);
+      hcur = run_blocks(c, ns, e->cplan.in[i], hcur, false, net, nullptr);
     }
-    e->cn_h[i] = hcur;
+    e->cn_h[j][i] = hcur;
     zero_conv(hcur, ns + "zero_convs." + std::to_string(i) + ".0", e->cplan.in_ch[i], &e->ctrl[i]);
   }
-  T m = run_blocks(c, ns, e->cplan.mid, hcur, false, 1, nullptr);
-  e->cn_h[c.nctrl - 1] = m;
+  T m = run_blocks(c, ns, e->cplan.mid, hcur, false, net, nullptr);
+  e->cn_h[j][c.nctrl - 1] = m;
   zero_conv(m, ns + "middle_block_out.0", e->cplan.in_ch.back(), &e->ctrl[c.nctrl - 1]);
-  splice(c, e->prog[P_CN_SH], p_cn, sp);
+  splice(c, cn_prog(e, j, CP_CN_SH), p_cn, sp);
 }
 
 // control export (fp16 NHWC -> fp32 NCHW boundary buffers) and import
@@ -1024,7 +1054,7 @@ static bool zero_convs_as_one(const BuildCtx& c) {
   const Engine* e = c.b.e;
   if (c.nctrl > kMultiMax || e->fp8.act_bits == 8 || e->uplan.out.size() + 1 != (size_t)c.nctrl) return false;
   for (int i = 0; i < c.nctrl; ++i)
-    if (e->cn_h[i].c % 64) return false;
+    if (e->cn_h[0][i].c % 64) return false;
   return true;
 }
 static void build_unet_decoder_multi(BuildCtx& c, std::vector<T> hs, T cat0, T view0);
@@ -1038,8 +1068,11 @@ static void build_unet_decoder(BuildCtx& c, DecoderMode mode, std::vector<T> hs,
     const f16* cp = e->ctrl[ci].p; const int ldc = e->ctrl[ci].ld; const float* sc = &e->scales[ci];
     b.push([=](hipStream_t s) { return add_scaled(yp, ld, yp, ld, cp, ldc, *sc, rows, Cc, s); });
   } else if (mode == D_FUSED) {
-    Builder::CO zo; zo.out = &view; zo.res = &view; zo.scale_host = &e->eff_scales[ci];
-    b.conv(e->cn_h[ci], std::string(NS_CN) + "middle_block_out.0", view.c, 1, 1, 0, zo);
+    // every extra net chains behind net 0's conv, in place over the running sum (res == out), like the middle block's own
+    for (int j = 0; j <= e->extra; ++j) {
+      Builder::CO zo; zo.out = &view; zo.res = &view; zo.scale_host = &e->eff_scales[j][ci];
+      b.conv(e->cn_h[j][ci], net_ns(1 + j) + "middle_block_out.0", view.c, 1, 1, 0, zo);
+    }
   }
   --ci;
   for (size_t oi = 0; oi < e->uplan.out.size(); ++oi) {
@@ -1049,8 +1082,10 @@ static void build_unet_decoder(BuildCtx& c, DecoderMode mode, std::vector<T> hs,
     const int c_h = cat.c - skip.c;
     if (mode == D_FUSED) {
       const T half = cat.view(c_h, skip.c);
-      Builder::CO zo; zo.out = &half; zo.res = &skip; zo.scale_host = &e->eff_scales[ci];
-      b.conv(e->cn_h[ci], std::string(NS_CN) + "zero_convs." + std::to_string(ci) + ".0", skip.c, 1, 1, 0, zo);
+      for (int j = 0; j <= e->extra; ++j) {
+        Builder::CO zo; zo.out = &half; zo.res = j ? &half : &skip; zo.scale_host = &e->eff_scales[j][ci];
+        b.conv(e->cn_h[j][ci], net_ns(1 + j) + "zero_convs." + std::to_string(ci) + ".0", skip.c, 1, 1, 0, zo);
+      }
     } else {
       f16* yp = cat.p + c_h; const int ld = cat.ld, rows = cat.rows(), Cc = skip.c;
       const f16* ap = skip.p; const int lda = skip.ld;
@@ -1092,10 +1127,12 @@ static void build_unet_decoder_multi(BuildCtx& c, std::vector<T> hs, T cat0, T v
     cats.push_back(b.alloc(prev.n, prev.h * up, prev.w * up, blocks.back().cout + hs[nh - 2 - oi].c));
   }
   // out = scale * zero_conv(cn_h[ci]) + skip into the second half of its stage's buffer (the middle block's: in place over view0)
-  std::vector<ConvGemm> zc;
-  std::vector<const float*> zs;
-  auto zero_conv = [&](int ci, const std::string& name, const T& out, const T& res) {
-    const T& x = e->cn_h[ci];
+  // Net 0's 13 problems are one launch; each extra net adds one more launch of the same tile whose 13 problems work in place on what
+  // the launch before left (res == out, the form the middle block's problem has in every launch) under that net's scales.
+  std::vector<ConvGemm> zc[kMaxControlNets];
+  std::vector<const float*> zs[kMaxControlNets];
+  auto zero_conv_net = [&](int j, int ci, const std::string& name, const T& out, const T& res) {
+    const T& x = e->cn_h[j][ci];
     const WEntry* w = b.W(name + ".weight");
     if (w && w->ipad != x.c && b.err.empty()) b.err = "conv " + name + ": input has " + std::to_string(x.c) + " channels, weight expects " + std::to_string(w->ipad);
     ConvGemm p;
@@ -1103,16 +1140,20 @@ static void build_unet_decoder_multi(BuildCtx& c, std::vector<T> hs, T cat0, T v
     p.B = x.n; p.Hi = p.Ho = x.h; p.Wi = p.Wo = x.w; p.Cin = x.c;
     p.M = x.rows(); p.N = out.c; p.K = x.c;
     p.ldx = x.ld; p.ldw = p.K; p.ldy = out.ld; p.ldres = res.ld;
-    zc.push_back(p);
-    zs.push_back(&e->eff_scales[ci]);
+    zc[j].push_back(p);
+    zs[j].push_back(&e->eff_scales[j][ci]);
+  };
+  auto zero_conv = [&](int ci, const std::string& leaf, const T& out, const T& res) {
+    for (int j = 0; j <= e->extra; ++j) zero_conv_net(j, ci, net_ns(1 + j) + leaf, out, j ? out : res);
   };
   int ci = c.nctrl - 1;
-  zero_conv(ci--, std::string(NS_CN) + "middle_block_out.0", view0, view0);
+  zero_conv(ci--, "middle_block_out.0", view0, view0);
   for (size_t oi = 0; oi < stages; ++oi, --ci) {
     const T& skip = hs[nh - 1 - oi];
-    zero_conv(ci, std::string(NS_CN) + "zero_convs." + std::to_string(ci) + ".0", cats[oi].view(cats[oi].c - skip.c, skip.c), skip);
+    zero_conv(ci, "zero_convs." + std::to_string(ci) + ".0", cats[oi].view(cats[oi].c - skip.c, skip.c), skip);
   }
-  if (!b.dry) b.prog->push_back(conv_gemm_multi_op(zc, kZeroConvTile, zs));
+  if (!b.dry)
+    for (int j = 0; j <= e->extra; ++j) b.prog->push_back(conv_gemm_multi_op(zc[j], kZeroConvTile, zs[j]));
   for (T& skip : hs) b.release(skip);
   for (size_t oi = 0; oi < stages; ++oi) {
     const std::vector<Blk>& blocks = e->uplan.out[oi];
@@ -1253,9 +1294,10 @@ static int build_all(Engine* e, bool dry, size_t* max_splitk, size_t* max_gn, si
   // small programs (their temporaries come and go: only after every persistent tensor has its place)
   build_latent_io(c);
   build_time_embeds(c);
-  for (int net = 0; net < 2; ++net) build_context(c, net);
-  build_hint(c);
-  c.b.on_lane(&e->lanes[L_SIDE], [&] { build_controlnet(c); });
+  for (int net = 0; net < 2 + e->extra; ++net) build_context(c, net);
+  for (int j = 0; j <= e->extra; ++j) build_hint(c, j);
+  // the extra nets run on the side stream behind net 0; every net's block outputs stay allocated there until the decoder has run
+  c.b.on_lane(&e->lanes[L_SIDE], [&] { for (int j = 0; j <= e->extra; ++j) build_controlnet(c, j); });
   build_control_io(c);
   for (int variant = 0; variant < 2; ++variant) build_unet(c, variant == 0);
   build_vae_decoder(c);
@@ -1289,6 +1331,11 @@ static void free_configured(Engine* e) {
     l = Lane();
   }
   for (Program& p : e->prog) p.clear();
+  for (auto& px : e->xprog) for (Program& p : px) p.clear();
+  for (int j = 0; j < kMaxControlNets - 1; ++j) {        // the hint caches are gone with the arenas, the scales return to 1
+    e->extra_hint_set[j] = false;
+    for (float& v : e->extra_scales[j]) v = 1.0f;
+  }
   e->tab_count = e->fp8.mx_launches = 0;
   e->device_bytes = e->ws.slab_bytes + e->fp8.q8_bytes + e->fp8.mx_bytes;      // what stays: the weights and their fp8 packs
 }
@@ -1300,7 +1347,8 @@ static void set_scales(Engine* h, const float* host_scales, int only_mid) {
   h->only_mid = only_mid;
   for (int i = 0; i < kMaxControls; ++i) {
     h->scales[i] = host_scales ? host_scales[i] : 1.0f;
-    h->eff_scales[i] = (only_mid && i != mid) ? 0.0f : h->scales[i];
+    h->eff_scales[0][i] = (only_mid && i != mid) ? 0.0f : h->scales[i];
+    for (int j = 1; j <= h->extra; ++j) h->eff_scales[j][i] = (only_mid && i != mid) ? 0.0f : h->extra_scales[j - 1][i];
   }
 }
 
@@ -1387,6 +1435,23 @@ int sdeo_enable_vae_encoder(sdeo_handle h) {
   return 0;
 }
 
+int sdeo_enable_extra_controlnets(sdeo_handle h, int count) {
+  SDEO_CHECK(count >= 1 && count <= kMaxControlNets - 1, "sdeo_enable_extra_controlnets: count %d out of range (1..%d extra control networks)",
+             count, kMaxControlNets - 1);
+  SDEO_CHECK(h, "sdeo_enable_extra_controlnets: null handle");
+  SDEO_CHECK(!h->extra, "sdeo_enable_extra_controlnets: already called (this handle has %d extra control networks)", h->extra);
+  for (const auto& w : h->ws.entries)
+    SDEO_CHECK(!w.loaded, "sdeo_enable_extra_controlnets: call it before the first sdeo_load_weight (%s is loaded)", w.name.c_str());
+  SDEO_CHECK(!h->finalized && !configured(h), "sdeo_enable_extra_controlnets: call it before sdeo_finalize_weights / sdeo_configure");
+  // behind everything registered so far: the offsets of the existing tensors do not move
+  Registry r{h};
+  for (int j = 1; j <= count; ++j) reg_controlnet(r, 1 + j);
+  if (int rc = h->ws.alloc("sdeo_enable_extra_controlnets", /*zero_fill=*/true)) return rc;
+  h->device_bytes = h->ws.slab_bytes;
+  h->extra = count;
+  return 0;
+}
+
 int sdeo_num_weights(sdeo_handle h) { return h ? (int)h->ws.entries.size() : 0; }
 
 int sdeo_weight_info(sdeo_handle h, int i, const char** name, int64_t dims[4], int* ndim) {
@@ -1402,6 +1467,9 @@ int sdeo_load_weight(sdeo_handle h, const char* name, const float* host_data, co
 
 int sdeo_finalize_weights(sdeo_handle h) {
   SDEO_CHECK(h, "sdeo_finalize_weights: null handle");
+  SDEO_CHECK(!(h->extra && h->fp8.act_bits == 8),
+             "sdeo_finalize_weights: block-scaled fp8 activations (sdeo_set_activation_precision 8) are not supported together with extra "
+             "control networks (%d enabled)", h->extra);
   if (int rc = h->ws.require_all("sdeo_finalize_weights")) return rc;
   // LayerNorm-folded copies of the Linear layers that consume a LayerNorm (rebuilt on every finalize, from the raw tensors)
   for (const FoldJob& f : h->folds) {
@@ -1490,12 +1558,13 @@ static int configure_impl(sdeo_handle h, int n, int latent_h, int latent_w) {
   const size_t px = (size_t)latent_h * latent_w;
   // boundary buffers
   if (int rc = dev_alloc(h, &h->in_x, (size_t)n * c.in_channels * px * 4)) return rc;
-  if (int rc = dev_alloc(h, &h->in_hint, (size_t)n * c.hint_channels * px * 64 * 4)) return rc;
+  for (int j = 0; j <= h->extra; ++j)
+    if (int rc = dev_alloc(h, &h->in_hint[j], (size_t)n * c.hint_channels * px * 64 * 4)) return rc;
   if (int rc = dev_alloc(h, &h->in_ctx, (size_t)n * c.context_len * c.context_dim * 4)) return rc;
   if (int rc = dev_alloc(h, &h->in_t, (size_t)n * 8)) return rc;
   if (int rc = dev_alloc(h, &h->tab_t, (size_t)sdeo_handle_s::kTabRows * 8)) return rc;
   SDEO_HIP(hipMemset(h->tab_t, 0, (size_t)sdeo_handle_s::kTabRows * 8));
-  for (int net = 0; net < 2; ++net) {
+  for (int net = 0; net < 2 + h->extra; ++net) {
     if (int rc = dev_alloc(h, &h->emb_all[net], (size_t)n * h->emb_total[net] * 4)) return rc;
     if (int rc = dev_alloc(h, &h->temb_tab[net], (size_t)sdeo_handle_s::kTabRows * h->emb_total[net] * 4)) return rc;
   }
@@ -1563,13 +1632,14 @@ static int stage_inputs(sdeo_handle h, const float* x, const float* hint, const 
   if (x) if (int rc = copy_in(h->in_x, x, (size_t)h->N * c.in_channels * px * 4, s)) return rc;
   if (t) if (int rc = copy_in(h->in_t, t, (size_t)h->N * 8, s)) return rc;
   if (hint && hint_is_new) {
-    if (int rc = copy_in(h->in_hint, hint, (size_t)h->N * c.hint_channels * px * 64 * 4, s)) return rc;
+    if (int rc = copy_in(h->in_hint[0], hint, (size_t)h->N * c.hint_channels * px * 64 * 4, s)) return rc;
     if (int rc = run(h, h->prog[P_HINT], s)) return rc;
   }
   if (ctx) {
     if (int rc = copy_in(h->in_ctx, ctx, (size_t)h->N * c.context_len * c.context_dim * 4, s)) return rc;
     if (ctx_for_net & 1) if (int rc = run(h, h->prog[P_CTX_UNET], s)) return rc;
-    if (ctx_for_net & 2) if (int rc = run(h, h->prog[P_CTX_CN], s)) return rc;
+    if (ctx_for_net & 2)
+      for (int j = 0; j <= h->extra; ++j) if (int rc = run(h, cn_prog(h, j, CP_CTX), s)) return rc;
   }
   return 0;
 }
@@ -1584,11 +1654,35 @@ static int select_time(sdeo_handle h, int flags, const int64_t* timesteps, const
   const int row = (flags & 8) ? (flags >> 8) : -1;
   SDEO_CHECK(row >= 0 || timesteps, "%s: timesteps required", who);
   SDEO_CHECK(row < h->tab_count, "%s: timestep row %d, but the table holds %d (sdeo_set_timestep_table)", who, row, h->tab_count);
-  for (int net = 0; net < 2; ++net) {
+  for (int net = 0; net < 2 + h->extra; ++net) {
     h->emb_cur[net] = row >= 0 ? h->temb_tab[net] + (size_t)row * h->emb_total[net] : h->emb_all[net];
     h->emb_ld_cur[net] = row >= 0 ? 0 : h->emb_total[net];
   }
   *row_out = row;
+  return 0;
+}
+
+// The time embeddings of the extra control networks.  They run in FRONT of net 0's ControlNet: their temporaries were planned on the
+// empty side arena, where net 0's block outputs (kept until the decoder has run) live afterwards.
+static int run_extra_time_embeds(sdeo_handle h, hipStream_t s) {
+  for (int j = 1; j <= h->extra; ++j) if (int rc = run(h, cn_prog(h, j, CP_TEMB), s)) return rc;
+  return 0;
+}
+
+// the extra control networks, one behind the other on the stream net 0's ControlNet ran on, without their zero convs
+static int run_extra_controlnets(sdeo_handle h, bool shared_cn, hipStream_t s) {
+  for (int j = 1; j <= h->extra; ++j) {
+    const Program& sh = cn_prog(h, j, CP_CN_SH);
+    if (int rc = run(h, shared_cn && !sh.empty() ? sh : cn_prog(h, j, CP_CN), s, true)) return rc;
+  }
+  return 0;
+}
+
+// a forward that runs the control networks needs every extra net's hint cache filled (sdeo_set_control_hint)
+static int extra_hints_ready(sdeo_handle h, const char* who) {
+  for (int j = 1; j <= h->extra; ++j)
+    SDEO_CHECK(h->extra_hint_set[j - 1], "%s: control network %d has no hint since the last sdeo_configure (call sdeo_set_control_hint(h, %d, ...))",
+               who, j, j);
   return 0;
 }
 
@@ -1607,8 +1701,12 @@ static int run_step_programs(sdeo_handle h, bool no_control, bool time_from_tabl
     // fork: ControlNet on the side stream, UNet encoder + middle block on the caller's stream (capturable)
     SDEO_HIP(hipEventRecord(h->ev_fork, s));
     SDEO_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-    if (!time_from_table) if (int rc = run(h, h->prog[P_TEMB + 1], h->side)) return rc;
+    if (!time_from_table) {
+      if (int rc = run(h, h->prog[P_TEMB + 1], h->side)) return rc;
+      if (int rc = run_extra_time_embeds(h, h->side)) return rc;
+    }
     if (int rc = run(h, p_cn, h->side, true)) return rc;
+    if (int rc = run_extra_controlnets(h, shared_cn, h->side)) return rc;
     SDEO_HIP(hipEventRecord(h->ev_join, h->side));
     if (!time_from_table) if (int rc = run(h, h->prog[P_TEMB + 0], s)) return rc;
     if (int rc = run(h, p_unet_enc, s)) return rc;
@@ -1616,31 +1714,79 @@ static int run_step_programs(sdeo_handle h, bool no_control, bool time_from_tabl
   } else {
     if (!time_from_table) {
       if (int rc = run(h, h->prog[P_TEMB + 1], s)) return rc;
+      if (int rc = run_extra_time_embeds(h, s)) return rc;
       if (int rc = run(h, h->prog[P_TEMB + 0], s)) return rc;
     }
     if (int rc = run(h, p_cn, s, true)) return rc;
+    if (int rc = run_extra_controlnets(h, shared_cn, s)) return rc;
     if (int rc = run(h, p_unet_enc, s)) return rc;
   }
   return run(h, h->prog[P_UNET_DEC_FUSED], s);      // applies the zero convs itself (skipped above)
 }
 
-int sdeo_controlnet_forward(sdeo_handle h, const float* x_noisy, const float* hint, const int64_t* timesteps,
-                            const float* context, float* const* controls, int flags, void* stream) {
-  REQUIRE_READY(h);
-  SDEO_CHECK(x_noisy && controls, "sdeo_controlnet_forward: null argument");
-  hipStream_t s = S(stream);
+// copy net j's hint in and run its hint block into its cached features (j >= 1; net 0's goes through stage_inputs)
+static int set_extra_hint(sdeo_handle h, int j, const float* hint, hipStream_t s) {
+  const size_t bytes = (size_t)h->N * h->cfg.hint_channels * h->lh * h->lw * 64 * 4;
+  if (int rc = copy_in(h->in_hint[j], hint, bytes, s)) return rc;
+  if (int rc = run(h, cn_prog(h, j, CP_HINT), s)) return rc;
+  h->extra_hint_set[j - 1] = true;
+  return 0;
+}
+
+static int controlnet_forward_impl(sdeo_handle h, int j, const float* x_noisy, const float* hint, const int64_t* timesteps,
+                                   const float* context, float* const* controls, int flags, const char* who, hipStream_t s) {
+  SDEO_CHECK(x_noisy && controls, "%s: null argument", who);
   const int hint_new = !(flags & 1), ctx_new = !(flags & 2);
-  SDEO_CHECK(!hint_new || hint, "sdeo_controlnet_forward: hint required");
-  SDEO_CHECK(!ctx_new || context, "sdeo_controlnet_forward: context required");
+  SDEO_CHECK(!hint_new || hint, "%s: hint required", who);
+  SDEO_CHECK(!ctx_new || context, "%s: context required", who);
+  SDEO_CHECK(j == 0 || hint_new || h->extra_hint_set[j - 1], "%s: control network %d has no hint since the last sdeo_configure", who, j);
   int trow = -1;
-  if (int rc = select_time(h, flags, timesteps, "sdeo_controlnet_forward", &trow)) return rc;
-  if (int rc = stage_inputs(h, x_noisy, hint, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, hint_new, 2, s)) return rc;
+  if (int rc = select_time(h, flags, timesteps, who, &trow)) return rc;
+  if (int rc = stage_inputs(h, x_noisy, j == 0 ? hint : nullptr, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, hint_new, 2, s)) return rc;
+  if (j > 0 && hint_new) if (int rc = set_extra_hint(h, j, hint, s)) return rc;
   if (int rc = run(h, h->prog[P_X0], s)) return rc;
-  if (trow < 0) if (int rc = run(h, h->prog[P_TEMB + 1], s)) return rc;
-  if (int rc = run(h, h->prog[P_CN], s)) return rc;
+  if (trow < 0) if (int rc = run(h, cn_prog(h, j, CP_TEMB), s)) return rc;
+  if (int rc = run(h, cn_prog(h, j, CP_CN), s)) return rc;
   if (int rc = run(h, h->prog[P_CN_EXPORT], s)) return rc;
   for (size_t i = 0; i < h->ctrl_elems.size(); ++i)
     if (controls[i]) if (int rc = copy_in(controls[i], h->out_ctrl[i], h->ctrl_elems[i] * 4, s)) return rc;
+  return 0;
+}
+
+int sdeo_controlnet_forward(sdeo_handle h, const float* x_noisy, const float* hint, const int64_t* timesteps,
+                            const float* context, float* const* controls, int flags, void* stream) {
+  REQUIRE_READY(h);
+  return controlnet_forward_impl(h, 0, x_noisy, hint, timesteps, context, controls, flags, "sdeo_controlnet_forward", S(stream));
+}
+
+int sdeo_controlnet_forward_net(sdeo_handle h, int net, const float* x_noisy, const float* hint, const int64_t* timesteps,
+                                const float* context, float* const* controls, int flags, void* stream) {
+  SDEO_CHECK(h, "sdeo_controlnet_forward_net: null handle");
+  SDEO_CHECK(net >= 0 && net <= h->extra, "sdeo_controlnet_forward_net: net %d out of range (0..%d)", net, h->extra);
+  REQUIRE_READY(h);
+  return controlnet_forward_impl(h, net, x_noisy, hint, timesteps, context, controls, flags,
+                                 net ? "sdeo_controlnet_forward_net" : "sdeo_controlnet_forward", S(stream));
+}
+
+// what the two setters of an extra net's state check first
+static int extra_net_ok(sdeo_handle h, int net, const char* who) {
+  SDEO_CHECK(h, "%s: null handle", who);
+  SDEO_CHECK(h->extra > 0, "%s: this handle has no extra control networks (call sdeo_enable_extra_controlnets before loading weights)", who);
+  SDEO_CHECK(net >= 1 && net <= h->extra, "%s: net %d out of range (1..%d)", who, net, h->extra);
+  SDEO_CHECK(configured(h), "%s: not configured (call sdeo_configure)", who);
+  return 0;
+}
+
+int sdeo_set_control_hint(sdeo_handle h, int net, const float* hint, void* stream) {
+  if (int rc = extra_net_ok(h, net, "sdeo_set_control_hint")) return rc;
+  SDEO_CHECK(h->finalized, "sdeo_set_control_hint: weights not finalized (call sdeo_finalize_weights)");
+  SDEO_CHECK(hint, "sdeo_set_control_hint: null hint");
+  return set_extra_hint(h, net, hint, S(stream));
+}
+
+int sdeo_set_control_scales(sdeo_handle h, int net, const float* host_scales13) {
+  if (int rc = extra_net_ok(h, net, "sdeo_set_control_scales")) return rc;
+  for (int i = 0; i < kMaxControls; ++i) h->extra_scales[net - 1][i] = host_scales13 ? host_scales13[i] : 1.0f;
   return 0;
 }
 
@@ -1681,6 +1827,7 @@ int sdeo_apply_model(sdeo_handle h, const float* x_noisy, const float* hint, con
   const int hint_new = !(flags & 1), ctx_new = !(flags & 2), no_control = (flags & 4) != 0;
   SDEO_CHECK(!ctx_new || context, "sdeo_apply_model: context required");
   SDEO_CHECK(no_control || !hint_new || hint, "sdeo_apply_model: hint required");
+  if (!no_control) if (int rc = extra_hints_ready(h, "sdeo_apply_model")) return rc;
   int trow = -1;
   if (int rc = select_time(h, flags, timesteps, "sdeo_apply_model", &trow)) return rc;
   if (int rc = stage_inputs(h, x_noisy, no_control ? nullptr : hint, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, hint_new,
@@ -1726,6 +1873,7 @@ static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float*
   SDEO_CHECK(h->N % 2 == 0, "%s: configured for %d images; the CFG pair needs an even count (n = 2 x latents)", who, h->N);
   SDEO_CHECK(table_row >= 0 && table_row < h->tab_count, "%s: timestep row %d, but the table holds %d (sdeo_set_timestep_table)", who,
              table_row, h->tab_count);
+  if (int rc = extra_hints_ready(h, who)) return rc;
   if (blend) {
     SDEO_CHECK(!(flags & SDEO_STEP_LATENT_STAGED), "%s: SDEO_STEP_LATENT_STAGED has no meaning here (the blend changes the latent and always restages it)", who);
     if (int rc = mask_blend_check(who, x, blend->orig, blend->noise, blend->mask, blend->mask_n, blend->mask_c, h->N / 2, h->cfg.in_channels,

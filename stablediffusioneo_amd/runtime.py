@@ -107,10 +107,13 @@ class SdeoRuntime(_HandleRuntime):
     """create -> load_state_dict -> configure(n, h, w) -> controlnet / unet / apply_model / vae_decode."""
 
     def __init__(self, ucfg: S.UNetConfig = S.UNET_SD15, vcfg: S.VAEConfig = S.VAE_SD15, device: Optional[torch.device] = None,
-                 weight_bits: int = 16, act_bits: int = 16, mx_min_rows: int = 0, vae_encoder: bool = False):
+                 weight_bits: int = 16, act_bits: int = 16, mx_min_rows: int = 0, vae_encoder: bool = False,
+                 extra_controlnets: int = 0):
         """weight_bits = 8: the UNet / ControlNet matrices are packed to fp8 (OCP e4m3fn, per-output-channel power-of-two scale) when
         the weights are finalised (BASELINE configs[4]; the reference's precision switch is `onnx2trt_static_plugin.py:40-42`).
-        vae_encoder = True: the handle also expects `first_stage_model.encoder.*` / `quant_conv.*` and runs `vae_encode`."""
+        vae_encoder = True: the handle also expects `first_stage_model.encoder.*` / `quant_conv.*` and runs `vae_encode`.
+        extra_controlnets = k (1..3): the handle also expects `control_model_<j>.*` for j = 1..k and every forward sums the residuals
+        of all 1 + k control networks (`set_control_hint`, `set_control_scales`)."""
         super().__init__(device)
         self.ucfg, self.vcfg = ucfg, vcfg
         self._cfg = make_config(ucfg, vcfg)
@@ -122,6 +125,12 @@ class SdeoRuntime(_HandleRuntime):
         self.vae_encoder = bool(vae_encoder)
         if self.vae_encoder:        # before any weight: the weight slab is sized when the encoder registers its tensors
             check(self.lib.sdeo_enable_vae_encoder(self.handle), "enable_vae_encoder")
+        self.extra_controlnets = int(extra_controlnets)
+        if self.extra_controlnets:  # before any weight, like the encoder
+            check(self.lib.sdeo_enable_extra_controlnets(self.handle, self.extra_controlnets), "enable_extra_controlnets")
+        # what the library holds for the extra nets: the scales last set, and the generation each hint was set in (0: never)
+        self._extra_scales = [None] * self.extra_controlnets
+        self._extra_hint_gen = [0] * self.extra_controlnets
         self.weight_bits = int(weight_bits)
         if self.weight_bits != 16:
             check(self.lib.sdeo_set_weight_precision(self.handle, self.weight_bits), "set_weight_precision")
@@ -136,11 +145,20 @@ class SdeoRuntime(_HandleRuntime):
         self.generation = 0
 
     # ---------------------------------------------------------------- weights
-    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False):
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False, extra_control: Optional[Sequence[Dict[str, torch.Tensor]]] = None):
         """`sd` uses the reference checkpoint names (model.diffusion_model.*, control_model.*, first_stage_model.*).
-        Tensors the hot path does not use (CLIP, VAE encoder, EMA ...) are ignored unless strict."""
+        Tensors the hot path does not use (CLIP, VAE encoder, EMA ...) are ignored unless strict.
+        extra_control: one state dict per extra control network; the tensors named `control_model.*` of dict j - 1 are loaded under
+        `control_model_<j>.*` (a whole control_sd15_*.pth dict is accepted: its other tensors are ignored)."""
+        extra_control = list(extra_control or [])
+        if len(extra_control) != self.extra_controlnets and (extra_control or strict):
+            raise _lib.SdeoError(f"load_state_dict: {len(extra_control)} extra control state dicts for {self.extra_controlnets} extra control networks")
         for k, v in sd.items():
             self.load_tensor(k, v, strict)
+        for j, esd in enumerate(extra_control, 1):
+            for k, v in esd.items():
+                if k.startswith(S.NS_CONTROL):
+                    self.load_tensor(f"control_model_{j}." + k[len(S.NS_CONTROL):], v, strict)
         self._finalize()
 
     def load_synthetic(self, seed: int = 0):
@@ -185,7 +203,31 @@ class SdeoRuntime(_HandleRuntime):
             self.n = self.h = self.w = 0            # a failed configure leaves the handle unconfigured
             check(self.lib.sdeo_configure(self.handle, n, h, w), "configure")
             self.n, self.h, self.w = n, h, w
+            self._extra_scales = [None] * self.extra_controlnets       # the library reset them to 1
         return self
+
+    # ---------------------------------------------------------------- extra control networks
+    def set_control_hint(self, net: int, hint):
+        """`sdeo_set_control_hint`: net (1..extra_controlnets)'s hint (n, hint_channels, 8h, 8w) into that net's cached hint features"""
+        u = self.ucfg
+        hint = self._f32(hint, (self.n, u.hint_channels, 8 * self.h, 8 * self.w))
+        check(self.lib.sdeo_set_control_hint(self.handle, int(net), ptr(hint), cur_stream()), "set_control_hint")
+        if 1 <= net <= self.extra_controlnets:
+            self._extra_hint_gen[net - 1] = self.generation
+
+    def extra_hint_is_set(self, net: int) -> bool:
+        """whether net's hint was set under the current configuration"""
+        return self._extra_hint_gen[net - 1] == self.generation and self.generation > 0
+
+    def set_control_scales(self, net: int, scales=None):
+        """`sdeo_set_control_scales`: net (1..extra_controlnets)'s 13 scales (None: all 1), kept until changed or reconfigured"""
+        check(self.lib.sdeo_set_control_scales(self.handle, int(net), self._scales(scales)), "set_control_scales")
+        if 1 <= net <= self.extra_controlnets:
+            self._extra_scales[net - 1] = tuple(float(s) for s in scales) if scales is not None else None
+
+    def extra_scales_key(self):
+        """the extra nets' scales as the library holds them: part of every key of a captured graph (a capture bakes them in)"""
+        return tuple(self._extra_scales)
 
     def control_shapes(self) -> List[tuple]:
         plan = S.unet_plan(self.ucfg, with_decoder=False)
@@ -213,7 +255,7 @@ class SdeoRuntime(_HandleRuntime):
             return None
         return (C.c_float * 13)(*[float(s) for s in list(scales) + [1.0] * (13 - len(scales))])
 
-    def controlnet(self, x, hint, t, ctx, flags: int = 0, outs: Optional[Sequence[torch.Tensor]] = None):
+    def controlnet(self, x, hint, t, ctx, flags: int = 0, outs: Optional[Sequence[torch.Tensor]] = None, net: int = 0):
         u = self.ucfg
         x = self._f32(x, (self.n, u.in_channels, self.h, self.w))
         hint = self._f32(hint, (self.n, u.hint_channels, 8 * self.h, 8 * self.w)) if hint is not None else None
@@ -222,8 +264,14 @@ class SdeoRuntime(_HandleRuntime):
         if outs is None:
             outs = [torch.empty(s, dtype=torch.float32, device=self.device) for s in self.control_shapes()]
         arr = (C.c_void_p * 13)(*[o.data_ptr() for o in outs])
-        check(self.lib.sdeo_controlnet_forward(self.handle, ptr(x), ptr(hint), ptr(t), ptr(ctx), arr, flags, cur_stream()),
-              "controlnet_forward")
+        if net == 0:
+            check(self.lib.sdeo_controlnet_forward(self.handle, ptr(x), ptr(hint), ptr(t), ptr(ctx), arr, flags, cur_stream()),
+                  "controlnet_forward")
+        else:
+            check(self.lib.sdeo_controlnet_forward_net(self.handle, int(net), ptr(x), ptr(hint), ptr(t), ptr(ctx), arr, flags,
+                                                       cur_stream()), "controlnet_forward_net")
+            if hint is not None and not (flags & HINT_CACHED) and 1 <= net <= self.extra_controlnets:
+                self._extra_hint_gen[net - 1] = self.generation
         return list(outs)
 
     def unet(self, x, t, ctx, control=None, scales=None, only_mid_control=False, flags: int = 0, out=None):
@@ -261,7 +309,8 @@ class SdeoRuntime(_HandleRuntime):
         TensorRT engines the same way, `Engine.py:139-152`).  The graph holds both streams of the step (ControlNet on the
         side stream, UNet encoder on the main one), so the GPU sees the whole fork/join at once.  Inputs are copied into
         fixed device buffers; the returned eps tensor is owned by the runtime (valid until the next call)."""
-        key = (self.generation, self.n, self.h, self.w, tuple(float(s) for s in (scales or [])), bool(only_mid_control))
+        key = (self.generation, self.n, self.h, self.w, tuple(float(s) for s in (scales or [])), bool(only_mid_control),
+               self.extra_scales_key())
         if getattr(self, "_graph_key", None) != key:
             u = self.ucfg
             self._gx = torch.zeros((self.n, u.in_channels, self.h, self.w), dtype=torch.float32, device=self.device)
