@@ -193,6 +193,14 @@ int sdeo_nchw_f32_to_nhwc_f16(void* y, int ldy, const float* x, int n, int c, in
 int sdeo_nhwc_f16_to_nchw_f32(float* y, const void* x, int ldx, int n, int c, int hw, float scale, void* stream);
 int sdeo_oihw_f32_to_krsc_f16(void* y, const float* w, int o, int i, int r, int s, int i_pad, void* stream);
 
+/* The kernel of sdeo_lora_apply on one stored tensor (csrc/lora.hip):  w[o][j] <- fp16(fp32(w[o][j]) + scale * sum_r up[o][r] down[r][j]).
+ * kind: how the tensor is stored -- 1 = matrix [out][in]; 0 = KRSC conv weight [out][k][k][ipad], down in [in][k][k] order, the pad
+ * channels in..ipad-1 neither read nor written; 3 = the GEGLU projection [out = 2H][in] with its value / gate rows interleaved in blocks
+ * of 16 (H % 16 == 0).  k = 1 for matrices; ipad is read for kind 0 only.  up [out][rank], down [rank][in * k * k]: fp32, host or device
+ * pointers (staged with hipMemcpyDefault).  rank 1..1024, scale finite.  Allocates, synchronises `stream` and frees: not capturable. */
+int sdeo_lora_merge_f16(void* w, int kind, int out, int in, int k, int ipad, const float* down, const float* up, int rank, float scale,
+                        void* stream);
+
 /* ------------------------------------------------------------------ net-level entry points */
 
 typedef struct sdeo_config {
@@ -410,8 +418,40 @@ int sdeo_set_control_scales(sdeo_handle h, int net, const float* host_scales13);
 int sdeo_controlnet_forward_net(sdeo_handle h, int net, const float* x_noisy, const float* hint, const int64_t* timesteps,
                                 const float* context, float* const* controls, int flags, void* stream);
 
-/* bytes of device memory the handle owns (weights + arena) */
+/* bytes of device memory the handle owns (weights + arena + the tensors saved under LoRA adapters) */
 size_t sdeo_device_bytes(sdeo_handle h);
+
+/* LoRA adapters, merged on the device IN PLACE into the stored weights (csrc/lora.hip):
+ *   W[o][j] <- fp16( fp32(W[o][j]) + scale * sum_{r < rank} up[o][r] * down[r][j] ),   o < out, j < in * kh * kw
+ * up [out][rank] and down [rank][in * kh * kw] are fp32 in the PyTorch layout of lora_up.weight / lora_down.weight (flattened) and stay
+ * fp32; products and sums are fp32, the add is fp32, the store rounds once to nearest-even.  The update lands where sdeo_load_weight put
+ * the tensor: inside a stacked matrix (to_q | to_k | to_v, attn2.to_k | to_v, the stacked emb_layers), in the row-interleaved GEGLU
+ * projection, in a KRSC conv weight whose pad channels stay zero.  Programs and captured graphs read weights by address, so they stay
+ * valid; what they computed with the earlier weights does not (below).
+ *
+ * sdeo_lora_apply: `name` is a registry name exactly as sdeo_weight_info returns it (any "model.diffusion_model.*", "control_model.*",
+ *   "control_model_<j>.*" or "first_stage_model.*" matrix or conv weight).  down / up may be host or device pointers (copied with
+ *   hipMemcpyDefault).  The first apply on a tensor saves its raw bytes (the copy counts in sdeo_device_bytes); several applies on one
+ *   tensor stack, each rounding once.  Synchronises `stream`; not capturable.  Refused before any device call, each with its own message,
+ *   the handle untouched: a null argument, an unknown name, a bias / norm vector (the GEGLU bias included), rank outside 1..1024, a
+ *   non-finite scale, weights not finalized, and a handle with sdeo_set_weight_precision(h, 8): its fp16 copies hold the dequantised
+ *   values, not the raw ones, so adapters on fp8-weight handles are out of scope.
+ * sdeo_lora_commit: rebuilds what sdeo_finalize_weights derives from the raw tensors (the LayerNorm folds and the ff.net.2 x proj_out
+ *   products) and marks every cache computed with the earlier weights stale, for every net: the hint features, the context K / V and the
+ *   timestep table.  Until the uncached call (a forward given the hint / the context, sdeo_set_control_hint, sdeo_set_timestep_table)
+ *   has run again, a call passing SDEO_HINT_CACHED, SDEO_CONTEXT_CACHED or SDEO_TIMESTEP_ROW and every fused sdeo_*_step is refused, each
+ *   cache with its own message.  Call it once after the last sdeo_lora_apply of a set.
+ * sdeo_lora_clear: copies every saved tensor back, frees the copies (sdeo_device_bytes returns to its earlier figure) and commits: the
+ *   handle is then bit for bit the handle no adapter was applied to.
+ * sdeo_lora_touched: the number of tensors currently modified (saved).
+ * sdeo_read_weight: the current RAW tensor `name`, converted back to fp32 in PyTorch layout into `out` (host or device pointer, as many
+ *   floats as sdeo_weight_info's dims multiply to): the inverse of sdeo_load_weight, the GEGLU de-interleave and KRSC -> OIHW without the
+ *   pad included; vectors are returned as stored (the interleaved GEGLU bias is refused).  A loader / test aid. */
+int sdeo_lora_apply(sdeo_handle h, const char* name, const float* down, const float* up, int rank, float scale, void* stream);
+int sdeo_lora_commit(sdeo_handle h);
+int sdeo_lora_clear(sdeo_handle h);
+int sdeo_lora_touched(sdeo_handle h);
+int sdeo_read_weight(sdeo_handle h, const char* name, float* out);
 
 /* ------------------------------------------------------------------ text encoder
  * FrozenCLIPEmbedder.forward (ldm/modules/encoders/modules.py:123-141): token ids -> CLIPTextModel ->
@@ -441,6 +481,14 @@ int sdeo_clip_configure(sdeo_clip_handle h, int batch);
  * vocabulary are clamped */
 int sdeo_clip_encode(sdeo_clip_handle h, const int32_t* tokens, int batch, float* out, void* stream);
 size_t sdeo_clip_device_bytes(sdeo_clip_handle h);
+/* LoRA adapters on the text tower: sdeo_lora_apply / _commit / _clear / _touched and sdeo_read_weight on the CLIP handle, names as in
+ * sdeo_clip_weight_info (anything up to and including "text_model." is stripped); q_proj / k_proj / v_proj live inside the stacked qkv
+ * matrix.  The tower runs on the raw tensors and caches nothing between encodes, so commit has nothing to rebuild or invalidate. */
+int sdeo_clip_lora_apply(sdeo_clip_handle h, const char* name, const float* down, const float* up, int rank, float scale, void* stream);
+int sdeo_clip_lora_commit(sdeo_clip_handle h);
+int sdeo_clip_lora_clear(sdeo_clip_handle h);
+int sdeo_clip_lora_touched(sdeo_clip_handle h);
+int sdeo_clip_read_weight(sdeo_clip_handle h, const char* name, float* out);
 
 /* ------------------------------------------------------------------ HED soft-edge annotator
  * annotator/hed/__init__.py (ControlNetHED_Apache2 + HEDdetector.__call__): x - norm, five VGG blocks of 3x3 convs + ReLU (2, 2, 3, 3,

@@ -42,7 +42,8 @@ def _default_canny():
 
 class hackathon():
 
-    def initialize(self, weights="synthetic:0", config="sd15", apply_canny=None, text_encoder=None, vae_encoder=False, sampler="ddim"):
+    def initialize(self, weights="synthetic:0", config="sd15", apply_canny=None, text_encoder=None, vae_encoder=False, sampler="ddim",
+                   loras=()):
         """text_encoder: None = `synthetic_text_encoder` (seeded stand-in contexts); "clip:<tokenizer dir>" = the
         FrozenCLIPEmbedder mirror on the HIP path (weights from the same source as the UNet's: synthetic seed or the
         checkpoint's `cond_stage_model.transformer.text_model.*`); bare "clip" is accepted only with synthetic weights (the
@@ -52,11 +53,28 @@ class hackathon():
         the same rules as "clip".  vae_encoder=True also builds the VAE encoder, which `process(init_image=...)` (img2img) needs.
         sampler: "ddim" (the reference's DDIMSampler), "dpmpp_2m" (DPM-Solver++(2M) on a log-SNR grid, `cldm/dpm_solver.py`: a
         deterministic second-order solver meant for about half of DDIM's step count; `process(..., eta != 0)` raises with it) or
-        "dpmpp_2m_sde" (its stochastic form, DPMSolverSDESampler: `process(..., eta)` with eta in [0, 1] scales the noise each step adds)."""
+        "dpmpp_2m_sde" (its stochastic form, DPMSolverSDESampler: `process(..., eta)` with eta in [0, 1] scales the noise each step adds).
+        loras: kohya-ss LoRA / LoCon adapters merged into the weights at start-up, [(path or dict, unet_scale[, te_scale]), ...]
+        (`set_loras`); te_scale needs the "clip" / "openclip" text encoder."""
         self.apply_canny = apply_canny or _default_canny()
-        return self._init_model(weights, config, text_encoder, vae_encoder, sampler=sampler)
+        return self._init_model(weights, config, text_encoder, vae_encoder, sampler=sampler, loras=loras)
 
-    def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim", extra_control=()):
+    def set_loras(self, loras=()):
+        """Swap the adapters between `process` calls: back to the base weights, every adapter of `loras` merged on the device
+        ([(path or dict, unet_scale[, te_scale]), ...], stacked in order), one commit.  set_loras([]) is the base model, bit for bit.
+        Returns the keys no adapter of the list could place (`lora.apply_lora`)."""
+        from . import lora as L
+        L.clear_loras(self.model)
+        unsupported = []
+        for entry in loras:
+            src, unet_scale, te_scale = entry[0], (entry[1] if len(entry) > 1 else 1.0), (entry[2] if len(entry) > 2 else None)
+            unsupported += L.apply_lora(self.model, src, unet_scale=unet_scale, te_scale=te_scale, commit=False)
+        for target in (self.model.rt, L._clip_runtime(self.model)):
+            if target is not None and target.lora_touched():
+                target.lora_commit()
+        return unsupported
+
+    def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim", extra_control=(), loras=()):
         """text encoder, ControlLDM and sampler of `initialize` (shared with hed2image).  extra_control: the weights of each extra
         control network (multi2image): a checkpoint path, a state dict with `control_model.*` names or "synthetic:<seed>"."""
         if sampler not in ("ddim", "dpmpp_2m", "dpmpp_2m_sde"):
@@ -100,6 +118,8 @@ class hackathon():
             self.ddim_sampler = DPMSolverSDESampler(self.model)
         else:
             self.ddim_sampler = DDIMSampler(self.model)
+        if loras:
+            self.set_loras(loras)
         return self
 
     def _load_with_extra(self, weights, extra_control):

@@ -146,6 +146,18 @@ class ControlLDM:
                                                   strict=False)
         return self
 
+    def load_lora(self, lora, unet_scale=1.0, te_scale=None, strict=False, commit=True):
+        """Merge a kohya-ss LoRA / LoCon adapter (a path or a dict) into the weights on the device (`stablediffusioneo_amd.lora.apply_lora`);
+        returns the keys it did not understand."""
+        from ..lora import apply_lora
+        return apply_lora(self, lora, unet_scale=unet_scale, te_scale=te_scale, strict=strict, commit=commit)
+
+    def clear_loras(self):
+        """Back to the base weights, bit for bit (`stablediffusioneo_amd.lora.clear_loras`)."""
+        from ..lora import clear_loras
+        clear_loras(self)
+        return self
+
     def low_vram_shift(self, is_diffusing):
         """`cldm/cldm.py:425-435` moves sub-models between host and device to fit small GPUs; with 288 GB of
         HBM everything stays resident."""

@@ -213,6 +213,40 @@ int sdeo_clip_encode(sdeo_clip_handle h, const int32_t* tokens, int batch, float
   return f16_to_f32(out, h->out16, (int64_t)rows * h->cfg.width, s);
 }
 
-size_t sdeo_clip_device_bytes(sdeo_clip_handle h) { return h ? h->ws.slab_bytes + h->act_bytes + h->splitk_bytes : 0; }
+size_t sdeo_clip_device_bytes(sdeo_clip_handle h) { return h ? h->ws.slab_bytes + h->act_bytes + h->splitk_bytes + h->ws.lora_backup_bytes : 0; }
+
+// ---- LoRA adapters.  The text tower runs on the raw tensors and caches nothing between encodes, so commit has
+// nothing to rebuild or invalidate: it only lets the staging buffer go.
+static std::string clip_key(const char* name) {
+  std::string key(name ? name : "");
+  const size_t pos = key.find("text_model.");
+  return pos == std::string::npos ? key : key.substr(pos + 11);
+}
+
+int sdeo_clip_lora_apply(sdeo_clip_handle h, const char* name, const float* down, const float* up, int rank, float scale, void* stream) {
+  SDEO_CHECK(h, "sdeo_clip_lora_apply: null handle");
+  return h->ws.lora_apply("sdeo_clip_lora_apply", name, clip_key(name), down, up, rank, scale,
+                          h->finalized ? nullptr : "weights not finalized (call sdeo_clip_finalize_weights)", reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdeo_clip_lora_commit(sdeo_clip_handle h) {
+  SDEO_CHECK(h, "sdeo_clip_lora_commit: null handle");
+  SDEO_CHECK(h->finalized, "sdeo_clip_lora_commit: weights not finalized (call sdeo_clip_finalize_weights)");
+  h->ws.lora_release_stage();
+  return 0;
+}
+
+int sdeo_clip_lora_clear(sdeo_clip_handle h) {
+  SDEO_CHECK(h, "sdeo_clip_lora_clear: null handle");
+  SDEO_CHECK(h->finalized, "sdeo_clip_lora_clear: weights not finalized (call sdeo_clip_finalize_weights)");
+  return h->ws.lora_restore();
+}
+
+int sdeo_clip_lora_touched(sdeo_clip_handle h) { return h ? h->ws.lora_touched() : 0; }
+
+int sdeo_clip_read_weight(sdeo_clip_handle h, const char* name, float* out) {
+  SDEO_CHECK(h, "sdeo_clip_read_weight: null handle");
+  return h->ws.read("sdeo_clip_read_weight", name, clip_key(name), out);
+}
 
 }  // extern "C"

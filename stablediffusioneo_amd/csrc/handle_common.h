@@ -79,6 +79,8 @@ struct WeightStore {
     if (slab) (void)hipFree(slab);
     if (stage) (void)hipFree(stage);
     slab = nullptr; stage = nullptr;
+    lora_free_backups();
+    lora_release_stage();
   }
 
   // dims[k] = pad for k in [ndim, ndims); null outputs are skipped (each entry point checks the ones it requires)
@@ -131,6 +133,101 @@ struct WeightStore {
     SDEO_CHECK(nmiss == 0, "%s: %d tensors missing (%s%s)", who, nmiss, missing.c_str(), nmiss > 5 ? ", ..." : "");
     if (stage) { (void)hipFree(stage); stage = nullptr; }
     return 0;
+  }
+
+  // ---- LoRA adapters (include/sdeo.h: sdeo_lora_* / sdeo_clip_lora_*).  An adapter is merged IN PLACE into the
+  // raw tensor of the slab (lora_merge_f16), so everything that reads weights by address -- programs, captured graphs -- stays valid.
+  // The first apply on a tensor saves its raw bytes (copy-on-first-write); restore copies every backup back and frees it.  The owner
+  // re-derives what it derives from the raw tensors (folds, composed products) and counts lora_backup_bytes in its device bytes.
+  struct LoraBackup { int entry; void* data; size_t bytes; };
+  std::vector<LoraBackup> lora_backups;
+  size_t lora_backup_bytes = 0;
+  float* lora_stage = nullptr;      // down | up of the apply under way (grows, freed by lora_release_stage)
+  size_t lora_stage_bytes = 0;
+
+  static size_t raw_bytes(const WEntry& w) {      // of rows 0 .. dims[0] of a matrix or conv weight
+    return (size_t)w.dims[0] * (w.kind == W_CONV ? (size_t)w.dims[2] * w.dims[3] * w.ipad : (size_t)w.dims[1]) * sizeof(f16);
+  }
+  int lora_touched() const { return (int)lora_backups.size(); }
+  void lora_release_stage() {
+    if (lora_stage) (void)hipFree(lora_stage);
+    lora_stage = nullptr; lora_stage_bytes = 0;
+  }
+  void lora_free_backups() {
+    for (auto& b : lora_backups) (void)hipFree(b.data);
+    lora_backups.clear();
+    lora_backup_bytes = 0;
+  }
+
+  // Every refusal happens before the first device call and leaves the store untouched.  not_ready: why the handle cannot take an
+  // adapter now (null: it can).  down [rank][in * kh * kw] / up [out][rank] fp32, host or device pointers (hipMemcpyDefault, as load).
+  // Synchronises `stream` (the staging buffer is reused by the next apply).
+  int lora_apply(const char* who, const char* name, const std::string& key, const float* down, const float* up, int rank, float scale,
+                 const char* not_ready, hipStream_t stream) {
+    SDEO_CHECK(name && down && up, "%s: null argument", who);
+    auto it = index.find(key);
+    SDEO_CHECK(it != index.end(), "%s: unknown tensor '%s'", who, name);
+    WEntry& w = entries[it->second];
+    SDEO_CHECK(w.kind == W_LINEAR || w.kind == W_CONV || w.kind == W_GEGLU_W, "%s: %s is a vector (bias / norm), an adapter applies to a matrix or a conv weight", who, name);
+    SDEO_CHECK(rank >= 1 && rank <= 1024, "%s: rank %d out of range (1..1024)", who, rank);
+    SDEO_CHECK(scale == scale && scale - scale == 0.f, "%s: scale is not finite", who);
+    SDEO_CHECK(!not_ready, "%s: %s", who, not_ready);
+    const int O = (int)w.dims[0], I = (int)w.dims[1], k = w.kind == W_CONV ? (int)w.dims[2] : 1;
+    SDEO_CHECK(w.kind != W_CONV || w.dims[2] == w.dims[3], "%s: %s has a %lld x %lld filter (square filters only)", who, name, (long long)w.dims[2], (long long)w.dims[3]);
+    const size_t nd = (size_t)rank * I * k * k, nu = (size_t)O * rank, need = (nd + nu) * sizeof(float);
+    if (need > lora_stage_bytes) {
+      lora_release_stage();
+      SDEO_HIP(hipMalloc((void**)&lora_stage, need));
+      lora_stage_bytes = need;
+    }
+    SDEO_HIP(hipMemcpy(lora_stage, down, nd * sizeof(float), hipMemcpyDefault));
+    SDEO_HIP(hipMemcpy(lora_stage + nd, up, nu * sizeof(float), hipMemcpyDefault));
+    bool saved = false;
+    for (auto& b : lora_backups) saved = saved || b.entry == it->second;
+    if (!saved) {
+      LoraBackup b{it->second, nullptr, raw_bytes(w)};
+      if (hipMalloc(&b.data, b.bytes) != hipSuccess) return fail("%s: cannot allocate %zu bytes to save %s", who, b.bytes, name);
+      if (hipMemcpyAsync(b.data, slab + w.off, b.bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) {
+        (void)hipFree(b.data);
+        return fail("%s: cannot save %s", who, name);
+      }
+      lora_backups.push_back(b);
+      lora_backup_bytes += b.bytes;
+    }
+    if (int rc = lora_merge_f16((f16*)(slab + w.off), w.kind, O, I, k, w.ipad, lora_stage, lora_stage + nd, rank, scale, stream)) return rc;
+    SDEO_HIP(hipStreamSynchronize(stream));
+    return 0;
+  }
+
+  // copy every backup back and free it: the raw tensors are bit for bit what load left
+  int lora_restore() {
+    for (auto& b : lora_backups) SDEO_HIP(hipMemcpy(slab + entries[b.entry].off, b.data, b.bytes, hipMemcpyDeviceToDevice));
+    SDEO_HIP(hipDeviceSynchronize());
+    lora_free_backups();
+    lora_release_stage();
+    return 0;
+  }
+
+  // the inverse of load: the current RAW tensor as fp32 in PyTorch layout (GEGLU rows de-interleaved, KRSC -> OIHW without the pad);
+  // out is a host or a device pointer
+  int read(const char* who, const char* name, const std::string& key, float* out) {
+    SDEO_CHECK(name && out, "%s: null argument", who);
+    auto it = index.find(key);
+    SDEO_CHECK(it != index.end(), "%s: unknown tensor '%s'", who, name);
+    const WEntry& w = entries[it->second];
+    SDEO_CHECK(w.loaded, "%s: %s is not loaded", who, name);
+    SDEO_CHECK(w.kind != W_GEGLU_B, "%s: %s is the interleaved GEGLU bias, which this call does not read back", who, name);
+    const size_t n = (size_t)(w.dims[0] * w.dims[1] * w.dims[2] * w.dims[3]);
+    if (w.kind == W_VEC) {
+      SDEO_HIP(hipMemcpy(out, slab + w.off, n * sizeof(float), hipMemcpyDefault));
+      return 0;
+    }
+    float* tmp = nullptr;
+    SDEO_HIP(hipMalloc((void**)&tmp, n * sizeof(float)));
+    int rc = lora_read_f32(tmp, (const f16*)(slab + w.off), w.kind, (int)w.dims[0], (int)w.dims[1], w.kind == W_CONV ? (int)w.dims[2] : 1, w.ipad, 0);
+    if (!rc && hipMemcpy(out, tmp, n * sizeof(float), hipMemcpyDefault) != hipSuccess) rc = fail("%s: cannot copy %s out", who, name);
+    (void)hipFree(tmp);
+    return rc;
   }
 };
 

@@ -207,6 +207,13 @@ int f16_to_f32(float* y, const f16* x, int64_t n, hipStream_t stream);
 // GEGLU projection [2H][cols] fp32 -> fp16 with value / gate rows interleaved in blocks of 16 (see conv_gemm act = 3); bias variant
 int geglu_interleave_f32_to_f16(f16* y, const float* x, int H, int cols, hipStream_t stream);
 int geglu_interleave_f32(float* y, const float* x, int H, hipStream_t stream);
+// LoRA merge into a stored tensor (csrc/lora.hip): w[o][j] <- fp16(fp32(w[o][j]) + scale * sum_r up[o][r] down[r][j]) with (o, j)
+// where WeightStore::load put it.  kind: the tensor's WKind (W_LINEAR, W_CONV or W_GEGLU_W); out / in / k / ipad its logical shape
+// ([out][in][k][k], k = 1 for a matrix) and stored input channels; down [rank][in * k * k], up [out][rank]: fp32 DEVICE pointers.
+int lora_merge_f16(f16* w, int kind, int out, int in, int k, int ipad, const float* down, const float* up, int rank, float scale,
+                   hipStream_t stream);
+// the inverse of WeightStore::load for the same kinds: out_f32 [out][in][k][k] = fp32 of the stored values, pad channels dropped
+int lora_read_f32(float* out_f32, const f16* w, int kind, int out, int in, int k, int ipad, hipStream_t stream);
 // LayerNorm folded into a Linear (KP::ln_stats): w_out = fp16(w * gamma), s = row sums of w_out, b_out = bias + w beta
 int fold_layernorm(f16* w_out, float* s_out, float* b_out, const f16* w, const float* gamma, const float* beta,
                    const float* bias, int rows, int C, hipStream_t stream);

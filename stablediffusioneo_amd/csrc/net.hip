@@ -148,6 +148,12 @@ struct sdeo_handle_s {
   Program xprog[kMaxControlNets - 1][CP_COUNT];
   float extra_scales[kMaxControlNets - 1][kMaxControls];
   bool extra_hint_set[kMaxControlNets - 1] = {false};
+  // sdeo_lora_commit changed the weights under the caches: net j's hint features, the context K / V of the UNet (bit 0) and of the
+  // control networks (bit 1), the timestep table.  Each stays stale until the call that fills it runs again; a call that asks for a
+  // stale cache is refused.  A handle that never commits an adapter never sets them.
+  bool hint_stale[kMaxControlNets] = {false};
+  int ctx_stale = 0;
+  bool tab_stale = false;
   // time embedding (`openaimodel.py:777-781` + every ResBlock's emb_layers): fp32 [N][emb_total] per net, written by P_TEMB + net from
   // in_t -- or, for a sampler that announced its schedule (sdeo_set_timestep_table), one row of a table computed once per schedule.
   // The ResBlock convs read their pointer / row stride at LAUNCH time (emb_cur / emb_ld_cur), like the control scales.
@@ -1337,7 +1343,7 @@ static void free_configured(Engine* e) {
     for (float& v : e->extra_scales[j]) v = 1.0f;
   }
   e->tab_count = e->fp8.mx_launches = 0;
-  e->device_bytes = e->ws.slab_bytes + e->fp8.q8_bytes + e->fp8.mx_bytes;      // what stays: the weights and their fp8 packs
+  e->device_bytes = e->ws.slab_bytes + e->fp8.q8_bytes + e->fp8.mx_bytes + e->ws.lora_backup_bytes;      // what stays: the weights, their fp8 packs, the tensors saved under adapters
 }
 
 // control scales of the next forward (null: all 1) and what P_UNET_DEC_FUSED applies of them: with only_mid_control
@@ -1465,12 +1471,22 @@ int sdeo_load_weight(sdeo_handle h, const char* name, const float* host_data, co
   return h->ws.load("sdeo_load_weight", name, name, host_data, dims, ndim, strict);
 }
 
+static int derive_weights(sdeo_handle h);
+
 int sdeo_finalize_weights(sdeo_handle h) {
   SDEO_CHECK(h, "sdeo_finalize_weights: null handle");
   SDEO_CHECK(!(h->extra && h->fp8.act_bits == 8),
              "sdeo_finalize_weights: block-scaled fp8 activations (sdeo_set_activation_precision 8) are not supported together with extra "
              "control networks (%d enabled)", h->extra);
   if (int rc = h->ws.require_all("sdeo_finalize_weights")) return rc;
+  if (int rc = derive_weights(h)) return rc;
+  h->finalized = true;
+  return 0;
+}
+
+// Everything a handle derives from its raw tensors, on the null stream, synchronised: sdeo_finalize_weights runs it once, sdeo_lora_commit
+// and sdeo_lora_clear again after the raw tensors changed.
+static int derive_weights(sdeo_handle h) {
   // LayerNorm-folded copies of the Linear layers that consume a LayerNorm (rebuilt on every finalize, from the raw tensors)
   for (const FoldJob& f : h->folds) {
     auto vec = [&](const std::string& n) { return n.empty() ? nullptr : h->ws.ptr<float>(n); };
@@ -1529,7 +1545,6 @@ int sdeo_finalize_weights(sdeo_handle h) {
         return rc;
   }
   SDEO_HIP(hipDeviceSynchronize());
-  h->finalized = true;
   return 0;
 }
 
@@ -1634,13 +1649,28 @@ static int stage_inputs(sdeo_handle h, const float* x, const float* hint, const 
   if (hint && hint_is_new) {
     if (int rc = copy_in(h->in_hint[0], hint, (size_t)h->N * c.hint_channels * px * 64 * 4, s)) return rc;
     if (int rc = run(h, h->prog[P_HINT], s)) return rc;
+    h->hint_stale[0] = false;
   }
   if (ctx) {
     if (int rc = copy_in(h->in_ctx, ctx, (size_t)h->N * c.context_len * c.context_dim * 4, s)) return rc;
     if (ctx_for_net & 1) if (int rc = run(h, h->prog[P_CTX_UNET], s)) return rc;
     if (ctx_for_net & 2)
       for (int j = 0; j <= h->extra; ++j) if (int rc = run(h, cn_prog(h, j, CP_CTX), s)) return rc;
+    h->ctx_stale &= ~ctx_for_net;
   }
+  return 0;
+}
+
+// A call that asks for a cache sdeo_lora_commit made stale is refused (before any device call), each cache with its own message.
+// hint_net: the control network whose SDEO_HINT_CACHED features the call reads (-1: none); ctx_nets: whose context K / V it reads from
+// the cache (bit 0 the UNet, bit 1 the control networks; 0: none)
+static int caches_fresh(sdeo_handle h, const char* who, int hint_net, int ctx_nets) {
+  SDEO_CHECK(hint_net < 0 || !h->hint_stale[hint_net],
+             "%s: SDEO_HINT_CACHED, but sdeo_lora_commit changed the weights the cached hint features of control network %d were computed "
+             "with (pass the hint again)", who, hint_net);
+  SDEO_CHECK(!(h->ctx_stale & ctx_nets),
+             "%s: SDEO_CONTEXT_CACHED, but sdeo_lora_commit changed the weights the cached context K / V were computed with (pass the "
+             "context again)", who);
   return 0;
 }
 
@@ -1654,6 +1684,8 @@ static int select_time(sdeo_handle h, int flags, const int64_t* timesteps, const
   const int row = (flags & 8) ? (flags >> 8) : -1;
   SDEO_CHECK(row >= 0 || timesteps, "%s: timesteps required", who);
   SDEO_CHECK(row < h->tab_count, "%s: timestep row %d, but the table holds %d (sdeo_set_timestep_table)", who, row, h->tab_count);
+  SDEO_CHECK(row < 0 || !h->tab_stale, "%s: SDEO_TIMESTEP_ROW, but sdeo_lora_commit changed the weights the timestep table was computed with "
+             "(call sdeo_set_timestep_table again)", who);
   for (int net = 0; net < 2 + h->extra; ++net) {
     h->emb_cur[net] = row >= 0 ? h->temb_tab[net] + (size_t)row * h->emb_total[net] : h->emb_all[net];
     h->emb_ld_cur[net] = row >= 0 ? 0 : h->emb_total[net];
@@ -1683,6 +1715,9 @@ static int extra_hints_ready(sdeo_handle h, const char* who) {
   for (int j = 1; j <= h->extra; ++j)
     SDEO_CHECK(h->extra_hint_set[j - 1], "%s: control network %d has no hint since the last sdeo_configure (call sdeo_set_control_hint(h, %d, ...))",
                who, j, j);
+  for (int j = 1; j <= h->extra; ++j)
+    SDEO_CHECK(!h->hint_stale[j], "%s: sdeo_lora_commit changed the weights the cached hint features of control network %d were computed with "
+               "(call sdeo_set_control_hint(h, %d, ...) again)", who, j, j);
   return 0;
 }
 
@@ -1730,6 +1765,7 @@ static int set_extra_hint(sdeo_handle h, int j, const float* hint, hipStream_t s
   if (int rc = copy_in(h->in_hint[j], hint, bytes, s)) return rc;
   if (int rc = run(h, cn_prog(h, j, CP_HINT), s)) return rc;
   h->extra_hint_set[j - 1] = true;
+  h->hint_stale[j] = false;
   return 0;
 }
 
@@ -1740,6 +1776,7 @@ static int controlnet_forward_impl(sdeo_handle h, int j, const float* x_noisy, c
   SDEO_CHECK(!hint_new || hint, "%s: hint required", who);
   SDEO_CHECK(!ctx_new || context, "%s: context required", who);
   SDEO_CHECK(j == 0 || hint_new || h->extra_hint_set[j - 1], "%s: control network %d has no hint since the last sdeo_configure", who, j);
+  if (int rc = caches_fresh(h, who, hint_new ? -1 : j, ctx_new ? 0 : 2)) return rc;
   int trow = -1;
   if (int rc = select_time(h, flags, timesteps, who, &trow)) return rc;
   if (int rc = stage_inputs(h, x_noisy, j == 0 ? hint : nullptr, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, hint_new, 2, s)) return rc;
@@ -1798,6 +1835,7 @@ int sdeo_unet_forward(sdeo_handle h, const float* x_noisy, const int64_t* timest
   hipStream_t s = S(stream);
   const int ctx_new = !(flags & 2);
   SDEO_CHECK(!ctx_new || context, "sdeo_unet_forward: context required");
+  if (int rc = caches_fresh(h, "sdeo_unet_forward", -1, ctx_new ? 0 : 1)) return rc;
   int trow = -1;
   if (int rc = select_time(h, flags, timesteps, "sdeo_unet_forward", &trow)) return rc;
   if (int rc = stage_inputs(h, x_noisy, nullptr, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, 0, 1, s)) return rc;
@@ -1828,6 +1866,7 @@ int sdeo_apply_model(sdeo_handle h, const float* x_noisy, const float* hint, con
   SDEO_CHECK(!ctx_new || context, "sdeo_apply_model: context required");
   SDEO_CHECK(no_control || !hint_new || hint, "sdeo_apply_model: hint required");
   if (!no_control) if (int rc = extra_hints_ready(h, "sdeo_apply_model")) return rc;
+  if (int rc = caches_fresh(h, "sdeo_apply_model", no_control || hint_new ? -1 : 0, ctx_new ? 0 : no_control ? 1 : 3)) return rc;
   int trow = -1;
   if (int rc = select_time(h, flags, timesteps, "sdeo_apply_model", &trow)) return rc;
   if (int rc = stage_inputs(h, x_noisy, no_control ? nullptr : hint, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, hint_new,
@@ -1852,6 +1891,7 @@ int sdeo_set_timestep_table(sdeo_handle h, const int64_t* host_timesteps, int co
   SDEO_HIP(hipStreamSynchronize(s));          // `padded` is a stack array; this call is made once per schedule, outside any capture
   if (int rc = run(h, h->prog[P_TEMB_TAB], s)) return rc;
   h->tab_count = count;
+  h->tab_stale = false;
   return 0;
 }
 
@@ -1873,7 +1913,9 @@ static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float*
   SDEO_CHECK(h->N % 2 == 0, "%s: configured for %d images; the CFG pair needs an even count (n = 2 x latents)", who, h->N);
   SDEO_CHECK(table_row >= 0 && table_row < h->tab_count, "%s: timestep row %d, but the table holds %d (sdeo_set_timestep_table)", who,
              table_row, h->tab_count);
+  SDEO_CHECK(!h->tab_stale, "%s: sdeo_lora_commit changed the weights the timestep table was computed with (call sdeo_set_timestep_table again)", who);
   if (int rc = extra_hints_ready(h, who)) return rc;
+  if (int rc = caches_fresh(h, who, 0, 3)) return rc;
   if (blend) {
     SDEO_CHECK(!(flags & SDEO_STEP_LATENT_STAGED), "%s: SDEO_STEP_LATENT_STAGED has no meaning here (the blend changes the latent and always restages it)", who);
     if (int rc = mask_blend_check(who, x, blend->orig, blend->noise, blend->mask, blend->mask_n, blend->mask_c, h->N / 2, h->cfg.in_channels,
@@ -2043,6 +2085,47 @@ int sdeo_vae_encode(sdeo_handle h, const float* images, const uint8_t* images_u8
 }
 
 size_t sdeo_device_bytes(sdeo_handle h) { return h ? h->device_bytes : 0; }
+
+// ---- LoRA adapters: WeightStore does the work, the handle adds what it derives from the raw tensors and its caches
+int sdeo_lora_apply(sdeo_handle h, const char* name, const float* down, const float* up, int rank, float scale, void* stream) {
+  SDEO_CHECK(h, "sdeo_lora_apply: null handle");
+  const char* not_ready = !h->finalized ? "weights not finalized (call sdeo_finalize_weights)"
+                          : h->fp8.weight_bits == 8 ? "this handle holds fp8 weights (sdeo_set_weight_precision 8): its fp16 copies are the dequantised values, "
+                                                      "not the raw ones, and adapters on it are not supported"
+                                                    : nullptr;
+  const size_t before = h->ws.lora_backup_bytes;
+  const int rc = h->ws.lora_apply("sdeo_lora_apply", name, name ? name : "", down, up, rank, scale, not_ready, S(stream));
+  h->device_bytes += h->ws.lora_backup_bytes - before;
+  return rc;
+}
+
+int sdeo_lora_commit(sdeo_handle h) {
+  SDEO_CHECK(h, "sdeo_lora_commit: null handle");
+  SDEO_CHECK(h->finalized, "sdeo_lora_commit: weights not finalized (call sdeo_finalize_weights)");
+  h->ws.lora_release_stage();
+  if (int rc = derive_weights(h)) return rc;
+  for (bool& b : h->hint_stale) b = true;
+  h->ctx_stale = 3;
+  h->tab_stale = true;
+  return 0;
+}
+
+int sdeo_lora_clear(sdeo_handle h) {
+  SDEO_CHECK(h, "sdeo_lora_clear: null handle");
+  SDEO_CHECK(h->finalized, "sdeo_lora_clear: weights not finalized (call sdeo_finalize_weights)");
+  const size_t before = h->ws.lora_backup_bytes;
+  const int rc = h->ws.lora_restore();
+  h->device_bytes -= before - h->ws.lora_backup_bytes;
+  if (rc) return rc;
+  return sdeo_lora_commit(h);
+}
+
+int sdeo_lora_touched(sdeo_handle h) { return h ? h->ws.lora_touched() : 0; }
+
+int sdeo_read_weight(sdeo_handle h, const char* name, float* out) {
+  SDEO_CHECK(h, "sdeo_read_weight: null handle");
+  return h->ws.read("sdeo_read_weight", name, name ? name : "", out);
+}
 
 int sdeo_profile_begin(sdeo_handle h) {
   SDEO_CHECK(h, "sdeo_profile_begin: null handle");

@@ -26,12 +26,12 @@ def _default_hed(weights):
 class hackathon(canny2image.hackathon):
 
     def initialize(self, weights="synthetic:0", hed_weights="synthetic:0", apply_hed=None, text_encoder=None, config="sd15",
-                   sampler="ddim"):
+                   sampler="ddim", loras=()):
         """weights / text_encoder / config / sampler: as canny2image.hackathon.initialize (a soft-edge ControlNet checkpoint has the same keys).
         hed_weights: the HED network's (ControlNetHED.pth path, state dict or "synthetic:<seed>"); apply_hed: any callable
         (HxWx3 uint8) -> HxW uint8 instead of the HIP HEDdetector."""
         self.apply_hed = apply_hed or _default_hed(hed_weights)
-        return self._init_model(weights, config, text_encoder, sampler=sampler)
+        return self._init_model(weights, config, text_encoder, sampler=sampler, loras=loras)
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, detect_resolution, ddim_steps, guess_mode,
                 strength, scale, seed, eta, x_T=None):

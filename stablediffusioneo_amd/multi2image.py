@@ -25,7 +25,7 @@ DEVICE_CONTROLS = ("canny", "hed", "scribble", "fake_scribble")
 class hackathon(canny2image.hackathon):
 
     def initialize(self, weights="synthetic:0", controls=("canny", "hed"), control_weights=(None, "synthetic:1"), hed_weights="synthetic:0",
-                   text_encoder=None, config="sd15", sampler="ddim"):
+                   text_encoder=None, config="sd15", sampler="ddim", loras=()):
         """controls: one entry per control network, "canny", "hed", "scribble", "fake_scribble" (the device hint producers of the
         single-net pipelines) or a callable (HxWx3 uint8) -> HxW uint8.  control_weights: one entry per network; entry 0 must be
         None (net 0 comes with `weights`), the others are a checkpoint path, a state dict or "synthetic:<seed>".
@@ -49,7 +49,7 @@ class hackathon(canny2image.hackathon):
         if "hed" in controls or "fake_scribble" in controls:
             from .hed2image import _default_hed
             self.apply_hed = _default_hed(hed_weights)
-        return self._init_model(weights, config, text_encoder, sampler=sampler, extra_control=control_weights[1:])
+        return self._init_model(weights, config, text_encoder, sampler=sampler, extra_control=control_weights[1:], loras=loras)
 
     def _hint(self, kind, img, low_threshold, high_threshold):
         """(3, H, W) fp32 hint in [0, 1] on the device, from the resized HxWx3 uint8 image"""

@@ -102,6 +102,54 @@ class _HandleRuntime:
     def device_bytes(self) -> int:
         return int(self._sym("device_bytes")(self.handle))
 
+    # ---------------------------------------------------------------- LoRA adapters (include/sdeo.h: sdeo_lora_*, sdeo_clip_lora_*)
+    def _weight_shape(self, name: str):
+        if getattr(self, "_expected", None) is None:
+            self._expected = self.expected_weights()
+        return self._expected.get(name)
+
+    def lora_apply(self, name: str, down: torch.Tensor, up: torch.Tensor, scale: float = 1.0):
+        """Merge scale * up @ down into the stored tensor `name` (a registry name of `expected_weights`), on the device and in place.
+        down: (rank, in[, kh, kw]) as lora_down.weight; up: (out, rank[, 1, 1]) as lora_up.weight; host or device tensors.  Call
+        `lora_commit` after the last apply of a set."""
+        shape = self._weight_shape(name)
+        if shape is not None and len(shape) >= 2:
+            rank = int(down.shape[0]) if down.dim() >= 2 else 0
+            fan = 1
+            for d in shape[1:]:
+                fan *= d
+            ok_down = rank >= 1 and down.numel() == rank * fan and (down.dim() == 2 or tuple(down.shape[1:]) == tuple(shape[1:]))
+            ok_up = up.dim() >= 2 and up.numel() == shape[0] * rank and tuple(up.shape[:2]) == (shape[0], rank)
+            if not (ok_down and ok_up):
+                raise ValueError(f"lora_apply({name}): down {tuple(down.shape)} / up {tuple(up.shape)} do not fit the weight {tuple(shape)}: "
+                                 f"expected down (rank, {', '.join(str(d) for d in shape[1:])}) and up ({shape[0]}, rank)")
+        # (an unknown name or a vector goes through: the library refuses it with its own message)
+        keep = lambda t: t.detach().to(dtype=torch.float32).contiguous() if t.device == self.device else t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+        down, up = keep(down), keep(up)
+        self._call("lora_apply", name.encode(), ptr(down), ptr(up), int(down.shape[0]) if down.dim() else 0, C.c_float(float(scale)), cur_stream(),
+                   detail=f"({name})")
+
+    def lora_commit(self):
+        """Rebuild what the library derives from the raw weights and invalidate everything computed with the earlier ones: bumps
+        `generation`, the key of the samplers' hint / context caches, the timestep table and every captured graph."""
+        self._call("lora_commit")
+        self.generation += 1
+
+    def lora_clear(self):
+        """Restore every tensor an adapter touched (bit for bit), free the saved copies, commit."""
+        self._call("lora_clear")
+        self.generation += 1
+
+    def lora_touched(self) -> int:
+        return int(self._sym("lora_touched")(self.handle))
+
+    def read_weight(self, name: str) -> torch.Tensor:
+        """The stored tensor `name` as fp32 in PyTorch layout (the fp16 values the library holds now), on the host."""
+        shape = self._weight_shape(name)
+        out = torch.empty(shape if shape is not None else (1,), dtype=torch.float32)
+        self._call("read_weight", name.encode(), ptr(out), detail=f"({name})")
+        return out
+
 
 class SdeoRuntime(_HandleRuntime):
     """create -> load_state_dict -> configure(n, h, w) -> controlnet / unet / apply_model / vae_decode."""

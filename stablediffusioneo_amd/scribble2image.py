@@ -19,9 +19,9 @@ from .annotator.util import HWC3, resize_image
 
 class hackathon(canny2image.hackathon):
 
-    def initialize(self, weights="synthetic:0", config="sd15", text_encoder=None, sampler="ddim"):
+    def initialize(self, weights="synthetic:0", config="sd15", text_encoder=None, sampler="ddim", loras=()):
         """weights / config / text_encoder / sampler: as canny2image.hackathon.initialize (a scribble ControlNet checkpoint has the same keys)"""
-        return self._init_model(weights, config, text_encoder, sampler=sampler)
+        return self._init_model(weights, config, text_encoder, sampler=sampler, loras=loras)
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, ddim_steps, guess_mode, strength, scale, seed,
                 eta, x_T=None):
