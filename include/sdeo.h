@@ -271,6 +271,40 @@ int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w);
 #define SDEO_TIMESTEP_ROW(i) (8 | ((i) << 8))
 #define SDEO_MAX_TABLE_STEPS 128
 
+/* State a handle keeps between calls, and who may read it (the cache contract).
+ * Four items outlive a call.  The fast paths read them by address and on the caller's word (a *_CACHED flag, SDEO_TIMESTEP_ROW, a fused
+ * sdeo_*_step, SDEO_STEP_LATENT_STAGED), so the handle keeps a host-side record of what each holds and checks it before the first
+ * device call of every entry point: a read is either right -- bit-identical to the same call given the inputs the cache was filled
+ * from -- or refused, with a message that names the flag (or the step) and the call that fills the cache.  A refused call touches
+ * nothing: not the caller's tensors (x, pred_x0, d, eps, controls), not the caches, not this record.  The checks run on the host when
+ * the call is made, so a captured call is checked at capture and costs nothing at replay.
+ *
+ *   item                      filled by                                   cleared by                          read by
+ *   ------------------------- ------------------------------------------- ----------------------------------- -----------------------------
+ *   hint features, per        net 0: sdeo_apply_model /                   sdeo_configure, sdeo_lora_commit,   SDEO_HINT_CACHED (that net);
+ *   control network           sdeo_controlnet_forward given the hint;     sdeo_lora_clear                     sdeo_apply_model with control
+ *                             net j >= 1: sdeo_set_control_hint,                                              (every extra net); every
+ *                             sdeo_controlnet_forward_net given the hint                                      sdeo_*_step (every net)
+ *   context K / V, per side   a forward given the context: both sides by  sdeo_configure, sdeo_lora_commit,   SDEO_CONTEXT_CACHED (the sides
+ *   (the UNet; the control    sdeo_apply_model with control; the UNet's   sdeo_lora_clear                     the call runs); every
+ *   networks)                 by sdeo_unet_forward and SDEO_NO_CONTROL;                                       sdeo_*_step (both sides)
+ *                             the control networks' by
+ *                             sdeo_controlnet_forward[_net]
+ *   timestep table            sdeo_set_timestep_table                     sdeo_configure, sdeo_lora_commit,   SDEO_TIMESTEP_ROW(i); every
+ *                                                                         sdeo_lora_clear                     sdeo_*_step (table_row)
+ *   staged fp16 latent        every sdeo_*_step that succeeds (for the    sdeo_configure, sdeo_apply_model,   SDEO_STEP_LATENT_STAGED
+ *                             x it updated)                               sdeo_unet_forward,
+ *                                                                         sdeo_controlnet_forward[_net]
+ *
+ *   - Every staged context has an epoch.  A call that reads the K / V of both sides from the cache (sdeo_apply_model with control and
+ *     SDEO_CONTEXT_CACHED, every sdeo_*_step) needs both computed from the same staged context: after sdeo_controlnet_forward,
+ *     sdeo_unet_forward or an SDEO_NO_CONTROL call given another context the two sides hold two prompts, and such a call is refused until
+ *     one sdeo_apply_model with control is given the context again.  A call that reads one side reads what that side was last given.
+ *   - SDEO_STEP_LATENT_STAGED is accepted only for the very x pointer the previous fused step updated, with no call from the "cleared
+ *     by" column in between.  The masked steps refuse the flag outright.
+ *   - sdeo_set_control_hint, sdeo_set_control_scales, sdeo_set_timestep_table, sdeo_vae_decode and sdeo_vae_encode leave every item
+ *     other than the one they fill as it is (the arena keeps the persistent tensors apart from the VAE programs). */
+
 /* ControlNet.forward (cldm/cldm.py:284-305).  NCHW fp32 at the boundary:
  *   x_noisy [n][4][h][w], hint [n][3][8h][8w] in [0,1], timesteps int64 [n], context [n][77][768],
  *   controls[13]: NCHW fp32 outputs in the reference's binding order (export_onnx_all.py:242-256);
@@ -303,7 +337,9 @@ int sdeo_set_timestep_table(sdeo_handle h, const int64_t* host_timesteps, int co
  * x <- sqrt(a_prev) pred_x0 + sqrt(1 - a_prev) e.  x [n/2][4][h][w] fp32 is updated IN PLACE, pred_x0 (may be NULL) receives the
  * prediction.  Arithmetic and rounding are those of sdeo_apply_model + sdeo_cfg_ddim_step (bit-identical results); what is saved
  * is the NCHW fp32 round trip of eps and the latent between the two.  flags: SDEO_STEP_LATENT_STAGED = x is exactly what the
- * previous sdeo_ddim_step on this handle left (its fp16 copy is already staged; skips one conversion launch).
+ * previous fused step on this handle left (its fp16 copy is already staged; skips one conversion launch).  The handle checks both this
+ * flag and the caches (the cache contract above): a step on a handle whose hint, context or table is missing, or a staged step on
+ * another x, is refused.
  * The two halves of [x; x] differ only in their text context, so the UNet computes input_blocks.1 up to its cross-attention once, on
  * the first half (same kernels, same plans: the results do not change).  SDEO_STEP_HINT_SHARED = the cached hint of image i + n/2 is
  * that of image i (the sampler passed the same control image for the conditional and the unconditional half): the ControlNet does

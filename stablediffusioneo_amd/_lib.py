@@ -96,6 +96,14 @@ def prototypes(header: str):
     return parse_header(open(header).read())[0]
 
 
+def header_constant(name: str, header: str = HEADER) -> int:
+    """The integer `#define name <digits>` of a header: SDEO_ABI_VERSION, SDEO_MAX_TABLE_STEPS, ... are read, never restated"""
+    m = re.search(rf"^\s*#\s*define\s+{re.escape(name)}\s+(\d+)\s*$", open(header).read(), re.M)
+    if not m:
+        raise SdeoError(f"{header} does not define the integer constant {name}")
+    return int(m.group(1))
+
+
 def declared_symbols(header: str = HEADER):
     """Names of every function include/sdeo.h declares (used by the CPU export test)."""
     return sorted(prototypes(header))
@@ -123,7 +131,7 @@ def load(path: str = LIB_PATH):
                 missing.append(name)
     if missing:
         raise SdeoError(f"{path} does not export {missing}")
-    want = int(re.search(r"#define\s+SDEO_ABI_VERSION\s+(\d+)", open(HEADER).read()).group(1))
+    want = header_constant("SDEO_ABI_VERSION")
     if lib.sdeo_version() != want:
         raise SdeoError(f"{path} reports ABI version {lib.sdeo_version()}, include/sdeo.h declares {want}: rebuild the library "
                         f"(operand semantics changed between versions)")

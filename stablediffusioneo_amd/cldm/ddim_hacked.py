@@ -18,7 +18,7 @@ import torch
 import os
 
 from .. import ops
-from ..runtime import CONTEXT_CACHED, HINT_CACHED
+from ..runtime import CONTEXT_CACHED, HINT_CACHED, MAX_TABLE_STEPS
 
 # replay the per-step apply_model from a hipGraph once hint / context are cached (SDEO_GRAPH=0: eager launches)
 USE_GRAPH = os.environ.get("SDEO_GRAPH", "1") != "0"
@@ -273,8 +273,9 @@ class DDIMSampler(object):
         """Steps 2..S as one graph: only the plain canny2image loop qualifies -- fused CFG pair, eps- or v-parameterisation, no
         callbacks / correctors, a mask only when `mask_graph_ok` (the callers check those).  With eta > 0 the steps read their noise
         from the sampler's rows (`step_noise_rows`), which hold plain torch.randn draws: a temperature other than 1 or a noise dropout
-        keep the per-step loop."""
-        if not (USE_GRAPH and USE_LOOP_GRAPH and img.is_cuda and total_steps >= 2 and self._fusable(c, uc, scale)):
+        keep the per-step loop.  So does a schedule longer than the library's timestep table (MAX_TABLE_STEPS rows): the captured steps
+        read their time embedding from it, the per-step loop needs none."""
+        if not (USE_GRAPH and USE_LOOP_GRAPH and img.is_cuda and 2 <= total_steps <= MAX_TABLE_STEPS and self._fusable(c, uc, scale)):
             return False
         if self.model.parameterization not in ("eps", "v"):
             return False

@@ -228,8 +228,10 @@ class DPMSolverSampler(object):
 
     # ------------------------------------------------------------------------------------------ whole-loop graph
     def _loop_graph_ok(self, img, c, uc, scale, total_steps):
-        """the gating of `DDIMSampler._loop_graph_ok` (the stochastic subclass's temperature / noise_dropout are ruled out by `sample`)"""
-        return bool(dh.USE_GRAPH and dh.USE_LOOP_GRAPH and img.is_cuda and total_steps >= 2 and self._pair._fusable(c, uc, scale)
+        """the gating of `DDIMSampler._loop_graph_ok`, the bound of the library's timestep table included (the stochastic subclass's
+        temperature / noise_dropout are ruled out by `sample`)"""
+        return bool(dh.USE_GRAPH and dh.USE_LOOP_GRAPH and img.is_cuda and 2 <= total_steps <= dh.MAX_TABLE_STEPS
+                    and self._pair._fusable(c, uc, scale)
                     and self.model.parameterization in ("eps", "v"))
 
     def _loop_graphed(self, img, c, uc, scale, total_steps, log_every_t, intermediates, mask=None, x0=None):

@@ -143,11 +143,20 @@ struct sdeo_handle_s {
   float eff_scales[kMaxControlNets][kMaxControls];
   int only_mid = 0;
   // extra control networks (sdeo_enable_extra_controlnets): how many, their programs, the scales sdeo_set_control_scales left
-  // (extra_scales[j - 1], kept until changed) and whether sdeo_set_control_hint filled net j's hint cache since the last configure
+  // (extra_scales[j - 1], kept until changed)
   int extra = 0;
   Program xprog[kMaxControlNets - 1][CP_COUNT];
   float extra_scales[kMaxControlNets - 1][kMaxControls];
-  bool extra_hint_set[kMaxControlNets - 1] = {false};
+  // The cache contract (include/sdeo.h, "State a handle keeps between calls"): host-side record of what the caches hold, checked before
+  // the first device call of every entry point that reads one on the caller's word.  A captured call is checked at capture.
+  //   hint_set[j]:     net j's hint block ran since the last sdeo_configure (net 0: a forward given the hint; j >= 1: sdeo_set_control_hint)
+  //   ctx_set:         whose context K / V were computed since the last sdeo_configure (bit 0 the UNet, bit 1 the control networks)
+  //   ctx_epoch:       advances every time a new context is staged; ctx_epoch_of[side] is the epoch side's K / V were computed from
+  //   x0_staged_for:   the caller's latent whose updated fp16 copy the last fused step left in x0; null once anything else wrote x0
+  bool hint_set[kMaxControlNets] = {false};
+  int ctx_set = 0;
+  unsigned long long ctx_epoch = 0, ctx_epoch_of[2] = {0, 0};
+  const float* x0_staged_for = nullptr;
   // sdeo_lora_commit changed the weights under the caches: net j's hint features, the context K / V of the UNet (bit 0) and of the
   // control networks (bit 1), the timestep table.  Each stays stale until the call that fills it runs again; a call that asks for a
   // stale cache is refused.  A handle that never commits an adapter never sets them.
@@ -1339,9 +1348,11 @@ static void free_configured(Engine* e) {
   for (Program& p : e->prog) p.clear();
   for (auto& px : e->xprog) for (Program& p : px) p.clear();
   for (int j = 0; j < kMaxControlNets - 1; ++j) {        // the hint caches are gone with the arenas, the scales return to 1
-    e->extra_hint_set[j] = false;
     for (float& v : e->extra_scales[j]) v = 1.0f;
   }
+  for (bool& b : e->hint_set) b = false;                 // ... and so are the context K / V and the staged latent
+  e->ctx_set = 0;
+  e->x0_staged_for = nullptr;
   e->tab_count = e->fp8.mx_launches = 0;
   e->device_bytes = e->ws.slab_bytes + e->fp8.q8_bytes + e->fp8.mx_bytes + e->ws.lora_backup_bytes;      // what stays: the weights, their fp8 packs, the tensors saved under adapters
 }
@@ -1650,18 +1661,31 @@ static int stage_inputs(sdeo_handle h, const float* x, const float* hint, const 
     if (int rc = copy_in(h->in_hint[0], hint, (size_t)h->N * c.hint_channels * px * 64 * 4, s)) return rc;
     if (int rc = run(h, h->prog[P_HINT], s)) return rc;
     h->hint_stale[0] = false;
+    h->hint_set[0] = true;
   }
   if (ctx) {
+    h->ctx_set &= ~ctx_for_net;                   // (a failed launch leaves the side unset, not half written and trusted)
+    ++h->ctx_epoch;
     if (int rc = copy_in(h->in_ctx, ctx, (size_t)h->N * c.context_len * c.context_dim * 4, s)) return rc;
     if (ctx_for_net & 1) if (int rc = run(h, h->prog[P_CTX_UNET], s)) return rc;
     if (ctx_for_net & 2)
       for (int j = 0; j <= h->extra; ++j) if (int rc = run(h, cn_prog(h, j, CP_CTX), s)) return rc;
     h->ctx_stale &= ~ctx_for_net;
+    h->ctx_set |= ctx_for_net;
+    for (int side = 0; side < 2; ++side) if (ctx_for_net >> side & 1) h->ctx_epoch_of[side] = h->ctx_epoch;
   }
   return 0;
 }
 
-// A call that asks for a cache sdeo_lora_commit made stale is refused (before any device call), each cache with its own message.
+// P_X0: the fp16 copy of in_x.  Whatever a fused step staged in x0 is gone.
+static int run_x0(sdeo_handle h, hipStream_t s) {
+  h->x0_staged_for = nullptr;
+  return run(h, h->prog[P_X0], s);
+}
+
+// A call that asks for a cache sdeo_lora_commit made stale, or one nothing filled since the last sdeo_configure, is refused (before any
+// device call), each cache with its own message; so is a call that reads the context K / V of both sides when the two were computed
+// from different contexts.
 // hint_net: the control network whose SDEO_HINT_CACHED features the call reads (-1: none); ctx_nets: whose context K / V it reads from
 // the cache (bit 0 the UNet, bit 1 the control networks; 0: none)
 static int caches_fresh(sdeo_handle h, const char* who, int hint_net, int ctx_nets) {
@@ -1671,6 +1695,19 @@ static int caches_fresh(sdeo_handle h, const char* who, int hint_net, int ctx_ne
   SDEO_CHECK(!(h->ctx_stale & ctx_nets),
              "%s: SDEO_CONTEXT_CACHED, but sdeo_lora_commit changed the weights the cached context K / V were computed with (pass the "
              "context again)", who);
+  SDEO_CHECK(hint_net < 0 || h->hint_set[hint_net],
+             "%s: SDEO_HINT_CACHED, but control network %d has no hint since the last sdeo_configure (%s)", who, hint_net,
+             hint_net == 0 ? "pass the hint to sdeo_apply_model or sdeo_controlnet_forward" : "call sdeo_set_control_hint");
+  SDEO_CHECK(!(ctx_nets & 1 & ~h->ctx_set),
+             "%s: SDEO_CONTEXT_CACHED, but the UNet has no context K / V since the last sdeo_configure (pass the context to "
+             "sdeo_apply_model or sdeo_unet_forward)", who);
+  SDEO_CHECK(!(ctx_nets & 2 & ~h->ctx_set),
+             "%s: SDEO_CONTEXT_CACHED, but the control networks have no context K / V since the last sdeo_configure (pass the context to "
+             "sdeo_apply_model or sdeo_controlnet_forward)", who);
+  SDEO_CHECK(ctx_nets != 3 || h->ctx_epoch_of[0] == h->ctx_epoch_of[1],
+             "%s: SDEO_CONTEXT_CACHED, but the cached context K / V of the UNet and of the control networks were computed from different "
+             "contexts (a call that refreshes one side only ran since: sdeo_unet_forward, sdeo_controlnet_forward or SDEO_NO_CONTROL; pass "
+             "the context to sdeo_apply_model again)", who);
   return 0;
 }
 
@@ -1713,7 +1750,7 @@ static int run_extra_controlnets(sdeo_handle h, bool shared_cn, hipStream_t s) {
 // a forward that runs the control networks needs every extra net's hint cache filled (sdeo_set_control_hint)
 static int extra_hints_ready(sdeo_handle h, const char* who) {
   for (int j = 1; j <= h->extra; ++j)
-    SDEO_CHECK(h->extra_hint_set[j - 1], "%s: control network %d has no hint since the last sdeo_configure (call sdeo_set_control_hint(h, %d, ...))",
+    SDEO_CHECK(h->hint_set[j], "%s: control network %d has no hint since the last sdeo_configure (call sdeo_set_control_hint(h, %d, ...))",
                who, j, j);
   for (int j = 1; j <= h->extra; ++j)
     SDEO_CHECK(!h->hint_stale[j], "%s: sdeo_lora_commit changed the weights the cached hint features of control network %d were computed with "
@@ -1764,7 +1801,7 @@ static int set_extra_hint(sdeo_handle h, int j, const float* hint, hipStream_t s
   const size_t bytes = (size_t)h->N * h->cfg.hint_channels * h->lh * h->lw * 64 * 4;
   if (int rc = copy_in(h->in_hint[j], hint, bytes, s)) return rc;
   if (int rc = run(h, cn_prog(h, j, CP_HINT), s)) return rc;
-  h->extra_hint_set[j - 1] = true;
+  h->hint_set[j] = true;
   h->hint_stale[j] = false;
   return 0;
 }
@@ -1775,13 +1812,13 @@ static int controlnet_forward_impl(sdeo_handle h, int j, const float* x_noisy, c
   const int hint_new = !(flags & 1), ctx_new = !(flags & 2);
   SDEO_CHECK(!hint_new || hint, "%s: hint required", who);
   SDEO_CHECK(!ctx_new || context, "%s: context required", who);
-  SDEO_CHECK(j == 0 || hint_new || h->extra_hint_set[j - 1], "%s: control network %d has no hint since the last sdeo_configure", who, j);
+  SDEO_CHECK(j == 0 || hint_new || h->hint_set[j], "%s: control network %d has no hint since the last sdeo_configure", who, j);
   if (int rc = caches_fresh(h, who, hint_new ? -1 : j, ctx_new ? 0 : 2)) return rc;
   int trow = -1;
   if (int rc = select_time(h, flags, timesteps, who, &trow)) return rc;
   if (int rc = stage_inputs(h, x_noisy, j == 0 ? hint : nullptr, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, hint_new, 2, s)) return rc;
   if (j > 0 && hint_new) if (int rc = set_extra_hint(h, j, hint, s)) return rc;
-  if (int rc = run(h, h->prog[P_X0], s)) return rc;
+  if (int rc = run_x0(h, s)) return rc;
   if (trow < 0) if (int rc = run(h, cn_prog(h, j, CP_TEMB), s)) return rc;
   if (int rc = run(h, cn_prog(h, j, CP_CN), s)) return rc;
   if (int rc = run(h, h->prog[P_CN_EXPORT], s)) return rc;
@@ -1840,7 +1877,7 @@ int sdeo_unet_forward(sdeo_handle h, const float* x_noisy, const int64_t* timest
   if (int rc = select_time(h, flags, timesteps, "sdeo_unet_forward", &trow)) return rc;
   if (int rc = stage_inputs(h, x_noisy, nullptr, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, 0, 1, s)) return rc;
   set_scales(h, host_control_scales, only_mid_control);
-  if (int rc = run(h, h->prog[P_X0], s)) return rc;
+  if (int rc = run_x0(h, s)) return rc;
   if (trow < 0) if (int rc = run(h, h->prog[P_TEMB + 0], s)) return rc;
   if (controls) {
     for (size_t i = 0; i < h->ctrl_elems.size(); ++i) {
@@ -1873,7 +1910,7 @@ int sdeo_apply_model(sdeo_handle h, const float* x_noisy, const float* hint, con
                             no_control ? 1 : 3, s))
     return rc;
   set_scales(h, host_control_scales, only_mid_control);
-  if (int rc = run(h, h->prog[P_X0], s)) return rc;
+  if (int rc = run_x0(h, s)) return rc;
   if (int rc = run_step_programs(h, no_control, trow >= 0, s)) return rc;
   if (int rc = run(h, h->prog[P_EPS_EXPORT], s)) return rc;
   return copy_in(eps, h->out_eps, (size_t)h->N * h->cfg.out_channels * h->lh * h->lw * 4, s);
@@ -1916,6 +1953,12 @@ static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float*
   SDEO_CHECK(!h->tab_stale, "%s: sdeo_lora_commit changed the weights the timestep table was computed with (call sdeo_set_timestep_table again)", who);
   if (int rc = extra_hints_ready(h, who)) return rc;
   if (int rc = caches_fresh(h, who, 0, 3)) return rc;
+  if (!blend && (flags & SDEO_STEP_LATENT_STAGED)) {
+    SDEO_CHECK(h->x0_staged_for, "%s: SDEO_STEP_LATENT_STAGED, but no fused step staged a latent since the last sdeo_configure, or another "
+               "forward (sdeo_apply_model, sdeo_unet_forward, sdeo_controlnet_forward) overwrote it since (drop the flag)", who);
+    SDEO_CHECK(h->x0_staged_for == x, "%s: SDEO_STEP_LATENT_STAGED, but the previous fused step ran on another latent (%p; this one is %p; "
+               "drop the flag)", who, (const void*)h->x0_staged_for, (const void*)x);
+  }
   if (blend) {
     SDEO_CHECK(!(flags & SDEO_STEP_LATENT_STAGED), "%s: SDEO_STEP_LATENT_STAGED has no meaning here (the blend changes the latent and always restages it)", who);
     if (int rc = mask_blend_check(who, x, blend->orig, blend->noise, blend->mask, blend->mask_n, blend->mask_c, h->N / 2, h->cfg.in_channels,
@@ -1925,6 +1968,7 @@ static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float*
   int trow = -1;
   if (int rc = select_time(h, 8 | (table_row << 8), nullptr, who, &trow)) return rc;
   set_scales(h, host_control_scales, only_mid_control);
+  h->x0_staged_for = nullptr;                     // until the update kernel has left the new latent in x0 (step_done)
   if (blend) {
     if (int rc = mask_blend_pair(x, blend->orig, blend->noise, blend->mask, blend->mask_n, blend->mask_c, blend->sqrt_a, blend->sqrt_1ma,
                                  h->x0.p, h->x0.ld, h->N / 2, h->cfg.in_channels, h->lh * h->lw, s))
@@ -1942,15 +1986,22 @@ struct StepNoise {
   float coef;
 };
 
+// the update kernel of a fused step wrote the new latent to x and its fp16 copy to x0: the next step on x may pass SDEO_STEP_LATENT_STAGED
+static int step_done(sdeo_handle h, const float* x, int rc) {
+  if (!rc) h->x0_staged_for = x;
+  return rc;
+}
+
 static int ddim_step_impl(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
                           float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, const StepBlend* blend,
                           const StepNoise* sn, const char* who, hipStream_t s) {
   if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, blend, who, s)) return rc;
   if (sn && sn->noise)
-    return cfg_ddim_pair_noise(x, pred_x0, h->eps16.p, h->eps16.ld, sn->noise, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels,
-                               h->lh * h->lw, cfg_scale, a_t, a_prev, sn->coef, sqrt_one_minus_at, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
-  return cfg_ddim_pair(x, pred_x0, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw, cfg_scale, a_t,
-                       a_prev, sqrt_one_minus_at, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
+    return step_done(h, x, cfg_ddim_pair_noise(x, pred_x0, h->eps16.p, h->eps16.ld, sn->noise, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels,
+                                               h->lh * h->lw, cfg_scale, a_t, a_prev, sn->coef, sqrt_one_minus_at,
+                                               (flags & SDEO_STEP_V_PREDICTION) != 0, s));
+  return step_done(h, x, cfg_ddim_pair(x, pred_x0, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw,
+                                       cfg_scale, a_t, a_prev, sqrt_one_minus_at, (flags & SDEO_STEP_V_PREDICTION) != 0, s));
 }
 
 static int dpmpp_2m_step_impl(sdeo_handle h, float* x, float* d, int table_row, float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x,
@@ -1959,10 +2010,11 @@ static int dpmpp_2m_step_impl(sdeo_handle h, float* x, float* d, int table_row, 
   SDEO_CHECK(d || k_p == 0.f, "%s: k_p=%g needs the previous data prediction, but d is null", who, k_p);
   if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, blend, who, s)) return rc;
   if (sn && sn->coef != 0.f)                     // k_n == 0: the existing kernel, whatever the noise pointer
-    return cfg_lms_pair_noise(x, d, h->eps16.p, h->eps16.ld, sn->noise, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw,
-                              cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, sn->coef, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
-  return cfg_lms_pair(x, d, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw, cfg_scale, a_t,
-                      sqrt_one_minus_at, k_x, k_d, k_p, (flags & SDEO_STEP_V_PREDICTION) != 0, s);
+    return step_done(h, x, cfg_lms_pair_noise(x, d, h->eps16.p, h->eps16.ld, sn->noise, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels,
+                                              h->lh * h->lw, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, sn->coef,
+                                              (flags & SDEO_STEP_V_PREDICTION) != 0, s));
+  return step_done(h, x, cfg_lms_pair(x, d, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw, cfg_scale,
+                                      a_t, sqrt_one_minus_at, k_x, k_d, k_p, (flags & SDEO_STEP_V_PREDICTION) != 0, s));
 }
 
 int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,

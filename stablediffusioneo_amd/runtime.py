@@ -21,6 +21,10 @@ def TIMESTEP_ROW(i: int) -> int:
     return 8 | (int(i) << 8)
 
 
+# rows of the library's timestep table (SDEO_MAX_TABLE_STEPS of include/sdeo.h): `set_timestep_table` refuses a longer schedule, so the
+# samplers keep the per-step loop, which needs no table, for one
+MAX_TABLE_STEPS = _lib.header_constant("SDEO_MAX_TABLE_STEPS")
+
 
 def make_config(ucfg: S.UNetConfig = S.UNET_SD15, vcfg: S.VAEConfig = S.VAE_SD15) -> SdeoConfig:
     c = SdeoConfig()
