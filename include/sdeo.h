@@ -302,6 +302,10 @@ int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w);
  *     one sdeo_apply_model with control is given the context again.  A call that reads one side reads what that side was last given.
  *   - SDEO_STEP_LATENT_STAGED is accepted only for the very x pointer the previous fused step updated, with no call from the "cleared
  *     by" column in between.  The masked steps refuse the flag outright.
+ *   - All six fused steps (sdeo_ddim_step, sdeo_dpmpp_2m_step, their _masked forms, sdeo_ddim_step_eta, sdeo_dpmpp_2m_sde_step) are one
+ *     step core given six descriptions, and refuse up front what their update kernel would refuse after the networks ran: an invalid
+ *     schedule (a_t <= 0, 1 - a_prev < 0), a non-finite k_x / k_d / k_p, d null with k_p != 0, next to the operand, flag, cache and table
+ *     checks.  A step refused for a coefficient has launched nothing and leaves the staged-latent record as it was.
  *   - sdeo_set_control_hint, sdeo_set_control_scales, sdeo_set_timestep_table, sdeo_vae_decode and sdeo_vae_encode leave every item
  *     other than the one they fill as it is (the arena keeps the persistent tensors apart from the VAE programs). */
 
@@ -369,7 +373,7 @@ int sdeo_dpmpp_2m_step(sdeo_handle h, float* x, float* d, int table_row, float c
  *   - every argument check happens before the first device call, each with its own message: a null x / orig / noise / mask, mask_n or
  *     mask_c outside the allowed values, an unconfigured handle, an odd configured n, a table row outside the table, an invalid
  *     schedule (what the update kernel would refuse), d null with k_p != 0.  A refused call leaves x, pred_x0 and d untouched;
- *   - capturable; sdeo_ddim_step and sdeo_dpmpp_2m_step are unchanged: same signatures, same launches, same bits. */
+ *   - capturable. */
 int sdeo_ddim_step_masked(sdeo_handle h, float* x, float* pred_x0, const float* orig, const float* noise, const float* mask, int mask_n,
                           int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row, float cfg_scale, float a_t, float a_prev,
                           float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream);
@@ -396,7 +400,7 @@ int sdeo_dpmpp_2m_step_masked(sdeo_handle h, float* x, float* d, const float* or
  *   - refused before the first device call, each with its own message, x / pred_x0 / d untouched: a null noise with sigma_t != 0 or
  *     k_n != 0; 1 - a_prev - sigma_t^2 < 0; a non-finite coefficient; a partial set of blend operands; SDEO_STEP_LATENT_STAGED together
  *     with a mask; and everything the unmasked and the masked steps refuse;
- *   - capturable; every earlier entry point is unchanged: same signatures, same launches, same bits. */
+ *   - capturable. */
 int sdeo_ddim_step_eta(sdeo_handle h, float* x, float* pred_x0, const float* noise, float sigma_t,
                        const float* orig, const float* mask_noise, const float* mask, int mask_n, int mask_c, float sqrt_a,
                        float sqrt_one_minus_a, int table_row, float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at,

@@ -131,6 +131,71 @@ def draw_rows(img, x0, mask_rows, step_rows, live, first, last):
             step_rows[i].copy_(torch.randn(img.shape, device=img.device))
 
 
+def captured_loop(owner, img, mask, x0, time_range, live, shape_key, log_every_t, intermediates, state, first_step, emit):
+    """The loop of a sampler `owner` with step 1 run eagerly (it computes the hint block and the context K / V of THIS image into the
+    runtime's caches) and steps 2..S replayed from captured graphs.  The graphs read the latent (owner._loop_x) and the sampler's second
+    state tensor (the attribute named `state`) from fixed buffers and the conditioning from those caches, so they are reused for every
+    image with the same key: the runtime's generation, read after step 1 (the first forward at a new shape re-plans the runtime), then
+    the sampler's `shape_key`; per-step constants are baked in at capture.
+      first_step(img, state_buf) -> (x, state): the eager step; `state` is what the intermediates record for it.
+      emit(i, staged, noise_row, blend): the library call of loop step i on the fixed buffers.  noise_row: the row its noise term reads
+        (live[i]), else None.  blend: with a mask, the operands of the blend in front of the step (`mask_operands`, coefficients baked
+        in) under the names of the stochastic steps' keywords, in the masked steps' positional order.  staged: the previous captured
+        step left this step's fp16 latent in place.
+    With a mask every step starts with x = q_sample(x0, t) * mask + (1 - mask) * x: ops.mask_blend in front of step 1.  The rows are drawn
+    per image in the per-step loop's order (`draw_rows`); step 1 draws inside first_step, so with a mask row 0 is drawn before it and
+    everything else after it."""
+    m, rt = owner.model, owner.model.rt
+    total_steps = len(time_range)
+    stochastic = any(live)
+    step_noise = step_noise_rows(owner, img, total_steps) if stochastic else None
+    noise = None
+    if mask is not None:
+        coefs = blend_coefficients(owner, m, time_range)
+        orig, mask_buf, noise = mask_operands(owner, img, mask, x0, total_steps, fill=not stochastic)
+        if stochastic:
+            draw_rows(img, x0, noise, None, [False], 0, 1)
+        img = ops.mask_blend(img.clone(memory_format=torch.contiguous_format), orig, noise[0], mask_buf, *coefs[0])
+    if getattr(owner, "_loop_key", None) is None or owner._loop_key[1:] != shape_key:
+        owner._loop_key = None
+        owner._loop_x = torch.empty_like(img, memory_format=torch.contiguous_format)
+        setattr(owner, state, torch.empty_like(owner._loop_x))
+    loop_x, loop_s = owner._loop_x, getattr(owner, state)
+    x1, s1 = first_step(img, loop_s)
+    if stochastic:
+        draw_rows(img, x0, noise, step_noise, live, 1, total_steps)
+    intermediates["x_inter"].append(x1)                  # index == total_steps - 1
+    intermediates["pred_x0"].append(s1)
+    loop_x.copy_(x1)
+    if getattr(rt, "_table_key", None) != (rt.generation, time_range):
+        rt.set_timestep_table(time_range)                # another schedule used the runtime since (the graphs read the table by address)
+    key = (rt.generation,) + shape_key
+    if owner._loop_key != key:
+        owner._loop_key = None
+        torch.cuda.synchronize(img.device)
+        graphs, kept_x, kept_s = [], [], []
+        per_graph = LOOP_GRAPH_STEPS if LOOP_GRAPH_STEPS > 0 else total_steps
+        for first in range(1, total_steps, per_graph):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for i in range(first, min(first + per_graph, total_steps)):
+                    blend = None if mask is None else dict(orig=orig, mask_noise=noise[i], mask=mask_buf, sqrt_a=coefs[i][0],
+                                                           sqrt_one_minus_a=coefs[i][1])
+                    emit(i, i > first and mask is None, step_noise[i] if live[i] else None, blend)
+                    if (total_steps - i - 1) % log_every_t == 0:
+                        kept_x.append(loop_x.clone())
+                        kept_s.append(loop_s.clone())
+            graphs.append(g)
+        owner._loop_graphs, owner._loop_kept = graphs, (kept_x, kept_s)
+        owner._loop_key = key
+    for g in owner._loop_graphs:
+        g.replay()
+    # the graphs' tensors are overwritten by the next replay: hand out copies
+    intermediates["x_inter"].extend(t.clone() for t in owner._loop_kept[0])
+    intermediates["pred_x0"].extend(t.clone() for t in owner._loop_kept[1])
+    return loop_x.clone(), intermediates
+
+
 class DDIMSampler(object):
     def __init__(self, model, schedule="linear", **kwargs):
         super().__init__()
@@ -284,91 +349,40 @@ class DDIMSampler(object):
         return hasattr(self, "_sigmas_all_zero") and temperature == 1. and noise_dropout == 0.
 
     def _loop_graphed(self, img, c, uc, scale, time_range, total_steps, log_every_t, intermediates, mask=None, x0=None):
-        """The loop of `cldm/ddim_hacked.py:137-160` with step 1 run eagerly (it computes the hint block and the context K / V of
-        THIS image into the runtime's caches) and steps 2..S replayed from one captured graph.  The graph reads the latent from a
-        fixed buffer and the conditioning from those caches, so it is reused for every image of the same shape, step count,
-        guidance scale and control scales; per-step constants (alpha_t, ...) are baked in at capture.
-        With a mask (`:154-157`) every step starts with the blend img = q_sample(x0, t) * mask + (1 - mask) * img: step 1 calls
-        ops.mask_blend, the captured steps are sdeo_ddim_step_masked calls that read x0, the mask and their noise row from the
-        sampler's fixed buffers (`mask_operands`); the blend coefficients are baked in like the other per-step constants.
-        With eta > 0 (`:227-230`) the captured steps with sigma_t != 0 are sdeo_ddim_step_eta calls that read their noise row by address;
-        a step with sigma_t == 0 captures the plain step, and the eta = 0 loop captures exactly what it always did."""
+        """The loop of `cldm/ddim_hacked.py:137-160` as a `captured_loop`: the schedule is known, so each captured step is ONE library call
+        (apply_model on [x; x] + CFG + DDIM update, x updated in place in the fixed buffer).  With a mask (`:154-157`) the captured steps
+        are sdeo_ddim_step_masked calls.  With eta > 0 (`:227-230`) loop step i adds sigma[S - 1 - i] * noise: the captured steps with
+        sigma_t != 0 are sdeo_ddim_step_eta calls that read their noise row by address; a step with sigma_t == 0 captures the plain step,
+        and the eta = 0 loop captures exactly what it always did."""
         m, rt = self.model, self.model.rt
-        b = img.shape[0]
-        dev = img.device
-        # eta > 0: loop step i adds sigma[S - 1 - i] * noise; its row is drawn per image in the per-step loop's order (`draw_rows`).  Step 1
-        # runs eagerly and draws inside p_sample_ddim, so with a mask row 0 is drawn before it and everything else after it.
-        stochastic = not self._sigmas_all_zero
+        time_range = tuple(int(t) for t in time_range)
         sig = self._sigmas_host
-        live = [stochastic and float(sig[total_steps - 1 - i]) != 0. for i in range(total_steps)]
-        step_noise = step_noise_rows(self, img, total_steps) if stochastic else None
-        noise = None
-        if mask is not None:
-            coefs = blend_coefficients(self, m, time_range)
-            orig, mask_buf, noise = mask_operands(self, img, mask, x0, total_steps, fill=not stochastic)
-            if stochastic:
-                draw_rows(img, x0, noise, None, [False], 0, 1)
-            img = ops.mask_blend(img.clone(memory_format=torch.contiguous_format), orig, noise[0], mask_buf, *coefs[0])
-        ts = torch.full((b,), int(time_range[0]), device=dev, dtype=torch.long)
-        img, pred_x0 = self.p_sample_ddim(img, c, ts, index=total_steps - 1, unconditional_guidance_scale=scale,
-                                          unconditional_conditioning=uc)
-        if stochastic:
-            draw_rows(img, x0, noise, step_noise, live, 1, total_steps)
-        intermediates["x_inter"].append(img)             # index == total_steps - 1
-        intermediates["pred_x0"].append(pred_x0)
+        live = [not self._sigmas_all_zero and float(sig[total_steps - 1 - i]) != 0. for i in range(total_steps)]
         # cond and uncond were given the SAME control tensors (canny2image / hed2image outside guess mode): the hint features of the
         # two halves of the batch are equal, which lets the ControlNet share what precedes its first cross-attention (baked in at capture)
         hint_shared = self._ident(c["c_concat"]) == self._ident(uc["c_concat"])
-        key = (rt.generation, tuple(img.shape), tuple(int(t) for t in time_range), float(scale), int(log_every_t),
-               m.scales_key(), bool(m.only_mid_control), getattr(self, "_schedule_key", None), LOOP_GRAPH_STEPS,
-               hint_shared, m.parameterization, None if mask is None else tuple(mask.shape))
-        if getattr(rt, "_table_key", None) != (rt.generation, tuple(int(t) for t in time_range)):
-            rt.set_timestep_table(time_range)            # another schedule used the runtime since (the graphs read the table by address)
-        if getattr(self, "_loop_key", None) != key:
-            self._loop_key = None
-            self._loop_x = torch.empty_like(img)
-            self._loop_x.copy_(img)
-            a_t, a_p, s1m = self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sqrt_one_minus_alphas
-            # the schedule is known: the time embeddings of all steps were computed once above (row i = step i of the loop) and each step is
-            # ONE library call (sdeo_ddim_step: apply_model on [x; x] + CFG + DDIM update, x updated in place in the fixed buffer)
-            self._loop_pred = torch.empty_like(img)
-            torch.cuda.synchronize(dev)
-            graphs, kept_x, kept_p = [], [], []
-            per_graph = LOOP_GRAPH_STEPS if LOOP_GRAPH_STEPS > 0 else total_steps
-            for first in range(1, total_steps, per_graph):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    for i in range(first, min(first + per_graph, total_steps)):
-                        index = total_steps - i - 1
-                        if live[i]:
-                            blend = {} if mask is None else dict(orig=orig, mask_noise=noise[i], mask=mask_buf, sqrt_a=coefs[i][0],
-                                                                 sqrt_one_minus_a=coefs[i][1])
-                            rt.ddim_step_eta(self._loop_x, self._loop_pred, step_noise[i], float(sig[index]), i, scale, float(a_t[index]),
-                                             float(a_p[index]), float(s1m[index]), m.net0_scales(), m.only_mid_control,
-                                             staged=i > first and mask is None, hint_shared=hint_shared,
-                                             v_prediction=m.parameterization == "v", **blend)
-                        elif mask is None:
-                            rt.ddim_step(self._loop_x, self._loop_pred, i, scale, float(a_t[index]), float(a_p[index]), float(s1m[index]),
-                                         m.net0_scales(), m.only_mid_control, staged=i > first, hint_shared=hint_shared,
-                                         v_prediction=m.parameterization == "v")
-                        else:
-                            rt.ddim_step_masked(self._loop_x, self._loop_pred, orig, noise[i], mask_buf, *coefs[i], i, scale,
-                                                float(a_t[index]), float(a_p[index]), float(s1m[index]), m.net0_scales(),
-                                                m.only_mid_control, hint_shared=hint_shared, v_prediction=m.parameterization == "v")
-                        if index % log_every_t == 0:
-                            kept_x.append(self._loop_x.clone())
-                            kept_p.append(self._loop_pred.clone())
-                graphs.append(g)
-            self._loop_graphs, self._loop_kept = graphs, (kept_x, kept_p)
-            self._loop_key = key
-        else:
-            self._loop_x.copy_(img)
-        for g in self._loop_graphs:
-            g.replay()
-        # the graphs' tensors are overwritten by the next replay: hand out copies
-        intermediates["x_inter"].extend(t.clone() for t in self._loop_kept[0])
-        intermediates["pred_x0"].extend(t.clone() for t in self._loop_kept[1])
-        return self._loop_x.clone(), intermediates
+        shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), m.scales_key(), bool(m.only_mid_control),
+                     getattr(self, "_schedule_key", None), LOOP_GRAPH_STEPS, hint_shared, m.parameterization,
+                     None if mask is None else tuple(mask.shape))
+        a_t, a_p, s1m = self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sqrt_one_minus_alphas
+
+        def first_step(img, pred):
+            ts = torch.full((img.shape[0],), time_range[0], device=img.device, dtype=torch.long)
+            return self.p_sample_ddim(img, c, ts, index=total_steps - 1, unconditional_guidance_scale=scale, unconditional_conditioning=uc)
+
+        def emit(i, staged, noise_row, blend):
+            index = total_steps - i - 1
+            x, pred = self._loop_x, self._loop_pred
+            tail = (i, scale, float(a_t[index]), float(a_p[index]), float(s1m[index]), m.net0_scales(), m.only_mid_control)
+            kw = dict(hint_shared=hint_shared, v_prediction=m.parameterization == "v")
+            if noise_row is not None:
+                rt.ddim_step_eta(x, pred, noise_row, float(sig[index]), *tail, staged=staged, **kw, **(blend or {}))
+            elif blend is None:
+                rt.ddim_step(x, pred, *tail, staged=staged, **kw)
+            else:
+                rt.ddim_step_masked(x, pred, *blend.values(), *tail, **kw)
+
+        return captured_loop(self, img, mask, x0, time_range, live, shape_key, log_every_t, intermediates, "_loop_pred", first_step, emit)
 
     # ------------------------------------------------------------------------------------------ one step
     @staticmethod

@@ -10,7 +10,7 @@ phi = -expm1(-h), and D the CFG-combined data prediction (the pred_x0 of the DDI
 The host folds all of it into three fp64 coefficients per step, x_next = k_x x + k_d D + k_p D_prev; the device side
 (`sdeo_cfg_dpmpp_2m_step`, `sdeo_dpmpp_2m_step`) never sees lambda.  The only state next to the latent is one fp32 tensor, D_prev.
 
-The loop has the shape of `DDIMSampler._loop_graphed`: step 1 runs eagerly (it fills the runtime's hint / context caches), steps 2..S are
+The loop is DDIM's (`ddim_hacked.captured_loop`): step 1 runs eagerly (it fills the runtime's hint / context caches), steps 2..S are
 replayed from a captured graph with the per-step coefficients baked in (with a mask: the masked steps, `ddim_hacked.mask_operands`); what
 does not qualify (callbacks, a replaced q_sample, no ControlNet hint on one half, scale == 1, a model without a runtime) runs one step at a time.  The switches are ddim_hacked's (SDEO_GRAPH,
 SDEO_LOOP_GRAPH, SDEO_LOOP_GRAPH_STEPS).
@@ -235,80 +235,38 @@ class DPMSolverSampler(object):
                     and self.model.parameterization in ("eps", "v"))
 
     def _loop_graphed(self, img, c, uc, scale, total_steps, log_every_t, intermediates, mask=None, x0=None):
-        """With a mask every step starts with x = q_sample(x0, t) * mask + (1 - mask) * x, as in `_run`: ops.mask_blend in front of the eager
-        step 1, sdeo_dpmpp_2m_step_masked for the captured steps (operands: `ddim_hacked.mask_operands`)."""
+        """`ddim_hacked.captured_loop` over this solver's steps: `_step` for the eager step 1, sdeo_dpmpp_2m_step for the captured ones
+        (with a mask sdeo_dpmpp_2m_step_masked; the stochastic subclass's steps with k_n[i] != 0 sdeo_dpmpp_2m_sde_step, which reads
+        its noise row by address).  The solver's only state next to x is D of the last step taken (self._loop_d)."""
         m, rt = self.model, self.model.rt
-        ts, a_t, k_x, k_d, k_p = self.timesteps, self.alphas, self.k_x, self.k_d, self.k_p
+        ts, a_t, k_x, k_d, k_p, k_n = self.timesteps, self.alphas, self.k_x, self.k_d, self.k_p, self.k_n
         time_range = tuple(int(t) for t in ts)
         ident = DDIMSampler._ident
         hint_shared = ident(c["c_concat"]) == ident(uc["c_concat"])
         per_graph = dh.LOOP_GRAPH_STEPS if dh.LOOP_GRAPH_STEPS > 0 else total_steps
-        # (rt.generation is read after step 1: the first forward at a new shape re-plans the runtime)
         shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), m.scales_key(),
                      bool(m.only_mid_control), self._schedule_key, per_graph, hint_shared, m.parameterization,
                      None if mask is None else tuple(mask.shape))
-        # the stochastic subclass: step i adds k_n[i] * noise, read from a row drawn per image in the per-step loop's order
-        # (`ddim_hacked.draw_rows`).  Step 1 runs eagerly and draws inside `_step`: with a mask, row 0 is drawn before it, the rest after.
-        k_n = self.k_n
         live = [k_n is not None and float(k_n[i]) != 0. for i in range(total_steps)]
-        stochastic = any(live)
-        step_noise = dh.step_noise_rows(self, img, total_steps) if stochastic else None
-        noise = None
-        if mask is not None:
-            coefs = dh.blend_coefficients(self, m, ts)
-            orig, mask_buf, noise = dh.mask_operands(self, img, mask, x0, total_steps, fill=not stochastic)
-            if stochastic:
-                dh.draw_rows(img, x0, noise, None, [False], 0, 1)
-            img = ops.mask_blend(img.clone(memory_format=torch.contiguous_format), orig, noise[0], mask_buf, *coefs[0])
-        if self._loop_key is None or self._loop_key[1:] != shape_key:
-            self._loop_key = None
-            self._loop_x = torch.empty_like(img, memory_format=torch.contiguous_format)
-            self._loop_d = torch.empty_like(self._loop_x)             # D of the last step taken: the solver's only state next to x
-        x1 = self._step(img, self._loop_d, c, uc, scale, 0, ts, a_t, k_x, k_d, k_p, k_n)
-        if stochastic:
-            dh.draw_rows(img, x0, noise, step_noise, live, 1, total_steps)
-        intermediates["x_inter"].append(x1)                           # index == total_steps - 1
-        intermediates["pred_x0"].append(self._loop_d.clone())
-        self._loop_x.copy_(x1)
-        if getattr(rt, "_table_key", None) != (rt.generation, time_range):
-            rt.set_timestep_table(time_range)                         # another schedule used the runtime since (the graphs read the table by address)
-        key = (rt.generation,) + shape_key
-        if self._loop_key != key:
-            self._loop_key = None
-            torch.cuda.synchronize(img.device)
-            graphs, kept_x, kept_d = [], [], []
-            v_pred = m.parameterization == "v"
-            for first in range(1, total_steps, per_graph):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    for i in range(first, min(first + per_graph, total_steps)):
-                        a = float(a_t[i])
-                        if live[i]:
-                            blend = {} if mask is None else dict(orig=orig, mask_noise=noise[i], mask=mask_buf, sqrt_a=coefs[i][0],
-                                                                 sqrt_one_minus_a=coefs[i][1])
-                            rt.dpmpp_2m_sde_step(self._loop_x, self._loop_d, step_noise[i], i, scale, a, float(np.sqrt(1.0 - a)), float(k_x[i]),
-                                                 float(k_d[i]), float(k_p[i]), float(k_n[i]), m.net0_scales(), m.only_mid_control,
-                                                 staged=i > first and mask is None, hint_shared=hint_shared, v_prediction=v_pred, **blend)
-                        elif mask is None:
-                            rt.dpmpp_2m_step(self._loop_x, self._loop_d, i, scale, a, float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]),
-                                             float(k_p[i]), m.net0_scales(), m.only_mid_control, staged=i > first, hint_shared=hint_shared,
-                                             v_prediction=v_pred)
-                        else:
-                            rt.dpmpp_2m_step_masked(self._loop_x, self._loop_d, orig, noise[i], mask_buf, *coefs[i], i, scale, a,
-                                                    float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]), float(k_p[i]), m.net0_scales(),
-                                                    m.only_mid_control, hint_shared=hint_shared, v_prediction=v_pred)
-                        if (total_steps - i - 1) % log_every_t == 0:
-                            kept_x.append(self._loop_x.clone())
-                            kept_d.append(self._loop_d.clone())
-                graphs.append(g)
-            self._loop_graphs, self._loop_kept = graphs, (kept_x, kept_d)
-            self._loop_key = key
-        for g in self._loop_graphs:
-            g.replay()
-        # the graphs' tensors are overwritten by the next replay: hand out copies
-        intermediates["x_inter"].extend(t.clone() for t in self._loop_kept[0])
-        intermediates["pred_x0"].extend(t.clone() for t in self._loop_kept[1])
-        return self._loop_x.clone(), intermediates
+
+        def first_step(img, d):
+            x1 = self._step(img, d, c, uc, scale, 0, ts, a_t, k_x, k_d, k_p, k_n)
+            return x1, d.clone()
+
+        def emit(i, staged, noise_row, blend):
+            a = float(a_t[i])
+            x, d = self._loop_x, self._loop_d
+            head = (i, scale, a, float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]), float(k_p[i]))
+            kw = dict(hint_shared=hint_shared, v_prediction=m.parameterization == "v")
+            if noise_row is not None:
+                rt.dpmpp_2m_sde_step(x, d, noise_row, *head, float(k_n[i]), m.net0_scales(), m.only_mid_control, staged=staged, **kw,
+                                     **(blend or {}))
+            elif blend is None:
+                rt.dpmpp_2m_step(x, d, *head, m.net0_scales(), m.only_mid_control, staged=staged, **kw)
+            else:
+                rt.dpmpp_2m_step_masked(x, d, *blend.values(), *head, m.net0_scales(), m.only_mid_control, **kw)
+
+        return dh.captured_loop(self, img, mask, x0, time_range, live, shape_key, log_every_t, intermediates, "_loop_d", first_step, emit)
 
     # ------------------------------------------------------------------------------------------ img2img
     @torch.no_grad()

@@ -423,15 +423,15 @@ int sdeo_cfg_ddim_step_v(float* x_prev, float* pred_x0, const float* x, const fl
 
 int sdeo_cfg_dpmpp_2m_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, float cfg_scale, float a_t,
                            float sqrt_one_minus_at, float k_x, float k_d, float k_p, int flags, int64_t n, void* stream) {
-  return cfg_lms_step(x_next, d, x, m_c, m_u, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, n, (flags & SDEO_STEP_V_PREDICTION) != 0,
-                      S(stream));
+  return cfg_lms_step("cfg_lms_step", x_next, d, x, m_c, m_u, nullptr, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, 0.f, n,
+                      (flags & SDEO_STEP_V_PREDICTION) != 0, S(stream));
 }
 
 int sdeo_cfg_dpmpp_2m_sde_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, const float* noise,
                                float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, int flags,
                                int64_t n, void* stream) {
-  return cfg_lms_noise_step(x_next, d, x, m_c, m_u, noise, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, k_n, n,
-                            (flags & SDEO_STEP_V_PREDICTION) != 0, S(stream));
+  return cfg_lms_step("cfg_lms_noise_step", x_next, d, x, m_c, m_u, noise, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, k_n, n,
+                      (flags & SDEO_STEP_V_PREDICTION) != 0, S(stream));
 }
 
 int sdeo_mask_blend(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a,

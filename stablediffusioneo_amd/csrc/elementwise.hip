@@ -3,6 +3,7 @@
 #include "kernels.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace sdeo {
 
@@ -302,6 +303,21 @@ __device__ __forceinline__ void cfg_ddim_elem_sel(float x, float c, float u, boo
   else cfg_ddim_elem(x, c, u, guided, s, at_coef, sqrt_aprev, dir_coef, sqrt_1m_at, p0, xp);
 }
 
+// The launch-time choice of a kernel's bool template parameters: f receives the two flags as std::bool_constant values, so that its body
+// can name K<v.value, n.value>.  Every launcher of the sampler-step family below chooses its instantiation through it.
+template <typename F>
+static inline void with_flags(bool a, bool b, F&& f) {
+  if (a) {
+    if (b) f(std::true_type{}, std::true_type{});
+    else f(std::true_type{}, std::false_type{});
+  } else {
+    if (b) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+  }
+}
+
+// `noise` (fp32, laid out like x) adds the sampler's noise term (`cldm/ddim_hacked.py:227-230`, eta > 0): one fused multiply-add on the
+// finished update, stated as fmaf here and in the pair kernel so that the two round alike whatever the compiler does.
 template <bool VPRED>
 __global__ __launch_bounds__(256) void cfg_ddim_kernel(float* __restrict__ x_prev, float* __restrict__ pred_x0,
                                                        const float* __restrict__ x, const float* __restrict__ ec,
@@ -311,65 +327,83 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(float* __restrict__ x_pre
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     float p0, xp;
     cfg_ddim_elem_sel<VPRED>(x[i], ec[i], eu ? eu[i] : 0.f, eu != nullptr, s, at_coef, sqrt_aprev, dir_coef, sqrt_1m_at, p0, xp);
-    if (noise) xp += sigma * noise[i];
+    if (noise) xp = fmaf(sigma, noise[i], xp);
     x_prev[i] = xp;
     if (pred_x0) pred_x0[i] = p0;
   }
 }
 
-// The same update for the fused CFG pair inside the library (sdeo_ddim_step): eps comes straight from the UNet's fp16 NHWC output
-// (images 0..b-1 conditional, b..2b-1 unconditional), x [b][C][HW] fp32 is updated in place, and the fp16 NHWC latent of the NEXT
-// forward (both halves of the pair, padding channels zero) is written on the way out.  One thread per (image, pixel).
-template <bool VPRED>
-__global__ __launch_bounds__(256) void cfg_ddim_pair_kernel(float* __restrict__ x, float* __restrict__ pred_x0, const f16* __restrict__ eps,
-                                                            int lde, f16* __restrict__ x0, int ld0, int b, int C, int HW, float s,
-                                                            float at_coef, float sqrt_aprev, float dir_coef, float sqrt_1m_at) {
+// The loop of every kernel that leaves the fp16 NHWC latent of the next forward in x0: one thread per (image, pixel) of a latent
+// [b][C][HW], and what elem(i, n, c, pix, j) returns for channel c (j: the element's index in the fp32 NCHW latent, i = n * HW + pix) goes
+// to both halves of the CFG pair (images n and n + b), padding channels zero.  elem does its own fp32 loads and stores.
+template <typename F>
+__device__ __forceinline__ void stage_pair(f16* __restrict__ x0, int ld0, int b, int C, int HW, F elem) {
   const int64_t total = (int64_t)b * HW;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int64_t n = i / HW, pix = i - n * HW;
-    const f16* ec = eps + i * lde;
-    const f16* eu = eps + (i + total) * lde;
     for (int c = 0; c < ld0; ++c) {
-      f16 v = (f16)0.f;
-      if (c < C) {
-        const int64_t j = (n * C + c) * HW + pix;
-        float p0, xp;
-        cfg_ddim_elem_sel<VPRED>(x[j], (float)ec[c], (float)eu[c], true, s, at_coef, sqrt_aprev, dir_coef, sqrt_1m_at, p0, xp);
-        x[j] = xp;
-        if (pred_x0) pred_x0[j] = p0;
-        v = (f16)xp;
-      }
+      const f16 v = c < C ? (f16)elem(i, n, c, pix, (n * C + c) * HW + pix) : (f16)0.f;
       x0[i * ld0 + c] = v;
       x0[(i + total) * ld0 + c] = v;
     }
   }
 }
 
-int cfg_ddim_pair(float* x, float* pred_x0, const f16* eps, int lde, f16* x0, int ld0, int b, int C, int HW, float cfg_scale, float a_t,
-                  float a_prev, float sqrt_one_minus_at, bool v_prediction, hipStream_t stream) {
+// The same update for the fused CFG pair inside the library (the sdeo_ddim_step family): eps comes straight from the UNet's fp16 NHWC
+// output (images 0..b-1 conditional, b..2b-1 unconditional), x [b][C][HW] fp32 is updated in place, and the latent of the NEXT forward is
+// staged on the way out (from the noisy value when NOISE).
+template <bool VPRED, bool NOISE>
+__global__ __launch_bounds__(256) void cfg_ddim_pair_kernel(float* __restrict__ x, float* __restrict__ pred_x0, const f16* __restrict__ eps,
+                                                            int lde, const float* __restrict__ noise, f16* __restrict__ x0, int ld0, int b,
+                                                            int C, int HW, float s, float at_coef, float sqrt_aprev, float dir_coef,
+                                                            float sigma, float sqrt_1m_at) {
+  const int64_t total = (int64_t)b * HW;
+  stage_pair(x0, ld0, b, C, HW, [=](int64_t i, int64_t, int c, int64_t, int64_t j) {
+    float p0, xp;
+    cfg_ddim_elem_sel<VPRED>(x[j], (float)eps[i * lde + c], (float)eps[(i + total) * lde + c], true, s, at_coef, sqrt_aprev, dir_coef,
+                             sqrt_1m_at, p0, xp);
+    if constexpr (NOISE) xp = fmaf(sigma, noise[j], xp);
+    x[j] = xp;
+    if (pred_x0) pred_x0[j] = p0;
+    return xp;
+  });
+}
+
+// What the DDIM update refuses, host only: callers that change x before it (the blend) or must leave x untouched refuse up front.
+// sigma_t null: the deterministic update, which takes no noise.
+int cfg_ddim_check(const char* who, float a_t, float a_prev, const float* noise, const float* sigma_t) {
+  if (!sigma_t) {
+    SDEO_CHECK(a_t > 0.f && (1.f - a_prev) >= 0.f, "%s: invalid schedule a_t=%g a_prev=%g", who, a_t, a_prev);
+    return 0;
+  }
+  const float sg = *sigma_t;
+  SDEO_CHECK(std::isfinite(a_t) && std::isfinite(a_prev) && std::isfinite(sg), "%s: non-finite coefficient a_t=%g a_prev=%g sigma_t=%g", who,
+             a_t, a_prev, sg);
+  SDEO_CHECK(noise || sg == 0.f, "%s: sigma_t=%g needs the step noise, but noise is null", who, sg);
+  SDEO_CHECK(a_t > 0.f, "%s: invalid schedule a_t=%g", who, a_t);
+  SDEO_CHECK((1.f - a_prev - sg * sg) >= 0.f, "%s: 1 - a_prev - sigma_t^2 < 0 (a_prev=%g sigma_t=%g)", who, a_prev, sg);
+  return 0;
+}
+
+// noise set: the stochastic update, bit-equal to cfg_ddim_step with the same noise / sigma_t; null: sigma_t is not read
+int cfg_ddim_pair(float* x, float* pred_x0, const f16* eps, int lde, const float* noise, float sigma_t, f16* x0, int ld0, int b, int C, int HW,
+                  float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, bool v_prediction, hipStream_t stream) {
   SDEO_CHECK(x && eps && x0 && b > 0 && C > 0 && HW > 0 && lde >= C && ld0 >= C, "cfg_ddim_pair: bad operand");
-  SDEO_CHECK(a_t > 0.f && (1.f - a_prev) >= 0.f, "cfg_ddim_pair: invalid schedule a_t=%g a_prev=%g", a_t, a_prev);
-  if (v_prediction)
-    hipLaunchKernelGGL(cfg_ddim_pair_kernel<true>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, pred_x0, eps, lde, x0, ld0, b, C, HW,
-                       cfg_scale, sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev), sqrt_one_minus_at);
-  else
-    hipLaunchKernelGGL(cfg_ddim_pair_kernel<false>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, pred_x0, eps, lde, x0, ld0, b, C, HW,
-                       cfg_scale, 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev), sqrt_one_minus_at);
+  if (int rc = cfg_ddim_check("cfg_ddim_pair", a_t, a_prev, noise, noise ? &sigma_t : nullptr)) return rc;
+  // the coefficients as cfg_ddim_step forms them, expression for expression
+  const float sg = noise ? sigma_t : 0.f;
+  with_flags(v_prediction, noise != nullptr, [&](auto v, auto n) {
+    hipLaunchKernelGGL((cfg_ddim_pair_kernel<v.value, n.value>), grid_for((int64_t)b * HW), dim3(256), 0, stream, x, pred_x0, eps, lde, noise, x0,
+                       ld0, b, C, HW, cfg_scale, v.value ? sqrtf(a_t) : 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sg * sg), sg,
+                       sqrt_one_minus_at);
+  });
   SDEO_HIP(hipGetLastError());
   return 0;
 }
 
-// latent [b][C][HW] fp32 -> fp16 NHWC for BOTH halves of the CFG pair (images n and n + b), padding channels zero
+// latent [b][C][HW] fp32 -> fp16 NHWC for BOTH halves of the CFG pair
 __global__ __launch_bounds__(256) void latent_pair_kernel(f16* __restrict__ x0, int ld0, const float* __restrict__ x, int b, int C, int HW) {
-  const int64_t total = (int64_t)b * HW;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t n = i / HW, pix = i - n * HW;
-    for (int c = 0; c < ld0; ++c) {
-      const f16 v = c < C ? (f16)x[(n * C + c) * HW + pix] : (f16)0.f;
-      x0[i * ld0 + c] = v;
-      x0[(i + total) * ld0 + c] = v;
-    }
-  }
+  stage_pair(x0, ld0, b, C, HW, [=](int64_t, int64_t, int, int64_t, int64_t j) { return x[j]; });
 }
 
 int latent_pair_to_nhwc(f16* x0, int ld0, const float* x, int b, int C, int HW, hipStream_t stream) {
@@ -411,26 +445,15 @@ __global__ __launch_bounds__(256) void mask_blend_kernel(float* x, const float* 
   }
 }
 
-// The blend as the front of a fused CFG-pair step, laid out as latent_pair_kernel (one thread per (image, pixel)): x [b][C][HW] is
-// blended in place and its fp16 NHWC copy goes to both halves of the pair, padding channels zero.
+// The blend as the front of a fused CFG-pair step: x [b][C][HW] is blended in place and the blended latent is staged.
 __global__ __launch_bounds__(256) void mask_blend_pair_kernel(float* x, const float* __restrict__ orig, const float* __restrict__ noise,
                                                               const float* __restrict__ mask, int mask_n, int mask_c, float sqrt_a,
                                                               float sqrt_1ma, f16* __restrict__ x0, int ld0, int b, int C, int HW) {
-  const int64_t total = (int64_t)b * HW;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t n = i / HW, pix = i - n * HW;
-    for (int c = 0; c < ld0; ++c) {
-      f16 v = (f16)0.f;
-      if (c < C) {
-        const int64_t j = (n * C + c) * HW + pix;
-        const float xb = mask_blend_elem(x[j], orig[j], noise[j], mask[mask_index(n, c, pix, mask_n, mask_c, HW)], sqrt_a, sqrt_1ma);
-        x[j] = xb;
-        v = (f16)xb;
-      }
-      x0[i * ld0 + c] = v;
-      x0[(i + total) * ld0 + c] = v;
-    }
-  }
+  stage_pair(x0, ld0, b, C, HW, [=](int64_t, int64_t n, int c, int64_t pix, int64_t j) {
+    const float xb = mask_blend_elem(x[j], orig[j], noise[j], mask[mask_index(n, c, pix, mask_n, mask_c, HW)], sqrt_a, sqrt_1ma);
+    x[j] = xb;
+    return xb;
+  });
 }
 
 int mask_blend_check(const char* who, const float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c,
@@ -487,81 +510,17 @@ int composite_u8(uint8_t* dst, const uint8_t* gen, const uint8_t* orig, const ui
   return 0;
 }
 
-int cfg_ddim_pair_check(const char* who, float a_t, float a_prev) {
-  SDEO_CHECK(a_t > 0.f && (1.f - a_prev) >= 0.f, "%s: invalid schedule a_t=%g a_prev=%g", who, a_t, a_prev);
-  return 0;
-}
-
-// cfg_ddim_pair_kernel with the sampler's noise term (`cldm/ddim_hacked.py:227-230`, eta > 0): x = x_prev + sigma * noise[j], noise fp32
-// [b][C][HW] like x; the fp16 staging of the next forward is written from the noisy value.  A sibling, so that the eta = 0 kernel keeps
-// its code.  In cfg_ddim_kernel `xp += sigma * noise[i]` is left to the compiler, which contracts it into one v_fmac_f32 (read in the ISA
-// of both of its instantiations): the same single rounding is stated here as fmaf, so the two round alike whatever the compiler does.
-template <bool VPRED>
-__global__ __launch_bounds__(256) void cfg_ddim_pair_noise_kernel(float* __restrict__ x, float* __restrict__ pred_x0,
-                                                                  const f16* __restrict__ eps, int lde, const float* __restrict__ noise,
-                                                                  f16* __restrict__ x0, int ld0, int b, int C, int HW, float s, float at_coef,
-                                                                  float sqrt_aprev, float dir_coef, float sigma, float sqrt_1m_at) {
-  const int64_t total = (int64_t)b * HW;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t n = i / HW, pix = i - n * HW;
-    const f16* ec = eps + i * lde;
-    const f16* eu = eps + (i + total) * lde;
-    for (int c = 0; c < ld0; ++c) {
-      f16 v = (f16)0.f;
-      if (c < C) {
-        const int64_t j = (n * C + c) * HW + pix;
-        float p0, xp;
-        cfg_ddim_elem_sel<VPRED>(x[j], (float)ec[c], (float)eu[c], true, s, at_coef, sqrt_aprev, dir_coef, sqrt_1m_at, p0, xp);
-        xp = fmaf(sigma, noise[j], xp);
-        x[j] = xp;
-        if (pred_x0) pred_x0[j] = p0;
-        v = (f16)xp;
-      }
-      x0[i * ld0 + c] = v;
-      x0[(i + total) * ld0 + c] = v;
-    }
-  }
-}
-
-// what the noisy pair update refuses, host only: callers that change x before it (the blend) or must leave x untouched refuse up front
-int cfg_ddim_pair_noise_check(const char* who, const float* noise, float a_t, float a_prev, float sigma_t) {
-  SDEO_CHECK(std::isfinite(a_t) && std::isfinite(a_prev) && std::isfinite(sigma_t), "%s: non-finite coefficient a_t=%g a_prev=%g sigma_t=%g",
-             who, a_t, a_prev, sigma_t);
-  SDEO_CHECK(noise || sigma_t == 0.f, "%s: sigma_t=%g needs the step noise, but noise is null", who, sigma_t);
-  SDEO_CHECK(a_t > 0.f, "%s: invalid schedule a_t=%g", who, a_t);
-  SDEO_CHECK((1.f - a_prev - sigma_t * sigma_t) >= 0.f, "%s: 1 - a_prev - sigma_t^2 < 0 (a_prev=%g sigma_t=%g)", who, a_prev, sigma_t);
-  return 0;
-}
-
-int cfg_ddim_pair_noise(float* x, float* pred_x0, const f16* eps, int lde, const float* noise, f16* x0, int ld0, int b, int C, int HW,
-                        float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, bool v_prediction,
-                        hipStream_t stream) {
-  SDEO_CHECK(x && eps && noise && x0 && b > 0 && C > 0 && HW > 0 && lde >= C && ld0 >= C, "cfg_ddim_pair_noise: bad operand");
-  if (int rc = cfg_ddim_pair_noise_check("cfg_ddim_pair_noise", noise, a_t, a_prev, sigma_t)) return rc;
-  // the coefficients as cfg_ddim_step forms them, expression for expression
-  if (v_prediction)
-    hipLaunchKernelGGL(cfg_ddim_pair_noise_kernel<true>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, pred_x0, eps, lde, noise, x0, ld0,
-                       b, C, HW, cfg_scale, sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sigma_t * sigma_t), sigma_t, sqrt_one_minus_at);
-  else
-    hipLaunchKernelGGL(cfg_ddim_pair_noise_kernel<false>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, pred_x0, eps, lde, noise, x0, ld0,
-                       b, C, HW, cfg_scale, 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sigma_t * sigma_t), sigma_t,
-                       sqrt_one_minus_at);
-  SDEO_HIP(hipGetLastError());
-  return 0;
-}
-
 int cfg_ddim_step(float* x_prev, float* pred_x0, const float* x, const float* eps_c, const float* eps_u, const float* noise,
                   float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, int64_t n, bool v_prediction,
                   hipStream_t stream) {
   SDEO_CHECK(x_prev && x && eps_c && n > 0, "cfg_ddim_step: bad operand");
   SDEO_CHECK(a_t > 0.f && (1.f - a_prev - sigma_t * sigma_t) >= 0.f, "cfg_ddim_step: invalid schedule a_t=%g a_prev=%g sigma=%g",
              a_t, a_prev, sigma_t);
-  if (v_prediction)
-    hipLaunchKernelGGL(cfg_ddim_kernel<true>, grid_for(n), dim3(256), 0, stream, x_prev, pred_x0, x, eps_c, eps_u, noise, cfg_scale,
-                       sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sigma_t * sigma_t), sigma_t, sqrt_one_minus_at, n);
-  else
-    hipLaunchKernelGGL(cfg_ddim_kernel<false>, grid_for(n), dim3(256), 0, stream, x_prev, pred_x0, x, eps_c, eps_u, noise, cfg_scale,
-                       1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sigma_t * sigma_t), sigma_t, sqrt_one_minus_at, n);
+  with_flags(v_prediction, false, [&](auto v, auto) {
+    hipLaunchKernelGGL(cfg_ddim_kernel<v.value>, grid_for(n), dim3(256), 0, stream, x_prev, pred_x0, x, eps_c, eps_u, noise, cfg_scale,
+                       v.value ? sqrtf(a_t) : 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sigma_t * sigma_t), sigma_t,
+                       sqrt_one_minus_at, n);
+  });
   SDEO_HIP(hipGetLastError());
   return 0;
 }
@@ -580,48 +539,47 @@ __device__ __forceinline__ void cfg_lms_elem(float x, float c, float u, bool gui
 }
 
 // fp32 NCHW operands.  d is read (when k_p != 0) and then written by the same thread at the same index, so it carries no __restrict__.
-template <bool VPRED>
+// NOISE is the stochastic member of the family (DPM-Solver++(2M) SDE): a fourth term, x_next = ... + k_n noise, one more fused
+// multiply-add on what cfg_lms_elem returns (stated as fmaf in both kernels so that they round alike).  noise is fp32, laid out like x.
+template <bool VPRED, bool NOISE>
 __global__ __launch_bounds__(256) void cfg_lms_kernel(float* __restrict__ x_next, float* d, const float* __restrict__ x,
-                                                      const float* __restrict__ mc, const float* __restrict__ mu, float s, float at_coef,
-                                                      float sqrt_1m_at, float k_x, float k_d, float k_p, int64_t n) {
+                                                      const float* __restrict__ mc, const float* __restrict__ mu,
+                                                      const float* __restrict__ noise, float s, float at_coef, float sqrt_1m_at, float k_x,
+                                                      float k_d, float k_p, float k_n, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     float p0, xn;
     const float dp = k_p != 0.f ? d[i] : 0.f;
     cfg_lms_elem<VPRED>(x[i], mc[i], mu ? mu[i] : 0.f, mu != nullptr, s, at_coef, sqrt_1m_at, k_x, k_d, k_p, dp, p0, xn);
+    if constexpr (NOISE) xn = fmaf(k_n, noise[i], xn);
     x_next[i] = xn;
     if (d) d[i] = p0;
   }
 }
 
-// The same update for the fused CFG pair (sdeo_dpmpp_2m_step), laid out as cfg_ddim_pair_kernel: fp16 NHWC model output (conditional
-// images first), x [b][C][HW] fp32 updated in place, the fp16 NHWC latent of both halves staged for the next forward.
-template <bool VPRED>
+// The same update for the fused CFG pair (the sdeo_dpmpp_2m_step family), laid out as cfg_ddim_pair_kernel: fp16 NHWC model output
+// (conditional images first), x [b][C][HW] fp32 updated in place, the latent of the next forward staged.
+template <bool VPRED, bool NOISE>
 __global__ __launch_bounds__(256) void cfg_lms_pair_kernel(float* __restrict__ x, float* d, const f16* __restrict__ eps, int lde,
-                                                           f16* __restrict__ x0, int ld0, int b, int C, int HW, float s, float at_coef,
-                                                           float sqrt_1m_at, float k_x, float k_d, float k_p) {
+                                                           const float* __restrict__ noise, f16* __restrict__ x0, int ld0, int b, int C, int HW,
+                                                           float s, float at_coef, float sqrt_1m_at, float k_x, float k_d, float k_p,
+                                                           float k_n) {
   const int64_t total = (int64_t)b * HW;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t n = i / HW, pix = i - n * HW;
-    const f16* ec = eps + i * lde;
-    const f16* eu = eps + (i + total) * lde;
-    for (int c = 0; c < ld0; ++c) {
-      f16 v = (f16)0.f;
-      if (c < C) {
-        const int64_t j = (n * C + c) * HW + pix;
-        float p0, xn;
-        const float dp = k_p != 0.f ? d[j] : 0.f;
-        cfg_lms_elem<VPRED>(x[j], (float)ec[c], (float)eu[c], true, s, at_coef, sqrt_1m_at, k_x, k_d, k_p, dp, p0, xn);
-        x[j] = xn;
-        if (d) d[j] = p0;
-        v = (f16)xn;
-      }
-      x0[i * ld0 + c] = v;
-      x0[(i + total) * ld0 + c] = v;
-    }
-  }
+  stage_pair(x0, ld0, b, C, HW, [=](int64_t i, int64_t, int c, int64_t, int64_t j) {
+    float p0, xn;
+    const float dp = k_p != 0.f ? d[j] : 0.f;
+    cfg_lms_elem<VPRED>(x[j], (float)eps[i * lde + c], (float)eps[(i + total) * lde + c], true, s, at_coef, sqrt_1m_at, k_x, k_d, k_p, dp, p0,
+                        xn);
+    if constexpr (NOISE) xn = fmaf(k_n, noise[j], xn);
+    x[j] = xn;
+    if (d) d[j] = p0;
+    return xn;
+  });
 }
 
-int lms_coefs_ok(const char* who, const float* d, float a_t, float k_x, float k_d, float k_p) {
+// what the multistep update refuses, host only (k_n = 0: the deterministic update, which takes no noise)
+int cfg_lms_check(const char* who, const float* d, const float* noise, float a_t, float k_x, float k_d, float k_p, float k_n) {
+  SDEO_CHECK(std::isfinite(k_n), "%s: non-finite coefficient k_n=%g", who, k_n);
+  SDEO_CHECK(noise || k_n == 0.f, "%s: k_n=%g needs the step noise, but noise is null", who, k_n);
   SDEO_CHECK(a_t > 0.f, "%s: invalid schedule a_t=%g", who, a_t);
   SDEO_CHECK(std::isfinite(k_x) && std::isfinite(k_d) && std::isfinite(k_p), "%s: non-finite coefficient k_x=%g k_d=%g k_p=%g", who, k_x, k_d,
              k_p);
@@ -629,115 +587,28 @@ int lms_coefs_ok(const char* who, const float* d, float a_t, float k_x, float k_
   return 0;
 }
 
-int cfg_lms_pair(float* x, float* d, const f16* eps, int lde, f16* x0, int ld0, int b, int C, int HW, float cfg_scale, float a_t,
-                 float sqrt_one_minus_at, float k_x, float k_d, float k_p, bool v_prediction, hipStream_t stream) {
+// k_n == 0: the deterministic kernel, whatever the noise pointer
+int cfg_lms_pair(float* x, float* d, const f16* eps, int lde, const float* noise, float k_n, f16* x0, int ld0, int b, int C, int HW,
+                 float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, bool v_prediction, hipStream_t stream) {
   SDEO_CHECK(x && eps && x0 && b > 0 && C > 0 && HW > 0 && lde >= C && ld0 >= C, "cfg_lms_pair: bad operand");
-  if (int rc = lms_coefs_ok("cfg_lms_pair", d, a_t, k_x, k_d, k_p)) return rc;
-  if (v_prediction)
-    hipLaunchKernelGGL(cfg_lms_pair_kernel<true>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, d, eps, lde, x0, ld0, b, C, HW,
-                       cfg_scale, sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p);
-  else
-    hipLaunchKernelGGL(cfg_lms_pair_kernel<false>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, d, eps, lde, x0, ld0, b, C, HW,
-                       cfg_scale, 1.0f / sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p);
+  if (int rc = cfg_lms_check("cfg_lms_pair", d, noise, a_t, k_x, k_d, k_p, k_n)) return rc;
+  with_flags(v_prediction, k_n != 0.f, [&](auto v, auto n) {
+    hipLaunchKernelGGL((cfg_lms_pair_kernel<v.value, n.value>), grid_for((int64_t)b * HW), dim3(256), 0, stream, x, d, eps, lde, noise, x0, ld0, b,
+                       C, HW, cfg_scale, v.value ? sqrtf(a_t) : 1.0f / sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p, k_n);
+  });
   SDEO_HIP(hipGetLastError());
   return 0;
 }
 
-// The stochastic member of the family (DPM-Solver++(2M) SDE): the same update with a fourth term, x_next = k_x x + k_d D + k_p D_prev +
-// k_n noise, one more fused multiply-add on what cfg_lms_elem returns (stated as fmaf in both kernels so that they round alike).  They are
-// siblings of cfg_lms_kernel / cfg_lms_pair_kernel, which keep their code; the host launches those when k_n == 0.  noise is fp32, laid
-// out like x.
-template <bool VPRED>
-__global__ __launch_bounds__(256) void cfg_lms_noise_kernel(float* __restrict__ x_next, float* d, const float* __restrict__ x,
-                                                            const float* __restrict__ mc, const float* __restrict__ mu,
-                                                            const float* __restrict__ noise, float s, float at_coef, float sqrt_1m_at,
-                                                            float k_x, float k_d, float k_p, float k_n, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float p0, xn;
-    const float dp = k_p != 0.f ? d[i] : 0.f;
-    cfg_lms_elem<VPRED>(x[i], mc[i], mu ? mu[i] : 0.f, mu != nullptr, s, at_coef, sqrt_1m_at, k_x, k_d, k_p, dp, p0, xn);
-    x_next[i] = fmaf(k_n, noise[i], xn);
-    if (d) d[i] = p0;
-  }
-}
-
-template <bool VPRED>
-__global__ __launch_bounds__(256) void cfg_lms_pair_noise_kernel(float* __restrict__ x, float* d, const f16* __restrict__ eps, int lde,
-                                                                 const float* __restrict__ noise, f16* __restrict__ x0, int ld0, int b, int C,
-                                                                 int HW, float s, float at_coef, float sqrt_1m_at, float k_x, float k_d,
-                                                                 float k_p, float k_n) {
-  const int64_t total = (int64_t)b * HW;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t n = i / HW, pix = i - n * HW;
-    const f16* ec = eps + i * lde;
-    const f16* eu = eps + (i + total) * lde;
-    for (int c = 0; c < ld0; ++c) {
-      f16 v = (f16)0.f;
-      if (c < C) {
-        const int64_t j = (n * C + c) * HW + pix;
-        float p0, xn;
-        const float dp = k_p != 0.f ? d[j] : 0.f;
-        cfg_lms_elem<VPRED>(x[j], (float)ec[c], (float)eu[c], true, s, at_coef, sqrt_1m_at, k_x, k_d, k_p, dp, p0, xn);
-        xn = fmaf(k_n, noise[j], xn);
-        x[j] = xn;
-        if (d) d[j] = p0;
-        v = (f16)xn;
-      }
-      x0[i * ld0 + c] = v;
-      x0[(i + total) * ld0 + c] = v;
-    }
-  }
-}
-
-// lms_coefs_ok plus the noise term's own conditions (host only)
-int lms_noise_coefs_ok(const char* who, const float* d, const float* noise, float a_t, float k_x, float k_d, float k_p, float k_n) {
-  SDEO_CHECK(std::isfinite(k_n), "%s: non-finite coefficient k_n=%g", who, k_n);
-  SDEO_CHECK(noise || k_n == 0.f, "%s: k_n=%g needs the step noise, but noise is null", who, k_n);
-  return lms_coefs_ok(who, d, a_t, k_x, k_d, k_p);
-}
-
-int cfg_lms_pair_noise(float* x, float* d, const f16* eps, int lde, const float* noise, f16* x0, int ld0, int b, int C, int HW,
-                       float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, bool v_prediction,
-                       hipStream_t stream) {
-  SDEO_CHECK(x && eps && noise && x0 && b > 0 && C > 0 && HW > 0 && lde >= C && ld0 >= C, "cfg_lms_pair_noise: bad operand");
-  if (int rc = lms_noise_coefs_ok("cfg_lms_pair_noise", d, noise, a_t, k_x, k_d, k_p, k_n)) return rc;
-  if (v_prediction)
-    hipLaunchKernelGGL(cfg_lms_pair_noise_kernel<true>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, d, eps, lde, noise, x0, ld0, b, C,
-                       HW, cfg_scale, sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p, k_n);
-  else
-    hipLaunchKernelGGL(cfg_lms_pair_noise_kernel<false>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, d, eps, lde, noise, x0, ld0, b, C,
-                       HW, cfg_scale, 1.0f / sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p, k_n);
-  SDEO_HIP(hipGetLastError());
-  return 0;
-}
-
-int cfg_lms_noise_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, const float* noise, float cfg_scale,
-                       float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, int64_t n, bool v_prediction,
-                       hipStream_t stream) {
-  SDEO_CHECK(x_next && x && m_c && n > 0, "cfg_lms_noise_step: bad operand");
-  if (int rc = lms_noise_coefs_ok("cfg_lms_noise_step", d, noise, a_t, k_x, k_d, k_p, k_n)) return rc;
-  if (k_n == 0.f)                                // no noise term: the existing kernel, the same launch, the same bits
-    return cfg_lms_step(x_next, d, x, m_c, m_u, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, n, v_prediction, stream);
-  if (v_prediction)
-    hipLaunchKernelGGL(cfg_lms_noise_kernel<true>, grid_for(n), dim3(256), 0, stream, x_next, d, x, m_c, m_u, noise, cfg_scale, sqrtf(a_t),
-                       sqrt_one_minus_at, k_x, k_d, k_p, k_n, n);
-  else
-    hipLaunchKernelGGL(cfg_lms_noise_kernel<false>, grid_for(n), dim3(256), 0, stream, x_next, d, x, m_c, m_u, noise, cfg_scale,
-                       1.0f / sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p, k_n, n);
-  SDEO_HIP(hipGetLastError());
-  return 0;
-}
-
-int cfg_lms_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, float cfg_scale, float a_t,
-                 float sqrt_one_minus_at, float k_x, float k_d, float k_p, int64_t n, bool v_prediction, hipStream_t stream) {
-  SDEO_CHECK(x_next && x && m_c && n > 0, "cfg_lms_step: bad operand");
-  if (int rc = lms_coefs_ok("cfg_lms_step", d, a_t, k_x, k_d, k_p)) return rc;
-  if (v_prediction)
-    hipLaunchKernelGGL(cfg_lms_kernel<true>, grid_for(n), dim3(256), 0, stream, x_next, d, x, m_c, m_u, cfg_scale, sqrtf(a_t),
-                       sqrt_one_minus_at, k_x, k_d, k_p, n);
-  else
-    hipLaunchKernelGGL(cfg_lms_kernel<false>, grid_for(n), dim3(256), 0, stream, x_next, d, x, m_c, m_u, cfg_scale, 1.0f / sqrtf(a_t),
-                       sqrt_one_minus_at, k_x, k_d, k_p, n);
+int cfg_lms_step(const char* who, float* x_next, float* d, const float* x, const float* m_c, const float* m_u, const float* noise,
+                 float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, int64_t n, bool v_prediction,
+                 hipStream_t stream) {
+  SDEO_CHECK(x_next && x && m_c && n > 0, "%s: bad operand", who);
+  if (int rc = cfg_lms_check(who, d, noise, a_t, k_x, k_d, k_p, k_n)) return rc;
+  with_flags(v_prediction, k_n != 0.f, [&](auto v, auto ns) {
+    hipLaunchKernelGGL((cfg_lms_kernel<v.value, ns.value>), grid_for(n), dim3(256), 0, stream, x_next, d, x, m_c, m_u, noise, cfg_scale,
+                       v.value ? sqrtf(a_t) : 1.0f / sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p, k_n, n);
+  });
   SDEO_HIP(hipGetLastError());
   return 0;
 }

@@ -242,22 +242,28 @@ int resize_lanczos4_u8(uint8_t* dst, const uint8_t* src, int h, int w, int c, in
 int resize_area_u8(uint8_t* dst, const uint8_t* src, int h, int w, int c, int dh, int dw, const int* xstart, const int* xidx,
                    const float* xw, const int* ystart, const int* yidx, const float* yw, hipStream_t stream);
 int resize_area_fast_u8(uint8_t* dst, const uint8_t* src, int h, int w, int c, int dh, int dw, hipStream_t stream);
-// classifier-free guidance + DDIM update on NCHW fp32 latents (ddim_hacked.py:192,208-231)
-int cfg_ddim_pair(float* x, float* pred_x0, const f16* eps, int lde, f16* x0, int ld0, int b, int C, int HW, float cfg_scale, float a_t,
-                  float a_prev, float sqrt_one_minus_at, bool v_prediction, hipStream_t stream);
+// classifier-free guidance + DDIM update on NCHW fp32 latents (ddim_hacked.py:192,208-231).  The pair form takes the UNet's fp16 NHWC
+// output, updates x in place and stages the fp16 NHWC latent of the next forward in both halves of x0.  noise (fp32, laid out like x) set:
+// + sigma_t * noise with dir_coef = sqrt(1 - a_prev - sigma_t^2) (`cldm/ddim_hacked.py:227-230`), one more fused multiply-add, bit-equal
+// to cfg_ddim_step with the same noise / sigma_t, and the staged latent is the noisy one; noise null: sigma_t is not read.
+int cfg_ddim_pair(float* x, float* pred_x0, const f16* eps, int lde, const float* noise, float sigma_t, f16* x0, int ld0, int b, int C, int HW,
+                  float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, bool v_prediction, hipStream_t stream);
 int latent_pair_to_nhwc(f16* x0, int ld0, const float* x, int b, int C, int HW, hipStream_t stream);
 int cfg_ddim_step(float* x_prev, float* pred_x0, const float* x, const float* eps_c, const float* eps_u, const float* noise,
                   float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, int64_t n,
                   bool v_prediction, hipStream_t stream);
-// classifier-free guidance + one linear-multistep update x_next = k_x x + k_d D + k_p D_prev (DPM-Solver++(2M)); D is cfg_ddim_step's
-// pred_x0 and replaces D_prev in d.  The pair form is laid out as cfg_ddim_pair.
-int cfg_lms_pair(float* x, float* d, const f16* eps, int lde, f16* x0, int ld0, int b, int C, int HW, float cfg_scale, float a_t,
-                 float sqrt_one_minus_at, float k_x, float k_d, float k_p, bool v_prediction, hipStream_t stream);
-int cfg_lms_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, float cfg_scale, float a_t,
-                 float sqrt_one_minus_at, float k_x, float k_d, float k_p, int64_t n, bool v_prediction, hipStream_t stream);
-// host-side checks of the two pair updates (no device call), for callers that must refuse before they launch anything
-int cfg_ddim_pair_check(const char* who, float a_t, float a_prev);
-int lms_coefs_ok(const char* who, const float* d, float a_t, float k_x, float k_d, float k_p);
+// classifier-free guidance + one linear-multistep update x_next = k_x x + k_d D + k_p D_prev + k_n noise (DPM-Solver++(2M) and its SDE
+// form); D is cfg_ddim_step's pred_x0 and replaces D_prev in d.  k_n == 0 is the deterministic update, whatever the noise pointer (it may
+// be null).  The pair form is laid out as cfg_ddim_pair.  `who` names the flat step in its refusals.
+int cfg_lms_pair(float* x, float* d, const f16* eps, int lde, const float* noise, float k_n, f16* x0, int ld0, int b, int C, int HW,
+                 float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, bool v_prediction, hipStream_t stream);
+int cfg_lms_step(const char* who, float* x_next, float* d, const float* x, const float* m_c, const float* m_u, const float* noise,
+                 float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, int64_t n, bool v_prediction,
+                 hipStream_t stream);
+// host-side checks of the two pair updates (no device call), for callers that must refuse before they launch anything.  sigma_t null:
+// the deterministic DDIM update (noise is not looked at); k_n = 0: the deterministic multistep update.
+int cfg_ddim_check(const char* who, float a_t, float a_prev, const float* noise, const float* sigma_t);
+int cfg_lms_check(const char* who, const float* d, const float* noise, float a_t, float k_x, float k_d, float k_p, float k_n);
 // The sampler's mask / x0 blend (cldm/ddim_hacked.py:154-157) on fp32 NCHW latents [n][C][HW], in place:
 //   x <- mask * (sqrt_a * orig + sqrt_1ma * noise) + (1 - mask) * x,   mask [mask_n][mask_c][HW], mask_n in {1, n}, mask_c in {1, C}
 // rounded operation by operation like the torch expression (no fma contraction).  mask_blend_pair: the same blend as the front of a fused
@@ -269,23 +275,6 @@ int mask_blend(float* x, const float* orig, const float* noise, const float* mas
                int n, int C, int HW, hipStream_t stream);
 int mask_blend_pair(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a,
                     float sqrt_1ma, f16* x0, int ld0, int b, int C, int HW, hipStream_t stream);
-// The stochastic forms of the two updates: one more operand, noise (fp32, laid out like x), and one more fused multiply-add.
-//   cfg_ddim_pair_noise: cfg_ddim_pair + sigma_t * noise with dir_coef = sqrt(1 - a_prev - sigma_t^2) (`cldm/ddim_hacked.py:227-230`),
-//     bit-equal to cfg_ddim_step with the same noise / sigma_t; the staged fp16 latent is the noisy one.
-//   cfg_lms_noise_step / cfg_lms_pair_noise: x_next = k_x x + k_d D + k_p D_prev + k_n noise (DPM-Solver++(2M) SDE); with k_n == 0
-//     cfg_lms_noise_step is cfg_lms_step (noise may then be null).
-//   *_check / *_ok: their coefficient checks alone (host only).
-int cfg_ddim_pair_noise_check(const char* who, const float* noise, float a_t, float a_prev, float sigma_t);
-int cfg_ddim_pair_noise(float* x, float* pred_x0, const f16* eps, int lde, const float* noise, f16* x0, int ld0, int b, int C, int HW,
-                        float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, bool v_prediction,
-                        hipStream_t stream);
-int lms_noise_coefs_ok(const char* who, const float* d, const float* noise, float a_t, float k_x, float k_d, float k_p, float k_n);
-int cfg_lms_pair_noise(float* x, float* d, const f16* eps, int lde, const float* noise, f16* x0, int ld0, int b, int C, int HW,
-                       float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, bool v_prediction,
-                       hipStream_t stream);
-int cfg_lms_noise_step(float* x_next, float* d, const float* x, const float* m_c, const float* m_u, const float* noise, float cfg_scale,
-                       float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, int64_t n, bool v_prediction,
-                       hipStream_t stream);
 // dst = (gen * m + orig * (255 - m) + 127) / 255 in integers: uint8 HWC images [H][W][C], C in 1..4, uint8 mask [H][W]
 int composite_u8(uint8_t* dst, const uint8_t* gen, const uint8_t* orig, const uint8_t* mask, int H, int W, int C, hipStream_t stream);
 

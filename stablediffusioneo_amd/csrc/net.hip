@@ -1968,7 +1968,7 @@ static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float*
   int trow = -1;
   if (int rc = select_time(h, 8 | (table_row << 8), nullptr, who, &trow)) return rc;
   set_scales(h, host_control_scales, only_mid_control);
-  h->x0_staged_for = nullptr;                     // until the update kernel has left the new latent in x0 (step_done)
+  h->x0_staged_for = nullptr;                     // until the update kernel has left the new latent in x0 (fused_step)
   if (blend) {
     if (int rc = mask_blend_pair(x, blend->orig, blend->noise, blend->mask, blend->mask_n, blend->mask_c, blend->sqrt_a, blend->sqrt_1ma,
                                  h->x0.p, h->x0.ld, h->N / 2, h->cfg.in_channels, h->lh * h->lw, s))
@@ -1980,117 +1980,125 @@ static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float*
   return run_step_programs(h, false, true, s, true, (flags & SDEO_STEP_HINT_SHARED) != 0);
 }
 
-// The noise term of a stochastic step (coef: sigma_t of the DDIM step, k_n of the SDE solver's); null, or a null row, for the plain update.
-struct StepNoise {
-  const float* noise;
-  float coef;
+// One fused CFG-pair step as its entry point describes it: which update, its coefficients, the optional noise term and the optional blend.
+struct Step {
+  const char* who;                  // the entry point
+  const char* coef_who;             // who refuses a coefficient: the entry point; for the two plain steps the update's launcher, as ever
+  bool multistep = false;           // x_next = k_x x + k_d D + k_p D_prev (+ k_n noise); else the DDIM update
+  bool stochastic = false;          // an _eta / _sde entry point: cfg_scale and the noise term are checked too, the blend is optional
+  float* aux = nullptr;             // pred_x0 of the DDIM update, d of the multistep update
+  float cfg_scale = 0.f, a_t = 0.f, sqrt_one_minus_at = 0.f;
+  float a_prev = 0.f;               // DDIM
+  float k_x = 0.f, k_d = 0.f, k_p = 0.f;   // multistep
+  const float* noise = nullptr;     // the noise term and its coefficient: sigma_t of the DDIM step, k_n of the SDE solver's
+  float noise_coef = 0.f;
+  bool blended = false;             // the mask / x0 blend in front of the forward
+  StepBlend blend{};
 };
 
-// the update kernel of a fused step wrote the new latent to x and its fp16 copy to x0: the next step on x may pass SDEO_STEP_LATENT_STAGED
-static int step_done(sdeo_handle h, const float* x, int rc) {
+// a stochastic step takes the blend's operands all or none
+static int step_blend_operands(const char* who, const StepBlend& b, int flags) {
+  if (!b.orig) {
+    SDEO_CHECK(!b.noise && !b.mask, "%s: partial blend operands: orig is null, so mask_noise and mask must be null too (the unmasked step)", who);
+    return 0;
+  }
+  SDEO_CHECK(b.noise && b.mask, "%s: partial blend operands: orig is given, so mask_noise and mask are needed too", who);
+  SDEO_CHECK(!(flags & SDEO_STEP_LATENT_STAGED), "%s: SDEO_STEP_LATENT_STAGED together with a mask (the blend changes the latent and always restages it)", who);
+  return 0;
+}
+
+// Every fused step: what the update kernel would refuse after the networks ran is refused here, up front, with what cfg_pair_forward
+// checks before its first launch; then the forward, the update, and the record that x's fp16 copy is staged for the next step on x
+// (the next step may then pass SDEO_STEP_LATENT_STAGED).  A refused step has launched nothing and leaves that record alone.
+static int fused_step(sdeo_handle h, float* x, const Step& st, int table_row, const float* host_control_scales, int only_mid_control,
+                      int flags, hipStream_t s) {
+  if (st.stochastic && st.multistep)
+    SDEO_CHECK(std::isfinite(st.cfg_scale) && std::isfinite(st.a_t) && std::isfinite(st.sqrt_one_minus_at),
+               "%s: non-finite coefficient cfg_scale=%g a_t=%g sqrt_one_minus_at=%g", st.who, st.cfg_scale, st.a_t, st.sqrt_one_minus_at);
+  else if (st.stochastic)
+    SDEO_CHECK(std::isfinite(st.cfg_scale) && std::isfinite(st.sqrt_one_minus_at), "%s: non-finite coefficient cfg_scale=%g sqrt_one_minus_at=%g",
+               st.who, st.cfg_scale, st.sqrt_one_minus_at);
+  if (int rc = st.multistep ? cfg_lms_check(st.coef_who, st.aux, st.noise, st.a_t, st.k_x, st.k_d, st.k_p, st.noise_coef)
+                            : cfg_ddim_check(st.coef_who, st.a_t, st.a_prev, st.noise, st.stochastic ? &st.noise_coef : nullptr))
+    return rc;
+  if (st.stochastic) if (int rc = step_blend_operands(st.who, st.blend, flags)) return rc;
+  if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, st.blended ? &st.blend : nullptr, st.who, s))
+    return rc;
+  const bool v_prediction = (flags & SDEO_STEP_V_PREDICTION) != 0;
+  const int b = h->N / 2, C = h->cfg.out_channels, HW = h->lh * h->lw;
+  const int rc = st.multistep ? cfg_lms_pair(x, st.aux, h->eps16.p, h->eps16.ld, st.noise, st.noise_coef, h->x0.p, h->x0.ld, b, C, HW, st.cfg_scale,
+                                             st.a_t, st.sqrt_one_minus_at, st.k_x, st.k_d, st.k_p, v_prediction, s)
+                              : cfg_ddim_pair(x, st.aux, h->eps16.p, h->eps16.ld, st.noise, st.noise_coef, h->x0.p, h->x0.ld, b, C, HW, st.cfg_scale,
+                                              st.a_t, st.a_prev, st.sqrt_one_minus_at, v_prediction, s);
   if (!rc) h->x0_staged_for = x;
   return rc;
 }
 
-static int ddim_step_impl(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
-                          float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, const StepBlend* blend,
-                          const StepNoise* sn, const char* who, hipStream_t s) {
-  if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, blend, who, s)) return rc;
-  if (sn && sn->noise)
-    return step_done(h, x, cfg_ddim_pair_noise(x, pred_x0, h->eps16.p, h->eps16.ld, sn->noise, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels,
-                                               h->lh * h->lw, cfg_scale, a_t, a_prev, sn->coef, sqrt_one_minus_at,
-                                               (flags & SDEO_STEP_V_PREDICTION) != 0, s));
-  return step_done(h, x, cfg_ddim_pair(x, pred_x0, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw,
-                                       cfg_scale, a_t, a_prev, sqrt_one_minus_at, (flags & SDEO_STEP_V_PREDICTION) != 0, s));
+static Step ddim_update(const char* who, float* pred_x0, float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at) {
+  Step st{who, who};
+  st.aux = pred_x0, st.cfg_scale = cfg_scale, st.a_t = a_t, st.a_prev = a_prev, st.sqrt_one_minus_at = sqrt_one_minus_at;
+  return st;
 }
 
-static int dpmpp_2m_step_impl(sdeo_handle h, float* x, float* d, int table_row, float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x,
-                              float k_d, float k_p, const float* host_control_scales, int only_mid_control, int flags, const StepBlend* blend,
-                              const StepNoise* sn, const char* who, hipStream_t s) {
-  SDEO_CHECK(d || k_p == 0.f, "%s: k_p=%g needs the previous data prediction, but d is null", who, k_p);
-  if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, blend, who, s)) return rc;
-  if (sn && sn->coef != 0.f)                     // k_n == 0: the existing kernel, whatever the noise pointer
-    return step_done(h, x, cfg_lms_pair_noise(x, d, h->eps16.p, h->eps16.ld, sn->noise, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels,
-                                              h->lh * h->lw, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, sn->coef,
-                                              (flags & SDEO_STEP_V_PREDICTION) != 0, s));
-  return step_done(h, x, cfg_lms_pair(x, d, h->eps16.p, h->eps16.ld, h->x0.p, h->x0.ld, h->N / 2, h->cfg.out_channels, h->lh * h->lw, cfg_scale,
-                                      a_t, sqrt_one_minus_at, k_x, k_d, k_p, (flags & SDEO_STEP_V_PREDICTION) != 0, s));
+static Step multistep_update(const char* who, float* d, float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p) {
+  Step st{who, who};
+  st.multistep = true;
+  st.aux = d, st.cfg_scale = cfg_scale, st.a_t = a_t, st.sqrt_one_minus_at = sqrt_one_minus_at, st.k_x = k_x, st.k_d = k_d, st.k_p = k_p;
+  return st;
 }
 
 int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
                    float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
-  return ddim_step_impl(h, x, pred_x0, table_row, cfg_scale, a_t, a_prev, sqrt_one_minus_at, host_control_scales, only_mid_control, flags,
-                        nullptr, nullptr, "sdeo_ddim_step", S(stream));
+  Step st = ddim_update("sdeo_ddim_step", pred_x0, cfg_scale, a_t, a_prev, sqrt_one_minus_at);
+  st.coef_who = "cfg_ddim_pair";
+  return fused_step(h, x, st, table_row, host_control_scales, only_mid_control, flags, S(stream));
 }
 
 int sdeo_dpmpp_2m_step(sdeo_handle h, float* x, float* d, int table_row, float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x,
                        float k_d, float k_p, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
-  return dpmpp_2m_step_impl(h, x, d, table_row, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, host_control_scales, only_mid_control,
-                            flags, nullptr, nullptr, "sdeo_dpmpp_2m_step", S(stream));
+  Step st = multistep_update("sdeo_dpmpp_2m_step", d, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p);
+  SDEO_CHECK(d || k_p == 0.f, "%s: k_p=%g needs the previous data prediction, but d is null", st.who, k_p);   // this one in its own name
+  st.coef_who = "cfg_lms_pair";
+  return fused_step(h, x, st, table_row, host_control_scales, only_mid_control, flags, S(stream));
 }
 
-// The masked steps change x before the networks run, so what the update kernel would refuse after them is refused here, up front.
 int sdeo_ddim_step_masked(sdeo_handle h, float* x, float* pred_x0, const float* orig, const float* noise, const float* mask, int mask_n,
                           int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row, float cfg_scale, float a_t, float a_prev,
                           float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream) {
-  const char* who = "sdeo_ddim_step_masked";
-  if (int rc = cfg_ddim_pair_check(who, a_t, a_prev)) return rc;
-  const StepBlend blend{orig, noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
-  return ddim_step_impl(h, x, pred_x0, table_row, cfg_scale, a_t, a_prev, sqrt_one_minus_at, host_control_scales, only_mid_control, flags,
-                        &blend, nullptr, who, S(stream));
+  Step st = ddim_update("sdeo_ddim_step_masked", pred_x0, cfg_scale, a_t, a_prev, sqrt_one_minus_at);
+  st.blended = true, st.blend = {orig, noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
+  return fused_step(h, x, st, table_row, host_control_scales, only_mid_control, flags, S(stream));
 }
 
 int sdeo_dpmpp_2m_step_masked(sdeo_handle h, float* x, float* d, const float* orig, const float* noise, const float* mask, int mask_n,
                               int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row, float cfg_scale, float a_t,
                               float sqrt_one_minus_at, float k_x, float k_d, float k_p, const float* host_control_scales,
                               int only_mid_control, int flags, void* stream) {
-  const char* who = "sdeo_dpmpp_2m_step_masked";
-  if (int rc = lms_coefs_ok(who, d, a_t, k_x, k_d, k_p)) return rc;
-  const StepBlend blend{orig, noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
-  return dpmpp_2m_step_impl(h, x, d, table_row, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, host_control_scales, only_mid_control,
-                            flags, &blend, nullptr, who, S(stream));
+  Step st = multistep_update("sdeo_dpmpp_2m_step_masked", d, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p);
+  st.blended = true, st.blend = {orig, noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
+  return fused_step(h, x, st, table_row, host_control_scales, only_mid_control, flags, S(stream));
 }
 
-// The stochastic steps.  Like the masked steps they refuse up front what their update kernel would refuse after the networks ran, and
-// what is theirs alone: a coefficient without its noise row, a partial set of blend operands, the staged flag together with a blend.
-static int step_blend_operands(const char* who, const float* orig, const float* mask_noise, const float* mask, int flags) {
-  if (!orig) {
-    SDEO_CHECK(!mask_noise && !mask, "%s: partial blend operands: orig is null, so mask_noise and mask must be null too (the unmasked step)", who);
-    return 0;
-  }
-  SDEO_CHECK(mask_noise && mask, "%s: partial blend operands: orig is given, so mask_noise and mask are needed too", who);
-  SDEO_CHECK(!(flags & SDEO_STEP_LATENT_STAGED), "%s: SDEO_STEP_LATENT_STAGED together with a mask (the blend changes the latent and always restages it)", who);
-  return 0;
-}
-
+// The stochastic steps also refuse what is theirs alone: a coefficient without its noise row, a partial set of blend operands, the
+// staged flag together with a blend.
 int sdeo_ddim_step_eta(sdeo_handle h, float* x, float* pred_x0, const float* noise, float sigma_t, const float* orig,
                        const float* mask_noise, const float* mask, int mask_n, int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row,
                        float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, const float* host_control_scales,
                        int only_mid_control, int flags, void* stream) {
-  const char* who = "sdeo_ddim_step_eta";
-  SDEO_CHECK(std::isfinite(cfg_scale) && std::isfinite(sqrt_one_minus_at), "%s: non-finite coefficient cfg_scale=%g sqrt_one_minus_at=%g", who,
-             cfg_scale, sqrt_one_minus_at);
-  if (int rc = cfg_ddim_pair_noise_check(who, noise, a_t, a_prev, sigma_t)) return rc;
-  if (int rc = step_blend_operands(who, orig, mask_noise, mask, flags)) return rc;
-  const StepBlend blend{orig, mask_noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
-  const StepNoise sn{noise, sigma_t};
-  return ddim_step_impl(h, x, pred_x0, table_row, cfg_scale, a_t, a_prev, sqrt_one_minus_at, host_control_scales, only_mid_control, flags,
-                        orig ? &blend : nullptr, &sn, who, S(stream));
+  Step st = ddim_update("sdeo_ddim_step_eta", pred_x0, cfg_scale, a_t, a_prev, sqrt_one_minus_at);
+  st.stochastic = true, st.noise = noise, st.noise_coef = sigma_t;
+  st.blended = orig != nullptr, st.blend = {orig, mask_noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
+  return fused_step(h, x, st, table_row, host_control_scales, only_mid_control, flags, S(stream));
 }
 
 int sdeo_dpmpp_2m_sde_step(sdeo_handle h, float* x, float* d, const float* noise, const float* orig, const float* mask_noise,
                            const float* mask, int mask_n, int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row, float cfg_scale,
                            float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, const float* host_control_scales,
                            int only_mid_control, int flags, void* stream) {
-  const char* who = "sdeo_dpmpp_2m_sde_step";
-  SDEO_CHECK(std::isfinite(cfg_scale) && std::isfinite(a_t) && std::isfinite(sqrt_one_minus_at),
-             "%s: non-finite coefficient cfg_scale=%g a_t=%g sqrt_one_minus_at=%g", who, cfg_scale, a_t, sqrt_one_minus_at);
-  if (int rc = lms_noise_coefs_ok(who, d, noise, a_t, k_x, k_d, k_p, k_n)) return rc;
-  if (int rc = step_blend_operands(who, orig, mask_noise, mask, flags)) return rc;
-  const StepBlend blend{orig, mask_noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
-  const StepNoise sn{noise, k_n};
-  return dpmpp_2m_step_impl(h, x, d, table_row, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, host_control_scales, only_mid_control,
-                            flags, orig ? &blend : nullptr, &sn, who, S(stream));
+  Step st = multistep_update("sdeo_dpmpp_2m_sde_step", d, cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p);
+  st.stochastic = true, st.noise = noise, st.noise_coef = k_n;
+  st.blended = orig != nullptr, st.blend = {orig, mask_noise, mask, mask_n, mask_c, sqrt_a, sqrt_one_minus_a};
+  return fused_step(h, x, st, table_row, host_control_scales, only_mid_control, flags, S(stream));
 }
 
 int sdeo_vae_decode(sdeo_handle h, const float* z, int n, float* images, uint8_t* images_u8, void* stream) {

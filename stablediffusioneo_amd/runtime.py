@@ -393,18 +393,27 @@ class SdeoRuntime(_HandleRuntime):
         self._table_key = (self.generation, tuple(ts))      # whose schedule the table holds (captured graphs read it by address)
         return len(ts)
 
+    def _step_tensors(self, x, aux):
+        """what the six fused steps ask of the latent and of their second state tensor (pred_x0 / d, optional)"""
+        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
+        assert aux is None or (aux.is_contiguous() and aux.dtype == torch.float32 and aux.shape == x.shape)
+
+    @staticmethod
+    def _step_flags(staged, hint_shared, v_prediction, flags=0):
+        """the SDEO_STEP_* word of a fused step (flags: extra bits as they are)"""
+        return (flags | (STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)
+                | (STEP_V_PREDICTION if v_prediction else 0))
+
     def ddim_step(self, x, pred_x0, row: int, cfg_scale: float, a_t: float, a_prev: float, sqrt_one_minus_at: float, scales=None,
                   only_mid_control: bool = False, staged: bool = False, hint_shared: bool = False, v_prediction: bool = False):
         """`sdeo_ddim_step`: one eta = 0 DDIM step of the CFG pair; x (b,4,h,w) fp32 contiguous is updated in place.
         hint_shared: the cached hints of the unconditional half are those of the conditional half (SDEO_STEP_HINT_SHARED), so the
         ControlNet too computes what precedes its first cross-attention once.  v_prediction: the model predicts v
         (SDEO_STEP_V_PREDICTION)."""
-        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
-        assert pred_x0 is None or (pred_x0.is_contiguous() and pred_x0.dtype == torch.float32 and pred_x0.shape == x.shape)
+        self._step_tensors(x, pred_x0)
+        flags = self._step_flags(staged, hint_shared, v_prediction)
         check(self.lib.sdeo_ddim_step(self.handle, ptr(x), ptr(pred_x0), int(row), cfg_scale, a_t, a_prev, sqrt_one_minus_at,
-                                      self._scales(scales), int(only_mid_control),
-                                      (STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)
-                                      | (STEP_V_PREDICTION if v_prediction else 0), cur_stream()), "ddim_step")
+                                      self._scales(scales), int(only_mid_control), flags, cur_stream()), "ddim_step")
         return x
 
     def dpmpp_2m_step(self, x, d, row: int, cfg_scale: float, a_t: float, sqrt_one_minus_at: float, k_x: float, k_d: float, k_p: float,
@@ -412,12 +421,10 @@ class SdeoRuntime(_HandleRuntime):
                       v_prediction: bool = False):
         """`sdeo_dpmpp_2m_step`: one DPM-Solver++(2M) step of the CFG pair, as `ddim_step` with the linear-multistep update
         x <- k_x x + k_d D + k_p d, d <- D; x and d (b,4,h,w) fp32 contiguous are updated in place (d may be None when k_p == 0)."""
-        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
-        assert d is None or (d.is_contiguous() and d.dtype == torch.float32 and d.shape == x.shape)
+        self._step_tensors(x, d)
+        flags = self._step_flags(staged, hint_shared, v_prediction)
         check(self.lib.sdeo_dpmpp_2m_step(self.handle, ptr(x), ptr(d), int(row), cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p,
-                                          self._scales(scales), int(only_mid_control),
-                                          (STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)
-                                          | (STEP_V_PREDICTION if v_prediction else 0), cur_stream()), "dpmpp_2m_step")
+                                          self._scales(scales), int(only_mid_control), flags, cur_stream()), "dpmpp_2m_step")
         return x
 
     def _blend_args(self, x, orig, noise, mask):
@@ -435,26 +442,22 @@ class SdeoRuntime(_HandleRuntime):
         """`sdeo_ddim_step_masked`: x <- mask * (sqrt_a orig + sqrt_one_minus_a noise) + (1 - mask) x, then `ddim_step` on it, both in
         place; bit-identical to `ops.mask_blend` followed by the unstaged `ddim_step`.  There is no `staged`: the blend always restages
         (flags: extra SDEO_STEP_* bits as they are, for the tests of what the library refuses)."""
-        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
-        assert pred_x0 is None or (pred_x0.is_contiguous() and pred_x0.dtype == torch.float32 and pred_x0.shape == x.shape)
+        self._step_tensors(x, pred_x0)
+        flags = self._step_flags(False, hint_shared, v_prediction, flags)
         check(self.lib.sdeo_ddim_step_masked(self.handle, ptr(x), ptr(pred_x0), *self._blend_args(x, orig, noise, mask), sqrt_a,
                                              sqrt_one_minus_a, int(row), cfg_scale, a_t, a_prev, sqrt_one_minus_at, self._scales(scales),
-                                             int(only_mid_control),
-                                             flags | (STEP_HINT_SHARED if hint_shared else 0) | (STEP_V_PREDICTION if v_prediction else 0),
-                                             cur_stream()), "ddim_step_masked")
+                                             int(only_mid_control), flags, cur_stream()), "ddim_step_masked")
         return x
 
     def dpmpp_2m_step_masked(self, x, d, orig, noise, mask, sqrt_a: float, sqrt_one_minus_a: float, row: int, cfg_scale: float, a_t: float,
                              sqrt_one_minus_at: float, k_x: float, k_d: float, k_p: float, scales=None, only_mid_control: bool = False,
                              hint_shared: bool = False, v_prediction: bool = False, flags: int = 0):
         """`sdeo_dpmpp_2m_step_masked`: the blend of `ddim_step_masked`, then `dpmpp_2m_step` on the blended latent"""
-        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
-        assert d is None or (d.is_contiguous() and d.dtype == torch.float32 and d.shape == x.shape)
+        self._step_tensors(x, d)
+        flags = self._step_flags(False, hint_shared, v_prediction, flags)
         check(self.lib.sdeo_dpmpp_2m_step_masked(self.handle, ptr(x), ptr(d), *self._blend_args(x, orig, noise, mask), sqrt_a,
                                                  sqrt_one_minus_a, int(row), cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p,
-                                                 self._scales(scales), int(only_mid_control),
-                                                 flags | (STEP_HINT_SHARED if hint_shared else 0) | (STEP_V_PREDICTION if v_prediction else 0),
-                                                 cur_stream()), "dpmpp_2m_step_masked")
+                                                 self._scales(scales), int(only_mid_control), flags, cur_stream()), "dpmpp_2m_step_masked")
         return x
 
     def _eta_args(self, x, noise, orig, mask_noise, mask):
@@ -477,13 +480,12 @@ class SdeoRuntime(_HandleRuntime):
         sigma_t^2)), in place; noise (b,4,h,w) fp32 is read by address, so a captured call sees what the row holds at replay.  With orig /
         mask_noise / mask / sqrt_a / sqrt_one_minus_a the blend of `ddim_step_masked` runs in front (no `staged` then).  Bit-identical to
         `apply_model` on [x; x] + `ops.cfg_ddim_step` with the same noise and sigma_t."""
-        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
-        assert pred_x0 is None or (pred_x0.is_contiguous() and pred_x0.dtype == torch.float32 and pred_x0.shape == x.shape)
+        self._step_tensors(x, pred_x0)
         pn, po, pm, pk, mn, mc = self._eta_args(x, noise, orig, mask_noise, mask)
+        flags = self._step_flags(staged, hint_shared, v_prediction, flags)
         check(self.lib.sdeo_ddim_step_eta(self.handle, ptr(x), ptr(pred_x0), pn, sigma_t, po, pm, pk, mn, mc, sqrt_a, sqrt_one_minus_a,
                                           int(row), cfg_scale, a_t, a_prev, sqrt_one_minus_at, self._scales(scales), int(only_mid_control),
-                                          flags | (STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)
-                                          | (STEP_V_PREDICTION if v_prediction else 0), cur_stream()), "ddim_step_eta")
+                                          flags, cur_stream()), "ddim_step_eta")
         return x
 
     def dpmpp_2m_sde_step(self, x, d, noise, row: int, cfg_scale: float, a_t: float, sqrt_one_minus_at: float, k_x: float, k_d: float,
@@ -492,14 +494,12 @@ class SdeoRuntime(_HandleRuntime):
                           sqrt_one_minus_a: float = 0.0, flags: int = 0):
         """`sdeo_dpmpp_2m_sde_step`: `dpmpp_2m_step` with the SDE solver's fourth term, x <- k_x x + k_d D + k_p d + k_n noise, d <- D;
         the blend operands as in `ddim_step_eta`"""
-        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
-        assert d is None or (d.is_contiguous() and d.dtype == torch.float32 and d.shape == x.shape)
+        self._step_tensors(x, d)
         pn, po, pm, pk, mn, mc = self._eta_args(x, noise, orig, mask_noise, mask)
+        flags = self._step_flags(staged, hint_shared, v_prediction, flags)
         check(self.lib.sdeo_dpmpp_2m_sde_step(self.handle, ptr(x), ptr(d), pn, po, pm, pk, mn, mc, sqrt_a, sqrt_one_minus_a, int(row),
                                               cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, k_n, self._scales(scales),
-                                              int(only_mid_control),
-                                              flags | (STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)
-                                              | (STEP_V_PREDICTION if v_prediction else 0), cur_stream()), "dpmpp_2m_sde_step")
+                                              int(only_mid_control), flags, cur_stream()), "dpmpp_2m_sde_step")
         return x
 
     def vae_decode(self, z, want_u8: bool = False):

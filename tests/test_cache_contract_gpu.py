@@ -407,6 +407,28 @@ def test_staged_step_on_another_tensor_is_refused(handles):
     assert_right({"x": xa, "pred": pred}, reference("tiny", rr, I, "staged", {"hint": "A", "hint1": "A", "ctx_u": "A", "ctx_c": "A", "tab": "A"}, v))
 
 
+def test_plain_step_refuses_its_coefficients_before_it_touches_anything(handles):
+    """the two plain steps refuse a bad coefficient like the other four: before the first device call, the staged-latent record kept"""
+    from stablediffusioneo_amd._lib import SdeoError
+    rt, rr, I, v = handles("tiny")
+    fill(rt, I)
+    xa = I.x.clone()
+    pred = _sent((1, 4, H, W), I)
+    rt.ddim_step(xa, None, 0, CFG, *STEP0, float(np.sqrt(1.0 - STEP0[0])), SCALES)
+    torch.cuda.synchronize()
+    staged_x = xa.clone()
+    refused = [("invalid schedule", lambda: rt.ddim_step(xa, pred, ROW, CFG, 0.0, A_P, S1M, SCALES)),
+               ("a_t", lambda: rt.dpmpp_2m_step(xa, pred, ROW, CFG, 0.0, S1M, 1.0, 0.5, 0.0, SCALES)),
+               ("non-finite", lambda: rt.dpmpp_2m_step(xa, pred, ROW, CFG, A_T, S1M, float("nan"), 0.5, 0.0, SCALES))]
+    for message, call in refused:
+        with pytest.raises(SdeoError, match=message):
+            call()
+        torch.cuda.synchronize()
+        assert torch.equal(xa, staged_x) and bool((pred == SENTINEL).all()), message
+    rt.ddim_step(xa, pred, ROW, CFG, A_T, A_P, S1M, SCALES, staged=True)                         # the refusals cleared nothing: xa is still staged
+    assert_right({"x": xa, "pred": pred}, reference("tiny", rr, I, "staged", {"hint": "A", "hint1": "A", "ctx_u": "A", "ctx_c": "A", "tab": "A"}, v))
+
+
 def test_mixed_prompt_is_refused_until_one_full_apply_model(handles):
     """sdeo_controlnet_forward given a new context refreshes the control networks' K / V only: a cached read of both sides would mix two
     prompts.  One sdeo_apply_model given the context makes the cached read legal again, with that context on both sides."""
