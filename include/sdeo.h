@@ -306,6 +306,10 @@ int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w);
  *     step core given six descriptions, and refuse up front what their update kernel would refuse after the networks ran: an invalid
  *     schedule (a_t <= 0, 1 - a_prev < 0), a non-finite k_x / k_d / k_p, d null with k_p != 0, next to the operand, flag, cache and table
  *     checks.  A step refused for a coefficient has launched nothing and leaves the staged-latent record as it was.
+ *   - SDEO_STEP_UNGUIDED changes what a step reads, not whom it asks: the hint features and context K / V are those of the configured n
+ *     images (filled by sdeo_apply_model on those n), the table rows are the same rows, and the staged latent is recorded for the x it
+ *     updated, n latents of it, together with the kind of step: a pair step stages n / 2 latents twice, an unguided one n latents
+ *     once, so SDEO_STEP_LATENT_STAGED after a step of the other kind is refused like a staged step on another x.
  *   - sdeo_set_control_hint, sdeo_set_control_scales, sdeo_set_timestep_table, sdeo_vae_decode and sdeo_vae_encode leave every item
  *     other than the one they fill as it is (the arena keeps the persistent tensors apart from the VAE programs). */
 
@@ -352,12 +356,23 @@ int sdeo_set_timestep_table(sdeo_handle h, const int64_t* host_timesteps, int co
 #define SDEO_STEP_HINT_SHARED 32
 /* the model predicts v: the update is that of sdeo_cfg_ddim_step_v.  Without the flag nothing about the step changes. */
 #define SDEO_STEP_V_PREDICTION 64
+/* No guidance: the un-paired member of all six fused steps (the `unconditional_conditioning is None or scale == 1` branch of
+ * cldm/ddim_hacked.py:188-189).  x, pred_x0 / d, noise, orig and mask_noise are [n][4][h][w] with n the CONFIGURED count, any n >= 1;
+ * mask_n is in {1, n}.  The forward runs on x once per image (the plain programs: no shared prefix applies), the model output of image
+ * i is used as it is, and cfg_scale is neither read nor checked.  Bit-identical to sdeo_apply_model on x followed by the matching
+ * unfused call with a null eps_u / m_u (sdeo_cfg_ddim_step(_v), sdeo_cfg_dpmpp_2m_step, sdeo_cfg_dpmpp_2m_sde_step); with blend operands
+ * to sdeo_mask_blend followed by the unmasked call; staged to unstaged.  SDEO_STEP_HINT_SHARED together with it is refused (there is no
+ * second half); SDEO_STEP_LATENT_STAGED, SDEO_STEP_V_PREDICTION, the blend operands, the cache contract and the table checks keep their
+ * meaning, and every refusal precedes the first device call.  Without the flag every step does what it did, the refusal of an odd n
+ * included.  Capturable. */
+#define SDEO_STEP_UNGUIDED 128
 int sdeo_ddim_step(sdeo_handle h, float* x, float* pred_x0, int table_row, float cfg_scale, float a_t, float a_prev,
                    float sqrt_one_minus_at, const float* host_control_scales, int only_mid_control, int flags, void* stream);
 
 /* the fused CFG-pair step, as sdeo_ddim_step with that update: same flags, same caches, same table rows; capturable.
  * x <- k_x x + k_d D + k_p d(on entry), d <- D (see sdeo_cfg_dpmpp_2m_step); the caller owns d [n/2][4][h][w] fp32 (NULL only when
- * k_p == 0).  Bit-identical to sdeo_apply_model on [x; x] followed by sdeo_cfg_dpmpp_2m_step. */
+ * k_p == 0).  Bit-identical to sdeo_apply_model on [x; x] followed by sdeo_cfg_dpmpp_2m_step.  With SDEO_STEP_UNGUIDED: x and d are
+ * [n][4][h][w], and the reference is sdeo_apply_model on x followed by sdeo_cfg_dpmpp_2m_step with m_u == NULL. */
 int sdeo_dpmpp_2m_step(sdeo_handle h, float* x, float* d, int table_row, float cfg_scale, float a_t, float sqrt_one_minus_at,
                        float k_x, float k_d, float k_p, const float* host_control_scales, int only_mid_control, int flags, void* stream);
 
@@ -373,6 +388,8 @@ int sdeo_dpmpp_2m_step(sdeo_handle h, float* x, float* d, int table_row, float c
  *   - every argument check happens before the first device call, each with its own message: a null x / orig / noise / mask, mask_n or
  *     mask_c outside the allowed values, an unconfigured handle, an odd configured n, a table row outside the table, an invalid
  *     schedule (what the update kernel would refuse), d null with k_p != 0.  A refused call leaves x, pred_x0 and d untouched;
+ *   - with SDEO_STEP_UNGUIDED every [n/2] above reads [n] (x, pred_x0 / d, orig, noise; mask_n in {1, n}), an odd n is accepted, and the
+ *     blend runs in the launch that stages the fp16 copy of x, each image once;
  *   - capturable. */
 int sdeo_ddim_step_masked(sdeo_handle h, float* x, float* pred_x0, const float* orig, const float* noise, const float* mask, int mask_n,
                           int mask_c, float sqrt_a, float sqrt_one_minus_a, int table_row, float cfg_scale, float a_t, float a_prev,
@@ -400,6 +417,8 @@ int sdeo_dpmpp_2m_step_masked(sdeo_handle h, float* x, float* d, const float* or
  *   - refused before the first device call, each with its own message, x / pred_x0 / d untouched: a null noise with sigma_t != 0 or
  *     k_n != 0; 1 - a_prev - sigma_t^2 < 0; a non-finite coefficient; a partial set of blend operands; SDEO_STEP_LATENT_STAGED together
  *     with a mask; and everything the unmasked and the masked steps refuse;
+ *   - with SDEO_STEP_UNGUIDED noise, orig and mask_noise are [n][4][h][w] like x, cfg_scale is not among the coefficients checked, and the
+ *     unfused calls of the first item are given eps_u / m_u == NULL after sdeo_apply_model on x;
  *   - capturable. */
 int sdeo_ddim_step_eta(sdeo_handle h, float* x, float* pred_x0, const float* noise, float sigma_t,
                        const float* orig, const float* mask_noise, const float* mask, int mask_n, int mask_c, float sqrt_a,

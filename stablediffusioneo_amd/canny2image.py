@@ -53,7 +53,11 @@ class hackathon():
         the same rules as "clip".  vae_encoder=True also builds the VAE encoder, which `process(init_image=...)` (img2img) needs.
         sampler: "ddim" (the reference's DDIMSampler), "dpmpp_2m" (DPM-Solver++(2M) on a log-SNR grid, `cldm/dpm_solver.py`: a
         deterministic second-order solver meant for about half of DDIM's step count; `process(..., eta != 0)` raises with it) or
-        "dpmpp_2m_sde" (its stochastic form, DPMSolverSDESampler: `process(..., eta)` with eta in [0, 1] scales the noise each step adds).
+        "dpmpp_2m_sde" (its stochastic form, DPMSolverSDESampler: `process(..., eta)` with eta in [0, 1] scales the noise each step adds),
+        or "lcm" (the Latent-Consistency multistep sampler, `cldm/lcm.py`, for weights with an LCM-LoRA among `loras`: it wants 2-8 steps
+        and a scale of 1-2; `process(..., eta != 0)` raises with it).  LCM-LoRA has no guidance embedding, so the scale is plain
+        classifier-free guidance and 1.0 drops the unconditional branch; full LCM checkpoints with `time_embedding.cond_proj` are not
+        supported and are refused by the loader's unknown-key report.
         loras: kohya-ss LoRA / LoCon adapters merged into the weights at start-up, [(path or dict, unet_scale[, te_scale]), ...]
         (`set_loras`); te_scale needs the "clip" / "openclip" text encoder."""
         self.apply_canny = apply_canny or _default_canny()
@@ -77,8 +81,8 @@ class hackathon():
     def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim", extra_control=(), loras=()):
         """text encoder, ControlLDM and sampler of `initialize` (shared with hed2image).  extra_control: the weights of each extra
         control network (multi2image): a checkpoint path, a state dict with `control_model.*` names or "synthetic:<seed>"."""
-        if sampler not in ("ddim", "dpmpp_2m", "dpmpp_2m_sde"):
-            raise ValueError(f'sampler {sampler!r}: "ddim", "dpmpp_2m" or "dpmpp_2m_sde"')
+        if sampler not in ("ddim", "dpmpp_2m", "dpmpp_2m_sde", "lcm"):
+            raise ValueError(f'sampler {sampler!r}: "ddim", "dpmpp_2m", "dpmpp_2m_sde" or "lcm"')
         if isinstance(text_encoder, str) and text_encoder.split(":")[0] in ("clip", "openclip"):
             from .ldm.modules.encoders.modules import FrozenCLIPEmbedder, FrozenOpenCLIPEmbedder
             kind = text_encoder.split(":")[0]
@@ -116,6 +120,9 @@ class hackathon():
         elif sampler == "dpmpp_2m_sde":
             from .cldm.dpm_solver import DPMSolverSDESampler
             self.ddim_sampler = DPMSolverSDESampler(self.model)
+        elif sampler == "lcm":
+            from .cldm.lcm import LCMSampler
+            self.ddim_sampler = LCMSampler(self.model)
         else:
             self.ddim_sampler = DDIMSampler(self.model)
         if loras:
@@ -154,7 +161,9 @@ class hackathon():
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, ddim_steps, guess_mode,
                 strength, scale, seed, eta, low_threshold, high_threshold, x_T=None, init_image=None, denoise_strength=0.75, mask_image=None):
-        """init_image (HxWx3 uint8, optional): img2img with upstream `scripts/img2img.py` semantics -- the image is resized like the
+        """scale == 1.0 is no guidance (`cldm/ddim_hacked.py:188-189`): the unconditional branch is not run, and with any sampler the
+        loop's captured steps are the un-paired ones (SDEO_STEP_UNGUIDED), one forward per image and step.
+        init_image (HxWx3 uint8, optional): img2img with upstream `scripts/img2img.py` semantics -- the image is resized like the
         input, encoded (posterior sample), noised to t_enc = int(denoise_strength * ddim_steps) by stochastic_encode and denoised from
         there by DDIMSampler.decode; the Canny hint still comes from `input_image`.  Needs initialize(..., vae_encoder=True).
         mask_image (HxW or HxWx{1,3} uint8, optional; needs init_image and the encoder): inpainting -- white repaints, black keeps the

@@ -334,13 +334,20 @@ class DDIMSampler(object):
         return (uc is not None and scale != 1. and hasattr(m, "rt") and isinstance(c, dict) and isinstance(uc, dict)
                 and c.get("c_concat") is not None and uc.get("c_concat") is not None)
 
+    def _unguided(self, c, uc, scale):
+        """no guidance (`cldm/ddim_hacked.py:188-189`) on a model with a runtime and a ControlNet hint: the loop graph's steps are then
+        the un-paired fused steps (SDEO_STEP_UNGUIDED) on the b latents.  Guess mode (uc given, scale != 1, no hint on uc) is neither
+        this nor `_fusable`."""
+        return ((uc is None or scale == 1.) and hasattr(self.model, "rt") and isinstance(c, dict) and c.get("c_concat") is not None)
+
     def _loop_graph_ok(self, img, c, uc, scale, total_steps, temperature=1., noise_dropout=0.):
-        """Steps 2..S as one graph: only the plain canny2image loop qualifies -- fused CFG pair, eps- or v-parameterisation, no
+        """Steps 2..S as one graph: only the plain canny2image loop qualifies -- fused CFG pair or no guidance at all, eps- or v-parameterisation, no
         callbacks / correctors, a mask only when `mask_graph_ok` (the callers check those).  With eta > 0 the steps read their noise
         from the sampler's rows (`step_noise_rows`), which hold plain torch.randn draws: a temperature other than 1 or a noise dropout
         keep the per-step loop.  So does a schedule longer than the library's timestep table (MAX_TABLE_STEPS rows): the captured steps
         read their time embedding from it, the per-step loop needs none."""
-        if not (USE_GRAPH and USE_LOOP_GRAPH and img.is_cuda and 2 <= total_steps <= MAX_TABLE_STEPS and self._fusable(c, uc, scale)):
+        if not (USE_GRAPH and USE_LOOP_GRAPH and img.is_cuda and 2 <= total_steps <= MAX_TABLE_STEPS
+                and (self._fusable(c, uc, scale) or self._unguided(c, uc, scale))):
             return False
         if self.model.parameterization not in ("eps", "v"):
             return False
@@ -353,17 +360,19 @@ class DDIMSampler(object):
         (apply_model on [x; x] + CFG + DDIM update, x updated in place in the fixed buffer).  With a mask (`:154-157`) the captured steps
         are sdeo_ddim_step_masked calls.  With eta > 0 (`:227-230`) loop step i adds sigma[S - 1 - i] * noise: the captured steps with
         sigma_t != 0 are sdeo_ddim_step_eta calls that read their noise row by address; a step with sigma_t == 0 captures the plain step,
-        and the eta = 0 loop captures exactly what it always did."""
+        and the eta = 0 loop captures exactly what it always did.  Without guidance (`_unguided`) the same calls carry unguided=True: the
+        eager step 1 is the single apply_model on the b latents, which fills the caches at n = b."""
         m, rt = self.model, self.model.rt
         time_range = tuple(int(t) for t in time_range)
         sig = self._sigmas_host
         live = [not self._sigmas_all_zero and float(sig[total_steps - 1 - i]) != 0. for i in range(total_steps)]
         # cond and uncond were given the SAME control tensors (canny2image / hed2image outside guess mode): the hint features of the
         # two halves of the batch are equal, which lets the ControlNet share what precedes its first cross-attention (baked in at capture)
-        hint_shared = self._ident(c["c_concat"]) == self._ident(uc["c_concat"])
+        unguided = self._unguided(c, uc, scale)
+        hint_shared = not unguided and self._ident(c["c_concat"]) == self._ident(uc["c_concat"])
         shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), m.scales_key(), bool(m.only_mid_control),
                      getattr(self, "_schedule_key", None), LOOP_GRAPH_STEPS, hint_shared, m.parameterization,
-                     None if mask is None else tuple(mask.shape))
+                     None if mask is None else tuple(mask.shape), unguided)
         a_t, a_p, s1m = self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sqrt_one_minus_alphas
 
         def first_step(img, pred):
@@ -374,7 +383,7 @@ class DDIMSampler(object):
             index = total_steps - i - 1
             x, pred = self._loop_x, self._loop_pred
             tail = (i, scale, float(a_t[index]), float(a_p[index]), float(s1m[index]), m.net0_scales(), m.only_mid_control)
-            kw = dict(hint_shared=hint_shared, v_prediction=m.parameterization == "v")
+            kw = dict(hint_shared=hint_shared, v_prediction=m.parameterization == "v", unguided=unguided)
             if noise_row is not None:
                 rt.ddim_step_eta(x, pred, noise_row, float(sig[index]), *tail, staged=staged, **kw, **(blend or {}))
             elif blend is None:

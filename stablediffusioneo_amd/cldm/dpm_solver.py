@@ -12,7 +12,8 @@ The host folds all of it into three fp64 coefficients per step, x_next = k_x x +
 
 The loop is DDIM's (`ddim_hacked.captured_loop`): step 1 runs eagerly (it fills the runtime's hint / context caches), steps 2..S are
 replayed from a captured graph with the per-step coefficients baked in (with a mask: the masked steps, `ddim_hacked.mask_operands`); what
-does not qualify (callbacks, a replaced q_sample, no ControlNet hint on one half, scale == 1, a model without a runtime) runs one step at a time.  The switches are ddim_hacked's (SDEO_GRAPH,
+does not qualify (callbacks, a replaced q_sample, no ControlNet hint on one half, a model without a runtime) runs one step at a time; without
+guidance (scale == 1 or no unconditional conditioning) the captured steps are the un-paired ones (SDEO_STEP_UNGUIDED).  The switches are ddim_hacked's (SDEO_GRAPH,
 SDEO_LOOP_GRAPH, SDEO_LOOP_GRAPH_STEPS).
 
 `DPMSolverSDESampler` is the stochastic member of the family, DPM-Solver++(2M) SDE (the same paper's SDE form; eta scales the injected
@@ -231,7 +232,7 @@ class DPMSolverSampler(object):
         """the gating of `DDIMSampler._loop_graph_ok`, the bound of the library's timestep table included (the stochastic subclass's
         temperature / noise_dropout are ruled out by `sample`)"""
         return bool(dh.USE_GRAPH and dh.USE_LOOP_GRAPH and img.is_cuda and 2 <= total_steps <= dh.MAX_TABLE_STEPS
-                    and self._pair._fusable(c, uc, scale)
+                    and (self._pair._fusable(c, uc, scale) or self._pair._unguided(c, uc, scale))
                     and self.model.parameterization in ("eps", "v"))
 
     def _loop_graphed(self, img, c, uc, scale, total_steps, log_every_t, intermediates, mask=None, x0=None):
@@ -242,11 +243,12 @@ class DPMSolverSampler(object):
         ts, a_t, k_x, k_d, k_p, k_n = self.timesteps, self.alphas, self.k_x, self.k_d, self.k_p, self.k_n
         time_range = tuple(int(t) for t in ts)
         ident = DDIMSampler._ident
-        hint_shared = ident(c["c_concat"]) == ident(uc["c_concat"])
+        unguided = self._pair._unguided(c, uc, scale)       # no guidance: the same steps with unguided=True on the b latents
+        hint_shared = not unguided and ident(c["c_concat"]) == ident(uc["c_concat"])
         per_graph = dh.LOOP_GRAPH_STEPS if dh.LOOP_GRAPH_STEPS > 0 else total_steps
         shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), m.scales_key(),
                      bool(m.only_mid_control), self._schedule_key, per_graph, hint_shared, m.parameterization,
-                     None if mask is None else tuple(mask.shape))
+                     None if mask is None else tuple(mask.shape), unguided)
         live = [k_n is not None and float(k_n[i]) != 0. for i in range(total_steps)]
 
         def first_step(img, d):
@@ -257,7 +259,7 @@ class DPMSolverSampler(object):
             a = float(a_t[i])
             x, d = self._loop_x, self._loop_d
             head = (i, scale, a, float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]), float(k_p[i]))
-            kw = dict(hint_shared=hint_shared, v_prediction=m.parameterization == "v")
+            kw = dict(hint_shared=hint_shared, v_prediction=m.parameterization == "v", unguided=unguided)
             if noise_row is not None:
                 rt.dpmpp_2m_sde_step(x, d, noise_row, *head, float(k_n[i]), m.net0_scales(), m.only_mid_control, staged=staged, **kw,
                                      **(blend or {}))

@@ -316,6 +316,13 @@ static inline void with_flags(bool a, bool b, F&& f) {
   }
 }
 
+// a third flag in front of the two: f receives it first
+template <typename F>
+static inline void with_flags(bool p, bool a, bool b, F&& f) {
+  if (p) with_flags(a, b, [&](auto x, auto y) { f(std::true_type{}, x, y); });
+  else with_flags(a, b, [&](auto x, auto y) { f(std::false_type{}, x, y); });
+}
+
 // `noise` (fp32, laid out like x) adds the sampler's noise term (`cldm/ddim_hacked.py:227-230`, eta > 0): one fused multiply-add on the
 // finished update, stated as fmaf here and in the pair kernel so that the two round alike whatever the compiler does.
 template <bool VPRED>
@@ -336,7 +343,9 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(float* __restrict__ x_pre
 // The loop of every kernel that leaves the fp16 NHWC latent of the next forward in x0: one thread per (image, pixel) of a latent
 // [b][C][HW], and what elem(i, n, c, pix, j) returns for channel c (j: the element's index in the fp32 NCHW latent, i = n * HW + pix) goes
 // to both halves of the CFG pair (images n and n + b), padding channels zero.  elem does its own fp32 loads and stores.
-template <typename F>
+// PAIRED = false is the un-paired member of every kernel below (SDEO_STEP_UNGUIDED): b is then the whole batch, each image is staged
+// once, and the model output of image n is used as it is (the `guided = false` leg of the element functions).
+template <bool PAIRED, typename F>
 __device__ __forceinline__ void stage_pair(f16* __restrict__ x0, int ld0, int b, int C, int HW, F elem) {
   const int64_t total = (int64_t)b * HW;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -344,7 +353,7 @@ __device__ __forceinline__ void stage_pair(f16* __restrict__ x0, int ld0, int b,
     for (int c = 0; c < ld0; ++c) {
       const f16 v = c < C ? (f16)elem(i, n, c, pix, (n * C + c) * HW + pix) : (f16)0.f;
       x0[i * ld0 + c] = v;
-      x0[(i + total) * ld0 + c] = v;
+      if constexpr (PAIRED) x0[(i + total) * ld0 + c] = v;
     }
   }
 }
@@ -352,16 +361,16 @@ __device__ __forceinline__ void stage_pair(f16* __restrict__ x0, int ld0, int b,
 // The same update for the fused CFG pair inside the library (the sdeo_ddim_step family): eps comes straight from the UNet's fp16 NHWC
 // output (images 0..b-1 conditional, b..2b-1 unconditional), x [b][C][HW] fp32 is updated in place, and the latent of the NEXT forward is
 // staged on the way out (from the noisy value when NOISE).
-template <bool VPRED, bool NOISE>
+template <bool PAIRED, bool VPRED, bool NOISE>
 __global__ __launch_bounds__(256) void cfg_ddim_pair_kernel(float* __restrict__ x, float* __restrict__ pred_x0, const f16* __restrict__ eps,
                                                             int lde, const float* __restrict__ noise, f16* __restrict__ x0, int ld0, int b,
                                                             int C, int HW, float s, float at_coef, float sqrt_aprev, float dir_coef,
                                                             float sigma, float sqrt_1m_at) {
   const int64_t total = (int64_t)b * HW;
-  stage_pair(x0, ld0, b, C, HW, [=](int64_t i, int64_t, int c, int64_t, int64_t j) {
+  stage_pair<PAIRED>(x0, ld0, b, C, HW, [=](int64_t i, int64_t, int c, int64_t, int64_t j) {
     float p0, xp;
-    cfg_ddim_elem_sel<VPRED>(x[j], (float)eps[i * lde + c], (float)eps[(i + total) * lde + c], true, s, at_coef, sqrt_aprev, dir_coef,
-                             sqrt_1m_at, p0, xp);
+    cfg_ddim_elem_sel<VPRED>(x[j], (float)eps[i * lde + c], PAIRED ? (float)eps[(i + total) * lde + c] : 0.f, PAIRED, s, at_coef, sqrt_aprev,
+                             dir_coef, sqrt_1m_at, p0, xp);
     if constexpr (NOISE) xp = fmaf(sigma, noise[j], xp);
     x[j] = xp;
     if (pred_x0) pred_x0[j] = p0;
@@ -387,28 +396,30 @@ int cfg_ddim_check(const char* who, float a_t, float a_prev, const float* noise,
 
 // noise set: the stochastic update, bit-equal to cfg_ddim_step with the same noise / sigma_t; null: sigma_t is not read
 int cfg_ddim_pair(float* x, float* pred_x0, const f16* eps, int lde, const float* noise, float sigma_t, f16* x0, int ld0, int b, int C, int HW,
-                  float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, bool v_prediction, hipStream_t stream) {
+                  float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, bool v_prediction, bool paired, hipStream_t stream) {
   SDEO_CHECK(x && eps && x0 && b > 0 && C > 0 && HW > 0 && lde >= C && ld0 >= C, "cfg_ddim_pair: bad operand");
   if (int rc = cfg_ddim_check("cfg_ddim_pair", a_t, a_prev, noise, noise ? &sigma_t : nullptr)) return rc;
   // the coefficients as cfg_ddim_step forms them, expression for expression
   const float sg = noise ? sigma_t : 0.f;
-  with_flags(v_prediction, noise != nullptr, [&](auto v, auto n) {
-    hipLaunchKernelGGL((cfg_ddim_pair_kernel<v.value, n.value>), grid_for((int64_t)b * HW), dim3(256), 0, stream, x, pred_x0, eps, lde, noise, x0,
-                       ld0, b, C, HW, cfg_scale, v.value ? sqrtf(a_t) : 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sg * sg), sg,
+  with_flags(paired, v_prediction, noise != nullptr, [&](auto p, auto v, auto n) {
+    hipLaunchKernelGGL((cfg_ddim_pair_kernel<p.value, v.value, n.value>), grid_for((int64_t)b * HW), dim3(256), 0, stream, x, pred_x0, eps, lde,
+                       noise, x0, ld0, b, C, HW, cfg_scale, v.value ? sqrtf(a_t) : 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(1.f - a_prev - sg * sg), sg,
                        sqrt_one_minus_at);
   });
   SDEO_HIP(hipGetLastError());
   return 0;
 }
 
-// latent [b][C][HW] fp32 -> fp16 NHWC for BOTH halves of the CFG pair
+// latent [b][C][HW] fp32 -> fp16 NHWC for BOTH halves of the CFG pair (un-paired: each image once)
+template <bool PAIRED>
 __global__ __launch_bounds__(256) void latent_pair_kernel(f16* __restrict__ x0, int ld0, const float* __restrict__ x, int b, int C, int HW) {
-  stage_pair(x0, ld0, b, C, HW, [=](int64_t, int64_t, int, int64_t, int64_t j) { return x[j]; });
+  stage_pair<PAIRED>(x0, ld0, b, C, HW, [=](int64_t, int64_t, int, int64_t, int64_t j) { return x[j]; });
 }
 
-int latent_pair_to_nhwc(f16* x0, int ld0, const float* x, int b, int C, int HW, hipStream_t stream) {
+int latent_pair_to_nhwc(f16* x0, int ld0, const float* x, int b, int C, int HW, bool paired, hipStream_t stream) {
   SDEO_CHECK(x0 && x && b > 0 && C > 0 && HW > 0 && ld0 >= C, "latent_pair_to_nhwc: bad operand");
-  hipLaunchKernelGGL(latent_pair_kernel, grid_for((int64_t)b * HW), dim3(256), 0, stream, x0, ld0, x, b, C, HW);
+  hipLaunchKernelGGL(paired ? latent_pair_kernel<true> : latent_pair_kernel<false>, grid_for((int64_t)b * HW), dim3(256), 0, stream, x0, ld0,
+                     x, b, C, HW);
   SDEO_HIP(hipGetLastError());
   return 0;
 }
@@ -446,10 +457,11 @@ __global__ __launch_bounds__(256) void mask_blend_kernel(float* x, const float* 
 }
 
 // The blend as the front of a fused CFG-pair step: x [b][C][HW] is blended in place and the blended latent is staged.
+template <bool PAIRED>
 __global__ __launch_bounds__(256) void mask_blend_pair_kernel(float* x, const float* __restrict__ orig, const float* __restrict__ noise,
                                                               const float* __restrict__ mask, int mask_n, int mask_c, float sqrt_a,
                                                               float sqrt_1ma, f16* __restrict__ x0, int ld0, int b, int C, int HW) {
-  stage_pair(x0, ld0, b, C, HW, [=](int64_t, int64_t n, int c, int64_t pix, int64_t j) {
+  stage_pair<PAIRED>(x0, ld0, b, C, HW, [=](int64_t, int64_t n, int c, int64_t pix, int64_t j) {
     const float xb = mask_blend_elem(x[j], orig[j], noise[j], mask[mask_index(n, c, pix, mask_n, mask_c, HW)], sqrt_a, sqrt_1ma);
     x[j] = xb;
     return xb;
@@ -479,11 +491,11 @@ int mask_blend(float* x, const float* orig, const float* noise, const float* mas
 }
 
 int mask_blend_pair(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a,
-                    float sqrt_1ma, f16* x0, int ld0, int b, int C, int HW, hipStream_t stream) {
+                    float sqrt_1ma, f16* x0, int ld0, int b, int C, int HW, bool paired, hipStream_t stream) {
   if (int rc = mask_blend_check("mask_blend_pair", x, orig, noise, mask, mask_n, mask_c, b, C, HW)) return rc;
   SDEO_CHECK(x0 && ld0 >= C, "mask_blend_pair: bad staging operand");
-  hipLaunchKernelGGL(mask_blend_pair_kernel, grid_for((int64_t)b * HW), dim3(256), 0, stream, x, orig, noise, mask, mask_n, mask_c, sqrt_a,
-                     sqrt_1ma, x0, ld0, b, C, HW);
+  hipLaunchKernelGGL(paired ? mask_blend_pair_kernel<true> : mask_blend_pair_kernel<false>, grid_for((int64_t)b * HW), dim3(256), 0, stream,
+                     x, orig, noise, mask, mask_n, mask_c, sqrt_a, sqrt_1ma, x0, ld0, b, C, HW);
   SDEO_HIP(hipGetLastError());
   return 0;
 }
@@ -558,17 +570,17 @@ __global__ __launch_bounds__(256) void cfg_lms_kernel(float* __restrict__ x_next
 
 // The same update for the fused CFG pair (the sdeo_dpmpp_2m_step family), laid out as cfg_ddim_pair_kernel: fp16 NHWC model output
 // (conditional images first), x [b][C][HW] fp32 updated in place, the latent of the next forward staged.
-template <bool VPRED, bool NOISE>
+template <bool PAIRED, bool VPRED, bool NOISE>
 __global__ __launch_bounds__(256) void cfg_lms_pair_kernel(float* __restrict__ x, float* d, const f16* __restrict__ eps, int lde,
                                                            const float* __restrict__ noise, f16* __restrict__ x0, int ld0, int b, int C, int HW,
                                                            float s, float at_coef, float sqrt_1m_at, float k_x, float k_d, float k_p,
                                                            float k_n) {
   const int64_t total = (int64_t)b * HW;
-  stage_pair(x0, ld0, b, C, HW, [=](int64_t i, int64_t, int c, int64_t, int64_t j) {
+  stage_pair<PAIRED>(x0, ld0, b, C, HW, [=](int64_t i, int64_t, int c, int64_t, int64_t j) {
     float p0, xn;
     const float dp = k_p != 0.f ? d[j] : 0.f;
-    cfg_lms_elem<VPRED>(x[j], (float)eps[i * lde + c], (float)eps[(i + total) * lde + c], true, s, at_coef, sqrt_1m_at, k_x, k_d, k_p, dp, p0,
-                        xn);
+    cfg_lms_elem<VPRED>(x[j], (float)eps[i * lde + c], PAIRED ? (float)eps[(i + total) * lde + c] : 0.f, PAIRED, s, at_coef, sqrt_1m_at, k_x,
+                        k_d, k_p, dp, p0, xn);
     if constexpr (NOISE) xn = fmaf(k_n, noise[j], xn);
     x[j] = xn;
     if (d) d[j] = p0;
@@ -589,12 +601,13 @@ int cfg_lms_check(const char* who, const float* d, const float* noise, float a_t
 
 // k_n == 0: the deterministic kernel, whatever the noise pointer
 int cfg_lms_pair(float* x, float* d, const f16* eps, int lde, const float* noise, float k_n, f16* x0, int ld0, int b, int C, int HW,
-                 float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, bool v_prediction, hipStream_t stream) {
+                 float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, bool v_prediction, bool paired,
+                 hipStream_t stream) {
   SDEO_CHECK(x && eps && x0 && b > 0 && C > 0 && HW > 0 && lde >= C && ld0 >= C, "cfg_lms_pair: bad operand");
   if (int rc = cfg_lms_check("cfg_lms_pair", d, noise, a_t, k_x, k_d, k_p, k_n)) return rc;
-  with_flags(v_prediction, k_n != 0.f, [&](auto v, auto n) {
-    hipLaunchKernelGGL((cfg_lms_pair_kernel<v.value, n.value>), grid_for((int64_t)b * HW), dim3(256), 0, stream, x, d, eps, lde, noise, x0, ld0, b,
-                       C, HW, cfg_scale, v.value ? sqrtf(a_t) : 1.0f / sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p, k_n);
+  with_flags(paired, v_prediction, k_n != 0.f, [&](auto p, auto v, auto n) {
+    hipLaunchKernelGGL((cfg_lms_pair_kernel<p.value, v.value, n.value>), grid_for((int64_t)b * HW), dim3(256), 0, stream, x, d, eps, lde, noise,
+                       x0, ld0, b, C, HW, cfg_scale, v.value ? sqrtf(a_t) : 1.0f / sqrtf(a_t), sqrt_one_minus_at, k_x, k_d, k_p, k_n);
   });
   SDEO_HIP(hipGetLastError());
   return 0;

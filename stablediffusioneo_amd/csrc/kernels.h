@@ -246,9 +246,11 @@ int resize_area_fast_u8(uint8_t* dst, const uint8_t* src, int h, int w, int c, i
 // output, updates x in place and stages the fp16 NHWC latent of the next forward in both halves of x0.  noise (fp32, laid out like x) set:
 // + sigma_t * noise with dir_coef = sqrt(1 - a_prev - sigma_t^2) (`cldm/ddim_hacked.py:227-230`), one more fused multiply-add, bit-equal
 // to cfg_ddim_step with the same noise / sigma_t, and the staged latent is the noisy one; noise null: sigma_t is not read.
+// paired = false (every pair launcher here): the un-paired member, SDEO_STEP_UNGUIDED.  b is the whole batch, eps rows 0..b-1 are used as
+// they are (cfg_scale is not read), and each image is staged once: bit-equal to the flat step with a null eps_u / m_u.
 int cfg_ddim_pair(float* x, float* pred_x0, const f16* eps, int lde, const float* noise, float sigma_t, f16* x0, int ld0, int b, int C, int HW,
-                  float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, bool v_prediction, hipStream_t stream);
-int latent_pair_to_nhwc(f16* x0, int ld0, const float* x, int b, int C, int HW, hipStream_t stream);
+                  float cfg_scale, float a_t, float a_prev, float sqrt_one_minus_at, bool v_prediction, bool paired, hipStream_t stream);
+int latent_pair_to_nhwc(f16* x0, int ld0, const float* x, int b, int C, int HW, bool paired, hipStream_t stream);
 int cfg_ddim_step(float* x_prev, float* pred_x0, const float* x, const float* eps_c, const float* eps_u, const float* noise,
                   float cfg_scale, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, int64_t n,
                   bool v_prediction, hipStream_t stream);
@@ -256,7 +258,8 @@ int cfg_ddim_step(float* x_prev, float* pred_x0, const float* x, const float* ep
 // form); D is cfg_ddim_step's pred_x0 and replaces D_prev in d.  k_n == 0 is the deterministic update, whatever the noise pointer (it may
 // be null).  The pair form is laid out as cfg_ddim_pair.  `who` names the flat step in its refusals.
 int cfg_lms_pair(float* x, float* d, const f16* eps, int lde, const float* noise, float k_n, f16* x0, int ld0, int b, int C, int HW,
-                 float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, bool v_prediction, hipStream_t stream);
+                 float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, bool v_prediction, bool paired,
+                 hipStream_t stream);
 int cfg_lms_step(const char* who, float* x_next, float* d, const float* x, const float* m_c, const float* m_u, const float* noise,
                  float cfg_scale, float a_t, float sqrt_one_minus_at, float k_x, float k_d, float k_p, float k_n, int64_t n, bool v_prediction,
                  hipStream_t stream);
@@ -274,7 +277,7 @@ int mask_blend_check(const char* who, const float* x, const float* orig, const f
 int mask_blend(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a, float sqrt_1ma,
                int n, int C, int HW, hipStream_t stream);
 int mask_blend_pair(float* x, const float* orig, const float* noise, const float* mask, int mask_n, int mask_c, float sqrt_a,
-                    float sqrt_1ma, f16* x0, int ld0, int b, int C, int HW, hipStream_t stream);
+                    float sqrt_1ma, f16* x0, int ld0, int b, int C, int HW, bool paired, hipStream_t stream);
 // dst = (gen * m + orig * (255 - m) + 127) / 255 in integers: uint8 HWC images [H][W][C], C in 1..4, uint8 mask [H][W]
 int composite_u8(uint8_t* dst, const uint8_t* gen, const uint8_t* orig, const uint8_t* mask, int H, int W, int C, hipStream_t stream);
 

@@ -153,10 +153,12 @@ struct sdeo_handle_s {
   //   ctx_set:         whose context K / V were computed since the last sdeo_configure (bit 0 the UNet, bit 1 the control networks)
   //   ctx_epoch:       advances every time a new context is staged; ctx_epoch_of[side] is the epoch side's K / V were computed from
   //   x0_staged_for:   the caller's latent whose updated fp16 copy the last fused step left in x0; null once anything else wrote x0
+  //   x0_staged_paired: that step was a CFG-pair step (b = N / 2 latents, each staged twice), not an unguided one (N latents, once)
   bool hint_set[kMaxControlNets] = {false};
   int ctx_set = 0;
   unsigned long long ctx_epoch = 0, ctx_epoch_of[2] = {0, 0};
   const float* x0_staged_for = nullptr;
+  bool x0_staged_paired = true;
   // sdeo_lora_commit changed the weights under the caches: net j's hint features, the context K / V of the UNet (bit 0) and of the
   // control networks (bit 1), the timestep table.  Each stays stale until the call that fills it runs again; a call that asks for a
   // stale cache is refused.  A handle that never commits an adapter never sets them.
@@ -1942,12 +1944,18 @@ struct StepBlend {
 // What every fused CFG-pair step does before its update kernel: the checks, the time-embedding row, the control scales, the fp16 copy of
 // [x; x] unless the previous step staged it, and the networks.  Leaves the model output in h->eps16.  With a blend, x is first replaced
 // by the blended latent, in the launch that stages its fp16 copy.  Every check precedes the first device call.
+// SDEO_STEP_UNGUIDED: the un-paired member.  x holds the configured N latents (any N >= 1), each is staged and run once, and the programs
+// are the plain ones: no two images of the batch are the same, so no shared prefix holds.
 static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float* host_control_scales, int only_mid_control, int flags,
                             const StepBlend* blend, const char* who, hipStream_t s) {
   REQUIRE_READY(h);
   SDEO_CHECK(x, "%s: null latent", who);
   SDEO_CHECK(h->cfg.in_channels == h->cfg.out_channels, "%s: eps and latent must have the same channel count", who);
-  SDEO_CHECK(h->N % 2 == 0, "%s: configured for %d images; the CFG pair needs an even count (n = 2 x latents)", who, h->N);
+  const bool paired = !(flags & SDEO_STEP_UNGUIDED);
+  const int b = paired ? h->N / 2 : h->N;         // latents in x
+  SDEO_CHECK(!paired || h->N % 2 == 0, "%s: configured for %d images; the CFG pair needs an even count (n = 2 x latents)", who, h->N);
+  SDEO_CHECK(paired || !(flags & SDEO_STEP_HINT_SHARED), "%s: SDEO_STEP_HINT_SHARED together with SDEO_STEP_UNGUIDED (an unguided step has no "
+             "second half whose hints could be those of the first)", who);
   SDEO_CHECK(table_row >= 0 && table_row < h->tab_count, "%s: timestep row %d, but the table holds %d (sdeo_set_timestep_table)", who,
              table_row, h->tab_count);
   SDEO_CHECK(!h->tab_stale, "%s: sdeo_lora_commit changed the weights the timestep table was computed with (call sdeo_set_timestep_table again)", who);
@@ -1958,10 +1966,12 @@ static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float*
                "forward (sdeo_apply_model, sdeo_unet_forward, sdeo_controlnet_forward) overwrote it since (drop the flag)", who);
     SDEO_CHECK(h->x0_staged_for == x, "%s: SDEO_STEP_LATENT_STAGED, but the previous fused step ran on another latent (%p; this one is %p; "
                "drop the flag)", who, (const void*)h->x0_staged_for, (const void*)x);
+    SDEO_CHECK(h->x0_staged_paired == paired, "%s: SDEO_STEP_LATENT_STAGED, but the previous fused step was %s and staged its latent as such "
+               "(drop the flag)", who, h->x0_staged_paired ? "a CFG-pair step" : "an unguided step (SDEO_STEP_UNGUIDED)");
   }
   if (blend) {
     SDEO_CHECK(!(flags & SDEO_STEP_LATENT_STAGED), "%s: SDEO_STEP_LATENT_STAGED has no meaning here (the blend changes the latent and always restages it)", who);
-    if (int rc = mask_blend_check(who, x, blend->orig, blend->noise, blend->mask, blend->mask_n, blend->mask_c, h->N / 2, h->cfg.in_channels,
+    if (int rc = mask_blend_check(who, x, blend->orig, blend->noise, blend->mask, blend->mask_n, blend->mask_c, b, h->cfg.in_channels,
                                   h->lh * h->lw))
       return rc;
   }
@@ -1971,13 +1981,13 @@ static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float*
   h->x0_staged_for = nullptr;                     // until the update kernel has left the new latent in x0 (fused_step)
   if (blend) {
     if (int rc = mask_blend_pair(x, blend->orig, blend->noise, blend->mask, blend->mask_n, blend->mask_c, blend->sqrt_a, blend->sqrt_1ma,
-                                 h->x0.p, h->x0.ld, h->N / 2, h->cfg.in_channels, h->lh * h->lw, s))
+                                 h->x0.p, h->x0.ld, b, h->cfg.in_channels, h->lh * h->lw, paired, s))
       return rc;
   } else if (!(flags & SDEO_STEP_LATENT_STAGED)) {
-    if (int rc = latent_pair_to_nhwc(h->x0.p, h->x0.ld, x, h->N / 2, h->cfg.in_channels, h->lh * h->lw, s)) return rc;
+    if (int rc = latent_pair_to_nhwc(h->x0.p, h->x0.ld, x, b, h->cfg.in_channels, h->lh * h->lw, paired, s)) return rc;
   }
   // x0 = [x; x] at one timestep: the UNet's shared prefix always holds, the ControlNet's when the caller vouches for the hints
-  return run_step_programs(h, false, true, s, true, (flags & SDEO_STEP_HINT_SHARED) != 0);
+  return run_step_programs(h, false, true, s, paired, paired && (flags & SDEO_STEP_HINT_SHARED) != 0);
 }
 
 // One fused CFG-pair step as its entry point describes it: which update, its coefficients, the optional noise term and the optional blend.
@@ -2012,11 +2022,13 @@ static int step_blend_operands(const char* who, const StepBlend& b, int flags) {
 // (the next step may then pass SDEO_STEP_LATENT_STAGED).  A refused step has launched nothing and leaves that record alone.
 static int fused_step(sdeo_handle h, float* x, const Step& st, int table_row, const float* host_control_scales, int only_mid_control,
                       int flags, hipStream_t s) {
+  const bool paired = !(flags & SDEO_STEP_UNGUIDED);
+  const float cfg_scale = paired ? st.cfg_scale : 0.f;        // an unguided step neither reads nor checks it
   if (st.stochastic && st.multistep)
-    SDEO_CHECK(std::isfinite(st.cfg_scale) && std::isfinite(st.a_t) && std::isfinite(st.sqrt_one_minus_at),
+    SDEO_CHECK(std::isfinite(cfg_scale) && std::isfinite(st.a_t) && std::isfinite(st.sqrt_one_minus_at),
                "%s: non-finite coefficient cfg_scale=%g a_t=%g sqrt_one_minus_at=%g", st.who, st.cfg_scale, st.a_t, st.sqrt_one_minus_at);
   else if (st.stochastic)
-    SDEO_CHECK(std::isfinite(st.cfg_scale) && std::isfinite(st.sqrt_one_minus_at), "%s: non-finite coefficient cfg_scale=%g sqrt_one_minus_at=%g",
+    SDEO_CHECK(std::isfinite(cfg_scale) && std::isfinite(st.sqrt_one_minus_at), "%s: non-finite coefficient cfg_scale=%g sqrt_one_minus_at=%g",
                st.who, st.cfg_scale, st.sqrt_one_minus_at);
   if (int rc = st.multistep ? cfg_lms_check(st.coef_who, st.aux, st.noise, st.a_t, st.k_x, st.k_d, st.k_p, st.noise_coef)
                             : cfg_ddim_check(st.coef_who, st.a_t, st.a_prev, st.noise, st.stochastic ? &st.noise_coef : nullptr))
@@ -2025,12 +2037,12 @@ static int fused_step(sdeo_handle h, float* x, const Step& st, int table_row, co
   if (int rc = cfg_pair_forward(h, x, table_row, host_control_scales, only_mid_control, flags, st.blended ? &st.blend : nullptr, st.who, s))
     return rc;
   const bool v_prediction = (flags & SDEO_STEP_V_PREDICTION) != 0;
-  const int b = h->N / 2, C = h->cfg.out_channels, HW = h->lh * h->lw;
-  const int rc = st.multistep ? cfg_lms_pair(x, st.aux, h->eps16.p, h->eps16.ld, st.noise, st.noise_coef, h->x0.p, h->x0.ld, b, C, HW, st.cfg_scale,
-                                             st.a_t, st.sqrt_one_minus_at, st.k_x, st.k_d, st.k_p, v_prediction, s)
-                              : cfg_ddim_pair(x, st.aux, h->eps16.p, h->eps16.ld, st.noise, st.noise_coef, h->x0.p, h->x0.ld, b, C, HW, st.cfg_scale,
-                                              st.a_t, st.a_prev, st.sqrt_one_minus_at, v_prediction, s);
-  if (!rc) h->x0_staged_for = x;
+  const int b = paired ? h->N / 2 : h->N, C = h->cfg.out_channels, HW = h->lh * h->lw;
+  const int rc = st.multistep ? cfg_lms_pair(x, st.aux, h->eps16.p, h->eps16.ld, st.noise, st.noise_coef, h->x0.p, h->x0.ld, b, C, HW, cfg_scale,
+                                             st.a_t, st.sqrt_one_minus_at, st.k_x, st.k_d, st.k_p, v_prediction, paired, s)
+                              : cfg_ddim_pair(x, st.aux, h->eps16.p, h->eps16.ld, st.noise, st.noise_coef, h->x0.p, h->x0.ld, b, C, HW, cfg_scale,
+                                              st.a_t, st.a_prev, st.sqrt_one_minus_at, v_prediction, paired, s);
+  if (!rc) h->x0_staged_for = x, h->x0_staged_paired = paired;
   return rc;
 }
 

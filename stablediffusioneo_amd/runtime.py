@@ -14,6 +14,7 @@ HINT_CACHED, CONTEXT_CACHED, NO_CONTROL = 1, 2, 4
 STEP_LATENT_STAGED = 16
 STEP_HINT_SHARED = 32
 STEP_V_PREDICTION = 64
+STEP_UNGUIDED = 128
 
 
 def TIMESTEP_ROW(i: int) -> int:
@@ -393,36 +394,39 @@ class SdeoRuntime(_HandleRuntime):
         self._table_key = (self.generation, tuple(ts))      # whose schedule the table holds (captured graphs read it by address)
         return len(ts)
 
-    def _step_tensors(self, x, aux):
-        """what the six fused steps ask of the latent and of their second state tensor (pred_x0 / d, optional)"""
-        assert x.is_contiguous() and x.dtype == torch.float32 and 2 * x.shape[0] == self.n
+    def _step_tensors(self, x, aux, unguided=False):
+        """what the six fused steps ask of the latent and of their second state tensor (pred_x0 / d, optional): half the configured
+        count of latents for the CFG pair, all of it for an unguided step"""
+        assert x.is_contiguous() and x.dtype == torch.float32 and (1 if unguided else 2) * x.shape[0] == self.n
         assert aux is None or (aux.is_contiguous() and aux.dtype == torch.float32 and aux.shape == x.shape)
 
     @staticmethod
-    def _step_flags(staged, hint_shared, v_prediction, flags=0):
+    def _step_flags(staged, hint_shared, v_prediction, flags=0, unguided=False):
         """the SDEO_STEP_* word of a fused step (flags: extra bits as they are)"""
         return (flags | (STEP_LATENT_STAGED if staged else 0) | (STEP_HINT_SHARED if hint_shared else 0)
-                | (STEP_V_PREDICTION if v_prediction else 0))
+                | (STEP_V_PREDICTION if v_prediction else 0) | (STEP_UNGUIDED if unguided else 0))
 
     def ddim_step(self, x, pred_x0, row: int, cfg_scale: float, a_t: float, a_prev: float, sqrt_one_minus_at: float, scales=None,
-                  only_mid_control: bool = False, staged: bool = False, hint_shared: bool = False, v_prediction: bool = False):
+                  only_mid_control: bool = False, staged: bool = False, hint_shared: bool = False, v_prediction: bool = False,
+                  unguided: bool = False, flags: int = 0):
         """`sdeo_ddim_step`: one eta = 0 DDIM step of the CFG pair; x (b,4,h,w) fp32 contiguous is updated in place.
         hint_shared: the cached hints of the unconditional half are those of the conditional half (SDEO_STEP_HINT_SHARED), so the
         ControlNet too computes what precedes its first cross-attention once.  v_prediction: the model predicts v
-        (SDEO_STEP_V_PREDICTION)."""
-        self._step_tensors(x, pred_x0)
-        flags = self._step_flags(staged, hint_shared, v_prediction)
+        (SDEO_STEP_V_PREDICTION).  unguided (here and on the other five steps): SDEO_STEP_UNGUIDED, no guidance -- x holds the configured
+        n latents, each runs once and its model output is used as it is; cfg_scale is not read and hint_shared must be off."""
+        self._step_tensors(x, pred_x0, unguided)
+        flags = self._step_flags(staged, hint_shared, v_prediction, flags, unguided)
         check(self.lib.sdeo_ddim_step(self.handle, ptr(x), ptr(pred_x0), int(row), cfg_scale, a_t, a_prev, sqrt_one_minus_at,
                                       self._scales(scales), int(only_mid_control), flags, cur_stream()), "ddim_step")
         return x
 
     def dpmpp_2m_step(self, x, d, row: int, cfg_scale: float, a_t: float, sqrt_one_minus_at: float, k_x: float, k_d: float, k_p: float,
                       scales=None, only_mid_control: bool = False, staged: bool = False, hint_shared: bool = False,
-                      v_prediction: bool = False):
+                      v_prediction: bool = False, unguided: bool = False, flags: int = 0):
         """`sdeo_dpmpp_2m_step`: one DPM-Solver++(2M) step of the CFG pair, as `ddim_step` with the linear-multistep update
         x <- k_x x + k_d D + k_p d, d <- D; x and d (b,4,h,w) fp32 contiguous are updated in place (d may be None when k_p == 0)."""
-        self._step_tensors(x, d)
-        flags = self._step_flags(staged, hint_shared, v_prediction)
+        self._step_tensors(x, d, unguided)
+        flags = self._step_flags(staged, hint_shared, v_prediction, flags, unguided)
         check(self.lib.sdeo_dpmpp_2m_step(self.handle, ptr(x), ptr(d), int(row), cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p,
                                           self._scales(scales), int(only_mid_control), flags, cur_stream()), "dpmpp_2m_step")
         return x
@@ -438,12 +442,12 @@ class SdeoRuntime(_HandleRuntime):
 
     def ddim_step_masked(self, x, pred_x0, orig, noise, mask, sqrt_a: float, sqrt_one_minus_a: float, row: int, cfg_scale: float, a_t: float,
                          a_prev: float, sqrt_one_minus_at: float, scales=None, only_mid_control: bool = False, hint_shared: bool = False,
-                         v_prediction: bool = False, flags: int = 0):
+                         v_prediction: bool = False, flags: int = 0, unguided: bool = False):
         """`sdeo_ddim_step_masked`: x <- mask * (sqrt_a orig + sqrt_one_minus_a noise) + (1 - mask) x, then `ddim_step` on it, both in
         place; bit-identical to `ops.mask_blend` followed by the unstaged `ddim_step`.  There is no `staged`: the blend always restages
         (flags: extra SDEO_STEP_* bits as they are, for the tests of what the library refuses)."""
-        self._step_tensors(x, pred_x0)
-        flags = self._step_flags(False, hint_shared, v_prediction, flags)
+        self._step_tensors(x, pred_x0, unguided)
+        flags = self._step_flags(False, hint_shared, v_prediction, flags, unguided)
         check(self.lib.sdeo_ddim_step_masked(self.handle, ptr(x), ptr(pred_x0), *self._blend_args(x, orig, noise, mask), sqrt_a,
                                              sqrt_one_minus_a, int(row), cfg_scale, a_t, a_prev, sqrt_one_minus_at, self._scales(scales),
                                              int(only_mid_control), flags, cur_stream()), "ddim_step_masked")
@@ -451,10 +455,10 @@ class SdeoRuntime(_HandleRuntime):
 
     def dpmpp_2m_step_masked(self, x, d, orig, noise, mask, sqrt_a: float, sqrt_one_minus_a: float, row: int, cfg_scale: float, a_t: float,
                              sqrt_one_minus_at: float, k_x: float, k_d: float, k_p: float, scales=None, only_mid_control: bool = False,
-                             hint_shared: bool = False, v_prediction: bool = False, flags: int = 0):
+                             hint_shared: bool = False, v_prediction: bool = False, flags: int = 0, unguided: bool = False):
         """`sdeo_dpmpp_2m_step_masked`: the blend of `ddim_step_masked`, then `dpmpp_2m_step` on the blended latent"""
-        self._step_tensors(x, d)
-        flags = self._step_flags(False, hint_shared, v_prediction, flags)
+        self._step_tensors(x, d, unguided)
+        flags = self._step_flags(False, hint_shared, v_prediction, flags, unguided)
         check(self.lib.sdeo_dpmpp_2m_step_masked(self.handle, ptr(x), ptr(d), *self._blend_args(x, orig, noise, mask), sqrt_a,
                                                  sqrt_one_minus_a, int(row), cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p,
                                                  self._scales(scales), int(only_mid_control), flags, cur_stream()), "dpmpp_2m_step_masked")
@@ -475,14 +479,14 @@ class SdeoRuntime(_HandleRuntime):
     def ddim_step_eta(self, x, pred_x0, noise, sigma_t: float, row: int, cfg_scale: float, a_t: float, a_prev: float,
                       sqrt_one_minus_at: float, scales=None, only_mid_control: bool = False, staged: bool = False, hint_shared: bool = False,
                       v_prediction: bool = False, orig=None, mask_noise=None, mask=None, sqrt_a: float = 0.0, sqrt_one_minus_a: float = 0.0,
-                      flags: int = 0):
+                      flags: int = 0, unguided: bool = False):
         """`sdeo_ddim_step_eta`: `ddim_step` with the sampler's noise term, x <- x_prev + sigma_t * noise (dir_coef = sqrt(1 - a_prev -
         sigma_t^2)), in place; noise (b,4,h,w) fp32 is read by address, so a captured call sees what the row holds at replay.  With orig /
         mask_noise / mask / sqrt_a / sqrt_one_minus_a the blend of `ddim_step_masked` runs in front (no `staged` then).  Bit-identical to
         `apply_model` on [x; x] + `ops.cfg_ddim_step` with the same noise and sigma_t."""
-        self._step_tensors(x, pred_x0)
+        self._step_tensors(x, pred_x0, unguided)
         pn, po, pm, pk, mn, mc = self._eta_args(x, noise, orig, mask_noise, mask)
-        flags = self._step_flags(staged, hint_shared, v_prediction, flags)
+        flags = self._step_flags(staged, hint_shared, v_prediction, flags, unguided)
         check(self.lib.sdeo_ddim_step_eta(self.handle, ptr(x), ptr(pred_x0), pn, sigma_t, po, pm, pk, mn, mc, sqrt_a, sqrt_one_minus_a,
                                           int(row), cfg_scale, a_t, a_prev, sqrt_one_minus_at, self._scales(scales), int(only_mid_control),
                                           flags, cur_stream()), "ddim_step_eta")
@@ -491,12 +495,12 @@ class SdeoRuntime(_HandleRuntime):
     def dpmpp_2m_sde_step(self, x, d, noise, row: int, cfg_scale: float, a_t: float, sqrt_one_minus_at: float, k_x: float, k_d: float,
                           k_p: float, k_n: float, scales=None, only_mid_control: bool = False, staged: bool = False,
                           hint_shared: bool = False, v_prediction: bool = False, orig=None, mask_noise=None, mask=None, sqrt_a: float = 0.0,
-                          sqrt_one_minus_a: float = 0.0, flags: int = 0):
+                          sqrt_one_minus_a: float = 0.0, flags: int = 0, unguided: bool = False):
         """`sdeo_dpmpp_2m_sde_step`: `dpmpp_2m_step` with the SDE solver's fourth term, x <- k_x x + k_d D + k_p d + k_n noise, d <- D;
         the blend operands as in `ddim_step_eta`"""
-        self._step_tensors(x, d)
+        self._step_tensors(x, d, unguided)
         pn, po, pm, pk, mn, mc = self._eta_args(x, noise, orig, mask_noise, mask)
-        flags = self._step_flags(staged, hint_shared, v_prediction, flags)
+        flags = self._step_flags(staged, hint_shared, v_prediction, flags, unguided)
         check(self.lib.sdeo_dpmpp_2m_sde_step(self.handle, ptr(x), ptr(d), pn, po, pm, pk, mn, mc, sqrt_a, sqrt_one_minus_a, int(row),
                                               cfg_scale, a_t, sqrt_one_minus_at, k_x, k_d, k_p, k_n, self._scales(scales),
                                               int(only_mid_control), flags, cur_stream()), "dpmpp_2m_sde_step")
