@@ -264,7 +264,8 @@ int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w);
  * DDIM loop passes the *_CACHED flags after the first step (the corresponding pointers may then be NULL). */
 #define SDEO_HINT_CACHED 1
 #define SDEO_CONTEXT_CACHED 2
-#define SDEO_NO_CONTROL 4 /* apply_model only: the c_concat=None branch (UNet without ControlNet) */
+/* SDEO_NO_CONTROL: apply_model only, the c_concat=None branch (UNet without ControlNet) */
+#define SDEO_NO_CONTROL 4
 /* The time embedding (timestep_embedding -> time_embed MLP -> every ResBlock's emb_layers, openaimodel.py:777-781, 255-275)
  * depends only on t.  A sampler that knows its schedule hands it over once (sdeo_set_timestep_table) and then passes
  * SDEO_TIMESTEP_ROW(i) instead of a timesteps pointer: every image of the batch runs at timestep i of that table. */
@@ -273,7 +274,8 @@ int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w);
 
 /* State a handle keeps between calls, and who may read it (the cache contract).
  * Four items outlive a call.  The fast paths read them by address and on the caller's word (a *_CACHED flag, SDEO_TIMESTEP_ROW, a fused
- * sdeo_*_step, SDEO_STEP_LATENT_STAGED), so the handle keeps a host-side record of what each holds and checks it before the first
+ * sdeo_*_step, SDEO_STEP_LATENT_STAGED), so the handle keeps a host-side record (csrc/cache_record.h: one type, one transition per
+ * "filled by" / "cleared by" entry below, one check per "read by" entry) of what each holds and checks it before the first
  * device call of every entry point: a read is either right -- bit-identical to the same call given the inputs the cache was filled
  * from -- or refused, with a message that names the flag (or the step) and the call that fills the cache.  A refused call touches
  * nothing: not the caller's tensors (x, pred_x0, d, eps, controls), not the caches, not this record.  The checks run on the host when

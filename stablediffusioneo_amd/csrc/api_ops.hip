@@ -195,7 +195,7 @@ int sdeo_conv2d_pad_nhwc_f16(void* y, const void* x, const void* w_krsc, const f
 }
 
 // conv2d whose epilogue emits the GroupNorm partials of its output, followed by the normalise-only GroupNorm that consumes them
-// (the [conv -> GroupNorm] pairs of the networks, csrc/net.hip).  *slots = entries per image the plan writes; 0 = this shape's plan
+// (the [conv -> GroupNorm] pairs of the networks, csrc/net_build.hip).  *slots = entries per image the plan writes; 0 = this shape's plan
 // cannot emit them (nothing is launched then).  partials >= n * slots * groups * 2 floats (+ n * groups * 2 when slots > 128).
 int sdeo_debug_conv2d_gn_f16(void* ynorm, void* y, const void* x, const void* w_krsc, const float* bias, const void* res, int n, int h,
                              int w, int cin, int cout, int ksize, int stride, int upsample2x, const float* gamma, const float* beta,

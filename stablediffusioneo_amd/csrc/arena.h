@@ -1,4 +1,4 @@
-// Activation arena of the network executor (net.hip): the first-fit offset planner and the tensor record that knows whether it owns
+// Activation arena of the network executor (net_build.hip): the first-fit offset planner and the tensor record that knows whether it owns
 // its block.  Standard C++ only (no HIP include): tests/arena_check.cpp builds this header with the host compiler.
 #pragma once
 #include <stddef.h>

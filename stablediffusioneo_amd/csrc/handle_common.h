@@ -1,4 +1,4 @@
-// Host-side machinery shared by the network handles (net.hip, clip.hip, hed.hip): the weight registry / slab / loader and the
+// Host-side machinery shared by the network handles (net_handle.h with net.hip / net_weights.hip / net_build.hip, clip.hip, hed.hip): the weight registry / slab / loader and the
 // program runner with its per-launch profiler.  A handle registers its tensors (take / add), allocates the slab once, forwards its
 // *_weight_info / *_load_weight / *_finalize_weights entry points here, and unrolls its network into a Program at configure time.
 #pragma once
@@ -236,7 +236,7 @@ struct Op {          // one launch of a program + what it is for the profiler
   const char* key = "other";
   std::string tag;           // problem shape, shown by the profiler when SDEO_PROFILE_DETAIL=1
   double flops = 0, bytes = 0;
-  bool zero_conv = false;    // net.hip's ControlNet program: a zero conv (skipped when the UNet decoder applies the zero convs itself)
+  bool zero_conv = false;    // net_build.hip's ControlNet program: a zero conv (skipped when the UNet decoder applies the zero convs itself)
   template <class F>
   Op(F f, const char* key_ = "other", double flops_ = 0, double bytes_ = 0, std::string tag_ = std::string())
       : fn(std::move(f)), key(key_), tag(std::move(tag_)), flops(flops_), bytes(bytes_) {}

@@ -61,7 +61,7 @@ struct ConvGemm {
   const uint8_t* mx_sx = nullptr;  // [M][mx_ldsx]
   const uint8_t* mx_sw = nullptr;  // [N][mx_ldsw]
   int mx_ldsx = 0, mx_ldsw = 0;
-  // shared prefix of a batch whose halves are identical up to here (the CFG pair, csrc/net.hip build_attn):
+  // shared prefix of a batch whose halves are identical up to here (the CFG pair, csrc/net_build.hip build_attn):
   // res_rows: `res` holds this many rows and output row m adds row m - res_rows when m >= res_rows (0: M rows, one per output row;
   //   M / 2: both halves of the batch add the residual the first half computed).  M / 2 <= res_rows <= M.
   // plan_B: this launch is the first B images (rows, for a GEMM) of a problem of plan_B; it runs that problem's plan (tile, split-K,
@@ -159,7 +159,7 @@ struct AttnArgs {
   int ldo, ldq, ldk, ldv, B, H, Tq, Tk, TkS, TkSv, d;
   float scale;
   int causal;
-  // shared prefix of a batch whose halves are identical up to here (the CFG pair, csrc/net.hip build_attn):
+  // shared prefix of a batch whose halves are identical up to here (the CFG pair, csrc/net_build.hip build_attn):
   // qB: batches of Q; batch b reads the queries of batch b - qB when b >= qB (0: B, one per batch; B / 2 <= qB <= B)
   // plan_B: select the kernel as for a problem of plan_B batches (this launch is a batch prefix of it); 0: B
   int qB = 0;

@@ -1,4 +1,4 @@
-// Architecture plans of the network executor (net.hip): the block lists of the UNet / ControlNet, the hint block and the VAE levels,
+// Architecture plans of the network executor (net_weights.hip, net_build.hip): the block lists of the UNet / ControlNet, the hint block and the VAE levels,
 // mirror of stablediffusioneo_amd/spec.py (itself pinned to the reference constructors by tests/golden/manifest_sd15.json).
 // Standard C++ only (no HIP include): tests/arena_check.cpp compares make_uplan with spec.unet_plan on the host.
 #pragma once

@@ -59,7 +59,7 @@ int sdeo_debug_layernorm_ld_f16(void* y, int ldy, const void* x, int ldx, const 
                                 float eps, void* stream);
 int sdeo_debug_softmax_rows(void* p, int ldp, const float* s, int lds, int rows, int cols, float scale, void* stream);
 
-/* op-level hooks for the LayerNorm fold (tests): the networks use these paths internally (csrc/net.hip build_attn).
+/* op-level hooks for the LayerNorm fold (tests): the networks use these paths internally (csrc/net_build.hip build_attn).
  * fold: w_out = fp16(w * gamma) [rows][c], s_out[rows] = row sums of w_out, b_out[rows] = bias + w beta (bias may be NULL)
  * gemm_stats: sdeo_gemm_f16 (fp16 out) that also writes per-row (sum, sumsq) partials of y: stats fp32 [m][stats_ld][2];
  *   *strips_out = valid partials per row (0: the plan is split-K and cannot emit them; nothing was launched)
@@ -75,14 +75,14 @@ int sdeo_debug_gemm_stats_f16(void* y, int ldy, const void* x, int ldx, const vo
 int sdeo_debug_gemm_ln_f16(void* y, int ldy, const void* x, int ldx, const void* w_folded, int ldw, const float* ln_s,
                            const float* bias_folded, const float* stats, int stats_ld, int strips, int ln_c, int m, int n, int k, int act, float eps, void* workspace, size_t workspace_bytes, void* stream);
 int sdeo_debug_row_stats_f16(float* stats, int stats_ld, const void* x, int ldx, int rows, int c, void* stream);
-/* [conv whose epilogue emits the GroupNorm partials of its output] -> [normalise-only GroupNorm]: the pair csrc/net.hip builds for
+/* [conv whose epilogue emits the GroupNorm partials of its output] -> [normalise-only GroupNorm]: the pair csrc/net_build.hip builds for
  * every conv that feeds a GroupNorm.  *slots = partial entries per image (0: this shape's plan cannot emit them, nothing ran);
  * partials >= n * slots * groups * 2 floats (+ n * groups * 2 when slots > 128) */
 int sdeo_debug_conv2d_gn_f16(void* ynorm, void* y, const void* x, const void* w_krsc, const float* bias, const void* res, int n, int h,
                              int w, int cin, int cout, int ksize, int stride, int upsample2x, const float* gamma, const float* beta,
                              int groups, float eps, int with_silu, float* partials, size_t partial_floats, int* slots, void* stream);
 
-/* op-level hooks of the shared prefix of the CFG pair (tests; csrc/net.hip build_attn): operands that a full-batch launch reads from a
+/* op-level hooks of the shared prefix of the CFG pair (tests; csrc/net_build.hip build_attn): operands that a full-batch launch reads from a
  * half-batch tensor.
  * gemm_res_rows: sdeo_gemm_f16 (fp16 out) whose residual holds res_rows rows (m / 2 <= res_rows <= m): output row r adds residual
  *   row r - res_rows when r >= res_rows.  stats != NULL: also the per-row partials as sdeo_debug_gemm_stats_f16, except that with a

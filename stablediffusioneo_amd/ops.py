@@ -288,7 +288,7 @@ def gemm_with_row_stats(x, w, bias=None, res=None):
 
 def gemm_res_rows(x, w, res, res_rows, bias=None, want_stats=False):
     """y = x w^T (+bias) + res[r mod res_rows] in fp16: the residual holds res_rows = m / 2 rows that both halves of the batch add
-    (the shared prefix of the CFG pair, csrc/net.hip build_attn).  res may be a column block of a wider tensor.
+    (the shared prefix of the CFG pair, csrc/net_build.hip build_attn).  res may be a column block of a wider tensor.
     want_stats: returns (y, stats, strips) as gemm_with_row_stats."""
     lib = _lib.load()
     _need_cuda(x, w, res)
@@ -411,7 +411,7 @@ def attention(q, k, v, heads, tk=None, scale=None, causal=False, out=None):
 
 def attention_q_shared(q, k, v, heads, tk=None, scale=None):
     """attention() whose q (B/2,Tq,H*d) is shared by the two halves of the batch of k / v (B,...): batch i attends with the queries of
-    batch i mod B/2 (the cross-attention of the CFG pair's shared prefix, csrc/net.hip build_attn).  Returns (B,Tq,H*d)."""
+    batch i mod B/2 (the cross-attention of the CFG pair's shared prefix, csrc/net_build.hip build_attn).  Returns (B,Tq,H*d)."""
     lib = _lib.load()
     _need_cuda(q, k, v)
     qb, tq, c = q.shape

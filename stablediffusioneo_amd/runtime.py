@@ -10,15 +10,14 @@ import torch
 from . import _lib, spec as S
 from ._lib import SdeoConfig, check, cur_stream, ptr
 
-HINT_CACHED, CONTEXT_CACHED, NO_CONTROL = 1, 2, 4
-STEP_LATENT_STAGED = 16
-STEP_HINT_SHARED = 32
-STEP_V_PREDICTION = 64
-STEP_UNGUIDED = 128
+# the flags of include/sdeo.h, read from it like every other constant
+HINT_CACHED, CONTEXT_CACHED, NO_CONTROL = (_lib.header_constant("SDEO_" + n) for n in ("HINT_CACHED", "CONTEXT_CACHED", "NO_CONTROL"))
+STEP_LATENT_STAGED, STEP_HINT_SHARED, STEP_V_PREDICTION, STEP_UNGUIDED = (
+    _lib.header_constant("SDEO_STEP_" + n) for n in ("LATENT_STAGED", "HINT_SHARED", "V_PREDICTION", "UNGUIDED"))
 
 
 def TIMESTEP_ROW(i: int) -> int:
-    """SDEO_TIMESTEP_ROW(i) of include/sdeo.h: run at row i of the table set with `set_timestep_table`"""
+    """SDEO_TIMESTEP_ROW(i) of include/sdeo.h (a function-like macro, so restated): run at row i of the table set with `set_timestep_table`"""
     return 8 | (int(i) << 8)
 
 

@@ -6,7 +6,7 @@ both tests build from a row.
 A row is (B, heads, Tq, Tk, d, causal, form, name):
   form "contig"   q / k / v / out contiguous, ld = heads * d                                        (parity)
        "gather"   query i is a scaled copy of key pi(i), pi onto [0, Tk): every key position counts (see gather_operands)
-       "self"     q | k | v are the three column blocks of one [B][T][3C] buffer (csrc/net.hip build_attn, attn1; csrc/clip.hip)
+       "self"     q | k | v are the three column blocks of one [B][T][3C] buffer (csrc/net_build.hip build_attn, attn1; csrc/clip.hip)
        "cross"    q at ld = C, k | v the halves of a [B][TkS][2C] context buffer, rows Tk..TkS-1 filled with large finite values (attn2)
        "kvpad"    k and v in separate buffers whose rows are padded differently (TkS != TkSv)
        "outblock" the output is a column block of a wider, row-padded buffer

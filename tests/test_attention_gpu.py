@@ -75,7 +75,7 @@ def _pad_rows(t, rows, fill):
 
 @pytest.mark.parametrize("case", A.FORM_CASES, ids=A.case_id)
 def test_operand_form(ops, case):
-    """the operand forms of csrc/net.hip build_attn / build_vae_attn and csrc/clip.hip: strides change addresses, not arithmetic, so
+    """the operand forms of csrc/net_build.hip build_attn / build_vae_attn and csrc/clip.hip: strides change addresses, not arithmetic, so
     every form agrees bit for bit with the same call on contiguous copies (which meets the parity bound)"""
     b, h, tq, tk, d, causal, form, _ = case
     c = h * d

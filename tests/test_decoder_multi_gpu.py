@@ -1,4 +1,4 @@
-"""The fused decoder's thirteen zero convs as ONE multi-problem launch (csrc/net.hip build_unet_decoder_multi): sdeo_apply_model on the
+"""The fused decoder's thirteen zero convs as ONE multi-problem launch (csrc/net_build.hip build_unet_decoder_multi): sdeo_apply_model on the
 tiny configuration, N = 2, against the reference goldens (tests/golden/tiny_nets.npz) and the oracle at the tolerance of
 tests/test_nets_gpu.py (max error 2e-2, mean error 4e-3 of the output's scale), with the control scales that reach the launch
 through its kernel arguments: all one, all zero (a zero scale still writes the skip: the UNet without control), non-uniform, and

@@ -462,7 +462,7 @@ def test_gemm_with_folded_layernorm(ops, case):
 @pytest.mark.parametrize("case", [(256, 64), (512, 320), (96, 640)], ids=str)
 def test_composed_ff2_proj_out(ops, case):
     """ff.net.2 followed by the SpatialTransformer's proj_out (`attention.py:75-76`, `:385`, `:431-450`) as ONE Linear over the
-    row-concatenated operand [g | t] (stablediffusioneo_amd/csrc/net.hip: ComposeJob, built at weight finalisation):
+    row-concatenated operand [g | t] (stablediffusioneo_amd/csrc/net_handle.h: ComposeJob, built at weight finalisation):
     proj_out(ff2(g) + t) + x  ==  [g | t] [ (Wp W2) | Wp ]^T + (Wp b2 + bp) + x.  Reference: the two Linear maps in fp32."""
     rows, c = case
     k2 = 4 * c

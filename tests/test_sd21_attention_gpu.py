@@ -1,5 +1,5 @@
 """The attention launches of the SD-2.x nets (heads 5 / 10 / 20 / 20 at d = 64 on the CFG pair) and of the OpenCLIP-H text tower
-(16 causal heads at d = 64), at their real sizes and in the operand form csrc/net.hip / csrc/clip.hip pass: "self" = q | k | v column
+(16 causal heads at d = 64), at their real sizes and in the operand form csrc/net_build.hip / csrc/clip.hip pass: "self" = q | k | v column
 blocks of one [B][T][3C] buffer, "cross" = k | v halves of a row-padded [B][TkS][2C] context buffer.  No kernel here is new: each row
 names the instantiation it selects, which tests/test_attention_gpu.py already runs at other shapes, and is held to the same fp64
 reference and the same per-kernel bound (|err| <= 3e-3 + 3e-3 |ref|)."""

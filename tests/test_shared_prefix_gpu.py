@@ -1,4 +1,4 @@
-"""The shared prefix of the CFG pair (csrc/net.hip build_shared_prefix): sdeo_ddim_step runs input_blocks.1 up to its cross-attention
+"""The shared prefix of the CFG pair (csrc/net_build.hip build_shared_prefix): sdeo_ddim_step runs input_blocks.1 up to its cross-attention
 on the conditional half of [x; x] only, and the full-batch launches behind it read the half-batch tensors for both halves.
 
 Every comparison is torch.equal against the unshared path: a half-batch launch takes the kernel plan of the full-batch problem and the

@@ -1,7 +1,7 @@
-"""The weight store of csrc/handle_common.h, pinned from its three doors: SdeoRuntime (csrc/net.hip), ClipRuntime (csrc/clip.hip) and
+"""The weight store of csrc/handle_common.h, pinned from its three doors: SdeoRuntime (csrc/net_weights.hip), ClipRuntime (csrc/clip.hip) and
 HedRuntime (csrc/hed.hip) run ONE contract: the registry equals the spec.param_spec_* inventory, unknown / mis-shaped tensors are
 refused with the door's own function name, finalize reports missing tensors by name in registry order, and a tensor re-loaded after
-finalize (the upload buffer was freed; net.hip rebuilds its LayerNorm folds and composed matrices) leaves the output bit-identical.
+finalize (the upload buffer was freed; net_weights.hip rebuilds its LayerNorm folds and composed matrices) leaves the output bit-identical.
 Every error path returns from host-side validation before any launch."""
 import ctypes as C
 
