@@ -106,6 +106,18 @@ int sdeo_layernorm_f16(void* y, const void* x, const float* gamma, const float* 
 int sdeo_attention_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int b,
                        int heads, int tq, int tk, int tk_stride, int v_batch_stride, int d, float scale, void* stream);
 
+/* O = softmax(Q K^T scale) V + weight2 * softmax(Q K2^T scale) V2: two key sets, two softmaxes, one launch.
+ * The decoupled cross-attention of an image-prompt adapter: K / V are the text keys, K2 / V2 a few image tokens.  Q, K, V, O as
+ * sdeo_attention_f16 takes them; K2 [b][tk2_stride][ldk2], V2 [b][v2_batch_stride][ldv2], 1 <= tk2 <= 64, keys >= tk2 masked.  Both
+ * normalised terms and their sum are formed in fp32 and rounded to fp16 once; weight2 = 0 gives the bits of sdeo_attention_f16 wherever
+ * that runs its one-wave-per-query-block form (tk < 128, or d >= 88).  Head dim d: 8..96 in steps of 8, 120, 128, 152, 160.
+ * Refused before any device call, each with its own message: a null operand, tk2 outside 1..64, a non-finite weight2, another head
+ * dim, operands that are not 16-byte aligned or ld* that are no multiples of 8 (ldo: 4). */
+int sdeo_attention2_f16(void* o, int ldo, const void* q, int ldq,
+                        const void* k, int ldk, const void* v, int ldv, int tk, int tk_stride, int v_batch_stride,
+                        const void* k2, int ldk2, const void* v2, int ldv2, int tk2, int tk2_stride, int v2_batch_stride,
+                        float weight2, int b, int heads, int tq, int d, float scale, void* stream);
+
 /* as sdeo_attention_f16 with the causal mask of the CLIP text transformer: key j is masked for query t when j > t
  * (needs tq == tk) */
 int sdeo_attention_causal_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int b,
@@ -255,6 +267,24 @@ int sdeo_set_activation_precision(sdeo_handle h, int bits, int min_rows);
 int sdeo_num_weights(sdeo_handle h);
 int sdeo_weight_info(sdeo_handle h, int i, const char** name, int64_t dims[4], int* ndim);
 
+/* Image-prompt adapter (IP-Adapter, decoupled cross-attention): every UNet cross-attention gets a second key / value projection over
+ * num_tokens image tokens with a softmax of its own,  O = softmax(Q K_text^T s) V_text + ip_scale * softmax(Q K_ip^T s) V_ip,  in front
+ * of to_out.  One launch per cross-attention as before (sdeo_attention2_f16): the step's dispatch count does not change.
+ * sdeo_enable_ip_adapter: after sdeo_create[_ex], before the first sdeo_load_weight.  num_tokens 1..64 (4 = ip-adapter_sd15, 16 = the
+ *   "plus" token count).  Registers, for every UNet attention block (the control networks get none),
+ *   model.diffusion_model.<block>.transformer_blocks.0.attn2.to_k_ip.weight and ...to_v_ip.weight, [C][context_dim], no bias, behind
+ *   everything registered at that moment: existing offsets do not move.  A handle that never calls it is bit for bit what it was.
+ *   Refused on such a handle, each with its own message: sdeo_finalize_weights after sdeo_set_weight_precision(h, 8); sdeo_lora_apply on
+ *   a to_k_ip / to_v_ip name.
+ * sdeo_set_ip_tokens: tokens fp32 [n][num_tokens][context_dim], device.  Projects them into the K_ip | V_ip of every cross-attention
+ *   (one GEMM each), once per image prompt; the forwards and steps read the result by address, so a captured step sees new tokens
+ *   without re-capture.  Only launches: capturable.
+ * sdeo_set_ip_scale: ip_scale of the following forwards, read at launch like the control scales (a captured step bakes it in).
+ *   Default 1; sdeo_configure resets it to 1.  0 gives the bits of a handle without the adapter. */
+int sdeo_enable_ip_adapter(sdeo_handle h, int num_tokens);
+int sdeo_set_ip_tokens(sdeo_handle h, const float* tokens, void* stream);
+int sdeo_set_ip_scale(sdeo_handle h, float scale);
+
 /* Fix the problem size (allocate_buffers equivalent): n = images per call of the *_forward functions
  * (the CFG pair counts as 2), latent h x w.  Allocates the activation arena once. */
 int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w);
@@ -273,7 +303,7 @@ int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w);
 #define SDEO_MAX_TABLE_STEPS 128
 
 /* State a handle keeps between calls, and who may read it (the cache contract).
- * Four items outlive a call.  The fast paths read them by address and on the caller's word (a *_CACHED flag, SDEO_TIMESTEP_ROW, a fused
+ * Five items outlive a call.  The fast paths read them by address and on the caller's word (a *_CACHED flag, SDEO_TIMESTEP_ROW, a fused
  * sdeo_*_step, SDEO_STEP_LATENT_STAGED), so the handle keeps a host-side record (csrc/cache_record.h: one type, one transition per
  * "filled by" / "cleared by" entry below, one check per "read by" entry) of what each holds and checks it before the first
  * device call of every entry point: a read is either right -- bit-identical to the same call given the inputs the cache was filled
@@ -297,7 +327,14 @@ int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w);
  *   staged fp16 latent        every sdeo_*_step that succeeds (for the    sdeo_configure, sdeo_apply_model,   SDEO_STEP_LATENT_STAGED
  *                             x it updated)                               sdeo_unet_forward,
  *                                                                         sdeo_controlnet_forward[_net]
+ *   image-prompt K / V        sdeo_set_ip_tokens                          sdeo_configure                      every call that runs the UNet
+ *   (handles with                                                                                             on such a handle:
+ *   sdeo_enable_ip_adapter)                                                                                   sdeo_unet_forward,
+ *                                                                                                             sdeo_apply_model, every
+ *                                                                                                             sdeo_*_step
  *
+ *   - sdeo_lora_commit / sdeo_lora_clear do not clear the image-prompt K / V: no adapter can touch the ip matrices they were computed
+ *     with (sdeo_lora_apply refuses a to_k_ip / to_v_ip name).
  *   - Every staged context has an epoch.  A call that reads the K / V of both sides from the cache (sdeo_apply_model with control and
  *     SDEO_CONTEXT_CACHED, every sdeo_*_step) needs both computed from the same staged context: after sdeo_controlnet_forward,
  *     sdeo_unet_forward or an SDEO_NO_CONTROL call given another context the two sides hold two prompts, and such a call is refused until

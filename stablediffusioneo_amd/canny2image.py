@@ -43,7 +43,7 @@ def _default_canny():
 class hackathon():
 
     def initialize(self, weights="synthetic:0", config="sd15", apply_canny=None, text_encoder=None, vae_encoder=False, sampler="ddim",
-                   loras=()):
+                   loras=(), ip_adapter=None):
         """text_encoder: None = `synthetic_text_encoder` (seeded stand-in contexts); "clip:<tokenizer dir>" = the
         FrozenCLIPEmbedder mirror on the HIP path (weights from the same source as the UNet's: synthetic seed or the
         checkpoint's `cond_stage_model.transformer.text_model.*`); bare "clip" is accepted only with synthetic weights (the
@@ -59,9 +59,12 @@ class hackathon():
         classifier-free guidance and 1.0 drops the unconditional branch; full LCM checkpoints with `time_embedding.cond_proj` are not
         supported and are refused by the loader's unknown-key report.
         loras: kohya-ss LoRA / LoCon adapters merged into the weights at start-up, [(path or dict, unet_scale[, te_scale]), ...]
-        (`set_loras`); te_scale needs the "clip" / "openclip" text encoder."""
+        (`set_loras`); te_scale needs the "clip" / "openclip" text encoder.
+        ip_adapter: an image-prompt adapter (IP-Adapter) on every UNet cross-attention: the path of an ip-adapter_sd15 .bin / .safetensors
+        file, its dict, or "synthetic:<seed>[:T]" (seeded ip matrices and projection, T tokens, default 4).  `process(..., ip_image_embeds=)`
+        then takes the CLIP image embedding of the image prompt (there is no CLIP vision tower here: the caller computes it)."""
         self.apply_canny = apply_canny or _default_canny()
-        return self._init_model(weights, config, text_encoder, vae_encoder, sampler=sampler, loras=loras)
+        return self._init_model(weights, config, text_encoder, vae_encoder, sampler=sampler, loras=loras, ip_adapter=ip_adapter)
 
     def set_loras(self, loras=()):
         """Swap the adapters between `process` calls: back to the base weights, every adapter of `loras` merged on the device
@@ -78,7 +81,7 @@ class hackathon():
                 target.lora_commit()
         return unsupported
 
-    def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim", extra_control=(), loras=()):
+    def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim", extra_control=(), loras=(), ip_adapter=None):
         """text encoder, ControlLDM and sampler of `initialize` (shared with hed2image).  extra_control: the weights of each extra
         control network (multi2image): a checkpoint path, a state dict with `control_model.*` names or "synthetic:<seed>"."""
         if sampler not in ("ddim", "dpmpp_2m", "dpmpp_2m_sde", "lcm"):
@@ -97,7 +100,26 @@ class hackathon():
                 ccfg = dataclasses.replace(S.CLIP_TINY21, width=S.UNET_TINY21.context_dim) if tiny else S.CLIP_SD21
                 text_encoder = FrozenOpenCLIPEmbedder(version=tok_dir, layer="penultimate", config=ccfg,
                                                       allow_hash_tokenizer=synthetic and tok_dir is None)
-        self.model = create_model(config, cond_stage_model=text_encoder, vae_encoder=vae_encoder, extra_controlnets=len(extra_control))
+        # image-prompt adapter: the token count comes from the file's projection (or the synthetic spec) before the handle exists
+        ip_file, ip_seed, ip_tokens = None, None, 0
+        if isinstance(ip_adapter, str) and ip_adapter.startswith("synthetic"):
+            parts = ip_adapter.split(":")
+            ip_seed, ip_tokens = (int(parts[1]) if len(parts) > 1 else 0), (int(parts[2]) if len(parts) > 2 else 4)
+        elif ip_adapter is not None:
+            from . import ip_adapter as IPA
+            ip_file = ip_adapter if isinstance(ip_adapter, dict) else IPA.read_file(ip_adapter)
+            proj = IPA.split_groups(ip_file)[0]
+            if "proj.weight" in proj and "norm.weight" in proj:
+                ip_tokens = int(proj["proj.weight"].shape[0]) // int(proj["norm.weight"].shape[0])
+            else:
+                ip_tokens = 4       # (a Resampler file: refused with its own message by load_ip_adapter below)
+        self.model = create_model(config, cond_stage_model=text_encoder, vae_encoder=vae_encoder, extra_controlnets=len(extra_control),
+                                  ip_adapter_tokens=ip_tokens)
+        if ip_seed is not None:
+            from . import ip_adapter as IPA
+            ip_file = IPA.synthetic_adapter(self.model.rt.ucfg, ip_tokens, ip_seed)
+        if ip_file is not None:
+            self.model.load_ip_adapter(ip_file)      # before the base weights: they finalise the handle
         if text_encoder is None:      # the seeded stand-in, as wide as the chosen config's context
             text_encoder = functools.partial(synthetic_text_encoder, length=self.model.rt.ucfg.context_len, dim=self.model.rt.ucfg.context_dim)
             self.model.cond_stage_model = text_encoder
@@ -106,7 +128,14 @@ class hackathon():
             self._load_with_extra(weights, extra_control)
         elif isinstance(weights, str) and weights.startswith("synthetic"):
             seed = int(weights.split(":")[1]) if ":" in weights else 0
-            self.model.rt.load_synthetic(seed)
+            if ip_file is None:
+                self.model.rt.load_synthetic(seed)
+            else:                                     # everything but the adapter's own matrices, loaded above
+                rt = self.model.rt
+                for name, shape in rt.expected_weights().items():
+                    if "_ip.weight" not in name:
+                        rt.load_tensor(name, S.synth_tensor(name, shape, seed))
+                rt._finalize()
             if hasattr(self.text_encoder, "transformer"):
                 self.text_encoder.transformer.load_synthetic(seed)
         elif isinstance(weights, dict):
@@ -150,7 +179,7 @@ class hackathon():
                         rt.load_tensor(prefix + k[len(S.NS_CONTROL):], v, False)
         if synthetic(weights):
             for name, shape in expected.items():
-                if not name.startswith(prefixes):
+                if not name.startswith(prefixes) and not ("_ip.weight" in name and getattr(self.model, "ip_proj", None) is not None):
                     rt.load_tensor(name, S.synth_tensor(name, shape, seed_of(weights)))
             rt._finalize()
             if hasattr(self.text_encoder, "transformer"):
@@ -160,8 +189,13 @@ class hackathon():
             self.model.load_state_dict(sd)       # (the extra nets are loaded: this finalises everything)
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, ddim_steps, guess_mode,
-                strength, scale, seed, eta, low_threshold, high_threshold, x_T=None, init_image=None, denoise_strength=0.75, mask_image=None):
-        """scale == 1.0 is no guidance (`cldm/ddim_hacked.py:188-189`): the unconditional branch is not run, and with any sampler the
+                strength, scale, seed, eta, low_threshold, high_threshold, x_T=None, init_image=None, denoise_strength=0.75, mask_image=None,
+                ip_image_embeds=None, ip_tokens=None, ip_scale=1.0):
+        """ip_image_embeds (1 or num_samples, embed_dim): the CLIP image embedding of an image prompt, projected by the adapter given to
+        `initialize(ip_adapter=)`; or ip_tokens (1 or num_samples, T, context_dim) from a projection run elsewhere; ip_scale weights the
+        image term (0: the image prompt is off, the result is that of a pipeline without an adapter).  The unconditional half gets the
+        projection of a zero embedding (zero tokens with ip_tokens), as in the adapter's own pipeline.
+        scale == 1.0 is no guidance (`cldm/ddim_hacked.py:188-189`): the unconditional branch is not run, and with any sampler the
         loop's captured steps are the un-paired ones (SDEO_STEP_UNGUIDED), one forward per image and step.
         init_image (HxWx3 uint8, optional): img2img with upstream `scripts/img2img.py` semantics -- the image is resized like the
         input, encoded (posterior sample), noised to t_enc = int(denoise_strength * ddim_steps) by stochastic_encode and denoised from
@@ -190,10 +224,11 @@ class hackathon():
                 control = control.permute(0, 3, 1, 2).contiguous()
             return self._sample(control, prompt, a_prompt, n_prompt, num_samples, H, W, ddim_steps, guess_mode, strength, scale, seed, eta,
                                 x_T=x_T, init_image=init_image, image_resolution=image_resolution, denoise_strength=denoise_strength,
-                                mask_image=mask_image)
+                                mask_image=mask_image, ip_image_embeds=ip_image_embeds, ip_tokens=ip_tokens, ip_scale=ip_scale)
 
     def _sample(self, control, prompt, a_prompt, n_prompt, num_samples, H, W, ddim_steps, guess_mode, strength, scale, seed, eta, x_T=None,
-                init_image=None, image_resolution=None, denoise_strength=0.75, mask_image=None):
+                init_image=None, image_resolution=None, denoise_strength=0.75, mask_image=None, ip_image_embeds=None, ip_tokens=None,
+                ip_scale=1.0):
         """everything of `process` after the hint (`canny2image_torch.py:40-71`): seeding, conditioning, the DDIM loop and the decode
         to uint8 HWC images; control is the (num_samples, 3, H, W) fp32 hint on the device -- or, with several control networks, the list
         of their hints, and strength one float per net"""
@@ -203,6 +238,7 @@ class hackathon():
             random.seed(seed)
             np.random.seed(seed)
             torch.manual_seed(seed)       # pytorch_lightning.seed_everything (`canny2image_torch.py:42`)
+            self._set_image_prompt(ip_image_embeds, ip_tokens, ip_scale)
             control = list(control) if isinstance(control, (list, tuple)) else [control]
             cond = {"c_concat": control,
                     "c_crossattn": [self.model.get_learned_conditioning([prompt + ", " + a_prompt] * num_samples)]}
@@ -225,6 +261,30 @@ class hackathon():
             x_samples = self.model.decode_first_stage_uint8(samples).cpu().numpy()
             results = [x_samples[i] for i in range(num_samples)]
         return results
+
+    def set_image_prompt(self, ip_image_embeds=None, ip_tokens=None, ip_scale=1.0):
+        """The image prompt of the following `process` calls that give none themselves (scribble2image.process keeps the upstream
+        signature and takes it this way); arguments as `process(..., ip_image_embeds=, ip_tokens=, ip_scale=)`."""
+        self._image_prompt = (ip_image_embeds, ip_tokens, ip_scale)
+        return self
+
+    def _set_image_prompt(self, ip_image_embeds, ip_tokens, ip_scale):
+        """the image prompt of this request on the model; a pipeline with an adapter needs one with every request"""
+        m = self.model
+        if ip_image_embeds is None and ip_tokens is None and getattr(self, "_image_prompt", None) is not None:
+            ip_image_embeds, ip_tokens, ip_scale = self._image_prompt
+        if not m.rt.ip_adapter_tokens:
+            if ip_image_embeds is not None or ip_tokens is not None:
+                raise ValueError("ip_image_embeds / ip_tokens need an adapter: initialize(..., ip_adapter=...)")
+            return
+        if (ip_image_embeds is None) == (ip_tokens is None):
+            raise ValueError("this pipeline has an image-prompt adapter: give exactly one of ip_image_embeds and ip_tokens, to process or "
+                             "to set_image_prompt (ip_scale=0 switches the image prompt off)")
+        if ip_tokens is not None:
+            m.set_ip_tokens(ip_tokens)
+        else:
+            m.set_ip_image_embeds(ip_image_embeds)
+        m.ip_scale = float(ip_scale)
 
     def _init_latent(self, init_image, image_resolution, hw, num_samples):
         """(resized init image HxWx3 uint8 on the host, z0 = get_first_stage_encoding(encode_first_stage(it)) for num_samples copies)"""

@@ -217,11 +217,79 @@ class ControlLDM:
         """every net's scales: part of the key of every captured graph"""
         return tuple(v for row in self.per_net_scales() for v in row)
 
+    # -- image prompts (IP-Adapter; the runtime was created with ip_adapter_tokens = T).  The image tokens are conditioning like the
+    # text context: the conditional request carries the image's tokens, the unconditional one the projection of a zero embedding, as in
+    # the adapter's own pipeline.  They are kept here per role and travel in the conditioning dicts as "c_ip" (`with_ip`).
+    def load_ip_adapter(self, adapter):
+        """Load an IP-Adapter file (a path or its state dict) into a model created with ip_adapter_tokens: the to_k_ip / to_v_ip matrices
+        go to the runtime, the image projection stays here (`stablediffusioneo_amd.ip_adapter`).  Call it before the base weights are
+        finalised (`load_state_dict`), like the extra control networks' weights."""
+        from ..ip_adapter import load_ip_adapter
+        self.ip_proj = load_ip_adapter(self.rt, adapter)
+        return self
+
+    def set_ip_tokens(self, cond, uncond=None):
+        """Raw image tokens (b or 1, T, context_dim) for the conditional requests; uncond: for the unconditional ones (None: zeros)."""
+        t_, cd = self.rt.ip_adapter_tokens, self.rt.ucfg.context_dim
+        if not t_:
+            raise RuntimeError("set_ip_tokens: the model was created without an image-prompt adapter (create_model(..., ip_adapter_tokens=T))")
+        prep = lambda x: x.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        cond = prep(cond)
+        uncond = torch.zeros_like(cond) if uncond is None else prep(uncond)
+        for name, x in (("cond", cond), ("uncond", uncond)):
+            if x.dim() != 3 or tuple(x.shape[1:]) != (t_, cd):
+                raise ValueError(f"set_ip_tokens: {name} tokens of shape {tuple(x.shape)}, the adapter takes (b, {t_}, {cd})")
+        # The samplers key their conditioning caches on the identity of the tensors they are given (storage, in-place version, shape):
+        # tokens of the same shape are copied INTO the kept tensors, which bumps their version; fresh tensors could land on the
+        # address the previous ones had and look unchanged.
+        old = getattr(self, "_ip", None)
+        if old is not None and old["cond"].shape == cond.shape and old["uncond"].shape == uncond.shape:
+            old["cond"].copy_(cond)
+            old["uncond"].copy_(uncond)
+        else:
+            self._ip = {"cond": cond.clone(), "uncond": uncond.clone()}
+        return self
+
+    def set_ip_image_embeds(self, cond_embeds, uncond_embeds=None, scale=1.0):
+        """CLIP image embeddings (b or 1, embed_dim) -> tokens through the loaded adapter's ImageProjModel (torch fp32 on the device, once
+        per image).  uncond_embeds None: the projection of zeros."""
+        if getattr(self, "ip_proj", None) is None:
+            raise RuntimeError("set_ip_image_embeds: no image projection (load_ip_adapter first, or give tokens to set_ip_tokens)")
+        cond_embeds = cond_embeds.detach().to(device=self.device, dtype=torch.float32)
+        uncond_embeds = torch.zeros_like(cond_embeds) if uncond_embeds is None else uncond_embeds.detach().to(device=self.device, dtype=torch.float32)
+        self.set_ip_tokens(self.ip_proj(cond_embeds), self.ip_proj(uncond_embeds))
+        self.ip_scale = float(scale)
+        return self
+
+    ip_scale = 1.0
+
+    def with_ip(self, cond, role, b):
+        """`cond` with the image tokens of `role` ("cond" / "uncond") for b images under "c_ip", unless it carries some already or the
+        model has no adapter.  Stored tokens of one image serve any b (a view: its identity is the stored tensor's)."""
+        if not self.rt.ip_adapter_tokens or not isinstance(cond, dict) or cond.get("c_ip") is not None:
+            return cond
+        if getattr(self, "_ip", None) is None:
+            raise RuntimeError("this model has an image-prompt adapter but no image tokens: call set_ip_image_embeds or set_ip_tokens first")
+        t = self._ip[role]
+        if t.shape[0] not in (1, b):
+            raise ValueError(f"{t.shape[0]} sets of image tokens for {b} images")
+        return {**cond, "c_ip": [t if t.shape[0] == b else t.expand(b, -1, -1)]}
+
+    def sync_ip_scale(self):
+        """hand `ip_scale` to the runtime when it differs (sdeo_configure resets the library's to 1)"""
+        if self.rt.ip_adapter_tokens and self.rt.ip_scale != float(self.ip_scale):
+            self.rt.set_ip_scale(self.ip_scale)
+
     def apply_model(self, x_noisy, t, cond, *args, flags: int = 0, out=None, **kwargs):
-        """`cldm/cldm.py:328-341`.  With K control networks the channel concatenation of c_concat holds K hints: chunk j is net j's."""
+        """`cldm/cldm.py:328-341`.  With K control networks the channel concatenation of c_concat holds K hints: chunk j is net j's.
+        With an image-prompt adapter cond["c_ip"] holds the image tokens of the n images (absent: the stored conditional ones)."""
         assert isinstance(cond, dict)
         cond_txt = torch.cat(cond["c_crossattn"], 1) if cond["c_crossattn"] is not None else None
         self.rt.configure(x_noisy.shape[0], x_noisy.shape[2], x_noisy.shape[3])
+        if self.rt.ip_adapter_tokens:
+            self.sync_ip_scale()
+            if not (flags & CONTEXT_CACHED):      # the image tokens are conditioning: cached with the context K / V
+                self.rt.set_ip_tokens(torch.cat(self.with_ip(cond, "cond", x_noisy.shape[0])["c_ip"], 0))
         if cond["c_concat"] is None:
             return self.rt.apply_model(x_noisy, None, t, cond_txt, None, self.only_mid_control, flags & CONTEXT_CACHED, out)
         hint = torch.cat(cond["c_concat"], 1)

@@ -131,6 +131,12 @@ def draw_rows(img, x0, mask_rows, step_rows, live, first, last):
             step_rows[i].copy_(torch.randn(img.shape, device=img.device))
 
 
+def ip_key(m):
+    """what a captured step bakes in of the model's image-prompt adapter: whether it is on, and the scale (new tokens alone rewrite
+    K_ip | V_ip in place and need no re-capture)"""
+    return (m.rt.ip_adapter_tokens, float(m.ip_scale)) if getattr(m.rt, "ip_adapter_tokens", 0) else None
+
+
 def captured_loop(owner, img, mask, x0, time_range, live, shape_key, log_every_t, intermediates, state, first_step, emit):
     """The loop of a sampler `owner` with step 1 run eagerly (it computes the hint block and the context K / V of THIS image into the
     runtime's caches) and steps 2..S replayed from captured graphs.  The graphs read the latent (owner._loop_x) and the sampler's second
@@ -372,7 +378,7 @@ class DDIMSampler(object):
         hint_shared = not unguided and self._ident(c["c_concat"]) == self._ident(uc["c_concat"])
         shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), m.scales_key(), bool(m.only_mid_control),
                      getattr(self, "_schedule_key", None), LOOP_GRAPH_STEPS, hint_shared, m.parameterization,
-                     None if mask is None else tuple(mask.shape), unguided)
+                     None if mask is None else tuple(mask.shape), unguided, ip_key(m))
         a_t, a_p, s1m = self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sqrt_one_minus_alphas
 
         def first_step(img, pred):
@@ -403,6 +409,11 @@ class DDIMSampler(object):
     def _eps_pair(self, x, c, t, uc, scale):
         """eps for (cond, uncond); returns (eps_c, eps_u) with eps_u None when guidance is off."""
         m = self.model
+        b = x.shape[0]
+        has_ip = bool(getattr(getattr(m, "rt", None), "ip_adapter_tokens", 0))
+        if has_ip:      # the image tokens of each role travel with its conditioning (ControlLDM.with_ip)
+            c = m.with_ip(c, "cond", b)
+            uc = m.with_ip(uc, "uncond", b) if uc is not None and scale != 1. else uc
         if uc is None or scale == 1.:
             return m.apply_model(x, t, c), None
         fusable = (hasattr(m, "rt") and isinstance(c, dict) and isinstance(uc, dict) and c.get("c_concat") is not None
@@ -410,12 +421,15 @@ class DDIMSampler(object):
         if not fusable:
             # e.g. guess mode: the unconditional branch runs without ControlNet (`canny2image_torch.py:48`)
             return m.apply_model(x, t, c), m.apply_model(x, t, uc)
-        b = x.shape[0]
 
         ident = self._ident
         key = (ident(c["c_concat"]), ident(uc["c_concat"]), ident(c["c_crossattn"]), ident(uc["c_crossattn"]), tuple(x.shape))
+        if has_ip:      # new image tokens refill K_ip | V_ip like a new context; the scale is set on the runtime at every forward
+            key += (ident(c["c_ip"]), ident(uc["c_ip"]))
         if key == self._cache_key:
             rt = m.rt.configure(2 * b, x.shape[2], x.shape[3])
+            if has_ip:
+                m.sync_ip_scale()
             if USE_GRAPH:
                 eps2 = rt.apply_model_graphed(torch.cat([x, x]), torch.cat([t, t]), m.net0_scales(), m.only_mid_control)
             else:
@@ -425,6 +439,8 @@ class DDIMSampler(object):
             hint_c, hint_u = torch.cat(c["c_concat"], 1), torch.cat(uc["c_concat"], 1)
             ctx_c, ctx_u = torch.cat(c["c_crossattn"], 1), torch.cat(uc["c_crossattn"], 1)
             pair = {"c_concat": [torch.cat([hint_c, hint_u])], "c_crossattn": [torch.cat([ctx_c, ctx_u])]}
+            if has_ip:
+                pair["c_ip"] = [torch.cat(c["c_ip"] + uc["c_ip"], 0)]
             eps2 = m.apply_model(torch.cat([x, x]), torch.cat([t, t]), pair)
             self._cache_key = key
         return eps2[:b], eps2[b:]

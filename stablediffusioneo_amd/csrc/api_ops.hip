@@ -144,6 +144,10 @@ const char* sdeo_debug_attention_kernel_name(int B, int H, int Tq, int Tk, int d
   return attention_kernel_name(B, H, Tq, Tk, d, causal);
 }
 
+const char* sdeo_debug_attention2_kernel_name(int B, int H, int Tq, int Tk, int Tk2, int d) {
+  return attention2_kernel_name(B, H, Tq, Tk, Tk2, d);
+}
+
 // Plan query (tests): the ConvGemm of an sdeo_conv2d_nhwc_f16 / sdeo_gemm_f16 call, built by the same fill_conv / fill_gemm, with
 // `act` and armed fp8 weights (fp8 != 0) as that call would see them; returns the tuned-table key it looks up (key10) and the
 // (tile, split-K) the launcher picks.  Host only: no device call.
@@ -391,6 +395,39 @@ int sdeo_debug_attention_qb_f16(void* o, int ldo, const void* q, int ldq, const 
   AttnArgs a{(f16*)o, (const f16*)q, (const f16*)k, (const f16*)v, ldo, ldq, ldk, ldv, b, heads, tq, tk, tk_stride, v_batch_stride, d, scale, 0};
   a.qB = q_batches;
   return attention(a, S(stream));
+}
+
+// check_only: the refusals of the launch without the launch (sdeo_debug_attention2_check)
+static int attention2_api(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int tk, int tk_stride,
+                          int v_batch_stride, const void* k2, int ldk2, const void* v2, int ldv2, int tk2, int tk2_stride,
+                          int v2_batch_stride, float weight2, int b, int q_batches, int heads, int tq, int d, float scale, void* stream,
+                          bool check_only = false) {
+  AttnArgs a{(f16*)o, (const f16*)q, (const f16*)k, (const f16*)v, ldo, ldq, ldk, ldv, b, heads, tq, tk, tk_stride, v_batch_stride, d, scale, 0};
+  a.qB = q_batches;
+  const Attn2Seg s2{(const f16*)k2, (const f16*)v2, ldk2, ldv2, tk2, tk2_stride, v2_batch_stride, weight2};
+  return check_only ? attention2_check(a, s2) : attention2(a, s2, S(stream));
+}
+
+int sdeo_debug_attention2_check(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int tk, int tk_stride,
+                                int v_batch_stride, const void* k2, int ldk2, const void* v2, int ldv2, int tk2, int tk2_stride,
+                                int v2_batch_stride, float weight2, int b, int heads, int tq, int d, float scale) {
+  return attention2_api(o, ldo, q, ldq, k, ldk, v, ldv, tk, tk_stride, v_batch_stride, k2, ldk2, v2, ldv2, tk2, tk2_stride, v2_batch_stride,
+                        weight2, b, 0, heads, tq, d, scale, nullptr, true);
+}
+
+int sdeo_attention2_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int tk, int tk_stride,
+                        int v_batch_stride, const void* k2, int ldk2, const void* v2, int ldv2, int tk2, int tk2_stride,
+                        int v2_batch_stride, float weight2, int b, int heads, int tq, int d, float scale, void* stream) {
+  return attention2_api(o, ldo, q, ldq, k, ldk, v, ldv, tk, tk_stride, v_batch_stride, k2, ldk2, v2, ldv2, tk2, tk2_stride, v2_batch_stride,
+                        weight2, b, 0, heads, tq, d, scale, stream);
+}
+
+int sdeo_debug_attention2_qb_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int tk,
+                                 int tk_stride, int v_batch_stride, const void* k2, int ldk2, const void* v2, int ldv2, int tk2,
+                                 int tk2_stride, int v2_batch_stride, float weight2, int b, int q_batches, int heads, int tq, int d,
+                                 float scale, void* stream) {
+  return attention2_api(o, ldo, q, ldq, k, ldk, v, ldv, tk, tk_stride, v_batch_stride, k2, ldk2, v2, ldv2, tk2, tk2_stride, v2_batch_stride,
+                        weight2, b, q_batches, heads, tq, d, scale, stream);
 }
 
 int sdeo_attention_causal_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int b,

@@ -1,5 +1,5 @@
 // The cache contract of a handle (include/sdeo.h, "State a handle keeps between calls") as one host-only type:
-// what the four items that outlive a call hold, one transition per "filled by" / "cleared by" row of that table, and the checks the
+// what the five items that outlive a call hold, one transition per "filled by" / "cleared by" row of that table, and the checks the
 // entry points make before their first device call.  This header is the contract's only implementation: the entry points of net.hip
 // and net_weights.hip read as record checks, device work and record transitions, and nothing outside this file touches a field.
 // Standard C++ only (no HIP include): tests/cache_record_check.cpp builds it with the host compiler and supplies its own sdeo::fail.
@@ -35,7 +35,12 @@ class CacheRecord {
     ctx_set = 0;
     x0_staged_for = nullptr;
     tab_count = 0;
+    ip_set = false;
   }
+  // sdeo_set_ip_tokens projected the image tokens of an adapter handle into every cross-attention's K_ip | V_ip.  No sdeo_lora_commit
+  // makes them stale: no adapter can touch the ip matrices (sdeo_lora_apply refuses their names), so weights_changed leaves this alone.
+  void ip_staging() { ip_set = false; }                  // (a failed launch leaves the item unset)
+  void ip_filled() { ip_set = true; }
   // the hint block of control network j ran on a hint given now
   void hint_filled(int j) {
     hint_stale[j] = false;
@@ -140,12 +145,20 @@ class CacheRecord {
     return 0;
   }
 
+  // a call that runs the UNet on a handle with the image-prompt adapter enabled (the caller asks only on such a handle)
+  int ip_tokens(const char* who) const {
+    if (!ip_set)
+      return fail("%s: this handle has an image-prompt adapter (sdeo_enable_ip_adapter), but no image-prompt K / V since the last "
+                  "sdeo_configure (call sdeo_set_ip_tokens)", who);
+    return 0;
+  }
+
   friend bool operator==(const CacheRecord& a, const CacheRecord& b) {
     for (int j = 0; j < kMaxNets; ++j)
       if (a.hint_set[j] != b.hint_set[j] || a.hint_stale[j] != b.hint_stale[j]) return false;
     return a.ctx_set == b.ctx_set && a.ctx_stale == b.ctx_stale && a.ctx_epoch == b.ctx_epoch && a.ctx_epoch_of[0] == b.ctx_epoch_of[0] &&
            a.ctx_epoch_of[1] == b.ctx_epoch_of[1] && a.x0_staged_for == b.x0_staged_for && a.x0_staged_paired == b.x0_staged_paired &&
-           a.tab_count == b.tab_count && a.tab_stale == b.tab_stale;
+           a.tab_count == b.tab_count && a.tab_stale == b.tab_stale && a.ip_set == b.ip_set;
   }
   friend bool operator!=(const CacheRecord& a, const CacheRecord& b) { return !(a == b); }
 
@@ -157,6 +170,7 @@ class CacheRecord {
   //   x0_staged_paired: that step was a CFG-pair step (b = N / 2 latents, each staged twice), not an unguided one (N latents, once)
   //   tab_count:        rows of the timestep table sdeo_set_timestep_table filled since the last sdeo_configure
   //   *_stale:          sdeo_lora_commit changed the weights the item was computed with
+  //   ip_set:           sdeo_set_ip_tokens filled the image-prompt K / V since the last sdeo_configure (adapter handles only)
   bool hint_set[kMaxNets] = {false};
   bool hint_stale[kMaxNets] = {false};
   int ctx_set = 0, ctx_stale = 0;
@@ -165,6 +179,7 @@ class CacheRecord {
   bool x0_staged_paired = true;
   int tab_count = 0;
   bool tab_stale = false;
+  bool ip_set = false;
 };
 
 }  // namespace sdeo

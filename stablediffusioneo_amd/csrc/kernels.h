@@ -169,6 +169,20 @@ int attention(const AttnArgs& a, hipStream_t stream);
 // the instantiation attention() launches for this shape ("attention_kernel<3,2,true,4>", "attention_wide_kernel<128>"), from the
 // launcher's own selection; nullptr with the error set for a shape attention() rejects.  Host only.
 const char* attention_kernel_name(int B, int H, int Tq, int Tk, int d, int causal);
+// Two key segments, two softmaxes, ONE launch:  O = softmax(Q K^T * scale) V + w * softmax(Q K2^T * scale) V2  (decoupled
+// cross-attention: text keys, then the image-prompt keys).  a: the first segment exactly as attention() takes it (not causal; qB and
+// plan_B included).  s2: K2[(b*TkS+j)*ldk + h*d + i], V2[(b*TkSv+j)*ldv + h*d + i], 1 <= Tk <= 64 keys, keys >= Tk masked.  Both
+// normalised outputs and their sum stay in fp32; the result is rounded to fp16 once.  Head dims of the KS = 1 kernels (8..160).
+struct Attn2Seg {
+  const f16* k; const f16* v;
+  int ldk, ldv, Tk, TkS, TkSv;
+  float w;
+};
+int attention2(const AttnArgs& a, const Attn2Seg& s2, hipStream_t stream);
+// the checks attention2() makes before its launch, alone: 0, or the refusal.  Host only, never touches an operand.
+int attention2_check(const AttnArgs& a, const Attn2Seg& s2);
+// the instantiation attention2() launches ("attention2_kernel<3,true>": D16, MPAD); nullptr with the error set for a rejected shape
+const char* attention2_kernel_name(int B, int H, int Tq, int Tk, int Tk2, int d);
 // vt[c][b*TkSv + t] = v[(b*T + t)*ldv + c]   (VAE AttnBlock's materialised-score path)
 int transpose_pad(f16* vt, int ldvt, const f16* v, int ldv, int B, int T, int TkSv, int C, hipStream_t stream);
 

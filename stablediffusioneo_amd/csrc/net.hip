@@ -151,8 +151,33 @@ int sdeo_enable_extra_controlnets(sdeo_handle h, int count) {
   return 0;
 }
 
+int sdeo_enable_ip_adapter(sdeo_handle h, int num_tokens) {
+  SDEO_CHECK(num_tokens >= 1 && num_tokens <= 64, "sdeo_enable_ip_adapter: num_tokens %d out of range (1..64 image tokens)", num_tokens);
+  SDEO_CHECK(h, "sdeo_enable_ip_adapter: null handle");
+  SDEO_CHECK(!h->ip_tokens, "sdeo_enable_ip_adapter: already called (this handle has an adapter of %d tokens)", h->ip_tokens);
+  for (const auto& w : h->ws.entries)
+    SDEO_CHECK(!w.loaded, "sdeo_enable_ip_adapter: call it before the first sdeo_load_weight (%s is loaded)", w.name.c_str());
+  SDEO_CHECK(!h->finalized && !configured(h), "sdeo_enable_ip_adapter: call it before sdeo_finalize_weights / sdeo_configure");
+  // the two-segment cross-attention exists for the head dims of the one-wave-per-query-block kernels: refuse the others here, on the host
+  int bad_d = 0;
+  for_each_block(h->uplan, [&](const Blk& b) {
+    if (b.kind == B_ATTN && !bad_d && !attention2_kernel_name(1, b.heads, 1, h->cfg.context_len, num_tokens, b.cin / b.heads)) bad_d = b.cin / b.heads;
+  });
+  if (bad_d) {
+    const std::string why = sdeo_last_error();
+    return fail("sdeo_enable_ip_adapter: head dim %d has no two-segment attention kernel (%s)", bad_d, why.c_str());
+  }
+  // behind everything registered so far: the offsets of the existing tensors do not move
+  reg_ip_adapter(h);
+  if (int rc = h->ws.alloc("sdeo_enable_ip_adapter", /*zero_fill=*/true)) return rc;
+  h->device_bytes = h->ws.slab_bytes;
+  h->ip_tokens = num_tokens;
+  return 0;
+}
+
 static int configure_impl(sdeo_handle h, int n, int latent_h, int latent_w) {
   free_configured(h);
+  h->ip_scale = 1.0f;
   h->N = n; h->lh = latent_h; h->lw = latent_w;
   const sdeo_config& c = h->cfg;
   const size_t px = (size_t)latent_h * latent_w;
@@ -162,6 +187,7 @@ static int configure_impl(sdeo_handle h, int n, int latent_h, int latent_w) {
     if (int rc = dev_alloc(h, &h->in_hint[j], (size_t)n * c.hint_channels * px * 64 * 4)) return rc;
   if (int rc = dev_alloc(h, &h->in_ctx, (size_t)n * c.context_len * c.context_dim * 4)) return rc;
   if (int rc = dev_alloc(h, &h->in_t, (size_t)n * 8)) return rc;
+  if (h->ip_tokens) if (int rc = dev_alloc(h, &h->in_ip, (size_t)n * h->ip_tokens * c.context_dim * 4)) return rc;
   if (int rc = dev_alloc(h, &h->tab_t, (size_t)sdeo_handle_s::kTabRows * 8)) return rc;
   SDEO_HIP(hipMemset(h->tab_t, 0, (size_t)sdeo_handle_s::kTabRows * 8));
   for (int net = 0; net < 2 + h->extra; ++net) {
@@ -398,6 +424,30 @@ int sdeo_set_control_scales(sdeo_handle h, int net, const float* host_scales13) 
   return 0;
 }
 
+// What sdeo_enable_ip_adapter adds to a handle's life: the tokens of the image prompt, projected once into the K_ip | V_ip every UNet
+// cross-attention reads by address (P_CTX_IP), and the weight of the image term.
+int sdeo_set_ip_tokens(sdeo_handle h, const float* tokens, void* stream) {
+  SDEO_CHECK(h, "sdeo_set_ip_tokens: null handle");
+  SDEO_CHECK(h->ip_tokens, "sdeo_set_ip_tokens: this handle has no image-prompt adapter (call sdeo_enable_ip_adapter before loading weights)");
+  SDEO_CHECK(h->finalized, "sdeo_set_ip_tokens: weights not finalized (call sdeo_finalize_weights)");
+  SDEO_CHECK(configured(h), "sdeo_set_ip_tokens: not configured (call sdeo_configure)");
+  SDEO_CHECK(tokens, "sdeo_set_ip_tokens: null tokens");
+  hipStream_t s = S(stream);
+  h->cache.ip_staging();
+  if (int rc = copy_in(h->in_ip, tokens, (size_t)h->N * h->ip_tokens * h->cfg.context_dim * 4, s)) return rc;
+  if (int rc = run(h, h->prog[P_CTX_IP], s)) return rc;
+  h->cache.ip_filled();
+  return 0;
+}
+
+int sdeo_set_ip_scale(sdeo_handle h, float scale) {
+  SDEO_CHECK(h, "sdeo_set_ip_scale: null handle");
+  SDEO_CHECK(h->ip_tokens, "sdeo_set_ip_scale: this handle has no image-prompt adapter (call sdeo_enable_ip_adapter before loading weights)");
+  SDEO_CHECK(std::isfinite(scale), "sdeo_set_ip_scale: the scale is not finite");
+  h->ip_scale = scale;
+  return 0;
+}
+
 int sdeo_unet_forward(sdeo_handle h, const float* x_noisy, const int64_t* timesteps, const float* context,
                       const float* const* controls, const float* host_control_scales, int only_mid_control, float* eps,
                       int flags, void* stream) {
@@ -407,6 +457,7 @@ int sdeo_unet_forward(sdeo_handle h, const float* x_noisy, const int64_t* timest
   const int ctx_new = !(flags & SDEO_CONTEXT_CACHED);
   SDEO_CHECK(!ctx_new || context, "sdeo_unet_forward: context required");
   if (int rc = h->cache.cached_reads("sdeo_unet_forward", -1, ctx_new ? 0 : CacheRecord::UNET)) return rc;
+  if (h->ip_tokens) if (int rc = h->cache.ip_tokens("sdeo_unet_forward")) return rc;
   int trow = -1;
   if (int rc = select_time(h, flags, timesteps, "sdeo_unet_forward", &trow)) return rc;
   if (int rc = stage_inputs(h, x_noisy, nullptr, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, 0, CacheRecord::UNET, s)) return rc;
@@ -439,6 +490,7 @@ int sdeo_apply_model(sdeo_handle h, const float* x_noisy, const float* hint, con
   const int sides = no_control ? CacheRecord::UNET : CacheRecord::BOTH;      // whose context K / V this call runs on
   if (!no_control) if (int rc = h->cache.extra_hints("sdeo_apply_model", h->extra)) return rc;
   if (int rc = h->cache.cached_reads("sdeo_apply_model", no_control || hint_new ? -1 : 0, ctx_new ? 0 : sides)) return rc;
+  if (h->ip_tokens) if (int rc = h->cache.ip_tokens("sdeo_apply_model")) return rc;
   int trow = -1;
   if (int rc = select_time(h, flags, timesteps, "sdeo_apply_model", &trow)) return rc;
   if (int rc = stage_inputs(h, x_noisy, no_control ? nullptr : hint, trow < 0 ? timesteps : nullptr, ctx_new ? context : nullptr, hint_new,
@@ -491,6 +543,7 @@ static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float*
   if (int rc = h->cache.step_table_row(who, table_row)) return rc;
   if (int rc = h->cache.extra_hints(who, h->extra)) return rc;
   if (int rc = h->cache.cached_reads(who, 0, CacheRecord::BOTH)) return rc;
+  if (h->ip_tokens) if (int rc = h->cache.ip_tokens(who)) return rc;
   if (!blend && (flags & SDEO_STEP_LATENT_STAGED)) if (int rc = h->cache.staged_latent(who, x, paired)) return rc;
   if (blend) {
     SDEO_CHECK(!(flags & SDEO_STEP_LATENT_STAGED), "%s: SDEO_STEP_LATENT_STAGED has no meaning here (the blend changes the latent and always restages it)", who);

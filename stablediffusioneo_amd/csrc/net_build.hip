@@ -267,15 +267,25 @@ struct Builder {
   }
 
   // qB: batches of q when the full-batch launch reads the queries of the first half twice (0: B).  Under `half` the first B / 2 batches run.
+  // k2: a second key segment (the image-prompt K_ip | V_ip of a handle with sdeo_enable_ip_adapter), [B * Tk2S][ldk2] with V_ip at v2:
+  // the SAME launch becomes the two-segment one (attention2), weighted by e->ip_scale as it is when the launch runs.
   void attn(const T& o, const f16* q, int ldq, const f16* k, int ldk, const f16* v, int ldv, int B, int H, int Tq, int Tk, int TkS, int TkSv, int d,
-            int qB = 0) {
+            int qB = 0, const f16* k2 = nullptr, const f16* v2 = nullptr, int ldk2 = 0, int Tk2 = 0, int Tk2S = 0) {
     AttnArgs a{o.p, q, k, v, o.ld, ldq, ldk, ldv, B, H, Tq, Tk, TkS, TkSv, d, 1.0f / sqrtf((float)d), 0};
     a.qB = qB;
     if (half) { a.plan_B = B; a.B = B / 2; }
     B = a.B;
+    const std::string tag = "Tq" + std::to_string(Tq) + " Tk" + std::to_string(Tk) + (k2 ? "+" + std::to_string(Tk2) : "") + " d" + std::to_string(d);
+    if (k2) {
+      if (!attention2_kernel_name(a.plan_B ? a.plan_B : a.B, H, Tq, Tk, Tk2, d) && err.empty()) err = std::string("image-prompt cross-attention: ") + sdeo_last_error();
+      const Attn2Seg s2{k2, v2, ldk2, ldk2, Tk2, Tk2S, Tk2S, 0.f};
+      const float* w = &e->ip_scale;
+      push([=](hipStream_t s) { Attn2Seg x = s2; x.w = *w; return attention2(a, x, s); }, "attention",
+           4.0 * B * H * (double)Tq * (Tk + Tk2) * d, 2.0 * B * H * d * (2.0 * Tq + 2.0 * (Tk + Tk2)), tag);
+      return;
+    }
     push([=](hipStream_t s) { return attention(a, s); }, "attention",
-         4.0 * B * H * (double)Tq * Tk * d, 2.0 * B * H * d * (2.0 * Tq + 2.0 * Tk),
-         "Tq" + std::to_string(Tq) + " Tk" + std::to_string(Tk) + " d" + std::to_string(d));
+         4.0 * B * H * (double)Tq * Tk * d, 2.0 * B * H * d * (2.0 * Tq + 2.0 * Tk), tag);
   }
 };
 
@@ -357,7 +367,8 @@ static T build_res(Builder& b, const std::string& ns, const Blk& blk, const T& x
 // x + f(LN(x)) runs as: [GEMM that writes x also writes x's per-row statistics] -> [GEMM of f's first Linear on the RAW x with
 // LN folded in] -> ... ; see the file comment.
 // kv: cross-attention K | V of this block, computed from the context: [N*TkS][2C] (K in columns 0..C-1, V in C..2C-1)
-static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& x, const T& kv, const T* out = nullptr) {
+// kv_ip: K_ip | V_ip of the same block from the image tokens, [N*round8(ip_tokens)][2C] (UNet blocks of an adapter handle), or null
+static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& x, const T& kv, const T* kv_ip, const T* out = nullptr) {
   const sdeo_config& c = b.e->cfg;
   const std::string p = ns + blk.name;
   const std::string t = p + ".transformer_blocks.0";
@@ -386,7 +397,10 @@ static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& 
   T q2 = b.gemm(tok1, b.named_w(t + ".attn2.q_ln.w"), C, C, b.named_v(t + ".attn2.q_ln.b"), l2);
   b.half = false;
   T o2 = b.alloc(x.n, x.h, x.w, C);
-  b.attn(o2, q2.p, C, kv.p, 2 * C, kv.p + C, 2 * C, N, H, Tq, c.context_len, TkS, TkS, d, b.share ? N / 2 : 0);
+  // (+ the image-prompt segment: softmax(q K^T) V + ip_scale softmax(q K_ip^T) V_ip, still one launch)
+  if (kv_ip) b.attn(o2, q2.p, C, kv.p, 2 * C, kv.p + C, 2 * C, N, H, Tq, c.context_len, TkS, TkS, d, b.share ? N / 2 : 0,
+                    kv_ip->p, kv_ip->p + C, 2 * C, b.e->ip_tokens, round8(b.e->ip_tokens));
+  else b.attn(o2, q2.p, C, kv.p, 2 * C, kv.p + C, 2 * C, N, H, Tq, c.context_len, TkS, TkS, d, b.share ? N / 2 : 0);
   b.release(q2);
   // ff.net.2 and proj_out are two Linear maps with only the residual add between them: composed at finalisation into ONE [C][5C]
   // matrix over the row-concatenated operand [GEGLU output (4C) | tok2 (C)] (ComposeJob), so attn2.to_out writes tok2 into the last C
@@ -483,6 +497,9 @@ struct BuildCtx {      // state of one build_all pass
   int N, h, w, TkS, nctrl;
   std::unordered_map<std::string, T> kv[kNets];   // per net: attn block name -> cached K | V
   T ctx16, hint_feat[kMaxControlNets];            // per control net: the cached output of its hint block
+  // image-prompt adapter: the padded fp16 tokens and, per UNet attn block, the cached K_ip | V_ip
+  T ip16;
+  std::unordered_map<std::string, T> kv_ip;
 };
 
 // persistent tensors first (never released): controls, context, cached K/V^T, hint features
@@ -500,6 +517,11 @@ static void build_persistent(BuildCtx& c) {
   for (int net = 0; net < 2 + e->extra; ++net) {        // (the extra nets' tensors behind everything a plain handle places)
     if (net >= 2) c.hint_feat[net - 1] = b.alloc(c.N, c.h, c.w, e->cfg.model_channels);
     for (const Blk* ab : attn_blocks(net ? e->cplan : e->uplan)) c.kv[net][net_ns(net) + ab->name] = b.alloc2d(c.N * c.TkS, 2 * ab->cin);
+  }
+  if (e->ip_tokens) {                                   // (the adapter's tensors behind those again)
+    const int TS = round8(e->ip_tokens);
+    c.ip16 = b.alloc2d(c.N * TS, e->cfg.context_dim);
+    for (const Blk* ab : attn_blocks(e->uplan)) c.kv_ip[net_ns(0) + ab->name] = b.alloc2d(c.N * TS, 2 * ab->cin);
   }
 }
 
@@ -540,6 +562,20 @@ static void build_context(BuildCtx& c, int net) {
   }
 }
 
+// image-prompt program (sdeo_set_ip_tokens): fp32 [N][T][ctx] -> fp16 rows padded to round8(T); K_ip | V_ip = tokens [Wk_ip; Wv_ip]^T
+// per UNet attn block, one GEMM each
+static void build_context_ip(BuildCtx& c) {
+  Builder& b = c.b; Engine* e = b.e;
+  b.prog = &e->prog[P_CTX_IP];
+  f16* o = c.ip16.p; const float* in = e->in_ip; const int N = c.N, T_ = e->ip_tokens, TS = round8(T_), Cd = e->cfg.context_dim;
+  b.push([=](hipStream_t s) { return pad_rows_f32_to_f16(o, in, N, T_, TS, Cd, s); });
+  for (const Blk* ab : attn_blocks(e->uplan)) {
+    const std::string name = net_ns(0) + ab->name;
+    Builder::CO kvo; kvo.out = &c.kv_ip[name];
+    b.gemm(c.ip16, b.named_w(name + ".transformer_blocks.0.attn2.to_kv_ip"), Cd, 2 * ab->cin, nullptr, kvo);
+  }
+}
+
 // hint program of control net j (`cldm/cldm.py:147-163,288`): 8 conv3x3, SiLU between, cached across steps
 static void build_hint(BuildCtx& c, int j) {
   Builder& b = c.b; Engine* e = b.e;
@@ -566,7 +602,7 @@ static T run_blocks(BuildCtx& c, const std::string& ns, const std::vector<Blk>& 
     T y;
     switch (blk.kind) {
       case B_RES: y = build_res(b, ns, blk, x, net, out); break;
-      case B_ATTN: y = build_attn(b, ns, blk, x, c.kv[net].at(ns + blk.name), out); break;
+      case B_ATTN: y = build_attn(b, ns, blk, x, c.kv[net].at(ns + blk.name), net == 0 && b.e->ip_tokens ? &c.kv_ip.at(ns + blk.name) : nullptr, out); break;
       default: {   // B_CONV_IN / B_DOWN / B_UP: one conv3x3, stride 2 (Downsample) or over the nearest-x2 source (Upsample)
         Builder::CO o; o.out = out; o.gn_next = true;
         y = b.conv(x, ns + blk.name + conv_suffix(blk.kind), blk.cout, 3, blk.kind == B_DOWN ? 2 : 1, blk.kind == B_UP ? 1 : 0, o);
@@ -920,6 +956,7 @@ int sdeo::build_all(Engine* e, bool dry, size_t* max_splitk, size_t* max_gn, siz
   build_latent_io(c);
   build_time_embeds(c);
   for (int net = 0; net < 2 + e->extra; ++net) build_context(c, net);
+  if (e->ip_tokens) build_context_ip(c);
   for (int j = 0; j <= e->extra; ++j) build_hint(c, j);
   // the extra nets run on the side stream behind net 0; every net's block outputs stay allocated there until the decoder has run
   c.b.on_lane(&e->lanes[L_SIDE], [&] { for (int j = 0; j <= e->extra; ++j) build_controlnet(c, j); });

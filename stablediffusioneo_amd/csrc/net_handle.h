@@ -75,7 +75,9 @@ enum CnProg { CP_HINT, CP_CTX, CP_CN, CP_CN_SH, CP_TEMB, CP_COUNT };
 // has no transformer
 enum ProgId {
   P_HINT, P_CTX_CN, P_CTX_UNET, P_CN, P_CN_SH, P_CN_EXPORT, P_CTRL_IMPORT, P_UNET_ENC, P_UNET_ENC_SH, P_UNET_DEC, P_UNET_DEC_FUSED,
-  P_UNET_NOCTRL, P_VAE, P_VAE_ENC, P_TEMB, P_TEMB_CN, P_TEMB_TAB, P_X0, P_EPS_EXPORT, P_COUNT
+  P_UNET_NOCTRL, P_VAE, P_VAE_ENC, P_TEMB, P_TEMB_CN, P_TEMB_TAB, P_X0, P_EPS_EXPORT,
+  P_CTX_IP,      // sdeo_set_ip_tokens: image tokens -> K_ip | V_ip of every UNet cross-attention (empty without sdeo_enable_ip_adapter)
+  P_COUNT
 };
 
 }  // namespace sdeo
@@ -114,6 +116,11 @@ struct sdeo_handle_s {
   bool vae_encoder = false;
   float* enc_img = nullptr; uint8_t* enc_img_u8 = nullptr; float* enc_noise = nullptr; float* enc_z = nullptr; float* enc_moments = nullptr;
   int enc_from_u8 = 0, enc_with_noise = 0;
+  // image-prompt adapter (sdeo_enable_ip_adapter): tokens per image (0: none), the boundary buffer of sdeo_set_ip_tokens
+  // ([N][ip_tokens][context_dim] fp32) and the weight of the image term, read at LAUNCH by every cross-attention of the UNet
+  int ip_tokens = 0;
+  float* in_ip = nullptr;
+  float ip_scale = 1.0f;
   std::vector<void*> extra_allocs;
   // persistent activations
   T ctrl[kMaxControls];  // fp16 NHWC controls (ControlNet output / UNet input), unscaled
@@ -176,6 +183,7 @@ static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); 
 void build_registry(Engine* e);
 void reg_extra_controlnets(Engine* e, int count);
 void reg_vae_encoder(Engine* e);
+void reg_ip_adapter(Engine* e);
 // net_build.hip: one pass over every program of the handle (dry: plan the arenas only)
 int build_all(Engine* e, bool dry, size_t* max_splitk, size_t* max_gn, size_t peaks[L_COUNT]);
 

@@ -229,6 +229,29 @@ void sdeo::reg_vae_encoder(Engine* e) {
   r.conv(std::string(NS_VAE) + "quant_conv", zc2, zc2, 1, round8(zc2));
 }
 
+// Image-prompt adapter (sdeo_enable_ip_adapter): to_k_ip | to_v_ip of every UNet cross-attention, stacked as one [2c][ctx] matrix the
+// way to_kv is, behind everything registered so far.  No fp8 region: fp8 handles refuse the adapter (sdeo_finalize_weights).
+void sdeo::reg_ip_adapter(Engine* e) {
+  Registry r{e};
+  r.quant = false;
+  const int ctx = e->cfg.context_dim;
+  for_each_block(e->uplan, [&](const Blk& b) {
+    if (b.kind != B_ATTN) return;
+    const std::string t = std::string(NS_UNET) + b.name + ".transformer_blocks.0";
+    const int c = b.cin;
+    const size_t kv = r.take((size_t)2 * c * ctx * 2);
+    e->named_off[t + ".attn2.to_kv_ip"] = kv;
+    r.add(t + ".attn2.to_k_ip.weight", W_LINEAR, {c, ctx}, kv);
+    r.add(t + ".attn2.to_v_ip.weight", W_LINEAR, {c, ctx}, kv + (size_t)c * ctx * 2);
+  });
+}
+
+// the two tensors per cross-attention reg_ip_adapter registers
+static bool is_ip_weight(const char* name) {
+  const std::string n = name ? name : "";
+  return n.find(".attn2.to_k_ip.") != std::string::npos || n.find(".attn2.to_v_ip.") != std::string::npos;
+}
+
 extern "C" {
 
 int sdeo_num_weights(sdeo_handle h) { return h ? (int)h->ws.entries.size() : 0; }
@@ -251,6 +274,9 @@ int sdeo_finalize_weights(sdeo_handle h) {
   SDEO_CHECK(!(h->extra && h->fp8.act_bits == 8),
              "sdeo_finalize_weights: block-scaled fp8 activations (sdeo_set_activation_precision 8) are not supported together with extra "
              "control networks (%d enabled)", h->extra);
+  SDEO_CHECK(!(h->ip_tokens && h->fp8.weight_bits == 8),
+             "sdeo_finalize_weights: fp8 weights (sdeo_set_weight_precision 8) are not supported together with the image-prompt adapter "
+             "(sdeo_enable_ip_adapter)");
   if (int rc = h->ws.require_all("sdeo_finalize_weights")) return rc;
   if (int rc = derive_weights(h)) return rc;
   h->finalized = true;
@@ -342,6 +368,8 @@ int sdeo_set_weight_precision(sdeo_handle h, int bits) {
 // ---- LoRA adapters: WeightStore does the work, the handle adds what it derives from the raw tensors and its caches
 int sdeo_lora_apply(sdeo_handle h, const char* name, const float* down, const float* up, int rank, float scale, void* stream) {
   SDEO_CHECK(h, "sdeo_lora_apply: null handle");
+  SDEO_CHECK(!is_ip_weight(name), "sdeo_lora_apply: %s belongs to the image-prompt adapter: adapters on the ip matrices are not supported "
+             "(the cached image-prompt K / V rely on them never changing)", name);
   const char* not_ready = !h->finalized ? "weights not finalized (call sdeo_finalize_weights)"
                           : h->fp8.weight_bits == 8 ? "this handle holds fp8 weights (sdeo_set_weight_precision 8): its fp16 copies are the dequantised values, "
                                                       "not the raw ones, and adapters on it are not supported"

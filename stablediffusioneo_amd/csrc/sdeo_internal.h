@@ -19,6 +19,14 @@ const char* sdeo_debug_conv2d_kernel_name(int n, int h, int w, int cin, int cout
  * the launcher's own selection.  NULL, with sdeo_last_error set, for a shape the launch rejects (head dim).  Host only, no device call;
  * the string is valid until the calling thread's next query. */
 const char* sdeo_debug_attention_kernel_name(int B, int H, int Tq, int Tk, int d, int causal);
+/* the same for sdeo_attention2_f16 ("attention2_kernel<3,true>": D16, MPAD; the two-segment forms of attention_kernel<D16,1,MPAD,4>).
+ * NULL, with sdeo_last_error set, for a shape the launch rejects (head dim, Tk2 outside 1..64). */
+const char* sdeo_debug_attention2_kernel_name(int B, int H, int Tq, int Tk, int Tk2, int d);
+/* the checks sdeo_attention2_f16 makes before its launch, alone (same arguments without the stream): 0 when the call would launch, else
+ * its refusal with sdeo_last_error set.  Host only: no device call is made and no operand is read, so a test may pass any address. */
+int sdeo_debug_attention2_check(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int tk, int tk_stride,
+                                int v_batch_stride, const void* k2, int ldk2, const void* v2, int ldv2, int tk2, int tk2_stride,
+                                int v2_batch_stride, float weight2, int b, int heads, int tq, int d, float scale);
 /* plan queries (tests; host only, no device call): the problem of an sdeo_conv2d_nhwc_f16 / sdeo_gemm_f16 call of this shape with
  * `act` and, for fp8 != 0, fp8 weights -> the tuned-table key it looks up (key10) and the (tile, split-K) it would launch */
 int sdeo_debug_conv2d_plan(int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, int act, int fp8, int* key10,
@@ -94,6 +102,11 @@ int sdeo_debug_gemm_res_rows_f16(void* y, int ldy, const void* x, int ldx, const
                                  size_t workspace_bytes, void* stream);
 int sdeo_debug_attention_qb_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int b,
                                 int q_batches, int heads, int tq, int tk, int tk_stride, int v_batch_stride, int d, float scale, void* stream);
+/* attention2_qb: sdeo_attention2_f16 with the same query sharing (k, v, k2, v2 and o hold b batches) */
+int sdeo_debug_attention2_qb_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int tk,
+                                 int tk_stride, int v_batch_stride, const void* k2, int ldk2, const void* v2, int ldv2, int tk2,
+                                 int tk2_stride, int v2_batch_stride, float weight2, int b, int q_batches, int heads, int tq, int d,
+                                 float scale, void* stream);
 
 /* fp8 weight pack at op level (tests): quantise [rows][cols] fp16 in place to its dequantised values, codes -> q, scales -> scale;
  * sdeo_debug_next_weights_fp8 makes the NEXT sdeo_gemm_f16 / sdeo_conv2d_nhwc_f16 call of this thread stream these codes

@@ -427,6 +427,33 @@ def attention_q_shared(q, k, v, heads, tk=None, scale=None):
     return o
 
 
+def attention2(q, k, v, k2, v2, heads, weight2, tk=None, tk2=None, scale=None, out=None):
+    """softmax(q k^T s) v + weight2 * softmax(q k2^T s) v2 in one launch (sdeo_attention2_f16: decoupled cross-attention).
+    q (B,Tq,H*d) or (B/2,Tq,H*d): the two halves of the batch then share the queries, as in attention_q_shared.  k, v as attention()
+    takes them; k2 (B,Tk2S,H*d), v2 (B,Tk2Sv,H*d) with 1 <= tk2 <= 64 keys, views of the same kind.  Returns (B,Tq,H*d)."""
+    lib = _lib.load()
+    _need_cuda(q, k, v, k2, v2, out)
+    qb, tq, c = q.shape
+    b, tks, tksv, tks2, tksv2 = k.shape[0], k.shape[1], v.shape[1], k2.shape[1], v2.shape[1]
+    tk = min(tks, tksv) if tk is None else tk
+    tk2 = min(tks2, tksv2) if tk2 is None else tk2
+    d = c // heads
+    scale = d ** -0.5 if scale is None else scale
+    assert qb == b or 2 * qb == b
+    assert all(t.shape[0] == b and t.shape[2] == c for t in (k, v, k2, v2))
+    o = torch.empty((b, tq, c), dtype=torch.float16, device=q.device) if out is None else out
+    assert o.shape == (b, tq, c)
+    ldq, ldk, ldv, ldo = _rows_view(q, "q"), _rows_view(k, "k"), _rows_view(v, "v"), _rows_view(o, "out")
+    ldk2, ldv2 = _rows_view(k2, "k2"), _rows_view(v2, "v2")
+    segs = (ptr(k), ldk, ptr(v), ldv, tk, tks, tksv, ptr(k2), ldk2, ptr(v2), ldv2, tk2, tks2, tksv2, weight2)
+    if qb == b:
+        rc = lib.sdeo_attention2_f16(ptr(o), ldo, ptr(q), ldq, *segs, b, heads, tq, d, scale, cur_stream())
+    else:
+        rc = lib.sdeo_debug_attention2_qb_f16(ptr(o), ldo, ptr(q), ldq, *segs, b, qb, heads, tq, d, scale, cur_stream())
+    check(rc, "attention2")
+    return o
+
+
 def geglu(a):
     lib = _lib.load()
     _need_cuda(a)

@@ -160,12 +160,14 @@ class SdeoRuntime(_HandleRuntime):
 
     def __init__(self, ucfg: S.UNetConfig = S.UNET_SD15, vcfg: S.VAEConfig = S.VAE_SD15, device: Optional[torch.device] = None,
                  weight_bits: int = 16, act_bits: int = 16, mx_min_rows: int = 0, vae_encoder: bool = False,
-                 extra_controlnets: int = 0):
+                 extra_controlnets: int = 0, ip_adapter_tokens: int = 0):
         """weight_bits = 8: the UNet / ControlNet matrices are packed to fp8 (OCP e4m3fn, per-output-channel power-of-two scale) when
         the weights are finalised (BASELINE configs[4]; the reference's precision switch is `onnx2trt_static_plugin.py:40-42`).
         vae_encoder = True: the handle also expects `first_stage_model.encoder.*` / `quant_conv.*` and runs `vae_encode`.
         extra_controlnets = k (1..3): the handle also expects `control_model_<j>.*` for j = 1..k and every forward sums the residuals
-        of all 1 + k control networks (`set_control_hint`, `set_control_scales`)."""
+        of all 1 + k control networks (`set_control_hint`, `set_control_scales`).
+        ip_adapter_tokens = T (1..64): the handle also expects `...attn2.to_k_ip.weight` / `to_v_ip.weight` of every UNet cross-attention
+        (spec.param_spec_ip_adapter) and every forward adds the image term of `set_ip_tokens`, weighted by `set_ip_scale`."""
         super().__init__(device)
         self.ucfg, self.vcfg = ucfg, vcfg
         self._cfg = make_config(ucfg, vcfg)
@@ -183,6 +185,10 @@ class SdeoRuntime(_HandleRuntime):
         # what the library holds for the extra nets: the scales last set, and the generation each hint was set in (0: never)
         self._extra_scales = [None] * self.extra_controlnets
         self._extra_hint_gen = [0] * self.extra_controlnets
+        self.ip_adapter_tokens = int(ip_adapter_tokens)
+        if self.ip_adapter_tokens:  # before any weight, like the encoder
+            check(self.lib.sdeo_enable_ip_adapter(self.handle, self.ip_adapter_tokens), "enable_ip_adapter")
+        self.ip_scale = 1.0         # as the library holds it (sdeo_configure resets it to 1): part of every key of a captured graph
         self.weight_bits = int(weight_bits)
         if self.weight_bits != 16:
             check(self.lib.sdeo_set_weight_precision(self.handle, self.weight_bits), "set_weight_precision")
@@ -256,7 +262,24 @@ class SdeoRuntime(_HandleRuntime):
             check(self.lib.sdeo_configure(self.handle, n, h, w), "configure")
             self.n, self.h, self.w = n, h, w
             self._extra_scales = [None] * self.extra_controlnets       # the library reset them to 1
+            self.ip_scale = 1.0                                        # ... and the weight of the image term
         return self
+
+    # ---------------------------------------------------------------- image-prompt adapter
+    def set_ip_tokens(self, tokens):
+        """`sdeo_set_ip_tokens`: the image tokens (n, ip_adapter_tokens, context_dim) into the K_ip | V_ip every UNet cross-attention reads.
+        Once per image prompt; the result is read by address, so a captured step sees new tokens without re-capture."""
+        tokens = self._f32(tokens, (self.n, self.ip_adapter_tokens, self.ucfg.context_dim))
+        check(self.lib.sdeo_set_ip_tokens(self.handle, ptr(tokens), cur_stream()), "set_ip_tokens")
+
+    def set_ip_scale(self, scale: float = 1.0):
+        """`sdeo_set_ip_scale`: weight of the image term in the following forwards (read at launch: a captured step bakes it in)"""
+        check(self.lib.sdeo_set_ip_scale(self.handle, C.c_float(float(scale))), "set_ip_scale")
+        self.ip_scale = float(scale)
+
+    def ip_key(self):
+        """what a captured graph bakes in of the adapter: whether it is on, and the scale"""
+        return (self.ip_adapter_tokens, self.ip_scale)
 
     # ---------------------------------------------------------------- extra control networks
     def set_control_hint(self, net: int, hint):
@@ -362,7 +385,7 @@ class SdeoRuntime(_HandleRuntime):
         side stream, UNet encoder on the main one), so the GPU sees the whole fork/join at once.  Inputs are copied into
         fixed device buffers; the returned eps tensor is owned by the runtime (valid until the next call)."""
         key = (self.generation, self.n, self.h, self.w, tuple(float(s) for s in (scales or [])), bool(only_mid_control),
-               self.extra_scales_key())
+               self.extra_scales_key(), self.ip_key())
         if getattr(self, "_graph_key", None) != key:
             u = self.ucfg
             self._gx = torch.zeros((self.n, u.in_channels, self.h, self.w), dtype=torch.float32, device=self.device)

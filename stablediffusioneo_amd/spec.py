@@ -269,6 +269,21 @@ def param_spec_unet(cfg: UNetConfig = UNET_SD15):
     return spec
 
 
+def param_spec_ip_adapter(cfg: UNetConfig = UNET_SD15):
+    """What an image-prompt adapter (IP-Adapter) adds to the UNet: `<block>.transformer_blocks.0.attn2.to_k_ip.weight` and
+    `...to_v_ip.weight`, (C, context_dim) each and no bias, for every UNet attention block, in the order of a forward pass (input blocks,
+    middle block, output blocks): the order in which `sdeo_enable_ip_adapter` registers them.  Names without the `model.diffusion_model.`
+    prefix, like `param_spec_unet`."""
+    spec = OrderedDict()
+    plan = unet_plan(cfg)
+    for blocks in list(plan.input_blocks) + [plan.middle_block] + list(plan.output_blocks):
+        for b in blocks:
+            if b.kind == "attn":
+                for leaf in ("to_k_ip", "to_v_ip"):
+                    _lin(spec, f"{b.name}.transformer_blocks.0.attn2.{leaf}", cfg.context_dim, b.cin, bias=False)
+    return spec
+
+
 def param_spec_controlnet(cfg: UNetConfig = UNET_SD15):
     """ControlNet parameters, reference naming (`cldm/cldm.py:131-282`)."""
     spec = OrderedDict()
