@@ -238,6 +238,7 @@ int sdeo_debug_gemm_plan(int m, int n, int k, int act, int fp8, int* key10, int*
 
 // (tile, split-K) of the last conv / GEMM launch (host-side record; -1 / 0 before the first)
 void sdeo_debug_last_gemm_plan(int* tile, int* splitk) { conv_gemm_last_plan(tile, splitk); }
+int sdeo_debug_last_gemm_epilogue(void) { return conv_gemm_last_epilogue(); }
 
 int sdeo_debug_tile_info(int tile, int* kind, int* bm, int* bn, int* stages, int* caps, const char** name) {
   return conv_gemm_tile_info(tile, kind, bm, bn, stages, caps, name);
@@ -322,6 +323,26 @@ int sdeo_debug_gemm_res_rows_f16(void* y, int ldy, const void* x, int ldx, const
     *strips_out = conv_gemm_stats_strips(p);
     SDEO_CHECK(*strips_out <= stats_ld, "gemm_res_rows: %d strips do not fit stats_ld %d", *strips_out, stats_ld);
     if (*strips_out > 0) { p.stats_out = stats; p.stats_ld = stats_ld; }
+  }
+  return conv_gemm(p, S(stream));
+}
+
+// sdeo_conv2d_nhwc_f16 (stride 1, no bias2) with what csrc/net_build.hip's conv() can add to a conv: a residual of res_rows rows
+// (0 = one per output row), row statistics out, and (for the host check only: it is refused for filters larger than 1x1) a
+// LayerNorm-folded input
+int sdeo_debug_conv2d_ex_f16(void* y, const void* x, const void* w_krsc, const float* bias, const void* res, int res_rows, int n, int h,
+                             int w, int cin, int cout, int ksize, float* stats, int stats_ld, int* strips_out, const float* ln_stats,
+                             const float* ln_s, int ln_ld, int ln_strips, void* workspace, size_t workspace_bytes, void* stream) {
+  ConvGemm p;
+  if (int rc = fill_conv(p, n, h, w, cin, cout, ksize, 1, 0)) return rc;
+  p.x = (const f16*)x; p.w = (const f16*)w_krsc; p.y = (f16*)y; p.bias = bias; p.res = (const f16*)res; p.res_rows = res_rows;
+  p.workspace = (float*)workspace; p.workspace_bytes = workspace_bytes;
+  if (ln_stats) { p.ln_stats = ln_stats; p.ln_s = ln_s; p.ln_ld = ln_ld; p.ln_strips = ln_strips; p.ln_c = cin; p.ln_eps = 1e-5f; }
+  if (stats) {
+    SDEO_CHECK(strips_out, "conv2d_ex: null argument");
+    *strips_out = conv_gemm_stats_strips(p);
+    SDEO_CHECK(*strips_out > 0 && *strips_out <= stats_ld, "conv2d_ex: %d strips do not fit stats_ld %d", *strips_out, stats_ld);
+    p.stats_out = stats; p.stats_ld = stats_ld;
   }
   return conv_gemm(p, S(stream));
 }

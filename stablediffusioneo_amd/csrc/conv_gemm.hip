@@ -62,10 +62,14 @@ namespace sdeo {
 // A workgroup finds (problem, tile in problem) by a branch-free scan of the prefix sums in SGPRs, copies that problem's block in one
 // batch and from there on IS a workgroup of that problem's own launch: same K order, same epilogue, bit-identical output.  Unsplit
 // fp16 plans only (host-checked).  With MULTI = false nothing of this is compiled and the kernel is the one it was.
-template <int BM, int BN, int STAGES, bool UPS, bool WS, bool W8 = false, int KPB = 1, bool MX = false, bool MULTI = false>
+// EPI (EpiKind, conv_inl.h): EPI_DIRECT deals the weight rows of each wave's strip to the LDS rows in the order of direct_row_chan
+// (a change of the loaders' SOURCE rows only: the LDS image, the fragment reads and the K loop are those of EPI_STAGED, so the
+// fragment reads stay bank-conflict free) and stores from the accumulators (epilogue_direct); the staged epilogue is not compiled in.
+template <int BM, int BN, int STAGES, bool UPS, bool WS, bool W8 = false, int KPB = 1, bool MX = false, bool MULTI = false, int EPI = EPI_STAGED>
 __global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const std::conditional_t<MULTI, MPArgs, KP> pp) {
   kernarg_warm<sizeof(pp)>();
   static_assert(!MULTI || (!W8 && !MX), "multi-problem launches stream fp16 weights");
+  static_assert(EPI == EPI_STAGED || (!W8 && !MX && !MULTI && !UPS), "the register-direct epilogue exists for the plain fp16 kernels");
   // The scalars both roles need before their first DMA / fragment read, fetched in ONE batch and pinned in SGPRs: left to the
   // compiler each is an s_load + s_waitcnt lgkmcnt(0) next to its first use, ten dependent scalar round trips in front of the
   // first DMA of a launch whose whole K loop lasts a few microseconds.
@@ -181,7 +185,8 @@ __global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const std
 #pragma unroll
     for (int i = 0; i < WP; ++i) {
       if constexpr (!W8) {
-        const int n = n0 + lrow + i * RPP;
+        const int lr = lrow + i * RPP;             // LDS row of the weight tile; the channel it holds:
+        const int n = n0 + (EPI == EPI_DIRECT ? lr / TN * TN + direct_row_chan<NI>(lr % TN) : lr);
         const bool nv = n < p.N && !dbg_on(p, 2);
         wptr[i] = nv ? reinterpret_cast<const char*>(p.w + (size_t)n * p.ldw + (size_t)kbeg * BK + cl * 8) : zero;
         winc[i] = nv ? BK * 2 : 0;
@@ -299,7 +304,7 @@ __global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const std
   const bool use_bpre = p.bias && !p.bias_per_row && p.splitk == 1;
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
-    const int n = n0 + wn * TN + i * 16 + fq * 4;
+    const int n = n0 + wn * TN + lane_chan<NI, EPI == EPI_DIRECT>(i, fq);
     bpre[i] = (use_bpre && n < p.N) ? *reinterpret_cast<const f32x4*>(p.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
@@ -527,22 +532,40 @@ __global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const std
   if (dbg_on(p, 32)) return;
   static_assert(4 * epilogue_scratch_bytes(TN) <= STAGES * STAGE, "epilogue scratch");
   constexpr int SCR = (STAGES * STAGE / 4) & ~15;        // LDS each wave may use as epilogue scratch
-  constexpr int NBLK = epilogue_blocks(TN, MI, SCR);
-  char* scratch = smem + wave * SCR;
-  epilogue<NI, MI, TM, TN, NBLK>(pe, acc, m0, n0, wm, wn, frow, fq, z, bpre, use_bpre, scratch, ln_lds ? lnsm + wm * TM : nullptr);
-  if (pe.gn_out) {                         // GroupNorm partials of this tile (loader waves, if any, are gone: the barrier counts the rest)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wm == 0) {                         // waves 2 wn and 2 wn + 1 share strip wn
-      const int bimg = m0 / pe.HoWo;
-      gn_partials_finish<TN, 2>(pe, smem + 2 * wn * SCR, SCR, lane, bimg, (m0 - bimg * pe.HoWo) / BM, n0 + wn * TN);
+  [[maybe_unused]] constexpr int NBLK = epilogue_blocks(TN, MI, SCR);
+  [[maybe_unused]] char* scratch = smem + wave * SCR;
+  int mrow[MI];
+#pragma unroll
+  for (int j = 0; j < MI; ++j) {
+    const int m = m0 + wm * TM + j * 16 + frow;
+    mrow[j] = m < pe.M ? m : -1;
+  }
+  const float2* lnrow = ln_lds ? lnsm + wm * TM : nullptr;
+  // One epilogue in the code.  SDEO_DBG_GEMM bit 128 takes a second trip through THE SAME instructions (a loop the compiler may not
+  // unroll), so the second trip runs code the first one has just fetched: stamps 3 -> 4 against 5 -> 6 is cold fetch against work.
+  // In the production build the loop condition is the constant false and there is no loop.
+  int trip = 0;
+#pragma nounroll
+  do {
+    if constexpr (EPI == EPI_DIRECT) {
+      epilogue_direct<NI, MI, TN>(pe, acc, mrow, n0 + wn * TN, fq, bpre, use_bpre, lnrow);
+    } else {
+      epilogue_rows<NI, MI, TN, NBLK>(pe, acc, mrow, n0 + wn * TN, fq, z, bpre, use_bpre, scratch, lnrow);
+      if (pe.gn_out) {                     // GroupNorm partials of this tile (loader waves, if any, are gone: the barrier counts the rest)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        if (wm == 0) {                     // waves 2 wn and 2 wn + 1 share strip wn
+          const int bimg = m0 / pe.HoWo;
+          gn_partials_finish<TN, 2>(pe, smem + 2 * wn * SCR, SCR, lane, bimg, (m0 - bimg * pe.HoWo) / BM, n0 + wn * TN);
+        }
+      }
     }
-  }
-  if (dbg_on(p, 64)) {
-    stamp(p, 4);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp(p, 5);
-  }
+    if (dbg_on(p, 64)) {
+      stamp(p, trip ? 6 : 4);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (!trip) stamp(p, 5);
+    }
+  } while (dbg_on(p, 128) && ++trip < 2);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -787,13 +810,13 @@ static int launch_k(K kernel, int smem, DeviceOnce* attr_done, const KP& kp, int
   return 0;
 }
 
-template <int BM, int BN, int ST, bool UPS, bool WS, bool W8 = false, int KPB = 1, bool MX = false>
+template <int BM, int BN, int ST, bool UPS, bool WS, bool W8 = false, int KPB = 1, bool MX = false, int EPI = EPI_STAGED>
 static int launch_dma(const KP& kp, int tiles, hipStream_t stream) {
   static DeviceOnce done;
   // ring + the LayerNorm row scalars (conv_gemm_dma_kernel: lnsm); an fp8 weight row is 64 bytes, one DMA pass covers 64 rows
   constexpr int smem = ST * (W8 ? BM * 128 + (BN + 63) / 64 * 4096 : (BM + BN) * 128) + BM * 8;
   static_assert(smem <= 160 * 1024, "LDS");
-  return launch_k(&conv_gemm_dma_kernel<BM, BN, ST, UPS, WS, W8, KPB, MX>, smem, &done, kp, tiles, stream, WS ? 512 : 256);
+  return launch_k(&conv_gemm_dma_kernel<BM, BN, ST, UPS, WS, W8, KPB, MX, false, EPI>, smem, &done, kp, tiles, stream, WS ? 512 : 256);
 }
 
 // multi-problem launch of one instantiation (conv_gemm_dma_kernel MULTI): `tiles` = the sum over the problems
@@ -822,11 +845,18 @@ static int launch_generic(const KP& kp, int tiles, hipStream_t stream) {
 // The tile table (TileCfg: conv_inl.h).  Adding a tile = one row here (appended: indices are public) + its index in the tests' tile
 // lists, which tests/test_tile_table_cpu.py holds against this table.  CAPS: CAP_LIGHT makes the row the four-wave instantiation;
 // CAP_W8 / CAP_MX add the fp8-weight / block-scaled-fp8 instantiation of the same shape (wave-specialised, no folded Upsample, KPB 1).
-template <int BM, int BN, int ST, int CAPS = 0, int KPB = 1>
+// Epilogue kinds (EpiKind): a row has the EPI_DIRECT form of its plain fp16 instantiation (TileCfg::direct) when the networks can
+// plan it unsplit: the rows the heuristic may pick (no CAP_LIGHT / CAP_GROUPED / CAP_HALO) and the rows the committed plan table
+// (tuned_plans_gfx950.json) runs at split-K 1.  The others say so here (dma_tile<..., false>) and in conv_halo.hip (HALO against
+// HALO_D): rows 29, 31, 33, 42 and the halo rows 13, 15 - 18, 22 - 25, 36, 38.  A launch on such a row (a forced tile, a new plan
+// table) keeps the staged epilogue: direct_ok() is the one place that decides.  The folded-Upsample, fp8, block-scaled and
+// multi-problem instantiations and the register-staged fallback kernel exist as EPI_STAGED only.
+template <int BM, int BN, int ST, int CAPS = 0, int KPB = 1, bool DIRECT = true>
 static constexpr TileCfg dma_tile(const char* name) {
   constexpr bool WS = !(CAPS & CAP_LIGHT);
   TileCfg c{BM, BN, 64, ST, TK_DMA, CAPS | (KPB > 1 ? CAP_GROUPED : 0), KPB, 0, 0, name,
-            &launch_dma<BM, BN, ST, false, WS, false, KPB>, &launch_dma<BM, BN, ST, true, WS, false, KPB>, nullptr, nullptr};
+            &launch_dma<BM, BN, ST, false, WS, false, KPB>, &launch_dma<BM, BN, ST, true, WS, false, KPB>, nullptr, nullptr, nullptr};
+  if constexpr (DIRECT) c.direct = &launch_dma<BM, BN, ST, false, WS, false, KPB, false, EPI_DIRECT>;
   if constexpr ((CAPS & CAP_W8) != 0) c.w8 = &launch_dma<BM, BN, ST, false, true, true>;
   if constexpr ((CAPS & CAP_MX) != 0) c.mx = &launch_dma<BM, BN, ST, false, true, false, 1, true>;
   return c;
@@ -867,16 +897,16 @@ static const TileCfg kTiles[] = {
     dma_tile<128, 64, 2, CAP_LIGHT>("conv_gemm_dma_kernel<128,64,2>"),
     dma_tile<64, 64, 2, CAP_LIGHT>("conv_gemm_dma_kernel<64,64,2>"),
     dma_tile<128, 128, 2, CAP_LIGHT>("conv_gemm_dma_kernel<128,128,2>"),
-    dma_tile<128, 160, 2, CAP_LIGHT>("conv_gemm_dma_kernel<128,160,2>"),
+    dma_tile<128, 160, 2, CAP_LIGHT, 1, false>("conv_gemm_dma_kernel<128,160,2>"),
     dma_tile<64, 160, 2, CAP_LIGHT>("conv_gemm_dma_kernel<64,160,2>"),
-    dma_tile<32, 160, 2, CAP_LIGHT>("conv_gemm_dma_kernel<32,160,2>"),
+    dma_tile<32, 160, 2, CAP_LIGHT, 1, false>("conv_gemm_dma_kernel<32,160,2>"),
     dma_tile<64, 64, 3, CAP_LIGHT>("conv_gemm_dma_kernel<64,64,3>"),
-    dma_tile<128, 64, 3, CAP_LIGHT>("conv_gemm_dma_kernel<128,64,3>/4w"),
+    dma_tile<128, 64, 3, CAP_LIGHT, 1, false>("conv_gemm_dma_kernel<128,64,3>/4w"),
     // halo kernels with one barrier per filter row (three taps)
     halo_row(10), halo_row(11), halo_row(12), halo_row(13), halo_row(14), halo_row(15), halo_row(16),
     // implicit-GEMM tiles with one barrier per GROUP of K-steps (conv_gemm_dma_kernel KPB): name<BM,BN,STAGES,KPB>
     dma_tile<32, 160, 6, 0, 2>("conv_gemm_dma_kernel<32,160,6,k2>"),
-    dma_tile<64, 64, 8, 0, 2>("conv_gemm_dma_kernel<64,64,8,k2>"),
+    dma_tile<64, 64, 8, 0, 2, false>("conv_gemm_dma_kernel<64,64,8,k2>"),
     dma_tile<64, 64, 9, 0, 3>("conv_gemm_dma_kernel<64,64,9,k3>"),
     dma_tile<64, 160, 5, 0, 2>("conv_gemm_dma_kernel<64,160,5,k2>"),
     dma_tile<128, 64, 6, 0, 2>("conv_gemm_dma_kernel<128,64,6,k2>"),
@@ -889,7 +919,7 @@ static const int kTileCount = (int)std::size(kTiles);
 static bool by_plan_only(const TileCfg& c) { return (c.caps & (CAP_HALO | CAP_LIGHT | CAP_GROUPED)) != 0; }
 static const int kNumCU = 256;
 
-struct Plan { int tile; int splitk; int nk; int tiles_m, tiles_n; };
+struct Plan { int tile; int splitk; int nk; int tiles_m, tiles_n; int direct; };      // direct: the launch runs the EPI_DIRECT instantiation of the tile (set by prepare)
 
 static bool is_fast(const ConvGemm& p) { return p.Cin % 64 == 0; }
 static bool halo_ok(const ConvGemm& p, const TileCfg& c) {
@@ -1042,8 +1072,19 @@ void conv_gemm_query_plan(const ConvGemm& p0, int key[10], int* tile, int* split
 }
 
 // (tile, split-K) of the last problem conv_gemm() launched: host-side only, read by the tests through sdeo_debug_last_gemm_plan
-static int g_last_tile = -1, g_last_splitk = 0;
+static int g_last_tile = -1, g_last_splitk = 0, g_last_epilogue = -1;
 void conv_gemm_last_plan(int* tile, int* splitk) { *tile = g_last_tile; *splitk = g_last_splitk; }
+int conv_gemm_last_epilogue() { return g_last_epilogue; }       // EpiKind of that launch
+
+// Which launches run the EPI_DIRECT instantiation of their tile (epilogue_direct): those the LDS-transposed epilogue would serve
+// (kp.coalesce: unsplit, fp16 output, N % 8 == 0, 16-byte aligned output and residual rows) in a plain mode.  The GEGLU pair
+// epilogue, the GroupNorm partials and the per-image bias2 (slower direct than staged when measured) stay staged, split-K launches keep the plain channel order (their slabs and
+// splitk_reduce_kernel are untouched), and the folded Upsample, fp8 and block-scaled kernels have no direct form.
+// SDEO_EPI_DIRECT=0 (measurement) keeps every launch on the staged epilogue.
+static int direct_ok(const ConvGemm& p, const KP& kp, const TileCfg& c) {
+  static const int on = [] { const char* e = getenv("SDEO_EPI_DIRECT"); return e ? atoi(e) : 1; }();
+  return on && c.direct && kp.coalesce && p.act != 3 && !p.gn_out && !p.bias2 && !p.ups && !p.wscale && !p.mx_sx;
+}
 
 // argument checks + plan + kernel parameters of one problem
 static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
@@ -1106,6 +1147,7 @@ static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
   if (p.ln_stats) {
     SDEO_CHECK(p.ln_s && p.ln_strips >= 1 && p.ln_ld >= p.ln_strips && p.ln_c > 0, "conv_gemm: incomplete LayerNorm-fold arguments");
     SDEO_CHECK(!p.bias_per_row && !p.y32, "conv_gemm: the LayerNorm fold applies to row-major fp16 products only");
+    SDEO_CHECK(p.K == p.Cin && p.stride == 1 && !p.ups, "conv_gemm: the LayerNorm fold needs one input row per output row (a %dx%d filter mixes rows with different statistics)", p.R, p.S);
     kp.ln_stats = p.ln_stats; kp.ln_s = p.ln_s; kp.ln_strips = p.ln_strips; kp.ln_ld = p.ln_ld;
     kp.ln_invc = 1.0f / (float)p.ln_c; kp.ln_eps = p.ln_eps;
   }
@@ -1139,6 +1181,7 @@ static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
                   (reinterpret_cast<uintptr_t>(p.y) & 15) == 0 &&
                   (!p.res || (p.ldres % 8 == 0 && (reinterpret_cast<uintptr_t>(p.res) & 15) == 0));
     SDEO_CHECK(!p.gn_out || kp.coalesce, "conv_gemm: GroupNorm partials need the LDS-transposed epilogue");
+    pl.direct = direct_ok(p, kp, kTiles[pl.tile]);
   }
   if (pl.splitk > 1) {
     const size_t need = (size_t)pl.splitk * p.M * p.N * sizeof(float);
@@ -1153,7 +1196,8 @@ static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
 static int dispatch(const Plan& pl, int ups, bool w8, const KP& kp, hipStream_t stream) {
   if (pl.tile < 0 || pl.tile >= kTileCount) return fail("conv_gemm: bad tile %d", pl.tile);
   const TileCfg& c = kTiles[pl.tile];
-  const TileLaunch launch = kp.mx_sx ? c.mx : w8 ? c.w8 : ups ? c.ups : c.plain;
+  if (pl.direct && (kp.mx_sx || w8 || ups || !c.direct)) return fail("conv_gemm: tile %d has no register-direct instantiation for this launch", pl.tile);
+  const TileLaunch launch = pl.direct ? c.direct : kp.mx_sx ? c.mx : w8 ? c.w8 : ups ? c.ups : c.plain;
   if (!launch) return fail("conv_gemm: tile %d has no %s instantiation", pl.tile, kp.mx_sx ? "block-scaled fp8" : w8 ? "fp8-weight" : "folded-upsample");
   if (int rc = launch(kp, pl.tiles_m * pl.tiles_n, stream)) return rc;
   if (pl.splitk > 1) {
@@ -1171,7 +1215,7 @@ int conv_gemm(const ConvGemm& p0, hipStream_t stream) {
   Plan pl;
   KP kp{};
   if (int rc = prepare(p, pl, kp)) return rc;
-  g_last_tile = pl.tile; g_last_splitk = pl.splitk;
+  g_last_tile = pl.tile; g_last_splitk = pl.splitk; g_last_epilogue = pl.direct ? EPI_DIRECT : EPI_STAGED;
   return dispatch(pl, p.ups, p.wscale != nullptr, kp, stream);
 }
 
@@ -1236,7 +1280,7 @@ int conv_gemm_multi_launch(const ConvGemmMultiPlan& pl, const void* table_dev, c
   a.tab = static_cast<const MPTable*>(table_dev);
   a.count = pl.count;
   for (int i = 0; i < pl.count; ++i) a.scale[i] = scales ? scales[i] : pl.scale[i];
-  g_last_tile = pl.tile; g_last_splitk = 1;
+  g_last_tile = pl.tile; g_last_splitk = 1; g_last_epilogue = EPI_STAGED;
   return mt->launch(a, pl.tiles, stream);
 }
 

@@ -33,7 +33,9 @@ constexpr int halo_stages(int ph, int pw, int bn, int tpb = 1) {
 // TPB = 3: the loaders and the MFMA waves meet at ONE barrier per filter row (three taps, 192-deep) instead of one per tap: the
 // per-step skeleton (counted wait + barrier + loop bookkeeping, ~120 ns per tap by the ablations of DESIGN.md section 11) is paid a
 // third as often and the MFMA waves run three taps of fragment reads and MFMAs without meeting the loaders.
-template <int PH, int PW, int BN, int NMW, int TPB = 1>
+// EPI (EpiKind, conv_inl.h): EPI_DIRECT deals the BN weight rows to the LDS rows in the order of direct_row_chan (the loaders' source
+// rows only; LDS image, fragment reads and K loop unchanged) and stores from the accumulators (epilogue_direct).
+template <int PH, int PW, int BN, int NMW, int TPB = 1, int EPI = EPI_STAGED>
 __global__ __launch_bounds__(NMW * 64 + 256) void conv3x3_halo_kernel(const KP pp) {
   kernarg_warm<sizeof(KP)>();
   // prologue scalars in one batch, pinned in SGPRs (see conv_gemm_dma_kernel)
@@ -105,7 +107,7 @@ __global__ __launch_bounds__(NMW * 64 + 256) void conv3x3_halo_kernel(const KP p
     for (int q = 0; q < LW; ++q) {
       const int wr = (q * 4 + lw) * 8 + lrow;
       const int cl = pc ^ ((wr >> 1) & 7);
-      const int n = n0 + wr;
+      const int n = n0 + (EPI == EPI_DIRECT && wr < BN ? direct_row_chan<NI>(wr) : wr);      // the channel LDS row wr holds
       wok[q] = wr < BN && n < p.N;
       wsrc[q] = reinterpret_cast<const char*>(p.w) + ((size_t)(wok[q] ? n : 0) * p.ldw + cl * 8) * 2;
     }
@@ -181,7 +183,7 @@ __global__ __launch_bounds__(NMW * 64 + 256) void conv3x3_halo_kernel(const KP p
   const bool use_bpre = BPRE && p.bias && !p.bias_per_row && p.splitk == 1;
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
-    const int n = n0 + i * 16 + fq * 4;
+    const int n = n0 + lane_chan<NI, EPI == EPI_DIRECT>(i, fq);
     bpre[i] = (use_bpre && n < p.N) ? *reinterpret_cast<const f32x4*>(p.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
@@ -274,22 +276,27 @@ __global__ __launch_bounds__(NMW * 64 + 256) void conv3x3_halo_kernel(const KP p
   if (dbg_on(p, 32)) return;
   static_assert(NMW * epilogue_scratch_bytes(BN) <= 2 * XBYTES + WST * TPB * WBYTES, "epilogue scratch");
   constexpr int SCR = ((2 * XBYTES + WST * TPB * WBYTES) / NMW) & ~15;     // LDS each MFMA wave may use as epilogue scratch
-  constexpr int NBLK = epilogue_blocks(BN, MI, SCR);
-  epilogue_rows<NI, MI, BN, NBLK>(pe, acc, mrow, n0, fq, z, bpre, use_bpre, smem + wave * SCR);
-  if (pe.gn_out) {                         // GroupNorm partials of this patch: the loader waves are gone, the barrier counts the rest
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wave == 0) gn_partials_finish<BN, NMW>(pe, smem, SCR, lane, b, trem, n0);
-  }
-  if (dbg_on(p, 64)) {
-    stamp(p, 4);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp(p, 5);
-    if (dbg_on(p, 128)) {        // the same epilogue once more, now with its code resident: cold instruction fetch vs work
-      epilogue_rows<NI, MI, BN>(p, acc, mrow, n0, fq, z, bpre, use_bpre, smem + wave * epilogue_scratch_bytes(BN));
-      stamp(p, 6);
+  [[maybe_unused]] constexpr int NBLK = epilogue_blocks(BN, MI, SCR);
+  // one epilogue in the code; SDEO_DBG_GEMM bit 128 takes a second trip through the same instructions (see conv_gemm_dma_kernel)
+  int trip = 0;
+#pragma nounroll
+  do {
+    if constexpr (EPI == EPI_DIRECT) {
+      epilogue_direct<NI, MI, BN>(pe, acc, mrow, n0, fq, bpre, use_bpre);
+    } else {
+      epilogue_rows<NI, MI, BN, NBLK>(pe, acc, mrow, n0, fq, z, bpre, use_bpre, smem + wave * SCR);
+      if (pe.gn_out) {                     // GroupNorm partials of this patch: the loader waves are gone, the barrier counts the rest
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        if (wave == 0) gn_partials_finish<BN, NMW>(pe, smem, SCR, lane, b, trem, n0);
+      }
     }
-  }
+    if (dbg_on(p, 64)) {
+      stamp(p, trip ? 6 : 4);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (!trip) stamp(p, 5);
+    }
+  } while (dbg_on(p, 128) && ++trip < 2);
 }
 
 int conv_halo_read_stamps(unsigned long long* out, int n) {
@@ -301,37 +308,42 @@ int conv_halo_read_stamps(unsigned long long* out, int n) {
 // ------------------------------------------------------------------------------------------------
 // launcher + the variants' rows of the tile table
 // ------------------------------------------------------------------------------------------------
-template <int PH, int PW, int BN, int NMW, int TPB = 1>
+template <int PH, int PW, int BN, int NMW, int TPB = 1, int EPI = EPI_STAGED>
 static int launch_halo_t(const KP& kp, int tiles, hipStream_t stream) {
   constexpr int smem = 2 * halo_xbytes(PH, PW) + halo_stages(PH, PW, BN, TPB) * TPB * halo_wbytes(BN);
   static_assert(smem <= 160 * 1024, "LDS");
   static DeviceOnce done;
   if (done.need()) {
-    SDEO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<PH, PW, BN, NMW, TPB>),
+    SDEO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<PH, PW, BN, NMW, TPB, EPI>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     done.mark();
   }
-  hipLaunchKernelGGL((conv3x3_halo_kernel<PH, PW, BN, NMW, TPB>), dim3(tiles, 1, kp.splitk), dim3(NMW * 64 + 256), smem, stream, kp);
+  hipLaunchKernelGGL((conv3x3_halo_kernel<PH, PW, BN, NMW, TPB, EPI>), dim3(tiles, 1, kp.splitk), dim3(NMW * 64 + 256), smem, stream, kp);
   SDEO_HIP(hipGetLastError());
   return 0;
 }
 
-template <int PH, int PW, int BN, int NMW, int TPB = 1>
+template <bool DIRECT, int PH, int PW, int BN, int NMW, int TPB = 1>
 static constexpr TileCfg halo_tile(const char* name) {
-  return {PH * PW, BN, 64, halo_stages(PH, PW, BN, TPB), TK_HALO, CAP_HALO, 1, PH, PW, name, &launch_halo_t<PH, PW, BN, NMW, TPB>, nullptr, nullptr, nullptr};
+  TileCfg c{PH * PW, BN, 64, halo_stages(PH, PW, BN, TPB), TK_HALO, CAP_HALO, 1, PH, PW, name, &launch_halo_t<PH, PW, BN, NMW, TPB>, nullptr, nullptr, nullptr, nullptr};
+  if constexpr (DIRECT) c.direct = &launch_halo_t<PH, PW, BN, NMW, TPB, EPI_DIRECT>;
+  return c;
 }
-// a variant is written down once: its template arguments, spelled without blanks, are also its name
-#define HALO(...) halo_tile<__VA_ARGS__>("conv3x3_halo_kernel<" #__VA_ARGS__ ">")
+// a variant is written down once: its template arguments, spelled without blanks, are also its name.  HALO_D: the variant also has
+// the EPI_DIRECT form (the variants the committed plan table runs unsplit, see the list at kTiles in conv_gemm.hip).
+#define HALO(...) halo_tile<false, __VA_ARGS__>("conv3x3_halo_kernel<" #__VA_ARGS__ ">")
+#define HALO_D(...) halo_tile<true, __VA_ARGS__>("conv3x3_halo_kernel<" #__VA_ARGS__ ">")
 const TileCfg& halo_row(int variant) {
   static const TileCfg rows[] = {
-      HALO(8,16,80,4), HALO(8,16,160,4), HALO(8,8,80,4), HALO(8,8,160,4), HALO(8,16,64,4), HALO(8,16,128,4),
+      HALO(8,16,80,4), HALO_D(8,16,160,4), HALO(8,8,80,4), HALO(8,8,160,4), HALO(8,16,64,4), HALO(8,16,128,4),
       // two MFMA waves per SIMD
       HALO(8,16,80,8), HALO(8,16,160,8), HALO(8,16,64,8), HALO(8,16,128,8),
       // one barrier per filter row (TPB = 3)
-      HALO(8,16,80,4,3), HALO(8,16,80,8,3), HALO(8,16,64,4,3), HALO(8,8,80,4,3), HALO(8,8,160,4,3), HALO(8,16,128,8,3), HALO(8,16,64,8,3),
+      HALO_D(8,16,80,4,3), HALO_D(8,16,80,8,3), HALO(8,16,64,4,3), HALO_D(8,8,80,4,3), HALO(8,8,160,4,3), HALO_D(8,16,128,8,3), HALO_D(8,16,64,8,3),
   };
   return rows[variant];
 }
 #undef HALO
+#undef HALO_D
 
 }  // namespace sdeo

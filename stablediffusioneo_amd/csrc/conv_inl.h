@@ -29,7 +29,8 @@ struct KP {
   int tiles_m, tiles_n;
   // measurement builds only (-DSDEO_DEBUG_KERNELS, `python -m stablediffusioneo_amd.build --debug` -> libsdeo_dbg.so; the
   // field is ignored by the production kernels): SDEO_DBG_GEMM bits, results are wrong under them: 1 = activation DMAs read
-  // the zero page, 2 = weight DMAs do, 4 = no MFMAs, 8 = no DMAs after the prologue, 16 = no fragment reads, 32 = no epilogue
+  // the zero page, 2 = weight DMAs do, 4 = no MFMAs, 8 = no DMAs after the prologue, 16 = no fragment reads, 32 = no epilogue,
+  // 64 = phase stamps, 128 (with 64) = a second trip through the same epilogue instructions, resident by then (stamps 5 -> 6)
   int dbg;
   int n_fastest;     // tile order inside an XCD's contiguous run: 1 = all N tiles of an M tile are neighbours
   int coalesce;      // host-checked: the LDS-transposed 16-byte epilogue applies (see epilogue_rows)
@@ -245,10 +246,31 @@ __device__ __forceinline__ void ln_row_scalars(const KP& p, int row, float& r, f
   rm = r * mean;
 }
 
+// ---- epilogue kind: a compile-time argument of the kernels, chosen per launch on the host (conv_gemm.hip: prepare / dispatch).
+//      The tile table's rows and names do not know about it.
+//  EPI_STAGED  everything epilogue_rows does (LDS-transposed stores, GEGLU pair, GroupNorm partials, split-K slabs, 8-byte fallback)
+//  EPI_DIRECT  16-byte stores straight from the accumulators (epilogue_direct): the weight rows of a strip are dealt to the MFMA
+//              rows in a permuted order, so that a lane holds 8 consecutive channels across accumulator tiles 2q and 2q + 1
+enum EpiKind { EPI_STAGED = 0, EPI_DIRECT = 1 };
+
+// EPI_DIRECT channel map of a strip of NI 16-row accumulator tiles.  Row rho of tile i carries channel
+// 32 (i >> 1) + 8 (rho >> 2) + 4 (i & 1) + (rho & 3) of the strip: the accumulator rows of lane (frow, fq) are rho = 4 fq + t, so the
+// lane holds channels 32 q + 8 fq + {0..3} in tile 2q and + {4..7} in tile 2q + 1, and the four fq lanes of a pixel cover 32
+// consecutive channels.  An unpaired last tile (NI odd) keeps the plain order: 16 i + rho.
+template <int NI>
+__device__ __forceinline__ constexpr int direct_row_chan(int r) {          // channel held by row r (= 16 i + rho) of the strip
+  const int i = r >> 4, rho = r & 15;
+  return (NI % 2 == 1 && i == NI - 1) ? r : 32 * (i >> 1) + 8 * (rho >> 2) + 4 * (i & 1) + (rho & 3);
+}
+template <int NI, bool DIRECT>
+__device__ __forceinline__ constexpr int lane_chan(int i, int fq) {        // first of the 4 channels lane quarter fq holds in tile i
+  return DIRECT ? direct_row_chan<NI>(i * 16 + fq * 4) : i * 16 + fq * 4;
+}
+
 // acc <- rstd * acc - rstd * mean * s   (see KP::ln_stats).  `lnrow` (optional, LDS): the (rstd, rstd * mean) of this wave's
 // rows, indexed j * 16 + frow, computed at kernel start while the first K-step was in flight (conv_gemm_dma_kernel); without it
 // each lane sums its rows' partials here.
-template <int NI, int MI>
+template <int NI, int MI, bool DIRECT = false>
 __device__ __forceinline__ void ln_correct(const KP& p, f32x4 (&acc)[NI][MI], const int (&mrow)[MI], int nb, int fq,
                                            const float2* lnrow) {
   const int frow = threadIdx.x & 15;
@@ -261,10 +283,136 @@ __device__ __forceinline__ void ln_correct(const KP& p, f32x4 (&acc)[NI][MI], co
   }
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
-    const int n = nb + i * 16 + fq * 4;
+    const int n = nb + lane_chan<NI, DIRECT>(i, fq);
     const f32x4 sv = n < p.N ? *reinterpret_cast<const f32x4*>(p.ln_s + n) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < MI; ++j) acc[i][j] = acc[i][j] * r[j] - sv * rm[j];
+  }
+}
+
+// EPI_DIRECT epilogue: the plain modes (act 0 / 1 / 2 / 4 / 5, bias, control scale, residual, LayerNorm-folded
+// input, row statistics out; not the per-image bias2: measured slower here than staged) of an unsplit fp16 launch whose rows are 16-byte aligned (the host's conditions for KP::coalesce),
+// straight from the accumulators in the lane_chan<NI, true> layout.  No LDS, no wave barrier, one pass: per (pixel, 8 channels)
+// one 16-byte residual load and one 16-byte store; the four fq lanes of a pixel write 64 contiguous bytes.  An unpaired last tile
+// (NI odd) moves 8 bytes.  Same arithmetic and the same single rounding as the staged path, in the same order (bias,
+// activation, scale, residual; the multiply by `scale` is kept apart from the residual add as it is there), so the stored values
+// are bit-identical.  The row statistics keep the staged path's summation order as well (the 8 values of a group in channel order,
+// then the groups of the strip in channel order: the partials of a row's groups are gathered into its fq = 0 lane by index
+// shuffles), so they are bit-identical too and a network computes the same bits on either kind.
+__device__ __forceinline__ float relu_f(float v) { return fmaxf(v, 0.f); }
+template <int NI, int MI, int TN>
+__device__ __forceinline__ void epilogue_direct(const KP& p, f32x4 (&acc)[NI][MI], const int (&mrow)[MI], int nb, int fq,
+                                                const f32x4 (&bpre)[NI], bool use_bpre, const float2* lnrow = nullptr) {
+#pragma clang fp contract(off)
+  constexpr int NP = NI / 2;               // paired tiles: 8 channels per lane
+  constexpr bool ODD = NI % 2 == 1;
+  if (p.ln_stats) ln_correct<NI, MI, true>(p, acc, mrow, nb, fq, lnrow);
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int n = nb + lane_chan<NI, true>(i, fq);
+    const f32x4 bv = use_bpre ? bpre[i] : ((p.bias && n < p.N) ? *reinterpret_cast<const f32x4*>(p.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+    for (int j = 0; j < MI; ++j) acc[i][j] += bv;
+  }
+  // one uniform branch per launch, the loops inside each case
+#define SDEO_ACT_ALL(f)                                       \
+  _Pragma("unroll") for (int i = 0; i < NI; ++i)              \
+  _Pragma("unroll") for (int j = 0; j < MI; ++j)              \
+  _Pragma("unroll") for (int t = 0; t < 4; ++t) acc[i][j][t] = f(acc[i][j][t]);
+  switch (p.act) {
+    case 1: SDEO_ACT_ALL(silu_f) break;
+    case 2: SDEO_ACT_ALL(quick_gelu_f) break;
+    case 4: SDEO_ACT_ALL(relu_f) break;
+    case 5: SDEO_ACT_ALL(gelu_erf_f) break;
+    default: break;
+  }
+#undef SDEO_ACT_ALL
+  const float scale = p.scale;
+  // residual loads of every block first: they depend on nothing above
+  f16x8 resv[MI][NP > 0 ? NP : 1];
+  f16x4 reso[MI];
+#pragma unroll
+  for (int j = 0; j < MI; ++j) {
+#pragma unroll
+    for (int q = 0; q < NP; ++q) resv[j][q] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    reso[j] = f16x4{0, 0, 0, 0};
+  }
+  if (p.res) {
+#pragma unroll
+    for (int j = 0; j < MI; ++j) {
+      if (mrow[j] < 0) continue;
+      const f16* rp = p.res + (size_t)res_row(p, mrow[j]) * p.ldres + nb;
+#pragma unroll
+      for (int q = 0; q < NP; ++q)
+        if (nb + 32 * q + 8 * fq < p.N) resv[j][q] = *reinterpret_cast<const f16x8*>(rp + 32 * q + 8 * fq);
+      if (ODD && nb + 16 * (NI - 1) + 4 * fq < p.N) reso[j] = *reinterpret_cast<const f16x4*>(rp + 16 * (NI - 1) + 4 * fq);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < MI; ++j) {
+    const int m = mrow[j];
+    if (m < 0) continue;
+    f16* yp = p.y + (size_t)m * p.ldy + nb;
+    float gs[NP > 0 ? NP : 1], gq[NP > 0 ? NP : 1];      // (sum, sumsq) of this lane's 8-channel group of pair q: group 4 q + fq of the strip
+    f16x4 oo = f16x4{0, 0, 0, 0};                         // this lane's stored values of the unpaired tile
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+      gs[q] = 0.f; gq[q] = 0.f;
+      const int c = 32 * q + 8 * fq;
+      if (nb + c >= p.N) continue;
+      const f32x4 lo = acc[2 * q][j] * scale, hi = acc[2 * q + 1][j] * scale;
+      f16x8 o;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        o[u] = (f16)(lo[u] + (float)resv[j][q][u]);
+        o[4 + u] = (f16)(hi[u] + (float)resv[j][q][4 + u]);
+      }
+      *reinterpret_cast<f16x8*>(yp + c) = o;
+      if (p.stats_out) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { const float f = (float)o[u]; gs[q] += f; gq[q] += f * f; }
+      }
+    }
+    if (ODD) {
+      const int c = 16 * (NI - 1) + 4 * fq;
+      if (nb + c < p.N) {
+        const f32x4 v = acc[NI - 1][j] * scale;
+        f16x4 o;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) o[u] = (f16)(v[u] + (float)reso[j][u]);
+        *reinterpret_cast<f16x4*>(yp + c) = o;
+        oo = o;
+      }
+    }
+    if (p.stats_out) {
+      // The four lanes fq = 0..3 with this frow hold the strip's columns of row m between them (and share m: they take this branch
+      // together).  Every lane runs the gather, lane fq = 0 has the use of it.  Groups past N hold zeros, as in the staged path.
+      const int l0 = threadIdx.x & 15;
+      float ts = 0.f, tq = 0.f;
+#pragma unroll
+      for (int q = 0; q < NP; ++q)
+#pragma unroll
+        for (int f = 0; f < 4; ++f) { ts += __shfl(gs[q], l0 + 16 * f, 64); tq += __shfl(gq[q], l0 + 16 * f, 64); }
+      if (ODD) {         // the unpaired tile: groups of 8 channels span the lane pairs fq = (0, 1) and (2, 3)
+        const uint2 raw = __builtin_bit_cast(uint2, oo);
+        float v[16];
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+          const uint2 r = make_uint2(__shfl(raw.x, l0 + 16 * f, 64), __shfl(raw.y, l0 + 16 * f, 64));
+          const f16x4 h = __builtin_bit_cast(f16x4, r);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) v[f * 4 + u] = (float)h[u];
+        }
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          float s8 = 0.f, q8 = 0.f;
+#pragma unroll
+          for (int u = 0; u < 8; ++u) { s8 += v[g * 8 + u]; q8 += v[g * 8 + u] * v[g * 8 + u]; }
+          ts += s8; tq += q8;
+        }
+      }
+      if (fq == 0 && nb < p.N) reinterpret_cast<float2*>(p.stats_out)[(size_t)m * p.stats_ld + nb / TN] = make_float2(ts, tq);
+    }
   }
 }
 
@@ -659,6 +807,7 @@ struct TileCfg {
   int ph, pw;                  // TK_HALO: the patch of output pixels a workgroup owns
   const char* name;            // the instantiation, as profiles and bench.py --full key on it
   TileLaunch plain, ups, w8, mx;    // fp16 / folded nearest-x2 upsample / fp8 weights / block-scaled fp8; null where none exists
+  TileLaunch direct;                // the plain fp16 instantiation with the register-direct epilogue (EPI_DIRECT); null where none exists
 };
 // the halo-reuse 3x3 kernel's rows (conv_halo.hip: 17 variants), which kTiles takes in by position
 const TileCfg& halo_row(int variant);

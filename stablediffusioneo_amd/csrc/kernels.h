@@ -104,6 +104,7 @@ int conv_gemm_plan_splitk(const ConvGemm& p);       // split-K factor of the pla
 // tests: the tuned-table key of p and the (tile, split-K) the launcher picks for it (host only); the plan of the last launch
 void conv_gemm_query_plan(const ConvGemm& p, int key[10], int* tile, int* splitk);
 void conv_gemm_last_plan(int* tile, int* splitk);
+int conv_gemm_last_epilogue();
 // row `tile` of the tile table (kind: TileKind, caps: TileCap bits, conv_inl.h); non-zero past the end
 int conv_gemm_tile_info(int tile, int* kind, int* bm, int* bn, int* stages, int* caps, const char** name);
 // name of the kernel instantiation the launcher will pick (for profiles; matches the rocprof kernel name's template args)

@@ -42,6 +42,8 @@ int sdeo_debug_gemm_multi_f16(int count, const int* tile, const int* splitk, con
                               const void* const* bias, const void* const* res, const int* ldres, const float* scale, void* stream);
 /* (tile, split-K) of the last conv / GEMM launch (host-side record; -1 / 0 before the first) */
 void sdeo_debug_last_gemm_plan(int* tile, int* splitk);
+/* epilogue kind of that launch (csrc/conv_inl.h: EpiKind): 0 staged through LDS, 1 stored from the accumulators; -1 before the first */
+int sdeo_debug_last_gemm_epilogue(void);
 /* row `tile` of the conv / GEMM tile table (csrc/conv_gemm.hip: kTiles); returns non-zero past the end.  kind: 0 LDS-DMA implicit GEMM,
  * 1 register-staged fallback, 2 halo-reuse 3x3.  caps: 1 four-wave, 2 grouped barrier, 4 has an fp8-weight instantiation,
  * 8 has a block-scaled-fp8 instantiation, 16 halo.  Host only. */
@@ -100,6 +102,12 @@ int sdeo_debug_conv2d_gn_f16(void* ynorm, void* y, const void* x, const void* w_
 int sdeo_debug_gemm_res_rows_f16(void* y, int ldy, const void* x, int ldx, const void* w, int ldw, const float* bias, const void* res,
                                  int ldres, int res_rows, int m, int n, int k, float* stats, int stats_ld, int* strips_out, void* workspace,
                                  size_t workspace_bytes, void* stream);
+/* conv2d_ex: sdeo_conv2d_nhwc_f16 (stride 1, fp16 out) with a residual of res_rows rows (0: one per output row), per-row (sum, sumsq)
+ *   partials out (stats != NULL; *strips_out = partials per row) and a LayerNorm-folded input (ln_stats != NULL), which the launch
+ *   refuses on the host for filters larger than 1x1 */
+int sdeo_debug_conv2d_ex_f16(void* y, const void* x, const void* w_krsc, const float* bias, const void* res, int res_rows, int n, int h,
+                             int w, int cin, int cout, int ksize, float* stats, int stats_ld, int* strips_out, const float* ln_stats,
+                             const float* ln_s, int ln_ld, int ln_strips, void* workspace, size_t workspace_bytes, void* stream);
 int sdeo_debug_attention_qb_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int b,
                                 int q_batches, int heads, int tq, int tk, int tk_stride, int v_batch_stride, int d, float scale, void* stream);
 /* attention2_qb: sdeo_attention2_f16 with the same query sharing (k, v, k2, v2 and o hold b batches) */

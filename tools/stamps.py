@@ -53,5 +53,69 @@ def main():
         report(0, min(4096, ((m + bm - 1) // bm) * ((nn + bn - 1) // bn)), f"gemm {m}x{nn}x{k} tile {tile}", us)
 
 
+def anatomy(out_path):
+    """Cold against warm epilogue (SDEO_DBG_GEMM=192: bit 128 sends every workgroup through the SAME epilogue instructions twice).
+
+        SDEO_DBG_GEMM=192 [SDEO_EPI_DIRECT=0] python tools/stamps.py --anatomy out.json
+
+    Per case, medians over the workgroups of ONE launch that follows a launch of a different, large kernel (a 256-wide tile:
+    more machine code than an instruction cache holds), as in the networks: cold = stamps 3 -> 4 (loop done -> stores of the
+    first trip issued), warm = 5 -> 6 (the second trip), drain = 4 -> 5.  `same_kernel_before` is the first figure when the
+    preceding launch was the same kernel.  A run fills its own section of out.json ("staged_epilogue" under SDEO_EPI_DIRECT=0,
+    else "direct_epilogue") and keeps the other: two runs give the committed profiles/epilogue_anatomy.json."""
+    import json
+    ev_x, ev_w = rnd(512, 256), rnd(512, 256, scale=0.05)
+
+    def evict():
+        lib.sdeo_debug_force_gemm_plan(C.c_int(8), C.c_int(1))          # conv_gemm_dma_kernel<256,160,3>
+        ops.gemm(ev_x, ev_w)
+
+    def med(which, nwg, a, b):
+        buf = np.zeros(4096 * 16, dtype=np.uint64)
+        lib.sdeo_debug_read_stamps(C.c_int(which), buf.ctypes.data_as(C.c_void_p), C.c_int(buf.size))
+        st = buf.reshape(4096, 16)[:nwg].astype(np.int64)
+        st = st[(st[:, a] > 0) & (st[:, b] > 0)]
+        return float(np.median(st[:, b] - st[:, a])) / 100.0, int(len(st))
+
+    cases = []
+    for label, which, tile, nwg, make in [
+            ("conv3x3 320->320 @64x64, conv3x3_halo_kernel<8,16,80,4,3>", 1, 34, 2 * 8 * 4 * 4,
+             lambda: (rnd(2, 64, 64, 320), rnd(320, 3, 3, 320, scale=0.02), True)),
+            ("conv3x3 1280->1280 @8x8, conv3x3_halo_kernel<8,8,80,4,3>", 1, 37, 2 * 16,
+             lambda: (rnd(2, 8, 8, 1280), rnd(1280, 3, 3, 1280, scale=0.02), True)),
+            ("gemm 8192x320x320, conv_gemm_dma_kernel<64,160,3>", 0, 6, 128 * 2,
+             lambda: (rnd(8192, 320), rnd(320, 320, scale=0.02), False))]:
+        x, w, conv = make()
+        b = torch.zeros(w.shape[0], device="cuda")
+
+        def run():
+            lib.sdeo_debug_force_gemm_plan(C.c_int(tile), C.c_int(1))
+            return ops.conv2d_nhwc(x, w, b) if conv else ops.gemm(x, w, b)
+        run(); evict(); torch.cuda.synchronize()
+        evict(); run(); torch.cuda.synchronize()
+        cold, n = med(which, nwg, 3, 4)
+        warm, _ = med(which, nwg, 5, 6)
+        drain, _ = med(which, nwg, 4, 5)
+        run(); run(); torch.cuda.synchronize()
+        same, _ = med(which, nwg, 3, 4)
+        cases.append({"case": label, "workgroups": n, "epilogue": int(lib.sdeo_debug_last_gemm_epilogue()),
+                      "cold_us": cold, "warm_us": warm, "drain_us": drain, "same_kernel_before_us": same})
+        print(cases[-1])
+    lib.sdeo_debug_force_gemm_plan(C.c_int(-1), C.c_int(0))
+    out = json.load(open(out_path)) if os.path.exists(out_path) else {}
+    out["_how"] = ("measurement build (libsdeo_dbg.so), SDEO_DBG_GEMM=192 python tools/stamps.py --anatomy <this file>, once with "
+                   "SDEO_EPI_DIRECT=0 and once without; medians over the workgroups of one launch that follows a launch of "
+                   "conv_gemm_dma_kernel<256,160,3>; us")
+    out["_fields"] = ("cold = loop done -> stores of the first trip through the epilogue issued (stamps 3 -> 4); warm = the second trip "
+                      "through the same instructions (5 -> 6); drain = stores issued -> complete (4 -> 5); same_kernel_before = cold when "
+                      "the preceding launch was the same kernel.  The stamps and the debug branches cost time of their own")
+    out["direct_epilogue" if os.environ.get("SDEO_EPI_DIRECT", "1") != "0" else "staged_epilogue"] = cases
+    with open(out_path, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 if __name__ == "__main__":
-    main()
+    if "--anatomy" in sys.argv:
+        anatomy(sys.argv[sys.argv.index("--anatomy") + 1])
+    else:
+        main()
