@@ -204,11 +204,20 @@ int sdeo_conv2d_pad_nhwc_f16(void* y, const void* x, const void* w_krsc, const f
 int sdeo_debug_conv2d_gn_f16(void* ynorm, void* y, const void* x, const void* w_krsc, const float* bias, const void* res, int n, int h,
                              int w, int cin, int cout, int ksize, int stride, int upsample2x, const float* gamma, const float* beta,
                              int groups, float eps, int with_silu, float* partials, size_t partial_floats, int* slots, void* stream) {
+  return sdeo_debug_conv2d_gn_b2_f16(ynorm, y, x, w_krsc, bias, nullptr, res, n, h, w, cin, cout, ksize, stride, upsample2x, gamma, beta, groups, eps,
+                                     with_silu, partials, partial_floats, slots, stream);
+}
+
+int sdeo_debug_conv2d_gn_b2_f16(void* ynorm, void* y, const void* x, const void* w_krsc, const float* bias, const float* bias2, const void* res,
+                                int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, const float* gamma,
+                                const float* beta, int groups, float eps, int with_silu, float* partials, size_t partial_floats, int* slots,
+                                void* stream) {
   (void)disarm_fp8();
   SDEO_CHECK(slots && groups > 0 && cout % groups == 0, "conv2d_gn: bad arguments");
   ConvGemm p;
   if (int rc = fill_conv(p, n, h, w, cin, cout, ksize, stride, upsample2x)) return rc;
   p.x = (const f16*)x; p.w = (const f16*)w_krsc; p.y = (f16*)y; p.bias = bias; p.res = (const f16*)res;
+  p.bias2 = bias2; p.ld_bias2 = cout;
   const int cpg = cout / groups;
   *slots = conv_gemm_gn_slots(p, cpg);
   if (*slots <= 0) { *slots = 0; return 0; }
@@ -239,6 +248,10 @@ int sdeo_debug_gemm_plan(int m, int n, int k, int act, int fp8, int* key10, int*
 // (tile, split-K) of the last conv / GEMM launch (host-side record; -1 / 0 before the first)
 void sdeo_debug_last_gemm_plan(int* tile, int* splitk) { conv_gemm_last_plan(tile, splitk); }
 int sdeo_debug_last_gemm_epilogue(void) { return conv_gemm_last_epilogue(); }
+int sdeo_debug_last_gemm_epilogue_mode(void) { return conv_gemm_last_epilogue_mode(); }
+void sdeo_debug_force_gemm_epilogue_mode(int mode) { conv_gemm_debug_force_epilogue_mode(mode); }
+int sdeo_debug_tile_has_epilogue_mode(int tile, int mode) { return conv_gemm_tile_has_epilogue_mode(tile, mode); }
+int sdeo_debug_gemm_epilogue_census(int* rows6, int cap, int clear) { return conv_gemm_epilogue_census(rows6, cap, clear); }
 
 int sdeo_debug_tile_info(int tile, int* kind, int* bm, int* bn, int* stages, int* caps, const char** name) {
   return conv_gemm_tile_info(tile, kind, bm, bn, stages, caps, name);

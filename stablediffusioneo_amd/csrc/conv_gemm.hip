@@ -550,8 +550,8 @@ __global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const std
     if constexpr (EPI == EPI_DIRECT) {
       epilogue_direct<NI, MI, TN>(pe, acc, mrow, n0 + wn * TN, fq, bpre, use_bpre, lnrow);
     } else {
-      epilogue_rows<NI, MI, TN, NBLK>(pe, acc, mrow, n0 + wn * TN, fq, z, bpre, use_bpre, scratch, lnrow);
-      if (pe.gn_out) {                     // GroupNorm partials of this tile (loader waves, if any, are gone: the barrier counts the rest)
+      epilogue_rows<NI, MI, TN, NBLK, EPI>(pe, acc, mrow, n0 + wn * TN, fq, z, bpre, use_bpre, scratch, lnrow);
+      if (EpiMode<EPI>::gn(pe)) {          // GroupNorm partials of this tile (loader waves, if any, are gone: the barrier counts the rest)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         if (wm == 0) {                     // waves 2 wn and 2 wn + 1 share strip wn
@@ -845,36 +845,45 @@ static int launch_generic(const KP& kp, int tiles, hipStream_t stream) {
 // The tile table (TileCfg: conv_inl.h).  Adding a tile = one row here (appended: indices are public) + its index in the tests' tile
 // lists, which tests/test_tile_table_cpu.py holds against this table.  CAPS: CAP_LIGHT makes the row the four-wave instantiation;
 // CAP_W8 / CAP_MX add the fp8-weight / block-scaled-fp8 instantiation of the same shape (wave-specialised, no folded Upsample, KPB 1).
-// Epilogue kinds (EpiKind): a row has the EPI_DIRECT form of its plain fp16 instantiation (TileCfg::direct) when the networks can
-// plan it unsplit: the rows the heuristic may pick (no CAP_LIGHT / CAP_GROUPED / CAP_HALO) and the rows the committed plan table
-// (tuned_plans_gfx950.json) runs at split-K 1.  The others say so here (dma_tile<..., false>) and in conv_halo.hip (HALO against
-// HALO_D): rows 29, 31, 33, 42 and the halo rows 13, 15 - 18, 22 - 25, 36, 38.  A launch on such a row (a forced tile, a new plan
-// table) keeps the staged epilogue: direct_ok() is the one place that decides.  The folded-Upsample, fp8, block-scaled and
-// multi-problem instantiations and the register-staged fallback kernel exist as EPI_STAGED only.
-template <int BM, int BN, int ST, int CAPS = 0, int KPB = 1, bool DIRECT = true>
+// Epilogue kinds (EpiKind; KINDS = the mask of K_* bits of a row): a row has the EPI_DIRECT form of its plain fp16 instantiation when
+// the networks can plan it unsplit: the rows the heuristic may pick (no CAP_LIGHT / CAP_GROUPED / CAP_HALO) and the rows the
+// committed plan table (tuned_plans_gfx950.json) runs at split-K 1.  The others say so here (KINDS = 0) and in conv_halo.hip (HALO
+// against HALO_D): rows 29, 31, 33, 42 and the halo rows 13, 15 - 18, 22 - 25, 36, 38.  A row has a specialised kind of the staged
+// family (K_SK split-K slabs, K_GG GEGLU pair, K_GN / K_GNB GroupNorm partials without / with bias2) where the flagship step
+// launches that (tile, mode) pair under the committed plan table: the census of tools/epilogue_census.py, recorded in
+// tests/golden/epilogue_census.json and held against this table by tests/test_epilogue_kinds_cpu.py.  A launch on a row without
+// the kind of its mode (a forced tile, another network, a new plan table) runs the generic staged kernel: epi_kind() is the one
+// place that decides.  The folded-Upsample, fp8, block-scaled and multi-problem instantiations and the register-staged fallback
+// kernel exist as EPI_STAGED only.
+template <int BM, int BN, int ST, int CAPS = 0, int KPB = 1, int KINDS = K_D>
 static constexpr TileCfg dma_tile(const char* name) {
   constexpr bool WS = !(CAPS & CAP_LIGHT);
   TileCfg c{BM, BN, 64, ST, TK_DMA, CAPS | (KPB > 1 ? CAP_GROUPED : 0), KPB, 0, 0, name,
-            &launch_dma<BM, BN, ST, false, WS, false, KPB>, &launch_dma<BM, BN, ST, true, WS, false, KPB>, nullptr, nullptr, nullptr};
-  if constexpr (DIRECT) c.direct = &launch_dma<BM, BN, ST, false, WS, false, KPB, false, EPI_DIRECT>;
+            &launch_dma<BM, BN, ST, false, WS, false, KPB>, &launch_dma<BM, BN, ST, true, WS, false, KPB>, nullptr, nullptr, {}};
+  c.epi[EPI_STAGED] = c.plain;
+  if constexpr ((KINDS & K_D) != 0) c.epi[EPI_DIRECT] = &launch_dma<BM, BN, ST, false, WS, false, KPB, false, EPI_DIRECT>;
+  if constexpr ((KINDS & K_SK) != 0) c.epi[EPI_SPLITK] = &launch_dma<BM, BN, ST, false, WS, false, KPB, false, EPI_SPLITK>;
+  if constexpr ((KINDS & K_GG) != 0) c.epi[EPI_GEGLU] = &launch_dma<BM, BN, ST, false, WS, false, KPB, false, EPI_GEGLU>;
+  if constexpr ((KINDS & K_GN) != 0) c.epi[EPI_GN] = &launch_dma<BM, BN, ST, false, WS, false, KPB, false, EPI_GN>;
+  if constexpr ((KINDS & K_GNB) != 0) c.epi[EPI_GN_B2] = &launch_dma<BM, BN, ST, false, WS, false, KPB, false, EPI_GN_B2>;
   if constexpr ((CAPS & CAP_W8) != 0) c.w8 = &launch_dma<BM, BN, ST, false, true, true>;
   if constexpr ((CAPS & CAP_MX) != 0) c.mx = &launch_dma<BM, BN, ST, false, true, false, 1, true>;
   return c;
 }
 template <int BM, int BN>
 static constexpr TileCfg generic_tile(const char* name) {      // the kernel folds the Upsample at run time
-  return {BM, BN, 32, 2, TK_GENERIC, 0, 1, 0, 0, name, &launch_generic<BM, BN>, &launch_generic<BM, BN>, nullptr, nullptr};
+  return {BM, BN, 32, 2, TK_GENERIC, 0, 1, 0, 0, name, &launch_generic<BM, BN>, &launch_generic<BM, BN>, nullptr, nullptr, {&launch_generic<BM, BN>}};
 }
 static const TileCfg kTiles[] = {
     dma_tile<128, 128, 3, CAP_MX>("conv_gemm_dma_kernel<128,128,3>"),
     dma_tile<128, 64, 3, CAP_W8 | CAP_MX>("conv_gemm_dma_kernel<128,64,3>"),
-    dma_tile<64, 64, 4, CAP_W8>("conv_gemm_dma_kernel<64,64,4>"),
+    dma_tile<64, 64, 4, CAP_W8, 1, K_D | K_SK | K_GG>("conv_gemm_dma_kernel<64,64,4>"),
     generic_tile<128, 64>("conv_gemm_kernel<128,64,32,true>"),
     generic_tile<64, 64>("conv_gemm_kernel<64,64,32,true>"),
     dma_tile<256, 128, 3>("conv_gemm_dma_kernel<256,128,3>"),
     // 160-wide weight panels: the channel counts of this model are multiples of 320, and what bounds these kernels is the
     // bytes a CU has to take in per K-step, so the tile menu is built to hit 256 equal workgroups
-    dma_tile<64, 160, 3, CAP_W8 | CAP_MX>("conv_gemm_dma_kernel<64,160,3>"),
+    dma_tile<64, 160, 3, CAP_W8 | CAP_MX, 1, K_D | K_SK | K_GN>("conv_gemm_dma_kernel<64,160,3>"),
     dma_tile<128, 160, 3>("conv_gemm_dma_kernel<128,160,3>"),      // (its block-scaled fp8 form spills at the 256-register cap)
     dma_tile<256, 160, 3>("conv_gemm_dma_kernel<256,160,3>"),
     dma_tile<32, 160, 4, CAP_W8>("conv_gemm_dma_kernel<32,160,4>"),
@@ -894,19 +903,19 @@ static const TileCfg kTiles[] = {
     // epilogue are each ~2 us and serial inside a workgroup (tools/stamps.py), so what overlaps them is OTHER workgroups on the
     // same CU.  Four-wave workgroups (no loader waves: half the register footprint per workgroup) on a two-slot ring fit three
     // or four to a CU.
-    dma_tile<128, 64, 2, CAP_LIGHT>("conv_gemm_dma_kernel<128,64,2>"),
+    dma_tile<128, 64, 2, CAP_LIGHT, 1, K_D | K_GG>("conv_gemm_dma_kernel<128,64,2>"),
     dma_tile<64, 64, 2, CAP_LIGHT>("conv_gemm_dma_kernel<64,64,2>"),
-    dma_tile<128, 128, 2, CAP_LIGHT>("conv_gemm_dma_kernel<128,128,2>"),
-    dma_tile<128, 160, 2, CAP_LIGHT, 1, false>("conv_gemm_dma_kernel<128,160,2>"),
+    dma_tile<128, 128, 2, CAP_LIGHT>("conv_gemm_dma_kernel<128,128,2>"),      // (its GEGLU kind measured no gain: DESIGN.md section 32)
+    dma_tile<128, 160, 2, CAP_LIGHT, 1, 0>("conv_gemm_dma_kernel<128,160,2>"),
     dma_tile<64, 160, 2, CAP_LIGHT>("conv_gemm_dma_kernel<64,160,2>"),
-    dma_tile<32, 160, 2, CAP_LIGHT, 1, false>("conv_gemm_dma_kernel<32,160,2>"),
+    dma_tile<32, 160, 2, CAP_LIGHT, 1, 0>("conv_gemm_dma_kernel<32,160,2>"),
     dma_tile<64, 64, 3, CAP_LIGHT>("conv_gemm_dma_kernel<64,64,3>"),
-    dma_tile<128, 64, 3, CAP_LIGHT, 1, false>("conv_gemm_dma_kernel<128,64,3>/4w"),
+    dma_tile<128, 64, 3, CAP_LIGHT, 1, 0>("conv_gemm_dma_kernel<128,64,3>/4w"),
     // halo kernels with one barrier per filter row (three taps)
     halo_row(10), halo_row(11), halo_row(12), halo_row(13), halo_row(14), halo_row(15), halo_row(16),
     // implicit-GEMM tiles with one barrier per GROUP of K-steps (conv_gemm_dma_kernel KPB): name<BM,BN,STAGES,KPB>
-    dma_tile<32, 160, 6, 0, 2>("conv_gemm_dma_kernel<32,160,6,k2>"),
-    dma_tile<64, 64, 8, 0, 2, false>("conv_gemm_dma_kernel<64,64,8,k2>"),
+    dma_tile<32, 160, 6, 0, 2, K_D | K_GN>("conv_gemm_dma_kernel<32,160,6,k2>"),
+    dma_tile<64, 64, 8, 0, 2, 0>("conv_gemm_dma_kernel<64,64,8,k2>"),
     dma_tile<64, 64, 9, 0, 3>("conv_gemm_dma_kernel<64,64,9,k3>"),
     dma_tile<64, 160, 5, 0, 2>("conv_gemm_dma_kernel<64,160,5,k2>"),
     dma_tile<128, 64, 6, 0, 2>("conv_gemm_dma_kernel<128,64,6,k2>"),
@@ -919,7 +928,7 @@ static const int kTileCount = (int)std::size(kTiles);
 static bool by_plan_only(const TileCfg& c) { return (c.caps & (CAP_HALO | CAP_LIGHT | CAP_GROUPED)) != 0; }
 static const int kNumCU = 256;
 
-struct Plan { int tile; int splitk; int nk; int tiles_m, tiles_n; int direct; };      // direct: the launch runs the EPI_DIRECT instantiation of the tile (set by prepare)
+struct Plan { int tile; int splitk; int nk; int tiles_m, tiles_n; int epi; };      // epi: the EpiKind instantiation of the tile the launch runs (set by prepare)
 
 static bool is_fast(const ConvGemm& p) { return p.Cin % 64 == 0; }
 static bool halo_ok(const ConvGemm& p, const TileCfg& c) {
@@ -1074,7 +1083,31 @@ void conv_gemm_query_plan(const ConvGemm& p0, int key[10], int* tile, int* split
 // (tile, split-K) of the last problem conv_gemm() launched: host-side only, read by the tests through sdeo_debug_last_gemm_plan
 static int g_last_tile = -1, g_last_splitk = 0, g_last_epilogue = -1;
 void conv_gemm_last_plan(int* tile, int* splitk) { *tile = g_last_tile; *splitk = g_last_splitk; }
-int conv_gemm_last_epilogue() { return g_last_epilogue; }       // EpiKind of that launch
+int conv_gemm_last_epilogue() { return g_last_epilogue < 0 ? -1 : g_last_epilogue == EPI_DIRECT ? EPI_DIRECT : EPI_STAGED; }       // the family of that launch
+int conv_gemm_last_epilogue_mode() { return g_last_epilogue >= EPI_SPLITK ? g_last_epilogue : 0; }      // its kind within the staged family (0 = generic)
+static int g_force_epi_mode = -1;
+void conv_gemm_debug_force_epilogue_mode(int mode) { g_force_epi_mode = mode; }
+int conv_gemm_tile_has_epilogue_mode(int tile, int mode) {
+  return tile >= 0 && tile < kTileCount && mode >= 0 && mode < EPI_KINDS && mode != EPI_DIRECT && kTiles[tile].epi[mode] != nullptr;
+}
+
+// Census of the launches dispatch() made: (tile, split-K, operand form, EpiKind run, mode flags of the problem) -> count.  Host
+// side, plain integers; tools/epilogue_census.py reads and clears it.  form: 0 plain, 1 folded Upsample, 2 fp8 weights,
+// 3 block-scaled fp8, 4 multi-problem.  flags: act | 8 bias2 | 16 GroupNorm partials | 32 row statistics | 64 LayerNorm fold |
+// 128 residual | 256 coalesced.
+static std::map<std::array<int, 5>, int> g_census;
+static int census_flags(const KP& kp) {
+  return kp.act | (kp.bias2 ? 8 : 0) | (kp.gn_out ? 16 : 0) | (kp.stats_out ? 32 : 0) | (kp.ln_stats ? 64 : 0) | (kp.res ? 128 : 0) | (kp.coalesce ? 256 : 0);
+}
+int conv_gemm_epilogue_census(int* rows6, int cap, int clear) {       // rows of (tile, split-K, form, kind, flags, count); returns their number
+  int n = 0;
+  for (auto& kv : g_census) {
+    if (n < cap) { for (int i = 0; i < 5; ++i) rows6[n * 6 + i] = kv.first[i]; rows6[n * 6 + 5] = kv.second; }
+    ++n;
+  }
+  if (clear) g_census.clear();
+  return n;
+}
 
 // Which launches run the EPI_DIRECT instantiation of their tile (epilogue_direct): those the LDS-transposed epilogue would serve
 // (kp.coalesce: unsplit, fp16 output, N % 8 == 0, 16-byte aligned output and residual rows) in a plain mode.  The GEGLU pair
@@ -1083,7 +1116,28 @@ int conv_gemm_last_epilogue() { return g_last_epilogue; }       // EpiKind of th
 // SDEO_EPI_DIRECT=0 (measurement) keeps every launch on the staged epilogue.
 static int direct_ok(const ConvGemm& p, const KP& kp, const TileCfg& c) {
   static const int on = [] { const char* e = getenv("SDEO_EPI_DIRECT"); return e ? atoi(e) : 1; }();
-  return on && c.direct && kp.coalesce && p.act != 3 && !p.gn_out && !p.bias2 && !p.ups && !p.wscale && !p.mx_sx;
+  return on && c.epi[EPI_DIRECT] && kp.coalesce && p.act != 3 && !p.gn_out && !p.bias2 && !p.ups && !p.wscale && !p.mx_sx;
+}
+// The kind of the staged family whose mode the problem in kp has (EpiMode, conv_inl.h), EPI_STAGED when it has none: what a
+// specialised kernel may assume is exactly what is tested here.  The fp8, block-scaled and folded-Upsample instantiations exist
+// as EPI_STAGED only.
+static int staged_mode(const KP& kp) {
+  if (kp.wscale || kp.mx_sx || kp.ups) return EPI_STAGED;
+  if (kp.splitk > 1) return EPI_SPLITK;
+  if (!kp.coalesce || kp.stats_out) return EPI_STAGED;
+  if (kp.act == 3) return EPI_GEGLU;
+  if (kp.ln_stats || kp.act != 0 || !kp.gn_out) return EPI_STAGED;
+  return kp.bias2 ? EPI_GN_B2 : EPI_GN;
+}
+// The EpiKind a launch runs: the one place that decides.  A row without the instantiation of the problem's mode runs the generic
+// kernel.  SDEO_EPI_KINDS=0 (measurement) and conv_gemm_debug_force_epilogue_mode(0) keep every non-direct launch on it.
+static int epi_kind(const ConvGemm& p, const KP& kp, const Plan& pl) {
+  static const int kinds_on = [] { const char* e = getenv("SDEO_EPI_KINDS"); return e ? atoi(e) : 1; }();
+  const TileCfg& c = kTiles[pl.tile];
+  if (direct_ok(p, kp, c)) return EPI_DIRECT;
+  if (!kinds_on || g_force_epi_mode == 0) return EPI_STAGED;
+  const int k = staged_mode(kp);
+  return c.epi[k] ? k : EPI_STAGED;
 }
 
 // argument checks + plan + kernel parameters of one problem
@@ -1165,6 +1219,7 @@ static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
   }
   kp.nk = pl.nk; kp.splitk = pl.splitk; kp.nk_per_split = cdiv(pl.nk, pl.splitk);
   kp.tiles_m = pl.tiles_m; kp.tiles_n = pl.tiles_n;
+  pl.epi = EPI_STAGED;
   {
     // Each of the 8 XCDs has a private L2 and gets a contiguous run of tiles.  With N fastest every activation row is
     // fetched by one XCD but every XCD streams all the weights; with M fastest it is the other way round (each XCD
@@ -1181,7 +1236,6 @@ static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
                   (reinterpret_cast<uintptr_t>(p.y) & 15) == 0 &&
                   (!p.res || (p.ldres % 8 == 0 && (reinterpret_cast<uintptr_t>(p.res) & 15) == 0));
     SDEO_CHECK(!p.gn_out || kp.coalesce, "conv_gemm: GroupNorm partials need the LDS-transposed epilogue");
-    pl.direct = direct_ok(p, kp, kTiles[pl.tile]);
   }
   if (pl.splitk > 1) {
     const size_t need = (size_t)pl.splitk * p.M * p.N * sizeof(float);
@@ -1189,6 +1243,7 @@ static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
                p.workspace_bytes, need);
   }
   if (kTiles[pl.tile].kind == TK_HALO) SDEO_CHECK(halo_ok(p, kTiles[pl.tile]), "conv_gemm: halo plan on an ineligible problem");
+  pl.epi = epi_kind(p, kp, pl);
   return 0;
 }
 
@@ -1196,9 +1251,13 @@ static int prepare(const ConvGemm& p, Plan& pl, KP& kp) {
 static int dispatch(const Plan& pl, int ups, bool w8, const KP& kp, hipStream_t stream) {
   if (pl.tile < 0 || pl.tile >= kTileCount) return fail("conv_gemm: bad tile %d", pl.tile);
   const TileCfg& c = kTiles[pl.tile];
-  if (pl.direct && (kp.mx_sx || w8 || ups || !c.direct)) return fail("conv_gemm: tile %d has no register-direct instantiation for this launch", pl.tile);
-  const TileLaunch launch = pl.direct ? c.direct : kp.mx_sx ? c.mx : w8 ? c.w8 : ups ? c.ups : c.plain;
+  if (pl.epi < 0 || pl.epi >= EPI_KINDS) return fail("conv_gemm: bad epilogue kind %d", pl.epi);
+  if (pl.epi != EPI_STAGED && (kp.mx_sx || w8 || ups || !c.epi[pl.epi]))
+    return fail("conv_gemm: tile %d has no %s instantiation for this launch", pl.tile, pl.epi == EPI_DIRECT ? "register-direct" : "specialised staged");
+  if (pl.epi >= EPI_SPLITK && pl.epi != staged_mode(kp)) return fail("conv_gemm: epilogue kind %d does not match the problem's mode (%d)", pl.epi, staged_mode(kp));
+  const TileLaunch launch = pl.epi != EPI_STAGED ? c.epi[pl.epi] : kp.mx_sx ? c.mx : w8 ? c.w8 : ups ? c.ups : c.plain;
   if (!launch) return fail("conv_gemm: tile %d has no %s instantiation", pl.tile, kp.mx_sx ? "block-scaled fp8" : w8 ? "fp8-weight" : "folded-upsample");
+  ++g_census[{pl.tile, pl.splitk, kp.mx_sx ? 3 : w8 ? 2 : ups ? 1 : 0, pl.epi, census_flags(kp)}];
   if (int rc = launch(kp, pl.tiles_m * pl.tiles_n, stream)) return rc;
   if (pl.splitk > 1) {
     const int64_t n = (int64_t)kp.M * (kp.N / 4);
@@ -1215,7 +1274,7 @@ int conv_gemm(const ConvGemm& p0, hipStream_t stream) {
   Plan pl;
   KP kp{};
   if (int rc = prepare(p, pl, kp)) return rc;
-  g_last_tile = pl.tile; g_last_splitk = pl.splitk; g_last_epilogue = pl.direct ? EPI_DIRECT : EPI_STAGED;
+  g_last_tile = pl.tile; g_last_splitk = pl.splitk; g_last_epilogue = pl.epi;
   return dispatch(pl, p.ups, p.wscale != nullptr, kp, stream);
 }
 
@@ -1281,6 +1340,7 @@ int conv_gemm_multi_launch(const ConvGemmMultiPlan& pl, const void* table_dev, c
   a.count = pl.count;
   for (int i = 0; i < pl.count; ++i) a.scale[i] = scales ? scales[i] : pl.scale[i];
   g_last_tile = pl.tile; g_last_splitk = 1; g_last_epilogue = EPI_STAGED;
+  ++g_census[{pl.tile, 1, 4, EPI_STAGED, 0}];
   return mt->launch(a, pl.tiles, stream);
 }
 

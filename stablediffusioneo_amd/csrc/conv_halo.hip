@@ -284,8 +284,8 @@ __global__ __launch_bounds__(NMW * 64 + 256) void conv3x3_halo_kernel(const KP p
     if constexpr (EPI == EPI_DIRECT) {
       epilogue_direct<NI, MI, BN>(pe, acc, mrow, n0, fq, bpre, use_bpre);
     } else {
-      epilogue_rows<NI, MI, BN, NBLK>(pe, acc, mrow, n0, fq, z, bpre, use_bpre, smem + wave * SCR);
-      if (pe.gn_out) {                     // GroupNorm partials of this patch: the loader waves are gone, the barrier counts the rest
+      epilogue_rows<NI, MI, BN, NBLK, EPI>(pe, acc, mrow, n0, fq, z, bpre, use_bpre, smem + wave * SCR);
+      if (EpiMode<EPI>::gn(pe)) {          // GroupNorm partials of this patch: the loader waves are gone, the barrier counts the rest
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         if (wave == 0) gn_partials_finish<BN, NMW>(pe, smem, SCR, lane, b, trem, n0);
@@ -323,27 +323,34 @@ static int launch_halo_t(const KP& kp, int tiles, hipStream_t stream) {
   return 0;
 }
 
-template <bool DIRECT, int PH, int PW, int BN, int NMW, int TPB = 1>
+template <int KINDS, int PH, int PW, int BN, int NMW, int TPB = 1>
 static constexpr TileCfg halo_tile(const char* name) {
-  TileCfg c{PH * PW, BN, 64, halo_stages(PH, PW, BN, TPB), TK_HALO, CAP_HALO, 1, PH, PW, name, &launch_halo_t<PH, PW, BN, NMW, TPB>, nullptr, nullptr, nullptr, nullptr};
-  if constexpr (DIRECT) c.direct = &launch_halo_t<PH, PW, BN, NMW, TPB, EPI_DIRECT>;
+  TileCfg c{PH * PW, BN, 64, halo_stages(PH, PW, BN, TPB), TK_HALO, CAP_HALO, 1, PH, PW, name, &launch_halo_t<PH, PW, BN, NMW, TPB>, nullptr, nullptr, nullptr, {}};
+  c.epi[EPI_STAGED] = c.plain;
+  if constexpr ((KINDS & K_D) != 0) c.epi[EPI_DIRECT] = &launch_halo_t<PH, PW, BN, NMW, TPB, EPI_DIRECT>;
+  if constexpr ((KINDS & K_SK) != 0) c.epi[EPI_SPLITK] = &launch_halo_t<PH, PW, BN, NMW, TPB, EPI_SPLITK>;
+  if constexpr ((KINDS & K_GN) != 0) c.epi[EPI_GN] = &launch_halo_t<PH, PW, BN, NMW, TPB, EPI_GN>;
+  if constexpr ((KINDS & K_GNB) != 0) c.epi[EPI_GN_B2] = &launch_halo_t<PH, PW, BN, NMW, TPB, EPI_GN_B2>;
   return c;
 }
 // a variant is written down once: its template arguments, spelled without blanks, are also its name.  HALO_D: the variant also has
-// the EPI_DIRECT form (the variants the committed plan table runs unsplit, see the list at kTiles in conv_gemm.hip).
-#define HALO(...) halo_tile<false, __VA_ARGS__>("conv3x3_halo_kernel<" #__VA_ARGS__ ">")
-#define HALO_D(...) halo_tile<true, __VA_ARGS__>("conv3x3_halo_kernel<" #__VA_ARGS__ ">")
+// the EPI_DIRECT form (the variants the committed plan table runs unsplit, see the list at kTiles in conv_gemm.hip).  HALO_K: and
+// the specialised kinds of the staged family that the flagship step launches on it (the census, see there).
+#define HALO(...) halo_tile<0, __VA_ARGS__>("conv3x3_halo_kernel<" #__VA_ARGS__ ">")
+#define HALO_D(...) halo_tile<K_D, __VA_ARGS__>("conv3x3_halo_kernel<" #__VA_ARGS__ ">")
+#define HALO_K(kinds, ...) halo_tile<K_D | kinds, __VA_ARGS__>("conv3x3_halo_kernel<" #__VA_ARGS__ ">")
 const TileCfg& halo_row(int variant) {
   static const TileCfg rows[] = {
       HALO(8,16,80,4), HALO_D(8,16,160,4), HALO(8,8,80,4), HALO(8,8,160,4), HALO(8,16,64,4), HALO(8,16,128,4),
       // two MFMA waves per SIMD
       HALO(8,16,80,8), HALO(8,16,160,8), HALO(8,16,64,8), HALO(8,16,128,8),
       // one barrier per filter row (TPB = 3)
-      HALO_D(8,16,80,4,3), HALO_D(8,16,80,8,3), HALO(8,16,64,4,3), HALO_D(8,8,80,4,3), HALO(8,8,160,4,3), HALO_D(8,16,128,8,3), HALO_D(8,16,64,8,3),
+      HALO_K(K_SK, 8,16,80,4,3), HALO_K(K_GN | K_GNB, 8,16,80,8,3), HALO(8,16,64,4,3), HALO_K(K_SK | K_GN | K_GNB, 8,8,80,4,3), HALO(8,8,160,4,3), HALO_D(8,16,128,8,3), HALO_D(8,16,64,8,3),
   };
   return rows[variant];
 }
 #undef HALO
 #undef HALO_D
+#undef HALO_K
 
 }  // namespace sdeo

@@ -251,7 +251,34 @@ __device__ __forceinline__ void ln_row_scalars(const KP& p, int row, float& r, f
 //  EPI_STAGED  everything epilogue_rows does (LDS-transposed stores, GEGLU pair, GroupNorm partials, split-K slabs, 8-byte fallback)
 //  EPI_DIRECT  16-byte stores straight from the accumulators (epilogue_direct): the weight rows of a strip are dealt to the MFMA
 //              rows in a permuted order, so that a lane holds 8 consecutive channels across accumulator tiles 2q and 2q + 1
-enum EpiKind { EPI_STAGED = 0, EPI_DIRECT = 1 };
+// The kinds from EPI_SPLITK on are the staged family: epilogue_rows with the tests of one launch mode resolved at compile time
+// (EpiMode below), so that a launch carries the one path it takes instead of all of them.  Same source text, same operations in
+// the same order: every stored value, GroupNorm partial and split-K slab is bit-identical to EPI_STAGED, which stays the fallback
+// of every launch without a specialised form.  The host picks the kind (conv_gemm.hip: epi_kind) and guarantees its mode.
+//  EPI_SPLITK  splitk > 1: the fp32 slab stores of the per-row loop
+//  EPI_GEGLU   act == 3 on the coalesced path: the pair path through the LDS transposition (LayerNorm fold still read at run time)
+//  EPI_GN      coalesced, GroupNorm partials out, no bias2, no activation (residual read at run time)
+//  EPI_GN_B2   the same with a per-image bias2
+enum EpiKind { EPI_STAGED = 0, EPI_DIRECT = 1, EPI_SPLITK = 2, EPI_GEGLU = 3, EPI_GN = 4, EPI_GN_B2 = 5, EPI_KINDS = 6 };
+
+// What a kind knows of its launch at compile time.  Each predicate reads the parameter block in EPI_STAGED and is a constant in a
+// specialised kind, so the branches of epilogue_rows it guards exist in the instantiations that can take them only.
+template <int EPI>
+struct EpiMode {
+  static_assert(EPI == EPI_STAGED || (EPI >= EPI_SPLITK && EPI < EPI_KINDS), "a kind of the staged family");
+  static constexpr bool generic = EPI == EPI_STAGED;
+  static constexpr bool k_gn = EPI == EPI_GN || EPI == EPI_GN_B2;
+  static constexpr bool k_block = k_gn;                 // the kinds of the coalesced block path
+  static constexpr bool k_b2 = EPI == EPI_GN_B2;        // stage_block<..., B2, ACT> of a block kind
+  static constexpr int k_act = 0;
+  static __device__ __forceinline__ bool split(const KP& p) { return generic ? p.splitk > 1 : EPI == EPI_SPLITK; }
+  static __device__ __forceinline__ bool pair(const KP& p, const char* scratch) { return generic ? scratch && p.coalesce && p.act == 3 : EPI == EPI_GEGLU; }
+  static __device__ __forceinline__ bool block(const KP& p, const char* scratch) { return generic ? scratch && p.coalesce && p.act != 3 : k_block; }
+  static __device__ __forceinline__ bool gn(const KP& p) { return generic ? p.gn_out != nullptr : k_gn; }
+  static __device__ __forceinline__ bool stats(const KP& p) { return generic && p.stats_out != nullptr; }
+  static __device__ __forceinline__ bool wscale(const KP& p) { return generic && p.wscale != nullptr && p.splitk == 1; }
+  static __device__ __forceinline__ bool ln(const KP& p) { return generic ? p.ln_stats != nullptr && p.splitk == 1 : EPI == EPI_GEGLU && p.ln_stats != nullptr; }
+};
 
 // EPI_DIRECT channel map of a strip of NI 16-row accumulator tiles.  Row rho of tile i carries channel
 // 32 (i >> 1) + 8 (rho >> 2) + 4 (i & 1) + (rho & 3) of the strip: the accumulator rows of lane (frow, fq) are rho = 4 fq + t, so the
@@ -420,12 +447,14 @@ __device__ __forceinline__ void epilogue_direct(const KP& p, f32x4 (&acc)[NI][MI
 // MI blocks costs MI dependent write -> read -> store chains; staging several blocks first issues their residual loads, LDS
 // reads and global stores back to back (measured with tools/gemm_ablate.py: the epilogue is ~40 % of a many-tile short-K GEMM
 // and of the order of a third of every ~8 us conv / GEMM launch).
-template <int NI, int MI, int TN, int NB = 1>
+template <int NI, int MI, int TN, int NB = 1, int EPI = EPI_STAGED>
 __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI], const int (&mrow)[MI], int nb, int fq, int z,
                                               const f32x4 (&bpre)[NI], bool use_bpre, char* scratch = nullptr,
                                               const float2* lnrow = nullptr) {
   static_assert(NB >= 1 && MI % NB == 0, "blocks per staging round");
-  if (p.wscale && p.splitk == 1) {
+  using Mode = EpiMode<EPI>;
+  static_assert(EPI != EPI_GEGLU || (NI % 2 == 0 && TN % 32 == 0), "the GEGLU pair needs an even number of accumulator tiles per strip");
+  if (Mode::wscale(p)) {
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int n = nb + i * 16 + fq * 4;
@@ -434,9 +463,9 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
       for (int j = 0; j < MI; ++j) acc[i][j] *= sc;
     }
   }
-  if (p.ln_stats && p.splitk == 1) ln_correct<NI, MI>(p, acc, mrow, nb, fq, lnrow);
+  if (Mode::ln(p)) ln_correct<NI, MI>(p, acc, mrow, nb, fq, lnrow);
   if constexpr (NI % 2 == 0 && TN % 32 == 0) {
-    if (scratch && p.coalesce && p.act == 3) {
+    if (Mode::pair(p, scratch)) {
       // GEGLU pair epilogue (see below) through the same LDS transposition: value * gelu(gate) is formed in the accumulator
       // layout, staged as fp32 [16 rows][TN / 2] and stored in 16-byte pieces, TN bytes contiguous per row
       constexpr int TNO = TN / 2, ROWB = TNO * 4 + 16, G = TNO / 8, PASSES = (16 * G + 63) / 64;
@@ -488,7 +517,7 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
       return;
     }
   }
-  if (scratch && p.coalesce && p.act != 3) {
+  if (Mode::block(p, scratch)) {
     constexpr int ROWB = TN * 4 + 16;            // odd multiple of 16 bytes: the 16 rows of a block start in different banks
     constexpr int G = TN / 8;                    // 8-channel groups per row
     constexpr int PASSES = (16 * G + 63) / 64;
@@ -549,7 +578,9 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
 #pragma unroll
         for (int i = 0; i < NI; ++i) accj[i] = acc[i][j0 + jb];
         if (dbg_on(p, 2048)) continue;          // ablation: no staging writes
-        switch (mode) {
+        if constexpr (!Mode::generic) {
+          stage_block<NI, TN, Mode::k_b2, Mode::k_act>(p, accj, bias, m, nb, fq, frow, sc);
+        } else switch (mode) {
           case 0: stage_block<NI, TN, false, 0>(p, accj, bias, m, nb, fq, frow, sc); break;
           case 1: stage_block<NI, TN, false, 1>(p, accj, bias, m, nb, fq, frow, sc); break;
           case 2: stage_block<NI, TN, false, 2>(p, accj, bias, m, nb, fq, frow, sc); break;
@@ -581,18 +612,18 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
               o[4 + u] = (f16)(hi[u] + (float)resv[jb][t][4 + u]);
             }
             if (!dbg_on(p, 512)) *reinterpret_cast<f16x8*>(p.y + (size_t)mm[jb][t] * p.ldy + nn[t]) = o;
-            if (p.stats_out) {
+            if (Mode::stats(p)) {
 #pragma unroll
               for (int u = 0; u < 8; ++u) { const float f = (float)o[u]; ssum += f; ssq += f * f; }
             }
-            if (p.gn_out) *reinterpret_cast<f16x8*>(scratch + jb * BLOCKB + 16 * ROWB + (rr[t] * TN + (nn[t] - nb)) * 2) = o;
-          } else if (p.gn_out && t * 64 + lane < 16 * G) {     // rows / columns past the problem count as zeros
+            if (Mode::gn(p)) *reinterpret_cast<f16x8*>(scratch + jb * BLOCKB + 16 * ROWB + (rr[t] * TN + (nn[t] - nb)) * 2) = o;
+          } else if (Mode::gn(p) && t * 64 + lane < 16 * G) {     // rows / columns past the problem count as zeros
             *reinterpret_cast<f16x8*>(scratch + jb * BLOCKB + 16 * ROWB + (rr[t] * TN + (nn[t] - nb)) * 2) = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
           }
-          if (p.stats_out && t * 64 + lane < 16 * G) spart[t * 64 + lane] = make_float2(ssum, ssq);     // index = row * G + group
+          if (Mode::stats(p) && t * 64 + lane < 16 * G) spart[t * 64 + lane] = make_float2(ssum, ssq);     // index = row * G + group
         }
       }
-      if (p.gn_out) {
+      if (Mode::gn(p)) {
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int jb = 0; jb < NB; ++jb) {
@@ -607,7 +638,7 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
           }
         }
       }
-      if (p.stats_out) {
+      if (Mode::stats(p)) {
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int jb = 0; jb < NB; ++jb) {
@@ -625,7 +656,7 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
       if (j0 == 0) stamp(p, 11);
       __builtin_amdgcn_wave_barrier();        // the next round overwrites the scratch rows
     }
-    if (p.gn_out) {      // this wave's per-column (sum, sumsq) at the start of its scratch: gn_partials_finish combines the waves
+    if (Mode::gn(p)) {      // this wave's per-column (sum, sumsq) at the start of its scratch: gn_partials_finish combines the waves
 #pragma unroll
       for (int c = 0; c < GCH; ++c)
         if (c * 64 + lane < TN) reinterpret_cast<float2*>(scratch)[c * 64 + lane] = make_float2(gsum[c], gsq[c]);
@@ -637,7 +668,7 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
   for (int j = 0; j < MI; ++j) {
     const int m = mrow[j];
     if (m < 0) continue;
-    if constexpr (NI % 2 == 0 && TN % 32 == 0) {
+    if constexpr (Mode::generic && NI % 2 == 0 && TN % 32 == 0) {
       if (p.act == 3) {
         // GEGLU (`attention.py:49-56`) fused into ff.net.0.proj: the weight rows were interleaved at load time in blocks of
         // 16 (block 2q = value channels 16q..16q+15, block 2q+1 = their gates), so accumulator tiles i and i+1 hold, in the
@@ -666,7 +697,7 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
       const int n = nb + i * 16 + fq * 4;
       if (n >= p.N) continue;
       f32x4 v = acc[i][j];
-      if (p.splitk > 1) {
+      if (Mode::split(p)) {
         *reinterpret_cast<f32x4*>(p.ws + ((size_t)z * p.M + m) * p.N + n) = v;
         continue;
       }
@@ -708,7 +739,7 @@ __device__ __forceinline__ void epilogue_rows(const KP& p, f32x4 (&acc)[NI][MI],
         }
       }
     }
-    if (p.stats_out && p.splitk == 1) {
+    if (Mode::stats(p) && !Mode::split(p)) {
       // the four lanes fq = 0..3 with this frow hold the strip's columns of row m between them
       ssum += __shfl_xor(ssum, 16, 64); ssq += __shfl_xor(ssq, 16, 64);
       ssum += __shfl_xor(ssum, 32, 64); ssq += __shfl_xor(ssq, 32, 64);
@@ -807,8 +838,11 @@ struct TileCfg {
   int ph, pw;                  // TK_HALO: the patch of output pixels a workgroup owns
   const char* name;            // the instantiation, as profiles and bench.py --full key on it
   TileLaunch plain, ups, w8, mx;    // fp16 / folded nearest-x2 upsample / fp8 weights / block-scaled fp8; null where none exists
-  TileLaunch direct;                // the plain fp16 instantiation with the register-direct epilogue (EPI_DIRECT); null where none exists
+  TileLaunch epi[EPI_KINDS];        // the plain fp16 instantiation per epilogue kind (EpiKind): [EPI_STAGED] = plain, the others null where
+                                    // the row has no such kind
 };
+// the kinds a row instantiates besides EPI_STAGED, as a mask in the row's description (dma_tile / halo_tile)
+constexpr int K_D = 1 << EPI_DIRECT, K_SK = 1 << EPI_SPLITK, K_GG = 1 << EPI_GEGLU, K_GN = 1 << EPI_GN, K_GNB = 1 << EPI_GN_B2;
 // the halo-reuse 3x3 kernel's rows (conv_halo.hip: 17 variants), which kTiles takes in by position
 const TileCfg& halo_row(int variant);
 

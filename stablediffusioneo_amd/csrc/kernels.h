@@ -104,7 +104,12 @@ int conv_gemm_plan_splitk(const ConvGemm& p);       // split-K factor of the pla
 // tests: the tuned-table key of p and the (tile, split-K) the launcher picks for it (host only); the plan of the last launch
 void conv_gemm_query_plan(const ConvGemm& p, int key[10], int* tile, int* splitk);
 void conv_gemm_last_plan(int* tile, int* splitk);
-int conv_gemm_last_epilogue();
+int conv_gemm_last_epilogue();                     // 0 the staged family, 1 EPI_DIRECT
+int conv_gemm_last_epilogue_mode();                // the EpiKind within the staged family (conv_inl.h), 0 = the generic kernel
+void conv_gemm_debug_force_epilogue_mode(int mode);      // -1 automatic, 0 every non-direct launch on the generic kernel
+int conv_gemm_tile_has_epilogue_mode(int tile, int mode);
+// launches dispatched since the last clear as rows of (tile, split-K, operand form, EpiKind, mode flags, count): conv_gemm.hip, g_census
+int conv_gemm_epilogue_census(int* rows6, int cap, int clear);
 // row `tile` of the tile table (kind: TileKind, caps: TileCap bits, conv_inl.h); non-zero past the end
 int conv_gemm_tile_info(int tile, int* kind, int* bm, int* bn, int* stages, int* caps, const char** name);
 // name of the kernel instantiation the launcher will pick (for profiles; matches the rocprof kernel name's template args)

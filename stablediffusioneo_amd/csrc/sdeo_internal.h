@@ -42,8 +42,21 @@ int sdeo_debug_gemm_multi_f16(int count, const int* tile, const int* splitk, con
                               const void* const* bias, const void* const* res, const int* ldres, const float* scale, void* stream);
 /* (tile, split-K) of the last conv / GEMM launch (host-side record; -1 / 0 before the first) */
 void sdeo_debug_last_gemm_plan(int* tile, int* splitk);
-/* epilogue kind of that launch (csrc/conv_inl.h: EpiKind): 0 staged through LDS, 1 stored from the accumulators; -1 before the first */
+/* epilogue kind of that launch (csrc/conv_inl.h: EpiKind): 0 the staged family (the generic kernel and every specialisation of it),
+ * 1 stored from the accumulators; -1 before the first */
 int sdeo_debug_last_gemm_epilogue(void);
+/* the staged mode of that launch: 0 the generic kernel (and every direct launch), else the EpiKind of the specialised kernel:
+ * 2 split-K slabs, 3 GEGLU pair, 4 GroupNorm partials, 5 GroupNorm partials with a per-image bias2 */
+int sdeo_debug_last_gemm_epilogue_mode(void);
+/* -1 automatic, 0 every non-direct launch runs the generic staged kernel (process-wide, as SDEO_EPI_KINDS=0): A/B inside one process */
+void sdeo_debug_force_gemm_epilogue_mode(int mode);
+/* 1 when row `tile` of the tile table has the specialised kernel of staged mode `mode` (0: the generic kernel).  Host only. */
+int sdeo_debug_tile_has_epilogue_mode(int tile, int mode);
+/* the conv / GEMM launches dispatched since the last clear, as rows of six ints (tile, split-K, operand form, EpiKind run, mode flags,
+ * count) written to rows6 (room for `cap` rows); returns the number of rows.  form: 0 plain, 1 folded Upsample, 2 fp8 weights,
+ * 3 block-scaled fp8, 4 multi-problem.  flags: act | 8 bias2 | 16 GroupNorm partials | 32 row statistics | 64 LayerNorm fold |
+ * 128 residual | 256 coalesced epilogue.  Host-side counters (launches under graph replay are not seen).  tools/epilogue_census.py */
+int sdeo_debug_gemm_epilogue_census(int* rows6, int cap, int clear);
 /* row `tile` of the conv / GEMM tile table (csrc/conv_gemm.hip: kTiles); returns non-zero past the end.  kind: 0 LDS-DMA implicit GEMM,
  * 1 register-staged fallback, 2 halo-reuse 3x3.  caps: 1 four-wave, 2 grouped barrier, 4 has an fp8-weight instantiation,
  * 8 has a block-scaled-fp8 instantiation, 16 halo.  Host only. */
@@ -91,6 +104,11 @@ int sdeo_debug_row_stats_f16(float* stats, int stats_ld, const void* x, int ldx,
 int sdeo_debug_conv2d_gn_f16(void* ynorm, void* y, const void* x, const void* w_krsc, const float* bias, const void* res, int n, int h,
                              int w, int cin, int cout, int ksize, int stride, int upsample2x, const float* gamma, const float* beta,
                              int groups, float eps, int with_silu, float* partials, size_t partial_floats, int* slots, void* stream);
+/* the same with a per-image bias2 ([n][cout] fp32, NULL = none) added before the store: the ResBlock in_layers conv + time embedding */
+int sdeo_debug_conv2d_gn_b2_f16(void* ynorm, void* y, const void* x, const void* w_krsc, const float* bias, const float* bias2, const void* res,
+                                int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, const float* gamma,
+                                const float* beta, int groups, float eps, int with_silu, float* partials, size_t partial_floats, int* slots,
+                                void* stream);
 
 /* op-level hooks of the shared prefix of the CFG pair (tests; csrc/net_build.hip build_attn): operands that a full-batch launch reads from a
  * half-batch tensor.

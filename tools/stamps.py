@@ -114,8 +114,84 @@ def anatomy(out_path):
         json.dump(out, f, indent=1)
 
 
+def anatomy_kinds(out_path):
+    """Cold against warm epilogue of the specialised kinds of the staged family against the generic staged kernel (measurement build):
+
+        SDEO_DBG_GEMM=192 python tools/stamps.py --anatomy-kinds out.json
+
+    The cases of anatomy() run in the modes the flagship step runs them in: the two halo convs as GroupNorm-partial launches (the 64x64
+    one on conv3x3_halo_kernel<8,16,80,8,3>, the row the step plans for it unsplit), two GEGLU GEMMs (the row of the first, conv_gemm_dma_kernel<128,128,2>, has
+    no pair kind any more: both its runs are the generic kernel) and one split-K GEMM.  Each case
+    runs as the specialised kernel and, under sdeo_debug_force_gemm_epilogue_mode(0), as the generic one, in one process; fields as
+    in anatomy()."""
+    import json
+    from stablediffusioneo_amd._lib import check, cur_stream, ptr
+    ev_x, ev_w = rnd(512, 256), rnd(512, 256, scale=0.05)
+
+    def evict():
+        lib.sdeo_debug_force_gemm_plan(C.c_int(8), C.c_int(1))          # conv_gemm_dma_kernel<256,160,3>
+        ops.gemm(ev_x, ev_w)
+
+    def med(which, nwg, a, b):
+        buf = np.zeros(4096 * 16, dtype=np.uint64)
+        lib.sdeo_debug_read_stamps(C.c_int(which), buf.ctypes.data_as(C.c_void_p), C.c_int(buf.size))
+        st = buf.reshape(4096, 16)[:nwg].astype(np.int64)
+        st = st[(st[:, a] > 0) & (st[:, b] > 0)]
+        return float(np.median(st[:, b] - st[:, a])) / 100.0, int(len(st))
+
+    def conv_gn(n, hw, c):
+        x, w, b, res = rnd(n, hw, hw, c), rnd(c, 3, 3, c, scale=0.02), torch.zeros(c, device="cuda"), rnd(n, hw, hw, c)
+        y, yn = torch.empty_like(res), torch.empty_like(res)
+        gamma, beta = torch.ones(c, device="cuda"), torch.zeros(c, device="cuda")
+        pf = n * hw * hw * 32 * 2
+        part, slots = torch.zeros(pf, device="cuda"), C.c_int(0)
+        return lambda: check(lib.sdeo_debug_conv2d_gn_b2_f16(ptr(yn), ptr(y), ptr(x), ptr(w), ptr(b), None, ptr(res), n, hw, hw, c, c, 3, 1, 0, ptr(gamma),
+                                                             ptr(beta), 32, 1e-5, 1, ptr(part), pf, C.byref(slots), cur_stream()), "conv2d_gn")
+
+    xg, wg = rnd(8192, 320), ops.geglu_interleave(rnd(2560, 320, scale=0.02))
+    xh, wh = rnd(2048, 640), ops.geglu_interleave(rnd(5120, 640, scale=0.02))
+    xs, ws_, rs = rnd(128, 1280), rnd(1280, 1280, scale=0.02), rnd(128, 1280)
+    cases = []
+    for label, which, tile, sk, nwg, fn in [
+            ("GroupNorm partials + residual: conv3x3 320->320 @64x64, conv3x3_halo_kernel<8,16,80,8,3>", 1, 35, 1, 2 * 8 * 4 * 4, conv_gn(2, 64, 320)),
+            ("GroupNorm partials + residual: conv3x3 1280->1280 @8x8, conv3x3_halo_kernel<8,8,80,4,3>", 1, 37, 1, 2 * 16, conv_gn(2, 8, 1280)),
+            ("GEGLU pair: gemm 8192x2560x320, conv_gemm_dma_kernel<128,128,2>", 0, 28, 1, 64 * 20, lambda: ops.gemm_geglu(xg, wg)),
+            ("GEGLU pair: gemm 2048x5120x640, conv_gemm_dma_kernel<128,64,2>", 0, 26, 1, 16 * 80, lambda: ops.gemm_geglu(xh, wh)),
+            ("split-K 5 slabs: gemm 128x1280x1280 + residual, conv_gemm_dma_kernel<64,64,4>", 0, 2, 5, 2 * 20 * 5, lambda: ops.gemm(xs, ws_, res=rs))]:
+        for force, side in ((-1, "specialised"), (0, "generic")):
+            lib.sdeo_debug_force_gemm_epilogue_mode(C.c_int(force))
+
+            def run():
+                lib.sdeo_debug_force_gemm_plan(C.c_int(tile), C.c_int(sk))
+                fn()
+            run(); evict(); torch.cuda.synchronize()
+            evict(); run(); torch.cuda.synchronize()
+            cold, n = med(which, nwg, 3, 4)
+            warm, _ = med(which, nwg, 5, 6)
+            drain, _ = med(which, nwg, 4, 5)
+            mode = int(lib.sdeo_debug_last_gemm_epilogue_mode())
+            run(); run(); torch.cuda.synchronize()
+            same, _ = med(which, nwg, 3, 4)
+            cases.append({"case": label, "kernel": side, "workgroups": n, "cold_us": cold, "warm_us": warm, "drain_us": drain,
+                          "same_kernel_before_us": same, "epilogue_mode": mode})
+            print(cases[-1])
+    lib.sdeo_debug_force_gemm_epilogue_mode(C.c_int(-1))
+    lib.sdeo_debug_force_gemm_plan(C.c_int(-1), C.c_int(0))
+    out = {"_how": ("measurement build (libsdeo_dbg.so), SDEO_DBG_GEMM=192 python tools/stamps.py --anatomy-kinds <this file>; each case as the "
+                    "specialised kernel of its mode and, under sdeo_debug_force_gemm_epilogue_mode(0), as the generic staged kernel; medians over "
+                    "the workgroups of one launch that follows a launch of conv_gemm_dma_kernel<256,160,3>; us"),
+           "_fields": ("cold = loop done -> stores of the first trip through the epilogue issued (stamps 3 -> 4); warm = the second trip through the "
+                       "same instructions (5 -> 6); drain = stores issued -> complete (4 -> 5); same_kernel_before = cold when the preceding launch "
+                       "was the same kernel.  The stamps and the debug branches cost time of their own"),
+           "cases": cases}
+    with open(out_path, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 if __name__ == "__main__":
-    if "--anatomy" in sys.argv:
+    if "--anatomy-kinds" in sys.argv:
+        anatomy_kinds(sys.argv[sys.argv.index("--anatomy-kinds") + 1])
+    elif "--anatomy" in sys.argv:
         anatomy(sys.argv[sys.argv.index("--anatomy") + 1])
     else:
         main()
