@@ -212,12 +212,13 @@ int sdeo_debug_conv2d_gn_b2_f16(void* ynorm, void* y, const void* x, const void*
                                 int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x, const float* gamma,
                                 const float* beta, int groups, float eps, int with_silu, float* partials, size_t partial_floats, int* slots,
                                 void* stream) {
-  (void)disarm_fp8();
+  const Fp8Arm arm = disarm_fp8();
   SDEO_CHECK(slots && groups > 0 && cout % groups == 0, "conv2d_gn: bad arguments");
   ConvGemm p;
   if (int rc = fill_conv(p, n, h, w, cin, cout, ksize, stride, upsample2x)) return rc;
   p.x = (const f16*)x; p.w = (const f16*)w_krsc; p.y = (f16*)y; p.bias = bias; p.res = (const f16*)res;
   p.bias2 = bias2; p.ld_bias2 = cout;
+  take_fp8(p, arm);
   const int cpg = cout / groups;
   *slots = conv_gemm_gn_slots(p, cpg);
   if (*slots <= 0) { *slots = 0; return 0; }
@@ -294,6 +295,29 @@ int sdeo_debug_gemm_mx_f16(void* y, int ldy, const void* xq, const void* xs, con
   return conv_gemm(p, S(stream));
 }
 
+// sdeo_debug_gemm_mx_f16 with what csrc/net_build.hip hands a block-scaled launch besides bias / residual / act: an output scale, a
+// residual of res_rows rows, row statistics out and a LayerNorm-folded input (act 3: the GEGLU pair, weights in geglu_interleave order)
+int sdeo_debug_gemm_mx_ex_f16(void* y, int ldy, const void* xq, const void* xs, const void* wq, const void* ws, const float* bias, const void* res,
+                              int ldres, int res_rows, int m, int n, int k, int act, float scale, float* stats, int stats_ld, int* strips_out,
+                              const float* ln_stats, const float* ln_s, int ln_ld, int ln_strips, int ln_c, float eps, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  (void)disarm_fp8();
+  ConvGemm p;
+  fill_gemm(p, m, n, k);
+  p.x = (const f16*)xq; p.w = (const f16*)wq; p.y = (f16*)y; p.bias = bias; p.res = (const f16*)res;
+  p.ldx = k; p.ldw = k; p.ldy = ldy; p.ldres = ldres; p.res_rows = res_rows; p.act = act; p.scale = scale;
+  p.mx_sx = (const uint8_t*)xs; p.mx_sw = (const uint8_t*)ws; p.mx_ldsx = k / 32; p.mx_ldsw = k / 32;
+  p.workspace = (float*)workspace; p.workspace_bytes = workspace_bytes;
+  if (ln_stats) { p.ln_stats = ln_stats; p.ln_s = ln_s; p.ln_ld = ln_ld; p.ln_strips = ln_strips; p.ln_c = ln_c; p.ln_eps = eps; }
+  if (stats) {       // as sdeo_debug_gemm_res_rows_f16: a split-K plan (*strips_out = 0) still runs and leaves the statistics to row_stats
+    SDEO_CHECK(strips_out, "gemm_mx_ex: null argument");
+    *strips_out = conv_gemm_stats_strips(p);
+    SDEO_CHECK(*strips_out <= stats_ld, "gemm_mx_ex: %d strips do not fit stats_ld %d", *strips_out, stats_ld);
+    if (*strips_out > 0) { p.stats_out = stats; p.stats_ld = stats_ld; }
+  }
+  return conv_gemm(p, S(stream));
+}
+
 int sdeo_debug_quantize_fp8_rows(void* w_f16_inout, void* q_out, float* scale_out, int rows, int cols, void* stream) {
   return quantize_fp8_rows((uint8_t*)q_out, scale_out, (f16*)w_f16_inout, rows, cols, cols, cols, S(stream));
 }
@@ -311,11 +335,13 @@ int sdeo_debug_compose_proj(void* w_out, float* b_out, const void* wp, const flo
 
 int sdeo_debug_gemm_stats_f16(void* y, int ldy, const void* x, int ldx, const void* w, int ldw, const float* bias, const void* res,
                               int ldres, int m, int n, int k, float* stats, int stats_ld, int* strips_out, void* stream) {
+  const Fp8Arm arm = disarm_fp8();
   SDEO_CHECK(stats && strips_out, "gemm_stats: null argument");
   ConvGemm p;
   fill_gemm(p, m, n, k);
   p.x = (const f16*)x; p.w = (const f16*)w; p.bias = bias; p.res = (const f16*)res; p.y = (f16*)y;
   p.ldx = ldx; p.ldw = ldw; p.ldy = ldy; p.ldres = ldres;
+  take_fp8(p, arm);
   *strips_out = conv_gemm_stats_strips(p);
   if (*strips_out == 0) return 0;
   SDEO_CHECK(*strips_out <= stats_ld, "gemm_stats: %d strips do not fit stats_ld %d", *strips_out, stats_ld);
@@ -326,11 +352,13 @@ int sdeo_debug_gemm_stats_f16(void* y, int ldy, const void* x, int ldx, const vo
 int sdeo_debug_gemm_res_rows_f16(void* y, int ldy, const void* x, int ldx, const void* w, int ldw, const float* bias, const void* res,
                                  int ldres, int res_rows, int m, int n, int k, float* stats, int stats_ld, int* strips_out, void* workspace,
                                  size_t workspace_bytes, void* stream) {
+  const Fp8Arm arm = disarm_fp8();
   ConvGemm p;
   fill_gemm(p, m, n, k);
   p.x = (const f16*)x; p.w = (const f16*)w; p.bias = bias; p.res = (const f16*)res; p.y = (f16*)y;
   p.ldx = ldx; p.ldw = ldw; p.ldy = ldy; p.ldres = ldres; p.res_rows = res_rows;
   p.workspace = (float*)workspace; p.workspace_bytes = workspace_bytes;
+  take_fp8(p, arm);
   if (stats) {
     SDEO_CHECK(strips_out, "gemm_res_rows: null argument");
     *strips_out = conv_gemm_stats_strips(p);
@@ -346,10 +374,12 @@ int sdeo_debug_gemm_res_rows_f16(void* y, int ldy, const void* x, int ldx, const
 int sdeo_debug_conv2d_ex_f16(void* y, const void* x, const void* w_krsc, const float* bias, const void* res, int res_rows, int n, int h,
                              int w, int cin, int cout, int ksize, float* stats, int stats_ld, int* strips_out, const float* ln_stats,
                              const float* ln_s, int ln_ld, int ln_strips, void* workspace, size_t workspace_bytes, void* stream) {
+  const Fp8Arm arm = disarm_fp8();
   ConvGemm p;
   if (int rc = fill_conv(p, n, h, w, cin, cout, ksize, 1, 0)) return rc;
   p.x = (const f16*)x; p.w = (const f16*)w_krsc; p.y = (f16*)y; p.bias = bias; p.res = (const f16*)res; p.res_rows = res_rows;
   p.workspace = (float*)workspace; p.workspace_bytes = workspace_bytes;
+  take_fp8(p, arm);
   if (ln_stats) { p.ln_stats = ln_stats; p.ln_s = ln_s; p.ln_ld = ln_ld; p.ln_strips = ln_strips; p.ln_c = cin; p.ln_eps = 1e-5f; }
   if (stats) {
     SDEO_CHECK(strips_out, "conv2d_ex: null argument");
@@ -363,6 +393,7 @@ int sdeo_debug_conv2d_ex_f16(void* y, const void* x, const void* w_krsc, const f
 int sdeo_debug_gemm_multi_f16(int count, const int* tile, const int* splitk, const int* m, const int* n, const int* k, void* const* y,
                               const int* ldy, const void* const* x, const int* ldx, const void* const* w, const int* ldw,
                               const void* const* bias, const void* const* res, const int* ldres, const float* scale, void* stream) {
+  (void)disarm_fp8();       // multi-problem launches are fp16 only
   SDEO_CHECK(count >= 1 && tile && splitk && m && n && k && y && ldy && x && ldx && w && ldw && scale, "gemm_multi: null argument");
   std::vector<ConvGemm> ps((size_t)count);
   for (int i = 0; i < count; ++i) {
@@ -389,12 +420,14 @@ int sdeo_debug_gemm_multi_f16(int count, const int* tile, const int* splitk, con
 
 int sdeo_debug_gemm_ln_f16(void* y, int ldy, const void* x, int ldx, const void* w_folded, int ldw, const float* ln_s,
                            const float* bias_folded, const float* stats, int stats_ld, int strips, int ln_c, int m, int n, int k, int act, float eps, void* workspace, size_t workspace_bytes, void* stream) {
+  const Fp8Arm arm = disarm_fp8();
   ConvGemm p;
   fill_gemm(p, m, n, k);
   p.x = (const f16*)x; p.w = (const f16*)w_folded; p.bias = bias_folded; p.y = (f16*)y;
   p.ldx = ldx; p.ldw = ldw; p.ldy = ldy; p.act = act;
   p.ln_stats = stats; p.ln_s = ln_s; p.ln_strips = strips; p.ln_ld = stats_ld; p.ln_c = ln_c; p.ln_eps = eps;
   p.workspace = (float*)workspace; p.workspace_bytes = workspace_bytes;
+  take_fp8(p, arm);
   return conv_gemm(p, S(stream));
 }
 

@@ -289,10 +289,14 @@ struct Builder {
   }
 };
 
-// block-scaled fp8 on both sides: pack the activations (one launch), run the GEMM on the fp8 MFMA
+// block-scaled fp8 on both sides: pack the activations (one launch), run the GEMM on the fp8 MFMA.
+// Not with the LayerNorm fold: the fold multiplies the RAW rows and subtracts mean * s afterwards, so the pack would round the rows
+// with their mean still in them.  e4m3 rounds relative to the element, i.e. to the mean of a row that sits far off zero, and that error
+// does not cancel in acc - mean * s: at 16 standard deviations off zero the folded block-scaled launch measured 0.37 of the output
+// scale against 0.037 for LayerNorm first, pack second (profiles/mx_ln_fold_error.json).  Those GEMMs keep fp16 activations.
 void Fp8State::use_mx(ConvGemm& p, int Mplan, Builder& b) {
   if (!(act_bits == 8 && mxslab && Mplan >= mx_min_rows && p.R == 1 && p.S == 1 && p.stride == 1 && !p.ups && p.K % 128 == 0 &&
-        p.K == p.Cin && p.ldx % 16 == 0 && !p.bias_per_row && p.y && !p.y32))
+        p.K == p.Cin && p.ldx % 16 == 0 && !p.bias_per_row && p.y && !p.y32 && !p.ln_stats))
     return;
   auto it = mxindex.find((size_t)(reinterpret_cast<const char*>(p.w) - b.e->ws.slab));
   if (it == mxindex.end() || it->second.cols != p.ldw || p.N > it->second.rows) return;

@@ -135,13 +135,23 @@ int sdeo_debug_attention2_qb_f16(void* o, int ldo, const void* q, int ldq, const
                                  float scale, void* stream);
 
 /* fp8 weight pack at op level (tests): quantise [rows][cols] fp16 in place to its dequantised values, codes -> q, scales -> scale;
- * sdeo_debug_next_weights_fp8 makes the NEXT sdeo_gemm_f16 / sdeo_conv2d_nhwc_f16 call of this thread stream these codes
- * (K-contiguous bytes, same [N][K] / KRSC layout) instead of its fp16 weight argument */
+ * sdeo_debug_next_weights_fp8 makes the NEXT conv / GEMM call of this thread (sdeo_gemm_f16, sdeo_conv2d_nhwc_f16, sdeo_conv2d_pad_nhwc_f16,
+ * sdeo_debug_gemm_stats_f16, _gemm_res_rows_f16, _gemm_ln_f16, _conv2d_ex_f16, _conv2d_gn_f16, _conv2d_gn_b2_f16) stream these codes
+ * (K-contiguous bytes, same [N][K] / KRSC layout) instead of its fp16 weight argument; sdeo_debug_gemm_multi_f16 and the
+ * block-scaled entries drop it unused.  Every one of them disarms first, so a refused call leaves nothing armed */
 /* block-scaled fp8 (e4m3fn codes + one e8m0 scale per 32 elements of a row) at op level: the pack of an fp16 [rows][cols] matrix
  * (q_out [rows][cols] bytes, scales_out [rows][cols / 32] bytes) and y = x w^T on two packed operands with v_mfma_scale_f32_16x16x128_f8f6f4 */
 int sdeo_debug_quantize_mx(void* q_out, void* scales_out, const void* x, int rows, int cols, void* stream);
 int sdeo_debug_gemm_mx_f16(void* y, int ldy, const void* xq, const void* xs, const void* wq, const void* ws, const float* bias, const void* res,
                            int ldres, int m, int n, int k, int act, void* workspace, size_t workspace_bytes, void* stream);
+/* gemm_mx_ex: sdeo_debug_gemm_mx_f16 with an output scale (ahead of the residual), a residual of res_rows rows (0: one per output
+ *   row), per-row (sum, sumsq) partials out (stats != NULL; *strips_out = 0 with a split-K plan: the GEMM still runs, the statistics
+ *   are sdeo_debug_row_stats_f16's) and a LayerNorm-folded input (ln_stats != NULL, as sdeo_debug_gemm_ln_f16 takes it); act 3 = the
+ *   GEGLU pair on weights in geglu_interleave order (ldy >= n / 2) */
+int sdeo_debug_gemm_mx_ex_f16(void* y, int ldy, const void* xq, const void* xs, const void* wq, const void* ws, const float* bias, const void* res,
+                              int ldres, int res_rows, int m, int n, int k, int act, float scale, float* stats, int stats_ld, int* strips_out,
+                              const float* ln_stats, const float* ln_s, int ln_ld, int ln_strips, int ln_c, float eps, void* workspace,
+                              size_t workspace_bytes, void* stream);
 int sdeo_debug_quantize_fp8_rows(void* w_f16_inout, void* q_out, float* scale_out, int rows, int cols, void* stream);
 void sdeo_debug_next_weights_fp8(const void* q, const float* scale);
 

@@ -109,6 +109,35 @@ def gemm_mx(xq, xs, wq, ws, bias=None, res=None, act=0):
     return y
 
 
+def gemm_mx_ex(xq, xs, wq, ws, bias=None, res=None, res_rows=0, act=0, scale=1.0, want_stats=False, ln=None, eps=1e-5):
+    """gemm_mx with what the networks hand a block-scaled launch besides bias / residual / act (sdeo_debug_gemm_mx_ex_f16): an output
+    scale ahead of the residual, a residual of res_rows rows (0: one per output row; res may be a column block), row statistics out
+    (want_stats: returns (y, stats, strips) as gemm_with_row_stats) and a LayerNorm-folded input, ln = (stats [m][ld][2], strips, s [n])
+    with bias the folded bias.  act 3: the GEGLU pair, weights / bias in geglu_interleave order."""
+    lib = _lib.load()
+    _need_cuda(xq, wq)
+    m, k = xq.shape
+    n = wq.shape[0]
+    assert k % 128 == 0 and wq.shape[1] == k and xs.shape == (m, k // 32) and ws.shape == (n, k // 32)
+    assert res is None or (res.shape == (res_rows or m, n) and res.stride(1) == 1)
+    y = torch.empty((m, n // 2 if act == 3 else n), dtype=torch.float16, device=xq.device)
+    ld = max(1, (n + 31) // 32)
+    stats = torch.zeros((m, ld, 2), dtype=torch.float32, device=xq.device) if want_stats else None
+    strips = C.c_int(0)
+    lst, lstrips, lns = ln if ln is not None else (None, 0, None)
+    wsb = _ws(64 << 20, xq.device)
+    check(lib.sdeo_debug_gemm_mx_ex_f16(ptr(y), y.shape[1], ptr(xq), ptr(xs), ptr(wq), ptr(ws), ptr(bias), ptr(res),
+                                        res.stride(0) if res is not None else 0, res_rows, m, n, k, act, scale, ptr(stats), ld,
+                                        C.byref(strips), ptr(lst), ptr(lns), lst.shape[1] if lst is not None else 0, lstrips, k, eps,
+                                        ptr(wsb), wsb.numel(), cur_stream()), "gemm_mx_ex")
+    if not want_stats:
+        return y
+    if strips.value == 0:
+        check(lib.sdeo_debug_row_stats_f16(ptr(stats), ld, ptr(y), y.shape[1], m, y.shape[1], cur_stream()), "row_stats")
+        return y, stats, 1
+    return y, stats, strips.value
+
+
 def _arm_fp8(lib, w8):
     if w8 is not None:
         q, sc = w8
@@ -166,9 +195,11 @@ def conv2d_pad_nhwc(x, w_krsc, pad_before, pad_after, bias=None, bias2=None, res
     return y
 
 
-def conv2d_gn(x, w_krsc, gamma, beta, bias=None, res=None, stride=1, upsample2x=False, groups=32, eps=1e-5, swish=False):
+def conv2d_gn(x, w_krsc, gamma, beta, bias=None, res=None, stride=1, upsample2x=False, groups=32, eps=1e-5, swish=False, bias2=None,
+              w8=None, want_partials=False):
     """[conv2d whose epilogue emits the GroupNorm partials of its output] -> [normalise-only GroupNorm]: returns (y, GroupNorm(y), slots)
-    or None when the plan of this shape cannot emit partials (split-K, strips cutting a group, ...)."""
+    or None when the plan of this shape cannot emit partials (split-K, strips cutting a group, ...).  bias2: a per-image (N, Cout) fp32
+    bias.  w8 = (codes, scales): stream the fp8 copy.  want_partials: (y, GroupNorm(y), slots, partials [N][slots][groups][2])."""
     lib = _lib.load()
     _need_cuda(x, w_krsc, gamma, beta)
     n, h, w, cin = x.shape
@@ -183,12 +214,44 @@ def conv2d_gn(x, w_krsc, gamma, beta, bias=None, res=None, stride=1, upsample2x=
     pf = n * (ho * wo) * groups * 2 // 16 + n * groups * 2 + 1024           # tiles hold >= 32 rows: more than any plan needs
     part = torch.empty(pf, dtype=torch.float32, device=x.device)
     slots = C.c_int(0)
-    check(lib.sdeo_debug_conv2d_gn_f16(ptr(yn), ptr(y), ptr(x), ptr(w_krsc), ptr(bias), ptr(res), n, h, w, cin, cout, k, stride,
-                                       int(upsample2x), ptr(gamma), ptr(beta), groups, eps, int(swish), ptr(part), pf, C.byref(slots),
-                                       cur_stream()), "conv2d_gn")
+    _arm_fp8(lib, w8)
+    if bias2 is None:
+        check(lib.sdeo_debug_conv2d_gn_f16(ptr(yn), ptr(y), ptr(x), ptr(w_krsc), ptr(bias), ptr(res), n, h, w, cin, cout, k, stride,
+                                           int(upsample2x), ptr(gamma), ptr(beta), groups, eps, int(swish), ptr(part), pf, C.byref(slots),
+                                           cur_stream()), "conv2d_gn")
+    else:
+        assert bias2.shape == (n, cout) and bias2.dtype == torch.float32 and bias2.is_contiguous()
+        check(lib.sdeo_debug_conv2d_gn_b2_f16(ptr(yn), ptr(y), ptr(x), ptr(w_krsc), ptr(bias), ptr(bias2), ptr(res), n, h, w, cin, cout, k,
+                                              stride, int(upsample2x), ptr(gamma), ptr(beta), groups, eps, int(swish), ptr(part), pf,
+                                              C.byref(slots), cur_stream()), "conv2d_gn")
     if slots.value == 0:
         return None
+    if want_partials:
+        return y, yn, slots.value, part[: n * slots.value * groups * 2].view(n, slots.value, groups, 2)
     return y, yn, slots.value
+
+
+def conv2d_ex(x, w_krsc, bias=None, res=None, res_rows=0, want_stats=False, ln=None, w8=None):
+    """conv2d_nhwc (stride 1) with what the networks can add to a conv (sdeo_debug_conv2d_ex_f16): a residual of res_rows rows
+    ((res_rows, Cout); 0: one per output row), row statistics out (want_stats) and, for 1x1 filters, a LayerNorm-folded input
+    ln = (stats [M][ld][2] with one strip, s [Cout]).  w8 = (codes, scales): stream the fp8 copy.  Returns (y, stats or None, strips)."""
+    lib = _lib.load()
+    _need_cuda(x, w_krsc)
+    n, h, w, cin = x.shape
+    cout, k = w_krsc.shape[0], w_krsc.shape[1]
+    assert w_krsc.shape[3] == cin and x.is_contiguous() and w_krsc.is_contiguous()
+    y = torch.empty((n, h, w, cout), dtype=torch.float16, device=x.device)
+    ld = max(1, (cout + 31) // 32)
+    stats = torch.zeros((n * h * w, ld, 2), dtype=torch.float32, device=x.device) if want_stats else None
+    strips = C.c_int(0)
+    nb = lib.sdeo_conv2d_workspace_bytes(n, h, w, cin, cout, k, 1, 0)
+    ws = _ws(nb if w8 is None else max(nb, 64 << 20), x.device)
+    lst, lns = ln if ln is not None else (None, None)
+    _arm_fp8(lib, w8)
+    check(lib.sdeo_debug_conv2d_ex_f16(ptr(y), ptr(x), ptr(w_krsc), ptr(bias), ptr(res), res_rows, n, h, w, cin, cout, k, ptr(stats), ld,
+                                       C.byref(strips), ptr(lst), ptr(lns), lst.shape[1] if lst is not None else 0,
+                                       1 if lst is not None else 0, ptr(ws), ws.numel(), cur_stream()), "conv2d_ex")
+    return y, stats, strips.value
 
 
 def gemm(x, w, bias=None, res=None, act=0, scale=1.0, out_f32=False, bias_per_row=False, w8=None, out=None):
@@ -265,9 +328,10 @@ def compose_proj(wp, bp, w2, b2):
     return wo, bo
 
 
-def gemm_with_row_stats(x, w, bias=None, res=None):
+def gemm_with_row_stats(x, w, bias=None, res=None, w8=None):
     """y = x w^T (+bias)(+res) in fp16 plus the per-row (sum, sumsq) partials its epilogue writes: (y, stats [m][ld][2], strips).
-    When the plan for this shape is split-K the statistics come from the row_stats kernel (strips = 1), as in the networks."""
+    When the plan for this shape is split-K the statistics come from the row_stats kernel (strips = 1), as in the networks.
+    w8 = (codes, scales): stream the fp8 copy of w instead."""
     lib = _lib.load()
     _need_cuda(x, w)
     m, k = x.shape
@@ -276,20 +340,21 @@ def gemm_with_row_stats(x, w, bias=None, res=None):
     ld = max(1, (n + 31) // 32)
     stats = torch.zeros((m, ld, 2), dtype=torch.float32, device=x.device)
     strips = C.c_int(0)
+    _arm_fp8(lib, w8)
     check(lib.sdeo_debug_gemm_stats_f16(ptr(y), n, ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(res),
                                         res.stride(0) if res is not None else 0, m, n, k, ptr(stats), ld, C.byref(strips),
                                         cur_stream()), "gemm_stats")
     if strips.value == 0:
-        y = gemm(x, w, bias=bias, res=res)
+        y = gemm(x, w, bias=bias, res=res, w8=w8)
         check(lib.sdeo_debug_row_stats_f16(ptr(stats), ld, ptr(y), n, m, n, cur_stream()), "row_stats")
         return y, stats, 1
     return y, stats, strips.value
 
 
-def gemm_res_rows(x, w, res, res_rows, bias=None, want_stats=False):
+def gemm_res_rows(x, w, res, res_rows, bias=None, want_stats=False, w8=None):
     """y = x w^T (+bias) + res[r mod res_rows] in fp16: the residual holds res_rows = m / 2 rows that both halves of the batch add
     (the shared prefix of the CFG pair, csrc/net_build.hip build_attn).  res may be a column block of a wider tensor.
-    want_stats: returns (y, stats, strips) as gemm_with_row_stats."""
+    want_stats: returns (y, stats, strips) as gemm_with_row_stats.  w8 = (codes, scales): stream the fp8 copy of w instead."""
     lib = _lib.load()
     _need_cuda(x, w, res)
     m, k = x.shape
@@ -299,7 +364,9 @@ def gemm_res_rows(x, w, res, res_rows, bias=None, want_stats=False):
     ld = max(1, (n + 31) // 32)
     stats = torch.zeros((m, ld, 2), dtype=torch.float32, device=x.device) if want_stats else None
     strips = C.c_int(0)
-    ws = _ws(lib.sdeo_gemm_workspace_bytes(m, n, k), x.device)
+    nb = lib.sdeo_gemm_workspace_bytes(m, n, k)
+    ws = _ws(nb if w8 is None else max(nb, 64 << 20), x.device)
+    _arm_fp8(lib, w8)
     check(lib.sdeo_debug_gemm_res_rows_f16(ptr(y), n, ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(res),
                                            res.stride(0), res_rows, m, n, k, ptr(stats), ld, C.byref(strips), ptr(ws), ws.numel(),
                                            cur_stream()), "gemm_res_rows")
@@ -311,14 +378,17 @@ def gemm_res_rows(x, w, res, res_rows, bias=None, want_stats=False):
     return y, stats, strips.value
 
 
-def gemm_layernorm(x, stats, strips, w_folded, ln_s, bias_folded, act=0, eps=1e-5):
-    """y[m][n] = act(LN(x)[m] . w[n] + b[n]) with x [m][k] raw and the fold of (w, gamma, beta, bias)."""
+def gemm_layernorm(x, stats, strips, w_folded, ln_s, bias_folded, act=0, eps=1e-5, w8=None):
+    """y[m][n] = act(LN(x)[m] . w[n] + b[n]) with x [m][k] raw and the fold of (w, gamma, beta, bias).  w8 = (codes, scales) of the
+    folded matrix: stream the fp8 copy (ln_s must then hold the row sums of the dequantised matrix)."""
     lib = _lib.load()
     _need_cuda(x, w_folded, stats)
     m, k = x.shape
     n = w_folded.shape[0]
     y = torch.empty((m, n // 2 if act == 3 else n), dtype=torch.float16, device=x.device)
-    ws = _ws(lib.sdeo_gemm_workspace_bytes(m, n, k), x.device)
+    nb = lib.sdeo_gemm_workspace_bytes(m, n, k)
+    ws = _ws(nb if w8 is None else max(nb, 64 << 20), x.device)
+    _arm_fp8(lib, w8)
     check(lib.sdeo_debug_gemm_ln_f16(ptr(y), y.shape[1], ptr(x), x.stride(0), ptr(w_folded), w_folded.stride(0), ptr(ln_s), ptr(bias_folded),
                                      ptr(stats), stats.shape[1], strips, k, m, n, k, act, eps, ptr(ws), ws.numel(), cur_stream()), "gemm_ln")
     return y
