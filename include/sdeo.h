@@ -590,6 +590,59 @@ int sdeo_clip_lora_clear(sdeo_clip_handle h);
 int sdeo_clip_lora_touched(sdeo_clip_handle h);
 int sdeo_clip_read_weight(sdeo_clip_handle h, const char* name, float* out);
 
+/* ------------------------------------------------------------------ image encoder (the image prompt of sdeo_set_ip_tokens, from a picture)
+ * HuggingFace CLIPVisionModelWithProjection: pixel_values -> image_embeds [batch][proj], optionally hidden_states[-2].  The tower the
+ * ip-adapter_sd15 files are trained against is OpenCLIP ViT-H/14: image 224, patch 14 (257 tokens), width 1280, 32 layers, 16 heads,
+ * ffn 5120, erf GELU, proj 1024.  Tensor names are those of the HuggingFace state dict below "vision_model." (anything up to and
+ * including "vision_model." is stripped) plus "visual_projection.weight":
+ *   embeddings.class_embedding [W], embeddings.patch_embedding.weight [W][3][p][p], embeddings.position_embedding.weight [T][W],
+ *   pre_layrnorm.* (the upstream spelling), encoder.layers.N.* as in the text tower, post_layernorm.*, visual_projection.weight [proj][W].
+ *
+ * sdeo_clip_image_preprocess_u8: CLIPImageProcessor for ONE 8-bit RGB HWC image of any size, on the device -- PIL's
+ *   Image.resize(BICUBIC) of the shortest side to S (the long side is int(S * long / short)), the centre crop S x S
+ *   (top = (nh - S) / 2, left = (nw - S) / 2, floor), v = fp32(u * (1.0 / 255)), (v - mean) / std in fp32 with CLIP's mean / std, and
+ *   the result as fp16 patch rows [(S / patch)^2][Kp]: Kp = 3 patch^2 rounded up to a multiple of 8, column (py * patch + px) * 3 + c,
+ *   columns >= 3 patch^2 zero.  PIL's resampler is integer arithmetic (ImagingResample, a = -0.5 bicubic, 22 fractional bits, the
+ *   horizontal pass first, an 8-bit intermediate); the per-axis tables hold it and are built on the host from the sizes alone
+ *   (stablediffusioneo_amd/annotator/util.py: clip_preprocess_tables), for the S columns / rows of the CROP only:
+ *     x_first[S], x_count[S]: first source column and tap count of crop column j; x_coeffs[S][x_taps]: its int32 coefficients;
+ *     y_*: the same for the crop's rows against source rows; src_row0, src_rows: the source rows the crop's rows tap (only those
+ *     are resampled horizontally).  Table entries are clamped on the device: no table makes a launch read outside the image.
+ *   Two launches: the horizontal pass into the 8-bit workspace, then vertical pass + normalise + patchify.  crop_u8 (optional,
+ *   [S][S][3]) receives the resized-and-cropped 8-bit image.  workspace: >= sdeo_clip_image_preprocess_workspace_bytes(ih, iw, S) bytes
+ *   (src_rows * S * 3 are used).  Only launches: capturable.
+ *
+ * The handle has the text handle's life cycle: create (refuses, before any device call and each with its own message, image % patch
+ * != 0, a head dim sdeo_attention_f16 does not take, width / ffn / proj that are no multiples of 8), load_weight, finalize_weights,
+ * configure(batch 1..16, want_hidden), then per encode: fill every slot's patch rows -- sdeo_clip_vision_set_pixels (pixel_values fp32
+ * NCHW [batch][3][S][S], preprocessed elsewhere; fills all slots) or sdeo_clip_vision_set_image_u8 per slot (the op above into slot's
+ * rows) -- and sdeo_clip_vision_encode: image_embeds fp32 [batch][proj]; hidden (optional; needs want_hidden = 1) fp32 [batch][T][W],
+ * hidden_states[-2].  An encode whose slots were not all filled since the last encode is refused, as are a batch other than the
+ * configured one and a non-NULL hidden without want_hidden.  image_embeds has the same bits with want_hidden 0 and 1. */
+typedef struct sdeo_clip_vision_handle_s* sdeo_clip_vision_handle;
+typedef struct sdeo_clip_vision_config {
+  int image, patch, width, layers, heads, ffn, proj;
+} sdeo_clip_vision_config;
+size_t sdeo_clip_image_preprocess_workspace_bytes(int ih, int iw, int S);
+int sdeo_clip_image_preprocess_u8(void* patch_rows, uint8_t* crop_u8, const uint8_t* img_hwc, int ih, int iw, int S, int patch,
+                                  const int32_t* x_first, const int32_t* x_count, const int32_t* x_coeffs, int x_taps, const int32_t* y_first,
+                                  const int32_t* y_count, const int32_t* y_coeffs, int y_taps, int src_row0, int src_rows, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int sdeo_clip_vision_create(const sdeo_clip_vision_config* cfg, sdeo_clip_vision_handle* out);
+int sdeo_clip_vision_destroy(sdeo_clip_vision_handle h);
+int sdeo_clip_vision_num_weights(sdeo_clip_vision_handle h);
+int sdeo_clip_vision_weight_info(sdeo_clip_vision_handle h, int i, const char** name, int64_t dims[4], int* ndim);
+int sdeo_clip_vision_load_weight(sdeo_clip_vision_handle h, const char* name, const float* host_data, const int64_t* dims, int ndim, int strict);
+int sdeo_clip_vision_finalize_weights(sdeo_clip_vision_handle h);
+int sdeo_clip_vision_configure(sdeo_clip_vision_handle h, int batch, int want_hidden);
+int sdeo_clip_vision_set_pixels(sdeo_clip_vision_handle h, const float* pixel_values, int batch, void* stream);
+int sdeo_clip_vision_set_image_u8(sdeo_clip_vision_handle h, int slot, const uint8_t* img_hwc, int ih, int iw, const int32_t* x_first,
+                                  const int32_t* x_count, const int32_t* x_coeffs, int x_taps, const int32_t* y_first, const int32_t* y_count,
+                                  const int32_t* y_coeffs, int y_taps, int src_row0, int src_rows, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+int sdeo_clip_vision_encode(sdeo_clip_vision_handle h, int batch, float* image_embeds, float* hidden, void* stream);
+size_t sdeo_clip_vision_device_bytes(sdeo_clip_vision_handle h);
+
 /* ------------------------------------------------------------------ HED soft-edge annotator
  * annotator/hed/__init__.py (ControlNetHED_Apache2 + HEDdetector.__call__): x - norm, five VGG blocks of 3x3 convs + ReLU (2, 2, 3, 3,
  * 3 convs; 64, 128, 256, 512, 512 channels) with a 2x2 / stride-2 max-pool in front of blocks 2..5 and a 1x1 projection to one

@@ -42,6 +42,11 @@ class SdeoClipConfig(C.Structure):
                 ("ffn", C.c_int)]
 
 
+class SdeoClipVisionConfig(C.Structure):
+    _fields_ = [("image", C.c_int), ("patch", C.c_int), ("width", C.c_int), ("layers", C.c_int), ("heads", C.c_int), ("ffn", C.c_int),
+                ("proj", C.c_int)]
+
+
 class SdeoError(RuntimeError):
     pass
 

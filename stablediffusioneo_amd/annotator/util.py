@@ -106,6 +106,63 @@ def _area_axis(ssize: int, dsize: int):
     return np.asarray(start, dtype=np.int32), np.asarray(idx, dtype=np.int32), np.asarray(wgt, dtype=np.float32)
 
 
+def _pil_bicubic(x: float) -> float:
+    """`bicubic_filter` of PIL's Resample.c (a = -0.5)"""
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _pil_bicubic_axis(insize: int, outsize: int, lo: int = 0, n: int = None):
+    """PIL's `precompute_coeffs` + `normalize_coeffs_8bpc` for `Image.resize(..., BICUBIC)` along one axis, for the destination
+    indices lo .. lo + n - 1 (default: all): (first source index [n], tap count [n], int32 coefficients [n][taps] with 22 fractional
+    bits, zero past the count).  Weights are summed in index order in double, normalised, then rounded as int(+-0.5 + w * 2^22);
+    a pass is clip8((2^21 + sum pix * k) >> 22).  Bit-equal to PIL 12 on every size pair tried (tests/test_clip_vision_cpu.py)."""
+    n = outsize - lo if n is None else n
+    scale = filterscale = insize / outsize
+    if filterscale < 1.0:
+        filterscale = 1.0
+    support = 2.0 * filterscale
+    taps = int(np.ceil(support)) * 2 + 1
+    first, count, coef = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, taps), np.int32)
+    ss = 1.0 / filterscale
+    for i in range(n):
+        center = (lo + i + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), insize) - xmin
+        w = [_pil_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        first[i], count[i] = xmin, xmax
+        coef[i, :xmax] = [int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22)) for v in w]
+    return first, count, coef
+
+
+def clip_preprocess_size(ih: int, iw: int, size: int):
+    """(nh, nw, top, left) of CLIPImageProcessor: the shortest side resized to `size`, the long one to int(size * long / short), then
+    the centre crop size x size"""
+    nh, nw = (size, int(size * iw / ih)) if ih <= iw else (int(size * ih / iw), size)
+    return nh, nw, (nh - size) // 2, (nw - size) // 2
+
+
+def clip_preprocess_tables(ih: int, iw: int, size: int):
+    """The tables `sdeo_clip_image_preprocess_u8` takes for an ih x iw image (numpy, host): the resampler's coefficients for the `size`
+    columns and rows of the CROP only, and the source rows [src_row0, src_row0 + src_rows) those rows tap."""
+    nh, nw, top, left = clip_preprocess_size(ih, iw, size)
+    xf, xc, xk = _pil_bicubic_axis(iw, nw, left, size)
+    yf, yc, yk = _pil_bicubic_axis(ih, nh, top, size)
+    row0 = int(yf.min())
+    return {"x_first": xf, "x_count": xc, "x_coeffs": xk, "x_taps": int(xk.shape[1]), "y_first": yf, "y_count": yc, "y_coeffs": yk,
+            "y_taps": int(yk.shape[1]), "src_row0": row0, "src_rows": int((yf + yc).max()) - row0}
+
+
 # ---------------------------------------------------------------------------------------------- cv2.resize on the device
 def resize_u8(img, dst_h: int, dst_w: int, interpolation: str):
     """`cv2.resize(img, (dst_w, dst_h), interpolation)` for an HWC uint8 image; interpolation 'lanczos4' | 'area'.

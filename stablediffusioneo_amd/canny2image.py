@@ -43,7 +43,7 @@ def _default_canny():
 class hackathon():
 
     def initialize(self, weights="synthetic:0", config="sd15", apply_canny=None, text_encoder=None, vae_encoder=False, sampler="ddim",
-                   loras=(), ip_adapter=None):
+                   loras=(), ip_adapter=None, image_encoder=None):
         """text_encoder: None = `synthetic_text_encoder` (seeded stand-in contexts); "clip:<tokenizer dir>" = the
         FrozenCLIPEmbedder mirror on the HIP path (weights from the same source as the UNet's: synthetic seed or the
         checkpoint's `cond_stage_model.transformer.text_model.*`); bare "clip" is accepted only with synthetic weights (the
@@ -62,9 +62,36 @@ class hackathon():
         (`set_loras`); te_scale needs the "clip" / "openclip" text encoder.
         ip_adapter: an image-prompt adapter (IP-Adapter) on every UNet cross-attention: the path of an ip-adapter_sd15 .bin / .safetensors
         file, its dict, or "synthetic:<seed>[:T]" (seeded ip matrices and projection, T tokens, default 4).  `process(..., ip_image_embeds=)`
-        then takes the CLIP image embedding of the image prompt (there is no CLIP vision tower here: the caller computes it)."""
+        then takes the CLIP image embedding of the image prompt.
+        image_encoder (needs ip_adapter): the CLIP vision tower that computes that embedding from a picture, so that
+        `process(..., ip_image=HxWx3 uint8)` works -- a `CLIPVisionModelWithProjection` state dict, the path of IP-Adapter's
+        `image_encoder/model.safetensors`, or "synthetic:<seed>" (seeded weights).  ViT-H/14 (spec.CLIP_VISION_H14; the reduced tower with
+        the "tiny" configs); its projection width must equal the adapter's embed_dim.  Without it no vision handle is built."""
         self.apply_canny = apply_canny or _default_canny()
-        return self._init_model(weights, config, text_encoder, vae_encoder, sampler=sampler, loras=loras, ip_adapter=ip_adapter)
+        return self._init_model(weights, config, text_encoder, vae_encoder, sampler=sampler, loras=loras, ip_adapter=ip_adapter,
+                                image_encoder=image_encoder)
+
+    def _init_image_encoder(self, image_encoder, tiny):
+        """the CLIP vision tower of `initialize(image_encoder=)`; its projection must be as wide as the adapter's image embedding"""
+        from .ldm.modules.encoders.modules import FrozenCLIPImageEmbedder
+        embed_dim = self.model.ip_proj.embed_dim
+        # (the reduced tower is built as wide at its output as the adapter's projection takes, like the reduced OpenCLIP text tower)
+        cfg = dataclasses.replace(S.CLIP_VISION_TINY, proj=embed_dim) if tiny else S.CLIP_VISION_H14
+        synthetic = isinstance(image_encoder, str) and image_encoder.startswith("synthetic")
+        if not synthetic:
+            sd = FrozenCLIPImageEmbedder.read_state_dict(image_encoder)
+            proj = sd.get("visual_projection.weight")
+            if proj is not None and int(proj.shape[0]) != embed_dim:
+                raise ValueError(f"image_encoder: visual_projection gives embeddings of {int(proj.shape[0])}, the adapter's image projection "
+                                 f"takes embed_dim {embed_dim}")
+        if cfg.proj != embed_dim:
+            raise ValueError(f"image_encoder: the tower's proj is {cfg.proj}, the adapter's image projection takes embed_dim {embed_dim}")
+        enc = FrozenCLIPImageEmbedder(device=self.model.device, config=cfg)
+        if synthetic:
+            enc.transformer.load_synthetic(int(image_encoder.split(":")[1]) if ":" in image_encoder else 0)
+        else:
+            enc.load_state_dict(sd)
+        return enc
 
     def set_loras(self, loras=()):
         """Swap the adapters between `process` calls: back to the base weights, every adapter of `loras` merged on the device
@@ -81,11 +108,15 @@ class hackathon():
                 target.lora_commit()
         return unsupported
 
-    def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim", extra_control=(), loras=(), ip_adapter=None):
+    def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim", extra_control=(), loras=(), ip_adapter=None,
+                    image_encoder=None):
         """text encoder, ControlLDM and sampler of `initialize` (shared with hed2image).  extra_control: the weights of each extra
         control network (multi2image): a checkpoint path, a state dict with `control_model.*` names or "synthetic:<seed>"."""
         if sampler not in ("ddim", "dpmpp_2m", "dpmpp_2m_sde", "lcm"):
             raise ValueError(f'sampler {sampler!r}: "ddim", "dpmpp_2m", "dpmpp_2m_sde" or "lcm"')
+        if image_encoder is not None and ip_adapter is None:
+            raise ValueError("image_encoder needs an adapter to feed: initialize(..., ip_adapter=..., image_encoder=...)")
+        self.image_encoder = None
         if isinstance(text_encoder, str) and text_encoder.split(":")[0] in ("clip", "openclip"):
             from .ldm.modules.encoders.modules import FrozenCLIPEmbedder, FrozenOpenCLIPEmbedder
             kind = text_encoder.split(":")[0]
@@ -120,6 +151,8 @@ class hackathon():
             ip_file = IPA.synthetic_adapter(self.model.rt.ucfg, ip_tokens, ip_seed)
         if ip_file is not None:
             self.model.load_ip_adapter(ip_file)      # before the base weights: they finalise the handle
+        if image_encoder is not None:
+            self.image_encoder = self._init_image_encoder(image_encoder, isinstance(config, str) and config.startswith("tiny"))
         if text_encoder is None:      # the seeded stand-in, as wide as the chosen config's context
             text_encoder = functools.partial(synthetic_text_encoder, length=self.model.rt.ucfg.context_len, dim=self.model.rt.ucfg.context_dim)
             self.model.cond_stage_model = text_encoder
@@ -190,8 +223,11 @@ class hackathon():
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, ddim_steps, guess_mode,
                 strength, scale, seed, eta, low_threshold, high_threshold, x_T=None, init_image=None, denoise_strength=0.75, mask_image=None,
-                ip_image_embeds=None, ip_tokens=None, ip_scale=1.0):
-        """ip_image_embeds (1 or num_samples, embed_dim): the CLIP image embedding of an image prompt, projected by the adapter given to
+                ip_image_embeds=None, ip_tokens=None, ip_scale=1.0, ip_image=None):
+        """ip_image (HxWx3 uint8, any size): the image prompt as a picture, encoded by the tower given to `initialize(image_encoder=)`
+        (preprocessing and tower on the device) and then treated as its ip_image_embeds; exactly one of ip_image, ip_image_embeds and
+        ip_tokens.
+        ip_image_embeds (1 or num_samples, embed_dim): the CLIP image embedding of an image prompt, projected by the adapter given to
         `initialize(ip_adapter=)`; or ip_tokens (1 or num_samples, T, context_dim) from a projection run elsewhere; ip_scale weights the
         image term (0: the image prompt is off, the result is that of a pipeline without an adapter).  The unconditional half gets the
         projection of a zero embedding (zero tokens with ip_tokens), as in the adapter's own pipeline.
@@ -224,11 +260,12 @@ class hackathon():
                 control = control.permute(0, 3, 1, 2).contiguous()
             return self._sample(control, prompt, a_prompt, n_prompt, num_samples, H, W, ddim_steps, guess_mode, strength, scale, seed, eta,
                                 x_T=x_T, init_image=init_image, image_resolution=image_resolution, denoise_strength=denoise_strength,
-                                mask_image=mask_image, ip_image_embeds=ip_image_embeds, ip_tokens=ip_tokens, ip_scale=ip_scale)
+                                mask_image=mask_image, ip_image_embeds=ip_image_embeds, ip_tokens=ip_tokens, ip_scale=ip_scale,
+                                ip_image=ip_image)
 
     def _sample(self, control, prompt, a_prompt, n_prompt, num_samples, H, W, ddim_steps, guess_mode, strength, scale, seed, eta, x_T=None,
                 init_image=None, image_resolution=None, denoise_strength=0.75, mask_image=None, ip_image_embeds=None, ip_tokens=None,
-                ip_scale=1.0):
+                ip_scale=1.0, ip_image=None):
         """everything of `process` after the hint (`canny2image_torch.py:40-71`): seeding, conditioning, the DDIM loop and the decode
         to uint8 HWC images; control is the (num_samples, 3, H, W) fp32 hint on the device -- or, with several control networks, the list
         of their hints, and strength one float per net"""
@@ -238,7 +275,7 @@ class hackathon():
             random.seed(seed)
             np.random.seed(seed)
             torch.manual_seed(seed)       # pytorch_lightning.seed_everything (`canny2image_torch.py:42`)
-            self._set_image_prompt(ip_image_embeds, ip_tokens, ip_scale)
+            self._set_image_prompt(ip_image_embeds, ip_tokens, ip_scale, ip_image)
             control = list(control) if isinstance(control, (list, tuple)) else [control]
             cond = {"c_concat": control,
                     "c_crossattn": [self.model.get_learned_conditioning([prompt + ", " + a_prompt] * num_samples)]}
@@ -262,24 +299,31 @@ class hackathon():
             results = [x_samples[i] for i in range(num_samples)]
         return results
 
-    def set_image_prompt(self, ip_image_embeds=None, ip_tokens=None, ip_scale=1.0):
+    def set_image_prompt(self, ip_image_embeds=None, ip_tokens=None, ip_scale=1.0, ip_image=None):
         """The image prompt of the following `process` calls that give none themselves (scribble2image.process keeps the upstream
-        signature and takes it this way); arguments as `process(..., ip_image_embeds=, ip_tokens=, ip_scale=)`."""
-        self._image_prompt = (ip_image_embeds, ip_tokens, ip_scale)
+        signature and takes it this way); arguments as `process(..., ip_image_embeds=, ip_tokens=, ip_scale=, ip_image=)`."""
+        self._image_prompt = (ip_image_embeds, ip_tokens, ip_scale, ip_image)
         return self
 
-    def _set_image_prompt(self, ip_image_embeds, ip_tokens, ip_scale):
+    def _set_image_prompt(self, ip_image_embeds, ip_tokens, ip_scale, ip_image=None):
         """the image prompt of this request on the model; a pipeline with an adapter needs one with every request"""
         m = self.model
-        if ip_image_embeds is None and ip_tokens is None and getattr(self, "_image_prompt", None) is not None:
-            ip_image_embeds, ip_tokens, ip_scale = self._image_prompt
+        if ip_image_embeds is None and ip_tokens is None and ip_image is None and getattr(self, "_image_prompt", None) is not None:
+            ip_image_embeds, ip_tokens, ip_scale, ip_image = self._image_prompt
         if not m.rt.ip_adapter_tokens:
-            if ip_image_embeds is not None or ip_tokens is not None:
+            if ip_image_embeds is not None or ip_tokens is not None or ip_image is not None:
                 raise ValueError("ip_image_embeds / ip_tokens need an adapter: initialize(..., ip_adapter=...)")
             return
+        if ip_image is not None:
+            if ip_image_embeds is not None or ip_tokens is not None:
+                raise ValueError("this pipeline has an image-prompt adapter: give exactly one of ip_image, ip_image_embeds and ip_tokens")
+            if getattr(self, "image_encoder", None) is None:
+                raise ValueError("ip_image needs the CLIP vision tower: initialize(..., ip_adapter=..., image_encoder=...) "
+                                 "(or encode the picture elsewhere and pass ip_image_embeds)")
+            ip_image_embeds = self.image_encoder(ip_image)
         if (ip_image_embeds is None) == (ip_tokens is None):
-            raise ValueError("this pipeline has an image-prompt adapter: give exactly one of ip_image_embeds and ip_tokens, to process or "
-                             "to set_image_prompt (ip_scale=0 switches the image prompt off)")
+            raise ValueError("this pipeline has an image-prompt adapter: give exactly one of ip_image_embeds and ip_tokens (or ip_image, with "
+                             "initialize(..., image_encoder=)), to process or to set_image_prompt (ip_scale=0 switches the image prompt off)")
         if ip_tokens is not None:
             m.set_ip_tokens(ip_tokens)
         else:

@@ -23,7 +23,7 @@ from .annotator.util import HWC3, resize_image, target_size
 class hackathon(hed2image.hackathon):
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, detect_resolution, ddim_steps, guess_mode,
-                strength, scale, seed, eta, x_T=None, ip_image_embeds=None, ip_tokens=None, ip_scale=1.0):
+                strength, scale, seed, eta, x_T=None, ip_image_embeds=None, ip_tokens=None, ip_scale=1.0, ip_image=None):
         H0, W0 = input_image.shape[:2]
         det_hw, img_hw = target_size(H0, W0, detect_resolution), target_size(H0, W0, image_resolution)
         if det_hw != img_hw:
@@ -43,4 +43,4 @@ class hackathon(hed2image.hackathon):
                 control = ops.fake_scribble(edges.to(device), scribble=False, control=True)[1]
             control = torch.stack([control for _ in range(num_samples)], dim=0).contiguous()
             return self._sample(control, prompt, a_prompt, n_prompt, num_samples, H, W, ddim_steps, guess_mode, strength, scale, seed, eta,
-                                x_T=x_T, ip_image_embeds=ip_image_embeds, ip_tokens=ip_tokens, ip_scale=ip_scale)
+                                x_T=x_T, ip_image_embeds=ip_image_embeds, ip_tokens=ip_tokens, ip_scale=ip_scale, ip_image=ip_image)

@@ -26,15 +26,15 @@ def _default_hed(weights):
 class hackathon(canny2image.hackathon):
 
     def initialize(self, weights="synthetic:0", hed_weights="synthetic:0", apply_hed=None, text_encoder=None, config="sd15",
-                   sampler="ddim", loras=(), ip_adapter=None):
-        """weights / text_encoder / config / sampler: as canny2image.hackathon.initialize (a soft-edge ControlNet checkpoint has the same keys).
+                   sampler="ddim", loras=(), ip_adapter=None, image_encoder=None):
+        """weights / text_encoder / config / sampler / ip_adapter / image_encoder: as canny2image.hackathon.initialize (a soft-edge ControlNet checkpoint has the same keys).
         hed_weights: the HED network's (ControlNetHED.pth path, state dict or "synthetic:<seed>"); apply_hed: any callable
         (HxWx3 uint8) -> HxW uint8 instead of the HIP HEDdetector."""
         self.apply_hed = apply_hed or _default_hed(hed_weights)
-        return self._init_model(weights, config, text_encoder, sampler=sampler, loras=loras, ip_adapter=ip_adapter)
+        return self._init_model(weights, config, text_encoder, sampler=sampler, loras=loras, ip_adapter=ip_adapter, image_encoder=image_encoder)
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, detect_resolution, ddim_steps, guess_mode,
-                strength, scale, seed, eta, x_T=None, ip_image_embeds=None, ip_tokens=None, ip_scale=1.0):
+                strength, scale, seed, eta, x_T=None, ip_image_embeds=None, ip_tokens=None, ip_scale=1.0, ip_image=None):
         H0, W0 = input_image.shape[:2]
         det_hw, img_hw = target_size(H0, W0, detect_resolution), target_size(H0, W0, image_resolution)
         if det_hw != img_hw:
@@ -55,4 +55,4 @@ class hackathon(canny2image.hackathon):
                 control = torch.stack([control for _ in range(num_samples)], dim=0)
                 control = control.permute(0, 3, 1, 2).contiguous()
             return self._sample(control, prompt, a_prompt, n_prompt, num_samples, H, W, ddim_steps, guess_mode, strength, scale, seed, eta,
-                                x_T=x_T, ip_image_embeds=ip_image_embeds, ip_tokens=ip_tokens, ip_scale=ip_scale)
+                                x_T=x_T, ip_image_embeds=ip_image_embeds, ip_tokens=ip_tokens, ip_scale=ip_scale, ip_image=ip_image)

@@ -171,3 +171,45 @@ class FrozenOpenCLIPEmbedder(AbstractEncoder):
 
     def encode(self, text):
         return self(text)
+
+
+class FrozenCLIPImageEmbedder(AbstractEncoder):
+    """The CLIP image encoder of an image prompt (IP-Adapter's `image_encoder`: HuggingFace `CLIPVisionModelWithProjection`, OpenCLIP
+    ViT-H/14) on the HIP path: `forward(images)` takes one (H, W, 3) uint8 RGB picture or a list of them, of any sizes, and returns
+    `image_embeds` [B, proj] fp32 on the device.  `CLIPImageProcessor` (PIL bicubic resize, centre crop, normalisation) and the tower
+    both run through libsdeo.so (`ClipVisionRuntime`).  `version` names a hub model in upstream code and is ignored here: the weights
+    come from `load_state_dict` (a state dict, or the path of a local `model.safetensors`); there is no network access."""
+
+    def __init__(self, version: Optional[str] = None, device="cuda", freeze=True, config: S.ClipVisionConfig = S.CLIP_VISION_H14,
+                 runtime=None, want_hidden: bool = False):
+        from ....runtime import ClipVisionRuntime
+        self.device = device
+        self.config = config
+        self.transformer = runtime if runtime is not None else ClipVisionRuntime(config, device if device != "cuda" else None, want_hidden=want_hidden)
+
+    def freeze(self):
+        return self
+
+    @staticmethod
+    def read_state_dict(sd):
+        """`sd` itself when it is a dict, else the tensors of the file at that path (.safetensors or a torch checkpoint)"""
+        if isinstance(sd, dict):
+            return sd
+        from ....cldm.model import load_state_dict
+        return load_state_dict(os.fspath(sd))
+
+    def load_state_dict(self, sd, strict=False):
+        """a `CLIPVisionModelWithProjection` state dict (`vision_model.*`, `visual_projection.weight`) or the path of IP-Adapter's
+        `image_encoder/model.safetensors`"""
+        self.transformer.load_state_dict(self.read_state_dict(sd), strict=strict)
+        return self
+
+    def forward(self, images):
+        if not isinstance(images, (list, tuple)):
+            images = [images]
+        return self.transformer.encode_images(list(images))
+
+    __call__ = forward
+
+    def encode(self, images):
+        return self(images)

@@ -25,11 +25,11 @@ DEVICE_CONTROLS = ("canny", "hed", "scribble", "fake_scribble")
 class hackathon(canny2image.hackathon):
 
     def initialize(self, weights="synthetic:0", controls=("canny", "hed"), control_weights=(None, "synthetic:1"), hed_weights="synthetic:0",
-                   text_encoder=None, config="sd15", sampler="ddim", loras=(), ip_adapter=None):
+                   text_encoder=None, config="sd15", sampler="ddim", loras=(), ip_adapter=None, image_encoder=None):
         """controls: one entry per control network, "canny", "hed", "scribble", "fake_scribble" (the device hint producers of the
         single-net pipelines) or a callable (HxWx3 uint8) -> HxW uint8.  control_weights: one entry per network; entry 0 must be
         None (net 0 comes with `weights`), the others are a checkpoint path, a state dict or "synthetic:<seed>".
-        weights / text_encoder / config / sampler: as canny2image.hackathon.initialize; hed_weights: as hed2image's."""
+        weights / text_encoder / config / sampler / ip_adapter / image_encoder: as canny2image.hackathon.initialize; hed_weights: as hed2image's."""
         controls = tuple(controls)
         control_weights = tuple(control_weights)
         if not 1 <= len(controls) <= 4:
@@ -49,7 +49,8 @@ class hackathon(canny2image.hackathon):
         if "hed" in controls or "fake_scribble" in controls:
             from .hed2image import _default_hed
             self.apply_hed = _default_hed(hed_weights)
-        return self._init_model(weights, config, text_encoder, sampler=sampler, extra_control=control_weights[1:], loras=loras, ip_adapter=ip_adapter)
+        return self._init_model(weights, config, text_encoder, sampler=sampler, extra_control=control_weights[1:], loras=loras, ip_adapter=ip_adapter,
+                                image_encoder=image_encoder)
 
     def _hint(self, kind, img, low_threshold, high_threshold):
         """(3, H, W) fp32 hint in [0, 1] on the device, from the resized HxWx3 uint8 image"""
@@ -66,7 +67,7 @@ class hackathon(canny2image.hackathon):
         return (torch.from_numpy(detected.copy()).float().to(device) / 255.0).permute(2, 0, 1).contiguous()
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, ddim_steps, guess_mode, strengths, scale,
-                seed, eta, low_threshold, high_threshold, x_T=None, ip_image_embeds=None, ip_tokens=None, ip_scale=1.0, control_images=None):
+                seed, eta, low_threshold, high_threshold, x_T=None, ip_image_embeds=None, ip_tokens=None, ip_scale=1.0, control_images=None, ip_image=None):
         """strengths: one float per control network.  control_images: one source image per network (None entries and the default: the
         input image); each must resize to the input image's H x W."""
         k = len(self.controls)
@@ -88,4 +89,4 @@ class hackathon(canny2image.hackathon):
                 hint = self._hint(kind, src_img, low_threshold, high_threshold)
                 control.append(torch.stack([hint for _ in range(num_samples)], dim=0).contiguous())
             return self._sample(control, prompt, a_prompt, n_prompt, num_samples, H, W, ddim_steps, guess_mode, strengths, scale, seed, eta,
-                                x_T=x_T, ip_image_embeds=ip_image_embeds, ip_tokens=ip_tokens, ip_scale=ip_scale)
+                                x_T=x_T, ip_image_embeds=ip_image_embeds, ip_tokens=ip_tokens, ip_scale=ip_scale, ip_image=ip_image)

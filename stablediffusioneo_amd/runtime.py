@@ -666,6 +666,130 @@ class ClipRuntime(_HandleRuntime):
         return out
 
 
+class ClipVisionRuntime(_HandleRuntime):
+    """CLIP vision tower with projection on the HIP path (csrc/clip_vision.hip; HuggingFace `CLIPVisionModelWithProjection`):
+    create -> load_state_dict -> configure(batch) -> encode_images(pictures) / encode_pixels(pixel_values).  The preprocessing
+    (`CLIPImageProcessor`: PIL bicubic resize, centre crop, normalise) runs on the device too (`preprocess`)."""
+
+    _prefix = "sdeo_clip_vision_"
+    _ndims = 4
+
+    def __init__(self, cfg: S.ClipVisionConfig = S.CLIP_VISION_H14, device: Optional[torch.device] = None, want_hidden: bool = False):
+        """want_hidden: the encodes also return hidden_states[-2] (batch, tokens, width), the input of a Resampler projection"""
+        super().__init__(device)
+        self.cfg = cfg
+        self._cfg = _lib.SdeoClipVisionConfig(cfg.image, cfg.patch, cfg.width, cfg.layers, cfg.heads, cfg.ffn, cfg.proj)
+        check(self.lib.sdeo_clip_vision_create(C.byref(self._cfg), C.byref(self.handle)), "sdeo_clip_vision_create")
+        self.want_hidden = bool(want_hidden)
+        self.batch = 0
+        self.generation = 0
+        self._work = None            # the preprocess workspace, grown on demand
+
+    @property
+    def kp(self) -> int:
+        """columns of a patch row: 3 patch^2 rounded up to a multiple of 8"""
+        return (3 * self.cfg.patch ** 2 + 7) // 8 * 8
+
+    def load_weight(self, name: str, t: torch.Tensor, strict: bool = True):
+        self.load_tensor(name, t, strict)
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False):
+        """HuggingFace keys of `CLIPVisionModelWithProjection` (`vision_model.*`, `visual_projection.weight`; bare names below
+        `vision_model.` are accepted); anything else (`position_ids`, a text tower) is ignored unless strict."""
+        for k, v in sd.items():
+            if not torch.is_floating_point(v):
+                continue
+            self.load_tensor(k, v, strict)
+        self._finalize()
+        return self
+
+    def load_synthetic(self, seed: int = 0):
+        return self.load_state_dict(S.synth_clip_vision_state_dict(self.cfg, seed), strict=True)
+
+    def configure(self, batch: int):
+        if batch != self.batch:
+            self.generation += 1
+            self.batch = 0
+            check(self.lib.sdeo_clip_vision_configure(self.handle, int(batch), int(self.want_hidden)), "sdeo_clip_vision_configure")
+            self.batch = batch
+        return self
+
+    # ---------------------------------------------------------------- preprocessing
+    def _image(self, image) -> torch.Tensor:
+        t = torch.from_numpy(image) if not torch.is_tensor(image) else image
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"an image prompt is a uint8 (H, W, 3) RGB image, got {tuple(t.shape)} {t.dtype}")
+        return t.to(self.device).contiguous()
+
+    def _tables(self, ih: int, iw: int):
+        """(device int32 tensor holding all six tables, the op's table arguments in order) for an ih x iw image"""
+        from .annotator.util import clip_preprocess_tables
+        import numpy as np
+        tb = clip_preprocess_tables(ih, iw, self.cfg.image)
+        parts = [tb[k].reshape(-1) for k in ("x_first", "x_count", "x_coeffs", "y_first", "y_count", "y_coeffs")]
+        dev = torch.from_numpy(np.concatenate(parts).astype(np.int32)).to(self.device)
+        offs = [0]
+        for p in parts:
+            offs.append(offs[-1] + p.size)
+        at = lambda i: C.c_void_p(dev.data_ptr() + 4 * offs[i])
+        need = int(self.lib.sdeo_clip_image_preprocess_workspace_bytes(ih, iw, self.cfg.image))
+        if self._work is None or self._work.numel() < need:
+            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        args = (at(0), at(1), at(2), tb["x_taps"], at(3), at(4), at(5), tb["y_taps"], tb["src_row0"], tb["src_rows"], ptr(self._work),
+                C.c_size_t(self._work.numel()), cur_stream())
+        return dev, args
+
+    def preprocess(self, image, want_crop: bool = False):
+        """`sdeo_clip_image_preprocess_u8` on one (H, W, 3) uint8 image (host array or tensor): the fp16 patch rows (patches, Kp), and
+        with want_crop the resized-and-cropped uint8 image (S, S, 3), on the device."""
+        img = self._image(image)
+        c = self.cfg
+        rows = torch.empty(((c.image // c.patch) ** 2, self.kp), dtype=torch.float16, device=self.device)
+        crop = torch.empty((c.image, c.image, 3), dtype=torch.uint8, device=self.device) if want_crop else None
+        keep, args = self._tables(int(img.shape[0]), int(img.shape[1]))
+        check(self.lib.sdeo_clip_image_preprocess_u8(ptr(rows), ptr(crop), ptr(img), int(img.shape[0]), int(img.shape[1]), c.image, c.patch, *args),
+              "sdeo_clip_image_preprocess_u8")
+        return (rows, crop) if want_crop else rows
+
+    def unpatchify(self, rows: torch.Tensor) -> torch.Tensor:
+        """patch rows (patches, Kp) -> pixel values (3, S, S), the pad columns dropped (column (py * p + px) * 3 + c)"""
+        c = self.cfg
+        g, p = c.image // c.patch, c.patch
+        return rows[:, :3 * p * p].reshape(g, g, p, p, 3).permute(4, 0, 2, 1, 3).reshape(3, c.image, c.image)
+
+    # ---------------------------------------------------------------- encodes
+    def _encode(self):
+        c = self.cfg
+        out = torch.empty((self.batch, c.proj), dtype=torch.float32, device=self.device)
+        hid = torch.empty((self.batch, c.tokens, c.width), dtype=torch.float32, device=self.device) if self.want_hidden else None
+        check(self.lib.sdeo_clip_vision_encode(self.handle, self.batch, ptr(out), ptr(hid), cur_stream()), "sdeo_clip_vision_encode")
+        return (out, hid) if self.want_hidden else out
+
+    def encode_pixels(self, pixel_values: torch.Tensor):
+        """pixel_values (batch, 3, S, S) as `CLIPImageProcessor` returns them -> image_embeds (batch, proj) fp32 on the device, or
+        (image_embeds, hidden_states[-2]) with want_hidden"""
+        s = self.cfg.image
+        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, s, s):
+            raise ValueError(f"pixel_values must be (batch, 3, {s}, {s}), got {tuple(pixel_values.shape)}")
+        self.configure(int(pixel_values.shape[0]))
+        pix = pixel_values.to(device=self.device, dtype=torch.float32).contiguous()
+        check(self.lib.sdeo_clip_vision_set_pixels(self.handle, ptr(pix), self.batch, cur_stream()), "sdeo_clip_vision_set_pixels")
+        return self._encode()
+
+    def encode_images(self, images):
+        """images: a list of (H, W, 3) uint8 RGB pictures of any sizes (host arrays or tensors) -> as `encode_pixels`; resize, crop,
+        normalisation and patchify run on the device, one picture per slot"""
+        images = [self._image(im) for im in images]
+        if not images:
+            raise ValueError("encode_images: no image")
+        self.configure(len(images))
+        for slot, img in enumerate(images):
+            keep, args = self._tables(int(img.shape[0]), int(img.shape[1]))
+            check(self.lib.sdeo_clip_vision_set_image_u8(self.handle, slot, ptr(img), int(img.shape[0]), int(img.shape[1]), *args),
+                  "sdeo_clip_vision_set_image_u8")
+        return self._encode()
+
+
 class HedRuntime(_HandleRuntime):
     """HED soft-edge annotator on the HIP path (`annotator/hed/__init__.py`: ControlNetHED_Apache2 + HEDdetector.__call__):
     create -> load_state_dict -> configure(H, W) -> detect(image).  One image per call; csrc/hed.hip."""

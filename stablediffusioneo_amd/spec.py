@@ -449,6 +449,72 @@ def param_spec_clip(cfg: ClipConfig = CLIP_SD15) -> "OrderedDict[str, tuple]":
     return spec
 
 
+@dataclass(frozen=True)
+class ClipVisionConfig:
+    """CLIP vision tower with projection (HuggingFace `CLIPVisionModelWithProjection`); the defaults are OpenCLIP ViT-H/14, the image
+    encoder the ip-adapter_sd15 files are trained against (`image_encoder/config.json` of that repository)."""
+    image: int = 224
+    patch: int = 14
+    width: int = 1280
+    layers: int = 32
+    heads: int = 16
+    ffn: int = 5120
+    proj: int = 1024
+
+    @property
+    def tokens(self) -> int:
+        return (self.image // self.patch) ** 2 + 1
+
+
+CLIP_VISION_H14 = ClipVisionConfig()
+# everything inside one tile: T = 17
+CLIP_VISION_TINY = ClipVisionConfig(image=56, patch=14, width=64, layers=3, heads=4, ffn=128, proj=48)
+# the real T = 257, P = 256, Kp = 592 and d = 80 at toy widths: the ragged key tile, the K tail, the strided class-row LayerNorm
+CLIP_VISION_TINY80 = ClipVisionConfig(image=224, patch=14, width=160, layers=2, heads=2, ffn=320, proj=64)
+NS_CLIP_VISION = "image_encoder.vision_model."      # seed namespace of the synthetic draw
+
+
+def param_spec_clip_vision(cfg: ClipVisionConfig = CLIP_VISION_H14) -> "OrderedDict[str, tuple]":
+    """Tensor names below `vision_model.` (plus `visual_projection.weight`) and shapes of the HuggingFace
+    CLIPVisionModelWithProjection state dict, in the order `sdeo_clip_vision_weight_info` lists them."""
+    w, f = cfg.width, cfg.ffn
+    spec = OrderedDict()
+    spec["embeddings.class_embedding"] = (w,)
+    spec["embeddings.patch_embedding.weight"] = (w, 3, cfg.patch, cfg.patch)
+    spec["embeddings.position_embedding.weight"] = (cfg.tokens, w)
+    spec["pre_layrnorm.weight"] = (w,)
+    spec["pre_layrnorm.bias"] = (w,)
+    for i in range(cfg.layers):
+        p = f"encoder.layers.{i}."
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            spec[p + f"self_attn.{n}.weight"] = (w, w)
+            spec[p + f"self_attn.{n}.bias"] = (w,)
+        spec[p + "layer_norm1.weight"] = (w,)
+        spec[p + "layer_norm1.bias"] = (w,)
+        spec[p + "mlp.fc1.weight"] = (f, w)
+        spec[p + "mlp.fc1.bias"] = (f,)
+        spec[p + "mlp.fc2.weight"] = (w, f)
+        spec[p + "mlp.fc2.bias"] = (w,)
+        spec[p + "layer_norm2.weight"] = (w,)
+        spec[p + "layer_norm2.bias"] = (w,)
+    spec["post_layernorm.weight"] = (w,)
+    spec["post_layernorm.bias"] = (w,)
+    spec["visual_projection.weight"] = (cfg.proj, w)
+    return spec
+
+
+def synth_clip_vision_state_dict(cfg: ClipVisionConfig = CLIP_VISION_H14, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Seeded vision-tower weights (fp32, CPU) under the names of `param_spec_clip_vision`, as `ClipVisionRuntime.load_synthetic` draws
+    them; pre_layrnorm / post_layernorm scales are drawn around 1 like every other norm."""
+    out = OrderedDict()
+    for k, shp in param_spec_clip_vision(cfg).items():
+        t = synth_tensor(NS_CLIP_VISION + k, shp, seed)
+        if k in ("pre_layrnorm.weight", "post_layernorm.weight"):
+            t = 1.0 + 5.0 * t          # (synth_tensor knows "layer_norm" only: 0.02 N -> 1 + 0.1 N)
+        out[k] = t
+    return out
+
+
 def synth_tensor(name: str, shape, seed: int = 0) -> torch.Tensor:
     """Deterministic stand-in for one checkpoint tensor (fp32, CPU).
 

@@ -13,6 +13,7 @@
 #         attn_counters     SQ counter passes on the T = 4096, d = 40 self-attention (tools/one_attn.py) -> attn_counters.json
 #         step_counters     whole-step counter passes, eager + one stream (tools/step_counters.py) -> step_counters.json
 #         pmc_graph_only / pmc_overlap_only   one --pmc pass of a 2-step sampler run with ONLY graph replay / ONLY the side stream on
+#         clip_vision_time  image-prompt timing: preprocess, ViT-H/14 encode, torch fp16 yardstick -> profiles/clip_vision_time.json
 #         py:<script>[,args] python <script> args                          -> py_<n>.log
 R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${1:-r3}
@@ -82,6 +83,7 @@ for st in "$@"; do
     pmc_overlap_only) step pmc_overlap_only s_pmc_mode overlap_only ;;
     pmc_both) step pmc_both s_pmc_mode both ;;
     benchx:*) a=${st#benchx:}; nm=$(echo $a | tr -d ',-' | cut -c1-30); step "$st" bash -c "timeout -k 10 500 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-roofline $(echo $a | tr ',' ' ') > $OUT/benchx_$nm.json 2> $OUT/benchx_$nm.err; rc=\$?; head -c 900 $OUT/benchx_$nm.json; echo; exit \$rc" ;;
+    clip_vision_time) step "$st" bash -c "timeout -k 10 600 python tools/clip_vision_time.py --json $OUT/clip_vision_time.json > $OUT/clip_vision_time.log 2>&1; rc=\$?; tail -8 $OUT/clip_vision_time.log; exit \$rc" ;;
     py:*) a=${st#py:}; step "$st" bash -c "timeout -k 10 600 python $(echo $a | tr ',' ' ') > $OUT/py_$N.log 2>&1; rc=\$?; tail -25 $OUT/py_$N.log; exit \$rc" ;;
     *) echo "unknown step $st" ;;
   esac
