@@ -643,6 +643,54 @@ int sdeo_clip_vision_set_image_u8(sdeo_clip_vision_handle h, int slot, const uin
 int sdeo_clip_vision_encode(sdeo_clip_vision_handle h, int batch, float* image_embeds, float* hidden, void* stream);
 size_t sdeo_clip_vision_device_bytes(sdeo_clip_vision_handle h);
 
+/* ------------------------------------------------------------------ IP-Adapter Plus image projection (the Resampler; csrc/resampler.hip)
+ * hidden_states[-2] of the vision tower (what sdeo_clip_vision_encode writes as `hidden`) -> the num_queries image tokens
+ * sdeo_set_ip_tokens reads, without touching the host.  The definition below is this library's statement of the published module; it is
+ * UNPINNED to upstream code (neither the adapter's source nor a "plus" file was at hand).  ip-adapter-plus_sd15: tokens T 257, embed_dim
+ * E 1280, dim D 768, depth 4, dim_head d 64, heads H 12 (inner = H d = 768), num_queries Q 16, ffn F 3072, out_dim O 768.
+ *   x   = proj_in(hidden)                                  Linear E -> D with bias
+ *   lat = latents, repeated per image                      parameter [1][Q][D]
+ *   per layer l:  xn = norm1(x), ln = norm2(lat)           LayerNorm, eps 1e-5, affine
+ *                 q = to_q(ln);  k | v = to_kv(cat(xn, ln) over the token axis)          no biases; T + Q keys
+ *                 per head: w = softmax((q s)(k s)^T) in fp32, s = d^-1/4 (== scale d^-1/2), ONE softmax over all T + Q keys; o = w v
+ *                 lat = to_out(o) + lat;  lat = W2 gelu_erf(W1 norm_ff(lat)) + lat       no biases
+ *   tokens = norm_out(proj_out(lat))                       Linear D -> O with bias, LayerNorm(O)
+ * Tensor names are the adapter file's keys below "image_proj." (anything up to and including "image_proj." is stripped): latents
+ * [1][Q][D], proj_in.{weight,bias}, proj_out.{weight,bias}, norm_out.{weight,bias}, and per layer layers.<l>.0.{norm1,norm2}.{weight,bias},
+ * layers.<l>.0.to_q.weight [inner][D], .to_kv.weight [2 inner][D], .to_out.weight [D][inner], layers.<l>.1.0.{weight,bias} (norm_ff),
+ * layers.<l>.1.1.weight [F][D] (W1), layers.<l>.1.3.weight [D][F] (W2).  The latent stream is fp16 like both towers'; proj_out and
+ * norm_out run in fp32.
+ *
+ * Life cycle of the other handles: create, load_weight, finalize_weights, configure(batch 1..16), project.  create refuses, before any
+ * device call and each with its own message: widths that are no multiples of 8, dim or out_dim above 2048, heads * dim_head that is
+ * no inner width the matrices can have, a head dim sdeo_attention_f16 does not take, num_queries outside 1..64.  project refuses an
+ * unfinalised or unconfigured handle and a batch other than the configured one; hidden fp32 device [batch][tokens][embed_dim], tokens_out
+ * fp32 device [batch][num_queries][out_dim], both 16-byte aligned.  It only launches: no allocation, no synchronisation, capturable.
+ * sdeo_resampler_num_launches: the ops of the configured program, 5 + 8 depth (one kernel each; two for a GEMM whose plan splits K).
+ *
+ * Its two normalisation kernels as ops:
+ * sdeo_layernorm_pair_f16: ONE launch normalises the b*t rows of x [b][t][c] with (gamma1, beta1) into rows 0..t-1 of kv_in[b][t + q][c]
+ *   and the b*q rows of lat [b][q][c] with (gamma2, beta2) into rows t.. of kv_in and, the same bits, into the dense q_in [b * q][c].
+ *   fp16 rows, fp32 gamma / beta, c a multiple of 8 up to 2048, operands 16-byte aligned.
+ * sdeo_layernorm_f32: LayerNorm over the last dim of fp32 [rows][c], fp32 out (c a multiple of 4 up to 2048). */
+int sdeo_layernorm_pair_f16(void* kv_in, void* q_in, const void* x, const void* lat, const float* gamma1, const float* beta1, const float* gamma2,
+                            const float* beta2, int b, int t, int q, int c, float eps, void* stream);
+int sdeo_layernorm_f32(float* y, const float* x, const float* gamma, const float* beta, int rows, int c, float eps, void* stream);
+typedef struct sdeo_resampler_handle_s* sdeo_resampler_handle;
+typedef struct sdeo_resampler_config {
+  int tokens, embed_dim, dim, depth, dim_head, heads, num_queries, ffn, out_dim;
+} sdeo_resampler_config;
+int sdeo_resampler_create(const sdeo_resampler_config* cfg, sdeo_resampler_handle* out);
+int sdeo_resampler_destroy(sdeo_resampler_handle h);
+int sdeo_resampler_num_weights(sdeo_resampler_handle h);
+int sdeo_resampler_weight_info(sdeo_resampler_handle h, int i, const char** name, int64_t dims[4], int* ndim);
+int sdeo_resampler_load_weight(sdeo_resampler_handle h, const char* name, const float* host_data, const int64_t* dims, int ndim, int strict);
+int sdeo_resampler_finalize_weights(sdeo_resampler_handle h);
+int sdeo_resampler_configure(sdeo_resampler_handle h, int batch);
+int sdeo_resampler_num_launches(sdeo_resampler_handle h);
+int sdeo_resampler_project(sdeo_resampler_handle h, const float* hidden, int batch, float* tokens_out, void* stream);
+size_t sdeo_resampler_device_bytes(sdeo_resampler_handle h);
+
 /* ------------------------------------------------------------------ HED soft-edge annotator
  * annotator/hed/__init__.py (ControlNetHED_Apache2 + HEDdetector.__call__): x - norm, five VGG blocks of 3x3 convs + ReLU (2, 2, 3, 3,
  * 3 convs; 64, 128, 256, 512, 512 channels) with a 2x2 / stride-2 max-pool in front of blocks 2..5 and a 1x1 projection to one

@@ -47,6 +47,11 @@ class SdeoClipVisionConfig(C.Structure):
                 ("proj", C.c_int)]
 
 
+class SdeoResamplerConfig(C.Structure):
+    _fields_ = [("tokens", C.c_int), ("embed_dim", C.c_int), ("dim", C.c_int), ("depth", C.c_int), ("dim_head", C.c_int), ("heads", C.c_int),
+                ("num_queries", C.c_int), ("ffn", C.c_int), ("out_dim", C.c_int)]
+
+
 class SdeoError(RuntimeError):
     pass
 

@@ -66,7 +66,12 @@ class hackathon():
         image_encoder (needs ip_adapter): the CLIP vision tower that computes that embedding from a picture, so that
         `process(..., ip_image=HxWx3 uint8)` works -- a `CLIPVisionModelWithProjection` state dict, the path of IP-Adapter's
         `image_encoder/model.safetensors`, or "synthetic:<seed>" (seeded weights).  ViT-H/14 (spec.CLIP_VISION_H14; the reduced tower with
-        the "tiny" configs); its projection width must equal the adapter's embed_dim.  Without it no vision handle is built."""
+        the "tiny" configs); its projection width must equal the adapter's embed_dim.  Without it no vision handle is built.
+        A "plus" adapter (ip-adapter-plus_sd15 / -plus-face_sd15, its dict, or "synthetic-plus:<seed>[:Q]"; Q image tokens, from `latents`)
+        projects with the Resampler on the HIP path: the tower is then configured to keep hidden_states[-2], its WIDTH must equal the
+        Resampler's proj_in input width, `process(..., ip_image=)` gives Resampler(hidden states of the picture) to the conditional half
+        and Resampler(hidden states of an all-zero pixel_values) to the unconditional one (computed once per pipeline).  Without
+        image_encoder a plus pipeline takes ip_tokens only."""
         self.apply_canny = apply_canny or _default_canny()
         return self._init_model(weights, config, text_encoder, vae_encoder, sampler=sampler, loras=loras, ip_adapter=ip_adapter,
                                 image_encoder=image_encoder)
@@ -74,7 +79,28 @@ class hackathon():
     def _init_image_encoder(self, image_encoder, tiny):
         """the CLIP vision tower of `initialize(image_encoder=)`; its projection must be as wide as the adapter's image embedding"""
         from .ldm.modules.encoders.modules import FrozenCLIPImageEmbedder
+        from .ip_adapter import Resampler
         embed_dim = self.model.ip_proj.embed_dim
+        if isinstance(self.model.ip_proj, Resampler):
+            # a "plus" adapter reads hidden_states[-2]: proj_in's input width is the tower's WIDTH, and the tower keeps the hidden states
+            cfg = S.CLIP_VISION_TINY if tiny else S.CLIP_VISION_H14
+            sd = None
+            if not (isinstance(image_encoder, str) and image_encoder.startswith("synthetic")):
+                sd = FrozenCLIPImageEmbedder.read_state_dict(image_encoder)
+                cls = next((v for k, v in sd.items() if k.endswith("embeddings.class_embedding")), None)
+                if cls is not None and int(cls.shape[0]) != embed_dim:
+                    raise ValueError(f"image_encoder: the tower is {int(cls.shape[0])} wide, the adapter's Resampler (proj_in) takes hidden states "
+                                     f"of width {embed_dim}")
+            if cfg.width != embed_dim:
+                raise ValueError(f"image_encoder: the tower is {cfg.width} wide, the adapter's Resampler (proj_in) takes hidden states of width "
+                                 f"{embed_dim}")
+            self.model.ip_proj.set_tokens(cfg.tokens)
+            enc = FrozenCLIPImageEmbedder(device=self.model.device, config=cfg, want_hidden=True)
+            if sd is None:
+                enc.transformer.load_synthetic(int(image_encoder.split(":")[1]) if ":" in image_encoder else 0)
+            else:
+                enc.load_state_dict(sd)
+            return enc
         # (the reduced tower is built as wide at its output as the adapter's projection takes, like the reduced OpenCLIP text tower)
         cfg = dataclasses.replace(S.CLIP_VISION_TINY, proj=embed_dim) if tiny else S.CLIP_VISION_H14
         synthetic = isinstance(image_encoder, str) and image_encoder.startswith("synthetic")
@@ -132,9 +158,11 @@ class hackathon():
                 text_encoder = FrozenOpenCLIPEmbedder(version=tok_dir, layer="penultimate", config=ccfg,
                                                       allow_hash_tokenizer=synthetic and tok_dir is None)
         # image-prompt adapter: the token count comes from the file's projection (or the synthetic spec) before the handle exists
-        ip_file, ip_seed, ip_tokens = None, None, 0
+        ip_file, ip_seed, ip_tokens, ip_kind = None, None, 0, "sd15"
+        tiny = isinstance(config, str) and config.startswith("tiny")
         if isinstance(ip_adapter, str) and ip_adapter.startswith("synthetic"):
             parts = ip_adapter.split(":")
+            ip_kind = "plus" if parts[0] == "synthetic-plus" else "sd15"
             ip_seed, ip_tokens = (int(parts[1]) if len(parts) > 1 else 0), (int(parts[2]) if len(parts) > 2 else 4)
         elif ip_adapter is not None:
             from . import ip_adapter as IPA
@@ -142,17 +170,21 @@ class hackathon():
             proj = IPA.split_groups(ip_file)[0]
             if "proj.weight" in proj and "norm.weight" in proj:
                 ip_tokens = int(proj["proj.weight"].shape[0]) // int(proj["norm.weight"].shape[0])
+            elif "latents" in proj and proj["latents"].dim() == 3:
+                ip_tokens = int(proj["latents"].shape[1])       # a "plus" file's Resampler: num_queries
             else:
-                ip_tokens = 4       # (a Resampler file: refused with its own message by load_ip_adapter below)
+                ip_tokens = 4       # (refused with its own message by load_ip_adapter below)
         self.model = create_model(config, cond_stage_model=text_encoder, vae_encoder=vae_encoder, extra_controlnets=len(extra_control),
                                   ip_adapter_tokens=ip_tokens)
+        self._ip_uncond_tokens = None        # a "plus" adapter's unconditional image tokens (`_plus_uncond_tokens`)
         if ip_seed is not None:
             from . import ip_adapter as IPA
-            ip_file = IPA.synthetic_adapter(self.model.rt.ucfg, ip_tokens, ip_seed)
+            ip_file = IPA.synthetic_adapter(self.model.rt.ucfg, ip_tokens, ip_seed, kind=ip_kind)
         if ip_file is not None:
-            self.model.load_ip_adapter(ip_file)      # before the base weights: they finalise the handle
+            # before the base weights: they finalise the handle.  A Resampler is built for the token count of the tower of this config
+            self.model.load_ip_adapter(ip_file, image_tokens=(S.CLIP_VISION_TINY if tiny else S.CLIP_VISION_H14).tokens)
         if image_encoder is not None:
-            self.image_encoder = self._init_image_encoder(image_encoder, isinstance(config, str) and config.startswith("tiny"))
+            self.image_encoder = self._init_image_encoder(image_encoder, tiny)
         if text_encoder is None:      # the seeded stand-in, as wide as the chosen config's context
             text_encoder = functools.partial(synthetic_text_encoder, length=self.model.rt.ucfg.context_len, dim=self.model.rt.ucfg.context_dim)
             self.model.cond_stage_model = text_encoder
@@ -314,21 +346,41 @@ class hackathon():
             if ip_image_embeds is not None or ip_tokens is not None or ip_image is not None:
                 raise ValueError("ip_image_embeds / ip_tokens need an adapter: initialize(..., ip_adapter=...)")
             return
+        from .ip_adapter import Resampler
+        plus = isinstance(getattr(m, "ip_proj", None), Resampler)
         if ip_image is not None:
             if ip_image_embeds is not None or ip_tokens is not None:
                 raise ValueError("this pipeline has an image-prompt adapter: give exactly one of ip_image, ip_image_embeds and ip_tokens")
             if getattr(self, "image_encoder", None) is None:
                 raise ValueError("ip_image needs the CLIP vision tower: initialize(..., ip_adapter=..., image_encoder=...) "
                                  "(or encode the picture elsewhere and pass ip_image_embeds)")
-            ip_image_embeds = self.image_encoder(ip_image)
+            if plus:
+                # the adapter's own rule: cond = Resampler(hidden_states[-2] of the picture), uncond = Resampler(those of a zero
+                # pixel_values); the latter depend on the weights only and are computed once per pipeline
+                ip_image_embeds = self.image_encoder.hidden(ip_image)
+            else:
+                ip_image_embeds = self.image_encoder(ip_image)
+        if plus and ip_image_embeds is not None and getattr(self, "image_encoder", None) is None:
+            raise ValueError("this pipeline's adapter is a 'plus' file (Resampler) without a vision tower: it takes ip_tokens only -- "
+                             "ip_image_embeds would have to be the tower's hidden_states[-2] with those of a zero image for the unconditional "
+                             "half; initialize(..., image_encoder=...) and pass ip_image")
         if (ip_image_embeds is None) == (ip_tokens is None):
             raise ValueError("this pipeline has an image-prompt adapter: give exactly one of ip_image_embeds and ip_tokens (or ip_image, with "
                              "initialize(..., image_encoder=)), to process or to set_image_prompt (ip_scale=0 switches the image prompt off)")
         if ip_tokens is not None:
             m.set_ip_tokens(ip_tokens)
+        elif plus:
+            m.set_ip_tokens(m.ip_proj(ip_image_embeds), self._plus_uncond_tokens())
         else:
             m.set_ip_image_embeds(ip_image_embeds)
         m.ip_scale = float(ip_scale)
+
+    def _plus_uncond_tokens(self):
+        """The unconditional image tokens of a "plus" adapter: Resampler(hidden_states[-2] of an all-zero pixel_values), the adapter's own
+        rule.  They depend on the weights only: computed once per pipeline and kept."""
+        if self._ip_uncond_tokens is None:
+            self._ip_uncond_tokens = self.model.ip_proj(self.image_encoder.hidden_of_zero_pixels()).clone()
+        return self._ip_uncond_tokens
 
     def _init_latent(self, init_image, image_resolution, hw, num_samples):
         """(resized init image HxWx3 uint8 on the host, z0 = get_first_stage_encoding(encode_first_stage(it)) for num_samples copies)"""

@@ -220,12 +220,13 @@ class ControlLDM:
     # -- image prompts (IP-Adapter; the runtime was created with ip_adapter_tokens = T).  The image tokens are conditioning like the
     # text context: the conditional request carries the image's tokens, the unconditional one the projection of a zero embedding, as in
     # the adapter's own pipeline.  They are kept here per role and travel in the conditioning dicts as "c_ip" (`with_ip`).
-    def load_ip_adapter(self, adapter):
+    def load_ip_adapter(self, adapter, image_tokens=None):
         """Load an IP-Adapter file (a path or its state dict) into a model created with ip_adapter_tokens: the to_k_ip / to_v_ip matrices
-        go to the runtime, the image projection stays here (`stablediffusioneo_amd.ip_adapter`).  Call it before the base weights are
-        finalised (`load_state_dict`), like the extra control networks' weights."""
+        go to the runtime, the image projection stays here (`stablediffusioneo_amd.ip_adapter`: an ImageProjModel, or the Resampler of a
+        "plus" file, fed by a vision tower of image_tokens tokens).  Call it before the base weights are finalised (`load_state_dict`),
+        like the extra control networks' weights."""
         from ..ip_adapter import load_ip_adapter
-        self.ip_proj = load_ip_adapter(self.rt, adapter)
+        self.ip_proj = load_ip_adapter(self.rt, adapter, image_tokens)
         return self
 
     def set_ip_tokens(self, cond, uncond=None):
@@ -252,7 +253,10 @@ class ControlLDM:
 
     def set_ip_image_embeds(self, cond_embeds, uncond_embeds=None, scale=1.0):
         """CLIP image embeddings (b or 1, embed_dim) -> tokens through the loaded adapter's ImageProjModel (torch fp32 on the device, once
-        per image).  uncond_embeds None: the projection of zeros."""
+        per image).  uncond_embeds None: the projection of zeros.
+        With the Resampler of a "plus" file the embeddings are the tower's hidden_states[-2] (b or 1, tokens, embed_dim), projected on
+        the HIP path; the adapter's own rule for the unconditional half is the hidden states of an all-zero pixel_values, which the
+        caller computes with the tower and passes as uncond_embeds (None here is still zeros)."""
         if getattr(self, "ip_proj", None) is None:
             raise RuntimeError("set_ip_image_embeds: no image projection (load_ip_adapter first, or give tokens to set_ip_tokens)")
         cond_embeds = cond_embeds.detach().to(device=self.device, dtype=torch.float32)

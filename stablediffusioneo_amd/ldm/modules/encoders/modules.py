@@ -213,3 +213,22 @@ class FrozenCLIPImageEmbedder(AbstractEncoder):
 
     def encode(self, images):
         return self(images)
+
+    def _need_hidden(self):
+        if not self.transformer.want_hidden:
+            raise RuntimeError("hidden_states[-2] needs a tower configured with want_hidden: FrozenCLIPImageEmbedder(..., want_hidden=True)")
+
+    def hidden(self, images):
+        """hidden_states[-2] [B, tokens, width] fp32 on the device of one picture or a list of them: what the Resampler projection of
+        the IP-Adapter "plus" files reads (the tower must have been built with want_hidden)"""
+        self._need_hidden()
+        if not isinstance(images, (list, tuple)):
+            images = [images]
+        return self.transformer.encode_images(list(images))[1]
+
+    def hidden_of_zero_pixels(self):
+        """hidden_states[-2] [1, tokens, width] of an all-zero `pixel_values`: the "plus" adapters' unconditional image prompt.  It
+        depends on the weights only."""
+        self._need_hidden()
+        s = self.config.image
+        return self.transformer.encode_pixels(torch.zeros((1, 3, s, s), dtype=torch.float32, device=self.transformer.device))[1]

@@ -436,6 +436,34 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
     return y
 
 
+def layernorm_pair(x, lat, gamma1, beta1, gamma2, beta2, eps=1e-5, kv_in=None, q_in=None):
+    """The Resampler's per-layer normalisation in one launch (`sdeo_layernorm_pair_f16`): x (b, t, c) fp16 normalised with (gamma1,
+    beta1) and lat (b, q, c) fp16 with (gamma2, beta2) -> (kv_in (b, t + q, c): x's rows then lat's; q_in (b * q, c): lat's rows again).
+    kv_in / q_in: optional contiguous destinations."""
+    lib = _lib.load()
+    _need_cuda(x, lat, gamma1, beta1, gamma2, beta2, kv_in, q_in)
+    b, t, c = x.shape
+    q = lat.shape[1]
+    assert lat.shape == (b, q, c) and x.dtype == torch.float16 and lat.dtype == torch.float16 and x.is_contiguous() and lat.is_contiguous()
+    assert all(v.dtype == torch.float32 and v.shape == (c,) and v.is_contiguous() for v in (gamma1, beta1, gamma2, beta2))
+    kv_in = _out(kv_in, (b, t + q, c), torch.float16, x.device)
+    q_in = _out(q_in, (b * q, c), torch.float16, x.device)
+    check(lib.sdeo_layernorm_pair_f16(ptr(kv_in), ptr(q_in), ptr(x), ptr(lat), ptr(gamma1), ptr(beta1), ptr(gamma2), ptr(beta2), b, t, q, c, eps,
+                                      cur_stream()), "layernorm_pair")
+    return kv_in, q_in
+
+
+def layernorm_f32(x, gamma, beta, eps=1e-5, out=None):
+    """LayerNorm over the last dim of fp32 x (rows, c), fp32 out (`sdeo_layernorm_f32`; the Resampler's norm_out)"""
+    lib = _lib.load()
+    _need_cuda(x, gamma, beta, out)
+    rows, c = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and gamma.dtype == torch.float32 and beta.dtype == torch.float32
+    y = _out(out, (rows, c), torch.float32, x.device)
+    check(lib.sdeo_layernorm_f32(ptr(y), ptr(x), ptr(gamma), ptr(beta), rows, c, eps, cur_stream()), "layernorm_f32")
+    return y
+
+
 def softmax_rows(s, scale=1.0, out=None):
     """fp16 softmax(s * scale) over the last dim of fp32 scores s (rows, cols): the VAE AttnBlock's materialised-score path.
     s and out (optional destination) may be column blocks of wider buffers: the row stride is .stride(0)."""

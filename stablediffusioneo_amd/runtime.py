@@ -790,6 +790,63 @@ class ClipVisionRuntime(_HandleRuntime):
         return self._encode()
 
 
+class ResamplerRuntime(_HandleRuntime):
+    """The Resampler image projection of the IP-Adapter "plus" files on the HIP path (csrc/resampler.hip): create -> load_state_dict ->
+    configure(batch) -> project(hidden).  `hidden` is the vision tower's hidden_states[-2] (`ClipVisionRuntime(want_hidden=True)`), the
+    result what `SdeoRuntime.set_ip_tokens` takes; both stay on the device."""
+
+    _prefix = "sdeo_resampler_"
+    _ndims = 4
+
+    def __init__(self, cfg: S.ResamplerConfig = S.RESAMPLER_PLUS_SD15, device: Optional[torch.device] = None):
+        super().__init__(device)
+        self.cfg = cfg
+        self._cfg = _lib.SdeoResamplerConfig(cfg.tokens, cfg.embed_dim, cfg.dim, cfg.depth, cfg.dim_head, cfg.heads, cfg.num_queries, cfg.ffn,
+                                             cfg.out_dim)
+        check(self.lib.sdeo_resampler_create(C.byref(self._cfg), C.byref(self.handle)), "sdeo_resampler_create")
+        self.batch = 0
+        self.generation = 0
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False):
+        """the adapter file's `image_proj` group (bare keys, or `image_proj.<key>`); anything else is ignored unless strict"""
+        for k, v in sd.items():
+            if not torch.is_floating_point(v):
+                continue
+            self.load_tensor(k, v, strict)
+        self._finalize()
+        return self
+
+    def load_synthetic(self, seed: int = 0):
+        return self.load_state_dict(S.synth_resampler_state_dict(self.cfg, seed), strict=True)
+
+    def configure(self, batch: int):
+        if batch != self.batch:
+            self.generation += 1
+            self.batch = 0
+            check(self.lib.sdeo_resampler_configure(self.handle, int(batch)), "sdeo_resampler_configure")
+            self.batch = batch
+        return self
+
+    def num_launches(self) -> int:
+        """launches of one `project` at the configured batch"""
+        return int(self.lib.sdeo_resampler_num_launches(self.handle))
+
+    def project(self, hidden: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """hidden (batch, tokens, embed_dim) -> image tokens (batch, num_queries, out_dim) fp32 on the device (into `out` when given)"""
+        c = self.cfg
+        if hidden.dim() != 3 or tuple(hidden.shape[1:]) != (c.tokens, c.embed_dim):
+            raise ValueError(f"hidden states of shape {tuple(hidden.shape)}, the Resampler takes (b, {c.tokens}, {c.embed_dim})")
+        self.configure(int(hidden.shape[0]))
+        hid = hidden.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        shape = (self.batch, c.num_queries, c.out_dim)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise _lib.SdeoError(f"project: out must be a contiguous fp32 tensor of shape {shape} on {self.device}")
+        check(self.lib.sdeo_resampler_project(self.handle, ptr(hid), self.batch, ptr(out), cur_stream()), "sdeo_resampler_project")
+        return out
+
+
 class HedRuntime(_HandleRuntime):
     """HED soft-edge annotator on the HIP path (`annotator/hed/__init__.py`: ControlNetHED_Apache2 + HEDdetector.__call__):
     create -> load_state_dict -> configure(H, W) -> detect(image).  One image per call; csrc/hed.hip."""

@@ -515,6 +515,79 @@ def synth_clip_vision_state_dict(cfg: ClipVisionConfig = CLIP_VISION_H14, seed: 
     return out
 
 
+@dataclass(frozen=True)
+class ResamplerConfig:
+    """The Resampler image projection of the IP-Adapter "plus" files (csrc/resampler.hip; include/sdeo.h states the algorithm); the
+    defaults are ip-adapter-plus_sd15 / ip-adapter-plus-face_sd15 behind the ViT-H/14 tower's hidden_states[-2]."""
+    tokens: int = 257
+    embed_dim: int = 1280
+    dim: int = 768
+    depth: int = 4
+    dim_head: int = 64
+    heads: int = 12
+    num_queries: int = 16
+    ffn: int = 3072
+    out_dim: int = 768
+
+    @property
+    def inner(self) -> int:
+        return self.heads * self.dim_head
+
+
+RESAMPLER_PLUS_SD15 = ResamplerConfig()
+# inner 64 != dim; dim = 12 vectors of 8, less than a wave; every key in one tile; fits CLIP_VISION_TINY (T 17, W 64) + UNET_TINY (96)
+RESAMPLER_TINY = ResamplerConfig(tokens=17, embed_dim=64, dim=96, depth=2, dim_head=32, heads=2, num_queries=4, ffn=384, out_dim=96)
+# the real T + Q = 273 ragged key tile, the real head dim and token count; fits CLIP_VISION_TINY80 (T 257, W 160)
+RESAMPLER_TINY273 = ResamplerConfig(tokens=257, embed_dim=160, dim=128, depth=2, dim_head=64, heads=2, num_queries=16, ffn=512, out_dim=96)
+NS_RESAMPLER = "image_proj."                        # the file's group; also the seed namespace of the synthetic draw
+RESAMPLER_DIM_HEAD = 64                             # the file does not state it; 64 in every published file
+
+
+def param_spec_resampler(cfg: ResamplerConfig = RESAMPLER_PLUS_SD15) -> "OrderedDict[str, tuple]":
+    """Tensor names below `image_proj.` and shapes of a "plus" adapter file's Resampler, in the order `sdeo_resampler_weight_info`
+    lists them.  The key names are stated from the published files and are UNPINNED: no plus file was at hand."""
+    d, i, f = cfg.dim, cfg.inner, cfg.ffn
+    spec = OrderedDict()
+    spec["latents"] = (1, cfg.num_queries, d)
+    spec["proj_in.weight"] = (d, cfg.embed_dim)
+    spec["proj_in.bias"] = (d,)
+    spec["proj_out.weight"] = (cfg.out_dim, d)
+    spec["proj_out.bias"] = (cfg.out_dim,)
+    spec["norm_out.weight"] = (cfg.out_dim,)
+    spec["norm_out.bias"] = (cfg.out_dim,)
+    for l in range(cfg.depth):
+        a, ff = f"layers.{l}.0.", f"layers.{l}.1."
+        for n in ("norm1", "norm2"):
+            spec[a + n + ".weight"] = (d,)
+            spec[a + n + ".bias"] = (d,)
+        spec[a + "to_q.weight"] = (i, d)
+        spec[a + "to_kv.weight"] = (2 * i, d)
+        spec[a + "to_out.weight"] = (d, i)
+        spec[ff + "0.weight"] = (d,)
+        spec[ff + "0.bias"] = (d,)
+        spec[ff + "1.weight"] = (f, d)
+        spec[ff + "3.weight"] = (d, f)
+    return spec
+
+
+def synth_resampler_state_dict(cfg: ResamplerConfig = RESAMPLER_PLUS_SD15, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Seeded Resampler weights (fp32, CPU) under the names of `param_spec_resampler`, as `ResamplerRuntime.load_synthetic` draws them.
+    Two tensors `synth_tensor` would get wrong: `latents` is randn / sqrt(dim) as the module initialises it (its fan-in rule would give
+    1 / sqrt(num_queries * dim)), and `layers.<l>.1.0.weight`, the FF LayerNorm's scale, has no "norm" in its name."""
+    out = OrderedDict()
+    for k, shp in param_spec_resampler(cfg).items():
+        if k == "latents":
+            g = torch.Generator(device="cpu")
+            g.manual_seed(_seed_for(seed, NS_RESAMPLER + k))
+            t = torch.randn(shp, generator=g) / cfg.dim ** 0.5
+        else:
+            t = synth_tensor(NS_RESAMPLER + k, shp, seed)
+            if k.endswith(".1.0.weight"):
+                t = 1.0 + 5.0 * t          # 0.02 N -> 1 + 0.1 N, like every other norm scale
+        out[k] = t
+    return out
+
+
 def synth_tensor(name: str, shape, seed: int = 0) -> torch.Tensor:
     """Deterministic stand-in for one checkpoint tensor (fp32, CPU).
 

@@ -14,6 +14,7 @@
 #         step_counters     whole-step counter passes, eager + one stream (tools/step_counters.py) -> step_counters.json
 #         pmc_graph_only / pmc_overlap_only   one --pmc pass of a 2-step sampler run with ONLY graph replay / ONLY the side stream on
 #         clip_vision_time  image-prompt timing: preprocess, ViT-H/14 encode, torch fp16 yardstick -> profiles/clip_vision_time.json
+#         resampler_time    IP-Adapter Plus Resampler: project at batch 1 / 2, torch fp16 yardstick, weight-read floor -> profiles/resampler_time.json
 #         py:<script>[,args] python <script> args                          -> py_<n>.log
 R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${1:-r3}
@@ -84,6 +85,7 @@ for st in "$@"; do
     pmc_both) step pmc_both s_pmc_mode both ;;
     benchx:*) a=${st#benchx:}; nm=$(echo $a | tr -d ',-' | cut -c1-30); step "$st" bash -c "timeout -k 10 500 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-roofline $(echo $a | tr ',' ' ') > $OUT/benchx_$nm.json 2> $OUT/benchx_$nm.err; rc=\$?; head -c 900 $OUT/benchx_$nm.json; echo; exit \$rc" ;;
     clip_vision_time) step "$st" bash -c "timeout -k 10 600 python tools/clip_vision_time.py --json $OUT/clip_vision_time.json > $OUT/clip_vision_time.log 2>&1; rc=\$?; tail -8 $OUT/clip_vision_time.log; exit \$rc" ;;
+    resampler_time) step "$st" bash -c "timeout -k 10 600 python tools/resampler_time.py --json $OUT/resampler_time.json > $OUT/resampler_time.log 2>&1; rc=\$?; tail -8 $OUT/resampler_time.log; exit \$rc" ;;
     py:*) a=${st#py:}; step "$st" bash -c "timeout -k 10 600 python $(echo $a | tr ',' ' ') > $OUT/py_$N.log 2>&1; rc=\$?; tail -25 $OUT/py_$N.log; exit \$rc" ;;
     *) echo "unknown step $st" ;;
   esac
