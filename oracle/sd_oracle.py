@@ -147,16 +147,22 @@ def basic_transformer_block(sd: SD, p, x, context, heads):
     return x
 
 
+def _proj(sd: SD, name, x):
+    w = sd[name + ".weight"]
+    return F.conv2d(x, w[:, :, None, None] if w.dim() == 2 else w, sd[name + ".bias"])
+
+
 def spatial_transformer(sd: SD, p, x, context, heads):
-    """SpatialTransformer.forward (`attention.py:431-450`), use_linear=False, depth=1."""
+    """SpatialTransformer.forward (`attention.py:431-450`), depth=1.  use_linear=True (2-D proj weights, the SD-2.x layout) applies
+    nn.Linear per token on either side of the rearrange: the same map as the 1x1 conv, so it is run as one."""
     b, c, h, w = x.shape
     x_in = x
     x = group_norm(sd, f"{p}.norm", x, 1e-6)
-    x = _conv(sd, f"{p}.proj_in", x, padding=0)
+    x = _proj(sd, f"{p}.proj_in", x)
     x = x.permute(0, 2, 3, 1).reshape(b, h * w, c)
     x = basic_transformer_block(sd, f"{p}.transformer_blocks.0", x, context, heads)
     x = x.reshape(b, h, w, c).permute(0, 3, 1, 2)
-    x = _conv(sd, f"{p}.proj_out", x, padding=0)
+    x = _proj(sd, f"{p}.proj_out", x)
     return x + x_in
 
 

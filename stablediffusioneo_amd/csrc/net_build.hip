@@ -44,6 +44,7 @@ struct ConvOpts {                     // conv / gemm options
   const T* res = nullptr;
   bool res_half = false;         // a full-batch launch whose residual was computed for the first half of the batch only (Builder::share)
   int act = 0;
+  int plan_rows = 0;             // gemm(): run the plan of the same GEMM at this many rows (ConvGemm::plan_B); 0: its own
   const float* scale_host = nullptr;   // read at launch time (control scales)
   const T* out = nullptr;        // write into this view instead of allocating
   int cout_store = -1;           // stored output channels (>= logical, padded rows of W are zero)
@@ -67,6 +68,7 @@ struct Builder {
   // full-batch tensors (same arena plan, it writes a prefix of them) and the full-batch problem's kernel plan (ConvGemm::plan_B,
   // AttnArgs::plan_B), so every row it writes is bit-identical to the full-batch launch's.
   bool share = false, half = false;
+  bool borrowed_plan = false;      // gemm() -> launch_conv(): plan_B comes from ConvOpts::plan_rows
   Program* prog = nullptr;
   size_t max_splitk = 0, max_gn = 0;
   std::string err;
@@ -111,8 +113,9 @@ struct Builder {
   const float* named_v(const std::string& name) { return reinterpret_cast<const float*>(e->ws.slab + e->named_off.at(name)); }
 
   void launch_conv(ConvGemm p, const float* scale_host, RowStats* stats = nullptr, T* gn_y = nullptr, const ConvOpts* lo = nullptr) {
-    // precision and scratch sizes follow the problem whose plan the launch takes (a half-batch launch: the full-batch one)
-    const int Mplan = p.plan_B ? p.M / p.B * p.plan_B : p.M;
+    // precision and scratch sizes follow the problem whose plan the launch takes (a half-batch launch: the full-batch one); a GEMM
+    // that only borrows the plan of more rows (ConvOpts::plan_rows) keeps the operand form of its own
+    const int Mplan = p.plan_B && !borrowed_plan ? p.M / p.B * p.plan_B : p.M;
     e->fp8.use_mx(p, Mplan, *this);
     e->fp8.use_fp8_weights(p, Mplan, e->ws.slab);
     const size_t tune_ws = e->autotune ? conv_gemm_autotune_workspace_bytes(p) : 0;
@@ -219,10 +222,12 @@ struct Builder {
     p.B = rows; p.Cin = x.c; p.M = rows; p.N = n; p.K = x.c;
     p.ldx = x.ld; p.ldw = ldw; p.act = o.act;
     if (half) p.plan_B = x.rows();
+    else if (o.plan_rows > rows) { p.plan_B = o.plan_rows; borrowed_plan = true; }
     if (o.res_half) p.res_rows = rows / 2;
     set_ln(p, o);
     if (o.ln && o.ln->c != x.c && err.empty()) err = "LayerNorm statistics of a " + std::to_string(o.ln->c) + "-channel tensor fed to K = " + std::to_string(x.c);
     launch_conv(p, o.scale_host, o.stats);
+    borrowed_plan = false;
     return y;
   }
 
@@ -437,11 +442,17 @@ static void build_time_embed(Builder& b, const std::string& ns, int net, int row
     f16* o = te.p;
     b.push([=](hipStream_t s) { return timestep_embedding(o, tp, rows, mc, s); });
   }
-  Builder::CO a; a.act = 1;
+  // The per-forward embedding (rows = N) runs the plans of the schedule's table (kTabRows rows): a row of the table and the same
+  // timestep passed as t are then the same instruction sequence, which is what SDEO_TIMESTEP_ROW promises (include/sdeo.h: a cached
+  // read is bit-identical).  Planned on their own rows the two part at full width: time_embed.2 (1280 x 1280) splits K at N rows
+  // and does not at 128, and the sums come out in another order.  (The operand form stays that of the launch's own rows: with
+  // block-scaled activations asked for from 128 rows down, a test setting, the table is packed to fp8 and these are not, as before.)
+  Builder::CO a; a.act = 1; a.plan_rows = Engine::kTabRows;
+  Builder::CO last; last.plan_rows = Engine::kTabRows;
   b.advance(te, b.gemm(te, b.wptr(ns + "time_embed.0.weight"), mc, emb, b.vptr(ns + "time_embed.0.bias"), a));
   // every consumer of emb applies SiLU first (emb_layers = SiLU -> Linear), so store SiLU(emb)
   b.advance(te, b.gemm(te, b.wptr(ns + "time_embed.2.weight"), emb, emb, b.vptr(ns + "time_embed.2.bias"), a));
-  b.gemm(te, b.named_w(ns + "emb_all.weight"), emb, total, b.named_v(ns + "emb_all.bias"), Builder::CO(), out, total);
+  b.gemm(te, b.named_w(ns + "emb_all.weight"), emb, total, b.named_v(ns + "emb_all.bias"), last, out, total);
   b.release(te);
 }
 

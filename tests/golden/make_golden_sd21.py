@@ -2,7 +2,7 @@
 (`num_head_channels`, `use_linear_in_transformer`, context_dim 1024), its DDIMSampler on a v-prediction model, and HuggingFace's
 CLIPTextModel with erf-GELU as the OpenCLIP text tower.  Same recipe and stubs as make_golden.py (build container only, CPU).
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_sd21.py [--only manifest,tiny,full,sampler,openclip]
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_sd21.py [--only manifest,tiny,full,sampler,openclip,shapes]
 
 Outputs (arrays, names and shapes only; inputs and weights are regenerated from seeds by the tests):
     manifest_sd21.json    parameter names + shapes of the reference ControlledUnetModel / ControlNet with the UNET_SD21 values (meta device)
@@ -10,6 +10,7 @@ Outputs (arrays, names and shapes only; inputs and weights are regenerated from 
     sd21_lat8.npz         full UNET_SD21 (866 M + its ControlNet) at latent 8x8, N = 2, t = [801, 1]: 13 controls + eps (~10 GB host RAM)
     sampler_v.npz         DDIMSampler.sample with parameterization = "v": analytic model (S = 10; scale 1 / 9; eta 0 / 0.5) with every
                           model output and noise draw recorded, and one run over the reference tiny21 nets (S = 4, 8x8, scale 7.5)
+    sd21_shapes.npz       full UNET_SD21 at the untuned shapes of tests/shape_cases.py SD21_SHAPES: eps, every 40th control channel, statistics
     openclip_tiny.npz     CLIPTextModel(hidden_act="gelu") on CLIP_TINY21: token ids, "last" and "penultimate" outputs
 """
 import argparse
@@ -102,6 +103,33 @@ def gen_full():
     out["eps"] = eps.numpy()
     np.savez_compressed(os.path.join(HERE, "sd21_lat8.npz"), **out)
     print("sd21_lat8:", len(out), "arrays", sum(v.nbytes for v in out.values()) / 1e6, "MB")
+
+
+def gen_shapes():
+    """tests/shape_cases.py SD21_SHAPES on the full UNET_SD21 nets (every row its own x / context / hint / t), stored like
+    make_golden_full.py --only shapes; the project's oracle runs on the same inputs and must agree to 1e-4 of max|eps|."""
+    from make_golden_full import store_pass
+    from oracle import sd_oracle as O
+    from tests import shape_cases as SC
+    ucfg = S.UNET_SD21
+    unet, cn = loaded_ref(ucfg)
+    up, cp, hc = S.unet_plan(ucfg), S.unet_plan(ucfg, False), S.hint_block_convs(ucfg)
+    su, sc = unet.state_dict(), cn.state_dict()
+    out = {}
+    for c in SC.SD21_SHAPES:
+        x, ctx, hint, t = SC.case_inputs(c, ctx_dim=ucfg.context_dim)
+        with torch.no_grad(), G.quiet():
+            ctrl = cn(x=x, hint=hint, timesteps=t, context=ctx)
+            eps = unet(x=x, timesteps=t, context=ctx, control=[k.clone() for k in ctrl], only_mid_control=False)
+            eps_o = O.apply_model(su, sc, up, cp, hc, x, t, ctx, hint, [1.0] * 13)
+        d = float((eps_o - eps).abs().max() / eps.abs().max())
+        print(f"sd21_shapes {c.tag}: |eps|max {float(eps.abs().max()):.3f}, oracle vs reference max|diff|/max|eps| = {d:.2e}", flush=True)
+        assert d <= 1e-4, f"{c.tag}: the oracle is {d:.2e} of max|eps| away from the reference"
+        store_pass(out, c.tag, ctrl, eps)
+    p = os.path.join(HERE, "sd21_shapes.npz")
+    np.savez_compressed(p, **out)
+    print("sd21_shapes:", len(out), "arrays", f"{os.path.getsize(p) / 2**20:.3f} MiB")
+    assert os.path.getsize(p) < 2**20
 
 
 def gen_sampler():
@@ -251,7 +279,8 @@ if __name__ == "__main__":
     a = ap.parse_args()
     G.install_stubs()
     torch.set_grad_enabled(False)
-    steps = {"manifest": gen_manifest, "tiny": gen_tiny_nets, "sampler": gen_sampler, "openclip": gen_openclip, "full": gen_full}
+    steps = {"manifest": gen_manifest, "tiny": gen_tiny_nets, "sampler": gen_sampler, "openclip": gen_openclip, "full": gen_full,
+             "shapes": gen_shapes}
     for k, fn in steps.items():
         if a.only and k not in a.only.split(","):
             continue

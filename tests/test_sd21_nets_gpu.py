@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests.common import GOLDEN, make_inputs
+from tests.shape_cases import SD21_SHAPES
 from tests.test_nets_gpu import REL_MAX, REL_MEAN, check
 
 pytestmark = pytest.mark.gpu
@@ -63,13 +64,21 @@ def test_tiny21_nets_vs_reference_golden(tiny21_rt, n, h, w, t):
     assert torch.equal(eps2, eps3)               # cached hint / context: the same bits
 
 
-def test_full_sd21_latent8_vs_reference_golden():
-    """Full SD-2.1 layout (865.9 M + its ControlNet; heads 5 / 10 / 20 / 20 at d = 64, context 1024) at latent 8x8, N = 2."""
+@pytest.fixture(scope="module")
+def sd21_rt():
+    """the full UNET_SD21 runtime, loaded once for the module"""
     from stablediffusioneo_amd import spec as S
     from stablediffusioneo_amd.runtime import SdeoRuntime
-    g = np.load(os.path.join(GOLDEN, "sd21_lat8.npz"))
     rt = SdeoRuntime(S.UNET_SD21, S.VAE_TINY)
     rt.load_synthetic(0)
+    return rt
+
+
+def test_full_sd21_latent8_vs_reference_golden(sd21_rt):
+    """Full SD-2.1 layout (865.9 M + its ControlNet; heads 5 / 10 / 20 / 20 at d = 64, context 1024) at latent 8x8, N = 2."""
+    from stablediffusioneo_amd import spec as S
+    g = np.load(os.path.join(GOLDEN, "sd21_lat8.npz"))
+    rt = sd21_rt
     exp = rt.expected_weights()
     assert exp["model.diffusion_model.middle_block.1.proj_in.weight"] == (1280, 1280)
     assert exp["model.diffusion_model.middle_block.1.transformer_blocks.0.attn2.to_v.weight"] == (1280, 1024)
@@ -80,6 +89,17 @@ def test_full_sd21_latent8_vs_reference_golden():
     for i, c in enumerate(ctrl):
         check(c, g[f"control{i}"], f"sd21 control{i}", rel_max=SD21_MAX, rel_mean=SD21_MEAN)
     check(rt.apply_model(x, hint, t, ctx), g["eps"], "sd21 eps (apply_model)", rel_max=SD21_MAX, rel_mean=SD21_MEAN)
+
+
+@pytest.mark.parametrize("case", SD21_SHAPES, ids=[c.tag for c in SD21_SHAPES])
+def test_full_sd21_shape_sweep_vs_reference(sd21_rt, case):
+    """the full SD-2.1 layout at the untuned shapes of tests/shape_cases.py (d = 64 attention at T = 960 / 240 / 60 / 15, Linear proj_in at
+    M no multiple of the tile): tests/golden/sd21_shapes.npz, checked as the SD-1.5 sweep is (three entry points; global, per-sample,
+    frame / interior) under SD21_MAX / SD21_MEAN"""
+    from stablediffusioneo_amd import spec as S
+    from tests.test_fullsize_golden_gpu import check_sweep_case
+    g = np.load(os.path.join(GOLDEN, "sd21_shapes.npz"))
+    check_sweep_case(sd21_rt, g, case, ctx_dim=S.UNET_SD21.context_dim, rel_max=SD21_MAX, rel_mean=SD21_MEAN, name="sd21")
 
 
 def _create_ex(cfg, nhc, linear, size=None):
