@@ -15,7 +15,7 @@
 // >= 3 p^2 are zero on both sides.  K = 592 is no multiple of 64, so the patch GEMM runs the register-staged kernel, whose K-steps of 32
 // mask their tail per 8-column chunk (conv_gemm.hip: kok).
 #include "../../include/sdeo.h"
-#include "handle_common.h"
+#include "clip_layers.h"
 
 using namespace sdeo;
 
@@ -197,21 +197,20 @@ static int preprocess_launch(f16* patch_rows, uint8_t* crop, const uint8_t* img,
 
 }  // namespace
 
-struct sdeo_clip_vision_handle_s {
+struct sdeo_clip_vision_handle_s : ProgramHandle {
   sdeo_clip_vision_config cfg{};
-  WeightStore ws;
-  bool finalized = false;
   // configured state
   int batch = 0, want_hidden = 0;
-  char* act = nullptr;
-  size_t act_bytes = 0;
-  float* splitk_ws = nullptr;
-  size_t splitk_bytes = 0;
-  Program prog;
   f16* rows = nullptr;           // patch rows [batch * P][Kp]: what the two ways in fill
   f16* keep = nullptr;           // want_hidden: the residual stream in front of the last layer [batch * T][W]
   float* out = nullptr;          // the caller's image_embeds of the encode under way (the projection GEMM writes it)
   unsigned filled = 0;           // bit b: slot b's patch rows were filled since the last encode
+
+  void free_configured() {
+    rows = nullptr; keep = nullptr;
+    batch = 0; want_hidden = 0; filled = 0;
+    ProgramHandle::free_configured();
+  }
 };
 
 namespace {
@@ -225,7 +224,7 @@ static int tokens_of(const sdeo_clip_vision_config& c) { return (c.image / c.pat
 static void build_registry(Vis* e) {
   const sdeo_clip_vision_config& c = e->cfg;
   WeightStore& r = e->ws;
-  const int W = c.width, F = c.ffn, T = tokens_of(c);
+  const int W = c.width, T = tokens_of(c);
   auto mat = [&](const std::string& n, int rows, int cols, size_t off) { r.add(n, W_LINEAR, {rows, cols}, off); };
   auto vec = [&](const std::string& n, int len, size_t off) { r.add(n, W_VEC, {len}, off); };
   vec("embeddings.class_embedding", W, r.take((size_t)W * 4));
@@ -234,37 +233,62 @@ static void build_registry(Vis* e) {
   mat("embeddings.position_embedding.weight", T, W, r.take((size_t)T * W * 2));
   vec("pre_layrnorm.weight", W, r.take((size_t)W * 4));
   vec("pre_layrnorm.bias", W, r.take((size_t)W * 4));
-  for (int l = 0; l < c.layers; ++l) {
-    const std::string p = "encoder.layers." + std::to_string(l) + ".";
-    const size_t qkv = r.take((size_t)3 * W * W * 2), qkvb = r.take((size_t)3 * W * 4);      // q | k | v stacked as in clip.hip
-    mat(p + "self_attn.q_proj.weight", W, W, qkv);
-    mat(p + "self_attn.k_proj.weight", W, W, qkv + (size_t)W * W * 2);
-    mat(p + "self_attn.v_proj.weight", W, W, qkv + (size_t)2 * W * W * 2);
-    vec(p + "self_attn.q_proj.bias", W, qkvb);
-    vec(p + "self_attn.k_proj.bias", W, qkvb + (size_t)W * 4);
-    vec(p + "self_attn.v_proj.bias", W, qkvb + (size_t)2 * W * 4);
-    mat(p + "self_attn.out_proj.weight", W, W, r.take((size_t)W * W * 2));
-    vec(p + "self_attn.out_proj.bias", W, r.take((size_t)W * 4));
-    vec(p + "layer_norm1.weight", W, r.take((size_t)W * 4));
-    vec(p + "layer_norm1.bias", W, r.take((size_t)W * 4));
-    mat(p + "mlp.fc1.weight", F, W, r.take((size_t)F * W * 2));
-    vec(p + "mlp.fc1.bias", F, r.take((size_t)F * 4));
-    mat(p + "mlp.fc2.weight", W, F, r.take((size_t)W * F * 2));
-    vec(p + "mlp.fc2.bias", W, r.take((size_t)W * 4));
-    vec(p + "layer_norm2.weight", W, r.take((size_t)W * 4));
-    vec(p + "layer_norm2.bias", W, r.take((size_t)W * 4));
-  }
+  clip_layers_register(r, c.layers, W, c.ffn);
   vec("post_layernorm.weight", W, r.take((size_t)W * 4));
   vec("post_layernorm.bias", W, r.take((size_t)W * 4));
   mat("visual_projection.weight", c.proj, W, r.take((size_t)c.proj * W * 2));
 }
 
-static void free_configured(Vis* e) {
-  if (e->act) (void)hipFree(e->act);
-  if (e->splitk_ws) (void)hipFree(e->splitk_ws);
-  e->act = nullptr; e->splitk_ws = nullptr; e->rows = nullptr; e->keep = nullptr;
-  e->prog.clear();
-  e->batch = 0; e->want_hidden = 0; e->splitk_bytes = 0; e->act_bytes = 0; e->filled = 0;
+// the body of sdeo_clip_vision_configure after its checks
+static int configure_impl(Vis* e, int B, int want_hidden) {
+  const sdeo_clip_vision_config& c = e->cfg;
+  const int T = tokens_of(c), P = T - 1, W = c.width, F = c.ffn, Kp = patch_kp(c.patch);
+  const int rows = B * T;
+  // activation buffers: patch rows [B P][Kp] fp16; patches [B P][W] fp32; xa, xb, a [rows][W]; qkv [rows][3W]; o [rows][W]; hid [rows][F];
+  // cls [B][W] fp16; keep [rows][W] (want_hidden)
+  const size_t o_rows = e->take((size_t)B * P * Kp * 2), o_pe = e->take((size_t)B * P * W * 4), o_xa = e->take((size_t)rows * W * 2),
+               o_xb = e->take((size_t)rows * W * 2), o_a = e->take((size_t)rows * W * 2), o_qkv = e->take((size_t)rows * 3 * W * 2),
+               o_o = e->take((size_t)rows * W * 2), o_h = e->take((size_t)rows * F * 2), o_cls = e->take((size_t)B * W * 2),
+               o_keep = want_hidden ? e->take((size_t)rows * W * 2) : 0;
+  if (int rc = e->alloc_act()) return rc;
+  const ClipLayerBufs b{e->at<f16>(o_xa), e->at<f16>(o_xb), e->at<f16>(o_a), e->at<f16>(o_qkv), e->at<f16>(o_o), e->at<f16>(o_h)};
+  f16 *xa = b.x, *cls = e->at<f16>(o_cls);
+  float* pe = e->at<float>(o_pe);
+  e->rows = e->at<f16>(o_rows);
+  e->keep = want_hidden ? e->at<f16>(o_keep) : nullptr;
+
+  auto wp = [&](const std::string& n) { return e->ws.ptr<f16>(n); };
+  auto vp = [&](const std::string& n) { return e->ws.ptr<float>(n); };
+  // 1. patch GEMM: fp32 out, so the embedding sum below is formed from unrounded products
+  e->gemm(e->rows, B * P, Kp, wp(kPatchWeight), W, nullptr, 0, nullptr, nullptr, pe);
+  // 2. class token + position embedding + pre_layrnorm
+  {
+    const float *ce = vp("embeddings.class_embedding"), *g = vp("pre_layrnorm.weight"), *bt = vp("pre_layrnorm.bias");
+    const f16* pos = wp("embeddings.position_embedding.weight");
+    e->prog.push_back(Op([=](hipStream_t s) {
+      hipLaunchKernelGGL(embed_ln_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, xa, pe, ce, pos, g, bt, rows, T, W, 1e-5f);
+      SDEO_HIP(hipGetLastError());
+      return 0;
+    }, "embed_ln", 0, 4.0 * B * P * W + 2.0 * rows * W));
+  }
+  // 3. the text tower's layers without the mask, erf GELU; hidden_states[-2] is copied out in front of the last one (the ping-pong
+  // buffers overwrite it)
+  const f16* x = clip_layers_push(*e, b, c.layers, B, T, W, F, c.heads, /*causal=*/0, /*mlp_act=*/5, [&](int l, const f16* src) {
+    if (!want_hidden || l != c.layers - 1) return;
+    f16* keep = e->keep;
+    e->prog.push_back(Op([=](hipStream_t s) {
+      SDEO_HIP(hipMemcpyAsync(keep, src, (size_t)rows * W * 2, hipMemcpyDeviceToDevice, s));
+      return 0;
+    }, "keep_hidden", 0, 4.0 * rows * W));
+  });
+  // 4. post_layernorm over the class-token rows only (row stride T W)
+  e->ln(cls, x, T * W, vp("post_layernorm.weight"), vp("post_layernorm.bias"), B, W);
+  // 5. visual_projection, fp32 into the caller's buffer of this encode
+  e->gemm(cls, B, W, wp("visual_projection.weight"), c.proj, nullptr, 0, nullptr, nullptr, nullptr, [e](ConvGemm& p) { p.y32 = e->out; });
+  if (int rc = e->alloc_splitk()) return rc;
+  e->batch = B;
+  e->want_hidden = want_hidden ? 1 : 0;
+  return 0;
 }
 
 }  // namespace
@@ -303,36 +327,21 @@ int sdeo_clip_vision_create(const sdeo_clip_vision_config* cfg, sdeo_clip_vision
   Vis* e = new Vis();
   e->cfg = *cfg;
   build_registry(e);
-  if (int rc = e->ws.alloc("sdeo_clip_vision_create", /*zero_fill=*/false)) {
-    delete e;
-    return rc;
-  }
-  *out = e;
-  return 0;
+  return handle_created("sdeo_clip_vision_create", e, out);
 }
 
-int sdeo_clip_vision_destroy(sdeo_clip_vision_handle h) {
-  if (!h) return 0;
-  free_configured(h);
-  h->ws.destroy();
-  delete h;
-  return 0;
-}
+int sdeo_clip_vision_destroy(sdeo_clip_vision_handle h) { return handle_destroy(h); }
 
-int sdeo_clip_vision_num_weights(sdeo_clip_vision_handle h) { return h ? (int)h->ws.entries.size() : 0; }
+int sdeo_clip_vision_num_weights(sdeo_clip_vision_handle h) { return handle_num_weights(h); }
 
 int sdeo_clip_vision_weight_info(sdeo_clip_vision_handle h, int i, const char** name, int64_t dims[4], int* ndim) {
-  SDEO_CHECK(h && i >= 0 && i < (int)h->ws.entries.size() && name && dims && ndim, "sdeo_clip_vision_weight_info: bad argument");
-  h->ws.info(i, name, dims, 4, 1, ndim);
-  return 0;
+  return handle_weight_info("sdeo_clip_vision_weight_info", h, i, name, dims, 4, 1, ndim);
 }
 
 int sdeo_clip_vision_load_weight(sdeo_clip_vision_handle h, const char* name, const float* host_data, const int64_t* dims, int ndim, int strict) {
   const char* who = "sdeo_clip_vision_load_weight";
   SDEO_CHECK(h && name && host_data && dims, "%s: null argument", who);
-  std::string key(name);
-  const size_t pos = key.find("vision_model.");
-  if (pos != std::string::npos) key = key.substr(pos + 13);
+  const std::string key = registry_key(name, "vision_model.");
   if (key != kPatchWeight) return h->ws.load(who, name, key, host_data, dims, ndim, strict);
   WeightStore& r = h->ws;
   WEntry& w = r.entries[r.index.at(key)];
@@ -348,101 +357,12 @@ int sdeo_clip_vision_load_weight(sdeo_clip_vision_handle h, const char* name, co
   return 0;
 }
 
-int sdeo_clip_vision_finalize_weights(sdeo_clip_vision_handle h) {
-  SDEO_CHECK(h, "sdeo_clip_vision_finalize_weights: null handle");
-  if (int rc = h->ws.require_all("sdeo_clip_vision_finalize_weights")) return rc;
-  h->finalized = true;
-  return 0;
-}
+int sdeo_clip_vision_finalize_weights(sdeo_clip_vision_handle h) { return handle_finalize_weights("sdeo_clip_vision_finalize_weights", h); }
 
 int sdeo_clip_vision_configure(sdeo_clip_vision_handle h, int batch, int want_hidden) {
   SDEO_CHECK(h && h->finalized, "sdeo_clip_vision_configure: weights not finalized");
   SDEO_CHECK(batch >= 1 && batch <= 16, "sdeo_clip_vision_configure: batch=%d out of range (1..16)", batch);
-  free_configured(h);
-  Vis* e = h;
-  const sdeo_clip_vision_config& c = e->cfg;
-  const int B = batch, T = tokens_of(c), P = T - 1, W = c.width, F = c.ffn, H = c.heads, d = W / H, Kp = patch_kp(c.patch);
-  const int rows = B * T;
-  // activation buffers: patch rows [B P][Kp] fp16; patches [B P][W] fp32; xa, xb, a [rows][W]; qkv [rows][3W]; o [rows][W]; hid [rows][F];
-  // cls [B][W] fp16; keep [rows][W] (want_hidden)
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = align_up(off, 256); off = o + bytes; return o; };
-  const size_t o_rows = take((size_t)B * P * Kp * 2), o_pe = take((size_t)B * P * W * 4), o_xa = take((size_t)rows * W * 2),
-               o_xb = take((size_t)rows * W * 2), o_a = take((size_t)rows * W * 2), o_qkv = take((size_t)rows * 3 * W * 2),
-               o_o = take((size_t)rows * W * 2), o_h = take((size_t)rows * F * 2), o_cls = take((size_t)B * W * 2),
-               o_keep = want_hidden ? take((size_t)rows * W * 2) : 0;
-  e->act_bytes = align_up(off, 256);
-  SDEO_HIP(hipMalloc((void**)&e->act, e->act_bytes));
-  SDEO_HIP(hipMemset(e->act, 0, e->act_bytes));
-  auto P16 = [&](size_t o) { return reinterpret_cast<f16*>(e->act + o); };
-  f16 *xa = P16(o_xa), *xb = P16(o_xb), *a = P16(o_a), *qkv = P16(o_qkv), *o = P16(o_o), *hid = P16(o_h), *cls = P16(o_cls);
-  float* pe = reinterpret_cast<float*>(e->act + o_pe);
-  e->rows = P16(o_rows);
-  e->keep = want_hidden ? P16(o_keep) : nullptr;
-
-  const WorkspaceRef wsr{&e->splitk_ws, &e->splitk_bytes};
-  auto gemm = [&](const f16* x, int M, int K, const f16* w, int N, const float* bias, int act, const f16* res, f16* y, float* y32,
-                  std::function<void(ConvGemm&)> late = nullptr) {
-    ConvGemm p;
-    p.x = x; p.w = w; p.y = y; p.y32 = y32; p.bias = bias; p.res = res; p.ldres = N;
-    p.B = M; p.Cin = K; p.M = M; p.N = N; p.K = K; p.ldx = K; p.ldw = K; p.ldy = N; p.act = act;
-    e->prog.push_back(conv_gemm_op(p, wsr, &e->splitk_bytes, false, 0, late));
-  };
-  auto ln = [&](const f16* xi, const float* g, const float* b) {
-    e->prog.push_back(Op([=](hipStream_t s) { return layernorm(a, W, xi, W, g, b, rows, W, 1e-5f, s); }, "layernorm", 0, 4.0 * rows * W));
-  };
-  auto wp = [&](const std::string& n) { return e->ws.ptr<f16>(n); };
-  auto vp = [&](const std::string& n) { return e->ws.ptr<float>(n); };
-  // 1. patch GEMM: fp32 out, so the embedding sum below is formed from unrounded products
-  gemm(e->rows, B * P, Kp, wp(kPatchWeight), W, nullptr, 0, nullptr, nullptr, pe);
-  // 2. class token + position embedding + pre_layrnorm
-  {
-    const float *ce = vp("embeddings.class_embedding"), *g = vp("pre_layrnorm.weight"), *b = vp("pre_layrnorm.bias");
-    const f16* pos = wp("embeddings.position_embedding.weight");
-    e->prog.push_back(Op([=](hipStream_t s) {
-      hipLaunchKernelGGL(embed_ln_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, xa, pe, ce, pos, g, b, rows, T, W, 1e-5f);
-      SDEO_HIP(hipGetLastError());
-      return 0;
-    }, "embed_ln", 0, 4.0 * B * P * W + 2.0 * rows * W));
-  }
-  // 3. the text tower's layer loop without the mask, erf GELU
-  f16* x = xa;
-  f16* xn = xb;
-  const float scale = 1.0f / sqrtf((float)d);
-  for (int l = 0; l < c.layers; ++l) {
-    const std::string p = "encoder.layers." + std::to_string(l) + ".";
-    if (want_hidden && l == c.layers - 1) {      // hidden_states[-2]: the ping-pong buffers overwrite it below
-      f16* keep = e->keep;
-      const f16* src = x;
-      e->prog.push_back(Op([=](hipStream_t s) {
-        SDEO_HIP(hipMemcpyAsync(keep, src, (size_t)rows * W * 2, hipMemcpyDeviceToDevice, s));
-        return 0;
-      }, "keep_hidden", 0, 4.0 * rows * W));
-    }
-    ln(x, vp(p + "layer_norm1.weight"), vp(p + "layer_norm1.bias"));
-    gemm(a, rows, W, wp(p + "self_attn.q_proj.weight"), 3 * W, vp(p + "self_attn.q_proj.bias"), 0, nullptr, qkv, nullptr);
-    e->prog.push_back(Op([=](hipStream_t s) {
-      return attention(o, W, qkv, 3 * W, qkv + W, 3 * W, qkv + 2 * W, 3 * W, B, H, T, T, T, T, d, scale, s, /*causal=*/0);
-    }, "attention", 4.0 * B * H * (double)T * T * d, 2.0 * B * H * d * (2.0 * T + 2.0 * T)));
-    gemm(o, rows, W, wp(p + "self_attn.out_proj.weight"), W, vp(p + "self_attn.out_proj.bias"), 0, x, xn, nullptr);
-    std::swap(x, xn);
-    ln(x, vp(p + "layer_norm2.weight"), vp(p + "layer_norm2.bias"));
-    gemm(a, rows, W, wp(p + "mlp.fc1.weight"), F, vp(p + "mlp.fc1.bias"), 5, nullptr, hid, nullptr);
-    gemm(hid, rows, F, wp(p + "mlp.fc2.weight"), W, vp(p + "mlp.fc2.bias"), 0, x, xn, nullptr);
-    std::swap(x, xn);
-  }
-  // 4. post_layernorm over the class-token rows only (row stride T W)
-  {
-    const float *g = vp("post_layernorm.weight"), *b = vp("post_layernorm.bias");
-    const f16* xf = x;
-    e->prog.push_back(Op([=](hipStream_t s) { return layernorm(cls, W, xf, T * W, g, b, B, W, 1e-5f, s); }, "layernorm", 0, 4.0 * B * W));
-  }
-  // 5. visual_projection, fp32 into the caller's buffer of this encode
-  gemm(cls, B, W, wp("visual_projection.weight"), c.proj, nullptr, 0, nullptr, nullptr, nullptr, [e](ConvGemm& p) { p.y32 = e->out; });
-  if (e->splitk_bytes) SDEO_HIP(hipMalloc((void**)&e->splitk_ws, e->splitk_bytes));
-  e->batch = B;
-  e->want_hidden = want_hidden ? 1 : 0;
-  return 0;
+  return handle_configure(h, [&] { return configure_impl(h, batch, want_hidden); });
 }
 
 int sdeo_clip_vision_set_pixels(sdeo_clip_vision_handle h, const float* pixel_values, int batch, void* stream) {
@@ -499,6 +419,6 @@ int sdeo_clip_vision_encode(sdeo_clip_vision_handle h, int batch, float* image_e
   return 0;
 }
 
-size_t sdeo_clip_vision_device_bytes(sdeo_clip_vision_handle h) { return h ? h->ws.slab_bytes + h->act_bytes + h->splitk_bytes : 0; }
+size_t sdeo_clip_vision_device_bytes(sdeo_clip_vision_handle h) { return handle_device_bytes(h); }
 
 }  // extern "C"

@@ -1,6 +1,10 @@
-// Host-side machinery shared by the network handles (net_handle.h with net.hip / net_weights.hip / net_build.hip, clip.hip, hed.hip): the weight registry / slab / loader and the
-// program runner with its per-launch profiler.  A handle registers its tensors (take / add), allocates the slab once, forwards its
-// *_weight_info / *_load_weight / *_finalize_weights entry points here, and unrolls its network into a Program at configure time.
+// Host-side machinery shared by the five network handles -- sdeo_* (net_handle.h with net.hip / net_weights.hip / net_build.hip),
+// sdeo_clip_* (clip.hip), sdeo_clip_vision_* (clip_vision.hip), sdeo_resampler_* (resampler.hip) and sdeo_hed_* (hed.hip): the weight
+// registry / slab / loader and the program runner with its per-launch profiler.  A handle registers its tensors (take / add),
+// allocates the slab once, forwards its *_weight_info / *_load_weight / *_finalize_weights entry points here, and unrolls its network
+// into a Program at configure time.  The four handles that run one program over one activation block share more than that: their
+// state, configure-time helpers and entry-point bodies are program_handle.h's ProgramHandle, and the CLIP layer of the two towers is
+// clip_layers.h.
 #pragma once
 #include <stdlib.h>
 

@@ -11,7 +11,7 @@
 //   hed_fuse_kernel      cv2.resize INTER_LINEAR on float32 (= F.interpolate bilinear, align_corners=False) of the five maps at each
 //                        output pixel, fp32 mean in numpy's order, fp64 sigmoid, truncation to uint8 (+ optional control tensor)
 #include "../../include/sdeo.h"
-#include "handle_common.h"
+#include "program_handle.h"
 #include "sdeo_internal.h"
 
 using namespace sdeo;
@@ -180,21 +180,20 @@ const int kBlockCh[5] = {64, 128, 256, 512, 512};
 
 }  // namespace
 
-struct sdeo_hed_handle_s {
-  WeightStore ws;
-  bool finalized = false;
+struct sdeo_hed_handle_s : ProgramHandle {
   // configured state
   int H = 0, W = 0;
-  char* act = nullptr;
-  size_t act_bytes = 0;
-  float* splitk_ws = nullptr;
-  size_t splitk_bytes = 0;
   const uint8_t* img = nullptr;      // the image of the current sdeo_hed_detect_u8 call (read by the intake op)
   uint8_t* edges = nullptr;
   float* control = nullptr;
   HedMaps maps{};
-  Program prog;
   Profiler prof;                     // sdeo_debug_hed_profile
+
+  void free_configured() {
+    maps = HedMaps{};
+    H = W = 0;
+    ProgramHandle::free_configured();
+  }
 };
 
 namespace {
@@ -220,87 +219,22 @@ static void build_registry(Hed* e) {
   }
 }
 
-static void free_configured(Hed* e) {
-  if (e->act) (void)hipFree(e->act);
-  if (e->splitk_ws) (void)hipFree(e->splitk_ws);
-  e->act = nullptr; e->splitk_ws = nullptr;
-  e->act_bytes = e->splitk_bytes = 0;
-  e->prog.clear();
-  e->H = e->W = 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int sdeo_hed_create(sdeo_hed_handle* out) {
-  SDEO_CHECK(out, "sdeo_hed_create: null argument");
-  Hed* e = new Hed();
-  build_registry(e);
-  if (int rc = e->ws.alloc("sdeo_hed_create", /*zero_fill=*/false)) {
-    delete e;
-    return rc;
-  }
-  *out = e;
-  return 0;
-}
-
-int sdeo_hed_destroy(sdeo_hed_handle h) {
-  if (!h) return 0;
-  free_configured(h);
-  h->ws.destroy();
-  delete h;
-  return 0;
-}
-
-int sdeo_hed_num_weights(sdeo_hed_handle h) { return h ? (int)h->ws.entries.size() : 0; }
-
-int sdeo_hed_weight_info(sdeo_hed_handle h, int i, const char** name, int64_t dims[4], int* ndim) {
-  SDEO_CHECK(h && i >= 0 && i < (int)h->ws.entries.size() && name && dims && ndim, "sdeo_hed_weight_info: bad argument");
-  h->ws.info(i, name, dims, 4, 0, ndim);
-  return 0;
-}
-
-int sdeo_hed_load_weight(sdeo_hed_handle h, const char* name, const float* host_data, const int64_t* dims, int ndim, int strict) {
-  SDEO_CHECK(h && name && host_data && dims, "sdeo_hed_load_weight: null argument");
-  if (int rc = h->ws.load("sdeo_hed_load_weight", name, name, host_data, dims, ndim, strict)) return rc;
-  if (h->ws.find(name)) h->finalized = false;      // a tensor changed: finalize again before the next configure / detect
-  return 0;
-}
-
-int sdeo_hed_finalize_weights(sdeo_hed_handle h) {
-  SDEO_CHECK(h, "sdeo_hed_finalize_weights: null handle");
-  if (int rc = h->ws.require_all("sdeo_hed_finalize_weights")) return rc;
-  h->finalized = true;
-  return 0;
-}
-
-int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
-  SDEO_CHECK(h, "sdeo_hed_configure: null handle");
-  SDEO_CHECK(h->finalized, "sdeo_hed_configure: weights not finalized");
-  SDEO_CHECK(height >= 16 && width >= 16 && height <= 8192 && width <= 8192, "sdeo_hed_configure: image %dx%d out of range (16..8192)",
-             height, width);
-  free_configured(h);
-  Hed* e = h;
-  const int H = height, W = width;
+// the body of sdeo_hed_configure after its checks
+static int configure_impl(Hed* e, int H, int W) {
   int hk[5], wk[5];
   hk[0] = H; wk[0] = W;
   for (int k = 1; k < 5; ++k) { hk[k] = hk[k - 1] / 2; wk[k] = wk[k - 1] / 2; }
   // arena: intake [H W][8] fp16; two ping-pong activation buffers of max_k h_k w_k C_k fp16 (block 1 is the largest); five side maps
   size_t act_elems = 0;
   for (int k = 0; k < 5; ++k) act_elems = std::max(act_elems, (size_t)hk[k] * wk[k] * kBlockCh[k]);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = align_up(off, 256); off = o + bytes; return o; };
-  const size_t o_in = take((size_t)H * W * 8 * 2), o_a = take(act_elems * 2), o_b = take(act_elems * 2);
+  const size_t o_in = e->take((size_t)H * W * 8 * 2), o_a = e->take(act_elems * 2), o_b = e->take(act_elems * 2);
   size_t o_side[5];
-  for (int k = 0; k < 5; ++k) o_side[k] = take((size_t)hk[k] * wk[k] * 4);
-  e->act_bytes = align_up(off, 256);
-  SDEO_HIP(hipMalloc((void**)&e->act, e->act_bytes));
-  SDEO_HIP(hipMemset(e->act, 0, e->act_bytes));
-  f16* xin = reinterpret_cast<f16*>(e->act + o_in);
-  f16* buf[2] = {reinterpret_cast<f16*>(e->act + o_a), reinterpret_cast<f16*>(e->act + o_b)};
+  for (int k = 0; k < 5; ++k) o_side[k] = e->take((size_t)hk[k] * wk[k] * 4);
+  if (int rc = e->alloc_act()) return rc;
+  f16* xin = e->at<f16>(o_in);
+  f16* buf[2] = {e->at<f16>(o_a), e->at<f16>(o_b)};
   for (int k = 0; k < 5; ++k) {
-    e->maps.m[k] = reinterpret_cast<float*>(e->act + o_side[k]);
+    e->maps.m[k] = e->at<float>(o_side[k]);
     e->maps.h[k] = hk[k];
     e->maps.w[k] = wk[k];
   }
@@ -330,7 +264,7 @@ int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
       q.Ho = h; q.Wo = w; q.M = h * w; q.N = c; q.K = 9 * cin;
       q.ldx = cin; q.ldw = q.K; q.ldy = c; q.ldres = c; q.ld_bias2 = c;
       q.act = 4;
-      e->prog.push_back(conv_gemm_op(q, WorkspaceRef{&e->splitk_ws, &e->splitk_bytes}, &e->splitk_bytes, false, 9 * (b == 0 && i == 0 ? 3 : cin)));
+      e->push(q, /*flop_k=*/9 * (b == 0 && i == 0 ? 3 : cin));
       cur = dst;
       cur_buf = cur_buf < 0 ? 0 : cur_buf ^ 1;
       cin = c;
@@ -345,10 +279,46 @@ int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
     }
   }
   e->prog.push_back(Op([e, H, W](hipStream_t s) { return hed_fuse(e->edges, e->control, e->maps, H, W, s); }, "hed_fuse_kernel"));
-  if (e->splitk_bytes) SDEO_HIP(hipMalloc((void**)&e->splitk_ws, e->splitk_bytes));
+  if (int rc = e->alloc_splitk()) return rc;
   e->H = H;
   e->W = W;
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdeo_hed_create(sdeo_hed_handle* out) {
+  SDEO_CHECK(out, "sdeo_hed_create: null argument");
+  Hed* e = new Hed();
+  build_registry(e);
+  return handle_created("sdeo_hed_create", e, out);
+}
+
+int sdeo_hed_destroy(sdeo_hed_handle h) { return handle_destroy(h); }
+
+int sdeo_hed_num_weights(sdeo_hed_handle h) { return handle_num_weights(h); }
+
+int sdeo_hed_weight_info(sdeo_hed_handle h, int i, const char** name, int64_t dims[4], int* ndim) {
+  return handle_weight_info("sdeo_hed_weight_info", h, i, name, dims, 4, 0, ndim);
+}
+
+int sdeo_hed_load_weight(sdeo_hed_handle h, const char* name, const float* host_data, const int64_t* dims, int ndim, int strict) {
+  SDEO_CHECK(h && name && host_data && dims, "sdeo_hed_load_weight: null argument");
+  if (int rc = h->ws.load("sdeo_hed_load_weight", name, name, host_data, dims, ndim, strict)) return rc;
+  if (h->ws.find(name)) h->finalized = false;      // a tensor changed: finalize again before the next configure / detect
+  return 0;
+}
+
+int sdeo_hed_finalize_weights(sdeo_hed_handle h) { return handle_finalize_weights("sdeo_hed_finalize_weights", h); }
+
+int sdeo_hed_configure(sdeo_hed_handle h, int height, int width) {
+  SDEO_CHECK(h, "sdeo_hed_configure: null handle");
+  SDEO_CHECK(h->finalized, "sdeo_hed_configure: weights not finalized");
+  SDEO_CHECK(height >= 16 && width >= 16 && height <= 8192 && width <= 8192, "sdeo_hed_configure: image %dx%d out of range (16..8192)",
+             height, width);
+  return handle_configure(h, [&] { return configure_impl(h, height, width); });
 }
 
 int sdeo_hed_detect_u8(sdeo_hed_handle h, const uint8_t* img_hwc, uint8_t* edges, float* control_chw, float* const* side, void* stream) {
@@ -370,7 +340,7 @@ int sdeo_hed_detect_u8(sdeo_hed_handle h, const uint8_t* img_hwc, uint8_t* edges
   return 0;
 }
 
-size_t sdeo_hed_device_bytes(sdeo_hed_handle h) { return h ? h->ws.slab_bytes + h->act_bytes + h->splitk_bytes : 0; }
+size_t sdeo_hed_device_bytes(sdeo_hed_handle h) { return handle_device_bytes(h); }
 
 // ---- not in sdeo.h: tests and tools
 

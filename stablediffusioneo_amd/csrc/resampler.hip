@@ -17,7 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/sdeo.h"
-#include "handle_common.h"
+#include "program_handle.h"
 
 using namespace sdeo;
 
@@ -169,19 +169,17 @@ static int layernorm_f32(float* y, const float* x, const float* gamma, const flo
 
 }  // namespace
 
-struct sdeo_resampler_handle_s {
+struct sdeo_resampler_handle_s : ProgramHandle {
   sdeo_resampler_config cfg{};
-  WeightStore ws;
-  bool finalized = false;
   // configured state
   int batch = 0;
-  char* act = nullptr;
-  size_t act_bytes = 0;
-  float* splitk_ws = nullptr;
-  size_t splitk_bytes = 0;
-  Program prog;
   const float* in = nullptr;     // the caller's hidden / tokens_out of the project under way
   float* out = nullptr;
+
+  void free_configured() {
+    batch = 0;
+    ProgramHandle::free_configured();
+  }
 };
 
 namespace {
@@ -218,12 +216,71 @@ static void build_registry(Res* e) {
   }
 }
 
-static void free_configured(Res* e) {
-  if (e->act) (void)hipFree(e->act);
-  if (e->splitk_ws) (void)hipFree(e->splitk_ws);
-  e->act = nullptr; e->splitk_ws = nullptr;
-  e->prog.clear();
-  e->batch = 0; e->splitk_bytes = 0; e->act_bytes = 0;
+// the body of sdeo_resampler_configure after its checks
+static int configure_impl(Res* e, int B) {
+  const sdeo_resampler_config& c = e->cfg;
+  const int T = c.tokens, E = c.embed_dim, D = c.dim, H = c.heads, d = c.dim_head, I = H * d, Q = c.num_queries, F = c.ffn, O = c.out_dim;
+  const int xrows = B * T, lrows = B * Q, krows = B * (T + Q);
+  // activation buffers: hid [B T][E] fp16; x [B T][D]; la, lb [B Q][D] (the latent stream, ping-pong); kv_in [B (T + Q)][D]; q_in, a
+  // [B Q][D]; q, o [B Q][I]; kv [B (T + Q)][2 I]; ff [B Q][F]; po [B Q][O] fp32
+  const size_t o_hid = e->take((size_t)xrows * E * 2), o_x = e->take((size_t)xrows * D * 2), o_la = e->take((size_t)lrows * D * 2),
+               o_lb = e->take((size_t)lrows * D * 2), o_kvin = e->take((size_t)krows * D * 2), o_qin = e->take((size_t)lrows * D * 2),
+               o_a = e->take((size_t)lrows * D * 2), o_q = e->take((size_t)lrows * I * 2), o_o = e->take((size_t)lrows * I * 2),
+               o_kv = e->take((size_t)krows * 2 * I * 2), o_ff = e->take((size_t)lrows * F * 2), o_po = e->take((size_t)lrows * O * 4);
+  if (int rc = e->alloc_act()) return rc;
+  auto P16 = [&](size_t o) { return e->at<f16>(o); };
+  f16 *hid = P16(o_hid), *x = P16(o_x), *la = P16(o_la), *lb = P16(o_lb), *kv_in = P16(o_kvin), *q_in = P16(o_qin), *a = P16(o_a), *q = P16(o_q),
+      *o = P16(o_o), *kv = P16(o_kv), *ff = P16(o_ff);
+  float* po = e->at<float>(o_po);
+
+  auto wp = [&](const std::string& n) { return e->ws.ptr<f16>(n); };
+  auto vp = [&](const std::string& n) { return e->ws.ptr<float>(n); };
+  // 1. the caller's fp32 hidden states -> fp16 rows; proj_in
+  e->prog.push_back(Op([=](hipStream_t s) { return f32_to_f16(hid, e->in, (int64_t)xrows * E, s); }, "f32_to_f16", 0, 6.0 * xrows * E));
+  e->gemm(hid, xrows, E, wp("proj_in.weight"), D, vp("proj_in.bias"), 0, nullptr, x);
+  // 2. the latent parameter into every image's rows
+  {
+    const f16* src = wp("latents");
+    const int n8 = Q * D / 8;
+    e->prog.push_back(Op([=](hipStream_t s) {
+      hipLaunchKernelGGL(broadcast_rows_kernel, dim3(cdiv(B * n8, 256)), dim3(256), 0, s, la, src, B, n8);
+      SDEO_HIP(hipGetLastError());
+      return 0;
+    }, "broadcast_rows", 0, 2.0 * (B + 1) * Q * D));
+  }
+  // 3. the layers
+  f16* lat = la;
+  f16* nxt = lb;
+  const float scale = 1.0f / sqrtf((float)d);
+  for (int l = 0; l < c.depth; ++l) {
+    const std::string pa = "layers." + std::to_string(l) + ".0.", pf = "layers." + std::to_string(l) + ".1.";
+    {
+      const float *g1 = vp(pa + "norm1.weight"), *b1 = vp(pa + "norm1.bias"), *g2 = vp(pa + "norm2.weight"), *b2 = vp(pa + "norm2.bias");
+      const f16* li = lat;
+      e->prog.push_back(Op([=](hipStream_t s) { return layernorm_pair(kv_in, q_in, x, li, g1, b1, g2, b2, B, T, Q, D, 1e-5f, s); }, "layernorm_pair", 0,
+                           4.0 * krows * D + 2.0 * lrows * D));
+    }
+    e->gemm(q_in, lrows, D, wp(pa + "to_q.weight"), I, nullptr, 0, nullptr, q);
+    e->gemm(kv_in, krows, D, wp(pa + "to_kv.weight"), 2 * I, nullptr, 0, nullptr, kv);
+    e->prog.push_back(Op([=](hipStream_t s) {
+      return attention(o, I, q, I, kv, 2 * I, kv + I, 2 * I, B, H, Q, T + Q, T + Q, T + Q, d, scale, s, /*causal=*/0);
+    }, "attention", 4.0 * B * H * (double)Q * (T + Q) * d, 2.0 * B * H * d * (2.0 * Q + 2.0 * (T + Q))));
+    e->gemm(o, lrows, I, wp(pa + "to_out.weight"), D, nullptr, 0, lat, nxt);
+    std::swap(lat, nxt);
+    e->ln(a, lat, D, vp(pf + "0.weight"), vp(pf + "0.bias"), lrows, D);
+    e->gemm(a, lrows, D, wp(pf + "1.weight"), F, nullptr, 5, nullptr, ff);
+    e->gemm(ff, lrows, F, wp(pf + "3.weight"), D, nullptr, 0, lat, nxt);
+    std::swap(lat, nxt);
+  }
+  // 4. proj_out in fp32, norm_out fp32 -> the caller's tokens
+  e->gemm(lat, lrows, D, wp("proj_out.weight"), O, vp("proj_out.bias"), 0, nullptr, nullptr, po);
+  {
+    const float *g = vp("norm_out.weight"), *b = vp("norm_out.bias");
+    e->prog.push_back(Op([=](hipStream_t s) { return layernorm_f32(e->out, po, g, b, lrows, O, 1e-5f, s); }, "layernorm_f32", 0, 8.0 * lrows * O));
+  }
+  if (int rc = e->alloc_splitk()) return rc;
+  e->batch = B;
+  return 0;
 }
 
 }  // namespace
@@ -262,129 +319,29 @@ int sdeo_resampler_create(const sdeo_resampler_config* cfg, sdeo_resampler_handl
   Res* e = new Res();
   e->cfg = *cfg;
   build_registry(e);
-  if (int rc = e->ws.alloc(who, /*zero_fill=*/false)) {
-    delete e;
-    return rc;
-  }
-  *out = e;
-  return 0;
+  return handle_created(who, e, out);
 }
 
-int sdeo_resampler_destroy(sdeo_resampler_handle h) {
-  if (!h) return 0;
-  free_configured(h);
-  h->ws.destroy();
-  delete h;
-  return 0;
-}
+int sdeo_resampler_destroy(sdeo_resampler_handle h) { return handle_destroy(h); }
 
-int sdeo_resampler_num_weights(sdeo_resampler_handle h) { return h ? (int)h->ws.entries.size() : 0; }
+int sdeo_resampler_num_weights(sdeo_resampler_handle h) { return handle_num_weights(h); }
 
 int sdeo_resampler_weight_info(sdeo_resampler_handle h, int i, const char** name, int64_t dims[4], int* ndim) {
-  SDEO_CHECK(h && i >= 0 && i < (int)h->ws.entries.size() && name && dims && ndim, "sdeo_resampler_weight_info: bad argument");
-  h->ws.info(i, name, dims, 4, 1, ndim);
-  return 0;
+  return handle_weight_info("sdeo_resampler_weight_info", h, i, name, dims, 4, 1, ndim);
 }
 
 int sdeo_resampler_load_weight(sdeo_resampler_handle h, const char* name, const float* host_data, const int64_t* dims, int ndim, int strict) {
   const char* who = "sdeo_resampler_load_weight";
   SDEO_CHECK(h && name && host_data && dims, "%s: null argument", who);
-  std::string key(name);
-  const size_t pos = key.find("image_proj.");
-  if (pos != std::string::npos) key = key.substr(pos + 11);
-  return h->ws.load(who, name, key, host_data, dims, ndim, strict);
+  return h->ws.load(who, name, registry_key(name, "image_proj."), host_data, dims, ndim, strict);
 }
 
-int sdeo_resampler_finalize_weights(sdeo_resampler_handle h) {
-  SDEO_CHECK(h, "sdeo_resampler_finalize_weights: null handle");
-  if (int rc = h->ws.require_all("sdeo_resampler_finalize_weights")) return rc;
-  h->finalized = true;
-  return 0;
-}
+int sdeo_resampler_finalize_weights(sdeo_resampler_handle h) { return handle_finalize_weights("sdeo_resampler_finalize_weights", h); }
 
 int sdeo_resampler_configure(sdeo_resampler_handle h, int batch) {
   SDEO_CHECK(h && h->finalized, "sdeo_resampler_configure: weights not finalized");
   SDEO_CHECK(batch >= 1 && batch <= 16, "sdeo_resampler_configure: batch=%d out of range (1..16)", batch);
-  free_configured(h);
-  Res* e = h;
-  const sdeo_resampler_config& c = e->cfg;
-  const int B = batch, T = c.tokens, E = c.embed_dim, D = c.dim, H = c.heads, d = c.dim_head, I = H * d, Q = c.num_queries, F = c.ffn, O = c.out_dim;
-  const int xrows = B * T, lrows = B * Q, krows = B * (T + Q);
-  // activation buffers: hid [B T][E] fp16; x [B T][D]; la, lb [B Q][D] (the latent stream, ping-pong); kv_in [B (T + Q)][D]; q_in, a
-  // [B Q][D]; q, o [B Q][I]; kv [B (T + Q)][2 I]; ff [B Q][F]; po [B Q][O] fp32
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = align_up(off, 256); off = o + bytes; return o; };
-  const size_t o_hid = take((size_t)xrows * E * 2), o_x = take((size_t)xrows * D * 2), o_la = take((size_t)lrows * D * 2),
-               o_lb = take((size_t)lrows * D * 2), o_kvin = take((size_t)krows * D * 2), o_qin = take((size_t)lrows * D * 2),
-               o_a = take((size_t)lrows * D * 2), o_q = take((size_t)lrows * I * 2), o_o = take((size_t)lrows * I * 2),
-               o_kv = take((size_t)krows * 2 * I * 2), o_ff = take((size_t)lrows * F * 2), o_po = take((size_t)lrows * O * 4);
-  e->act_bytes = align_up(off, 256);
-  SDEO_HIP(hipMalloc((void**)&e->act, e->act_bytes));
-  SDEO_HIP(hipMemset(e->act, 0, e->act_bytes));
-  auto P16 = [&](size_t o) { return reinterpret_cast<f16*>(e->act + o); };
-  f16 *hid = P16(o_hid), *x = P16(o_x), *la = P16(o_la), *lb = P16(o_lb), *kv_in = P16(o_kvin), *q_in = P16(o_qin), *a = P16(o_a), *q = P16(o_q),
-      *o = P16(o_o), *kv = P16(o_kv), *ff = P16(o_ff);
-  float* po = reinterpret_cast<float*>(e->act + o_po);
-
-  const WorkspaceRef wsr{&e->splitk_ws, &e->splitk_bytes};
-  auto gemm = [&](const f16* xi, int M, int K, const f16* w, int N, const float* bias, int act, const f16* res, f16* y, float* y32) {
-    ConvGemm p;
-    p.x = xi; p.w = w; p.y = y; p.y32 = y32; p.bias = bias; p.res = res; p.ldres = N;
-    p.B = M; p.Cin = K; p.M = M; p.N = N; p.K = K; p.ldx = K; p.ldw = K; p.ldy = N; p.act = act;
-    e->prog.push_back(conv_gemm_op(p, wsr, &e->splitk_bytes));
-  };
-  auto wp = [&](const std::string& n) { return e->ws.ptr<f16>(n); };
-  auto vp = [&](const std::string& n) { return e->ws.ptr<float>(n); };
-  // 1. the caller's fp32 hidden states -> fp16 rows; proj_in
-  e->prog.push_back(Op([=](hipStream_t s) { return f32_to_f16(hid, e->in, (int64_t)xrows * E, s); }, "f32_to_f16", 0, 6.0 * xrows * E));
-  gemm(hid, xrows, E, wp("proj_in.weight"), D, vp("proj_in.bias"), 0, nullptr, x, nullptr);
-  // 2. the latent parameter into every image's rows
-  {
-    const f16* src = wp("latents");
-    const int n8 = Q * D / 8;
-    e->prog.push_back(Op([=](hipStream_t s) {
-      hipLaunchKernelGGL(broadcast_rows_kernel, dim3(cdiv(B * n8, 256)), dim3(256), 0, s, la, src, B, n8);
-      SDEO_HIP(hipGetLastError());
-      return 0;
-    }, "broadcast_rows", 0, 2.0 * (B + 1) * Q * D));
-  }
-  // 3. the layers
-  f16* lat = la;
-  f16* nxt = lb;
-  const float scale = 1.0f / sqrtf((float)d);
-  for (int l = 0; l < c.depth; ++l) {
-    const std::string pa = "layers." + std::to_string(l) + ".0.", pf = "layers." + std::to_string(l) + ".1.";
-    {
-      const float *g1 = vp(pa + "norm1.weight"), *b1 = vp(pa + "norm1.bias"), *g2 = vp(pa + "norm2.weight"), *b2 = vp(pa + "norm2.bias");
-      const f16* li = lat;
-      e->prog.push_back(Op([=](hipStream_t s) { return layernorm_pair(kv_in, q_in, x, li, g1, b1, g2, b2, B, T, Q, D, 1e-5f, s); }, "layernorm_pair", 0,
-                           4.0 * krows * D + 2.0 * lrows * D));
-    }
-    gemm(q_in, lrows, D, wp(pa + "to_q.weight"), I, nullptr, 0, nullptr, q, nullptr);
-    gemm(kv_in, krows, D, wp(pa + "to_kv.weight"), 2 * I, nullptr, 0, nullptr, kv, nullptr);
-    e->prog.push_back(Op([=](hipStream_t s) {
-      return attention(o, I, q, I, kv, 2 * I, kv + I, 2 * I, B, H, Q, T + Q, T + Q, T + Q, d, scale, s, /*causal=*/0);
-    }, "attention", 4.0 * B * H * (double)Q * (T + Q) * d, 2.0 * B * H * d * (2.0 * Q + 2.0 * (T + Q))));
-    gemm(o, lrows, I, wp(pa + "to_out.weight"), D, nullptr, 0, lat, nxt, nullptr);
-    std::swap(lat, nxt);
-    {
-      const float *g = vp(pf + "0.weight"), *b = vp(pf + "0.bias");
-      const f16* li = lat;
-      e->prog.push_back(Op([=](hipStream_t s) { return layernorm(a, D, li, D, g, b, lrows, D, 1e-5f, s); }, "layernorm", 0, 4.0 * lrows * D));
-    }
-    gemm(a, lrows, D, wp(pf + "1.weight"), F, nullptr, 5, nullptr, ff, nullptr);
-    gemm(ff, lrows, F, wp(pf + "3.weight"), D, nullptr, 0, lat, nxt, nullptr);
-    std::swap(lat, nxt);
-  }
-  // 4. proj_out in fp32, norm_out fp32 -> the caller's tokens
-  gemm(lat, lrows, D, wp("proj_out.weight"), O, vp("proj_out.bias"), 0, nullptr, nullptr, po);
-  {
-    const float *g = vp("norm_out.weight"), *b = vp("norm_out.bias");
-    e->prog.push_back(Op([=](hipStream_t s) { return layernorm_f32(e->out, po, g, b, lrows, O, 1e-5f, s); }, "layernorm_f32", 0, 8.0 * lrows * O));
-  }
-  if (e->splitk_bytes) SDEO_HIP(hipMalloc((void**)&e->splitk_ws, e->splitk_bytes));
-  e->batch = B;
-  return 0;
+  return handle_configure(h, [&] { return configure_impl(h, batch); });
 }
 
 int sdeo_resampler_num_launches(sdeo_resampler_handle h) { return h ? (int)h->prog.size() : 0; }
@@ -401,6 +358,6 @@ int sdeo_resampler_project(sdeo_resampler_handle h, const float* hidden, int bat
   return run_program(h->prog, reinterpret_cast<hipStream_t>(stream));
 }
 
-size_t sdeo_resampler_device_bytes(sdeo_resampler_handle h) { return h ? h->ws.slab_bytes + h->act_bytes + h->splitk_bytes : 0; }
+size_t sdeo_resampler_device_bytes(sdeo_resampler_handle h) { return handle_device_bytes(h); }
 
 }  // extern "C"

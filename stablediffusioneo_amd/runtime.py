@@ -103,6 +103,16 @@ class _HandleRuntime:
     def _finalize(self):
         self._call("finalize_weights")
 
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False):
+        """Every floating-point tensor of `sd` through `<prefix>load_weight` (which ignores a name it does not know unless strict), then
+        finalize.  The subclasses say which names their door takes."""
+        for k, v in sd.items():
+            if not torch.is_floating_point(v):
+                continue
+            self.load_tensor(k, v, strict)
+        self._finalize()
+        return self
+
     def device_bytes(self) -> int:
         return int(self._sym("device_bytes")(self.handle))
 
@@ -628,13 +638,7 @@ class ClipRuntime(_HandleRuntime):
         """Accepts HuggingFace names (`text_model.*`, or bare), or the SD checkpoint's `cond_stage_model.transformer.text_model.*`,
         or OpenCLIP's names (bare, or below `model.` / `cond_stage_model.model.` as an SD-2.x checkpoint stores them; see
         `openclip_to_hf`); anything else (e.g. `position_ids`, the UNet tensors of a full checkpoint) is ignored unless strict."""
-        sd = openclip_to_hf(sd)
-        for k, v in sd.items():
-            if not torch.is_floating_point(v):
-                continue
-            self.load_tensor(k, v, strict)
-        self._finalize()
-        return self
+        return super().load_state_dict(openclip_to_hf(sd), strict)
 
     def load_synthetic(self, seed: int = 0):
         for name, shape in self.expected_weights().items():
@@ -696,12 +700,7 @@ class ClipVisionRuntime(_HandleRuntime):
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False):
         """HuggingFace keys of `CLIPVisionModelWithProjection` (`vision_model.*`, `visual_projection.weight`; bare names below
         `vision_model.` are accepted); anything else (`position_ids`, a text tower) is ignored unless strict."""
-        for k, v in sd.items():
-            if not torch.is_floating_point(v):
-                continue
-            self.load_tensor(k, v, strict)
-        self._finalize()
-        return self
+        return super().load_state_dict(sd, strict)
 
     def load_synthetic(self, seed: int = 0):
         return self.load_state_dict(S.synth_clip_vision_state_dict(self.cfg, seed), strict=True)
@@ -809,12 +808,7 @@ class ResamplerRuntime(_HandleRuntime):
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False):
         """the adapter file's `image_proj` group (bare keys, or `image_proj.<key>`); anything else is ignored unless strict"""
-        for k, v in sd.items():
-            if not torch.is_floating_point(v):
-                continue
-            self.load_tensor(k, v, strict)
-        self._finalize()
-        return self
+        return super().load_state_dict(sd, strict)
 
     def load_synthetic(self, seed: int = 0):
         return self.load_state_dict(S.synth_resampler_state_dict(self.cfg, seed), strict=True)
@@ -861,11 +855,7 @@ class HedRuntime(_HandleRuntime):
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = False):
         """The reference state dict / ControlNetHED.pth names (`norm`, `block{1..5}.convs.{i}.*`, `block{1..5}.projection.*`);
         other floating-point tensors are ignored unless strict."""
-        for k, v in sd.items():
-            if not torch.is_floating_point(v):
-                continue
-            self.load_tensor(k, v, strict)
-        self._finalize()
+        super().load_state_dict(sd, strict)
         self.size = (0, 0)
         return self
 

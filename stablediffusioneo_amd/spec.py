@@ -425,12 +425,9 @@ CLIP_TINY21 = ClipConfig(vocab=1000, positions=77, width=128, layers=3, heads=4,
 NS_CLIP = "cond_stage_model.transformer.text_model."
 
 
-def param_spec_clip(cfg: ClipConfig = CLIP_SD15) -> "OrderedDict[str, tuple]":
-    """Tensor names below `text_model.` and shapes of the HuggingFace CLIPTextModel state dict."""
+def _clip_layers(spec, cfg):
+    """`encoder.layers.{i}.*` of a CLIP tower (text or vision: cfg has layers, width and ffn), weight then bias per projection"""
     w, f = cfg.width, cfg.ffn
-    spec = OrderedDict()
-    spec["embeddings.token_embedding.weight"] = (cfg.vocab, w)
-    spec["embeddings.position_embedding.weight"] = (cfg.positions, w)
     for i in range(cfg.layers):
         p = f"encoder.layers.{i}."
         for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
@@ -444,6 +441,15 @@ def param_spec_clip(cfg: ClipConfig = CLIP_SD15) -> "OrderedDict[str, tuple]":
         spec[p + "mlp.fc2.bias"] = (w,)
         spec[p + "layer_norm2.weight"] = (w,)
         spec[p + "layer_norm2.bias"] = (w,)
+
+
+def param_spec_clip(cfg: ClipConfig = CLIP_SD15) -> "OrderedDict[str, tuple]":
+    """Tensor names below `text_model.` and shapes of the HuggingFace CLIPTextModel state dict."""
+    w = cfg.width
+    spec = OrderedDict()
+    spec["embeddings.token_embedding.weight"] = (cfg.vocab, w)
+    spec["embeddings.position_embedding.weight"] = (cfg.positions, w)
+    _clip_layers(spec, cfg)
     spec["final_layer_norm.weight"] = (w,)
     spec["final_layer_norm.bias"] = (w,)
     return spec
@@ -476,27 +482,16 @@ NS_CLIP_VISION = "image_encoder.vision_model."      # seed namespace of the synt
 
 def param_spec_clip_vision(cfg: ClipVisionConfig = CLIP_VISION_H14) -> "OrderedDict[str, tuple]":
     """Tensor names below `vision_model.` (plus `visual_projection.weight`) and shapes of the HuggingFace
-    CLIPVisionModelWithProjection state dict, in the order `sdeo_clip_vision_weight_info` lists them."""
-    w, f = cfg.width, cfg.ffn
+    CLIPVisionModelWithProjection state dict.  `sdeo_clip_vision_weight_info` lists the same tensors, with the stacked q | k | v
+    weights of a layer in front of their biases (as the text tower's registry does)."""
+    w = cfg.width
     spec = OrderedDict()
     spec["embeddings.class_embedding"] = (w,)
     spec["embeddings.patch_embedding.weight"] = (w, 3, cfg.patch, cfg.patch)
     spec["embeddings.position_embedding.weight"] = (cfg.tokens, w)
     spec["pre_layrnorm.weight"] = (w,)
     spec["pre_layrnorm.bias"] = (w,)
-    for i in range(cfg.layers):
-        p = f"encoder.layers.{i}."
-        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-            spec[p + f"self_attn.{n}.weight"] = (w, w)
-            spec[p + f"self_attn.{n}.bias"] = (w,)
-        spec[p + "layer_norm1.weight"] = (w,)
-        spec[p + "layer_norm1.bias"] = (w,)
-        spec[p + "mlp.fc1.weight"] = (f, w)
-        spec[p + "mlp.fc1.bias"] = (f,)
-        spec[p + "mlp.fc2.weight"] = (w, f)
-        spec[p + "mlp.fc2.bias"] = (w,)
-        spec[p + "layer_norm2.weight"] = (w,)
-        spec[p + "layer_norm2.bias"] = (w,)
+    _clip_layers(spec, cfg)
     spec["post_layernorm.weight"] = (w,)
     spec["post_layernorm.bias"] = (w,)
     spec["visual_projection.weight"] = (cfg.proj, w)

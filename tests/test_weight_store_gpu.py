@@ -1,7 +1,8 @@
-"""The weight store of csrc/handle_common.h, pinned from its three doors: SdeoRuntime (csrc/net_weights.hip), ClipRuntime (csrc/clip.hip) and
-HedRuntime (csrc/hed.hip) run ONE contract: the registry equals the spec.param_spec_* inventory, unknown / mis-shaped tensors are
-refused with the door's own function name, finalize reports missing tensors by name in registry order, and a tensor re-loaded after
-finalize (the upload buffer was freed; net_weights.hip rebuilds its LayerNorm folds and composed matrices) leaves the output bit-identical.
+"""The weight store of csrc/handle_common.h, pinned from its five doors: SdeoRuntime (csrc/net_weights.hip), ClipRuntime (csrc/clip.hip),
+ClipVisionRuntime (csrc/clip_vision.hip), ResamplerRuntime (csrc/resampler.hip) and HedRuntime (csrc/hed.hip) run ONE contract: the
+registry equals the spec.param_spec_* inventory, unknown / mis-shaped tensors are refused with the door's own function name, finalize
+reports missing tensors by name in registry order, and a tensor re-loaded after finalize (the upload buffer was freed;
+net_weights.hip rebuilds its LayerNorm folds and composed matrices) leaves the output bit-identical.
 Every error path returns from host-side validation before any launch."""
 import ctypes as C
 
@@ -9,7 +10,7 @@ import pytest
 import torch
 
 from stablediffusioneo_amd import _lib, spec as S
-from stablediffusioneo_amd.runtime import ClipRuntime, HedRuntime, SdeoRuntime
+from stablediffusioneo_amd.runtime import ClipRuntime, ClipVisionRuntime, HedRuntime, ResamplerRuntime, SdeoRuntime
 from tests.common import make_inputs
 from tests.encoder_inputs import make_image_u8
 
@@ -27,6 +28,18 @@ def clip_forward(rt):
     return [rt.configure(1).encode(torch.randint(0, S.CLIP_TINY.vocab, (1, S.CLIP_TINY.positions), generator=g)).clone()]
 
 
+def clip_vision_forward(rt):
+    g = torch.Generator(device="cpu")
+    g.manual_seed(6)
+    return [t.clone() for t in rt.encode_pixels(torch.randn((1, 3, 56, 56), generator=g))]
+
+
+def resampler_forward(rt):
+    g = torch.Generator(device="cpu")
+    g.manual_seed(8)
+    return [rt.project(torch.randn((1, 17, 64), generator=g)).clone()]
+
+
 def hed_forward(rt):
     out = rt.detect(make_image_u8(1, 32, 48, seed=7)[0], edges=True, side=True)
     return [out["edges"].clone()] + [m.clone() for m in out["side"]]
@@ -39,6 +52,12 @@ DOORS = {
              S.NS_UNET + "input_blocks.1.1.transformer_blocks.0.attn1.to_q.weight", sdeo_forward),
     "clip": (lambda: ClipRuntime(S.CLIP_TINY), lambda: S.param_spec_clip(S.CLIP_TINY),
              lambda spec: S.synth_state_dict(spec, 0, S.NS_CLIP), "sdeo_clip_load_weight", "encoder.layers.0.mlp.fc1.weight", clip_forward),
+    "clip_vision": (lambda: ClipVisionRuntime(S.CLIP_VISION_TINY, want_hidden=True), lambda: S.param_spec_clip_vision(S.CLIP_VISION_TINY),
+                    lambda spec: S.synth_clip_vision_state_dict(S.CLIP_VISION_TINY, 0), "sdeo_clip_vision_load_weight",
+                    "encoder.layers.0.mlp.fc1.weight", clip_vision_forward),
+    "resampler": (lambda: ResamplerRuntime(S.RESAMPLER_TINY), lambda: S.param_spec_resampler(S.RESAMPLER_TINY),
+                  lambda spec: S.synth_resampler_state_dict(S.RESAMPLER_TINY, 0), "sdeo_resampler_load_weight", "layers.0.0.to_kv.weight",
+                  resampler_forward),
     "hed": (lambda: HedRuntime(), S.param_spec_hed, lambda spec: S.synth_hed_state_dict(0), "sdeo_hed_load_weight",
             "block2.convs.0.weight", hed_forward),
 }
@@ -61,8 +80,8 @@ def test_weight_store_contract(door):
     make, inventory, synth, fn, matrix, forward = DOORS[door]
     rt, spec = make(), inventory()
 
-    # registry == inventory in names and shapes; `names` is the registry's own order (CLIP registers its stacked q | k | v weights
-    # before their biases, the inventory lists weight and bias per projection)
+    # registry == inventory in names and shapes; `names` is the registry's own order (both CLIP towers register their stacked q | k | v
+    # weights before their biases, the inventory lists weight and bias per projection)
     got = rt.expected_weights()
     names = list(got)
     assert sorted(names) == sorted(spec)
@@ -73,13 +92,14 @@ def test_weight_store_contract(door):
     rc, msg = raw_load(rt, fn, "no.such.tensor", (3,), strict=True)
     assert rc != 0 and "unexpected tensor" in msg and msg.startswith(fn + ":"), msg
 
-    # known name, wrong rank / wrong extent
-    shape = tuple(spec[matrix])
-    for bad in (shape + (1,), shape[:-1]):
-        rc, msg = raw_load(rt, fn, matrix, bad, strict=True)
-        assert rc != 0 and "dims, expected" in msg and matrix in msg, msg
-    rc, msg = raw_load(rt, fn, matrix, shape[:-1] + (shape[-1] + 1,), strict=True)
-    assert rc != 0 and matrix in msg and "expected" in msg and "dims, expected" not in msg, msg
+    # known name, wrong rank / wrong extent; for the vision door also on the patch embedding, whose loader is the door's own
+    for tensor in (matrix,) + (("embeddings.patch_embedding.weight",) if door == "clip_vision" else ()):
+        shape = tuple(spec[tensor])
+        for bad in (shape + (1,), shape[:-1]):
+            rc, msg = raw_load(rt, fn, tensor, bad, strict=True)
+            assert rc != 0 and "dims, expected" in msg and tensor in msg, msg
+        rc, msg = raw_load(rt, fn, tensor, shape[:-1] + (shape[-1] + 1,), strict=True)
+        assert rc != 0 and tensor in msg and "expected" in msg and "dims, expected" not in msg, msg
 
     # finalize with nothing loaded: the first five registry names, in order
     with pytest.raises(_lib.SdeoError) as ei:
