@@ -843,7 +843,8 @@ static int launch_generic(const KP& kp, int tiles, hipStream_t stream) {
 }
 
 // The tile table (TileCfg: conv_inl.h).  Adding a tile = one row here (appended: indices are public) + its index in the tests' tile
-// lists, which tests/test_tile_table_cpu.py holds against this table.  CAPS: CAP_LIGHT makes the row the four-wave instantiation;
+// lists, which tests/test_tile_table_cpu.py holds against this table (a TK_GENERIC row: FALLBACK_TILES / TILE_BM of
+// tests/fallback_cases.py, run by tests/test_fallback_kernel_cpu.py and tests/test_fallback_kernel_gpu.py).  CAPS: CAP_LIGHT makes the row the four-wave instantiation;
 // CAP_W8 / CAP_MX add the fp8-weight / block-scaled-fp8 instantiation of the same shape (wave-specialised, no folded Upsample, KPB 1).
 // Epilogue kinds (EpiKind; KINDS = the mask of K_* bits of a row): a row has the EPI_DIRECT form of its plain fp16 instantiation when
 // the networks can plan it unsplit: the rows the heuristic may pick (no CAP_LIGHT / CAP_GROUPED / CAP_HALO) and the rows the

@@ -1,7 +1,8 @@
 """CPU-side checks of the conv / GEMM tile table (csrc/conv_gemm.hip: kTiles), read through sdeo_debug_tile_info:
 
 * the tile lists the GPU tests force (DMA_TILES / GROUPED_TILES / HALO_TILES in tests/test_ops_gpu.py, W8_TILES in
-  tests/test_fp8_gpu.py, MX_TILES in tests/test_mx_gpu.py) are exactly what the table says, so a tile added without coverage fails here;
+  tests/test_fp8_gpu.py, MX_TILES in tests/test_mx_gpu.py, FALLBACK_TILES in tests/fallback_cases.py for the TK_GENERIC rows) are
+  exactly what the table says, so a tile added without coverage fails here;
 * the planner still plans what tests/golden/plan_snapshot.json recorded (tests/golden/make_plan_snapshot.py): for every problem
   of the snapshot, the (tile, split-K) under every forced tile x forced split-K, and the kernel name of the convs.
 
@@ -80,11 +81,13 @@ def test_table_is_self_consistent(lib):
 
 
 def test_gpu_test_tile_lists_cover_the_table(lib):
+    from tests.fallback_cases import FALLBACK_TILES
     from tests.test_fp8_gpu import W8_TILES
     from tests.test_mx_gpu import MX_TILES
     from tests.test_ops_gpu import DMA_TILES, GROUPED_TILES, HALO_TILES
     table = tile_table(lib)
     assert DMA_TILES == [i for i, t in enumerate(table) if t["kind"] == TK_DMA]
+    assert FALLBACK_TILES == [i for i, t in enumerate(table) if t["kind"] == TK_GENERIC]
     assert GROUPED_TILES == with_cap(table, CAP_GROUPED)
     assert W8_TILES == with_cap(table, CAP_W8)
     assert MX_TILES == with_cap(table, CAP_MX)
