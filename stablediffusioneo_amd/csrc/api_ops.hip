@@ -198,6 +198,22 @@ int sdeo_conv2d_pad_nhwc_f16(void* y, const void* x, const void* w_krsc, const f
   return conv_gemm(p, S(stream));
 }
 
+// sdeo_conv2d_pad_nhwc_f16 on views: x a channel block of [pixels][ldx], y / res column blocks of [M][ldy] / [M][ldres] (the concat
+// buffers of csrc/net_build.hip).  What a view may be is the launcher's to say (prepare): nothing about ldx / ldy / ldres is checked here.
+int sdeo_debug_conv2d_view_f16(void* y, int ldy, const void* x, int ldx, const void* w_krsc, const float* bias, const float* bias2,
+                               const void* res, int ldres, int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x,
+                               int pad_before, int pad_after, int act, float scale, void* workspace, size_t workspace_bytes, void* stream) {
+  const Fp8Arm arm = disarm_fp8();
+  SDEO_CHECK(pad_before >= 0 && pad_after >= 0, "conv2d_view: negative padding (%d, %d)", pad_before, pad_after);
+  ConvGemm p;
+  if (int rc = fill_conv(p, n, h, w, cin, cout, ksize, stride, upsample2x, pad_before, pad_after)) return rc;
+  p.x = (const f16*)x; p.w = (const f16*)w_krsc; p.y = (f16*)y; p.bias = bias; p.bias2 = bias2; p.res = (const f16*)res;
+  p.ldx = ldx; p.ldy = ldy; p.ldres = ldres;
+  p.act = act; p.scale = scale; p.workspace = (float*)workspace; p.workspace_bytes = workspace_bytes;
+  take_fp8(p, arm);
+  return conv_gemm(p, S(stream));
+}
+
 // conv2d whose epilogue emits the GroupNorm partials of its output, followed by the normalise-only GroupNorm that consumes them
 // (the [conv -> GroupNorm] pairs of the networks, csrc/net_build.hip).  *slots = entries per image the plan writes; 0 = this shape's plan
 // cannot emit them (nothing is launched then).  partials >= n * slots * groups * 2 floats (+ n * groups * 2 when slots > 128).

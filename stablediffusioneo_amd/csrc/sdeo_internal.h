@@ -126,6 +126,12 @@ int sdeo_debug_gemm_res_rows_f16(void* y, int ldy, const void* x, int ldx, const
 int sdeo_debug_conv2d_ex_f16(void* y, const void* x, const void* w_krsc, const float* bias, const void* res, int res_rows, int n, int h,
                              int w, int cin, int cout, int ksize, float* stats, int stats_ld, int* strips_out, const float* ln_stats,
                              const float* ln_s, int ln_ld, int ln_strips, void* workspace, size_t workspace_bytes, void* stream);
+/* conv2d_view: sdeo_conv2d_pad_nhwc_f16 on views of wider buffers, as csrc/net_build.hip runs the decoder convs into a concat buffer:
+ *   x is a channel block of [n * h * w][ldx], y and res are column blocks of [n * ho * wo][ldy] / [ldres] (tests).  The leading dimensions
+ *   and the alignment of the three pointers are checked by the launcher alone (csrc/conv_gemm.hip: prepare) */
+int sdeo_debug_conv2d_view_f16(void* y, int ldy, const void* x, int ldx, const void* w_krsc, const float* bias, const float* bias2,
+                               const void* res, int ldres, int n, int h, int w, int cin, int cout, int ksize, int stride, int upsample2x,
+                               int pad_before, int pad_after, int act, float scale, void* workspace, size_t workspace_bytes, void* stream);
 int sdeo_debug_attention_qb_f16(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int b,
                                 int q_batches, int heads, int tq, int tk, int tk_stride, int v_batch_stride, int d, float scale, void* stream);
 /* attention2_qb: sdeo_attention2_f16 with the same query sharing (k, v, k2, v2 and o hold b batches) */
@@ -136,7 +142,7 @@ int sdeo_debug_attention2_qb_f16(void* o, int ldo, const void* q, int ldq, const
 
 /* fp8 weight pack at op level (tests): quantise [rows][cols] fp16 in place to its dequantised values, codes -> q, scales -> scale;
  * sdeo_debug_next_weights_fp8 makes the NEXT conv / GEMM call of this thread (sdeo_gemm_f16, sdeo_conv2d_nhwc_f16, sdeo_conv2d_pad_nhwc_f16,
- * sdeo_debug_gemm_stats_f16, _gemm_res_rows_f16, _gemm_ln_f16, _conv2d_ex_f16, _conv2d_gn_f16, _conv2d_gn_b2_f16) stream these codes
+ * sdeo_debug_gemm_stats_f16, _gemm_res_rows_f16, _gemm_ln_f16, _conv2d_ex_f16, _conv2d_view_f16, _conv2d_gn_f16, _conv2d_gn_b2_f16) stream these codes
  * (K-contiguous bytes, same [N][K] / KRSC layout) instead of its fp16 weight argument; sdeo_debug_gemm_multi_f16 and the
  * block-scaled entries drop it unused.  Every one of them disarms first, so a refused call leaves nothing armed */
 /* block-scaled fp8 (e4m3fn codes + one e8m0 scale per 32 elements of a row) at op level: the pack of an fp16 [rows][cols] matrix

@@ -195,6 +195,41 @@ def conv2d_pad_nhwc(x, w_krsc, pad_before, pad_after, bias=None, bias2=None, res
     return y
 
 
+def _pixel_ld(t, what):
+    """pixel stride, in elements, of an (N,H,W,C) fp16 view with unit channel stride and densely stacked pixels: a contiguous tensor
+    or a channel block of a wider [pixels][ld] buffer"""
+    n, h, w, _ = t.shape
+    ld = t.stride(2)
+    if not (t.dtype == torch.float16 and t.stride(3) == 1 and (h == 1 or t.stride(1) == w * ld) and (n == 1 or t.stride(0) == h * w * ld)):
+        raise _lib.SdeoError(f"conv2d_view: {what} must be fp16 NHWC with unit channel stride and densely stacked pixels "
+                             f"(shape {tuple(t.shape)}, strides {t.stride()})")
+    return ld
+
+
+def conv2d_view(x, w_krsc, pad_before, pad_after, out, bias=None, bias2=None, res=None, stride=1, upsample2x=False, act=0, scale=1.0,
+                w8=None):
+    """conv2d_pad_nhwc on views (sdeo_debug_conv2d_view_f16): x an (N,H,W,Cin) channel block of a wider [pixels][ldx] buffer, out and
+    res (N,Ho,Wo,Cout) column blocks of wider [rows][ldy] / [rows][ldres] buffers, as the networks write a conv into a concat buffer.
+    The leading dimensions are the views' pixel strides; which of them the kernels can address is the launcher's decision (SdeoError)."""
+    lib = _lib.load()
+    _need_cuda(x, w_krsc, out, res)
+    n, h, w, cin = x.shape
+    cout, k, _, cin_w = w_krsc.shape
+    assert cin == cin_w and w_krsc.is_contiguous()
+    hv, wv = (2 * h, 2 * w) if upsample2x else (h, w)
+    ho = (hv + pad_before + pad_after - k) // stride + 1
+    wo = (wv + pad_before + pad_after - k) // stride + 1
+    assert tuple(out.shape) == (n, ho, wo, cout) and (res is None or tuple(res.shape) == (n, ho, wo, cout)), (tuple(out.shape), (n, ho, wo, cout))
+    ldx, ldy, ldres = _pixel_ld(x, "x"), _pixel_ld(out, "out"), 0 if res is None else _pixel_ld(res, "res")
+    args = (n, h, w, cin, cout, k, stride, int(upsample2x), pad_before, pad_after)
+    nb = lib.sdeo_conv2d_pad_workspace_bytes(*args)
+    ws = _ws(nb if w8 is None else max(nb, 64 << 20), x.device)
+    _arm_fp8(lib, w8)
+    check(lib.sdeo_debug_conv2d_view_f16(ptr(out), ldy, ptr(x), ldx, ptr(w_krsc), ptr(bias), ptr(bias2), ptr(res), ldres, *args, act, scale,
+                                         ptr(ws), ws.numel(), cur_stream()), "conv2d_view")
+    return out
+
+
 def conv2d_gn(x, w_krsc, gamma, beta, bias=None, res=None, stride=1, upsample2x=False, groups=32, eps=1e-5, swish=False, bias2=None,
               w8=None, want_partials=False):
     """[conv2d whose epilogue emits the GroupNorm partials of its output] -> [normalise-only GroupNorm]: returns (y, GroupNorm(y), slots)

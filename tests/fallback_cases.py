@@ -37,17 +37,18 @@ def cdiv(a, b):
     return (a + b - 1) // b
 
 
-def expected_splitk(k, sk):
-    """the factor the planner runs when sk is forced (csrc/conv_gemm.hip: make_plan): clipped to the number of K-steps, then
-    re-derived from the slab length so that no slab is empty"""
-    nk = cdiv(k, BK)
+def expected_splitk(k, sk, bk=BK):
+    """the factor the planner runs when sk is forced (csrc/conv_gemm.hip: make_plan): clipped to the number of K-steps (of bk: 32
+    here, 64 on the LDS-DMA and halo rows, tests/conv_geometry_cases.py), then re-derived from the slab length so that no slab is
+    empty"""
+    nk = cdiv(k, bk)
     return cdiv(nk, cdiv(nk, min(sk, nk)))
 
 
-def slabs(k, sk):
+def slabs(k, sk, bk=BK):
     """K-steps of each slab of a launch forced to split-K sk"""
-    nk = cdiv(k, BK)
-    per = cdiv(nk, expected_splitk(k, sk))
+    nk = cdiv(k, bk)
+    per = cdiv(nk, expected_splitk(k, sk, bk))
     return [min(per, nk - z) for z in range(0, nk, per)]
 
 
