@@ -212,6 +212,16 @@ int sdeo_oihw_f32_to_krsc_f16(void* y, const float* w, int o, int i, int r, int 
  * pointers (staged with hipMemcpyDefault).  rank 1..1024, scale finite.  Allocates, synchronises `stream` and frees: not capturable. */
 int sdeo_lora_merge_f16(void* w, int kind, int out, int in, int k, int ipad, const float* down, const float* up, int rank, float scale,
                         void* stream);
+/* The kernels of sdeo_loha_apply / sdeo_lokr_apply on one stored tensor (csrc/lora.hip); w, kind, out, in, k, ipad as above, the forms
+ * and the operands as defined at sdeo_loha_apply below: fp32, host or device pointers, in the layout the file holds them, absent
+ * operands null.  w <- fp16(fp32(w) + scale * dW), the multiplier alpha / rank already inside `scale`.  Every refusal (a null w, a bad
+ * kind / shape, a missing or mixed operand set, a rank outside 1..1024, factor shapes that do not fit the tensor, a non-finite scale)
+ * comes before any device call.  Allocate, synchronise `stream` and free: not capturable. */
+int sdeo_loha_merge_f16(void* w, int kind, int out, int in, int k, int ipad, const float* w1_a, const float* w1_b, const float* w2_a,
+                        const float* w2_b, const float* t1, const float* t2, int rank, float scale, void* stream);
+int sdeo_lokr_merge_f16(void* w, int kind, int out, int in, int k, int ipad, const float* w1, const float* w1_a, const float* w1_b, int rank1,
+                        const float* w2, const float* w2_a, const float* w2_b, const float* t2, int rank2, int out_l, int in_m, float scale,
+                        void* stream);
 
 /* ------------------------------------------------------------------ net-level entry points */
 
@@ -553,6 +563,43 @@ int sdeo_lora_clear(sdeo_handle h);
 int sdeo_lora_touched(sdeo_handle h);
 int sdeo_read_weight(sdeo_handle h, const char* name, float* out);
 
+/* LoHa and LoKr adapters (LyCORIS algo=loha / algo=lokr), merged like sdeo_lora_apply: in place, the first write saved, the same
+ * commit / clear / touched / read_weight.  The definitions below are this library's contract; they are not
+ * pinned to upstream code.  The target weight is W with shape [O][I] or [O][I][kh][kw]; J = I*kh*kw and kk = kh*kw (kk = 1 for a
+ * matrix).  The merged weight is W + scale * dW, rounded once to fp16; the caller folds the multiplier (alpha / r, or 1) into scale.
+ *
+ * LoHa (plain).  Leaves: hada_w1_a [O][r], hada_w1_b [r][J], hada_w2_a [O][r], hada_w2_b [r][J], optional alpha.
+ *   dW = (w1_a @ w1_b) (.) (w2_a @ w2_b), viewed as W.  Multiplier: alpha / r, or 1 without alpha.
+ * LoHa, Tucker form (convs with kk > 1 only).  Extra leaves: hada_t1, hada_t2, both [r][r][kh][kw].  The four factors are then
+ *   transposed against the plain form: hada_wX_a [r][O] and hada_wX_b [r][I].
+ *   PX[o][c][y][x] = sum_i sum_j tX[i][j][y][x] * wX_a[i][o] * wX_b[j][c];  dW = P1 (.) P2.
+ * LoKr.  O = Ol*Ok and I = Im*In.  The factors are read from the tensor shapes (here: out_l = Ol, in_m = Im).
+ *   w1 is [Ol][Im].  It comes either as the leaf lokr_w1, or as lokr_w1_a [Ol][r] @ lokr_w1_b [r][Im].
+ *   w2 is [Ok][In*kk].  It comes in one of three forms: the leaf lokr_w2, shape [Ok][In] or [Ok][In][kh][kw];
+ *     lokr_w2_a [Ok][r] @ lokr_w2_b [r][In*kk];  the Tucker form: lokr_t2 [r][r][kh][kw], lokr_w2_a [r][Ok], lokr_w2_b [r][In],
+ *     contracted like LoHa's.
+ *   dW[ol*Ok + ok][(im*In + in)*kk + s] = w1[ol][im] * w2[ok][in*kk + s].  For a matrix this is torch.kron(w1, w2).  For a conv it is
+ *     torch.kron(w1[:, :, None, None], w2).
+ *   Multiplier: alpha / r.  r is the row count of lokr_w2_b if present, else of lokr_w1_b.  Without alpha, or with both factors
+ *     full, the multiplier is 1.
+ * The key set decides the form.  A module is merged only when its leaves are exactly one complete form.
+ *
+ * Arithmetic: fp32 throughout.  LoHa: two fmaf chains in rank order and one multiply.  LoKr: one gathered w1 value times either a
+ * loaded w2 value or one fmaf chain over w2's rank.  w1 = w1_a @ w1_b and a Tucker core folded into its b factor
+ * (b_eff[i][(c,y,x)] = sum_j t[i][j][y][x] * b[j][c], chain in j order) are written as fp32 by a pre-pass.  Then fmaf(scale, dW, fp32(W)),
+ * rounded once; an element whose update is exactly zero is not stored; pad channels are neither read nor written.
+ *
+ * Operands: fp32, host or device pointers, in the layout above; an absent operand is a null pointer.  sdeo_loha_apply: t1 and t2 both
+ * null (plain) or both given (Tucker).  sdeo_lokr_apply: w1, or w1_a and w1_b with rank1; w2, or w2_a and w2_b with rank2, t2 given
+ * for the Tucker form; rank1 / rank2 are ignored where the factor comes whole.  Refused before any device call, each with its own
+ * message, the handle untouched: a null name or a missing / mixed operand set, an unknown name, a bias / norm vector, a rank outside
+ * 1..1024, a non-finite scale, weights not finalized, an fp8-weight handle, a to_k_ip / to_v_ip matrix, and factor shapes that do not
+ * fit the tensor (out_l / in_m not dividing out / in, a Tucker core on a matrix or a 1 x 1 conv). */
+int sdeo_loha_apply(sdeo_handle h, const char* name, const float* w1_a, const float* w1_b, const float* w2_a, const float* w2_b,
+                    const float* t1, const float* t2, int rank, float scale, void* stream);
+int sdeo_lokr_apply(sdeo_handle h, const char* name, const float* w1, const float* w1_a, const float* w1_b, int rank1, const float* w2,
+                    const float* w2_a, const float* w2_b, const float* t2, int rank2, int out_l, int in_m, float scale, void* stream);
+
 /* ------------------------------------------------------------------ text encoder
  * FrozenCLIPEmbedder.forward (ldm/modules/encoders/modules.py:123-141): token ids -> CLIPTextModel ->
  * last_hidden_state [batch][positions][width].  The tokenizer stays on the host (it needs the vocabulary
@@ -581,10 +628,16 @@ int sdeo_clip_configure(sdeo_clip_handle h, int batch);
  * vocabulary are clamped */
 int sdeo_clip_encode(sdeo_clip_handle h, const int32_t* tokens, int batch, float* out, void* stream);
 size_t sdeo_clip_device_bytes(sdeo_clip_handle h);
-/* LoRA adapters on the text tower: sdeo_lora_apply / _commit / _clear / _touched and sdeo_read_weight on the CLIP handle, names as in
+/* LoRA / LoHa / LoKr adapters on the text tower: sdeo_lora_apply / sdeo_loha_apply / sdeo_lokr_apply / _commit / _clear / _touched and
+ * sdeo_read_weight on the CLIP handle, names as in
  * sdeo_clip_weight_info (anything up to and including "text_model." is stripped); q_proj / k_proj / v_proj live inside the stacked qkv
  * matrix.  The tower runs on the raw tensors and caches nothing between encodes, so commit has nothing to rebuild or invalidate. */
 int sdeo_clip_lora_apply(sdeo_clip_handle h, const char* name, const float* down, const float* up, int rank, float scale, void* stream);
+int sdeo_clip_loha_apply(sdeo_clip_handle h, const char* name, const float* w1_a, const float* w1_b, const float* w2_a, const float* w2_b,
+                         const float* t1, const float* t2, int rank, float scale, void* stream);
+int sdeo_clip_lokr_apply(sdeo_clip_handle h, const char* name, const float* w1, const float* w1_a, const float* w1_b, int rank1,
+                         const float* w2, const float* w2_a, const float* w2_b, const float* t2, int rank2, int out_l, int in_m, float scale,
+                         void* stream);
 int sdeo_clip_lora_commit(sdeo_clip_handle h);
 int sdeo_clip_lora_clear(sdeo_clip_handle h);
 int sdeo_clip_lora_touched(sdeo_clip_handle h);

@@ -147,7 +147,7 @@ class ControlLDM:
         return self
 
     def load_lora(self, lora, unet_scale=1.0, te_scale=None, strict=False, commit=True):
-        """Merge a kohya-ss LoRA / LoCon adapter (a path or a dict) into the weights on the device (`stablediffusioneo_amd.lora.apply_lora`);
+        """Merge a kohya-ss LoRA / LoCon or LyCORIS LoHa / LoKr adapter (a path or a dict) into the weights on the device (`stablediffusioneo_amd.lora.apply_lora`);
         returns the keys it did not understand."""
         from ..lora import apply_lora
         return apply_lora(self, lora, unet_scale=unet_scale, te_scale=te_scale, strict=strict, commit=commit)

@@ -143,6 +143,20 @@ int sdeo_clip_lora_apply(sdeo_clip_handle h, const char* name, const float* down
                           h->finalized ? nullptr : "weights not finalized (call sdeo_clip_finalize_weights)", reinterpret_cast<hipStream_t>(stream));
 }
 
+int sdeo_clip_loha_apply(sdeo_clip_handle h, const char* name, const float* w1_a, const float* w1_b, const float* w2_a, const float* w2_b,
+                         const float* t1, const float* t2, int rank, float scale, void* stream) {
+  SDEO_CHECK(h, "sdeo_clip_loha_apply: null handle");
+  return h->ws.loha_apply("sdeo_clip_loha_apply", name, clip_key(name), w1_a, w1_b, w2_a, w2_b, t1, t2, rank, scale,
+                          h->finalized ? nullptr : "weights not finalized (call sdeo_clip_finalize_weights)", reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdeo_clip_lokr_apply(sdeo_clip_handle h, const char* name, const float* w1, const float* w1_a, const float* w1_b, int rank1, const float* w2,
+                         const float* w2_a, const float* w2_b, const float* t2, int rank2, int out_l, int in_m, float scale, void* stream) {
+  SDEO_CHECK(h, "sdeo_clip_lokr_apply: null handle");
+  return h->ws.lokr_apply("sdeo_clip_lokr_apply", name, clip_key(name), w1, w1_a, w1_b, rank1, w2, w2_a, w2_b, t2, rank2, out_l, in_m, scale,
+                          h->finalized ? nullptr : "weights not finalized (call sdeo_clip_finalize_weights)", reinterpret_cast<hipStream_t>(stream));
+}
+
 int sdeo_clip_lora_commit(sdeo_clip_handle h) {
   SDEO_CHECK(h, "sdeo_clip_lora_commit: null handle");
   SDEO_CHECK(h->finalized, "sdeo_clip_lora_commit: weights not finalized (call sdeo_clip_finalize_weights)");

@@ -164,32 +164,40 @@ struct WeightStore {
   }
 
   // Every refusal happens before the first device call and leaves the store untouched.  not_ready: why the handle cannot take an
-  // adapter now (null: it can).  down [rank][in * kh * kw] / up [out][rank] fp32, host or device pointers (hipMemcpyDefault, as load).
-  // Synchronises `stream` (the staging buffer is reused by the next apply).
-  int lora_apply(const char* who, const char* name, const std::string& key, const float* down, const float* up, int rank, float scale,
-                 const char* not_ready, hipStream_t stream) {
-    SDEO_CHECK(name && down && up, "%s: null argument", who);
+  // adapter now (null: it can).  The three formats share the refusals, the staging buffer and the first-write backup:
+  //   adapter_entry   null argument, unknown name, vector                          (then the format's own: rank, operand set, shapes)
+  //   adapter_ready   non-finite scale, handle not ready, non-square filter
+  //   adapter_stage   the staging buffer grown to `floats`;  adapter_backup: the tensor's raw bytes saved on its first write
+  int adapter_entry(const char* who, const char* name, const std::string& key, bool operands, int* entry) const {
+    SDEO_CHECK(name && operands, "%s: null argument", who);
     auto it = index.find(key);
     SDEO_CHECK(it != index.end(), "%s: unknown tensor '%s'", who, name);
-    WEntry& w = entries[it->second];
+    const WEntry& w = entries[it->second];
     SDEO_CHECK(w.kind == W_LINEAR || w.kind == W_CONV || w.kind == W_GEGLU_W, "%s: %s is a vector (bias / norm), an adapter applies to a matrix or a conv weight", who, name);
-    SDEO_CHECK(rank >= 1 && rank <= 1024, "%s: rank %d out of range (1..1024)", who, rank);
+    *entry = it->second;
+    return 0;
+  }
+  int adapter_ready(const char* who, const char* name, const WEntry& w, float scale, const char* not_ready) const {
     SDEO_CHECK(scale == scale && scale - scale == 0.f, "%s: scale is not finite", who);
     SDEO_CHECK(!not_ready, "%s: %s", who, not_ready);
-    const int O = (int)w.dims[0], I = (int)w.dims[1], k = w.kind == W_CONV ? (int)w.dims[2] : 1;
     SDEO_CHECK(w.kind != W_CONV || w.dims[2] == w.dims[3], "%s: %s has a %lld x %lld filter (square filters only)", who, name, (long long)w.dims[2], (long long)w.dims[3]);
-    const size_t nd = (size_t)rank * I * k * k, nu = (size_t)O * rank, need = (nd + nu) * sizeof(float);
+    return 0;
+  }
+  int adapter_stage(size_t floats) {
+    const size_t need = floats * sizeof(float);
     if (need > lora_stage_bytes) {
       lora_release_stage();
       SDEO_HIP(hipMalloc((void**)&lora_stage, need));
       lora_stage_bytes = need;
     }
-    SDEO_HIP(hipMemcpy(lora_stage, down, nd * sizeof(float), hipMemcpyDefault));
-    SDEO_HIP(hipMemcpy(lora_stage + nd, up, nu * sizeof(float), hipMemcpyDefault));
+    return 0;
+  }
+  int adapter_backup(const char* who, const char* name, int entry, hipStream_t stream) {
+    const WEntry& w = entries[entry];
     bool saved = false;
-    for (auto& b : lora_backups) saved = saved || b.entry == it->second;
+    for (auto& b : lora_backups) saved = saved || b.entry == entry;
     if (!saved) {
-      LoraBackup b{it->second, nullptr, raw_bytes(w)};
+      LoraBackup b{entry, nullptr, raw_bytes(w)};
       if (hipMalloc(&b.data, b.bytes) != hipSuccess) return fail("%s: cannot allocate %zu bytes to save %s", who, b.bytes, name);
       if (hipMemcpyAsync(b.data, slab + w.off, b.bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) {
         (void)hipFree(b.data);
@@ -198,9 +206,58 @@ struct WeightStore {
       lora_backups.push_back(b);
       lora_backup_bytes += b.bytes;
     }
+    return 0;
+  }
+
+  // down [rank][in * kh * kw] / up [out][rank] fp32, host or device pointers (hipMemcpyDefault, as load).
+  // Synchronises `stream` (the staging buffer is reused by the next apply).
+  int lora_apply(const char* who, const char* name, const std::string& key, const float* down, const float* up, int rank, float scale,
+                 const char* not_ready, hipStream_t stream) {
+    int e;
+    if (int rc = adapter_entry(who, name, key, down && up, &e)) return rc;
+    WEntry& w = entries[e];
+    SDEO_CHECK(rank >= 1 && rank <= 1024, "%s: rank %d out of range (1..1024)", who, rank);
+    if (int rc = adapter_ready(who, name, w, scale, not_ready)) return rc;
+    const int O = (int)w.dims[0], I = (int)w.dims[1], k = w.kind == W_CONV ? (int)w.dims[2] : 1;
+    const size_t nd = (size_t)rank * I * k * k, nu = (size_t)O * rank;
+    if (int rc = adapter_stage(nd + nu)) return rc;
+    SDEO_HIP(hipMemcpy(lora_stage, down, nd * sizeof(float), hipMemcpyDefault));
+    SDEO_HIP(hipMemcpy(lora_stage + nd, up, nu * sizeof(float), hipMemcpyDefault));
+    if (int rc = adapter_backup(who, name, e, stream)) return rc;
     if (int rc = lora_merge_f16((f16*)(slab + w.off), w.kind, O, I, k, w.ipad, lora_stage, lora_stage + nd, rank, scale, stream)) return rc;
     SDEO_HIP(hipStreamSynchronize(stream));
     return 0;
+  }
+
+  // LoHa / LoKr (kernels.h: LycoOps; include/sdeo.h defines the forms): the operands as the file holds them, host or device pointers.
+  // loha_apply and lokr_apply differ only in how the entry point filled `ops`.
+  int lyco_apply(const char* who, const char* name, const std::string& key, const LycoOps& ops, float scale, const char* not_ready,
+                 hipStream_t stream) {
+    int e;
+    if (int rc = adapter_entry(who, name, key, true, &e)) return rc;
+    WEntry& w = entries[e];
+    const int O = (int)w.dims[0], I = (int)w.dims[1], k = w.kind == W_CONV ? (int)w.dims[2] : 1;
+    if (int rc = lyco_check(who, ops, w.kind, O, I, k)) return rc;
+    if (int rc = adapter_ready(who, name, w, scale, not_ready)) return rc;
+    if (int rc = adapter_stage(lyco_stage_floats(ops, O, I, k))) return rc;
+    if (int rc = adapter_backup(who, name, e, stream)) return rc;
+    if (int rc = lyco_merge_f16((f16*)(slab + w.off), w.kind, O, I, k, w.ipad, ops, lora_stage, scale, stream)) return rc;
+    SDEO_HIP(hipStreamSynchronize(stream));
+    return 0;
+  }
+  int loha_apply(const char* who, const char* name, const std::string& key, const float* w1_a, const float* w1_b, const float* w2_a,
+                 const float* w2_b, const float* t1, const float* t2, int rank, float scale, const char* not_ready, hipStream_t stream) {
+    LycoOps ops;
+    ops.algo = LYCO_LOHA; ops.a1 = w1_a; ops.b1 = w1_b; ops.t1 = t1; ops.a2 = w2_a; ops.b2 = w2_b; ops.t2 = t2; ops.rank1 = ops.rank2 = rank;
+    return lyco_apply(who, name, key, ops, scale, not_ready, stream);
+  }
+  int lokr_apply(const char* who, const char* name, const std::string& key, const float* w1, const float* w1_a, const float* w1_b, int rank1,
+                 const float* w2, const float* w2_a, const float* w2_b, const float* t2, int rank2, int out_l, int in_m, float scale,
+                 const char* not_ready, hipStream_t stream) {
+    LycoOps ops;
+    ops.algo = LYCO_LOKR; ops.w1 = w1; ops.a1 = w1_a; ops.b1 = w1_b; ops.rank1 = rank1; ops.w2 = w2; ops.a2 = w2_a; ops.b2 = w2_b; ops.t2 = t2;
+    ops.rank2 = rank2; ops.out_l = out_l; ops.in_m = in_m;
+    return lyco_apply(who, name, key, ops, scale, not_ready, stream);
   }
 
   // copy every backup back and free it: the raw tensors are bit for bit what load left

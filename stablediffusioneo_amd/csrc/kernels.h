@@ -232,6 +232,26 @@ int geglu_interleave_f32(float* y, const float* x, int H, hipStream_t stream);
 // ([out][in][k][k], k = 1 for a matrix) and stored input channels; down [rank][in * k * k], up [out][rank]: fp32 DEVICE pointers.
 int lora_merge_f16(f16* w, int kind, int out, int in, int k, int ipad, const float* down, const float* up, int rank, float scale,
                    hipStream_t stream);
+// LoHa / LoKr merge into a stored tensor (csrc/lora.hip; include/sdeo.h: sdeo_loha_merge_f16 / sdeo_lokr_merge_f16 define the forms).
+// The operands of one module as the file holds them, fp32, HOST OR DEVICE pointers, absent ones null:
+//   LoHa: a1 / b1 / t1 = hada_w1_a / hada_w1_b / hada_t1, a2 / b2 / t2 likewise, rank1 the rank of both
+//   LoKr: w1 or a1 @ b1 (rank1);  w2 or a2 @ b2 or the Tucker form t2, a2, b2 (rank2);  out_l x in_m the shape of w1
+struct LycoOps {
+  int algo = 0;                      // LYCO_LOHA, LYCO_LOKR
+  const float *w1 = nullptr, *a1 = nullptr, *b1 = nullptr, *t1 = nullptr;
+  const float *w2 = nullptr, *a2 = nullptr, *b2 = nullptr, *t2 = nullptr;
+  int rank1 = 0, rank2 = 0;
+  int out_l = 0, in_m = 0;
+};
+enum { LYCO_LOHA = 1, LYCO_LOKR = 2 };
+// every refusal that depends on the operands and the tensor's shape, no device call: a missing or mixed operand set, a rank outside
+// 1..1024, factor shapes that do not fit [out][in][k][k] (a Tucker core on a matrix included)
+int lyco_check(const char* who, const LycoOps& ops, int kind, int out, int in, int k);
+// floats of staging the merge needs (the operands as given + the composed ones of the pre-pass)
+size_t lyco_stage_floats(const LycoOps& ops, int out, int in, int k);
+// copies the operands into `stage` (a device buffer of lyco_stage_floats), runs the pre-pass and the merge on `stream`; the caller has
+// run lyco_check and synchronises before it reuses the buffer
+int lyco_merge_f16(f16* w, int kind, int out, int in, int k, int ipad, const LycoOps& ops, float* stage, float scale, hipStream_t stream);
 // the inverse of WeightStore::load for the same kinds: out_f32 [out][in][k][k] = fp32 of the stored values, pad channels dropped
 int lora_read_f32(float* out_f32, const f16* w, int kind, int out, int in, int k, int ipad, hipStream_t stream);
 // LayerNorm folded into a Linear (KP::ln_stats): w_out = fp16(w * gamma), s = row sums of w_out, b_out = bias + w beta

@@ -252,6 +252,22 @@ static bool is_ip_weight(const char* name) {
   return n.find(".attn2.to_k_ip.") != std::string::npos || n.find(".attn2.to_v_ip.") != std::string::npos;
 }
 
+// what the three apply entry points share: the handle-level refusals, then `apply(not_ready)` on the store, then the byte count
+template <class F>
+static int adapter_apply(const char* who, sdeo_handle h, const char* name, F apply) {
+  SDEO_CHECK(h, "%s: null handle", who);
+  SDEO_CHECK(!is_ip_weight(name), "%s: %s belongs to the image-prompt adapter: adapters on the ip matrices are not supported "
+             "(the cached image-prompt K / V rely on them never changing)", who, name);
+  const char* not_ready = !h->finalized ? "weights not finalized (call sdeo_finalize_weights)"
+                          : h->fp8.weight_bits == 8 ? "this handle holds fp8 weights (sdeo_set_weight_precision 8): its fp16 copies are the dequantised values, "
+                                                      "not the raw ones, and adapters on it are not supported"
+                                                    : nullptr;
+  const size_t before = h->ws.lora_backup_bytes;
+  const int rc = apply(not_ready);
+  h->device_bytes += h->ws.lora_backup_bytes - before;
+  return rc;
+}
+
 extern "C" {
 
 int sdeo_num_weights(sdeo_handle h) { return h ? (int)h->ws.entries.size() : 0; }
@@ -367,17 +383,24 @@ int sdeo_set_weight_precision(sdeo_handle h, int bits) {
 
 // ---- LoRA adapters: WeightStore does the work, the handle adds what it derives from the raw tensors and its caches
 int sdeo_lora_apply(sdeo_handle h, const char* name, const float* down, const float* up, int rank, float scale, void* stream) {
-  SDEO_CHECK(h, "sdeo_lora_apply: null handle");
-  SDEO_CHECK(!is_ip_weight(name), "sdeo_lora_apply: %s belongs to the image-prompt adapter: adapters on the ip matrices are not supported "
-             "(the cached image-prompt K / V rely on them never changing)", name);
-  const char* not_ready = !h->finalized ? "weights not finalized (call sdeo_finalize_weights)"
-                          : h->fp8.weight_bits == 8 ? "this handle holds fp8 weights (sdeo_set_weight_precision 8): its fp16 copies are the dequantised values, "
-                                                      "not the raw ones, and adapters on it are not supported"
-                                                    : nullptr;
-  const size_t before = h->ws.lora_backup_bytes;
-  const int rc = h->ws.lora_apply("sdeo_lora_apply", name, name ? name : "", down, up, rank, scale, not_ready, S(stream));
-  h->device_bytes += h->ws.lora_backup_bytes - before;
-  return rc;
+  return adapter_apply("sdeo_lora_apply", h, name, [&](const char* not_ready) {
+    return h->ws.lora_apply("sdeo_lora_apply", name, name ? name : "", down, up, rank, scale, not_ready, S(stream));
+  });
+}
+
+int sdeo_loha_apply(sdeo_handle h, const char* name, const float* w1_a, const float* w1_b, const float* w2_a, const float* w2_b,
+                    const float* t1, const float* t2, int rank, float scale, void* stream) {
+  return adapter_apply("sdeo_loha_apply", h, name, [&](const char* not_ready) {
+    return h->ws.loha_apply("sdeo_loha_apply", name, name ? name : "", w1_a, w1_b, w2_a, w2_b, t1, t2, rank, scale, not_ready, S(stream));
+  });
+}
+
+int sdeo_lokr_apply(sdeo_handle h, const char* name, const float* w1, const float* w1_a, const float* w1_b, int rank1, const float* w2,
+                    const float* w2_a, const float* w2_b, const float* t2, int rank2, int out_l, int in_m, float scale, void* stream) {
+  return adapter_apply("sdeo_lokr_apply", h, name, [&](const char* not_ready) {
+    return h->ws.lokr_apply("sdeo_lokr_apply", name, name ? name : "", w1, w1_a, w1_b, rank1, w2, w2_a, w2_b, t2, rank2, out_l, in_m, scale,
+                            not_ready, S(stream));
+  });
 }
 
 int sdeo_lora_commit(sdeo_handle h) {

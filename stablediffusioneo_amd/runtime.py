@@ -138,10 +138,86 @@ class _HandleRuntime:
                 raise ValueError(f"lora_apply({name}): down {tuple(down.shape)} / up {tuple(up.shape)} do not fit the weight {tuple(shape)}: "
                                  f"expected down (rank, {', '.join(str(d) for d in shape[1:])}) and up ({shape[0]}, rank)")
         # (an unknown name or a vector goes through: the library refuses it with its own message)
-        keep = lambda t: t.detach().to(dtype=torch.float32).contiguous() if t.device == self.device else t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-        down, up = keep(down), keep(up)
+        down, up = self._keep(down), self._keep(up)
         self._call("lora_apply", name.encode(), ptr(down), ptr(up), int(down.shape[0]) if down.dim() else 0, C.c_float(float(scale)), cur_stream(),
                    detail=f"({name})")
+
+    def _keep(self, t: Optional[torch.Tensor]):
+        """an adapter operand as contiguous fp32 where it is (this device) or on the host; None stays None (an absent operand)"""
+        if t is None:
+            return None
+        return t.detach().to(dtype=torch.float32).contiguous() if t.device == self.device else t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+
+    def _adapter_shape(self, name: str):
+        """(out, in, kh * kw, the weight's shape) of a matrix / conv weight of this handle, or None (the library refuses the name)"""
+        shape = self._weight_shape(name)
+        if shape is None or len(shape) < 2:
+            return None
+        kk = 1
+        for d in shape[2:]:
+            kk *= d
+        return shape[0], shape[1], kk, tuple(shape)
+
+    def loha_apply(self, name: str, w1_a, w1_b, w2_a, w2_b, t1=None, t2=None, scale: float = 1.0):
+        """Merge scale * (w1_a @ w1_b) (.) (w2_a @ w2_b) into the stored tensor `name`, on the device and in place (include/sdeo.h:
+        sdeo_loha_apply defines the forms).  Plain: w?_a (out, r), w?_b (r, in * kh * kw).  Tucker (t1 and t2 (r, r, kh, kw) given, convs
+        with kh * kw > 1): w?_a (r, out), w?_b (r, in).  Host or device tensors.  Call `lora_commit` after the last apply of a set."""
+        ops = {"w1_a": w1_a, "w1_b": w1_b, "w2_a": w2_a, "w2_b": w2_b, "t1": t1, "t2": t2}
+        info = self._adapter_shape(name)
+        tucker = t1 is not None or t2 is not None
+        rank = int(w1_b.shape[0]) if w1_b is not None and w1_b.dim() >= 1 else 0
+        if info is not None and all(ops[k] is not None for k in ("w1_a", "w1_b", "w2_a", "w2_b")):
+            o, i, kk, shape = info
+            if tucker:
+                want = {"w1_a": (rank, o), "w1_b": (rank, i), "w2_a": (rank, o), "w2_b": (rank, i), "t1": (rank, rank) + shape[2:], "t2": (rank, rank) + shape[2:]}
+                ok = kk > 1 and all(ops[k] is not None and tuple(ops[k].shape) == want[k] for k in want)
+            else:
+                want = {"w1_a": (o, rank), "w1_b": (rank, i * kk), "w2_a": (o, rank), "w2_b": (rank, i * kk)}
+                ok = all(tuple(ops[k].shape) == want[k] for k in want)
+            if not (ok and rank >= 1):
+                raise ValueError(f"loha_apply({name}): the factors {({k: tuple(v.shape) for k, v in ops.items() if v is not None})} do not fit the weight "
+                                 f"{shape}: expected {want}" + (" (a Tucker core needs a conv with a filter larger than 1 x 1)" if tucker and kk == 1 else ""))
+        kept = {k: self._keep(v) for k, v in ops.items()}
+        self._call("loha_apply", name.encode(), *(None if kept[k] is None else ptr(kept[k]) for k in ("w1_a", "w1_b", "w2_a", "w2_b", "t1", "t2")),
+                   rank, C.c_float(float(scale)), cur_stream(), detail=f"({name})")
+
+    def lokr_apply(self, name: str, w1=None, w1_a=None, w1_b=None, w2=None, w2_a=None, w2_b=None, t2=None, scale: float = 1.0):
+        """Merge scale * kron(w1, w2) into the stored tensor `name` (include/sdeo.h: sdeo_lokr_apply defines the forms).  w1 (Ol, Im)
+        whole or as w1_a (Ol, r) @ w1_b (r, Im); w2 (Ok, In[, kh, kw]) whole, as w2_a (Ok, r) @ w2_b (r, In * kh * kw), or in the Tucker
+        form t2 (r, r, kh, kw), w2_a (r, Ok), w2_b (r, In); out = Ol * Ok and in = Im * In are read from the shapes.  Host or device
+        tensors.  Call `lora_commit` after the last apply of a set."""
+        ops = {"w1": w1, "w1_a": w1_a, "w1_b": w1_b, "w2": w2, "w2_a": w2_a, "w2_b": w2_b, "t2": t2}
+        info = self._adapter_shape(name)
+        dims = lambda t, n: t is not None and t.dim() == n
+        rank1 = int(w1_b.shape[0]) if dims(w1_b, 2) else 0
+        rank2 = int(w2_b.shape[0]) if dims(w2_b, 2) else 0
+        ol = int(w1.shape[0]) if dims(w1, 2) else int(w1_a.shape[0]) if dims(w1_a, 2) else 0
+        im = int(w1.shape[1]) if dims(w1, 2) else int(w1_b.shape[1]) if dims(w1_b, 2) else 0
+        if info is not None:
+            o, i, kk, shape = info
+            fits = ol >= 1 and im >= 1 and o % ol == 0 and i % im == 0
+            ok_, in_ = (o // ol, i // im) if fits else (0, 0)
+            want = {}
+            if w1 is not None:
+                want["w1"] = (ol, im)
+            else:
+                want.update({"w1_a": (ol, rank1), "w1_b": (rank1, im)})
+            if w2 is not None:
+                want["w2"] = (ok_, in_) if kk == 1 and w2.dim() == 2 else (ok_, in_) + shape[2:]
+            elif t2 is not None:
+                want.update({"w2_a": (rank2, ok_), "w2_b": (rank2, in_), "t2": (rank2, rank2) + shape[2:]})
+            else:
+                want.update({"w2_a": (ok_, rank2), "w2_b": (rank2, in_ * kk)})
+            ok = fits and set(want) == {k for k, v in ops.items() if v is not None} and all(tuple(ops[k].shape) == want[k] for k in want)
+            ok = ok and (t2 is None or kk > 1) and ("w1_a" not in want or rank1 >= 1) and ("w2_a" not in want or rank2 >= 1)
+            if not ok:
+                raise ValueError(f"lokr_apply({name}): the factors {({k: tuple(v.shape) for k, v in ops.items() if v is not None})} do not fit the weight "
+                                 f"{shape}: expected one complete form with w1 (Ol, Im) and w2 ({shape[0]} / Ol, {shape[1]} / Im" +
+                                 (", " + ", ".join(str(d) for d in shape[2:]) if len(shape) > 2 else "") + ")")
+        kept = {k: self._keep(v) for k, v in ops.items()}
+        p = lambda k: None if kept[k] is None else ptr(kept[k])
+        self._call("lokr_apply", name.encode(), p("w1"), p("w1_a"), p("w1_b"), rank1, p("w2"), p("w2_a"), p("w2_b"), p("t2"), rank2, ol, im,
+                   C.c_float(float(scale)), cur_stream(), detail=f"({name})")
 
     def lora_commit(self):
         """Rebuild what the library derives from the raw weights and invalidate everything computed with the earlier ones: bumps
