@@ -64,6 +64,16 @@ size_t sdeo_groupnorm_workspace_bytes(int n, int hw, int groups);
 int sdeo_groupnorm_nhwc_f16(void* y, const void* x, const float* gamma, const float* beta, int n, int h, int w, int c,
                             int groups, float eps, int with_swish, void* workspace, void* stream);
 
+/* FreeU on one decoder concat buffer, in place (steps 2 and 3 of the definition at sdeo_set_freeu; the stage rule is the caller's).
+ * buf: fp16 NHWC [n * h * w][ld], 16-byte aligned; h in columns [0, c_h), the skip in [c_h, c_h + c_skip); columns from c_h / 2 to c_h
+ * and from c_h + c_skip on are not touched.  c_h % 16 == 0, c_skip % 8 == 0, ld % 8 == 0, ld >= c_h + c_skip, h and w at most 512.
+ * b, s in [0, SDEO_FREEU_MAX]; version 1 or 2.  b == 1 leaves the h half bit for bit as it is, s == 1 the skip half.
+ * workspace: >= sdeo_freeu_workspace_bytes(n, h, w) bytes (the version-2 mean map; may be NULL for version 1 or b == 1).
+ * Two launches at most (version 1: one), no allocation, no synchronisation: capturable. */
+size_t sdeo_freeu_workspace_bytes(int n, int h, int w);
+int sdeo_freeu_nhwc_f16(void* buf, int ld, int n, int h, int w, int c_h, int c_skip, float b, float s, int version, void* workspace,
+                        void* stream);
+
 /* conv2d on NHWC fp16 activations with KRSC fp16 weights (implicit GEMM on MFMA).
  *   y[n][ho][wo][cout] = act( conv(x, w) + bias[cout] + bias2[n][cout] ) * scale + res[n][ho][wo][cout]
  * cin/cout are the STORED channel counts (cin % 8 == 0, cout % 4 == 0); upsample2x=1 folds a nearest x2
@@ -296,6 +306,40 @@ int sdeo_weight_info(sdeo_handle h, int i, const char** name, int64_t dims[4], i
 int sdeo_enable_ip_adapter(sdeo_handle h, int num_tokens);
 int sdeo_set_ip_tokens(sdeo_handle h, const float* tokens, void* stream);
 int sdeo_set_ip_scale(sdeo_handle h, float scale);
+
+/* FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net"; diffusers' enable_freeu): backbone scaling and a Fourier filter of the skip
+ * in front of the UNet decoder's concats.  No weights.  Parameters b1, b2, s1, s2 and version in {1, 2}; mc = model_channels.
+ * In ControlledUnetModel.forward, for every output block, just before h = cat([h, skip], 1) -- skip being exactly what enters the concat:
+ * hs.pop() without control or with only_mid_control, hs.pop() + control.pop() otherwise (with extra control networks: the sum over
+ * the nets under their scales):
+ *   1. stage, by the channel count C of h: C == 4 mc -> (b, s) = (b1, s1); C == 2 mc -> (b, s) = (b2, s2); any other block is untouched.
+ *      (SD-1.5 / 2.x: the authors' h.shape[1] == 1280 / == 640, output blocks 0..6 and 7..9.)
+ *   2. backbone, on the first half of h's channels.  version 1: h[:, :C/2] *= b.  version 2 (what diffusers ships): m = h.mean(1) over
+ *      all C channels ([n][H][W]); per image m = (m - min m) / (max m - min m); h[:, :C/2] *= (b - 1) m + 1.  Where max m == min m the
+ *      factor is 1 (the torch expression gives NaN there: the one stated deviation).
+ *   3. skip, the Fourier filter with threshold 1: X = fftshift(fftn(skip, dim = (-2, -1))); rows H/2-1 : H/2+1 and columns W/2-1 : W/2+1
+ *      of X times s; skip = ifftn(ifftshift(X)).real.  Equivalently, per image and channel, with K(N) = {0} for N == 1, else {-1, 0}:
+ *        y[u][v] = x[u][v] + (s - 1) / (H W) * sum over a in K(H), b in K(W) of (A_ab cos t - B_ab sin t),
+ *        t = 2 pi (a u / H + b v / W),  A_ab = sum x cos t,  B_ab = -sum x sin t      (at most seven fp32 sums per channel)
+ * All arithmetic is fp32 on the fp16 values, every output element is rounded to fp16 once, the sines and cosines are the device
+ * library's double-precision ones (no fast intrinsics), every sum runs in a fixed order.
+ *
+ * sdeo_set_freeu: FreeU on for the following sdeo_unet_forward, sdeo_apply_model and all six fused steps (paired, SDEO_STEP_UNGUIDED,
+ *   masked, stochastic; with extra control networks, an image-prompt adapter, the 2.x layout).  The control networks, the shared
+ *   prefix and the VAE are untouched.  sdeo_configure builds every UNet decoder program twice, without and with the FreeU launches (at
+ *   most two per affected concat, one with version 1; they allocate nothing); on / off selects which one runs, so a handle with FreeU
+ *   off -- never set, or set and turned off -- runs exactly the programs of a handle that knows nothing of it: same weights, same
+ *   device bytes, same launches, same bits.  The four values and the version are read at launch (a captured step bakes them in, like
+ *   ip_scale); sdeo_configure turns FreeU off, as it resets ip_scale.  Callable before sdeo_configure only to be reset by it.
+ *   Refused before any device call, naming the argument: a value that is not finite, negative or above SDEO_FREEU_MAX (8: b times an
+ *   fp16 activation of up to 65504 / 8 stays finite), a version other than 1 or 2.  A refused call leaves the handle as it was.
+ *   No item of the cache contract depends on it: hint features, context K / V, the table and the staged latent are computed in front
+ *   of the decoder.
+ * sdeo_clear_freeu: off.
+ * Untested: handles with fp8 weights or activations (nothing refuses them). */
+#define SDEO_FREEU_MAX 8
+int sdeo_set_freeu(sdeo_handle h, float b1, float b2, float s1, float s2, int version);
+int sdeo_clear_freeu(sdeo_handle h);
 
 /* Fix the problem size (allocate_buffers equivalent): n = images per call of the *_forward functions
  * (the CFG pair counts as 2), latent h x w.  Allocates the activation arena once. */

@@ -43,7 +43,7 @@ def _default_canny():
 class hackathon():
 
     def initialize(self, weights="synthetic:0", config="sd15", apply_canny=None, text_encoder=None, vae_encoder=False, sampler="ddim",
-                   loras=(), ip_adapter=None, image_encoder=None):
+                   loras=(), ip_adapter=None, image_encoder=None, freeu=None):
         """text_encoder: None = `synthetic_text_encoder` (seeded stand-in contexts); "clip:<tokenizer dir>" = the
         FrozenCLIPEmbedder mirror on the HIP path (weights from the same source as the UNet's: synthetic seed or the
         checkpoint's `cond_stage_model.transformer.text_model.*`); bare "clip" is accepted only with synthetic weights (the
@@ -71,10 +71,31 @@ class hackathon():
         projects with the Resampler on the HIP path: the tower is then configured to keep hidden_states[-2], its WIDTH must equal the
         Resampler's proj_in input width, `process(..., ip_image=)` gives Resampler(hidden states of the picture) to the conditional half
         and Resampler(hidden states of an all-zero pixel_values) to the unconditional one (computed once per pipeline).  Without
-        image_encoder a plus pipeline takes ip_tokens only."""
+        image_encoder a plus pipeline takes ip_tokens only.
+        freeu: (b1, b2, s1, s2[, version]) turns FreeU on for every request (`set_freeu`; version 2, the mean-map form, unless given).
+        There are no default values; the authors' suggestions, quoted from memory and NOT verified here, are 1.3 / 1.4 / 0.9 / 0.2 for
+        SD-1.4 and 1.4 / 1.6 / 0.9 / 0.2 for SD-2.1."""
+        freeu = self._freeu_arg(freeu)
         self.apply_canny = apply_canny or _default_canny()
         return self._init_model(weights, config, text_encoder, vae_encoder, sampler=sampler, loras=loras, ip_adapter=ip_adapter,
-                                image_encoder=image_encoder)
+                                image_encoder=image_encoder, freeu=freeu)
+
+    @staticmethod
+    def _freeu_arg(freeu):
+        """`initialize(freeu=)` checked before anything is built: None, or the (b1, b2, s1, s2, version) `set_freeu` will take"""
+        if freeu is None:
+            return None
+        from .runtime import freeu_args
+        if not isinstance(freeu, (tuple, list)):
+            raise ValueError(f"freeu: expected (b1, b2, s1, s2[, version]) or None, got {freeu!r}")
+        return freeu_args(freeu, None, None, None)
+
+    def set_freeu(self, b1=None, b2=None, s1=None, s2=None, version=2):
+        """FreeU for the following `process` calls (its signature does not change): the four values and the version, or one sequence
+        (b1, b2, s1, s2[, version]); `set_freeu(None)` turns it off, and the same seed then gives the image it gave before.  New values
+        make the sampler capture its loop anew, the same values replay it."""
+        self.model.set_freeu(b1, b2, s1, s2, version)
+        return self
 
     def _init_image_encoder(self, image_encoder, tiny):
         """the CLIP vision tower of `initialize(image_encoder=)`; its projection must be as wide as the adapter's image embedding"""
@@ -135,7 +156,7 @@ class hackathon():
         return unsupported
 
     def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim", extra_control=(), loras=(), ip_adapter=None,
-                    image_encoder=None):
+                    image_encoder=None, freeu=None):
         """text encoder, ControlLDM and sampler of `initialize` (shared with hed2image).  extra_control: the weights of each extra
         control network (multi2image): a checkpoint path, a state dict with `control_model.*` names or "synthetic:<seed>"."""
         if sampler not in ("ddim", "dpmpp_2m", "dpmpp_2m_sde", "lcm"):
@@ -221,6 +242,8 @@ class hackathon():
             self.ddim_sampler = DDIMSampler(self.model)
         if loras:
             self.set_loras(loras)
+        if freeu is not None:
+            self.set_freeu(freeu)
         return self
 
     def _load_with_extra(self, weights, extra_control):

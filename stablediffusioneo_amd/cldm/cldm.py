@@ -284,6 +284,16 @@ class ControlLDM:
         if self.rt.ip_adapter_tokens and self.rt.ip_scale != float(self.ip_scale):
             self.rt.set_ip_scale(self.ip_scale)
 
+    # -- FreeU (include/sdeo.h: sdeo_set_freeu): backbone scaling and the skip's Fourier filter in the UNet decoder, no weights
+    def set_freeu(self, b1=None, b2=None, s1=None, s2=None, version: int = 2):
+        """FreeU in every following forward and sampler run (`SdeoRuntime.set_freeu`); `set_freeu(None)` turns it off.  The samplers'
+        captured loops are keyed on it: new values capture anew, the same values replay."""
+        self.rt.set_freeu(b1, b2, s1, s2, version)
+        return self
+
+    def freeu_key(self):
+        return self.rt.freeu_key()
+
     def apply_model(self, x_noisy, t, cond, *args, flags: int = 0, out=None, **kwargs):
         """`cldm/cldm.py:328-341`.  With K control networks the channel concatenation of c_concat holds K hints: chunk j is net j's.
         With an image-prompt adapter cond["c_ip"] holds the image tokens of the n images (absent: the stored conditional ones)."""

@@ -137,6 +137,12 @@ def ip_key(m):
     return (m.rt.ip_adapter_tokens, float(m.ip_scale)) if getattr(m.rt, "ip_adapter_tokens", 0) else None
 
 
+def freeu_key(m):
+    """what a captured step bakes in of FreeU (`SdeoRuntime.set_freeu`): None when off, else the four values and the version"""
+    rt = getattr(m, "rt", None)
+    return rt.freeu_key() if hasattr(rt, "freeu_key") else None
+
+
 def captured_loop(owner, img, mask, x0, time_range, live, shape_key, log_every_t, intermediates, state, first_step, emit):
     """The loop of a sampler `owner` with step 1 run eagerly (it computes the hint block and the context K / V of THIS image into the
     runtime's caches) and steps 2..S replayed from captured graphs.  The graphs read the latent (owner._loop_x) and the sampler's second
@@ -378,7 +384,7 @@ class DDIMSampler(object):
         hint_shared = not unguided and self._ident(c["c_concat"]) == self._ident(uc["c_concat"])
         shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), m.scales_key(), bool(m.only_mid_control),
                      getattr(self, "_schedule_key", None), LOOP_GRAPH_STEPS, hint_shared, m.parameterization,
-                     None if mask is None else tuple(mask.shape), unguided, ip_key(m))
+                     None if mask is None else tuple(mask.shape), unguided, ip_key(m), freeu_key(m))
         a_t, a_p, s1m = self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sqrt_one_minus_alphas
 
         def first_step(img, pred):

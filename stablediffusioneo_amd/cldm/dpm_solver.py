@@ -248,7 +248,7 @@ class DPMSolverSampler(object):
         per_graph = dh.LOOP_GRAPH_STEPS if dh.LOOP_GRAPH_STEPS > 0 else total_steps
         shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), m.scales_key(),
                      bool(m.only_mid_control), self._schedule_key, per_graph, hint_shared, m.parameterization,
-                     None if mask is None else tuple(mask.shape), unguided, dh.ip_key(m))
+                     None if mask is None else tuple(mask.shape), unguided, dh.ip_key(m), dh.freeu_key(m))
         live = [k_n is not None and float(k_n[i]) != 0. for i in range(total_steps)]
 
         def first_step(img, d):

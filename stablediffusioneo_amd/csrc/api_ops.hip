@@ -51,6 +51,14 @@ int sdeo_groupnorm_nhwc_f16(void* y, const void* x, const float* gamma, const fl
                         S(stream));
 }
 
+size_t sdeo_freeu_workspace_bytes(int n, int h, int w) { return freeu_workspace_bytes(n, h, w); }
+
+int sdeo_freeu_nhwc_f16(void* buf, int ld, int n, int h, int w, int c_h, int c_skip, float b, float s, int version, void* workspace,
+                        void* stream) {
+  if (int rc = freeu_check("sdeo_freeu_nhwc_f16", (const f16*)buf, ld, n, h, w, c_h, c_skip, b, s, version, (const float*)workspace)) return rc;
+  return freeu_nhwc_f16((f16*)buf, ld, n, h, w, c_h, c_skip, b, s, version, (float*)workspace, S(stream));
+}
+
 int sdeo_debug_groupnorm_path(int n, int hw, int c, int groups) {
   if (!(n > 0 && hw > 0 && c > 0 && c % 8 == 0 && groups > 0 && groups <= 64 && c % groups == 0)) {
     fail("groupnorm_path: n=%d hw=%d c=%d groups=%d", n, hw, c, groups);

@@ -298,6 +298,7 @@ struct Op {          // one launch of a program + what it is for the profiler
   std::string tag;           // problem shape, shown by the profiler when SDEO_PROFILE_DETAIL=1
   double flops = 0, bytes = 0;
   bool zero_conv = false;    // net_build.hip's ControlNet program: a zero conv (skipped when the UNet decoder applies the zero convs itself)
+  bool freeu = false;        // net_build.hip's UNet decoders: a FreeU launch (only in the programs a handle runs with sdeo_set_freeu on)
   template <class F>
   Op(F f, const char* key_ = "other", double flops_ = 0, double bytes_ = 0, std::string tag_ = std::string())
       : fn(std::move(f)), key(key_), tag(std::move(tag_)), flops(flops_), bytes(bytes_) {}

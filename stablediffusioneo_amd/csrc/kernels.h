@@ -321,4 +321,18 @@ int mask_blend_pair(float* x, const float* orig, const float* noise, const float
 // dst = (gen * m + orig * (255 - m) + 127) / 255 in integers: uint8 HWC images [H][W][C], C in 1..4, uint8 mask [H][W]
 int composite_u8(uint8_t* dst, const uint8_t* gen, const uint8_t* orig, const uint8_t* mask, int H, int W, int C, hipStream_t stream);
 
+// FreeU on one decoder concat buffer, in place (freeu.hip; include/sdeo.h: sdeo_freeu_nhwc_f16 defines the arithmetic).  buf: fp16 NHWC
+// [n * h * w][ld], h in columns [0, c_h), the skip in [c_h, c_h + c_skip); nothing else is touched.  version 1: one launch; version 2:
+// the mean-map launch into `workspace` (freeu_workspace_bytes: n * h * w floats), then the apply launch.  b == 1 / s == 1 launch nothing
+// for their half.  No allocation, no synchronisation.  freeu_check: the operand checks alone; freeu_params_check: the four values and
+// the version as sdeo_set_freeu takes them (both host only).
+constexpr float kFreeuMax = 8.0f;      // cap of b and s: b times an fp16 activation of up to 65504 / 8 = 8188 stays finite
+constexpr int kFreeuMaxDim = 512;      // largest map height / width (the trigonometric tables of a skip workgroup live in LDS)
+int freeu_params_check(const char* who, float b1, float b2, float s1, float s2, int version);
+int freeu_check(const char* who, const f16* buf, int ld, int n, int h, int w, int c_h, int c_skip, float b, float s, int version,
+                const float* workspace);
+size_t freeu_workspace_bytes(int n, int h, int w);
+int freeu_nhwc_f16(f16* buf, int ld, int n, int h, int w, int c_h, int c_skip, float b, float s, int version, float* workspace,
+                   hipStream_t stream);
+
 }  // namespace sdeo

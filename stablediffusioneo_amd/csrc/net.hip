@@ -15,6 +15,12 @@ static int run(Engine* e, const Program& p, hipStream_t s, bool skip_zero_convs 
   return 0;
 }
 
+// a program that holds a UNet decoder: with sdeo_set_freeu on, the one that kept its FreeU launches
+static const Program& decoder_program(const Engine* e, ProgId id) {
+  if (!e->freeu_on) return e->prog[id];
+  return e->prog_freeu[id == P_UNET_DEC ? 0 : id == P_UNET_DEC_FUSED ? 1 : 2];
+}
+
 template <typename Tp>
 static int dev_alloc(Engine* e, Tp** p, size_t bytes) {
   void* v = nullptr;
@@ -33,6 +39,7 @@ static void free_configured(Engine* e) {
     l = Lane();
   }
   for (Program& p : e->prog) p.clear();
+  for (Program& p : e->prog_freeu) p.clear();
   for (auto& px : e->xprog) for (Program& p : px) p.clear();
   for (int j = 0; j < kMaxControlNets - 1; ++j) {        // the hint caches are gone with the arenas, the scales return to 1
     for (float& v : e->extra_scales[j]) v = 1.0f;
@@ -178,6 +185,10 @@ int sdeo_enable_ip_adapter(sdeo_handle h, int num_tokens) {
 static int configure_impl(sdeo_handle h, int n, int latent_h, int latent_w) {
   free_configured(h);
   h->ip_scale = 1.0f;
+  h->freeu_on = false;           // FreeU off and its values back to the identity, as ip_scale returns to 1
+  h->freeu_b[0] = h->freeu_b[1] = h->freeu_s[0] = h->freeu_s[1] = 1.0f;
+  h->freeu_version = 2;
+  h->freeu_refusal.clear();
   h->N = n; h->lh = latent_h; h->lw = latent_w;
   const sdeo_config& c = h->cfg;
   const size_t px = (size_t)latent_h * latent_w;
@@ -326,7 +337,7 @@ static int run_step_programs(sdeo_handle h, bool no_control, bool time_from_tabl
   const Program& p_cn = shared_cn && !h->prog[P_CN_SH].empty() ? h->prog[P_CN_SH] : h->prog[P_CN];
   if (no_control) {
     if (!time_from_table) if (int rc = run(h, h->prog[P_TEMB + 0], s)) return rc;
-    return run(h, h->prog[P_UNET_NOCTRL], s);
+    return run(h, decoder_program(h, P_UNET_NOCTRL), s);
   }
   if (h->overlap && !h->prof.on) {
     // fork: ControlNet on the side stream, UNet encoder + middle block on the caller's stream (capturable)
@@ -352,7 +363,7 @@ static int run_step_programs(sdeo_handle h, bool no_control, bool time_from_tabl
     if (int rc = run_extra_controlnets(h, shared_cn, s)) return rc;
     if (int rc = run(h, p_unet_enc, s)) return rc;
   }
-  return run(h, h->prog[P_UNET_DEC_FUSED], s);      // applies the zero convs itself (skipped above)
+  return run(h, decoder_program(h, P_UNET_DEC_FUSED), s);      // applies the zero convs itself (skipped above)
 }
 
 // copy net j's hint in and run its hint block into its cached features (j >= 1; net 0's goes through stage_inputs)
@@ -448,6 +459,24 @@ int sdeo_set_ip_scale(sdeo_handle h, float scale) {
   return 0;
 }
 
+// FreeU: which decoder programs the following forwards and steps run, and the values their FreeU launches read when they run.  Host
+// state only: every refusal precedes it, and there is no device call to precede.
+int sdeo_set_freeu(sdeo_handle h, float b1, float b2, float s1, float s2, int version) {
+  if (int rc = freeu_params_check("sdeo_set_freeu", b1, b2, s1, s2, version)) return rc;
+  SDEO_CHECK(h, "sdeo_set_freeu: null handle");
+  SDEO_CHECK(h->freeu_refusal.empty(), "sdeo_set_freeu: %s", h->freeu_refusal.c_str());
+  h->freeu_b[0] = b1; h->freeu_b[1] = b2; h->freeu_s[0] = s1; h->freeu_s[1] = s2;
+  h->freeu_version = version;
+  h->freeu_on = true;
+  return 0;
+}
+
+int sdeo_clear_freeu(sdeo_handle h) {
+  SDEO_CHECK(h, "sdeo_clear_freeu: null handle");
+  h->freeu_on = false;
+  return 0;
+}
+
 int sdeo_unet_forward(sdeo_handle h, const float* x_noisy, const int64_t* timesteps, const float* context,
                       const float* const* controls, const float* host_control_scales, int only_mid_control, float* eps,
                       int flags, void* stream) {
@@ -471,9 +500,9 @@ int sdeo_unet_forward(sdeo_handle h, const float* x_noisy, const int64_t* timest
     }
     if (int rc = run(h, h->prog[P_CTRL_IMPORT], s)) return rc;
     if (int rc = run(h, h->prog[P_UNET_ENC], s)) return rc;
-    if (int rc = run(h, h->prog[P_UNET_DEC], s)) return rc;
+    if (int rc = run(h, decoder_program(h, P_UNET_DEC), s)) return rc;
   } else {
-    if (int rc = run(h, h->prog[P_UNET_NOCTRL], s)) return rc;
+    if (int rc = run(h, decoder_program(h, P_UNET_NOCTRL), s)) return rc;
   }
   if (int rc = run(h, h->prog[P_EPS_EXPORT], s)) return rc;
   return copy_in(eps, h->out_eps, (size_t)h->N * h->cfg.out_channels * h->lh * h->lw * 4, s);

@@ -263,6 +263,35 @@ struct Builder {
     return y;
   }
 
+  // FreeU on a decoder concat buffer whose two halves are written (include/sdeo.h: sdeo_set_freeu): in place, flagged launches that
+  // only the handle's FreeU programs keep (build_all).  cat's first c_h columns are h; the stage rule picks (b, s), read at launch with
+  // the version.  The version-2 mean map lives in the lane's GroupNorm workspace: the launches sit between the producers of the buffer
+  // and the first GroupNorm that reads it, on one stream, so nothing else holds it.
+  // The GroupNorm behind the concat must not take statistics from a producer's epilogue, which an in-place change would leave stale: a
+  // concat buffer never carries any (conv() reserves partials only for a tensor it allocates, a concat half is written through
+  // ConvOpts::out), and a buffer that did is refused here.
+  void freeu(const T& cat, int c_h) {
+    const int mc = e->cfg.model_channels;
+    const int stage = c_h == 4 * mc ? 0 : c_h == 2 * mc ? 1 : -1;
+    if (stage < 0) return;
+    const int c_skip = cat.c - c_h;
+    if (cat.gnp && err.empty()) err = "FreeU on a concat buffer that carries GroupNorm statistics of its producer";
+    if (cat.h > kFreeuMaxDim || cat.w > kFreeuMaxDim || c_h % 16 || c_skip % 8 || cat.ld % 8) {      // (sdeo_set_freeu refuses; the plain programs are unaffected)
+      if (e->freeu_refusal.empty())
+        e->freeu_refusal = "a " + std::to_string(cat.h) + " x " + std::to_string(cat.w) + " concat of " + std::to_string(c_h) + " + " +
+                           std::to_string(c_skip) + " channels is outside what the FreeU kernels take";
+      return;
+    }
+    max_gn = std::max(max_gn, freeu_workspace_bytes(cat.n, cat.h, cat.w));
+    const Lane* ws = lane;
+    f16* p = cat.p; const int ld = cat.ld, n = cat.n, h = cat.h, w = cat.w;
+    const float* bp = &e->freeu_b[stage]; const float* sp = &e->freeu_s[stage]; const int* vp = &e->freeu_version;
+    Op op([=](hipStream_t s) { return freeu_nhwc_f16(p, ld, n, h, w, c_h, c_skip, *bp, *sp, *vp, ws->gn_ws, s); }, "freeu", 0,
+          2.0 * n * h * w * (2.0 * c_h + 3.0 * c_skip), "C" + std::to_string(c_h) + "+" + std::to_string(c_skip) + " HW" + std::to_string(h * w));
+    op.freeu = true;
+    if (!dry) prog->push_back(std::move(op));
+  }
+
   // conv3x3(act(GroupNorm(x))) (`openaimodel.py:255-275`, `model.py:129-149`): GroupNorm launch(es) + conv
   T gn_conv(const T& x, const std::string& gn_name, float eps, int silu_, const std::string& conv_name, int cout, CO o) {
     T t = gn(x, gn_name, eps, silu_);
@@ -767,6 +796,7 @@ static void build_unet_decoder(BuildCtx& c, DecoderMode mode, std::vector<T> hs,
       const float* sc = &e->scales[ci]; const int* om = &e->only_mid;
       b.push([=](hipStream_t s) { return add_scaled(yp, ld, ap, lda, (*om) ? nullptr : cp, ldc, *sc, rows, Cc, s); });
     }
+    b.freeu(cat, c_h);           // both halves of the concat are in place
     --ci;
     b.release(skip);
     const std::vector<Blk>& blocks = e->uplan.out[oi];
@@ -831,6 +861,7 @@ static void build_unet_decoder_multi(BuildCtx& c, std::vector<T> hs, T cat0, T v
   for (T& skip : hs) b.release(skip);
   for (size_t oi = 0; oi < stages; ++oi) {
     const std::vector<Blk>& blocks = e->uplan.out[oi];
+    b.freeu(cats[oi], cats[oi].c - hs[nh - 1 - oi].c);      // h from the stage before (the middle block), the skip from the launch above
     if (oi + 1 < stages) {
       const T nview = cats[oi + 1].view(0, blocks.back().cout);
       run_blocks(c, ns, blocks, cats[oi], true, 0, &nview);
@@ -977,6 +1008,14 @@ int sdeo::build_all(Engine* e, bool dry, size_t* max_splitk, size_t* max_gn, siz
   c.b.on_lane(&e->lanes[L_SIDE], [&] { for (int j = 0; j <= e->extra; ++j) build_controlnet(c, j); });
   build_control_io(c);
   for (int variant = 0; variant < 2; ++variant) build_unet(c, variant == 0);
+  // the three programs that hold a decoder, as built, are the FreeU programs; without their flagged launches, the ones a handle runs
+  // with FreeU off: launch for launch what this pass builds when Builder::freeu pushes nothing
+  static const ProgId kWithDecoder[3] = {P_UNET_DEC, P_UNET_DEC_FUSED, P_UNET_NOCTRL};
+  for (int i = 0; i < 3; ++i) {
+    Program& p = e->prog[kWithDecoder[i]];
+    e->prog_freeu[i] = p;
+    p.erase(std::remove_if(p.begin(), p.end(), [](const Op& op) { return op.freeu; }), p.end());
+  }
   build_vae_decoder(c);
   if (e->vae_encoder) build_vae_encoder(c);
   for (int i = 0; i < L_COUNT; ++i) {

@@ -121,6 +121,15 @@ struct sdeo_handle_s {
   int ip_tokens = 0;
   float* in_ip = nullptr;
   float ip_scale = 1.0f;
+  // FreeU (sdeo_set_freeu): whether the decoder programs with the FreeU launches run, and what those launches read at LAUNCH -- (b, s) of
+  // the 4 mc-channel stage and of the 2 mc-channel stage, and the version.  prog_freeu: P_UNET_DEC, P_UNET_DEC_FUSED and P_UNET_NOCTRL
+  // as built, FreeU launches included; prog[] holds them without (build_all).  freeu_refusal: why these programs cannot run FreeU (a map
+  // beyond the kernel's size limit), empty when they can
+  bool freeu_on = false;
+  float freeu_b[2] = {1.0f, 1.0f}, freeu_s[2] = {1.0f, 1.0f};
+  int freeu_version = 2;
+  Program prog_freeu[3];
+  std::string freeu_refusal;
   std::vector<void*> extra_allocs;
   // persistent activations
   T ctrl[kMaxControls];  // fp16 NHWC controls (ControlNet output / UNet input), unscaled

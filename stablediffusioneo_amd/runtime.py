@@ -26,6 +26,36 @@ def TIMESTEP_ROW(i: int) -> int:
 MAX_TABLE_STEPS = _lib.header_constant("SDEO_MAX_TABLE_STEPS")
 
 
+# cap of the four FreeU values (SDEO_FREEU_MAX of include/sdeo.h)
+FREEU_MAX = _lib.header_constant("SDEO_FREEU_MAX")
+
+
+def freeu_args(b1, b2, s1, s2, version=2):
+    """(b1, b2, s1, s2, version) as floats and an int after the checks `sdeo_set_freeu` makes, made here first so that a refusal names
+    the argument as a ValueError whether or not a device is there; also takes one sequence of four or five as `b1`."""
+    if isinstance(b1, (tuple, list)) and b2 is None and s1 is None and s2 is None:
+        if len(b1) not in (4, 5):
+            raise ValueError(f"freeu: expected (b1, b2, s1, s2[, version]), got {len(b1)} values")
+        seq = tuple(b1)
+        b1, b2, s1, s2 = seq[:4]
+        version = seq[4] if len(seq) == 5 else version
+    vals = []
+    for name, v in (("b1", b1), ("b2", b2), ("s1", s1), ("s2", s2)):
+        if v is None or isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"freeu: {name} must be a number, got {v!r} (there are no default values)")
+        v = float(v)
+        if v != v or v in (float("inf"), float("-inf")):
+            raise ValueError(f"freeu: {name} = {v} is not finite")
+        if v < 0:
+            raise ValueError(f"freeu: {name} = {v} is negative")
+        if v > FREEU_MAX:
+            raise ValueError(f"freeu: {name} = {v} is above the cap of {FREEU_MAX}")
+        vals.append(v)
+    if isinstance(version, bool) or not isinstance(version, int) or version not in (1, 2):
+        raise ValueError(f"freeu: version must be 1 (constant backbone factor) or 2 (mean-map factor), got {version!r}")
+    return (*vals, int(version))
+
+
 def make_config(ucfg: S.UNetConfig = S.UNET_SD15, vcfg: S.VAEConfig = S.VAE_SD15) -> SdeoConfig:
     c = SdeoConfig()
     c.in_channels, c.out_channels, c.hint_channels = ucfg.in_channels, ucfg.out_channels, ucfg.hint_channels
@@ -275,6 +305,7 @@ class SdeoRuntime(_HandleRuntime):
         if self.ip_adapter_tokens:  # before any weight, like the encoder
             check(self.lib.sdeo_enable_ip_adapter(self.handle, self.ip_adapter_tokens), "enable_ip_adapter")
         self.ip_scale = 1.0         # as the library holds it (sdeo_configure resets it to 1): part of every key of a captured graph
+        self._freeu = None          # (b1, b2, s1, s2, version) or None = off, as asked of `set_freeu`: kept across `configure`
         self.weight_bits = int(weight_bits)
         if self.weight_bits != 16:
             check(self.lib.sdeo_set_weight_precision(self.handle, self.weight_bits), "set_weight_precision")
@@ -349,7 +380,30 @@ class SdeoRuntime(_HandleRuntime):
             self.n, self.h, self.w = n, h, w
             self._extra_scales = [None] * self.extra_controlnets       # the library reset them to 1
             self.ip_scale = 1.0                                        # ... and the weight of the image term
+            if self._freeu is not None:                                # ... and turned FreeU off: hand it over again
+                self._call("set_freeu", *(C.c_float(v) for v in self._freeu[:4]), self._freeu[4])
         return self
+
+    # ---------------------------------------------------------------- FreeU
+    def set_freeu(self, b1=None, b2=None, s1=None, s2=None, version: int = 2):
+        """`sdeo_set_freeu`: FreeU (include/sdeo.h defines it) in every following UNet forward and fused step: backbone factors b1 / b2
+        and skip filter scales s1 / s2 of the 4 mc / 2 mc-channel decoder stages, version 1 (constant factor) or 2 (mean-map factor, what
+        diffusers ships).  `set_freeu(None)`: off (`sdeo_clear_freeu`).  There are no default values.  The values are read at launch, so
+        a captured graph bakes them in: `freeu_key` is part of every graph key.  Unlike the library, the runtime keeps the setting across
+        `configure`.  Refused (ValueError, nothing changes): a value that is missing, not finite, negative or above FREEU_MAX, a version
+        other than 1 or 2."""
+        if b1 is None and b2 is None and s1 is None and s2 is None:
+            self._call("clear_freeu")
+            self._freeu = None
+            return self
+        key = freeu_args(b1, b2, s1, s2, version)
+        self._call("set_freeu", *(C.c_float(v) for v in key[:4]), key[4])
+        self._freeu = key
+        return self
+
+    def freeu_key(self):
+        """what a captured graph bakes in of FreeU: None when off, else (b1, b2, s1, s2, version)"""
+        return self._freeu
 
     # ---------------------------------------------------------------- image-prompt adapter
     def set_ip_tokens(self, tokens):
@@ -471,7 +525,7 @@ class SdeoRuntime(_HandleRuntime):
         side stream, UNet encoder on the main one), so the GPU sees the whole fork/join at once.  Inputs are copied into
         fixed device buffers; the returned eps tensor is owned by the runtime (valid until the next call)."""
         key = (self.generation, self.n, self.h, self.w, tuple(float(s) for s in (scales or [])), bool(only_mid_control),
-               self.extra_scales_key(), self.ip_key())
+               self.extra_scales_key(), self.ip_key(), self.freeu_key())
         if getattr(self, "_graph_key", None) != key:
             u = self.ucfg
             self._gx = torch.zeros((self.n, u.in_channels, self.h, self.w), dtype=torch.float32, device=self.device)
