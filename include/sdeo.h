@@ -572,6 +572,49 @@ int sdeo_set_control_scales(sdeo_handle h, int net, const float* host_scales13);
 int sdeo_controlnet_forward_net(sdeo_handle h, int net, const float* x_noisy, const float* hint, const int64_t* timesteps,
                                 const float* context, float* const* controls, int flags, void* stream);
 
+/* Control modes (opt-in): per call and per control network, apply the network to both halves of the CFG pair, to the conditional half
+ * only, or not at all -- what a control window ("starting / ending control step") and guess mode (the unconditional half runs without
+ * ControlNet, canny2image_torch.py:48) come down to -- with the work shrinking accordingly: a COND net runs on n / 2 images, an OFF
+ * net does not run.
+ * sdeo_enable_control_modes: after sdeo_create[_ex], before sdeo_configure.  Adds no weight and no device memory: sdeo_configure builds,
+ *   per control network, one more program (the network on the first n / 2 images: every launch the batch prefix of its full-batch
+ *   launch, in the same tensors) and the further forms of that net's zero-conv launch in the fused decoders.  A handle that never
+ *   calls it is bit for bit what it was, sdeo_device_bytes included.  Refused by name: a handle with fp8 weights
+ *   (sdeo_set_weight_precision 8) or block-scaled fp8 activations (sdeo_set_activation_precision 8) -- here or, when the precision is
+ *   set later, by sdeo_configure; a call after sdeo_configure.
+ * sdeo_set_control_mode: net 0..extra (0 = "control_model."), mode one of
+ *     SDEO_CONTROL_BOTH  every image (what a handle without modes does);
+ *     SDEO_CONTROL_COND  images [0, n/2) only: the conditional half of [cond; uncond];
+ *     SDEO_CONTROL_OFF   no image.
+ *   Host state like an extra net's scales: read when a call launches (a captured step bakes it in), kept until changed; sdeo_configure
+ *   resets every net to BOTH.  It acts in sdeo_apply_model and in all six fused steps, their masked, noisy, staged and v-prediction
+ *   forms included; sdeo_unet_forward, sdeo_controlnet_forward[_net] and the 13-tensor boundary ignore it.  Refused, before any device
+ *   call and each with its own message: a handle without sdeo_enable_control_modes, a net outside 0..extra, a mode that is none of
+ *   the three.  sdeo_apply_model with a COND net on an odd configured n is refused there, before its first device call.
+ * What runs, for the modes (m_0 .. m_k) of a call:
+ *   - all BOTH: exactly the programs of a handle without modes -- same launches, same bits;
+ *   - all OFF: the no-control program (the SDEO_NO_CONTROL branch of sdeo_apply_model): no fork, no ControlNet launch;
+ *   - anything else: an OFF net's programs do not run; a COND net's half-batch program does; the fused decoder applies, per active net,
+ *     scale * zero_conv(block outputs) to the net's LIVE rows -- all of them, or those of the first n / 2 images.  The live-row rule: a
+ *     row that is not live receives its residual unchanged (the skip, or the running sum of the nets in front); it is selected, never
+ *     multiplied by a zero scale, because the block outputs of a COND net hold nothing meaningful beyond the first half.  The first
+ *     ACTIVE net takes the skip as its residual, the later ones work in place over the running sum.  No mode adds a launch to the step
+ *     where the zero convs run as one multi-problem launch per net (channel counts that are multiples of 64); the per-conv form passes
+ *     the other half's skip rows through with one copy launch per zero conv of the first active net when that net is COND.
+ *   - every live row of eps is bit-identical to the same call with that net in BOTH mode when every net is BOTH or COND alike; an
+ *     image no net is live on is bit-identical to what the all-OFF decoder arithmetic gives it (the skip passes through unchanged).
+ * SDEO_STEP_UNGUIDED: there is no second half, COND means BOTH and OFF means no control.  SDEO_STEP_HINT_SHARED stays accepted and has
+ *   no effect for a net in COND or OFF mode.
+ * The cache contract is untouched by the modes: a fused step still wants every net's hint cached and the context K / V of both sides,
+ *   whatever the modes; a call that is given a hint (or a context) stages it and runs the hint block (the K / V projections of every
+ *   net) whatever the modes, so the first active step of a window finds them cached.
+ * Left for later: fp8 handles; per-half scales other than 1 / 0. */
+#define SDEO_CONTROL_BOTH 0
+#define SDEO_CONTROL_COND 1
+#define SDEO_CONTROL_OFF 2
+int sdeo_enable_control_modes(sdeo_handle h);
+int sdeo_set_control_mode(sdeo_handle h, int net, int mode);
+
 /* bytes of device memory the handle owns (weights + arena + the tensors saved under LoRA adapters) */
 size_t sdeo_device_bytes(sdeo_handle h);
 

@@ -43,7 +43,7 @@ def _default_canny():
 class hackathon():
 
     def initialize(self, weights="synthetic:0", config="sd15", apply_canny=None, text_encoder=None, vae_encoder=False, sampler="ddim",
-                   loras=(), ip_adapter=None, image_encoder=None, freeu=None):
+                   loras=(), ip_adapter=None, image_encoder=None, freeu=None, control_schedule=None):
         """text_encoder: None = `synthetic_text_encoder` (seeded stand-in contexts); "clip:<tokenizer dir>" = the
         FrozenCLIPEmbedder mirror on the HIP path (weights from the same source as the UNet's: synthetic seed or the
         checkpoint's `cond_stage_model.transformer.text_model.*`); bare "clip" is accepted only with synthetic weights (the
@@ -74,11 +74,24 @@ class hackathon():
         image_encoder a plus pipeline takes ip_tokens only.
         freeu: (b1, b2, s1, s2[, version]) turns FreeU on for every request (`set_freeu`; version 2, the mean-map form, unless given).
         There are no default values; the authors' suggestions, quoted from memory and NOT verified here, are 1.3 / 1.4 / 0.9 / 0.2 for
-        SD-1.4 and 1.4 / 1.6 / 0.9 / 0.2 for SD-2.1."""
+        SD-1.4 and 1.4 / 1.6 / 0.9 / 0.2 for SD-2.1.
+        control_schedule: a `cldm.control_schedule.ControlSchedule` (or a list with one per control network): the window of the run in
+        which the ControlNet acts ("starting / ending control step") and whether it acts on both halves of the guidance pair or on the
+        conditional half only (`set_control_schedule`).  None (the default) builds the pipeline without the feature.  With a schedule
+        in force `process` hands the control to both conditionings and lets the schedule drop it, so guess_mode=True under on="cond"
+        is the reference's guess mode -- the 0.825^(12-i) scales, the unconditional half uncontrolled -- on the fused, graphed path
+        instead of two one-image forwards per step: the fast way to run guess mode."""
         freeu = self._freeu_arg(freeu)
         self.apply_canny = apply_canny or _default_canny()
         return self._init_model(weights, config, text_encoder, vae_encoder, sampler=sampler, loras=loras, ip_adapter=ip_adapter,
-                                image_encoder=image_encoder, freeu=freeu)
+                                image_encoder=image_encoder, freeu=freeu, control_schedule=control_schedule)
+
+    def set_control_schedule(self, schedule=None):
+        """The control schedule of the following `process` calls (its signature does not change): one ControlSchedule, a list with one per
+        control network, or None (off: every request runs as it did before).  Needs `initialize(..., control_schedule=...)`, which
+        builds the runtime with control modes.  The same schedule replays the sampler's captured loop, another one captures anew."""
+        self.model.set_control_schedule(schedule)
+        return self
 
     @staticmethod
     def _freeu_arg(freeu):
@@ -156,11 +169,14 @@ class hackathon():
         return unsupported
 
     def _init_model(self, weights, config, text_encoder, vae_encoder=False, sampler="ddim", extra_control=(), loras=(), ip_adapter=None,
-                    image_encoder=None, freeu=None):
+                    image_encoder=None, freeu=None, control_schedule=None):
         """text encoder, ControlLDM and sampler of `initialize` (shared with hed2image).  extra_control: the weights of each extra
         control network (multi2image): a checkpoint path, a state dict with `control_model.*` names or "synthetic:<seed>"."""
         if sampler not in ("ddim", "dpmpp_2m", "dpmpp_2m_sde", "lcm"):
             raise ValueError(f'sampler {sampler!r}: "ddim", "dpmpp_2m", "dpmpp_2m_sde" or "lcm"')
+        if control_schedule is not None:      # checked before anything is built
+            from .cldm.control_schedule import normalize
+            normalize(control_schedule, 1 + len(extra_control))
         if image_encoder is not None and ip_adapter is None:
             raise ValueError("image_encoder needs an adapter to feed: initialize(..., ip_adapter=..., image_encoder=...)")
         self.image_encoder = None
@@ -196,7 +212,7 @@ class hackathon():
             else:
                 ip_tokens = 4       # (refused with its own message by load_ip_adapter below)
         self.model = create_model(config, cond_stage_model=text_encoder, vae_encoder=vae_encoder, extra_controlnets=len(extra_control),
-                                  ip_adapter_tokens=ip_tokens)
+                                  ip_adapter_tokens=ip_tokens, control_modes=control_schedule is not None)
         self._ip_uncond_tokens = None        # a "plus" adapter's unconditional image tokens (`_plus_uncond_tokens`)
         if ip_seed is not None:
             from . import ip_adapter as IPA
@@ -244,6 +260,8 @@ class hackathon():
             self.set_loras(loras)
         if freeu is not None:
             self.set_freeu(freeu)
+        if control_schedule is not None:
+            self.set_control_schedule(control_schedule)
         return self
 
     def _load_with_extra(self, weights, extra_control):
@@ -334,7 +352,8 @@ class hackathon():
             control = list(control) if isinstance(control, (list, tuple)) else [control]
             cond = {"c_concat": control,
                     "c_crossattn": [self.model.get_learned_conditioning([prompt + ", " + a_prompt] * num_samples)]}
-            un_cond = {"c_concat": None if guess_mode else control,
+            # (with a control schedule in force both sides carry the control and the schedule drops it: the request stays on the fused path)
+            un_cond = {"c_concat": None if guess_mode and self.model.control_schedule is None else control,
                        "c_crossattn": [self.model.get_learned_conditioning([n_prompt] * num_samples)]}
             shape = (4, H // 8, W // 8)
             # `canny2image_torch.py:54`: guess-mode scales 0.825**(12-i)

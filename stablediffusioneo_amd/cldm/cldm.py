@@ -294,6 +294,20 @@ class ControlLDM:
     def freeu_key(self):
         return self.rt.freeu_key()
 
+    # -- control schedule (`cldm/control_schedule.py`): per step and per net, both halves / the conditional half / off.  None: nothing
+    # changes anywhere.  The samplers read the attribute; the setter checks it against the model first.
+    control_schedule = None
+
+    def set_control_schedule(self, schedule=None):
+        """one ControlSchedule (every net), a list with one per net, or None (off).  Needs create_model(..., control_modes=True).  The
+        samplers' captured loops are keyed on it: the same schedule replays, another one captures anew, None replays what ran before."""
+        from .control_schedule import normalize
+        normalize(schedule, 1 + self.rt.extra_controlnets)
+        if schedule is not None and not getattr(self.rt, "control_modes", False):
+            raise RuntimeError("set_control_schedule: the model was created without control modes (create_model(..., control_modes=True))")
+        self.control_schedule = schedule
+        return self
+
     def apply_model(self, x_noisy, t, cond, *args, flags: int = 0, out=None, **kwargs):
         """`cldm/cldm.py:328-341`.  With K control networks the channel concatenation of c_concat holds K hints: chunk j is net j's.
         With an image-prompt adapter cond["c_ip"] holds the image tokens of the n images (absent: the stored conditional ones)."""

@@ -19,6 +19,7 @@ import os
 
 from .. import ops
 from ..runtime import CONTEXT_CACHED, HINT_CACHED, MAX_TABLE_STEPS
+from . import control_schedule as cs
 
 # replay the per-step apply_model from a hipGraph once hint / context are cached (SDEO_GRAPH=0: eager launches)
 USE_GRAPH = os.environ.get("SDEO_GRAPH", "1") != "0"
@@ -141,6 +142,25 @@ def freeu_key(m):
     """what a captured step bakes in of FreeU (`SdeoRuntime.set_freeu`): None when off, else the four values and the version"""
     rt = getattr(m, "rt", None)
     return rt.freeu_key() if hasattr(rt, "freeu_key") else None
+
+
+def control_plan(pair, c, uc, scale, total_steps):
+    """The control modes of every step of a run under the model's `control_schedule` (`control_schedule.step_plan`), or None: no
+    schedule, or a request off the fused path -- guess mode's `uc["c_concat"] = None` among them, which keeps its two-call route.
+    pair: the DDIMSampler whose `_fusable` / `_unguided` judge the request."""
+    if getattr(pair.model, "control_schedule", None) is None:
+        return None
+    unguided = pair._unguided(c, uc, scale)
+    return cs.step_plan(pair.model, unguided or pair._fusable(c, uc, scale), unguided, total_steps)
+
+
+def loop_modes_key(m, plan):
+    """what a captured loop bakes in of the control modes: under a schedule its key (every step sets its own modes), else the modes the
+    runtime holds -- set by hand through `SdeoRuntime.set_control_mode`, all BOTH otherwise"""
+    if plan is not None:
+        return cs.schedule_key(m.control_schedule)
+    rt = getattr(m, "rt", None)
+    return ("modes", rt.modes_key()) if hasattr(rt, "modes_key") else None
 
 
 def captured_loop(owner, img, mask, x0, time_range, live, shape_key, log_every_t, intermediates, state, first_step, emit):
@@ -314,6 +334,7 @@ class DDIMSampler(object):
                                         temperature, noise_dropout)):
             return self._loop_graphed(img, cond, unconditional_conditioning, unconditional_guidance_scale, time_range,
                                       total_steps, log_every_t, intermediates, mask=mask, x0=x0)
+        plan = None if ddim_use_original_steps else control_plan(self, cond, unconditional_conditioning, unconditional_guidance_scale, total_steps)
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
@@ -324,13 +345,14 @@ class DDIMSampler(object):
             if ucg_schedule is not None:
                 assert len(ucg_schedule) == len(time_range)
                 unconditional_guidance_scale = ucg_schedule[i]
-            img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, use_original_steps=ddim_use_original_steps,
-                                              quantize_denoised=quantize_denoised, temperature=temperature,
-                                              noise_dropout=noise_dropout, score_corrector=score_corrector,
-                                              corrector_kwargs=corrector_kwargs,
-                                              unconditional_guidance_scale=unconditional_guidance_scale,
-                                              unconditional_conditioning=unconditional_conditioning,
-                                              dynamic_threshold=dynamic_threshold)
+            with cs.step_modes(self.model, plan, i):
+                img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, use_original_steps=ddim_use_original_steps,
+                                                  quantize_denoised=quantize_denoised, temperature=temperature,
+                                                  noise_dropout=noise_dropout, score_corrector=score_corrector,
+                                                  corrector_kwargs=corrector_kwargs,
+                                                  unconditional_guidance_scale=unconditional_guidance_scale,
+                                                  unconditional_conditioning=unconditional_conditioning,
+                                                  dynamic_threshold=dynamic_threshold)
             if callback:
                 callback(i)
             if img_callback:
@@ -385,23 +407,28 @@ class DDIMSampler(object):
         shape_key = (tuple(img.shape), time_range, float(scale), int(log_every_t), m.scales_key(), bool(m.only_mid_control),
                      getattr(self, "_schedule_key", None), LOOP_GRAPH_STEPS, hint_shared, m.parameterization,
                      None if mask is None else tuple(mask.shape), unguided, ip_key(m), freeu_key(m))
+        # the control schedule: every step sets the nets' modes before its library call (a captured step bakes them in)
+        plan = control_plan(self, c, uc, scale, total_steps)
+        shape_key += (loop_modes_key(m, plan),)
         a_t, a_p, s1m = self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sqrt_one_minus_alphas
 
         def first_step(img, pred):
             ts = torch.full((img.shape[0],), time_range[0], device=img.device, dtype=torch.long)
-            return self.p_sample_ddim(img, c, ts, index=total_steps - 1, unconditional_guidance_scale=scale, unconditional_conditioning=uc)
+            with cs.step_modes(m, plan, 0):
+                return self.p_sample_ddim(img, c, ts, index=total_steps - 1, unconditional_guidance_scale=scale, unconditional_conditioning=uc)
 
         def emit(i, staged, noise_row, blend):
             index = total_steps - i - 1
             x, pred = self._loop_x, self._loop_pred
             tail = (i, scale, float(a_t[index]), float(a_p[index]), float(s1m[index]), m.net0_scales(), m.only_mid_control)
             kw = dict(hint_shared=hint_shared, v_prediction=m.parameterization == "v", unguided=unguided)
-            if noise_row is not None:
-                rt.ddim_step_eta(x, pred, noise_row, float(sig[index]), *tail, staged=staged, **kw, **(blend or {}))
-            elif blend is None:
-                rt.ddim_step(x, pred, *tail, staged=staged, **kw)
-            else:
-                rt.ddim_step_masked(x, pred, *blend.values(), *tail, **kw)
+            with cs.step_modes(m, plan, i):
+                if noise_row is not None:
+                    rt.ddim_step_eta(x, pred, noise_row, float(sig[index]), *tail, staged=staged, **kw, **(blend or {}))
+                elif blend is None:
+                    rt.ddim_step(x, pred, *tail, staged=staged, **kw)
+                else:
+                    rt.ddim_step_masked(x, pred, *blend.values(), *tail, **kw)
 
         return captured_loop(self, img, mask, x0, time_range, live, shape_key, log_every_t, intermediates, "_loop_pred", first_step, emit)
 
@@ -501,12 +528,14 @@ class DDIMSampler(object):
                                noise_dropout):
             return self._loop_graphed(img, conditioning, unconditional_conditioning, unconditional_guidance_scale, time_range,
                                       total_steps, log_every_t, intermediates)
+        plan = control_plan(self, conditioning, unconditional_conditioning, unconditional_guidance_scale, total_steps)
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((batch_size,), int(step), device=device, dtype=torch.long)
-            img, pred_x0 = self.p_sample_ddim(img, conditioning, ts, index=index, temperature=temperature,
-                                              unconditional_guidance_scale=unconditional_guidance_scale,
-                                              unconditional_conditioning=unconditional_conditioning)
+            with cs.step_modes(self.model, plan, i):
+                img, pred_x0 = self.p_sample_ddim(img, conditioning, ts, index=index, temperature=temperature,
+                                                  unconditional_guidance_scale=unconditional_guidance_scale,
+                                                  unconditional_conditioning=unconditional_conditioning)
             if index % log_every_t == 0 or index == total_steps - 1:
                 intermediates["x_inter"].append(img)
                 intermediates["pred_x0"].append(pred_x0)
@@ -581,12 +610,16 @@ class DDIMSampler(object):
         total_steps = timesteps.shape[0]
         x_dec = x_latent
         self._cache_key = None
+        # a control schedule counts its window on the whole grid: decode walks its last t_start steps
+        full = self.ddim_timesteps.shape[0]
+        plan = None if use_original_steps else control_plan(self, cond, unconditional_conditioning, unconditional_guidance_scale, full)
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
-            x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index, use_original_steps=use_original_steps,
-                                          unconditional_guidance_scale=unconditional_guidance_scale,
-                                          unconditional_conditioning=unconditional_conditioning)
+            with cs.step_modes(self.model, plan, full - total_steps + i):
+                x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index, use_original_steps=use_original_steps,
+                                              unconditional_guidance_scale=unconditional_guidance_scale,
+                                              unconditional_conditioning=unconditional_conditioning)
             if callback:
                 callback(i)
         return x_dec

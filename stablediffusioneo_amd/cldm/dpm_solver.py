@@ -183,7 +183,8 @@ class DPMSolverSampler(object):
             assert x0 is not None
         x = self._run(img, c, uc, scale, self.timesteps, self.alphas, self.k_x, self.k_d, self.k_p, mask=mask, x0=x0, callback=callback,
                       img_callback=img_callback, ucg_schedule=ucg_schedule, log_every_t=log_every_t, intermediates=intermediates,
-                      k_n=self.k_n, temperature=temperature, noise_dropout=noise_dropout)
+                      k_n=self.k_n, temperature=temperature, noise_dropout=noise_dropout,
+                      plan=dh.control_plan(self._pair, c, uc, scale, total_steps))
         return x, intermediates
 
     def _step(self, x, d, c, uc, scale, k, timesteps, alphas, k_x, k_d, k_p, k_n=None, temperature=1., noise_dropout=0.):
@@ -205,8 +206,9 @@ class DPMSolverSampler(object):
                                      v_prediction=self.model.parameterization == "v")
 
     def _run(self, x, c, uc, scale, timesteps, alphas, k_x, k_d, k_p, mask=None, x0=None, callback=None, img_callback=None,
-             ucg_schedule=None, log_every_t=100, intermediates=None, k_n=None, temperature=1., noise_dropout=0.):
-        """the per-step path over a run of steps that starts without history (k_p[0] == 0)"""
+             ucg_schedule=None, log_every_t=100, intermediates=None, k_n=None, temperature=1., noise_dropout=0., plan=None):
+        """the per-step path over a run of steps that starts without history (k_p[0] == 0); plan: the control modes of every step
+        (`ddim_hacked.control_plan`), set before the step's model call"""
         total = len(timesteps)
         d = torch.empty_like(x, memory_format=torch.contiguous_format)
         for k in range(total):
@@ -217,7 +219,8 @@ class DPMSolverSampler(object):
             if ucg_schedule is not None:
                 assert len(ucg_schedule) == total
                 scale = ucg_schedule[k]
-            x = self._step(x, d, c, uc, scale, k, timesteps, alphas, k_x, k_d, k_p, k_n, temperature, noise_dropout)
+            with dh.cs.step_modes(self.model, plan, k):
+                x = self._step(x, d, c, uc, scale, k, timesteps, alphas, k_x, k_d, k_p, k_n, temperature, noise_dropout)
             if callback:
                 callback(k)
             if img_callback:
@@ -250,9 +253,12 @@ class DPMSolverSampler(object):
                      bool(m.only_mid_control), self._schedule_key, per_graph, hint_shared, m.parameterization,
                      None if mask is None else tuple(mask.shape), unguided, dh.ip_key(m), dh.freeu_key(m))
         live = [k_n is not None and float(k_n[i]) != 0. for i in range(total_steps)]
+        plan = dh.control_plan(self._pair, c, uc, scale, total_steps)      # the control schedule, as in `DDIMSampler._loop_graphed`
+        shape_key += (dh.loop_modes_key(m, plan),)
 
         def first_step(img, d):
-            x1 = self._step(img, d, c, uc, scale, 0, ts, a_t, k_x, k_d, k_p, k_n)
+            with dh.cs.step_modes(m, plan, 0):
+                x1 = self._step(img, d, c, uc, scale, 0, ts, a_t, k_x, k_d, k_p, k_n)
             return x1, d.clone()
 
         def emit(i, staged, noise_row, blend):
@@ -260,13 +266,14 @@ class DPMSolverSampler(object):
             x, d = self._loop_x, self._loop_d
             head = (i, scale, a, float(np.sqrt(1.0 - a)), float(k_x[i]), float(k_d[i]), float(k_p[i]))
             kw = dict(hint_shared=hint_shared, v_prediction=m.parameterization == "v", unguided=unguided)
-            if noise_row is not None:
-                rt.dpmpp_2m_sde_step(x, d, noise_row, *head, float(k_n[i]), m.net0_scales(), m.only_mid_control, staged=staged, **kw,
-                                     **(blend or {}))
-            elif blend is None:
-                rt.dpmpp_2m_step(x, d, *head, m.net0_scales(), m.only_mid_control, staged=staged, **kw)
-            else:
-                rt.dpmpp_2m_step_masked(x, d, *blend.values(), *head, m.net0_scales(), m.only_mid_control, **kw)
+            with dh.cs.step_modes(m, plan, i):
+                if noise_row is not None:
+                    rt.dpmpp_2m_sde_step(x, d, noise_row, *head, float(k_n[i]), m.net0_scales(), m.only_mid_control, staged=staged, **kw,
+                                         **(blend or {}))
+                elif blend is None:
+                    rt.dpmpp_2m_step(x, d, *head, m.net0_scales(), m.only_mid_control, staged=staged, **kw)
+                else:
+                    rt.dpmpp_2m_step_masked(x, d, *blend.values(), *head, m.net0_scales(), m.only_mid_control, **kw)
 
         return dh.captured_loop(self, img, mask, x0, time_range, live, shape_key, log_every_t, intermediates, "_loop_d", first_step, emit)
 
@@ -300,8 +307,10 @@ class DPMSolverSampler(object):
         k_x, k_d, k_p, k_n = self._coefficients(alphas, alphas_next)
         self._pair._cache_key = None
         x = x_latent.to(device=self.model.device, dtype=torch.float32)
+        # a control schedule counts its window on the whole grid: decode walks its last t_start steps
+        plan = dh.control_plan(self._pair, cond, unconditional_conditioning, unconditional_guidance_scale, total)
         return self._run(x, cond, unconditional_conditioning, unconditional_guidance_scale, self.timesteps[first:], alphas, k_x, k_d, k_p,
-                         callback=callback, k_n=k_n)
+                         callback=callback, k_n=k_n, plan=None if plan is None else plan[first:])
 
 
 class DPMSolverSDESampler(DPMSolverSampler):

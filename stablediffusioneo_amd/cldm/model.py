@@ -56,11 +56,13 @@ def _from_params(p):
 
 
 def create_model(config_path=None, cond_stage_model=None, device=None, weight_bits=16, vae_encoder=False, extra_controlnets=0,
-                 ip_adapter_tokens=0):
+                 ip_adapter_tokens=0, control_modes=False):
     """vae_encoder=True: the runtime also holds the VAE encoder (encode_first_stage / get_first_stage_encoding, img2img).
     extra_controlnets=k: 1 + k control networks on the one UNet (their residuals are summed; `ControlLDM.apply_model`).
     ip_adapter_tokens=T: an image-prompt adapter of T tokens per image on every UNet cross-attention (`ControlLDM.load_ip_adapter`,
-    `set_ip_image_embeds`, `set_ip_tokens`)."""
+    `set_ip_image_embeds`, `set_ip_tokens`).
+    control_modes=True: the runtime can run each control network on both halves of the CFG pair, on the conditional half only or not
+    at all, which `ControlLDM.control_schedule` (`cldm/control_schedule.py`) needs."""
     ucfg, vcfg, sched = _NAMED["sd15"]
     if isinstance(config_path, str) and config_path in _NAMED:
         ucfg, vcfg, sched = _NAMED[config_path]
@@ -71,7 +73,7 @@ def create_model(config_path=None, cond_stage_model=None, device=None, weight_bi
         cfg = yaml.safe_load(open(config_path))
         ucfg, sched = _from_params(cfg.get("model", {}).get("params", {}))
     rt = SdeoRuntime(ucfg, vcfg, device=device, weight_bits=weight_bits, vae_encoder=vae_encoder, extra_controlnets=extra_controlnets,
-                     ip_adapter_tokens=ip_adapter_tokens)
+                     ip_adapter_tokens=ip_adapter_tokens, control_modes=control_modes)
     model = ControlLDM(rt, schedule=sched, cond_stage_model=cond_stage_model)
     print(f"Loaded model config from [{config_path}]")
     return model

@@ -65,10 +65,19 @@ namespace sdeo {
 // EPI (EpiKind, conv_inl.h): EPI_DIRECT deals the weight rows of each wave's strip to the LDS rows in the order of direct_row_chan
 // (a change of the loaders' SOURCE rows only: the LDS image, the fragment reads and the K loop are those of EPI_STAGED, so the
 // fragment reads stay bank-conflict free) and stores from the accumulators (epilogue_direct); the staged epilogue is not compiled in.
-template <int BM, int BN, int STAGES, bool UPS, bool WS, bool W8 = false, int KPB = 1, bool MX = false, bool MULTI = false, int EPI = EPI_STAGED>
-__global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const std::conditional_t<MULTI, MPArgs, KP> pp) {
+// LIVE (with MULTI; the argument is an MPArgsLive): problem i computes its first m_live[i] rows only.  An M tile wholly at or beyond
+// m_live runs no K loop (nk = 0: the loaders issue nothing, the MFMA waves go straight to the pre-epilogue barrier) and copies its `res`
+// rows to the output; the tile that straddles m_live computes, its epilogue stores the live rows only (mrow = -1 for the others, the
+// state rows beyond M have in every launch) and the rows left over are copied.  A dead row is SELECTED, never scaled: what the
+// activation rows beyond m_live hold does not reach the output.  res == y (an in-place problem): nothing is copied.  With LIVE = false
+// none of this is compiled.
+template <int BM, int BN, int STAGES, bool UPS, bool WS, bool W8 = false, int KPB = 1, bool MX = false, bool MULTI = false, int EPI = EPI_STAGED,
+          bool LIVE = false>
+__global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const std::conditional_t<LIVE, MPArgsLive, std::conditional_t<MULTI, MPArgs, KP>> pp) {
   kernarg_warm<sizeof(pp)>();
   static_assert(!MULTI || (!W8 && !MX), "multi-problem launches stream fp16 weights");
+  static_assert(!LIVE || MULTI, "live-row counts come with the multi-problem argument");
+  static_assert(!LIVE || !WS, "the pass-through of the dead rows strides by the 256 threads of a four-wave workgroup");
   static_assert(EPI == EPI_STAGED || (!W8 && !MX && !MULTI && !UPS), "the register-direct epilogue exists for the plain fp16 kernels");
   // The scalars both roles need before their first DMA / fragment read, fetched in ONE batch and pinned in SGPRs: left to the
   // compiler each is an s_load + s_waitcnt lgkmcnt(0) next to its first use, ten dependent scalar round trips in front of the
@@ -128,7 +137,9 @@ __global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const std
   const int z = blockIdx.z;
   const int kbeg = z * p.nk_per_split;
   const int kend = min(p.nk, kbeg + p.nk_per_split);
-  const int nk = kend - kbeg;
+  [[maybe_unused]] int m_live = 0;
+  if constexpr (LIVE) m_live = __builtin_amdgcn_readfirstlane(min(max(pp.m_live[mp_prob], 0), p.M));
+  const int nk = (LIVE && m0 >= m_live) ? 0 : kend - kbeg;     // (m0 is uniform: every wave of a dead tile skips the K loop)
 
   stamp(p, 0);
   const int chunk = tid & 7, lrow = tid >> 3;
@@ -538,7 +549,19 @@ __global__ __launch_bounds__(WS ? 512 : 256) void conv_gemm_dma_kernel(const std
 #pragma unroll
   for (int j = 0; j < MI; ++j) {
     const int m = m0 + wm * TM + j * 16 + frow;
-    mrow[j] = m < pe.M ? m : -1;
+    mrow[j] = m < (LIVE ? m_live : pe.M) ? m : -1;
+  }
+  if constexpr (LIVE) {
+    // the rows of this tile at or beyond m_live: out = res, 8 bytes per lane (N, ldy, ldres % 4 == 0 and 8-byte aligned bases: host-checked)
+    if (pe.res && pe.res != pe.y) {
+      const int r0 = max(m0, m_live), r1 = min(m0 + BM, pe.M);
+      const int c4 = min(BN, pe.N - n0) >> 2;
+      for (int idx = tid; idx < (r1 - r0) * c4; idx += 256) {
+        const int r = r0 + idx / c4, c = n0 + (idx % c4) * 4;
+        *reinterpret_cast<uint2*>(pe.y + (size_t)r * pe.ldy + c) = *reinterpret_cast<const uint2*>(pe.res + (size_t)r * pe.ldres + c);
+      }
+    }
+    if (m0 >= m_live) return;              // a dead tile has nothing to store (uniform; no barrier follows for a multi-problem launch)
   }
   const float2* lnrow = ln_lds ? lnsm + wm * TM : nullptr;
   // One epilogue in the code.  SDEO_DBG_GEMM bit 128 takes a second trip through THE SAME instructions (a loop the compiler may not
@@ -821,12 +844,13 @@ static int launch_dma(const KP& kp, int tiles, hipStream_t stream) {
 
 // multi-problem launch of one instantiation (conv_gemm_dma_kernel MULTI): `tiles` = the sum over the problems
 typedef int (*MultiLaunch)(const MPArgs& a, int tiles, hipStream_t stream);
-template <int BM, int BN, int ST, bool WS>
-static int launch_dma_multi(const MPArgs& a, int tiles, hipStream_t stream) {
+typedef int (*MultiLiveLaunch)(const MPArgsLive& a, int tiles, hipStream_t stream);
+template <int BM, int BN, int ST, bool WS, bool LIVE = false>
+static int launch_dma_multi(const std::conditional_t<LIVE, MPArgsLive, MPArgs>& a, int tiles, hipStream_t stream) {
   static DeviceOnce done;
   constexpr int smem = ST * (BM + BN) * 128 + BM * 8;
   static_assert(smem <= 160 * 1024, "LDS");
-  auto kernel = &conv_gemm_dma_kernel<BM, BN, ST, false, WS, false, 1, false, true>;
+  auto kernel = &conv_gemm_dma_kernel<BM, BN, ST, false, WS, false, 1, false, true, EPI_STAGED, LIVE>;
   if (done.need()) {
     SDEO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     done.mark();
@@ -1281,11 +1305,12 @@ int conv_gemm(const ConvGemm& p0, hipStream_t stream) {
 
 // The rows of kTiles that have a multi-problem instantiation (the table itself is untouched: a multi-problem launch is asked for by
 // name, never planned).  Each costs one more kernel, so there are as many as there are users.
-struct MultiTile { int tile, bm, bn, stages; bool light; MultiLaunch launch; const char* name; };
+// launch_live: the live-row instantiation (conv_gemm_multi_launch_live), where a user exists: the zero convs' tile.
+struct MultiTile { int tile, bm, bn, stages; bool light; MultiLaunch launch; const char* name; MultiLiveLaunch launch_live; };
 static const MultiTile kMultiTiles[] = {
-    {2, 64, 64, 4, false, &launch_dma_multi<64, 64, 4, true>, "conv_gemm_dma_kernel<64,64,4> multi"},
-    {6, 64, 160, 3, false, &launch_dma_multi<64, 160, 3, true>, "conv_gemm_dma_kernel<64,160,3> multi"},
-    {26, 128, 64, 2, true, &launch_dma_multi<128, 64, 2, false>, "conv_gemm_dma_kernel<128,64,2> multi"},
+    {2, 64, 64, 4, false, &launch_dma_multi<64, 64, 4, true>, "conv_gemm_dma_kernel<64,64,4> multi", nullptr},
+    {6, 64, 160, 3, false, &launch_dma_multi<64, 160, 3, true>, "conv_gemm_dma_kernel<64,160,3> multi", nullptr},
+    {26, 128, 64, 2, true, &launch_dma_multi<128, 64, 2, false>, "conv_gemm_dma_kernel<128,64,2> multi", &launch_dma_multi<128, 64, 2, false, true>},
 };
 static const MultiTile* multi_tile(int tile) {
   for (const MultiTile& m : kMultiTiles) {
@@ -1343,6 +1368,30 @@ int conv_gemm_multi_launch(const ConvGemmMultiPlan& pl, const void* table_dev, c
   g_last_tile = pl.tile; g_last_splitk = 1; g_last_epilogue = EPI_STAGED;
   ++g_census[{pl.tile, 1, 4, EPI_STAGED, 0}];
   return mt->launch(a, pl.tiles, stream);
+}
+
+int conv_gemm_multi_launch_live(const ConvGemmMultiPlan& pl, const void* table_dev, const float* scales, const int* m_live, hipStream_t stream) {
+  const MultiTile* mt = multi_tile(pl.tile);
+  SDEO_CHECK(mt && pl.count >= 1 && pl.count <= kMultiMax && pl.tiles > 0 && pl.table.size() == sizeof(MPTable), "conv_gemm_multi: launch of an unplanned table");
+  SDEO_CHECK(mt->launch_live, "conv_gemm_multi: tile %d has no live-row instantiation", pl.tile);
+  SDEO_CHECK(table_dev && (reinterpret_cast<uintptr_t>(table_dev) & 15) == 0, "conv_gemm_multi: the device table must be 16-byte aligned");
+  SDEO_CHECK(m_live, "conv_gemm_multi: live-row counts required");
+  const MPTable* tab = reinterpret_cast<const MPTable*>(pl.table.data());
+  MPArgsLive a{};
+  a.tab = static_cast<const MPTable*>(table_dev);
+  a.count = pl.count;
+  for (int i = 0; i < pl.count; ++i) {
+    const KP& kp = tab->kp[i];
+    SDEO_CHECK(m_live[i] >= 0 && m_live[i] <= kp.M, "conv_gemm_multi: problem %d: %d live rows of %d", i, m_live[i], kp.M);
+    // the pass-through of the dead rows moves 8 bytes per lane
+    SDEO_CHECK(kp.y && !kp.y32 && kp.res_rows == kp.M && kp.N % 4 == 0 && kp.ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(kp.y) & 7) == 0 &&
+                   (!kp.res || (kp.ldres % 4 == 0 && (reinterpret_cast<uintptr_t>(kp.res) & 7) == 0)),
+               "conv_gemm_multi: problem %d: the live-row form needs an fp16 output and a one-to-one residual, 8-byte aligned, N / ldy / ldres multiples of 4", i);
+    a.scale[i] = scales ? scales[i] : pl.scale[i];
+    a.m_live[i] = m_live[i];
+  }
+  g_last_tile = pl.tile; g_last_splitk = 1; g_last_epilogue = EPI_STAGED;
+  return mt->launch_live(a, pl.tiles, stream);
 }
 
 int conv_gemm_tile_info(int tile, int* kind, int* bm, int* bn, int* stages, int* caps, const char** name) {

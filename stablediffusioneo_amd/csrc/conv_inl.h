@@ -75,6 +75,15 @@ struct MPArgs {
   int count;
   float scale[kMultiMax];
 };
+// The argument of the live-row instantiation (conv_gemm_dma_kernel<..., MULTI, LIVE>): MPArgs plus, per problem, how many of its M rows
+// are live.  Rows at or beyond m_live are not computed: they receive their `res` row as it is (nothing when res is the output itself).
+// A type of its own, so that MPArgs -- the argument of the plain multi-problem kernel -- stays what it was.
+struct MPArgsLive {
+  const MPTable* tab;
+  int count;
+  float scale[kMultiMax];
+  int m_live[kMultiMax];
+};
 // reads of the table go through the constant address space: it does not change under the launch, and loads from there at a uniform
 // address are scalar ones (one s_load_dwordx16 for the prefix sums, a batch of them for a block)
 __device__ __forceinline__ int mp_prefix(const MPTable* tab, int i) {

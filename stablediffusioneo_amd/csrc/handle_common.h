@@ -299,6 +299,10 @@ struct Op {          // one launch of a program + what it is for the profiler
   double flops = 0, bytes = 0;
   bool zero_conv = false;    // net_build.hip's ControlNet program: a zero conv (skipped when the UNet decoder applies the zero convs itself)
   bool freeu = false;        // net_build.hip's UNet decoders: a FreeU launch (only in the programs a handle runs with sdeo_set_freeu on)
+  // net_build.hip's fused UNet decoder: a launch that applies control net zc_net's zero convs (-1: any other launch) in the form
+  // zc_form, bits ZC_COND (the first half of the batch only) | ZC_FIRST (no active net in front: the residual is the skip).  A handle
+  // with sdeo_enable_control_modes holds every form and runs, per net, the one its mode asks for (net.hip: run_decoder)
+  signed char zc_net = -1, zc_form = 0;
   template <class F>
   Op(F f, const char* key_ = "other", double flops_ = 0, double bytes_ = 0, std::string tag_ = std::string())
       : fn(std::move(f)), key(key_), tag(std::move(tag_)), flops(flops_), bytes(bytes_) {}
@@ -382,7 +386,9 @@ static inline Op conv_gemm_op(const ConvGemm& p0, WorkspaceRef ws, size_t* max_w
 // Several unsplit conv / GEMM problems on one tile as ONE launch (kernels.h: conv_gemm_multi_plan).  The device table is written here,
 // once, and lives as long as the op; scale_host[i] (optional, may hold nulls) is problem i's `scale`, read when the launch runs.  A
 // set of problems the launcher refuses gives an op that fails with that message.  Profile key: the tile's kernel + "multi xN".
-static inline Op conv_gemm_multi_op(const std::vector<ConvGemm>& ps, int tile, std::vector<const float*> scale_host = {}) {
+// m_live (optional, one per problem): the live-row form (conv_gemm_multi_launch_live); flops and bytes then count the live rows.
+static inline Op conv_gemm_multi_op(const std::vector<ConvGemm>& ps, int tile, std::vector<const float*> scale_host = {},
+                                    std::vector<int> m_live = {}) {
   static std::set<std::string> keys;       // Op::key is a C string that outlives the op
   auto pl = std::make_shared<ConvGemmMultiPlan>();
   std::shared_ptr<void> dev;
@@ -398,13 +404,23 @@ static inline Op conv_gemm_multi_op(const std::vector<ConvGemm>& ps, int tile, s
     dev.reset(d, [](void* q) { if (q) (void)hipFree(q); });
   }
   scale_host.resize(ps.size(), nullptr);
-  const char* key = keys.insert(std::string(err.empty() ? pl->name : "conv_gemm multi") + " x" + std::to_string(ps.size())).first->c_str();
-  return Op([pl, dev, err, scale_host](hipStream_t s) {
+  const char* key = keys.insert(std::string(err.empty() ? pl->name : "conv_gemm multi") + (m_live.empty() ? "" : " live") + " x" + std::to_string(ps.size())).first->c_str();
+  if (!m_live.empty() && m_live.size() != ps.size() && err.empty()) err = "conv_gemm_multi: one live-row count per problem";
+  double flops = pl->flops, bytes = pl->bytes;
+  if (!m_live.empty() && err.empty()) {
+    flops = bytes = 0;
+    for (size_t i = 0; i < ps.size(); ++i) {
+      flops += 2.0 * m_live[i] * ps[i].N * (double)ps[i].K;
+      bytes += 2.0 * ((double)m_live[i] * ps[i].Cin + (double)ps[i].N * ps[i].K + (double)ps[i].M * ps[i].N);
+    }
+  }
+  return Op([pl, dev, err, scale_host, m_live](hipStream_t s) {
     if (!err.empty()) return fail("%s", err.c_str());
     float sc[kMultiMax];
     for (int i = 0; i < pl->count; ++i) sc[i] = scale_host[i] ? *scale_host[i] : pl->scale[i];
+    if (!m_live.empty()) return conv_gemm_multi_launch_live(*pl, dev.get(), sc, m_live.data(), s);
     return conv_gemm_multi_launch(*pl, dev.get(), sc, s);
-  }, key, pl->flops, pl->bytes, "tiles" + std::to_string(pl->tiles));
+  }, key, flops, bytes, "tiles" + std::to_string(pl->tiles) + (m_live.empty() ? "" : " live"));
 }
 
 // profiling off (or no profiler): one std::function call per op and nothing else

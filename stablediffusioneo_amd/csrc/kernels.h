@@ -90,6 +90,11 @@ struct ConvGemmMultiPlan {
 };
 int conv_gemm_multi_plan(const std::vector<ConvGemm>& ps, int tile, ConvGemmMultiPlan* out);
 int conv_gemm_multi_launch(const ConvGemmMultiPlan& pl, const void* table_dev, const float* scales, hipStream_t stream);
+// The live-row form of the same launch (its own kernel instantiation; the zero convs' tile has one): problem i computes its first
+// m_live[i] rows (0..M) and every row beyond them receives its `res` row unchanged -- selected, not scaled, so what x holds there never
+// matters; nothing is written there when res is the output itself or null.  Row tiles wholly beyond m_live run no K loop.  The live
+// rows are bit-identical to conv_gemm_multi_launch's.  Needs fp16 outputs, one residual row per output row, N / ldy / ldres % 4 == 0.
+int conv_gemm_multi_launch_live(const ConvGemmMultiPlan& pl, const void* table_dev, const float* scales, const int* m_live, hipStream_t stream);
 // M tiles per image of the plan chosen for p when its epilogue can emit GroupNorm partials for groups of cpg channels, else 0
 int conv_gemm_gn_slots(const ConvGemm& p, int cpg);
 // whether the plan chosen for p is a halo-reuse 3x3 kernel (which has no fp8-weight variant)

@@ -21,6 +21,44 @@ static const Program& decoder_program(const Engine* e, ProgId id) {
   return e->prog_freeu[id == P_UNET_DEC ? 0 : id == P_UNET_DEC_FUSED ? 1 : 2];
 }
 
+// Control modes of one call (sdeo_set_control_mode), as the call sees them: without a second half (an unguided step) COND means BOTH.
+struct CallModes {
+  int m[kMaxControlNets] = {0};
+  bool any_cond = false, all_off = false, all_both = true;
+};
+static CallModes call_modes(const Engine* e, bool has_second_half) {
+  CallModes cm;
+  if (!e->control_modes) return cm;
+  cm.all_off = true;
+  for (int j = 0; j <= e->extra; ++j) {
+    cm.m[j] = e->cmode[j] == SDEO_CONTROL_COND && !has_second_half ? SDEO_CONTROL_BOTH : e->cmode[j];
+    cm.any_cond |= cm.m[j] == SDEO_CONTROL_COND;
+    cm.all_off &= cm.m[j] == SDEO_CONTROL_OFF;
+    cm.all_both &= cm.m[j] == SDEO_CONTROL_BOTH;
+  }
+  return cm;
+}
+
+// The fused decoder under the modes of this call: of each net's zero-conv launches the one form its mode asks for -- none for an OFF
+// net; for the others all rows or the first half, with the skip as the residual for the first active net and in place behind it.
+// All BOTH picks exactly the launches a plain handle's program holds.
+static int run_decoder(Engine* e, const Program& p, const CallModes& cm, hipStream_t s) {
+  if (!e->control_modes) return run(e, p, s);
+  int want[kMaxControlNets];
+  bool seen = false;
+  for (int j = 0; j < kMaxControlNets; ++j) {
+    want[j] = -1;
+    if (j > e->extra || cm.m[j] == SDEO_CONTROL_OFF) continue;
+    want[j] = (cm.m[j] == SDEO_CONTROL_COND ? 1 : 0) | (seen ? 0 : 2);      // (ZC_COND | ZC_FIRST of net_build.hip)
+    seen = true;
+  }
+  for (auto& op : p) {
+    if (op.zc_net >= 0 && op.zc_form != want[(int)op.zc_net]) continue;
+    if (int rc = e->prof.on ? e->prof.record(op, s) : op(s)) return rc;
+  }
+  return 0;
+}
+
 template <typename Tp>
 static int dev_alloc(Engine* e, Tp** p, size_t bytes) {
   void* v = nullptr;
@@ -41,6 +79,8 @@ static void free_configured(Engine* e) {
   for (Program& p : e->prog) p.clear();
   for (Program& p : e->prog_freeu) p.clear();
   for (auto& px : e->xprog) for (Program& p : px) p.clear();
+  for (Program& p : e->cn_half) p.clear();
+  for (int& m : e->cmode) m = SDEO_CONTROL_BOTH;          // the control modes return to BOTH
   for (int j = 0; j < kMaxControlNets - 1; ++j) {        // the hint caches are gone with the arenas, the scales return to 1
     for (float& v : e->extra_scales[j]) v = 1.0f;
   }
@@ -182,6 +222,25 @@ int sdeo_enable_ip_adapter(sdeo_handle h, int num_tokens) {
   return 0;
 }
 
+int sdeo_enable_control_modes(sdeo_handle h) {
+  SDEO_CHECK(h, "sdeo_enable_control_modes: null handle");
+  SDEO_CHECK(!configured(h), "sdeo_enable_control_modes: call it before sdeo_configure");
+  SDEO_CHECK(h->fp8.weight_bits != 8, "sdeo_enable_control_modes: fp8 weights (sdeo_set_weight_precision 8) are not supported with control modes");
+  SDEO_CHECK(h->fp8.act_bits != 8, "sdeo_enable_control_modes: block-scaled fp8 activations (sdeo_set_activation_precision 8) are not supported with control modes");
+  h->control_modes = true;
+  return 0;
+}
+
+int sdeo_set_control_mode(sdeo_handle h, int net, int mode) {
+  SDEO_CHECK(h, "sdeo_set_control_mode: null handle");
+  SDEO_CHECK(h->control_modes, "sdeo_set_control_mode: this handle has no control modes (call sdeo_enable_control_modes before sdeo_configure)");
+  SDEO_CHECK(net >= 0 && net <= h->extra, "sdeo_set_control_mode: net %d out of range (0..%d)", net, h->extra);
+  SDEO_CHECK(mode == SDEO_CONTROL_BOTH || mode == SDEO_CONTROL_COND || mode == SDEO_CONTROL_OFF,
+             "sdeo_set_control_mode: mode %d is none of SDEO_CONTROL_BOTH, SDEO_CONTROL_COND, SDEO_CONTROL_OFF", mode);
+  h->cmode[net] = mode;
+  return 0;
+}
+
 static int configure_impl(sdeo_handle h, int n, int latent_h, int latent_w) {
   free_configured(h);
   h->ip_scale = 1.0f;
@@ -251,6 +310,8 @@ int sdeo_configure(sdeo_handle h, int n, int latent_h, int latent_w) {
   SDEO_CHECK(latent_h >= maxds && latent_w >= maxds && latent_h % maxds == 0 && latent_w % maxds == 0,
              "sdeo_configure: latent %dx%d must be a positive multiple of %d", latent_h, latent_w, maxds);
   SDEO_CHECK(h->fp8.weight_bits != 8 || h->fp8.q8slab, "sdeo_configure: fp8 weights are packed by sdeo_finalize_weights: call it first");
+  SDEO_CHECK(!h->control_modes || (h->fp8.weight_bits != 8 && h->fp8.act_bits != 8),
+             "sdeo_configure: control modes (sdeo_enable_control_modes) are not supported with fp8 weights or block-scaled fp8 activations");
   const int rc = configure_impl(h, n, latent_h, latent_w);
   if (rc) free_configured(h);
   return rc;
@@ -314,28 +375,35 @@ static int select_time(sdeo_handle h, int flags, const int64_t* timesteps, const
 
 // The time embeddings of the extra control networks.  They run in FRONT of net 0's ControlNet: their temporaries were planned on the
 // empty side arena, where net 0's block outputs (kept until the decoder has run) live afterwards.
-static int run_extra_time_embeds(sdeo_handle h, hipStream_t s) {
-  for (int j = 1; j <= h->extra; ++j) if (int rc = run(h, cn_prog(h, j, CP_TEMB), s)) return rc;
+static int run_extra_time_embeds(sdeo_handle h, const CallModes& cm, hipStream_t s) {
+  for (int j = 1; j <= h->extra; ++j)
+    if (cm.m[j] != SDEO_CONTROL_OFF) if (int rc = run(h, cn_prog(h, j, CP_TEMB), s)) return rc;
   return 0;
 }
 
+// control net j's program of this call, without its zero convs: none for an OFF net, the half-batch one for a COND net, else the
+// full-batch one or, where the caller vouches for the hints and configure built it, its shared-prefix variant
+static int run_controlnet(sdeo_handle h, int j, const CallModes& cm, bool shared_cn, hipStream_t s) {
+  if (cm.m[j] == SDEO_CONTROL_OFF) return 0;
+  if (cm.m[j] == SDEO_CONTROL_COND) return run(h, h->cn_half[j], s);
+  const Program& sh = cn_prog(h, j, CP_CN_SH);
+  return run(h, shared_cn && !sh.empty() ? sh : cn_prog(h, j, CP_CN), s, true);
+}
+
 // the extra control networks, one behind the other on the stream net 0's ControlNet ran on, without their zero convs
-static int run_extra_controlnets(sdeo_handle h, bool shared_cn, hipStream_t s) {
-  for (int j = 1; j <= h->extra; ++j) {
-    const Program& sh = cn_prog(h, j, CP_CN_SH);
-    if (int rc = run(h, shared_cn && !sh.empty() ? sh : cn_prog(h, j, CP_CN), s, true)) return rc;
-  }
+static int run_extra_controlnets(sdeo_handle h, const CallModes& cm, bool shared_cn, hipStream_t s) {
+  for (int j = 1; j <= h->extra; ++j) if (int rc = run_controlnet(h, j, cm, shared_cn, s)) return rc;
   return 0;
 }
 
 // ControlNet || UNet encoder, join, UNet decoder: eps16 holds the result.  The latent is already in x0.
 // shared_unet / shared_cn: the two halves of the batch are the same images at the same timestep (and, for the ControlNet, under the same
 // hint): run the programs whose shared prefix is computed once, where configure built them
-static int run_step_programs(sdeo_handle h, bool no_control, bool time_from_table, hipStream_t s, bool shared_unet = false,
+// cm: the control modes of this call (call_modes).  Every net OFF is the no-control program: no fork, no ControlNet launch.
+static int run_step_programs(sdeo_handle h, bool no_control, bool time_from_table, hipStream_t s, const CallModes& cm, bool shared_unet = false,
                              bool shared_cn = false) {
   const Program& p_unet_enc = shared_unet && !h->prog[P_UNET_ENC_SH].empty() ? h->prog[P_UNET_ENC_SH] : h->prog[P_UNET_ENC];
-  const Program& p_cn = shared_cn && !h->prog[P_CN_SH].empty() ? h->prog[P_CN_SH] : h->prog[P_CN];
-  if (no_control) {
+  if (no_control || cm.all_off) {
     if (!time_from_table) if (int rc = run(h, h->prog[P_TEMB + 0], s)) return rc;
     return run(h, decoder_program(h, P_UNET_NOCTRL), s);
   }
@@ -344,26 +412,26 @@ static int run_step_programs(sdeo_handle h, bool no_control, bool time_from_tabl
     SDEO_HIP(hipEventRecord(h->ev_fork, s));
     SDEO_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
     if (!time_from_table) {
-      if (int rc = run(h, h->prog[P_TEMB + 1], h->side)) return rc;
-      if (int rc = run_extra_time_embeds(h, h->side)) return rc;
+      if (cm.m[0] != SDEO_CONTROL_OFF) if (int rc = run(h, h->prog[P_TEMB + 1], h->side)) return rc;
+      if (int rc = run_extra_time_embeds(h, cm, h->side)) return rc;
     }
-    if (int rc = run(h, p_cn, h->side, true)) return rc;
-    if (int rc = run_extra_controlnets(h, shared_cn, h->side)) return rc;
+    if (int rc = run_controlnet(h, 0, cm, shared_cn, h->side)) return rc;
+    if (int rc = run_extra_controlnets(h, cm, shared_cn, h->side)) return rc;
     SDEO_HIP(hipEventRecord(h->ev_join, h->side));
     if (!time_from_table) if (int rc = run(h, h->prog[P_TEMB + 0], s)) return rc;
     if (int rc = run(h, p_unet_enc, s)) return rc;
     SDEO_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
   } else {
     if (!time_from_table) {
-      if (int rc = run(h, h->prog[P_TEMB + 1], s)) return rc;
-      if (int rc = run_extra_time_embeds(h, s)) return rc;
+      if (cm.m[0] != SDEO_CONTROL_OFF) if (int rc = run(h, h->prog[P_TEMB + 1], s)) return rc;
+      if (int rc = run_extra_time_embeds(h, cm, s)) return rc;
       if (int rc = run(h, h->prog[P_TEMB + 0], s)) return rc;
     }
-    if (int rc = run(h, p_cn, s, true)) return rc;
-    if (int rc = run_extra_controlnets(h, shared_cn, s)) return rc;
+    if (int rc = run_controlnet(h, 0, cm, shared_cn, s)) return rc;
+    if (int rc = run_extra_controlnets(h, cm, shared_cn, s)) return rc;
     if (int rc = run(h, p_unet_enc, s)) return rc;
   }
-  return run(h, decoder_program(h, P_UNET_DEC_FUSED), s);      // applies the zero convs itself (skipped above)
+  return run_decoder(h, decoder_program(h, P_UNET_DEC_FUSED), cm, s);      // applies the zero convs itself (skipped above)
 }
 
 // copy net j's hint in and run its hint block into its cached features (j >= 1; net 0's goes through stage_inputs)
@@ -516,6 +584,9 @@ int sdeo_apply_model(sdeo_handle h, const float* x_noisy, const float* hint, con
   const int hint_new = !(flags & SDEO_HINT_CACHED), ctx_new = !(flags & SDEO_CONTEXT_CACHED), no_control = (flags & SDEO_NO_CONTROL) != 0;
   SDEO_CHECK(!ctx_new || context, "sdeo_apply_model: context required");
   SDEO_CHECK(no_control || !hint_new || hint, "sdeo_apply_model: hint required");
+  const CallModes cm = call_modes(h, true);
+  SDEO_CHECK(no_control || !cm.any_cond || h->N % 2 == 0, "sdeo_apply_model: SDEO_CONTROL_COND runs the control network on the first n / 2 images, "
+             "the conditional half of [cond; uncond]: configured for %d images, an odd count", h->N);
   const int sides = no_control ? CacheRecord::UNET : CacheRecord::BOTH;      // whose context K / V this call runs on
   if (!no_control) if (int rc = h->cache.extra_hints("sdeo_apply_model", h->extra)) return rc;
   if (int rc = h->cache.cached_reads("sdeo_apply_model", no_control || hint_new ? -1 : 0, ctx_new ? 0 : sides)) return rc;
@@ -527,7 +598,7 @@ int sdeo_apply_model(sdeo_handle h, const float* x_noisy, const float* hint, con
     return rc;
   set_scales(h, host_control_scales, only_mid_control);
   if (int rc = run_x0(h, s)) return rc;
-  if (int rc = run_step_programs(h, no_control, trow >= 0, s)) return rc;
+  if (int rc = run_step_programs(h, no_control, trow >= 0, s, cm)) return rc;
   if (int rc = run(h, h->prog[P_EPS_EXPORT], s)) return rc;
   return copy_in(eps, h->out_eps, (size_t)h->N * h->cfg.out_channels * h->lh * h->lw * 4, s);
 }
@@ -592,7 +663,7 @@ static int cfg_pair_forward(sdeo_handle h, float* x, int table_row, const float*
     if (int rc = latent_pair_to_nhwc(h->x0.p, h->x0.ld, x, b, h->cfg.in_channels, h->lh * h->lw, paired, s)) return rc;
   }
   // x0 = [x; x] at one timestep: the UNet's shared prefix always holds, the ControlNet's when the caller vouches for the hints
-  return run_step_programs(h, false, true, s, paired, paired && (flags & SDEO_STEP_HINT_SHARED) != 0);
+  return run_step_programs(h, false, true, s, call_modes(h, paired), paired, paired && (flags & SDEO_STEP_HINT_SHARED) != 0);
 }
 
 // One fused CFG-pair step as its entry point describes it: which update, its coefficients, the optional noise term and the optional blend.

@@ -67,7 +67,9 @@ struct Builder {
   // cross-attention run on the first N / 2 images; build_res / build_attn raise `half` around those ops.  A half-batch launch keeps the
   // full-batch tensors (same arena plan, it writes a prefix of them) and the full-batch problem's kernel plan (ConvGemm::plan_B,
   // AttnArgs::plan_B), so every row it writes is bit-identical to the full-batch launch's.
-  bool share = false, half = false;
+  // half_all: the program built now runs EVERY launch on the first N / 2 images (a control net in SDEO_CONTROL_COND: build_controlnet);
+  // `half` then stays raised, under the same two promises.
+  bool share = false, half = false, half_all = false;
   bool borrowed_plan = false;      // gemm() -> launch_conv(): plan_B comes from ConvOpts::plan_rows
   Program* prog = nullptr;
   size_t max_splitk = 0, max_gn = 0;
@@ -119,7 +121,7 @@ struct Builder {
     e->fp8.use_mx(p, Mplan, *this);
     e->fp8.use_fp8_weights(p, Mplan, e->ws.slab);
     const size_t tune_ws = e->autotune ? conv_gemm_autotune_workspace_bytes(p) : 0;
-    if (!dry && e->autotune && !share) {       // (the shared variant of a block runs the plans its full-batch build measured)
+    if (!dry && e->autotune && !share && !half_all) {       // (the shared variant of a block runs the plans its full-batch build measured)
       ConvGemm q = p;
       q.workspace = lane->splitk_ws;
       q.workspace_bytes = lane->splitk_ws_bytes;
@@ -133,7 +135,7 @@ struct Builder {
         p.gn_out = gn_y->gnp; p.gn_cpg = cpg; p.gn_slots = slots; p.gn_groups = 32;
       }
     }
-    if (!dry && !share && getenv("SDEO_DUMP_GEMM"))   // shape census for tools/tune_gemm.py
+    if (!dry && !share && !half_all && getenv("SDEO_DUMP_GEMM"))   // shape census for tools/tune_gemm.py
       fprintf(stderr, "SDEO_GEMM %d %d %d %d %d %d %d %d %d %d %s\n", p.M, p.N, p.K, p.Cin, p.R, p.stride, p.ups, p.B, p.Hi, p.Wi,
               conv_gemm_kernel_name(p));
     bool stats_by_kernel = false;
@@ -389,7 +391,7 @@ static T build_vae_res(Builder& b, const std::string& p, const T& x, int cin, in
 
 static T build_res(Builder& b, const std::string& ns, const Blk& blk, const T& x, int net, const T* out = nullptr) {
   const std::string p = ns + blk.name;
-  b.half = b.share;              // the ResBlock in front of the first transformer: both halves of the CFG pair are the same images
+  b.half = b.share || b.half_all;      // the ResBlock in front of the first transformer: both halves of the CFG pair are the same images
   Builder::CO o1;
   o1.bias2_off = b.e->emb_row.at(p);
   o1.bias2 = b.e->emb_all[net] + o1.bias2_off;     // what planning / autotune see; the launch reads emb_cur / emb_ld_cur
@@ -397,7 +399,7 @@ static T build_res(Builder& b, const std::string& ns, const Blk& blk, const T& x
   o1.bias2_cur = &b.e->emb_cur[net];
   o1.ld_bias2_cur = &b.e->emb_ld_cur[net];
   T y = build_resblock(b, p, false, x, blk.cin, blk.cout, o1, out);
-  b.half = false;
+  b.half = b.half_all;
   return y;
 }
 
@@ -414,7 +416,7 @@ static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& 
   const int TkS = round8(c.context_len);
   // b.share: x holds the first N / 2 images only and everything up to attn2.to_q runs on them; the cross-attention (per-image K / V),
   // attn2.to_out and the last GEMM run at full batch and read q2 / tok1 / x of image i - N / 2 for the second half
-  b.half = b.share;
+  b.half = b.share || b.half_all;
   T g = b.gn(x, p + ".norm", 1e-6f, 0);
   RowStats st0 = b.alloc_stats(x.rows(), C), st1 = b.alloc_stats(x.rows(), C), st2 = b.alloc_stats(x.rows(), C);
   Builder::CO pi; pi.stats = &st0;
@@ -433,7 +435,7 @@ static T build_attn(Builder& b, const std::string& ns, const Blk& blk, const T& 
   // attn2 (cross, K | V precomputed from the context)
   Builder::CO l2; l2.ln = &st1; l2.ln_s = b.named_v(t + ".attn2.q_ln.s");
   T q2 = b.gemm(tok1, b.named_w(t + ".attn2.q_ln.w"), C, C, b.named_v(t + ".attn2.q_ln.b"), l2);
-  b.half = false;
+  b.half = b.half_all;
   T o2 = b.alloc(x.n, x.h, x.w, C);
   // (+ the image-prompt segment: softmax(q K^T) V + ip_scale softmax(q K_ip^T) V_ip, still one launch)
   if (kv_ip) b.attn(o2, q2.p, C, kv.p, 2 * C, kv.p + C, 2 * C, N, H, Tq, c.context_len, TkS, TkS, d, b.share ? N / 2 : 0,
@@ -692,16 +694,21 @@ static void splice(const BuildCtx& c, Program& out, const Program& full, const S
 
 // ControlNet program of control net j (`cldm/cldm.py:284-305`).  Every net writes its 13 controls into the same e->ctrl: only
 // sdeo_controlnet_forward[_net] runs the zero convs here, one net per call.
-static void build_controlnet(BuildCtx& c, int j) {
+// half_prog: the same network on the first N / 2 images into e->cn_half[j], for a net in SDEO_CONTROL_COND: no zero convs (the fused
+// decoder applies them), every launch a batch prefix of its full-batch one, from the arena state the full program was built from and
+// therefore in the same tensors (checked).
+static void build_controlnet(BuildCtx& c, int j, bool half_prog = false) {
   Builder& b = c.b; Engine* e = b.e;
   Splice sp;
-  Program& p_cn = cn_prog(e, j, CP_CN);
+  Program& p_cn = half_prog ? e->cn_half[j] : cn_prog(e, j, CP_CN);
   b.prog = &p_cn;
+  b.half_all = b.half = half_prog;
   const int net = 1 + j;
   const std::string ns = net_ns(net);
   // The block outputs stay allocated (cn_h): sdeo_apply_model / sdeo_ddim_step skip the zero convs here and let the UNet decoder apply
   // them with the skip connection as the residual operand (P_UNET_DEC_FUSED); sdeo_controlnet_forward runs them here (13 controls out).
   auto zero_conv = [&](const T& x, const std::string& name, int cout, const T* out) {
+    if (half_prog) return;
     const size_t first = p_cn.size();
     Builder::CO zo; zo.out = out;
     b.conv(x, name, cout, 1, 1, 0, zo);
@@ -713,18 +720,37 @@ static void build_controlnet(BuildCtx& c, int j) {
       // input_blocks.0 conv, then h += guided_hint (residual epilogue)
       Builder::CO o; o.res = &c.hint_feat[j]; o.gn_next = true;
       hcur = b.conv(hcur, ns + e->cplan.in[0][0].name, e->cfg.model_channels, 3, 1, 0, o);
-    } else if (i == 1) {
+    } else if (i == 1 && !half_prog) {
       hcur = build_shared_prefix(c, ns, e->cplan.in[i], hcur, net, sp);
     } else {
       hcur = run_blocks(c, ns, e->cplan.in[i], hcur, false, net, nullptr);
     }
+    if (half_prog && hcur.p != e->cn_h[j][i].p && b.err.empty()) b.err = "the half-batch program of " + ns + " plans another arena";
     e->cn_h[j][i] = hcur;
     zero_conv(hcur, ns + "zero_convs." + std::to_string(i) + ".0", e->cplan.in_ch[i], &e->ctrl[i]);
   }
   T m = run_blocks(c, ns, e->cplan.mid, hcur, false, net, nullptr);
+  if (half_prog && m.p != e->cn_h[j][c.nctrl - 1].p && b.err.empty()) b.err = "the half-batch program of " + ns + " plans another arena";
   e->cn_h[j][c.nctrl - 1] = m;
   zero_conv(m, ns + "middle_block_out.0", e->cplan.in_ch.back(), &e->ctrl[c.nctrl - 1]);
-  splice(c, cn_prog(e, j, CP_CN_SH), p_cn, sp);
+  b.half_all = b.half = false;
+  if (!half_prog) splice(c, cn_prog(e, j, CP_CN_SH), p_cn, sp);
+}
+
+// control net j's programs: the full-batch one (with its shared-prefix variant) and, on a handle with sdeo_enable_control_modes and an
+// even N, the half-batch one, built from the same arena state
+static void build_controlnet_programs(BuildCtx& c, int j) {
+  Builder& b = c.b; Engine* e = b.e;
+  Arena& arena = *b.lane->arena;
+  const Arena before = arena;
+  build_controlnet(c, j);
+  if (!e->control_modes || c.N % 2) return;
+  Arena after = arena;
+  arena = before;
+  build_controlnet(c, j, true);
+  if (arena.end != after.end && b.err.empty()) b.err = "the half-batch program of " + net_ns(1 + j) + " plans another arena";
+  after.peak = std::max(after.peak, arena.peak);
+  arena = after;
 }
 
 // control export (fp16 NHWC -> fp32 NCHW boundary buffers) and import
@@ -760,6 +786,37 @@ static bool zero_convs_as_one(const BuildCtx& c) {
     if (e->cn_h[0][i].c % 64) return false;
   return true;
 }
+// The forms (Op::zc_form) net j's zero-conv launch exists in.  A plain handle: the one it always ran -- net 0 takes the skip as its
+// residual (ZC_FIRST), every later net works in place over the running sum.  A handle with sdeo_enable_control_modes: either role (an
+// OFF net in front makes a later net the first active one; net 0 can only be first), each on all rows and, for an even N, on the
+// first half of the batch (ZC_COND), where the rows of the other half are passed through from the residual.
+enum { ZC_COND = 1, ZC_FIRST = 2 };
+static std::vector<int> zero_conv_forms(const BuildCtx& c, int j) {
+  if (!c.b.e->control_modes) return {j == 0 ? ZC_FIRST : 0};
+  std::vector<int> f = j == 0 ? std::vector<int>{ZC_FIRST} : std::vector<int>{0, ZC_FIRST};
+  if (c.N % 2 == 0) for (size_t i = 0, n = f.size(); i < n; ++i) f.push_back(f[i] | ZC_COND);
+  return f;
+}
+// The per-conv form of net j's zero conv `leaf` of control ci: out = scale * zero_conv(cn_h[j][ci]) + res in each form of the net, res
+// being `skip` for the first active net and the running sum `out` behind it.  ZC_COND: the launch is the batch prefix of the full one
+// (Builder::half) and, where the residual is not the output itself, one pass-through launch copies the other half's skip rows.
+static void zero_conv_per_conv(BuildCtx& c, int j, int ci, const std::string& leaf, const T& out, const T& skip) {
+  Builder& b = c.b; Engine* e = b.e;
+  for (int form : zero_conv_forms(c, j)) {
+    const size_t first = b.prog->size();
+    const T& res = (form & ZC_FIRST) ? skip : out;
+    Builder::CO zo; zo.out = &out; zo.res = &res; zo.scale_host = &e->eff_scales[j][ci];
+    b.half = (form & ZC_COND) != 0;
+    b.conv(e->cn_h[j][ci], net_ns(1 + j) + leaf, out.c, 1, 1, 0, zo);
+    b.half = false;
+    if ((form & ZC_COND) && res.p != out.p) {
+      const int rows = out.rows() / 2, Cc = out.c, ldy = out.ld, lda = res.ld;
+      f16* yp = out.p + (size_t)rows * ldy; const f16* ap = res.p + (size_t)rows * lda;
+      b.push([=](hipStream_t s) { return add_scaled(yp, ldy, ap, lda, nullptr, 0, 1.0f, rows, Cc, s); }, "elementwise", 0, 4.0 * rows * Cc);
+    }
+    if (!b.dry) for (size_t k = first; k < b.prog->size(); ++k) { (*b.prog)[k].zc_net = (signed char)j; (*b.prog)[k].zc_form = (signed char)form; }
+  }
+}
 static void build_unet_decoder_multi(BuildCtx& c, std::vector<T> hs, T cat0, T view0);
 static void build_unet_decoder(BuildCtx& c, DecoderMode mode, std::vector<T> hs, T cat, T view) {
   Builder& b = c.b; Engine* e = b.e;
@@ -772,10 +829,7 @@ static void build_unet_decoder(BuildCtx& c, DecoderMode mode, std::vector<T> hs,
     b.push([=](hipStream_t s) { return add_scaled(yp, ld, yp, ld, cp, ldc, *sc, rows, Cc, s); });
   } else if (mode == D_FUSED) {
     // every extra net chains behind net 0's conv, in place over the running sum (res == out), like the middle block's own
-    for (int j = 0; j <= e->extra; ++j) {
-      Builder::CO zo; zo.out = &view; zo.res = &view; zo.scale_host = &e->eff_scales[j][ci];
-      b.conv(e->cn_h[j][ci], net_ns(1 + j) + "middle_block_out.0", view.c, 1, 1, 0, zo);
-    }
+    for (int j = 0; j <= e->extra; ++j) zero_conv_per_conv(c, j, ci, "middle_block_out.0", view, view);
   }
   --ci;
   for (size_t oi = 0; oi < e->uplan.out.size(); ++oi) {
@@ -785,10 +839,7 @@ static void build_unet_decoder(BuildCtx& c, DecoderMode mode, std::vector<T> hs,
     const int c_h = cat.c - skip.c;
     if (mode == D_FUSED) {
       const T half = cat.view(c_h, skip.c);
-      for (int j = 0; j <= e->extra; ++j) {
-        Builder::CO zo; zo.out = &half; zo.res = j ? &half : &skip; zo.scale_host = &e->eff_scales[j][ci];
-        b.conv(e->cn_h[j][ci], net_ns(1 + j) + "zero_convs." + std::to_string(ci) + ".0", skip.c, 1, 1, 0, zo);
-      }
+      for (int j = 0; j <= e->extra; ++j) zero_conv_per_conv(c, j, ci, "zero_convs." + std::to_string(ci) + ".0", half, skip);
     } else {
       f16* yp = cat.p + c_h; const int ld = cat.ld, rows = cat.rows(), Cc = skip.c;
       const f16* ap = skip.p; const int lda = skip.ld;
@@ -833,7 +884,8 @@ static void build_unet_decoder_multi(BuildCtx& c, std::vector<T> hs, T cat0, T v
   // out = scale * zero_conv(cn_h[ci]) + skip into the second half of its stage's buffer (the middle block's: in place over view0)
   // Net 0's 13 problems are one launch; each extra net adds one more launch of the same tile whose 13 problems work in place on what
   // the launch before left (res == out, the form the middle block's problem has in every launch) under that net's scales.
-  std::vector<ConvGemm> zc[kMaxControlNets];
+  // (zc[j]: net j's problems with the running sum as the residual; zc_first[j]: with the skips, the form of the first active net)
+  std::vector<ConvGemm> zc[kMaxControlNets], zc_first[kMaxControlNets];
   std::vector<const float*> zs[kMaxControlNets];
   auto zero_conv_net = [&](int j, int ci, const std::string& name, const T& out, const T& res) {
     const T& x = e->cn_h[j][ci];
@@ -844,11 +896,13 @@ static void build_unet_decoder_multi(BuildCtx& c, std::vector<T> hs, T cat0, T v
     p.B = x.n; p.Hi = p.Ho = x.h; p.Wi = p.Wo = x.w; p.Cin = x.c;
     p.M = x.rows(); p.N = out.c; p.K = x.c;
     p.ldx = x.ld; p.ldw = p.K; p.ldy = out.ld; p.ldres = res.ld;
+    zc_first[j].push_back(p);
+    p.res = out.p; p.ldres = out.ld;
     zc[j].push_back(p);
     zs[j].push_back(&e->eff_scales[j][ci]);
   };
   auto zero_conv = [&](int ci, const std::string& leaf, const T& out, const T& res) {
-    for (int j = 0; j <= e->extra; ++j) zero_conv_net(j, ci, net_ns(1 + j) + leaf, out, j ? out : res);
+    for (int j = 0; j <= e->extra; ++j) zero_conv_net(j, ci, net_ns(1 + j) + leaf, out, res);
   };
   int ci = c.nctrl - 1;
   zero_conv(ci--, "middle_block_out.0", view0, view0);
@@ -857,7 +911,15 @@ static void build_unet_decoder_multi(BuildCtx& c, std::vector<T> hs, T cat0, T v
     zero_conv(ci, "zero_convs." + std::to_string(ci) + ".0", cats[oi].view(cats[oi].c - skip.c, skip.c), skip);
   }
   if (!b.dry)
-    for (int j = 0; j <= e->extra; ++j) b.prog->push_back(conv_gemm_multi_op(zc[j], kZeroConvTile, zs[j]));
+    for (int j = 0; j <= e->extra; ++j)
+      for (int form : zero_conv_forms(c, j)) {
+        const std::vector<ConvGemm>& ps = (form & ZC_FIRST) ? zc_first[j] : zc[j];
+        std::vector<int> live;               // ZC_COND: the rows of the first half of the batch
+        if (form & ZC_COND) for (const ConvGemm& p : ps) live.push_back(p.M / 2);
+        Op op = conv_gemm_multi_op(ps, kZeroConvTile, zs[j], live);
+        op.zc_net = (signed char)j; op.zc_form = (signed char)form;
+        b.prog->push_back(std::move(op));
+      }
   for (T& skip : hs) b.release(skip);
   for (size_t oi = 0; oi < stages; ++oi) {
     const std::vector<Blk>& blocks = e->uplan.out[oi];
@@ -1005,7 +1067,7 @@ int sdeo::build_all(Engine* e, bool dry, size_t* max_splitk, size_t* max_gn, siz
   if (e->ip_tokens) build_context_ip(c);
   for (int j = 0; j <= e->extra; ++j) build_hint(c, j);
   // the extra nets run on the side stream behind net 0; every net's block outputs stay allocated there until the decoder has run
-  c.b.on_lane(&e->lanes[L_SIDE], [&] { for (int j = 0; j <= e->extra; ++j) build_controlnet(c, j); });
+  c.b.on_lane(&e->lanes[L_SIDE], [&] { for (int j = 0; j <= e->extra; ++j) build_controlnet_programs(c, j); });
   build_control_io(c);
   for (int variant = 0; variant < 2; ++variant) build_unet(c, variant == 0);
   // the three programs that hold a decoder, as built, are the FreeU programs; without their flagged launches, the ones a handle runs

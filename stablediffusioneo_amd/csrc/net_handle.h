@@ -143,6 +143,13 @@ struct sdeo_handle_s {
   int extra = 0;
   Program xprog[kMaxControlNets - 1][CP_COUNT];
   float extra_scales[kMaxControlNets - 1][kMaxControls];
+  // control modes (sdeo_enable_control_modes): per control net SDEO_CONTROL_BOTH / _COND / _OFF, host state read when a call launches
+  // (sdeo_set_control_mode; sdeo_configure resets them to BOTH).  cn_half[j]: net j's ControlNet program on the first N / 2 images
+  // (build_controlnet: every launch a batch prefix of the full-batch one, in the same tensors; empty when N is odd).  The fused decoders
+  // of such a handle hold every form of each net's zero-conv launch (Op::zc_form); run_decoder picks.
+  bool control_modes = false;
+  int cmode[kMaxControlNets] = {0};
+  Program cn_half[kMaxControlNets];
   // The cache contract (include/sdeo.h, "State a handle keeps between calls"): host-side record of what the caches hold, checked before
   // the first device call of every entry point that reads one on the caller's word.  A captured call is checked at capture.
   CacheRecord cache;

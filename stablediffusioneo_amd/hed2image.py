@@ -26,13 +26,14 @@ def _default_hed(weights):
 class hackathon(canny2image.hackathon):
 
     def initialize(self, weights="synthetic:0", hed_weights="synthetic:0", apply_hed=None, text_encoder=None, config="sd15",
-                   sampler="ddim", loras=(), ip_adapter=None, image_encoder=None, freeu=None):
+                   sampler="ddim", loras=(), ip_adapter=None, image_encoder=None, freeu=None, control_schedule=None):
         """weights / text_encoder / config / sampler / ip_adapter / image_encoder: as canny2image.hackathon.initialize (a soft-edge ControlNet checkpoint has the same keys).
         hed_weights: the HED network's (ControlNetHED.pth path, state dict or "synthetic:<seed>"); apply_hed: any callable
-        (HxWx3 uint8) -> HxW uint8 instead of the HIP HEDdetector.  freeu: as canny2image's."""
+        (HxWx3 uint8) -> HxW uint8 instead of the HIP HEDdetector.  freeu, control_schedule: as canny2image's."""
         freeu = self._freeu_arg(freeu)
         self.apply_hed = apply_hed or _default_hed(hed_weights)
-        return self._init_model(weights, config, text_encoder, sampler=sampler, loras=loras, ip_adapter=ip_adapter, image_encoder=image_encoder, freeu=freeu)
+        return self._init_model(weights, config, text_encoder, sampler=sampler, loras=loras, ip_adapter=ip_adapter, image_encoder=image_encoder, freeu=freeu,
+                                control_schedule=control_schedule)
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, detect_resolution, ddim_steps, guess_mode,
                 strength, scale, seed, eta, x_T=None, ip_image_embeds=None, ip_tokens=None, ip_scale=1.0, ip_image=None):

@@ -25,12 +25,14 @@ DEVICE_CONTROLS = ("canny", "hed", "scribble", "fake_scribble")
 class hackathon(canny2image.hackathon):
 
     def initialize(self, weights="synthetic:0", controls=("canny", "hed"), control_weights=(None, "synthetic:1"), hed_weights="synthetic:0",
-                   text_encoder=None, config="sd15", sampler="ddim", loras=(), ip_adapter=None, image_encoder=None, freeu=None):
+                   text_encoder=None, config="sd15", sampler="ddim", loras=(), ip_adapter=None, image_encoder=None, freeu=None,
+                   control_schedule=None):
         """controls: one entry per control network, "canny", "hed", "scribble", "fake_scribble" (the device hint producers of the
         single-net pipelines) or a callable (HxWx3 uint8) -> HxW uint8.  control_weights: one entry per network; entry 0 must be
         None (net 0 comes with `weights`), the others are a checkpoint path, a state dict or "synthetic:<seed>".
         weights / text_encoder / config / sampler / ip_adapter / image_encoder: as canny2image.hackathon.initialize; hed_weights: as hed2image's.
-        freeu: as canny2image's."""
+        freeu: as canny2image's.  control_schedule: as canny2image's; a list gives every control network a window and an `on` of its own
+        (one ControlSchedule per entry of `controls`)."""
         freeu = self._freeu_arg(freeu)
         controls = tuple(controls)
         control_weights = tuple(control_weights)
@@ -52,7 +54,7 @@ class hackathon(canny2image.hackathon):
             from .hed2image import _default_hed
             self.apply_hed = _default_hed(hed_weights)
         return self._init_model(weights, config, text_encoder, sampler=sampler, extra_control=control_weights[1:], loras=loras, ip_adapter=ip_adapter,
-                                image_encoder=image_encoder, freeu=freeu)
+                                image_encoder=image_encoder, freeu=freeu, control_schedule=control_schedule)
 
     def _hint(self, kind, img, low_threshold, high_threshold):
         """(3, H, W) fp32 hint in [0, 1] on the device, from the resized HxWx3 uint8 image"""

@@ -26,6 +26,10 @@ def TIMESTEP_ROW(i: int) -> int:
 MAX_TABLE_STEPS = _lib.header_constant("SDEO_MAX_TABLE_STEPS")
 
 
+# control modes of `SdeoRuntime.set_control_mode` (SDEO_CONTROL_* of include/sdeo.h)
+CONTROL_BOTH, CONTROL_COND, CONTROL_OFF = (_lib.header_constant("SDEO_CONTROL_" + n) for n in ("BOTH", "COND", "OFF"))
+
+
 # cap of the four FreeU values (SDEO_FREEU_MAX of include/sdeo.h)
 FREEU_MAX = _lib.header_constant("SDEO_FREEU_MAX")
 
@@ -276,14 +280,16 @@ class SdeoRuntime(_HandleRuntime):
 
     def __init__(self, ucfg: S.UNetConfig = S.UNET_SD15, vcfg: S.VAEConfig = S.VAE_SD15, device: Optional[torch.device] = None,
                  weight_bits: int = 16, act_bits: int = 16, mx_min_rows: int = 0, vae_encoder: bool = False,
-                 extra_controlnets: int = 0, ip_adapter_tokens: int = 0):
+                 extra_controlnets: int = 0, ip_adapter_tokens: int = 0, control_modes: bool = False):
         """weight_bits = 8: the UNet / ControlNet matrices are packed to fp8 (OCP e4m3fn, per-output-channel power-of-two scale) when
         the weights are finalised (BASELINE configs[4]; the reference's precision switch is `onnx2trt_static_plugin.py:40-42`).
         vae_encoder = True: the handle also expects `first_stage_model.encoder.*` / `quant_conv.*` and runs `vae_encode`.
         extra_controlnets = k (1..3): the handle also expects `control_model_<j>.*` for j = 1..k and every forward sums the residuals
         of all 1 + k control networks (`set_control_hint`, `set_control_scales`).
         ip_adapter_tokens = T (1..64): the handle also expects `...attn2.to_k_ip.weight` / `to_v_ip.weight` of every UNet cross-attention
-        (spec.param_spec_ip_adapter) and every forward adds the image term of `set_ip_tokens`, weighted by `set_ip_scale`."""
+        (spec.param_spec_ip_adapter) and every forward adds the image term of `set_ip_tokens`, weighted by `set_ip_scale`.
+        control_modes = True: `sdeo_enable_control_modes` -- `set_control_mode` may then run each control network on both halves of the
+        CFG pair, on the conditional half only, or not at all."""
         super().__init__(device)
         self.ucfg, self.vcfg = ucfg, vcfg
         self._cfg = make_config(ucfg, vcfg)
@@ -313,6 +319,10 @@ class SdeoRuntime(_HandleRuntime):
         self.act_bits = int(act_bits)
         if self.act_bits != 16:
             check(self.lib.sdeo_set_activation_precision(self.handle, self.act_bits, int(mx_min_rows)), "set_activation_precision")
+        self.control_modes = bool(control_modes)
+        if self.control_modes:      # after the precisions: the library refuses the feature on an fp8 handle by name
+            check(self.lib.sdeo_enable_control_modes(self.handle), "enable_control_modes")
+        self._modes = [CONTROL_BOTH] * (1 + self.extra_controlnets)    # as the library holds them (sdeo_configure resets them to BOTH)
         self.n = self.h = self.w = 0
         self.n_controls = 13
         # bumped by every sdeo_configure: the library frees and re-plans its arenas / boundary buffers there, so a hipGraph
@@ -380,6 +390,8 @@ class SdeoRuntime(_HandleRuntime):
             self.n, self.h, self.w = n, h, w
             self._extra_scales = [None] * self.extra_controlnets       # the library reset them to 1
             self.ip_scale = 1.0                                        # ... and the weight of the image term
+            modes, self._modes = self._modes, [CONTROL_BOTH] * (1 + self.extra_controlnets)   # ... and every control mode to BOTH:
+            self.set_control_modes(modes)                              # the runtime keeps them across `configure`, like FreeU
             if self._freeu is not None:                                # ... and turned FreeU off: hand it over again
                 self._call("set_freeu", *(C.c_float(v) for v in self._freeu[:4]), self._freeu[4])
         return self
@@ -404,6 +416,30 @@ class SdeoRuntime(_HandleRuntime):
     def freeu_key(self):
         """what a captured graph bakes in of FreeU: None when off, else (b1, b2, s1, s2, version)"""
         return self._freeu
+
+    # ---------------------------------------------------------------- control modes
+    def set_control_mode(self, net: int, mode: int):
+        """`sdeo_set_control_mode`: control network `net` (0..extra_controlnets) on every image (CONTROL_BOTH), on the first n / 2 --
+        the conditional half of [cond; uncond] -- only (CONTROL_COND), or not at all (CONTROL_OFF), in the following `apply_model` calls
+        and fused steps.  Read at launch (a captured step bakes it in: `modes_key` is part of the key of `apply_model_graphed` and of the samplers' captured loops), kept until changed;
+        unlike the library, the runtime keeps them across `configure`.  Needs SdeoRuntime(..., control_modes=True)."""
+        check(self.lib.sdeo_set_control_mode(self.handle, int(net), int(mode)), "set_control_mode")
+        self._modes[int(net)] = int(mode)
+        return self
+
+    def set_control_modes(self, modes):
+        """one mode per control network (None: all BOTH); only the nets whose mode changes are told"""
+        modes = [CONTROL_BOTH] * len(self._modes) if modes is None else [int(m) for m in modes]
+        if len(modes) != len(self._modes):
+            raise ValueError(f"set_control_modes: {len(modes)} modes for {len(self._modes)} control networks")
+        for net, m in enumerate(modes):
+            if m != self._modes[net]:
+                self.set_control_mode(net, m)
+        return self
+
+    def modes_key(self):
+        """the control modes as the library holds them: part of every key of a captured graph"""
+        return tuple(self._modes)
 
     # ---------------------------------------------------------------- image-prompt adapter
     def set_ip_tokens(self, tokens):
@@ -525,7 +561,7 @@ class SdeoRuntime(_HandleRuntime):
         side stream, UNet encoder on the main one), so the GPU sees the whole fork/join at once.  Inputs are copied into
         fixed device buffers; the returned eps tensor is owned by the runtime (valid until the next call)."""
         key = (self.generation, self.n, self.h, self.w, tuple(float(s) for s in (scales or [])), bool(only_mid_control),
-               self.extra_scales_key(), self.ip_key(), self.freeu_key())
+               self.extra_scales_key(), self.ip_key(), self.freeu_key(), self.modes_key())
         if getattr(self, "_graph_key", None) != key:
             u = self.ucfg
             self._gx = torch.zeros((self.n, u.in_channels, self.h, self.w), dtype=torch.float32, device=self.device)

@@ -20,12 +20,12 @@ from .annotator.util import HWC3, resize_image
 class hackathon(canny2image.hackathon):
 
     def initialize(self, weights="synthetic:0", config="sd15", text_encoder=None, sampler="ddim", loras=(), ip_adapter=None, image_encoder=None,
-                   freeu=None):
+                   freeu=None, control_schedule=None):
         """weights / config / text_encoder / sampler / ip_adapter / image_encoder: as canny2image.hackathon.initialize (a scribble ControlNet checkpoint has
         the same keys).  `process` keeps the upstream signature: with an adapter the image prompt of the following requests is given
-        through `set_image_prompt(ip_image_embeds=, ip_tokens=, ip_scale=, ip_image=)`."""
+        through `set_image_prompt(ip_image_embeds=, ip_tokens=, ip_scale=, ip_image=)`.  control_schedule: as canny2image's."""
         return self._init_model(weights, config, text_encoder, sampler=sampler, loras=loras, ip_adapter=ip_adapter, image_encoder=image_encoder,
-                                freeu=self._freeu_arg(freeu))
+                                freeu=self._freeu_arg(freeu), control_schedule=control_schedule)
 
     def process(self, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, ddim_steps, guess_mode, strength, scale, seed,
                 eta, x_T=None):
